@@ -13,7 +13,14 @@ what INTEGRATION.md tells a single-process caller like Qdrant to hold) and print
 
 One "step" = one query against the whole store: encode_query -> score_all over the rank's shard ->
 the exchange of per-shard results.  Inputs are resident in HBM before the timed region.  Rank 0
-prints ONE JSON line (metric, value, roofline, cpu_baseline, ...).
+prints ONE JSON line (metric, value, unit, ms_per_step, ...).
+
+A plain run does only what that line's headline needs: set-up, warm-up, the --steps timed steps, the
+line.  `--full` adds everything else the benchmark measures or checks: HIP-event kernel times inside
+the timed steps, the `roofline` block (with the streaming-read probe and the committed PMC traffic),
+and the `cpu_baseline` with its bit-for-bit parity check.  `--dump-outputs DIR` writes what the last
+timed step computed (what a caller of that path receives) as DIR/<name>.npy, so that two builds can be
+compared output for output on the same seeded inputs.
 
 Workload (BASELINE.json configs[1]): f32 i.i.d. uniform [0,1) vectors (demos/benches/encode.rs:17-22),
 fixed seed, scalar-u8 encoded on the GPU by the library itself; queries from the same distribution.
@@ -86,12 +93,12 @@ def parse_args():
                     help="1: encode_query of step i+1 runs on a side stream while the scan of step i runs (two query "
                          "objects); 0 / -1 (default): strictly in line, which measured faster")
     ap.add_argument("--time-every", type=int, default=0,
-                    help="HIP-event-time the scan kernel every this many steps (0 = auto: every step at N=1, every "
+                    help="--full: HIP-event-time the scan kernel every this many steps (0 = auto: every step at N=1, every "
                          "8th at N>1: an event pair costs ~10 us of launch gap, 7 %% of a 1.25M-row shard scan)")
     ap.add_argument("--k", type=int, default=30)
     ap.add_argument("--cpu-sample-rows", type=int, default=0,
-                    help="rows of the store the CPU baseline scans (0 = all of them, capped at 10M)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: rows of the store the CPU baseline scans (0 = all of them, capped at 10M)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--queries", type=int, default=16)
     ap.add_argument("--batch-queries", type=int, default=0,
                     help="opt-in second workload (BASELINE config 4 shape): per step, top-k of this many queries "
@@ -103,7 +110,16 @@ def parse_args():
                     help="rehearsal only: put every rank on this one device (needs --backend gloo)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed even at world size 1 (exercises the RCCL code path on one GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: kernel event times, the roofline "
+                         "block (streaming-read probe, PMC traffic) and the CPU baseline with its parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 "
+                         "scores, float64 row ids; at most 64 MB in all, a fixed seeded sample of rows beyond that)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def host_cpu_model() -> str:
@@ -254,6 +270,35 @@ def pmc_traffic(key, n, read_bytes_per_launch_unit):
     return None, None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write {name: array (torch tensor or numpy)} as out_dir/<name>.npy, floating point as float32 and
+    row ids (u32, 0xFFFFFFFF = no row) as float64, which holds every id exactly.  When the arrays exceed `limit` bytes in
+    all, each keeps the same seeded random sample of its rows, in ascending order, and <name>_rows.npy (float64) lists
+    which rows they are."""
+    import numpy as np
+
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if a.dtype == np.int32:  # ids handed back as i32 bit patterns
+            a = a.view(np.uint32)
+        host[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    budget = limit - 2 * 4096 * len(host)  # less room for the .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if total > budget and a.ndim > 0 and a.shape[0] > 1:
+            row_bytes = a.nbytes // a.shape[0] + 8  # the row and its entry in <name>_rows.npy
+            keep = max(1, min(a.shape[0], int(budget * (a.nbytes / total)) // row_bytes))
+            rows = np.sort(np.random.default_rng(12345).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def free_port() -> int:
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
         so.bind(("127.0.0.1", 0))
@@ -365,30 +410,14 @@ def run_single_process(args):
     for d in set(devices):
         torch.cuda.synchronize(d)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"scores": out[:n_total]} if exchange == "scores" else {"ids": ids, "scores": sc})
 
-    # the dominant kernel, timed on shard 0's own handle with HIP events on the stream it is launched on
     view, _base = sh.shard(0)
     n0 = view.count
-    with torch.cuda.device(devices[0]):
-        q0 = view.encode_query(queries[0])
-        o0 = torch.empty(max(n0, 1), dtype=torch.float32, device=dev)
-        for _ in range(10):
-            view.score_all(q0, out=o0)
-        evs = []
-        for _ in range(20):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            view.score_all(q0, out=o0)
-            b.record()
-            evs.append((a, b))
-        torch.cuda.synchronize()
-    kern_all = [a.elapsed_time(b) for a, b in evs]
-    kern_ms = float(np.mean(kern_all))
-    bytes_per_row = view.scan_bytes_per_row()
-    achieved = bytes_per_row * n0 / (kern_ms * 1e-3) / 1e9
     names = [torch.cuda.get_device_name(d) for d in devices]
     headline = (n_total == 10_000_000 and dim == 768 and args.distance == "dot")
-    print(json.dumps({
+    line = {
         "metric": "scored vectors/sec, 10Mx768 u8 dot" if headline else f"scored vectors/sec, {n_total}x{dim} u8 {args.distance}",
         "value": n_total * args.steps / elapsed, "unit": "vectors/s", "n_gpus": G, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
@@ -402,13 +431,33 @@ def run_single_process(args):
                    "rows_per_gpu": n0, "dim": dim, "distance": args.distance, "exchange": exchange,
                    "exchange_reason": why, "total_rows": n_total, "queries": args.queries,
                    "shard_lanes": int(os.environ.get("QAMD_SHARD_LANES", "3"))},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBPS, "traffic": None, "kernel": "u8_scan_kernel", "kernel_ms": kern_ms,
-                     "kernel_ms_min": float(np.min(kern_all)), "kernel_ms_median": float(np.median(kern_all)),
-                     "kernel_ms_mean": kern_ms, "algorithmic_bytes_per_row": bytes_per_row, "rows_per_launch": n0,
-                     "note": "shard 0's scan timed on its own handle after the timed region (the sharded calls launch "
-                             "on the library's worker streams)"},
-    }), flush=True)
+    }
+    if args.full:
+        # the dominant kernel, timed on shard 0's own handle with HIP events on the stream it is launched on
+        with torch.cuda.device(devices[0]):
+            q0 = view.encode_query(queries[0])
+            o0 = torch.empty(max(n0, 1), dtype=torch.float32, device=dev)
+            for _ in range(10):
+                view.score_all(q0, out=o0)
+            evs = []
+            for _ in range(20):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                view.score_all(q0, out=o0)
+                b.record()
+                evs.append((a, b))
+            torch.cuda.synchronize()
+        kern_all = [a.elapsed_time(b) for a, b in evs]
+        kern_ms = float(np.mean(kern_all))
+        bytes_per_row = view.scan_bytes_per_row()
+        achieved = bytes_per_row * n0 / (kern_ms * 1e-3) / 1e9
+        line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                            "frac": achieved / HBM_PEAK_GBPS, "traffic": None, "kernel": "u8_scan_kernel", "kernel_ms": kern_ms,
+                            "kernel_ms_min": float(np.min(kern_all)), "kernel_ms_median": float(np.median(kern_all)),
+                            "kernel_ms_mean": kern_ms, "algorithmic_bytes_per_row": bytes_per_row, "rows_per_launch": n0,
+                            "note": "shard 0's scan timed on its own handle after the timed region (the sharded calls "
+                                    "launch on the library's worker streams)"}
+    print(json.dumps(line), flush=True)
 
 
 def main():
@@ -423,7 +472,7 @@ def main():
 
     import quantization_amd as qa
     from quantization_amd import _lib
-    from quantization_amd.sharded import ScoreGather, ShardedTopK, max_shard_rows, shard_range
+    from quantization_amd.sharded import ScoreGather, ShardedTopK, assemble_global_scores, max_shard_rows, shard_range
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -575,9 +624,11 @@ def main():
             xchg.bases = [args.rows * r for r in range(world)]
         ids, sc = xchg.buffers()
 
+        last = [None]  # the (ids, scores) [Q, k] the last step's exchange handed back
+
         def bstep(_i):
             enc.topk_batch(batch, k, largest=True, out_ids=ids, out_scores=sc)
-            return xchg.exchange(largest=True)
+            last[0] = xchg.exchange(largest=True)
 
         # untimed set-up passes for about a quarter second of GPU work (the clock ramps with busy time, see the scan path below)
         # (every rank runs the SAME number of passes: a step holds a collective)
@@ -597,65 +648,10 @@ def main():
             bstep(i)
         elapsed = timed_region(bstep, args.steps)
         if rank == 0:
-            if args.quantizer == "pq":
-                m = bytes_per_row
-                kernel_name, launches = enc.scan_kernel()
-                cpu = None
-                if world == 1 and not args.no_cpu_baseline:
-                    try:
-                        q0 = enc.encode_query(bq[0])
-                        full = enc.score_all(q0, out=torch.empty(n, dtype=torch.float32, device=dev)).cpu().numpy()
-                        S = min(n, args.cpu_sample_rows or n, 10_000_000)
-                        cpu = cpu_baseline("pq", enc, bq[0].cpu().numpy(), full, 0 if args.distance == "dot" else 2, S, args.pq_chunk)
-                        cpu["unit"] = "pairs/s"
-                        cpu["sample"] = (f"ONE query of the batch (the CPU path scores a batch as {Q} such passes: pairs/s is the same "
-                                         f"figure); ") + cpu["sample"]
-                        enc.topk_batch(batch, k, largest=True, out_ids=ids, out_scores=sc)
-                        got_ids = ids[:k].cpu().numpy().view(np.uint32)
-                        got_sc = sc[:k].cpu().numpy()
-                        order = np.lexsort((np.arange(n), -full))[:k]
-                        cpu["batch_topk_of_that_query_matches"] = bool(np.array_equal(got_sc.view(np.uint32), full[order].view(np.uint32))
-                                                                       and np.array_equal(np.sort(full[got_ids]), np.sort(full[order])))
-                    except Exception as e:
-                        cpu = {"value": None, "unit": "pairs/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
-                step_s = elapsed / args.steps
-                gbps = float(Q) * n * m / step_s / 1e9  # every query streams the store's code bytes once
-                one, source = pmc_traffic(f"pq_scan_m{m}", n, n * m)  # the single scan's profile: the same kernel, Q times
-                print(json.dumps({
-                    "metric": f"(query, vector) pairs scored/sec, {Q} queries x {total_rows}x{dim} pq dot, top-{k} each",
-                    "value": float(Q) * total_rows * args.steps / elapsed, "unit": "pairs/s", "n_gpus": world,
-                    "steps": args.steps, "warmup": max(1, args.warmup), "ms_per_step": step_s * 1e3,
-                    "higher_is_better": True, "scaling": scaling_field, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-                    "config": {"workload": f"{Q} queries x {total_rows} x {dim} PQ rows (chunk {args.pq_chunk}: {m} code bytes; {n} rows on "
-                                           f"rank 0), per step: topk_batch over the shard (a table fills the LDS: the per-query "
-                                           f"pipelines back to back) + all-gather of world*Q*k pairs + per-query merge on the GPU",
-                               "rows_per_gpu": n, "dim": dim, "queries": Q, "k": k, "total_rows": total_rows, **dist_info},
-                    "roofline": {"bound": "hbm", "achieved": gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": gbps / HBM_PEAK_GBPS,
-                                 "traffic": None if one is None else one * Q,
-                                 "traffic_source": None if one is None else f"{Q} x the single scan's: {source}",
-                                 "kernel": kernel_name, "launches_per_query": launches, "ms_per_query": step_s * 1e3 / Q,
-                                 "algorithmic_read_bytes_per_step": Q * n * m,
-                                 "note": "m code bytes per (query, row) pair from HBM: no two queries' tables fit the LDS together, so "
-                                         "every query streams the store; achieved is over the WHOLE step (tables, sample passes, "
-                                         "filter scans, merges, exchange); traffic = the committed single-scan PMC profile x queries"},
-                    "cpu_baseline": cpu,
-                }), flush=True)
-                if use_dist:
-                    dist.barrier()
-                    dist.destroy_process_group()
-                return
-            is_bin = args.quantizer == "binary"
-            ad = dim if is_bin else enc.metadata["actual_dim"]  # binary: one 0/1 operand byte per bit on the matrix cores
-            ops = 2.0 * Q * n * ad  # per GPU and step
-            # binary batches of 3 and of 5+ queries on rows of 4 / 6 / 8 / 12 128-bit words take the fp4 matrix-core kernels (csrc/bin.hip:
-            # bin_gemm_rs4_kernel while the batch's nibble image fits in LDS, bin_gemm_qs4_kernel beyond)
-            bin_fp4 = is_bin and (Q == 3 or Q >= 5) and (ad + 127) // 128 in (4, 6, 8, 12)
-            mfma_peak = MFMA_FP4_PEAK_TOPS if bin_fp4 else MFMA_INT8_PEAK_TOPS
-            per_gpu_tops = ops * args.steps / elapsed / 1e12
-            row_bytes = nb if is_bin else bytes_per_row
-            traffic, source = pmc_traffic(f"{'bin' if is_bin else 'u8'}_batch{Q}_{dim}", n, n * row_bytes)
+            if args.dump_outputs:
+                write_outputs(args.dump_outputs, {"ids": last[0][0], "scores": last[0][1]})
             cpu = None
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 # the reference has no batched form: a batch of Q queries is Q passes of its caller loop, timed here for
                 # one query of the batch over a bounded sample of the store's own rows; the batch's top-k for that query
                 # is checked against the top-k of the CPU's scores when the sample is the whole store
@@ -676,26 +672,66 @@ def main():
                                                                    and np.array_equal(np.sort(full[got_ids]), np.sort(full[order])))
                 except Exception as e:
                     cpu = {"value": None, "unit": "pairs/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
-            print(json.dumps({
-                "metric": f"(query, vector) pairs scored/sec, {Q} queries x {total_rows}x{dim} {args.quantizer} dot, top-{k} each",
-                "value": float(Q) * total_rows * args.steps / elapsed, "unit": "pairs/s", "n_gpus": world,
-                "steps": args.steps, "warmup": max(1, args.warmup), "ms_per_step": elapsed / args.steps * 1e3,
-                "higher_is_better": True, "scaling": scaling_field, "vs_baseline": None,
-                "dtype": ("1-bit x 1-bit -> exact count (bits as E2M1 0/1 nibbles, MFMA fp4 -> f32)" if bin_fp4 else
-                          "1-bit x 1-bit -> i32 (bits expanded to 0/1 bytes, MFMA int8)") if is_bin else "u8 x u8 -> i32 (MFMA int8)",
-                "data": "synthetic",
-                "config": {"workload": f"{Q} queries x {total_rows} x {dim} {'binary' if is_bin else 'scalar-u8'} rows ({n} on rank 0), per step: "
-                                       f"topk_batch over the shard + all-gather of world*Q*k pairs + per-query merge "
-                                       f"on the GPU",
-                           "rows_per_gpu": n, "dim": dim, "queries": Q, "k": k, "total_rows": total_rows, **dist_info},
-                "roofline": batch_roofline(per_gpu_tops, mfma_peak, ops, n * row_bytes, elapsed / args.steps) | {
-                             "traffic": traffic, "traffic_source": source,
-                             "algorithmic_read_bytes_per_step": n * row_bytes,
-                             "note": ("fp4" if bin_fp4 else "int8") + " op/s per GPU over the whole step (sample pass, filter GEMM, scatter, "
-                                     "sort, exchange); algorithmic ops = 2 * actual_dim per (query, row) pair; traffic = HBM bytes "
-                                     "of the step's dominant (filter) kernel: the store's rows leave HBM once per batch"},
-                "cpu_baseline": cpu,
-            }), flush=True)
+            if args.quantizer == "pq":
+                m = bytes_per_row
+                step_s = elapsed / args.steps
+                line = {
+                    "metric": f"(query, vector) pairs scored/sec, {Q} queries x {total_rows}x{dim} pq dot, top-{k} each",
+                    "value": float(Q) * total_rows * args.steps / elapsed, "unit": "pairs/s", "n_gpus": world,
+                    "steps": args.steps, "warmup": max(1, args.warmup), "ms_per_step": step_s * 1e3,
+                    "higher_is_better": True, "scaling": scaling_field, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                    "config": {"workload": f"{Q} queries x {total_rows} x {dim} PQ rows (chunk {args.pq_chunk}: {m} code bytes; {n} rows on "
+                                           f"rank 0), per step: topk_batch over the shard (a table fills the LDS: the per-query "
+                                           f"pipelines back to back) + all-gather of world*Q*k pairs + per-query merge on the GPU",
+                               "rows_per_gpu": n, "dim": dim, "queries": Q, "k": k, "total_rows": total_rows, **dist_info},
+                }
+                if args.full:
+                    kernel_name, launches = enc.scan_kernel()
+                    gbps = float(Q) * n * m / step_s / 1e9  # every query streams the store's code bytes once
+                    one, source = pmc_traffic(f"pq_scan_m{m}", n, n * m)  # the single scan's profile: the same kernel, Q times
+                    line["roofline"] = {
+                        "bound": "hbm", "achieved": gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": gbps / HBM_PEAK_GBPS,
+                        "traffic": None if one is None else one * Q,
+                        "traffic_source": None if one is None else f"{Q} x the single scan's: {source}",
+                        "kernel": kernel_name, "launches_per_query": launches, "ms_per_query": step_s * 1e3 / Q,
+                        "algorithmic_read_bytes_per_step": Q * n * m,
+                        "note": "m code bytes per (query, row) pair from HBM: no two queries' tables fit the LDS together, so "
+                                "every query streams the store; achieved is over the WHOLE step (tables, sample passes, "
+                                "filter scans, merges, exchange); traffic = the committed single-scan PMC profile x queries"}
+            else:
+                is_bin = args.quantizer == "binary"
+                ad = dim if is_bin else enc.metadata["actual_dim"]  # binary: one 0/1 operand byte per bit on the matrix cores
+                # binary batches of 3 and of 5+ queries on rows of 4 / 6 / 8 / 12 128-bit words take the fp4 matrix-core kernels (csrc/bin.hip:
+                # bin_gemm_rs4_kernel while the batch's nibble image fits in LDS, bin_gemm_qs4_kernel beyond)
+                bin_fp4 = is_bin and (Q == 3 or Q >= 5) and (ad + 127) // 128 in (4, 6, 8, 12)
+                line = {
+                    "metric": f"(query, vector) pairs scored/sec, {Q} queries x {total_rows}x{dim} {args.quantizer} dot, top-{k} each",
+                    "value": float(Q) * total_rows * args.steps / elapsed, "unit": "pairs/s", "n_gpus": world,
+                    "steps": args.steps, "warmup": max(1, args.warmup), "ms_per_step": elapsed / args.steps * 1e3,
+                    "higher_is_better": True, "scaling": scaling_field, "vs_baseline": None,
+                    "dtype": ("1-bit x 1-bit -> exact count (bits as E2M1 0/1 nibbles, MFMA fp4 -> f32)" if bin_fp4 else
+                              "1-bit x 1-bit -> i32 (bits expanded to 0/1 bytes, MFMA int8)") if is_bin else "u8 x u8 -> i32 (MFMA int8)",
+                    "data": "synthetic",
+                    "config": {"workload": f"{Q} queries x {total_rows} x {dim} {'binary' if is_bin else 'scalar-u8'} rows ({n} on rank 0), per step: "
+                                           f"topk_batch over the shard + all-gather of world*Q*k pairs + per-query merge "
+                                           f"on the GPU",
+                               "rows_per_gpu": n, "dim": dim, "queries": Q, "k": k, "total_rows": total_rows, **dist_info},
+                }
+                if args.full:
+                    ops = 2.0 * Q * n * ad  # per GPU and step
+                    mfma_peak = MFMA_FP4_PEAK_TOPS if bin_fp4 else MFMA_INT8_PEAK_TOPS
+                    per_gpu_tops = ops * args.steps / elapsed / 1e12
+                    row_bytes = nb if is_bin else bytes_per_row
+                    traffic, source = pmc_traffic(f"{'bin' if is_bin else 'u8'}_batch{Q}_{dim}", n, n * row_bytes)
+                    line["roofline"] = batch_roofline(per_gpu_tops, mfma_peak, ops, n * row_bytes, elapsed / args.steps) | {
+                        "traffic": traffic, "traffic_source": source,
+                        "algorithmic_read_bytes_per_step": n * row_bytes,
+                        "note": ("fp4" if bin_fp4 else "int8") + " op/s per GPU over the whole step (sample pass, filter GEMM, scatter, "
+                                "sort, exchange); algorithmic ops = 2 * actual_dim per (query, row) pair; traffic = HBM bytes "
+                                "of the step's dominant (filter) kernel: the store's rows leave HBM once per batch"}
+            if args.full:
+                line["cpu_baseline"] = cpu
+            print(json.dumps(line), flush=True)
         if use_dist:
             dist.barrier()
             dist.destroy_process_group()
@@ -705,7 +741,7 @@ def main():
     group = args.gather_group or (4 if multi else 1)
     encode_ahead = args.encode_ahead == 1  # measured at 1.25M rows/GPU: 0.151 ms per step against 0.147 in line
     # (the side stream's kernel and the two cross-stream waits cost more than the 4 us encode they hide)
-    time_every = args.time_every or (8 if multi else 1)
+    time_every = (args.time_every or (8 if multi else 1)) if args.full else 0  # 0: no kernel events in a plain run
     qobjs = [enc.encode_query(queries[0]), enc.encode_query(queries[0])]
     gather = topk = None
     if args.exchange == "scores":
@@ -717,6 +753,7 @@ def main():
         if scaling_field == "weak" and world > 1:
             topk.bases = [args.rows * r for r in range(world)]
     scores_plain = torch.empty(max(n_max, 1), dtype=torch.float32, device=dev) if gather is None else None
+    last_topk = [None]  # (ids, scores) of the last --exchange topk step
 
     # The hot step goes to the C ABI directly with pre-bound arguments: at 8 GPUs a shard scan is
     # ~0.15 ms, so the tens of microseconds the Python mirror spends per call (buffer checks,
@@ -751,7 +788,7 @@ def main():
         else:
             st |= encode(i, stream)
         out = gather.slot(i) if gather is not None else scores_plain
-        timed = timed and (i % time_every == 0)
+        timed = timed and time_every > 0 and (i % time_every == 0)
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -768,7 +805,7 @@ def main():
         elif topk is not None:
             ids, sc = topk.buffers()  # per-shard selection over the fresh scores, then k pairs/rank
             qa.topk_scores(out, n, args.k, largest=True, out_ids=ids, out_scores=sc)
-            topk.exchange(largest=True)
+            last_topk[0] = topk.exchange(largest=True)
 
     # set-up, like the encode above: untimed passes so that the W warm-up steps and the K timed steps start from a ramped
     # clock and warm allocator pools.  The ramp takes TIME, not launches: a 0.2 ms PQ scan was still getting faster 40
@@ -799,6 +836,14 @@ def main():
             gather.drain()
 
     elapsed = timed_region(body, args.steps)
+    if args.dump_outputs:
+        if gather is not None:  # the last step's scores of every shard, on the rank that step gathered to
+            last = gather.collect(args.steps - 1)
+            if last is not None:
+                write_outputs(args.dump_outputs, {"scores": assemble_global_scores(last, total_rows, world)})
+        elif rank == 0:
+            write_outputs(args.dump_outputs, {"ids": last_topk[0][0], "scores": last_topk[0][1]} if topk is not None
+                          else {"scores": scores_plain[:n]})  # --exchange none: rank 0's own shard
     kern_all = [a.elapsed_time(b) for a, b in ev_pairs]
     kern_ms = float(np.mean(kern_all)) if kern_all else float("nan")
     if os.environ.get("QAMD_BENCH_TRACE") and rank == 0:  # developer: per-step kernel times
@@ -808,65 +853,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = total_rows * args.steps / elapsed
-        achieved = bytes_per_row * n / (kern_ms * 1e-3) / 1e9
-        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBPS, "traffic": None,
-                    "kernel": kernel_name, "kernel_ms": kern_ms,
-                    "kernel_ms_min": float(np.min(kern_all)), "kernel_ms_median": float(np.median(kern_all)),
-                    "kernel_ms_mean": kern_ms,
-                    "algorithmic_bytes_per_row": bytes_per_row, "rows_per_launch": n,
-                    # `achieved` counts what SURVEY 8(d) counts: the row bytes READ.  The scan also writes one f32 score per
-                    # row; with it the kernel moves this much (3 % more for 128-byte binary rows, 0.5 % for u8 at dim 768):
-                    "score_bytes_written_per_row": 4,
-                    "achieved_incl_score_writes": (bytes_per_row + 4) * n / (kern_ms * 1e-3) / 1e9}
-        if args.quantizer == "pq":
-            # The PQ scan reads only m bytes per row from HBM; the LDS gather rate rides along.
-            lds = 4.0 * bytes_per_row * n / (kern_ms * 1e-3) / 1e9
-            if pq_skew:
-                # pq_scan_skew_kernel (m = 32 / 64 / 96 / 128): transposed LUT + quads skewed in time, no bank conflicts
-                # (SQ_LDS_BANK_CONFLICT = 0): the nominal bound, HBM reads of m bytes per row, is the roofline again
-                roofline.update({"lds_gather_GBps": lds, "lds_gather_frac_of_conflict_free_peak": lds / LDS_B32_PEAK_GBPS,
-                                 "note": "m code bytes per row from HBM; per chunk and row one ds_read_u8 (code), one "
-                                         "ds_read_b32 (table entry) and two vector-ALU operations, all conflict-free.  The "
-                                         "kernel runs 3 % above its own stream (loads, LDS ring, 4-byte score stores); the "
-                                         "stores - 4 % of the bytes - cost a quarter of that stream's time "
-                                         "(profiles/r04_pq_skew_probe.txt)"})
-            else:
-                roofline.update({"bound": "lds", "achieved": lds, "peak": LDS_B32_PEAK_GBPS, "frac": lds / LDS_B32_PEAK_GBPS,
-                                 "hbm_achieved_GBps": achieved, "hbm_frac": achieved / HBM_PEAK_GBPS,
-                                 "note": "achieved = 4 B x m LUT gathers per row (ds_read_b32) against the conflict-free "
-                                         "LDS rate of all CUs; random 8-bit codes give ~3.5-way bank conflicts, i.e. a "
-                                         "practical ceiling near 0.29 of that peak"})
-        pmc_key = {"u8": "u8_scan", "binary": "bin_scan", "pq": f"pq_scan_m{bytes_per_row}"}[args.quantizer]
-        traffic, source = pmc_traffic(pmc_key, n, n * bytes_per_row)
-        if traffic is not None:
-            roofline["traffic"] = traffic
-            roofline["traffic_source"] = source
-        # on-box streaming-read ceiling with the same load shape (16 B/lane, nt): a measurement helper built
-        # beside the tools (tools/probe), not an entry point of the product library
-        try:
-            P = C.CDLL(_lib.PROBE_PATH)
-            P.qamd_probe_stream_read.restype = C.c_int
-            P.qamd_probe_stream_read.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-            probe = torch.empty(4 << 30, dtype=torch.uint8, device=dev)
-            probe.zero_()
-            scratch = torch.empty(1 << 16, dtype=torch.uint8, device=dev)
-            s = torch.cuda.current_stream().cuda_stream
-            for _ in range(3):
-                if P.qamd_probe_stream_read(probe.data_ptr(), probe.numel(), scratch.data_ptr(), s):
-                    raise RuntimeError("probe launch failed")
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(10):
-                P.qamd_probe_stream_read(probe.data_ptr(), probe.numel(), scratch.data_ptr(), s)
-            b.record()
-            torch.cuda.synchronize()
-            roofline["stream_read_ceiling_GBps"] = probe.numel() * 10 / (a.elapsed_time(b) * 1e-3) / 1e9
-            del probe
-        except Exception as e:  # pragma: no cover
-            roofline["stream_read_ceiling_GBps"] = None
-            roofline["stream_read_error"] = str(e)
-
         headline = (total_rows == 10_000_000 and dim == 768 and args.distance == "dot" and args.quantizer == "u8")
         shard_txt = (f"{total_rows} x {dim} store" if world == 1 else
                      f"{total_rows} x {dim} store row-sharded over {world} GPUs ({n} rows on rank 0, {scaling_field} scaling)")
@@ -886,23 +872,82 @@ def main():
                        "quantizer": args.quantizer, "rows_per_gpu": n, "dim": dim, "distance": args.distance,
                        "exchange": args.exchange, "exchange_reason": exchange_reason,
                        "gather_group": group if gather is not None else None, **dist_info,
-                       "encode_ahead": encode_ahead, "kernel_timed_every": time_every,
+                       "encode_ahead": encode_ahead, "kernel_timed_every": time_every or None,
                        "gather_root": args.gather_root if (world > 1 and args.exchange == "scores") else None,
                        "total_rows": total_rows, "queries": args.queries},
-            "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            achieved = bytes_per_row * n / (kern_ms * 1e-3) / 1e9
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBPS, "traffic": None,
+                        "kernel": kernel_name, "kernel_ms": kern_ms,
+                        "kernel_ms_min": float(np.min(kern_all)), "kernel_ms_median": float(np.median(kern_all)),
+                        "kernel_ms_mean": kern_ms,
+                        "algorithmic_bytes_per_row": bytes_per_row, "rows_per_launch": n,
+                        # `achieved` counts what SURVEY 8(d) counts: the row bytes READ.  The scan also writes one f32 score per
+                        # row; with it the kernel moves this much (3 % more for 128-byte binary rows, 0.5 % for u8 at dim 768):
+                        "score_bytes_written_per_row": 4,
+                        "achieved_incl_score_writes": (bytes_per_row + 4) * n / (kern_ms * 1e-3) / 1e9}
+            if args.quantizer == "pq":
+                # The PQ scan reads only m bytes per row from HBM; the LDS gather rate rides along.
+                lds = 4.0 * bytes_per_row * n / (kern_ms * 1e-3) / 1e9
+                if pq_skew:
+                    # pq_scan_skew_kernel (m = 32 / 64 / 96 / 128): transposed LUT + quads skewed in time, no bank conflicts
+                    # (SQ_LDS_BANK_CONFLICT = 0): the nominal bound, HBM reads of m bytes per row, is the roofline again
+                    roofline.update({"lds_gather_GBps": lds, "lds_gather_frac_of_conflict_free_peak": lds / LDS_B32_PEAK_GBPS,
+                                     "note": "m code bytes per row from HBM; per chunk and row one ds_read_u8 (code), one "
+                                             "ds_read_b32 (table entry) and two vector-ALU operations, all conflict-free.  The "
+                                             "kernel runs 3 % above its own stream (loads, LDS ring, 4-byte score stores); the "
+                                             "stores - 4 % of the bytes - cost a quarter of that stream's time "
+                                             "(profiles/r04_pq_skew_probe.txt)"})
+                else:
+                    roofline.update({"bound": "lds", "achieved": lds, "peak": LDS_B32_PEAK_GBPS, "frac": lds / LDS_B32_PEAK_GBPS,
+                                     "hbm_achieved_GBps": achieved, "hbm_frac": achieved / HBM_PEAK_GBPS,
+                                     "note": "achieved = 4 B x m LUT gathers per row (ds_read_b32) against the conflict-free "
+                                             "LDS rate of all CUs; random 8-bit codes give ~3.5-way bank conflicts, i.e. a "
+                                             "practical ceiling near 0.29 of that peak"})
+            pmc_key = {"u8": "u8_scan", "binary": "bin_scan", "pq": f"pq_scan_m{bytes_per_row}"}[args.quantizer]
+            traffic, source = pmc_traffic(pmc_key, n, n * bytes_per_row)
+            if traffic is not None:
+                roofline["traffic"] = traffic
+                roofline["traffic_source"] = source
+            # on-box streaming-read ceiling with the same load shape (16 B/lane, nt): a measurement helper built
+            # beside the tools (tools/probe), not an entry point of the product library
             try:
+                P = C.CDLL(_lib.PROBE_PATH)
+                P.qamd_probe_stream_read.restype = C.c_int
+                P.qamd_probe_stream_read.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+                probe = torch.empty(4 << 30, dtype=torch.uint8, device=dev)
+                probe.zero_()
+                scratch = torch.empty(1 << 16, dtype=torch.uint8, device=dev)
+                s = torch.cuda.current_stream().cuda_stream
+                for _ in range(3):
+                    if P.qamd_probe_stream_read(probe.data_ptr(), probe.numel(), scratch.data_ptr(), s):
+                        raise RuntimeError("probe launch failed")
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(10):
+                    P.qamd_probe_stream_read(probe.data_ptr(), probe.numel(), scratch.data_ptr(), s)
+                b.record()
                 torch.cuda.synchronize()
-                enc.encode_query(queries[0], reuse=qobjs[0])
-                full = enc.score_all(qobjs[0], out=torch.empty(n, dtype=torch.float32, device=dev))
-                torch.cuda.synchronize()
-                sample_rows = min(n, args.cpu_sample_rows or n, 10_000_000)
-                result["cpu_baseline"] = cpu_baseline(args.quantizer, enc, queries[0].cpu().numpy(), full.cpu().numpy(),
-                                                      0 if args.distance == "dot" else 2, sample_rows, args.pq_chunk)
-            except Exception as e:
-                result["cpu_baseline"] = {"value": None, "unit": "vectors/s", "cores": 0, "kind": "port",
-                                          "sample": f"failed: {e}"}
+                roofline["stream_read_ceiling_GBps"] = probe.numel() * 10 / (a.elapsed_time(b) * 1e-3) / 1e9
+                del probe
+            except Exception as e:  # pragma: no cover
+                roofline["stream_read_ceiling_GBps"] = None
+                roofline["stream_read_error"] = str(e)
+            result["roofline"] = roofline
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    torch.cuda.synchronize()
+                    enc.encode_query(queries[0], reuse=qobjs[0])
+                    full = enc.score_all(qobjs[0], out=torch.empty(n, dtype=torch.float32, device=dev))
+                    torch.cuda.synchronize()
+                    sample_rows = min(n, args.cpu_sample_rows or n, 10_000_000)
+                    result["cpu_baseline"] = cpu_baseline(args.quantizer, enc, queries[0].cpu().numpy(), full.cpu().numpy(),
+                                                          0 if args.distance == "dot" else 2, sample_rows, args.pq_chunk)
+                except Exception as e:
+                    result["cpu_baseline"] = {"value": None, "unit": "vectors/s", "cores": 0, "kind": "port",
+                                              "sample": f"failed: {e}"}
         print(json.dumps(result), flush=True)
 
     if use_dist:

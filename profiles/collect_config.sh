@@ -11,6 +11,7 @@
 set -u
 TAG=$1; COMMIT=$2; NAME=$3; KEY=$4; NEEDLE=$5; ROWS=$6; ROWB=$7; LPU=$8; WB=$9
 shift 10
+set -- --full "$@"  # the line quotes roofline and cpu_baseline, which bench.py prints with --full
 export TMPDIR=/tmp
 OUT=gpurun_out/${TAG}_prof_${NAME}
 mkdir -p "$OUT"

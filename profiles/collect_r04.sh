@@ -28,5 +28,5 @@ run batch192    u8_batch192_768     u8_gemm_rk16_kernel           10000000  772 
 run batch384    u8_batch384_768     u8_gemm_rk16_kernel           10000000  772    1 0 -- --batch-queries 384 --k 30 --steps 10 --warmup 5
 run batch768    u8_batch768_768     u8_gemm_rk16_kernel           10000000  772    1 0 -- --batch-queries 768 --k 30 --steps 8 --warmup 3
 run batch256    u8_batch256_768     u8_gemm_qr16_kernel           10000000  772    1 0 -- --batch-queries 256 --k 30 --steps 10 --warmup 5
-line_only pq_batch64 -- --quantizer pq --batch-queries 64 --k 30 --steps 3 --warmup 1
-line_only pq_batch1024_1536 -- --quantizer pq --dim 1536 --rows 12500000 --batch-queries 1024 --k 30 --steps 2 --warmup 1
+line_only pq_batch64 -- --full --quantizer pq --batch-queries 64 --k 30 --steps 3 --warmup 1
+line_only pq_batch1024_1536 -- --full --quantizer pq --dim 1536 --rows 12500000 --batch-queries 1024 --k 30 --steps 2 --warmup 1

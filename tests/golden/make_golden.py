@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/pair_kernels.npz from the reference's own C kernels.
+"""Generate tests/golden/pair_kernels.npz and ref_differential.npz from the reference's own C kernels.
 
 Run in the build container only (needs /root/reference to compile oracle/_ref):
 
@@ -76,6 +76,28 @@ def main() -> None:
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "pair_kernels.npz")
     np.savez_compressed(path, **out)
     print(f"wrote {path}: {len(case_names)} cases, {os.path.getsize(path)} bytes")
+    write_differential(R)
+
+
+def write_differential(R) -> None:
+    """tests/golden/ref_differential.npz: the reference's outputs for util.ref_differential_cases() (inputs regenerated
+    from their seed; a digest of them is stored alongside)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from util import cases_digest, ref_differential_cases
+
+    cases = ref_differential_cases()
+    out = {k: np.zeros(len(cases), dtype=np.float32) for k in ("dot_avx", "dot_sse", "l1_avx")}
+    out["popcnt128"] = np.zeros(len(cases), dtype=np.uint32)
+    for i, (dim, q, v) in enumerate(cases):
+        qp, vp = q.ctypes.data, v.ctypes.data
+        out["dot_avx"][i] = R.impl_score_dot_avx(qp, vp, dim)
+        out["dot_sse"][i] = R.impl_score_dot_sse(qp, vp, dim)
+        out["l1_avx"][i] = R.impl_score_l1_avx(qp, vp, dim)
+        out["popcnt128"][i] = R.impl_xor_popcnt_sse_uint128(qp, vp, dim // 16)
+    out["inputs_sha256"] = np.array(cases_digest(cases))
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_differential.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {len(cases)} pairs, {os.path.getsize(path)} bytes")
 
 
 if __name__ == "__main__":

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ def _last_json(out: str) -> dict:
 @pytest.mark.parametrize("extra", [[], ["--quantizer", "binary", "--dim", "1024"], ["--quantizer", "pq"],
                                    ["--quantizer", "pq", "--pq-chunk", "4"], ["--distance", "l2"]])
 def test_bench_single_gpu_line(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--rows-per-gpu", "300000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--rows-per-gpu", "300000",
            "--cpu-sample-rows", "50000"] + extra
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -81,7 +82,7 @@ def test_bench_four_ranks_strong_scaling_grouped_rotating_gather():
     """Four ranks on one GPU over gloo: the strong-scaling default (store fixed, 4 ragged shards), gathers in
     groups of 4 queries with a rotating root, a step count that leaves a partly filled last group."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr",
-           "127.0.0.1", "--master-port", "29535", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "10",
+           "127.0.0.1", "--master-port", "29535", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--steps", "10",
            "--warmup", "3", "--rows", "400003", "--backend", "gloo", "--all-ranks-on-device", "0"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
@@ -95,7 +96,7 @@ def test_bench_four_ranks_strong_scaling_grouped_rotating_gather():
 def test_bench_batched_topk_mode(ranks):
     """The opt-in config-4 shape: many queries per step on the matrix cores, sharded rows, one
     all-gather of world*Q*k pairs (two ranks rehearsed on one GPU over gloo)."""
-    base = [os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--rows-per-gpu",
+    base = [os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--rows-per-gpu",
             "1200000", "--dim", "192", "--batch-queries", "200", "--k", "10"]
     if ranks == 1:
         cmd = [sys.executable] + base
@@ -119,7 +120,7 @@ def test_bench_batched_topk_mode(ranks):
 def test_bench_pq_batched_mode():
     """--quantizer pq --batch-queries: BASELINE config 4's PQ leg in small - the per-query pipelines back to back, priced against the code
     bytes every query streams; one query of the batch checked against the oracle's caller loop."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--quantizer", "pq", "--steps", "1", "--warmup", "1", "--rows", "300000", "--dim",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--quantizer", "pq", "--steps", "1", "--warmup", "1", "--rows", "300000", "--dim",
            "192", "--batch-queries", "8", "--k", "10"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, QAMD_BENCH_PREWARM_S="0.02"))
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
@@ -162,7 +163,7 @@ def test_bench_binary_multi_rank_defaults_to_the_topk_exchange():
 @pytest.mark.parametrize("exchange", ["scores", "topk"])
 def test_bench_single_process_sharded_handle(exchange):
     """--single-process: one process drives the shards through qamd_u8_sharded_* (two logical shards here)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--single-process", "--gpus", "2", "--devices", "0,0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--single-process", "--gpus", "2", "--devices", "0,0",
            "--steps", "5", "--warmup", "2", "--rows", "300001", "--exchange", exchange]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
@@ -171,3 +172,34 @@ def test_bench_single_process_sharded_handle(exchange):
     assert j["config"]["launch"] == "single-process" and j["config"]["devices"] == [0, 0]
     assert j["config"]["rows_per_gpu"] == 150000 and j["config"]["exchange"] == exchange
     assert 0 < j["roofline"]["frac"] < 1.2
+
+
+@pytest.mark.parametrize("extra", [[], ["--batch-queries", "8", "--k", "10", "--dim", "192"]])
+def test_bench_plain_run_is_lean_and_dumps_what_full_computes(extra, tmp_path):
+    """A plain run prints the headline line without the --full extras (roofline, CPU baseline); --dump-outputs writes what
+    the last timed step computed, and a --full run of the same arguments computes the same outputs bit for bit."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--rows", "300000"] + extra
+    lines = {}
+    for mode, flags in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        res = subprocess.run(base + flags + ["--dump-outputs", str(tmp_path / mode)], capture_output=True, text=True,
+                             timeout=600, cwd=ROOT)
+        assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
+        lines[mode] = _last_json(res.stdout)
+    j = lines["plain"]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert j.get(key) is not None, key
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and "roofline" not in j and "cpu_baseline" not in j
+    assert {k: v for k, v in j.items() if k not in ("value", "ms_per_step", "host_enqueue_ms_per_step", "config")} == \
+        {k: v for k, v in lines["full"].items() if k not in ("value", "ms_per_step", "host_enqueue_ms_per_step", "config",
+                                                              "roofline", "cpu_baseline")}
+    assert "roofline" in lines["full"]
+    names = ["ids.npy", "scores.npy"] if extra else ["scores.npy"]
+    assert sorted(os.listdir(tmp_path / "plain")) == names == sorted(os.listdir(tmp_path / "full"))
+    scores = np.load(tmp_path / "plain" / "scores.npy")
+    assert scores.dtype == np.float32 and scores.shape == ((8, 10) if extra else (300000,)) and np.isfinite(scores).all()
+    if extra:
+        ids = np.load(tmp_path / "plain" / "ids.npy")
+        assert ids.dtype == np.float64 and ids.shape == (8, 10) and ((ids >= 0) & (ids < 300000)).all()
+    for f in names:
+        a, b = np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)
+        assert a.tobytes() == b.tobytes(), f

@@ -4,9 +4,11 @@ pair_kernels.npz holds outputs of quantization/cpp/avx2.c + cpp/sse.c compiled w
 build.rs's flags (tests/golden/make_golden.py).  Bit-exact comparisons.
 """
 import ctypes as C
+import os
 
 import numpy as np
-import pytest
+
+from util import cases_digest, ref_differential_cases
 
 
 def _each(golden):
@@ -73,26 +75,23 @@ def test_exact_integer_for_encoder_codes_up_to_dim_1040(qo, golden):
 
 
 def test_live_reference_differential(qo):
-    """When oracle/_ref is present (built here, shipped prebuilt to the GPU box), fuzz the
-    restatement against it on fresh inputs."""
+    """Fuzz the restatement on seeded inputs against the outputs the compiled reference returned for them
+    (tests/golden/ref_differential.npz), and against oracle/_ref itself when it is present (built here, shipped
+    prebuilt to the GPU box)."""
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_differential.npz"))
+    cases = ref_differential_cases()
+    assert cases_digest(cases) == str(want["inputs_sha256"]), "seeded inputs changed: re-run tests/golden/make_golden.py"
     R = qo.ref()
-    if R is None:
-        pytest.skip("oracle/_ref not built")
     L = qo.lib()
-    rng = np.random.default_rng(7)
-    for dim in (16, 48, 80, 768, 1536, 3072):
-        for hi in (128, 256):
-            for _ in range(25):
-                q = rng.integers(0, hi, size=dim, dtype=np.uint8)
-                v = rng.integers(0, hi, size=dim, dtype=np.uint8)
-                qp, vp = q.ctypes.data, v.ctypes.data
-                a = np.float32(R.impl_score_dot_avx(qp, vp, dim))
-                b = np.float32(L.qo_dot_avx2_order(qp, vp, dim))
-                assert a.view(np.uint32) == b.view(np.uint32)
-                a = np.float32(R.impl_score_dot_sse(qp, vp, dim))
-                b = np.float32(L.qo_dot_sse_order(qp, vp, dim))
-                assert a.view(np.uint32) == b.view(np.uint32)
-                a = np.float32(R.impl_score_l1_avx(qp, vp, dim))
-                b = np.float32(L.qo_l1_avx2_order(qp, vp, dim))
-                assert a.view(np.uint32) == b.view(np.uint32)
-                assert R.impl_xor_popcnt_sse_uint128(qp, vp, dim // 16) == L.qo_xor_popcnt(qp, vp, dim)
+    for i, (dim, q, v) in enumerate(cases):
+        qp, vp = q.ctypes.data, v.ctypes.data
+        for key, mine, ref in (("dot_avx", L.qo_dot_avx2_order, R and R.impl_score_dot_avx),
+                               ("dot_sse", L.qo_dot_sse_order, R and R.impl_score_dot_sse),
+                               ("l1_avx", L.qo_l1_avx2_order, R and R.impl_score_l1_avx)):
+            b = np.float32(mine(qp, vp, dim))
+            assert b.view(np.uint32) == want[key][i].view(np.uint32), (key, i, dim)
+            if R is not None:
+                assert np.float32(ref(qp, vp, dim)).view(np.uint32) == b.view(np.uint32), (key, i, dim)
+        assert L.qo_xor_popcnt(qp, vp, dim) == want["popcnt128"][i], ("popcnt128", i, dim)
+        if R is not None:
+            assert R.impl_xor_popcnt_sse_uint128(qp, vp, dim // 16) == want["popcnt128"][i], ("popcnt128", i, dim)
