@@ -259,7 +259,15 @@ QAMD_API qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_ba
 /* Extension (no reference counterpart): how a pair sum >= 2^24 (only possible for
  * actual_dim > 1040) becomes f32.  0 (default): exact integer, rounded once — what the
  * reference's scalar path does (encoded_vectors_u8.rs:158).  1: the 8-lane f32 summation
- * order of impl_score_dot_avx (quantization/cpp/avx2.c:41-62), bit for bit. */
+ * order of impl_score_dot_avx (quantization/cpp/avx2.c:41-62), bit for bit.
+ * The mode holds for the whole handle: score_point, score_internal, score_all, score_ids,
+ * score_internal_ids, both bursts (*_ids_batch), topk, score_batch and topk_batch.  In mode 1
+ * the batch calls take per-query scans instead of the matrix cores.
+ * Mode 1 changes Dot and L2 only; L1 is the exact sum in both modes (impl_score_l1_avx's u16
+ * lanes wrap from actual_dim 8272 on: not reproduced).  Mode 1's claim holds for codes <= 127,
+ * what the encoder writes.  Up to actual_dim 2080 the two modes give the same bits (each f32
+ * half sum of the lane order stays below 2^24); they can differ from 2096 on.  Sharded handles
+ * have no lane switch: they always answer in mode 0. */
 QAMD_API qamd_status qamd_u8_set_lane_mode(qamd_u8 *h, int mode);
 
 /* ===================================================================================

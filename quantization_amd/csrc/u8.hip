@@ -93,13 +93,39 @@ template <int G> __device__ __forceinline__ uint32_t group_sum(uint32_t v) {
     return v;
 }
 
-// encoded_vectors_u8.rs:347 / :409.  s is the exact integer pair sum.
-__device__ __forceinline__ float epilogue(float multiplier, uint32_t s, float q_off, float v_off,
-                                          float diff, int mode) {
-    float sf = (float)(int32_t)s;
+// encoded_vectors_u8.rs:347 / :409 on the pair sum as an f32 (sf).
+__device__ __forceinline__ float epilogue_f(float multiplier, float sf, float q_off, float v_off, float diff, int mode) {
     float ms = multiplier * sf;
     if (mode == EPI_POINT) return (ms + q_off) + v_off;
     return ms + ((q_off + v_off) - diff);
+}
+// s is the exact integer pair sum (lane mode 0: rounded once).
+__device__ __forceinline__ float epilogue(float multiplier, uint32_t s, float q_off, float v_off,
+                                          float diff, int mode) {
+    return epilogue_f(multiplier, (float)(int32_t)s, q_off, v_off, diff, mode);
+}
+
+// Lane mode 1 (avx2.c lane order, any dim): lane k of the reference's 8 x i32 accumulator gets byte pairs p with
+// p % 8 == k of every 32-byte block (avx2.c:41-45) and bytes 2k, 2k+1 of a 16-byte tail (:49-58).  A block has 16
+// pairs, so in both 16-byte pieces of a block dword j holds pairs that go to lanes 2j (bytes 0, 1) and 2j+1 (bytes
+// 2, 3), and so does the tail: eight integer accumulators, acc[2j] += the low-half products of dword j, acc[2j+1] +=
+// the high-half ones.
+__device__ __forceinline__ void dot16_lanes(const uint4 &v, const uint4 &q, uint32_t (&acc)[8]) {
+    const uint32_t vd[4] = {v.x, v.y, v.z, v.w};
+    const uint32_t qd[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        acc[2 * j] = __builtin_amdgcn_udot4(vd[j], qd[j] & 0x0000FFFFu, acc[2 * j], false);
+        acc[2 * j + 1] = __builtin_amdgcn_udot4(vd[j], qd[j] & 0xFFFF0000u, acc[2 * j + 1], false);
+    }
+}
+// Each lane summed over the row group, converted to f32 and added ((l0+l4)+(l2+l6))+((l1+l5)+(l3+l7)) (HSUM256_PS).
+template <int G> __device__ __forceinline__ float avx2_lane_sum(uint32_t (&acc)[8]) {
+    float f[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) f[k] = (float)(int32_t)group_sum<G>(acc[k]);
+    float a0 = f[0] + f[4], a1 = f[1] + f[5], a2 = f[2] + f[6], a3 = f[3] + f[7];
+    return (a0 + a2) + (a1 + a3);
 }
 
 // encoded_vectors_u8.rs:234-237  ((v-offset)/alpha).clamp(0,127) as u8
@@ -483,13 +509,7 @@ __global__ __launch_bounds__(kBlock) void u8_scan_generic_kernel(
     }
 }
 
-// avx2.c lane-exact variant (any dim): lane k of the reference's 8 x i32 accumulator gets
-// byte pairs p with p % 8 == k of every 32-byte block (avx2.c:41-45) and bytes 2k,2k+1 of a
-// 16-byte tail (:49-58).  Within a 16-byte chunk c (two per block) dword j holds pairs
-// 2j, 2j+1 of that chunk, i.e. lanes (2j + 8*(c&1)... ) -> since a block has 16 pairs and
-// lane = pair % 8, both chunks of a block map dword j to lanes 2j and 2j+1.  So 8 integer
-// accumulators: acc[2j] += lo-half products of dword j, acc[2j+1] += hi-half products.
-// Each is converted to f32 and summed ((l0+l4)+(l2+l6))+((l1+l5)+(l3+l7)) (HSUM256_PS).
+// Lane mode 1 scan (any dim): dot16_lanes / avx2_lane_sum, the scan's EPI_POINT epilogue.
 template <bool DUMMY>
 __global__ __launch_bounds__(kBlock) void u8_scan_avx2_lanes_kernel(
     const uint4 *__restrict__ codes, const float *__restrict__ offsets,
@@ -505,23 +525,9 @@ __global__ __launch_bounds__(kBlock) void u8_scan_avx2_lanes_kernel(
         const uint64_t row = base + rslot;
         const uint4 *p = codes + row * row_chunks;
         uint32_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (uint32_t c = sub; c < row_chunks; c += G) {
-            uint4 v = ld_nt(p + c);
-            uint4 qv = qcodes[c];
-            const uint32_t vd[4] = {v.x, v.y, v.z, v.w};
-            const uint32_t qd[4] = {qv.x, qv.y, qv.z, qv.w};
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                acc[2 * j] = __builtin_amdgcn_udot4(vd[j], qd[j] & 0x0000FFFFu, acc[2 * j], false);
-                acc[2 * j + 1] = __builtin_amdgcn_udot4(vd[j], qd[j] & 0xFFFF0000u, acc[2 * j + 1], false);
-            }
-        }
-        float f[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) f[k] = (float)(int32_t)group_sum<G>(acc[k]);
-        float a0 = f[0] + f[4], a1 = f[1] + f[5], a2 = f[2] + f[6], a3 = f[3] + f[7];
-        float s = (a0 + a2) + (a1 + a3);
-        if (sub == 0 && row < n_rows) out[row] = (multiplier * s + q_off) + offsets[row];
+        for (uint32_t c = sub; c < row_chunks; c += G) dot16_lanes(ld_nt(p + c), qcodes[c], acc);
+        const float s = avx2_lane_sum<G>(acc);
+        if (sub == 0 && row < n_rows) out[row] = epilogue_f(multiplier, s, q_off, offsets[row], 0.0f, EPI_POINT);
     }
 }
 
@@ -537,14 +543,17 @@ __global__ __launch_bounds__(kBlock) void u8_scan_avx2_lanes_kernel(
 // by ONE binary search (thread 0, through LDS) and every group then walks forward from there as its
 // pair index grows -- a binary search per pair was ten dependent loads in front of every row fetch
 // (1M random pairs: 0.26 ms; this form: profiles/r03_bursts.jsonl).
-// Same integer sum and the same f32 epilogue as the scan => the same score bits.
-template <bool IS_L1, int ITERS>
+// Same integer sum and the same f32 epilogue as the scan => the same score bits.  LANES (lane mode 1, Dot / L2, any
+// row length through ITERS = 0): the lane-mode-1 scan's arithmetic instead (dot16_lanes, avx2_lane_sum, epilogue_f),
+// so score_internal's `diff` epilogue is unchanged.
+template <bool IS_L1, int ITERS, bool LANES = false>
 __global__ __launch_bounds__(kBlock) void u8_score_pairs_kernel(
     const uint4 *__restrict__ codes, const float *__restrict__ offsets, const uint4 *q_single, const float *q_off_single,
     const uint8_t *__restrict__ q_batch, uint32_t q_pitch, const float *__restrict__ q_offs,
     const uint32_t *__restrict__ lists, uint32_t n_lists, const uint32_t *__restrict__ list_rows, float multiplier,
     float diff, int mode, const uint32_t *__restrict__ ids, uint64_t n_ids, uint32_t n_rows, uint32_t row_chunks,
     uint32_t pairs_per_block, float *__restrict__ out) {
+    static_assert(!LANES || ITERS == 0, "the lane-order form is the any-length loop");
     constexpr int G = 16, GROUPS = kBlock / G;
     __shared__ uint32_t first_list;
     const int lane = threadIdx.x & 63;
@@ -585,6 +594,7 @@ __global__ __launch_bounds__(kBlock) void u8_score_pairs_kernel(
             for (int j = 0; j < ITERS; j++)
                 if (j + 1 < ITERS || sub + j * G < row_chunks) acc = IS_L1 ? sad16(v[j], qv[j], acc) : dot16(v[j], qv[j], acc);
         } else {
+            uint32_t lanes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             for (uint32_t c0 = sub; c0 < row_chunks; c0 += 4 * G) {
                 uint4 v[4], qv[4];
 #pragma unroll
@@ -594,8 +604,17 @@ __global__ __launch_bounds__(kBlock) void u8_score_pairs_kernel(
                     qv[j] = qp[cc];
                 }
 #pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (c0 + j * G < row_chunks) acc = IS_L1 ? sad16(v[j], qv[j], acc) : dot16(v[j], qv[j], acc);
+                for (int j = 0; j < 4; j++) {
+                    if (c0 + j * G >= row_chunks) continue;
+                    if constexpr (LANES) dot16_lanes(v[j], qv[j], lanes);
+                    else acc = IS_L1 ? sad16(v[j], qv[j], acc) : dot16(v[j], qv[j], acc);
+                }
+            }
+            if constexpr (LANES) {
+                static_assert(!IS_L1, "lane mode 1 changes Dot and L2 only");
+                const float s = avx2_lane_sum<G>(lanes);
+                if (sub == 0) out[k] = ok ? epilogue_f(multiplier, s, q_off, offsets[row], diff, mode) : __builtin_nanf("");
+                continue;
             }
         }
         acc = group_sum<G>(acc);
@@ -1175,6 +1194,13 @@ void launch_multi_shape(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitc
 #undef QAMD_U8_MULTI
 }
 
+// Lane mode 1 on a Dot / L2 store: every score comes from the avx2.c lane-order kernels (u8_scan_avx2_lanes_kernel,
+// u8_score_pairs_kernel<.., LANES>); the kernels that sum the exact integer (single- and multi-query scans, the fused
+// and single-launch top-k, the matrix cores) are not used.  L1 has no lane order: both modes are the exact sum.
+bool lane_order(const qamd_u8 *h) {
+    return h->lane_mode == 1 && h->meta.vector_parameters.distance_type != QAMD_L1;
+}
+
 // Widest pass of the multi-query scan for this row size: 4 queries (2 for rows of more than 96
 // pieces), 0 = none.  Measured on 10M x 768 / 12.5M x 1536, top-30 per query, whole call: 2 queries
 // 1.24 / 2.93 ms and 4 queries 1.38 / 3.50 ms against 1.65 / 3.85 ms on the matrix-core path; an
@@ -1185,7 +1211,7 @@ void launch_multi_shape(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitc
 uint32_t multi_width(const qamd_u8 *h) {
     const uint32_t rc = h->row_chunks, iters = (rc + 15) / 16;
     const bool l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
-    if (rc < 9 || iters > 8 || (h->lane_mode != 0 && !l1)) return 0;
+    if (rc < 9 || iters > 8 || lane_order(h)) return 0;
     return l1 && iters <= 3 ? 8 : iters <= 6 ? 4 : 2;
 }
 
@@ -1215,10 +1241,7 @@ bool launch_multi(const qamd_u8 *h, uint32_t nq_valid, const uint8_t *qcodes, ui
     return false;
 }
 
-bool fused_capable(const qamd_u8 *h) {
-    const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
-    return (is_l1 || h->lane_mode == 0) && h->row_chunks <= 128;
-}
+bool fused_capable(const qamd_u8 *h) { return !lane_order(h) && h->row_chunks <= 128; }
 
 // The single-launch top-k serves this store and k (and, for a fused query, these dims): its plan.
 bool u8_small_plan(const qamd_u8 *h, uint32_t k, SmallTopkPlan &plan) {
@@ -1235,7 +1258,7 @@ qamd_status scan_ptrs(const qamd_u8 *h, const uint4 *qc, const float *qo, float 
                       const TopkFilter *filt = nullptr) {
     if (h->count == 0) return QAMD_OK;
     const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
-    if (!is_l1 && h->lane_mode == 1) {
+    if (lane_order(h)) {
         uint64_t waves = (h->count + 3) / 4;
         unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
         hipLaunchKernelGGL((u8_scan_avx2_lanes_kernel<true>), dim3(grid), dim3(kBlock), 0, s,
@@ -1276,6 +1299,14 @@ qamd_status launch_pairs(const qamd_u8 *h, const uint4 *qc, const float *qo, con
                        h->offsets.as<float>(), qc, qo, q_batch, q_pitch, q_offs, lists, n_lists, list_rows,              \
                        h->meta.multiplier, diff, mode, ids_dev, n_ids, (uint32_t)h->count, h->row_chunks, (uint32_t)ppb, \
                        out_dev)
+    if (!IS_L1 && lane_order(h)) {
+        hipLaunchKernelGGL((u8_score_pairs_kernel<false, 0, true>), dim3(grid), dim3(kBlock), 0, s, h->codes.as<uint4>(),
+                           h->offsets.as<float>(), qc, qo, q_batch, q_pitch, q_offs, lists, n_lists, list_rows,
+                           h->meta.multiplier, diff, mode, ids_dev, n_ids, (uint32_t)h->count, h->row_chunks, (uint32_t)ppb,
+                           out_dev);
+        QAMD_HIP(hipGetLastError());
+        return QAMD_OK;
+    }
     switch (iters) {
         case 1: QAMD_U8_PAIRS(1); break;
         case 2: QAMD_U8_PAIRS(2); break;
@@ -2374,6 +2405,9 @@ qamd_status u8_score_lists(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t 
 
 // How many queries the vector-ALU multi-query scan takes per pass for this store (0: none).
 uint32_t u8_multi_width(const qamd_u8 *h) { return multi_width(h); }
+
+// Lane mode 1 on a Dot / L2 store: the batch API must take the per-query scans (the matrix cores sum exactly).
+bool u8_lane_order(const qamd_u8 *h) { return lane_order(h); }
 
 // out[j * count + row] for queries [0, n_queries) of a batch through the multi-query scan (groups of
 // `width`, then smaller groups, then single scans).

@@ -2952,7 +2952,8 @@ qamd_status qamd_u8_score_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, 
     }
     const uint32_t width = u8_multi_width(h);
     // (from three queries on the row-streaming MFMA kernel streams the rows as fast and does not slow down per query)
-    if (h->meta.vector_parameters.distance_type == QAMD_L1 ||
+    // Lane mode 1 (Dot, L2): the matrix cores sum exactly, so every query takes the lane-order scan (width 0).
+    if (h->meta.vector_parameters.distance_type == QAMD_L1 || u8_lane_order(h) ||
         (width && b->n_queries >= 2 && b->n_queries <= width && (b->n_queries == 2 || !rs_selected(h, b, false)))) {
         // sum |q - v| is not a contraction (no MFMA form), and for a handful of queries the vector-ALU
         // multi-query scan streams the rows faster than the matrix-core kernel's LDS-DMA path
@@ -2976,6 +2977,9 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
     hipStream_t s = as_stream(stream);
     const uint64_t Q = b->n_queries, n = h->count;
     const bool l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
+    if (u8_lane_order(h))  // lane mode 1 (Dot, L2): per-query lane-order scans, never the exact-sum matrix cores
+        return u8_topk_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)Q, k, largest,
+                                   out_ids, out_scores, out_mem, s);
     if (n > (2u << 20) && (l1 || (Q <= u8_multi_width(h) && Q >= 2 && (Q == 2 || !rs_selected(h, b, true)))))
         // L1 has no matrix form; and two queries (one pass of the vector-ALU multi-query scan) stream the
         // rows at the single-query scan's rate with less overhead around it than the matrix-core pass (from

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/pair_kernels.npz and ref_differential.npz from the reference's own C kernels.
+"""Generate tests/golden/pair_kernels.npz, ref_differential.npz and ref_wide_sums.npz from the reference's own C kernels.
 
 Run in the build container only (needs /root/reference to compile oracle/_ref):
 
@@ -77,6 +77,7 @@ def main() -> None:
     np.savez_compressed(path, **out)
     print(f"wrote {path}: {len(case_names)} cases, {os.path.getsize(path)} bytes")
     write_differential(R)
+    write_wide_sums(R)
 
 
 def write_differential(R) -> None:
@@ -96,6 +97,25 @@ def write_differential(R) -> None:
         out["popcnt128"][i] = R.impl_xor_popcnt_sse_uint128(qp, vp, dim // 16)
     out["inputs_sha256"] = np.array(cases_digest(cases))
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_differential.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {len(cases)} pairs, {os.path.getsize(path)} bytes")
+
+
+def write_wide_sums(R) -> None:
+    """tests/golden/ref_wide_sums.npz: impl_score_dot_avx / impl_score_l1_avx for util.wide_sum_cases() -- pair sums
+    past 2^24 and L1 lanes past 2^16, where the reference's AVX2 orders differ from the exact sum.  Outputs and the
+    digest of the seeded inputs only."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from util import cases_digest, wide_sum_cases
+
+    cases = wide_sum_cases()
+    out = {k: np.zeros(len(cases), dtype=np.float32) for k in ("dot_avx", "l1_avx")}
+    for i, (_tag, dim, q, v) in enumerate(cases):
+        qp, vp = q.ctypes.data, v.ctypes.data
+        out["dot_avx"][i] = R.impl_score_dot_avx(qp, vp, dim)
+        out["l1_avx"][i] = R.impl_score_l1_avx(qp, vp, dim)
+    out["inputs_sha256"] = np.array(cases_digest(cases))
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_wide_sums.npz")
     np.savez_compressed(path, **out)
     print(f"wrote {path}: {len(cases)} pairs, {os.path.getsize(path)} bytes")
 

@@ -240,6 +240,12 @@ def test_large_dims_generic_kernel_and_lane_modes(qo, dim):
     rows = np.zeros((n, ad + 4), dtype=np.uint8)
     rows[:, 4:] = codes
     rows[:, :4] = rng.standard_normal(n).astype(np.float32).view(np.uint8).reshape(n, 4)
+    # near-saturated rows (offset 0): past actual_dim 2080 they tell the lane modes apart, random [0, 127] rows
+    # rarely do at 4096
+    extra = np.zeros((27, ad + 4), dtype=np.uint8)
+    extra[:, 4:] = np.random.default_rng(dim + 1).integers(110, 128, size=(27, ad), dtype=np.uint8)
+    rows = np.concatenate([rows, extra])
+    n = rows.shape[0]
     md = {"actual_dim": ad, "alpha": 1.0, "offset": 0.0, "multiplier": 1.0,
           "vector_parameters": qa.VectorParameters(dim, n, D.Dot, False)}
     enc = qa.EncodedVectorsU8.from_storage(rows, md)
@@ -250,6 +256,12 @@ def test_large_dims_generic_kernel_and_lane_modes(qo, dim):
     _, qoff = qo.u8_encode_query(meta, query)
     got_codes = q.encoded_query
     want0 = qo.u8_score_all(meta, rows, got_codes, qoff, order=qo.ORDER_SIMPLE)
+    # the shape's edge: for codes <= 127 the two orders are equal up to actual_dim 2080 (test_oracle_golden.py)
+    differ = bits(want0) != bits(qo.u8_score_all(meta, rows, got_codes, qoff, order=qo.ORDER_AVX2))
+    if ad <= 2080:
+        assert not differ.any(), "the orders differ at actual_dim <= 2080"
+    else:
+        assert differ.any(), "no row tells the lane modes apart"
     assert_bits_equal(enc.score_all(q), want0, "mode 0")
     enc.set_lane_mode(1)
     want1 = qo.u8_score_all(meta, rows, got_codes, qoff, order=qo.ORDER_AVX2)
