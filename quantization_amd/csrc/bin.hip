@@ -932,6 +932,7 @@ qamd_status qamd_bin_topk(const qamd_bin *h, const qamd_bin_query *q, uint32_t k
                           float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(check_query(h, q));
     if (k == 0) return QAMD_OK;
+    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
     if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
@@ -1978,6 +1979,22 @@ qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b
         overflow = back[Q];
     }
     if (overflow) std::fill(status.begin(), status.end(), 1u);
+    static const bool debug_topk = dev_env("QAMD_DEBUG_TOPK") != nullptr;
+    if (debug_topk) {
+        std::vector<uint32_t> cnt(q_pad * kCounterStride);
+        (void)hipMemcpy(cnt.data(), counters, cnt.size() * 4, hipMemcpyDeviceToHost);
+        uint32_t mx = 0, mn = ~0u, redo = 0;
+        uint64_t sum = 0;
+        for (uint64_t q = 0; q < Q; q++) {
+            const uint32_t c = cnt[q * kCounterStride];
+            mx = std::max(mx, c);
+            mn = std::min(mn, c);
+            sum += c;
+            redo += status[q] != 0;
+        }
+        fprintf(stderr, "[qamd bin topk_batch] Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, %u queries redone\n",
+                (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx, redo);
+    }
     return QAMD_OK;
 }
 
@@ -2095,6 +2112,7 @@ qamd_status qamd_bin_topk_batch(const qamd_bin *h, const qamd_bin_query_batch *b
                                 uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(bin_check_batch(h, b));
     if (k == 0 || b->n_queries == 0) return QAMD_OK;
+    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
     if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
     QAMD_ON_DEVICE(h->device);
     const uint8_t *bits = b->bits.as<uint8_t>();

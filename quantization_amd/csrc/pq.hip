@@ -599,7 +599,9 @@ __global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_skew_kernel(
                         if (SLICED && !sl.last) {  // the lane sums go back to `partial` for the next slice
                             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(done), partial_rsrc, live ? (row * 4u + k) * 4u : 0xFFFFFFFFu, 0, 0);
                         } else if (FILTER) {
-                            if (k == 0 && live) topk_offer(filt, pivot, sc, row);
+                            // shard by wg, the workgroup's place among those of this query (blockIdx.x for one query):
+                            // keyed by blockIdx.x, n queries side by side each reached only 64 / n of their lists
+                            if (k == 0 && live) topk_offer_shard(filt, pivot, sc, row, wg);
                         } else if (COAL) {
                             // jb & 3 is a constant of the unrolled loop (D = 4, j0 % 4 == 0): lane k keeps block k's score, and
                             // after the run's last block the quads' 64 scores leave as one 256-byte store
@@ -2265,6 +2267,7 @@ qamd_status qamd_pq_topk(const qamd_pq *h, const qamd_pq_query *q, uint32_t k, i
                          float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(check_query(h, q));
     if (k == 0) return QAMD_OK;
+    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
     if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
@@ -2616,6 +2619,7 @@ qamd_status qamd_pq_topk_batch(const qamd_pq *h, const qamd_pq_query_batch *b, u
                                uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(pq_check_batch(h, b));
     if (k == 0 || b->n_queries == 0) return QAMD_OK;
+    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
     if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
     QAMD_ON_DEVICE(h->device);
     const size_t per = (size_t)h->m * kCentroids;

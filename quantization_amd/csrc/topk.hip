@@ -469,8 +469,8 @@ qamd_status fused_topk(uint64_t n, uint32_t k, int largest, uint32_t *out_ids, f
         if (debug_topk) {
             struct { uint32_t pivot_key, status, total; } dbg{};
             (void)hipMemcpy(&dbg, st, sizeof dbg, hipMemcpyDeviceToHost);
-            fprintf(stderr, "[qamd topk] n=%llu k=%u r=%u pivot_key=%08x candidates=%u status=%u\n",
-                    (unsigned long long)n, k, r, dbg.pivot_key, dbg.total, dbg.status);
+            fprintf(stderr, "[qamd topk] n=%llu k=%u r=%u pivot_key=%08x candidates=%u status=%u, %u queries redone\n",
+                    (unsigned long long)n, k, r, dbg.pivot_key, dbg.total, dbg.status, stt == QAMD_OK && status != 0 ? 1u : 0u);
         }
         if (stt == QAMD_OK && status == 0 && out_mem == QAMD_MEM_HOST) {
             if (hs.host) {  // the stream was synchronised by the status read
@@ -543,6 +543,9 @@ qamd_status fused_topk_batch(uint64_t n, uint32_t Q, uint32_t k, int largest, ui
         uint32_t *status_dev = reinterpret_cast<uint32_t *>(base + off_status);
         hipLaunchKernelGGL(sample_ids_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, sample_ids, S, n);
         std::vector<uint32_t> status(C);
+        static const bool debug_topk = dev_env("QAMD_DEBUG_TOPK") != nullptr;
+        uint32_t dbg_min = ~0u, dbg_max = 0, dbg_redo = 0;
+        uint64_t dbg_sum = 0;
         for (uint32_t q0 = 0; q0 < Q && st == QAMD_OK; q0 += C) {
             const uint32_t nq = std::min(C, Q - q0);
             // 1. every query of the chunk: sample scores -> pivot
@@ -582,9 +585,22 @@ qamd_status fused_topk_batch(uint64_t n, uint32_t Q, uint32_t k, int largest, ui
             }
             if (st == QAMD_OK && hipGetLastError() != hipSuccess) st = fail(QAMD_ERR_DEVICE, "batched top-k launch failed");
             if (st == QAMD_OK) st = copy_out(status.data(), QAMD_MEM_HOST, status_dev, (size_t)nq * 4, stream);  // one sync per chunk
+            if (debug_topk && st == QAMD_OK) {
+                for (uint32_t j = 0; j < nq; j++) {
+                    uint32_t total = 0;  // candidates kept (the emit kernel's sum of the capped shard counts)
+                    (void)hipMemcpy(&total, base + (size_t)j * per + offsetof(FusedState, total), 4, hipMemcpyDeviceToHost);
+                    dbg_min = std::min(dbg_min, total);
+                    dbg_max = std::max(dbg_max, total);
+                    dbg_sum += total;
+                    dbg_redo += status[j] != 0;
+                }
+            }
             for (uint32_t j = 0; j < nq && st == QAMD_OK; j++)
                 if (status[j] != 0) st = classic(q0 + j);  // heavy ties or an unlucky pivot: exact path
         }
+        if (debug_topk && st == QAMD_OK)
+            fprintf(stderr, "[qamd fused_topk_batch] Q=%u r=%u candidates min/mean/max = %u/%llu/%u, %u queries redone\n", Q, r,
+                    dbg_min, (unsigned long long)(dbg_sum / Q), dbg_max, dbg_redo);
     }
     if (scores) {
         thread_ws_release(WS_SCORES, stream);

@@ -53,14 +53,20 @@ __device__ __forceinline__ float topk_score_of_key(uint32_t key, bool largest) {
     return __uint_as_float(u);
 }
 
-__device__ __forceinline__ void topk_offer(const TopkFilter &f, uint32_t pivot, float score, uint32_t row) {
+// `shard` picks the candidate list (taken modulo kTopkShards).  A launch whose workgroups all serve one query keys it by
+// blockIdx.x (topk_offer); a launch that serves several queries side by side must key it by the workgroup's place among
+// those of ITS query, or each query reaches only 64 / n of its lists (pq.hip, SkewBatch).
+__device__ __forceinline__ void topk_offer_shard(const TopkFilter &f, uint32_t pivot, float score, uint32_t row, uint32_t shard) {
     const uint32_t key = topk_ordered_bits(score, f.largest != 0);
     if (key <= pivot) {
-        const uint32_t shard = blockIdx.x & (kTopkShards - 1);
+        shard &= kTopkShards - 1;
         const uint32_t pos = atomicAdd(f.counters + shard * kTopkCounterStride, 1u);
         if (pos < kTopkShardCap)
             f.candidates[shard * kTopkShardCap + pos] = ((unsigned long long)key << 32) | row;
     }
+}
+__device__ __forceinline__ void topk_offer(const TopkFilter &f, uint32_t pivot, float score, uint32_t row) {
+    topk_offer_shard(f, pivot, score, row, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -2006,6 +2006,7 @@ qamd_status qamd_u8_topk(const qamd_u8 *h, const qamd_u8_query *q, uint32_t k, i
                          float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(check_query(h, q));
     if (k == 0) return QAMD_OK;
+    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
     if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);

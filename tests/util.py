@@ -17,6 +17,24 @@ def assert_bits_equal(got, want, what=""):
             f"got {np.asarray(got, dtype=np.float32).ravel()[i]!r} want {np.asarray(want, dtype=np.float32).ravel()[i]!r}")
 
 
+def topk_want(scores, k: int, largest: bool = True):
+    """The top-k contract of include/quantization_amd.h restated on a whole-store score array: the stable best k (ties to
+    the lower row id), best first, padded to k as every entry point pads when the store has fewer rows: ids 0xFFFFFFFF,
+    scores -inf for `largest`, +inf otherwise.  Returns (ids u32[k], scores f32[k])."""
+    scores = np.asarray(scores, dtype=np.float32)
+    n = scores.size
+    key = -scores if largest else scores
+    cand = np.arange(n)
+    if 0 < k < n:  # only the rows at least as good as the k-th best (ties included) need the stable sort
+        cand = np.flatnonzero(key <= np.partition(key, k - 1)[k - 1])
+    order = cand[np.lexsort((cand, key[cand]))][: min(k, n)]
+    ids = np.full(k, 0xFFFFFFFF, dtype=np.uint32)
+    sc = np.full(k, -np.inf if largest else np.inf, dtype=np.float32)
+    ids[: order.size] = order
+    sc[: order.size] = scores[order]
+    return ids, sc
+
+
 def have_gpu() -> bool:
     try:
         from quantization_amd import _lib
