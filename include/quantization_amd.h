@@ -252,6 +252,8 @@ QAMD_API qamd_status qamd_u8_score_ids_batch(const qamd_u8 *h, const qamd_u8_que
                                              uint64_t n_ids, qamd_mem lists_mem, float *out, qamd_mem out_mem,
                                              void *stream);
 /* out_ids / out_scores: n_queries x k, per query as qamd_u8_topk.  Synchronises the stream. */
+/* (A device that does not report 256 CUs - a partitioned MI355X - never takes the rq kernels u8_gemm_rq16_kernel /
+ * u8_gemm_rk16_kernel; every grid is sized by its own CU count.  The answer is the same on every route.) */
 QAMD_API qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, uint32_t k,
                                         int largest, uint32_t *out_ids, float *out_scores,
                                         qamd_mem out_mem, void *stream);
@@ -393,7 +395,9 @@ QAMD_API qamd_status qamd_pq_kmeans_info(const qamd_pq *h, uint32_t *iterations,
  * 16 .. 128 chunks with m % 4 == 0), "pq_scan_skew_kernel<SLICED>" (longer rows with m % 32 == 0: one launch per LUT slice of
  * the store's planar scan image), "pq_scan_fast_kernel" (other row lengths), "pq_scan_kernel" (fewer than 4096 rows) - and
  * in *n_launches how many launches one scan is.  For measurement harnesses: bench.py names the kernel it times and picks
- * its roofline bound from this instead of re-deriving the library's dispatch. */
+ * its roofline bound from this instead of re-deriving the library's dispatch.  A store of at least 2^28 rows keeps no
+ * planar scan image, and a store of at least 2^30 rows does not use pq_scan_skew_kernel: both then take
+ * "pq_scan_fast_kernel" (rows of m > 144 chunks in ceil(m / 128) launches). */
 QAMD_API const char *qamd_pq_scan_kernel(const qamd_pq *h, uint32_t *n_launches);
 /* Streaming form (the reference walks its iterator twice: find_centroids :278-342, then
  * encode_storage :136-226): begin, observe every vector once (skipped when centroids are given),
@@ -480,6 +484,9 @@ QAMD_API qamd_status qamd_pq_score_ids_batch(const qamd_pq *h, const qamd_pq_que
                                              const uint32_t *list_offsets, uint32_t n_lists, const uint32_t *ids,
                                              uint64_t n_ids, qamd_mem lists_mem, float *out, qamd_mem out_mem,
                                              void *stream);
+/* Top-k of every query of the batch, as qamd_pq_topk.  A device that does not report 256 CUs (a partitioned MI355X) runs
+ * the filter passes query by query, never side by side; so does a store without a planar scan image (2^28 rows and more)
+ * whose rows have more than 144 chunks.  The answer is the same either way. */
 QAMD_API qamd_status qamd_pq_topk_batch(const qamd_pq *h, const qamd_pq_query_batch *b, uint32_t k,
                                         int largest, uint32_t *out_ids, float *out_scores,
                                         qamd_mem out_mem, void *stream);

@@ -709,7 +709,7 @@ qamd_status qamd_bin_encode(const float *data, qamd_mem data_mem, const qamd_vec
     const uint64_t dim = vp->dim, count = vp->count;
     if (count && dim) {
         // host rows are staged 256 MiB at a time; device rows are read in place, 8 GiB per launch
-        const uint64_t batch_bytes = data_mem == QAMD_MEM_HOST ? (256ull << 20) : (8ull << 30);
+        const uint64_t batch_bytes = stage_bytes(data_mem == QAMD_MEM_HOST ? (256ull << 20) : (8ull << 30));
         const uint64_t batch_rows = std::max<uint64_t>(1, std::min<uint64_t>(count, batch_bytes / (dim * 4)));
         DevBuf stage;
         if (data_mem == QAMD_MEM_HOST) QAMD_TRY(stage.alloc(batch_rows * dim * 4));
@@ -1992,8 +1992,9 @@ qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b
             sum += c;
             redo += status[q] != 0;
         }
-        fprintf(stderr, "[qamd bin topk_batch] Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, %u queries redone\n",
-                (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx, redo);
+        fprintf(stderr, "[qamd bin topk_batch] Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, filter %s, %u queries redone\n",
+                (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx,
+                rs4 ? "bin_gemm_rs4_kernel" : qs4 ? "bin_gemm_qs4_kernel" : "bin_gemm_rs_kernel", redo);
     }
     return QAMD_OK;
 }
@@ -2232,7 +2233,7 @@ qamd_status qamd_bin_encoder_push(qamd_bin_encoder *e, const float *batch, uint6
                     (unsigned long long)(e->pushed + n_rows), (unsigned long long)e->h->count);
     QAMD_ON_DEVICE(e->device);
     const uint64_t dim = e->h->vp.dim;
-    const uint64_t piece_rows = std::max<uint64_t>(1, (256ull << 20) / std::max<uint64_t>(dim * 4, 1));
+    const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / std::max<uint64_t>(dim * 4, 1));
     for (uint64_t r = 0; r < n_rows && dim; r += piece_rows) {
         const uint64_t nr = std::min(piece_rows, n_rows - r);
         const void *src = nullptr;

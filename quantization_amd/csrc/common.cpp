@@ -6,6 +6,7 @@
 #include <cerrno>
 #include <cmath>
 #include <cstdlib>
+#include <algorithm>
 #include <atomic>
 #include <fstream>
 #include <mutex>
@@ -435,6 +436,8 @@ const DeviceInfo &device_info() {
         hipDeviceProp_t p;
         if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
             info[dev].cu_count = p.multiProcessorCount;
+        static const uint64_t forced = dev_env_u64("QAMD_DEV_CU_COUNT", 0);  // developer: a partitioned device's count
+        if (forced) info[dev].cu_count = (int)std::min<uint64_t>(forced, 1024);
         known.fetch_or(1ull << dev, std::memory_order_acq_rel);
     }
     return info[dev];
@@ -565,3 +568,9 @@ int qamd_get_device(void) { return qamd::g_device; }
 
 void qamd_thread_release(void) { qamd::thread_release_all(); }
 }
+
+#ifdef QAMD_DEV
+// Developer-only (libquantization_amd_dev.so): the CU count every grid of the current device is sized by (QAMD_DEV_CU_COUNT
+// when set).
+extern "C" __attribute__((visibility("default"))) int qamd_dev_cu_count(void) { return qamd::device_info().cu_count; }
+#endif

@@ -74,6 +74,37 @@ inline const char *dev_env(const char *name) {
     return nullptr;
 #endif
 }
+// A positive integer from a developer variable, else `dflt` (unset, empty, zero or not a number).
+inline uint64_t dev_env_u64(const char *name, uint64_t dflt) {
+    const char *e = dev_env(name);
+    if (!e || !*e) return dflt;
+    char *end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    return (*end == 0 && v > 0) ? (uint64_t)v : dflt;
+}
+// Developer overrides of size gates, so that tests reach at small shapes the routes that only huge stores take.  Each is
+// read once per process; unset, the gate is the product's.
+//   QAMD_DEV_STAGE_BYTES     every host staging piece (256 MiB) and device batch (8 GiB) of the encoders, loads and exports
+//   QAMD_DEV_HOST_WHOLE=0    the one-shot u8 encoder never uploads host input whole (it stages it batch by batch)
+//   QAMD_DEV_PQ_PLANAR_ROWS  PQ stores of at least so many rows keep no planar scan image (2^28)
+//   QAMD_DEV_PQ_SKEW_ROWS    PQ stores of at least so many rows do not take pq_scan_skew_kernel (2^30)
+//   QAMD_DEV_CU_COUNT        device_info().cu_count (common.cpp): a partitioned device's CU count
+inline uint64_t stage_bytes(uint64_t dflt) {
+    static const uint64_t v = dev_env_u64("QAMD_DEV_STAGE_BYTES", 0);
+    return v ? v : dflt;
+}
+inline bool host_whole_allowed() {
+    static const bool on = [] { const char *e = dev_env("QAMD_DEV_HOST_WHOLE"); return !(e && e[0] == '0'); }();
+    return on;
+}
+inline uint64_t pq_planar_max_rows() {
+    static const uint64_t v = dev_env_u64("QAMD_DEV_PQ_PLANAR_ROWS", 1ull << 28);
+    return v;
+}
+inline uint64_t pq_skew_max_rows() {
+    static const uint64_t v = dev_env_u64("QAMD_DEV_PQ_SKEW_ROWS", 1ull << 30);
+    return v;
+}
 
 // One-time set-up per (call site, device) - hipFuncSetAttribute is a per-device property, and its first call also loads
 // the code object.  Two-phase: the device's bit is published only AFTER the set-up has succeeded; first callers that

@@ -1329,7 +1329,7 @@ void plan_slices(uint64_t m, std::vector<uint32_t> &chunk0, std::vector<uint32_t
 qamd_status alloc_store(qamd_pq *h) {
     h->m = chunks_of(h->vp.dim, h->chunk_size);
     plan_slices(h->m, h->slice_chunk0, h->slice_chunks);
-    if (h->count >= (1ull << 28)) h->slice_chunks.clear();  // (the partial sums leave through 32-bit buffer offsets)
+    if (h->count >= pq_planar_max_rows()) h->slice_chunks.clear();  // (the partial sums leave through 32-bit buffer offsets)
     const bool planar = !h->slice_chunks.empty();
     // rows of 16-byte pieces (the scan's load unit); tiny rows keep whole dwords; rows that pq_scan_fast_kernel scans in
     // slices (m > 144, not a multiple of 32) sit on a 128-byte pitch so that a slice launch reads whole lines
@@ -1421,7 +1421,7 @@ bool skew_sliced_capable(const qamd_pq *h) { return skew_enabled() && h->planar.
 // store rows per ring row: 1 for m = 32 / 64 / 96 / 128, 2 for m = 48 and m = 16; 0: not a shape of the kernel
 uint32_t skew_rows_per_ring_row(const qamd_pq *h) {
     // (scores leave through one buffer resource: 32-bit byte offsets)
-    if (!skew_enabled() || h->ds != h->m || h->count >= (1ull << 30)) return 0;
+    if (!skew_enabled() || h->ds != h->m || h->count >= pq_skew_max_rows()) return 0;
     if (h->m % 32 == 0 && h->m <= 128) return 1;
     return (h->m == 48 || h->m == 16) ? 2 : 0;
 }
@@ -1431,7 +1431,7 @@ uint32_t skew_rows_per_ring_row(const qamd_pq *h) {
 // 0: not such a shape (or one the kernel takes as it is); else the ring row's chunks, and *pad its bytes past ds.
 uint32_t skew_padded_ring(const qamd_pq *h, uint32_t *pad) {
     *pad = 0;
-    if (!skew_enabled() || h->count >= (1ull << 30) || h->m % 4 != 0 || h->ds % 16 != 0 || h->ds < 32 || h->ds > 128) return 0;
+    if (!skew_enabled() || h->count >= pq_skew_max_rows() || h->m % 4 != 0 || h->ds % 16 != 0 || h->ds < 32 || h->ds > 128) return 0;
     if (h->ds != round_up(h->m, 16)) return 0;
     const uint32_t ring = (uint32_t)round_up(h->ds, 32);
     if (ring == h->m || h->m == 48 || h->m == 16) return 0;  // whole ring rows, or two store rows per ring row
@@ -1719,7 +1719,7 @@ qamd_status encode_rows(qamd_pq *h, const float *data, qamd_mem data_mem, qamd_s
     const uint64_t dim = h->vp.dim, count = h->count;
     if (count == 0 || dim == 0) return QAMD_OK;
     // host rows are staged 256 MiB at a time; device rows are read in place, 8 GiB per launch
-    const uint64_t batch_bytes = data_mem == QAMD_MEM_HOST ? (256ull << 20) : (8ull << 30);
+    const uint64_t batch_bytes = stage_bytes(data_mem == QAMD_MEM_HOST ? (256ull << 20) : (8ull << 30));
     const uint64_t batch_rows = std::max<uint64_t>(1, std::min<uint64_t>(count, batch_bytes / (dim * 4)));
     DevBuf stage;
     if (data_mem == QAMD_MEM_HOST) QAMD_TRY(stage.alloc(batch_rows * dim * 4));
@@ -2414,7 +2414,7 @@ qamd_status qamd_pq_encoder_observe(qamd_pq_encoder *e, const float *batch, uint
         return fail(QAMD_ERR_ARGUMENTS, "Vector count %llu does not match vector parameters count %llu",
                     (unsigned long long)(e->observed + n_rows), (unsigned long long)count);
     QAMD_ON_DEVICE(e->device);
-    const uint64_t piece_rows = std::max<uint64_t>(1, (256ull << 20) / std::max<uint64_t>(dim * 4, 1));
+    const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / std::max<uint64_t>(dim * 4, 1));
     for (uint64_t r = 0; r < n_rows && dim && e->S; r += piece_rows) {
         const uint64_t nr = std::min(piece_rows, n_rows - r), base = e->observed + r;
         // sample slots whose row floor(k * count / S) falls into [base, base + nr)
@@ -2446,7 +2446,7 @@ qamd_status qamd_pq_encoder_push(qamd_pq_encoder *e, const float *batch, uint64_
     const uint64_t dim = h->vp.dim;
     if (dim && !e->pair_table.ptr && cs_fast_shape(dim, h->chunk_size))
         QAMD_TRY(build_pair_table(h->centroids.as<float>(), dim, h->chunk_size, h->m, e->pair_table, e->stream));
-    const uint64_t piece_rows = std::max<uint64_t>(1, (256ull << 20) / std::max<uint64_t>(dim * 4, 1));
+    const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / std::max<uint64_t>(dim * 4, 1));
     for (uint64_t r = 0; r < n_rows && dim; r += piece_rows) {
         const uint64_t nr = std::min(piece_rows, n_rows - r);
         const void *src = nullptr;

@@ -544,7 +544,7 @@ qamd_status fused_topk_batch(uint64_t n, uint32_t Q, uint32_t k, int largest, ui
         hipLaunchKernelGGL(sample_ids_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, sample_ids, S, n);
         std::vector<uint32_t> status(C);
         static const bool debug_topk = dev_env("QAMD_DEBUG_TOPK") != nullptr;
-        uint32_t dbg_min = ~0u, dbg_max = 0, dbg_redo = 0;
+        uint32_t dbg_min = ~0u, dbg_max = 0, dbg_redo = 0, dbg_side = 0, dbg_width = 0;  // side: filter launches of several queries
         uint64_t dbg_sum = 0;
         for (uint32_t q0 = 0; q0 < Q && st == QAMD_OK; q0 += C) {
             const uint32_t nq = std::min(C, Q - q0);
@@ -566,6 +566,10 @@ qamd_status fused_topk_batch(uint64_t n, uint32_t Q, uint32_t k, int largest, ui
                                         largest};
                     took = scan.scan_filter_multi(q0 + j, nq - j, sl, stream, st);
                     if (st != QAMD_OK) break;
+                    if (took > 0) {
+                        dbg_side++;
+                        dbg_width = std::max(dbg_width, took);
+                    }
                 }
                 if (took == 0) {
                     FusedState *fs = reinterpret_cast<FusedState *>(slice);
@@ -599,8 +603,8 @@ qamd_status fused_topk_batch(uint64_t n, uint32_t Q, uint32_t k, int largest, ui
                 if (status[j] != 0) st = classic(q0 + j);  // heavy ties or an unlucky pivot: exact path
         }
         if (debug_topk && st == QAMD_OK)
-            fprintf(stderr, "[qamd fused_topk_batch] Q=%u r=%u candidates min/mean/max = %u/%llu/%u, %u queries redone\n", Q, r,
-                    dbg_min, (unsigned long long)(dbg_sum / Q), dbg_max, dbg_redo);
+            fprintf(stderr, "[qamd fused_topk_batch] Q=%u r=%u candidates min/mean/max = %u/%llu/%u, side by side %u x %u, "
+                    "%u queries redone\n", Q, r, dbg_min, (unsigned long long)(dbg_sum / Q), dbg_max, dbg_side, dbg_width, dbg_redo);
     }
     if (scores) {
         thread_ws_release(WS_SCORES, stream);

@@ -1613,9 +1613,9 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
     if (data_mem == QAMD_MEM_HOST && !alpha_offset) {
         size_t free_b = 0, total_b = 0;
         const uint64_t bytes = count * dim * sizeof(float);
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes <= free_b / 4) {
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes <= free_b / 4 && host_whole_allowed()) {
             QAMD_TRY(whole.alloc(bytes, s));
-            const uint64_t piece = 256ull << 20;
+            const uint64_t piece = stage_bytes(256ull << 20);
             for (uint64_t off = 0; off < bytes; off += piece) {
                 if (stop && stop(stop_user)) return fail(QAMD_ERR_STOPPED, "Stopped");
                 QAMD_TRY(copy_in(static_cast<char *>(whole.ptr) + off, reinterpret_cast<const char *>(data) + off,
@@ -1628,7 +1628,7 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
 
     // Source rows: device-resident rows are processed in place (large batches: the stop
     // callback is polled between them), host rows are staged in bounded 256 MiB batches.
-    const uint64_t batch_bytes = data_mem == QAMD_MEM_HOST ? (256ull << 20) : (8ull << 30);
+    const uint64_t batch_bytes = stage_bytes(data_mem == QAMD_MEM_HOST ? (256ull << 20) : (8ull << 30));
     const uint64_t batch_rows = std::max<uint64_t>(1, std::min<uint64_t>(count, batch_bytes / (dim * 4 + 1)));
     DevBuf stage;
     if (data_mem == QAMD_MEM_HOST) QAMD_TRY(stage.alloc(batch_rows * dim * sizeof(float)));
@@ -1708,7 +1708,7 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
     QAMD_TRY(alloc_store(h.get()));
     const uint64_t stride = meta->actual_dim + 4;
     const uint32_t row_dwords = (uint32_t)(stride / 4);
-    const uint64_t batch_rows = std::max<uint64_t>(1, (256ull << 20) / stride);
+    const uint64_t batch_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / stride);
     DevBuf stage;
     if (rows_mem == QAMD_MEM_HOST && vp.count)
         QAMD_TRY(stage.alloc(std::min<uint64_t>(batch_rows, vp.count) * stride));
@@ -1746,7 +1746,7 @@ qamd_status qamd_u8_export_rows_range(const qamd_u8 *h, uint64_t first_row, uint
     hipStream_t s = as_stream(stream);
     const uint64_t stride = h->meta.actual_dim + 4;
     const uint32_t row_dwords = (uint32_t)(stride / 4);
-    const uint64_t batch_rows = std::max<uint64_t>(1, (256ull << 20) / stride);
+    const uint64_t batch_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / stride);
     DevBuf stage;
     if (rows_mem == QAMD_MEM_HOST) QAMD_TRY(stage.alloc(std::min<uint64_t>(batch_rows, n_rows) * stride));
     for (uint64_t r0 = 0; r0 < n_rows; r0 += batch_rows) {
@@ -2188,7 +2188,7 @@ qamd_status qamd_u8_encoder_observe(qamd_u8_encoder *e, const float *batch, uint
         e->observed += n_rows;
         return QAMD_OK;
     }
-    const uint64_t piece_rows = std::max<uint64_t>(1, kStagePieceBytes / (dim * 4));
+    const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(kStagePieceBytes) / (dim * 4));
     for (uint64_t r = 0; r < n_rows; r += piece_rows) {
         const uint64_t nr = std::min(piece_rows, n_rows - r);
         const void *src = nullptr;
@@ -2221,7 +2221,7 @@ qamd_status qamd_u8_encoder_push(qamd_u8_encoder *e, const float *batch, uint64_
     QAMD_ON_DEVICE(e->device);
     QAMD_TRY(encoder_close_pass1(e));
     const uint64_t dim = e->vp.dim;
-    const uint64_t piece_rows = std::max<uint64_t>(1, kStagePieceBytes / (dim * 4 + 1));
+    const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(kStagePieceBytes) / (dim * 4 + 1));
     for (uint64_t r = 0; r < n_rows; r += piece_rows) {
         const uint64_t nr = std::min(piece_rows, n_rows - r);
         const void *src = nullptr;
@@ -2272,7 +2272,7 @@ qamd_status u8_minmax_range(const float *data, qamd_mem mem, uint64_t n_rows, ui
     MinMaxAcc acc;
     QAMD_TRY(acc.init(s));
     DevBuf stage;
-    const uint64_t piece_rows = std::max<uint64_t>(1, kStagePieceBytes / std::max<uint64_t>(dim * 4, 1));
+    const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(kStagePieceBytes) / std::max<uint64_t>(dim * 4, 1));
     for (uint64_t r = 0; r < n_rows && dim; r += piece_rows) {
         const uint64_t nr = std::min(piece_rows, n_rows - r);
         const void *src = nullptr;

@@ -2797,6 +2797,21 @@ bool rs_selected(const qamd_u8 *h, const qamd_u8_query_batch *b, bool filter_mod
     return tiles == 1 || (mi == 4 && !qs_selected(h, b, filter_mode));
 }
 
+// The kernel of launch_gemm<1 / 2> on the whole store (what the QAMD_DEBUG_TOPK line of topk_batch names): launch_gemm's dispatch.
+const char *filter_kernel_name(const qamd_u8 *h, const qamd_u8_query_batch *b) {
+    if (qs_selected(h, b, true)) {
+        if (rq_selected(h, b)) {
+            static const char *ek = dev_env("QAMD_RQ_K");
+            return h->meta.actual_dim == 768 && !(ek && ek[0] == '0') ? "u8_gemm_rk16_kernel" : "u8_gemm_rq16_kernel";
+        }
+        if (qr_selected(h, b, true)) return "u8_gemm_qr16_kernel";
+        return b->frag16 ? "u8_gemm_qs16_kernel" : "u8_gemm_qs_kernel";
+    }
+    if (rs_selected(h, b, true)) return "u8_gemm_rs_kernel";
+    if (pp_selected(h, b, true)) return "u8_gemm_pp_kernel";
+    return "u8_gemm_kernel";
+}
+
 template <int MODE>
 qamd_status launch_gemm(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
                         const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
@@ -3153,8 +3168,8 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
                 sum += c;
                 redo += status[q];
             }
-            fprintf(stderr, "[qamd topk_batch] Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, %u queries redone\n",
-                    (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx, redo);
+            fprintf(stderr, "[qamd topk_batch] Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, filter %s, %u queries redone\n",
+                    (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx, filter_kernel_name(h, b), redo);
         }
     }
     // Queries not served by the fused pass (small stores, overflowed lists): exact single-query path.
