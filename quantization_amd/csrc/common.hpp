@@ -89,12 +89,17 @@ inline uint64_t dev_env_u64(const char *name, uint64_t dflt) {
 //   QAMD_DEV_PQ_PLANAR_ROWS  PQ stores of at least so many rows keep no planar scan image (2^28)
 //   QAMD_DEV_PQ_SKEW_ROWS    PQ stores of at least so many rows do not take pq_scan_skew_kernel (2^30)
 //   QAMD_DEV_CU_COUNT        device_info().cu_count (common.cpp): a partitioned device's CU count
+//   QAMD_DEV_U8_PACKED=0     u8 stores get no packed scan image (u8.hip build_packed): their scans read the byte codes
 inline uint64_t stage_bytes(uint64_t dflt) {
     static const uint64_t v = dev_env_u64("QAMD_DEV_STAGE_BYTES", 0);
     return v ? v : dflt;
 }
 inline bool host_whole_allowed() {
     static const bool on = [] { const char *e = dev_env("QAMD_DEV_HOST_WHOLE"); return !(e && e[0] == '0'); }();
+    return on;
+}
+inline bool u8_packed_allowed() {
+    static const bool on = [] { const char *e = dev_env("QAMD_DEV_U8_PACKED"); return !(e && e[0] == '0'); }();
     return on;
 }
 inline uint64_t pq_planar_max_rows() {

@@ -7,7 +7,9 @@
 // with stride actual_dim+4 (772 B at dim 768: only 4-byte aligned).  On device it is split
 // into  codes[count_padded][actual_dim]  (rows 16-byte aligned, contiguous) and
 // offsets[count] f32.  Same 772 algorithmic bytes per scored row; every code load is an
-// aligned 16-byte `global_load_dwordx4`.
+// aligned 16-byte `global_load_dwordx4`.  Dot / L2 stores also keep a packed scan image of the
+// codes at 7 bits each (u8_internal.hpp, build_packed), which their single-query scans read:
+// 676 instead of 772 bytes per row at dim 768.
 //
 // Scan mapping (HBM-bound integer work, no MFMA): a row is read by G = min(16, pow2(chunks))
 // adjacent lanes, 16 B per lane per iteration, so one wave-load covers 64/G consecutive rows
@@ -172,11 +174,20 @@ __device__ __forceinline__ uint32_t f32x4_to_u8x4_fast(const float4 &f, float al
 // unconditional (clamped address + select) so that they still issue back to back.
 // FILTER: fused top-k mode — no score is written; rows at least as good as the pivot are
 // appended to the candidate buffer (topk_device.hpp).
-template <int G, int ITERS, int UNROLL, bool IS_L1, bool EXACT, bool FILTER>
+// PACKED: `codes` is the store's packed scan image (u8_internal.hpp, build_packed): row_chunks
+// chunks per row, each with 16 codes in bits 0..6 and, in bit 7, bit plane b = c % 7 of the
+// 16 codes of extra chunk row_chunks + c / 7 (c < 7 * n_extra).  The lane that loads chunk c
+// also holds query chunks c and row_chunks + c / 7, so the pair sum needs no cross-lane unpack:
+//   dot(v & 0x7F.., q_c) + (dot(v & 0x80.., q_extra) >> 7) << b
+// (the second dot is a multiple of 128, so `>> (7 - b)` is the same number).  Same exact
+// integer sum as the byte codes, added in another order.  Dot / L2 only (SAD is not linear
+// in the bit planes).  At dim 768 a 16-row tile of 672-byte rows is 84 whole 128-byte lines.
+template <int G, int ITERS, int UNROLL, bool IS_L1, bool EXACT, bool FILTER, bool PACKED = false>
 __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
     const uint4 *__restrict__ codes, const float *__restrict__ offsets,
     const uint4 *__restrict__ qcodes, const float *__restrict__ q_off_p, float multiplier,
-    uint32_t n_rows, uint32_t row_chunks, float *__restrict__ out, TopkFilter filt) {
+    uint32_t n_rows, uint32_t row_chunks, uint32_t n_extra, float *__restrict__ out, TopkFilter filt) {
+    static_assert(!(PACKED && IS_L1), "the packed image serves Dot and L2 only");
     constexpr int RW = 64 / G;
     constexpr int TILE = RW * UNROLL;
     const int lane = threadIdx.x & 63;
@@ -196,6 +207,9 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
             const uint32_t c = sub + it * G;
             if (EXACT) {
                 v[u][it] = ld_nt(p + c);
+            } else if (PACKED) {  // past the row end the query chunks are zero: the clamped chunk adds nothing
+                // row_chunks > G * (ITERS - 1): only the last piece can be past the row end
+                v[u][it] = ld_nt(p + (it < ITERS - 1 || c < row_chunks ? c : row_chunks - 1));
             } else {
                 const uint32_t cc = c < row_chunks ? c : row_chunks - 1;
                 uint4 t = ld_nt(p + cc);
@@ -216,6 +230,18 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
             q[it] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);
         }
     }
+    uint4 qx[PACKED ? ITERS : 1];  // the query chunk whose bit plane rides in bit 7 of chunk c
+    uint32_t qsh[PACKED ? ITERS : 1];  // 7 - that plane
+    if (PACKED) {
+#pragma unroll
+        for (int it = 0; it < ITERS; it++) {
+            const uint32_t c = sub + it * G, e = c / 7;
+            const bool has = c < 7 * n_extra;  // implies c < row_chunks
+            const uint4 t = qcodes[has ? row_chunks + e : 0];
+            qx[it] = make_uint4(has ? t.x : 0, has ? t.y : 0, has ? t.z : 0, has ? t.w : 0);
+            qsh[it] = 7 - (c - 7 * e);
+        }
+    }
     const float q_off = *q_off_p;
     // Score stores: lane (rslot, sub = u % G) keeps row u's score, so that each group of G
     // tiles rows leaves the wave as ONE store of (64/G)*G = 64 consecutive floats at most —
@@ -233,8 +259,17 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
     for (int u = 0; u < UNROLL; u++) {
         uint32_t acc = 0;
 #pragma unroll
-        for (int it = 0; it < ITERS; it++)
-            acc = IS_L1 ? sad16(v[u][it], q[it], acc) : dot16(v[u][it], q[it], acc);
+        for (int it = 0; it < ITERS; it++) {
+            if (PACKED) {
+                const uint4 &w = v[u][it];
+                const uint32_t hi = dot16(make_uint4(w.x & 0x80808080u, w.y & 0x80808080u, w.z & 0x80808080u,
+                                                     w.w & 0x80808080u), qx[it], 0);
+                acc = dot16(make_uint4(w.x & 0x7F7F7F7Fu, w.y & 0x7F7F7F7Fu, w.z & 0x7F7F7F7Fu, w.w & 0x7F7F7F7Fu),
+                            q[it], acc) + (hi >> qsh[it]);
+            } else {
+                acc = IS_L1 ? sad16(v[u][it], q[it], acc) : dot16(v[u][it], q[it], acc);
+            }
+        }
         acc = group_sum<G>(acc);
         if (sub == (u % G)) mine = epilogue(multiplier, acc, q_off, v_off[u / G], 0.0f, EPI_POINT);
         if ((u % G) == G - 1 || u == UNROLL - 1) {
@@ -1024,6 +1059,35 @@ __global__ __launch_bounds__(kBlock) void join_rows_kernel(const uint32_t *__res
     }
 }
 
+// The packed scan image (u8_internal.hpp) of rows [0, n_rows): one thread per (row, packed chunk j).  Chunk j keeps
+// chunk j's codes in bits 0..6 and bit plane j % 7 of chunk P + j / 7 in bit 7.  A code above 127 anywhere in the rows
+// (bytes another producer wrote: from_rows, load) sets *bad, and the image is then dropped.
+__global__ __launch_bounds__(kBlock) void u8_pack7_kernel(const uint4 *__restrict__ codes, uint64_t n_rows,
+                                                          uint32_t row_chunks, uint32_t pchunks, uint32_t n_extra,
+                                                          uint4 *__restrict__ packed, uint32_t *__restrict__ bad) {
+    const uint64_t total = n_rows * pchunks, stride = (uint64_t)gridDim.x * kBlock;
+    uint32_t high = 0;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
+        const uint64_t r = t / pchunks;
+        const uint32_t j = (uint32_t)(t - r * pchunks);
+        const uint4 *row = codes + r * row_chunks;
+        const uint4 a = row[j];
+        uint32_t w[4] = {a.x & 0x7F7F7F7Fu, a.y & 0x7F7F7F7Fu, a.z & 0x7F7F7F7Fu, a.w & 0x7F7F7F7Fu};
+        high |= a.x | a.y | a.z | a.w;
+        if (j < 7 * n_extra) {
+            const uint4 x = row[pchunks + j / 7];
+            const uint32_t b = j % 7;
+            high |= x.x | x.y | x.z | x.w;
+            w[0] |= ((x.x >> b) & 0x01010101u) << 7;
+            w[1] |= ((x.y >> b) & 0x01010101u) << 7;
+            w[2] |= ((x.z >> b) & 0x01010101u) << 7;
+            w[3] |= ((x.w >> b) & 0x01010101u) << 7;
+        }
+        packed[t] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    if (high & 0x80808080u) atomicOr(bad, 1u);
+}
+
 int grid_for(uint64_t work_items, uint64_t per_block, int blocks_per_cu) {
     uint64_t want = (work_items + per_block - 1) / per_block;
     uint64_t cap = (uint64_t)device_info().cu_count * blocks_per_cu;
@@ -1055,48 +1119,103 @@ qamd_status alloc_store(qamd_u8 *h) {
     return QAMD_OK;
 }
 
+// Builds the store's packed scan image (u8_internal.hpp) from its byte codes; run at the end of every builder.  Only
+// the Dot / L2 scans of lane mode 0 read it, so L1 stores, stores of fewer than 8 chunks (no whole extra chunk) and of
+// more than 128 (the generic kernel) get none.  It costs 7/8 of the code bytes in HBM: it is skipped when it would
+// leave less free HBM than its own size, and a failed allocation only leaves the store on its byte codes.  So does
+// a code above 127 (rows another producer wrote).
+qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
+    h->packed.release();
+    h->packed_chunks = 0;
+    const uint32_t rc = h->row_chunks, n_extra = rc / 8, pchunks = rc - n_extra;
+    if (!u8_packed_allowed() || h->count == 0 || rc < 8 || rc > 128 ||
+        h->meta.vector_parameters.distance_type == QAMD_L1)
+        return QAMD_OK;
+    const uint64_t bytes = h->padded_rows * pchunks * 16;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 2 * bytes) {
+        (void)hipGetLastError();
+        return QAMD_OK;
+    }
+    DevBuf img, bad;
+    const std::string err = last_error();
+    if (img.alloc_zero_tail(bytes, h->count * pchunks * 16) != QAMD_OK || bad.alloc(sizeof(uint32_t), true) != QAMD_OK) {
+        (void)hipGetLastError();  // an out-of-memory here is not the build's failure
+        last_error() = err;
+        return QAMD_OK;
+    }
+    hipLaunchKernelGGL(u8_pack7_kernel, dim3(grid_for(h->count * pchunks, kBlock, 8)), dim3(kBlock), 0, s,
+                       h->codes.as<uint4>(), h->count, rc, pchunks, n_extra, img.as<uint4>(), bad.as<uint32_t>());
+    QAMD_HIP(hipGetLastError());
+    uint32_t high = 0;
+    QAMD_HIP(hipMemcpyAsync(&high, bad.ptr, sizeof(high), hipMemcpyDeviceToHost, s));
+    QAMD_HIP(hipStreamSynchronize(s));
+    if (high) return QAMD_OK;
+    h->packed = std::move(img);
+    h->packed_chunks = pchunks;
+    return QAMD_OK;
+}
+
 template <bool IS_L1> struct ScanLaunch {
+    // packed: the scan reads the packed image (Dot / L2 only); chunks = its chunks per row, else row_chunks.
     template <int G, int ITERS, int UNROLL>
-    static void go(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
-                   hipStream_t s) {
+    static void go(const qamd_u8 *h, bool packed, uint32_t chunks, const uint4 *qc, const float *qo, float *out,
+                   const TopkFilter *filt, hipStream_t s) {
         constexpr int TILE = (64 / G) * UNROLL;
         const uint64_t waves = (h->count + TILE - 1) / TILE;  // one wave per tile
         const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
-        const bool exact = h->row_chunks == (uint32_t)(G * ITERS);
-#define QAMD_U8_GO(EX, FI)                                                                                  \
-    hipLaunchKernelGGL((u8_scan_kernel<G, ITERS, UNROLL, IS_L1, EX, FI>), dim3(grid), dim3(kScanBlock), 0, s, \
-                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,            \
-                       (uint32_t)h->count, h->row_chunks, out, filt ? *filt : TopkFilter{})
+        const bool exact = chunks == (uint32_t)(G * ITERS);
+        const uint4 *codes = packed ? h->packed.as<uint4>() : h->codes.as<uint4>();
+        const uint32_t n_extra = h->row_chunks - chunks;
+#define QAMD_U8_GO(EX, FI, PK)                                                                                  \
+    hipLaunchKernelGGL((u8_scan_kernel<G, ITERS, UNROLL, IS_L1, EX, FI, PK>), dim3(grid),                      \
+                       dim3(kScanBlock), 0, s, codes, h->offsets.as<float>(), qc, qo, h->meta.multiplier,          \
+                       (uint32_t)h->count, chunks, n_extra, out, filt ? *filt : TopkFilter{})
+        if constexpr (!IS_L1) {
+            if (packed) {
+                if (filt) {
+                    if (exact) QAMD_U8_GO(true, true, true);
+                    else QAMD_U8_GO(false, true, true);
+                } else {
+                    if (exact) QAMD_U8_GO(true, false, true);
+                    else QAMD_U8_GO(false, false, true);
+                }
+                return;
+            }
+        }
         if (filt) {
-            if (exact) QAMD_U8_GO(true, true);
-            else QAMD_U8_GO(false, true);
+            if (exact) QAMD_U8_GO(true, true, false);
+            else QAMD_U8_GO(false, true, false);
         } else {
-            if (exact) QAMD_U8_GO(true, false);
-            else QAMD_U8_GO(false, false);
+            if (exact) QAMD_U8_GO(true, false, false);
+            else QAMD_U8_GO(false, false, false);
         }
 #undef QAMD_U8_GO
     }
 };
 
 // Returns false when the store's row size has no templated kernel (caller uses the generic one).
+// The Dot / L2 scans read the packed image when the store has one (its rows are 7/8 as long).
 template <bool IS_L1>
 bool launch_scan(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
                  hipStream_t s) {
     using L = ScanLaunch<IS_L1>;
-    const uint32_t rc = h->row_chunks;
-    if (rc == 1) return L::template go<1, 1, 4>(h, qc, qo, out, filt, s), true;
-    if (rc == 2) return L::template go<2, 1, 4>(h, qc, qo, out, filt, s), true;
-    if (rc <= 4) return L::template go<4, 1, 8>(h, qc, qo, out, filt, s), true;
-    if (rc <= 8) return L::template go<8, 1, 8>(h, qc, qo, out, filt, s), true;
+    const bool packed = !IS_L1 && h->packed_chunks != 0;
+    const uint32_t rc = packed ? h->packed_chunks : h->row_chunks;
+    h->last_scan_packed.store(packed ? 1 : 0, std::memory_order_relaxed);
+    if (rc == 1) return L::template go<1, 1, 4>(h, packed, rc, qc, qo, out, filt, s), true;
+    if (rc == 2) return L::template go<2, 1, 4>(h, packed, rc, qc, qo, out, filt, s), true;
+    if (rc <= 4) return L::template go<4, 1, 8>(h, packed, rc, qc, qo, out, filt, s), true;
+    if (rc <= 8) return L::template go<8, 1, 8>(h, packed, rc, qc, qo, out, filt, s), true;
     switch ((rc + 15) / 16) {
-        case 1: return L::template go<16, 1, 8>(h, qc, qo, out, filt, s), true;
-        case 2: return L::template go<16, 2, 4>(h, qc, qo, out, filt, s), true;
-        case 3: return L::template go<16, 3, 4>(h, qc, qo, out, filt, s), true;
-        case 4: return L::template go<16, 4, 2>(h, qc, qo, out, filt, s), true;
-        case 5: return L::template go<16, 5, 2>(h, qc, qo, out, filt, s), true;
-        case 6: return L::template go<16, 6, 2>(h, qc, qo, out, filt, s), true;
-        case 7: return L::template go<16, 7, 2>(h, qc, qo, out, filt, s), true;
-        case 8: return L::template go<16, 8, 2>(h, qc, qo, out, filt, s), true;
+        case 1: return L::template go<16, 1, 8>(h, packed, rc, qc, qo, out, filt, s), true;
+        case 2: return L::template go<16, 2, 4>(h, packed, rc, qc, qo, out, filt, s), true;
+        case 3: return L::template go<16, 3, 4>(h, packed, rc, qc, qo, out, filt, s), true;
+        case 4: return L::template go<16, 4, 2>(h, packed, rc, qc, qo, out, filt, s), true;
+        case 5: return L::template go<16, 5, 2>(h, packed, rc, qc, qo, out, filt, s), true;
+        case 6: return L::template go<16, 6, 2>(h, packed, rc, qc, qo, out, filt, s), true;
+        case 7: return L::template go<16, 7, 2>(h, packed, rc, qc, qo, out, filt, s), true;
+        case 8: return L::template go<16, 8, 2>(h, packed, rc, qc, qo, out, filt, s), true;
         default: break;
     }
     return false;
@@ -1153,6 +1272,7 @@ qamd_status launch_small(const qamd_u8 *h, const uint4 *qc, const float *qo, con
                          const SmallTopk &p, hipStream_t s) {
     using L = SmallLaunch<IS_L1>;
     const uint32_t rc = h->row_chunks;
+    h->last_scan_packed.store(0, std::memory_order_relaxed);
     if (rc == 1) return L::template go<1, 1>(h, qc, qo, fq, pl, p, s);
     if (rc == 2) return L::template go<2, 1>(h, qc, qo, fq, pl, p, s);
     if (rc <= 4) return L::template go<4, 1>(h, qc, qo, fq, pl, p, s);
@@ -1179,6 +1299,7 @@ void launch_multi_shape(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitc
     const uint64_t waves = (h->count + TILE - 1) / TILE;
     const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
     const bool exact = h->row_chunks == (uint32_t)(G * ITERS);
+    h->last_scan_packed.store(0, std::memory_order_relaxed);
 #define QAMD_U8_MULTI(EX, FI)                                                                                      \
     hipLaunchKernelGGL((u8_scan_multi_kernel<G, ITERS, UNROLL, NQ, IS_L1, EX, FI>), dim3(grid), dim3(kScanBlock), 0, s, \
                        h->codes.as<uint4>(), h->offsets.as<float>(), qcodes, (uint32_t)q_pitch, q_offs, nq_valid,   \
@@ -1258,6 +1379,7 @@ qamd_status scan_ptrs(const qamd_u8 *h, const uint4 *qc, const float *qo, float 
                       const TopkFilter *filt = nullptr) {
     if (h->count == 0) return QAMD_OK;
     const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
+    h->last_scan_packed.store(0, std::memory_order_relaxed);  // launch_scan reports the packed image
     if (lane_order(h)) {
         uint64_t waves = (h->count + 3) / 4;
         unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
@@ -1686,6 +1808,7 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
     h->meta.alpha = alpha;
     h->meta.offset = offset;
     h->meta.multiplier = host_multiplier(alpha, vp->distance_type, vp->invert);
+    QAMD_TRY(build_packed(h.get(), s));
     *out = h.release();
     return QAMD_OK;
 }
@@ -1727,6 +1850,7 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
         if (rows_mem == QAMD_MEM_HOST) QAMD_HIP(hipStreamSynchronize(s));
     }
     QAMD_HIP(hipStreamSynchronize(s));
+    QAMD_TRY(build_packed(h.get(), s));
     *out = h.release();
     return QAMD_OK;
 }
@@ -2250,6 +2374,7 @@ qamd_status qamd_u8_encoder_finish(qamd_u8_encoder *e, qamd_u8 **out) {
         e->h->meta.offset = e->offset;
         e->h->meta.multiplier = host_multiplier(e->alpha, e->vp.distance_type, e->vp.invert);
     }
+    QAMD_TRY(build_packed(e->h.get(), e->stream));
     *out = e->h.release();
     return QAMD_OK;
 }
@@ -2458,5 +2583,14 @@ extern "C" __attribute__((visibility("default"))) void qamd_dev_u8_ptrs(const qa
 }
 extern "C" __attribute__((visibility("default"))) const void *qamd_dev_u8_query_ptr(const qamd_u8_query *q) {
     return q->buf.ptr;
+}
+// The packed scan image (nullptr, 0 chunks: none) and which image the store's last scan launch read (1: packed).
+extern "C" __attribute__((visibility("default"))) void qamd_dev_u8_packed(const qamd_u8 *h, const void **packed,
+                                                                          uint32_t *chunks) {
+    *packed = h->packed.ptr;
+    *chunks = h->packed_chunks;
+}
+extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_packed(const qamd_u8 *h) {
+    return h->last_scan_packed.load(std::memory_order_relaxed);
 }
 #endif
