@@ -536,46 +536,13 @@ qamd_status pairs_launch(const qamd_bin *h, const uint32_t *q_single, const uint
     return QAMD_OK;
 }
 
-// out[k] = metric(query bit row `qbits`, row ids[k]) for host or device ids / outputs: the body of
-// score_ids and, with qbits = stored row i, of score_internal_ids.
+// out[k] = metric(query bit row `qbits`, row ids[k]) for host or device ids / outputs (run_ids, lists.hpp): the body
+// of score_ids and, with qbits = stored row i, of score_internal_ids.
 qamd_status score_ids_any(const qamd_bin *h, const uint32_t *qbits, const uint32_t *ids, uint64_t n_ids, qamd_mem ids_mem,
                           float *out, qamd_mem out_mem, hipStream_t s) {
-    DevBuf ids_tmp, out_tmp;
-    const uint32_t *ids_dev = ids;
-    // per-pair granularity (score_point and friends): ids and results through the calling
-    // thread's mapped host scratch -- no allocation, no copy calls
-    const HostScratch hs = (ids_mem == QAMD_MEM_HOST && out_mem == QAMD_MEM_HOST && n_ids <= 1024) ? host_scratch()
-                                                                                                  : HostScratch{};
-    if (hs.host) {
-        for (uint64_t k = 0; k < n_ids; k++) {
-            if (ids[k] >= h->count)
-                return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", ids[k],
-                            (unsigned long long)h->count);
-            hs.host[k] = ids[k];
-        }
-        QAMD_TRY(pairs_launch(h, qbits, nullptr, 0, nullptr, 0, nullptr, hs.dev, n_ids, reinterpret_cast<float *>(hs.dev + 1024), s));
-        QAMD_HIP(hipStreamSynchronize(s));
-        memcpy(out, hs.host + 1024, n_ids * 4);
-        return QAMD_OK;
-    }
-    if (ids_mem == QAMD_MEM_HOST) {
-        for (uint64_t k = 0; k < n_ids; k++)
-            if (ids[k] >= h->count)
-                return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", ids[k],
-                            (unsigned long long)h->count);
-        QAMD_TRY(ids_tmp.alloc(n_ids * 4));
-        QAMD_TRY(copy_in(ids_tmp.ptr, ids, QAMD_MEM_HOST, n_ids * 4, s));
-        ids_dev = ids_tmp.as<uint32_t>();
-    }
-    float *out_dev = out;
-    if (out_mem == QAMD_MEM_HOST) {
-        QAMD_TRY(out_tmp.alloc(n_ids * 4));
-        out_dev = out_tmp.as<float>();
-    }
-    QAMD_TRY(pairs_launch(h, qbits, nullptr, 0, nullptr, 0, nullptr, ids_dev, n_ids, out_dev, s));
-    if (out_mem == QAMD_MEM_HOST) QAMD_TRY(copy_out(out, QAMD_MEM_HOST, out_dev, n_ids * 4, s));
-    else if (ids_mem == QAMD_MEM_HOST) QAMD_HIP(hipStreamSynchronize(s));
-    return QAMD_OK;
+    return run_ids(ids, n_ids, ids_mem, out, out_mem, h->count, s, [&](const uint32_t *ids_dev, uint64_t n, float *out_dev) {
+        return pairs_launch(h, qbits, nullptr, 0, nullptr, 0, nullptr, ids_dev, n, out_dev, s);
+    });
 }
 
 bool fused_capable(const qamd_bin *h) { return h->ds % 16 == 0 && h->ds / 16 <= 64; }
@@ -755,9 +722,7 @@ qamd_status qamd_bin_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qam
 qamd_status qamd_bin_export_rows_range(const qamd_bin *h, uint64_t first_row, uint64_t n_rows, uint8_t *rows,
                                        qamd_mem rows_mem, void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
-    if (first_row > h->count || n_rows > h->count - first_row)
-        return fail(QAMD_ERR_OUT_OF_RANGE, "rows [%llu, +%llu) out of range (count %llu)", (unsigned long long)first_row,
-                    (unsigned long long)n_rows, (unsigned long long)h->count);
+    QAMD_TRY(check_row_range(first_row, n_rows, h->count));
     if (n_rows == 0 || h->nb == 0) return QAMD_OK;
     if (!rows) return fail(QAMD_ERR_ARGUMENTS, "rows is null");
     QAMD_ON_DEVICE(h->device);
@@ -782,13 +747,10 @@ qamd_status qamd_bin_export_rows(const qamd_bin *h, uint8_t *rows, qamd_mem rows
 qamd_status qamd_bin_save(const qamd_bin *h, const char *data_path, const char *meta_path) {
     if (!h || !data_path || !meta_path) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     std::string js = "{\"vector_parameters\":" + vector_parameters_json(h->vp) + "}";
-    make_parent_dirs(meta_path);
-    if (!write_file(meta_path, js.data(), js.size())) return fail(QAMD_ERR_IO, "cannot write %s", meta_path);
+    QAMD_TRY(save_file(meta_path, js.data(), js.size()));
     std::vector<uint8_t> rows(h->count * h->nb);
     QAMD_TRY(qamd_bin_export_rows(h, rows.data(), QAMD_MEM_HOST, nullptr));
-    make_parent_dirs(data_path);
-    if (!write_file(data_path, rows.data(), rows.size())) return fail(QAMD_ERR_IO, "cannot write %s", data_path);
-    return QAMD_OK;
+    return save_file(data_path, rows.data(), rows.size());
 }
 
 qamd_status qamd_bin_load(const char *data_path, const char *meta_path, const qamd_vector_parameters *vp,
@@ -803,11 +765,7 @@ qamd_status qamd_bin_load(const char *data_path, const char *meta_path, const qa
         if (!vpj || !parse_vector_parameters(*vpj, file_vp, err)) return fail(QAMD_ERR_IO, "%s: %s", meta_path, err.c_str());
     }
     std::string bytes;
-    if (!read_file(data_path, bytes)) return fail(QAMD_ERR_IO, "cannot read %s", data_path);
-    const uint64_t expected = row_bytes_of(vp->dim, store) * vp->count;  // :277-279
-    if (bytes.size() != expected)
-        return fail(QAMD_ERR_IO, "Loaded storage size %zu is not equal to expected size %llu", bytes.size(),
-                    (unsigned long long)expected);
+    QAMD_TRY(load_rows_file(data_path, row_bytes_of(vp->dim, store) * vp->count, bytes));  // :277-279
     qamd_vector_parameters eff = file_vp;  // metadata rules the metric, the caller's params the sizes
     eff.dim = vp->dim;
     eff.count = vp->count;
@@ -874,12 +832,7 @@ qamd_status qamd_bin_score_all(const qamd_bin *h, const qamd_bin_query *q, float
     hipStream_t s = as_stream(stream);
     QAMD_TRY(q->ready.wait(s));
     if (out_mem == QAMD_MEM_DEVICE) return scan_into(h, q, out, s);
-    float *tmp = nullptr;  // per-thread workspace: no hipMalloc / hipFree per query
-    QAMD_TRY(thread_ws_acquire(WS_SCORES, h->count * 4, s, reinterpret_cast<void **>(&tmp)));
-    qamd_status st = scan_into(h, q, tmp, s);
-    if (st == QAMD_OK) st = copy_out(out, QAMD_MEM_HOST, tmp, h->count * 4, s);
-    thread_ws_release(WS_SCORES, s, st == QAMD_OK);  // the download synchronised the stream
-    return st;
+    return score_all_to_host(h->count, out, s, [&](float *scores) { return scan_into(h, q, scores, s); });
 }
 
 qamd_status qamd_bin_score_ids(const qamd_bin *h, const qamd_bin_query *q, const uint32_t *ids, uint64_t n_ids,
@@ -931,9 +884,8 @@ qamd_status qamd_bin_score_internal_ids_batch(const qamd_bin *h, const uint32_t 
 qamd_status qamd_bin_topk(const qamd_bin *h, const qamd_bin_query *q, uint32_t k, int largest, uint32_t *out_ids,
                           float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(check_query(h, q));
-    if (k == 0) return QAMD_OK;
-    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
-    if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
+    qamd_status args = QAMD_OK;
+    if (!topk_wanted(k, 1, out_ids, out_scores, args)) return args;
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     QAMD_TRY(q->ready.wait(s));
@@ -942,12 +894,8 @@ qamd_status qamd_bin_topk(const qamd_bin *h, const qamd_bin_query *q, uint32_t k
         if (bin_topk_small(h, q->buf.ptr, k, largest, out_ids, out_scores, out_mem, s, st)) return st;
     }
     if (!fused_capable(h)) {
-        float *scores = nullptr;
-        QAMD_TRY(thread_ws_acquire(WS_SCORES, std::max<uint64_t>(h->count, 1) * 4, s, reinterpret_cast<void **>(&scores)));
-        qamd_status st = scan_into(h, q, scores, s);
-        if (st == QAMD_OK) st = topk_finish(scores, h->count, k, largest, out_ids, out_scores, out_mem, s);
-        thread_ws_release(WS_SCORES, s);
-        return st;
+        return topk_classic(h->count, k, largest, out_ids, out_scores, out_mem, s,
+                            [&](float *scores) { return scan_into(h, q, scores, s); });
     }
     FusedScan scan;
     scan.scan_scores = [&](float *scores, hipStream_t st) { return scan_into(h, q, scores, st); };
@@ -2112,9 +2060,8 @@ qamd_status qamd_bin_score_batch(const qamd_bin *h, const qamd_bin_query_batch *
 qamd_status qamd_bin_topk_batch(const qamd_bin *h, const qamd_bin_query_batch *b, uint32_t k, int largest,
                                 uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(bin_check_batch(h, b));
-    if (k == 0 || b->n_queries == 0) return QAMD_OK;
-    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
-    if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
+    qamd_status args = QAMD_OK;
+    if (!topk_wanted(k, b->n_queries, out_ids, out_scores, args)) return args;
     QAMD_ON_DEVICE(h->device);
     const uint8_t *bits = b->bits.as<uint8_t>();
     const uint64_t qs = b->q_stride;
@@ -2228,20 +2175,15 @@ qamd_status qamd_bin_encoder_begin(const qamd_vector_parameters *vp, qamd_bits_s
 qamd_status qamd_bin_encoder_push(qamd_bin_encoder *e, const float *batch, uint64_t n_rows, qamd_mem batch_mem) {
     if (!e || (!batch && n_rows && e->h->vp.dim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     if (e->stop && e->stop(e->stop_user)) return fail(QAMD_ERR_STOPPED, "Stopped");  // :174-176
-    if (e->pushed + n_rows > e->h->count)
-        return fail(QAMD_ERR_ARGUMENTS, "Vector count %llu does not match vector parameters count %llu",
-                    (unsigned long long)(e->pushed + n_rows), (unsigned long long)e->h->count);
+    if (e->pushed + n_rows > e->h->count) return count_mismatch(e->pushed + n_rows, e->h->count);
     QAMD_ON_DEVICE(e->device);
     const uint64_t dim = e->h->vp.dim;
     const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / std::max<uint64_t>(dim * 4, 1));
-    for (uint64_t r = 0; r < n_rows && dim; r += piece_rows) {
-        const uint64_t nr = std::min(piece_rows, n_rows - r);
-        const void *src = nullptr;
-        bool staged = false;
-        QAMD_TRY(local_view(batch + r * dim, batch_mem, nr * dim * 4, e->stage, e->stream, &src, &staged));
-        QAMD_TRY(launch_bin_encode(e->h.get(), static_cast<const float *>(src), nr, e->pushed + r, e->stream));
-        if (staged) QAMD_HIP(hipStreamSynchronize(e->stream));  // the staging buffer is reused
-    }
+    if (dim)
+        QAMD_TRY(for_each_staged_piece(batch, batch_mem, n_rows, dim, piece_rows, e->stage, e->stream,
+                                       [&](const float *src, uint64_t r, uint64_t nr) {
+            return launch_bin_encode(e->h.get(), src, nr, e->pushed + r, e->stream);
+        }));
     e->pushed += n_rows;
     return QAMD_OK;
 }
@@ -2249,21 +2191,14 @@ qamd_status qamd_bin_encoder_push(qamd_bin_encoder *e, const float *batch, uint6
 qamd_status qamd_bin_encoder_finish(qamd_bin_encoder *e, qamd_bin **out) {
     if (!e || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     std::unique_ptr<qamd_bin_encoder> own(e);
-    if (e->pushed != e->h->count)
-        return fail(QAMD_ERR_ARGUMENTS, "Vector count %llu does not match vector parameters count %llu",
-                    (unsigned long long)e->pushed, (unsigned long long)e->h->count);
+    if (e->pushed != e->h->count) return count_mismatch(e->pushed, e->h->count);
     QAMD_ON_DEVICE(e->device);
     QAMD_HIP(hipStreamSynchronize(e->stream));
     *out = e->h.release();
     return QAMD_OK;
 }
 
-void qamd_bin_encoder_abort(qamd_bin_encoder *e) {
-    if (!e) return;
-    DeviceGuard g(e->device);
-    (void)hipStreamSynchronize(e->stream);
-    delete e;
-}
+void qamd_bin_encoder_abort(qamd_bin_encoder *e) { abort_encoder(e); }
 
 }  // extern "C"
 

@@ -481,7 +481,7 @@ bool read_file(const char *path, std::string &out) {
     return bool(f) || f.eof();
 }
 
-bool write_file(const char *path, const void *data, size_t bytes) {
+static bool write_file(const char *path, const void *data, size_t bytes) {
     std::ofstream f(path, std::ios::binary | std::ios::trunc);
     if (!f) return false;
     if (bytes) f.write(static_cast<const char *>(data), (std::streamsize)bytes);
@@ -489,7 +489,7 @@ bool write_file(const char *path, const void *data, size_t bytes) {
     return bool(f);
 }
 
-void make_parent_dirs(const char *path) {
+static void make_parent_dirs(const char *path) {
     std::string p(path);
     size_t pos = p.find_last_of('/');
     if (pos == std::string::npos || pos == 0) return;
@@ -500,6 +500,32 @@ void make_parent_dirs(const char *path) {
             if (mkdir(sub.c_str(), 0777) != 0 && errno != EEXIST) return;
         }
     }
+}
+
+qamd_status save_file(const char *path, const void *data, size_t bytes) {
+    make_parent_dirs(path);
+    if (!write_file(path, data, bytes)) return fail(QAMD_ERR_IO, "cannot write %s", path);
+    return QAMD_OK;
+}
+
+qamd_status load_rows_file(const char *data_path, uint64_t expected, std::string &bytes) {
+    if (!read_file(data_path, bytes)) return fail(QAMD_ERR_IO, "cannot read %s", data_path);
+    if (bytes.size() != expected)
+        return fail(QAMD_ERR_IO, "Loaded storage size %zu is not equal to expected size %llu", bytes.size(),
+                    (unsigned long long)expected);
+    return QAMD_OK;
+}
+
+qamd_status count_mismatch(uint64_t got, uint64_t want) {
+    return fail(QAMD_ERR_ARGUMENTS, "Vector count %llu does not match vector parameters count %llu", (unsigned long long)got,
+                (unsigned long long)want);
+}
+
+qamd_status check_row_range(uint64_t first_row, uint64_t n_rows, uint64_t count) {
+    if (first_row > count || n_rows > count - first_row)
+        return fail(QAMD_ERR_OUT_OF_RANGE, "rows [%llu, +%llu) out of range (count %llu)", (unsigned long long)first_row,
+                    (unsigned long long)n_rows, (unsigned long long)count);
+    return QAMD_OK;
 }
 
 qamd_status read_metadata(const char *meta_path, JsonValue &root) {

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <cstdarg>
@@ -269,6 +270,35 @@ void thread_release_all();
 qamd_status local_view(const void *src, qamd_mem mem, size_t bytes, DevBuf &stage, hipStream_t s, const void **out,
                        bool *staged);
 
+// The encoders' walk over a batch of `n_rows` f32 rows of `dim` values, in pieces of at most `piece_rows` rows:
+// `consume(src, first_row, n)` enqueues its work on `s` for rows [first_row, first_row + n) of the batch, readable at
+// `src` (local_view through `stage`).  A staged piece is synchronised before the next one: the staging buffer is reused.
+template <class Consume>
+qamd_status for_each_staged_piece(const float *batch, qamd_mem batch_mem, uint64_t n_rows, uint64_t dim, uint64_t piece_rows,
+                                  DevBuf &stage, hipStream_t s, Consume &&consume) {
+    for (uint64_t r = 0; r < n_rows; r += piece_rows) {
+        const uint64_t nr = std::min(piece_rows, n_rows - r);
+        const void *src = nullptr;
+        bool staged = false;
+        QAMD_TRY(local_view(batch + r * dim, batch_mem, nr * dim * 4, stage, s, &src, &staged));
+        QAMD_TRY(consume(static_cast<const float *>(src), r, nr));
+        if (staged) QAMD_HIP(hipStreamSynchronize(s));
+    }
+    return QAMD_OK;
+}
+// "Vector count {got} does not match vector parameters count {want}": the EncodingError of a push / finish whose rows
+// do not add up to vector_parameters.count (validate_vector_parameters, encoded_vectors.rs:62-68).
+qamd_status count_mismatch(uint64_t got, uint64_t want);
+// *_encoder_abort: drops a streaming encoder of any quantizer.
+template <class Encoder> void abort_encoder(Encoder *e) {
+    if (!e) return;
+    DeviceGuard g(e->device);
+    (void)hipStreamSynchronize(e->stream);  // kernels may still be writing into the store being dropped
+    delete e;
+}
+// The range check of *_export_rows_range.
+qamd_status check_row_range(uint64_t first_row, uint64_t n_rows, uint64_t count);
+
 struct DeviceInfo {
     int cu_count = 256;
 };
@@ -279,8 +309,10 @@ inline uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 // serde_json metadata files (save / load): the writer's float formatting, file helpers, and the reader (json.hpp).
 std::string json_f32(float v);
 bool read_file(const char *path, std::string &out);
-bool write_file(const char *path, const void *data, size_t bytes);
-void make_parent_dirs(const char *path);
+// save: writes one of a store's two files, creating its directories; QAMD_ERR_IO when it cannot.
+qamd_status save_file(const char *path, const void *data, size_t bytes);
+// load: the raw row file, which must hold exactly `expected` bytes (encoded_storage.rs:40-51).
+qamd_status load_rows_file(const char *data_path, uint64_t expected, std::string &bytes);
 // Reads and parses a metadata file; QAMD_ERR_IO (std::io::Error in the reference: read_to_string / serde_json::from_str,
 // encoded_vectors_u8.rs:278-279) with the reader's message when it cannot.
 qamd_status read_metadata(const char *meta_path, JsonValue &root);

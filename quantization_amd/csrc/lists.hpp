@@ -69,6 +69,45 @@ inline uint32_t pairs_per_block(uint64_t n, uint32_t groups, uint32_t max_passes
     return (uint32_t)(groups * passes);
 }
 
+// One id list against one query: out[k] = score of ids[k], for host or device ids / outputs -- the body of every
+// score_ids and of the u8 / binary score_internal_ids.  Runs `launch(ids_dev, n_ids, out_dev)` once on `s`.
+//   Host ids are validated here (ids[k] < count, as run_lists); device ids cannot be.
+//   Host ids AND host output of at most 1024 ids (score_point and friends) ride in the calling thread's mapped
+//   scratch: no allocation, no copy call, one launch + one synchronisation.
+//   Device ids AND device output only enqueue; a host output, or host ids alone, synchronise `s`.
+template <class Launch>
+qamd_status run_ids(const uint32_t *ids, uint64_t n_ids, qamd_mem ids_mem, float *out, qamd_mem out_mem, uint64_t count,
+                    hipStream_t s, Launch &&launch) {
+    if (ids_mem == QAMD_MEM_HOST)
+        for (uint64_t k = 0; k < n_ids; k++)
+            if (ids[k] >= count)  // the reference panics here (encoded_storage.rs:29)
+                return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", ids[k], (unsigned long long)count);
+    const HostScratch hs = (ids_mem == QAMD_MEM_HOST && out_mem == QAMD_MEM_HOST && n_ids <= 1024) ? host_scratch() : HostScratch{};
+    if (hs.host) {
+        for (uint64_t k = 0; k < n_ids; k++) hs.host[k] = ids[k];
+        QAMD_TRY(launch(hs.dev, n_ids, reinterpret_cast<float *>(hs.dev + 1024)));
+        QAMD_HIP(hipStreamSynchronize(s));
+        memcpy(out, hs.host + 1024, n_ids * 4);
+        return QAMD_OK;
+    }
+    DevBuf ids_tmp, out_tmp;
+    const uint32_t *ids_dev = ids;
+    if (ids_mem == QAMD_MEM_HOST) {
+        QAMD_TRY(ids_tmp.alloc(n_ids * 4));
+        QAMD_TRY(copy_in(ids_tmp.ptr, ids, QAMD_MEM_HOST, n_ids * 4, s));
+        ids_dev = ids_tmp.as<uint32_t>();
+    }
+    float *out_dev = out;
+    if (out_mem == QAMD_MEM_HOST) {
+        QAMD_TRY(out_tmp.alloc(n_ids * 4));
+        out_dev = out_tmp.as<float>();
+    }
+    QAMD_TRY(launch(ids_dev, n_ids, out_dev));
+    if (out_mem == QAMD_MEM_HOST) return copy_out(out, QAMD_MEM_HOST, out_dev, n_ids * 4, s);
+    if (ids_mem == QAMD_MEM_HOST) QAMD_HIP(hipStreamSynchronize(s));  // the pageable host ids must stay valid until read
+    return QAMD_OK;
+}
+
 // Brings (list_offsets, ids, rows) and the output of one burst to the device, runs `launch(args)` on
 // `s`, and delivers the scores.
 //   lists_mem: where list_offsets, ids and rows live (one kind for all three); n_ids = list_offsets[n_lists].

@@ -1969,9 +1969,7 @@ qamd_status qamd_pq_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
 qamd_status qamd_pq_export_rows_range(const qamd_pq *h, uint64_t first_row, uint64_t n_rows, uint8_t *rows,
                                       qamd_mem rows_mem, void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
-    if (first_row > h->count || n_rows > h->count - first_row)
-        return fail(QAMD_ERR_OUT_OF_RANGE, "rows [%llu, +%llu) out of range (count %llu)", (unsigned long long)first_row,
-                    (unsigned long long)n_rows, (unsigned long long)h->count);
+    QAMD_TRY(check_row_range(first_row, n_rows, h->count));
     if (n_rows == 0 || h->m == 0) return QAMD_OK;
     if (!rows) return fail(QAMD_ERR_ARGUMENTS, "rows is null");
     QAMD_ON_DEVICE(h->device);
@@ -2012,13 +2010,10 @@ qamd_status qamd_pq_save(const qamd_pq *h, const char *data_path, const char *me
         js += "{\"start\":" + std::to_string(lo) + ",\"end\":" + std::to_string(hi) + "}";
     }
     js += "],\"vector_parameters\":" + vector_parameters_json(h->vp) + "}";
-    make_parent_dirs(meta_path);
-    if (!write_file(meta_path, js.data(), js.size())) return fail(QAMD_ERR_IO, "cannot write %s", meta_path);
+    QAMD_TRY(save_file(meta_path, js.data(), js.size()));
     std::vector<uint8_t> rows(h->count * h->m);
     QAMD_TRY(qamd_pq_export_rows(h, rows.data(), QAMD_MEM_HOST, nullptr));
-    make_parent_dirs(data_path);
-    if (!write_file(data_path, rows.data(), rows.size())) return fail(QAMD_ERR_IO, "cannot write %s", data_path);
-    return QAMD_OK;
+    return save_file(data_path, rows.data(), rows.size());
 }
 
 // load (:508-523): row size = metadata.vector_division.len(), count from the caller.
@@ -2068,11 +2063,7 @@ qamd_status qamd_pq_load(const char *data_path, const char *meta_path, const qam
         if (chunk_size == 0) chunk_size = 1;  // dim == 0: no ranges
     }
     std::string bytes;
-    if (!read_file(data_path, bytes)) return fail(QAMD_ERR_IO, "cannot read %s", data_path);
-    const uint64_t expected = m * vp->count;
-    if (bytes.size() != expected)
-        return fail(QAMD_ERR_IO, "Loaded storage size %zu is not equal to expected size %llu", bytes.size(),
-                    (unsigned long long)expected);
+    QAMD_TRY(load_rows_file(data_path, m * vp->count, bytes));
     qamd_vector_parameters eff = file_vp;
     eff.count = vp->count;
     if (chunks_of(eff.dim, chunk_size) != m) return fail(QAMD_ERR_IO, "vector_division does not tile dim");
@@ -2145,12 +2136,9 @@ qamd_status qamd_pq_score_all(const qamd_pq *h, const qamd_pq_query *q, float *o
     hipStream_t s = as_stream(stream);
     QAMD_TRY(q->ready.wait(s));
     if (out_mem == QAMD_MEM_DEVICE) return scan_launch(h, q->lut.as<float>(), nullptr, h->count, out, s, nullptr, q->lut_t());
-    float *tmp = nullptr;  // per-thread workspace: no hipMalloc / hipFree per query
-    QAMD_TRY(thread_ws_acquire(WS_SCORES, h->count * 4, s, reinterpret_cast<void **>(&tmp)));
-    qamd_status st = scan_launch(h, q->lut.as<float>(), nullptr, h->count, tmp, s, nullptr, q->lut_t());
-    if (st == QAMD_OK) st = copy_out(out, QAMD_MEM_HOST, tmp, h->count * 4, s);
-    thread_ws_release(WS_SCORES, s, st == QAMD_OK);  // the download synchronised the stream
-    return st;
+    return score_all_to_host(h->count, out, s, [&](float *scores) {
+        return scan_launch(h, q->lut.as<float>(), nullptr, h->count, scores, s, nullptr, q->lut_t());
+    });
 }
 
 qamd_status qamd_pq_score_ids(const qamd_pq *h, const qamd_pq_query *q, const uint32_t *ids, uint64_t n_ids,
@@ -2161,42 +2149,9 @@ qamd_status qamd_pq_score_ids(const qamd_pq *h, const qamd_pq_query *q, const ui
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     QAMD_TRY(q->ready.wait(s));
-    DevBuf ids_tmp, out_tmp;
-    const uint32_t *ids_dev = ids;
-    // per-pair granularity (score_point and friends): ids and results through the calling
-    // thread's mapped host scratch -- no allocation, no copy calls
-    const HostScratch hs = (ids_mem == QAMD_MEM_HOST && out_mem == QAMD_MEM_HOST && n_ids <= 1024) ? host_scratch()
-                                                                                                  : HostScratch{};
-    if (hs.host) {
-        for (uint64_t k = 0; k < n_ids; k++) {
-            if (ids[k] >= h->count)
-                return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", ids[k],
-                            (unsigned long long)h->count);
-            hs.host[k] = ids[k];
-        }
-        QAMD_TRY(scan_launch(h, q->lut.as<float>(), hs.dev, n_ids, reinterpret_cast<float *>(hs.dev + 1024), s));
-        QAMD_HIP(hipStreamSynchronize(s));
-        memcpy(out, hs.host + 1024, n_ids * 4);
-        return QAMD_OK;
-    }
-    if (ids_mem == QAMD_MEM_HOST) {
-        for (uint64_t k = 0; k < n_ids; k++)
-            if (ids[k] >= h->count)
-                return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", ids[k],
-                            (unsigned long long)h->count);
-        QAMD_TRY(ids_tmp.alloc(n_ids * 4));
-        QAMD_TRY(copy_in(ids_tmp.ptr, ids, QAMD_MEM_HOST, n_ids * 4, s));
-        ids_dev = ids_tmp.as<uint32_t>();
-    }
-    float *out_dev = out;
-    if (out_mem == QAMD_MEM_HOST) {
-        QAMD_TRY(out_tmp.alloc(n_ids * 4));
-        out_dev = out_tmp.as<float>();
-    }
-    QAMD_TRY(scan_launch(h, q->lut.as<float>(), ids_dev, n_ids, out_dev, s));
-    if (out_mem == QAMD_MEM_HOST) QAMD_TRY(copy_out(out, QAMD_MEM_HOST, out_dev, n_ids * 4, s));
-    else if (ids_mem == QAMD_MEM_HOST) QAMD_HIP(hipStreamSynchronize(s));
-    return QAMD_OK;
+    return run_ids(ids, n_ids, ids_mem, out, out_mem, h->count, s, [&](const uint32_t *ids_dev, uint64_t n, float *out_dev) {
+        return scan_launch(h, q->lut.as<float>(), ids_dev, n, out_dev, s);
+    });
 }
 
 qamd_status qamd_pq_score_point(const qamd_pq *h, const qamd_pq_query *q, uint32_t i, float *out) {
@@ -2266,9 +2221,8 @@ qamd_status qamd_pq_score_internal_ids_batch(const qamd_pq *h, const uint32_t *r
 qamd_status qamd_pq_topk(const qamd_pq *h, const qamd_pq_query *q, uint32_t k, int largest, uint32_t *out_ids,
                          float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(check_query(h, q));
-    if (k == 0) return QAMD_OK;
-    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
-    if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
+    qamd_status args = QAMD_OK;
+    if (!topk_wanted(k, 1, out_ids, out_scores, args)) return args;
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     QAMD_TRY(q->ready.wait(s));
@@ -2278,12 +2232,8 @@ qamd_status qamd_pq_topk(const qamd_pq *h, const qamd_pq_query *q, uint32_t k, i
         if (pq_topk_small(h, lut, k, largest, out_ids, out_scores, out_mem, s, st)) return st;
     }
     if (!fast_capable(h, h->count)) {
-        float *scores = nullptr;
-        QAMD_TRY(thread_ws_acquire(WS_SCORES, std::max<uint64_t>(h->count, 1) * 4, s, reinterpret_cast<void **>(&scores)));
-        qamd_status st = scan_launch(h, lut, nullptr, h->count, scores, s);
-        if (st == QAMD_OK) st = topk_finish(scores, h->count, k, largest, out_ids, out_scores, out_mem, s);
-        thread_ws_release(WS_SCORES, s);
-        return st;
+        return topk_classic(h->count, k, largest, out_ids, out_scores, out_mem, s,
+                            [&](float *scores) { return scan_launch(h, lut, nullptr, h->count, scores, s); });
     }
     FusedScan scan;
     const float *lut_t = q->lut_t();
@@ -2410,11 +2360,10 @@ qamd_status qamd_pq_encoder_observe(qamd_pq_encoder *e, const float *batch, uint
     }
     const uint64_t dim = e->h->vp.dim, count = e->h->count;
     if (e->pushed) return fail(QAMD_ERR_ARGUMENTS, "observe after push");
-    if (e->observed + n_rows > count)
-        return fail(QAMD_ERR_ARGUMENTS, "Vector count %llu does not match vector parameters count %llu",
-                    (unsigned long long)(e->observed + n_rows), (unsigned long long)count);
+    if (e->observed + n_rows > count) return count_mismatch(e->observed + n_rows, count);
     QAMD_ON_DEVICE(e->device);
     const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / std::max<uint64_t>(dim * 4, 1));
+    // (not for_each_staged_piece: a piece that holds no sample row is not even staged)
     for (uint64_t r = 0; r < n_rows && dim && e->S; r += piece_rows) {
         const uint64_t nr = std::min(piece_rows, n_rows - r), base = e->observed + r;
         // sample slots whose row floor(k * count / S) falls into [base, base + nr)
@@ -2438,25 +2387,20 @@ qamd_status qamd_pq_encoder_push(qamd_pq_encoder *e, const float *batch, uint64_
     if (!e || (!batch && n_rows && e->h->vp.dim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     if (e->stop && e->stop(e->stop_user)) return fail(QAMD_ERR_STOPPED, "Stopped");  // :198-200
     qamd_pq *h = e->h.get();
-    if (e->pushed + n_rows > h->count)
-        return fail(QAMD_ERR_ARGUMENTS, "Vector count %llu does not match vector parameters count %llu",
-                    (unsigned long long)(e->pushed + n_rows), (unsigned long long)h->count);
+    if (e->pushed + n_rows > h->count) return count_mismatch(e->pushed + n_rows, h->count);
     QAMD_ON_DEVICE(e->device);
     QAMD_TRY(pq_encoder_close_pass1(e));
     const uint64_t dim = h->vp.dim;
     if (dim && !e->pair_table.ptr && cs_fast_shape(dim, h->chunk_size))
         QAMD_TRY(build_pair_table(h->centroids.as<float>(), dim, h->chunk_size, h->m, e->pair_table, e->stream));
     const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / std::max<uint64_t>(dim * 4, 1));
-    for (uint64_t r = 0; r < n_rows && dim; r += piece_rows) {
-        const uint64_t nr = std::min(piece_rows, n_rows - r);
-        const void *src = nullptr;
-        bool staged = false;
-        QAMD_TRY(local_view(batch + r * dim, batch_mem, nr * dim * 4, e->stage, e->stream, &src, &staged));
-        QAMD_TRY(launch_assign(static_cast<const float *>(src), nr, dim, h->chunk_size, h->m, h->centroids.as<float>(),
-                               &e->pair_table, h->rows.as<uint8_t>(), h->ds, e->pushed + r, e->stream));
-        QAMD_TRY(build_planar(h, e->pushed + r, nr, e->stream));
-        if (staged) QAMD_HIP(hipStreamSynchronize(e->stream));
-    }
+    if (dim)
+        QAMD_TRY(for_each_staged_piece(batch, batch_mem, n_rows, dim, piece_rows, e->stage, e->stream,
+                                       [&](const float *src, uint64_t r, uint64_t nr) -> qamd_status {
+            QAMD_TRY(launch_assign(src, nr, dim, h->chunk_size, h->m, h->centroids.as<float>(), &e->pair_table,
+                                   h->rows.as<uint8_t>(), h->ds, e->pushed + r, e->stream));
+            return build_planar(h, e->pushed + r, nr, e->stream);
+        }));
     e->pushed += n_rows;
     return QAMD_OK;
 }
@@ -2464,9 +2408,7 @@ qamd_status qamd_pq_encoder_push(qamd_pq_encoder *e, const float *batch, uint64_
 qamd_status qamd_pq_encoder_finish(qamd_pq_encoder *e, qamd_pq **out) {
     if (!e || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     std::unique_ptr<qamd_pq_encoder> own(e);
-    if (e->pushed != e->h->count)
-        return fail(QAMD_ERR_ARGUMENTS, "Vector count %llu does not match vector parameters count %llu",
-                    (unsigned long long)e->pushed, (unsigned long long)e->h->count);
+    if (e->pushed != e->h->count) return count_mismatch(e->pushed, e->h->count);
     QAMD_ON_DEVICE(e->device);
     QAMD_TRY(pq_encoder_close_pass1(e));  // count == 0, or a caller that never pushed an empty store
     QAMD_HIP(hipStreamSynchronize(e->stream));
@@ -2475,12 +2417,7 @@ qamd_status qamd_pq_encoder_finish(qamd_pq_encoder *e, qamd_pq **out) {
     return QAMD_OK;
 }
 
-void qamd_pq_encoder_abort(qamd_pq_encoder *e) {
-    if (!e) return;
-    DeviceGuard g(e->device);
-    (void)hipStreamSynchronize(e->stream);
-    delete e;
-}
+void qamd_pq_encoder_abort(qamd_pq_encoder *e) { abort_encoder(e); }
 
 }  // extern "C"
 
@@ -2618,9 +2555,8 @@ qamd_status qamd_pq_score_batch(const qamd_pq *h, const qamd_pq_query_batch *b, 
 qamd_status qamd_pq_topk_batch(const qamd_pq *h, const qamd_pq_query_batch *b, uint32_t k, int largest,
                                uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(pq_check_batch(h, b));
-    if (k == 0 || b->n_queries == 0) return QAMD_OK;
-    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
-    if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
+    qamd_status args = QAMD_OK;
+    if (!topk_wanted(k, b->n_queries, out_ids, out_scores, args)) return args;
     QAMD_ON_DEVICE(h->device);
     const size_t per = (size_t)h->m * kCentroids;
     const float *luts = b->luts.as<float>();

@@ -324,8 +324,13 @@ int device_of(const void *ptr) {
 }
 
 // ------------------------------------------------------------------------------------ generic store
-// Ops: the single-device C ABI of one quantizer (identical shapes for u8 / bin / pq).
-template <class H, class Qy> struct Ops {
+// Ops: the single-device C ABI of one quantizer (identical shapes for u8 / bin / pq): H its store, Qy its encoded
+// query, B its query batch, E its streaming encoder.
+template <class H, class Qy, class B, class E> struct Ops {
+    using Store = H;
+    using Query = Qy;
+    using Batch = B;
+    using Encoder = E;
     qamd_status (*encode_query)(const H *, const float *, uint64_t, qamd_mem, void *, Qy **);
     void (*query_free)(Qy *);
     qamd_status (*score_all)(const H *, const Qy *, float *, qamd_mem, void *);
@@ -334,13 +339,19 @@ template <class H, class Qy> struct Ops {
     // encode_query of a HOST query of this many values launches nothing (the values are kept in the query
     // object until its first consumer, u8.hip): the sharded call then needs no fan-out either
     bool (*host_encode_is_lazy)(uint64_t qdim);
+    qamd_status (*encode_query_batch)(const H *, const float *, uint64_t, uint64_t, qamd_mem, void *, B **);
+    void (*query_batch_free)(B *);
+    qamd_status (*topk_batch)(const H *, const B *, uint32_t, int, uint32_t *, float *, qamd_mem, void *);
+    qamd_status (*encoder_push)(E *, const float *, uint64_t, qamd_mem);
+    void (*encoder_abort)(E *);
+    qamd_status (*encoder_finish)(E *, H **);
 };
 
-template <class H, class Qy> struct ShardedQuery {
-    std::vector<Qy *> per_shard;
-    const Ops<H, Qy> *ops = nullptr;
+template <class O> struct ShardedQuery {
+    std::vector<typename O::Query *> per_shard;
+    const O *ops = nullptr;
     ~ShardedQuery() {
-        for (Qy *q : per_shard)
+        for (auto *q : per_shard)
             if (q) ops->query_free(q);
     }
 };
@@ -390,8 +401,11 @@ qamd_status order_after_caller(qamd_mem mem, const void *buf, void *stream) {
     return QAMD_OK;
 }
 
-template <class H, class Qy> struct Sharded {
-    const Ops<H, Qy> *ops = nullptr;
+template <class O> struct Sharded {
+    using H = typename O::Store;
+    using Qy = typename O::Query;
+    using Encoder = typename O::Encoder;
+    const O *ops = nullptr;
     uint64_t count = 0;
     std::vector<int> devices;
     std::vector<uint64_t> base;  // G + 1 row bounds
@@ -503,27 +517,18 @@ template <class H, class Qy> struct Sharded {
         }
     }
 
-    qamd_status encode_query(const float *query, uint64_t qdim, qamd_mem mem, void *stream, ShardedQuery<H, Qy> **io) {
-        std::unique_ptr<ShardedQuery<H, Qy>> fresh;
-        ShardedQuery<H, Qy> *q = *io;
-        if (!q) {
-            fresh.reset(new ShardedQuery<H, Qy>);
-            q = fresh.get();
-            q->ops = ops;
-            q->per_shard.assign(G(), nullptr);
-        }
+    qamd_status encode_query(const float *query, uint64_t qdim, qamd_mem mem, void *stream, ShardedQuery<O> *q) {
         if (q->per_shard.size() != G()) return fail(QAMD_ERR_ARGUMENTS, "query belongs to another sharded store");
         const int src_dev = mem == QAMD_MEM_DEVICE ? device_of(query) : -1;
         if (mem == QAMD_MEM_HOST && ops->host_encode_is_lazy(qdim)) {  // G host-side copies, no GPU work, no lanes
             for (uint32_t g = 0; g < G(); g++)
                 QAMD_TRY(ops->encode_query(shards[g], query, qdim, mem, nullptr, &q->per_shard[g]));
-            if (fresh) *io = fresh.release();
             return QAMD_OK;
         }
         QAMD_TRY(order_after_caller(mem, query, stream));
         Lease slot;
         QAMD_TRY(lease(slot));
-        QAMD_TRY(pool.run([&](uint32_t g, Worker &w) -> qamd_status {
+        return pool.run([&](uint32_t g, Worker &w) -> qamd_status {
             const float *src = query;
             if (mem == QAMD_MEM_DEVICE && src_dev != w.device && qdim) {  // a device query lives on ONE GPU
                 DevBuf &stage = slot->query_stage[g];
@@ -538,12 +543,10 @@ template <class H, class Qy> struct Sharded {
             // a device query: the caller's buffer and the slot's staging copy are in use until the kernel has run
             if (mem == QAMD_MEM_DEVICE) QAMD_TRY(wait_stream(w.stream));
             return QAMD_OK;
-        }));
-        if (fresh) *io = fresh.release();
-        return QAMD_OK;
+        });
     }
 
-    qamd_status check(const ShardedQuery<H, Qy> *q) const {
+    qamd_status check(const ShardedQuery<O> *q) const {
         if (!q || q->per_shard.size() != shards.size()) return fail(QAMD_ERR_ARGUMENTS, "null or foreign sharded query");
         for (Qy *p : q->per_shard)
             if (!p) return fail(QAMD_ERR_ARGUMENTS, "sharded query was never encoded");
@@ -551,7 +554,7 @@ template <class H, class Qy> struct Sharded {
     }
 
     // out[base_g + i] = score_point(q, i of shard g).  Device output: on any one GPU.
-    qamd_status score_all(const ShardedQuery<H, Qy> *q, float *out, qamd_mem out_mem, void *stream) {
+    qamd_status score_all(const ShardedQuery<O> *q, float *out, qamd_mem out_mem, void *stream) {
         QAMD_TRY(check(q));
         if (count == 0) return QAMD_OK;
         if (!out) return fail(QAMD_ERR_ARGUMENTS, "out is null");
@@ -675,7 +678,7 @@ template <class H, class Qy> struct Sharded {
         return mst;
     }
 
-    qamd_status topk(const ShardedQuery<H, Qy> *q, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
+    qamd_status topk(const ShardedQuery<O> *q, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
                      qamd_mem out_mem, void *stream) {
         QAMD_TRY(check(q));
         return topk_common(1, k, largest, out_ids, out_scores, out_mem, stream,
@@ -733,19 +736,63 @@ qamd_status merge_lists(const uint32_t *ids, const float *scores, uint64_t shard
 
 // Query batches behind a sharded handle: one per-shard batch object each (the queries are replicated),
 // encoded by the shards' workers; identical shapes for the three quantizers.
-template <class B> struct ShardedBatch {
-    std::vector<B *> per_shard;
+template <class O> struct ShardedBatch {
+    std::vector<typename O::Batch *> per_shard;
     uint64_t n_queries = 0;
-    void (*free_fn)(B *) = nullptr;
+    const O *ops = nullptr;
     ~ShardedBatch() {
-        for (B *b : per_shard)
-            if (b && free_fn) free_fn(b);
+        for (auto *b : per_shard)
+            if (b) ops->query_batch_free(b);
     }
 };
 
-template <class S, class B, class EncodeFn>
+// ------------------------------------------------------------------------------------ the C ABI, once
+// The entry points with a body that is the same for the three quantizers: S is qamd_{u8,bin,pq}_sharded, SQ its query
+// type, SB its query-batch type.  The extern "C" functions below forward to these.
+template <class S> qamd_status sharded_peer_access(const S *h, uint32_t g, int *state, const char **reason) {
+    if (!h || !state || g >= h->G()) return fail(QAMD_ERR_ARGUMENTS, "bad shard index");
+    *state = h->peer[g].state;
+    if (reason) *reason = h->peer[g].reason.c_str();
+    return QAMD_OK;
+}
+
+template <class S>
+qamd_status sharded_shard(const S *h, uint32_t g, const typename S::H **shard, uint64_t *row_begin, int *device) {
+    if (!h || g >= h->G()) return fail(QAMD_ERR_ARGUMENTS, "no such shard");
+    if (shard) *shard = h->shards[g];
+    if (row_begin) *row_begin = h->base[g];
+    if (device) *device = h->devices[g];
+    return QAMD_OK;
+}
+
+template <class S, class SQ>
+qamd_status sharded_encode_query(S *h, const float *query, uint64_t qdim, qamd_mem query_mem, void *stream, SQ **query_io) {
+    if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    std::unique_ptr<SQ> fresh;
+    SQ *q = *query_io;
+    if (!q) {
+        fresh.reset(new SQ);
+        q = fresh.get();
+        q->ops = h->ops;
+        q->per_shard.assign(h->G(), nullptr);
+    }
+    QAMD_TRY(h->encode_query(query, qdim, query_mem, stream, q));
+    if (fresh) *query_io = fresh.release();
+    return QAMD_OK;
+}
+
+template <class S, class SB>
 qamd_status sharded_encode_query_batch(S *h, const float *queries, uint64_t n_queries, uint64_t qdim, qamd_mem queries_mem,
-                                       void *stream, ShardedBatch<B> *b, EncodeFn encode) {
+                                       void *stream, SB **batch_io) {
+    if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    std::unique_ptr<SB> fresh;
+    SB *b = *batch_io;
+    if (!b) {
+        fresh.reset(new SB);
+        b = fresh.get();
+        b->ops = h->ops;
+        b->per_shard.assign(h->G(), nullptr);
+    }
     if (b->per_shard.size() != h->G()) return fail(QAMD_ERR_ARGUMENTS, "batch belongs to another sharded store");
     const int src_dev = queries_mem == QAMD_MEM_DEVICE ? device_of(queries) : -1;
     const size_t bytes = (size_t)n_queries * qdim * 4;
@@ -760,41 +807,96 @@ qamd_status sharded_encode_query_batch(S *h, const float *queries, uint64_t n_qu
             QAMD_HIP(hipMemcpyAsync(stage.ptr, queries, bytes, hipMemcpyDefault, w.stream));
             src = stage.template as<float>();
         }
-        QAMD_TRY(encode(h->shards[g], src, n_queries, qdim, queries_mem, w.stream, &b->per_shard[g]));
+        QAMD_TRY(h->ops->encode_query_batch(h->shards[g], src, n_queries, qdim, queries_mem, w.stream, &b->per_shard[g]));
         return wait_stream(w.stream);  // batch objects carry no ready event: finished before anyone scores with them
     }));
     b->n_queries = n_queries;
+    if (fresh) *batch_io = fresh.release();
     return QAMD_OK;
 }
 
+template <class S, class SB>
+qamd_status sharded_topk_batch(S *h, const SB *b, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
+                               qamd_mem out_mem, void *stream) {
+    if (!h || !b || b->per_shard.size() != h->G()) return fail(QAMD_ERR_ARGUMENTS, "null or foreign argument");
+    return h->topk_common((uint32_t)b->n_queries, k, largest, out_ids, out_scores, out_mem, stream,
+                          [&](uint32_t g, Worker &w, uint32_t *ids, float *sc) {
+                              return h->ops->topk_batch(h->shards[g], b->per_shard[g], k, largest, ids, sc, QAMD_MEM_DEVICE,
+                                                        w.stream);
+                          });
+}
+
+// Every shard encodes its own rows of `data` with the quantizer's streaming encoder, which
+// `begin(shard's vector parameters, stream, &encoder)` opens on the lane's device.
+template <class S, class Begin>
+qamd_status sharded_encode_rows(S *h, const float *data, qamd_mem data_mem, const qamd_vector_parameters *vp, Begin begin) {
+    return h->pool.run([&](uint32_t g, Worker &w) -> qamd_status {
+        qamd_vector_parameters svp = *vp;
+        svp.count = h->base[g + 1] - h->base[g];
+        QAMD_TRY(qamd_set_device(w.device));
+        typename S::Encoder *e = nullptr;
+        QAMD_TRY(begin(&svp, w.stream, &e));
+        qamd_status st = h->ops->encoder_push(e, data + h->base[g] * vp->dim, svp.count, data_mem);
+        if (st != QAMD_OK) {
+            h->ops->encoder_abort(e);
+            return st;
+        }
+        return h->ops->encoder_finish(e, &h->shards[g]);
+    });
+}
+
+// Every shard takes its own rows (`stride` bytes each) of an encoded store: `from_rows(src, n_rows, stream, &shard)`
+// is the quantizer's from_rows for the shard's row count, on the lane's device.
+template <class S, class FromRows>
+qamd_status sharded_from_rows(S *h, const uint8_t *rows, qamd_mem rows_mem, uint64_t stride, FromRows from_rows) {
+    return h->pool.run([&](uint32_t g, Worker &w) -> qamd_status {
+        const uint64_t n = h->base[g + 1] - h->base[g];
+        DevBuf stage;
+        const void *src = nullptr;
+        QAMD_TRY(shard_source(rows ? rows + h->base[g] * stride : nullptr, rows_mem, n * stride, w.device, stage, w.stream,
+                              &src));
+        QAMD_TRY(qamd_set_device(w.device));
+        return from_rows(static_cast<const uint8_t *>(src), n, w.stream, &h->shards[g]);
+    });
+}
+
 bool never_lazy(uint64_t) { return false; }
-const Ops<qamd_u8, qamd_u8_query> kU8Ops = {qamd_u8_encode_query, qamd_u8_query_free, qamd_u8_score_all, qamd_u8_topk,
-                                            qamd_u8_free, u8_host_encode_is_lazy};
-const Ops<qamd_bin, qamd_bin_query> kBinOps = {qamd_bin_encode_query, qamd_bin_query_free, qamd_bin_score_all,
-                                               qamd_bin_topk, qamd_bin_free, never_lazy};
-const Ops<qamd_pq, qamd_pq_query> kPqOps = {qamd_pq_encode_query, qamd_pq_query_free, qamd_pq_score_all, qamd_pq_topk,
-                                            qamd_pq_free, never_lazy};
+using U8Ops = Ops<qamd_u8, qamd_u8_query, qamd_u8_query_batch, qamd_u8_encoder>;
+using BinOps = Ops<qamd_bin, qamd_bin_query, qamd_bin_query_batch, qamd_bin_encoder>;
+using PqOps = Ops<qamd_pq, qamd_pq_query, qamd_pq_query_batch, qamd_pq_encoder>;
+const U8Ops kU8Ops = {qamd_u8_encode_query,       qamd_u8_query_free,       qamd_u8_score_all,  qamd_u8_topk,
+                      qamd_u8_free,               u8_host_encode_is_lazy,   qamd_u8_encode_query_batch,
+                      qamd_u8_query_batch_free,   qamd_u8_topk_batch,       qamd_u8_encoder_push,
+                      qamd_u8_encoder_abort,      qamd_u8_encoder_finish};
+const BinOps kBinOps = {qamd_bin_encode_query,     qamd_bin_query_free,     qamd_bin_score_all, qamd_bin_topk,
+                        qamd_bin_free,             never_lazy,              qamd_bin_encode_query_batch,
+                        qamd_bin_query_batch_free, qamd_bin_topk_batch,     qamd_bin_encoder_push,
+                        qamd_bin_encoder_abort,    qamd_bin_encoder_finish};
+const PqOps kPqOps = {qamd_pq_encode_query,     qamd_pq_query_free,     qamd_pq_score_all, qamd_pq_topk,
+                      qamd_pq_free,             never_lazy,             qamd_pq_encode_query_batch,
+                      qamd_pq_query_batch_free, qamd_pq_topk_batch,     qamd_pq_encoder_push,
+                      qamd_pq_encoder_abort,    qamd_pq_encoder_finish};
 
 }  // namespace
 
-struct qamd_u8_sharded : Sharded<qamd_u8, qamd_u8_query> {
+struct qamd_u8_sharded : Sharded<U8Ops> {
     qamd_u8_metadata meta{};
 };
-struct qamd_u8_sharded_query : ShardedQuery<qamd_u8, qamd_u8_query> {};
-struct qamd_u8_sharded_query_batch : ShardedBatch<qamd_u8_query_batch> {};
-struct qamd_bin_sharded_query_batch : ShardedBatch<qamd_bin_query_batch> {};
-struct qamd_pq_sharded_query_batch : ShardedBatch<qamd_pq_query_batch> {};
-struct qamd_bin_sharded : Sharded<qamd_bin, qamd_bin_query> {
+struct qamd_u8_sharded_query : ShardedQuery<U8Ops> {};
+struct qamd_u8_sharded_query_batch : ShardedBatch<U8Ops> {};
+struct qamd_bin_sharded : Sharded<BinOps> {
     qamd_vector_parameters vp{};
     int store = 0;
 };
-struct qamd_bin_sharded_query : ShardedQuery<qamd_bin, qamd_bin_query> {};
-struct qamd_pq_sharded : Sharded<qamd_pq, qamd_pq_query> {
+struct qamd_bin_sharded_query : ShardedQuery<BinOps> {};
+struct qamd_bin_sharded_query_batch : ShardedBatch<BinOps> {};
+struct qamd_pq_sharded : Sharded<PqOps> {
     qamd_vector_parameters vp{};
     uint64_t chunk_size = 0;
     std::vector<float> centroids;
 };
-struct qamd_pq_sharded_query : ShardedQuery<qamd_pq, qamd_pq_query> {};
+struct qamd_pq_sharded_query : ShardedQuery<PqOps> {};
+struct qamd_pq_sharded_query_batch : ShardedBatch<PqOps> {};
 
 extern "C" {
 
@@ -854,18 +956,9 @@ qamd_status qamd_u8_sharded_encode(const float *data, qamd_mem data_mem, const q
         }
     }
     // PASS 2 (:73-118): every shard quantizes its own rows with the global (alpha, offset).
-    QAMD_TRY(h->pool.run([&](uint32_t g, Worker &w) -> qamd_status {
-        qamd_vector_parameters svp = *vp;
-        svp.count = h->base[g + 1] - h->base[g];
-        QAMD_TRY(qamd_set_device(w.device));
-        qamd_u8_encoder *e = nullptr;
-        QAMD_TRY(qamd_u8_encoder_begin(&svp, nullptr, vp->count ? ao : nullptr, stop, stop_user, w.stream, &e));
-        qamd_status st = qamd_u8_encoder_push(e, data + h->base[g] * dim, svp.count, data_mem);
-        if (st != QAMD_OK) {
-            qamd_u8_encoder_abort(e);
-            return st;
-        }
-        return qamd_u8_encoder_finish(e, &h->shards[g]);
+    QAMD_TRY(sharded_encode_rows(h.get(), data, data_mem, vp,
+                                 [&](const qamd_vector_parameters *svp, void *s, qamd_u8_encoder **e) {
+        return qamd_u8_encoder_begin(svp, nullptr, vp->count ? ao : nullptr, stop, stop_user, s, e);
     }));
     QAMD_TRY(qamd_u8_get_metadata(h->shards[0], &h->meta));
     if (vp->count && h->shards[0]->count == 0) {  // an empty first shard holds the empty-store metadata
@@ -889,16 +982,11 @@ qamd_status qamd_u8_sharded_from_rows(const uint8_t *rows, qamd_mem rows_mem, co
     h->meta = *meta;
     QAMD_TRY(h->init(devices, n_shards, meta->vector_parameters.count));
     QAMD_TRY(order_after_caller(rows_mem, rows, stream));
-    const uint64_t stride = meta->actual_dim + 4;
-    QAMD_TRY(h->pool.run([&](uint32_t g, Worker &w) -> qamd_status {
+    QAMD_TRY(sharded_from_rows(h.get(), rows, rows_mem, meta->actual_dim + 4,
+                               [&](const uint8_t *src, uint64_t n, void *s, qamd_u8 **shard) {
         qamd_u8_metadata sm = *meta;
-        sm.vector_parameters.count = h->base[g + 1] - h->base[g];
-        DevBuf stage;
-        const void *src = nullptr;
-        QAMD_TRY(shard_source(rows ? rows + h->base[g] * stride : nullptr, rows_mem, sm.vector_parameters.count * stride,
-                              w.device, stage, w.stream, &src));
-        QAMD_TRY(qamd_set_device(w.device));
-        return qamd_u8_from_rows(static_cast<const uint8_t *>(src), rows_mem, &sm, w.stream, &h->shards[g]);
+        sm.vector_parameters.count = n;
+        return qamd_u8_from_rows(src, rows_mem, &sm, s, shard);
     }));
     *out = h.release();
     return QAMD_OK;
@@ -906,19 +994,12 @@ qamd_status qamd_u8_sharded_from_rows(const uint8_t *rows, qamd_mem rows_mem, co
 
 uint32_t qamd_u8_sharded_shard_count(const qamd_u8_sharded *h) { return h ? h->G() : 0; }
 qamd_status qamd_u8_sharded_peer_access(const qamd_u8_sharded *h, uint32_t g, int *state, const char **reason) {
-    if (!h || !state || g >= h->G()) return fail(QAMD_ERR_ARGUMENTS, "bad shard index");
-    *state = h->peer[g].state;
-    if (reason) *reason = h->peer[g].reason.c_str();
-    return QAMD_OK;
+    return sharded_peer_access(h, g, state, reason);
 }
 
 qamd_status qamd_u8_sharded_shard(const qamd_u8_sharded *h, uint32_t g, const qamd_u8 **shard, uint64_t *row_begin,
                                   int *device) {
-    if (!h || g >= h->G()) return fail(QAMD_ERR_ARGUMENTS, "no such shard");
-    if (shard) *shard = h->shards[g];
-    if (row_begin) *row_begin = h->base[g];
-    if (device) *device = h->devices[g];
-    return QAMD_OK;
+    return sharded_shard(h, g, shard, row_begin, device);
 }
 
 qamd_status qamd_u8_sharded_get_metadata(const qamd_u8_sharded *h, qamd_u8_metadata *out) {
@@ -927,29 +1008,15 @@ qamd_status qamd_u8_sharded_get_metadata(const qamd_u8_sharded *h, qamd_u8_metad
     return QAMD_OK;
 }
 
-qamd_status qamd_u8_sharded_encode_query(qamd_u8_sharded *h, const float *query, uint64_t qdim, qamd_mem query_mem, void *stream,
-                                   qamd_u8_sharded_query **query_io) {
-    if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    ShardedQuery<qamd_u8, qamd_u8_query> *q = *query_io;
-    const bool fresh = q == nullptr;
-    if (fresh) {
-        auto *nq = new qamd_u8_sharded_query;
-        nq->ops = &kU8Ops;
-        nq->per_shard.assign(h->G(), nullptr);
-        q = nq;
-    }
-    qamd_status st = h->encode_query(query, qdim, query_mem, stream, &q);
-    if (st != QAMD_OK) {
-        if (fresh) delete static_cast<qamd_u8_sharded_query *>(q);
-        return st;
-    }
-    *query_io = static_cast<qamd_u8_sharded_query *>(q);
-    return QAMD_OK;
+qamd_status qamd_u8_sharded_encode_query(qamd_u8_sharded *h, const float *query, uint64_t qdim, qamd_mem query_mem,
+                                         void *stream, qamd_u8_sharded_query **query_io) {
+    return sharded_encode_query(h, query, qdim, query_mem, stream, query_io);
 }
 
 void qamd_u8_sharded_query_free(qamd_u8_sharded_query *q) { delete q; }
 
-qamd_status qamd_u8_sharded_score_all(qamd_u8_sharded *h, const qamd_u8_sharded_query *q, float *out, qamd_mem out_mem, void *stream) {
+qamd_status qamd_u8_sharded_score_all(qamd_u8_sharded *h, const qamd_u8_sharded_query *q, float *out, qamd_mem out_mem,
+                                      void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
     return h->score_all(q, out, out_mem, stream);
 }
@@ -962,31 +1029,15 @@ qamd_status qamd_u8_sharded_topk(qamd_u8_sharded *h, const qamd_u8_sharded_query
 
 qamd_status qamd_u8_sharded_encode_query_batch(qamd_u8_sharded *h, const float *queries, uint64_t n_queries, uint64_t qdim,
                                                qamd_mem queries_mem, void *stream,
-                                   qamd_u8_sharded_query_batch **batch_io) {
-    if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    std::unique_ptr<qamd_u8_sharded_query_batch> fresh;
-    qamd_u8_sharded_query_batch *b = *batch_io;
-    if (!b) {
-        fresh.reset(new qamd_u8_sharded_query_batch);
-        b = fresh.get();
-        b->per_shard.assign(h->G(), nullptr);
-        b->free_fn = qamd_u8_query_batch_free;
-    }
-    QAMD_TRY(sharded_encode_query_batch(h, queries, n_queries, qdim, queries_mem, stream, b, qamd_u8_encode_query_batch));
-    if (fresh) *batch_io = fresh.release();
-    return QAMD_OK;
+                                               qamd_u8_sharded_query_batch **batch_io) {
+    return sharded_encode_query_batch(h, queries, n_queries, qdim, queries_mem, stream, batch_io);
 }
 
 void qamd_u8_sharded_query_batch_free(qamd_u8_sharded_query_batch *b) { delete b; }
 
 qamd_status qamd_u8_sharded_topk_batch(qamd_u8_sharded *h, const qamd_u8_sharded_query_batch *b, uint32_t k, int largest,
                                        uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
-    if (!h || !b || b->per_shard.size() != h->G()) return fail(QAMD_ERR_ARGUMENTS, "null or foreign argument");
-    return h->topk_common((uint32_t)b->n_queries, k, largest, out_ids, out_scores, out_mem, stream,
-                          [&](uint32_t g, Worker &w, uint32_t *ids, float *sc) {
-                              return qamd_u8_topk_batch(h->shards[g], b->per_shard[g], k, largest, ids, sc, QAMD_MEM_DEVICE,
-                                                        w.stream);
-                          });
+    return sharded_topk_batch(h, b, k, largest, out_ids, out_scores, out_mem, stream);
 }
 
 void qamd_u8_sharded_free(qamd_u8_sharded *h) { delete h; }
@@ -1004,18 +1055,9 @@ qamd_status qamd_bin_sharded_encode(const float *data, qamd_mem data_mem, const 
     h->store = store;
     QAMD_TRY(h->init(devices, n_shards, vp->count));
     QAMD_TRY(order_after_caller(data_mem, data, stream));
-    QAMD_TRY(h->pool.run([&](uint32_t g, Worker &w) -> qamd_status {
-        qamd_vector_parameters svp = *vp;
-        svp.count = h->base[g + 1] - h->base[g];
-        QAMD_TRY(qamd_set_device(w.device));
-        qamd_bin_encoder *e = nullptr;
-        QAMD_TRY(qamd_bin_encoder_begin(&svp, store, stop, stop_user, w.stream, &e));
-        qamd_status st = qamd_bin_encoder_push(e, data + h->base[g] * vp->dim, svp.count, data_mem);
-        if (st != QAMD_OK) {
-            qamd_bin_encoder_abort(e);
-            return st;
-        }
-        return qamd_bin_encoder_finish(e, &h->shards[g]);
+    QAMD_TRY(sharded_encode_rows(h.get(), data, data_mem, vp,
+                                 [&](const qamd_vector_parameters *svp, void *s, qamd_bin_encoder **e) {
+        return qamd_bin_encoder_begin(svp, store, stop, stop_user, s, e);
     }));
     *out = h.release();
     return QAMD_OK;
@@ -1031,16 +1073,11 @@ qamd_status qamd_bin_sharded_from_rows(const uint8_t *rows, qamd_mem rows_mem, c
     h->store = store;
     QAMD_TRY(h->init(devices, n_shards, vp->count));
     QAMD_TRY(order_after_caller(rows_mem, rows, stream));
-    const uint64_t stride = qamd_bin_quantized_vector_size(vp, store);
-    QAMD_TRY(h->pool.run([&](uint32_t g, Worker &w) -> qamd_status {
+    QAMD_TRY(sharded_from_rows(h.get(), rows, rows_mem, qamd_bin_quantized_vector_size(vp, store),
+                               [&](const uint8_t *src, uint64_t n, void *s, qamd_bin **shard) {
         qamd_vector_parameters svp = *vp;
-        svp.count = h->base[g + 1] - h->base[g];
-        DevBuf stage;
-        const void *src = nullptr;
-        QAMD_TRY(shard_source(rows ? rows + h->base[g] * stride : nullptr, rows_mem, svp.count * stride, w.device, stage,
-                              w.stream, &src));
-        QAMD_TRY(qamd_set_device(w.device));
-        return qamd_bin_from_rows(static_cast<const uint8_t *>(src), rows_mem, &svp, store, w.stream, &h->shards[g]);
+        svp.count = n;
+        return qamd_bin_from_rows(src, rows_mem, &svp, store, s, shard);
     }));
     *out = h.release();
     return QAMD_OK;
@@ -1048,45 +1085,23 @@ qamd_status qamd_bin_sharded_from_rows(const uint8_t *rows, qamd_mem rows_mem, c
 
 uint32_t qamd_bin_sharded_shard_count(const qamd_bin_sharded *h) { return h ? h->G() : 0; }
 qamd_status qamd_bin_sharded_peer_access(const qamd_bin_sharded *h, uint32_t g, int *state, const char **reason) {
-    if (!h || !state || g >= h->G()) return fail(QAMD_ERR_ARGUMENTS, "bad shard index");
-    *state = h->peer[g].state;
-    if (reason) *reason = h->peer[g].reason.c_str();
-    return QAMD_OK;
+    return sharded_peer_access(h, g, state, reason);
 }
 
 qamd_status qamd_bin_sharded_shard(const qamd_bin_sharded *h, uint32_t g, const qamd_bin **shard, uint64_t *row_begin,
                                    int *device) {
-    if (!h || g >= h->G()) return fail(QAMD_ERR_ARGUMENTS, "no such shard");
-    if (shard) *shard = h->shards[g];
-    if (row_begin) *row_begin = h->base[g];
-    if (device) *device = h->devices[g];
-    return QAMD_OK;
+    return sharded_shard(h, g, shard, row_begin, device);
 }
 
-qamd_status qamd_bin_sharded_encode_query(qamd_bin_sharded *h, const float *query, uint64_t qdim, qamd_mem query_mem, void *stream,
-                                   qamd_bin_sharded_query **query_io) {
-    if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    ShardedQuery<qamd_bin, qamd_bin_query> *q = *query_io;
-    const bool fresh = q == nullptr;
-    if (fresh) {
-        auto *nq = new qamd_bin_sharded_query;
-        nq->ops = &kBinOps;
-        nq->per_shard.assign(h->G(), nullptr);
-        q = nq;
-    }
-    qamd_status st = h->encode_query(query, qdim, query_mem, stream, &q);
-    if (st != QAMD_OK) {
-        if (fresh) delete static_cast<qamd_bin_sharded_query *>(q);
-        return st;
-    }
-    *query_io = static_cast<qamd_bin_sharded_query *>(q);
-    return QAMD_OK;
+qamd_status qamd_bin_sharded_encode_query(qamd_bin_sharded *h, const float *query, uint64_t qdim, qamd_mem query_mem,
+                                          void *stream, qamd_bin_sharded_query **query_io) {
+    return sharded_encode_query(h, query, qdim, query_mem, stream, query_io);
 }
 
 void qamd_bin_sharded_query_free(qamd_bin_sharded_query *q) { delete q; }
 
-qamd_status qamd_bin_sharded_score_all(qamd_bin_sharded *h, const qamd_bin_sharded_query *q, float *out,
-                                       qamd_mem out_mem, void *stream) {
+qamd_status qamd_bin_sharded_score_all(qamd_bin_sharded *h, const qamd_bin_sharded_query *q, float *out, qamd_mem out_mem,
+                                       void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
     return h->score_all(q, out, out_mem, stream);
 }
@@ -1097,33 +1112,17 @@ qamd_status qamd_bin_sharded_topk(qamd_bin_sharded *h, const qamd_bin_sharded_qu
     return h->topk(q, k, largest, out_ids, out_scores, out_mem, stream);
 }
 
-qamd_status qamd_bin_sharded_encode_query_batch(qamd_bin_sharded *h, const float *queries, uint64_t n_queries,
-                                                uint64_t qdim, qamd_mem queries_mem, void *stream,
-                                   qamd_bin_sharded_query_batch **batch_io) {
-    if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    std::unique_ptr<qamd_bin_sharded_query_batch> fresh;
-    qamd_bin_sharded_query_batch *b = *batch_io;
-    if (!b) {
-        fresh.reset(new qamd_bin_sharded_query_batch);
-        b = fresh.get();
-        b->per_shard.assign(h->G(), nullptr);
-        b->free_fn = qamd_bin_query_batch_free;
-    }
-    QAMD_TRY(sharded_encode_query_batch(h, queries, n_queries, qdim, queries_mem, stream, b, qamd_bin_encode_query_batch));
-    if (fresh) *batch_io = fresh.release();
-    return QAMD_OK;
+qamd_status qamd_bin_sharded_encode_query_batch(qamd_bin_sharded *h, const float *queries, uint64_t n_queries, uint64_t qdim,
+                                                qamd_mem queries_mem, void *stream,
+                                                qamd_bin_sharded_query_batch **batch_io) {
+    return sharded_encode_query_batch(h, queries, n_queries, qdim, queries_mem, stream, batch_io);
 }
 
 void qamd_bin_sharded_query_batch_free(qamd_bin_sharded_query_batch *b) { delete b; }
 
 qamd_status qamd_bin_sharded_topk_batch(qamd_bin_sharded *h, const qamd_bin_sharded_query_batch *b, uint32_t k, int largest,
                                         uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
-    if (!h || !b || b->per_shard.size() != h->G()) return fail(QAMD_ERR_ARGUMENTS, "null or foreign argument");
-    return h->topk_common((uint32_t)b->n_queries, k, largest, out_ids, out_scores, out_mem, stream,
-                          [&](uint32_t g, Worker &w, uint32_t *ids, float *sc) {
-                              return qamd_bin_topk_batch(h->shards[g], b->per_shard[g], k, largest, ids, sc, QAMD_MEM_DEVICE,
-                                                         w.stream);
-                          });
+    return sharded_topk_batch(h, b, k, largest, out_ids, out_scores, out_mem, stream);
 }
 
 void qamd_bin_sharded_free(qamd_bin_sharded *h) { delete h; }
@@ -1150,19 +1149,9 @@ qamd_status qamd_pq_sharded_encode(const float *data, qamd_mem data_mem, const q
         QAMD_TRY(pq_train_centroids(data, data_mem, vp, chunk_size, max_kmeans_threads, stop, stop_user, nullptr,
                                     h->centroids, nullptr, nullptr));
     }
-    QAMD_TRY(h->pool.run([&](uint32_t g, Worker &w) -> qamd_status {
-        qamd_vector_parameters svp = *vp;
-        svp.count = h->base[g + 1] - h->base[g];
-        QAMD_TRY(qamd_set_device(w.device));
-        qamd_pq_encoder *e = nullptr;
-        QAMD_TRY(qamd_pq_encoder_begin(&svp, chunk_size, h->centroids.data(), max_kmeans_threads, stop, stop_user, w.stream,
-                                       &e));
-        qamd_status st = qamd_pq_encoder_push(e, data + h->base[g] * vp->dim, svp.count, data_mem);
-        if (st != QAMD_OK) {
-            qamd_pq_encoder_abort(e);
-            return st;
-        }
-        return qamd_pq_encoder_finish(e, &h->shards[g]);
+    QAMD_TRY(sharded_encode_rows(h.get(), data, data_mem, vp,
+                                 [&](const qamd_vector_parameters *svp, void *s, qamd_pq_encoder **e) {
+        return qamd_pq_encoder_begin(svp, chunk_size, h->centroids.data(), max_kmeans_threads, stop, stop_user, s, e);
     }));
     *out = h.release();
     return QAMD_OK;
@@ -1180,17 +1169,11 @@ qamd_status qamd_pq_sharded_from_rows(const uint8_t *rows, qamd_mem rows_mem, co
     h->centroids.assign(centroids, centroids + (size_t)QAMD_PQ_CENTROIDS * vp->dim);
     QAMD_TRY(h->init(devices, n_shards, vp->count));
     QAMD_TRY(order_after_caller(rows_mem, rows, stream));
-    const uint64_t stride = qamd_pq_quantized_vector_size(vp, chunk_size);
-    QAMD_TRY(h->pool.run([&](uint32_t g, Worker &w) -> qamd_status {
+    QAMD_TRY(sharded_from_rows(h.get(), rows, rows_mem, qamd_pq_quantized_vector_size(vp, chunk_size),
+                               [&](const uint8_t *src, uint64_t n, void *s, qamd_pq **shard) {
         qamd_vector_parameters svp = *vp;
-        svp.count = h->base[g + 1] - h->base[g];
-        DevBuf stage;
-        const void *src = nullptr;
-        QAMD_TRY(shard_source(rows ? rows + h->base[g] * stride : nullptr, rows_mem, svp.count * stride, w.device, stage,
-                              w.stream, &src));
-        QAMD_TRY(qamd_set_device(w.device));
-        return qamd_pq_from_rows(static_cast<const uint8_t *>(src), rows_mem, &svp, chunk_size, h->centroids.data(),
-                                 w.stream, &h->shards[g]);
+        svp.count = n;
+        return qamd_pq_from_rows(src, rows_mem, &svp, chunk_size, h->centroids.data(), s, shard);
     }));
     *out = h.release();
     return QAMD_OK;
@@ -1198,19 +1181,12 @@ qamd_status qamd_pq_sharded_from_rows(const uint8_t *rows, qamd_mem rows_mem, co
 
 uint32_t qamd_pq_sharded_shard_count(const qamd_pq_sharded *h) { return h ? h->G() : 0; }
 qamd_status qamd_pq_sharded_peer_access(const qamd_pq_sharded *h, uint32_t g, int *state, const char **reason) {
-    if (!h || !state || g >= h->G()) return fail(QAMD_ERR_ARGUMENTS, "bad shard index");
-    *state = h->peer[g].state;
-    if (reason) *reason = h->peer[g].reason.c_str();
-    return QAMD_OK;
+    return sharded_peer_access(h, g, state, reason);
 }
 
 qamd_status qamd_pq_sharded_shard(const qamd_pq_sharded *h, uint32_t g, const qamd_pq **shard, uint64_t *row_begin,
                                   int *device) {
-    if (!h || g >= h->G()) return fail(QAMD_ERR_ARGUMENTS, "no such shard");
-    if (shard) *shard = h->shards[g];
-    if (row_begin) *row_begin = h->base[g];
-    if (device) *device = h->devices[g];
-    return QAMD_OK;
+    return sharded_shard(h, g, shard, row_begin, device);
 }
 
 qamd_status qamd_pq_sharded_get_centroids(const qamd_pq_sharded *h, float *centroids) {
@@ -1219,29 +1195,15 @@ qamd_status qamd_pq_sharded_get_centroids(const qamd_pq_sharded *h, float *centr
     return QAMD_OK;
 }
 
-qamd_status qamd_pq_sharded_encode_query(qamd_pq_sharded *h, const float *query, uint64_t qdim, qamd_mem query_mem, void *stream,
-                                   qamd_pq_sharded_query **query_io) {
-    if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    ShardedQuery<qamd_pq, qamd_pq_query> *q = *query_io;
-    const bool fresh = q == nullptr;
-    if (fresh) {
-        auto *nq = new qamd_pq_sharded_query;
-        nq->ops = &kPqOps;
-        nq->per_shard.assign(h->G(), nullptr);
-        q = nq;
-    }
-    qamd_status st = h->encode_query(query, qdim, query_mem, stream, &q);
-    if (st != QAMD_OK) {
-        if (fresh) delete static_cast<qamd_pq_sharded_query *>(q);
-        return st;
-    }
-    *query_io = static_cast<qamd_pq_sharded_query *>(q);
-    return QAMD_OK;
+qamd_status qamd_pq_sharded_encode_query(qamd_pq_sharded *h, const float *query, uint64_t qdim, qamd_mem query_mem,
+                                         void *stream, qamd_pq_sharded_query **query_io) {
+    return sharded_encode_query(h, query, qdim, query_mem, stream, query_io);
 }
 
 void qamd_pq_sharded_query_free(qamd_pq_sharded_query *q) { delete q; }
 
-qamd_status qamd_pq_sharded_score_all(qamd_pq_sharded *h, const qamd_pq_sharded_query *q, float *out, qamd_mem out_mem, void *stream) {
+qamd_status qamd_pq_sharded_score_all(qamd_pq_sharded *h, const qamd_pq_sharded_query *q, float *out, qamd_mem out_mem,
+                                      void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
     return h->score_all(q, out, out_mem, stream);
 }
@@ -1254,31 +1216,15 @@ qamd_status qamd_pq_sharded_topk(qamd_pq_sharded *h, const qamd_pq_sharded_query
 
 qamd_status qamd_pq_sharded_encode_query_batch(qamd_pq_sharded *h, const float *queries, uint64_t n_queries, uint64_t qdim,
                                                qamd_mem queries_mem, void *stream,
-                                   qamd_pq_sharded_query_batch **batch_io) {
-    if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    std::unique_ptr<qamd_pq_sharded_query_batch> fresh;
-    qamd_pq_sharded_query_batch *b = *batch_io;
-    if (!b) {
-        fresh.reset(new qamd_pq_sharded_query_batch);
-        b = fresh.get();
-        b->per_shard.assign(h->G(), nullptr);
-        b->free_fn = qamd_pq_query_batch_free;
-    }
-    QAMD_TRY(sharded_encode_query_batch(h, queries, n_queries, qdim, queries_mem, stream, b, qamd_pq_encode_query_batch));
-    if (fresh) *batch_io = fresh.release();
-    return QAMD_OK;
+                                               qamd_pq_sharded_query_batch **batch_io) {
+    return sharded_encode_query_batch(h, queries, n_queries, qdim, queries_mem, stream, batch_io);
 }
 
 void qamd_pq_sharded_query_batch_free(qamd_pq_sharded_query_batch *b) { delete b; }
 
 qamd_status qamd_pq_sharded_topk_batch(qamd_pq_sharded *h, const qamd_pq_sharded_query_batch *b, uint32_t k, int largest,
                                        uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
-    if (!h || !b || b->per_shard.size() != h->G()) return fail(QAMD_ERR_ARGUMENTS, "null or foreign argument");
-    return h->topk_common((uint32_t)b->n_queries, k, largest, out_ids, out_scores, out_mem, stream,
-                          [&](uint32_t g, Worker &w, uint32_t *ids, float *sc) {
-                              return qamd_pq_topk_batch(h->shards[g], b->per_shard[g], k, largest, ids, sc, QAMD_MEM_DEVICE,
-                                                        w.stream);
-                          });
+    return sharded_topk_batch(h, b, k, largest, out_ids, out_scores, out_mem, stream);
 }
 
 void qamd_pq_sharded_free(qamd_pq_sharded *h) { delete h; }

@@ -485,12 +485,8 @@ qamd_status fused_topk(uint64_t n, uint32_t k, int largest, uint32_t *out_ids, f
         if (status == 0) return QAMD_OK;
         // fall through: pivot missed (heavy ties / adversarial order) -> exact classic path
     }
-    float *scores = nullptr;
-    QAMD_TRY(thread_ws_acquire(WS_SCORES, std::max<uint64_t>(n, 1) * 4, stream, reinterpret_cast<void **>(&scores)));
-    qamd_status st2 = scan.scan_scores(scores, stream);
-    if (st2 == QAMD_OK) st2 = topk_finish(scores, n, k, largest, out_ids, out_scores, out_mem, stream);
-    thread_ws_release(WS_SCORES, stream);
-    return st2;
+    return topk_classic(n, k, largest, out_ids, out_scores, out_mem, stream,
+                        [&](float *scores) { return scan.scan_scores(scores, stream); });
 }
 
 qamd_status fused_topk_batch(uint64_t n, uint32_t Q, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,

@@ -1,5 +1,6 @@
 // Exact device top-k over an f32 score array (see topk.hip).
 #pragma once
+#include <algorithm>
 #include <functional>
 
 #include "common.hpp"
@@ -22,6 +23,42 @@ qamd_status select_kth_f32(const float *vals_dev, uint64_t n, uint64_t k, bool l
 // Shared tail of the three *_topk entry points: scores already computed into scores_dev.
 qamd_status topk_finish(const float *scores_dev, uint64_t n, uint32_t k, int largest,
                         uint32_t *out_ids, float *out_scores, qamd_mem out_mem, hipStream_t stream);
+
+// What every *_topk / *_topk_batch entry point checks after its handles.  False when the call ends here: `st` is QAMD_OK
+// (k or the query count is 0: nothing is asked for) or the argument error.
+inline bool topk_wanted(uint32_t k, uint64_t n_queries, const void *out_ids, const void *out_scores, qamd_status &st) {
+    st = QAMD_OK;
+    if (k == 0 || n_queries == 0) return false;
+    if (k > 1024) st = fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
+    else if (!out_ids || !out_scores) st = fail(QAMD_ERR_ARGUMENTS, "null output");
+    return st == QAMD_OK;
+}
+
+// The unfused ("classic") top-k: `scan_scores(scores_dev)` enqueues the scores of all n rows on `stream` into the
+// calling thread's score workspace, the exact radix select picks from them.  Host outputs synchronise `stream`
+// (topk_finish); the workspace is handed on through its event either way.
+template <class Scan>
+qamd_status topk_classic(uint64_t n, uint32_t k, int largest, uint32_t *out_ids, float *out_scores, qamd_mem out_mem,
+                         hipStream_t stream, Scan &&scan_scores) {
+    float *scores = nullptr;
+    QAMD_TRY(thread_ws_acquire(WS_SCORES, std::max<uint64_t>(n, 1) * 4, stream, reinterpret_cast<void **>(&scores)));
+    qamd_status st = scan_scores(scores);
+    if (st == QAMD_OK) st = topk_finish(scores, n, k, largest, out_ids, out_scores, out_mem, stream);
+    thread_ws_release(WS_SCORES, stream);
+    return st;
+}
+
+// score_all into HOST memory: `scan(scores_dev)` enqueues the scores of all `count` rows on `stream` into the calling
+// thread's score workspace (no hipMalloc / hipFree per query); the download synchronises `stream`.
+template <class Scan>
+qamd_status score_all_to_host(uint64_t count, float *out, hipStream_t stream, Scan &&scan) {
+    float *tmp = nullptr;
+    QAMD_TRY(thread_ws_acquire(WS_SCORES, count * 4, stream, reinterpret_cast<void **>(&tmp)));
+    qamd_status st = scan(tmp);
+    if (st == QAMD_OK) st = copy_out(out, QAMD_MEM_HOST, tmp, count * 4, stream);
+    thread_ws_release(WS_SCORES, stream, st == QAMD_OK);  // the download synchronised the stream
+    return st;
+}
 
 // Fused scan + selection: the scan never materialises the score array.
 //   1. score S pseudo-randomly chosen rows (random-access kernel; S = 16384 .. 131072, growing with n),

@@ -1465,46 +1465,13 @@ float internal_diff(const qamd_u8 *h) {
     return h->meta.vector_parameters.invert ? -diff : diff;
 }
 
-// out[k] = score of (query (qc, qo), ids[k]) for host or device ids / outputs: the body of score_ids
-// and, with (qc, qo) = row i of the store and the internal epilogue, of score_internal_ids.
+// out[k] = score of (query (qc, qo), ids[k]) for host or device ids / outputs (run_ids, lists.hpp): the body of
+// score_ids and, with (qc, qo) = row i of the store and the internal epilogue, of score_internal_ids.
 qamd_status score_ids_any(const qamd_u8 *h, const uint4 *qc, const float *qo, float diff, int mode, const uint32_t *ids,
                           uint64_t n_ids, qamd_mem ids_mem, float *out, qamd_mem out_mem, hipStream_t s) {
-    DevBuf ids_tmp, out_tmp;
-    const uint32_t *ids_dev = ids;
-    // per-pair granularity (score_point and friends): ids and results through the calling
-    // thread's mapped host scratch -- no allocation, no copy calls
-    const HostScratch hs = (ids_mem == QAMD_MEM_HOST && out_mem == QAMD_MEM_HOST && n_ids <= 1024) ? host_scratch()
-                                                                                                  : HostScratch{};
-    if (hs.host) {
-        for (uint64_t k = 0; k < n_ids; k++) {
-            if (ids[k] >= h->count)
-                return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", ids[k],
-                            (unsigned long long)h->count);
-            hs.host[k] = ids[k];
-        }
-        QAMD_TRY(score_ids_dev(h, qc, qo, diff, mode, hs.dev, n_ids, reinterpret_cast<float *>(hs.dev + 1024), s));
-        QAMD_HIP(hipStreamSynchronize(s));
-        memcpy(out, hs.host + 1024, n_ids * 4);
-        return QAMD_OK;
-    }
-    if (ids_mem == QAMD_MEM_HOST) {
-        for (uint64_t k = 0; k < n_ids; k++)
-            if (ids[k] >= h->count)  // the reference panics here (encoded_storage.rs:29)
-                return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", ids[k],
-                            (unsigned long long)h->count);
-        QAMD_TRY(ids_tmp.alloc(n_ids * 4));
-        QAMD_TRY(copy_in(ids_tmp.ptr, ids, QAMD_MEM_HOST, n_ids * 4, s));
-        ids_dev = ids_tmp.as<uint32_t>();
-    }
-    float *out_dev = out;
-    if (out_mem == QAMD_MEM_HOST) {
-        QAMD_TRY(out_tmp.alloc(n_ids * 4));
-        out_dev = out_tmp.as<float>();
-    }
-    QAMD_TRY(score_ids_dev(h, qc, qo, diff, mode, ids_dev, n_ids, out_dev, s));
-    if (out_mem == QAMD_MEM_HOST) QAMD_TRY(copy_out(out, QAMD_MEM_HOST, out_dev, n_ids * 4, s));
-    else if (ids_mem == QAMD_MEM_HOST) QAMD_HIP(hipStreamSynchronize(s));
-    return QAMD_OK;
+    return run_ids(ids, n_ids, ids_mem, out, out_mem, h->count, s, [&](const uint32_t *ids_dev, uint64_t n, float *out_dev) {
+        return score_ids_dev(h, qc, qo, diff, mode, ids_dev, n, out_dev, s);
+    });
 }
 
 // Gather `n_out` evenly strided rows of a device-resident [count][dim] array (quantile sample).
@@ -1861,9 +1828,7 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
 qamd_status qamd_u8_export_rows_range(const qamd_u8 *h, uint64_t first_row, uint64_t n_rows, uint8_t *rows,
                                       qamd_mem rows_mem, void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
-    if (first_row > h->count || n_rows > h->count - first_row)
-        return fail(QAMD_ERR_OUT_OF_RANGE, "rows [%llu, +%llu) out of range (count %llu)", (unsigned long long)first_row,
-                    (unsigned long long)n_rows, (unsigned long long)h->count);
+    QAMD_TRY(check_row_range(first_row, n_rows, h->count));
     if (n_rows == 0) return QAMD_OK;
     if (!rows) return fail(QAMD_ERR_ARGUMENTS, "rows is null");
     QAMD_ON_DEVICE(h->device);
@@ -1905,16 +1870,11 @@ qamd_status qamd_u8_save(const qamd_u8 *h, const char *data_path, const char *me
                      ",\"alpha\":" + json_f32(h->meta.alpha) + ",\"offset\":" + json_f32(h->meta.offset) +
                      ",\"multiplier\":" + json_f32(h->meta.multiplier) +
                      ",\"vector_parameters\":" + vector_parameters_json(h->meta.vector_parameters) + "}";
-    make_parent_dirs(meta_path);
-    if (!write_file(meta_path, js.data(), js.size()))
-        return fail(QAMD_ERR_IO, "cannot write %s", meta_path);
+    QAMD_TRY(save_file(meta_path, js.data(), js.size()));
     const uint64_t stride = h->meta.actual_dim + 4;
     std::vector<uint8_t> rows(h->count * stride);
     QAMD_TRY(qamd_u8_export_rows(h, rows.data(), QAMD_MEM_HOST, nullptr));
-    make_parent_dirs(data_path);
-    if (!write_file(data_path, rows.data(), rows.size()))
-        return fail(QAMD_ERR_IO, "cannot write %s", data_path);
-    return QAMD_OK;
+    return save_file(data_path, rows.data(), rows.size());
 }
 
 // load (:273-288): metadata from JSON; row size/count from the CALLER's vector_parameters;
@@ -1935,11 +1895,7 @@ qamd_status qamd_u8_load(const char *data_path, const char *meta_path, const qam
     }
     const uint64_t size = qamd_u8_quantized_vector_size(vp);
     std::string bytes;
-    if (!read_file(data_path, bytes)) return fail(QAMD_ERR_IO, "cannot read %s", data_path);
-    const uint64_t expected = size * vp->count;
-    if (bytes.size() != expected)
-        return fail(QAMD_ERR_IO, "Loaded storage size %zu is not equal to expected size %llu", bytes.size(),
-                    (unsigned long long)expected);
+    QAMD_TRY(load_rows_file(data_path, size * vp->count, bytes));
     // The reference keeps the file's metadata but sizes rows from the caller's parameters.
     qamd_u8_metadata eff = meta;
     eff.vector_parameters.dim = vp->dim;
@@ -2068,12 +2024,7 @@ qamd_status qamd_u8_score_all(const qamd_u8 *h, const qamd_u8_query *q, float *o
         q->async_used.store(true, std::memory_order_relaxed);
         return scan_into(h, q, out, s);
     }
-    float *tmp = nullptr;  // per-thread workspace: no hipMalloc / hipFree per query
-    QAMD_TRY(thread_ws_acquire(WS_SCORES, h->count * sizeof(float), s, reinterpret_cast<void **>(&tmp)));
-    qamd_status st = scan_into(h, q, tmp, s);
-    if (st == QAMD_OK) st = copy_out(out, QAMD_MEM_HOST, tmp, h->count * sizeof(float), s);
-    thread_ws_release(WS_SCORES, s, st == QAMD_OK);  // the download synchronised the stream
-    return st;
+    return score_all_to_host(h->count, out, s, [&](float *scores) { return scan_into(h, q, scores, s); });
 }
 
 qamd_status qamd_u8_score_ids(const qamd_u8 *h, const qamd_u8_query *q, const uint32_t *ids, uint64_t n_ids,
@@ -2129,9 +2080,8 @@ qamd_status qamd_u8_score_internal(const qamd_u8 *h, uint32_t i, uint32_t j, flo
 qamd_status qamd_u8_topk(const qamd_u8 *h, const qamd_u8_query *q, uint32_t k, int largest, uint32_t *out_ids,
                          float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(check_query(h, q));
-    if (k == 0) return QAMD_OK;
-    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
-    if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
+    qamd_status args = QAMD_OK;
+    if (!topk_wanted(k, 1, out_ids, out_scores, args)) return args;
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     if (q->deferred.load(std::memory_order_acquire)) {
@@ -2303,9 +2253,7 @@ qamd_status qamd_u8_encoder_observe(qamd_u8_encoder *e, const float *batch, uint
         return QAMD_OK;
     }
     if (e->pushed) return fail(QAMD_ERR_ARGUMENTS, "observe after push");
-    if (e->observed + n_rows > e->vp.count)
-        return fail(QAMD_ERR_ARGUMENTS, "Vector count %llu does not match vector parameters count %llu",
-                    (unsigned long long)(e->observed + n_rows), (unsigned long long)e->vp.count);
+    if (e->observed + n_rows > e->vp.count) return count_mismatch(e->observed + n_rows, e->vp.count);
     QAMD_ON_DEVICE(e->device);
     const uint64_t dim = e->vp.dim, count = e->vp.count;
     if (dim == 0) {
@@ -2313,25 +2261,21 @@ qamd_status qamd_u8_encoder_observe(qamd_u8_encoder *e, const float *batch, uint
         return QAMD_OK;
     }
     const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(kStagePieceBytes) / (dim * 4));
-    for (uint64_t r = 0; r < n_rows; r += piece_rows) {
-        const uint64_t nr = std::min(piece_rows, n_rows - r);
-        const void *src = nullptr;
-        bool staged = false;
-        QAMD_TRY(local_view(batch + r * dim, batch_mem, nr * dim * 4, e->stage, e->stream, &src, &staged));
-        QAMD_TRY(e->acc.feed(static_cast<const float *>(src), nr * dim, e->stream));
+    QAMD_TRY(for_each_staged_piece(batch, batch_mem, n_rows, dim, piece_rows, e->stage, e->stream,
+                                   [&](const float *src, uint64_t r, uint64_t nr) -> qamd_status {
+        QAMD_TRY(e->acc.feed(src, nr * dim, e->stream));
         if (e->slice) {
             const uint64_t base = e->observed + r;
             const uint64_t k0 = first_sample_at_or_after(base, count, e->slice);
             const uint64_t k1 = std::min<uint64_t>(e->slice, first_sample_at_or_after(base + nr, count, e->slice));
             if (k1 > k0) {
                 hipLaunchKernelGGL(gather_sample_batch_kernel, dim3(grid_for((k1 - k0) * dim, kBlock * 4, 8)), dim3(kBlock),
-                                   0, e->stream, static_cast<const float *>(src), base, (uint32_t)dim, count, e->slice, k0,
-                                   k1, e->sample.as<float>());
+                                   0, e->stream, src, base, (uint32_t)dim, count, e->slice, k0, k1, e->sample.as<float>());
                 QAMD_HIP(hipGetLastError());
             }
         }
-        if (staged) QAMD_HIP(hipStreamSynchronize(e->stream));  // the staging buffer is reused
-    }
+        return QAMD_OK;
+    }));
     e->observed += n_rows;
     return QAMD_OK;
 }
@@ -2339,22 +2283,15 @@ qamd_status qamd_u8_encoder_observe(qamd_u8_encoder *e, const float *batch, uint
 qamd_status qamd_u8_encoder_push(qamd_u8_encoder *e, const float *batch, uint64_t n_rows, qamd_mem batch_mem) {
     if (!e || (!batch && n_rows && e->vp.dim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     if (e->stop && e->stop(e->stop_user)) return fail(QAMD_ERR_STOPPED, "Stopped");  // :74-76
-    if (e->pushed + n_rows > e->vp.count)
-        return fail(QAMD_ERR_ARGUMENTS, "Vector count %llu does not match vector parameters count %llu",
-                    (unsigned long long)(e->pushed + n_rows), (unsigned long long)e->vp.count);
+    if (e->pushed + n_rows > e->vp.count) return count_mismatch(e->pushed + n_rows, e->vp.count);
     QAMD_ON_DEVICE(e->device);
     QAMD_TRY(encoder_close_pass1(e));
     const uint64_t dim = e->vp.dim;
     const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(kStagePieceBytes) / (dim * 4 + 1));
-    for (uint64_t r = 0; r < n_rows; r += piece_rows) {
-        const uint64_t nr = std::min(piece_rows, n_rows - r);
-        const void *src = nullptr;
-        bool staged = false;
-        QAMD_TRY(local_view(batch + r * dim, batch_mem, nr * dim * 4, e->stage, e->stream, &src, &staged));
-        QAMD_TRY(launch_quantize(e->h.get(), static_cast<const float *>(src), nr, e->pushed + r, e->alpha, e->offset,
-                                 e->stream));
-        if (staged) QAMD_HIP(hipStreamSynchronize(e->stream));
-    }
+    QAMD_TRY(for_each_staged_piece(batch, batch_mem, n_rows, dim, piece_rows, e->stage, e->stream,
+                                   [&](const float *src, uint64_t r, uint64_t nr) {
+        return launch_quantize(e->h.get(), src, nr, e->pushed + r, e->alpha, e->offset, e->stream);
+    }));
     e->pushed += n_rows;
     return QAMD_OK;
 }
@@ -2362,9 +2299,7 @@ qamd_status qamd_u8_encoder_push(qamd_u8_encoder *e, const float *batch, uint64_
 qamd_status qamd_u8_encoder_finish(qamd_u8_encoder *e, qamd_u8 **out) {
     if (!e || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     std::unique_ptr<qamd_u8_encoder> own(e);  // consumed whatever happens
-    if (e->pushed != e->vp.count)
-        return fail(QAMD_ERR_ARGUMENTS, "Vector count %llu does not match vector parameters count %llu",
-                    (unsigned long long)e->pushed, (unsigned long long)e->vp.count);
+    if (e->pushed != e->vp.count) return count_mismatch(e->pushed, e->vp.count);
     QAMD_ON_DEVICE(e->device);
     QAMD_HIP(hipStreamSynchronize(e->stream));
     if (e->vp.count == 0) {  // :43-54
@@ -2379,12 +2314,7 @@ qamd_status qamd_u8_encoder_finish(qamd_u8_encoder *e, qamd_u8 **out) {
     return QAMD_OK;
 }
 
-void qamd_u8_encoder_abort(qamd_u8_encoder *e) {
-    if (!e) return;
-    DeviceGuard g(e->device);
-    (void)hipStreamSynchronize(e->stream);  // kernels may still be writing into the store being dropped
-    delete e;
-}
+void qamd_u8_encoder_abort(qamd_u8_encoder *e) { abort_encoder(e); }
 
 }  // extern "C"
 
@@ -2398,14 +2328,9 @@ qamd_status u8_minmax_range(const float *data, qamd_mem mem, uint64_t n_rows, ui
     QAMD_TRY(acc.init(s));
     DevBuf stage;
     const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(kStagePieceBytes) / std::max<uint64_t>(dim * 4, 1));
-    for (uint64_t r = 0; r < n_rows && dim; r += piece_rows) {
-        const uint64_t nr = std::min(piece_rows, n_rows - r);
-        const void *src = nullptr;
-        bool staged = false;
-        QAMD_TRY(local_view(data + r * dim, mem, nr * dim * 4, stage, s, &src, &staged));
-        QAMD_TRY(acc.feed(static_cast<const float *>(src), nr * dim, s));
-        if (staged) QAMD_HIP(hipStreamSynchronize(s));
-    }
+    if (dim)
+        QAMD_TRY(for_each_staged_piece(data, mem, n_rows, dim, piece_rows, stage, s,
+                                       [&](const float *src, uint64_t, uint64_t nr) { return acc.feed(src, nr * dim, s); }));
     return acc.result(s, *mn, *mx);
 }
 
@@ -2478,12 +2403,8 @@ qamd_status u8_topk_ptrs(const qamd_u8 *h, const uint8_t *codes_dev, const float
     }
     if (fq) return fail(QAMD_ERR_ARGUMENTS, "a deferred query needs the single-launch path");
     if (!fused_capable(h)) {  // rare layouts: classic path only
-        float *scores = nullptr;
-        QAMD_TRY(thread_ws_acquire(WS_SCORES, std::max<uint64_t>(h->count, 1) * 4, s, reinterpret_cast<void **>(&scores)));
-        qamd_status st = scan_ptrs(h, qc, qo, scores, s);
-        if (st == QAMD_OK) st = topk_finish(scores, h->count, k, largest, out_ids, out_scores, out_mem, s);
-        thread_ws_release(WS_SCORES, s);
-        return st;
+        return topk_classic(h->count, k, largest, out_ids, out_scores, out_mem, s,
+                            [&](float *scores) { return scan_ptrs(h, qc, qo, scores, s); });
     }
     return fused_topk(h->count, k, largest, out_ids, out_scores, out_mem, s, scan);
 }

@@ -2985,9 +2985,8 @@ qamd_status qamd_u8_score_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, 
 qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, uint32_t k, int largest,
                                uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(check_batch(h, b));
-    if (k == 0 || b->n_queries == 0) return QAMD_OK;
-    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "topk: k=%u exceeds 1024", k);
-    if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null output");
+    qamd_status args = QAMD_OK;
+    if (!topk_wanted(k, b->n_queries, out_ids, out_scores, args)) return args;
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     const uint64_t Q = b->n_queries, n = h->count;

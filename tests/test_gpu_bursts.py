@@ -60,6 +60,7 @@ def test_u8_bursts_equal_the_per_pair_reference_calls(dim, dist, invert, qo):
         d_out = torch.empty(n_ids, dtype=torch.float32, device="cuda")
         enc.score_internal_ids(17, torch.from_numpy(ids.view(np.int32)).cuda(), out=d_out)
         assert_bits_equal(d_out.cpu().numpy(), got, "device ids")
+        assert_bits_equal(enc.score_internal_ids(17, torch.from_numpy(ids.view(np.int32)).cuda()), got, "device ids, host output")
     assert np.float32(enc.score_internal(17, int(ids[0]))).view(np.uint32) == got[:1].view(np.uint32)[0]
     # score_internal_ids_batch: many rows, each with its own list
     for n_lists, max_len in ((9, 12), (64, 40)):
