@@ -655,6 +655,116 @@ QAMD_API qamd_status qamd_pq_sharded_topk_batch(qamd_pq_sharded *h, const qamd_p
 QAMD_API void qamd_pq_sharded_free(qamd_pq_sharded *h);
 
 /* ===================================================================================
+ * Rescoring with the original f32 vectors.
+ *
+ * The caller of the reference over-fetches candidates from a quantized scan, scores them again
+ * with the original vectors and keeps the best k (demos/src/ann_benchmark_data.rs:151-185 counts
+ * what the quantized scan alone recovers).  The exact score is `DistanceType::distance`
+ * (quantization/src/encoded_vectors.rs:37-45, pub): the SEQUENTIAL f32 sum, from +0.0, of a*b
+ * (Dot), |a-b| (L1) or (a-b)*(a-b) (L2) over the dimensions, a = query, b = row -- negated when
+ * `invert` is set, which is the quantity every quantizer's score approximates, so `largest` means
+ * here what it means for the *_topk of the quantized store.  Every score is that sum bit for bit
+ * (no FMA contraction, no reassociation, subnormals kept).
+ *
+ * Out of scope: sharded handles (re-rank per shard with the shard's rows, or after the merge on
+ * one device); f16 / bf16 originals; originals resident in host memory (host `data` is copied to
+ * HBM); bench.py does not measure these calls.
+ * =================================================================================== */
+typedef struct qamd_f32 qamd_f32; /* count x dim f32 rows in HBM + VectorParameters (:13-19) */
+
+/* `data`: count x dim f32, row-major.  borrow = 0 copies it into library-owned HBM (host or
+ * device source).  borrow = 1 keeps the CALLER's pointer: legal only for device memory of the
+ * current device, which the caller keeps alive and unchanged while the handle is used (a 30 GB
+ * tensor is not duplicated); with host memory it returns QAMD_ERR_ARGUMENTS.  Rows need no
+ * alignment beyond 4 bytes.  vp->distance_type / invert fix the metric and its sign
+ * (encoded_vectors.rs:37-45); count < 2^32, dim < 2^31. */
+QAMD_API qamd_status qamd_f32_from_data(const float *data, qamd_mem data_mem,
+                                        const qamd_vector_parameters *vp, int borrow, void *stream,
+                                        qamd_f32 **out);
+QAMD_API qamd_status qamd_f32_get_parameters(const qamd_f32 *h, qamd_vector_parameters *out);
+QAMD_API void qamd_f32_free(qamd_f32 *h);
+
+/* out[p] = distance(query, row ids[p]) (encoded_vectors.rs:37-45), sign flipped for invert.
+ * Buffer rules of the quantizers' *_score_ids: host ids are validated (an id >= count returns
+ * QAMD_ERR_OUT_OF_RANGE), a device id >= count scores NaN; ids and out both in device memory and
+ * a device query only enqueue.  A host query is copied first (synchronises `stream`). */
+QAMD_API qamd_status qamd_f32_score_ids(const qamd_f32 *h, const float *query, uint64_t qdim,
+                                        qamd_mem query_mem, const uint32_t *ids, uint64_t n_ids,
+                                        qamd_mem ids_mem, float *out, qamd_mem out_mem, void *stream);
+/* Many (query, id list) pairs in one launch, as *_score_ids_batch: list l =
+ * ids[list_offsets[l] .. list_offsets[l + 1]) is scored against query l of `queries`
+ * ([n_queries][qdim] f32, n_lists <= n_queries); out[p] = distance(query l, row ids[p])
+ * (encoded_vectors.rs:37-45).  Device lists need a device output. */
+QAMD_API qamd_status qamd_f32_score_ids_batch(const qamd_f32 *h, const float *queries,
+                                              uint64_t n_queries, uint64_t qdim, qamd_mem queries_mem,
+                                              const uint32_t *list_offsets, uint32_t n_lists,
+                                              const uint32_t *ids, uint64_t n_ids, qamd_mem lists_mem,
+                                              float *out, qamd_mem out_mem, void *stream);
+
+/* The best k of the given ids by exact score (encoded_vectors.rs:37-45): ordering contract of the
+ * *_topk entry points -- best first, ties to the lower id, padded with id 0xFFFFFFFF and -inf
+ * (largest) / +inf when fewer than k ids are given.  k <= 1024, n_ids <= 8192 (the capacity of
+ * the candidate sort).  Id 0xFFFFFFFF, the padding *_topk writes, is skipped; any other host id
+ * >= count returns QAMD_ERR_OUT_OF_RANGE, such a device id takes part with a NaN score.  An id
+ * listed twice is returned twice.  With every buffer in device memory the call only enqueues;
+ * host outputs cost one download and synchronise `stream`. */
+QAMD_API qamd_status qamd_f32_rerank(const qamd_f32 *h, const float *query, uint64_t qdim,
+                                     qamd_mem query_mem, const uint32_t *ids, uint32_t n_ids,
+                                     qamd_mem ids_mem, uint32_t k, int largest, uint32_t *out_ids,
+                                     float *out_scores, qamd_mem out_mem, void *stream);
+/* The same for n_queries queries at once (encoded_vectors.rs:37-45): ids [n_queries][n_ids],
+ * outputs [n_queries][k]. */
+QAMD_API qamd_status qamd_f32_rerank_batch(const qamd_f32 *h, const float *queries, uint64_t n_queries,
+                                           uint64_t qdim, qamd_mem queries_mem, const uint32_t *ids,
+                                           uint32_t n_ids, qamd_mem ids_mem, uint32_t k, int largest,
+                                           uint32_t *out_ids, float *out_scores, qamd_mem out_mem,
+                                           void *stream);
+
+/* The fused call: rerank(orig, query_f32, ids of *_topk(h, q, candidates, largest), k) -- the
+ * over-fetch and exact re-scoring of a caller of ann_benchmark_data.rs:151-185, scores by
+ * encoded_vectors.rs:37-45.  `q` is the encoded form of `query_f32` (the caller encodes it as for
+ * *_topk).  k <= candidates <= 1024.  `orig` must agree with `h` in count, dim, distance type,
+ * invert and device, else QAMD_ERR_ARGUMENTS.  The candidate ids stay on the device (the calling
+ * thread's workspace); host outputs cost one download.  Like *_topk, the call synchronises
+ * `stream`.  Output contract as qamd_f32_rerank. */
+QAMD_API qamd_status qamd_u8_topk_rescored(const qamd_u8 *h, const qamd_u8_query *q, const qamd_f32 *orig,
+                                           const float *query_f32, uint64_t qdim, qamd_mem query_mem,
+                                           uint32_t k, uint32_t candidates, int largest,
+                                           uint32_t *out_ids, float *out_scores, qamd_mem out_mem,
+                                           void *stream);
+QAMD_API qamd_status qamd_pq_topk_rescored(const qamd_pq *h, const qamd_pq_query *q, const qamd_f32 *orig,
+                                           const float *query_f32, uint64_t qdim, qamd_mem query_mem,
+                                           uint32_t k, uint32_t candidates, int largest,
+                                           uint32_t *out_ids, float *out_scores, qamd_mem out_mem,
+                                           void *stream);
+QAMD_API qamd_status qamd_bin_topk_rescored(const qamd_bin *h, const qamd_bin_query *q, const qamd_f32 *orig,
+                                            const float *query_f32, uint64_t qdim, qamd_mem query_mem,
+                                            uint32_t k, uint32_t candidates, int largest,
+                                            uint32_t *out_ids, float *out_scores, qamd_mem out_mem,
+                                            void *stream);
+/* The fused call over *_topk_batch (ann_benchmark_data.rs:151-185, encoded_vectors.rs:37-45):
+ * queries_f32 [n_queries][qdim] are the f32 forms of the batch's queries, n_queries that of the
+ * batch; outputs [n_queries][k]. */
+QAMD_API qamd_status qamd_u8_topk_batch_rescored(const qamd_u8 *h, const qamd_u8_query_batch *b,
+                                                 const qamd_f32 *orig, const float *queries_f32,
+                                                 uint64_t n_queries, uint64_t qdim, qamd_mem queries_mem,
+                                                 uint32_t k, uint32_t candidates, int largest,
+                                                 uint32_t *out_ids, float *out_scores, qamd_mem out_mem,
+                                                 void *stream);
+QAMD_API qamd_status qamd_pq_topk_batch_rescored(const qamd_pq *h, const qamd_pq_query_batch *b,
+                                                 const qamd_f32 *orig, const float *queries_f32,
+                                                 uint64_t n_queries, uint64_t qdim, qamd_mem queries_mem,
+                                                 uint32_t k, uint32_t candidates, int largest,
+                                                 uint32_t *out_ids, float *out_scores, qamd_mem out_mem,
+                                                 void *stream);
+QAMD_API qamd_status qamd_bin_topk_batch_rescored(const qamd_bin *h, const qamd_bin_query_batch *b,
+                                                  const qamd_f32 *orig, const float *queries_f32,
+                                                  uint64_t n_queries, uint64_t qdim, qamd_mem queries_mem,
+                                                  uint32_t k, uint32_t candidates, int largest,
+                                                  uint32_t *out_ids, float *out_scores, qamd_mem out_mem,
+                                                  void *stream);
+
+/* ===================================================================================
  * Selection over an existing score array (device memory), e.g. after a multi-GPU gather.
  * Same ordering contract as the *_topk entry points.
  * =================================================================================== */

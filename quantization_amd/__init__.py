@@ -10,6 +10,7 @@ from .encoded_vectors import DistanceType, EncodingError, VectorParameters, get_
 from .encoded_vectors_binary import BitsStoreType, EncodedBinVector, EncodedVectorsBin  # noqa: F401
 from .encoded_vectors_pq import EncodedQueryPQ, EncodedVectorsPQ  # noqa: F401
 from .encoded_vectors_u8 import EncodedQueryBatchU8, EncodedQueryU8, EncodedVectorsU8  # noqa: F401
+from .original_vectors import OriginalVectors  # noqa: F401
 from .sharded_store import ShardedVectorsBin, ShardedVectorsPQ, ShardedVectorsU8  # noqa: F401
 
 
@@ -42,7 +43,7 @@ def topk_scores(scores, n: int, k: int, largest: bool = True, out_ids=None, out_
 __all__ = [
     "topk_scores", "set_device", "get_device", "thread_release",
     "ShardedVectorsU8", "ShardedVectorsBin", "ShardedVectorsPQ",
-    "DistanceType", "VectorParameters", "EncodingError",
+    "DistanceType", "VectorParameters", "EncodingError", "OriginalVectors",
     "EncodedVectorsU8", "EncodedQueryU8", "EncodedQueryBatchU8",
     "EncodedVectorsPQ", "EncodedQueryPQ",
     "EncodedVectorsBin", "EncodedBinVector", "BitsStoreType",

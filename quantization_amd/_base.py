@@ -200,6 +200,40 @@ class EncodedVectorsBase:
             return ids.reshape(nq, k), sc.reshape(nq, k)
         return ids, sc
 
+    # ------------------------------------------------------------------ rescoring with the original vectors
+    def topk_rescored(self, query, orig, query_f32, k: int, candidates: int, largest: bool = True, out_ids=None,
+                      out_scores=None, stream=None):
+        """orig.rerank(query_f32, ids of topk(query, candidates, largest), k) in one call: the candidates stay on the
+        device.  `query` is the encoded form of `query_f32`; `orig` the OriginalVectors of this store;
+        k <= candidates <= 1024.  Returns (ids, scores) with the exact scores."""
+        check_same_device(self._device, query_f32, out_ids, out_scores)
+        qb = in_buf(query_f32, np.float32)
+        qdim = int(query_f32.numel()) if hasattr(query_f32, "numel") else int(np.size(query_f32))
+        ib, ids = out_buf(out_ids, k, np.uint32)
+        sb, sc = out_buf(out_scores, k, np.float32)
+        if ib.mem != sb.mem:
+            raise ValueError("out_ids and out_scores must both be host or both be device buffers")
+        check(self._fn("topk_rescored")(self._h, query._h, orig._h, qb.ptr, qdim, qb.mem, int(k), int(candidates),
+                                        int(bool(largest)), ib.ptr, sb.ptr, sb.mem, stream_ptr(stream)))
+        return ids, sc
+
+    def topk_batch_rescored(self, batch, orig, queries_f32, k: int, candidates: int, largest: bool = True, out_ids=None,
+                            out_scores=None, stream=None):
+        """topk_rescored for every query of `batch`; `queries_f32` [n_queries, dim] are their f32 forms.  Returns
+        [n_queries, k] ids and scores."""
+        check_same_device(self._device, queries_f32, out_ids, out_scores)
+        nq, qdim = int(queries_f32.shape[0]), int(queries_f32.shape[1])
+        qb = in_buf(queries_f32, np.float32)
+        ib, ids = out_buf(out_ids, nq * k, np.uint32)
+        sb, sc = out_buf(out_scores, nq * k, np.float32)
+        if ib.mem != sb.mem:
+            raise ValueError("out_ids and out_scores must both be host or both be device buffers")
+        check(self._fn("topk_batch_rescored")(self._h, batch._h, orig._h, qb.ptr, nq, qdim, qb.mem, int(k), int(candidates),
+                                              int(bool(largest)), ib.ptr, sb.ptr, sb.mem, stream_ptr(stream)))
+        if isinstance(ids, np.ndarray):
+            return ids.reshape(nq, k), sc.reshape(nq, k)
+        return ids, sc
+
     def __del__(self):
         if getattr(self, "_h", None) and getattr(self, "_owned", True):
             try:

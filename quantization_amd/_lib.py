@@ -221,6 +221,20 @@ def lib() -> C.CDLL:
         "qamd_pq_sharded_query_batch_free": (None, [vp]),
         "qamd_pq_sharded_topk_batch": (i32, [vp, vp, u32, i32, vp, vp, i32, vp]),
         "qamd_pq_sharded_free": (None, [vp]),
+        # the original f32 vectors: exact scoring and re-ranking of what a quantized scan returns
+        "qamd_f32_from_data": (i32, [vp, i32, VP, i32, vp, pp]),
+        "qamd_f32_get_parameters": (i32, [vp, VP]),
+        "qamd_f32_free": (None, [vp]),
+        "qamd_f32_score_ids": (i32, [vp, vp, u64, i32, vp, u64, i32, vp, i32, vp]),
+        "qamd_f32_score_ids_batch": (i32, [vp, vp, u64, u64, i32, vp, u32, vp, u64, i32, vp, i32, vp]),
+        "qamd_f32_rerank": (i32, [vp, vp, u64, i32, vp, u32, i32, u32, i32, vp, vp, i32, vp]),
+        "qamd_f32_rerank_batch": (i32, [vp, vp, u64, u64, i32, vp, u32, i32, u32, i32, vp, vp, i32, vp]),
+        "qamd_u8_topk_rescored": (i32, [vp, vp, vp, vp, u64, i32, u32, u32, i32, vp, vp, i32, vp]),
+        "qamd_u8_topk_batch_rescored": (i32, [vp, vp, vp, vp, u64, u64, i32, u32, u32, i32, vp, vp, i32, vp]),
+        "qamd_pq_topk_rescored": (i32, [vp, vp, vp, vp, u64, i32, u32, u32, i32, vp, vp, i32, vp]),
+        "qamd_pq_topk_batch_rescored": (i32, [vp, vp, vp, vp, u64, u64, i32, u32, u32, i32, vp, vp, i32, vp]),
+        "qamd_bin_topk_rescored": (i32, [vp, vp, vp, vp, u64, i32, u32, u32, i32, vp, vp, i32, vp]),
+        "qamd_bin_topk_batch_rescored": (i32, [vp, vp, vp, vp, u64, u64, i32, u32, u32, i32, vp, vp, i32, vp]),
         "qamd_topk_scores": (i32, [vp, u64, u32, i32, vp, vp, i32, vp]),
         "qamd_topk_merge": (i32, [vp, vp, u64, vp, u32, u32, u32, i32, vp, vp, i32, vp]),
     }

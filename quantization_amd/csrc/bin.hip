@@ -30,6 +30,7 @@
 #include "multi_reduce.hpp"
 #include "topk.hpp"
 #include "topk_device.hpp"
+#include "rescore.hpp"
 
 #pragma clang fp contract(off)
 
@@ -2209,3 +2210,30 @@ extern "C" __attribute__((visibility("default"))) const void *qamd_dev_bin_query
     return q->buf.ptr;
 }
 #endif
+
+// ============================================================================= rescoring with the original vectors
+// rerank(orig, query_f32, ids of topk(h, q, candidates, largest), k): one body for the three quantizers (rescore.hpp).
+extern "C" qamd_status qamd_bin_topk_rescored(const qamd_bin *h, const qamd_bin_query *q, const qamd_f32 *orig,
+                                              const float *query_f32, uint64_t qdim, qamd_mem query_mem, uint32_t k,
+                                              uint32_t candidates, int largest, uint32_t *out_ids, float *out_scores,
+                                              qamd_mem out_mem, void *stream) {
+    if (!h || !q) return qamd::fail(QAMD_ERR_ARGUMENTS, "null handle or query");
+    return qamd::topk_rescored(h->device, h->vp, orig, query_f32, 1, qdim, query_mem, k, candidates, largest, out_ids,
+                               out_scores, out_mem, qamd::as_stream(stream), [&](uint32_t *ids_dev, float *scores_dev) {
+                                   return qamd_bin_topk(h, q, candidates, largest, ids_dev, scores_dev, QAMD_MEM_DEVICE, stream);
+                               });
+}
+
+extern "C" qamd_status qamd_bin_topk_batch_rescored(const qamd_bin *h, const qamd_bin_query_batch *b, const qamd_f32 *orig,
+                                                    const float *queries_f32, uint64_t n_queries, uint64_t qdim,
+                                                    qamd_mem queries_mem, uint32_t k, uint32_t candidates, int largest,
+                                                    uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
+    if (!h || !b) return qamd::fail(QAMD_ERR_ARGUMENTS, "null handle or query batch");
+    if (n_queries != b->n_queries)
+        return qamd::fail(QAMD_ERR_ARGUMENTS, "%llu f32 queries, but the batch holds %llu", (unsigned long long)n_queries,
+                          (unsigned long long)b->n_queries);
+    return qamd::topk_rescored(h->device, h->vp, orig, queries_f32, n_queries, qdim, queries_mem, k, candidates, largest,
+                               out_ids, out_scores, out_mem, qamd::as_stream(stream), [&](uint32_t *ids_dev, float *scores_dev) {
+                                   return qamd_bin_topk_batch(h, b, candidates, largest, ids_dev, scores_dev, QAMD_MEM_DEVICE, stream);
+                               });
+}

@@ -270,6 +270,39 @@ __global__ __launch_bounds__(1024) void pivot_kernel(const float *__restrict__ s
     if (t < (int)kTopkShards) st->counters[t * kTopkCounterStride] = 0;
 }
 
+// The candidate sort and emit of a 1024-thread workgroup: bitonic sort of the N keys (a power of two, unused slots ~0)
+// in LDS, then the k_eff best decoded (key = order-preserving score bits << 32 | id) and the rest of the k outputs
+// padded.  fused_emit_kernel and rerank_emit_kernel both end here: one ordering, one NaN and tie rule.
+__device__ __forceinline__ void sort_emit_lds(unsigned long long *s, uint32_t N, uint32_t k, uint32_t k_eff, int largest,
+                                              uint32_t *__restrict__ out_ids, float *__restrict__ out_scores) {
+    const int t = threadIdx.x;
+    for (uint32_t size = 2; size <= N; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+            for (uint32_t i = t; i < N / 2; i += 1024) {
+                // i-th compare-exchange of this stage: pair (a, a + stride)
+                const uint32_t a = 2 * i - (i & (stride - 1));
+                const uint32_t b = a + stride;
+                const bool up = (a & size) == 0;
+                const unsigned long long x = s[a], y = s[b];
+                if ((x > y) == up) {
+                    s[a] = y;
+                    s[b] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = t; i < k; i += 1024) {
+        if (i < k_eff) {
+            out_ids[i] = (uint32_t)(s[i] & 0xFFFFFFFFull);
+            out_scores[i] = topk_score_of_key((uint32_t)(s[i] >> 32), largest != 0);
+        } else {
+            out_ids[i] = 0xFFFFFFFFu;
+            out_scores[i] = largest ? -__builtin_huge_valf() : __builtin_huge_valf();
+        }
+    }
+}
+
 // One workgroup of 1024 threads: bitonic sort of the <= 8192 candidates in LDS, emit the k best.
 __global__ __launch_bounds__(1024) void fused_emit_kernel(const unsigned long long *__restrict__ cand,
                                                          FusedState *st, uint64_t n, uint32_t k, int largest,
@@ -347,31 +380,7 @@ __global__ __launch_bounds__(1024) void fused_emit_kernel(const unsigned long lo
         if (j < offs[sh + 1] - offs[sh]) s[offs[sh] + j] = cand[i];
     }
     __syncthreads();
-    for (uint32_t size = 2; size <= N; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            for (uint32_t i = t; i < N / 2; i += 1024) {
-                // i-th compare-exchange of this stage: pair (a, a + stride)
-                const uint32_t a = 2 * i - (i & (stride - 1));
-                const uint32_t b = a + stride;
-                const bool up = (a & size) == 0;
-                const unsigned long long x = s[a], y = s[b];
-                if ((x > y) == up) {
-                    s[a] = y;
-                    s[b] = x;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (uint32_t i = t; i < k; i += 1024) {
-        if (i < k_eff) {
-            out_ids[i] = (uint32_t)(s[i] & 0xFFFFFFFFull);
-            out_scores[i] = topk_score_of_key((uint32_t)(s[i] >> 32), largest != 0);
-        } else {
-            out_ids[i] = 0xFFFFFFFFu;
-            out_scores[i] = largest ? -__builtin_huge_valf() : __builtin_huge_valf();
-        }
-    }
+    sort_emit_lds(s, N, k, k_eff, largest, out_ids, out_scores);
     if (t == 0 && status_host) *status_host = 0;  // (pivot_kernel set st->status = 0)
 }
 
@@ -383,7 +392,51 @@ __global__ void sample_ids_kernel(uint32_t *ids, uint32_t S, uint64_t n) {
     ids[j] = (uint32_t)(((h >> 32) * n) >> 32);
 }
 
+// Re-ranking (rescore.hpp): workgroup q sorts the n_ids (id, exact score) pairs of query q and emits its k best.  The
+// padding id 0xFFFFFFFF is skipped (its slot keeps the empty key ~0, which sorts behind every real key).
+__global__ __launch_bounds__(1024) void rerank_emit_kernel(const uint32_t *__restrict__ ids, const float *__restrict__ scores,
+                                                          uint32_t n_ids, uint32_t k, int largest,
+                                                          uint32_t *__restrict__ out_ids, float *__restrict__ out_scores) {
+    __shared__ unsigned long long s[kTopkCandCap];
+    __shared__ uint32_t n_valid;
+    const uint32_t t = threadIdx.x;
+    const size_t q = blockIdx.x;
+    ids += q * n_ids;
+    scores += q * n_ids;
+    if (t == 0) n_valid = 0;
+    uint32_t N = 64;
+    while (N < n_ids) N <<= 1;
+    __syncthreads();
+    uint32_t mine = 0;
+    for (uint32_t i = t; i < N; i += 1024) {
+        unsigned long long key = ~0ull;
+        if (i < n_ids) {
+            const uint32_t id = ids[i];
+            if (id != 0xFFFFFFFFu) {
+                key = ((unsigned long long)topk_ordered_bits(scores[i], largest != 0) << 32) | id;
+                mine++;
+            }
+        }
+        s[i] = key;
+    }
+    if (mine) atomicAdd(&n_valid, mine);
+    __syncthreads();
+    const uint32_t k_eff = n_valid < k ? n_valid : k;
+    sort_emit_lds(s, N, k, k_eff, largest, out_ids + q * k, out_scores + q * k);
+}
+
 }  // namespace
+
+qamd_status rerank_sort_emit(const uint32_t *ids_dev, const float *scores_dev, uint32_t n_queries, uint32_t n_ids, uint32_t k,
+                             int largest, uint32_t *out_ids_dev, float *out_scores_dev, hipStream_t stream) {
+    if (n_queries == 0 || k == 0) return QAMD_OK;
+    if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "rerank: k=%u exceeds 1024", k);
+    if (n_ids > kTopkCandCap) return fail(QAMD_ERR_ARGUMENTS, "rerank: %u ids per query exceed %u", n_ids, kTopkCandCap);
+    hipLaunchKernelGGL(rerank_emit_kernel, dim3(n_queries), dim3(1024), 0, stream, ids_dev, scores_dev, n_ids, k, largest,
+                       out_ids_dev, out_scores_dev);
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
 
 // Sample size S and pivot rank r of the fused path; false = take the classic path.
 static bool fused_policy(uint64_t n, uint32_t k, uint32_t &S, uint32_t &r) {

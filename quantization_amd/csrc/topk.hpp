@@ -101,6 +101,12 @@ struct BatchScan {
 qamd_status fused_topk_batch(uint64_t n, uint32_t n_queries, uint32_t k, int largest, uint32_t *out_ids,
                              float *out_scores, qamd_mem out_mem, hipStream_t stream, const BatchScan &scan);
 
+// Re-ranking (rescore.hpp): per query q the k best of the n_ids <= 8192 pairs (ids_dev[q][i], scores_dev[q][i]) into
+// out_*_dev[q][0..k), by the candidate sort and emit of the fused top-k (same ordering contract by construction).  Id
+// 0xFFFFFFFF is skipped.  Device memory throughout; only enqueues on `stream`.
+qamd_status rerank_sort_emit(const uint32_t *ids_dev, const float *scores_dev, uint32_t n_queries, uint32_t n_ids, uint32_t k,
+                             int largest, uint32_t *out_ids_dev, float *out_scores_dev, hipStream_t stream);
+
 // Single-launch top-k for small stores (count <= 2M rows, k <= 64): one kernel scans the rows,
 // every wave keeps its own best 64 in registers (wave-level bitonic merges, topk_device.hpp), the
 // workgroup folds its 16 waves and the last workgroup to finish folds the workgroups' lists and

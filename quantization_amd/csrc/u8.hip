@@ -35,6 +35,7 @@
 #include "multi_reduce.hpp"
 #include "topk.hpp"
 #include "topk_device.hpp"
+#include "rescore.hpp"
 #include "u8_internal.hpp"
 
 #pragma clang fp contract(off)
@@ -2515,3 +2516,16 @@ extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_pack
     return h->last_scan_packed.load(std::memory_order_relaxed);
 }
 #endif
+
+// ============================================================================= rescoring with the original vectors
+// rerank(orig, query_f32, ids of topk(h, q, candidates, largest), k): one body for the three quantizers (rescore.hpp).
+extern "C" qamd_status qamd_u8_topk_rescored(const qamd_u8 *h, const qamd_u8_query *q, const qamd_f32 *orig,
+                                              const float *query_f32, uint64_t qdim, qamd_mem query_mem, uint32_t k,
+                                              uint32_t candidates, int largest, uint32_t *out_ids, float *out_scores,
+                                              qamd_mem out_mem, void *stream) {
+    if (!h || !q) return qamd::fail(QAMD_ERR_ARGUMENTS, "null handle or query");
+    return qamd::topk_rescored(h->device, h->meta.vector_parameters, orig, query_f32, 1, qdim, query_mem, k, candidates, largest, out_ids,
+                               out_scores, out_mem, qamd::as_stream(stream), [&](uint32_t *ids_dev, float *scores_dev) {
+                                   return qamd_u8_topk(h, q, candidates, largest, ids_dev, scores_dev, QAMD_MEM_DEVICE, stream);
+                               });
+}

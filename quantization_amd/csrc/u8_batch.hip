@@ -48,6 +48,7 @@
 #include "common.hpp"
 #include "topk.hpp"
 #include "topk_device.hpp"
+#include "rescore.hpp"
 #include "u8_internal.hpp"
 #include "batch_common.hpp"
 
@@ -3187,3 +3188,19 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
 }
 
 }  // extern "C"
+
+// ============================================================================= rescoring with the original vectors
+// The batched form of qamd_u8_topk_rescored (u8.hip): the same body (rescore.hpp) over qamd_u8_topk_batch.
+extern "C" qamd_status qamd_u8_topk_batch_rescored(const qamd_u8 *h, const qamd_u8_query_batch *b, const qamd_f32 *orig,
+                                                    const float *queries_f32, uint64_t n_queries, uint64_t qdim,
+                                                    qamd_mem queries_mem, uint32_t k, uint32_t candidates, int largest,
+                                                    uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
+    if (!h || !b) return qamd::fail(QAMD_ERR_ARGUMENTS, "null handle or query batch");
+    if (n_queries != b->n_queries)
+        return qamd::fail(QAMD_ERR_ARGUMENTS, "%llu f32 queries, but the batch holds %llu", (unsigned long long)n_queries,
+                          (unsigned long long)b->n_queries);
+    return qamd::topk_rescored(h->device, h->meta.vector_parameters, orig, queries_f32, n_queries, qdim, queries_mem, k, candidates, largest,
+                               out_ids, out_scores, out_mem, qamd::as_stream(stream), [&](uint32_t *ids_dev, float *scores_dev) {
+                                   return qamd_u8_topk_batch(h, b, candidates, largest, ids_dev, scores_dev, QAMD_MEM_DEVICE, stream);
+                               });
+}

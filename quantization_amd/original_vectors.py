@@ -1,0 +1,128 @@
+"""The original f32 vectors of a store, for exact re-scoring of what a quantized scan returns
+(`qamd_f32_*` in include/quantization_amd.h).  A score is `DistanceType::distance`
+(quantization/src/encoded_vectors.rs:37-45) of (query, row), negated for `invert`."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .encoded_vectors import (VectorParameters, check, check_same_device, creating_on, flatten_rows, in_buf, out_buf,
+                              stream_ptr, validate)
+
+MAX_RERANK_IDS = 8192
+PAD_ID = 0xFFFFFFFF
+
+
+def _count(x) -> int:
+    return int(x.numel()) if hasattr(x, "numel") else int(np.size(x))
+
+
+class OriginalVectors:
+    """count x dim f32 rows resident in HBM, with the metric (`distance_type`, `invert`) of the
+    quantized store they belong to."""
+
+    def __init__(self, handle: C.c_void_p, vector_parameters: VectorParameters, device: int | None, keep=None):
+        self._h = handle
+        self.vector_parameters = vector_parameters
+        self._device = device
+        self._keep = keep  # the borrowed tensor: the handle reads the caller's memory
+
+    @classmethod
+    def from_data(cls, data, vector_parameters: VectorParameters, borrow: bool = False, stream=None) -> "OriginalVectors":
+        """`data`: [count, dim] f32, numpy array or torch tensor.  borrow=False copies it into
+        library-owned HBM.  borrow=True keeps reading the caller's CUDA tensor, which this object
+        keeps referenced (no second copy of a 30 GB tensor); host data cannot be borrowed."""
+        data = flatten_rows(data, vector_parameters.dim)
+        validate(data, vector_parameters)
+        buf = in_buf(data, np.float32)
+        if borrow and buf.mem == _lib.MEM_DEVICE and buf.obj is not data:
+            raise ValueError("a borrowed tensor must be contiguous float32: the handle reads it in place")
+        vp = vector_parameters.to_c()
+        out = C.c_void_p()
+        with creating_on(data) as dev:
+            check(_lib.lib().qamd_f32_from_data(buf.ptr, buf.mem, C.byref(vp), int(bool(borrow)), stream_ptr(stream),
+                                                C.byref(out)))
+        return cls(out, vector_parameters, dev, keep=buf.obj if borrow else None)
+
+    @property
+    def device(self) -> int | None:
+        return self._device
+
+    @property
+    def count(self) -> int:
+        return int(self.vector_parameters.count)
+
+    def get_parameters(self) -> VectorParameters:
+        c = _lib.VectorParametersC()
+        check(_lib.lib().qamd_f32_get_parameters(self._h, C.byref(c)))
+        return VectorParameters.from_c(c)
+
+    def _query(self, q):
+        check_same_device(self._device, q)
+        return in_buf(q, np.float32)
+
+    def score_ids(self, query, ids, out=None, stream=None):
+        """scores[k] = distance(query, row ids[k]), exact."""
+        check_same_device(self._device, ids, out)
+        qb, ib = self._query(query), in_buf(ids, np.uint32)
+        n = _count(ids)
+        buf, ret = out_buf(out, n, np.float32)
+        check(_lib.lib().qamd_f32_score_ids(self._h, qb.ptr, _count(query), qb.mem, ib.ptr, n, ib.mem, buf.ptr, buf.mem,
+                                            stream_ptr(stream)))
+        return ret
+
+    def score_ids_batch(self, queries, list_offsets, ids, out=None, stream=None):
+        """List l = ids[list_offsets[l]:list_offsets[l + 1]] against query l of `queries` [n_queries, dim];
+        scores[p] = distance(query l, row ids[p])."""
+        check_same_device(self._device, list_offsets, ids, out)
+        qb, ob, ib = self._query(queries), in_buf(list_offsets, np.uint32), in_buf(ids, np.uint32)
+        if ob.mem != ib.mem:
+            raise ValueError("list_offsets and ids must both be host or both be device buffers")
+        nq, qdim = int(queries.shape[0]), int(queries.shape[1])
+        n_lists, n_ids = _count(list_offsets) - 1, _count(ids)
+        buf, ret = out_buf(out, n_ids, np.float32)
+        check(_lib.lib().qamd_f32_score_ids_batch(self._h, qb.ptr, nq, qdim, qb.mem, ob.ptr, n_lists, ib.ptr, n_ids,
+                                                  ib.mem, buf.ptr, buf.mem, stream_ptr(stream)))
+        return ret
+
+    def rerank(self, query, ids, k: int, largest: bool = True, out_ids=None, out_scores=None, stream=None):
+        """The best k of `ids` by exact score: best first, ties to the lower id, padded with 0xFFFFFFFF and
+        -inf / +inf; id 0xFFFFFFFF is skipped.  Returns (ids, scores)."""
+        check_same_device(self._device, ids, out_ids, out_scores)
+        qb, ib = self._query(query), in_buf(ids, np.uint32)
+        ob, ret_ids = out_buf(out_ids, k, np.uint32)
+        sb, ret_sc = out_buf(out_scores, k, np.float32)
+        if ob.mem != sb.mem:
+            raise ValueError("out_ids and out_scores must both be host or both be device buffers")
+        check(_lib.lib().qamd_f32_rerank(self._h, qb.ptr, _count(query), qb.mem, ib.ptr, _count(ids), ib.mem, int(k),
+                                         int(bool(largest)), ob.ptr, sb.ptr, sb.mem, stream_ptr(stream)))
+        return ret_ids, ret_sc
+
+    def rerank_batch(self, queries, ids, k: int, largest: bool = True, out_ids=None, out_scores=None, stream=None):
+        """rerank for queries [n_queries, dim] and ids [n_queries, n_ids]; returns [n_queries, k] ids and scores."""
+        check_same_device(self._device, ids, out_ids, out_scores)
+        nq, qdim = int(queries.shape[0]), int(queries.shape[1])
+        if int(ids.shape[0]) != nq:
+            raise ValueError("one id list per query")
+        n_ids = int(ids.shape[1])
+        qb, ib = self._query(queries), in_buf(ids, np.uint32)
+        ob, ret_ids = out_buf(out_ids, nq * k, np.uint32)
+        sb, ret_sc = out_buf(out_scores, nq * k, np.float32)
+        if ob.mem != sb.mem:
+            raise ValueError("out_ids and out_scores must both be host or both be device buffers")
+        check(_lib.lib().qamd_f32_rerank_batch(self._h, qb.ptr, nq, qdim, qb.mem, ib.ptr, n_ids, ib.mem, int(k),
+                                               int(bool(largest)), ob.ptr, sb.ptr, sb.mem, stream_ptr(stream)))
+        if isinstance(ret_ids, np.ndarray):
+            return ret_ids.reshape(nq, k), ret_sc.reshape(nq, k)
+        return ret_ids, ret_sc
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                _lib.lib().qamd_f32_free(self._h)
+            except Exception:  # interpreter shutdown
+                pass
+        self._h = None
+        self._keep = None

@@ -10,7 +10,12 @@ Beside every GPU figure the same protocol through the oracle's CPU loop (score_p
 for a few queries, with the ids compared.  For PQ the accuracy is also measured with centroids trained on a RANDOM
 10 000-row sample (what the reference draws, encoded_vectors_pq.rs:300-307) instead of this library's evenly strided one.
 
-    python tools/ann_protocol.py [--rows 1000000] [--dims 128,768] [--queries 200] [--cpu-queries 3] [--out FILE.jsonl]
+With --rescore CANDIDATES every variant is also run as `topk_rescored(30, CANDIDATES)`: the quantized scan over-fetches
+CANDIDATES rows and the f32 data, held as a borrowed `OriginalVectors`, re-ranks them exactly; its same_10 / 20 / 30 and
+timings are reported beside the unrescored ones ("gpu_rescored").
+
+    python tools/ann_protocol.py [--rows 1000000] [--dims 128,768] [--queries 200] [--cpu-queries 3] [--rescore 100]
+                                 [--out FILE.jsonl]
 """
 import sys as _sys
 if "--help" in _sys.argv[1:] or "-h" in _sys.argv[1:]:  # every tool answers --help without touching the GPU (tests/test_tools.py)
@@ -104,6 +109,20 @@ def run_gpu(enc, queries_host, truth, largest):
     return res, all_ids
 
 
+def run_gpu_rescored(enc, orig, queries_host, truth, largest, candidates):
+    """One search = encode_query + topk_rescored(30, candidates): host query in, host ids out."""
+    ms, same = [], np.zeros(3)
+    for j, q in enumerate(queries_host):
+        t0 = time.perf_counter()
+        ids, _ = enc.topk_rescored(enc.encode_query(q), orig, q, 30, candidates, largest=largest)
+        ms.append((time.perf_counter() - t0) * 1e3)
+        same += same_counts(ids, truth[j])
+    res = timings_summary(ms)
+    res.update({"candidates": candidates, "same_10": same[0] / len(queries_host), "same_20": same[1] / len(queries_host),
+                "same_30": same[2] / len(queries_host)})
+    return res
+
+
 def run_cpu(kind, enc, queries_host, truth, largest, gpu_ids, extra):
     """The reference's loop on one host core through the oracle: encode_query, score_point for every row
     (score_all = that loop), the caller's 30-entry heap (qo.topk_heap = ann_benchmark_data.rs:151-167)."""
@@ -148,6 +167,8 @@ def main():
     ap.add_argument("--quantizers", default="u8,pq,binary")
     ap.add_argument("--metrics", default="angular,euclidean")
     ap.add_argument("--pq-chunk", type=int, default=8)
+    ap.add_argument("--rescore", type=int, default=0, metavar="CANDIDATES",
+                    help="also run topk_rescored(30, CANDIDATES) against the f32 data (30 <= CANDIDATES <= 1024)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -171,6 +192,7 @@ def main():
             truth = exact_neighbours(data, queries, angular)
             q_host = queries.cpu().numpy()
             vp = qa.VectorParameters(dim, args.rows, dist, False)
+            orig = qa.OriginalVectors.from_data(data, vp, borrow=True) if args.rescore else None
             base = {"protocol": "ann_benchmark (demos/src/ann_benchmark_data.rs:93-185)", "rows": args.rows, "dim": dim,
                     "metric": metric, "distance_type": dist.name, "data": "seeded Gaussian mixture with low-rank clusters"}
             for kind in args.quantizers.split(","):
@@ -198,11 +220,15 @@ def main():
                         enc.topk(enc.encode_query(q_host[0]), 30, largest=largest)
                     gpu, gpu_ids = run_gpu(enc, q_host, truth, largest)
                     rec = dict(base, quantizer=name, gpu=gpu, encode_seconds_all_variants=round(encode_s, 3))
+                    if orig is not None:
+                        for _ in range(3):
+                            enc.topk_rescored(enc.encode_query(q_host[0]), orig, q_host[0], 30, args.rescore, largest=largest)
+                        rec["gpu_rescored"] = run_gpu_rescored(enc, orig, q_host, truth, largest, args.rescore)
                     if args.cpu_queries > 0:
                         rec["cpu_oracle_loop"] = run_cpu(kind, enc, q_host[: args.cpu_queries], truth, largest, gpu_ids, extra)
                     emit(rec)
                 del variants
-            del data, queries
+            del orig, data, queries
     if out:
         out.close()
 
