@@ -666,11 +666,23 @@ QAMD_API void qamd_pq_sharded_free(qamd_pq_sharded *h);
  * here what it means for the *_topk of the quantized store.  Every score is that sum bit for bit
  * (no FMA contraction, no reassociation, subnormals kept).
  *
+ * The originals may be kept as f16 or bf16 (qamd_f32_from_data_typed): half the resident bytes
+ * and half the bytes of the row gather.  The handle carries its element type; queries stay f32.
+ * A score is then the SAME function, `DistanceType::distance` (encoded_vectors.rs:37-45), of the
+ * f32 query and the row WIDENED EXACTLY to f32: the sequential f32 sum from +0.0, each product or
+ * difference rounded to f32 before its add, negated for `invert` -- bit for bit, no tolerance.
+ * Widening loses nothing: every f16 and bf16 value is an f32 value.  f16 subnormals widen to f32
+ * normals and are not flushed; bf16 subnormals are f32 subnormals and are kept.
+ *
  * Out of scope: sharded handles (re-rank per shard with the shard's rows, or after the merge on
- * one device); f16 / bf16 originals; originals resident in host memory (host `data` is copied to
- * HBM); bench.py does not measure these calls.
+ * one device); encoders that read f16 / bf16 source data (the quantizers encode from f32);
+ * originals resident in host memory (host `data` is copied to HBM); bench.py does not measure
+ * these calls.
  * =================================================================================== */
-typedef struct qamd_f32 qamd_f32; /* count x dim f32 rows in HBM + VectorParameters (:13-19) */
+typedef struct qamd_f32 qamd_f32; /* count x dim rows (f32, f16 or bf16) in HBM + VectorParameters (:13-19) */
+
+/* Element types of the originals.  F16 = IEEE binary16, BF16 = the upper 16 bits of an f32. */
+typedef enum { QAMD_DTYPE_F32 = 0, QAMD_DTYPE_F16 = 1, QAMD_DTYPE_BF16 = 2 } qamd_dtype;
 
 /* `data`: count x dim f32, row-major.  borrow = 0 copies it into library-owned HBM (host or
  * device source).  borrow = 1 keeps the CALLER's pointer: legal only for device memory of the
@@ -681,7 +693,22 @@ typedef struct qamd_f32 qamd_f32; /* count x dim f32 rows in HBM + VectorParamet
 QAMD_API qamd_status qamd_f32_from_data(const float *data, qamd_mem data_mem,
                                         const qamd_vector_parameters *vp, int borrow, void *stream,
                                         qamd_f32 **out);
+/* The same with element types: `data` holds count x dim values of `data_dtype`, the handle keeps
+ * them as `store_dtype`.  Allowed pairs: data_dtype == store_dtype (any of the three: the bytes are
+ * copied or borrowed as they are), F32 -> F16 and F32 -> BF16; any other pair returns
+ * QAMD_ERR_ARGUMENTS.  The narrowing pairs run on the device, piece by piece through the staging
+ * buffer for host data: round to nearest even, overflow to +-inf, NaN stays NaN (quiet), results
+ * in the subnormal range of the store type are kept.  borrow = 1 keeps its rules above, needs
+ * data_dtype == store_dtype and a pointer aligned to the element size.  qamd_f32_from_data is
+ * (F32, F32).  Every qamd_f32_* scoring call and the six *_rescored calls take such a handle:
+ * scores are `DistanceType::distance` (encoded_vectors.rs:37-45) of the f32 query and the row
+ * widened exactly to f32. */
+QAMD_API qamd_status qamd_f32_from_data_typed(const void *data, qamd_dtype data_dtype, qamd_mem data_mem,
+                                              const qamd_vector_parameters *vp, qamd_dtype store_dtype,
+                                              int borrow, void *stream, qamd_f32 **out);
 QAMD_API qamd_status qamd_f32_get_parameters(const qamd_f32 *h, qamd_vector_parameters *out);
+/* The element type the handle keeps its rows in. */
+QAMD_API qamd_status qamd_f32_get_dtype(const qamd_f32 *h, qamd_dtype *out);
 QAMD_API void qamd_f32_free(qamd_f32 *h);
 
 /* out[p] = distance(query, row ids[p]) (encoded_vectors.rs:37-45), sign flipped for invert.

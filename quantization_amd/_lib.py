@@ -16,6 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 
 MEM_HOST, MEM_DEVICE = 0, 1
 OK, ERR_IO, ERR_ENCODING, ERR_ARGUMENTS, ERR_STOPPED, ERR_OUT_OF_RANGE, ERR_DEVICE = range(7)
+DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2  # qamd_dtype: element types of the original vectors
 
 
 class VectorParametersC(C.Structure):
@@ -223,7 +224,9 @@ def lib() -> C.CDLL:
         "qamd_pq_sharded_free": (None, [vp]),
         # the original f32 vectors: exact scoring and re-ranking of what a quantized scan returns
         "qamd_f32_from_data": (i32, [vp, i32, VP, i32, vp, pp]),
+        "qamd_f32_from_data_typed": (i32, [vp, i32, i32, VP, i32, i32, vp, pp]),
         "qamd_f32_get_parameters": (i32, [vp, VP]),
+        "qamd_f32_get_dtype": (i32, [vp, C.POINTER(C.c_int)]),
         "qamd_f32_free": (None, [vp]),
         "qamd_f32_score_ids": (i32, [vp, vp, u64, i32, vp, u64, i32, vp, i32, vp]),
         "qamd_f32_score_ids_batch": (i32, [vp, vp, u64, u64, i32, vp, u32, vp, u64, i32, vp, i32, vp]),

@@ -13,6 +13,29 @@
 // carrying the partial sum from segment to segment.  The loads of the next segment are issued before the adds
 // of the current one.  The query value of a step is wave-uniform when all 64 pairs belong to one list (a scalar
 // load); a wave that straddles lists reads it per lane.
+//
+// half_pairs_kernel: the same scheme for rows kept as f16 or bf16 (qamd_f32_from_data_typed).  A score is the same
+// sequential f32 sum over the row WIDENED EXACTLY to f32 (v_cvt_f32_f16, which keeps f16 subnormals: they are f32
+// normals; a bf16 is the upper half of an f32: a shift or a mask), so every product or difference is still rounded to
+// f32 before its add and the result equals qo_metric_f32 of the widened row bit for bit.  The tile is redesigned for
+// 2-byte elements: 128 coalesced bytes of a row are 64 values, so a segment is 64 values and a row needs half as many
+// passes, loads and LDS operations per value as an f32 row.
+//  * Loads.  dim even (and a dword-aligned base): every row starts on a dword, lane j of a half-wave loads the
+//    packed pair (2j, 2j + 1) with one dword load - 32 dword loads per lane cover the wave's 64 rows, as for f32.
+//    dim odd: every other row starts 2 bytes off a dword, so the same dword loads are issued at 2-byte aligned
+//    addresses (global memory takes them: the compiler emits them for an align-2 copy of 4 bytes; such a load costs a
+//    second cache-line access only where it straddles one), and only pairs that lie inside the row are loaded: the
+//    last value of an odd row is read once by the lane that owns the row, a 2-byte load.  Only this shape pays for it.
+//  * LDS.  The tile holds the PACKED dwords, not widened f32: 64 rows x 33 dwords per wave, the f32 kernel's 8448
+//    bytes for twice the values (widened values would need 65 dwords per row: 2 workgroups per CU less).  Bank
+//    arithmetic as above: ds_write_b32 / ds_read_b32 bank = dword address mod 32 over groups of 32 lanes; a
+//    half-wave writes the 32 consecutive dwords (2i + half) * 33 + col, col = 0..31: 32 banks; lane r reads
+//    r * 33 + c, bank (r + c) mod 32: 32 banks over r = 0..31 and over r = 32..63.  Both conflict-free.  Lane r
+//    widens the low half, adds its term, widens the high half, adds its term: the row's order.
+//  * The loads of the next segment are issued before the adds of the current one; the wave-uniform (scalar) query
+//    path and the per-lane path are those of the f32 kernel.
+// narrow_kernel: the F32 -> F16 / BF16 copy of qamd_f32_from_data_typed, a streaming kernel (16-byte loads, 8-byte
+// stores where the piece is aligned for them).
 #include "rescore.hpp"
 
 #include "lists.hpp"
@@ -101,14 +124,188 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     if (in_range) out[p] = valid ? (invert ? -sum : sum) : __builtin_nanf("");
 }
 
+constexpr int kHalfSeg = 64;  // values of an f16 / bf16 row per pass: 128 bytes, 32 packed dwords
+
+// The two 16-bit values of a packed dword, widened exactly to f32.
+template <int DTYPE> __device__ __forceinline__ float widen_lo(uint32_t w) {
+    if (DTYPE == QAMD_DTYPE_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu));
+    return __uint_as_float(w << 16);
+}
+template <int DTYPE> __device__ __forceinline__ float widen_hi(uint32_t w) {
+    if (DTYPE == QAMD_DTYPE_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
+    return __uint_as_float(w & 0xFFFF0000u);
+}
+
+// f32_pairs_kernel for rows of 16-bit values (DTYPE: QAMD_DTYPE_F16 or QAMD_DTYPE_BF16).  ALIGNED: dim is even and
+// `data` is dword aligned, so every row starts on a dword.
+template <int METRIC, int DTYPE, bool ALIGNED>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void half_pairs_kernel(
+    const uint16_t *__restrict__ data, uint32_t dim, uint32_t count, const float *__restrict__ queries,
+    const uint32_t *__restrict__ offsets, uint32_t n_lists, uint32_t per_list, const uint32_t *__restrict__ ids,
+    uint32_t n_pairs, int invert, float *__restrict__ out) {
+    __shared__ uint32_t tiles[kBlock / 64][64 * kTileStride];
+    __shared__ uint32_t first_list;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t *tile = tiles[wave];
+    const uint32_t p0 = blockIdx.x * (uint32_t)kBlock;
+    const uint32_t p = p0 + threadIdx.x;
+    const bool in_range = p < n_pairs;
+    uint32_t l = 0;
+    if (offsets) {
+        l = first_list_of_block(offsets, n_lists, p0, &first_list);
+        if (in_range) l = advance_list(offsets, n_lists, l, p);
+    } else if (in_range) {
+        l = p / per_list;
+    }
+    const uint32_t id = in_range ? ids[p] : 0xFFFFFFFFu;
+    const bool valid = id < count;
+    const uint32_t n_here = n_pairs - min(n_pairs, p0 + (uint32_t)wave * 64u);  // pairs at or after the wave's first
+    const int last_lane = n_here >= 64 ? 63 : (n_here ? (int)n_here - 1 : 0);
+    const uint32_t l_first = (uint32_t)__shfl((int)l, 0, 64), l_last = (uint32_t)__shfl((int)l, last_lane, 64);
+    const bool one_query = l_first == l_last;
+    const float *__restrict__ q_wave = queries + (size_t)__builtin_amdgcn_readfirstlane((int)l_first) * dim;
+    const float *__restrict__ q_lane = queries + (size_t)l * dim;
+
+    // lane j loads the packed pair (2 * (j & 31), + 1) of the rows 2i + (j >> 5), i = 0..31
+    const int col = lane & 31, half = lane >> 5;
+    uint32_t row_id[kSeg];
+#pragma unroll
+    for (int i = 0; i < kSeg; i++) row_id[i] = (uint32_t)__shfl((int)id, 2 * i + half, 64);
+    uint32_t next[kSeg];
+    auto load_segment = [&](uint32_t d0) {
+        const uint32_t d = d0 + 2u * (uint32_t)col;
+#pragma unroll
+        for (int i = 0; i < kSeg; i++) {
+            const size_t at = (size_t)row_id[i] * dim + d;
+            uint32_t w = 0;
+            if (row_id[i] < count && d + 1 < dim) {  // a pair inside the row; the last value of an odd dim is `last`
+                if (ALIGNED) w = reinterpret_cast<const uint32_t *>(data)[at >> 1];  // dim and d are even: so is `at`
+                else __builtin_memcpy(&w, data + at, 4);  // one dword load at a 2-byte aligned address
+            }
+            next[i] = w;
+        }
+    };
+    // odd dim: the row's last value has no partner; its lane loads it once
+    const float last = (valid && (dim & 1u)) ? widen_lo<DTYPE>(data[(size_t)id * dim + (dim - 1)]) : 0.0f;
+    float sum = 0.0f;
+    // the n values from d0 on, in the row's order: low half, then high half of each packed dword
+    auto add_terms = [&](const float *__restrict__ q, const uint32_t *mine, uint32_t d0, uint32_t n) {
+        uint32_t c = 0;
+        for (; c + 1 < n; c += 2) {
+            const uint32_t w = mine[c >> 1];
+            sum += term<METRIC>(q[d0 + c], widen_lo<DTYPE>(w));
+            sum += term<METRIC>(q[d0 + c + 1], widen_hi<DTYPE>(w));
+        }
+        if (c < n) sum += term<METRIC>(q[d0 + c], last);  // n is odd only at the end of a row of odd dim
+    };
+    load_segment(0);
+    for (uint32_t d0 = 0; d0 < dim; d0 += kHalfSeg) {
+#pragma unroll
+        for (int i = 0; i < kSeg; i++) tile[(2 * i + half) * kTileStride + col] = next[i];
+        __syncthreads();
+        if (d0 + kHalfSeg < dim) load_segment(d0 + kHalfSeg);
+        const uint32_t *mine = tile + lane * kTileStride;
+        const uint32_t n = min((uint32_t)kHalfSeg, dim - d0);
+        if (one_query) {
+            if (n == kHalfSeg) {
+#pragma unroll
+                for (int c = 0; c < kSeg; c++) {
+                    const uint32_t w = mine[c];
+                    sum += term<METRIC>(q_wave[d0 + 2 * c], widen_lo<DTYPE>(w));
+                    sum += term<METRIC>(q_wave[d0 + 2 * c + 1], widen_hi<DTYPE>(w));
+                }
+            } else {
+                add_terms(q_wave, mine, d0, n);
+            }
+        } else if (in_range) {
+            add_terms(q_lane, mine, d0, n);
+        }
+        __syncthreads();
+    }
+    if (in_range) out[p] = valid ? (invert ? -sum : sum) : __builtin_nanf("");
+}
+
+// f32 -> f16 / bf16: round to nearest even, overflow to +-inf, NaN stays NaN, subnormal results kept.
+template <int DTYPE> __device__ __forceinline__ uint32_t narrow(float x) {
+    if (DTYPE == QAMD_DTYPE_F16) return __builtin_bit_cast(uint16_t, (_Float16)x);  // v_cvt_f16_f32 in the default mode
+    const uint32_t u = __float_as_uint(x);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x0040u;  // a NaN whose payload sits in the low bits stays one
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;                    // the carry out of the mantissa is the overflow to inf
+}
+
+// dst[i] = narrow(src[i]), i < n.  VEC: src is 16-byte and dst 8-byte aligned.
+template <int DTYPE, bool VEC>
+__global__ __launch_bounds__(kBlock) void narrow_kernel(const float *__restrict__ src, uint16_t *__restrict__ dst, uint64_t n) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock, t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    uint64_t done = 0;
+    if (VEC) {
+        const uint64_t n4 = n / 4;
+        for (uint64_t i = t; i < n4; i += stride) {
+            const float4 v = reinterpret_cast<const float4 *>(src)[i];
+            uint2 o;
+            o.x = narrow<DTYPE>(v.x) | (narrow<DTYPE>(v.y) << 16);
+            o.y = narrow<DTYPE>(v.z) | (narrow<DTYPE>(v.w) << 16);
+            reinterpret_cast<uint2 *>(dst)[i] = o;
+        }
+        done = n4 * 4;
+    }
+    for (uint64_t i = done + t; i < n; i += stride) dst[i] = (uint16_t)narrow<DTYPE>(src[i]);
+}
+
+qamd_status narrow_launch(const float *src, uint16_t *dst, uint64_t n, qamd_dtype to, hipStream_t s) {
+    if (n == 0) return QAMD_OK;
+    const bool vec = reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 8 == 0;
+    const uint64_t per_block = (uint64_t)kBlock * (vec ? 4 : 1);
+    const unsigned grid = (unsigned)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)device_info().cu_count * 16);
+#define QAMD_NARROW_GO(T, V) hipLaunchKernelGGL((narrow_kernel<T, V>), dim3(grid), dim3(kBlock), 0, s, src, dst, n)
+    if (to == QAMD_DTYPE_F16) {
+        if (vec) QAMD_NARROW_GO(QAMD_DTYPE_F16, true);
+        else QAMD_NARROW_GO(QAMD_DTYPE_F16, false);
+    } else {
+        if (vec) QAMD_NARROW_GO(QAMD_DTYPE_BF16, true);
+        else QAMD_NARROW_GO(QAMD_DTYPE_BF16, false);
+    }
+#undef QAMD_NARROW_GO
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
+
+template <int DTYPE>
+void half_pairs_go(const qamd_f32 *h, unsigned grid, const float *queries_dev, const uint32_t *offsets, uint32_t n_lists,
+                   uint32_t per_list, const uint32_t *ids_dev, uint32_t n_pairs, float *out_dev, hipStream_t s) {
+    const bool aligned = h->vp.dim % 2 == 0 && reinterpret_cast<uintptr_t>(h->data) % 4 == 0;
+#define QAMD_HALF_GO(M, A)                                                                                              \
+    hipLaunchKernelGGL((half_pairs_kernel<M, DTYPE, A>), dim3(grid), dim3(kBlock), 0, s,                                \
+                       static_cast<const uint16_t *>(h->data), (uint32_t)h->vp.dim, (uint32_t)h->vp.count, queries_dev, \
+                       offsets, n_lists, per_list, ids_dev, n_pairs, (int)(h->vp.invert != 0), out_dev)
+#define QAMD_HALF_GO_M(M)              \
+    do {                               \
+        if (aligned) QAMD_HALF_GO(M, true); \
+        else QAMD_HALF_GO(M, false);   \
+    } while (0)
+    if (h->vp.distance_type == QAMD_DOT) QAMD_HALF_GO_M(QAMD_DOT);
+    else if (h->vp.distance_type == QAMD_L1) QAMD_HALF_GO_M(QAMD_L1);
+    else QAMD_HALF_GO_M(QAMD_L2);
+#undef QAMD_HALF_GO_M
+#undef QAMD_HALF_GO
+}
+
 qamd_status pairs_launch(const qamd_f32 *h, const float *queries_dev, const uint32_t *offsets, uint32_t n_lists,
                          uint32_t per_list, const uint32_t *ids_dev, uint64_t n_pairs, float *out_dev, hipStream_t s) {
     if (n_pairs == 0) return QAMD_OK;
     const unsigned grid = (unsigned)((n_pairs + kBlock - 1) / kBlock);
+    if (h->dtype != QAMD_DTYPE_F32) {
+        if (h->dtype == QAMD_DTYPE_F16)
+            half_pairs_go<QAMD_DTYPE_F16>(h, grid, queries_dev, offsets, n_lists, per_list, ids_dev, (uint32_t)n_pairs, out_dev, s);
+        else
+            half_pairs_go<QAMD_DTYPE_BF16>(h, grid, queries_dev, offsets, n_lists, per_list, ids_dev, (uint32_t)n_pairs, out_dev, s);
+        QAMD_HIP(hipGetLastError());
+        return QAMD_OK;
+    }
 #define QAMD_F32_GO(M)                                                                                                  \
-    hipLaunchKernelGGL(f32_pairs_kernel<M>, dim3(grid), dim3(kBlock), 0, s, h->data, (uint32_t)h->vp.dim,               \
-                       (uint32_t)h->vp.count, queries_dev, offsets, n_lists, per_list, ids_dev, (uint32_t)n_pairs,      \
-                       (int)(h->vp.invert != 0), out_dev)
+    hipLaunchKernelGGL(f32_pairs_kernel<M>, dim3(grid), dim3(kBlock), 0, s, static_cast<const float *>(h->data),        \
+                       (uint32_t)h->vp.dim, (uint32_t)h->vp.count, queries_dev, offsets, n_lists, per_list, ids_dev,    \
+                       (uint32_t)n_pairs, (int)(h->vp.invert != 0), out_dev)
     if (h->vp.distance_type == QAMD_DOT) QAMD_F32_GO(QAMD_DOT);
     else if (h->vp.distance_type == QAMD_L1) QAMD_F32_GO(QAMD_L1);
     else QAMD_F32_GO(QAMD_L2);
@@ -201,22 +398,38 @@ qamd_status rerank_device(const qamd_f32 *orig, const float *queries_dev, uint32
 
 using namespace qamd;
 
-extern "C" {
+namespace {
+
+size_t dtype_size(qamd_dtype t) { return t == QAMD_DTYPE_F32 ? 4 : 2; }
+const char *dtype_name(qamd_dtype t) { return t == QAMD_DTYPE_F32 ? "f32" : t == QAMD_DTYPE_F16 ? "f16" : "bf16"; }
+bool dtype_known(qamd_dtype t) { return t == QAMD_DTYPE_F32 || t == QAMD_DTYPE_F16 || t == QAMD_DTYPE_BF16; }
 
 // The originals of a store: `distance_type` and `invert` of `vp` fix what a score is - DistanceType::distance
-// (encoded_vectors.rs:37-45) of (query, row), negated for invert: the quantity every quantizer's score approximates.
-qamd_status qamd_f32_from_data(const float *data, qamd_mem data_mem, const qamd_vector_parameters *vp, int borrow,
-                               void *stream, qamd_f32 **out) {
+// (encoded_vectors.rs:37-45) of (query, row widened to f32), negated for invert: the quantity every quantizer's score
+// approximates.  `data` holds `data_dtype` values; the handle keeps `store_dtype`.
+qamd_status from_data_any(const void *data, qamd_dtype data_dtype, qamd_mem data_mem, const qamd_vector_parameters *vp,
+                          qamd_dtype store_dtype, int borrow, void *stream, qamd_f32 **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     *out = nullptr;
     if (vp->distance_type != QAMD_DOT && vp->distance_type != QAMD_L1 && vp->distance_type != QAMD_L2)
         return fail(QAMD_ERR_ARGUMENTS, "unknown distance type %d", (int)vp->distance_type);
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "at most 2^32 - 1 vectors");  // 0xFFFFFFFF is the padding id
     if (vp->dim > 0x7FFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "at most 2^31 - 1 dimensions");
+    if (!dtype_known(data_dtype) || !dtype_known(store_dtype))
+        return fail(QAMD_ERR_ARGUMENTS, "unknown element type (data %d, store %d)", (int)data_dtype, (int)store_dtype);
+    if (data_dtype != store_dtype && data_dtype != QAMD_DTYPE_F32)
+        return fail(QAMD_ERR_ARGUMENTS, "%s data cannot be kept as %s: only f32 data is converted", dtype_name(data_dtype),
+                    dtype_name(store_dtype));
     const uint64_t n = vp->count * vp->dim;
     if (n && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
     if (borrow && data_mem != QAMD_MEM_DEVICE)
         return fail(QAMD_ERR_ARGUMENTS, "only device memory can be borrowed: host originals are copied (borrow = 0)");
+    if (borrow && data_dtype != store_dtype)
+        return fail(QAMD_ERR_ARGUMENTS, "borrowed %s data cannot be kept as %s: a borrowed buffer is read in place",
+                    dtype_name(data_dtype), dtype_name(store_dtype));
+    const size_t esize = dtype_size(store_dtype);
+    if (borrow && reinterpret_cast<uintptr_t>(data) % esize)
+        return fail(QAMD_ERR_ARGUMENTS, "borrowed %s data must be aligned to %zu bytes", dtype_name(store_dtype), esize);
     const int device = current_device();
     QAMD_ON_DEVICE(device);
     if (borrow && n) {
@@ -231,16 +444,50 @@ qamd_status qamd_f32_from_data(const float *data, qamd_mem data_mem, const qamd_
     std::unique_ptr<qamd_f32> h(new qamd_f32);
     h->device = device;
     h->vp = *vp;
+    h->dtype = store_dtype;
     if (borrow) {
         h->data = data;
     } else {
         hipStream_t s = as_stream(stream);
-        QAMD_TRY(h->owned.alloc(std::max<uint64_t>(n, 1) * 4));
-        QAMD_TRY(copy_in(h->owned.ptr, data, data_mem, n * 4, s));
-        if (data_mem == QAMD_MEM_DEVICE) QAMD_HIP(hipStreamSynchronize(s));  // the caller may free its copy on return
-        h->data = h->owned.as<float>();
+        QAMD_TRY(h->owned.alloc(std::max<uint64_t>(n, 1) * esize));
+        if (data_dtype == store_dtype) {
+            QAMD_TRY(copy_in(h->owned.ptr, data, data_mem, n * esize, s));
+        } else if (n) {  // narrowed on the device, piece by piece: pieces of a multiple of 4 rows keep the 8-byte stores
+            uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / (vp->dim * 4));
+            if (piece_rows > 4) piece_rows -= piece_rows % 4;
+            DevBuf stage;
+            uint16_t *dst = h->owned.as<uint16_t>();
+            QAMD_TRY(for_each_staged_piece(static_cast<const float *>(data), data_mem, vp->count, vp->dim, piece_rows, stage, s,
+                                           [&](const float *src, uint64_t first_row, uint64_t nr) {
+                                               return narrow_launch(src, dst + first_row * vp->dim, nr * vp->dim, store_dtype, s);
+                                           }));
+        }
+        // the caller may free its copy on return, and `stage` goes out of scope
+        if (data_mem == QAMD_MEM_DEVICE || data_dtype != store_dtype) QAMD_HIP(hipStreamSynchronize(s));
+        h->data = h->owned.ptr;
     }
     *out = h.release();
+    return QAMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+qamd_status qamd_f32_from_data(const float *data, qamd_mem data_mem, const qamd_vector_parameters *vp, int borrow,
+                               void *stream, qamd_f32 **out) {
+    return from_data_any(data, QAMD_DTYPE_F32, data_mem, vp, QAMD_DTYPE_F32, borrow, stream, out);
+}
+
+qamd_status qamd_f32_from_data_typed(const void *data, qamd_dtype data_dtype, qamd_mem data_mem,
+                                     const qamd_vector_parameters *vp, qamd_dtype store_dtype, int borrow, void *stream,
+                                     qamd_f32 **out) {
+    return from_data_any(data, data_dtype, data_mem, vp, store_dtype, borrow, stream, out);
+}
+
+qamd_status qamd_f32_get_dtype(const qamd_f32 *h, qamd_dtype *out) {
+    if (!h || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    *out = h->dtype;
     return QAMD_OK;
 }
 

@@ -1,5 +1,5 @@
-// Rescoring with the original f32 vectors (f32.hip): the store of originals, the device-side re-rank that the
-// fused calls feed, and the one body of qamd_{u8,pq,bin}_topk_rescored / _topk_batch_rescored.
+// Rescoring with the original vectors, kept as f32, f16 or bf16 (f32.hip): the store of originals, the device-side
+// re-rank that the fused calls feed, and the one body of qamd_{u8,pq,bin}_topk_rescored / _topk_batch_rescored.
 //
 // The caller of the reference over-fetches from the quantized scan and scores the candidates again with
 // DistanceType::distance (quantization/src/encoded_vectors.rs:37-45) on the original vectors
@@ -9,12 +9,13 @@
 #include "common.hpp"
 #include "topk_device.hpp"
 
-// The originals: count x dim f32, row-major, in HBM of `device`.  `data` is `owned.ptr` (borrow = 0) or the
-// caller's pointer (borrow = 1: the caller keeps it alive).
+// The originals: count x dim values of `dtype` (f32, or f16 / bf16 as 16-bit patterns), row-major, in HBM of
+// `device`.  `data` is `owned.ptr` (borrow = 0) or the caller's pointer (borrow = 1: the caller keeps it alive).
 struct qamd_f32 {
     int device = 0;
     qamd_vector_parameters vp{};
-    const float *data = nullptr;
+    qamd_dtype dtype = QAMD_DTYPE_F32;
+    const void *data = nullptr;
     qamd::DevBuf owned;
 };
 

@@ -1,6 +1,6 @@
-"""The original f32 vectors of a store, for exact re-scoring of what a quantized scan returns
+"""The original vectors of a store, kept as f32, f16 or bf16, for exact re-scoring of what a quantized scan returns
 (`qamd_f32_*` in include/quantization_amd.h).  A score is `DistanceType::distance`
-(quantization/src/encoded_vectors.rs:37-45) of (query, row), negated for `invert`."""
+(quantization/src/encoded_vectors.rs:37-45) of (f32 query, row widened exactly to f32), negated for `invert`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -8,11 +8,29 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .encoded_vectors import (VectorParameters, check, check_same_device, creating_on, flatten_rows, in_buf, out_buf,
+from .encoded_vectors import (Buf, VectorParameters, check, check_same_device, creating_on, flatten_rows, in_buf, out_buf,
                               stream_ptr, validate)
 
 MAX_RERANK_IDS = 8192
 PAD_ID = 0xFFFFFFFF
+
+
+DTYPES = {"f32": _lib.DTYPE_F32, "f16": _lib.DTYPE_F16, "bf16": _lib.DTYPE_BF16}
+
+
+def _element_type(x) -> str | None:
+    """ "f32" / "f16" / "bf16" for float data of that type, "u16" for numpy uint16, None for anything else."""
+    name = str(x.dtype).replace("torch.", "")
+    return {"float32": "f32", "float16": "f16", "bfloat16": "bf16", "uint16": "u16"}.get(name)
+
+
+def _raw_buf(x) -> Buf:
+    """`x` (f16 / bf16 values or uint16 bit patterns) as it lies in memory, made contiguous."""
+    if isinstance(x, np.ndarray):
+        a = np.ascontiguousarray(x)
+        return Buf(C.c_void_p(a.ctypes.data), _lib.MEM_HOST, a)
+    t = x.contiguous()
+    return Buf(C.c_void_p(t.data_ptr()), _lib.MEM_DEVICE if t.is_cuda else _lib.MEM_HOST, t)
 
 
 def _count(x) -> int:
@@ -20,7 +38,7 @@ def _count(x) -> int:
 
 
 class OriginalVectors:
-    """count x dim f32 rows resident in HBM, with the metric (`distance_type`, `invert`) of the
+    """count x dim rows (f32, f16 or bf16) resident in HBM, with the metric (`distance_type`, `invert`) of the
     quantized store they belong to."""
 
     def __init__(self, handle: C.c_void_p, vector_parameters: VectorParameters, device: int | None, keep=None):
@@ -30,21 +48,51 @@ class OriginalVectors:
         self._keep = keep  # the borrowed tensor: the handle reads the caller's memory
 
     @classmethod
-    def from_data(cls, data, vector_parameters: VectorParameters, borrow: bool = False, stream=None) -> "OriginalVectors":
-        """`data`: [count, dim] f32, numpy array or torch tensor.  borrow=False copies it into
-        library-owned HBM.  borrow=True keeps reading the caller's CUDA tensor, which this object
-        keeps referenced (no second copy of a 30 GB tensor); host data cannot be borrowed."""
+    def from_data(cls, data, vector_parameters: VectorParameters, borrow: bool = False, stream=None,
+                  dtype: str | None = None) -> "OriginalVectors":
+        """`data`: [count, dim], numpy array or torch tensor.  borrow=False copies it into library-owned HBM.
+        borrow=True keeps reading the caller's CUDA tensor, which this object keeps referenced (no second copy of a
+        30 GB tensor); host data cannot be borrowed.
+
+        `dtype`: what the store keeps - "f32", "f16" or "bf16"; None = f32 from whatever is given.  f16 / bf16 rows
+        take half the HBM and score as their exact f32 widening.  With a `dtype`, data that is already f16 (numpy /
+        torch float16) or bf16 (torch bfloat16, or numpy uint16 holding the bit patterns) must be of that type and
+        is taken as it is; anything else is read as f32 and, for a half `dtype`, narrowed by the library on the
+        device (round to nearest even).  A borrowed tensor must already be of the store's type."""
+        if dtype is not None and dtype not in DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(DTYPES)} or None, got {dtype!r}")
         data = flatten_rows(data, vector_parameters.dim)
+        given = _element_type(data)
+        if given == "u16":
+            if dtype != "bf16":
+                raise ValueError("uint16 data is taken as bf16 bit patterns: pass dtype='bf16'")
+            given = "bf16"
+        if dtype is not None and given in ("f16", "bf16") and given != dtype:
+            raise ValueError(f"{given} data cannot be kept as {dtype}: only f32 data is converted")
         validate(data, vector_parameters)
-        buf = in_buf(data, np.float32)
-        if borrow and buf.mem == _lib.MEM_DEVICE and buf.obj is not data:
-            raise ValueError("a borrowed tensor must be contiguous float32: the handle reads it in place")
+        if dtype is not None and given == dtype and given != "f32":
+            buf = _raw_buf(data)
+        else:
+            buf, given = in_buf(data, np.float32), "f32"
+        if borrow and buf.mem == _lib.MEM_DEVICE and (buf.obj is not data or given != (dtype or "f32")):
+            raise ValueError(f"a borrowed tensor must be contiguous and already {dtype or 'f32'}: the handle reads it in place")
         vp = vector_parameters.to_c()
         out = C.c_void_p()
         with creating_on(data) as dev:
-            check(_lib.lib().qamd_f32_from_data(buf.ptr, buf.mem, C.byref(vp), int(bool(borrow)), stream_ptr(stream),
-                                                C.byref(out)))
+            if dtype is None:
+                check(_lib.lib().qamd_f32_from_data(buf.ptr, buf.mem, C.byref(vp), int(bool(borrow)), stream_ptr(stream),
+                                                    C.byref(out)))
+            else:
+                check(_lib.lib().qamd_f32_from_data_typed(buf.ptr, DTYPES[given], buf.mem, C.byref(vp), DTYPES[dtype],
+                                                          int(bool(borrow)), stream_ptr(stream), C.byref(out)))
         return cls(out, vector_parameters, dev, keep=buf.obj if borrow else None)
+
+    @property
+    def dtype(self) -> str:
+        """What the rows are kept as: "f32", "f16" or "bf16"."""
+        d = C.c_int()
+        check(_lib.lib().qamd_f32_get_dtype(self._h, C.byref(d)))
+        return next(name for name, v in DTYPES.items() if v == d.value)
 
     @property
     def device(self) -> int | None:

@@ -14,7 +14,7 @@ With --rescore CANDIDATES every variant is also run as `topk_rescored(30, CANDID
 CANDIDATES rows and the f32 data, held as a borrowed `OriginalVectors`, re-ranks them exactly; its same_10 / 20 / 30 and
 timings are reported beside the unrescored ones ("gpu_rescored").
 
-    python tools/ann_protocol.py [--rows 1000000] [--dims 128,768] [--queries 200] [--cpu-queries 3] [--rescore 100]
+    python tools/ann_protocol.py [--rows 1000000] [--dims 128,768] [--queries 200] [--cpu-queries 3] [--rescore 100 [--orig-dtype f16]]
                                  [--out FILE.jsonl]
 """
 import sys as _sys
@@ -169,6 +169,9 @@ def main():
     ap.add_argument("--pq-chunk", type=int, default=8)
     ap.add_argument("--rescore", type=int, default=0, metavar="CANDIDATES",
                     help="also run topk_rescored(30, CANDIDATES) against the f32 data (30 <= CANDIDATES <= 1024)")
+    ap.add_argument("--orig-dtype", default="f32", choices=["f32", "f16", "bf16"],
+                    help="with --rescore: what the store of originals keeps (f32 borrows the data tensor; f16 / bf16 are "
+                         "narrowed copies of it, half the HBM)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -192,7 +195,10 @@ def main():
             truth = exact_neighbours(data, queries, angular)
             q_host = queries.cpu().numpy()
             vp = qa.VectorParameters(dim, args.rows, dist, False)
-            orig = qa.OriginalVectors.from_data(data, vp, borrow=True) if args.rescore else None
+            orig = None
+            if args.rescore:
+                borrow = args.orig_dtype == "f32"  # a half store is a narrowed copy: nothing to read in place
+                orig = qa.OriginalVectors.from_data(data, vp, borrow=borrow, dtype=args.orig_dtype)
             base = {"protocol": "ann_benchmark (demos/src/ann_benchmark_data.rs:93-185)", "rows": args.rows, "dim": dim,
                     "metric": metric, "distance_type": dist.name, "data": "seeded Gaussian mixture with low-rank clusters"}
             for kind in args.quantizers.split(","):
@@ -224,6 +230,7 @@ def main():
                         for _ in range(3):
                             enc.topk_rescored(enc.encode_query(q_host[0]), orig, q_host[0], 30, args.rescore, largest=largest)
                         rec["gpu_rescored"] = run_gpu_rescored(enc, orig, q_host, truth, largest, args.rescore)
+                        rec["gpu_rescored"]["orig_dtype"] = orig.dtype
                     if args.cpu_queries > 0:
                         rec["cpu_oracle_loop"] = run_cpu(kind, enc, q_host[: args.cpu_queries], truth, largest, gpu_ids, extra)
                     emit(rec)
