@@ -109,8 +109,9 @@ QAMD_API uint64_t qamd_u8_quantized_vector_size(const qamd_vector_parameters *vp
 QAMD_API uint64_t qamd_u8_actual_dim(const qamd_vector_parameters *vp);
 
 /* Memory of a u8 store.  Every builder below (encode, encoder_finish, from_rows and so load) keeps the byte codes and,
- * for a Dot or L2 store of 128 to 2048 dims, a packed scan image beside them: the codes at 7 bits each, which the
- * single-query scans read instead of the bytes (12 % fewer bytes per row at dim 768).  The image costs a further 0.875 x
+ * for a Dot or L2 store of 128 to 2048 dims, a packed scan image beside them: the codes at 7 bits each, laid out in
+ * blocks of 64 rows, which the single-query scans read instead of the bytes, a row per lane (12 % fewer bytes per row at
+ * dim 768).  The image costs a further 0.875 x
  * the code bytes (6.7 GB on 10M x 768).  It is skipped when it would leave less free HBM than its own size, when its
  * allocation fails, and when a row holds a code above 127 (rows another producer wrote); the store then scans its
  * bytes, with the same results. */

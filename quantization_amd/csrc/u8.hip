@@ -8,10 +8,11 @@
 // into  codes[count_padded][actual_dim]  (rows 16-byte aligned, contiguous) and
 // offsets[count] f32.  Same 772 algorithmic bytes per scored row; every code load is an
 // aligned 16-byte `global_load_dwordx4`.  Dot / L2 stores also keep a packed scan image of the
-// codes at 7 bits each (u8_internal.hpp, build_packed), which their single-query scans read:
-// 676 instead of 772 bytes per row at dim 768.
+// codes at 7 bits each, in blocks of 64 rows (u8_internal.hpp, build_packed), which their
+// single-query scans read with a row per lane (u8_scan_blocked_kernel): 676 instead of 772 bytes
+// per row at dim 768.
 //
-// Scan mapping (HBM-bound integer work, no MFMA): a row is read by G = min(16, pow2(chunks))
+// Scan mapping of the byte codes (HBM-bound integer work, no MFMA): a row is read by G = min(16, pow2(chunks))
 // adjacent lanes, 16 B per lane per iteration, so one wave-load covers 64/G consecutive rows
 // = fully used 128-B lines.  The query's 16-byte chunks live in VGPRs for the whole kernel.
 // v_dot4_u32_u8 accumulates in 32-bit integers (exact), a log2(G)-step cross-lane add
@@ -28,6 +29,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -175,20 +177,11 @@ __device__ __forceinline__ uint32_t f32x4_to_u8x4_fast(const float4 &f, float al
 // unconditional (clamped address + select) so that they still issue back to back.
 // FILTER: fused top-k mode — no score is written; rows at least as good as the pivot are
 // appended to the candidate buffer (topk_device.hpp).
-// PACKED: `codes` is the store's packed scan image (u8_internal.hpp, build_packed): row_chunks
-// chunks per row, each with 16 codes in bits 0..6 and, in bit 7, bit plane b = c % 7 of the
-// 16 codes of extra chunk row_chunks + c / 7 (c < 7 * n_extra).  The lane that loads chunk c
-// also holds query chunks c and row_chunks + c / 7, so the pair sum needs no cross-lane unpack:
-//   dot(v & 0x7F.., q_c) + (dot(v & 0x80.., q_extra) >> 7) << b
-// (the second dot is a multiple of 128, so `>> (7 - b)` is the same number).  Same exact
-// integer sum as the byte codes, added in another order.  Dot / L2 only (SAD is not linear
-// in the bit planes).  At dim 768 a 16-row tile of 672-byte rows is 84 whole 128-byte lines.
-template <int G, int ITERS, int UNROLL, bool IS_L1, bool EXACT, bool FILTER, bool PACKED = false>
+template <int G, int ITERS, int UNROLL, bool IS_L1, bool EXACT, bool FILTER>
 __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
     const uint4 *__restrict__ codes, const float *__restrict__ offsets,
     const uint4 *__restrict__ qcodes, const float *__restrict__ q_off_p, float multiplier,
-    uint32_t n_rows, uint32_t row_chunks, uint32_t n_extra, float *__restrict__ out, TopkFilter filt) {
-    static_assert(!(PACKED && IS_L1), "the packed image serves Dot and L2 only");
+    uint32_t n_rows, uint32_t row_chunks, float *__restrict__ out, TopkFilter filt) {
     constexpr int RW = 64 / G;
     constexpr int TILE = RW * UNROLL;
     const int lane = threadIdx.x & 63;
@@ -208,9 +201,6 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
             const uint32_t c = sub + it * G;
             if (EXACT) {
                 v[u][it] = ld_nt(p + c);
-            } else if (PACKED) {  // past the row end the query chunks are zero: the clamped chunk adds nothing
-                // row_chunks > G * (ITERS - 1): only the last piece can be past the row end
-                v[u][it] = ld_nt(p + (it < ITERS - 1 || c < row_chunks ? c : row_chunks - 1));
             } else {
                 const uint32_t cc = c < row_chunks ? c : row_chunks - 1;
                 uint4 t = ld_nt(p + cc);
@@ -231,18 +221,6 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
             q[it] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);
         }
     }
-    uint4 qx[PACKED ? ITERS : 1];  // the query chunk whose bit plane rides in bit 7 of chunk c
-    uint32_t qsh[PACKED ? ITERS : 1];  // 7 - that plane
-    if (PACKED) {
-#pragma unroll
-        for (int it = 0; it < ITERS; it++) {
-            const uint32_t c = sub + it * G, e = c / 7;
-            const bool has = c < 7 * n_extra;  // implies c < row_chunks
-            const uint4 t = qcodes[has ? row_chunks + e : 0];
-            qx[it] = make_uint4(has ? t.x : 0, has ? t.y : 0, has ? t.z : 0, has ? t.w : 0);
-            qsh[it] = 7 - (c - 7 * e);
-        }
-    }
     const float q_off = *q_off_p;
     // Score stores: lane (rslot, sub = u % G) keeps row u's score, so that each group of G
     // tiles rows leaves the wave as ONE store of (64/G)*G = 64 consecutive floats at most —
@@ -260,17 +238,7 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
     for (int u = 0; u < UNROLL; u++) {
         uint32_t acc = 0;
 #pragma unroll
-        for (int it = 0; it < ITERS; it++) {
-            if (PACKED) {
-                const uint4 &w = v[u][it];
-                const uint32_t hi = dot16(make_uint4(w.x & 0x80808080u, w.y & 0x80808080u, w.z & 0x80808080u,
-                                                     w.w & 0x80808080u), qx[it], 0);
-                acc = dot16(make_uint4(w.x & 0x7F7F7F7Fu, w.y & 0x7F7F7F7Fu, w.z & 0x7F7F7F7Fu, w.w & 0x7F7F7F7Fu),
-                            q[it], acc) + (hi >> qsh[it]);
-            } else {
-                acc = IS_L1 ? sad16(v[u][it], q[it], acc) : dot16(v[u][it], q[it], acc);
-            }
-        }
+        for (int it = 0; it < ITERS; it++) acc = IS_L1 ? sad16(v[u][it], q[it], acc) : dot16(v[u][it], q[it], acc);
         acc = group_sum<G>(acc);
         if (sub == (u % G)) mine = epilogue(multiplier, acc, q_off, v_off[u / G], 0.0f, EPI_POINT);
         if ((u % G) == G - 1 || u == UNROLL - 1) {
@@ -283,6 +251,105 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
                 else __builtin_nontemporal_store(mine, out + row);
             }
         }
+    }
+}
+
+// ------------------------------------------------------------------------------ blocked scan of the packed image
+// The scan of a Dot / L2 store that has a packed image (u8_internal.hpp, build_packed).  The image keeps P = rc - rc / 8
+// chunks per row: chunk j has chunk j's codes in bits 0..6 and, in bit 7, bit plane j % 7 of extra chunk P + j / 7
+// (j < 7 * (rc / 8)); the last rc % 8 chunks carry no plane.  Rows lie in blocks of kPackBlockRows = 64: chunk j of the
+// 64 rows of block b is the kilobyte at 16-byte index (b * P + j) * 64, one chunk per row.
+//
+// Mapping: `split` (1, 2, 4, 8) waves per block, lane l owns row 64 * b + l.  Every wave-load is one whole, 1 KB-aligned
+// kilobyte (eight 128-byte lines, each requested once); no lane is ever past a row end, so one instantiation serves
+// every rc from 8 to 128.  The query chunks of a load are the same for all 64 lanes: they are read at wave-uniform
+// addresses (scalar loads through the constant cache) and occupy no vector register.  The row is walked in groups of 7
+// chunks that share one extra chunk, so the plane shift is a constant of the unrolled group:
+//   dot(v & 0x7F.., q_j) + (dot(v & 0x80.., q_extra) >> (7 - j % 7))
+// (the second dot is a multiple of 128 << plane).  Same exact integer as the byte codes give, added in another order;
+// no cross-lane reduction.  One group (7 loads, 28 VGPRs) is in flight per lane: a chunk's registers are refilled from
+// the next group right behind their last use.  40 VGPRs, 8 waves per SIMD; two groups in flight (56 VGPRs) do not fit
+// the 64 registers that 8 waves allow.
+// split > 1 (stores too small to fill the GPU with one wave per block): the waves of a block take contiguous shares of
+// the groups, their partial integer sums meet in LDS behind one barrier and the first wave finishes the rows.
+constexpr uint32_t kPackBlockRows = 64;
+constexpr uint32_t kPackBlockChunk = kPackBlockRows;  // uint4 between two chunks of one row
+
+__device__ __forceinline__ uint4 and16(const uint4 &v, uint32_t m) { return make_uint4(v.x & m, v.y & m, v.z & m, v.w & m); }
+
+template <bool FILTER>
+__global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void u8_scan_blocked_kernel(
+    const uint4 *__restrict__ image, const float *__restrict__ offsets, const uint4 *__restrict__ qcodes,
+    const float *__restrict__ q_off_p, float multiplier, uint32_t n_rows, uint32_t pchunks, uint32_t n_extra,
+    uint32_t split, float *__restrict__ out, TopkFilter filt) {
+    __shared__ uint32_t partial[kScanBlock];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t part = wave & (split - 1);
+    const uint64_t block = (uint64_t)blockIdx.x * ((kScanBlock / 64) / split) + wave / split;
+    const uint64_t row = block * kPackBlockRows + lane;
+    const bool live = block * kPackBlockRows < n_rows;  // wave-uniform; offsets[] and the image are padded past every block
+    // the groups of a row: n_extra groups of 7 chunks with a plane, then one of the n_rest chunks without
+    const uint32_t n_rest = pchunks - 7 * n_extra, n_groups = n_extra + (n_rest ? 1 : 0);
+    const uint32_t g_begin = live ? n_groups * part / split : 0, g_end = live ? n_groups * (part + 1) / split : 0;
+    // chunk c of the block: a wave-uniform base plus the lane's 16 bytes
+    const uint4 *blk = image + block * pchunks * kPackBlockChunk;
+    const uint32_t lane16 = lane * 16;
+    auto chunk_ptr = [&](uint32_t c) {
+        return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(blk + (uint64_t)c * kPackBlockChunk) + lane16);
+    };
+    // this wave's full groups [g_begin, gf_end) and whether the rest group is in its share
+    const uint32_t gf_end = g_end < n_extra ? g_end : n_extra;
+    const bool has_rest = g_end > n_extra;
+
+    uint4 v[7];
+    uint32_t acc = 0;
+    // adds full group g, held in v; REFILL: each chunk's registers are reloaded from group g + 1 behind their last use
+    auto eat = [&](uint32_t g, auto refill) {
+        const uint4 *q = qcodes + 7 * g;
+        const uint4 qx = qcodes[pchunks + g];
+#pragma unroll
+        for (int i = 0; i < 7; i++) {
+            const uint4 w = v[i];
+            acc = dot16(and16(w, 0x7F7F7F7Fu), q[i], acc) + (dot16(and16(w, 0x80808080u), qx, 0) >> (7 - i));
+            if (decltype(refill)::value) {  // pinned here, so that the load reuses the chunk's registers
+                __builtin_amdgcn_sched_barrier(0);
+                v[i] = ld_nt(chunk_ptr(7 * (g + 1) + i));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    if (g_begin < gf_end) {
+#pragma unroll
+        for (int i = 0; i < 7; i++) v[i] = ld_nt(chunk_ptr(7 * g_begin + i));
+    }
+    const float v_off = offsets[row];
+    const float q_off = *q_off_p;
+    uint32_t pivot = 0;
+    if (FILTER) pivot = *filt.pivot_key;
+    if (g_begin < gf_end) {
+        for (uint32_t g = g_begin; g + 1 < gf_end; g++) eat(g, std::true_type{});
+        eat(gf_end - 1, std::false_type{});
+    }
+    if (has_rest) {  // the chunks that carry no plane: bit 7 is zero
+        const uint4 *q = qcodes + 7 * n_extra;
+#pragma unroll
+        for (int i = 0; i < 7; i++)
+            if ((uint32_t)i < n_rest) v[i] = ld_nt(chunk_ptr(7 * n_extra + i));
+#pragma unroll
+        for (int i = 0; i < 7; i++)
+            if ((uint32_t)i < n_rest) acc = dot16(and16(v[i], 0x7F7F7F7Fu), q[i], acc);
+    }
+    if (split > 1) {
+        partial[threadIdx.x] = acc;
+        __syncthreads();
+        if (part == 0)
+            for (uint32_t p = 1; p < split; p++) acc += partial[threadIdx.x + 64 * p];
+    }
+    if (part == 0 && row < n_rows) {
+        const float score = epilogue(multiplier, acc, q_off, v_off, 0.0f, EPI_POINT);
+        if (FILTER) topk_offer(filt, pivot, score, (uint32_t)row);
+        else __builtin_nontemporal_store(score, out + row);
     }
 }
 
@@ -1061,8 +1128,9 @@ __global__ __launch_bounds__(kBlock) void join_rows_kernel(const uint32_t *__res
 }
 
 // The packed scan image (u8_internal.hpp) of rows [0, n_rows): one thread per (row, packed chunk j).  Chunk j keeps
-// chunk j's codes in bits 0..6 and bit plane j % 7 of chunk P + j / 7 in bit 7.  A code above 127 anywhere in the rows
-// (bytes another producer wrote: from_rows, load) sets *bad, and the image is then dropped.
+// chunk j's codes in bits 0..6 and bit plane j % 7 of chunk P + j / 7 in bit 7, and goes to its place in the row's
+// block of kPackBlockRows rows.  A code above 127 anywhere in the rows (bytes another producer wrote: from_rows, load)
+// sets *bad, and the image is then dropped.
 __global__ __launch_bounds__(kBlock) void u8_pack7_kernel(const uint4 *__restrict__ codes, uint64_t n_rows,
                                                           uint32_t row_chunks, uint32_t pchunks, uint32_t n_extra,
                                                           uint4 *__restrict__ packed, uint32_t *__restrict__ bad) {
@@ -1084,7 +1152,7 @@ __global__ __launch_bounds__(kBlock) void u8_pack7_kernel(const uint4 *__restric
             w[2] |= ((x.z >> b) & 0x01010101u) << 7;
             w[3] |= ((x.w >> b) & 0x01010101u) << 7;
         }
-        packed[t] = make_uint4(w[0], w[1], w[2], w[3]);
+        packed[((r / kPackBlockRows) * pchunks + j) * kPackBlockRows + r % kPackBlockRows] = make_uint4(w[0], w[1], w[2], w[3]);
     }
     if (high & 0x80808080u) atomicOr(bad, 1u);
 }
@@ -1127,6 +1195,7 @@ qamd_status alloc_store(qamd_u8 *h) {
 // a code above 127 (rows another producer wrote).
 qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
     h->packed.release();
+    h->packed_rows.release();
     h->packed_chunks = 0;
     const uint32_t rc = h->row_chunks, n_extra = rc / 8, pchunks = rc - n_extra;
     if (!u8_packed_allowed() || h->count == 0 || rc < 8 || rc > 128 ||
@@ -1140,7 +1209,8 @@ qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
     }
     DevBuf img, bad;
     const std::string err = last_error();
-    if (img.alloc_zero_tail(bytes, h->count * pchunks * 16) != QAMD_OK || bad.alloc(sizeof(uint32_t), true) != QAMD_OK) {
+    // rows of a block are interleaved: the padding rows of the last block are zeroed with it, before it is written
+    if (img.alloc_zero_tail(bytes, h->count / kPackBlockRows * kPackBlockRows * pchunks * 16) != QAMD_OK || bad.alloc(sizeof(uint32_t), true) != QAMD_OK) {
         (void)hipGetLastError();  // an out-of-memory here is not the build's failure
         last_error() = err;
         return QAMD_OK;
@@ -1158,42 +1228,52 @@ qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
 }
 
 template <bool IS_L1> struct ScanLaunch {
-    // packed: the scan reads the packed image (Dot / L2 only); chunks = its chunks per row, else row_chunks.
     template <int G, int ITERS, int UNROLL>
-    static void go(const qamd_u8 *h, bool packed, uint32_t chunks, const uint4 *qc, const float *qo, float *out,
-                   const TopkFilter *filt, hipStream_t s) {
+    static void go(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt, hipStream_t s) {
         constexpr int TILE = (64 / G) * UNROLL;
         const uint64_t waves = (h->count + TILE - 1) / TILE;  // one wave per tile
         const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
-        const bool exact = chunks == (uint32_t)(G * ITERS);
-        const uint4 *codes = packed ? h->packed.as<uint4>() : h->codes.as<uint4>();
-        const uint32_t n_extra = h->row_chunks - chunks;
-#define QAMD_U8_GO(EX, FI, PK)                                                                                  \
-    hipLaunchKernelGGL((u8_scan_kernel<G, ITERS, UNROLL, IS_L1, EX, FI, PK>), dim3(grid),                      \
-                       dim3(kScanBlock), 0, s, codes, h->offsets.as<float>(), qc, qo, h->meta.multiplier,          \
-                       (uint32_t)h->count, chunks, n_extra, out, filt ? *filt : TopkFilter{})
-        if constexpr (!IS_L1) {
-            if (packed) {
-                if (filt) {
-                    if (exact) QAMD_U8_GO(true, true, true);
-                    else QAMD_U8_GO(false, true, true);
-                } else {
-                    if (exact) QAMD_U8_GO(true, false, true);
-                    else QAMD_U8_GO(false, false, true);
-                }
-                return;
-            }
-        }
+        const bool exact = h->row_chunks == (uint32_t)(G * ITERS);
+#define QAMD_U8_GO(EX, FI)                                                                                     \
+    hipLaunchKernelGGL((u8_scan_kernel<G, ITERS, UNROLL, IS_L1, EX, FI>), dim3(grid), dim3(kScanBlock), 0, s,    \
+                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)h->count, \
+                       h->row_chunks, out, filt ? *filt : TopkFilter{})
         if (filt) {
-            if (exact) QAMD_U8_GO(true, true, false);
-            else QAMD_U8_GO(false, true, false);
+            if (exact) QAMD_U8_GO(true, true);
+            else QAMD_U8_GO(false, true);
         } else {
-            if (exact) QAMD_U8_GO(true, false, false);
-            else QAMD_U8_GO(false, false, false);
+            if (exact) QAMD_U8_GO(true, false);
+            else QAMD_U8_GO(false, false);
         }
 #undef QAMD_U8_GO
     }
 };
+
+// Waves per block of the blocked scan: one, unless the store's blocks are too few to give every SIMD four waves (half
+// of what it holds); then the smallest of 2, 4, 8 that does, else 8.
+uint32_t blocked_split(uint64_t count) {
+    const uint64_t blocks = (count + kPackBlockRows - 1) / kPackBlockRows;
+    const uint64_t want = (uint64_t)device_info().cu_count * 16;
+    uint32_t split = 1;
+    while (split < 8 && blocks * split < want) split *= 2;
+    return split;
+}
+
+// The Dot / L2 scan of a store that has a packed image: u8_scan_blocked_kernel over its blocks.
+void launch_scan_blocked(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
+                         hipStream_t s) {
+    const uint32_t split = blocked_split(h->count), blocks_per_wg = (kScanBlock / 64) / split;
+    const uint64_t blocks = (h->count + kPackBlockRows - 1) / kPackBlockRows;
+    const unsigned grid = (unsigned)((blocks + blocks_per_wg - 1) / blocks_per_wg);
+    h->last_scan_split.store((int)split, std::memory_order_relaxed);
+#define QAMD_U8_BLOCKED(FI)                                                                                          \
+    hipLaunchKernelGGL((u8_scan_blocked_kernel<FI>), dim3(grid), dim3(kScanBlock), 0, s, h->packed.as<uint4>(),       \
+                       h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)h->count, h->packed_chunks,      \
+                       h->row_chunks - h->packed_chunks, split, out, filt ? *filt : TopkFilter{})
+    if (filt) QAMD_U8_BLOCKED(true);
+    else QAMD_U8_BLOCKED(false);
+#undef QAMD_U8_BLOCKED
+}
 
 // Returns false when the store's row size has no templated kernel (caller uses the generic one).
 // The Dot / L2 scans read the packed image when the store has one (its rows are 7/8 as long).
@@ -1202,21 +1282,22 @@ bool launch_scan(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out,
                  hipStream_t s) {
     using L = ScanLaunch<IS_L1>;
     const bool packed = !IS_L1 && h->packed_chunks != 0;
-    const uint32_t rc = packed ? h->packed_chunks : h->row_chunks;
     h->last_scan_packed.store(packed ? 1 : 0, std::memory_order_relaxed);
-    if (rc == 1) return L::template go<1, 1, 4>(h, packed, rc, qc, qo, out, filt, s), true;
-    if (rc == 2) return L::template go<2, 1, 4>(h, packed, rc, qc, qo, out, filt, s), true;
-    if (rc <= 4) return L::template go<4, 1, 8>(h, packed, rc, qc, qo, out, filt, s), true;
-    if (rc <= 8) return L::template go<8, 1, 8>(h, packed, rc, qc, qo, out, filt, s), true;
+    if (packed) return launch_scan_blocked(h, qc, qo, out, filt, s), true;
+    const uint32_t rc = h->row_chunks;
+    if (rc == 1) return L::template go<1, 1, 4>(h, qc, qo, out, filt, s), true;
+    if (rc == 2) return L::template go<2, 1, 4>(h, qc, qo, out, filt, s), true;
+    if (rc <= 4) return L::template go<4, 1, 8>(h, qc, qo, out, filt, s), true;
+    if (rc <= 8) return L::template go<8, 1, 8>(h, qc, qo, out, filt, s), true;
     switch ((rc + 15) / 16) {
-        case 1: return L::template go<16, 1, 8>(h, packed, rc, qc, qo, out, filt, s), true;
-        case 2: return L::template go<16, 2, 4>(h, packed, rc, qc, qo, out, filt, s), true;
-        case 3: return L::template go<16, 3, 4>(h, packed, rc, qc, qo, out, filt, s), true;
-        case 4: return L::template go<16, 4, 2>(h, packed, rc, qc, qo, out, filt, s), true;
-        case 5: return L::template go<16, 5, 2>(h, packed, rc, qc, qo, out, filt, s), true;
-        case 6: return L::template go<16, 6, 2>(h, packed, rc, qc, qo, out, filt, s), true;
-        case 7: return L::template go<16, 7, 2>(h, packed, rc, qc, qo, out, filt, s), true;
-        case 8: return L::template go<16, 8, 2>(h, packed, rc, qc, qo, out, filt, s), true;
+        case 1: return L::template go<16, 1, 8>(h, qc, qo, out, filt, s), true;
+        case 2: return L::template go<16, 2, 4>(h, qc, qo, out, filt, s), true;
+        case 3: return L::template go<16, 3, 4>(h, qc, qo, out, filt, s), true;
+        case 4: return L::template go<16, 4, 2>(h, qc, qo, out, filt, s), true;
+        case 5: return L::template go<16, 5, 2>(h, qc, qo, out, filt, s), true;
+        case 6: return L::template go<16, 6, 2>(h, qc, qo, out, filt, s), true;
+        case 7: return L::template go<16, 7, 2>(h, qc, qo, out, filt, s), true;
+        case 8: return L::template go<16, 8, 2>(h, qc, qo, out, filt, s), true;
         default: break;
     }
     return false;
@@ -2506,11 +2587,48 @@ extern "C" __attribute__((visibility("default"))) void qamd_dev_u8_ptrs(const qa
 extern "C" __attribute__((visibility("default"))) const void *qamd_dev_u8_query_ptr(const qamd_u8_query *q) {
     return q->buf.ptr;
 }
-// The packed scan image (nullptr, 0 chunks: none) and which image the store's last scan launch read (1: packed).
+// The packed scan image in ROW-MAJOR order, [count][chunks] 16-byte chunks (nullptr, 0 chunks: none): un-blocked on the
+// first call into a buffer the handle owns, so that a reader needs to know the bit format only.
+namespace {
+__global__ __launch_bounds__(kBlock) void u8_unblock_kernel(const uint4 *__restrict__ image, uint64_t n_rows,
+                                                            uint32_t pchunks, uint4 *__restrict__ rows) {
+    const uint64_t total = n_rows * pchunks, stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
+        const uint64_t r = t / pchunks;
+        const uint32_t j = (uint32_t)(t - r * pchunks);
+        rows[t] = image[((r / kPackBlockRows) * pchunks + j) * kPackBlockRows + r % kPackBlockRows];
+    }
+}
+}  // namespace
 extern "C" __attribute__((visibility("default"))) void qamd_dev_u8_packed(const qamd_u8 *h, const void **packed,
                                                                           uint32_t *chunks) {
+    *packed = nullptr;
+    *chunks = 0;
+    if (!h->packed_chunks) return;
+    if (!h->packed_rows.ptr) {
+        const uint64_t n = h->count * h->packed_chunks;
+        if (h->packed_rows.alloc(n * 16, false) != QAMD_OK) return;
+        hipLaunchKernelGGL(u8_unblock_kernel, dim3(grid_for(n, kBlock, 8)), dim3(kBlock), 0, nullptr, h->packed.as<uint4>(),
+                           h->count, h->packed_chunks, h->packed_rows.as<uint4>());
+        if (hipStreamSynchronize(nullptr) != hipSuccess) {
+            h->packed_rows.release();
+            return;
+        }
+    }
+    *packed = h->packed_rows.ptr;
+    *chunks = h->packed_chunks;
+}
+// The image the scan really reads: blocks of `block_rows` rows, chunk j of row r at 16-byte index
+// ((r / block_rows) * chunks + j) * block_rows + r % block_rows; padded_rows / block_rows blocks.
+extern "C" __attribute__((visibility("default"))) void qamd_dev_u8_packed_blocked(const qamd_u8 *h, const void **packed,
+                                                                                  uint32_t *chunks, uint32_t *block_rows) {
     *packed = h->packed.ptr;
     *chunks = h->packed_chunks;
+    *block_rows = kPackBlockRows;
+}
+// Which image the store's last scan launch read (1: packed), and how many waves per block its last blocked scan took.
+extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_split(const qamd_u8 *h) {
+    return h->last_scan_split.load(std::memory_order_relaxed);
 }
 extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_packed(const qamd_u8 *h) {
     return h->last_scan_packed.load(std::memory_order_relaxed);

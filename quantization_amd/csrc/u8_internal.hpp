@@ -16,14 +16,18 @@ struct qamd_u8 {
     int lane_mode = 0;         // 0: integer sum rounded once; 1: avx2.c lane order
     qamd::DevBuf codes;        // [padded_rows][actual_dim]
     qamd::DevBuf offsets;      // [padded_rows] f32
-    // Packed scan image (u8.hip build_packed): the codes at 7 bits each, [padded_rows][packed_chunks] 16-byte chunks.
-    // Chunk j < packed_chunks keeps chunk j's codes in bits 0..6 of its bytes and, in bit 7, bit plane j % 7 of chunk
-    // packed_chunks + j / 7 (row_chunks / 8 such chunks).  Only the Dot / L2 scans of lane mode 0 read it; every other
-    // kernel reads `codes`.  Empty when the store has none (L1, fewer than 8 or more than 128 chunks, a code above 127,
-    // too little free HBM).
+    // Packed scan image (u8.hip build_packed): the codes at 7 bits each, packed_chunks 16-byte chunks per row.  Chunk
+    // j < packed_chunks keeps chunk j's codes in bits 0..6 of its bytes and, in bit 7, bit plane j % 7 of chunk
+    // packed_chunks + j / 7 (row_chunks / 8 such chunks).  Rows lie in blocks of 64 (kPackBlockRows): chunk j of row r is
+    // at 16-byte index ((r / 64) * packed_chunks + j) * 64 + r % 64, so that chunk j of a block's 64 rows is one aligned
+    // kilobyte, which one wave of u8_scan_blocked_kernel loads.  padded_rows is a multiple of 1024: blocks are whole, and
+    // padding rows are zero.  Only the Dot / L2 scans of lane mode 0 read it; every other kernel reads `codes`.  Empty
+    // when the store has none (L1, fewer than 8 or more than 128 chunks, a code above 127, too little free HBM).
     qamd::DevBuf packed;
     uint32_t packed_chunks = 0;
     mutable std::atomic<int> last_scan_packed{0};  // the image the last scan launch read (developer report)
+    mutable std::atomic<int> last_scan_split{0};   // waves per block of the last blocked scan launch (developer report)
+    mutable qamd::DevBuf packed_rows;              // developer report: the image un-blocked, [count][packed_chunks]
     // The batched top-k's pivot sample (u8_batch.hip): rows hash(j) of the store, j < sample_rows, then 512
     // zero rows; gathered once on first use (count / 64 rows at most: 1.6 % of the store), immutable after.
     mutable std::mutex sample_mu;
