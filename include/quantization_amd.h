@@ -323,6 +323,24 @@ QAMD_API qamd_status qamd_bin_load(const char *data_path, const char *meta_path,
 QAMD_API qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query, uint64_t qdim,
                                            qamd_mem query_mem, void *stream,
                                            qamd_bin_query **query_io);
+/* Scalar ("asymmetric") queries: the stored rows stay one bit per dimension, the query keeps 4 or 8.  The reference
+ * has NO counterpart (its snapshot predates upstream's asymmetric binary quantization); DESIGN.md 3.2d is the
+ * specification: codes c_i = min(L, (u32)((q_i + a) * (L / (a + a)) + 0.5f)) with L = 2^bits - 1 and a = max |q_i|,
+ * held as `bits` bit planes in the rows' layout, and the score calculate_metric(sum_b 2^b popcount(plane_b xor row))
+ * with dim * L in place of dim.  bits = 1 is qamd_bin_encode_query; other values than 1, 4, 8 and dims whose dim * L
+ * would leave f32's exact integers (above 65 792 at 8 bits, 1 118 481 at 4) are QAMD_ERR_ARGUMENTS.  *query_io is
+ * reused as by qamd_bin_encode_query and may change its bit count from call to call.  qamd_bin_score_point / _ids /
+ * _all, qamd_bin_topk and qamd_bin_topk_rescored take either kind of query.
+ * Deliberately left out: qamd_bin_query_batch and the qamd_bin_sharded_* query types are separate structs and stay
+ * binary-only (a scalar batch is an int8 dot product on the matrix cores: the natural follow-up). */
+QAMD_API qamd_status qamd_bin_encode_query_scalar(const qamd_bin *h, const float *query, uint64_t qdim,
+                                                  qamd_mem query_mem, uint32_t bits, void *stream,
+                                                  qamd_bin_query **query_io);
+/* No counterpart in the reference: *bits = the number of bit planes, *max_abs = a; a query from
+ * qamd_bin_encode_query gives 1 and 0.  Either pointer may be NULL. */
+QAMD_API qamd_status qamd_bin_query_info(const qamd_bin_query *q, uint32_t *bits, float *max_abs);
+/* *len = the bytes of the encoded query: one row of bits, or for a scalar query bits x row bytes, plane 0 (the least
+ * significant) first. */
 QAMD_API qamd_status qamd_bin_query_read(const qamd_bin_query *q, uint8_t *bits,
                                          uint64_t capacity, uint64_t *len);
 QAMD_API void qamd_bin_query_free(qamd_bin_query *q);

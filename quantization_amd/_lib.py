@@ -126,6 +126,8 @@ def lib() -> C.CDLL:
         "qamd_bin_save": (i32, [vp, C.c_char_p, C.c_char_p]),
         "qamd_bin_load": (i32, [C.c_char_p, C.c_char_p, VP, i32, pp]),
         "qamd_bin_encode_query": (i32, [vp, vp, u64, i32, vp, pp]),
+        "qamd_bin_encode_query_scalar": (i32, [vp, vp, u64, i32, u32, vp, pp]),
+        "qamd_bin_query_info": (i32, [vp, C.POINTER(u32), f32p]),
         "qamd_bin_query_read": (i32, [vp, vp, u64, C.POINTER(u64)]),
         "qamd_bin_query_free": (None, [vp]),
         "qamd_bin_score_point": (i32, [vp, vp, u32, f32p]),

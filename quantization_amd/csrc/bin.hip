@@ -79,9 +79,28 @@ __device__ __forceinline__ float metric(uint32_t x, float dim_f, int is_dot, int
     return zx ? zeros_count - xor_product : xor_product - zeros_count;
 }
 
+// Scalar queries (the reference has no counterpart): the query is PLANES bit planes of 4- or 8-bit
+// codes, plane b one device row stride after plane b - 1, and a row's X = sum_b 2^b popcount(plane_b xor row).
+// One 16-byte piece (or dword) of a row against the same piece of every plane:
+// PLANES x (4 v_xor + 4 v_bcnt) and one v_lshl_add into the row's single accumulator.
+template <int PLANES> __device__ __forceinline__ uint32_t xpop16_planes(const uint4 &v, const uint4 (&q)[PLANES], uint32_t acc) {
+#pragma unroll
+    for (int b = 0; b < PLANES; b++) acc += xpop16(v, q[b], 0u) << b;
+    return acc;
+}
+template <int PLANES> __device__ __forceinline__ uint32_t xpop_planes(uint32_t v, const uint32_t *q, uint32_t stride, uint32_t acc) {
+#pragma unroll
+    for (int b = 0; b < PLANES; b++) acc += (uint32_t)__popc(v ^ q[(size_t)b * stride]) << b;
+    return acc;
+}
+
 // Rows of ds >= 16 bytes (row_chunks = ds/16).  One wave per tile of (64/G)*UNROLL rows,
 // non-persistent grid (same reasoning and measurements as u8_scan_kernel in u8.hip).
-template <int G, int ITERS, int UNROLL, bool EXACT, bool FILTER>
+// PLANES > 1: qbits holds the planes of a scalar query at a stride of row_chunks pieces and dim_f is dim * (2^PLANES - 1).
+// The planes are used one piece index at a time, PLANES x 4 registers, and read through L1 / L2 (the query is at most 8 rows
+// long); the compiler is free to fetch them early and does for the long rows, which then run at 2-3 waves per SIMD
+// instead of 7-8 - still without scratch (resource report).
+template <int G, int ITERS, int UNROLL, bool EXACT, bool FILTER, int PLANES = 1>
 __global__ __launch_bounds__(kScanBlock) void bin_scan_kernel(const uint4 *__restrict__ rows,
                                                              const uint4 *__restrict__ qbits, float dim_f,
                                                              int is_dot, int invert, uint32_t n_rows,
@@ -95,15 +114,17 @@ __global__ __launch_bounds__(kScanBlock) void bin_scan_kernel(const uint4 *__res
     const uint64_t base = wave * TILE;
     if (base >= n_rows) return;
     uint4 q[ITERS];
+    if (PLANES == 1) {
 #pragma unroll
-    for (int it = 0; it < ITERS; it++) {
-        const uint32_t c = sub + it * G;
-        if (EXACT) {
-            q[it] = qbits[c];
-        } else {
-            const uint4 t = qbits[c < row_chunks ? c : row_chunks - 1];
-            const bool in = c < row_chunks;
-            q[it] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);
+        for (int it = 0; it < ITERS; it++) {
+            const uint32_t c = sub + it * G;
+            if (EXACT) {
+                q[it] = qbits[c];
+            } else {
+                const uint4 t = qbits[c < row_chunks ? c : row_chunks - 1];
+                const bool in = c < row_chunks;
+                q[it] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);
+            }
         }
     }
     uint4 v[UNROLL][ITERS];
@@ -119,8 +140,27 @@ __global__ __launch_bounds__(kScanBlock) void bin_scan_kernel(const uint4 *__res
             } else {  // masked lane: read the row's last chunk, then xor against itself -> 0 bits
                 const bool in = c < row_chunks;
                 uint4 t = ld_nt(p + (in ? c : row_chunks - 1));
-                v[u][it] = in ? t : q[it];
+                if (PLANES == 1) v[u][it] = in ? t : q[it];
+                else v[u][it] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);  // and zero plane pieces
             }
+        }
+    }
+    uint32_t x[UNROLL];
+    if (PLANES > 1) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) x[u] = 0;
+#pragma unroll
+        for (int it = 0; it < ITERS; it++) {
+            const uint32_t c = sub + it * G;
+            const bool in = EXACT || c < row_chunks;
+            uint4 qp[PLANES];
+#pragma unroll
+            for (int b = 0; b < PLANES; b++) {
+                const uint4 t = qbits[(size_t)b * row_chunks + (in ? c : row_chunks - 1)];
+                qp[b] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) x[u] = xpop16_planes<PLANES>(v[u][it], qp, x[u]);
         }
     }
     float mine = 0.0f;  // lane (rslot, sub = u % G) keeps row u's score: one coalesced nt store per G rows-groups
@@ -129,8 +169,12 @@ __global__ __launch_bounds__(kScanBlock) void bin_scan_kernel(const uint4 *__res
 #pragma unroll
     for (int u = 0; u < UNROLL; u++) {
         uint32_t acc = 0;
+        if (PLANES == 1) {
 #pragma unroll
-        for (int it = 0; it < ITERS; it++) acc = xpop16(v[u][it], q[it], acc);
+            for (int it = 0; it < ITERS; it++) acc = xpop16(v[u][it], q[it], acc);
+        } else {
+            acc = x[u];
+        }
         acc = group_sum<G>(acc);
         if (sub == (u % G)) mine = metric(acc, dim_f, is_dot, invert);
         if ((u % G) == G - 1 || u == UNROLL - 1) {
@@ -221,7 +265,7 @@ __global__ __launch_bounds__(kScanBlock) void bin_scan_multi_kernel(const uint4 
 // wave / workgroup / last-arriver merges of topk_device.hpp keep the best k.  Exact under any
 // number of ties (keys are distinct: score bits << 32 | row), which the sampled-pivot path is not
 // good at for binary scores (few distinct values -> candidate lists overflow -> classic fallback).
-template <int G, int ITERS, bool EXACT>
+template <int G, int ITERS, bool EXACT, int PLANES = 1>
 __global__ __launch_bounds__(1024) void bin_topk_small_kernel(const uint4 *__restrict__ rows,
                                                               const uint4 *__restrict__ qbits, float dim_f, int is_dot,
                                                               int invert, uint32_t n_rows, uint32_t row_chunks,
@@ -234,12 +278,14 @@ __global__ __launch_bounds__(1024) void bin_topk_small_kernel(const uint4 *__res
     const int sub = lane % G, rslot = lane / G;
     unsigned long long *stage = lds[kSmallTopkWaves + wave];
     uint4 q[ITERS];
+    if (PLANES == 1) {
 #pragma unroll
-    for (int it = 0; it < ITERS; it++) {
-        const uint32_t c = sub + it * G;
-        const bool in = EXACT || c < row_chunks;
-        const uint4 t = qbits[in ? c : row_chunks - 1];
-        q[it] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);
+        for (int it = 0; it < ITERS; it++) {
+            const uint32_t c = sub + it * G;
+            const bool in = EXACT || c < row_chunks;
+            const uint4 t = qbits[in ? c : row_chunks - 1];
+            q[it] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);
+        }
     }
     const uint64_t wg_base = (uint64_t)blockIdx.x * rows_per_wg;
     SmallTopkWave acc_list;
@@ -258,13 +304,35 @@ __global__ __launch_bounds__(1024) void bin_topk_small_kernel(const uint4 *__res
                 v[u][it] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);
             }
         }
+        uint32_t x[UNROLL];
+        if (PLANES > 1) {  // as in bin_scan_kernel: the planes of one piece at a time
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) x[u] = 0;
+#pragma unroll
+            for (int it = 0; it < ITERS; it++) {
+                const uint32_t c = sub + it * G;
+                const bool in = EXACT || c < row_chunks;
+                uint4 qp[PLANES];
+#pragma unroll
+                for (int b = 0; b < PLANES; b++) {
+                    const uint4 t = qbits[(size_t)b * row_chunks + (in ? c : row_chunks - 1)];
+                    qp[b] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);
+                }
+#pragma unroll
+                for (int u = 0; u < UNROLL; u++) x[u] = xpop16_planes<PLANES>(v[u][it], qp, x[u]);
+            }
+        }
 #pragma unroll
         for (int u = 0; u < UNROLL; u++) {
             const uint32_t local = (tile + u) * RW + rslot;
             const uint64_t row = wg_base + local;
             uint32_t acc = 0;
+            if (PLANES == 1) {
 #pragma unroll
-            for (int it = 0; it < ITERS; it++) acc = xpop16(v[u][it], q[it], acc);
+                for (int it = 0; it < ITERS; it++) acc = xpop16(v[u][it], q[it], acc);
+            } else {
+                acc = x[u];
+            }
             acc = group_sum<G>(acc);
             if (sub == 0) {
                 unsigned long long key = ~0ull;
@@ -282,7 +350,9 @@ __global__ __launch_bounds__(1024) void bin_topk_small_kernel(const uint4 *__res
 }
 
 // Any row size, dword granularity: used for tiny rows (ds 4 or 8), very long rows and the
-// random-access entry points.  ids == nullptr scans rows [0, n).
+// random-access entry points.  ids == nullptr scans rows [0, n).  PLANES > 1: plane b of a scalar query is at
+// qbits + b * row_words.
+template <int PLANES = 1>
 __global__ __launch_bounds__(kBlock) void bin_words_kernel(const uint32_t *__restrict__ rows,
                                                           const uint32_t *qbits, float dim_f, int is_dot,
                                                           int invert, const uint32_t *__restrict__ ids,
@@ -300,7 +370,11 @@ __global__ __launch_bounds__(kBlock) void bin_words_kernel(const uint32_t *__res
         uint32_t acc = 0;
         if (ok) {
             const uint32_t *p = rows + (uint64_t)row * row_words;
-            for (uint32_t w = sub; w < row_words; w += G) acc += __popc(p[w] ^ qbits[w]);
+            if (PLANES == 1) {
+                for (uint32_t w = sub; w < row_words; w += G) acc += __popc(p[w] ^ qbits[w]);
+            } else {
+                for (uint32_t w = sub; w < row_words; w += G) acc = xpop_planes<PLANES>(p[w], qbits + w, row_words, acc);
+            }
         }
         acc = group_sum<G>(acc);
         if (sub == 0 && k < n) out[k] = ok ? metric(acc, dim_f, is_dot, invert) : __builtin_nanf("");
@@ -313,7 +387,9 @@ __global__ __launch_bounds__(kBlock) void bin_words_kernel(const uint32_t *__res
 // bit row l of a query batch for the pairs of list l; lists and list_rows -> stored row list_rows[l].
 // VEC16 (ds % 16 == 0): 8 lanes per pair, 16-byte pieces, up to four in flight per lane; else 16 lanes
 // per pair at dword granularity (rows of 4 and 8 bytes).
-template <bool VEC16>
+// PLANES > 1: only with `lists` == nullptr and q_single the planes of a scalar query (plane b at q_single + b * row_words);
+// a stored row passed as q_single (score_internal) is one plane.
+template <bool VEC16, int PLANES = 1>
 __global__ __launch_bounds__(kBlock) void bin_pairs_kernel(const uint32_t *__restrict__ rows, const uint32_t *q_single,
                                                           const uint8_t *__restrict__ q_batch, uint32_t q_stride,
                                                           const uint32_t *__restrict__ lists, uint32_t n_lists,
@@ -347,7 +423,15 @@ __global__ __launch_bounds__(kBlock) void bin_pairs_kernel(const uint32_t *__res
         if (VEC16) {
             const uint32_t chunks = row_words / 4;
             const uint4 *p4 = reinterpret_cast<const uint4 *>(p), *q4 = reinterpret_cast<const uint4 *>(qp);
-            if (chunks <= (uint32_t)G) {  // the common rows (<= 1024 bits): one 16-byte piece per lane
+            if (PLANES > 1) {
+                for (uint32_t c = sub; c < chunks; c += G) {
+                    const uint4 v = p4[c];
+                    uint4 qp[PLANES];
+#pragma unroll
+                    for (int b = 0; b < PLANES; b++) qp[b] = q4[(size_t)b * chunks + c];
+                    acc = xpop16_planes<PLANES>(v, qp, acc);
+                }
+            } else if (chunks <= (uint32_t)G) {  // the common rows (<= 1024 bits): one 16-byte piece per lane
                 if ((uint32_t)sub < chunks) acc = xpop16(p4[sub], q4[sub], acc);
             } else {
                 for (uint32_t c0 = sub; c0 < chunks; c0 += 4 * G) {
@@ -363,6 +447,8 @@ __global__ __launch_bounds__(kBlock) void bin_pairs_kernel(const uint32_t *__res
                         if (c0 + j * G < chunks) acc = xpop16(v[j], qv[j], acc);
                 }
             }
+        } else if (PLANES > 1) {
+            for (uint32_t w = sub; w < row_words; w += G) acc = xpop_planes<PLANES>(p[w], qp + w, row_words, acc);
         } else {
             for (uint32_t w = sub; w < row_words; w += G) acc += __popc(p[w] ^ qp[w]);
         }
@@ -395,6 +481,62 @@ __global__ __launch_bounds__(kBlock) void bin_encode_kernel(const float *__restr
                 if (w + 1 < row_words) dst[w + 1] = (uint32_t)(mine >> 32);
                 mine = 0;
             }
+        }
+    }
+}
+
+// Scalar query encoding (the reference has no counterpart), one workgroup: a = max |q_i| over the finite
+// entries, then c_i = min(L, (u32)((q_i + a) * (L / (a + a)) + 0.5f)) with L = 2^bits - 1 - single f32 operations in
+// this order, the division hipcc's correctly rounded one - and plane b = bit b of every c_i in the rows' bit order
+// (one ballot per plane and 64 entries).  Every dword of every plane is written, pad bits as zeros.
+__global__ __launch_bounds__(kBlock) void bin_encode_scalar_kernel(const float *__restrict__ query, uint32_t dim,
+                                                                  uint32_t row_words, uint32_t bits,
+                                                                  uint32_t *__restrict__ planes, float *__restrict__ max_abs) {
+    __shared__ float wave_max[kBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inf = __builtin_huge_valf();
+    float a = 0.0f;
+    for (uint32_t i = threadIdx.x; i < dim; i += kBlock) {
+        const float v = fabsf(query[i]);
+        if (v < inf && v > a) a = v;  // NaN fails both
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) a = fmaxf(a, __shfl_xor(a, o));
+    if (lane == 0) wave_max[wave] = a;
+    __syncthreads();
+    a = wave_max[0];
+#pragma unroll
+    for (int w = 1; w < kBlock / 64; w++) a = fmaxf(a, wave_max[w]);
+    if (threadIdx.x == 0) *max_abs = a;
+    const uint32_t L = (1u << bits) - 1u;
+    const float scale = a == 0.0f ? 0.0f : (float)L / (a + a);
+    const uint32_t steps = (row_words + 1) / 2;
+    for (uint32_t st = wave; st < steps; st += kBlock / 64) {
+        const uint32_t i = st * 64 + lane;
+        uint32_t c = 0;
+        if (i < dim) {
+            float v = query[i];
+            if (v != v) v = 0.0f;
+            if (a == 0.0f) {
+                c = (L + 1u) / 2u;
+            } else {
+                const float t = (v + a) * scale;
+                const uint32_t r = (uint32_t)(t + 0.5f);
+                c = r < L ? r : L;
+            }
+            if (v == inf) c = L;
+            if (v == -inf) c = 0;
+        }
+        unsigned long long mine = 0;
+        for (uint32_t b = 0; b < bits; b++) {
+            const unsigned long long m = __ballot((c >> b) & 1u);
+            if ((uint32_t)lane == b) mine = m;
+        }
+        if ((uint32_t)lane < bits) {
+            uint32_t *dst = planes + (size_t)lane * row_words;
+            const uint32_t w = st * 2;
+            if (w < row_words) dst[w] = (uint32_t)mine;
+            if (w + 1 < row_words) dst[w + 1] = (uint32_t)(mine >> 32);
         }
     }
 }
@@ -471,7 +613,8 @@ struct qamd_bin {
 struct qamd_bin_query {
     int device = 0;
     uint64_t nb = 0, ds = 0, qdim_cap = 0;
-    DevBuf buf;  // ds bytes (+ padding)
+    DevBuf buf;  // ds bytes (+ padding); a scalar query: `bits` planes of ds bytes, the f32 max_abs 16 bytes after them
+    uint32_t bits = 1;  // 1: the reference's binary query; 4 / 8: bit planes of a scalar query
     ReadyEvent ready;  // the last encode_query
 };
 
@@ -484,7 +627,11 @@ qamd_status alloc_store(qamd_bin *h) {
     return h->rows.alloc(padded * h->ds, true);
 }
 
-template <int G, int ITERS, int UNROLL>
+// calculate_metric's `dim` for a query of `planes` bit planes: dim * (2^planes - 1), exact in f32 (encode_query_scalar
+// refuses dims past 2^24)
+float metric_dim(const qamd_bin *h, uint32_t planes) { return (float)(h->vp.dim * ((1ull << planes) - 1)); }
+
+template <int G, int ITERS, int UNROLL, int PLANES = 1>
 void launch_bin(const qamd_bin *h, const uint4 *qb, float *out, const TopkFilter *filt, hipStream_t s) {
     constexpr int TILE = (64 / G) * UNROLL;
     const uint32_t rc = (uint32_t)(h->ds / 16);
@@ -493,8 +640,8 @@ void launch_bin(const qamd_bin *h, const uint4 *qb, float *out, const TopkFilter
     const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
     const bool exact = rc == (uint32_t)(G * ITERS);
 #define QAMD_BIN_GO(EX, FI)                                                                                  \
-    hipLaunchKernelGGL((bin_scan_kernel<G, ITERS, UNROLL, EX, FI>), dim3(grid), dim3(kScanBlock), 0, s,      \
-                       h->rows.as<uint4>(), qb, (float)h->vp.dim, is_dot, h->vp.invert, (uint32_t)h->count, rc, \
+    hipLaunchKernelGGL((bin_scan_kernel<G, ITERS, UNROLL, EX, FI, PLANES>), dim3(grid), dim3(kScanBlock), 0, s,      \
+                       h->rows.as<uint4>(), qb, metric_dim(h, PLANES), is_dot, h->vp.invert, (uint32_t)h->count, rc, \
                        out, filt ? *filt : TopkFilter{})
     if (filt) {
         if (exact) QAMD_BIN_GO(true, true);
@@ -507,12 +654,17 @@ void launch_bin(const qamd_bin *h, const uint4 *qb, float *out, const TopkFilter
 }
 
 qamd_status words_launch(const qamd_bin *h, const uint32_t *qbits, const uint32_t *ids_dev, uint64_t n,
-                         float *out_dev, hipStream_t s) {
+                         float *out_dev, hipStream_t s, uint32_t planes = 1) {
     if (n == 0) return QAMD_OK;
     int grid = grid_for((n + 3) / 4, kBlock / 64, 8);
-    hipLaunchKernelGGL(bin_words_kernel, dim3(grid), dim3(kBlock), 0, s, h->rows.as<uint32_t>(), qbits,
-                       (float)h->vp.dim, (int)(h->vp.distance_type == QAMD_DOT), h->vp.invert, ids_dev, n,
-                       (uint32_t)h->count, (uint32_t)(h->ds / 4), out_dev);
+#define QAMD_BIN_WORDS(P)                                                                                     \
+    hipLaunchKernelGGL(bin_words_kernel<P>, dim3(grid), dim3(kBlock), 0, s, h->rows.as<uint32_t>(), qbits,    \
+                       metric_dim(h, P), (int)(h->vp.distance_type == QAMD_DOT), h->vp.invert, ids_dev, n,    \
+                       (uint32_t)h->count, (uint32_t)(h->ds / 4), out_dev)
+    if (planes == 8) QAMD_BIN_WORDS(8);
+    else if (planes == 4) QAMD_BIN_WORDS(4);
+    else QAMD_BIN_WORDS(1);
+#undef QAMD_BIN_WORDS
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
 }
@@ -520,18 +672,25 @@ qamd_status words_launch(const qamd_bin *h, const uint32_t *qbits, const uint32_
 // One launch of bin_pairs_kernel (lists == nullptr: the single query bit row for every id).
 qamd_status pairs_launch(const qamd_bin *h, const uint32_t *q_single, const uint8_t *q_batch, uint64_t q_stride,
                          const uint32_t *lists, uint32_t n_lists, const uint32_t *list_rows, const uint32_t *ids_dev,
-                         uint64_t n, float *out_dev, hipStream_t s) {
+                         uint64_t n, float *out_dev, hipStream_t s, uint32_t planes = 1) {
     if (n == 0) return QAMD_OK;
+    if (planes != 1 && (lists || !q_single)) return fail(QAMD_ERR_ARGUMENTS, "bit planes only come with a single query");
     const bool vec16 = h->ds % 16 == 0;
     const uint32_t ppb = pairs_per_block(n, vec16 ? 32 : 16);  // lane groups per workgroup
     const unsigned grid = (unsigned)((n + ppb - 1) / ppb);
-#define QAMD_BIN_PAIRS(V)                                                                                          \
-    hipLaunchKernelGGL(bin_pairs_kernel<V>, dim3(grid), dim3(kBlock), 0, s, h->rows.as<uint32_t>(), q_single, q_batch, \
-                       (uint32_t)q_stride, lists, n_lists, list_rows, (float)h->vp.dim,                            \
+#define QAMD_BIN_PAIRS(V, P)                                                                                       \
+    hipLaunchKernelGGL((bin_pairs_kernel<V, P>), dim3(grid), dim3(kBlock), 0, s, h->rows.as<uint32_t>(), q_single, q_batch, \
+                       (uint32_t)q_stride, lists, n_lists, list_rows, metric_dim(h, P),                            \
                        (int)(h->vp.distance_type == QAMD_DOT), h->vp.invert, ids_dev, n, (uint32_t)h->count,        \
                        (uint32_t)(h->ds / 4), ppb, out_dev)
-    if (vec16) QAMD_BIN_PAIRS(true);
-    else QAMD_BIN_PAIRS(false);
+    if (planes == 8) {
+        if (vec16) QAMD_BIN_PAIRS(true, 8);
+        else QAMD_BIN_PAIRS(false, 8);
+    } else if (planes == 4) {
+        if (vec16) QAMD_BIN_PAIRS(true, 4);
+        else QAMD_BIN_PAIRS(false, 4);
+    } else if (vec16) QAMD_BIN_PAIRS(true, 1);
+    else QAMD_BIN_PAIRS(false, 1);
 #undef QAMD_BIN_PAIRS
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
@@ -540,21 +699,39 @@ qamd_status pairs_launch(const qamd_bin *h, const uint32_t *q_single, const uint
 // out[k] = metric(query bit row `qbits`, row ids[k]) for host or device ids / outputs (run_ids, lists.hpp): the body
 // of score_ids and, with qbits = stored row i, of score_internal_ids.
 qamd_status score_ids_any(const qamd_bin *h, const uint32_t *qbits, const uint32_t *ids, uint64_t n_ids, qamd_mem ids_mem,
-                          float *out, qamd_mem out_mem, hipStream_t s) {
+                          float *out, qamd_mem out_mem, hipStream_t s, uint32_t planes = 1) {
     return run_ids(ids, n_ids, ids_mem, out, out_mem, h->count, s, [&](const uint32_t *ids_dev, uint64_t n, float *out_dev) {
-        return pairs_launch(h, qbits, nullptr, 0, nullptr, 0, nullptr, ids_dev, n, out_dev, s);
+        return pairs_launch(h, qbits, nullptr, 0, nullptr, 0, nullptr, ids_dev, n, out_dev, s, planes);
     });
 }
 
 bool fused_capable(const qamd_bin *h) { return h->ds % 16 == 0 && h->ds / 16 <= 64; }
 
+// The scan of a scalar query's planes: bin_scan_kernel's mapping per row length; only the 8-lane rows scan half the
+// rows per wave, to leave the registers their 16-row tile takes to the planes of a piece.
+template <int PLANES>
+void scan_planes(const qamd_bin *h, const uint4 *qb, float *out_dev, hipStream_t s, const TopkFilter *filt) {
+    const uint32_t rc = (uint32_t)(h->ds / 16);
+    if (rc == 1) launch_bin<1, 1, 4, PLANES>(h, qb, out_dev, filt, s);
+    else if (rc == 2) launch_bin<2, 1, 4, PLANES>(h, qb, out_dev, filt, s);
+    else if (rc <= 4) launch_bin<4, 1, 8, PLANES>(h, qb, out_dev, filt, s);
+    else if (rc <= 8) launch_bin<8, 1, 8, PLANES>(h, qb, out_dev, filt, s);
+    else if (rc <= 16) launch_bin<16, 1, 8, PLANES>(h, qb, out_dev, filt, s);
+    else if (rc <= 32) launch_bin<16, 2, 4, PLANES>(h, qb, out_dev, filt, s);
+    else if (rc <= 48) launch_bin<16, 3, 4, PLANES>(h, qb, out_dev, filt, s);
+    else launch_bin<16, 4, 2, PLANES>(h, qb, out_dev, filt, s);
+}
+
 qamd_status scan_bits(const qamd_bin *h, const void *qbits_dev, float *out_dev, hipStream_t s,
-                      const TopkFilter *filt = nullptr) {
+                      const TopkFilter *filt = nullptr, uint32_t planes = 1) {
     if (h->count == 0) return QAMD_OK;
     const uint32_t rc = (uint32_t)(h->ds / 16);
-    if (!fused_capable(h)) return words_launch(h, static_cast<const uint32_t *>(qbits_dev), nullptr, h->count, out_dev, s);
+    if (!fused_capable(h))
+        return words_launch(h, static_cast<const uint32_t *>(qbits_dev), nullptr, h->count, out_dev, s, planes);
     const uint4 *qb = static_cast<const uint4 *>(qbits_dev);
-    if (rc == 1) launch_bin<1, 1, 4>(h, qb, out_dev, filt, s);
+    if (planes == 8) scan_planes<8>(h, qb, out_dev, s, filt);
+    else if (planes == 4) scan_planes<4>(h, qb, out_dev, s, filt);
+    else if (rc == 1) launch_bin<1, 1, 4>(h, qb, out_dev, filt, s);
     else if (rc == 2) launch_bin<2, 1, 4>(h, qb, out_dev, filt, s);
     else if (rc <= 4) launch_bin<4, 1, 8>(h, qb, out_dev, filt, s);
     else if (rc <= 8) launch_bin<8, 1, 16>(h, qb, out_dev, filt, s);
@@ -568,16 +745,16 @@ qamd_status scan_bits(const qamd_bin *h, const void *qbits_dev, float *out_dev, 
 
 qamd_status scan_into(const qamd_bin *h, const qamd_bin_query *q, float *out_dev, hipStream_t s,
                       const TopkFilter *filt = nullptr) {
-    return scan_bits(h, q->buf.ptr, out_dev, s, filt);
+    return scan_bits(h, q->buf.ptr, out_dev, s, filt, q->bits);
 }
 
-template <int G, int ITERS>
+template <int G, int ITERS, int PLANES>
 qamd_status launch_bin_small(const qamd_bin *h, const uint4 *qb, const SmallTopkPlan &pl, const SmallTopk &p, hipStream_t s) {
     const uint32_t rc = (uint32_t)(h->ds / 16);
     const bool exact = rc == (uint32_t)(G * ITERS);
 #define QAMD_BIN_SMALL(EX)                                                                                         \
-    hipLaunchKernelGGL((bin_topk_small_kernel<G, ITERS, EX>), dim3(pl.workgroups), dim3(1024), 0, s, h->rows.as<uint4>(), \
-                       qb, (float)h->vp.dim, (int)(h->vp.distance_type == QAMD_DOT), h->vp.invert, (uint32_t)h->count, rc, \
+    hipLaunchKernelGGL((bin_topk_small_kernel<G, ITERS, EX, PLANES>), dim3(pl.workgroups), dim3(1024), 0, s, h->rows.as<uint4>(), \
+                       qb, metric_dim(h, PLANES), (int)(h->vp.distance_type == QAMD_DOT), h->vp.invert, (uint32_t)h->count, rc, \
                        pl.rows_per_wg, p)
     if (exact) QAMD_BIN_SMALL(true);
     else QAMD_BIN_SMALL(false);
@@ -588,28 +765,37 @@ qamd_status launch_bin_small(const qamd_bin *h, const uint4 *qb, const SmallTopk
 
 int bin_small_group(uint32_t rc) { return rc == 1 ? 1 : rc == 2 ? 2 : rc <= 4 ? 4 : rc <= 8 ? 8 : rc <= 64 ? 16 : 0; }
 
+template <int PLANES>
 qamd_status launch_small(const qamd_bin *h, const uint4 *qb, const SmallTopkPlan &pl, const SmallTopk &p, hipStream_t s) {
     const uint32_t rc = (uint32_t)(h->ds / 16);
-    if (rc == 1) return launch_bin_small<1, 1>(h, qb, pl, p, s);
-    if (rc == 2) return launch_bin_small<2, 1>(h, qb, pl, p, s);
-    if (rc <= 4) return launch_bin_small<4, 1>(h, qb, pl, p, s);
-    if (rc <= 8) return launch_bin_small<8, 1>(h, qb, pl, p, s);
-    if (rc <= 16) return launch_bin_small<16, 1>(h, qb, pl, p, s);
-    if (rc <= 32) return launch_bin_small<16, 2>(h, qb, pl, p, s);
-    if (rc <= 48) return launch_bin_small<16, 3>(h, qb, pl, p, s);
-    return launch_bin_small<16, 4>(h, qb, pl, p, s);
+    if (rc == 1) return launch_bin_small<1, 1, PLANES>(h, qb, pl, p, s);
+    if (rc == 2) return launch_bin_small<2, 1, PLANES>(h, qb, pl, p, s);
+    if (rc <= 4) return launch_bin_small<4, 1, PLANES>(h, qb, pl, p, s);
+    if (rc <= 8) return launch_bin_small<8, 1, PLANES>(h, qb, pl, p, s);
+    if (rc <= 16) return launch_bin_small<16, 1, PLANES>(h, qb, pl, p, s);
+    // 1024 threads leave 128 registers: several pieces per lane times several planes spill (bin_topk_small sends those on)
+    if constexpr (PLANES > 1) {
+        return fail(QAMD_ERR_ARGUMENTS, "no single-launch top-k for bit planes on rows of more than 16 pieces");
+    } else {
+        if (rc <= 32) return launch_bin_small<16, 2, PLANES>(h, qb, pl, p, s);
+        if (rc <= 48) return launch_bin_small<16, 3, PLANES>(h, qb, pl, p, s);
+        return launch_bin_small<16, 4, PLANES>(h, qb, pl, p, s);
+    }
 }
 
 // The single-launch top-k when the store qualifies (<= 2M rows, k <= 64, 16-byte row pieces): false = not applicable.
 bool bin_topk_small(const qamd_bin *h, const void *qbits_dev, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
-                    qamd_mem out_mem, hipStream_t s, qamd_status &st) {
+                    qamd_mem out_mem, hipStream_t s, qamd_status &st, uint32_t planes = 1) {
     const int g = bin_small_group((uint32_t)(h->ds / 16));
     SmallTopkPlan plan;
     if (!g || !fused_capable(h)) return false;
+    if (planes != 1 && h->ds / 16 > 16) return false;  // scalar queries on long rows: the fused / classic routes
     const uint32_t tile = 2 * (64 / g), least = (uint32_t)std::max<uint64_t>(16 * tile, (128 * 1024) / h->ds);
     if (!small_topk_plan(h->count, k, tile, least, plan)) return false;
     st = small_topk(plan, k, largest, out_ids, out_scores, out_mem, s, [&](const SmallTopk &p, hipStream_t stt) {
-        return launch_small(h, static_cast<const uint4 *>(qbits_dev), plan, p, stt);
+        const uint4 *qb = static_cast<const uint4 *>(qbits_dev);
+        return planes == 8 ? launch_small<8>(h, qb, plan, p, stt)
+               : planes == 4 ? launch_small<4>(h, qb, plan, p, stt) : launch_small<1>(h, qb, plan, p, stt);
     });
     return true;
 }
@@ -793,6 +979,7 @@ qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query, uint64_
         q->nb = nb;
         q->ds = ds;
     }
+    q->bits = 1;
     // Always packed on the device (one implementation); a host query is uploaded first.
     if (qdim) {
         const float *q_dev = query;
@@ -810,14 +997,81 @@ qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query, uint64_
     return QAMD_OK;
 }
 
+// Where a scalar query keeps max_abs, and its f32 staging area, behind `bits` planes of ds bytes.
+static uint64_t scalar_max_abs_at(uint64_t ds, uint32_t bits) { return round_up(bits * ds, 16) + 16; }
+
+// The reference has no counterpart (its query is one bit per dimension): DESIGN 3.2d is the specification.
+qamd_status qamd_bin_encode_query_scalar(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem,
+                                         uint32_t bits, void *stream, qamd_bin_query **query_io) {
+    if (bits == 1) return qamd_bin_encode_query(h, query, qdim, query_mem, stream, query_io);
+    if (bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
+    if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    // dim * (2^bits - 1) and every sum below it must be exact in f32: both limits keep it under 2^24
+    const uint64_t max_dim = bits == 8 ? 65792 : 1118481;
+    if (qdim > max_dim)
+        return fail(QAMD_ERR_ARGUMENTS, "a %u-bit query has at most %llu dimensions, not %llu", bits,
+                    (unsigned long long)max_dim, (unsigned long long)qdim);
+    QAMD_ON_DEVICE(h->device);
+    hipStream_t s = as_stream(stream);
+    const uint64_t nb = row_bytes_of(qdim, h->store), ds = device_stride_of(nb);
+    const uint64_t max_abs_at = scalar_max_abs_at(ds, bits), need = max_abs_at + 16 + qdim * 4 + 16;
+    qamd_bin_query *q = *query_io;
+    std::unique_ptr<qamd_bin_query> fresh;
+    if (!q) {
+        fresh.reset(new qamd_bin_query);
+        q = fresh.get();
+        q->device = h->device;
+    }
+    if (q->ds != ds || q->qdim_cap < qdim || !q->buf.ptr || q->buf.bytes < need) {
+        QAMD_TRY(q->buf.alloc(need, true));  // planes | max_abs | f32 staging
+        q->qdim_cap = qdim;
+        q->nb = nb;
+        q->ds = ds;
+    }
+    q->bits = bits;
+    const float *q_dev = query;
+    if (qdim && query_mem == QAMD_MEM_HOST) {
+        float *stage = reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at + 16);
+        QAMD_TRY(copy_in(stage, query, QAMD_MEM_HOST, qdim * 4, s));
+        q_dev = stage;
+    }
+    hipLaunchKernelGGL(bin_encode_scalar_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint32_t)qdim, (uint32_t)(ds / 4), bits,
+                       q->buf.as<uint32_t>(), reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at));
+    QAMD_HIP(hipGetLastError());
+    QAMD_TRY(q->ready.record(s));
+    if (fresh) *query_io = fresh.release();
+    return QAMD_OK;
+}
+
+qamd_status qamd_bin_query_info(const qamd_bin_query *q, uint32_t *bits, float *max_abs) {
+    if (!q) return fail(QAMD_ERR_ARGUMENTS, "null query");
+    if (bits) *bits = q->bits;
+    if (max_abs) {
+        *max_abs = 0.0f;
+        if (q->bits != 1) {
+            QAMD_ON_DEVICE(q->device);
+            QAMD_TRY(q->ready.wait(nullptr));
+            QAMD_TRY(copy_out(max_abs, QAMD_MEM_HOST, q->buf.as<uint8_t>() + scalar_max_abs_at(q->ds, q->bits), 4, nullptr));
+        }
+    }
+    return QAMD_OK;
+}
+
 qamd_status qamd_bin_query_read(const qamd_bin_query *q, uint8_t *bits, uint64_t capacity, uint64_t *len) {
     if (!q) return fail(QAMD_ERR_ARGUMENTS, "null query");
-    if (len) *len = q->nb;
+    const uint64_t total = q->bits * q->nb;  // a scalar query: its planes, plane 0 first, nb bytes each
+    if (len) *len = total;
     if (bits) {
-        if (capacity < q->nb) return fail(QAMD_ERR_ARGUMENTS, "bits buffer too small");
+        if (capacity < total) return fail(QAMD_ERR_ARGUMENTS, "bits buffer too small");
         QAMD_ON_DEVICE(q->device);
         QAMD_TRY(q->ready.wait(nullptr));
-        QAMD_TRY(copy_out(bits, QAMD_MEM_HOST, q->buf.ptr, q->nb, nullptr));
+        if (q->bits == 1 || q->nb == q->ds) {
+            QAMD_TRY(copy_out(bits, QAMD_MEM_HOST, q->buf.ptr, total, nullptr));
+        } else {  // tiny rows: planes are held at the 4-byte device stride
+            std::vector<uint8_t> wide(q->bits * q->ds);
+            QAMD_TRY(copy_out(wide.data(), QAMD_MEM_HOST, q->buf.ptr, wide.size(), nullptr));
+            for (uint32_t b = 0; b < q->bits; b++) memcpy(bits + b * q->nb, &wide[b * q->ds], q->nb);
+        }
     }
     return QAMD_OK;
 }
@@ -844,7 +1098,7 @@ qamd_status qamd_bin_score_ids(const qamd_bin *h, const qamd_bin_query *q, const
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     QAMD_TRY(q->ready.wait(s));
-    return score_ids_any(h, q->buf.as<uint32_t>(), ids, n_ids, ids_mem, out, out_mem, s);
+    return score_ids_any(h, q->buf.as<uint32_t>(), ids, n_ids, ids_mem, out, out_mem, s, q->bits);
 }
 
 qamd_status qamd_bin_score_point(const qamd_bin *h, const qamd_bin_query *q, uint32_t i, float *out) {
@@ -892,7 +1146,7 @@ qamd_status qamd_bin_topk(const qamd_bin *h, const qamd_bin_query *q, uint32_t k
     QAMD_TRY(q->ready.wait(s));
     {   // small stores: one launch, exact under any number of ties, no status read-back
         qamd_status st = QAMD_OK;
-        if (bin_topk_small(h, q->buf.ptr, k, largest, out_ids, out_scores, out_mem, s, st)) return st;
+        if (bin_topk_small(h, q->buf.ptr, k, largest, out_ids, out_scores, out_mem, s, st, q->bits)) return st;
     }
     if (!fused_capable(h)) {
         return topk_classic(h->count, k, largest, out_ids, out_scores, out_mem, s,
@@ -902,7 +1156,7 @@ qamd_status qamd_bin_topk(const qamd_bin *h, const qamd_bin_query *q, uint32_t k
     scan.scan_scores = [&](float *scores, hipStream_t st) { return scan_into(h, q, scores, st); };
     scan.scan_filter = [&](const TopkFilter &f, hipStream_t st) { return scan_into(h, q, nullptr, st, &f); };
     scan.score_ids = [&](const uint32_t *ids, uint64_t n_ids, float *out, hipStream_t st) {
-        return words_launch(h, q->buf.as<uint32_t>(), ids, n_ids, out, st);
+        return words_launch(h, q->buf.as<uint32_t>(), ids, n_ids, out, st, q->bits);
     };
     return fused_topk(h->count, k, largest, out_ids, out_scores, out_mem, s, scan);
 }

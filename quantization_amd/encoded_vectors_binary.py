@@ -26,14 +26,31 @@ class EncodedBinVector(EncodedQueryBase):
 
     _prefix = "bin"
 
+    def _info(self):
+        bits, max_abs = C.c_uint32(), C.c_float()
+        check(_lib.lib().qamd_bin_query_info(self._h, C.byref(bits), C.byref(max_abs)))
+        return int(bits.value), np.float32(max_abs.value)
+
+    @property
+    def bits(self) -> int:
+        """Bits kept per query dimension: 1 (the reference's query), or the 4 / 8 of a scalar query."""
+        return self._info()[0]
+
+    @property
+    def max_abs(self) -> np.float32:
+        """The largest finite |q_i| a scalar query's codes are scaled by; 0 for a binary query."""
+        return self._info()[1]
+
     @property
     def encoded_vector(self) -> np.ndarray:
+        """The row of bits, shape (nb,); for a scalar query its bit planes, shape (bits, nb), plane 0 first."""
         n = C.c_uint64()
         check(_lib.lib().qamd_bin_query_read(self._h, None, 0, C.byref(n)))
         bits = np.zeros(n.value, dtype=np.uint8)
         if n.value:
             check(_lib.lib().qamd_bin_query_read(self._h, C.c_void_p(bits.ctypes.data), n.value, None))
-        return bits
+        planes = self.bits
+        return bits if planes == 1 else bits.reshape(planes, -1)
 
 
 class EncodedVectorsBin(EncodedVectorsBase):
@@ -68,6 +85,20 @@ class EncodedVectorsBin(EncodedVectorsBase):
             check(_lib.lib().qamd_bin_encode(buf.ptr, buf.mem, C.byref(vp), int(store), stop, None,
                                              stream_ptr(stream), C.byref(out)))
         return cls(out, vector_parameters, store, dev)
+
+    def encode_query(self, query, reuse=None, stream=None, *, query_bits: int = 1):
+        """EncodedVectors::encode_query (:288-291).  query_bits = 4 or 8 keeps that many bits per query dimension
+        against the same one-bit rows (no counterpart in the reference); every single-query scoring
+        call takes the result."""
+        if query_bits == 1:
+            return super().encode_query(query, reuse, stream)
+        check_same_device(self._device, query)
+        buf = in_buf(query, np.float32)
+        n = int(np.prod(tuple(query.shape))) if hasattr(query, "shape") else len(query)
+        h = reuse._h if reuse is not None else C.c_void_p()
+        check(_lib.lib().qamd_bin_encode_query_scalar(self._h, buf.ptr, n, buf.mem, int(query_bits), stream_ptr(stream),
+                                                      C.byref(h)))
+        return reuse if reuse is not None else self._query_cls(h)
 
     @classmethod
     def encode_stream(cls, make_batches, vector_parameters: VectorParameters, stop_condition=None, *,

@@ -94,12 +94,12 @@ def same_counts(ids, truth):
     return [len(t & set(int(x) for x in ids[:c])) for c in (10, 20, 30)]
 
 
-def run_gpu(enc, queries_host, truth, largest):
+def run_gpu(enc, queries_host, truth, largest, encode_kw={}):
     ms, same = [], np.zeros(3)
     all_ids = []
     for j, q in enumerate(queries_host):
         t0 = time.perf_counter()
-        ids, _ = enc.topk(enc.encode_query(q), 30, largest=largest)  # host query in, host ids out: one search
+        ids, _ = enc.topk(enc.encode_query(q, **encode_kw), 30, largest=largest)  # host query in, host ids out: one search
         ms.append((time.perf_counter() - t0) * 1e3)
         same += same_counts(ids, truth[j])
         all_ids.append(np.asarray(ids))
@@ -172,8 +172,12 @@ def main():
     ap.add_argument("--orig-dtype", default="f32", choices=["f32", "f16", "bf16"],
                     help="with --rescore: what the store of originals keeps (f32 borrows the data tensor; f16 / bf16 are "
                          "narrowed copies of it, half the HBM)")
+    ap.add_argument("--bin-query-bits", default="1", metavar="BITS[,BITS]",
+                    help="binary: also search with 4- / 8-bit scalar queries against the same one-bit rows (DESIGN 3.2d), "
+                         "e.g. 1,4,8; each bit count past 1 adds a gpu_query_bits_N entry to the binary record")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    query_bits = [int(x) for x in args.bin_query_bits.split(",")]
     dev = torch.device("cuda", 0)
     out = open(args.out, "w") if args.out else None
 
@@ -226,6 +230,13 @@ def main():
                         enc.topk(enc.encode_query(q_host[0]), 30, largest=largest)
                     gpu, gpu_ids = run_gpu(enc, q_host, truth, largest)
                     rec = dict(base, quantizer=name, gpu=gpu, encode_seconds_all_variants=round(encode_s, 3))
+                    if kind == "binary":
+                        for bits in query_bits:
+                            if bits != 1:
+                                kw = {"query_bits": bits}
+                                for _ in range(3):
+                                    enc.topk(enc.encode_query(q_host[0], **kw), 30, largest=largest)
+                                rec[f"gpu_query_bits_{bits}"] = run_gpu(enc, q_host, truth, largest, kw)[0]
                     if orig is not None:
                         for _ in range(3):
                             enc.topk_rescored(enc.encode_query(q_host[0]), orig, q_host[0], 30, args.rescore, largest=largest)
