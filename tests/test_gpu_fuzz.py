@@ -5,16 +5,17 @@ import numpy as np
 import pytest
 
 import quantization_amd as qa
-from util import assert_bits_equal
+from util import assert_bits_equal, scalar_codes, scalar_planes, scalar_scores, topk_want
 
 pytestmark = pytest.mark.gpu
 D = qa.DistanceType
 
 
 def _topk_want(scores, k, largest):
-    n = scores.size
-    order = np.lexsort((np.arange(n), -scores if largest else scores))[: min(k, n)]
-    return order.astype(np.uint32), scores[order]
+    """util.topk_want without its padding: the rows a store of fewer than k rows really has."""
+    wi, ws = topk_want(scores, k, largest)
+    m = min(k, scores.size)
+    return wi[:m], ws[:m]
 
 
 def test_fuzz_u8(qo):
@@ -125,3 +126,43 @@ def test_fuzz_u8_batch():
             wi, ws = _topk_want(want, k, largest)
             assert np.array_equal(ids[qi][: wi.size], wi), tag + f" topk ids of query {qi}"
             assert_bits_equal(sc[qi][: wi.size], ws, tag + f" topk scores of query {qi}")
+
+
+def test_fuzz_binary_scalar_query():
+    """4- and 8-bit scalar queries against binary rows against the per-dimension oracle of util.py, on
+    the store's own bytes: every fifth case has rows of more than 16 16-byte pieces."""
+    rng = np.random.default_rng(20261018)
+    for case in range(30):
+        n = int(rng.integers(1, 4000))
+        dim = int(rng.integers(2049, 9000)) if case % 5 == 4 else int(rng.integers(1, 700))
+        bits = int(rng.choice([4, 8]))
+        dist = [D.Dot, D.L1, D.L2][int(rng.integers(0, 3))]
+        invert = bool(rng.integers(0, 2))
+        kind = [qa.BitsStoreType.U8, qa.BitsStoreType.U128][int(rng.integers(0, 2))]
+        data = rng.standard_normal((n, dim)).astype(np.float32)
+        flat = data.reshape(-1)
+        at = rng.integers(0, flat.size, size=6)
+        flat[at[:3]] = 0.0
+        flat[at[3:]] = -0.0
+        query = rng.standard_normal(dim).astype(np.float32)
+        odd = [None, np.nan, np.inf, -np.inf][int(rng.integers(0, 4))]
+        if odd is not None:
+            query[int(rng.integers(0, dim))] = odd
+        tag = f"case {case}: n={n} dim={dim} bits={bits} {dist.name} invert={invert} {kind.name} odd={odd}"
+        enc = qa.EncodedVectorsBin.encode(data, qa.VectorParameters(dim, n, dist, invert), store=kind)
+        rows = enc.storage_bytes()
+        q = enc.encode_query(query, query_bits=bits)
+        codes, a = scalar_codes(query, bits)
+        assert_bits_equal(q.max_abs, a, tag + " max_abs")
+        assert np.array_equal(q.encoded_vector, scalar_planes(codes, bits, rows.shape[1])), tag + " planes"
+        want = scalar_scores(rows, codes, dim, bits, dist, invert)
+        assert_bits_equal(enc.score_all(q), want, tag + " score_all")
+        ids = rng.integers(0, n, size=int(rng.integers(1, 3001))).astype(np.uint32)
+        assert_bits_equal(enc.score_ids(q, ids), want[ids], tag + " score_ids")
+        assert_bits_equal(enc.score_point(q, n - 1), want[n - 1], tag + " score_point(last row)")
+        k = int(rng.integers(1, 40))
+        largest = bool(rng.integers(0, 2))
+        gi, gs = enc.topk(q, k, largest=largest)
+        wi, ws = topk_want(want, k, largest)
+        assert np.array_equal(gi, wi), tag + f" topk ids (k={k} largest={largest})"
+        assert_bits_equal(gs, ws, tag + " topk scores")

@@ -120,3 +120,95 @@ def wide_sum_cases():
             v = rng.integers(0, 18, size=dim, dtype=np.uint8)
             cases.append(("l1_sat", dim, q, v))
     return cases
+
+
+# ------------------------------------------------------------------ scalar queries against binary rows, per dimension
+# DESIGN.md 3.2d read dimension by dimension: no bit planes, no popcounts.  Integers are int64; the only f32 steps are
+# the ones the text names.  tests/test_binary_scalar_query_model.py checks this oracle without a GPU.
+def scalar_codes(query, bits: int):
+    """(codes uint32[dim], a float32) of a `bits`-bit scalar query: a = max |q_i| over the finite entries (0 when there
+    is none); a == 0 -> every code (L + 1) / 2; else scale = (float)L / (a + a), NaN counts as 0.0f,
+    t_i = (q_i + a) * scale, c_i = min(L, (uint32)(t_i + 0.5f)); last +inf -> L and -inf -> 0.  Single f32 operations."""
+    f32 = np.float32
+    q = np.asarray(query, dtype=f32).ravel()
+    L = (1 << bits) - 1
+    finite = np.isfinite(q)
+    a = f32(np.abs(q[finite]).max()) if finite.any() else f32(0.0)
+    codes = np.full(q.size, (L + 1) // 2, dtype=np.uint32)
+    if a != 0:
+        scale = f32(f32(L) / f32(a + a))
+        v = np.where(finite, q, f32(0.0))  # NaN counts as 0.0f; the infinite entries are set below
+        t = (v + a).astype(f32) * scale    # float32 arrays: numpy rounds each step to f32, element by element
+        half = (t.astype(f32) + f32(0.5)).astype(f32)
+        codes[:] = np.minimum(L, np.trunc(half).astype(np.int64))  # truncation; t + 0.5 >= 0.5
+    codes[np.isposinf(q)] = L
+    codes[np.isneginf(q)] = 0
+    return codes, a
+
+
+def scalar_codes_f64(query, bits: int):
+    """The same codes in float64, floor((q + a) * L / (2a) + 0.5), over the finite entries; needs a > 0.
+    Returns (codes int64[finite entries], t + 0.5 float64[finite entries], finite mask)."""
+    q = np.asarray(query, dtype=np.float32).ravel()
+    L = (1 << bits) - 1
+    finite = np.isfinite(q)
+    v = q[finite].astype(np.float64)
+    a = np.abs(v).max()
+    assert a > 0
+    half = (v + a) * L / (2.0 * a) + 0.5
+    return np.minimum(L, np.floor(half)).astype(np.int64), half, finite
+
+
+def scalar_planes(codes, bits: int, nb: int) -> np.ndarray:
+    """uint8[bits, nb]: the stored form of a scalar query - bit b of code i at bit i % 8 of byte i / 8 of plane b, zero
+    pad bits - set one bit at a time."""
+    out = np.zeros((bits, nb), dtype=np.uint8)
+    for i, c in enumerate(np.asarray(codes).tolist()):
+        for b in range(bits):
+            if (c >> b) & 1:
+                out[b, i // 8] |= 1 << (i % 8)
+    return out
+
+
+def scalar_xor(rows_u8, codes, dim: int, bits: int) -> np.ndarray:
+    """int64[n]: X of every stored bit row.  Bit i of a row is byte i / 8, bit i % 8 (s_i in {0, 1});
+    S = sum_i (2 s_i - 1)(2 c_i - L) and X = (dim * L - S) / 2, exact.  Only the first `dim` bits of a row are read."""
+    rows_u8 = np.asarray(rows_u8, dtype=np.uint8)
+    n = rows_u8.shape[0]
+    L = (1 << bits) - 1
+    centred = 2 * np.asarray(codes, dtype=np.int64)[:dim] - L
+    assert centred.size == dim
+    at = np.arange(dim)
+    x = np.empty(n, dtype=np.int64)
+    for r0 in range(0, n, 2048):
+        block = rows_u8[r0:r0 + 2048]
+        s = ((block[:, at // 8] >> (at % 8).astype(np.uint8)) & 1).astype(np.int64)
+        twice = dim * L - (2 * s - 1) @ centred
+        assert not np.any(twice & 1) and np.all(twice >= 0) and np.all(twice <= 2 * dim * L)
+        x[r0:r0 + 2048] = twice // 2
+    return x
+
+
+def scalar_metric(x, dim: int, bits: int, dist, invert) -> np.ndarray:
+    """calculate_metric (encoded_vectors_binary.rs:237-252) on X with dim * L as its `dim`, in f32.
+    `dist`: a DistanceType (or its name)."""
+    dim_l = dim * ((1 << bits) - 1)
+    assert dim_l < 1 << 24, "past this the f32 steps below would round"
+    xor_product = np.asarray(x).astype(np.float32)
+    zeros_count = (np.float32(dim_l) - xor_product).astype(np.float32)
+    is_dot = getattr(dist, "name", str(dist)) == "Dot"
+    if is_dot and invert:
+        out = xor_product - zeros_count
+    elif is_dot:
+        out = zeros_count - xor_product
+    elif invert:  # L1 | L2, true
+        out = zeros_count - xor_product
+    else:         # L1 | L2, false
+        out = xor_product - zeros_count
+    return out.astype(np.float32)
+
+
+def scalar_scores(rows_u8, codes, dim: int, bits: int, dist, invert) -> np.ndarray:
+    """float32[n]: the score of every stored bit row against the codes of a scalar query (scalar_xor, then
+    scalar_metric).  bits = 1 with codes (q_i > 0) is the binary score."""
+    return scalar_metric(scalar_xor(rows_u8, codes, dim, bits), dim, bits, dist, invert)
