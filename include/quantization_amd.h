@@ -330,9 +330,9 @@ QAMD_API qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query
  * with dim * L in place of dim.  bits = 1 is qamd_bin_encode_query; other values than 1, 4, 8 and dims whose dim * L
  * would leave f32's exact integers (above 65 792 at 8 bits, 1 118 481 at 4) are QAMD_ERR_ARGUMENTS.  *query_io is
  * reused as by qamd_bin_encode_query and may change its bit count from call to call.  qamd_bin_score_point / _ids /
- * _all, qamd_bin_topk and qamd_bin_topk_rescored take either kind of query.
- * Deliberately left out: qamd_bin_query_batch and the qamd_bin_sharded_* query types are separate structs and stay
- * binary-only (a scalar batch is an int8 dot product on the matrix cores: the natural follow-up). */
+ * _all, qamd_bin_topk and qamd_bin_topk_rescored take either kind of query; a qamd_bin_query_batch holds scalar queries
+ * through qamd_bin_encode_query_batch_scalar below.
+ * Deliberately left out: the qamd_bin_sharded_* query types are separate structs and stay binary-only. */
 QAMD_API qamd_status qamd_bin_encode_query_scalar(const qamd_bin *h, const float *query, uint64_t qdim,
                                                   qamd_mem query_mem, uint32_t bits, void *stream,
                                                   qamd_bin_query **query_io);
@@ -374,6 +374,36 @@ typedef struct qamd_bin_query_batch qamd_bin_query_batch; /* n x EncodedBinVecto
 QAMD_API qamd_status qamd_bin_encode_query_batch(const qamd_bin *h, const float *queries, uint64_t n_queries,
                                                  uint64_t qdim, qamd_mem queries_mem, void *stream,
                                                  qamd_bin_query_batch **batch_io);
+/* A batch of scalar queries.  The reference has NO counterpart; DESIGN.md 3.2d is the specification.  Query q of the batch
+ * is exactly what qamd_bin_encode_query_scalar gives for row q of `queries` (a = max |q_i| per query, never across the
+ * batch; NaN, +-inf and the all-zero query as there), and every batch call below - qamd_bin_score_batch, _score_ids_batch,
+ * _topk_batch, _topk_batch_rescored - gives for it, bit for bit, what the single-query call gives for that query.  bits = 1
+ * is qamd_bin_encode_query_batch; other values than 1, 4, 8 and the dims qamd_bin_encode_query_scalar refuses are
+ * QAMD_ERR_ARGUMENTS.  *batch_io is reused as by qamd_bin_encode_query_batch and may change its bit count from call to
+ * call.  From 5 (score_batch) / 12 (topk_batch) queries on, on rows of whole 16-byte pieces, 64 .. 4992 bits, a scalar batch is one int8
+ * contraction per 32 / 64 queries on the matrix cores (bin_gemm_rs_kernel); elsewhere its queries are scanned one by one.
+ * Out of scope: the qamd_bin_sharded_* query types (binary-only), bench.py (it measures binary batches) and any tuning of
+ * the int8 kernel.  Measured against a loop of single-query calls (profiles/bin_scalar_batch.txt, 50M x 1024): 3.9 - 4.4 x
+ * at 8 queries (score_batch), 12 - 18 x from 32 queries on (both calls); the two thresholds are the binary route's and
+ * batches of 2 .. 7 (topk_batch: 2 .. 11) queries have not been timed on the matrix cores. */
+QAMD_API qamd_status qamd_bin_encode_query_batch_scalar(const qamd_bin *h, const float *queries, uint64_t n_queries,
+                                                        uint64_t qdim, qamd_mem queries_mem, uint32_t bits, void *stream,
+                                                        qamd_bin_query_batch **batch_io);
+/* No counterpart in the reference: *bits = bits per query dimension (1 for a batch from
+ * qamd_bin_encode_query_batch), *n_queries = the queries it holds.  Either pointer may be NULL. */
+QAMD_API qamd_status qamd_bin_query_batch_info(const qamd_bin_query_batch *b, uint32_t *bits, uint64_t *n_queries);
+/* Query q of the batch as qamd_bin_query_read gives a single query: *len = bits x row bytes, plane 0 first (one row of
+ * bits for a binary batch).  For tests and bindings; synchronises. */
+QAMD_API qamd_status qamd_bin_query_batch_read(const qamd_bin_query_batch *b, uint64_t q, uint8_t *bits,
+                                               uint64_t capacity, uint64_t *len);
+/* Which kernel qamd_bin_score_batch (k = 0) or the filter of qamd_bin_topk_batch (k > 0) takes for THIS store and batch,
+ * binary or scalar, as a static string: "bin_gemm_rs_kernel" (int8 matrix cores), "bin_gemm_rs4_kernel" /
+ * "bin_gemm_qs4_kernel" (FP4 matrix cores: binary batches only), "bin_scan_multi_kernel" (2 .. 8 binary queries per pass
+ * over the rows), or the per-query routes "bin_scan_kernel", "bin_words_kernel" (rows that are not whole 16-byte pieces,
+ * or longer than 64 of them) and, for k > 0 on small stores, "bin_topk_small_kernel".  NULL for a batch that does not
+ * belong to the store.  For measurement harnesses, as qamd_pq_scan_kernel: the entry points and this accessor call the
+ * same routing predicates. */
+QAMD_API const char *qamd_bin_batch_kernel(const qamd_bin *h, const qamd_bin_query_batch *b, uint32_t k);
 QAMD_API void qamd_bin_query_batch_free(qamd_bin_query_batch *b);
 /* out[q * count + i] = score_point(query q, i). */
 QAMD_API qamd_status qamd_bin_score_batch(const qamd_bin *h, const qamd_bin_query_batch *b, float *out,

@@ -140,6 +140,10 @@ def lib() -> C.CDLL:
         "qamd_bin_topk": (i32, [vp, vp, u32, i32, vp, vp, i32, vp]),
         "qamd_bin_free": (None, [vp]),
         "qamd_bin_encode_query_batch": (i32, [vp, vp, u64, u64, i32, vp, pp]),
+        "qamd_bin_encode_query_batch_scalar": (i32, [vp, vp, u64, u64, i32, u32, vp, pp]),
+        "qamd_bin_query_batch_info": (i32, [vp, C.POINTER(u32), C.POINTER(u64)]),
+        "qamd_bin_query_batch_read": (i32, [vp, u64, vp, u64, C.POINTER(u64)]),
+        "qamd_bin_batch_kernel": (C.c_char_p, [vp, vp, u32]),
         "qamd_bin_query_batch_free": (None, [vp]),
         "qamd_bin_score_batch": (i32, [vp, vp, vp, i32, vp]),
         "qamd_bin_topk_batch": (i32, [vp, vp, u32, i32, vp, vp, i32, vp]),

@@ -387,8 +387,8 @@ __global__ __launch_bounds__(kBlock) void bin_words_kernel(const uint32_t *__res
 // bit row l of a query batch for the pairs of list l; lists and list_rows -> stored row list_rows[l].
 // VEC16 (ds % 16 == 0): 8 lanes per pair, 16-byte pieces, up to four in flight per lane; else 16 lanes
 // per pair at dword granularity (rows of 4 and 8 bytes).
-// PLANES > 1: only with `lists` == nullptr and q_single the planes of a scalar query (plane b at q_single + b * row_words);
-// a stored row passed as q_single (score_internal) is one plane.
+// PLANES > 1: the query is the planes of a scalar query, plane b at + b * row_words dwords: q_single, or with lists the
+// planes of query l of a scalar batch at q_batch + l * q_stride.  A stored row (score_internal, list_rows) is one plane.
 template <bool VEC16, int PLANES = 1>
 __global__ __launch_bounds__(kBlock) void bin_pairs_kernel(const uint32_t *__restrict__ rows, const uint32_t *q_single,
                                                           const uint8_t *__restrict__ q_batch, uint32_t q_stride,
@@ -485,16 +485,25 @@ __global__ __launch_bounds__(kBlock) void bin_encode_kernel(const float *__restr
     }
 }
 
-// Scalar query encoding (the reference has no counterpart), one workgroup: a = max |q_i| over the finite
-// entries, then c_i = min(L, (u32)((q_i + a) * (L / (a + a)) + 0.5f)) with L = 2^bits - 1 - single f32 operations in
-// this order, the division hipcc's correctly rounded one - and plane b = bit b of every c_i in the rows' bit order
-// (one ballot per plane and 64 entries).  Every dword of every plane is written, pad bits as zeros.
+// Scalar query encoding (the reference has no counterpart), one workgroup per query: a = max |q_i| over the
+// query's finite entries, then c_i = min(L, (u32)((q_i + a) * (L / (a + a)) + 0.5f)) with L = 2^bits - 1 - single f32
+// operations in this order, the division hipcc's correctly rounded one - and plane b = bit b of every c_i in the rows' bit
+// order (one ballot per plane and 64 entries).  Every dword of every plane is written, pad bits as zeros.
+// Workgroup g takes query g: its floats at query + g * dim, its planes at planes + g * plane_words, its max_abs at
+// max_abs[g].  codes != nullptr (a query batch): also the matrix-core image of the query at codes + g * code_pitch - the
+// centred codes d_i = c_i - (L + 1) / 2 as int8, one byte per dimension, zero bytes from dim to code_pitch - 16, and
+// C = sum c_i as a u32 at code_pitch - 16 (bin_gemm_rs_kernel copies the whole pitch into its LDS tile).
 __global__ __launch_bounds__(kBlock) void bin_encode_scalar_kernel(const float *__restrict__ query, uint32_t dim,
                                                                   uint32_t row_words, uint32_t bits,
-                                                                  uint32_t *__restrict__ planes, float *__restrict__ max_abs) {
+                                                                  uint32_t *__restrict__ planes, uint32_t plane_words,
+                                                                  float *__restrict__ max_abs, int8_t *__restrict__ codes,
+                                                                  uint32_t code_pitch) {
     __shared__ float wave_max[kBlock / 64];
+    __shared__ uint32_t wave_sum[kBlock / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inf = __builtin_huge_valf();
+    query += (size_t)blockIdx.x * dim;
+    planes += (size_t)blockIdx.x * plane_words;
     float a = 0.0f;
     for (uint32_t i = threadIdx.x; i < dim; i += kBlock) {
         const float v = fabsf(query[i]);
@@ -507,10 +516,12 @@ __global__ __launch_bounds__(kBlock) void bin_encode_scalar_kernel(const float *
     a = wave_max[0];
 #pragma unroll
     for (int w = 1; w < kBlock / 64; w++) a = fmaxf(a, wave_max[w]);
-    if (threadIdx.x == 0) *max_abs = a;
+    if (threadIdx.x == 0) max_abs[blockIdx.x] = a;
     const uint32_t L = (1u << bits) - 1u;
     const float scale = a == 0.0f ? 0.0f : (float)L / (a + a);
-    const uint32_t steps = (row_words + 1) / 2;
+    // 64 entries per step; the code image is at least as long as a plane (whole 128-entry blocks)
+    const uint32_t steps = codes ? (code_pitch - 16) / 64 : (row_words + 1) / 2;
+    uint32_t csum = 0;
     for (uint32_t st = wave; st < steps; st += kBlock / 64) {
         const uint32_t i = st * 64 + lane;
         uint32_t c = 0;
@@ -527,6 +538,10 @@ __global__ __launch_bounds__(kBlock) void bin_encode_scalar_kernel(const float *
             if (v == inf) c = L;
             if (v == -inf) c = 0;
         }
+        if (codes) {
+            codes[(size_t)blockIdx.x * code_pitch + i] = i < dim ? (int8_t)((int)c - (int)((L + 1u) / 2u)) : (int8_t)0;
+            csum += c;
+        }
         unsigned long long mine = 0;
         for (uint32_t b = 0; b < bits; b++) {
             const unsigned long long m = __ballot((c >> b) & 1u);
@@ -537,6 +552,20 @@ __global__ __launch_bounds__(kBlock) void bin_encode_scalar_kernel(const float *
             const uint32_t w = st * 2;
             if (w < row_words) dst[w] = (uint32_t)mine;
             if (w + 1 < row_words) dst[w + 1] = (uint32_t)(mine >> 32);
+        }
+    }
+    if (codes) {  // C = sum c_i <= 255 * 1118481 < 2^32
+#pragma unroll
+        for (int o = 32; o; o >>= 1) csum += (uint32_t)__shfl_xor((int)csum, o);
+        if (lane == 0) wave_sum[wave] = csum;
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            uint32_t total = 0;
+#pragma unroll
+            for (int w = 0; w < kBlock / 64; w++) total += wave_sum[w];
+            // the last 16 bytes of the pitch: C, then three zero dwords
+            reinterpret_cast<uint32_t *>(codes + (size_t)blockIdx.x * code_pitch + (code_pitch - 16))[threadIdx.x] =
+                threadIdx.x == 0 ? total : 0u;
         }
     }
 }
@@ -674,7 +703,7 @@ qamd_status pairs_launch(const qamd_bin *h, const uint32_t *q_single, const uint
                          const uint32_t *lists, uint32_t n_lists, const uint32_t *list_rows, const uint32_t *ids_dev,
                          uint64_t n, float *out_dev, hipStream_t s, uint32_t planes = 1) {
     if (n == 0) return QAMD_OK;
-    if (planes != 1 && (lists || !q_single)) return fail(QAMD_ERR_ARGUMENTS, "bit planes only come with a single query");
+    if (planes != 1 && (list_rows || !(q_single || q_batch))) return fail(QAMD_ERR_ARGUMENTS, "bit planes only come with a query");
     const bool vec16 = h->ds % 16 == 0;
     const uint32_t ppb = pairs_per_block(n, vec16 ? 32 : 16);  // lane groups per workgroup
     const unsigned grid = (unsigned)((n + ppb - 1) / ppb);
@@ -783,15 +812,20 @@ qamd_status launch_small(const qamd_bin *h, const uint4 *qb, const SmallTopkPlan
     }
 }
 
-// The single-launch top-k when the store qualifies (<= 2M rows, k <= 64, 16-byte row pieces): false = not applicable.
-bool bin_topk_small(const qamd_bin *h, const void *qbits_dev, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
-                    qamd_mem out_mem, hipStream_t s, qamd_status &st, uint32_t planes = 1) {
+// Whether the single-launch top-k applies to this store, k and kind of query, and its plan.
+bool bin_small_plan(const qamd_bin *h, uint32_t k, uint32_t planes, SmallTopkPlan &plan) {
     const int g = bin_small_group((uint32_t)(h->ds / 16));
-    SmallTopkPlan plan;
     if (!g || !fused_capable(h)) return false;
     if (planes != 1 && h->ds / 16 > 16) return false;  // scalar queries on long rows: the fused / classic routes
     const uint32_t tile = 2 * (64 / g), least = (uint32_t)std::max<uint64_t>(16 * tile, (128 * 1024) / h->ds);
-    if (!small_topk_plan(h->count, k, tile, least, plan)) return false;
+    return small_topk_plan(h->count, k, tile, least, plan);
+}
+
+// The single-launch top-k when the store qualifies (<= 2M rows, k <= 64, 16-byte row pieces): false = not applicable.
+bool bin_topk_small(const qamd_bin *h, const void *qbits_dev, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
+                    qamd_mem out_mem, hipStream_t s, qamd_status &st, uint32_t planes = 1) {
+    SmallTopkPlan plan;
+    if (!bin_small_plan(h, k, planes, plan)) return false;
     st = small_topk(plan, k, largest, out_ids, out_scores, out_mem, s, [&](const SmallTopk &p, hipStream_t stt) {
         const uint4 *qb = static_cast<const uint4 *>(qbits_dev);
         return planes == 8 ? launch_small<8>(h, qb, plan, p, stt)
@@ -1036,7 +1070,8 @@ qamd_status qamd_bin_encode_query_scalar(const qamd_bin *h, const float *query, 
         q_dev = stage;
     }
     hipLaunchKernelGGL(bin_encode_scalar_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint32_t)qdim, (uint32_t)(ds / 4), bits,
-                       q->buf.as<uint32_t>(), reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at));
+                       q->buf.as<uint32_t>(), 0u, reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at),
+                       static_cast<int8_t *>(nullptr), 0u);
     QAMD_HIP(hipGetLastError());
     QAMD_TRY(q->ready.record(s));
     if (fresh) *query_io = fresh.release();
@@ -1174,7 +1209,14 @@ struct qamd_bin_query_batch {
     int device = 0;
     uint64_t nb = 0, ds = 0, n_queries = 0;
     uint64_t q_stride = 0;  // bytes between two queries' bit rows (multiple of 16)
-    DevBuf bits;            // [n_queries][q_stride]
+    DevBuf bits;            // [n_queries][q_stride]; binary batches only
+    // a batch of scalar queries (qamd_bin_encode_query_batch_scalar) holds two other images and NO bit rows:
+    uint32_t qbits = 1;       // bits per query dimension: 1, 4 or 8
+    uint64_t p_stride = 0;    // bytes between two queries' planes (multiple of 16); a query's planes as in qamd_bin_query
+    uint64_t code_pitch = 0;  // bytes between two queries' centred int8 codes: bin_gemm_rs_kernel's LDS pitch of this row length
+    DevBuf planes;            // [n_queries][p_stride]
+    DevBuf codes;             // [n_queries][code_pitch]: d_i, zero bytes, C = sum c_i in the last 16
+    DevBuf max_abs;           // [n_queries] f32
 };
 
 namespace {
@@ -1202,11 +1244,14 @@ void launch_bin_multi(const qamd_bin *h, const uint8_t *qbits, uint64_t q_stride
 #undef QAMD_BIN_MULTI
 }
 
+// The rows bin_scan_multi_kernel has forms for: 8 .. 64 pieces (every such store has the 4- and 2-query forms).
+bool multi_rows(const qamd_bin *h) { return h->ds % 16 == 0 && h->ds / 16 >= 8 && h->ds / 16 <= 64; }
+
 // Queries [q0, q0 + nq) with nq in {8, 4, 2}: rows of 8 .. 64 pieces (dims 1024 .. 8192 at the u128 granule).
 template <int NQ> bool multi_step(const qamd_bin *h, const uint8_t *qbits, uint64_t q_stride, float *out, hipStream_t s,
                                   const TopkFilterSlices *slices = nullptr) {
     const uint32_t rc = (uint32_t)(h->ds / 16);
-    if (rc < 8 || rc > 64 || h->ds % 16) return false;
+    if (!multi_rows(h)) return false;
     if (rc == 8) launch_bin_multi<8, 1, 8, NQ>(h, qbits, q_stride, out, s, slices);
     else if (rc <= 16) launch_bin_multi<16, 1, 4, NQ>(h, qbits, q_stride, out, s, slices);
     else if (rc <= 32) launch_bin_multi<16, 2, 2, NQ>(h, qbits, q_stride, out, s, slices);
@@ -1234,7 +1279,17 @@ template <int NQ> bool multi_step(const qamd_bin *h, const uint8_t *qbits, uint6
 // lists, scatter, emit - is batch_common.hpp's, as for u8.
 namespace {
 
-template <int MODE, bool LOW, int MI>  // MODE 0: scores out; 1 / 2: filter for the largest / smallest
+//
+// CODES (a batch of 4- or 8-bit scalar queries): the same contraction with another byte per dimension.  With
+// the centred codes d_i = c_i - (L + 1) / 2 (int8: [-8, 7] or [-128, 127]), A = sum_i s_i d_i, C = sum c_i and P = pop_v,
+//   X = sum_b 2^b popcount(plane_b xor row) = C - P - 2A
+//   dim L - 2X = (4A + (dim L - 2C)) + 2P        2X - dim L = (-4A + (2C - dim L)) - 2P
+// - the epilogue above with q_offset from C and the OTHER sign of the row term.  `qbits` is then the batch's code image
+// (bin_encode_scalar_kernel: q_stride = this kernel's LDS pitch, d_i bytes, C in the last 16 bytes), copied into the
+// tile 16 bytes at a time, and dim_f is dim * L.  4- and 8-bit queries are both one int8 per dimension: one instantiation
+// serves both.  Exact for the same reason: |4A| <= 512 dim, |q_offset| <= 255 dim, 2P <= 2 dim, and the route takes rows
+// of at most 4992 bits (bin_mfma_frags), so every operand and partial sum stays below 769 * 4992 < 2^22.
+template <int MODE, bool LOW, int MI, bool CODES = false>  // MODE 0: scores out; 1 / 2: filter for the largest / smallest
 __global__ __launch_bounds__(512) void bin_gemm_rs_kernel(const uint8_t *__restrict__ rows, uint32_t ds,
                                                          const uint8_t *__restrict__ qbits, uint32_t q_stride, float dim_f,
                                                          int zx, uint32_t n_rows, uint32_t n_queries, uint32_t q0,
@@ -1264,6 +1319,14 @@ __global__ __launch_bounds__(512) void bin_gemm_rs_kernel(const uint8_t *__restr
         return v;
     };
     // the query tile as bytes (queries past the batch: zero), its offsets and integer bounds
+    if (CODES) {
+        for (uint32_t idx = t; idx < (uint32_t)TQ * (PA / 16); idx += 512) {  // 16 code bytes each: q_stride == PA
+            const uint32_t q = idx / (PA / 16), piece = idx % (PA / 16);
+            v4i d = {0, 0, 0, 0};
+            if (q0 + q < n_queries) d = *reinterpret_cast<const v4i *>(qbits + (uint64_t)(q0 + q) * q_stride + piece * 16);
+            *reinterpret_cast<v4i *>(lds_raw + q * PA + piece * 16) = d;
+        }
+    } else
     for (uint32_t idx = t; idx < (uint32_t)TQ * nkb * 8; idx += 512) {  // 16 bits each
         const uint32_t q = idx / (nkb * 8), piece = idx % (nkb * 8);
         uint32_t bits16 = 0;
@@ -1271,7 +1334,10 @@ __global__ __launch_bounds__(512) void bin_gemm_rs_kernel(const uint8_t *__restr
         *reinterpret_cast<v4i *>(lds_raw + q * PA + piece * 16) = expand(bits16);
     }
     if (t < TQ) {
-        uint32_t pq = 0;
+        uint32_t pq = 0;  // CODES: C = sum c_i, kept behind the query's code bytes
+        if (CODES) {
+            if (q0 + t < n_queries) pq = *reinterpret_cast<const uint32_t *>(qbits + (uint64_t)(q0 + t) * q_stride + nkb * 128);
+        } else
         if (q0 + t < n_queries)
             for (uint32_t w = 0; w < nkb * 4; w++) pq += __popc(*reinterpret_cast<const uint32_t *>(qbits + (uint64_t)(q0 + t) * q_stride + w * 4));
         const float qo = zx ? dim_f - 2.0f * (float)pq : 2.0f * (float)pq - dim_f;
@@ -1342,9 +1408,12 @@ __global__ __launch_bounds__(512) void bin_gemm_rs_kernel(const uint8_t *__restr
             const uint32_t pv = pop[jj] + (uint32_t)__shfl_xor((int)pop[jj], 32);
             const uint64_t row = row0 + jj * 32 + r;
             const bool row_ok = row < n_rows;
-            const float v_off = zx ? -2.0f * (float)pv : 2.0f * (float)pv;
+            const float v_off = ((zx != 0) != CODES) ? -2.0f * (float)pv : 2.0f * (float)pv;  // CODES: the row term's sign is the other one
             int br = 0;
-            if (FILTER) br = row_ok ? pp_bound<LOW>(-v_off, fabsf(v_off), multiplier, 0) : (LOW ? -(int)kPpLim : (int)kPpLim);
+            // (a row past the end gets the bound of "never"; the accumulators of CODES can be negative and fall below
+            // -2^29 next to an "always" query bound, so there it is INT_MIN / INT_MAX, which no accumulator reaches)
+            constexpr int kNever = CODES ? 0x7FFFFFFF : (int)kPpLim;
+            if (FILTER) br = row_ok ? pp_bound<LOW>(-v_off, fabsf(v_off), multiplier, 0) : (LOW ? -kNever - (CODES ? 1 : 0) : kNever);
 #pragma unroll
             for (int i = 0; i < MI; i++) {
                 if (FILTER) {  // "some accumulator of the tile may pass": the largest is >= the row bound (LOW: the smallest <)
@@ -1943,8 +2012,29 @@ qamd_status launch_bin_gemm(const qamd_bin *h, const qamd_bin_query_batch *b, co
                            b->bits.as<uint8_t>(), (uint32_t)b->q_stride, (float)h->vp.dim, zx ? 1 : 0, (uint32_t)n_rows,   \
                            (uint32_t)b->n_queries, q0, out, out_pitch, filt);                                              \
     } while (0)
+    // a scalar batch: its code image at the kernel's own LDS pitch, and dim * L for dim (never its planes, never as bits)
+#define QAMD_BIN_GEMM_CODES(M_, LOW_, MI_)                                                                                  \
+    do {                                                                                                                   \
+        QAMD_LDS_OPT_IN((&bin_gemm_rs_kernel<M_, LOW_, MI_, true>), 160 * 1024);                                            \
+        hipLaunchKernelGGL((bin_gemm_rs_kernel<M_, LOW_, MI_, true>), dim3(grid), dim3(512), lds, s, rows, (uint32_t)h->ds, \
+                           b->codes.as<uint8_t>(), (uint32_t)b->code_pitch, metric_dim(h, b->qbits), zx ? 1 : 0,           \
+                           (uint32_t)n_rows, (uint32_t)b->n_queries, q0, out, out_pitch, filt);                            \
+    } while (0)
     constexpr int M = MODE == 0 ? 1 : MODE;
-    if (MODE == 0) {
+    if (b->qbits != 1) {
+        if (b->code_pitch != (h->ds / 16) * 128 + 16) return fail(QAMD_ERR_ARGUMENTS, "the batch's code image has another pitch");
+        // The filter runs on 32-query tiles only (bin_topk_batch_mfma): the 64-query filter forms need 20 bytes of scratch
+        // per lane at 256 registers - the binary ones have since they were written - and are not instantiated for codes.
+        if (MODE != 0 && mi != 1) return fail(QAMD_ERR_ARGUMENTS, "scalar batches filter on 32-query tiles");
+        if (MODE == 0) {
+            if (mi == 2) QAMD_BIN_GEMM_CODES(0, false, 2);
+            else QAMD_BIN_GEMM_CODES(0, false, 1);
+        } else if (low) {
+            QAMD_BIN_GEMM_CODES(M, true, 1);
+        } else {
+            QAMD_BIN_GEMM_CODES(M, false, 1);
+        }
+    } else if (MODE == 0) {
         if (mi == 2) QAMD_BIN_GEMM(0, false, 2);
         else QAMD_BIN_GEMM(0, false, 1);
     } else if (low) {
@@ -1954,9 +2044,37 @@ qamd_status launch_bin_gemm(const qamd_bin *h, const qamd_bin_query_batch *b, co
         if (mi == 2) QAMD_BIN_GEMM(M, false, 2);
         else QAMD_BIN_GEMM(M, false, 1);
     }
+#undef QAMD_BIN_GEMM_CODES
 #undef QAMD_BIN_GEMM
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
+}
+
+// Which filter the matrix-core top-k runs for this store and batch: the one place that decides it (bin_topk_batch_mfma
+// launches what this says, qamd_bin_batch_kernel names it).  Scalar batches take the int8 kernel only: centred codes are
+// not exact in E2M1.
+struct BinFilterPlan {
+    bool rs4 = false, qs4 = false;  // neither: bin_gemm_rs_kernel
+    uint32_t rs4_passes = 0, rs4_per_pass = 0;
+};
+BinFilterPlan bin_filter_plan(const qamd_bin *h, const qamd_bin_query_batch *b) {
+    BinFilterPlan p;
+    if (b->qbits != 1) return p;
+    const uint64_t Q = b->n_queries;
+    // rows of 512 / 1024 / 2048 bits, enough queries: the FP4 query-streaming form (QAMD_BIN4=0 / QAMD_BIN4_MIN: developer A/B)
+    static const char *e4 = dev_env("QAMD_BIN4"), *e4min = dev_env("QAMD_BIN4_MIN");
+    static const char *ers4 = dev_env("QAMD_BIN_RS4");  // developer A/B: 0 = without the row-streaming fp4 form
+    const bool fp4_shape = (h->ds == 64 || h->ds == 96 || h->ds == 128 || h->ds == 192) && !(e4 && e4[0] == '0');
+    // the whole batch's nibble image in LDS: the row-streaming fp4 form (one pass, no barriers); larger batches: query-streaming
+    // A batch of up to kRs4MaxPasses LDS images goes through that form in as many passes over the rows, the queries spread evenly
+    // (50M x 1024 bits: 289 queries = two passes of 160: 6.4 ms against the query-streaming form's 10.1; 576 = 2 x 288: 10.4 / 15.7)
+    static const char *ers4p = dev_env("QAMD_BIN_RS4_PASSES");  // developer A/B: the most passes the row-streaming form may take
+    const uint32_t rs4_cap = rs4_max_queries(h->ds), rs4_most = ers4p ? (uint32_t)atoi(ers4p) : kRs4MaxPasses;
+    p.rs4_passes = rs4_cap ? (uint32_t)((round_up(Q, 32) + rs4_cap - 1) / rs4_cap) : 0u;
+    p.rs4 = fp4_shape && !(ers4 && ers4[0] == '0') && p.rs4_passes >= 1 && p.rs4_passes <= rs4_most;
+    p.rs4_per_pass = p.rs4 ? (uint32_t)round_up((Q + p.rs4_passes - 1) / p.rs4_passes, 32) : 0u;  // queries per pass (whole tile pairs)
+    p.qs4 = p.rs4 || (fp4_shape && Q >= (e4min ? (uint64_t)atoll(e4min) : kQs4MinQueries));
+    return p;
 }
 
 // The batch on the matrix cores: per-query pivot from a cached row sample, one filtering pass per query tile
@@ -1965,7 +2083,7 @@ qamd_status launch_bin_gemm(const qamd_bin *h, const qamd_bin_query_batch *b, co
 qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b, uint32_t k, int largest, uint32_t *ids_dev,
                                 float *sc_dev, std::vector<uint32_t> &status, hipStream_t s) {
     const uint64_t Q = b->n_queries, n = h->count;
-    const int mi = bin_mfma_frags(h->ds, Q);
+    const int mi = b->qbits != 1 ? 1 : bin_mfma_frags(h->ds, Q);  // (scalar batches: 32-query tiles, launch_bin_gemm)
     const uint32_t TQ = 32u * (uint32_t)mi;
     const uint64_t q_pad = round_up(Q, 64);
     const double want = std::max<double>(Q <= 128 ? 1024.0 : 512.0, 3.0 * k);
@@ -1995,19 +2113,9 @@ qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b
             h->sample_count = rows_all;
         }
     }
-    // rows of 512 / 1024 / 2048 bits, enough queries: the FP4 query-streaming form (QAMD_BIN4=0 / QAMD_BIN4_MIN: developer A/B)
-    static const char *e4 = dev_env("QAMD_BIN4"), *e4min = dev_env("QAMD_BIN4_MIN");
-    static const char *ers4 = dev_env("QAMD_BIN_RS4");  // developer A/B: 0 = without the row-streaming fp4 form
-    const bool fp4_shape = (h->ds == 64 || h->ds == 96 || h->ds == 128 || h->ds == 192) && !(e4 && e4[0] == '0');
-    // the whole batch's nibble image in LDS: the row-streaming fp4 form (one pass, no barriers); larger batches: query-streaming
-    // A batch of up to kRs4MaxPasses LDS images goes through that form in as many passes over the rows, the queries spread evenly
-    // (50M x 1024 bits: 289 queries = two passes of 160: 6.4 ms against the query-streaming form's 10.1; 576 = 2 x 288: 10.4 / 15.7)
-    static const char *ers4p = dev_env("QAMD_BIN_RS4_PASSES");  // developer A/B: the most passes the row-streaming form may take
-    const uint32_t rs4_cap = rs4_max_queries(h->ds), rs4_most = ers4p ? (uint32_t)atoi(ers4p) : kRs4MaxPasses;
-    const uint32_t rs4_passes = rs4_cap ? (uint32_t)((round_up(Q, 32) + rs4_cap - 1) / rs4_cap) : 0u;
-    const bool rs4 = fp4_shape && !(ers4 && ers4[0] == '0') && rs4_passes >= 1 && rs4_passes <= rs4_most;
-    const uint32_t rs4_per_pass = rs4 ? (uint32_t)round_up((Q + rs4_passes - 1) / rs4_passes, 32) : 0u;  // queries per pass (whole tile pairs)
-    const bool qs4 = rs4 || (fp4_shape && Q >= (e4min ? (uint64_t)atoll(e4min) : kQs4MinQueries));
+    const BinFilterPlan plan = bin_filter_plan(h, b);
+    const bool rs4 = plan.rs4, qs4 = plan.qs4;
+    const uint32_t rs4_passes = plan.rs4_passes, rs4_per_pass = plan.rs4_per_pass;
     const uint32_t rs4_lists = pp_waves_per_launch() / 8 * (uint32_t)rs4_waves((int)(h->ds / 16));  // one list per wave of a launch
     const uint32_t n_lists = rs4 ? rs4_passes * rs4_lists
                                  : pp_waves_per_launch() * (qs4 ? (uint32_t)((Q + kQs4Slice - 1) / kQs4Slice) : 1u);
@@ -2195,9 +2303,11 @@ qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b
             sum += c;
             redo += status[q] != 0;
         }
-        fprintf(stderr, "[qamd bin topk_batch] Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, filter %s, %u queries redone\n",
+        char tail[32] = "";  // a scalar batch adds its bit count behind the fields the binary line has
+        if (b->qbits != 1) snprintf(tail, sizeof tail, ", query bits %u", b->qbits);
+        fprintf(stderr, "[qamd bin topk_batch] Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, filter %s, %u queries redone%s\n",
                 (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx,
-                rs4 ? "bin_gemm_rs4_kernel" : qs4 ? "bin_gemm_qs4_kernel" : "bin_gemm_rs_kernel", redo);
+                rs4 ? "bin_gemm_rs4_kernel" : qs4 ? "bin_gemm_qs4_kernel" : "bin_gemm_rs_kernel", redo, tail);
     }
     return QAMD_OK;
 }
@@ -2230,6 +2340,7 @@ qamd_status qamd_bin_encode_query_batch(const qamd_bin *h, const float *queries,
     b->ds = ds;
     b->q_stride = q_stride;
     b->n_queries = n_queries;
+    b->qbits = 1;
     if (n_queries && qdim) {
         DevBuf qtmp;
         const void *qd = nullptr;
@@ -2246,6 +2357,82 @@ qamd_status qamd_bin_encode_query_batch(const qamd_bin *h, const float *queries,
     return QAMD_OK;
 }
 
+// The reference has no counterpart: DESIGN 3.2d.  Query q of the batch is qamd_bin_encode_query_scalar of row q of
+// `queries` (the same kernel, one workgroup per query), kept as its planes and as the matrix cores' int8 image.
+qamd_status qamd_bin_encode_query_batch_scalar(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
+                                               qamd_mem queries_mem, uint32_t bits, void *stream,
+                                               qamd_bin_query_batch **batch_io) {
+    if (bits == 1) return qamd_bin_encode_query_batch(h, queries, n_queries, qdim, queries_mem, stream, batch_io);
+    if (bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
+    if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    const uint64_t max_dim = bits == 8 ? 65792 : 1118481;  // as qamd_bin_encode_query_scalar: dim * L stays exact in f32
+    if (qdim > max_dim)
+        return fail(QAMD_ERR_ARGUMENTS, "a %u-bit query has at most %llu dimensions, not %llu", bits,
+                    (unsigned long long)max_dim, (unsigned long long)qdim);
+    if (n_queries > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "too many queries");
+    QAMD_ON_DEVICE(h->device);
+    hipStream_t s = as_stream(stream);
+    const uint64_t nb = row_bytes_of(qdim, h->store), ds = device_stride_of(nb);
+    if (n_queries && nb != h->nb)
+        return fail(QAMD_ERR_ARGUMENTS, "queries have %llu bytes, rows have %llu", (unsigned long long)nb,
+                    (unsigned long long)h->nb);
+    qamd_bin_query_batch *b = *batch_io;
+    std::unique_ptr<qamd_bin_query_batch> fresh;
+    if (!b) {
+        fresh.reset(new qamd_bin_query_batch);
+        b = fresh.get();
+        b->device = h->device;
+    }
+    const uint64_t p_stride = round_up(bits * ds, 16);
+    const uint64_t code_pitch = round_up(ds, 16) * 8 + 16;  // ds / 16 K-blocks of 128 bytes + 16: bin_gemm_rs_kernel's PA
+    const size_t need_p = std::max<size_t>(p_stride * n_queries, 16), need_c = std::max<size_t>(code_pitch * n_queries, 16);
+    if (b->planes.bytes < need_p) QAMD_TRY(b->planes.alloc(need_p, true));
+    if (b->codes.bytes < need_c) QAMD_TRY(b->codes.alloc(need_c, true));
+    if (b->max_abs.bytes < std::max<size_t>(n_queries * 4, 16)) QAMD_TRY(b->max_abs.alloc(std::max<size_t>(n_queries * 4, 16), true));
+    b->nb = nb;
+    b->ds = ds;
+    b->n_queries = n_queries;
+    b->qbits = bits;
+    b->p_stride = p_stride;
+    b->code_pitch = code_pitch;
+    if (n_queries) {
+        DevBuf qtmp;
+        const void *qd = nullptr;
+        bool staged = false;
+        if (qdim) QAMD_TRY(local_view(queries, queries_mem, n_queries * qdim * 4, qtmp, s, &qd, &staged));
+        hipLaunchKernelGGL(bin_encode_scalar_kernel, dim3((unsigned)n_queries), dim3(kBlock), 0, s, static_cast<const float *>(qd),
+                           (uint32_t)qdim, (uint32_t)(ds / 4), bits, b->planes.as<uint32_t>(), (uint32_t)(p_stride / 4),
+                           b->max_abs.as<float>(), b->codes.as<int8_t>(), (uint32_t)code_pitch);
+        QAMD_HIP(hipGetLastError());
+        if (staged) QAMD_HIP(hipStreamSynchronize(s));
+    }
+    if (fresh) *batch_io = fresh.release();
+    return QAMD_OK;
+}
+
+qamd_status qamd_bin_query_batch_info(const qamd_bin_query_batch *b, uint32_t *bits, uint64_t *n_queries) {
+    if (!b) return fail(QAMD_ERR_ARGUMENTS, "null query batch");
+    if (bits) *bits = b->qbits;
+    if (n_queries) *n_queries = b->n_queries;
+    return QAMD_OK;
+}
+
+qamd_status qamd_bin_query_batch_read(const qamd_bin_query_batch *b, uint64_t q, uint8_t *bits, uint64_t capacity, uint64_t *len) {
+    if (!b) return fail(QAMD_ERR_ARGUMENTS, "null query batch");
+    if (q >= b->n_queries) return fail(QAMD_ERR_OUT_OF_RANGE, "query %llu of %llu", (unsigned long long)q, (unsigned long long)b->n_queries);
+    const uint64_t total = b->qbits * b->nb;  // as qamd_bin_query_read: the planes, plane 0 first, nb bytes each
+    if (len) *len = total;
+    if (bits) {
+        if (capacity < total) return fail(QAMD_ERR_ARGUMENTS, "bits buffer too small");
+        QAMD_ON_DEVICE(b->device);
+        const uint8_t *src = b->qbits == 1 ? b->bits.as<uint8_t>() + q * b->q_stride : b->planes.as<uint8_t>() + q * b->p_stride;
+        std::vector<uint8_t> wide(b->qbits * b->ds);  // planes are held at the device stride (4 bytes for the tiny rows)
+        if (!wide.empty()) QAMD_TRY(copy_out(wide.data(), QAMD_MEM_HOST, src, wide.size(), nullptr));
+        for (uint32_t pl = 0; pl < b->qbits; pl++) memcpy(bits + pl * b->nb, &wide[pl * b->ds], b->nb);
+    }
+    return QAMD_OK;
+}
+
 void qamd_bin_query_batch_free(qamd_bin_query_batch *b) { delete b; }
 
 static qamd_status bin_check_batch(const qamd_bin *h, const qamd_bin_query_batch *b) {
@@ -2253,7 +2440,69 @@ static qamd_status bin_check_batch(const qamd_bin *h, const qamd_bin_query_batch
     if (b->n_queries && b->nb != h->nb)
         return fail(QAMD_ERR_ARGUMENTS, "queries have %llu bytes, rows have %llu", (unsigned long long)b->nb,
                     (unsigned long long)h->nb);
+    if (b->qbits != 1 && b->qbits != 4 && b->qbits != 8) return fail(QAMD_ERR_ARGUMENTS, "query batch of %u bits", b->qbits);
+    if (b->n_queries && b->qbits != 1 && (b->ds != h->ds || !b->planes.ptr || !b->codes.ptr))
+        return fail(QAMD_ERR_ARGUMENTS, "scalar query batch without its planes or codes");
     return QAMD_OK;
+}
+
+// Query q of the batch as scan_bits / words_launch / bin_topk_small take it: its bit row, or its planes - a scalar batch
+// has no bit rows, and nothing reads b->bits for it.
+static const uint8_t *bin_batch_query(const qamd_bin_query_batch *b, uint64_t q) {
+    return b->qbits == 1 ? b->bits.as<uint8_t>() + q * b->q_stride : b->planes.as<uint8_t>() + q * b->p_stride;
+}
+
+// ---- routing: ONE predicate per entry point, called by the entry point and by qamd_bin_batch_kernel
+// The matrix gate both share: the query tile must fit LDS (bin_mfma_frags != 0: rows of at most 39 K-blocks = 4992 bits),
+// and at that length every operand and partial sum of the f32 epilogue is an integer below 2^23 - binary: 4 * 4992 + 2 *
+// 4992; scalar: 512 dim + 255 dim + 2 dim = 769 * 4992 < 2^22 - so the scores are those of the scan kernels bit for bit.
+static bool bin_mfma_capable(const qamd_bin *h) { return fused_capable(h) && bin_mfma_frags(h->ds) != 0 && h->vp.dim >= 64; }
+
+// The smallest scalar batch the matrix cores take: the values of the binary int8 route, 5 for score_batch and
+// kRs4MinQueries = 12 for topk_batch.  Measured (profiles/bin_scalar_batch.txt, 50M x 1024, 4 / 8 bits, batch against a loop
+// of single-query calls on the same handle; min-max within 5 % of every median): score_batch of 8 queries 2.15 / 2.24 ms
+// against 8.46 / 9.76 (3.9 x / 4.4 x), 32 queries 12.5 x / 14.1 x, 64 queries 16.5 x / 18.4 x; topk_batch(30) of 32 queries
+// 2.28 / 2.41 ms against 31.0 / 37.6 (13.6 x / 15.6 x), 64 queries 13.7 x / 16.2 x; 8 queries are under the topk gate and
+// tie with the loop (1.01 x).  A tile costs about 2.2 ms at 50M rows whatever its fill and one scalar scan 1.0 - 1.2 ms, so
+// the crossover is probably near 3 queries for both calls; batches of 2 .. 7 were not timed, so the gates stay at the
+// smallest sizes the table supports.  QAMD_BIN_SCALAR_MFMA_MIN: developer A/B, next to QAMD_BIN_MFMA_MIN.
+static uint64_t bin_scalar_mfma_min(uint64_t dflt) {
+    static const uint64_t v = dev_env_u64("QAMD_BIN_SCALAR_MFMA_MIN", 0);
+    return v ? v : dflt;
+}
+
+static bool bin_score_batch_on_mfma(const qamd_bin *h, const qamd_bin_query_batch *b) {
+    const uint64_t least = b->qbits == 1 ? 5 : bin_scalar_mfma_min(5);
+    return b->n_queries >= least && h->count >= 4096 && bin_mfma_capable(h);
+}
+
+static bool bin_topk_batch_on_mfma(const qamd_bin *h, const qamd_bin_query_batch *b, uint32_t k) {
+    const uint64_t Q = b->n_queries;
+    bool enough;
+    if (b->qbits != 1) {
+        enough = Q >= bin_scalar_mfma_min(kRs4MinQueries);
+    } else {
+        static const char *emin = dev_env("QAMD_BIN_MFMA_MIN");  // developer A/B: the smallest batch the matrix cores take
+        // rows of 512 / 768 / 1024 / 1536 bits: a pass of the row-streaming fp4 kernel costs 1.4-1.5 ms per 50M x 1024 whatever the batch,
+        // the vector-ALU scan 1.04 / 1.98 / 1.26 / 2.2 / 1.8 / 3.7 ms at 2 / 3 / 4 / 5 / 8 / 11 queries (profiles/r04_bin_batch.txt)
+        const bool fp4_rows = h->ds == 64 || h->ds == 96 || h->ds == 128 || h->ds == 192;
+        enough = emin ? Q >= (uint64_t)atoll(emin) : (fp4_rows ? (Q == 3 || Q >= 5) : Q >= kRs4MinQueries);
+    }
+    return enough && h->count >= 32768 && k <= 1024 && bin_mfma_capable(h);
+}
+
+const char *qamd_bin_batch_kernel(const qamd_bin *h, const qamd_bin_query_batch *b, uint32_t k) {
+    if (bin_check_batch(h, b) != QAMD_OK) return nullptr;
+    if (k == 0 ? bin_score_batch_on_mfma(h, b) : bin_topk_batch_on_mfma(h, b, k)) {
+        if (k == 0) return "bin_gemm_rs_kernel";
+        const BinFilterPlan plan = bin_filter_plan(h, b);
+        return plan.rs4 ? "bin_gemm_rs4_kernel" : plan.qs4 ? "bin_gemm_qs4_kernel" : "bin_gemm_rs_kernel";
+    }
+    // the per-query routes: small stores take the single-launch top-k; binary queries share a pass over the rows
+    SmallTopkPlan small;
+    if (k != 0 && h->count <= (2u << 20) && bin_small_plan(h, k, b->qbits, small)) return "bin_topk_small_kernel";
+    if (b->qbits == 1 && b->n_queries >= 2 && multi_rows(h)) return "bin_scan_multi_kernel";
+    return fused_capable(h) ? "bin_scan_kernel" : "bin_words_kernel";
 }
 
 // Many (query, id list) pairs in one launch (lists.hpp): out[p] = score_point(query l, ids[p]).
@@ -2266,6 +2515,9 @@ qamd_status qamd_bin_score_ids_batch(const qamd_bin *h, const qamd_bin_query_bat
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     return run_lists(list_offsets, n_lists, ids, n_ids, nullptr, lists_mem, out, out_mem, h->count, s, [&](const ListArgs &a) {
+        if (b->qbits != 1)  // list l against the planes of query l
+            return pairs_launch(h, nullptr, b->planes.as<uint8_t>(), b->p_stride, a.offsets, a.n_lists, nullptr, a.ids, a.n_pairs,
+                                a.out, s, b->qbits);
         return pairs_launch(h, nullptr, b->bits.as<uint8_t>(), b->q_stride, a.offsets, a.n_lists, nullptr, a.ids, a.n_pairs,
                             a.out, s);
     });
@@ -2284,20 +2536,21 @@ qamd_status qamd_bin_score_batch(const qamd_bin *h, const qamd_bin_query_batch *
         QAMD_TRY(tmp.alloc(b->n_queries * h->count * 4, s));
         out_dev = tmp.as<float>();
     }
-    const uint8_t *bits = b->bits.as<uint8_t>();
     uint64_t q = 0;
     // 5 queries and more: tiles of 32 / 64 queries on the matrix cores (same scores bit for bit: every f32
     // of the epilogue is an exact integer); the row bits are read once per tile instead of once per 8 queries
     // (measured at 50M x 1024: one 32-query tile 2.28 ms whatever the batch; the vector-ALU passes 1.81 ms for 4
     // queries, 2.6 for 8, and from there 2.6 ms per 8)
-    if (b->n_queries >= 5 && h->count >= 4096 && fused_capable(h) && bin_mfma_frags(h->ds) != 0 && h->vp.dim >= 64) {
+    if (bin_score_batch_on_mfma(h, b)) {
         const int mi = bin_mfma_frags(h->ds, b->n_queries);
         for (; q < b->n_queries; q += 32 * mi)  // (a partly filled last tile computes zero queries and stores nothing for them)
             QAMD_TRY(launch_bin_gemm<0>(h, b, h->rows.as<uint8_t>(), h->count, (uint32_t)q, mi, out_dev, h->count, BatchFilter{}, s));
     }
+    for (; b->qbits != 1 && q < b->n_queries; q++)  // scalar queries off the matrix cores: one scan of the planes each
+        QAMD_TRY(scan_bits(h, bin_batch_query(b, q), out_dev + q * h->count, s, nullptr, b->qbits));
     while (q < b->n_queries) {
         const uint64_t left = b->n_queries - q;
-        const uint8_t *qb = bits + q * b->q_stride;
+        const uint8_t *qb = bin_batch_query(b, q);
         float *o = out_dev + q * h->count;
         if (left >= 8 && multi_step<8>(h, qb, b->q_stride, o, s)) q += 8;
         else if (left >= 4 && multi_step<4>(h, qb, b->q_stride, o, s)) q += 4;
@@ -2318,23 +2571,24 @@ qamd_status qamd_bin_topk_batch(const qamd_bin *h, const qamd_bin_query_batch *b
     qamd_status args = QAMD_OK;
     if (!topk_wanted(k, b->n_queries, out_ids, out_scores, args)) return args;
     QAMD_ON_DEVICE(h->device);
-    const uint8_t *bits = b->bits.as<uint8_t>();
     const uint64_t qs = b->q_stride;
+    const uint32_t planes = b->qbits;  // 1: query q is its bit row; 4 / 8: its planes (bin_batch_query)
     BatchScan scan;
     scan.filter_capable = fused_capable(h);
-    scan.scan_scores = [&](uint32_t q, float *scores, hipStream_t st) { return scan_bits(h, bits + q * qs, scores, st); };
+    scan.scan_scores = [&](uint32_t q, float *scores, hipStream_t st) { return scan_bits(h, bin_batch_query(b, q), scores, st, nullptr, planes); };
     scan.scan_filter = [&](uint32_t q, const TopkFilter &f, hipStream_t st) {
-        return scan_bits(h, bits + q * qs, nullptr, st, &f);
+        return scan_bits(h, bin_batch_query(b, q), nullptr, st, &f, planes);
     };
     scan.score_ids = [&](uint32_t q, const uint32_t *ids, uint64_t n_ids, float *out, hipStream_t st) {
-        return words_launch(h, reinterpret_cast<const uint32_t *>(bits + q * qs), ids, n_ids, out, st);
+        return words_launch(h, reinterpret_cast<const uint32_t *>(bin_batch_query(b, q)), ids, n_ids, out, st, planes);
     };
     scan.topk_small = [&](uint32_t q, uint32_t *ids, float *sc, hipStream_t st, qamd_status &status) {
-        return bin_topk_small(h, bits + (uint64_t)q * qs, k, largest, ids, sc, QAMD_MEM_DEVICE, st, status);
+        return bin_topk_small(h, bin_batch_query(b, q), k, largest, ids, sc, QAMD_MEM_DEVICE, st, status, planes);
     };
-    // up to 8 queries share one pass over the rows (the filtering form of bin_scan_multi_kernel)
+    // up to 8 binary queries share one pass over the rows (the filtering form of bin_scan_multi_kernel)
+    if (planes == 1)
     scan.scan_filter_multi = [&](uint32_t q, uint32_t left, const TopkFilterSlices &sl, hipStream_t st, qamd_status &status) -> uint32_t {
-        const uint8_t *qb = bits + (uint64_t)q * qs;
+        const uint8_t *qb = bin_batch_query(b, q);
         uint32_t took = 0;
         if (left >= 8 && multi_step<8>(h, qb, qs, nullptr, st, &sl)) took = 8;
         else if (left >= 4 && multi_step<4>(h, qb, qs, nullptr, st, &sl)) took = 4;
@@ -2347,12 +2601,8 @@ qamd_status qamd_bin_topk_batch(const qamd_bin *h, const qamd_bin_query_batch *b
     // candidate list over- or underflowed there (heavy ties at small dims) go through the path below one by one
     const uint64_t Q = b->n_queries;
     hipStream_t s = as_stream(stream);
-    static const char *emin = dev_env("QAMD_BIN_MFMA_MIN");  // developer A/B: the smallest batch the matrix cores take
-    // rows of 512 / 768 / 1024 / 1536 bits: a pass of the row-streaming fp4 kernel costs 1.4-1.5 ms per 50M x 1024 whatever the batch,
-    // the vector-ALU scan 1.04 / 1.98 / 1.26 / 2.2 / 1.8 / 3.7 ms at 2 / 3 / 4 / 5 / 8 / 11 queries (profiles/r04_bin_batch.txt)
-    const bool fp4_rows = h->ds == 64 || h->ds == 96 || h->ds == 128 || h->ds == 192;
-    const bool enough = emin ? Q >= (uint64_t)atoll(emin) : (fp4_rows ? (Q == 3 || Q >= 5) : Q >= kRs4MinQueries);
-    if (enough && h->count >= 32768 && k <= 1024 && fused_capable(h) && bin_mfma_frags(h->ds) != 0 && h->vp.dim >= 64) {
+    // (bin_topk_batch_on_mfma: the gate, with the measurements behind the binary thresholds)
+    if (bin_topk_batch_on_mfma(h, b, k)) {
         StreamBuf ids_tmp, sc_tmp;
         uint32_t *ids_dev = out_ids;
         float *sc_dev = out_scores;

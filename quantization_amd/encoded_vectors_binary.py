@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._base import EncodedQueryBase, EncodedVectorsBase
+from ._base import EncodedQueryBase, EncodedQueryBatch, EncodedVectorsBase
 from .encoded_vectors import (EncodingError, VectorParameters, check, check_same_device, creating_on,
                               flatten_rows, get_device, in_buf, make_stop, out_buf, stream_ptr, validate)
 
@@ -53,9 +53,34 @@ class EncodedBinVector(EncodedQueryBase):
         return bits if planes == 1 else bits.reshape(planes, -1)
 
 
+class EncodedBinQueryBatch(EncodedQueryBatch):
+    """n x EncodedBinVector in HBM: binary queries, or 4- / 8-bit scalar queries."""
+
+    _prefix = "bin"
+
+    @property
+    def bits(self) -> int:
+        """Bits kept per query dimension: 1, 4 or 8."""
+        bits = C.c_uint32()
+        check(_lib.lib().qamd_bin_query_batch_info(self._h, C.byref(bits), None))
+        return int(bits.value)
+
+    def encoded_vector(self, q: int) -> np.ndarray:
+        """Query q as EncodedBinVector.encoded_vector gives it: its row of bits, shape (nb,), or its bit planes, shape
+        (bits, nb), plane 0 first.  A read-back for tests."""
+        n = C.c_uint64()
+        check(_lib.lib().qamd_bin_query_batch_read(self._h, int(q), None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        if n.value:
+            check(_lib.lib().qamd_bin_query_batch_read(self._h, int(q), C.c_void_p(out.ctypes.data), n.value, None))
+        planes = self.bits
+        return out if planes == 1 else out.reshape(planes, -1)
+
+
 class EncodedVectorsBin(EncodedVectorsBase):
     _prefix = "bin"
     _query_cls = EncodedBinVector
+    _batch_cls = EncodedBinQueryBatch
 
     def __init__(self, handle, vector_parameters: VectorParameters, store: BitsStoreType, device=None,
                  owned: bool = True):
@@ -99,6 +124,29 @@ class EncodedVectorsBin(EncodedVectorsBase):
         check(_lib.lib().qamd_bin_encode_query_scalar(self._h, buf.ptr, n, buf.mem, int(query_bits), stream_ptr(stream),
                                                       C.byref(h)))
         return reuse if reuse is not None else self._query_cls(h)
+
+    def encode_query_batch(self, queries, reuse=None, stream=None, *, query_bits: int = 1):
+        """encode_query for a [n_queries, dim] block of queries.  query_bits = 4 or 8: query q of the batch is
+        encode_query(queries[q], query_bits=...); score_batch, score_ids_batch, topk_batch and
+        topk_batch_rescored take either kind of batch."""
+        nq, qdim = int(queries.shape[0]), int(queries.shape[1])
+        check_same_device(self._device, queries)
+        buf = in_buf(queries, np.float32)
+        h = reuse._h if reuse is not None else C.c_void_p()
+        check(_lib.lib().qamd_bin_encode_query_batch_scalar(self._h, buf.ptr, nq, qdim, buf.mem, int(query_bits),
+                                                            stream_ptr(stream), C.byref(h)))
+        if reuse is not None:
+            reuse.n_queries = nq
+            return reuse
+        return self._batch_cls(h, nq, self._prefix)
+
+    def batch_kernel(self, batch, k: int = 0) -> str:
+        """The kernel score_batch (k = 0) or the filter of topk_batch (k > 0) takes for this store and batch
+        (qamd_bin_batch_kernel)."""
+        name = _lib.lib().qamd_bin_batch_kernel(self._h, batch._h, int(k))
+        if name is None:
+            raise EncodingError(_lib.ERR_ARGUMENTS, "the batch does not belong to this store")
+        return name.decode()
 
     @classmethod
     def encode_stream(cls, make_batches, vector_parameters: VectorParameters, stop_condition=None, *,
