@@ -14,25 +14,29 @@
 // K index is only a summation index, so lane (r, h) simply takes bytes [32s + 16h, +16) of
 // query/row r in k-step s: fragments are plain 16-byte pieces, no transposition anywhere.
 //
-// Six kernels share the arithmetic, the integer pre-filter and the epilogue; launch_gemm picks by what
-// is re-read and from where (DESIGN.md 3.3b has the table and the measurements):
+// Seven kernels share the arithmetic, the integer pre-filter and the epilogue.  Which one serves a pass of a batch, in
+// which template shape and with what bookkeeping, is decided once per pass by u8_gemm_route() (u8_gemm_route.hpp, a pure
+// function with the thresholds and the measurements behind them; DESIGN.md 3.3b and 3.7 have the tables); launch_gemm
+// and everything else here read that route.  They differ by what is re-read and from where:
 //   * u8_gemm_rs_kernel<MODE, LOW, MI, NT> -- row-streaming: up to 128 queries (and several 128-query
 //     tiles up to ~700): the query tile resident in LDS, every wave streams its own rows HBM ->
 //     registers (coalesced, nt) -> wave-private LDS transpose -> MFMA.  HBM-bound, no barriers.
-//   * u8_gemm_qs16_kernel<MODE, LOW, JT, IT> / u8_gemm_qs_kernel<MODE, LOW, MJ> -- query-streaming: many queries on
-//     rows of up to 1536 B: 128 (96) store rows resident in LDS, the batch streamed from L2 in MFMA fragment
-//     order straight into operand registers.  Rows leave HBM once; the reuse needs no co-scheduling of
-//     workgroups.  qs16 (round 3, the default) runs on v_mfma_i32_16x16x64_i8, which this part clocks a fifth
-//     higher under load than the 32x32x32 instruction of the round-2 form (QAMD_QS16=0 selects that one).
+//   * u8_gemm_qs16_kernel<MODE, LOW, JT, IT> -- query-streaming: many queries on rows of up to 1536 B: 128 (96) store
+//     rows resident in LDS, the batch streamed from L2 in MFMA fragment order straight into operand registers.  Rows
+//     leave HBM once; the reuse needs no co-scheduling of workgroups.  It runs on v_mfma_i32_16x16x64_i8, which this
+//     part clocks a fifth higher under load than the 32x32x32 instruction (DESIGN_HISTORY.md has the form it replaced).
 //   * u8_gemm_qr16_kernel<MODE, LOW, NSTEPS> -- 129 .. 256 queries on rows of 256 / 384 / 512 / 768 / 1024 B (round 3): a wave's 32
 //     queries in registers for all k-steps, the rows through a double-buffered 64-row LDS slab filled by LDS-DMA under
 //     the MFMAs; no vector-memory wait in the K loop, one barrier per block.
+//   * u8_gemm_rq16_kernel<MODE, LOW, NSTEPS> / u8_gemm_rk16_kernel<MODE, LOW, NSTEPS, NT> -- queries resident, rows
+//     streamed: the filter pass of topk_batch from 129 queries on rows of 256 / 384 / 512 / 768 B, in groups of query
+//     tiles side by side on the CUs of an XCD; rk16 is the K-outer form for 768-byte rows.
 //   * u8_gemm_pp_kernel<MODE, LOW, MI, MJ> -- ping-pong (round 1): both operands through an LDS-DMA
-//     ring, two wave groups half a phase apart; now for what the two above do not take.
+//     ring, two wave groups half a phase apart; now for what the ones above do not take.
 //   * u8_gemm_kernel<MODE, TQ, TR, WQ, WR, BK> -- the first version (128-byte K slabs through
 //     registers -> ds_write -> LDS at a 144-byte pitch, one barrier per slab, float-compare filter,
 //     per-query global atomics); now only for short rows no tile applies to, a zero / non-finite
-//     multiplier, and the developer switch QAMD_GEMM_CFG (r / q / p force one of the three above).
+//     multiplier, and the developer switch QAMD_GEMM_CFG (r / q / g / s / p force one of the families above).
 //
 // Top-k per query is fused as in topk.hip: a pivot per query from S sampled rows (scored by the
 // same kernel on a gathered sub-store; S grows with the store, see qamd_u8_topk_batch), a filter
@@ -43,6 +47,7 @@
 #include <cstdlib>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -51,6 +56,7 @@
 #include "rescore.hpp"
 #include "u8_internal.hpp"
 #include "batch_common.hpp"
+#include "u8_gemm_route.hpp"
 
 #pragma clang fp contract(off)
 
@@ -285,23 +291,6 @@ __global__ __launch_bounds__(64 * WQ * WR) void u8_gemm_kernel(const uint8_t *__
 // With DMA, barriers and fragment reads all removed the K loop still takes 1.2-1.4x the nominal
 // 32 cycles per MFMA in s_memtime ticks: the chip runs this kernel at about 1.8-2.0 GHz.
 constexpr int PP_KT = 64;  // K-tile bytes per row
-// Batch size from which the query-streaming kernel is preferred, by 128-byte K-blocks per row (measured, whole
-// topk_batch(30) calls at 7.68 GB of rows; below it several 128-query tiles of the row-streaming kernel, or the
-// ping-pong kernel where only 64-query tiles fit).  Round 3, with the 16x16x64 form of the kernel for rows of up to
-// 1024 bytes (profiles/r03_qs_experiments.txt), ms, row-streaming / query-streaming:
-//   rows of 256 B,  30M:   257 q  3.96 / 4.45    385 q  5.10 / 4.73    704 q  7.81 / 6.98    960 q  9.80 / 8.07
-//   rows of 384 B,  20M:   257 q  3.64 / 3.69    385 q  4.60 / 3.97    704 q  7.07 / 5.98    960 q  8.96 / 7.16
-//   rows of 512 B,  15M:   192 q  2.34 / 2.73    257 q  3.44 / 3.30    385 q  4.35 / 3.70    704 q  6.77 / 5.53
-//   rows of 768 B,  10M:   192 q  2.19 / 2.35    257 q  3.24 / 2.88    385 q  4.10 / 3.39    704 q  6.36 / 5.07
-//   rows of 1024 B, 7.5M:  192 q  2.22 / 2.21    257 q  3.41 / 2.74    385 q  4.76 / 3.25    704 q  8.61 / 4.89
-//   rows <= 1536 B: 12.5M x 1536: 256 q  pp 5.84 qs 6.34; 384 q  pp 10.3 qs 8.8; 640 q  pp 16.1 qs 13.8   (round 2)
-// i.e. from the third 128-query tile on (the fourth for rows of up to 384 bytes); the round-2 thresholds (960 / 704)
-// dated from before that round's block-change and epilogue work and this round's matrix instruction.  With chunks of 32
-// queries for batches of up to 256 (a chunk for every wave) the second tile goes the same way on rows past 768 bytes:
-//   rows of 768 B,  10M:   129 q  2.18 / 2.06    192 q  2.2-2.5 / 2.20    256 q  2.31 / 2.49     (kept on row-streaming)
-//   rows of 1024 B, 7.5M:  129 q  2.22 / 2.02    192 q  2.26 / 2.11       256 q  2.80 / 2.37
-//   rows of 1536 B, 12.5M: 129 q  5.44 / 4.88    192 q  5.53 / 5.23       256 q  6.87 / 5.90
-inline uint64_t qs_min_queries(uint32_t nkb) { return nkb <= 3 ? 385 : nkb <= 6 ? 257 : 129; }
 // Workgroup shapes (8 waves as 2 query groups x 4 row groups; a wave owns MI x MJ 32x32 tiles):
 //   <4,2>: 256 queries x 256 rows, ring of 4 x 32 KiB  -- more than 128 queries, MFMA-bound
 //   <2,4>: 128 queries x 512 rows, ring of 3 x 40 KiB  -- up to 128 queries: the store is streamed
@@ -957,38 +946,19 @@ __global__ __launch_bounds__(512) void u8_gemm_rs_kernel(const uint8_t *__restri
 }
 
 // ------------------------------------------------------------------------------------------
-// Query-streaming kernel (many queries, rows of up to 1152 code bytes).  The roles of the two
-// operands are swapped against the row-streaming kernel: a workgroup keeps a block of 128 STORE ROWS
+// Query-streaming kernel (many queries, rows of up to 1536 code bytes).  The roles of the two
+// operands are swapped against the row-streaming kernel: a workgroup keeps a block of 128 (96) STORE ROWS
 // resident in LDS and streams the whole query batch past it, then takes the next row block.
 //   * every row byte leaves HBM exactly once (nt), whatever the number of queries; what is re-read
 //     per row block is the QUERY batch (n_queries x row bytes, < 1 MiB per 1024 queries), and that
 //     stays in every XCD's L2 for the whole launch — no co-scheduling of workgroups needed for the
 //     reuse (the ping-pong and row-streaming kernels re-read ROWS through L2, which only works while
 //     the workgroups sharing them stay within microseconds of each other);
-//   * the batch carries a second copy of its codes in MFMA fragment order (swizzle_queries_kernel:
-//     per 32 queries and 128-byte K-block four 1 KiB pieces, lane (r, h) of piece x holding bytes
-//     [64h + 16x, +16) of query r), so a wave's streamed operand is eight fully coalesced 1 KiB
-//     loads per K-block straight into operand registers, one K-block ahead; no LDS, no transposition;
-//   * a wave takes 64 queries at a time (2 x 4 accumulator tiles of 32 x 32 against the 128 resident
-//     rows): per 32-byte k-step 4 ds_read_b128 + 8 MFMAs, half the LDS traffic per MFMA of the other
-//     two kernels; the 8 waves run independently between the two barriers of a row-block change.
+//   * the batch carries a second copy of its codes in MFMA fragment order (swizzle_queries16_kernel below), so a
+//     wave's streamed operand is fully coalesced 1 KiB loads straight into operand registers; no LDS, no transposition;
+//   * the 8 waves run independently between the two barriers of a row-block change.
 // Integer pre-filter, exact epilogue and wave-private candidate lists as in the ping-pong kernel; the
 // per-query integer bounds come precomputed from qs_bounds_kernel.
-__global__ __launch_bounds__(256) void swizzle_queries_kernel(const uint8_t *__restrict__ codes, uint32_t pitch,
-                                                             uint32_t q_pad, uint32_t nkb, uint4 *__restrict__ out) {
-    // out[((f * nkb + kb) * 4 + x) * 64 + lane] = bytes [128 kb + 64 h + 16 x, +16) of query 32 f + r
-    const uint64_t total = (uint64_t)(q_pad / 32) * nkb * 256;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256) {
-        const uint32_t lane = (uint32_t)(i & 63u), x = (uint32_t)(i >> 6) & 3u;
-        const uint64_t fk = i >> 8;
-        const uint32_t kb = (uint32_t)(fk % nkb), f = (uint32_t)(fk / nkb);
-        const uint32_t r = lane & 31u, h = lane >> 5, k = kb * 128u + 64u * h + 16u * x;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (k < pitch) v = *reinterpret_cast<const uint4 *>(codes + (uint64_t)(32u * f + r) * pitch + k);
-        out[i] = v;
-    }
-}
-
 template <bool LOW>
 __global__ __launch_bounds__(256) void qs_bounds_kernel(const float *__restrict__ pivots, const float *__restrict__ q_offsets,
                                                        float multiplier, int largest, uint32_t q_pad, int *__restrict__ bq) {
@@ -1000,328 +970,9 @@ __global__ __launch_bounds__(256) void qs_bounds_kernel(const float *__restrict_
     bq[q] = b;
 }
 
-template <int MODE, bool LOW, int MJ>  // MJ: 32-row fragments resident (4: rows of up to 1152 B; 3: up to 1536 B)
-__global__ __launch_bounds__(512) void u8_gemm_qs_kernel(const uint8_t *__restrict__ codes,
-                                                        const float *__restrict__ v_offsets,
-                                                        const uint4 *__restrict__ qfrag, const float *__restrict__ q_offsets,
-                                                        const int *__restrict__ bq_all, float multiplier, uint32_t n_rows,
-                                                        uint32_t n_queries, uint32_t q_pad, uint32_t ad,
-                                                        float *__restrict__ out, uint64_t out_pitch, BatchFilter filt) {
-    extern __shared__ __attribute__((aligned(1024))) uint8_t lds_raw[];
-    constexpr int MI = 2, KB = 128, QS_ROWS = 32 * MJ;  // resident rows per workgroup
-    // MODE 0: scores out; 1 / 2: filter for the largest / smallest; 3: the best score of every (query, row block)
-    // out[q * out_pitch + block] (direction filt.largest) - the pivot sample of a large batch without its Q x S score matrix
-    constexpr bool FILTER = MODE == 1 || MODE == 2;
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const uint32_t nkb = __builtin_amdgcn_readfirstlane((ad + KB - 1) / KB);
-    const uint32_t PA = nkb * KB + 16;  // LDS pitch of a row
-    const uint32_t n_blocks = (n_rows + QS_ROWS - 1) / QS_ROWS;
-    const uint32_t n_chunks = q_pad / 64;  // 64-query chunks (q_pad is a multiple of 256: whole chunks, zero queries at the end)
-    const uint32_t live_chunks = (n_queries + 63) / 64;
-    float *voff_s = reinterpret_cast<float *>(lds_raw + (size_t)QS_ROWS * PA);  // [128]
-    int *br_s = reinterpret_cast<int *>(voff_s + QS_ROWS);                       // [128]
-    uint32_t *wcount_s = reinterpret_cast<uint32_t *>(br_s + QS_ROWS) + wave;
-    int *bq_s = reinterpret_cast<int *>(br_s + QS_ROWS) + 16;                    // [64 * live_chunks] integer query bounds
-    constexpr bool LARGEST = MODE == 1;
-    if (FILTER && lane == 0) *wcount_s = 0;
-    if (FILTER)
-        for (uint32_t i = t; i < 64 * live_chunks; i += 512) bq_s[i] = bq_all[i];
-    const float never = (MODE == 3 ? filt.largest != 0 : LARGEST) ? -__builtin_huge_valf() : __builtin_huge_valf();
-    (void)n_chunks;
-
-    // streamed operand: chunk c, K-block kb -> fragments 2c and 2c + 1, 4 KiB each, contiguous per fragment
-    const uint4 *q_lane = qfrag + lane;
-    v4i A0[MI][4], A1[MI][4];
-    auto load_q = [&](v4i(&a)[MI][4], uint32_t c, uint32_t kb) {
-#pragma unroll
-        for (int i = 0; i < MI; i++) {
-            const uint4 *p = q_lane + ((uint64_t)(2 * c + i) * nkb + kb) * 256;
-#pragma unroll
-            for (int x = 0; x < 4; x++) {
-                const uint4 v = p[64 * x];
-                a[i][x] = v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
-            }
-        }
-    };
-    const uint8_t *b_base = lds_raw + r * PA + 64 * h;
-
-    // Row-block fill: the block is 128 * ad contiguous bytes of the store; thread t takes the 16-byte
-    // pieces t, t + 512, ... (at most 18), requested BEFORE the barrier that frees the LDS rows (a
-    // wave that finishes its queries early has its share of the next block in flight while the others
-    // compute) and written after it.  Bytes [ad, nkb * 128) of an LDS row are never written: the
-    // query image is zero there, so whatever they hold adds nothing (integer arithmetic).
-    const uint32_t per = ad / 16;                                  // pieces per row
-    const uint32_t n_pieces = __builtin_amdgcn_readfirstlane((QS_ROWS * per + 511) / 512);  // per thread (the last one may fall past the block)
-    const uint32_t p_row0 = (uint32_t)t / per, p_c0 = (uint32_t)t % per, d_row = 512 / per, d_c = 512 % per;
-    constexpr int MAXP = 18;
-    v4i st[MAXP];
-    float vo_pf = 0.0f;  // v_offset of row t of the requested block (threads 0..127)
-    // every element is (re)defined on every call (pieces past the count re-read the last one): a
-    // conditional definition would keep the old value alive through the whole query loop (spills).
-    // A thread's last piece may lie just past the block: in the store's row padding, never written.
-    // (Requesting the pieces BEFORE the wave's last epilogue, to take the last wave's HBM round trip
-    // out of the block change, was tried: accumulators + pieces + epilogue temporaries do not fit in
-    // 256 registers, and the spills cost more than the round trip.)
-    auto fill_request = [&](uint32_t blk) {
-        const uint8_t *p = codes + (uint64_t)blk * QS_ROWS * ad + (size_t)t * 16;
-#pragma unroll
-        for (int i = 0; i < 12; i++) {
-            const uint32_t ii = (uint32_t)i < n_pieces ? (uint32_t)i : n_pieces - 1;  // wave-uniform
-            st[i] = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(p + (size_t)ii * 8192));
-        }
-        if (n_pieces > 12) {  // rows longer than 768 B
-#pragma unroll
-            for (int i = 12; i < MAXP; i++) {
-                const uint32_t ii = (uint32_t)i < n_pieces ? (uint32_t)i : n_pieces - 1;
-                st[i] = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(p + (size_t)ii * 8192));
-            }
-        } else {  // "defined" without an instruction: keeps the old values from staying alive (see above)
-#pragma unroll
-            for (int i = 12; i < MAXP; i++) asm volatile("" : "=v"(st[i]));
-        }
-        vo_pf = v_offsets[(uint64_t)blk * QS_ROWS + (t < QS_ROWS ? t : 0)];  // padded like codes[]
-    };
-    auto fill_write = [&]() {
-        uint32_t row = p_row0, c = p_c0;
-        asm volatile("" : "+v"(row), "+v"(c));  // the 18 LDS addresses are recomputed per block, not kept (and spilled)
-#pragma unroll
-        for (int i = 0; i < MAXP; i++) {
-            if ((uint32_t)i < n_pieces && row < (uint32_t)QS_ROWS) *reinterpret_cast<v4i *>(lds_raw + row * PA + c * 16) = st[i];
-            row += d_row;
-            c += d_c;
-            if (c >= per) {
-                c -= per;
-                row++;
-            }
-        }
-    };
-    const uint32_t my_first = wave;  // this wave's first chunk of every row block
-    // developer timeline (libquantization_amd_dev.so only): cycles per phase, summed over the row blocks
-    unsigned long long *stamps = QAMD_GEMM_STAMPS();
-    const bool timed = stamps != nullptr;
-    unsigned long long tm_prev = timed ? __builtin_amdgcn_s_memtime() : 0ull, tm_acc[6] = {0, 0, 0, 0, 0, 0};
-    const unsigned long long tm_first = tm_prev, rt_first = timed ? __builtin_amdgcn_s_memrealtime() : 0ull;  // 100 MHz
-    auto lap = [&](int slot) {
-        if (timed) {
-            const unsigned long long now = __builtin_amdgcn_s_memtime();
-            tm_acc[slot] += now - tm_prev;
-            tm_prev = now;
-        }
-    };
-    fill_request(blockIdx.x < n_blocks ? blockIdx.x : 0u);
-    if (my_first < live_chunks) load_q(A0, my_first, 0);
-
-    for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-        const uint64_t row0 = (uint64_t)blk * QS_ROWS;
-        const uint32_t next_blk = blk + gridDim.x < n_blocks ? blk + gridDim.x : blk;  // past the end: re-request (always defined)
-        lap(5);  // (request issue, loop overhead)
-        __syncthreads();  // every wave is done with the previous block's rows
-        lap(0);  // waiting for the other waves
-        fill_write();
-        if (t < QS_ROWS) {
-            const bool ok = row0 + t < n_rows;
-            const float vo = vo_pf;  // requested with the rows
-            voff_s[t] = ok ? vo : never;
-            if (FILTER) br_s[t] = ok ? pp_bound<LOW>(-vo, fabsf(vo), multiplier, 0) : (LOW ? -(int)kPpLim : (int)kPpLim);
-        }
-        __syncthreads();
-        lap(1);  // own pieces landing + LDS writes + second barrier
-
-        for (uint32_t c = wave; c < live_chunks; c += 8) {
-            // the chunk whose first K-block is requested under this chunk's last MFMAs (of this row
-            // block, or the first one of the next: the queries do not depend on the rows)
-            const uint32_t c_next = c + 8 < live_chunks ? c + 8 : my_first;
-            v16i acc[MI][MJ];
-            int br[MJ];
-#pragma unroll
-            for (int jj = 0; jj < MJ; jj++) br[jj] = FILTER ? br_s[jj * 32 + r] : 0;
-            if (!FILTER) {
-#pragma unroll
-                for (int i = 0; i < MI; i++)
-#pragma unroll
-                    for (int jj = 0; jj < MJ; jj++)
-#pragma unroll
-                        for (int e = 0; e < 16; e++) acc[i][jj][e] = 0;
-            } else {
-#pragma unroll
-                for (int i = 0; i < MI; i++)
-#pragma unroll
-                    for (int gq = 0; gq < 4; gq++) {
-                        const v4i bq4 = *reinterpret_cast<const v4i *>(bq_s + 64 * c + i * 32 + 8 * gq + 4 * h);
-#pragma unroll
-                        for (int e = 0; e < 4; e++)
-#pragma unroll
-                            for (int jj = 0; jj < MJ; jj++) acc[i][jj][4 * gq + e] = -(bq4[e] + br[jj]);
-                    }
-            }
-            auto compute = [&](const v4i(&a)[MI][4], uint32_t kb) {
-                const uint8_t *pb = b_base + kb * KB;
-#pragma unroll
-                for (int x = 0; x < 4; x++) {
-                    v4i bf[MJ];
-#pragma unroll
-                    for (int jj = 0; jj < MJ; jj++) bf[jj] = *reinterpret_cast<const v4i *>(pb + (uint32_t)jj * 32u * PA + 16 * x);
-#pragma unroll
-                    for (int i = 0; i < MI; i++)
-#pragma unroll
-                        for (int jj = 0; jj < MJ; jj++)
-                            acc[i][jj] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i][x], bf[jj], acc[i][jj], 0, 0, 0);
-                }
-            };
-            // Two K-blocks per turn, each requested a K-block ahead (sched_barrier: the eight loads are
-            // issued HERE; left alone the scheduler sinks each load to just before its first use and
-            // the wave stalls on every L2 round trip).  The request after the chunk's last K-block is
-            // the next chunk's first one.
-            lap(2);  // accumulator set-up
-            // The two waves of a SIMD take turns at instruction priority, chunk by chunk: left alone the
-            // older wave (0..3) wins the MFMA arbitration every time, finishes its chunks a quarter
-            // earlier and idles at the barrier while the other one runs alone.
-            if (((c >> 3) + ((uint32_t)wave >> 2)) & 1u) __builtin_amdgcn_s_setprio(2);
-            else __builtin_amdgcn_s_setprio(0);
-            uint32_t kb = 0;
-            for (; kb + 1 < nkb; kb += 2) {
-                load_q(A1, c, kb + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                compute(A0, kb);
-                __builtin_amdgcn_sched_barrier(0);
-                if (kb + 2 < nkb) load_q(A0, c, kb + 2);
-                else load_q(A0, c_next, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                compute(A1, kb + 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            const bool odd = kb < nkb;
-            if (odd) {  // odd K-block count: the next chunk's first block arrives in A1 and is moved after the epilogue
-                load_q(A1, c_next, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                compute(A0, kb);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            lap(3);  // K loop
-            // ---- epilogue: 64 queries x 128 rows of this wave
-            uint32_t c_e = c, wave_e = (uint32_t)wave, lane_e = (uint32_t)lane;
-            asm volatile("" : "+s"(c_e), "+s"(wave_e), "+v"(lane_e));
-            if (MODE == 3) {  // best score per query over the block's rows (rows on the lanes of each half wave)
-                const bool lg = filt.largest != 0;
-                const uint32_t r3 = lane_e & 31u, h3 = lane_e >> 5;
-                float vo3[MJ];
-#pragma unroll
-                for (int jj = 0; jj < MJ; jj++) vo3[jj] = voff_s[jj * 32 + r3];  // `never` for rows past the end
-#pragma unroll
-                for (int i = 0; i < MI; i++)
-#pragma unroll
-                    for (int gq = 0; gq < 4; gq++) {
-                        const uint32_t q = 64 * c_e + i * 32 + 8 * gq + 4 * h3;
-                        const float4 qo4 = *reinterpret_cast<const float4 *>(q_offsets + q);
-                        const float qo[4] = {qo4.x, qo4.y, qo4.z, qo4.w};
-#pragma unroll
-                        for (int e = 0; e < 4; e++) {
-                            float best = never;
-#pragma unroll
-                            for (int jj = 0; jj < MJ; jj++) {
-                                const float sc = (multiplier * (float)acc[i][jj][4 * gq + e] + qo[e]) + vo3[jj];
-                                best = lg ? fmaxf(best, sc) : fminf(best, sc);
-                            }
-#pragma unroll
-                            for (int d = 16; d >= 1; d >>= 1) {
-                                const float o = __shfl_xor(best, d);
-                                best = lg ? fmaxf(best, o) : fminf(best, o);
-                            }
-                            if (r3 == 0 && q + e < n_queries) out[(uint64_t)(q + e) * out_pitch + blk] = best;
-                        }
-                    }
-            } else {
-            uint4 *wave_list = FILTER ? filt.wave_cand + (uint64_t)(filt.wave_base + blockIdx.x * 8 + wave_e) * filt.wave_cap : nullptr;
-            const uint32_t r_e = lane_e & 31u, h_e = lane_e >> 5;
-#pragma unroll
-            for (int jj = 0; jj < MJ; jj++) {
-                const uint64_t row = row0 + jj * 32 + r_e;
-                const bool row_ok = row < n_rows;
-                const float v_off = voff_s[jj * 32 + r_e];
-                const int brj = br[jj];
-#pragma unroll
-                for (int i = 0; i < MI; i++) {
-                    if (!FILTER) __builtin_amdgcn_sched_barrier(0);
-                    if (FILTER) {
-                        // "some accumulator of the tile may pass" = the smallest is negative (LOW) / the
-                        // largest is not: v_min3 / v_max3 fold two values per instruction
-                        int ext = acc[i][jj][0];
-#pragma unroll
-                        for (int e = 1; e < 15; e += 2)
-                            ext = LOW ? min(min(ext, acc[i][jj][e]), acc[i][jj][e + 1])
-                                      : max(max(ext, acc[i][jj][e]), acc[i][jj][e + 1]);
-                        ext = LOW ? min(ext, acc[i][jj][15]) : max(ext, acc[i][jj][15]);
-                        if (!__builtin_amdgcn_readfirstlane(__ballot(LOW ? ext < 0 : ext >= 0) != 0)) continue;
-                    }
-#pragma unroll
-                    for (int gq = 0; gq < 4; gq++) {
-                        const uint32_t q = 64 * c_e + i * 32 + 8 * gq + 4 * h_e;  // first of four consecutive queries
-                        if (!FILTER) {
-                            const float4 qo4 = *reinterpret_cast<const float4 *>(q_offsets + q);
-                            const float qo[4] = {qo4.x, qo4.y, qo4.z, qo4.w};
-#pragma unroll
-                            for (int e = 0; e < 4; e++) {
-                                const float sc = (multiplier * (float)acc[i][jj][4 * gq + e] + qo[e]) + v_off;
-                                if (row_ok && q + e < n_queries) out[(uint64_t)(q + e) * out_pitch + row] = sc;
-                            }
-                        } else {
-                            const int a0 = acc[i][jj][4 * gq], a1 = acc[i][jj][4 * gq + 1], a2 = acc[i][jj][4 * gq + 2],
-                                      a3 = acc[i][jj][4 * gq + 3];
-                            const bool may_pass = LOW ? ((a0 | a1 | a2 | a3) < 0) : ((a0 & a1 & a2 & a3) >= 0);
-                            if (may_pass) {
-                                const v4i bq4 = *reinterpret_cast<const v4i *>(bq_all + q);
-                                const float4 qo4 = *reinterpret_cast<const float4 *>(q_offsets + q);
-                                const float4 pv4 = *reinterpret_cast<const float4 *>(filt.pivot_scores + q);
-                                const float qo[4] = {qo4.x, qo4.y, qo4.z, qo4.w};
-                                const float pv[4] = {pv4.x, pv4.y, pv4.z, pv4.w};
-                                const int av[4] = {a0, a1, a2, a3};
-#pragma unroll
-                                for (int e = 0; e < 4; e++) {
-                                    const int s_int = av[e] + bq4[e] + brj;  // the plain integer dot product
-                                    const float sc = (multiplier * (float)s_int + qo[e]) + v_off;
-                                    const float d = LARGEST ? sc - pv[e] : pv[e] - sc;
-                                    if (d >= 0.0f) {
-                                        const uint32_t pos = atomicAdd(wcount_s, 1u);
-                                        if (pos < filt.wave_cap)
-                                            wave_list[pos] = make_uint4(topk_ordered_bits(sc, LARGEST), (uint32_t)row,
-                                                                        filt.query_base + q + e, 0u);
-                                    }
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            }  // MODE != 3
-            if (odd) {
-#pragma unroll
-                for (int i = 0; i < MI; i++)
-#pragma unroll
-                    for (int x = 0; x < 4; x++) A0[i][x] = A1[i][x];
-            }
-            lap(4);  // epilogue
-        }
-        // this wave's share of the next row block: requested as soon as its own chunks are done (the
-        // accumulators are dead, their registers hold the pieces until the barrier)
-        fill_request(next_blk);
-    }
-    if (timed && lane == 0 && blockIdx.x < kStampBlocks) {
-        unsigned long long *o = stamps + ((uint64_t)blockIdx.x * 8 + wave) * 16;
-        for (int i = 0; i < 6; i++) o[i] = tm_acc[i];
-        o[6] = __builtin_amdgcn_s_memtime() - tm_first;      // shader clocks spent in the kernel ...
-        o[7] = __builtin_amdgcn_s_memrealtime() - rt_first;  // ... and 10 ns ticks: the clock the kernel ran at
-        o[15] = 1;
-    }
-    if (FILTER && lane == 0) filt.wave_counts[filt.wave_base + blockIdx.x * 8 + wave] = *wcount_s;
-}
-
-
 // ------------------------------------------------------------------------------------------
-// The query-streaming kernel on v_mfma_i32_16x16x64_i8 (round 3).  Same structure, arithmetic and results as
-// u8_gemm_qs_kernel; what changes is the matrix instruction.  Under int8 MFMA load this part is clock-limited: a bare
+// The query-streaming kernel on v_mfma_i32_16x16x64_i8 (round 3).  Same structure, arithmetic and results as the
+// 32x32x32 form of round 2 that it replaced; what changes is the matrix instruction.  Under int8 MFMA load this part is clock-limited: a bare
 // loop of 32x32x32 instructions runs at 1.84-1.89 GHz (3.6-3.8 POP/s), the same loop on 16x16x64 at 2.2-2.3 GHz
 // (4.35-4.40 POP/s) - a fifth more work per second out of the same pipes (tools/mfma_peak.py).  A wave's tile is
 // unchanged, 64 queries x 128 rows = 4 x 8 accumulator tiles of 16 x 16 (128 registers), and so is the operand
@@ -1381,7 +1032,7 @@ __global__ __launch_bounds__(512) void u8_gemm_qs16_kernel(const uint8_t *__rest
 
     // streamed operand: chunk c, k-step j (64 bytes of K: K-block j / 2, half j % 2) -> one 1 KiB piece per 16-query tile
     // 4c .. 4c + 3.  Three buffers of one k-step each rotate: the step in use and the next two on their way (two k-steps
-    // = one K-block of lead, as in u8_gemm_qs_kernel, in 48 registers instead of 64: the 128 accumulator registers and
+    // = one K-block of lead, as in the 32x32x32 form, in 48 registers instead of 64: the 128 accumulator registers and
     // two waves per SIMD leave no more).
     const uint32_t nsteps = 2 * nkb;
     v4i Q0[IT], Q1[IT], Q2[IT];
@@ -1400,7 +1051,7 @@ __global__ __launch_bounds__(512) void u8_gemm_qs16_kernel(const uint8_t *__rest
     const uint32_t b_row = i16 * PA, b_gi = (g4 ^ i16) * 16u;
 
     // Row-block fill: thread t takes the 16-byte pieces t, t + 512, ... of the block's 128 * ad contiguous bytes
-    // (requested before the barrier that frees the LDS rows, written after it, as in u8_gemm_qs_kernel); piece c of
+    // (requested before the barrier that frees the LDS rows, written after it, as in the 32x32x32 form); piece c of
     // row r goes to place c ^ (r & 15).  Places a row does not fill (past its last chunk) are only ever multiplied
     // with the zero bytes of the query image.
     const uint32_t n_pieces = __builtin_amdgcn_readfirstlane((QS_ROWS * per + 511) / 512);
@@ -1522,7 +1173,7 @@ __global__ __launch_bounds__(512) void u8_gemm_qs16_kernel(const uint8_t *__rest
                 else load_step(a, c_next, j - nsteps);
             };
             lap(2);
-            // (the two waves of a SIMD take turns at priority chunk by chunk, as in u8_gemm_qs_kernel; without it the older
+            // (the two waves of a SIMD take turns at priority chunk by chunk, as in the 32x32x32 form; without it the older
             // wave wins every arbitration and idles a quarter of the block at the barrier; flipping every turn of three
             // k-steps instead balances no better: both measured)
             if (((c >> 3) + ((uint32_t)wave >> 2)) & 1u) __builtin_amdgcn_s_setprio(2);
@@ -1827,7 +1478,7 @@ __global__ __launch_bounds__(512) void u8_gemm_qr16_kernel(const uint8_t *__rest
                         for (int e = 0; e < 4; e++) acc[it][jt][e] = FILTER ? -(bq4[it][e] + br[jt]) : 0;
             }
             lap(2);
-            // the two waves of a SIMD (w, w + 4) take turns at priority block by block (see u8_gemm_qs_kernel)
+            // the two waves of a SIMD (w, w + 4) take turns at priority block by block (see u8_gemm_qs16_kernel)
             if ((((blk - blockIdx.x) / gridDim.x) + ((uint32_t)wave >> 2)) & 1u) __builtin_amdgcn_s_setprio(2);
             else __builtin_amdgcn_s_setprio(0);
             const uint32_t slab_addr = par * SLAB;
@@ -1967,11 +1618,6 @@ __global__ __launch_bounds__(512) void u8_gemm_qr16_kernel(const uint8_t *__rest
 // stream slot / G, and the G workgroups of a stream walk the same rows in the same order, so a row leaves HBM once and
 // the other groups find it in that XCD's L2 (or the memory-side cache).  Arithmetic, bounds and candidate lists are
 // u8_gemm_qr16_kernel's.
-struct RqGeometry {
-    uint32_t groups, pairs_lo /* tile pairs of every group */, pairs_extra /* the first so many groups take one more */,
-        streams_per_xcd, n_tiles /* of the batch, even */;
-};
-constexpr uint32_t rq_tile_cap(uint32_t nsteps) { return ((160u * 1024u - 2048u) / (nsteps * 1024u + 64u)) & ~1u; }
 template <int MODE, bool LOW, int NSTEPS>
 __global__ __launch_bounds__(512) void u8_gemm_rq16_kernel(const uint8_t *__restrict__ codes, const float *__restrict__ v_offsets,
                                                           const uint4 *__restrict__ qfrag, const float *__restrict__ q_offsets,
@@ -2301,9 +1947,8 @@ struct qamd_u8_query_batch {
     uint64_t pitch = 0;  // round_up(actual_dim, 64): whole 64-byte K-tiles, zero padded
     DevBuf codes;        // [q_pad][pitch], zero rows past n_queries
     DevBuf offsets;      // [q_pad] f32
-    DevBuf frag;         // the codes again in MFMA fragment order (swizzle_queries_kernel), for u8_gemm_qs_kernel
-    uint32_t frag_nkb = 0;  // 128-byte K-blocks per query in `frag`
-    bool frag16 = false;    // `frag` is in the order of u8_gemm_qs16_kernel (16-query tiles), else of u8_gemm_qs_kernel
+    DevBuf frag;         // the codes again in MFMA fragment order (swizzle_queries16_kernel), for the kernels that take it so
+    uint32_t frag_nkb = 0;  // 128-byte K-blocks per query in `frag` (0: the batch has no fragment copy)
 };
 
 namespace {
@@ -2316,523 +1961,292 @@ qamd_status check_batch(const qamd_u8 *h, const qamd_u8_query_batch *b) {
     return QAMD_OK;
 }
 
-// Launch the GEMM over rows [0, n_rows) of (codes, offsets) for every query of the batch.
+// The developer switches of this file, read once per process (tools/lib build; all-default in the product library).
+struct DevSwitches {
+    U8GemmSwitches route;
+    bool debug_topk = false;  // QAMD_DEBUG_TOPK: one line per topk_batch call on stderr
+};
+const DevSwitches &dev_switches() {
+    static const DevSwitches switches = [] {
+        auto text = [](const char *name) { return dev_env(name); };
+        auto number = [&](const char *name) {
+            const char *e = text(name);
+            return U8GemmSwitches::Number{e != nullptr, e ? (uint64_t)atoll(e) : 0};
+        };
+        auto is_off = [&](const char *name) {
+            const char *e = text(name);
+            return e && e[0] == '0';
+        };
+        DevSwitches d;
+        if (const char *cfg = text("QAMD_GEMM_CFG")) {
+            d.route.forced = true;
+            d.route.family = cfg[0];
+        }
+        d.route.rq = !is_off("QAMD_RQ");
+        d.route.rq_k = !is_off("QAMD_RQ_K");
+        d.route.rq_groups = number("QAMD_RQ_GROUPS");
+        d.route.qr_min = number("QAMD_QR_MIN");
+        d.route.qr_max = number("QAMD_QR_MAX");
+        d.route.rq_min = number("QAMD_RQ_MIN");
+        d.route.rq_max = number("QAMD_RQ_MAX");
+        d.debug_topk = text("QAMD_DEBUG_TOPK") != nullptr;
+        return d;
+    }();
+    return switches;
+}
+
+// The route (u8_gemm_route.hpp) of one pass of this batch over n_rows rows of the store, or of a sample of it.
+U8GemmRoute gemm_route(const qamd_u8 *h, const qamd_u8_query_batch *b, U8GemmPass pass, uint64_t n_rows) {
+    U8GemmInputs in;
+    in.actual_dim = h->meta.actual_dim;
+    in.rows = h->count;
+    in.multiplier = h->meta.multiplier;
+    in.n_queries = b->n_queries;
+    in.q_pad = b->q_pad;
+    in.frag_nkb = b->frag.ptr ? b->frag_nkb : 0;
+    in.cu_count = device_info().cu_count;
+    in.pass = pass;
+    in.whole_store = n_rows == h->count;
+    return u8_gemm_route(in, dev_switches().route);
+}
+
+// One GEMM pass: rows [0, n_rows) of (codes, v_offsets) against every query of the batch.
+struct GemmCall {
+    const qamd_u8 *h;
+    const qamd_u8_query_batch *b;
+    const uint8_t *codes;
+    const float *v_offsets;
+    uint64_t n_rows;
+    float *out;
+    uint64_t out_pitch;
+    BatchFilter filt;
+    hipStream_t s;
+};
+
+// fn(std::bool_constant<LOW>): LOW is the direction of the integer pre-filter of MODE 1 / 2 - "may pass" is s <= bound
+// when the score falls with s (multiplier < 0) xor smallest-first.  The other modes have no pre-filter (LOW = false).
+template <int MODE, typename Fn>
+qamd_status with_low(float multiplier, Fn &&fn) {
+    if constexpr (MODE == 1 || MODE == 2) {
+        if ((multiplier < 0.0f) != (MODE == 2)) return fn(std::true_type{});
+    }
+    return fn(std::false_type{});
+}
+
+// Per-query integer bounds of the pre-filter for the kernels that stream or hold queries in fragment order (behind the
+// pivots in stream order).
+template <bool LOW>
+qamd_status launch_qs_bounds(const GemmCall &c) {
+    hipLaunchKernelGGL(qs_bounds_kernel<LOW>, dim3((unsigned)(c.b->q_pad / 256)), dim3(256), 0, c.s, c.filt.pivot_scores,
+                       c.b->offsets.as<float>(), c.h->meta.multiplier, c.filt.largest, (uint32_t)c.b->q_pad, c.filt.query_bounds);
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
+
 template <int MODE, int TQ_, int TR_, int WQ, int WR, int BK_>
-qamd_status launch_gemm_cfg(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                            const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                            const BatchFilter &filt, hipStream_t s) {
-    const uint32_t q_tiles = (uint32_t)((b->n_queries + TQ_ - 1) / TQ_);  // q_pad (multiple of 256) covers them
-    const uint64_t r_tiles = round_up((n_rows + TR_ - 1) / TR_, 8);  // whole groups of 8 row tiles (one per XCD)
+qamd_status launch_gemm_cfg(const GemmCall &c) {
+    const uint32_t q_tiles = (uint32_t)((c.b->n_queries + TQ_ - 1) / TQ_);  // q_pad (multiple of 256) covers them
+    const uint64_t r_tiles = round_up((c.n_rows + TR_ - 1) / TR_, 8);  // whole groups of 8 row tiles (one per XCD)
     const uint64_t blocks = r_tiles * q_tiles;
     if (blocks > 0x7FFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "batch too large for one launch");
     constexpr size_t lds_bytes = (size_t)2 * (TQ_ + TR_) * (BK_ + 16);
     QAMD_LDS_OPT_IN((&u8_gemm_kernel<MODE, TQ_, TR_, WQ, WR, BK_>), (int)lds_bytes);
     hipLaunchKernelGGL((u8_gemm_kernel<MODE, TQ_, TR_, WQ, WR, BK_>), dim3((unsigned)blocks), dim3(64 * WQ * WR), lds_bytes,
-                       s, codes, v_offsets, b->codes.as<uint8_t>(), (uint32_t)b->pitch, b->offsets.as<float>(), h->meta.multiplier,
-                       (uint32_t)n_rows, (uint32_t)b->n_queries, (uint32_t)h->meta.actual_dim, q_tiles, out, out_pitch,
-                       filt);
+                       c.s, c.codes, c.v_offsets, c.b->codes.as<uint8_t>(), (uint32_t)c.b->pitch, c.b->offsets.as<float>(),
+                       c.h->meta.multiplier, (uint32_t)c.n_rows, (uint32_t)c.b->n_queries, (uint32_t)c.h->meta.actual_dim, q_tiles,
+                       c.out, c.out_pitch, c.filt);
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
 }
 
-inline uint32_t pp_launches(uint64_t n_queries) {
-    const uint64_t per = (uint64_t)std::max(1, device_info().cu_count / 8) * (n_queries <= 128 ? 128 : 256);
-    return (uint32_t)((n_queries + per - 1) / per);
+// The ping-pong and row-streaming kernels: one persistent workgroup per CU, a launch per cus_per_xcd query tiles of
+// TQW queries (8192 queries of the ping-pong kernel's 256-query tiles on 256 CUs).
+template <int MODE, auto KERNEL, uint64_t TQW, int LDS_OPT_IN>
+qamd_status launch_tile_sliced(const GemmCall &c, size_t lds_bytes) {
+    QAMD_LDS_OPT_IN(KERNEL, LDS_OPT_IN);
+    const qamd_u8_query_batch *b = c.b;
+    const uint32_t cus_per_xcd = (uint32_t)std::max(1, device_info().cu_count / 8);
+    const uint64_t all_q_tiles = (b->n_queries + TQW - 1) / TQW;
+    for (uint64_t qt0 = 0; qt0 < all_q_tiles; qt0 += cus_per_xcd) {
+        const uint32_t q_tiles = (uint32_t)std::min<uint64_t>(cus_per_xcd, all_q_tiles - qt0);
+        const uint32_t row_lanes = cus_per_xcd / q_tiles;
+        const uint64_t q_base = qt0 * TQW;
+        BatchFilter f = c.filt;
+        if (MODE != 0) {
+            f.pivot_scores += q_base;
+            f.query_base = (uint32_t)q_base;
+            f.wave_base = (uint32_t)(qt0 / cus_per_xcd) * pp_waves_per_launch();
+        }
+        hipLaunchKernelGGL(KERNEL, dim3(8 * row_lanes * q_tiles), dim3(512), lds_bytes, c.s, c.codes, c.v_offsets,
+                           b->codes.as<uint8_t>() + q_base * b->pitch, (uint32_t)b->pitch, b->offsets.as<float>() + q_base,
+                           c.h->meta.multiplier, (uint32_t)c.n_rows, (uint32_t)(b->n_queries - q_base),
+                           (uint32_t)c.h->meta.actual_dim, q_tiles, row_lanes, MODE == 0 ? c.out + q_base * c.out_pitch : c.out,
+                           c.out_pitch, f);
+        QAMD_HIP(hipGetLastError());
+    }
+    return QAMD_OK;
 }
-
-// Ping-pong kernel launch: one persistent workgroup per CU; at most 32 query tiles per launch
-// (8192 queries), larger batches go in slices of 8192.
 template <int MODE, bool LOW, int MI, int MJ>
-qamd_status launch_gemm_pp_cfg(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                           const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                           const BatchFilter &filt, hipStream_t s) {
-    QAMD_LDS_OPT_IN((&u8_gemm_pp_kernel<MODE, LOW, MI, MJ>), (int)(PpShape<MI, MJ>::LDS));
-    constexpr uint64_t TQW = 64 * MI;  // queries per workgroup tile
-    constexpr size_t lds_bytes = PpShape<MI, MJ>::LDS;
-    const uint32_t cus_per_xcd = (uint32_t)std::max(1, device_info().cu_count / 8);
-    const uint64_t all_q_tiles = (b->n_queries + TQW - 1) / TQW;
-    for (uint64_t qt0 = 0; qt0 < all_q_tiles; qt0 += cus_per_xcd) {
-        const uint32_t q_tiles = (uint32_t)std::min<uint64_t>(cus_per_xcd, all_q_tiles - qt0);
-        const uint32_t row_lanes = cus_per_xcd / q_tiles;
-        const uint64_t q_base = qt0 * TQW;
-        BatchFilter f = filt;
-        if (MODE != 0) {
-            f.pivot_scores += q_base;
-            f.query_base = (uint32_t)q_base;
-            f.wave_base = (uint32_t)(qt0 / cus_per_xcd) * pp_waves_per_launch();
-        }
-        hipLaunchKernelGGL((u8_gemm_pp_kernel<MODE, LOW, MI, MJ>), dim3(8 * row_lanes * q_tiles), dim3(512), lds_bytes, s,
-                           codes, v_offsets, b->codes.as<uint8_t>() + q_base * b->pitch, (uint32_t)b->pitch,
-                           b->offsets.as<float>() + q_base, h->meta.multiplier, (uint32_t)n_rows,
-                           (uint32_t)(b->n_queries - q_base), (uint32_t)h->meta.actual_dim, q_tiles, row_lanes,
-                           MODE == 0 ? out + q_base * out_pitch : out, out_pitch, f);
-        QAMD_HIP(hipGetLastError());
-    }
-    return QAMD_OK;
+qamd_status launch_gemm_pp(const GemmCall &c) {
+    return launch_tile_sliced<MODE, &u8_gemm_pp_kernel<MODE, LOW, MI, MJ>, 64 * MI, (int)PpShape<MI, MJ>::LDS>(c, PpShape<MI, MJ>::LDS);
 }
-
-template <int MODE>
-qamd_status launch_gemm_pp(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                           const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                           const BatchFilter &filt, hipStream_t s) {
-    const bool small = b->n_queries <= 128;  // 128-query tile: the store is streamed once, HBM-bound
-    if (MODE == 0)
-        return small ? launch_gemm_pp_cfg<0, false, 2, 4>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s)
-                     : launch_gemm_pp_cfg<0, false, 4, 2>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-    // "may pass" is s <= bound when the score falls with s (multiplier < 0) xor smallest-first
-    constexpr int M = MODE == 0 ? 1 : MODE;
-    const bool low = (h->meta.multiplier < 0.0f) != (MODE == 2);
-    if (small)
-        return low ? launch_gemm_pp_cfg<M, true, 2, 4>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s)
-                   : launch_gemm_pp_cfg<M, false, 2, 4>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-    return low ? launch_gemm_pp_cfg<M, true, 4, 2>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s)
-               : launch_gemm_pp_cfg<M, false, 4, 2>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-}
-
-// Row-streaming kernel launch: one persistent workgroup per CU, query tile resident in LDS.
-// rs_frags() = query fragments per workgroup (0: the tile does not fit, use another kernel).
-inline int rs_frags(uint64_t n_queries, uint64_t ad) {
-    const size_t lds_max = 160 * 1024;
-    for (int mi : {1, 2, 4})  // the smallest tile that holds the whole batch, else the largest that fits
-        if (n_queries <= (uint64_t)32 * mi && (size_t)32 * mi * (round_up(ad, 128) + 16) + 2048 + 32768 <= lds_max) return mi;
-    for (int mi : {4, 2, 1})
-        if ((size_t)32 * mi * (round_up(ad, 128) + 16) + 2048 + 32768 <= lds_max) return mi;
-    return 0;
-}
-
 template <int MODE, bool LOW, int MI, bool NT>
-qamd_status launch_gemm_rs_cfg(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                               const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                               const BatchFilter &filt, hipStream_t s) {
-    QAMD_LDS_OPT_IN((&u8_gemm_rs_kernel<MODE, LOW, MI, NT>), 160 * 1024);
-    constexpr uint64_t TQW = 32 * MI;
-    const size_t lds_bytes = RsShape<MI>::lds_bytes((uint32_t)h->meta.actual_dim);
-    const uint32_t cus_per_xcd = (uint32_t)std::max(1, device_info().cu_count / 8);
-    const uint64_t all_q_tiles = (b->n_queries + TQW - 1) / TQW;
-    for (uint64_t qt0 = 0; qt0 < all_q_tiles; qt0 += cus_per_xcd) {
-        const uint32_t q_tiles = (uint32_t)std::min<uint64_t>(cus_per_xcd, all_q_tiles - qt0);
-        const uint32_t row_lanes = cus_per_xcd / q_tiles;
-        const uint64_t q_base = qt0 * TQW;
-        BatchFilter f = filt;
-        if (MODE != 0) {
-            f.pivot_scores += q_base;
-            f.query_base = (uint32_t)q_base;
-            f.wave_base = (uint32_t)(qt0 / cus_per_xcd) * pp_waves_per_launch();
-        }
-        hipLaunchKernelGGL((u8_gemm_rs_kernel<MODE, LOW, MI, NT>), dim3(8 * row_lanes * q_tiles), dim3(512), lds_bytes, s,
-                           codes, v_offsets, b->codes.as<uint8_t>() + q_base * b->pitch, (uint32_t)b->pitch,
-                           b->offsets.as<float>() + q_base, h->meta.multiplier, (uint32_t)n_rows,
-                           (uint32_t)(b->n_queries - q_base), (uint32_t)h->meta.actual_dim, q_tiles, row_lanes,
-                           MODE == 0 ? out + q_base * out_pitch : out, out_pitch, f);
-        QAMD_HIP(hipGetLastError());
-    }
-    return QAMD_OK;
+qamd_status launch_gemm_rs(const GemmCall &c) {
+    return launch_tile_sliced<MODE, &u8_gemm_rs_kernel<MODE, LOW, MI, NT>, 32 * MI, 160 * 1024>(
+        c, RsShape<MI>::lds_bytes((uint32_t)c.h->meta.actual_dim));
 }
 
-template <int MODE>
-qamd_status launch_gemm_rs(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                           const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                           const BatchFilter &filt, hipStream_t s) {
-    const int mi = rs_frags(b->n_queries, h->meta.actual_dim);
-    constexpr int M = MODE == 0 ? 1 : MODE;
-    const bool low = MODE != 0 && (h->meta.multiplier < 0.0f) != (MODE == 2);
-    const bool nt = b->n_queries <= (uint64_t)32 * mi;  // one query tile: every row byte is read exactly once
-#define QAMD_RS2(MI_, NT_)                                                                                        \
-    (MODE == 0 ? launch_gemm_rs_cfg<0, false, MI_, NT_>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s)  \
-     : low     ? launch_gemm_rs_cfg<M, true, MI_, NT_>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s)   \
-               : launch_gemm_rs_cfg<M, false, MI_, NT_>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s))
-#define QAMD_RS(MI_) (nt ? QAMD_RS2(MI_, true) : QAMD_RS2(MI_, false))
-    if (mi == 4) return QAMD_RS(4);
-    if (mi == 2) return QAMD_RS(2);
-    return QAMD_RS(1);
-#undef QAMD_RS2
-#undef QAMD_RS
-}
-
-// Queries per launch slice of the kernel that serves this batch (wave-list bookkeeping).
-bool qr_selected(const qamd_u8 *h, const qamd_u8_query_batch *b, bool filter_mode);
-bool rq_selected(const qamd_u8 *h, const qamd_u8_query_batch *b);
-inline uint32_t gemm_launches(const qamd_u8 *h, const qamd_u8_query_batch *b, bool rs, bool qs) {
-    if (qs && qr_selected(h, b, true)) return (uint32_t)((b->n_queries + 255) / 256);  // passes of the queries-in-registers form
-    if (qs) return (uint32_t)((b->n_queries + 2048 - 1) / 2048);
-    if (!rs) return pp_launches(b->n_queries);
-    const uint64_t per = (uint64_t)std::max(1, device_info().cu_count / 8) * 32 * rs_frags(b->n_queries, h->meta.actual_dim);
-    return (uint32_t)((b->n_queries + per - 1) / per);
-}
-
-// Which kernel serves a batch: the ping-pong kernel (rows of at least three 64-byte K-tiles, a
-// usable multiplier for its integer pre-filter), else u8_gemm_kernel.
-bool pp_selected(const qamd_u8 *h, const qamd_u8_query_batch *b, bool filter_mode) {
-    static const char *cfg = dev_env("QAMD_GEMM_CFG");  // developer A/B switch: 0/3/4/5 = u8_gemm_kernel shapes
-    if (cfg && cfg[0] != 'p') return false;
-    const float m = h->meta.multiplier;
-    return h->meta.actual_dim > 128 && h->meta.actual_dim <= 32768 && (!filter_mode || (std::isfinite(m) && m != 0.0f));
-}
-
-// Query-streaming kernel launch: one persistent workgroup per CU, slices of kQsSlice queries (the
-// slice's fragment-order codes, 1.5 MiB at 768-byte rows, stay in every XCD's L2).
-constexpr uint64_t kQsSlice = 2048;
-template <int MODE, bool LOW, int MJ>
-qamd_status launch_gemm_qs_cfg(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                               const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                               const BatchFilter &filt, const int *bq, hipStream_t s) {
-    QAMD_LDS_OPT_IN((&u8_gemm_qs_kernel<MODE, LOW, MJ>), 160 * 1024);
-    const uint32_t nkb = b->frag_nkb;
-    constexpr int QS_ROWS = 32 * MJ;
-    const size_t lds_bytes = (size_t)QS_ROWS * (nkb * 128 + 16) + 2 * QS_ROWS * 4 + 64 + kQsSlice * 4;
-    const uint32_t grid = (uint32_t)std::max(1, device_info().cu_count / 8) * 8;
-    for (uint64_t q_base = 0; q_base < b->n_queries; q_base += kQsSlice) {
-        const uint32_t nq = (uint32_t)std::min<uint64_t>(kQsSlice, b->n_queries - q_base);
-        BatchFilter f = filt;
+// The query-streaming and queries-in-registers kernels: one persistent workgroup per CU, a launch per slice of the
+// batch; launch_slice(first query, queries, the slice's filter) starts one.
+template <int MODE, typename LaunchSlice>
+qamd_status launch_query_sliced(const GemmCall &c, uint64_t slice, LaunchSlice &&launch_slice) {
+    for (uint64_t q_base = 0; q_base < c.b->n_queries; q_base += slice) {
+        const uint32_t nq = (uint32_t)std::min<uint64_t>(slice, c.b->n_queries - q_base);
+        BatchFilter f = c.filt;
         if (MODE == 1 || MODE == 2) {
             f.pivot_scores += q_base;
             f.query_base = (uint32_t)q_base;
-            f.wave_base = (uint32_t)(q_base / kQsSlice) * pp_waves_per_launch();
+            f.wave_base = (uint32_t)(q_base / slice) * pp_waves_per_launch();
         }
-        hipLaunchKernelGGL((u8_gemm_qs_kernel<MODE, LOW, MJ>), dim3(grid), dim3(512), lds_bytes, s, codes, v_offsets,
-                           b->frag.as<uint4>() + (q_base / 32) * nkb * 256, b->offsets.as<float>() + q_base,
-                           (MODE == 1 || MODE == 2) ? bq + q_base : nullptr, h->meta.multiplier, (uint32_t)n_rows, nq,
-                           (uint32_t)round_up((uint64_t)nq, 64), (uint32_t)h->meta.actual_dim,
-                           (MODE == 0 || MODE == 3) ? out + q_base * out_pitch : out, out_pitch, f);
+        launch_slice(q_base, nq, f);
         QAMD_HIP(hipGetLastError());
     }
     return QAMD_OK;
 }
-
-// The same on v_mfma_i32_16x16x64_i8 (u8_gemm_qs16_kernel): rows of up to 1024 bytes, the batch's fragment copy in its order.
-constexpr uint64_t kQs16SmallBatch = 256;
-inline bool qs16_wanted(uint32_t nkb) {
-    static const char *e = dev_env("QAMD_QS16");  // developer A/B: 0 = the 32x32x32 kernel for every row length
-    return nkb >= 1 && nkb <= 12 && !(e && e[0] == '0');
-}
-
 template <int MODE, bool LOW, int JT, int IT>
-qamd_status launch_gemm_qs16_cfg(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                                 const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                                 const BatchFilter &filt, const int *bq, hipStream_t s) {
+qamd_status launch_gemm_qs16(const GemmCall &c) {
     QAMD_LDS_OPT_IN((&u8_gemm_qs16_kernel<MODE, LOW, JT, IT>), 160 * 1024);
-    const uint32_t nkb = b->frag_nkb;
+    constexpr bool FILTER = MODE == 1 || MODE == 2;
     constexpr int QS_ROWS = 16 * JT;
-    const uint32_t per = (uint32_t)(h->meta.actual_dim / 16);
+    const qamd_u8_query_batch *b = c.b;
+    const uint32_t nkb = b->frag_nkb, ad = (uint32_t)c.h->meta.actual_dim, per = ad / 16;
     const size_t lds_bytes = (size_t)QS_ROWS * (((per + 15) / 16) * 256) + 2 * QS_ROWS * 4 + 64 + kQsSlice * 4;
     const uint32_t grid = (uint32_t)std::max(1, device_info().cu_count / 8) * 8;
-    for (uint64_t q_base = 0; q_base < b->n_queries; q_base += kQsSlice) {
-        const uint32_t nq = (uint32_t)std::min<uint64_t>(kQsSlice, b->n_queries - q_base);
-        BatchFilter f = filt;
-        if (MODE == 1 || MODE == 2) {
-            f.pivot_scores += q_base;
-            f.query_base = (uint32_t)q_base;
-            f.wave_base = (uint32_t)(q_base / kQsSlice) * pp_waves_per_launch();
-        }
-        hipLaunchKernelGGL((u8_gemm_qs16_kernel<MODE, LOW, JT, IT>), dim3(grid), dim3(512), lds_bytes, s, codes, v_offsets,
+    return launch_query_sliced<MODE>(c, kQsSlice, [&](uint64_t q_base, uint32_t nq, const BatchFilter &f) {
+        hipLaunchKernelGGL((u8_gemm_qs16_kernel<MODE, LOW, JT, IT>), dim3(grid), dim3(512), lds_bytes, c.s, c.codes, c.v_offsets,
                            b->frag.as<uint4>() + (q_base / 16) * nkb * 128, b->offsets.as<float>() + q_base,
-                           (MODE == 1 || MODE == 2) ? bq + q_base : nullptr, h->meta.multiplier, (uint32_t)n_rows, nq,
-                           (uint32_t)round_up((uint64_t)nq, 64), (uint32_t)h->meta.actual_dim,
-                           (MODE == 0 || MODE == 3) ? out + q_base * out_pitch : out, out_pitch, f);
-        QAMD_HIP(hipGetLastError());
-    }
-    return QAMD_OK;
+                           FILTER ? c.filt.query_bounds + q_base : nullptr, c.h->meta.multiplier, (uint32_t)c.n_rows, nq,
+                           (uint32_t)round_up((uint64_t)nq, 64), ad, FILTER ? c.out : c.out + q_base * c.out_pitch, c.out_pitch, f);
+    });
 }
-
-// Queries in registers, rows through a double-buffered LDS slab (u8_gemm_qr16_kernel): batches cut into passes of 256
-// queries.  QAMD_GEMM_CFG=g forces it where it can run (developer A/B); QAMD_QR_MIN / QAMD_QR_MAX move its range.
-// Measured (profiles/r03_qs_experiments.txt §7), whole topk_batch(30) ms, row-streaming passes / this kernel:
-//   10M x 768:    129 q 2.17 / 1.65   192 q 2.21 / 1.75   256 q 2.26 / 1.91     (two passes: 512 q 3.81 against 3.66 query-streaming)
-//   7.5M x 1024:   65 q 1.52 / 1.23   129 q 2.18 / 1.55   256 q 2.75 / 1.84
-//   15M x 512:    129 q 2.28 / 1.76   256 q 2.41 / 2.08       30M x 256:  129 q 2.68 / 2.44   256 q 2.84 / 2.55
-// -> one pass only: 129 .. 256 queries (from 65 on 1024-byte rows, where the row-streaming kernel needs two 64-query tiles).
-constexpr uint64_t kQrQueries = 256;
-inline bool qr_possible(const qamd_u8 *h, const qamd_u8_query_batch *b, bool filter_mode) {
-    const float m = h->meta.multiplier;
-    if (filter_mode && !(std::isfinite(m) && m != 0.0f)) return false;
-    const uint64_t ad = h->meta.actual_dim;
-    return b->frag.ptr && b->frag16 && (ad == 256 || ad == 384 || ad == 512 || ad == 768 || ad == 1024);
-}
-bool qr_selected(const qamd_u8 *h, const qamd_u8_query_batch *b, bool filter_mode) {
-    static const char *cfg = dev_env("QAMD_GEMM_CFG");
-    static const char *lo = dev_env("QAMD_QR_MIN"), *hi = dev_env("QAMD_QR_MAX");
-    if (cfg && cfg[0] != 'g') return false;
-    if (!qr_possible(h, b, filter_mode)) return false;
-    if (cfg) return true;
-    // a store of fewer than ~4 slabs per workgroup (a small Qdrant segment) leaves this persistent grid a ragged tail too:
-    // the same guard as qs_selected (the row-streaming tiles split such a store evenly)
-    if (!lo && !hi && h->count < 131072 && h->meta.actual_dim <= 1152) return false;
-    const uint64_t q_min = lo ? (uint64_t)atoll(lo) : (h->meta.actual_dim == 1024 ? 65 : 129);
-    const uint64_t q_max = hi ? (uint64_t)atoll(hi) : kQrQueries;
-    return b->n_queries >= q_min && b->n_queries <= q_max;
-}
-
-template <int MODE, bool LOW>
-qamd_status launch_gemm_qr_cfg(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                               const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                               const BatchFilter &filt, const int *bq, hipStream_t s) {
+template <int MODE, bool LOW, int NSTEPS>
+qamd_status launch_gemm_qr16(const GemmCall &c) {
+    QAMD_LDS_OPT_IN((&u8_gemm_qr16_kernel<MODE, LOW, NSTEPS>), 160 * 1024);
+    constexpr bool FILTER = MODE == 1 || MODE == 2;
+    const qamd_u8_query_batch *b = c.b;
     const uint32_t nkb = b->frag_nkb;
-    const uint64_t ad = h->meta.actual_dim;
+    const uint64_t ad = c.h->meta.actual_dim;
     const size_t lds_bytes = 2 * (size_t)64 * round_up(ad, 256) + 4 * 64 * 4 + 64;
     const uint32_t grid = (uint32_t)std::max(1, device_info().cu_count / 8) * 8;
-    for (uint64_t q_base = 0; q_base < b->n_queries; q_base += kQrQueries) {
-        const uint32_t nq = (uint32_t)std::min<uint64_t>(kQrQueries, b->n_queries - q_base);
-        BatchFilter f = filt;
-        if (MODE == 1 || MODE == 2) {
-            f.pivot_scores += q_base;
-            f.query_base = (uint32_t)q_base;
-            f.wave_base = (uint32_t)(q_base / kQrQueries) * pp_waves_per_launch();
-        }
-#define QAMD_QR(NS_)                                                                                                          \
-    do {                                                                                                                     \
-        QAMD_LDS_OPT_IN((&u8_gemm_qr16_kernel<MODE, LOW, NS_>), 160 * 1024); \
-        hipLaunchKernelGGL((u8_gemm_qr16_kernel<MODE, LOW, NS_>), dim3(grid), dim3(512), lds_bytes, s, codes, v_offsets,     \
-                           b->frag.as<uint4>() + (q_base / 16) * nkb * 128, b->offsets.as<float>() + q_base,                 \
-                           (MODE == 1 || MODE == 2) ? bq + q_base : nullptr, h->meta.multiplier, (uint32_t)n_rows, nq,       \
-                           (uint32_t)ad, (MODE == 0 || MODE == 3) ? out + q_base * out_pitch : out, out_pitch, f);           \
-    } while (0)
-        if (nkb == 2) QAMD_QR(4);
-        else if (nkb == 3) QAMD_QR(6);
-        else if (nkb == 4) QAMD_QR(8);
-        else if (nkb == 6) QAMD_QR(12);
-        else QAMD_QR(16);
-#undef QAMD_QR
-        QAMD_HIP(hipGetLastError());
-    }
-    return QAMD_OK;
+    return launch_query_sliced<MODE>(c, kQrQueries, [&](uint64_t q_base, uint32_t nq, const BatchFilter &f) {
+        hipLaunchKernelGGL((u8_gemm_qr16_kernel<MODE, LOW, NSTEPS>), dim3(grid), dim3(512), lds_bytes, c.s, c.codes, c.v_offsets,
+                           b->frag.as<uint4>() + (q_base / 16) * nkb * 128, b->offsets.as<float>() + q_base,
+                           FILTER ? c.filt.query_bounds + q_base : nullptr, c.h->meta.multiplier, (uint32_t)c.n_rows, nq,
+                           (uint32_t)ad, FILTER ? c.out : c.out + q_base * c.out_pitch, c.out_pitch, f);
+    });
 }
 
-template <int MODE>
-qamd_status launch_gemm_qr(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                           const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                           const BatchFilter &filt, hipStream_t s) {
-    if (MODE == 0) return launch_gemm_qr_cfg<0, false>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, nullptr, s);
-    if (MODE == 3) return launch_gemm_qr_cfg<3, false>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, nullptr, s);
-    constexpr int M = (MODE == 1 || MODE == 2) ? MODE : 1;
-    const bool low = (h->meta.multiplier < 0.0f) != (MODE == 2);
-    int *bq = filt.query_bounds;  // per-query integer bounds of the pre-filter, behind the pivots in stream order
-    if (low)
-        hipLaunchKernelGGL(qs_bounds_kernel<true>, dim3((unsigned)(b->q_pad / 256)), dim3(256), 0, s, filt.pivot_scores,
-                           b->offsets.as<float>(), h->meta.multiplier, filt.largest, (uint32_t)b->q_pad, bq);
-    else
-        hipLaunchKernelGGL(qs_bounds_kernel<false>, dim3((unsigned)(b->q_pad / 256)), dim3(256), 0, s, filt.pivot_scores,
-                           b->offsets.as<float>(), h->meta.multiplier, filt.largest, (uint32_t)b->q_pad, bq);
-    QAMD_HIP(hipGetLastError());
-    return low ? launch_gemm_qr_cfg<M, true>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, bq, s)
-               : launch_gemm_qr_cfg<M, false>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, bq, s);
-}
-
-// Queries resident, rows streamed (u8_gemm_rq16_kernel): the filter pass of topk_batch for batches of kRqMinQueries and more
-// on rows of 256 / 384 / 512 / 768 bytes, in groups of query tiles that run side by side on the CUs of an XCD.
-// QAMD_GEMM_CFG=s forces it where it can run, QAMD_RQ=0 switches it off (developer A/B, tools/lib build).
-constexpr uint64_t kRqMinQueries = 129;
-inline RqGeometry rq_geometry(uint64_t n_queries, uint32_t nsteps) {
-    // the fewest groups whose tile pairs fit a CU's LDS, the pairs spread evenly; 32 / G row streams per XCD (QAMD_RQ_GROUPS:
-    // developer A/B).  More groups than needed only add L2 -> CU traffic: at 10M x 768, 1024 queries, 6 groups 8.3 ms, 8 groups 8.7.
-    static const char *eg = dev_env("QAMD_RQ_GROUPS");
-    RqGeometry g{};
-    g.n_tiles = (uint32_t)(round_up(n_queries, 32) / 16);
-    const uint32_t pairs = g.n_tiles / 2, cap_pairs = rq_tile_cap(nsteps) / 2;
-    g.groups = eg ? (uint32_t)atoi(eg) : (pairs + cap_pairs - 1) / cap_pairs;
-    if (g.groups == 0 || g.groups > 8 || g.groups > pairs || (pairs + g.groups - 1) / g.groups > cap_pairs) {
-        g.groups = 0;
-        return g;
-    }
-    g.pairs_lo = pairs / g.groups;
-    g.pairs_extra = pairs % g.groups;
-    g.streams_per_xcd = 32u / g.groups;
-    return g;
-}
-bool rq_selected(const qamd_u8 *h, const qamd_u8_query_batch *b) {
-    static const char *cfg = dev_env("QAMD_GEMM_CFG"), *off = dev_env("QAMD_RQ"), *lo = dev_env("QAMD_RQ_MIN"), *hi = dev_env("QAMD_RQ_MAX");
-    if ((cfg && cfg[0] != 's') || (off && off[0] == '0')) return false;
-    const float m = h->meta.multiplier;
-    const uint64_t ad = h->meta.actual_dim;
-    if (!(std::isfinite(m) && m != 0.0f) || !b->frag.ptr || !b->frag16) return false;
-    if (!(ad == 256 || ad == 384 || ad == 512 || ad == 768)) return false;
-    if (device_info().cu_count != 256 || b->q_pad < round_up(b->n_queries, 32)) return false;  // (8 XCDs of 32 CUs: the group / stream map)
-    const RqGeometry g = rq_geometry(b->n_queries, (uint32_t)(ad / 64));
-    if (g.groups == 0) return false;  // (more than eight LDS images)
-    if (cfg) return true;
-    if (h->count < 131072) return false;  // (a small store: the row-streaming tiles split it evenly)
-    if (lo || hi) return b->n_queries >= (lo ? (uint64_t)atoll(lo) : kRqMinQueries) && b->n_queries <= (hi ? (uint64_t)atoll(hi) : ~0ull);
-    if (b->n_queries < kRqMinQueries) return false;
-    // Measured, whole topk_batch(30) ms, before / this kernel (tools/experiments/u8_rq_sweep.sh, profiles/r04_u8_rq.txt):
-    //   15M x 512:  129 q 1.95 / 1.49  288 q 3.42 / 2.19 | 289 q 3.40 / 2.64  576 q 5.32 / 4.14 | 768 q 5.84 / 5.48  1152 q 7.91 / 7.61
-    //   30M x 256:  129 q 2.75 / 1.60  608 q 7.04 / 4.77 | 609 q 7.05 / 5.10  1216 q 10.6 / 8.89 | 1800 q 14.0 / 12.5  2400 q 19.7 / 16.6
-    // 768-byte rows, the K-outer form (u8_gemm_rk16_kernel), before / with it:  129 q 1.64 / 1.49   192 q 1.78 / 1.54 | 193-256 q (two
-    // groups) 1.92-2.03 / 2.33-2.38: the queries-in-registers kernel keeps those | 257 q 2.94 / 2.50  288 q 2.99 / 2.51  384 q 3.26 / 2.62 |
-    // three groups: 400 q 3.52 / 3.65  512 q 3.83 / 3.91 (no), 576 q 4.80 / 4.00 (past the query-streaming kernel's step at 513) |
-    // four: 640 q 5.07 / 4.71  768 q 5.50 / 5.08 | five and more (30 of an XCD's 32 CUs, or half-empty groups): 832 q 5.85 / 6.25,
-    // 1024 q in eight groups of eight tiles 6.44 / 6.44
-    if (ad == 768)
-        return g.groups == 1 || (g.groups == 2 && b->n_queries > kQrQueries) || (g.groups == 3 && b->n_queries > 512) || g.groups == 4;
-    return g.groups <= 4;
-}
-template <int MODE, bool LOW>
-qamd_status launch_gemm_rq_cfg(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes, const float *v_offsets,
-                               uint64_t n_rows, const BatchFilter &filt, const int *bq, hipStream_t s) {
-    const uint32_t nsteps = (uint32_t)(h->meta.actual_dim / 64);
-    const RqGeometry g = rq_geometry(b->n_queries, nsteps);
-    const size_t max_tiles = 2 * (size_t)(g.pairs_lo + (g.pairs_extra ? 1 : 0));
-    const size_t lds_bytes = max_tiles * nsteps * 1024 + max_tiles * 64 + 64;
-    BatchFilter f = filt;
+// The resident-queries kernels: the whole batch in one launch of 256 workgroups (8 XCDs of 32 CUs), LDS for the
+// largest group's tiles.  NT = 0: the tile-outer form (u8_gemm_rq16_kernel), else the K-outer form with NT tiles.
+template <int MODE, bool LOW, int NSTEPS, int NT>
+qamd_status launch_gemm_rq(const GemmCall &c, const RqGeometry &g) {
+    BatchFilter f = c.filt;
     f.query_base = 0;
     f.wave_base = 0;
-    static const char *ek = dev_env("QAMD_RQ_K");  // developer A/B: 0 = the tile-outer form on 768-byte rows as well
-    if (nsteps == 12 && !(ek && ek[0] == '0')) {    // the K-outer form: all tiles' accumulators in registers
-#define QAMD_RK(NT_)                                                                                                       \
-    do {                                                                                                                  \
-        QAMD_LDS_OPT_IN((&u8_gemm_rk16_kernel<MODE, LOW, 12, NT_>), 160 * 1024);                                           \
-        hipLaunchKernelGGL((u8_gemm_rk16_kernel<MODE, LOW, 12, NT_>), dim3(256), dim3(512),                                \
-                           (size_t)NT_ * 12 * 1024 + (size_t)NT_ * 64 + 64, s, codes, v_offsets, b->frag.as<uint4>(),     \
-                           b->offsets.as<float>(), bq, h->meta.multiplier, (uint32_t)n_rows, g, f);                       \
-    } while (0)
-        if (max_tiles <= 8) QAMD_RK(8);
-        else if (max_tiles <= 10) QAMD_RK(10);
-        else QAMD_RK(12);
-#undef QAMD_RK
-        QAMD_HIP(hipGetLastError());
-        return QAMD_OK;
+    if constexpr (NT != 0) {
+        QAMD_LDS_OPT_IN((&u8_gemm_rk16_kernel<MODE, LOW, NSTEPS, NT>), 160 * 1024);
+        hipLaunchKernelGGL((u8_gemm_rk16_kernel<MODE, LOW, NSTEPS, NT>), dim3(256), dim3(512),
+                           (size_t)NT * NSTEPS * 1024 + (size_t)NT * 64 + 64, c.s, c.codes, c.v_offsets, c.b->frag.as<uint4>(),
+                           c.b->offsets.as<float>(), c.filt.query_bounds, c.h->meta.multiplier, (uint32_t)c.n_rows, g, f);
+    } else {
+        const size_t max_tiles = 2 * (size_t)(g.pairs_lo + (g.pairs_extra ? 1 : 0));
+        QAMD_LDS_OPT_IN((&u8_gemm_rq16_kernel<MODE, LOW, NSTEPS>), 160 * 1024);
+        hipLaunchKernelGGL((u8_gemm_rq16_kernel<MODE, LOW, NSTEPS>), dim3(256), dim3(512),
+                           max_tiles * NSTEPS * 1024 + max_tiles * 64 + 64, c.s, c.codes, c.v_offsets, c.b->frag.as<uint4>(),
+                           c.b->offsets.as<float>(), c.filt.query_bounds, c.h->meta.multiplier, (uint32_t)c.n_rows, g, f);
     }
-#define QAMD_RQ(NS_)                                                                                                       \
-    do {                                                                                                                  \
-        QAMD_LDS_OPT_IN((&u8_gemm_rq16_kernel<MODE, LOW, NS_>), 160 * 1024);                                               \
-        hipLaunchKernelGGL((u8_gemm_rq16_kernel<MODE, LOW, NS_>), dim3(256), dim3(512), lds_bytes, s, codes, v_offsets,    \
-                           b->frag.as<uint4>(), b->offsets.as<float>(), bq, h->meta.multiplier, (uint32_t)n_rows, g, f);  \
-    } while (0)
-    switch (nsteps) {
-        case 4: QAMD_RQ(4); break;
-        case 6: QAMD_RQ(6); break;
-        case 8: QAMD_RQ(8); break;
-        default: QAMD_RQ(12); break;
-    }
-#undef QAMD_RQ
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
 }
 
+// Launch the kernel of the route in its template shape.  MODE 0: scores out; 1 / 2: filter for the largest / smallest;
+// 3: the best score of every (query, block of rt.sample_block_rows rows).  The route must be the one of this pass:
+// MODE 3 exists for the query-streaming forms only, the resident-queries kernels for MODE 1 / 2 only.
 template <int MODE>
-qamd_status launch_gemm_qs(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                           const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                           const BatchFilter &filt, hipStream_t s) {
-    if ((MODE == 1 || MODE == 2) && n_rows == h->count && rq_selected(h, b)) {  // the filter pass over the store itself
-        constexpr int M = (MODE == 1 || MODE == 2) ? MODE : 1;
-        const bool low = (h->meta.multiplier < 0.0f) != (MODE == 2);
-        int *bq = filt.query_bounds;
-        if (low)
-            hipLaunchKernelGGL(qs_bounds_kernel<true>, dim3((unsigned)(b->q_pad / 256)), dim3(256), 0, s, filt.pivot_scores,
-                               b->offsets.as<float>(), h->meta.multiplier, filt.largest, (uint32_t)b->q_pad, bq);
-        else
-            hipLaunchKernelGGL(qs_bounds_kernel<false>, dim3((unsigned)(b->q_pad / 256)), dim3(256), 0, s, filt.pivot_scores,
-                               b->offsets.as<float>(), h->meta.multiplier, filt.largest, (uint32_t)b->q_pad, bq);
-        QAMD_HIP(hipGetLastError());
-        return low ? launch_gemm_rq_cfg<M, true>(h, b, codes, v_offsets, n_rows, filt, bq, s)
-                   : launch_gemm_rq_cfg<M, false>(h, b, codes, v_offsets, n_rows, filt, bq, s);
-    }
-    if (qr_selected(h, b, MODE != 0)) return launch_gemm_qr<MODE>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-    const bool wide = b->frag_nkb <= 9;  // 128 resident rows fit (rows of up to 1152 B), else 96
-    const bool tall = b->frag_nkb <= 8;  // 16x16x64 form: 128 resident rows of up to 1024 bytes, else 96
-    const bool small = b->n_queries <= kQs16SmallBatch;  // chunks of 32 queries: a chunk for every wave
-#define QAMD_QS16(M_, LOW_, BQ_)                                                                                                  \
-    (tall ? (small ? launch_gemm_qs16_cfg<M_, LOW_, 8, 2>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, BQ_, s)           \
-                   : launch_gemm_qs16_cfg<M_, LOW_, 8, 4>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, BQ_, s))          \
-          : (small ? launch_gemm_qs16_cfg<M_, LOW_, 6, 2>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, BQ_, s)           \
-                   : launch_gemm_qs16_cfg<M_, LOW_, 6, 4>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, BQ_, s)))
-    if (b->frag16 && MODE == 0) return QAMD_QS16(0, false, nullptr);
-    if (b->frag16 && MODE == 3) return QAMD_QS16(3, false, nullptr);
-    if (MODE == 0)
-        return wide ? launch_gemm_qs_cfg<0, false, 4>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, nullptr, s)
-                    : launch_gemm_qs_cfg<0, false, 3>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, nullptr, s);
-    if (MODE == 3)
-        return wide ? launch_gemm_qs_cfg<3, false, 4>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, nullptr, s)
-                    : launch_gemm_qs_cfg<3, false, 3>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, nullptr, s);
-    constexpr int M = (MODE == 1 || MODE == 2) ? MODE : 1;
-    const bool low = (h->meta.multiplier < 0.0f) != (MODE == 2);
-    // per-query integer bounds of the pre-filter, behind the pivots in stream order
-    int *bq = filt.query_bounds;
-    if (low)
-        hipLaunchKernelGGL(qs_bounds_kernel<true>, dim3((unsigned)(b->q_pad / 256)), dim3(256), 0, s, filt.pivot_scores,
-                           b->offsets.as<float>(), h->meta.multiplier, filt.largest, (uint32_t)b->q_pad, bq);
-    else
-        hipLaunchKernelGGL(qs_bounds_kernel<false>, dim3((unsigned)(b->q_pad / 256)), dim3(256), 0, s, filt.pivot_scores,
-                           b->offsets.as<float>(), h->meta.multiplier, filt.largest, (uint32_t)b->q_pad, bq);
-    QAMD_HIP(hipGetLastError());
-    if (b->frag16) return low ? QAMD_QS16(M, true, bq) : QAMD_QS16(M, false, bq);
-#undef QAMD_QS16
-    if (wide)
-        return low ? launch_gemm_qs_cfg<M, true, 4>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, bq, s)
-                   : launch_gemm_qs_cfg<M, false, 4>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, bq, s);
-    return low ? launch_gemm_qs_cfg<M, true, 3>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, bq, s)
-               : launch_gemm_qs_cfg<M, false, 3>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, bq, s);
-}
-
-// The query-streaming kernel: rows short enough for a 128-row block in LDS, a fragment-order copy in
-// the batch, enough queries to keep the 8 waves of a workgroup busy (64 queries per wave and turn).
-bool qs_selected(const qamd_u8 *h, const qamd_u8_query_batch *b, bool filter_mode) {
-    static const char *cfg = dev_env("QAMD_GEMM_CFG");
-    if (qr_selected(h, b, filter_mode)) return true;  // a form of it (launch_gemm_qs dispatches)
-    if (filter_mode && rq_selected(h, b)) return true;  // (the sample pass of such a batch takes the query-streaming forms)
-    if (cfg && cfg[0] != 'q') return false;
-    const float m = h->meta.multiplier;
-    if (filter_mode && !(std::isfinite(m) && m != 0.0f)) return false;
-    if (!b->frag.ptr || b->frag_nkb == 0 || b->frag_nkb > 12) return false;
-    if (cfg) return true;
-    // a store of fewer than ~4 row blocks per workgroup (a small Qdrant segment) leaves the persistent workgroups a
-    // ragged tail; the row-streaming tiles split such a store evenly (100k x 768, 1024 queries: 0.24 against 0.28 ms)
-    if (h->count < 131072 && h->meta.actual_dim <= 1152) return false;
-    return b->n_queries >= qs_min_queries(b->frag_nkb);
-}
-
-// The row-streaming kernel: where the ping-pong kernel could run (same pre-filter conditions), the
-// query tile fits in LDS, and the batch is small enough to be HBM-bound (QAMD_GEMM_CFG=r / p force).
-bool rs_selected(const qamd_u8 *h, const qamd_u8_query_batch *b, bool filter_mode) {
-    static const char *cfg = dev_env("QAMD_GEMM_CFG");
-    if (cfg && cfg[0] != 'r') return false;
-    const float m = h->meta.multiplier;
-    if (filter_mode && !(std::isfinite(m) && m != 0.0f)) return false;
-    const int mi = rs_frags(b->n_queries, h->meta.actual_dim);
-    if (mi == 0 || h->meta.actual_dim > 32768) return false;
-    if (cfg) return true;
-    // One query tile: every row byte leaves HBM once, at the plain scan's rate.  Several tiles re-read the
-    // rows (at HBM pace a line lives ~5 us in the XCD's L2, too short for the tiles' workgroups to share
-    // it), which still beats the ping-pong kernel for 128-query tiles up to 768 queries (measured at
-    // 10M x 768: 160 q 2.22 vs 2.41 ms, 384 q 3.39 vs 4.51, 512 q 4.29 vs 4.66, 1024 q 8.64 vs 8.70)
-    // and loses with the 64-query tiles of longer rows (12.5M x 1536: 96 q 3.88 vs 3.74, 256 q 6.83 vs 5.58).
-    const uint64_t tiles = (b->n_queries + 32 * mi - 1) / (32 * mi);
-    return tiles == 1 || (mi == 4 && !qs_selected(h, b, filter_mode));
-}
-
-// The kernel of launch_gemm<1 / 2> on the whole store (what the QAMD_DEBUG_TOPK line of topk_batch names): launch_gemm's dispatch.
-const char *filter_kernel_name(const qamd_u8 *h, const qamd_u8_query_batch *b) {
-    if (qs_selected(h, b, true)) {
-        if (rq_selected(h, b)) {
-            static const char *ek = dev_env("QAMD_RQ_K");
-            return h->meta.actual_dim == 768 && !(ek && ek[0] == '0') ? "u8_gemm_rk16_kernel" : "u8_gemm_rq16_kernel";
+qamd_status launch_gemm(const U8GemmRoute &rt, const GemmCall &c) {
+    if (c.n_rows == 0 || c.b->n_queries == 0) return QAMD_OK;
+    using K = U8GemmKernel;
+    constexpr bool FILTER = MODE == 1 || MODE == 2;
+    const bool fragment_order = rt.kernel == K::Qs16 || rt.kernel == K::Qr16 || rt.kernel == K::Rq16 || rt.kernel == K::Rk16;
+    return with_low<MODE>(c.h->meta.multiplier, [&](auto low) -> qamd_status {
+        constexpr bool LOW = decltype(low)::value;
+        if constexpr (FILTER) {
+            if (fragment_order) QAMD_TRY(launch_qs_bounds<LOW>(c));
         }
-        if (qr_selected(h, b, true)) return "u8_gemm_qr16_kernel";
-        return b->frag16 ? "u8_gemm_qs16_kernel" : "u8_gemm_qs_kernel";
-    }
-    if (rs_selected(h, b, true)) return "u8_gemm_rs_kernel";
-    if (pp_selected(h, b, true)) return "u8_gemm_pp_kernel";
-    return "u8_gemm_kernel";
-}
-
-template <int MODE>
-qamd_status launch_gemm(const qamd_u8 *h, const qamd_u8_query_batch *b, const uint8_t *codes,
-                        const float *v_offsets, uint64_t n_rows, float *out, uint64_t out_pitch,
-                        const BatchFilter &filt, hipStream_t s) {
-    if (n_rows == 0 || b->n_queries == 0) return QAMD_OK;
-    // q_pad is a multiple of 256 and the row padding of every store covers a 256-row tile.
-    if (qs_selected(h, b, MODE != 0)) return launch_gemm_qs<MODE>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-    if (rs_selected(h, b, MODE != 0)) return launch_gemm_rs<MODE>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-    if (pp_selected(h, b, MODE != 0)) return launch_gemm_pp<MODE>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-    if (b->n_queries > 128) {
-        static const char *cfg = dev_env("QAMD_GEMM_CFG");
-        if (cfg && cfg[0] == '3')  // two 4-wave workgroups per CU (61 KiB LDS each), 128 q x 256 rows
-            return launch_gemm_cfg<MODE, 128, 256, 2, 2, 64>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-        if (cfg && cfg[0] == '4')  // same, 256 q x 128 rows
-            return launch_gemm_cfg<MODE, 256, 128, 2, 2, 64>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-        if (cfg && cfg[0] == '5')  // one wave per SIMD, 128 x 128 outputs per wave (256 accumulator registers)
-            return launch_gemm_cfg<MODE, 256, 256, 2, 2, 128>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-        return launch_gemm_cfg<MODE, 256, 256, 2, 4, 128>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
-    }
-    return launch_gemm_cfg<MODE, 128, 128, 2, 2, 128>(h, b, codes, v_offsets, n_rows, out, out_pitch, filt, s);
+        switch (rt.kernel) {
+            case K::Qs16:
+                switch (rt.jt * 10 + rt.it) {
+                    case 82: return launch_gemm_qs16<MODE, LOW, 8, 2>(c);
+                    case 84: return launch_gemm_qs16<MODE, LOW, 8, 4>(c);
+                    case 62: return launch_gemm_qs16<MODE, LOW, 6, 2>(c);
+                    case 64: return launch_gemm_qs16<MODE, LOW, 6, 4>(c);
+                }
+                break;
+            case K::Qr16:
+                switch (rt.nsteps) {
+                    case 4: return launch_gemm_qr16<MODE, LOW, 4>(c);
+                    case 6: return launch_gemm_qr16<MODE, LOW, 6>(c);
+                    case 8: return launch_gemm_qr16<MODE, LOW, 8>(c);
+                    case 12: return launch_gemm_qr16<MODE, LOW, 12>(c);
+                    case 16: return launch_gemm_qr16<MODE, LOW, 16>(c);
+                }
+                break;
+            case K::Rq16:
+                if constexpr (FILTER) {
+                    switch (rt.nsteps) {
+                        case 4: return launch_gemm_rq<MODE, LOW, 4, 0>(c, rt.rq);
+                        case 6: return launch_gemm_rq<MODE, LOW, 6, 0>(c, rt.rq);
+                        case 8: return launch_gemm_rq<MODE, LOW, 8, 0>(c, rt.rq);
+                        case 12: return launch_gemm_rq<MODE, LOW, 12, 0>(c, rt.rq);
+                    }
+                }
+                break;
+            case K::Rk16:
+                if constexpr (FILTER) {
+                    switch (rt.nt_tiles) {
+                        case 8: return launch_gemm_rq<MODE, LOW, 12, 8>(c, rt.rq);
+                        case 10: return launch_gemm_rq<MODE, LOW, 12, 10>(c, rt.rq);
+                        case 12: return launch_gemm_rq<MODE, LOW, 12, 12>(c, rt.rq);
+                    }
+                }
+                break;
+            case K::Rs:
+                if constexpr (MODE != 3) {
+                    switch (rt.mi * 2 + (rt.nt ? 1 : 0)) {
+                        case 9: return launch_gemm_rs<MODE, LOW, 4, true>(c);
+                        case 8: return launch_gemm_rs<MODE, LOW, 4, false>(c);
+                        case 5: return launch_gemm_rs<MODE, LOW, 2, true>(c);
+                        case 4: return launch_gemm_rs<MODE, LOW, 2, false>(c);
+                        case 3: return launch_gemm_rs<MODE, LOW, 1, true>(c);
+                        case 2: return launch_gemm_rs<MODE, LOW, 1, false>(c);
+                    }
+                }
+                break;
+            case K::Pp:
+                if constexpr (MODE != 3) {
+                    if (rt.mi == 2 && rt.mj == 4) return launch_gemm_pp<MODE, LOW, 2, 4>(c);
+                    if (rt.mi == 4 && rt.mj == 2) return launch_gemm_pp<MODE, LOW, 4, 2>(c);
+                }
+                break;
+            case K::Gemm:
+                if constexpr (MODE != 3) {
+                    if (rt.tile == 128) return launch_gemm_cfg<MODE, 128, 128, 2, 2, 128>(c);
+                    if (rt.tile == 256) return launch_gemm_cfg<MODE, 256, 256, 2, 4, 128>(c);
+                }
+                break;
+        }
+        return fail(QAMD_ERR_ARGUMENTS, "no %s of this shape for GEMM mode %d", rt.name, MODE);
+    });
 }
 
 // The pivot sample of a store, gathered once per handle: sample row j is store row hash(j) whatever
@@ -2914,17 +2328,12 @@ qamd_status qamd_u8_encode_query_batch(const qamd_u8 *h, const float *queries, u
         }
         QAMD_TRY(u8_encode_queries_device(h, qd, n_queries, qdim, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), s));
         const uint32_t nkb = (uint32_t)((ad + 127) / 128);
-        if (nkb <= 12) {  // rows the query-streaming kernel can hold: the codes again, in MFMA fragment order
+        if (nkb <= 12) {  // rows the query-streaming kernels can hold: the codes again, in MFMA fragment order
             const size_t frag_bytes = (size_t)(q_pad / 32) * nkb * 4096;
             if (b->frag.bytes < frag_bytes) QAMD_TRY(b->frag.alloc(frag_bytes));
             b->frag_nkb = nkb;
-            b->frag16 = qs16_wanted(nkb);
-            if (b->frag16)
-                hipLaunchKernelGGL(swizzle_queries16_kernel, dim3((unsigned)std::min<uint64_t>(2048, (frag_bytes / 16 + 255) / 256)),
-                                   dim3(256), 0, s, b->codes.as<uint8_t>(), (uint32_t)b->pitch, (uint32_t)q_pad, nkb, b->frag.as<uint4>());
-            else
-                hipLaunchKernelGGL(swizzle_queries_kernel, dim3((unsigned)std::min<uint64_t>(2048, (frag_bytes / 16 + 255) / 256)),
-                                   dim3(256), 0, s, b->codes.as<uint8_t>(), (uint32_t)b->pitch, (uint32_t)q_pad, nkb, b->frag.as<uint4>());
+            hipLaunchKernelGGL(swizzle_queries16_kernel, dim3((unsigned)std::min<uint64_t>(2048, (frag_bytes / 16 + 255) / 256)),
+                               dim3(256), 0, s, b->codes.as<uint8_t>(), (uint32_t)b->pitch, (uint32_t)q_pad, nkb, b->frag.as<uint4>());
             QAMD_HIP(hipGetLastError());
         } else {
             b->frag_nkb = 0;
@@ -2967,17 +2376,18 @@ qamd_status qamd_u8_score_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, 
         out_dev = tmp.as<float>();
     }
     const uint32_t width = u8_multi_width(h);
+    const U8GemmRoute route = gemm_route(h, b, U8GemmPass::Score, h->count);
     // (from three queries on the row-streaming MFMA kernel streams the rows as fast and does not slow down per query)
     // Lane mode 1 (Dot, L2): the matrix cores sum exactly, so every query takes the lane-order scan (width 0).
     if (h->meta.vector_parameters.distance_type == QAMD_L1 || u8_lane_order(h) ||
-        (width && b->n_queries >= 2 && b->n_queries <= width && (b->n_queries == 2 || !rs_selected(h, b, false)))) {
+        (width && b->n_queries >= 2 && b->n_queries <= width && (b->n_queries == 2 || !route.rs_ok))) {
         // sum |q - v| is not a contraction (no MFMA form), and for a handful of queries the vector-ALU
         // multi-query scan streams the rows faster than the matrix-core kernel's LDS-DMA path
         QAMD_TRY(u8_score_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)b->n_queries,
                                       out_dev, s));
     } else {
-        QAMD_TRY(launch_gemm<0>(h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), h->count, out_dev, h->count,
-                                BatchFilter{}, s));
+        QAMD_TRY(launch_gemm<0>(route, {h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), h->count, out_dev, h->count,
+                                        BatchFilter{}, s}));
     }
     if (out_mem == QAMD_MEM_HOST) QAMD_TRY(copy_out(out, QAMD_MEM_HOST, out_dev, total * 4, s));
     return QAMD_OK;
@@ -2995,7 +2405,9 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
     if (u8_lane_order(h))  // lane mode 1 (Dot, L2): per-query lane-order scans, never the exact-sum matrix cores
         return u8_topk_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)Q, k, largest,
                                    out_ids, out_scores, out_mem, s);
-    if (n > (2u << 20) && (l1 || (Q <= u8_multi_width(h) && Q >= 2 && (Q == 2 || !rs_selected(h, b, true)))))
+    // The route of the filter pass over the store: everything below reads it (and the sample pass its own).
+    const U8GemmRoute filter_route = gemm_route(h, b, U8GemmPass::Filter, n);
+    if (n > (2u << 20) && (l1 || (Q <= u8_multi_width(h) && Q >= 2 && (Q == 2 || !filter_route.rs_ok))))
         // L1 has no matrix form; and two queries (one pass of the vector-ALU multi-query scan) stream the
         // rows at the single-query scan's rate with less overhead around it than the matrix-core pass (from
         // three queries on the row-streaming kernel wins: 1.26 against 1.31-1.39 ms per 10M x 768).  Per-query sample + pivot, ONE filtering pass per group of queries, one
@@ -3039,13 +2451,11 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
         const uint64_t ad = h->meta.actual_dim;
         // ONE stream-ordered allocation for all scratch of the call, carved up below: hipFreeAsync
         // costs ~65 us per buffer on this runtime, and ten buffers were a third of a small batch's time.
-        const bool qs = qs_selected(h, b, true);
-        const bool rs = !qs && rs_selected(h, b, true);
-        const bool pp = qs || rs || pp_selected(h, b, true);  // all three append to wave-private lists
+        const bool pp = filter_route.wave_lists;  // every kernel but u8_gemm_kernel appends to wave-private lists
         uint32_t n_lists = 0, wave_cap = 0;
         if (pp) {
             // wave-private lists: 4x the expected appends per wave (about `target`..2*target per query)
-            n_lists = gemm_launches(h, b, rs, qs) * pp_waves_per_launch();
+            n_lists = filter_route.list_launches * pp_waves_per_launch();
             const double per_wave = 2.0 * target * (double)Q / (double)n_lists;
             wave_cap = (uint32_t)std::min<double>(1u << 20, std::max<double>(1024.0, 4.0 * per_wave));
         }
@@ -3067,7 +2477,9 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
         const bool cached = S <= rows_all && sample_store(h, rows_all, s, &s_codes, &s_offs) == QAMD_OK;
         const size_t o_codes = reserve(cached ? 16 : (uint64_t)(S + 512) * ad);  // + one (largest) tile of zero rows
         const size_t o_offs = reserve(cached ? 16 : (uint64_t)(S + 512) * 4);
-        const size_t o_scores = reserve(qs ? Q * ((uint64_t)S / 64 + 2) * 4 : Q * (uint64_t)S * 4);  // sample scores, or block bests
+        const U8GemmRoute sample_route = gemm_route(h, b, U8GemmPass::Sample, S);
+        const uint32_t rows_per_block = sample_route.sample_block_rows;
+        const size_t o_scores = reserve(rows_per_block ? Q * ((uint64_t)S / 64 + 2) * 4 : Q * (uint64_t)S * 4);  // sample scores, or block bests
         const size_t o_cand = reserve(Q * (uint64_t)kBatchCap * 8);
         const size_t o_status = reserve((Q + 1) * 4);  // per-query status, then the wave-list overflow flag
         const size_t o_bounds = reserve(b->q_pad * 4);
@@ -3098,20 +2510,20 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
             s_codes = g_codes;
             s_offs = g_offs;
         }
-        if (qs) {
-            // the query-streaming kernel hands back the best sample score of every (query, 128- or 96-row
+        if (rows_per_block) {
+            // the query-streaming kernel hands back the best sample score of every (query, 64-, 128- or 96-row
             // block) instead of the Q x S score matrix (0.64 GB written and read back at 1024 queries and
             // 10M rows); the pivot is the r-th best of those: the r best sample rows of a query share a
             // block with probability ~ r^2 / (2 blocks), and a pivot that is a little off only moves the
             // candidate count (the filter pass, not the pivot, decides what is in the result)
-            const uint32_t rows_per_block = qr_selected(h, b, true) ? 64 : (b->frag16 ? b->frag_nkb <= 8 : b->frag_nkb <= 9) ? 128 : 96, s_blocks = (S + rows_per_block - 1) / rows_per_block;
+            const uint32_t s_blocks = (S + rows_per_block - 1) / rows_per_block;
             BatchFilter fs{};
             fs.largest = largest;
-            QAMD_TRY(launch_gemm_qs<3>(h, b, s_codes, s_offs, S, s_scores, s_blocks, fs, s));
+            QAMD_TRY(launch_gemm<3>(sample_route, {h, b, s_codes, s_offs, S, s_scores, s_blocks, fs, s}));
             hipLaunchKernelGGL(batch_pivot_kernel, dim3((unsigned)b->q_pad), dim3(1024), 0, s, s_scores, s_blocks,
                                (uint64_t)s_blocks, r, largest, (uint32_t)Q, pivots, counters);
         } else {
-            QAMD_TRY(launch_gemm<0>(h, b, s_codes, s_offs, S, s_scores, S, BatchFilter{}, s));
+            QAMD_TRY(launch_gemm<0>(sample_route, {h, b, s_codes, s_offs, S, s_scores, S, BatchFilter{}, s}));
             hipLaunchKernelGGL(batch_pivot_kernel, dim3((unsigned)b->q_pad), dim3(1024), 0, s, s_scores, S, (uint64_t)S, r,
                                largest, (uint32_t)Q, pivots, counters);
         }
@@ -3127,9 +2539,9 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
             f.wave_counts = wave_counts;
         }
         if (largest)
-            QAMD_TRY(launch_gemm<1>(h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s));
+            QAMD_TRY(launch_gemm<1>(filter_route, {h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
         else
-            QAMD_TRY(launch_gemm<2>(h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s));
+            QAMD_TRY(launch_gemm<2>(filter_route, {h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
         if (pp && Q <= 4096)
             hipLaunchKernelGGL(wave_scatter_grouped_kernel, dim3(std::min<uint32_t>(n_lists, 128)), dim3(1024), (size_t)Q * 8, s,
                                wave_cand, wave_counts, f.wave_cap, n_lists, (uint32_t)Q, counters, cand, overflow_dev);
@@ -3155,8 +2567,7 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
             overflow = back[Q];
         }
         if (pp && overflow) std::fill(status.begin(), status.end(), 1u);  // a wave list overflowed: redo all exactly
-        static const bool debug_topk = dev_env("QAMD_DEBUG_TOPK") != nullptr;
-        if (debug_topk) {
+        if (dev_switches().debug_topk) {
             std::vector<uint32_t> cnt(b->q_pad * kCounterStride);
             (void)hipMemcpy(cnt.data(), counters, cnt.size() * 4, hipMemcpyDeviceToHost);
             uint32_t mx = 0, mn = ~0u, redo = 0;
@@ -3169,7 +2580,7 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
                 redo += status[q];
             }
             fprintf(stderr, "[qamd topk_batch] Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, filter %s, %u queries redone\n",
-                    (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx, filter_kernel_name(h, b), redo);
+                    (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx, filter_route.name, redo);
         }
     }
     // Queries not served by the fused pass (small stores, overflowed lists): exact single-query path.

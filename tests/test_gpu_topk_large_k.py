@@ -9,7 +9,7 @@ A batch is checked query by query against the oracle, not against the single-que
 The route of each case is named next to it, with the dispatch condition that sends it there:
   csrc/topk.hip        fused_policy (fused: n >= 32768 and r <= 64), fused_topk, fused_topk_batch (small stores: n <= 2M, k <= 64)
   csrc/u8_batch.hip    qamd_u8_topk_batch (lane mode 1 / vector-ALU scans / matrix cores; fused: n >= 32768 and r <= 64),
-                       rs_selected / qs_selected / pp_selected
+                       u8_gemm_route() (csrc/u8_gemm_route.hpp)
   csrc/bin.hip         qamd_bin_topk_batch (matrix cores: 3 or 5+ queries on 512/768/1024/1536-bit rows, 12+ elsewhere,
                        n >= 32768), bin_topk_batch_mfma (r <= 64)
   csrc/pq.hip          qamd_pq_topk_batch (side by side: n >= 2^20 and 256 CUs), launch_fast (sliced rows: m > 144)
@@ -147,10 +147,10 @@ def test_single_query_pq_fused_on_a_million_rows(qo):
 
 # ------------------------------------------------------------------ u8 topk_batch
 @pytest.mark.parametrize("n,dim,nq,route", [
-    (140_001, 96, 20, "rs"),       # u8_gemm_rs_kernel: one 32-query tile fits in LDS (rs_selected: tiles == 1)
+    (140_001, 96, 20, "rs"),       # u8_gemm_rs_kernel: one 32-query tile fits in LDS (one tile)
     (140_001, 96, 385, "qs"),      # query-streaming kernel: 131072+ rows, frag_nkb = 1 <= 3 -> qs_min_queries = 385
     (100_003, 1168, 65, "pp"),     # ping-pong kernel: only 64-query tiles fit 1168-byte rows and two would be needed (not rs),
-                                   # 65 < qs_min_queries(10) = 129 (not qs); pp_selected: 128 < actual_dim <= 32768
+                                   # 65 < qs_min_queries(10) = 129 (not qs); ping-pong: 128 < actual_dim <= 32768
 ])
 def test_u8_batch_matrix_core_routes(n, dim, nq, route, qo):
     """The fused matrix-core path (n >= 32768, r <= 64 at every k: r = 63 at k = 1024 on 100_003 rows): k <= 64

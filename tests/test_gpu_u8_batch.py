@@ -272,19 +272,21 @@ def test_handful_of_queries_take_the_vector_alu_multi_query_scan(dim, nq, dist, 
                           f"query {qi} vs oracle")
 
 
-# ---- row-streaming kernel (u8_gemm_rs_kernel): batches whose query tile fits in LDS
+# ---- row-streaming kernel (u8_gemm_rs_kernel): batches whose query tile fits in LDS (a 128-query tile holds rows of up to 896
+# code bytes, a 64-query tile 1920, a 32-query tile 3968), and what takes over where it does not.  The kernel named on each
+# line is the one u8_gemm_route() returns for the shape (tests/cpu/u8_gemm_route_dump.cpp prints the table).
 @pytest.mark.parametrize("n,dim,nq", [
     (70_001, 96, 20),      # one K-block per row (odd count), 32-query tile
-    (50_000, 200, 64),     # row length 208: the last K-block runs into the next row (query image is zero there)
+    (50_000, 200, 64),     # row length 208: the last K-block runs into the next row (query image is zero there); 64-query tile
     (300_017, 384, 100),   # three K-blocks, 128-query tile, more than one row tile per workgroup, ragged tail
-    (140_000, 512, 300),   # three 128-query tiles per row lane (the last one partly filled)
-    (20_000, 1000, 128),   # eight K-blocks, row length not a multiple of 128
-    (9_000, 1152, 128),    # the longest row a 128-query tile holds
-    (9_000, 1168, 128),    # one step longer: only 64-query tiles fit, two would be needed -> ping-pong kernel
-    (6_000, 2304, 33),     # the longest row a 64-query tile holds
-    (3_000, 4600, 32),     # 32-query tile
-    (3_000, 4600, 40),     # ... two of them would be needed -> ping-pong kernel
-    (2_000, 4700, 8),      # no tile fits: the ping-pong kernel serves it
+    (140_000, 512, 300),   # a store of 131072+ rows: scores from u8_gemm_qs16_kernel, the filter pass from u8_gemm_rq16_kernel (two groups)
+    (20_000, 1000, 128),   # eight K-blocks, row length not a multiple of 128: only 64-query tiles fit, two would be needed -> ping-pong kernel
+    (9_000, 1152, 128),    # ... the same
+    (9_000, 1168, 128),    # ... the same, one step longer
+    (6_000, 2304, 33),     # only a 32-query tile fits, two would be needed -> ping-pong kernel
+    (3_000, 4600, 32),     # no tile fits (4608 code bytes): the ping-pong kernel serves it
+    (3_000, 4600, 40),
+    (2_000, 4700, 8),
 ])
 def test_row_streaming_kernel_shapes(n, dim, nq, qo):
     rng = np.random.default_rng(n + dim + nq)
@@ -325,15 +327,32 @@ def test_row_streaming_kernel_pivot_sample_is_cached_and_stable():
             assert np.array_equal(ids[qi], wi) and np.array_equal(sc[qi].view(np.uint32), ws.view(np.uint32)), (nq, qi)
 
 
-def test_row_streaming_kernel_forced_for_many_query_tiles():
-    """QAMD_GEMM_CFG=r (developer switch, read once per process) sends every batch whose tile fits
-    through the row-streaming kernel: several query tiles per row lane, rows shared through the XCD's L2."""
+def _run_with_forced_family(family, kernel, body, timeout):
+    """Runs `body` (Python source; `qa`, `np`, `D` are imported) in a fresh process on the developer library with
+    QAMD_GEMM_CFG=<family> (developer switches are read once per process, and only by that library) and QAMD_DEBUG_TOPK=1,
+    and asserts that it ends with "ok" and that every topk_batch call's debug line names `kernel` as its filter pass.
+    Returns the number of such lines."""
     import os
     import subprocess
     import sys
-    code = r'''
-import numpy as np, quantization_amd as qa
-D = qa.DistanceType
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dev_lib = os.path.join(root, "tools", "lib", "libquantization_amd_dev.so")
+    if not os.path.exists(dev_lib):
+        pytest.skip("developer build not present")
+    code = "import sys\nsys.path.insert(0, %r)\nimport numpy as np, quantization_amd as qa\nD = qa.DistanceType\n" % root + body
+    env = dict(os.environ, QAMD_LIB_PATH=dev_lib, QAMD_GEMM_CFG=family, QAMD_DEBUG_TOPK="1")
+    res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=timeout, env=env, cwd=root)
+    assert res.returncode == 0 and res.stdout.strip().endswith("ok"), (res.stdout + res.stderr)[-3000:]
+    lines = [ln for ln in res.stderr.splitlines() if ln.startswith("[qamd topk_batch]")]
+    wrong = [ln for ln in lines if f"filter {kernel}," not in ln]
+    assert lines and not wrong, (len(lines), wrong[:5])
+    return len(lines)
+
+
+def test_row_streaming_kernel_forced_for_many_query_tiles():
+    """QAMD_GEMM_CFG=r (developer switch, read once per process by the developer library) sends every batch whose tile fits
+    through the row-streaming kernel: several query tiles per row lane, rows shared through the XCD's L2."""
+    body = r'''
 rng = np.random.default_rng(5)
 n, dim, nq = 200_003, 192, 300
 data = rng.random((n, dim), dtype=np.float32)
@@ -349,44 +368,44 @@ for qi in (0, 127, 128, 255, 256, 299):
     assert np.array_equal(got[qi].view(np.uint32), enc.score_all(q).view(np.uint32)), qi
 print("ok")
 '''
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, QAMD_GEMM_CFG="r", PYTHONPATH=root)
-    res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env, cwd=root)
-    assert res.returncode == 0 and "ok" in res.stdout, (res.stdout + res.stderr)[-2000:]
+    assert _run_with_forced_family("r", "u8_gemm_rs_kernel", body, 600) == 1
 
 
-# ---- query-streaming kernels (u8_gemm_qs16_kernel on 16x16x64 MFMAs for rows of up to 1024 code bytes, u8_gemm_qs_kernel
-# on 32x32x32 up to 1536): from 385 / 257 / 129 queries (rows of up to 384 / 768 / 1536 bytes: qs_min_queries); batches of up
-# to 256 queries in chunks of 32 per wave
+# ---- query-streaming kernel (u8_gemm_qs16_kernel on 16x16x64 MFMAs: 128 resident rows of up to 1024 code bytes, 96 of up to
+# 1536): from 385 / 257 / 129 queries (rows of up to 384 / 768 / 1536 bytes: qs_min_queries); batches of up to 256 queries in
+# chunks of 32 per wave.  A store of fewer than 131072 rows of up to 1152 bytes never reaches it, nor the queries-in-registers
+# kernel (the row-streaming tiles split such a store evenly): the kernel named on each line is the one u8_gemm_route() returns
+# for the shape, and test_query_streaming_kernel_forced / test_queries_in_registers_kernel_forced below run the shapes the
+# guard keeps away through the kernels they were written for.
 @pytest.mark.parametrize("n,dim,nq", [
-    (140_000, 768, 300),    # stores of 131072+ rows take the query-streaming kernels by default: 5 chunks of 64 queries
-    (140_000, 1536, 200),   # ... 96 resident rows, chunks of 32 queries
-    (33_000, 768, 130),     # queries in registers (u8_gemm_qr16_kernel): 129 .. 256 queries on rows of 256 / 512 / 768 / 1024 bytes
-    (70_001, 768, 256),     # ... all eight waves busy, several row blocks per workgroup, ragged tail
-    (33_000, 512, 200),
-    (33_000, 256, 129),
-    (33_000, 384, 250),     # 384-byte rows on a 512-byte LDS pitch (places past the row's last chunk are filler)
-    (33_000, 1024, 70),     # (from 65 queries on 1024-byte rows)
-    (33_000, 1024, 129),
-    (33_000, 1024, 256),    # 8 chunks of 32: the last batch size of the small-chunk form
-    (33_000, 1536, 200),    # 96 resident rows, chunks of 32
-    (33_000, 768, 257),     # the first batch size past two row-streaming tiles: 5 query chunks, three waves idle
-    (33_000, 768, 256),     # ... and the last one the row-streaming kernel keeps
-    (33_000, 768, 385),
-    (33_000, 512, 390),
-    (33_000, 1024, 700),    # the longest row of the 16x16x64 form: 16 k-steps (one left over after five turns of three)
-    (33_000, 896, 300),     # 14 k-steps (two left over)
-    (33_000, 640, 300),     # rows that end inside a 256-byte LDS group (pitch 768)
-    (33_000, 256, 400),     # 4 k-steps
-    (33_000, 1040, 300),    # one step longer: the 32x32x32 form
-    (40_003, 96, 704),      # one K-block per row (odd count)
-    (35_000, 200, 800),     # row length 208, two K-blocks; 13 query chunks over 8 waves
-    (70_001, 384, 1024),    # three K-blocks (odd), two chunks per wave, several row blocks per workgroup, ragged tail
-    (33_000, 1152, 720),    # the longest row a 128-row resident block holds
-    (33_000, 1168, 720),    # one step longer: 96 resident rows
+    (140_000, 768, 300),    # a store of 131072+ rows: scores and block bests from qs16 (5 chunks of 64 queries), the filter pass from u8_gemm_rk16_kernel
+    (140_000, 1536, 200),   # ... qs16 for every pass: 96 resident rows, chunks of 32 queries
+    (33_000, 768, 130),     # small store: two 128-query tiles of the row-streaming kernel
+    (70_001, 768, 256),     # ... the same, several row tiles per workgroup, ragged tail
+    (33_000, 512, 200),     # ... the same
+    (33_000, 256, 129),     # ... the same
+    (33_000, 384, 250),     # ... the same
+    (33_000, 1024, 70),     # small store, 1024-byte rows (64-query tiles, two would be needed): ping-pong kernel, 128-query tile
+    (33_000, 1024, 129),    # ... ping-pong kernel, 256-query tile
+    (33_000, 1024, 256),    # ... the same
+    (33_000, 1536, 200),    # rows past 1152 bytes take qs16 on a small store as well: 96 resident rows, chunks of 32
+    (33_000, 768, 257),     # small store: three row-streaming tiles
+    (33_000, 768, 256),     # ... two
+    (33_000, 768, 385),     # ... four
+    (33_000, 512, 390),     # ... four
+    (33_000, 1024, 700),    # small store, 1024-byte rows: ping-pong kernel
+    (33_000, 896, 300),     # small store: three row-streaming tiles (the longest row a 128-query tile holds)
+    (33_000, 640, 300),     # ... three
+    (33_000, 256, 400),     # ... four
+    (33_000, 1040, 300),    # small store: ping-pong kernel
+    (40_003, 96, 704),      # small store: six row-streaming tiles, one K-block per row (odd count)
+    (35_000, 200, 800),     # ... seven, row length 208, two K-blocks
+    (70_001, 384, 1024),    # ... eight, three K-blocks (odd), several row tiles per workgroup, ragged tail
+    (33_000, 1152, 720),    # small store, the longest row the guard covers: ping-pong kernel
+    (33_000, 1168, 720),    # one step longer: qs16, 96 resident rows, 12 query chunks of 64 over 8 waves
     (40_000, 1536, 800),    # the longest row 96 resident rows hold
     (33_000, 1552, 704),    # one step longer: ping-pong kernel
-    (34_000, 128, 2100),    # two launch slices of 2048 queries
+    (34_000, 128, 2100),    # small store: 17 row-streaming tiles
 ])
 def test_query_streaming_kernel_shapes(n, dim, nq, qo):
     rng = np.random.default_rng(n + dim + nq)
@@ -411,6 +430,59 @@ def test_query_streaming_kernel_shapes(n, dim, nq, qo):
             wi, ws = enc.topk(qobj, 30, largest=largest)
             assert np.array_equal(ids[qi], wi), (qi, n, dim)
             assert np.array_equal(sc[qi].view(np.uint32), ws.view(np.uint32)), (qi, n, dim)
+
+
+# The top-k half of test_query_streaming_kernel_shapes for a list of shapes, as source for _run_with_forced_family.
+_FORCED_TOPK_BODY = r'''
+for n, dim, nq in SHAPES:
+    rng = np.random.default_rng(n + dim + nq)
+    data = rng.random((n, dim), dtype=np.float32)
+    queries = rng.random((nq, dim), dtype=np.float32)
+    for dist, invert, largest in ((D.Dot, False, True), (D.L2, True, False)):
+        enc = qa.EncodedVectorsU8.encode(data, qa.VectorParameters(dim, n, dist, invert))
+        ids, sc = enc.topk_batch(enc.encode_query_batch(queries), 30, largest=largest)
+        qobj = None
+        for qi in sorted({0, 1, 63, 64, nq // 3, nq // 2, nq - 65, nq - 2, nq - 1}):
+            qobj = enc.encode_query(queries[qi], reuse=qobj)
+            wi, ws = enc.topk(qobj, 30, largest=largest)
+            assert np.array_equal(ids[qi], wi), (qi, n, dim, nq)
+            assert np.array_equal(sc[qi].view(np.uint32), ws.view(np.uint32)), (qi, n, dim, nq)
+print("ok")
+'''
+
+
+def test_query_streaming_kernel_forced():
+    # QAMD_GEMM_CFG=q: the shapes of test_query_streaming_kernel_shapes that a store of 33 000 rows sends to the row-streaming
+    # and ping-pong kernels, through u8_gemm_qs16_kernel (sample pass: block bests, filter pass: wave lists) - ids and score
+    # bits against the single-query topk at the same picks.
+    shapes = [
+        (33_000, 1024, 700),    # the longest row of the 128-row block: 16 k-steps (one left over after five turns of three)
+        (33_000, 896, 300),     # 14 k-steps (two left over)
+        (33_000, 640, 300),     # rows that end inside a 256-byte LDS group (pitch 768)
+        (33_000, 256, 400),     # 4 k-steps
+        (40_003, 96, 704),      # one K-block per row (odd count)
+        (35_000, 200, 800),     # row length 208, two K-blocks; 13 query chunks over 8 waves
+        (33_000, 1152, 720),    # nine K-blocks: 96 resident rows
+        (33_000, 1168, 720),    # ten (row length not a multiple of 128)
+        (33_000, 1024, 256),    # 8 chunks of 32: the last batch size of the small-chunk form
+        (34_000, 128, 2100),    # two launch slices of 2048 queries
+    ]
+    body = f"SHAPES = {shapes!r}\n" + _FORCED_TOPK_BODY
+    assert _run_with_forced_family("q", "u8_gemm_qs16_kernel", body, 900) == 2 * len(shapes)
+
+
+def test_queries_in_registers_kernel_forced():
+    # QAMD_GEMM_CFG=g: u8_gemm_qr16_kernel on the row lengths it exists for (4 / 6 / 8 / 12 / 16 k-steps), at the batch
+    # sizes of test_query_streaming_kernel_shapes that a store of 33 000 rows keeps away from it.
+    shapes = [
+        (33_000, 768, 130),     # 129 .. 256 queries on rows of 256 / 384 / 512 / 768 / 1024 bytes: five waves busy
+        (33_000, 512, 200),
+        (33_000, 256, 129),
+        (33_000, 384, 250),     # 384-byte rows on a 512-byte LDS pitch (places past the row's last chunk are filler)
+        (33_000, 1024, 70),     # (from 65 queries on 1024-byte rows)
+    ]
+    body = f"SHAPES = {shapes!r}\n" + _FORCED_TOPK_BODY
+    assert _run_with_forced_family("g", "u8_gemm_qr16_kernel", body, 900) == 2 * len(shapes)
 
 
 # ---- queries resident, rows streamed (late round 4): the filter pass of 129+ queries on stores of 131072+ rows of 256 / 384 / 512 /

@@ -1,4 +1,4 @@
-"""In-kernel timeline of u8_gemm_kernel (developer tool): phase durations in shader cycles.
+"""In-kernel timeline of the u8 multi-query kernels (developer tool): phase durations in shader cycles.
 
 Usage: python tools/gemm_timeline.py [NQ] [N] [DIM]
 """
@@ -59,8 +59,8 @@ if os.environ.get("QAMD_GEMM_CFG", "p")[0] in "qgs":  # g: the queries-in-regist
         print(f"  {nm:46s} {x.mean():12.0f}  {100 * x.mean() / tot:5.1f} %   (p10 {np.percentile(x, 10):10.0f}, p90 {np.percentile(x, 90):10.0f})")
     n_blocks = (n + blk_rows - 1) // blk_rows / n_wg
     chunk_q = int(os.environ.get("CHUNK_Q", 64))
-    mf = n_blocks * ((nq + chunk_q - 1) // chunk_q) / WAVES * ((enc.metadata["actual_dim"] + 127) // 128) * (blk_rows // 4) * chunk_q / 64
-    print(f"  MFMAs per wave {mf:.0f}: K loop cycles per MFMA {blk[:, :, 3].mean() / mf:.1f} (two waves share a SIMD: 64 nominal)")
+    mf = n_blocks * ((nq + chunk_q - 1) // chunk_q) / WAVES * ((enc.metadata["actual_dim"] + 127) // 128) * (blk_rows // 2) * chunk_q / 64  # v_mfma_i32_16x16x64_i8
+    print(f"  MFMAs per wave {mf:.0f}: K loop cycles per MFMA {blk[:, :, 3].mean() / mf:.1f} (32 nominal for 16x16x64 i8; two waves share a SIMD)")
     if blk[:, :, 7].mean() > 0:
         print(f"  kernel {blk[:, :, 7].mean() / 100:.1f} us per wave (10 ns ticks), shader clock while it ran "
               f"{blk[:, :, 6].mean() / blk[:, :, 7].mean() * 100:.0f} MHz")
