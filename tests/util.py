@@ -212,3 +212,226 @@ def scalar_scores(rows_u8, codes, dim: int, bits: int, dist, invert) -> np.ndarr
     """float32[n]: the score of every stored bit row against the codes of a scalar query (scalar_xor, then
     scalar_metric).  bits = 1 with codes (q_i > 0) is the binary score."""
     return scalar_metric(scalar_xor(rows_u8, codes, dim, bits), dim, bits, dist, invert)
+
+
+# ------------------------------------------------------------------ product quantizer: inputs at the encoder's edges
+# tests/test_pq_encode_model.py checks these generators against the oracle without a GPU; the GPU files rely on them.
+def assert_bits_equal_nan(got, want, what=""):
+    """assert_bits_equal, except that where `want` is a NaN any NaN is accepted (an x86 NaN and a GPU default NaN
+    differ in the sign bit).  Everywhere else the bits must match, the sign of zero included."""
+    g = np.ascontiguousarray(got, dtype=np.float32).ravel()
+    w = np.ascontiguousarray(want, dtype=np.float32).ravel()
+    assert g.shape == w.shape, f"{what}: {g.shape} values, want {w.shape}"
+    bad = np.flatnonzero(np.where(np.isnan(w), ~np.isnan(g), bits(g) != bits(w)))
+    if bad.size:
+        i = int(bad[0])
+        raise AssertionError(f"{what}: {bad.size}/{g.size} values differ; first at {i}: got {g[i]!r} "
+                             f"({bits(g)[i]:#010x}) want {w[i]!r} ({bits(w)[i]:#010x})")
+
+
+def pq_sq_dist(a, k, mode: str = "plain") -> np.ndarray:
+    """Squared distance over the last axis of f32 arrays, one f32 rounding per operation.
+    "plain": t = a - k, d += t * t in index order (encode_vector, encoded_vectors_pq.rs:237-265);
+    "rev":   the same with the sum taken from the last index down;
+    "fma":   the contracted chain d = f32(f64(t) * f64(t) + f64(d)) (the f64 product of two f32 is exact)."""
+    f32 = np.float32
+    with np.errstate(all="ignore"):
+        t = (np.asarray(a, dtype=f32) - np.asarray(k, dtype=f32)).astype(f32)
+        d = np.zeros(t.shape[:-1], dtype=f32)
+        js = range(t.shape[-1])
+        for j in (reversed(js) if mode == "rev" else js):
+            tj = t[..., j]
+            if mode == "fma":
+                d = (tj.astype(np.float64) * tj.astype(np.float64) + d.astype(np.float64)).astype(f32)
+            else:
+                d = (d + (tj * tj).astype(f32)).astype(f32)
+    return d
+
+
+PQ_TIE_SLOTS = 128
+
+
+def pq_tie_slot_indices(chunk: int, slot: int) -> tuple[int, int]:
+    """The two centroid indices (low, high) of near-tie slot `slot` of chunk `chunk` of a pq_near_tie_case.  Even
+    chunks: both halves of pair `slot`, (2s, 2s + 1) - with (0, 1) and (254, 255).  Odd chunks: across two pairs,
+    (2s + 1, 2s + 2) - every boundary between two pipeline steps of pq_encode_cs_kernel is among them, whatever its
+    pairs per step (31 | 32, 63 | 64, ...) - and slot 127 takes what is left, (0, 255)."""
+    if chunk % 2 == 0:
+        return 2 * slot, 2 * slot + 1
+    return (2 * slot + 1, 2 * slot + 2) if slot < PQ_TIE_SLOTS - 1 else (0, 255)
+
+
+class PqTieCase:
+    """data [n, m * length], cen [256, m * length]; per cell (chunk, slot): lo / hi centroid indices, the two plain
+    f32 distances d_lo / d_hi of the cell's row vector, and what marks it: `contract` (the contracted chain picks the
+    other centroid), `order` (the reversed sum does), `tie` (d_lo == d_hi exactly).  slot[r, c]: the cell of row r."""
+
+
+def pq_near_tie_case(length: int, n: int, seed: int, m: int = 8, first: int = 0) -> PqTieCase:
+    """Rows that sit between two centroids at (nearly) the same f32 distance, for chunks of `length` values.
+
+    Candidate: a row vector a near its slot's centre, centroid k1 = fl(a + o) with a small offset o, t = fl(a - k1) and
+    k2 = fl(a + rot1(t)): the mirrored centroid with its differences rotated by one place, so that the two distances
+    are the same squares summed in a different order, up to the roundings.  The rotation is fixed (a random permutation
+    gave 0.7 % contraction-sensitive candidates at length 4 against 7 - 10 %).  The slot's centre is up to 64 in
+    coordinate 0, where an f32 has a 2^-17 grid: the row and k1 are drawn on that grid in coordinate 0 and in the last
+    coordinate (whose difference the rotation moves to coordinate 0), so that no rounding there pulls the two distances
+    apart by more than the few ulps the test is about (13-bit differences: their squares still round); the
+    coordinates between are full-precision values around zero.  Every fourth candidate is an exact
+    mirror on a 2^-12 grid instead (k1 = a - t, k2 = a + t, nothing rounds): a tie under every evaluation order.  Odd
+    candidates put k1 at the higher index of their slot, even ones at the lower.  Slot s lives around (s - 64, 0, 0,
+    ...) and nothing of it strays more than 3/16 from there in any coordinate, so every other slot's centroids are far.
+    Per slot the candidates on which the contracted chain, the reversed sum, or an exact tie decide the code come first,
+    in turn, starting with kind `first` (0, 1, 2 in that order), and chunk c takes the slot's c-th: nearly every cell of
+    the case is one of them, and a case of one chunk holds 128 cells of kind `first`."""
+    f32 = np.float32
+    S = PQ_TIE_SLOTS
+    per = max(160, m + 32)
+    rng = np.random.default_rng([seed, length])
+    centre = np.zeros((S, 1, length), dtype=f32)
+    centre[:, 0, 0] = np.arange(S, dtype=f32) - 64
+    u = (rng.random((S, per, length), dtype=f32) * 2 - 1) * f32(2.0 ** -4)
+    o = (rng.random((S, per, length), dtype=f32) * 2 - 1) * f32(2.0 ** -4)
+    for j in {0, length - 1}:  # (see the docstring: these two coordinates stay on a 2^-17 grid)
+        u[..., j] = np.round(u[..., j] * f32(2.0 ** 17)) * f32(2.0 ** -17)
+        o[..., j] = np.round(o[..., j] * f32(2.0 ** 17)) * f32(2.0 ** -17)
+    a = (centre + u).astype(f32)
+    k1 = (a + o).astype(f32)
+    t = (a - k1).astype(f32)
+    k2 = (a + np.roll(t, 1, axis=-1)).astype(f32)
+    mirror = np.arange(per) % 4 == 3
+    ug = np.round(u[:, mirror] * 4096) / 4096
+    tg = np.round(o[:, mirror] * 4096) / 4096
+    tg[..., 0] = np.where(np.all(tg == 0, axis=-1), f32(2.0 ** -12), tg[..., 0])
+    a[:, mirror] = centre + ug
+    k1[:, mirror] = a[:, mirror] - tg
+    k2[:, mirror] = a[:, mirror] + tg
+    swap = (np.arange(per) % 2 == 1)[None, :, None]
+    lo, hi = np.where(swap, k2, k1), np.where(swap, k1, k2)
+    pick = {mode: pq_sq_dist(a, hi, mode) < pq_sq_dist(a, lo, mode) for mode in ("plain", "fma", "rev")}
+    d_lo, d_hi = pq_sq_dist(a, lo), pq_sq_dist(a, hi)
+    contract, order, tie = pick["fma"] != pick["plain"], pick["rev"] != pick["plain"], d_lo == d_hi
+    # rank the slot's candidates: the three kinds in turn (starting with kind `first`), then the rest
+    cat = np.where(contract, 0, np.where(order, 1, np.where(tie, 2, 3)))
+    prio = np.arange(per)[None, :] + per * (mirror[None, :] & (cat == 2))  # drawn ties before the mirrored ones
+    by_cat = np.argsort(cat * (4 * per) + prio, axis=1, kind="stable")
+    rank = np.empty_like(by_cat)
+    np.put_along_axis(rank, by_cat, np.broadcast_to(np.arange(per)[None, :], by_cat.shape), axis=1)
+    starts = np.cumsum(np.stack([(cat == k).sum(axis=1) for k in range(4)], axis=1), axis=1) - \
+        np.stack([(cat == k).sum(axis=1) for k in range(4)], axis=1)
+    pos = rank - np.take_along_axis(starts, cat, axis=1)
+    key = np.where(cat < 3, pos * 3 + (cat - first) % 3, 3 * per + prio)
+    pick_i = np.argsort(key, axis=1, kind="stable")[:, :m]  # [S, m]: chunk c takes the slot's c-th
+    case = PqTieCase()
+    case.length, case.m, case.n = length, m, n
+    case.cen = np.zeros((256, m * length), dtype=f32)
+    ss = np.arange(S)
+    idx = np.array([[pq_tie_slot_indices(c, sl) for sl in range(S)] for c in range(2)])  # [layout, S, (lo, hi)]
+    case.lo = idx[np.arange(m) % 2, :, 0]
+    case.hi = idx[np.arange(m) % 2, :, 1]
+    for c in range(m):
+        cols = slice(c * length, (c + 1) * length)
+        case.cen[case.lo[c], cols] = lo[ss, pick_i[:, c]]
+        case.cen[case.hi[c], cols] = hi[ss, pick_i[:, c]]
+    gather = lambda x: np.ascontiguousarray(np.swapaxes(x[ss[:, None], pick_i], 0, 1))  # [S, per, ...] -> [m, S, ...]
+    cell_a = gather(a)
+    case.d_lo, case.d_hi = gather(d_lo), gather(d_hi)
+    case.contract, case.order, case.tie = gather(contract), gather(order), gather(tie)
+    case.slot = (np.arange(n)[:, None] + 37 * np.arange(m)[None, :]) % S
+    case.data = np.ascontiguousarray(cell_a[np.arange(m)[None, :], case.slot].reshape(n, m * length))
+    # the code of the plain chain with the strict '<' walk: the lower index unless the higher one is strictly nearer
+    case.want = np.where(case.d_hi < case.d_lo, case.hi, case.lo)[np.arange(m)[None, :], case.slot].astype(np.uint8)
+    return case
+
+
+def pq_near_tie_table(dim: int, chunk: int, n: int, seed: int, first: int = 0):
+    """(data [n, dim], cen [256, dim], cases) for any (dim, chunk): one pq_near_tie_case per distinct chunk length
+    (the ragged last chunk has its own), pasted side by side.  cases: [(first chunk, PqTieCase)]."""
+    m = (dim + chunk - 1) // chunk
+    last = dim - (m - 1) * chunk
+    groups = [(0, m, chunk)] if last == chunk else ([(0, m - 1, chunk)] if m > 1 else []) + [(m - 1, 1, last)]
+    data = np.zeros((n, dim), dtype=np.float32)
+    cen = np.zeros((256, dim), dtype=np.float32)
+    cases = []
+    for c0, mg, length in groups:
+        case = pq_near_tie_case(length, n, seed, m=mg, first=first)
+        data[:, c0 * chunk:c0 * chunk + mg * length] = case.data
+        cen[:, c0 * chunk:c0 * chunk + mg * length] = case.cen
+        cases.append((c0, case))
+    return data, cen, cases
+
+
+# What tests/test_gpu_pq_encode_edges.py encodes: (chunk, dim) of every pq_encode_cs_kernel<chunk> instantiation, the
+# shapes of pq_encode_kernel ((40, 33): the chunk is larger than the dim), and row counts that are no multiple of the
+# 256-row workgroup.  Table v of a shape has PQ_EDGE_ROW_COUNTS[v] rows and starts its slots with kind v, so that a
+# shape of ONE chunk still sees 128 cells of each kind; tests/test_pq_encode_model.py asserts the counts on these tables.
+PQ_EDGE_CS_SHAPES = [(1, 8), (2, 16), (4, 32), (8, 64), (16, 128), (32, 256)]
+PQ_EDGE_GENERIC_SHAPES = [(3, 10), (7, 100), (20, 50), (24, 24), (40, 33)]
+PQ_EDGE_ROW_COUNTS = (257, 1000, 2051)
+_edge_tables = {}
+
+
+def pq_edge_tie_tables(chunk: int, dim: int):
+    """[(data [n, dim], cen [256, dim], cases)] for n in PQ_EDGE_ROW_COUNTS; built once per shape."""
+    if (chunk, dim) not in _edge_tables:
+        _edge_tables[chunk, dim] = [pq_near_tie_table(dim, chunk, n, seed=chunk * 1000 + dim, first=v)
+                                    for v, n in enumerate(PQ_EDGE_ROW_COUNTS)]
+    return _edge_tables[chunk, dim]
+
+
+def describe_code_mismatches(got, want, data, cen, chunk: int, limit: int = 5) -> str:
+    """(row, chunk, got, want, the two plain f32 distances) of the first few differing codes."""
+    bad = np.argwhere(np.asarray(got) != np.asarray(want))
+    out = [f"{len(bad)} of {np.asarray(want).size} codes differ"]
+    for r, c in bad[:limit]:
+        cols = slice(c * chunk, min((c + 1) * chunk, data.shape[1]))
+        g, w = int(got[r, c]), int(want[r, c])
+        out.append(f"row {r} chunk {c}: got {g} (d = {pq_sq_dist(data[r, cols], cen[g, cols])!r}) "
+                   f"want {w} (d = {pq_sq_dist(data[r, cols], cen[w, cols])!r})")
+    return "; ".join(out)
+
+
+# Scalar values of the special centroids: centroid k holds PQ_SPECIAL_CENTROIDS[k] in every coordinate (but see k = 2);
+# 12 .. 254 are 2.0, 2.5, ... and 255 is 1000.25.
+PQ_SPECIAL_CENTROIDS = {0: 0.0, 1: 1.0, 2: np.nan, 3: np.inf, 4: -np.inf, 5: 3e38, 6: -3e38, 7: 1e-40, 8: 2e-40,
+                        9: -0.0, 10: -1e-40, 11: 3e-20, 255: 1000.25}
+# (name, the row's value in every coordinate, its code in every chunk by the reference's walk: d starts at f32::MAX,
+# index order, strict '<')
+PQ_SPECIAL_ROWS = [
+    ("one", 1.0, 1),            # d = 0 at centroid 1; centroid 2 (a NaN in its first coordinate) is skipped: NaN < x is false
+    ("plus_inf", np.inf, 0),    # every distance is +inf or NaN (inf - inf): nothing is < f32::MAX, the code stays 0
+    ("minus_inf", -np.inf, 0),
+    ("big", 3e38, 5),           # 0 at centroid 5; against -3e38 the difference itself overflows
+    ("minus_big", -3e38, 6),
+    ("overflow", -2.5e38, 0),   # the nearest centroid, -3e38, is 5e37 away: its square overflows like all others
+    ("subnormal", 1e-40, 0),    # differences to 0.0, +-1e-40, 2e-40 are subnormal, their squares 0: a tie at 0, index order
+    ("minus_subnormal", -1e-40, 0),
+    ("minus_zero", -0.0, 0),    # distance +0.0 to centroid 0; centroid 9 (-0.0) ties and comes later
+    ("tiny", 2e-20, 11),        # squares 4e-40 (centroids 0, 7 .. 10) against 1e-40 (centroid 11): subnormal, not flushed
+    ("last", 1000.25, 255),     # equal to centroid 255: distance 0 at the last index
+    ("midway", 0.5, 0),         # 0.25 per coordinate to both 0.0 and 1.0: the exact tie goes to the lower index
+    ("nearer_one", 0.625, 1),
+]
+
+
+def pq_special_case(dim: int, chunk: int):
+    """(data [14, dim], cen [256, dim], want u8 [14, m]): rows and centroids with NaN, infinities, values whose
+    differences overflow, subnormals and negative zero, and the codes the reference's walk gives them (stated in
+    PQ_SPECIAL_ROWS, not computed).  Row 0 is all 1.0 with a NaN in its first coordinate: chunk 0 has only NaN
+    distances and keeps code 0, the other chunks are 1.  Centroid 2 is 1.0 with a NaN in the first coordinate of every
+    chunk (a NaN that enters the sum first and stays)."""
+    f32 = np.float32
+    m = (dim + chunk - 1) // chunk
+    vals = np.array([PQ_SPECIAL_CENTROIDS.get(k, 2.0 + 0.5 * (k - 12)) for k in range(256)], dtype=f32)
+    cen = np.repeat(vals[:, None], dim, axis=1)
+    cen[2, :] = 1.0
+    cen[2, ::chunk] = np.nan
+    data = np.zeros((1 + len(PQ_SPECIAL_ROWS), dim), dtype=f32)
+    want = np.zeros((data.shape[0], m), dtype=np.uint8)
+    data[0, :] = 1.0
+    data[0, 0] = np.nan
+    want[0, 1:] = 1
+    for i, (_name, value, code) in enumerate(PQ_SPECIAL_ROWS, start=1):
+        data[i, :] = f32(value)
+        want[i, :] = code
+    return data, np.ascontiguousarray(cen), want
