@@ -230,7 +230,14 @@ QAMD_API qamd_status qamd_u8_score_ids(const qamd_u8 *h, const qamd_u8_query *q,
                                        float *out, qamd_mem out_mem, void *stream);
 /* Fused scan + selection (demos/src/ann_benchmark_data.rs:151-167 keeps the best 30 in a
  * heap).  largest != 0 keeps the k largest scores, else the k smallest; ties break to the
- * lower index; results are sorted best-first.  k <= 1024. */
+ * lower index; results are sorted best-first.  k <= 1024.
+ * Order of scores (every *_topk, *_topk_batch, *_sharded_topk*, *_topk_rescored, qamd_f32_rerank*, qamd_topk_scores
+ * and qamd_topk_merge): rows are ranked by one total order on the f32 bit pattern of the score, not by a float
+ * compare.  Ascending it reads -NaN < -inf < negative finite < -0 < +0 < positive finite < +inf < +NaN; among NaNs of
+ * one sign a larger payload lies further out.  `largest` takes that order from the top, smallest-first from the
+ * bottom: a +NaN score is the best row of a `largest` call and the worst of a smallest-first call, a -NaN score the
+ * reverse.  Equal bit patterns go to the lower id.  A returned score is the row's own score bits: a NaN keeps its
+ * sign and payload.  (The padding of a short list, id 0xFFFFFFFF with -inf / +inf, comes after every row.) */
 QAMD_API qamd_status qamd_u8_topk(const qamd_u8 *h, const qamd_u8_query *q, uint32_t k,
                                   int largest, uint32_t *out_ids, float *out_scores,
                                   qamd_mem out_mem, void *stream);
@@ -782,7 +789,10 @@ QAMD_API qamd_status qamd_f32_score_ids_batch(const qamd_f32 *h, const float *qu
  * (largest) / +inf when fewer than k ids are given.  k <= 1024, n_ids <= 8192 (the capacity of
  * the candidate sort).  Id 0xFFFFFFFF, the padding *_topk writes, is skipped; any other host id
  * >= count returns QAMD_ERR_OUT_OF_RANGE, such a device id takes part with a NaN score.  An id
- * listed twice is returned twice.  With every buffer in device memory the call only enqueues;
+ * listed twice is returned twice.  Order of scores: as stated at qamd_u8_topk - one total order on the f32 bit
+ * pattern (ascending -NaN < -inf < negative finite < -0 < +0 < positive finite < +inf < +NaN, equal bit patterns to
+ * the lower id); exact scores of rows that hold inf or NaN, and the NaN of an id past the end, are ranked by it like
+ * any other, and a returned score is the row's own score bits.  With every buffer in device memory the call only enqueues;
  * host outputs cost one download and synchronise `stream`. */
 QAMD_API qamd_status qamd_f32_rerank(const qamd_f32 *h, const float *query, uint64_t qdim,
                                      qamd_mem query_mem, const uint32_t *ids, uint32_t n_ids,

@@ -33,7 +33,23 @@ struct BatchFilter {
     uint32_t wave_base;     // first wave list of this launch
     uint32_t query_base;    // global index of the launch's query 0
     int *query_bounds;      // [Qpad] scratch for the query-streaming kernel's integer bounds
+    uint32_t n_queries;     // queries of the whole batch: a padding query (global index >= n_queries) never appends
 };
+
+// The exact epilogue's filter: "key <= pivot key" (topk_ordered_bits), decided by ONE float compare wherever the
+// compare is ordered - only the rare passing element pays for the key - and by the keys themselves where it is not (a
+// NaN score or a NaN pivot).  So a NaN on the winning side of the order passes (+NaN in a `largest` query) and one
+// on the losing side does not, and the number of appended candidates stays what the emit kernels take it for: rows
+// at least as good as the pivot (batch_emit_kernel's `pushed < k` under-flow test).  The one superset left is -0
+// against a +0 pivot.  Compared directly, not through the sign of a difference: inf - inf is NaN, and a row as
+// good as an infinite pivot is a tie like any other.  Padding rows and padding queries carry infinite `never` offsets
+// and pivots, which tie with an infinite counterpart here: the caller keeps them out by index (row < n_rows,
+// query < n_queries).
+template <bool LARGEST> __device__ __forceinline__ bool batch_filter_pass(float sc, float pv) {
+    if (LARGEST ? sc >= pv : sc <= pv) return true;
+    if (sc == sc && pv == pv) return false;
+    return topk_ordered_bits(sc, LARGEST) <= topk_ordered_bits(pv, LARGEST);
+}
 
 
 // Integer pre-filter (MODE 1/2).  The filter "score at least as good as the pivot" is, in exact
@@ -58,6 +74,38 @@ __device__ __forceinline__ int pp_bound(float num /* pivot - q_off, or -v_off */
     if (!(t == t)) t = all;  // NaN: let the exact epilogue decide
     t = fminf(fmaxf(t, -kPpLim), kPpLim);
     return (int)t;
+}
+// Non-finite inputs, walked (the bound may only ever be too permissive; `all` is the bound every s passes):
+//   num NaN (a NaN pivot or q_off; pivot and q_off infinite alike: inf - inf)   x = NaN -> t = NaN -> all
+//   num +-inf, m finite     x = +-inf and slack = +inf: x -+ slack is +-inf on the permissive side (clamped to all) or
+//                           inf - inf = NaN -> all
+//   v_off NaN or +-inf      never gets here: pp_row_bound gives such a row a bound that beats every query's
+//   m NaN                   x = NaN -> all
+//   m = +-inf, num finite   x = +-0, slack = 1: a finite bound near 0 - but then every score is m * s = +-inf (s > 0) or
+//                           NaN (s = 0), so is every sample score and with them the pivot: the query's bound is `all`
+//                           (pp_query_bound) and cancels nothing.  (Such a store has no pre-filter anyway: u8_gemm_route
+//                           sends multiplier 0 and inf to u8_gemm_kernel.)
+//   m = 0                   x = +-inf or 0 / 0, slack = inf or NaN: as above, all
+// The bound of a ROW.  A row whose offset is NaN or infinite has a NaN or infinite score whatever s is, and must reach
+// the exact epilogue against EVERY query bound, a clamped "nothing passes" (+-kPpLim) included: its bound is 2 kPpLim on
+// the permissive side, which no query bound cancels (s - B_q - B_row stays inside an int: |B_q| <= 2^29, s < 2^29).
+template <bool LOW>
+__device__ __forceinline__ int pp_row_bound(float v_off, float m) {
+    if (!(fabsf(v_off) < __builtin_huge_valf())) return LOW ? 2 * (int)kPpLim : -2 * (int)kPpLim;
+    return pp_bound<LOW>(-v_off, fabsf(v_off), m, 0);
+}
+// The bound of a QUERY.  A padding query (not `real`) gets the bound nothing passes.  An infinite pivot gets `all`: at
+// the worst end of the order everything passes anyway, and at the best end (more sampled rows than the pivot rank
+// score +-inf) the rows that tie with it or beat it - the same infinity, a NaN of that sign - must reach the exact
+// epilogue, and a row's permissive bound cannot be relied on to cancel a query's "never" (LOW: the sum would have
+// to exceed every s).  Such a query pays the exact epilogue for every row and, with that many ties, usually ends
+// in the exact single-query path.
+template <bool LOW>
+__device__ __forceinline__ int pp_query_bound(float pivot, float q_off, float m, bool real) {
+    int b = pp_bound<LOW>(pivot - q_off, fabsf(pivot) + fabsf(q_off), m, 1);  // LOW: s <= T  <=>  s - (T + 1) < 0
+    if (__builtin_isinf(pivot)) b = LOW ? (int)kPpLim : -(int)kPpLim;
+    if (!real) b = LOW ? -(int)kPpLim : (int)kPpLim;
+    return b;
 }
 
 

@@ -193,8 +193,9 @@ __global__ __launch_bounds__(64 * WQ * WR) void u8_gemm_kernel(const uint8_t *__
     // + 4*(lane >> 5): query index on the registers, store row on the lanes (coalesced writes).
     // The tile's per-query constants (offset, pivot key) go through LDS once: read per element
     // from global memory they were 256 loads per lane and dominated the whole kernel.
-    // The filter is a FLOAT compare against the pivot score (a superset of "key <= pivot key":
-    // only the rare passing element pays for the key, the atomic and the store) — the first
+    // The filter is a FLOAT compare against the pivot score (batch_filter_pass: "key <= pivot key", by the
+    // keys only where a NaN makes the compare unordered; only the rare passing element pays for the key,
+    // the atomic and the store) — the first
     // version built the ordered key of all 128 results per lane and spent more instructions in
     // this epilogue (5000) than in the MFMA loop.
     float *q_off_s = reinterpret_cast<float *>(lds_raw);  // [TQ_]   (operand buffers are dead now)
@@ -232,18 +233,16 @@ __global__ __launch_bounds__(64 * WQ * WR) void u8_gemm_kernel(const uint8_t *__
                 } else {
                     const float4 pv4 = *reinterpret_cast<const float4 *>(pivot_s + ql);
                     const float pv[4] = {pv4.x, pv4.y, pv4.z, pv4.w};
-                    // margin d >= 0  <=>  the score is at least as good as the pivot (the sign of an
-                    // f32 difference is exact).  One max over the four margins and one compare decide
-                    // for the whole group; NaN scores never pass (v_max drops them).
-                    float d[4];
+                    // batch_filter_pass per element, one branch for the group.  Padding rows and queries are kept out
+                    // by index: their infinite `never` offset / pivot ties with an infinite counterpart.
+                    bool pass[4];
 #pragma unroll
-                    for (int e = 0; e < 4; e++) d[e] = LARGEST ? sc[e] - pv[e] : pv[e] - sc[e];
-                    const float dmax = fmaxf(fmaxf(d[0], d[1]), fmaxf(d[2], d[3]));
-                    if (dmax >= 0.0f) {
+                    for (int e = 0; e < 4; e++) pass[e] = batch_filter_pass<LARGEST>(sc[e], pv[e]);
+                    if (row_ok && (pass[0] | pass[1] | pass[2] | pass[3])) {
 #pragma unroll
                         for (int e = 0; e < 4; e++) {
-                            if (d[e] >= 0.0f) {
-                                const uint32_t q = q0 + ql + e;
+                            const uint32_t q = q0 + ql + e;
+                            if (pass[e] && q < n_queries) {
                                 const uint32_t key = topk_ordered_bits(sc[e], LARGEST);
                                 const uint32_t pos = atomicAdd(filt.counters + (uint64_t)q * kCounterStride, 1u);
                                 if (pos < kBatchCap)
@@ -403,10 +402,7 @@ __global__ __launch_bounds__(512) void u8_gemm_pp_kernel(const uint8_t *__restri
         if (MODE != 0) {
             const float pv = filt.pivot_scores[q0 + t];
             pivot_s[t] = pv;
-            int bq = pp_bound<LOW>(pv - qo, fabsf(pv) + fabsf(qo), multiplier, 1);  // LOW: s <= T  <=>  s - (T+1) < 0
-            if (__builtin_isinf(pv))  // padding query (nothing may pass) or a degenerate pivot (everything does)
-                bq = ((pv > 0.0f) == LARGEST) == LOW ? -(int)kPpLim : (int)kPpLim;
-            bq_s[t] = bq;
+            bq_s[t] = pp_query_bound<LOW>(pv, qo, multiplier, q0 + t < n_queries);
         }
     }
     __syncthreads();
@@ -520,7 +516,7 @@ __global__ __launch_bounds__(512) void u8_gemm_pp_kernel(const uint8_t *__restri
         const uint64_t row_a = (uint64_t)tile * TR + wr * RW + r;
 #pragma unroll
         for (int jj = 0; jj < MJ; jj++)
-            br[jj] = row_a + 32 * jj < n_rows ? pp_bound<LOW>(-vo_cur[jj], fabsf(vo_cur[jj]), multiplier, 0)
+            br[jj] = row_a + 32 * jj < n_rows ? pp_row_bound<LOW>(vo_cur[jj], multiplier)
                                               : (LOW ? -(int)kPpLim : (int)kPpLim);
 #pragma unroll
         for (int i = 0; i < MI; i++)
@@ -645,8 +641,7 @@ __global__ __launch_bounds__(512) void u8_gemm_pp_kernel(const uint8_t *__restri
                             for (int e = 0; e < 4; e++) {
                                 const int s_int = av[e] + bq4[e] + brj;  // the plain integer dot product
                                 const float sc = (multiplier * (float)s_int + qo[e]) + v_off;
-                                const float d = LARGEST ? sc - pv[e] : pv[e] - sc;
-                                if (d >= 0.0f) {
+                                if (batch_filter_pass<LARGEST>(sc, pv[e]) && row_ok && filt.query_base + q0_e + ql + e < filt.n_queries) {
                                     // wave-private list: an LDS counter, a fire-and-forget 16-byte store
                                     const uint32_t pos = atomicAdd(wcount_s, 1u);
                                     if (pos < filt.wave_cap)
@@ -738,9 +733,7 @@ __global__ __launch_bounds__(512) void u8_gemm_rs_kernel(const uint8_t *__restri
         if (MODE != 0) {
             const float pv = filt.pivot_scores[q0 + t];
             pivot_s[t] = pv;
-            int bq = pp_bound<LOW>(pv - qo, fabsf(pv) + fabsf(qo), multiplier, 1);
-            if (__builtin_isinf(pv)) bq = ((pv > 0.0f) == LARGEST) == LOW ? -(int)kPpLim : (int)kPpLim;
-            bq_s[t] = bq;
+            bq_s[t] = pp_query_bound<LOW>(pv, qo, multiplier, q0 + t < n_queries);
         }
     }
     {  // the query tile, zero beyond the batch's pitch
@@ -848,7 +841,7 @@ __global__ __launch_bounds__(512) void u8_gemm_rs_kernel(const uint8_t *__restri
             }
 #pragma unroll
             for (int jj = 0; jj < MJ; jj++)
-                br[jj] = row_a + 32 * jj < n_rows ? pp_bound<LOW>(-vo_cur[jj], fabsf(vo_cur[jj]), multiplier, 0)
+                br[jj] = row_a + 32 * jj < n_rows ? pp_row_bound<LOW>(vo_cur[jj], multiplier)
                                                   : (LOW ? -(int)kPpLim : (int)kPpLim);
 #pragma unroll
             for (int i = 0; i < MI; i++)
@@ -928,8 +921,7 @@ __global__ __launch_bounds__(512) void u8_gemm_rs_kernel(const uint8_t *__restri
                             for (int e = 0; e < 4; e++) {
                                 const int s_int = av[e] + bq4[e] + brj;  // the plain integer dot product
                                 const float sc = (multiplier * (float)s_int + qo[e]) + v_off;
-                                const float d = LARGEST ? sc - pv[e] : pv[e] - sc;
-                                if (d >= 0.0f) {
+                                if (batch_filter_pass<LARGEST>(sc, pv[e]) && row_ok && filt.query_base + q0_e + ql + e < filt.n_queries) {
                                     const uint32_t pos = atomicAdd(wcount_s, 1u);
                                     if (pos < filt.wave_cap)
                                         wave_list[pos] = make_uint4(topk_ordered_bits(sc, LARGEST), (uint32_t)row,
@@ -961,13 +953,10 @@ __global__ __launch_bounds__(512) void u8_gemm_rs_kernel(const uint8_t *__restri
 // per-query integer bounds come precomputed from qs_bounds_kernel.
 template <bool LOW>
 __global__ __launch_bounds__(256) void qs_bounds_kernel(const float *__restrict__ pivots, const float *__restrict__ q_offsets,
-                                                       float multiplier, int largest, uint32_t q_pad, int *__restrict__ bq) {
+                                                       float multiplier, uint32_t n_queries, uint32_t q_pad, int *__restrict__ bq) {
     const uint32_t q = blockIdx.x * 256 + threadIdx.x;
     if (q >= q_pad) return;
-    const float pv = pivots[q], qo = q_offsets[q];
-    int b = pp_bound<LOW>(pv - qo, fabsf(pv) + fabsf(qo), multiplier, 1);
-    if (__builtin_isinf(pv)) b = ((pv > 0.0f) == (largest != 0)) == LOW ? -(int)kPpLim : (int)kPpLim;
-    bq[q] = b;
+    bq[q] = pp_query_bound<LOW>(pivots[q], q_offsets[q], multiplier, q < n_queries);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1122,7 +1111,7 @@ __global__ __launch_bounds__(512) void u8_gemm_qs16_kernel(const uint8_t *__rest
             const bool ok = row0 + t < n_rows;
             const float vo = vo_pf;
             voff_s[t] = ok ? vo : never;
-            if (FILTER) br_s[t] = ok ? pp_bound<LOW>(-vo, fabsf(vo), multiplier, 0) : (LOW ? -(int)kPpLim : (int)kPpLim);
+            if (FILTER) br_s[t] = ok ? pp_row_bound<LOW>(vo, multiplier) : (LOW ? -(int)kPpLim : (int)kPpLim);
         }
         __syncthreads();
         lap(1);
@@ -1286,8 +1275,7 @@ __global__ __launch_bounds__(512) void u8_gemm_qs16_kernel(const uint8_t *__rest
                                 for (int e = 0; e < 4; e++) {
                                     const int s_int = av[e] + bq4[e] + brj;  // the plain integer dot product
                                     const float sc = (multiplier * (float)s_int + qo[e]) + v_off;
-                                    const float d = LARGEST ? sc - pv[e] : pv[e] - sc;
-                                    if (d >= 0.0f) {
+                                    if (batch_filter_pass<LARGEST>(sc, pv[e]) && row_ok && filt.query_base + q + e < filt.n_queries) {
                                         const uint32_t pos = atomicAdd(wcount_s, 1u);
                                         if (pos < filt.wave_cap)
                                             wave_list[pos] = make_uint4(topk_ordered_bits(sc, LARGEST), (uint32_t)row,
@@ -1407,7 +1395,7 @@ __global__ __launch_bounds__(512) void u8_gemm_qr16_kernel(const uint8_t *__rest
             const bool ok = row0 + t < n_rows;
             const float vo = vo_pf;
             voff_s[par * QR_ROWS + t] = ok ? vo : never;
-            if (FILTER) br_s[par * QR_ROWS + t] = ok ? pp_bound<LOW>(-vo, fabsf(vo), multiplier, 0) : (LOW ? -(int)kPpLim : (int)kPpLim);
+            if (FILTER) br_s[par * QR_ROWS + t] = ok ? pp_row_bound<LOW>(vo, multiplier) : (LOW ? -(int)kPpLim : (int)kPpLim);
         }
     };
     const uint32_t first_blk = blockIdx.x < n_blocks ? blockIdx.x : 0u;
@@ -1569,8 +1557,7 @@ __global__ __launch_bounds__(512) void u8_gemm_qr16_kernel(const uint8_t *__rest
                                     for (int e = 0; e < 4; e++) {
                                         const int s_int = av[e] + bq4[it][e] + brj;  // the plain integer dot product
                                         const float sc = (multiplier * (float)s_int + qo[it][e]) + v_off;
-                                        const float d = LARGEST ? sc - pv[e] : pv[e] - sc;
-                                        if (d >= 0.0f) {
+                                        if (batch_filter_pass<LARGEST>(sc, pv[e]) && row_ok && filt.query_base + q + e < filt.n_queries) {
                                             const uint32_t pos = atomicAdd(wcount_s, 1u);
                                             if (pos < filt.wave_cap)
                                                 wave_list[pos] = make_uint4(topk_ordered_bits(sc, LARGEST), (uint32_t)row,
@@ -1678,7 +1665,7 @@ __global__ __launch_bounds__(512) void u8_gemm_rq16_kernel(const uint8_t *__rest
             for (int rt = 0; rt < RT; rt++) {
                 v_off[rt] = vo[rt];
                 const bool ok = row0 + rt * 16 + i16 < n_rows;
-                br[rt] = ok ? pp_bound<LOW>(-v_off[rt], fabsf(v_off[rt]), multiplier, 0) : (LOW ? -(int)kPpLim : (int)kPpLim);
+                br[rt] = ok ? pp_row_bound<LOW>(v_off[rt], multiplier) : (LOW ? -(int)kPpLim : (int)kPpLim);
             }
             for (uint32_t qt = 0; qt < my_tiles; qt += QP) {
                 v4i acc[QP][RT];
@@ -1729,8 +1716,7 @@ __global__ __launch_bounds__(512) void u8_gemm_rq16_kernel(const uint8_t *__rest
                                 for (int e = 0; e < 4; e++) {
                                     const int s_int = av[e] - nbq_s[ql + e] + br[rt];  // the plain integer dot product
                                     const float sc = (multiplier * (float)s_int + qo[e]) + v_off[rt];
-                                    const float d = LARGEST ? sc - pv[e] : pv[e] - sc;
-                                    if (d >= 0.0f) {
+                                    if (batch_filter_pass<LARGEST>(sc, pv[e]) && row < n_rows && filt.query_base + q + e < filt.n_queries) {
                                         const uint32_t pos = atomicAdd(wcount_s, 1u);
                                         if (pos < filt.wave_cap)
                                             wave_list[pos] = make_uint4(topk_ordered_bits(sc, LARGEST), (uint32_t)row, filt.query_base + q + e, 0u);
@@ -1840,7 +1826,7 @@ __global__ __launch_bounds__(512) void u8_gemm_rk16_kernel(const uint8_t *__rest
             for (int rt = 0; rt < RT; rt++) {
                 v_off[rt] = vo_cur[rt];
                 const bool ok = row0 + rt * 16 + i16 < n_rows;
-                br[rt] = ok ? pp_bound<LOW>(-v_off[rt], fabsf(v_off[rt]), multiplier, 0) : (LOW ? -(int)kPpLim : (int)kPpLim);
+                br[rt] = ok ? pp_row_bound<LOW>(v_off[rt], multiplier) : (LOW ? -(int)kPpLim : (int)kPpLim);
                 vo_nxt[rt] = v_offsets[(uint64_t)next * (16 * RT) + rt * 16 + i16];
             }
             lap(5);
@@ -1901,7 +1887,7 @@ __global__ __launch_bounds__(512) void u8_gemm_rk16_kernel(const uint8_t *__rest
                     for (int rt = 0; rt < RT; rt++) {
                         const int a0 = acc[q][rt][0], a1 = acc[q][rt][1], a2 = acc[q][rt][2], a3 = acc[q][rt][3];
                         const bool may_pass = LOW ? ((a0 | a1 | a2 | a3) < 0) : ((a0 & a1 & a2 & a3) >= 0);
-                        if (may_pass) {
+                        if (may_pass && (uint32_t)q < my_tiles) {  // (a padding tile's bound yields to a non-finite row's: pp_row_bound)
                             const uint32_t ql = 16u * q + 4u * g_e, qq = 16u * tile0 + ql;  // in the group / in the launch's batch
                             const uint64_t row = row0 + rt * 16 + i16;
                             const float4 pv4 = *reinterpret_cast<const float4 *>(filt.pivot_scores + qq);
@@ -1912,8 +1898,7 @@ __global__ __launch_bounds__(512) void u8_gemm_rk16_kernel(const uint8_t *__rest
                             for (int e = 0; e < 4; e++) {
                                 const int s_int = av[e] - nbq_s[ql + e] + br[rt];  // the plain integer dot product
                                 const float sc = (multiplier * (float)s_int + qo[e]) + v_off[rt];
-                                const float d = LARGEST ? sc - pv[e] : pv[e] - sc;
-                                if (d >= 0.0f) {
+                                if (batch_filter_pass<LARGEST>(sc, pv[e]) && row < n_rows && filt.query_base + qq + e < filt.n_queries) {
                                     const uint32_t pos = atomicAdd(wcount_s, 1u);
                                     if (pos < filt.wave_cap)
                                         wave_list[pos] = make_uint4(topk_ordered_bits(sc, LARGEST), (uint32_t)row, filt.query_base + qq + e, 0u);
@@ -2038,7 +2023,7 @@ qamd_status with_low(float multiplier, Fn &&fn) {
 template <bool LOW>
 qamd_status launch_qs_bounds(const GemmCall &c) {
     hipLaunchKernelGGL(qs_bounds_kernel<LOW>, dim3((unsigned)(c.b->q_pad / 256)), dim3(256), 0, c.s, c.filt.pivot_scores,
-                       c.b->offsets.as<float>(), c.h->meta.multiplier, c.filt.largest, (uint32_t)c.b->q_pad, c.filt.query_bounds);
+                       c.b->offsets.as<float>(), c.h->meta.multiplier, (uint32_t)c.b->n_queries, (uint32_t)c.b->q_pad, c.filt.query_bounds);
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
 }
@@ -2532,6 +2517,7 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
         f.counters = counters;
         f.candidates = cand;
         f.largest = largest;
+        f.n_queries = (uint32_t)Q;
         f.query_bounds = reinterpret_cast<int *>(base + o_bounds);
         if (pp) {
             f.wave_cap = wave_cap;

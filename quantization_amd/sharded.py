@@ -157,16 +157,27 @@ def assemble_global_scores(gathered, count: int, world: int):
     return np.concatenate(parts)
 
 
+def topk_order_keys(scores, largest: bool) -> np.ndarray:
+    """uint32 sort keys of f32 scores, smallest = best: the order-preserving key of csrc/topk_device.hpp
+    (topk_ordered_bits) on the bit pattern.  Ascending it reads -NaN < -inf < negative finite < -0 < +0 < positive
+    finite < +inf < +NaN; `largest` inverts it."""
+    u = np.ascontiguousarray(scores, dtype=np.float32).view(np.uint32).copy()
+    u ^= np.where(u >> 31 != 0, np.uint32(0xFFFFFFFF), np.uint32(0x80000000)).astype(np.uint32)
+    return ~u if largest else u
+
+
 def merge_topk(ids_per_rank, scores_per_rank, bases, k: int, largest: bool):
     """Merge per-shard top-k lists (local ids + shard base -> global ids) into the global top-k,
-    best first, ties to the lower global id — the same order a single-GPU topk returns.
+    best first, ties to the lower global id — the same order a single-GPU topk returns and the device merge
+    (`merge_topk_kernel`) uses: by topk_order_keys, then by id, so a NaN ranks by its sign (+NaN above +inf, -NaN below
+    -inf) and -0 below +0.  Returned scores are the lists' own bits.
     Inputs are numpy arrays [world, k]; ids 0xFFFFFFFF mark padding entries."""
     ids = np.asarray(ids_per_rank, dtype=np.uint32).astype(np.int64)
-    sc = np.asarray(scores_per_rank, dtype=np.float32)
+    sc = np.ascontiguousarray(scores_per_rank, dtype=np.float32)
     valid = ids != 0xFFFFFFFF
     gids = ids + np.asarray(bases, dtype=np.int64)[:, None]
     gids, sc = gids[valid], sc[valid]
-    order = np.lexsort((gids, -sc if largest else sc))[:k]
+    order = np.lexsort((gids, topk_order_keys(sc, largest)))[:k]
     out_ids = np.full(k, 0xFFFFFFFF, dtype=np.uint32)
     out_sc = np.full(k, -np.inf if largest else np.inf, dtype=np.float32)
     out_ids[: order.size] = gids[order].astype(np.uint32)
@@ -263,20 +274,10 @@ class ShardedTopKBatch:
         host = self.all.numpy()
         ids = host[:, 0].view(np.uint32)   # [world, nq, k]
         sc = host[:, 1].view(np.float32)
-        # all queries at once: [nq, world*k] candidates per query, one lexsort along the rows
-        valid = (ids != 0xFFFFFFFF).transpose(1, 0, 2).reshape(self.nq, -1)
-        gids = (ids.astype(np.int64) + np.asarray(self.bases, dtype=np.int64)[:, None, None])
-        gids = gids.transpose(1, 0, 2).reshape(self.nq, -1)
-        s2 = sc.transpose(1, 0, 2).reshape(self.nq, -1)
-        key = np.where(valid, -s2 if largest else s2, np.inf).astype(np.float64)  # padding sorts last
-        gkey = np.where(valid, gids, np.iinfo(np.int64).max)
-        order = np.lexsort((gkey, key), axis=1)[:, : self.k]
-        out_ids = np.take_along_axis(gids, order, axis=1).astype(np.uint32)
-        out_sc = np.take_along_axis(s2, order, axis=1).astype(np.float32)
-        ok = np.take_along_axis(valid, order, axis=1)
-        out_ids[~ok] = 0xFFFFFFFF
-        out_sc[~ok] = -np.inf if largest else np.inf
-        return out_ids, out_sc
+        merged = [merge_topk(ids[:, q], sc[:, q], self.bases, self.k, largest) for q in range(self.nq)]  # one rule
+        if not merged:
+            return np.zeros((0, self.k), dtype=np.uint32), np.zeros((0, self.k), dtype=np.float32)
+        return np.stack([m[0] for m in merged]), np.stack([m[1] for m in merged])
 
 
 # ----------------------------------------------------------------------------------------------- distributed encode

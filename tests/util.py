@@ -35,6 +35,50 @@ def topk_want(scores, k: int, largest: bool = True):
     return ids, sc
 
 
+def topk_order_keys(scores, largest: bool = True) -> np.ndarray:
+    """uint32 sort keys of f32 scores in the total order every top-k route uses on the bit pattern: ascending
+    -NaN < -inf < negative finite < -0 < +0 < positive finite < +inf < +NaN, inverted for `largest`; the smallest key is
+    the best row.  Among NaNs of one sign the payload counts like a magnitude."""
+    u = bits(scores).ravel().copy()
+    u ^= np.where(u >> 31 != 0, np.uint32(0xFFFFFFFF), np.uint32(0x80000000)).astype(np.uint32)
+    return ~u if largest else u
+
+
+def topk_total_order(scores, k: int, largest: bool = True):
+    """topk_want on the bit patterns instead of the float values: a stable sort on (topk_order_keys, row id), best first,
+    padded to k exactly as topk_want pads.  It states what topk_want cannot: where NaNs of either sign and payload rank,
+    and that -0 is below +0.  Returned scores are the rows' own bits.  Returns (ids u32[k], scores f32[k])."""
+    scores = np.ascontiguousarray(scores, dtype=np.float32).ravel()
+    n = scores.size
+    key = topk_order_keys(scores, largest)
+    cand = np.arange(n)
+    if 0 < k < n:  # only the rows whose key is at most the k-th smallest (ties included) need the stable sort
+        cand = np.flatnonzero(key <= np.partition(key, k - 1)[k - 1])
+    order = cand[np.argsort(key[cand], kind="stable")][: min(k, n)]
+    ids = np.full(k, 0xFFFFFFFF, dtype=np.uint32)
+    sc = np.full(k, -np.inf if largest else np.inf, dtype=np.float32)
+    ids[: order.size] = order
+    sc[: order.size] = scores[order]
+    return ids, sc
+
+
+# The u8 batch shapes of tests/test_gpu_topk_special_scores.py: (kernel family of the filter pass on 256 CUs, rows, dim,
+# queries), the smallest store that reaches each family.  Stores below 131072 rows of up to 896 code bytes take rs at every
+# batch size; from 131072 rows on: 16 .. 208 bytes qs16 from 385 queries; 256 bytes rq16 from 129; 768 bytes rk16 at
+# 129 .. 192 and qr16 at 193 .. 256; 1024-byte rows of a small store pp from 65 queries.  SPECIAL_U8_GEMM_SHAPE at
+# multiplier 0 or inf takes u8_gemm_kernel.  tests/test_topk_order_model.py checks all of this against u8_gemm_route().
+SPECIAL_U8_FAMILIES = [
+    ("rs", 33_000, 64, 5),
+    ("pp", 33_000, 1024, 70),
+    ("qs16", 131_079, 16, 385),
+    ("rq16", 131_079, 256, 129),
+    ("rk16", 131_079, 768, 129),
+    ("qr16", 131_079, 768, 193),
+]
+SPECIAL_U8_GEMM_SHAPE = (33_000, 64, 5)
+SPECIAL_U8_SHORT_ROW_BATCHES = [(2 ** 20 + 7, 32, 2), (2 ** 20 + 7, 32, 4)]  # rs: rows too short for the vector-ALU pass
+
+
 def have_gpu() -> bool:
     try:
         from quantization_amd import _lib
