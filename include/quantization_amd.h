@@ -326,6 +326,72 @@ QAMD_API qamd_status qamd_bin_save(const qamd_bin *h, const char *data_path, con
 QAMD_API qamd_status qamd_bin_load(const char *data_path, const char *meta_path,
                                    const qamd_vector_parameters *vp, qamd_bits_store store,
                                    qamd_bin **out);
+/* Two-bit rows: per dimension i two strict f32 compares against thresholds lo_i <= hi_i taken from the data.  The
+ * reference has NO counterpart (its snapshot predates upstream's two-bit encoding); DESIGN.md 3.2e is the specification.
+ *   - A row holds code_bits = 2 * dim bits in the one-bit layout (byte j / 8, bit j % 8): bit i = x_i > lo_i, bit
+ *     dim + i = x_i > hi_i - the second plane starts at bit dim, aligned or not.  NaN and -inf give (0,0), +inf (1,1); the
+ *     reachable codes (0,0), (1,0), (1,1) are levels 0, 1, 2 and their Hamming distance is the difference in level.  Row
+ *     bytes are qamd_bin_quantized_vector_size_enc = the one-bit size of a vector of code_bits dimensions; pad bits are 0.
+ *   - A score is calculate_metric (:237-252) on the xor-popcount of two such rows with code_bits in place of dim.  dim is
+ *     at most 2^23 (QAMD_ERR_ARGUMENTS beyond), so every score is an exact f32 integer.
+ *   - qamd_bin_encode_query / _encode_query_batch on a two-bit handle encode the query like a row (qdim must be the
+ *     handle's dim); every scoring call, every batch route and the rescored top-k then serve the store as they serve a
+ *     one-bit store of code_bits dimensions.  The vectors' dimension stays vp.dim: originals of a rescored top-k have dim.
+ *   - Statistics (bit-exact, independent of how a caller batches the rows): column i's rows are cut into blocks of 4096
+ *     by row index; within a block S = sum (double)x and Q = sum (double)x * (double)x accumulate in row order from +0.0
+ *     over the finite entries, n counts them; the block sums are added in block order.
+ *   - Thresholds (host, f64, single operations): mean = S / n, var = Q / n - mean * mean (both 0 for n = 0), var = 0
+ *     unless var > 0, sd = sqrt(var), lo = (float)(mean - t * sd), hi = (float)(mean + t * sd).  Default t = 0.43 (near
+ *     the terciles of a normal column; not validated on real embeddings).
+ * Out of scope: the qamd_bin_sharded_* handles stay one-bit; scalar (4- / 8-bit) queries against two-bit rows are refused
+ * (QAMD_ERR_ARGUMENTS: centred codes against a shifted, scaled store are a separate design); a 1.5-bit encoding; bench.py
+ * (it measures one-bit stores). */
+typedef enum { QAMD_BIN_ONE_BIT = 0, QAMD_BIN_TWO_BITS = 1 } qamd_bin_encoding;
+QAMD_API uint64_t qamd_bin_quantized_vector_size_enc(const qamd_vector_parameters *vp, qamd_bits_store store,
+                                                     qamd_bin_encoding encoding);
+/* The statistics above over ONE contiguous block of n_rows x dim values (blocks of 4096 counted from the call's first
+ * row); n, sum, sumsq: dim host entries each.  On its own for the reason qamd_u8_find_min_max is: a host that holds the
+ * rows in several places adds the three arrays of its holders and derives ONE set of thresholds with
+ * qamd_bin_thresholds_from_stats.  Unlike min / max, a sum of per-holder sums is NOT bit-equal to the single-handle
+ * result (f64 addition is not associative): every holder must then be given the same derived thresholds. */
+QAMD_API qamd_status qamd_bin_find_stats(const float *data, qamd_mem data_mem, uint64_t n_rows, uint64_t dim,
+                                         void *stream, uint64_t *n, double *sum, double *sumsq);
+/* Host only: never touches a device and works on a machine without one. */
+QAMD_API qamd_status qamd_bin_thresholds_from_stats(uint64_t dim, const uint64_t *n, const double *sum,
+                                                    const double *sumsq, double t, float *lo, float *hi);
+/* qamd_bin_encode with an encoding.  lo, hi: dim host floats each, or both NULL = qamd_bin_find_stats over `data`, then
+ * qamd_bin_thresholds_from_stats with t = 0.43.  QAMD_ERR_ARGUMENTS for exactly one NULL, any NaN, lo_i > hi_i and
+ * dim > 2^23.  QAMD_BIN_ONE_BIT: lo and hi must be NULL and the call is qamd_bin_encode. */
+QAMD_API qamd_status qamd_bin_encode_enc(const float *data, qamd_mem data_mem,
+                                         const qamd_vector_parameters *vp, qamd_bits_store store,
+                                         qamd_bin_encoding encoding, const float *lo, const float *hi,
+                                         qamd_stop_fn stop, void *stop_user, void *stream, qamd_bin **out);
+/* Streaming form.  Two bits with NULL thresholds: observe all vp.count rows (any batch sizes; the open block's sums are
+ * carried from call to call), then push them again in the same order; a push after too few observed rows and an observe
+ * after a push are QAMD_ERR_ARGUMENTS.  With thresholds given, or one bit, observe is an accepted no-op.  Thresholds and
+ * rows are byte-identical to qamd_bin_encode_enc on the concatenated data, whatever the batch sizes.  push, finish and
+ * abort are those of qamd_bin_encoder_begin. */
+QAMD_API qamd_status qamd_bin_encoder_begin_enc(const qamd_vector_parameters *vp, qamd_bits_store store,
+                                                qamd_bin_encoding encoding, const float *lo, const float *hi,
+                                                qamd_stop_fn stop, void *stop_user, void *stream,
+                                                qamd_bin_encoder **out);
+QAMD_API qamd_status qamd_bin_encoder_observe(qamd_bin_encoder *e, const float *batch, uint64_t n_rows,
+                                              qamd_mem batch_mem);
+/* Two bits: thresholds are required (queries need them). */
+QAMD_API qamd_status qamd_bin_from_rows_enc(const uint8_t *rows, qamd_mem rows_mem,
+                                            const qamd_vector_parameters *vp, qamd_bits_store store,
+                                            qamd_bin_encoding encoding, const float *lo, const float *hi,
+                                            void *stream, qamd_bin **out);
+/* Either pointer may be NULL.  *code_bits = the bits of a row: dim, or 2 * dim. */
+QAMD_API qamd_status qamd_bin_get_encoding(const qamd_bin *h, qamd_bin_encoding *encoding, uint64_t *code_bits);
+/* dim host floats each; QAMD_ERR_ARGUMENTS on a one-bit handle. */
+QAMD_API qamd_status qamd_bin_get_thresholds(const qamd_bin *h, float *lo, float *hi);
+/* qamd_bin_save of a two-bit handle writes {"vector_parameters":{..},"encoding":"TwoBits","thresholds":{"lo":[..],
+ * "hi":[..]}} (infinite thresholds have no JSON form: QAMD_ERR_IO); a one-bit file is the reference's, unchanged.
+ * qamd_bin_load: no "encoding" key, or "OneBit", is one bit; rows are sized by the file's encoding, thresholds restored
+ * bit for bit; QAMD_ERR_IO before any device call for an unknown encoding, "TwoBits" without thresholds, arrays whose
+ * length is not the caller's dim, and lo > hi. */
+
 /* encode_query (:288-291). */
 QAMD_API qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query, uint64_t qdim,
                                            qamd_mem query_mem, void *stream,

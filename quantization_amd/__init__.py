@@ -7,7 +7,7 @@ HIP library and a GPU every call raises.
 """
 from ._lib import build, lib  # noqa: F401
 from .encoded_vectors import DistanceType, EncodingError, VectorParameters, get_device, set_device  # noqa: F401
-from .encoded_vectors_binary import BitsStoreType, EncodedBinVector, EncodedVectorsBin  # noqa: F401
+from .encoded_vectors_binary import BinaryEncoding, BitsStoreType, EncodedBinVector, EncodedVectorsBin  # noqa: F401
 from .encoded_vectors_pq import EncodedQueryPQ, EncodedVectorsPQ  # noqa: F401
 from .encoded_vectors_u8 import EncodedQueryBatchU8, EncodedQueryU8, EncodedVectorsU8  # noqa: F401
 from .original_vectors import OriginalVectors  # noqa: F401
@@ -46,6 +46,6 @@ __all__ = [
     "DistanceType", "VectorParameters", "EncodingError", "OriginalVectors",
     "EncodedVectorsU8", "EncodedQueryU8", "EncodedQueryBatchU8",
     "EncodedVectorsPQ", "EncodedQueryPQ",
-    "EncodedVectorsBin", "EncodedBinVector", "BitsStoreType",
+    "EncodedVectorsBin", "EncodedBinVector", "BitsStoreType", "BinaryEncoding",
     "build", "lib",
 ]

@@ -151,6 +151,16 @@ def lib() -> C.CDLL:
         "qamd_bin_encoder_push": (i32, [vp, vp, u64, i32]),
         "qamd_bin_encoder_finish": (i32, [vp, pp]),
         "qamd_bin_encoder_abort": (None, [vp]),
+        # binary, two-bit rows
+        "qamd_bin_quantized_vector_size_enc": (u64, [VP, i32, i32]),
+        "qamd_bin_find_stats": (i32, [vp, i32, u64, u64, vp, vp, vp, vp]),
+        "qamd_bin_thresholds_from_stats": (i32, [u64, vp, vp, vp, C.c_double, vp, vp]),
+        "qamd_bin_encode_enc": (i32, [vp, i32, VP, i32, i32, vp, vp, STOP_FN, vp, vp, pp]),
+        "qamd_bin_encoder_begin_enc": (i32, [VP, i32, i32, vp, vp, STOP_FN, vp, vp, pp]),
+        "qamd_bin_encoder_observe": (i32, [vp, vp, u64, i32]),
+        "qamd_bin_from_rows_enc": (i32, [vp, i32, VP, i32, i32, vp, vp, vp, pp]),
+        "qamd_bin_get_encoding": (i32, [vp, C.POINTER(i32), C.POINTER(u64)]),
+        "qamd_bin_get_thresholds": (i32, [vp, vp, vp]),
         # pq
         "qamd_pq_quantized_vector_size": (u64, [VP, u64]),
         "qamd_pq_encode": (i32, [vp, i32, VP, u64, vp, u32, STOP_FN, vp, vp, pp]),

@@ -605,6 +605,167 @@ __global__ __launch_bounds__(kBlock) void bin_encode_flat_kernel(const float4 *_
     }
 }
 
+// ---- two-bit rows (the reference has no counterpart) ----
+// Per-dimension statistics.  The definition fixes the order of every addition, so the result does not depend on how a
+// caller batches the rows: column i's rows are cut into blocks of kStatRows by row index, a block's S = sum (double)x and
+// Q = sum (double)x * (double)x run in row order from +0.0 over its finite entries (n counts them), and the block sums are
+// added in block order (bin_stats_fold_kernel).  No floating-point atomics, no tree.
+// One workgroup of 64 lanes takes block blockIdx.x of the launch and 256 columns; a lane owns four adjacent columns and
+// walks the block's rows, eight rows in flight: consecutive lanes read consecutive 16-byte pieces of a row.  VEC: dim % 4 ==
+// 0 and a 16-byte aligned source; otherwise four guarded dword loads.  The eight loads of a step must all be issued
+// before the first wait: nothing conditional may stand between them and the adds.  A non-finite entry adds +0.0, which leaves a sum
+// that started at +0.0 unchanged bit for bit (it can never be -0.0).
+// `fill` rows of the launch's first block came with earlier launches: their sums are the carry the block starts from, and
+// the block takes only kStatRows - fill rows here.
+constexpr uint32_t kStatRows = 4096;
+
+template <bool VEC>
+__global__ __launch_bounds__(64) void bin_stats_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                      uint32_t fill, const double *__restrict__ carry_s,
+                                                      const double *__restrict__ carry_q,
+                                                      const uint32_t *__restrict__ carry_n, double *__restrict__ part_s,
+                                                      double *__restrict__ part_q, uint32_t *__restrict__ part_n) {
+    const uint64_t b = blockIdx.x;
+    const uint32_t c0 = (blockIdx.y * 64 + threadIdx.x) * 4;
+    if (c0 >= dim) return;
+    const uint64_t r0 = b ? b * kStatRows - fill : 0;
+    const uint64_t r1 = (b + 1) * kStatRows - fill < n_rows ? (b + 1) * kStatRows - fill : n_rows;
+    const float inf = __builtin_huge_valf();
+    double s[4], q[4];
+    uint32_t n[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const bool take = b == 0 && fill != 0 && c0 + e < dim;
+        s[e] = take ? carry_s[c0 + e] : 0.0;
+        q[e] = take ? carry_q[c0 + e] : 0.0;
+        n[e] = take ? carry_n[c0 + e] : 0u;
+    }
+    for (uint64_t r = r0; r < r1; r += 8) {
+        float v[8][4];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const uint64_t rr = r + u < r1 ? r + u : r1 - 1;
+            const float *p = data + rr * dim + c0;
+            if (VEC) {
+                const float4 t = __builtin_bit_cast(float4, ld_nt(reinterpret_cast<const uint4 *>(p)));
+                v[u][0] = t.x, v[u][1] = t.y, v[u][2] = t.z, v[u][3] = t.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; e++) v[u][e] = c0 + e < dim ? p[e] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) {  // (no early exit: a branch here lets the compiler sink each load behind it)
+            const bool row = r + u < r1;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const bool finite = row && fabsf(v[u][e]) < inf;  // NaN fails; a row past the block adds +0.0 like it
+                const double d = finite ? (double)v[u][e] : 0.0;
+                s[e] += d;
+                q[e] += d * d;  // the product of two f32 values is exact in f64
+                n[e] += finite ? 1u : 0u;
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        if (c0 + e < dim) {
+            part_s[b * dim + c0 + e] = s[e];
+            part_q[b * dim + c0 + e] = q[e];
+            part_n[b * dim + c0 + e] = n[e];
+        }
+    }
+}
+
+// The launch's blocks into the running totals, in block order; a last block that is not full yet becomes the carry.
+__global__ __launch_bounds__(kBlock) void bin_stats_fold_kernel(const double *__restrict__ part_s,
+                                                               const double *__restrict__ part_q,
+                                                               const uint32_t *__restrict__ part_n, uint64_t n_blocks,
+                                                               uint32_t dim, int last_open, double *__restrict__ tot_s,
+                                                               double *__restrict__ tot_q,
+                                                               unsigned long long *__restrict__ tot_n,
+                                                               double *__restrict__ carry_s, double *__restrict__ carry_q,
+                                                               uint32_t *__restrict__ carry_n) {
+    const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= dim) return;
+    double s = tot_s[c], q = tot_q[c];
+    unsigned long long n = tot_n[c];
+    const uint64_t full = n_blocks - (last_open ? 1 : 0);
+    for (uint64_t b = 0; b < full; b++) {
+        s += part_s[b * dim + c];
+        q += part_q[b * dim + c];
+        n += part_n[b * dim + c];
+    }
+    tot_s[c] = s;
+    tot_q[c] = q;
+    tot_n[c] = n;
+    if (last_open) {
+        carry_s[c] = part_s[full * dim + c];
+        carry_q[c] = part_q[full * dim + c];
+        carry_n[c] = part_n[full * dim + c];
+    }
+}
+
+// Threshold encoder for rows, the single query (a grid of one) and query batches: bit i of a row is x_i > lo_i, bit
+// dim + i is x_i > hi_i (thr = lo | hi, 2 dim floats), strict f32 compares, so NaN and -inf give (0,0) and +inf (1,1).
+// bin_encode_kernel's mapping - one wave per row, 64 values per step - with every float read once and two ballots per
+// step.  The ballot of the low plane is 64-bit word `st` of the row as it stands; the high plane starts at bit dim, so
+// with s = dim % 64 != 0 its ballot is shifted by s and merged with what the previous step left over (`carry`).  Lane
+// (st % 64) keeps the two finished words of step st and the wave stores them every 64 steps.  Word dim / 64 holds the
+// end of the low plane (known at the last step) and the start of the high one (known at the first): lane 0 writes it
+// after the loop, with the last carry behind it.  Every dword of the row is written, pad bits as zeros.
+__global__ __launch_bounds__(kBlock) void bin_encode_thr_kernel(const float *__restrict__ data, uint64_t n_rows,
+                                                               uint32_t dim, uint32_t row_words,
+                                                               const float *__restrict__ thr,
+                                                               uint32_t *__restrict__ rows, uint64_t row0) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    const uint32_t full = dim / 64, s = dim % 64, steps = (dim + 63) / 64;
+    auto put = [row_words](uint32_t *dst, uint32_t word64, unsigned long long v) {
+        const uint32_t w = word64 * 2;
+        if (w < row_words) dst[w] = (uint32_t)v;
+        if (w + 1 < row_words) dst[w + 1] = (uint32_t)(v >> 32);
+    };
+    for (uint64_t r = wave; r < n_rows; r += n_waves) {
+        const float *src = data + r * dim;
+        uint32_t *dst = rows + (row0 + r) * row_words;
+        unsigned long long mine0 = 0, mine1 = 0, carry = 0, first1 = 0, last0 = 0;
+        for (uint32_t st = 0; st < steps; st++) {
+            const uint32_t j = st * 64 + lane;
+            const bool in = j < dim;
+            const float v = in ? src[j] : 0.0f;
+            const float lo = in ? thr[j] : 0.0f, hi = in ? thr[dim + j] : 0.0f;
+            const unsigned long long b0 = __ballot(in && v > lo), b1 = __ballot(in && v > hi);
+            const unsigned long long m1 = s ? carry | (b1 << s) : b1;  // word full + st of the row
+            carry = s ? b1 >> (64 - s) : 0ull;
+            if (st == 0) first1 = m1;
+            if (st == full) last0 = b0;  // (only with s != 0: the low plane's last, partial word)
+            if ((st & 63u) == (uint32_t)lane) {
+                mine0 = b0;
+                mine1 = m1;
+            }
+            if ((st & 63u) == 63u || st + 1 == steps) {
+                const uint32_t k = (st & ~63u) + lane;  // the step this lane kept
+                if (k <= st) {
+                    if (k < full) put(dst, k, mine0);
+                    if (s == 0 || k > 0) put(dst, full + k, mine1);
+                }
+                mine0 = mine1 = 0;
+            }
+        }
+        uint32_t done = full + steps;  // 64-bit words written so far
+        if (s) {
+            if (lane == 0) {
+                put(dst, full, last0 | first1);
+                put(dst, full + steps, carry);
+            }
+            done += 1;
+        }
+        for (uint32_t w = done * 2 + lane; w < row_words; w += 64) dst[w] = 0;
+    }
+}
+
 int grid_for(uint64_t work_items, uint64_t per_block, int blocks_per_cu) {
     uint64_t want = (work_items + per_block - 1) / per_block;
     uint64_t cap = (uint64_t)device_info().cu_count * blocks_per_cu;
@@ -632,6 +793,12 @@ struct qamd_bin {
     uint64_t nb = 0;  // reference row bytes
     uint64_t ds = 0;  // device row stride (bytes)
     DevBuf rows;      // [padded_rows][ds]
+    // Two-bit rows: a row holds code_bits = 2 dim bits and is scored as a one-bit row of that length;
+    // vp.dim stays the vectors' dimension (thresholds, queries, the originals of a rescored top-k).
+    int encoding = QAMD_BIN_ONE_BIT;
+    uint64_t code_bits = 0;       // bits of a row: dim, or 2 dim
+    std::vector<float> thr_host;  // two-bit: lo[dim] | hi[dim]
+    DevBuf thr;                   // the same, for the encoders of rows and queries
     // the batched top-k's pivot sample (rows hash(j) of the store, j < sample_count, then 512 zero rows);
     // gathered once on first use (count / 64 rows at most), immutable after
     mutable std::mutex sample_mu;
@@ -650,15 +817,16 @@ struct qamd_bin_query {
 namespace {
 
 qamd_status alloc_store(qamd_bin *h) {
-    h->nb = row_bytes_of(h->vp.dim, h->store);
+    h->code_bits = h->encoding == QAMD_BIN_TWO_BITS ? 2 * h->vp.dim : h->vp.dim;
+    h->nb = row_bytes_of(h->code_bits, h->store);
     h->ds = device_stride_of(h->nb);
     const uint64_t padded = round_up(h->count, kRowPad) + kRowPad;
     return h->rows.alloc(padded * h->ds, true);
 }
 
-// calculate_metric's `dim` for a query of `planes` bit planes: dim * (2^planes - 1), exact in f32 (encode_query_scalar
-// refuses dims past 2^24)
-float metric_dim(const qamd_bin *h, uint32_t planes) { return (float)(h->vp.dim * ((1ull << planes) - 1)); }
+// calculate_metric's `dim` for a query of `planes` bit planes: the row's bits * (2^planes - 1), exact in f32
+// (encode_query_scalar refuses dims past 2^24, two-bit rows dims past 2^23)
+float metric_dim(const qamd_bin *h, uint32_t planes) { return (float)(h->code_bits * ((1ull << planes) - 1)); }
 
 template <int G, int ITERS, int UNROLL, int PLANES = 1>
 void launch_bin(const qamd_bin *h, const uint4 *qb, float *out, const TopkFilter *filt, hipStream_t s) {
@@ -858,7 +1026,11 @@ qamd_status upload_rows(qamd_bin *h, const uint8_t *rows, qamd_mem mem, hipStrea
 qamd_status launch_bin_encode(qamd_bin *h, const float *src, uint64_t nr, uint64_t r0, hipStream_t s) {
     const uint64_t dim = h->vp.dim;
     if (nr == 0 || dim == 0) return QAMD_OK;
-    if (dim % 128 == 0 && h->ds * 8 == dim && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+    if (h->encoding == QAMD_BIN_TWO_BITS) {
+        int grid = grid_for(nr, kBlock / 64, 8);
+        hipLaunchKernelGGL(bin_encode_thr_kernel, dim3(grid), dim3(kBlock), 0, s, src, nr, (uint32_t)dim,
+                           (uint32_t)(h->ds / 4), h->thr.as<float>(), h->rows.as<uint32_t>(), r0);
+    } else if (dim % 128 == 0 && h->ds * 8 == dim && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
         const uint64_t n4 = nr * dim / 4;
         const unsigned grid = (unsigned)((n4 + 1024 * (kBlock / 64) - 1) / (1024 * (kBlock / 64)));
         hipLaunchKernelGGL(bin_encode_flat_kernel, dim3(grid), dim3(kBlock), 0, s, reinterpret_cast<const float4 *>(src),
@@ -872,31 +1044,10 @@ qamd_status launch_bin_encode(qamd_bin *h, const float *src, uint64_t nr, uint64
     return QAMD_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-uint64_t qamd_bin_quantized_vector_size(const qamd_vector_parameters *vp, qamd_bits_store store) {
-    return row_bytes_of(vp->dim, store);
-}
-
-qamd_status qamd_bin_encode(const float *data, qamd_mem data_mem, const qamd_vector_parameters *vp,
-                            qamd_bits_store store, qamd_stop_fn stop, void *stop_user, void *stream,
-                            qamd_bin **out) {
-    if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
-    if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
-    QAMD_ON_DEVICE(current_device());
-    hipStream_t s = as_stream(stream);
-    std::unique_ptr<qamd_bin> h(new qamd_bin);
-    h->device = current_device();
-    h->vp = *vp;
-    h->store = store;
-    h->count = vp->count;
-    QAMD_TRY(alloc_store(h.get()));
-    const uint64_t dim = vp->dim, count = vp->count;
+// The rows of a one-shot encode: host rows are staged 256 MiB at a time; device rows are read in place, 8 GiB per launch.
+qamd_status encode_all(qamd_bin *h, const float *data, qamd_mem data_mem, qamd_stop_fn stop, void *stop_user, hipStream_t s) {
+    const uint64_t dim = h->vp.dim, count = h->count;
     if (count && dim) {
-        // host rows are staged 256 MiB at a time; device rows are read in place, 8 GiB per launch
         const uint64_t batch_bytes = stage_bytes(data_mem == QAMD_MEM_HOST ? (256ull << 20) : (8ull << 30));
         const uint64_t batch_rows = std::max<uint64_t>(1, std::min<uint64_t>(count, batch_bytes / (dim * 4)));
         DevBuf stage;
@@ -909,33 +1060,270 @@ qamd_status qamd_bin_encode(const float *data, qamd_mem data_mem, const qamd_vec
                 QAMD_TRY(copy_in(stage.ptr, src, QAMD_MEM_HOST, nr * dim * 4, s));
                 src = stage.as<float>();
             }
-            QAMD_TRY(launch_bin_encode(h.get(), src, nr, r0, s));
+            QAMD_TRY(launch_bin_encode(h, src, nr, r0, s));
             if (data_mem == QAMD_MEM_HOST || stop) QAMD_HIP(hipStreamSynchronize(s));
         }
         QAMD_HIP(hipStreamSynchronize(s));
     } else if (stop && count && stop(stop_user)) {
         return fail(QAMD_ERR_STOPPED, "Stopped");
     }
-    *out = h.release();
     return QAMD_OK;
 }
 
-qamd_status qamd_bin_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd_vector_parameters *vp,
-                               qamd_bits_store store, void *stream, qamd_bin **out) {
-    if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
-    QAMD_ON_DEVICE(current_device());
-    std::unique_ptr<qamd_bin> h(new qamd_bin);
+// ---- two-bit rows: statistics, thresholds, arguments
+constexpr uint64_t kTwoBitMaxDim = 1ull << 23;  // 2 dim <= 2^24: every count and score is an exact f32 integer
+constexpr double kTwoBitDefaultT = 0.43;
+
+// The running statistics of a sequence of row batches (bin_stats_kernel): totals of the closed blocks and the open
+// block's sums on the device, `fill` = rows the open block holds.  The batches' cuts do not show in the result.
+struct BinStats {
+    uint64_t dim = 0;
+    uint32_t fill = 0;
+    DevBuf state;  // tot_s, tot_q (f64), tot_n (u64), carry_s, carry_q (f64), carry_n (u32): [dim] each
+
+    double *tot_s() const { return state.as<double>(); }
+    double *tot_q() const { return tot_s() + dim; }
+    unsigned long long *tot_n() const { return reinterpret_cast<unsigned long long *>(tot_q() + dim); }
+    double *carry_s() const { return tot_s() + 3 * dim; }
+    double *carry_q() const { return tot_s() + 4 * dim; }
+    uint32_t *carry_n() const { return reinterpret_cast<uint32_t *>(tot_s() + 5 * dim); }
+
+    qamd_status begin(uint64_t d) {
+        dim = d;
+        fill = 0;
+        return state.alloc(std::max<uint64_t>(dim, 1) * 44, true);
+    }
+    // `n` rows at `src` (readable on the current device), enqueued on `s`
+    qamd_status add(const float *src, uint64_t n, hipStream_t s) {
+        if (n == 0 || dim == 0) return QAMD_OK;
+        const uint64_t blocks = (n + fill + kStatRows - 1) / kStatRows;
+        if (blocks > 0x7FFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "too many rows in one statistics launch");
+        StreamBuf part;  // the launch's block sums: part_s, part_q (f64), part_n (u32), [blocks][dim] each
+        QAMD_TRY(part.alloc(blocks * dim * 20, s));
+        double *ps = part.as<double>(), *pq = ps + blocks * dim;
+        uint32_t *pn = reinterpret_cast<uint32_t *>(pq + blocks * dim);
+        const dim3 grid((unsigned)blocks, (unsigned)((dim + 255) / 256));
+        if (dim % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0)
+            hipLaunchKernelGGL(bin_stats_kernel<true>, grid, dim3(64), 0, s, src, n, (uint32_t)dim, fill, carry_s(), carry_q(),
+                               carry_n(), ps, pq, pn);
+        else
+            hipLaunchKernelGGL(bin_stats_kernel<false>, grid, dim3(64), 0, s, src, n, (uint32_t)dim, fill, carry_s(), carry_q(),
+                               carry_n(), ps, pq, pn);
+        const uint32_t new_fill = (uint32_t)((n + fill) % kStatRows);
+        hipLaunchKernelGGL(bin_stats_fold_kernel, dim3((unsigned)((dim + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ps, pq, pn,
+                           blocks, (uint32_t)dim, new_fill != 0 ? 1 : 0, tot_s(), tot_q(), tot_n(), carry_s(), carry_q(), carry_n());
+        QAMD_HIP(hipGetLastError());
+        fill = new_fill;
+        return QAMD_OK;
+    }
+    // The open block closes as the last one.  Host outputs of `dim` entries.
+    qamd_status finish(hipStream_t s, uint64_t *n, double *sum, double *sumsq) {
+        if (dim == 0) return QAMD_OK;
+        std::vector<uint8_t> host(dim * 44);
+        QAMD_TRY(copy_out(host.data(), QAMD_MEM_HOST, state.ptr, host.size(), s));
+        QAMD_HIP(hipStreamSynchronize(s));
+        const double *ts = reinterpret_cast<const double *>(host.data()), *tq = ts + dim, *cs = ts + 3 * dim, *cq = ts + 4 * dim;
+        const uint64_t *tn = reinterpret_cast<const uint64_t *>(ts + 2 * dim);
+        const uint32_t *cn = reinterpret_cast<const uint32_t *>(ts + 5 * dim);
+        for (uint64_t i = 0; i < dim; i++) {
+            sum[i] = fill ? ts[i] + cs[i] : ts[i];
+            sumsq[i] = fill ? tq[i] + cq[i] : tq[i];
+            n[i] = fill ? tn[i] + cn[i] : tn[i];
+        }
+        return QAMD_OK;
+    }
+};
+
+// A batch of rows, in host or device memory, into the statistics: in pieces as the encoders stage them.
+// `stop` is polled before every piece, as the row pass polls it.
+qamd_status stats_feed(BinStats &st, const float *data, qamd_mem mem, uint64_t n_rows, DevBuf &stage, hipStream_t s,
+                       qamd_stop_fn stop = nullptr, void *stop_user = nullptr) {
+    if (st.dim == 0 || n_rows == 0) return QAMD_OK;
+    const uint64_t piece_bytes = stage_bytes(mem == QAMD_MEM_HOST ? (256ull << 20) : (8ull << 30));
+    const uint64_t piece_rows = std::max<uint64_t>(1, piece_bytes / (st.dim * 4));
+    return for_each_staged_piece(data, mem, n_rows, st.dim, piece_rows, stage, s,
+                                 [&](const float *src, uint64_t, uint64_t nr) -> qamd_status {
+        if (stop && stop(stop_user)) return fail(QAMD_ERR_STOPPED, "Stopped");
+        return st.add(src, nr, s);
+    });
+}
+
+// Host only, f64, single operations in the order of DESIGN 3.2e (this file compiles with contraction off).
+void thresholds_of(uint64_t dim, const uint64_t *n, const double *sum, const double *sumsq, double t, float *lo, float *hi) {
+    for (uint64_t i = 0; i < dim; i++) {
+        double mean = 0.0, var = 0.0;
+        if (n[i] != 0) {
+            const double cnt = (double)n[i];
+            mean = sum[i] / cnt;
+            const double m2 = mean * mean;
+            var = sumsq[i] / cnt - m2;
+        }
+        if (!(var > 0.0)) var = 0.0;
+        const double sd = std::sqrt(var);
+        const double w = t * sd;
+        lo[i] = (float)(mean - w);
+        hi[i] = (float)(mean + w);
+    }
+}
+
+// What every *_enc entry point checks before it needs a device.  `required`: two-bit rows cannot do without thresholds.
+qamd_status check_enc_args(const qamd_vector_parameters *vp, int encoding, const float *lo, const float *hi, bool required) {
+    if (encoding != QAMD_BIN_ONE_BIT && encoding != QAMD_BIN_TWO_BITS) return fail(QAMD_ERR_ARGUMENTS, "unknown binary encoding %d", encoding);
+    if ((lo == nullptr) != (hi == nullptr)) return fail(QAMD_ERR_ARGUMENTS, "thresholds: lo and hi come together");
+    if (encoding == QAMD_BIN_ONE_BIT) {
+        if (lo) return fail(QAMD_ERR_ARGUMENTS, "one-bit rows take no thresholds");
+        return QAMD_OK;
+    }
+    if (vp->dim > kTwoBitMaxDim)
+        return fail(QAMD_ERR_ARGUMENTS, "two-bit rows have at most %llu dimensions, not %llu", (unsigned long long)kTwoBitMaxDim,
+                    (unsigned long long)vp->dim);
+    if (!lo && required) return fail(QAMD_ERR_ARGUMENTS, "two-bit rows need their thresholds");
+    for (uint64_t i = 0; lo && i < vp->dim; i++) {
+        if (lo[i] != lo[i] || hi[i] != hi[i]) return fail(QAMD_ERR_ARGUMENTS, "threshold %llu is NaN", (unsigned long long)i);
+        if (lo[i] > hi[i]) return fail(QAMD_ERR_ARGUMENTS, "threshold %llu: lo %g > hi %g", (unsigned long long)i, lo[i], hi[i]);
+    }
+    return QAMD_OK;
+}
+
+qamd_status set_thresholds(qamd_bin *h, const float *lo, const float *hi, hipStream_t s) {
+    const uint64_t dim = h->vp.dim;
+    h->thr_host.resize(2 * dim);
+    if (dim == 0) return QAMD_OK;
+    memcpy(h->thr_host.data(), lo, dim * 4);
+    memcpy(h->thr_host.data() + dim, hi, dim * 4);
+    QAMD_TRY(h->thr.alloc(2 * dim * 4));
+    QAMD_TRY(copy_in(h->thr.ptr, h->thr_host.data(), QAMD_MEM_HOST, 2 * dim * 4, s));
+    QAMD_HIP(hipStreamSynchronize(s));  // (thr_host may be resized by no one, but the copy reads pageable memory)
+    return QAMD_OK;
+}
+
+qamd_status set_thresholds_from_stats(qamd_bin *h, BinStats &st, hipStream_t s) {
+    const uint64_t dim = h->vp.dim;
+    std::vector<uint64_t> n(dim);
+    std::vector<double> sum(dim), sumsq(dim);
+    std::vector<float> lo(dim), hi(dim);
+    QAMD_TRY(st.finish(s, n.data(), sum.data(), sumsq.data()));
+    thresholds_of(dim, n.data(), sum.data(), sumsq.data(), kTwoBitDefaultT, lo.data(), hi.data());
+    return set_thresholds(h, lo.data(), hi.data(), s);
+}
+
+qamd_status new_store(const qamd_vector_parameters *vp, int store, int encoding, std::unique_ptr<qamd_bin> &h) {
+    h.reset(new qamd_bin);
     h->device = current_device();
     h->vp = *vp;
     h->store = store;
     h->count = vp->count;
-    QAMD_TRY(alloc_store(h.get()));
+    h->encoding = encoding;
+    return alloc_store(h.get());
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t qamd_bin_quantized_vector_size(const qamd_vector_parameters *vp, qamd_bits_store store) {
+    return row_bytes_of(vp->dim, store);
+}
+
+uint64_t qamd_bin_quantized_vector_size_enc(const qamd_vector_parameters *vp, qamd_bits_store store, qamd_bin_encoding encoding) {
+    return row_bytes_of(encoding == QAMD_BIN_TWO_BITS ? 2 * vp->dim : vp->dim, store);
+}
+
+qamd_status qamd_bin_find_stats(const float *data, qamd_mem data_mem, uint64_t n_rows, uint64_t dim, void *stream, uint64_t *n,
+                                double *sum, double *sumsq) {
+    if (dim && (!n || !sum || !sumsq)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (!data && n_rows && dim) return fail(QAMD_ERR_ARGUMENTS, "data is null");
+    if (dim > kTwoBitMaxDim) return fail(QAMD_ERR_ARGUMENTS, "at most %llu dimensions", (unsigned long long)kTwoBitMaxDim);
+    if (n_rows == 0 || dim == 0) {  // nothing to read: no device either
+        for (uint64_t i = 0; i < dim; i++) n[i] = 0, sum[i] = 0.0, sumsq[i] = 0.0;
+        return QAMD_OK;
+    }
+    QAMD_ON_DEVICE(current_device());
+    hipStream_t s = as_stream(stream);
+    BinStats st;
+    DevBuf stage;
+    QAMD_TRY(st.begin(dim));
+    QAMD_TRY(stats_feed(st, data, data_mem, n_rows, stage, s));
+    return st.finish(s, n, sum, sumsq);
+}
+
+qamd_status qamd_bin_thresholds_from_stats(uint64_t dim, const uint64_t *n, const double *sum, const double *sumsq, double t,
+                                           float *lo, float *hi) {
+    if (dim && (!n || !sum || !sumsq || !lo || !hi)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (t != t) return fail(QAMD_ERR_ARGUMENTS, "t is NaN");
+    thresholds_of(dim, n, sum, sumsq, t, lo, hi);
+    return QAMD_OK;
+}
+
+qamd_status qamd_bin_encode_enc(const float *data, qamd_mem data_mem, const qamd_vector_parameters *vp, qamd_bits_store store,
+                                qamd_bin_encoding encoding, const float *lo, const float *hi, qamd_stop_fn stop,
+                                void *stop_user, void *stream, qamd_bin **out) {
+    if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    QAMD_TRY(check_enc_args(vp, encoding, lo, hi, false));
+    if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
+    if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
+    QAMD_ON_DEVICE(current_device());
+    hipStream_t s = as_stream(stream);
+    std::unique_ptr<qamd_bin> h;
+    QAMD_TRY(new_store(vp, store, encoding, h));
+    if (lo) {
+        QAMD_TRY(set_thresholds(h.get(), lo, hi, s));
+    } else if (encoding == QAMD_BIN_TWO_BITS) {  // one pass over the data for the statistics, then the rows
+        BinStats st;
+        DevBuf stage;
+        QAMD_TRY(st.begin(vp->dim));
+        QAMD_TRY(stats_feed(st, data, data_mem, vp->count, stage, s, stop, stop_user));
+        QAMD_TRY(set_thresholds_from_stats(h.get(), st, s));
+    }
+    QAMD_TRY(encode_all(h.get(), data, data_mem, stop, stop_user, s));
+    *out = h.release();
+    return QAMD_OK;
+}
+
+qamd_status qamd_bin_from_rows_enc(const uint8_t *rows, qamd_mem rows_mem, const qamd_vector_parameters *vp,
+                                   qamd_bits_store store, qamd_bin_encoding encoding, const float *lo, const float *hi,
+                                   void *stream, qamd_bin **out) {
+    if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    QAMD_TRY(check_enc_args(vp, encoding, lo, hi, true));
+    if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
+    QAMD_ON_DEVICE(current_device());
+    std::unique_ptr<qamd_bin> h;
+    QAMD_TRY(new_store(vp, store, encoding, h));
     if (h->count && h->nb && !rows) return fail(QAMD_ERR_ARGUMENTS, "rows is null");
+    if (lo) QAMD_TRY(set_thresholds(h.get(), lo, hi, as_stream(stream)));
     QAMD_TRY(upload_rows(h.get(), rows, rows_mem, as_stream(stream)));
     QAMD_HIP(hipStreamSynchronize(as_stream(stream)));
     *out = h.release();
     return QAMD_OK;
+}
+
+qamd_status qamd_bin_get_encoding(const qamd_bin *h, qamd_bin_encoding *encoding, uint64_t *code_bits) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    if (encoding) *encoding = (qamd_bin_encoding)h->encoding;
+    if (code_bits) *code_bits = h->code_bits;
+    return QAMD_OK;
+}
+
+qamd_status qamd_bin_get_thresholds(const qamd_bin *h, float *lo, float *hi) {
+    if (!h || !lo || !hi) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (h->encoding != QAMD_BIN_TWO_BITS) return fail(QAMD_ERR_ARGUMENTS, "one-bit rows have no thresholds");
+    const uint64_t dim = h->vp.dim;
+    if (dim) {
+        memcpy(lo, h->thr_host.data(), dim * 4);
+        memcpy(hi, h->thr_host.data() + dim, dim * 4);
+    }
+    return QAMD_OK;
+}
+
+qamd_status qamd_bin_encode(const float *data, qamd_mem data_mem, const qamd_vector_parameters *vp,
+                            qamd_bits_store store, qamd_stop_fn stop, void *stop_user, void *stream,
+                            qamd_bin **out) {
+    return qamd_bin_encode_enc(data, data_mem, vp, store, QAMD_BIN_ONE_BIT, nullptr, nullptr, stop, stop_user, stream, out);
+}
+
+qamd_status qamd_bin_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd_vector_parameters *vp,
+                               qamd_bits_store store, void *stream, qamd_bin **out) {
+    return qamd_bin_from_rows_enc(rows, rows_mem, vp, store, QAMD_BIN_ONE_BIT, nullptr, nullptr, stream, out);
 }
 
 // Rows [first_row, first_row + n_rows) as the reference's storage holds them (push_vector_data,
@@ -967,7 +1355,22 @@ qamd_status qamd_bin_export_rows(const qamd_bin *h, uint8_t *rows, qamd_mem rows
 // save/load (:260-286): Metadata{vector_parameters} as serde_json + raw row bytes.
 qamd_status qamd_bin_save(const qamd_bin *h, const char *data_path, const char *meta_path) {
     if (!h || !data_path || !meta_path) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    std::string js = "{\"vector_parameters\":" + vector_parameters_json(h->vp) + "}";
+    for (float t : h->thr_host)
+        if (!(fabsf(t) < __builtin_huge_valf())) return fail(QAMD_ERR_IO, "an infinite threshold has no form in the metadata file");
+    std::string js = "{\"vector_parameters\":" + vector_parameters_json(h->vp);
+    if (h->encoding == QAMD_BIN_TWO_BITS) {  // (a one-bit file stays the reference's, byte for byte)
+        js += ",\"encoding\":\"TwoBits\",\"thresholds\":{";
+        for (int side = 0; side < 2; side++) {
+            js += side ? ",\"hi\":[" : "\"lo\":[";
+            for (uint64_t i = 0; i < h->vp.dim; i++) {
+                if (i) js += ",";
+                js += json_f32(h->thr_host[side * h->vp.dim + i]);
+            }
+            js += "]";
+        }
+        js += "}";
+    }
+    js += "}";
     QAMD_TRY(save_file(meta_path, js.data(), js.size()));
     std::vector<uint8_t> rows(h->count * h->nb);
     QAMD_TRY(qamd_bin_export_rows(h, rows.data(), QAMD_MEM_HOST, nullptr));
@@ -985,11 +1388,43 @@ qamd_status qamd_bin_load(const char *data_path, const char *meta_path, const qa
         const JsonValue *vpj = json_field(root, "vector_parameters", err);
         if (!vpj || !parse_vector_parameters(*vpj, file_vp, err)) return fail(QAMD_ERR_IO, "%s: %s", meta_path, err.c_str());
     }
+    // "encoding": absent or "OneBit" is the reference's file; "TwoBits" comes with its thresholds.  Every
+    // refusal below is made before a device is needed.
+    int encoding = QAMD_BIN_ONE_BIT;
+    std::vector<float> thr;
+    for (const auto &m : root.members) {
+        if (m.first != "encoding") continue;
+        if (m.second.kind == JsonValue::String && m.second.text == "TwoBits") encoding = QAMD_BIN_TWO_BITS;
+        else if (m.second.kind != JsonValue::String || m.second.text != "OneBit")
+            return fail(QAMD_ERR_IO, "%s: unknown encoding", meta_path);
+    }
+    if (encoding == QAMD_BIN_TWO_BITS) {
+        std::string err;
+        const JsonValue *tj = json_field(root, "thresholds", err);
+        if (!tj) return fail(QAMD_ERR_IO, "%s: TwoBits: %s", meta_path, err.c_str());
+        if (vp->dim > kTwoBitMaxDim) return fail(QAMD_ERR_IO, "%s: two-bit rows of %llu dimensions", meta_path, (unsigned long long)vp->dim);
+        thr.resize(2 * vp->dim);
+        for (int side = 0; side < 2; side++) {
+            const JsonValue *a = json_field(*tj, side ? "hi" : "lo", err);
+            if (!a) return fail(QAMD_ERR_IO, "%s: thresholds: %s", meta_path, err.c_str());
+            if (a->kind != JsonValue::Array || a->items.size() != vp->dim)
+                return fail(QAMD_ERR_IO, "%s: thresholds: expected %llu values per side", meta_path, (unsigned long long)vp->dim);
+            for (uint64_t i = 0; i < vp->dim; i++)
+                if (!json_number_as_f32(a->items[i], thr[side * vp->dim + i], err))
+                    return fail(QAMD_ERR_IO, "%s: thresholds: %s", meta_path, err.c_str());
+        }
+        for (uint64_t i = 0; i < vp->dim; i++)
+            if (!(thr[i] <= thr[vp->dim + i])) return fail(QAMD_ERR_IO, "%s: thresholds: lo > hi at %llu", meta_path, (unsigned long long)i);
+    }
     std::string bytes;
-    QAMD_TRY(load_rows_file(data_path, row_bytes_of(vp->dim, store) * vp->count, bytes));  // :277-279
+    const uint64_t code_bits = encoding == QAMD_BIN_TWO_BITS ? 2 * vp->dim : vp->dim;
+    QAMD_TRY(load_rows_file(data_path, row_bytes_of(code_bits, store) * vp->count, bytes));  // :277-279
     qamd_vector_parameters eff = file_vp;  // metadata rules the metric, the caller's params the sizes
     eff.dim = vp->dim;
     eff.count = vp->count;
+    if (encoding == QAMD_BIN_TWO_BITS)
+        return qamd_bin_from_rows_enc(reinterpret_cast<const uint8_t *>(bytes.data()), QAMD_MEM_HOST, &eff, store, QAMD_BIN_TWO_BITS,
+                                      thr.data(), thr.data() + vp->dim, nullptr, out);
     return qamd_bin_from_rows(reinterpret_cast<const uint8_t *>(bytes.data()), QAMD_MEM_HOST, &eff, store, nullptr,
                               out);
 }
@@ -997,9 +1432,13 @@ qamd_status qamd_bin_load(const char *data_path, const char *meta_path, const qa
 qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem,
                                   void *stream, qamd_bin_query **query_io) {
     if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    const bool two = h->encoding == QAMD_BIN_TWO_BITS;  // the row's thresholds and layout
+    if (two && qdim != h->vp.dim)
+        return fail(QAMD_ERR_ARGUMENTS, "a query of %llu dimensions against thresholds of %llu", (unsigned long long)qdim,
+                    (unsigned long long)h->vp.dim);
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
-    const uint64_t nb = row_bytes_of(qdim, h->store), ds = device_stride_of(nb);
+    const uint64_t nb = row_bytes_of(two ? 2 * qdim : qdim, h->store), ds = device_stride_of(nb);
     qamd_bin_query *q = *query_io;
     std::unique_ptr<qamd_bin_query> fresh;
     if (!q) {
@@ -1022,8 +1461,12 @@ qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query, uint64_
             QAMD_TRY(copy_in(stage, query, QAMD_MEM_HOST, qdim * 4, s));
             q_dev = stage;
         }
-        hipLaunchKernelGGL(bin_encode_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint64_t)1, (uint32_t)qdim,
-                           (uint32_t)(ds / 4), q->buf.as<uint32_t>(), (uint64_t)0);
+        if (two)
+            hipLaunchKernelGGL(bin_encode_thr_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint64_t)1, (uint32_t)qdim,
+                               (uint32_t)(ds / 4), h->thr.as<float>(), q->buf.as<uint32_t>(), (uint64_t)0);
+        else
+            hipLaunchKernelGGL(bin_encode_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint64_t)1, (uint32_t)qdim,
+                               (uint32_t)(ds / 4), q->buf.as<uint32_t>(), (uint64_t)0);
         QAMD_HIP(hipGetLastError());
     }
     QAMD_TRY(q->ready.record(s));
@@ -1040,6 +1483,7 @@ qamd_status qamd_bin_encode_query_scalar(const qamd_bin *h, const float *query, 
     if (bits == 1) return qamd_bin_encode_query(h, query, qdim, query_mem, stream, query_io);
     if (bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
     if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (h->encoding == QAMD_BIN_TWO_BITS) return fail(QAMD_ERR_ARGUMENTS, "two-bit rows take no scalar queries");
     // dim * (2^bits - 1) and every sum below it must be exact in f32: both limits keep it under 2^24
     const uint64_t max_dim = bits == 8 ? 65792 : 1118481;
     if (qdim > max_dim)
@@ -1232,7 +1676,7 @@ void launch_bin_multi(const qamd_bin *h, const uint8_t *qbits, uint64_t q_stride
 #define QAMD_BIN_MULTI(EX, FI)                                                                                    \
     hipLaunchKernelGGL((bin_scan_multi_kernel<G, ITERS, UNROLL, NQ, EX, FI>), dim3(grid), dim3(kScanBlock), 0, s, \
                        h->rows.as<uint4>(), reinterpret_cast<const uint4 *>(qbits), (uint32_t)(q_stride / 16),    \
-                       (float)h->vp.dim, (int)(h->vp.distance_type == QAMD_DOT), h->vp.invert, (uint32_t)h->count, \
+                       metric_dim(h, 1), (int)(h->vp.distance_type == QAMD_DOT), h->vp.invert, (uint32_t)h->count, \
                        rc, out, (uint64_t)h->count, slices ? *slices : TopkFilterSlices{})
     if (slices) {
         if (exact) QAMD_BIN_MULTI(true, true);
@@ -2009,7 +2453,7 @@ qamd_status launch_bin_gemm(const qamd_bin *h, const qamd_bin_query_batch *b, co
     do {                                                                                                                   \
         QAMD_LDS_OPT_IN((&bin_gemm_rs_kernel<M_, LOW_, MI_>), 160 * 1024); \
         hipLaunchKernelGGL((bin_gemm_rs_kernel<M_, LOW_, MI_>), dim3(grid), dim3(512), lds, s, rows, (uint32_t)h->ds,      \
-                           b->bits.as<uint8_t>(), (uint32_t)b->q_stride, (float)h->vp.dim, zx ? 1 : 0, (uint32_t)n_rows,   \
+                           b->bits.as<uint8_t>(), (uint32_t)b->q_stride, metric_dim(h, 1), zx ? 1 : 0, (uint32_t)n_rows,   \
                            (uint32_t)b->n_queries, q0, out, out_pitch, filt);                                              \
     } while (0)
     // a scalar batch: its code image at the kernel's own LDS pitch, and dim * L for dim (never its planes, never as bits)
@@ -2174,10 +2618,10 @@ qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b
         const unsigned pgrid = (unsigned)std::max<uint64_t>((q_pad + 255) / 256, std::min<uint64_t>(2048, (frag_bytes / 16 + 255) / 256));
         if (low)
             hipLaunchKernelGGL(bin_frag4_kernel<true>, dim3(pgrid), dim3(256), 0, s, b->bits.as<uint8_t>(), (uint32_t)b->q_stride, (uint32_t)Q,
-                               (uint32_t)q_pad, nsteps, (float)h->vp.dim, zx ? 1 : 0, largest, pivots, frag, q_off, bq);
+                               (uint32_t)q_pad, nsteps, metric_dim(h, 1), zx ? 1 : 0, largest, pivots, frag, q_off, bq);
         else
             hipLaunchKernelGGL(bin_frag4_kernel<false>, dim3(pgrid), dim3(256), 0, s, b->bits.as<uint8_t>(), (uint32_t)b->q_stride, (uint32_t)Q,
-                               (uint32_t)q_pad, nsteps, (float)h->vp.dim, zx ? 1 : 0, largest, pivots, frag, q_off, bq);
+                               (uint32_t)q_pad, nsteps, metric_dim(h, 1), zx ? 1 : 0, largest, pivots, frag, q_off, bq);
         const size_t qs_rows = h->ds > 128 ? 96 : 128;
         const size_t lds = 2 * qs_rows * round_up(h->ds * 4, 256) + 4 * qs_rows * 4 + 64 + kQs4Slice * 4;
         const uint32_t grid = (uint32_t)std::max(1, device_info().cu_count / 8) * 8;
@@ -2320,9 +2764,13 @@ extern "C" {
 qamd_status qamd_bin_encode_query_batch(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
                                         qamd_mem queries_mem, void *stream, qamd_bin_query_batch **batch_io) {
     if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    const bool two = h->encoding == QAMD_BIN_TWO_BITS;
+    if (two && n_queries && qdim != h->vp.dim)
+        return fail(QAMD_ERR_ARGUMENTS, "queries of %llu dimensions against thresholds of %llu", (unsigned long long)qdim,
+                    (unsigned long long)h->vp.dim);
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
-    const uint64_t nb = row_bytes_of(qdim, h->store), ds = device_stride_of(nb);
+    const uint64_t nb = row_bytes_of(two ? 2 * qdim : qdim, h->store), ds = device_stride_of(nb);
     if (n_queries && nb != h->nb)
         return fail(QAMD_ERR_ARGUMENTS, "queries have %llu bytes, rows have %llu", (unsigned long long)nb,
                     (unsigned long long)h->nb);
@@ -2348,8 +2796,12 @@ qamd_status qamd_bin_encode_query_batch(const qamd_bin *h, const float *queries,
         QAMD_TRY(local_view(queries, queries_mem, n_queries * qdim * 4, qtmp, s, &qd, &staged));
         // the row encoder with one "row" per query and the batch's stride (:288-291 is encode_vector itself)
         int grid = grid_for(n_queries, kBlock / 64, 8);
-        hipLaunchKernelGGL(bin_encode_kernel, dim3(grid), dim3(kBlock), 0, s, static_cast<const float *>(qd), n_queries,
-                           (uint32_t)qdim, (uint32_t)(q_stride / 4), b->bits.as<uint32_t>(), (uint64_t)0);
+        if (two)
+            hipLaunchKernelGGL(bin_encode_thr_kernel, dim3(grid), dim3(kBlock), 0, s, static_cast<const float *>(qd), n_queries,
+                               (uint32_t)qdim, (uint32_t)(q_stride / 4), h->thr.as<float>(), b->bits.as<uint32_t>(), (uint64_t)0);
+        else
+            hipLaunchKernelGGL(bin_encode_kernel, dim3(grid), dim3(kBlock), 0, s, static_cast<const float *>(qd), n_queries,
+                               (uint32_t)qdim, (uint32_t)(q_stride / 4), b->bits.as<uint32_t>(), (uint64_t)0);
         QAMD_HIP(hipGetLastError());
         if (staged) QAMD_HIP(hipStreamSynchronize(s));
     }
@@ -2365,6 +2817,7 @@ qamd_status qamd_bin_encode_query_batch_scalar(const qamd_bin *h, const float *q
     if (bits == 1) return qamd_bin_encode_query_batch(h, queries, n_queries, qdim, queries_mem, stream, batch_io);
     if (bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
     if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (h->encoding == QAMD_BIN_TWO_BITS) return fail(QAMD_ERR_ARGUMENTS, "two-bit rows take no scalar queries");
     const uint64_t max_dim = bits == 8 ? 65792 : 1118481;  // as qamd_bin_encode_query_scalar: dim * L stays exact in f32
     if (qdim > max_dim)
         return fail(QAMD_ERR_ARGUMENTS, "a %u-bit query has at most %llu dimensions, not %llu", bits,
@@ -2456,7 +2909,7 @@ static const uint8_t *bin_batch_query(const qamd_bin_query_batch *b, uint64_t q)
 // The matrix gate both share: the query tile must fit LDS (bin_mfma_frags != 0: rows of at most 39 K-blocks = 4992 bits),
 // and at that length every operand and partial sum of the f32 epilogue is an integer below 2^23 - binary: 4 * 4992 + 2 *
 // 4992; scalar: 512 dim + 255 dim + 2 dim = 769 * 4992 < 2^22 - so the scores are those of the scan kernels bit for bit.
-static bool bin_mfma_capable(const qamd_bin *h) { return fused_capable(h) && bin_mfma_frags(h->ds) != 0 && h->vp.dim >= 64; }
+static bool bin_mfma_capable(const qamd_bin *h) { return fused_capable(h) && bin_mfma_frags(h->ds) != 0 && h->code_bits >= 64; }
 
 // The smallest scalar batch the matrix cores take: the values of the binary int8 route, 5 for score_batch and
 // kRs4MinQueries = 12 for topk_batch.  Measured (profiles/bin_scalar_batch.txt, 50M x 1024, 4 / 8 bits, batch against a loop
@@ -2653,13 +3106,36 @@ struct qamd_bin_encoder {
     std::unique_ptr<qamd_bin> h;
     uint64_t pushed = 0;
     DevBuf stage;
+    // two-bit rows without given thresholds: every row is observed before the first push
+    bool learns = false;    // set by begin
+    bool learning = false;  // the observe pass is open
+    uint64_t observed = 0;
+    BinStats stats;
 };
+
+// The end of the observe pass: the statistics of all vp.count rows become the store's thresholds.
+static qamd_status bin_encoder_close_observe(qamd_bin_encoder *e) {
+    if (!e->learning) return QAMD_OK;
+    if (e->observed != e->h->count)
+        return fail(QAMD_ERR_ARGUMENTS, "%llu of %llu rows were observed before the first push", (unsigned long long)e->observed,
+                    (unsigned long long)e->h->count);
+    QAMD_TRY(set_thresholds_from_stats(e->h.get(), e->stats, e->stream));
+    e->learning = false;
+    return QAMD_OK;
+}
 
 extern "C" {
 
 qamd_status qamd_bin_encoder_begin(const qamd_vector_parameters *vp, qamd_bits_store store, qamd_stop_fn stop,
                                    void *stop_user, void *stream, qamd_bin_encoder **out) {
+    return qamd_bin_encoder_begin_enc(vp, store, QAMD_BIN_ONE_BIT, nullptr, nullptr, stop, stop_user, stream, out);
+}
+
+qamd_status qamd_bin_encoder_begin_enc(const qamd_vector_parameters *vp, qamd_bits_store store, qamd_bin_encoding encoding,
+                                       const float *lo, const float *hi, qamd_stop_fn stop, void *stop_user, void *stream,
+                                       qamd_bin_encoder **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    QAMD_TRY(check_enc_args(vp, encoding, lo, hi, false));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     QAMD_ON_DEVICE(current_device());
     std::unique_ptr<qamd_bin_encoder> e(new qamd_bin_encoder);
@@ -2667,13 +3143,26 @@ qamd_status qamd_bin_encoder_begin(const qamd_vector_parameters *vp, qamd_bits_s
     e->stream = as_stream(stream);
     e->stop = stop;
     e->stop_user = stop_user;
-    e->h.reset(new qamd_bin);
-    e->h->device = e->device;
-    e->h->vp = *vp;
-    e->h->store = store;
-    e->h->count = vp->count;
-    QAMD_TRY(alloc_store(e->h.get()));
+    QAMD_TRY(new_store(vp, store, encoding, e->h));
+    if (lo) {
+        QAMD_TRY(set_thresholds(e->h.get(), lo, hi, e->stream));
+    } else if (encoding == QAMD_BIN_TWO_BITS) {
+        e->learns = e->learning = true;
+        QAMD_TRY(e->stats.begin(vp->dim));
+    }
     *out = e.release();
+    return QAMD_OK;
+}
+
+qamd_status qamd_bin_encoder_observe(qamd_bin_encoder *e, const float *batch, uint64_t n_rows, qamd_mem batch_mem) {
+    if (!e || (!batch && n_rows && e->h->vp.dim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (e->stop && e->stop(e->stop_user)) return fail(QAMD_ERR_STOPPED, "Stopped");
+    if (!e->learns) return QAMD_OK;  // one bit, or thresholds given: nothing to learn
+    if (!e->learning) return fail(QAMD_ERR_ARGUMENTS, "observe after push");
+    if (e->observed + n_rows > e->h->count) return count_mismatch(e->observed + n_rows, e->h->count);
+    QAMD_ON_DEVICE(e->device);
+    QAMD_TRY(stats_feed(e->stats, batch, batch_mem, n_rows, e->stage, e->stream, e->stop, e->stop_user));
+    e->observed += n_rows;
     return QAMD_OK;
 }
 
@@ -2682,6 +3171,7 @@ qamd_status qamd_bin_encoder_push(qamd_bin_encoder *e, const float *batch, uint6
     if (e->stop && e->stop(e->stop_user)) return fail(QAMD_ERR_STOPPED, "Stopped");  // :174-176
     if (e->pushed + n_rows > e->h->count) return count_mismatch(e->pushed + n_rows, e->h->count);
     QAMD_ON_DEVICE(e->device);
+    QAMD_TRY(bin_encoder_close_observe(e));
     const uint64_t dim = e->h->vp.dim;
     const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / std::max<uint64_t>(dim * 4, 1));
     if (dim)
@@ -2698,6 +3188,7 @@ qamd_status qamd_bin_encoder_finish(qamd_bin_encoder *e, qamd_bin **out) {
     std::unique_ptr<qamd_bin_encoder> own(e);
     if (e->pushed != e->h->count) return count_mismatch(e->pushed, e->h->count);
     QAMD_ON_DEVICE(e->device);
+    QAMD_TRY(bin_encoder_close_observe(e));  // (a store of no rows: thresholds of no statistics)
     QAMD_HIP(hipStreamSynchronize(e->stream));
     *out = e->h.release();
     return QAMD_OK;

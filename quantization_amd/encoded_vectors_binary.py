@@ -21,6 +21,25 @@ class BitsStoreType(enum.IntEnum):
     U128 = 1
 
 
+class BinaryEncoding(enum.IntEnum):
+    """Bits kept per stored dimension.  TwoBits has no counterpart in the reference: two compares per dimension against
+    thresholds mean -+ t * deviation of that dimension's data."""
+
+    OneBit = 0
+    TwoBits = 1
+
+
+def _thresholds_arg(thresholds, dim: int):
+    """(lo, hi) -> two contiguous f32 arrays of dim entries and their pointers; None -> NULL pointers."""
+    if thresholds is None:
+        return None, None, None
+    lo = np.ascontiguousarray(thresholds[0], dtype=np.float32).reshape(-1)
+    hi = np.ascontiguousarray(thresholds[1], dtype=np.float32).reshape(-1)
+    if lo.size != dim or hi.size != dim:
+        raise EncodingError(_lib.ERR_ARGUMENTS, f"thresholds of {lo.size} and {hi.size} entries for dim {dim}")
+    return (lo, hi), C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data)
+
+
 class EncodedBinVector(EncodedQueryBase):
     """encoded_vectors_binary.rs:17-19."""
 
@@ -87,6 +106,22 @@ class EncodedVectorsBin(EncodedVectorsBase):
         super().__init__(handle, device, owned)
         self._vp = vector_parameters
         self._store = BitsStoreType(store)
+        enc = C.c_int()
+        check(_lib.lib().qamd_bin_get_encoding(self._h, C.byref(enc), None))
+        self._encoding = BinaryEncoding(enc.value)
+
+    @property
+    def encoding(self) -> BinaryEncoding:
+        return self._encoding
+
+    @property
+    def thresholds(self):
+        """(lo, hi), dim f32 entries each, of a two-bit store; None for one bit."""
+        if self._encoding != BinaryEncoding.TwoBits:
+            return None
+        lo, hi = np.zeros(self._vp.dim, dtype=np.float32), np.zeros(self._vp.dim, dtype=np.float32)
+        check(_lib.lib().qamd_bin_get_thresholds(self._h, C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data)))
+        return lo, hi
 
     @property
     def vector_parameters(self) -> VectorParameters:
@@ -94,22 +129,54 @@ class EncodedVectorsBin(EncodedVectorsBase):
 
     @property
     def metadata(self) -> dict:
+        if self._encoding == BinaryEncoding.TwoBits:
+            return {"vector_parameters": self._vp, "encoding": self._encoding, "thresholds": self.thresholds}
         return {"vector_parameters": self._vp}  # :21-24
 
     @classmethod
     def encode(cls, orig_data, vector_parameters: VectorParameters, stop_condition=None, *,
-               store: BitsStoreType = BitsStoreType.U8, stream=None) -> "EncodedVectorsBin":
-        """EncodedVectorsBin::<TBitsStoreType, _>::encode (:165-191)."""
+               store: BitsStoreType = BitsStoreType.U8, stream=None,
+               encoding: BinaryEncoding = BinaryEncoding.OneBit, thresholds=None) -> "EncodedVectorsBin":
+        """EncodedVectorsBin::<TBitsStoreType, _>::encode (:165-191).  encoding = TwoBits: `thresholds` = (lo, hi), or
+        None to take them from the data (find_stats, then thresholds_from_stats with t = 0.43)."""
         data = flatten_rows(orig_data, vector_parameters.dim)
         validate(data, vector_parameters)
         vp = vector_parameters.to_c()
         buf = in_buf(data, np.float32)
         stop = make_stop(stop_condition)
         out = C.c_void_p()
+        keep, lo, hi = _thresholds_arg(thresholds, vector_parameters.dim)
         with creating_on(data) as dev:
-            check(_lib.lib().qamd_bin_encode(buf.ptr, buf.mem, C.byref(vp), int(store), stop, None,
-                                             stream_ptr(stream), C.byref(out)))
+            check(_lib.lib().qamd_bin_encode_enc(buf.ptr, buf.mem, C.byref(vp), int(store), int(encoding), lo, hi, stop,
+                                                 None, stream_ptr(stream), C.byref(out)))
         return cls(out, vector_parameters, store, dev)
+
+    @staticmethod
+    def find_stats(data, stream=None):
+        """(n, sum, sumsq) per dimension of a [n_rows, dim] block of f32 rows (qamd_bin_find_stats): u64 counts of the
+        finite entries and their f64 sums, bit-exact whatever the batch a caller later encodes in."""
+        n_rows, dim = int(data.shape[0]), int(data.shape[1])
+        buf = in_buf(data, np.float32)
+        n, s, q = np.zeros(dim, dtype=np.uint64), np.zeros(dim, dtype=np.float64), np.zeros(dim, dtype=np.float64)
+        with creating_on(data):
+            check(_lib.lib().qamd_bin_find_stats(buf.ptr, buf.mem, n_rows, dim, stream_ptr(stream), C.c_void_p(n.ctypes.data),
+                                                 C.c_void_p(s.ctypes.data), C.c_void_p(q.ctypes.data)))
+        return n, s, q
+
+    @staticmethod
+    def thresholds_from_stats(n, sum, sumsq, t: float = 0.43):
+        """(lo, hi) = mean -+ t * deviation per dimension (qamd_bin_thresholds_from_stats; host only)."""
+        n = np.ascontiguousarray(n, dtype=np.uint64)
+        s = np.ascontiguousarray(sum, dtype=np.float64)
+        q = np.ascontiguousarray(sumsq, dtype=np.float64)
+        dim = n.size
+        if s.size != dim or q.size != dim:
+            raise EncodingError(_lib.ERR_ARGUMENTS, "n, sum and sumsq have one entry per dimension each")
+        lo, hi = np.zeros(dim, dtype=np.float32), np.zeros(dim, dtype=np.float32)
+        check(_lib.lib().qamd_bin_thresholds_from_stats(dim, C.c_void_p(n.ctypes.data), C.c_void_p(s.ctypes.data),
+                                                        C.c_void_p(q.ctypes.data), float(t), C.c_void_p(lo.ctypes.data),
+                                                        C.c_void_p(hi.ctypes.data)))
+        return lo, hi
 
     def encode_query(self, query, reuse=None, stream=None, *, query_bits: int = 1):
         """EncodedVectors::encode_query (:288-291).  query_bits = 4 or 8 keeps that many bits per query dimension
@@ -150,24 +217,32 @@ class EncodedVectorsBin(EncodedVectorsBase):
 
     @classmethod
     def encode_stream(cls, make_batches, vector_parameters: VectorParameters, stop_condition=None, *,
-                      store: BitsStoreType = BitsStoreType.U8, stream=None) -> "EncodedVectorsBin":
+                      store: BitsStoreType = BitsStoreType.U8, stream=None,
+                      encoding: BinaryEncoding = BinaryEncoding.OneBit, thresholds=None) -> "EncodedVectorsBin":
         """encode from the reference's iterator contract (:165-191 walks it once): `make_batches()`
-        returns an iterator over [n_i, dim] f32 batches; rows are appended in order."""
+        returns an iterator over [n_i, dim] f32 batches; rows are appended in order.  TwoBits without thresholds walks
+        it twice: every batch is observed first (the per-dimension statistics), then pushed."""
         L = _lib.lib()
         vp = vector_parameters.to_c()
         stop = make_stop(stop_condition)
         first = next(iter(make_batches()), None)
         enc = C.c_void_p()
+        keep, lo, hi = _thresholds_arg(thresholds, vector_parameters.dim)
         with creating_on(first) as dev:
-            check(L.qamd_bin_encoder_begin(C.byref(vp), int(store), stop, None, stream_ptr(stream), C.byref(enc)))
+            check(L.qamd_bin_encoder_begin_enc(C.byref(vp), int(store), int(encoding), lo, hi, stop, None,
+                                               stream_ptr(stream), C.byref(enc)))
+        passes = [L.qamd_bin_encoder_push]
+        if encoding == BinaryEncoding.TwoBits and thresholds is None:
+            passes.insert(0, L.qamd_bin_encoder_observe)
         try:
-            for batch in make_batches():
-                if len(batch.shape) != 2 or (batch.shape[0] and batch.shape[1] != vector_parameters.dim):
-                    raise EncodingError(_lib.ERR_ARGUMENTS, f"Vector length {batch.shape[-1]} does not match "
-                                                            f"vector parameters dim {vector_parameters.dim}")
-                check_same_device(dev, batch)
-                buf = in_buf(batch, np.float32)
-                check(L.qamd_bin_encoder_push(enc, buf.ptr, int(batch.shape[0]), buf.mem))
+            for feed in passes:
+                for batch in make_batches():
+                    if len(batch.shape) != 2 or (batch.shape[0] and batch.shape[1] != vector_parameters.dim):
+                        raise EncodingError(_lib.ERR_ARGUMENTS, f"Vector length {batch.shape[-1]} does not match "
+                                                                f"vector parameters dim {vector_parameters.dim}")
+                    check_same_device(dev, batch)
+                    buf = in_buf(batch, np.float32)
+                    check(feed(enc, buf.ptr, int(batch.shape[0]), buf.mem))
             out = C.c_void_p()
             h, enc = enc, None
             check(L.qamd_bin_encoder_finish(h, C.byref(out)))
@@ -178,13 +253,16 @@ class EncodedVectorsBin(EncodedVectorsBase):
 
     @classmethod
     def from_storage(cls, rows, vector_parameters: VectorParameters,
-                     store: BitsStoreType = BitsStoreType.U8, stream=None) -> "EncodedVectorsBin":
+                     store: BitsStoreType = BitsStoreType.U8, stream=None,
+                     encoding: BinaryEncoding = BinaryEncoding.OneBit, thresholds=None) -> "EncodedVectorsBin":
+        """A store from rows encoded elsewhere.  TwoBits needs `thresholds` = (lo, hi): queries are encoded with them."""
         vp = vector_parameters.to_c()
         buf = in_buf(rows, np.uint8)
         out = C.c_void_p()
+        keep, lo, hi = _thresholds_arg(thresholds, vector_parameters.dim)
         with creating_on(rows) as dev:
-            check(_lib.lib().qamd_bin_from_rows(buf.ptr, buf.mem, C.byref(vp), int(store), stream_ptr(stream),
-                                                C.byref(out)))
+            check(_lib.lib().qamd_bin_from_rows_enc(buf.ptr, buf.mem, C.byref(vp), int(store), int(encoding), lo, hi,
+                                                    stream_ptr(stream), C.byref(out)))
         return cls(out, vector_parameters, store, dev)
 
     @classmethod
@@ -208,14 +286,15 @@ class EncodedVectorsBin(EncodedVectorsBase):
 
     @staticmethod
     def get_quantized_vector_size_from_params(vector_parameters: VectorParameters,
-                                              store: BitsStoreType = BitsStoreType.U8) -> int:
+                                              store: BitsStoreType = BitsStoreType.U8,
+                                              encoding: BinaryEncoding = BinaryEncoding.OneBit) -> int:
         """:210-213, bytes per row."""
         vp = vector_parameters.to_c()
-        return int(_lib.lib().qamd_bin_quantized_vector_size(C.byref(vp), int(store)))
+        return int(_lib.lib().qamd_bin_quantized_vector_size_enc(C.byref(vp), int(store), int(encoding)))
 
     def storage_bytes(self, out=None, stream=None):
         n = self._vp.count
-        nb = self.get_quantized_vector_size_from_params(self._vp, self._store)
+        nb = self.get_quantized_vector_size_from_params(self._vp, self._store, self._encoding)
         check_same_device(self._device, out)
         buf, ret = out_buf(out, n * nb, np.uint8)
         check(_lib.lib().qamd_bin_export_rows(self._h, buf.ptr, buf.mem, stream_ptr(stream)))
@@ -223,7 +302,7 @@ class EncodedVectorsBin(EncodedVectorsBase):
 
     def storage_rows(self, first_row: int, n_rows: int, out=None, stream=None):
         """Rows [first_row, first_row + n_rows) as push_vector_data would receive them (encoded_storage.rs:17-25)."""
-        nb = self.get_quantized_vector_size_from_params(self._vp, self._store)
+        nb = self.get_quantized_vector_size_from_params(self._vp, self._store, self._encoding)
         check_same_device(self._device, out)
         buf, ret = out_buf(out, n_rows * nb, np.uint8)
         check(_lib.lib().qamd_bin_export_rows_range(self._h, int(first_row), int(n_rows), buf.ptr, buf.mem,

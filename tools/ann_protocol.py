@@ -175,6 +175,10 @@ def main():
     ap.add_argument("--bin-query-bits", default="1", metavar="BITS[,BITS]",
                     help="binary: also search with 4- / 8-bit scalar queries against the same one-bit rows (DESIGN 3.2d), "
                          "e.g. 1,4,8; each bit count past 1 adds a gpu_query_bits_N entry to the binary record")
+    ap.add_argument("--bin-encodings", default="one", metavar="one[,two[,two:T]]",
+                    help="binary: a record per row encoding: one = the reference's sign bit; two = two-bit rows with "
+                         "thresholds mean -+ 0.43 deviations per dimension (DESIGN 3.2e); two:T = the same with t = T.  "
+                         "Two-bit records have no scalar-query entries and no CPU loop (the oracle restates the reference)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     query_bits = [int(x) for x in args.bin_query_bits.split(",")]
@@ -222,7 +226,14 @@ def main():
                     variants.append((f"pq chunk {args.pq_chunk}, centroids trained on a RANDOM sample (the reference's draw)",
                                      qa.EncodedVectorsPQ.encode(data, vp, args.pq_chunk, centroids=cen), extra))
                 else:
-                    variants.append(("binary", qa.EncodedVectorsBin.encode(data, vp), {}))
+                    for how in args.bin_encodings.split(","):
+                        if how == "one":
+                            variants.append(("binary", qa.EncodedVectorsBin.encode(data, vp), {}))
+                            continue
+                        t = float(how.split(":")[1]) if ":" in how else 0.43
+                        thr = qa.EncodedVectorsBin.thresholds_from_stats(*qa.EncodedVectorsBin.find_stats(data), t)
+                        enc = qa.EncodedVectorsBin.encode(data, vp, encoding=qa.BinaryEncoding.TwoBits, thresholds=thr)
+                        variants.append((f"binary two-bit rows, t = {t:g}", enc, {"two_bit": True}))
                 torch.cuda.synchronize()
                 encode_s = time.perf_counter() - t0
                 for name, enc, extra in variants:
@@ -230,7 +241,7 @@ def main():
                         enc.topk(enc.encode_query(q_host[0]), 30, largest=largest)
                     gpu, gpu_ids = run_gpu(enc, q_host, truth, largest)
                     rec = dict(base, quantizer=name, gpu=gpu, encode_seconds_all_variants=round(encode_s, 3))
-                    if kind == "binary":
+                    if kind == "binary" and not extra.get("two_bit"):
                         for bits in query_bits:
                             if bits != 1:
                                 kw = {"query_bits": bits}
@@ -242,7 +253,7 @@ def main():
                             enc.topk_rescored(enc.encode_query(q_host[0]), orig, q_host[0], 30, args.rescore, largest=largest)
                         rec["gpu_rescored"] = run_gpu_rescored(enc, orig, q_host, truth, largest, args.rescore)
                         rec["gpu_rescored"]["orig_dtype"] = orig.dtype
-                    if args.cpu_queries > 0:
+                    if args.cpu_queries > 0 and not extra.get("two_bit"):
                         rec["cpu_oracle_loop"] = run_cpu(kind, enc, q_host[: args.cpu_queries], truth, largest, gpu_ids, extra)
                     emit(rec)
                 del variants
