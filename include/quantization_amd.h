@@ -343,9 +343,10 @@ QAMD_API qamd_status qamd_bin_load(const char *data_path, const char *meta_path,
  *   - Thresholds (host, f64, single operations): mean = S / n, var = Q / n - mean * mean (both 0 for n = 0), var = 0
  *     unless var > 0, sd = sqrt(var), lo = (float)(mean - t * sd), hi = (float)(mean + t * sd).  Default t = 0.43 (near
  *     the terciles of a normal column; not validated on real embeddings).
- * Out of scope: the qamd_bin_sharded_* handles stay one-bit; scalar (4- / 8-bit) queries against two-bit rows are refused
- * (QAMD_ERR_ARGUMENTS: centred codes against a shifted, scaled store are a separate design); a 1.5-bit encoding; bench.py
- * (it measures one-bit stores). */
+ * Out of scope: the qamd_bin_sharded_* handles stay one-bit; a 1.5-bit encoding; bench.py (it measures one-bit stores).
+ * Scalar (4- / 8-bit) queries against two-bit rows come from qamd_bin_encode_query_scalar_w / _batch_scalar_w below
+ * (DESIGN.md 3.2f); the unweighted qamd_bin_encode_query_scalar / _batch_scalar refuse a two-bit handle
+ * (QAMD_ERR_ARGUMENTS). */
 typedef enum { QAMD_BIN_ONE_BIT = 0, QAMD_BIN_TWO_BITS = 1 } qamd_bin_encoding;
 QAMD_API uint64_t qamd_bin_quantized_vector_size_enc(const qamd_vector_parameters *vp, qamd_bits_store store,
                                                      qamd_bin_encoding encoding);
@@ -409,6 +410,22 @@ QAMD_API qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query
 QAMD_API qamd_status qamd_bin_encode_query_scalar(const qamd_bin *h, const float *query, uint64_t qdim,
                                                   qamd_mem query_mem, uint32_t bits, void *stream,
                                                   qamd_bin_query **query_io);
+/* Weighted scalar queries: 4- or 8-bit queries against TWO-BIT rows.  The reference has NO counterpart; DESIGN.md 3.2f is
+ * the specification.  A two-bit row stands for about mean_i + sd_i * (level_i - 1) in column i, and sd_i is proportional to
+ * h_i = hi_i - lo_i, so the codes come from w_i = q_i * h_i (h_i = 0 where it is not finite, a NaN w_i = 0) exactly as
+ * qamd_bin_encode_query_scalar takes them from q_i (a = max |w_i| over the finite w_i), and the code of dimension i sits
+ * at bit i AND bit dim + i of each of the `bits` planes, which are rows of code_bits = 2 dim bits.  Every scoring call
+ * then serves the query as it serves a scalar query against one-bit rows of code_bits dimensions: X = sum_b 2^b
+ * popcount(plane_b xor row) adds 2 c_i, L or 2 (L - c_i) for a dimension at level 0, 1 or 2, and the score is
+ * calculate_metric on X with code_bits * L for dim.  qdim must be the handle's dim; dims above 32 896 at 8 bits and
+ * 559 240 at 4 (code_bits * L past f32's exact integers) and bits other than 1, 4, 8 are QAMD_ERR_ARGUMENTS; bits = 1 is
+ * qamd_bin_encode_query.  On a one-bit handle the call IS qamd_bin_encode_query_scalar (h_i = 1), bit for bit, so a
+ * caller need not branch on the encoding.  Arguments and reuse of *query_io as there; one object may move between bit
+ * counts and between the two calls.  Recall in a numpy model on synthetic data only: not validated on
+ * real embeddings. */
+QAMD_API qamd_status qamd_bin_encode_query_scalar_w(const qamd_bin *h, const float *query, uint64_t qdim,
+                                                    qamd_mem query_mem, uint32_t bits, void *stream,
+                                                    qamd_bin_query **query_io);
 /* No counterpart in the reference: *bits = the number of bit planes, *max_abs = a; a query from
  * qamd_bin_encode_query gives 1 and 0.  Either pointer may be NULL. */
 QAMD_API qamd_status qamd_bin_query_info(const qamd_bin_query *q, uint32_t *bits, float *max_abs);
@@ -462,6 +479,14 @@ QAMD_API qamd_status qamd_bin_encode_query_batch(const qamd_bin *h, const float 
 QAMD_API qamd_status qamd_bin_encode_query_batch_scalar(const qamd_bin *h, const float *queries, uint64_t n_queries,
                                                         uint64_t qdim, qamd_mem queries_mem, uint32_t bits, void *stream,
                                                         qamd_bin_query_batch **batch_io);
+/* A batch of weighted scalar queries: query q is exactly what qamd_bin_encode_query_scalar_w gives for row
+ * q of `queries` (a per query), and every batch call gives for it what the single-query call gives.  The matrix-core
+ * image holds one int8 per bit position of a row (d_i at byte i and byte dim + i) and C = 2 sum c_i, so the gates and
+ * routes above hold with code_bits for dim: rows of 64 .. 4992 bits, that is dim <= 2496.  On a one-bit handle the call
+ * is qamd_bin_encode_query_batch_scalar. */
+QAMD_API qamd_status qamd_bin_encode_query_batch_scalar_w(const qamd_bin *h, const float *queries, uint64_t n_queries,
+                                                          uint64_t qdim, qamd_mem queries_mem, uint32_t bits, void *stream,
+                                                          qamd_bin_query_batch **batch_io);
 /* No counterpart in the reference: *bits = bits per query dimension (1 for a batch from
  * qamd_bin_encode_query_batch), *n_queries = the queries it holds.  Either pointer may be NULL. */
 QAMD_API qamd_status qamd_bin_query_batch_info(const qamd_bin_query_batch *b, uint32_t *bits, uint64_t *n_queries);

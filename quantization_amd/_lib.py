@@ -161,6 +161,9 @@ def lib() -> C.CDLL:
         "qamd_bin_from_rows_enc": (i32, [vp, i32, VP, i32, i32, vp, vp, vp, pp]),
         "qamd_bin_get_encoding": (i32, [vp, C.POINTER(i32), C.POINTER(u64)]),
         "qamd_bin_get_thresholds": (i32, [vp, vp, vp]),
+        # binary, weighted scalar queries against two-bit rows
+        "qamd_bin_encode_query_scalar_w": (i32, [vp, vp, u64, i32, u32, vp, pp]),
+        "qamd_bin_encode_query_batch_scalar_w": (i32, [vp, vp, u64, u64, i32, u32, vp, pp]),
         # pq
         "qamd_pq_quantized_vector_size": (u64, [VP, u64]),
         "qamd_pq_encode": (i32, [vp, i32, VP, u64, vp, u32, STOP_FN, vp, vp, pp]),

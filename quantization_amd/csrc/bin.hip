@@ -766,6 +766,96 @@ __global__ __launch_bounds__(kBlock) void bin_encode_thr_kernel(const float *__r
     }
 }
 
+// Weighted scalar query encoding against two-bit rows (the reference has no counterpart), one workgroup per
+// query: bin_encode_scalar_kernel on w_i = q_i * (hi_i - lo_i) instead of q_i, with the code of dimension i at BOTH bit i and
+// bit dim + i of every plane - the row's two planes (thr = lo | hi, 2 dim floats).  A row of levels l_i then scores
+// X = sum_i (l_i = 0: 2 c_i, 1: L, 2: 2 (L - c_i)), the order of const + sum_i (l_i - 1) w_i.  h_i = hi_i - lo_i counts as 0
+// when it is not finite (every row is at level 1 there), a NaN w_i as 0; a = max |w_i| over the finite w_i.  Single f32
+// operations in this order: the product and the sum after it must stay two instructions (no v_fma).
+// Pass 2 walks the 2 dim bit positions 64 per step; lane j takes its dimension's q, lo and hi again (L2 hits) rather than
+// shift and merge the second copy as bin_encode_thr_kernel does.  Every dword of every plane is written, pad bits as
+// zeros.  codes != nullptr: the int8 image has one byte per bit position (d_i twice) and C = 2 sum c_i.
+__global__ __launch_bounds__(kBlock) void bin_encode_scalar_thr_kernel(const float *__restrict__ query, uint32_t dim,
+                                                                      const float *__restrict__ thr, uint32_t row_words,
+                                                                      uint32_t bits, uint32_t *__restrict__ planes,
+                                                                      uint32_t plane_words, float *__restrict__ max_abs,
+                                                                      int8_t *__restrict__ codes, uint32_t code_pitch) {
+    __shared__ float wave_max[kBlock / 64];
+    __shared__ uint32_t wave_sum[kBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inf = __builtin_huge_valf();
+    query += (size_t)blockIdx.x * dim;
+    planes += (size_t)blockIdx.x * plane_words;
+    auto weighted = [&](uint32_t i) {
+        float h = thr[dim + i] - thr[i];
+        if (!(fabsf(h) < inf)) h = 0.0f;  // inf, and NaN from inf - inf
+        const float w = query[i] * h;
+        return w != w ? 0.0f : w;  // (inf * 0 too)
+    };
+    float a = 0.0f;
+    for (uint32_t i = threadIdx.x; i < dim; i += kBlock) {
+        const float v = fabsf(weighted(i));
+        if (v < inf && v > a) a = v;
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) a = fmaxf(a, __shfl_xor(a, o));
+    if (lane == 0) wave_max[wave] = a;
+    __syncthreads();
+    a = wave_max[0];
+#pragma unroll
+    for (int w = 1; w < kBlock / 64; w++) a = fmaxf(a, wave_max[w]);
+    if (threadIdx.x == 0) max_abs[blockIdx.x] = a;
+    const uint32_t L = (1u << bits) - 1u, code_bits = 2u * dim;
+    const float scale = a == 0.0f ? 0.0f : (float)L / (a + a);
+    // 64 bit positions per step; the code image is at least as long as a plane (whole 128-entry blocks)
+    const uint32_t steps = codes ? (code_pitch - 16) / 64 : (row_words + 1) / 2;
+    uint32_t csum = 0;
+    for (uint32_t st = wave; st < steps; st += kBlock / 64) {
+        const uint32_t j = st * 64 + lane;
+        uint32_t c = 0;
+        if (j < code_bits) {
+            const float v = weighted(j < dim ? j : j - dim);
+            if (a == 0.0f) {
+                c = (L + 1u) / 2u;
+            } else {
+                const float t = (v + a) * scale;
+                const uint32_t r = (uint32_t)(t + 0.5f);
+                c = r < L ? r : L;
+            }
+            if (v == inf) c = L;
+            if (v == -inf) c = 0;
+        }
+        if (codes) {
+            codes[(size_t)blockIdx.x * code_pitch + j] = j < code_bits ? (int8_t)((int)c - (int)((L + 1u) / 2u)) : (int8_t)0;
+            csum += c;
+        }
+        unsigned long long mine = 0;
+        for (uint32_t b = 0; b < bits; b++) {
+            const unsigned long long m = __ballot((c >> b) & 1u);
+            if ((uint32_t)lane == b) mine = m;
+        }
+        if ((uint32_t)lane < bits) {
+            uint32_t *dst = planes + (size_t)lane * row_words;
+            const uint32_t w = st * 2;
+            if (w < row_words) dst[w] = (uint32_t)mine;
+            if (w + 1 < row_words) dst[w + 1] = (uint32_t)(mine >> 32);
+        }
+    }
+    if (codes) {  // C = 2 sum c_i <= 255 * 4992 on the matrix route, < 2^24 anywhere
+#pragma unroll
+        for (int o = 32; o; o >>= 1) csum += (uint32_t)__shfl_xor((int)csum, o);
+        if (lane == 0) wave_sum[wave] = csum;
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            uint32_t total = 0;
+#pragma unroll
+            for (int w = 0; w < kBlock / 64; w++) total += wave_sum[w];
+            reinterpret_cast<uint32_t *>(codes + (size_t)blockIdx.x * code_pitch + (code_pitch - 16))[threadIdx.x] =
+                threadIdx.x == 0 ? total : 0u;
+        }
+    }
+}
+
 int grid_for(uint64_t work_items, uint64_t per_block, int blocks_per_cu) {
     uint64_t want = (work_items + per_block - 1) / per_block;
     uint64_t cap = (uint64_t)device_info().cu_count * blocks_per_cu;
@@ -1477,21 +1567,30 @@ qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query, uint64_
 // Where a scalar query keeps max_abs, and its f32 staging area, behind `bits` planes of ds bytes.
 static uint64_t scalar_max_abs_at(uint64_t ds, uint32_t bits) { return round_up(bits * ds, 16) + 16; }
 
-// The reference has no counterpart (its query is one bit per dimension): DESIGN 3.2d is the specification.
-qamd_status qamd_bin_encode_query_scalar(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem,
-                                         uint32_t bits, void *stream, qamd_bin_query **query_io) {
+// The most dimensions a `bits`-bit scalar query may have: code_bits * (2^bits - 1) and every sum below it must be exact
+// in f32, so the row's bits stay at or under 65 792 (8 bits) / 1 118 481 (4 bits) - half as many dimensions on two-bit rows.
+static uint64_t scalar_max_dim(uint32_t bits, bool two) { return (bits == 8 ? 65792u : 1118481u) / (two ? 2u : 1u); }
+
+// The reference has no counterpart (its query is one bit per dimension): DESIGN 3.2d is the specification, 3.2f that of
+// `weighted` on two-bit rows (codes from q_i * (hi_i - lo_i), sized by code_bits).  On one-bit rows both are the same call.
+static qamd_status encode_query_scalar(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem, uint32_t bits,
+                                       bool weighted, void *stream, qamd_bin_query **query_io) {
     if (bits == 1) return qamd_bin_encode_query(h, query, qdim, query_mem, stream, query_io);
     if (bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
     if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    if (h->encoding == QAMD_BIN_TWO_BITS) return fail(QAMD_ERR_ARGUMENTS, "two-bit rows take no scalar queries");
-    // dim * (2^bits - 1) and every sum below it must be exact in f32: both limits keep it under 2^24
-    const uint64_t max_dim = bits == 8 ? 65792 : 1118481;
+    const bool two = h->encoding == QAMD_BIN_TWO_BITS;
+    if (two && !weighted)
+        return fail(QAMD_ERR_ARGUMENTS, "two-bit rows take scalar queries through qamd_bin_encode_query_scalar_w");
+    if (two && qdim != h->vp.dim)
+        return fail(QAMD_ERR_ARGUMENTS, "a query of %llu dimensions against thresholds of %llu", (unsigned long long)qdim,
+                    (unsigned long long)h->vp.dim);
+    const uint64_t max_dim = scalar_max_dim(bits, two);
     if (qdim > max_dim)
         return fail(QAMD_ERR_ARGUMENTS, "a %u-bit query has at most %llu dimensions, not %llu", bits,
                     (unsigned long long)max_dim, (unsigned long long)qdim);
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
-    const uint64_t nb = row_bytes_of(qdim, h->store), ds = device_stride_of(nb);
+    const uint64_t nb = row_bytes_of(two ? 2 * qdim : qdim, h->store), ds = device_stride_of(nb);
     const uint64_t max_abs_at = scalar_max_abs_at(ds, bits), need = max_abs_at + 16 + qdim * 4 + 16;
     qamd_bin_query *q = *query_io;
     std::unique_ptr<qamd_bin_query> fresh;
@@ -1513,13 +1612,27 @@ qamd_status qamd_bin_encode_query_scalar(const qamd_bin *h, const float *query, 
         QAMD_TRY(copy_in(stage, query, QAMD_MEM_HOST, qdim * 4, s));
         q_dev = stage;
     }
-    hipLaunchKernelGGL(bin_encode_scalar_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint32_t)qdim, (uint32_t)(ds / 4), bits,
-                       q->buf.as<uint32_t>(), 0u, reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at),
-                       static_cast<int8_t *>(nullptr), 0u);
+    float *max_abs = reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at);
+    if (two)
+        hipLaunchKernelGGL(bin_encode_scalar_thr_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint32_t)qdim, h->thr.as<float>(),
+                           (uint32_t)(ds / 4), bits, q->buf.as<uint32_t>(), 0u, max_abs, static_cast<int8_t *>(nullptr), 0u);
+    else
+        hipLaunchKernelGGL(bin_encode_scalar_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint32_t)qdim, (uint32_t)(ds / 4), bits,
+                           q->buf.as<uint32_t>(), 0u, max_abs, static_cast<int8_t *>(nullptr), 0u);
     QAMD_HIP(hipGetLastError());
     QAMD_TRY(q->ready.record(s));
     if (fresh) *query_io = fresh.release();
     return QAMD_OK;
+}
+
+qamd_status qamd_bin_encode_query_scalar(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem,
+                                         uint32_t bits, void *stream, qamd_bin_query **query_io) {
+    return encode_query_scalar(h, query, qdim, query_mem, bits, false, stream, query_io);
+}
+
+qamd_status qamd_bin_encode_query_scalar_w(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem,
+                                           uint32_t bits, void *stream, qamd_bin_query **query_io) {
+    return encode_query_scalar(h, query, qdim, query_mem, bits, true, stream, query_io);
 }
 
 qamd_status qamd_bin_query_info(const qamd_bin_query *q, uint32_t *bits, float *max_abs) {
@@ -2809,23 +2922,31 @@ qamd_status qamd_bin_encode_query_batch(const qamd_bin *h, const float *queries,
     return QAMD_OK;
 }
 
+}  // extern "C"
+
 // The reference has no counterpart: DESIGN 3.2d.  Query q of the batch is qamd_bin_encode_query_scalar of row q of
 // `queries` (the same kernel, one workgroup per query), kept as its planes and as the matrix cores' int8 image.
-qamd_status qamd_bin_encode_query_batch_scalar(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
-                                               qamd_mem queries_mem, uint32_t bits, void *stream,
-                                               qamd_bin_query_batch **batch_io) {
+// `weighted` on two-bit rows: DESIGN 3.2f, the planes and the image sized by code_bits.
+static qamd_status encode_query_batch_scalar(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
+                                             qamd_mem queries_mem, uint32_t bits, bool weighted, void *stream,
+                                             qamd_bin_query_batch **batch_io) {
     if (bits == 1) return qamd_bin_encode_query_batch(h, queries, n_queries, qdim, queries_mem, stream, batch_io);
     if (bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
     if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    if (h->encoding == QAMD_BIN_TWO_BITS) return fail(QAMD_ERR_ARGUMENTS, "two-bit rows take no scalar queries");
-    const uint64_t max_dim = bits == 8 ? 65792 : 1118481;  // as qamd_bin_encode_query_scalar: dim * L stays exact in f32
+    const bool two = h->encoding == QAMD_BIN_TWO_BITS;
+    if (two && !weighted)
+        return fail(QAMD_ERR_ARGUMENTS, "two-bit rows take scalar queries through qamd_bin_encode_query_batch_scalar_w");
+    if (two && n_queries && qdim != h->vp.dim)
+        return fail(QAMD_ERR_ARGUMENTS, "queries of %llu dimensions against thresholds of %llu", (unsigned long long)qdim,
+                    (unsigned long long)h->vp.dim);
+    const uint64_t max_dim = scalar_max_dim(bits, two);  // as the single query: code_bits * L stays exact in f32
     if (qdim > max_dim)
         return fail(QAMD_ERR_ARGUMENTS, "a %u-bit query has at most %llu dimensions, not %llu", bits,
                     (unsigned long long)max_dim, (unsigned long long)qdim);
     if (n_queries > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "too many queries");
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
-    const uint64_t nb = row_bytes_of(qdim, h->store), ds = device_stride_of(nb);
+    const uint64_t nb = row_bytes_of(two ? 2 * qdim : qdim, h->store), ds = device_stride_of(nb);
     if (n_queries && nb != h->nb)
         return fail(QAMD_ERR_ARGUMENTS, "queries have %llu bytes, rows have %llu", (unsigned long long)nb,
                     (unsigned long long)h->nb);
@@ -2853,14 +2974,36 @@ qamd_status qamd_bin_encode_query_batch_scalar(const qamd_bin *h, const float *q
         const void *qd = nullptr;
         bool staged = false;
         if (qdim) QAMD_TRY(local_view(queries, queries_mem, n_queries * qdim * 4, qtmp, s, &qd, &staged));
-        hipLaunchKernelGGL(bin_encode_scalar_kernel, dim3((unsigned)n_queries), dim3(kBlock), 0, s, static_cast<const float *>(qd),
-                           (uint32_t)qdim, (uint32_t)(ds / 4), bits, b->planes.as<uint32_t>(), (uint32_t)(p_stride / 4),
-                           b->max_abs.as<float>(), b->codes.as<int8_t>(), (uint32_t)code_pitch);
+        if (two)
+            hipLaunchKernelGGL(bin_encode_scalar_thr_kernel, dim3((unsigned)n_queries), dim3(kBlock), 0, s,
+                               static_cast<const float *>(qd), (uint32_t)qdim, h->thr.as<float>(), (uint32_t)(ds / 4), bits,
+                               b->planes.as<uint32_t>(), (uint32_t)(p_stride / 4), b->max_abs.as<float>(), b->codes.as<int8_t>(),
+                               (uint32_t)code_pitch);
+        else
+            hipLaunchKernelGGL(bin_encode_scalar_kernel, dim3((unsigned)n_queries), dim3(kBlock), 0, s,
+                               static_cast<const float *>(qd), (uint32_t)qdim, (uint32_t)(ds / 4), bits, b->planes.as<uint32_t>(),
+                               (uint32_t)(p_stride / 4), b->max_abs.as<float>(), b->codes.as<int8_t>(), (uint32_t)code_pitch);
         QAMD_HIP(hipGetLastError());
         if (staged) QAMD_HIP(hipStreamSynchronize(s));
     }
     if (fresh) *batch_io = fresh.release();
     return QAMD_OK;
+}
+
+extern "C" {
+
+qamd_status qamd_bin_encode_query_batch_scalar(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
+                                               qamd_mem queries_mem, uint32_t bits, void *stream,
+                                               qamd_bin_query_batch **batch_io) {
+    return encode_query_batch_scalar(h, queries, n_queries, qdim, queries_mem, bits, false, stream, batch_io);
+}
+
+// on two-bit rows query q is qamd_bin_encode_query_scalar_w of row q of `queries`, its int8 image one byte
+// per bit position of a row; on one-bit rows the call above.
+qamd_status qamd_bin_encode_query_batch_scalar_w(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
+                                                 qamd_mem queries_mem, uint32_t bits, void *stream,
+                                                 qamd_bin_query_batch **batch_io) {
+    return encode_query_batch_scalar(h, queries, n_queries, qdim, queries_mem, bits, true, stream, batch_io);
 }
 
 qamd_status qamd_bin_query_batch_info(const qamd_bin_query_batch *b, uint32_t *bits, uint64_t *n_queries) {

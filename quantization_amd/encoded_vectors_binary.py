@@ -178,30 +178,35 @@ class EncodedVectorsBin(EncodedVectorsBase):
                                                         C.c_void_p(hi.ctypes.data)))
         return lo, hi
 
-    def encode_query(self, query, reuse=None, stream=None, *, query_bits: int = 1):
+    def encode_query(self, query, reuse=None, stream=None, *, query_bits: int = 1, weighted: bool = False):
         """EncodedVectors::encode_query (:288-291).  query_bits = 4 or 8 keeps that many bits per query dimension
         against the same one-bit rows (no counterpart in the reference); every single-query scoring
-        call takes the result."""
-        if query_bits == 1:
+        call takes the result.  weighted = True: against two-bit rows the codes come from
+        q_i * (hi_i - lo_i) and sit at both planes of a row; against one-bit rows it changes nothing.  Without it a
+        two-bit store refuses query_bits other than 1."""
+        if query_bits == 1 and not weighted:
             return super().encode_query(query, reuse, stream)
         check_same_device(self._device, query)
         buf = in_buf(query, np.float32)
         n = int(np.prod(tuple(query.shape))) if hasattr(query, "shape") else len(query)
         h = reuse._h if reuse is not None else C.c_void_p()
-        check(_lib.lib().qamd_bin_encode_query_scalar(self._h, buf.ptr, n, buf.mem, int(query_bits), stream_ptr(stream),
-                                                      C.byref(h)))
+        L = _lib.lib()
+        fn = L.qamd_bin_encode_query_scalar_w if weighted else L.qamd_bin_encode_query_scalar
+        check(fn(self._h, buf.ptr, n, buf.mem, int(query_bits), stream_ptr(stream), C.byref(h)))
         return reuse if reuse is not None else self._query_cls(h)
 
-    def encode_query_batch(self, queries, reuse=None, stream=None, *, query_bits: int = 1):
+    def encode_query_batch(self, queries, reuse=None, stream=None, *, query_bits: int = 1, weighted: bool = False):
         """encode_query for a [n_queries, dim] block of queries.  query_bits = 4 or 8: query q of the batch is
-        encode_query(queries[q], query_bits=...); score_batch, score_ids_batch, topk_batch and
-        topk_batch_rescored take either kind of batch."""
+        encode_query(queries[q], query_bits=...), with weighted = True that of
+        encode_query(queries[q], query_bits=..., weighted=True); score_batch, score_ids_batch,
+        topk_batch and topk_batch_rescored take either kind of batch."""
         nq, qdim = int(queries.shape[0]), int(queries.shape[1])
         check_same_device(self._device, queries)
         buf = in_buf(queries, np.float32)
         h = reuse._h if reuse is not None else C.c_void_p()
-        check(_lib.lib().qamd_bin_encode_query_batch_scalar(self._h, buf.ptr, nq, qdim, buf.mem, int(query_bits),
-                                                            stream_ptr(stream), C.byref(h)))
+        L = _lib.lib()
+        fn = L.qamd_bin_encode_query_batch_scalar_w if weighted else L.qamd_bin_encode_query_batch_scalar
+        check(fn(self._h, buf.ptr, nq, qdim, buf.mem, int(query_bits), stream_ptr(stream), C.byref(h)))
         if reuse is not None:
             reuse.n_queries = nq
             return reuse

@@ -173,12 +173,14 @@ def main():
                     help="with --rescore: what the store of originals keeps (f32 borrows the data tensor; f16 / bf16 are "
                          "narrowed copies of it, half the HBM)")
     ap.add_argument("--bin-query-bits", default="1", metavar="BITS[,BITS]",
-                    help="binary: also search with 4- / 8-bit scalar queries against the same one-bit rows (DESIGN 3.2d), "
-                         "e.g. 1,4,8; each bit count past 1 adds a gpu_query_bits_N entry to the binary record")
+                    help="binary: also search with 4- / 8-bit scalar queries against the same rows, e.g. 1,4,8; each bit "
+                         "count past 1 adds a gpu_query_bits_N entry to a one-bit record (DESIGN 3.2d) and a "
+                         "gpu_weighted_query_bits_N entry - weighted queries, DESIGN 3.2f - to a two-bit record")
     ap.add_argument("--bin-encodings", default="one", metavar="one[,two[,two:T]]",
                     help="binary: a record per row encoding: one = the reference's sign bit; two = two-bit rows with "
                          "thresholds mean -+ 0.43 deviations per dimension (DESIGN 3.2e); two:T = the same with t = T.  "
-                         "Two-bit records have no scalar-query entries and no CPU loop (the oracle restates the reference)")
+                         "Two-bit records have no CPU loop (the oracle restates the reference); with --bin-query-bits "
+                         "4,8 they carry weighted scalar-query entries")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     query_bits = [int(x) for x in args.bin_query_bits.split(",")]
@@ -241,13 +243,15 @@ def main():
                         enc.topk(enc.encode_query(q_host[0]), 30, largest=largest)
                     gpu, gpu_ids = run_gpu(enc, q_host, truth, largest)
                     rec = dict(base, quantizer=name, gpu=gpu, encode_seconds_all_variants=round(encode_s, 3))
-                    if kind == "binary" and not extra.get("two_bit"):
+                    if kind == "binary":
+                        two_bit = bool(extra.get("two_bit"))  # two-bit rows take the weighted queries of DESIGN 3.2f
                         for bits in query_bits:
                             if bits != 1:
-                                kw = {"query_bits": bits}
+                                kw = {"query_bits": bits, "weighted": True} if two_bit else {"query_bits": bits}
                                 for _ in range(3):
                                     enc.topk(enc.encode_query(q_host[0], **kw), 30, largest=largest)
-                                rec[f"gpu_query_bits_{bits}"] = run_gpu(enc, q_host, truth, largest, kw)[0]
+                                key = f"gpu_weighted_query_bits_{bits}" if two_bit else f"gpu_query_bits_{bits}"
+                                rec[key] = run_gpu(enc, q_host, truth, largest, kw)[0]
                     if orig is not None:
                         for _ in range(3):
                             enc.topk_rescored(enc.encode_query(q_host[0]), orig, q_host[0], 30, args.rescore, largest=largest)
