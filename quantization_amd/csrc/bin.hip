@@ -485,91 +485,6 @@ __global__ __launch_bounds__(kBlock) void bin_encode_kernel(const float *__restr
     }
 }
 
-// Scalar query encoding (the reference has no counterpart), one workgroup per query: a = max |q_i| over the
-// query's finite entries, then c_i = min(L, (u32)((q_i + a) * (L / (a + a)) + 0.5f)) with L = 2^bits - 1 - single f32
-// operations in this order, the division hipcc's correctly rounded one - and plane b = bit b of every c_i in the rows' bit
-// order (one ballot per plane and 64 entries).  Every dword of every plane is written, pad bits as zeros.
-// Workgroup g takes query g: its floats at query + g * dim, its planes at planes + g * plane_words, its max_abs at
-// max_abs[g].  codes != nullptr (a query batch): also the matrix-core image of the query at codes + g * code_pitch - the
-// centred codes d_i = c_i - (L + 1) / 2 as int8, one byte per dimension, zero bytes from dim to code_pitch - 16, and
-// C = sum c_i as a u32 at code_pitch - 16 (bin_gemm_rs_kernel copies the whole pitch into its LDS tile).
-__global__ __launch_bounds__(kBlock) void bin_encode_scalar_kernel(const float *__restrict__ query, uint32_t dim,
-                                                                  uint32_t row_words, uint32_t bits,
-                                                                  uint32_t *__restrict__ planes, uint32_t plane_words,
-                                                                  float *__restrict__ max_abs, int8_t *__restrict__ codes,
-                                                                  uint32_t code_pitch) {
-    __shared__ float wave_max[kBlock / 64];
-    __shared__ uint32_t wave_sum[kBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float inf = __builtin_huge_valf();
-    query += (size_t)blockIdx.x * dim;
-    planes += (size_t)blockIdx.x * plane_words;
-    float a = 0.0f;
-    for (uint32_t i = threadIdx.x; i < dim; i += kBlock) {
-        const float v = fabsf(query[i]);
-        if (v < inf && v > a) a = v;  // NaN fails both
-    }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) a = fmaxf(a, __shfl_xor(a, o));
-    if (lane == 0) wave_max[wave] = a;
-    __syncthreads();
-    a = wave_max[0];
-#pragma unroll
-    for (int w = 1; w < kBlock / 64; w++) a = fmaxf(a, wave_max[w]);
-    if (threadIdx.x == 0) max_abs[blockIdx.x] = a;
-    const uint32_t L = (1u << bits) - 1u;
-    const float scale = a == 0.0f ? 0.0f : (float)L / (a + a);
-    // 64 entries per step; the code image is at least as long as a plane (whole 128-entry blocks)
-    const uint32_t steps = codes ? (code_pitch - 16) / 64 : (row_words + 1) / 2;
-    uint32_t csum = 0;
-    for (uint32_t st = wave; st < steps; st += kBlock / 64) {
-        const uint32_t i = st * 64 + lane;
-        uint32_t c = 0;
-        if (i < dim) {
-            float v = query[i];
-            if (v != v) v = 0.0f;
-            if (a == 0.0f) {
-                c = (L + 1u) / 2u;
-            } else {
-                const float t = (v + a) * scale;
-                const uint32_t r = (uint32_t)(t + 0.5f);
-                c = r < L ? r : L;
-            }
-            if (v == inf) c = L;
-            if (v == -inf) c = 0;
-        }
-        if (codes) {
-            codes[(size_t)blockIdx.x * code_pitch + i] = i < dim ? (int8_t)((int)c - (int)((L + 1u) / 2u)) : (int8_t)0;
-            csum += c;
-        }
-        unsigned long long mine = 0;
-        for (uint32_t b = 0; b < bits; b++) {
-            const unsigned long long m = __ballot((c >> b) & 1u);
-            if ((uint32_t)lane == b) mine = m;
-        }
-        if ((uint32_t)lane < bits) {
-            uint32_t *dst = planes + (size_t)lane * row_words;
-            const uint32_t w = st * 2;
-            if (w < row_words) dst[w] = (uint32_t)mine;
-            if (w + 1 < row_words) dst[w + 1] = (uint32_t)(mine >> 32);
-        }
-    }
-    if (codes) {  // C = sum c_i <= 255 * 1118481 < 2^32
-#pragma unroll
-        for (int o = 32; o; o >>= 1) csum += (uint32_t)__shfl_xor((int)csum, o);
-        if (lane == 0) wave_sum[wave] = csum;
-        __syncthreads();
-        if (threadIdx.x < 4) {
-            uint32_t total = 0;
-#pragma unroll
-            for (int w = 0; w < kBlock / 64; w++) total += wave_sum[w];
-            // the last 16 bytes of the pitch: C, then three zero dwords
-            reinterpret_cast<uint32_t *>(codes + (size_t)blockIdx.x * code_pitch + (code_pitch - 16))[threadIdx.x] =
-                threadIdx.x == 0 ? total : 0u;
-        }
-    }
-}
-
 // encode_vector, streaming form for stores whose rows are whole 128-bit words with no row
 // padding (dim % 128 == 0): the batch is one flat stream of floats -> bits.  One wave per
 // 16 KiB tile; wave-load j reads 64 consecutive float4 (nt), each lane turns its four signs
@@ -766,35 +681,45 @@ __global__ __launch_bounds__(kBlock) void bin_encode_thr_kernel(const float *__r
     }
 }
 
-// Weighted scalar query encoding against two-bit rows (the reference has no counterpart), one workgroup per
-// query: bin_encode_scalar_kernel on w_i = q_i * (hi_i - lo_i) instead of q_i, with the code of dimension i at BOTH bit i and
-// bit dim + i of every plane - the row's two planes (thr = lo | hi, 2 dim floats).  A row of levels l_i then scores
-// X = sum_i (l_i = 0: 2 c_i, 1: L, 2: 2 (L - c_i)), the order of const + sum_i (l_i - 1) w_i.  h_i = hi_i - lo_i counts as 0
-// when it is not finite (every row is at level 1 there), a NaN w_i as 0; a = max |w_i| over the finite w_i.  Single f32
-// operations in this order: the product and the sum after it must stay two instructions (no v_fma).
-// Pass 2 walks the 2 dim bit positions 64 per step; lane j takes its dimension's q, lo and hi again (L2 hits) rather than
-// shift and merge the second copy as bin_encode_thr_kernel does.  Every dword of every plane is written, pad bits as
-// zeros.  codes != nullptr: the int8 image has one byte per bit position (d_i twice) and C = 2 sum c_i.
-__global__ __launch_bounds__(kBlock) void bin_encode_scalar_thr_kernel(const float *__restrict__ query, uint32_t dim,
-                                                                      const float *__restrict__ thr, uint32_t row_words,
-                                                                      uint32_t bits, uint32_t *__restrict__ planes,
-                                                                      uint32_t plane_words, float *__restrict__ max_abs,
-                                                                      int8_t *__restrict__ codes, uint32_t code_pitch) {
+// Scalar query encoding (the reference has no counterpart), one workgroup per query: a = max |v_i| over the
+// finite values v_i = q_i (a NaN counts as 0), then c_i = min(L, (u32)((v_i + a) * (L / (a + a)) + 0.5f)) with
+// L = 2^bits - 1 - single f32 operations in this order, the division hipcc's correctly rounded one - and plane b = bit b
+// of the code at every bit position of a row, position i that of dimension i (one ballot per plane and 64 positions).
+// Every dword of every plane is written, pad bits as zeros.
+// WEIGHTED (two-bit rows): v_i = w_i = q_i * (hi_i - lo_i) (thr = lo | hi, 2 dim floats; hi_i - lo_i counts
+// as 0 when it is not finite: every row is at level 1 there), and the code of dimension i sits at BOTH bit i and bit
+// dim + i of every plane, the row's two planes; lane j of the second copy reads q, lo and hi again (L2 hits) rather than
+// shift and merge as bin_encode_thr_kernel does.  The product and the sum after it stay two instructions (no v_fma).
+// Workgroup g takes query g: its floats at query + g * dim, its planes at planes + g * plane_words, its max_abs at
+// max_abs[g].  codes != nullptr (a query batch): also the matrix-core image of the query at codes + g * code_pitch - the
+// centred codes d = c - (L + 1) / 2 as int8, one byte per bit position, zero bytes from there to code_pitch - 16, and C =
+// the sum of every position's code as a u32 at code_pitch - 16 (bin_gemm_rs_kernel copies the whole pitch into its LDS tile).
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void bin_encode_scalar_kernel(const float *__restrict__ query, uint32_t dim,
+                                                                  const float *__restrict__ thr, uint32_t row_words,
+                                                                  uint32_t bits, uint32_t *__restrict__ planes,
+                                                                  uint32_t plane_words, float *__restrict__ max_abs,
+                                                                  int8_t *__restrict__ codes, uint32_t code_pitch) {
     __shared__ float wave_max[kBlock / 64];
     __shared__ uint32_t wave_sum[kBlock / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inf = __builtin_huge_valf();
     query += (size_t)blockIdx.x * dim;
     planes += (size_t)blockIdx.x * plane_words;
-    auto weighted = [&](uint32_t i) {
-        float h = thr[dim + i] - thr[i];
-        if (!(fabsf(h) < inf)) h = 0.0f;  // inf, and NaN from inf - inf
-        const float w = query[i] * h;
-        return w != w ? 0.0f : w;  // (inf * 0 too)
+    auto value = [&](uint32_t i) {
+        if constexpr (WEIGHTED) {
+            float h = thr[dim + i] - thr[i];
+            if (!(fabsf(h) < inf)) h = 0.0f;  // inf, and NaN from inf - inf
+            const float w = query[i] * h;
+            return w != w ? 0.0f : w;  // (inf * 0 too)
+        } else {
+            const float v = query[i];
+            return v != v ? 0.0f : v;
+        }
     };
     float a = 0.0f;
     for (uint32_t i = threadIdx.x; i < dim; i += kBlock) {
-        const float v = fabsf(weighted(i));
+        const float v = fabsf(value(i));
         if (v < inf && v > a) a = v;
     }
 #pragma unroll
@@ -805,7 +730,7 @@ __global__ __launch_bounds__(kBlock) void bin_encode_scalar_thr_kernel(const flo
 #pragma unroll
     for (int w = 1; w < kBlock / 64; w++) a = fmaxf(a, wave_max[w]);
     if (threadIdx.x == 0) max_abs[blockIdx.x] = a;
-    const uint32_t L = (1u << bits) - 1u, code_bits = 2u * dim;
+    const uint32_t L = (1u << bits) - 1u, code_bits = WEIGHTED ? 2u * dim : dim;
     const float scale = a == 0.0f ? 0.0f : (float)L / (a + a);
     // 64 bit positions per step; the code image is at least as long as a plane (whole 128-entry blocks)
     const uint32_t steps = codes ? (code_pitch - 16) / 64 : (row_words + 1) / 2;
@@ -814,7 +739,7 @@ __global__ __launch_bounds__(kBlock) void bin_encode_scalar_thr_kernel(const flo
         const uint32_t j = st * 64 + lane;
         uint32_t c = 0;
         if (j < code_bits) {
-            const float v = weighted(j < dim ? j : j - dim);
+            const float v = value(WEIGHTED && j >= dim ? j - dim : j);
             if (a == 0.0f) {
                 c = (L + 1u) / 2u;
             } else {
@@ -841,7 +766,7 @@ __global__ __launch_bounds__(kBlock) void bin_encode_scalar_thr_kernel(const flo
             if (w + 1 < row_words) dst[w + 1] = (uint32_t)(mine >> 32);
         }
     }
-    if (codes) {  // C = 2 sum c_i <= 255 * 4992 on the matrix route, < 2^24 anywhere
+    if (codes) {  // C <= 255 * 1118481 < 2^32 (weighted: 255 * 4992 on the matrix route, < 2^24 anywhere)
 #pragma unroll
         for (int o = 32; o; o >>= 1) csum += (uint32_t)__shfl_xor((int)csum, o);
         if (lane == 0) wave_sum[wave] = csum;
@@ -850,6 +775,7 @@ __global__ __launch_bounds__(kBlock) void bin_encode_scalar_thr_kernel(const flo
             uint32_t total = 0;
 #pragma unroll
             for (int w = 0; w < kBlock / 64; w++) total += wave_sum[w];
+            // the last 16 bytes of the pitch: C, then three zero dwords
             reinterpret_cast<uint32_t *>(codes + (size_t)blockIdx.x * code_pitch + (code_pitch - 16))[threadIdx.x] =
                 threadIdx.x == 0 ? total : 0u;
         }
@@ -915,7 +841,7 @@ qamd_status alloc_store(qamd_bin *h) {
 }
 
 // calculate_metric's `dim` for a query of `planes` bit planes: the row's bits * (2^planes - 1), exact in f32
-// (encode_query_scalar refuses dims past 2^24, two-bit rows dims past 2^23)
+// (encode_query refuses scalar dims past 2^24, two-bit rows dims past 2^23)
 float metric_dim(const qamd_bin *h, uint32_t planes) { return (float)(h->code_bits * ((1ull << planes) - 1)); }
 
 template <int G, int ITERS, int UNROLL, int PLANES = 1>
@@ -994,15 +920,15 @@ qamd_status score_ids_any(const qamd_bin *h, const uint32_t *qbits, const uint32
 
 bool fused_capable(const qamd_bin *h) { return h->ds % 16 == 0 && h->ds / 16 <= 64; }
 
-// The scan of a scalar query's planes: bin_scan_kernel's mapping per row length; only the 8-lane rows scan half the
-// rows per wave, to leave the registers their 16-row tile takes to the planes of a piece.
+// The scan of a query's planes (1: its bit row), bin_scan_kernel's mapping per row length; the 8-lane rows of a scalar
+// query scan half the rows per wave, to leave the registers their 16-row tile takes to the planes of a piece.
 template <int PLANES>
 void scan_planes(const qamd_bin *h, const uint4 *qb, float *out_dev, hipStream_t s, const TopkFilter *filt) {
     const uint32_t rc = (uint32_t)(h->ds / 16);
     if (rc == 1) launch_bin<1, 1, 4, PLANES>(h, qb, out_dev, filt, s);
     else if (rc == 2) launch_bin<2, 1, 4, PLANES>(h, qb, out_dev, filt, s);
     else if (rc <= 4) launch_bin<4, 1, 8, PLANES>(h, qb, out_dev, filt, s);
-    else if (rc <= 8) launch_bin<8, 1, 8, PLANES>(h, qb, out_dev, filt, s);
+    else if (rc <= 8) launch_bin<8, 1, (PLANES == 1 ? 16 : 8), PLANES>(h, qb, out_dev, filt, s);
     else if (rc <= 16) launch_bin<16, 1, 8, PLANES>(h, qb, out_dev, filt, s);
     else if (rc <= 32) launch_bin<16, 2, 4, PLANES>(h, qb, out_dev, filt, s);
     else if (rc <= 48) launch_bin<16, 3, 4, PLANES>(h, qb, out_dev, filt, s);
@@ -1012,20 +938,12 @@ void scan_planes(const qamd_bin *h, const uint4 *qb, float *out_dev, hipStream_t
 qamd_status scan_bits(const qamd_bin *h, const void *qbits_dev, float *out_dev, hipStream_t s,
                       const TopkFilter *filt = nullptr, uint32_t planes = 1) {
     if (h->count == 0) return QAMD_OK;
-    const uint32_t rc = (uint32_t)(h->ds / 16);
     if (!fused_capable(h))
         return words_launch(h, static_cast<const uint32_t *>(qbits_dev), nullptr, h->count, out_dev, s, planes);
     const uint4 *qb = static_cast<const uint4 *>(qbits_dev);
     if (planes == 8) scan_planes<8>(h, qb, out_dev, s, filt);
     else if (planes == 4) scan_planes<4>(h, qb, out_dev, s, filt);
-    else if (rc == 1) launch_bin<1, 1, 4>(h, qb, out_dev, filt, s);
-    else if (rc == 2) launch_bin<2, 1, 4>(h, qb, out_dev, filt, s);
-    else if (rc <= 4) launch_bin<4, 1, 8>(h, qb, out_dev, filt, s);
-    else if (rc <= 8) launch_bin<8, 1, 16>(h, qb, out_dev, filt, s);
-    else if (rc <= 16) launch_bin<16, 1, 8>(h, qb, out_dev, filt, s);
-    else if (rc <= 32) launch_bin<16, 2, 4>(h, qb, out_dev, filt, s);
-    else if (rc <= 48) launch_bin<16, 3, 4>(h, qb, out_dev, filt, s);
-    else launch_bin<16, 4, 2>(h, qb, out_dev, filt, s);
+    else scan_planes<1>(h, qb, out_dev, s, filt);
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
 }
@@ -1112,23 +1030,46 @@ qamd_status upload_rows(qamd_bin *h, const uint8_t *rows, qamd_mem mem, hipStrea
     return copy_in(h->rows.ptr, wide.data(), QAMD_MEM_HOST, wide.size(), s);
 }
 
+// The bit encoder for a one-bit or two-bit store: `n` vectors of `dim` floats into bit rows of `row_words` dwords, the
+// first at row r0 of dst - the store's rows, a query's bit row, a batch's (one "row" per query, :288-291 is encode_vector
+// itself).
+void launch_bit_encoder(const qamd_bin *h, const float *src, uint64_t n, uint64_t dim, uint64_t row_words, uint32_t *dst,
+                        uint64_t r0, hipStream_t s) {
+    if (n == 0 || dim == 0) return;
+    const int grid = grid_for(n, kBlock / 64, 8);
+    if (h->encoding == QAMD_BIN_TWO_BITS)
+        hipLaunchKernelGGL(bin_encode_thr_kernel, dim3(grid), dim3(kBlock), 0, s, src, n, (uint32_t)dim, (uint32_t)row_words,
+                           h->thr.as<float>(), dst, r0);
+    else
+        hipLaunchKernelGGL(bin_encode_kernel, dim3(grid), dim3(kBlock), 0, s, src, n, (uint32_t)dim, (uint32_t)row_words, dst, r0);
+}
+
+// The scalar encoder for a one-bit or two-bit (weighted) store: `n` queries of `dim` floats, one workgroup
+// each.  The single query has no code image: codes = nullptr.
+void launch_scalar_encoder(const qamd_bin *h, const float *src, uint64_t n, uint64_t dim, uint64_t ds, uint32_t bits,
+                           uint32_t *planes, uint64_t p_stride, float *max_abs, int8_t *codes, uint64_t code_pitch,
+                           hipStream_t s) {
+    if (h->encoding == QAMD_BIN_TWO_BITS)
+        hipLaunchKernelGGL(bin_encode_scalar_kernel<true>, dim3((unsigned)n), dim3(kBlock), 0, s, src, (uint32_t)dim,
+                           h->thr.as<float>(), (uint32_t)(ds / 4), bits, planes, (uint32_t)(p_stride / 4), max_abs, codes,
+                           (uint32_t)code_pitch);
+    else
+        hipLaunchKernelGGL(bin_encode_scalar_kernel<false>, dim3((unsigned)n), dim3(kBlock), 0, s, src, (uint32_t)dim,
+                           static_cast<const float *>(nullptr), (uint32_t)(ds / 4), bits, planes, (uint32_t)(p_stride / 4),
+                           max_abs, codes, (uint32_t)code_pitch);
+}
+
 // encode_vector (:193-208) for `nr` device-resident rows: rows r0 .. r0+nr of the store.
 qamd_status launch_bin_encode(qamd_bin *h, const float *src, uint64_t nr, uint64_t r0, hipStream_t s) {
     const uint64_t dim = h->vp.dim;
     if (nr == 0 || dim == 0) return QAMD_OK;
-    if (h->encoding == QAMD_BIN_TWO_BITS) {
-        int grid = grid_for(nr, kBlock / 64, 8);
-        hipLaunchKernelGGL(bin_encode_thr_kernel, dim3(grid), dim3(kBlock), 0, s, src, nr, (uint32_t)dim,
-                           (uint32_t)(h->ds / 4), h->thr.as<float>(), h->rows.as<uint32_t>(), r0);
-    } else if (dim % 128 == 0 && h->ds * 8 == dim && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+    if (h->encoding != QAMD_BIN_TWO_BITS && dim % 128 == 0 && h->ds * 8 == dim && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
         const uint64_t n4 = nr * dim / 4;
         const unsigned grid = (unsigned)((n4 + 1024 * (kBlock / 64) - 1) / (1024 * (kBlock / 64)));
         hipLaunchKernelGGL(bin_encode_flat_kernel, dim3(grid), dim3(kBlock), 0, s, reinterpret_cast<const float4 *>(src),
                            n4, h->rows.as<uint32_t>() + r0 * (h->ds / 4));
     } else {
-        int grid = grid_for(nr, kBlock / 64, 8);
-        hipLaunchKernelGGL(bin_encode_kernel, dim3(grid), dim3(kBlock), 0, s, src, nr, (uint32_t)dim,
-                           (uint32_t)(h->ds / 4), h->rows.as<uint32_t>(), r0);
+        launch_bit_encoder(h, src, nr, dim, h->ds / 4, h->rows.as<uint32_t>(), r0, s);
     }
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
@@ -1519,73 +1460,28 @@ qamd_status qamd_bin_load(const char *data_path, const char *meta_path, const qa
                               out);
 }
 
-qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem,
-                                  void *stream, qamd_bin_query **query_io) {
-    if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    const bool two = h->encoding == QAMD_BIN_TWO_BITS;  // the row's thresholds and layout (DESIGN 3.2e)
-    if (two && qdim != h->vp.dim)
-        return fail(QAMD_ERR_ARGUMENTS, "a query of %llu dimensions against thresholds of %llu", (unsigned long long)qdim,
-                    (unsigned long long)h->vp.dim);
-    QAMD_ON_DEVICE(h->device);
-    hipStream_t s = as_stream(stream);
-    const uint64_t nb = row_bytes_of(two ? 2 * qdim : qdim, h->store), ds = device_stride_of(nb);
-    qamd_bin_query *q = *query_io;
-    std::unique_ptr<qamd_bin_query> fresh;
-    if (!q) {
-        fresh.reset(new qamd_bin_query);
-        q = fresh.get();
-        q->device = h->device;
-    }
-    if (q->ds != ds || q->qdim_cap < qdim || !q->buf.ptr) {
-        QAMD_TRY(q->buf.alloc(round_up(ds, 16) + 16 + qdim * 4 + 16, true));  // bits | f32 staging
-        q->qdim_cap = qdim;
-        q->nb = nb;
-        q->ds = ds;
-    }
-    q->bits = 1;
-    // Always packed on the device (one implementation); a host query is uploaded first.
-    if (qdim) {
-        const float *q_dev = query;
-        if (query_mem == QAMD_MEM_HOST) {
-            float *stage = reinterpret_cast<float *>(q->buf.as<uint8_t>() + round_up(ds, 16) + 16);
-            QAMD_TRY(copy_in(stage, query, QAMD_MEM_HOST, qdim * 4, s));
-            q_dev = stage;
-        }
-        if (two)
-            hipLaunchKernelGGL(bin_encode_thr_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint64_t)1, (uint32_t)qdim,
-                               (uint32_t)(ds / 4), h->thr.as<float>(), q->buf.as<uint32_t>(), (uint64_t)0);
-        else
-            hipLaunchKernelGGL(bin_encode_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint64_t)1, (uint32_t)qdim,
-                               (uint32_t)(ds / 4), q->buf.as<uint32_t>(), (uint64_t)0);
-        QAMD_HIP(hipGetLastError());
-    }
-    QAMD_TRY(q->ready.record(s));
-    if (fresh) *query_io = fresh.release();
-    return QAMD_OK;
-}
-
-// Where a scalar query keeps max_abs, and its f32 staging area, behind `bits` planes of ds bytes.
+// Where a query keeps max_abs, and behind it its f32 staging area, after `bits` planes of ds bytes.
 static uint64_t scalar_max_abs_at(uint64_t ds, uint32_t bits) { return round_up(bits * ds, 16) + 16; }
 
 // The most dimensions a `bits`-bit scalar query may have: code_bits * (2^bits - 1) and every sum below it must be exact
 // in f32, so the row's bits stay at or under 65 792 (8 bits) / 1 118 481 (4 bits) - half as many dimensions on two-bit rows.
 static uint64_t scalar_max_dim(uint32_t bits, bool two) { return (bits == 8 ? 65792u : 1118481u) / (two ? 2u : 1u); }
 
-// The reference has no counterpart (its query is one bit per dimension): DESIGN 3.2d is the specification, 3.2f that of
-// `weighted` on two-bit rows (codes from q_i * (hi_i - lo_i), sized by code_bits).  On one-bit rows both are the same call.
-static qamd_status encode_query_scalar(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem, uint32_t bits,
-                                       bool weighted, void *stream, qamd_bin_query **query_io) {
-    if (bits == 1) return qamd_bin_encode_query(h, query, qdim, query_mem, stream, query_io);
-    if (bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
+// Every single-query encode.  bits = 1: the reference's binary query, one plane from the row encoder.  bits = 4 / 8 have
+// no counterpart there: DESIGN 3.2d is the specification, 3.2f that of `weighted` on two-bit rows (codes from
+// q_i * (hi_i - lo_i), sized by code_bits); on one-bit rows both are the same call.
+static qamd_status encode_query(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem, uint32_t bits,
+                                bool weighted, void *stream, qamd_bin_query **query_io) {
+    if (bits != 1 && bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
     if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    const bool two = h->encoding == QAMD_BIN_TWO_BITS;
-    if (two && !weighted)
+    const bool two = h->encoding == QAMD_BIN_TWO_BITS;  // the row's thresholds and layout (DESIGN 3.2e)
+    if (bits != 1 && two && !weighted)
         return fail(QAMD_ERR_ARGUMENTS, "two-bit rows take scalar queries through qamd_bin_encode_query_scalar_w");
     if (two && qdim != h->vp.dim)
         return fail(QAMD_ERR_ARGUMENTS, "a query of %llu dimensions against thresholds of %llu", (unsigned long long)qdim,
                     (unsigned long long)h->vp.dim);
     const uint64_t max_dim = scalar_max_dim(bits, two);
-    if (qdim > max_dim)
+    if (bits != 1 && qdim > max_dim)
         return fail(QAMD_ERR_ARGUMENTS, "a %u-bit query has at most %llu dimensions, not %llu", bits,
                     (unsigned long long)max_dim, (unsigned long long)qdim);
     QAMD_ON_DEVICE(h->device);
@@ -1606,33 +1502,37 @@ static qamd_status encode_query_scalar(const qamd_bin *h, const float *query, ui
         q->ds = ds;
     }
     q->bits = bits;
+    // Always encoded on the device (one implementation); a host query is uploaded first.
     const float *q_dev = query;
     if (qdim && query_mem == QAMD_MEM_HOST) {
         float *stage = reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at + 16);
         QAMD_TRY(copy_in(stage, query, QAMD_MEM_HOST, qdim * 4, s));
         q_dev = stage;
     }
-    float *max_abs = reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at);
-    if (two)
-        hipLaunchKernelGGL(bin_encode_scalar_thr_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint32_t)qdim, h->thr.as<float>(),
-                           (uint32_t)(ds / 4), bits, q->buf.as<uint32_t>(), 0u, max_abs, static_cast<int8_t *>(nullptr), 0u);
+    if (bits == 1)
+        launch_bit_encoder(h, q_dev, 1, qdim, ds / 4, q->buf.as<uint32_t>(), 0, s);
     else
-        hipLaunchKernelGGL(bin_encode_scalar_kernel, dim3(1), dim3(kBlock), 0, s, q_dev, (uint32_t)qdim, (uint32_t)(ds / 4), bits,
-                           q->buf.as<uint32_t>(), 0u, max_abs, static_cast<int8_t *>(nullptr), 0u);
+        launch_scalar_encoder(h, q_dev, 1, qdim, ds, bits, q->buf.as<uint32_t>(), 0,
+                              reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at), nullptr, 0, s);
     QAMD_HIP(hipGetLastError());
     QAMD_TRY(q->ready.record(s));
     if (fresh) *query_io = fresh.release();
     return QAMD_OK;
 }
 
+qamd_status qamd_bin_encode_query(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem,
+                                  void *stream, qamd_bin_query **query_io) {
+    return encode_query(h, query, qdim, query_mem, 1, false, stream, query_io);
+}
+
 qamd_status qamd_bin_encode_query_scalar(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem,
                                          uint32_t bits, void *stream, qamd_bin_query **query_io) {
-    return encode_query_scalar(h, query, qdim, query_mem, bits, false, stream, query_io);
+    return encode_query(h, query, qdim, query_mem, bits, false, stream, query_io);
 }
 
 qamd_status qamd_bin_encode_query_scalar_w(const qamd_bin *h, const float *query, uint64_t qdim, qamd_mem query_mem,
                                            uint32_t bits, void *stream, qamd_bin_query **query_io) {
-    return encode_query_scalar(h, query, qdim, query_mem, bits, true, stream, query_io);
+    return encode_query(h, query, qdim, query_mem, bits, true, stream, query_io);
 }
 
 qamd_status qamd_bin_query_info(const qamd_bin_query *q, uint32_t *bits, float *max_abs) {
@@ -1765,16 +1665,19 @@ void qamd_bin_free(qamd_bin *h) { delete h; }
 struct qamd_bin_query_batch {
     int device = 0;
     uint64_t nb = 0, ds = 0, n_queries = 0;
-    uint64_t q_stride = 0;  // bytes between two queries' bit rows (multiple of 16)
-    DevBuf bits;            // [n_queries][q_stride]; binary batches only
-    // a batch of scalar queries (qamd_bin_encode_query_batch_scalar) holds two other images and NO bit rows:
-    uint32_t qbits = 1;       // bits per query dimension: 1, 4 or 8
+    uint32_t qbits = 1;       // bits per query dimension: 1 (the reference's binary query), 4 or 8
     uint64_t p_stride = 0;    // bytes between two queries' planes (multiple of 16); a query's planes as in qamd_bin_query
+    DevBuf planes;            // [n_queries][p_stride]: a binary batch is a batch of one plane, the query's bit row
+    // a batch of scalar queries (qamd_bin_encode_query_batch_scalar) holds a second image for the matrix cores:
     uint64_t code_pitch = 0;  // bytes between two queries' centred int8 codes: bin_gemm_rs_kernel's LDS pitch of this row length
-    DevBuf planes;            // [n_queries][p_stride]
     DevBuf codes;             // [n_queries][code_pitch]: d_i, zero bytes, C = sum c_i in the last 16
     DevBuf max_abs;           // [n_queries] f32
 };
+
+// Query q of the batch as scan_bits / words_launch / bin_topk_small take it: its planes (its bit row at qbits = 1).
+static const uint8_t *bin_batch_query(const qamd_bin_query_batch *b, uint64_t q) {
+    return b->planes.as<uint8_t>() + q * b->p_stride;
+}
 
 namespace {
 
@@ -2562,19 +2465,14 @@ qamd_status launch_bin_gemm(const qamd_bin *h, const qamd_bin_query_batch *b, co
     const bool low = MODE != 0 && (!zx) != (MODE == 2);  // multiplier = zx ? +4 : -4
     const size_t lds = (size_t)32 * mi * ((h->ds / 16) * 128 + 16) + 3 * 64 * 4 + 64;
     const uint32_t grid = (uint32_t)std::max(1, device_info().cu_count / 8) * 8;
-#define QAMD_BIN_GEMM(M_, LOW_, MI_)                                                                                        \
+    // a binary batch: its bit rows (the one plane); a scalar batch: its code image at the kernel's own LDS pitch, and
+    // dim * L for dim (never its planes, never as bits)
+#define QAMD_BIN_GEMM(M_, LOW_, MI_, CODES_)                                                                                \
     do {                                                                                                                   \
-        QAMD_LDS_OPT_IN((&bin_gemm_rs_kernel<M_, LOW_, MI_>), 160 * 1024); \
-        hipLaunchKernelGGL((bin_gemm_rs_kernel<M_, LOW_, MI_>), dim3(grid), dim3(512), lds, s, rows, (uint32_t)h->ds,      \
-                           b->bits.as<uint8_t>(), (uint32_t)b->q_stride, metric_dim(h, 1), zx ? 1 : 0, (uint32_t)n_rows,   \
-                           (uint32_t)b->n_queries, q0, out, out_pitch, filt);                                              \
-    } while (0)
-    // a scalar batch: its code image at the kernel's own LDS pitch, and dim * L for dim (never its planes, never as bits)
-#define QAMD_BIN_GEMM_CODES(M_, LOW_, MI_)                                                                                  \
-    do {                                                                                                                   \
-        QAMD_LDS_OPT_IN((&bin_gemm_rs_kernel<M_, LOW_, MI_, true>), 160 * 1024);                                            \
-        hipLaunchKernelGGL((bin_gemm_rs_kernel<M_, LOW_, MI_, true>), dim3(grid), dim3(512), lds, s, rows, (uint32_t)h->ds, \
-                           b->codes.as<uint8_t>(), (uint32_t)b->code_pitch, metric_dim(h, b->qbits), zx ? 1 : 0,           \
+        QAMD_LDS_OPT_IN((&bin_gemm_rs_kernel<M_, LOW_, MI_, CODES_>), 160 * 1024);                                          \
+        hipLaunchKernelGGL((bin_gemm_rs_kernel<M_, LOW_, MI_, CODES_>), dim3(grid), dim3(512), lds, s, rows, (uint32_t)h->ds, \
+                           CODES_ ? b->codes.as<uint8_t>() : b->planes.as<uint8_t>(),                                      \
+                           (uint32_t)(CODES_ ? b->code_pitch : b->p_stride), metric_dim(h, b->qbits), zx ? 1 : 0,          \
                            (uint32_t)n_rows, (uint32_t)b->n_queries, q0, out, out_pitch, filt);                            \
     } while (0)
     constexpr int M = MODE == 0 ? 1 : MODE;
@@ -2584,24 +2482,23 @@ qamd_status launch_bin_gemm(const qamd_bin *h, const qamd_bin_query_batch *b, co
         // per lane at 256 registers - the binary ones have since they were written - and are not instantiated for codes.
         if (MODE != 0 && mi != 1) return fail(QAMD_ERR_ARGUMENTS, "scalar batches filter on 32-query tiles");
         if (MODE == 0) {
-            if (mi == 2) QAMD_BIN_GEMM_CODES(0, false, 2);
-            else QAMD_BIN_GEMM_CODES(0, false, 1);
+            if (mi == 2) QAMD_BIN_GEMM(0, false, 2, true);
+            else QAMD_BIN_GEMM(0, false, 1, true);
         } else if (low) {
-            QAMD_BIN_GEMM_CODES(M, true, 1);
+            QAMD_BIN_GEMM(M, true, 1, true);
         } else {
-            QAMD_BIN_GEMM_CODES(M, false, 1);
+            QAMD_BIN_GEMM(M, false, 1, true);
         }
     } else if (MODE == 0) {
-        if (mi == 2) QAMD_BIN_GEMM(0, false, 2);
-        else QAMD_BIN_GEMM(0, false, 1);
+        if (mi == 2) QAMD_BIN_GEMM(0, false, 2, false);
+        else QAMD_BIN_GEMM(0, false, 1, false);
     } else if (low) {
-        if (mi == 2) QAMD_BIN_GEMM(M, true, 2);
-        else QAMD_BIN_GEMM(M, true, 1);
+        if (mi == 2) QAMD_BIN_GEMM(M, true, 2, false);
+        else QAMD_BIN_GEMM(M, true, 1, false);
     } else {
-        if (mi == 2) QAMD_BIN_GEMM(M, false, 2);
-        else QAMD_BIN_GEMM(M, false, 1);
+        if (mi == 2) QAMD_BIN_GEMM(M, false, 2, false);
+        else QAMD_BIN_GEMM(M, false, 1, false);
     }
-#undef QAMD_BIN_GEMM_CODES
 #undef QAMD_BIN_GEMM
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
@@ -2730,10 +2627,10 @@ qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b
         int *bq = reinterpret_cast<int *>(q_off + q_pad);
         const unsigned pgrid = (unsigned)std::max<uint64_t>((q_pad + 255) / 256, std::min<uint64_t>(2048, (frag_bytes / 16 + 255) / 256));
         if (low)
-            hipLaunchKernelGGL(bin_frag4_kernel<true>, dim3(pgrid), dim3(256), 0, s, b->bits.as<uint8_t>(), (uint32_t)b->q_stride, (uint32_t)Q,
+            hipLaunchKernelGGL(bin_frag4_kernel<true>, dim3(pgrid), dim3(256), 0, s, b->planes.as<uint8_t>(), (uint32_t)b->p_stride, (uint32_t)Q,
                                (uint32_t)q_pad, nsteps, metric_dim(h, 1), zx ? 1 : 0, largest, pivots, frag, q_off, bq);
         else
-            hipLaunchKernelGGL(bin_frag4_kernel<false>, dim3(pgrid), dim3(256), 0, s, b->bits.as<uint8_t>(), (uint32_t)b->q_stride, (uint32_t)Q,
+            hipLaunchKernelGGL(bin_frag4_kernel<false>, dim3(pgrid), dim3(256), 0, s, b->planes.as<uint8_t>(), (uint32_t)b->p_stride, (uint32_t)Q,
                                (uint32_t)q_pad, nsteps, metric_dim(h, 1), zx ? 1 : 0, largest, pivots, frag, q_off, bq);
         const size_t qs_rows = h->ds > 128 ? 96 : 128;
         const size_t lds = 2 * qs_rows * round_up(h->ds * 4, 256) + 4 * qs_rows * 4 + 64 + kQs4Slice * 4;
@@ -2872,78 +2769,25 @@ qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b
 }  // namespace
 
 
-extern "C" {
-
-qamd_status qamd_bin_encode_query_batch(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
-                                        qamd_mem queries_mem, void *stream, qamd_bin_query_batch **batch_io) {
+// Every batch encode: query q of the batch is the single-query encode of row q of `queries` (the same kernels, one bit
+// "row" or one workgroup per query), kept as its planes and, for 4 / 8 bits, as the matrix cores' int8
+// image.  `weighted` on two-bit rows: DESIGN 3.2f, the planes and the image sized by code_bits.
+static qamd_status encode_query_batch(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
+                                      qamd_mem queries_mem, uint32_t bits, bool weighted, void *stream,
+                                      qamd_bin_query_batch **batch_io) {
+    if (bits != 1 && bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
     if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     const bool two = h->encoding == QAMD_BIN_TWO_BITS;
-    if (two && n_queries && qdim != h->vp.dim)
-        return fail(QAMD_ERR_ARGUMENTS, "queries of %llu dimensions against thresholds of %llu", (unsigned long long)qdim,
-                    (unsigned long long)h->vp.dim);
-    QAMD_ON_DEVICE(h->device);
-    hipStream_t s = as_stream(stream);
-    const uint64_t nb = row_bytes_of(two ? 2 * qdim : qdim, h->store), ds = device_stride_of(nb);
-    if (n_queries && nb != h->nb)
-        return fail(QAMD_ERR_ARGUMENTS, "queries have %llu bytes, rows have %llu", (unsigned long long)nb,
-                    (unsigned long long)h->nb);
-    qamd_bin_query_batch *b = *batch_io;
-    std::unique_ptr<qamd_bin_query_batch> fresh;
-    if (!b) {
-        fresh.reset(new qamd_bin_query_batch);
-        b = fresh.get();
-        b->device = h->device;
-    }
-    const uint64_t q_stride = round_up(ds, 16);
-    const size_t need = std::max<size_t>(q_stride * n_queries, 16);
-    if (b->bits.bytes < need || b->q_stride != q_stride) QAMD_TRY(b->bits.alloc(need, true));
-    b->nb = nb;
-    b->ds = ds;
-    b->q_stride = q_stride;
-    b->n_queries = n_queries;
-    b->qbits = 1;
-    if (n_queries && qdim) {
-        DevBuf qtmp;
-        const void *qd = nullptr;
-        bool staged = false;
-        QAMD_TRY(local_view(queries, queries_mem, n_queries * qdim * 4, qtmp, s, &qd, &staged));
-        // the row encoder with one "row" per query and the batch's stride (:288-291 is encode_vector itself)
-        int grid = grid_for(n_queries, kBlock / 64, 8);
-        if (two)
-            hipLaunchKernelGGL(bin_encode_thr_kernel, dim3(grid), dim3(kBlock), 0, s, static_cast<const float *>(qd), n_queries,
-                               (uint32_t)qdim, (uint32_t)(q_stride / 4), h->thr.as<float>(), b->bits.as<uint32_t>(), (uint64_t)0);
-        else
-            hipLaunchKernelGGL(bin_encode_kernel, dim3(grid), dim3(kBlock), 0, s, static_cast<const float *>(qd), n_queries,
-                               (uint32_t)qdim, (uint32_t)(q_stride / 4), b->bits.as<uint32_t>(), (uint64_t)0);
-        QAMD_HIP(hipGetLastError());
-        if (staged) QAMD_HIP(hipStreamSynchronize(s));
-    }
-    if (fresh) *batch_io = fresh.release();
-    return QAMD_OK;
-}
-
-}  // extern "C"
-
-// The reference has no counterpart: DESIGN 3.2d.  Query q of the batch is qamd_bin_encode_query_scalar of row q of
-// `queries` (the same kernel, one workgroup per query), kept as its planes and as the matrix cores' int8 image.
-// `weighted` on two-bit rows: DESIGN 3.2f, the planes and the image sized by code_bits.
-static qamd_status encode_query_batch_scalar(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
-                                             qamd_mem queries_mem, uint32_t bits, bool weighted, void *stream,
-                                             qamd_bin_query_batch **batch_io) {
-    if (bits == 1) return qamd_bin_encode_query_batch(h, queries, n_queries, qdim, queries_mem, stream, batch_io);
-    if (bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
-    if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    const bool two = h->encoding == QAMD_BIN_TWO_BITS;
-    if (two && !weighted)
+    if (bits != 1 && two && !weighted)
         return fail(QAMD_ERR_ARGUMENTS, "two-bit rows take scalar queries through qamd_bin_encode_query_batch_scalar_w");
     if (two && n_queries && qdim != h->vp.dim)
         return fail(QAMD_ERR_ARGUMENTS, "queries of %llu dimensions against thresholds of %llu", (unsigned long long)qdim,
                     (unsigned long long)h->vp.dim);
     const uint64_t max_dim = scalar_max_dim(bits, two);  // as the single query: code_bits * L stays exact in f32
-    if (qdim > max_dim)
+    if (bits != 1 && qdim > max_dim)
         return fail(QAMD_ERR_ARGUMENTS, "a %u-bit query has at most %llu dimensions, not %llu", bits,
                     (unsigned long long)max_dim, (unsigned long long)qdim);
-    if (n_queries > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "too many queries");
+    if (bits != 1 && n_queries > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "too many queries");  // one workgroup each
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     const uint64_t nb = row_bytes_of(two ? 2 * qdim : qdim, h->store), ds = device_stride_of(nb);
@@ -2960,9 +2804,12 @@ static qamd_status encode_query_batch_scalar(const qamd_bin *h, const float *que
     const uint64_t p_stride = round_up(bits * ds, 16);
     const uint64_t code_pitch = round_up(ds, 16) * 8 + 16;  // ds / 16 K-blocks of 128 bytes + 16: bin_gemm_rs_kernel's PA
     const size_t need_p = std::max<size_t>(p_stride * n_queries, 16), need_c = std::max<size_t>(code_pitch * n_queries, 16);
-    if (b->planes.bytes < need_p) QAMD_TRY(b->planes.alloc(need_p, true));
-    if (b->codes.bytes < need_c) QAMD_TRY(b->codes.alloc(need_c, true));
-    if (b->max_abs.bytes < std::max<size_t>(n_queries * 4, 16)) QAMD_TRY(b->max_abs.alloc(std::max<size_t>(n_queries * 4, 16), true));
+    // zeroed planes whenever their layout changes: a reused batch of any earlier kind behaves as a fresh one
+    if (b->planes.bytes < need_p || b->p_stride != p_stride || b->qbits != bits) QAMD_TRY(b->planes.alloc(need_p, true));
+    if (bits != 1) {  // (the encoder writes every byte of a query's pitch and its max_abs)
+        if (b->codes.bytes < need_c) QAMD_TRY(b->codes.alloc(need_c, true));
+        if (b->max_abs.bytes < std::max<size_t>(n_queries * 4, 16)) QAMD_TRY(b->max_abs.alloc(std::max<size_t>(n_queries * 4, 16), true));
+    }
     b->nb = nb;
     b->ds = ds;
     b->n_queries = n_queries;
@@ -2974,15 +2821,11 @@ static qamd_status encode_query_batch_scalar(const qamd_bin *h, const float *que
         const void *qd = nullptr;
         bool staged = false;
         if (qdim) QAMD_TRY(local_view(queries, queries_mem, n_queries * qdim * 4, qtmp, s, &qd, &staged));
-        if (two)
-            hipLaunchKernelGGL(bin_encode_scalar_thr_kernel, dim3((unsigned)n_queries), dim3(kBlock), 0, s,
-                               static_cast<const float *>(qd), (uint32_t)qdim, h->thr.as<float>(), (uint32_t)(ds / 4), bits,
-                               b->planes.as<uint32_t>(), (uint32_t)(p_stride / 4), b->max_abs.as<float>(), b->codes.as<int8_t>(),
-                               (uint32_t)code_pitch);
+        if (bits == 1)
+            launch_bit_encoder(h, static_cast<const float *>(qd), n_queries, qdim, p_stride / 4, b->planes.as<uint32_t>(), 0, s);
         else
-            hipLaunchKernelGGL(bin_encode_scalar_kernel, dim3((unsigned)n_queries), dim3(kBlock), 0, s,
-                               static_cast<const float *>(qd), (uint32_t)qdim, (uint32_t)(ds / 4), bits, b->planes.as<uint32_t>(),
-                               (uint32_t)(p_stride / 4), b->max_abs.as<float>(), b->codes.as<int8_t>(), (uint32_t)code_pitch);
+            launch_scalar_encoder(h, static_cast<const float *>(qd), n_queries, qdim, ds, bits, b->planes.as<uint32_t>(), p_stride,
+                                  b->max_abs.as<float>(), b->codes.as<int8_t>(), code_pitch, s);
         QAMD_HIP(hipGetLastError());
         if (staged) QAMD_HIP(hipStreamSynchronize(s));
     }
@@ -2992,10 +2835,15 @@ static qamd_status encode_query_batch_scalar(const qamd_bin *h, const float *que
 
 extern "C" {
 
+qamd_status qamd_bin_encode_query_batch(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
+                                        qamd_mem queries_mem, void *stream, qamd_bin_query_batch **batch_io) {
+    return encode_query_batch(h, queries, n_queries, qdim, queries_mem, 1, false, stream, batch_io);
+}
+
 qamd_status qamd_bin_encode_query_batch_scalar(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
                                                qamd_mem queries_mem, uint32_t bits, void *stream,
                                                qamd_bin_query_batch **batch_io) {
-    return encode_query_batch_scalar(h, queries, n_queries, qdim, queries_mem, bits, false, stream, batch_io);
+    return encode_query_batch(h, queries, n_queries, qdim, queries_mem, bits, false, stream, batch_io);
 }
 
 // on two-bit rows query q is qamd_bin_encode_query_scalar_w of row q of `queries`, its int8 image one byte
@@ -3003,7 +2851,7 @@ qamd_status qamd_bin_encode_query_batch_scalar(const qamd_bin *h, const float *q
 qamd_status qamd_bin_encode_query_batch_scalar_w(const qamd_bin *h, const float *queries, uint64_t n_queries, uint64_t qdim,
                                                  qamd_mem queries_mem, uint32_t bits, void *stream,
                                                  qamd_bin_query_batch **batch_io) {
-    return encode_query_batch_scalar(h, queries, n_queries, qdim, queries_mem, bits, true, stream, batch_io);
+    return encode_query_batch(h, queries, n_queries, qdim, queries_mem, bits, true, stream, batch_io);
 }
 
 qamd_status qamd_bin_query_batch_info(const qamd_bin_query_batch *b, uint32_t *bits, uint64_t *n_queries) {
@@ -3021,9 +2869,8 @@ qamd_status qamd_bin_query_batch_read(const qamd_bin_query_batch *b, uint64_t q,
     if (bits) {
         if (capacity < total) return fail(QAMD_ERR_ARGUMENTS, "bits buffer too small");
         QAMD_ON_DEVICE(b->device);
-        const uint8_t *src = b->qbits == 1 ? b->bits.as<uint8_t>() + q * b->q_stride : b->planes.as<uint8_t>() + q * b->p_stride;
         std::vector<uint8_t> wide(b->qbits * b->ds);  // planes are held at the device stride (4 bytes for the tiny rows)
-        if (!wide.empty()) QAMD_TRY(copy_out(wide.data(), QAMD_MEM_HOST, src, wide.size(), nullptr));
+        if (!wide.empty()) QAMD_TRY(copy_out(wide.data(), QAMD_MEM_HOST, bin_batch_query(b, q), wide.size(), nullptr));
         for (uint32_t pl = 0; pl < b->qbits; pl++) memcpy(bits + pl * b->nb, &wide[pl * b->ds], b->nb);
     }
     return QAMD_OK;
@@ -3040,12 +2887,6 @@ static qamd_status bin_check_batch(const qamd_bin *h, const qamd_bin_query_batch
     if (b->n_queries && b->qbits != 1 && (b->ds != h->ds || !b->planes.ptr || !b->codes.ptr))
         return fail(QAMD_ERR_ARGUMENTS, "scalar query batch without its planes or codes");
     return QAMD_OK;
-}
-
-// Query q of the batch as scan_bits / words_launch / bin_topk_small take it: its bit row, or its planes - a scalar batch
-// has no bit rows, and nothing reads b->bits for it.
-static const uint8_t *bin_batch_query(const qamd_bin_query_batch *b, uint64_t q) {
-    return b->qbits == 1 ? b->bits.as<uint8_t>() + q * b->q_stride : b->planes.as<uint8_t>() + q * b->p_stride;
 }
 
 // ---- routing: ONE predicate per entry point, called by the entry point and by qamd_bin_batch_kernel
@@ -3111,11 +2952,9 @@ qamd_status qamd_bin_score_ids_batch(const qamd_bin *h, const qamd_bin_query_bat
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     return run_lists(list_offsets, n_lists, ids, n_ids, nullptr, lists_mem, out, out_mem, h->count, s, [&](const ListArgs &a) {
-        if (b->qbits != 1)  // list l against the planes of query l
-            return pairs_launch(h, nullptr, b->planes.as<uint8_t>(), b->p_stride, a.offsets, a.n_lists, nullptr, a.ids, a.n_pairs,
-                                a.out, s, b->qbits);
-        return pairs_launch(h, nullptr, b->bits.as<uint8_t>(), b->q_stride, a.offsets, a.n_lists, nullptr, a.ids, a.n_pairs,
-                            a.out, s);
+        // list l against the planes of query l
+        return pairs_launch(h, nullptr, b->planes.as<uint8_t>(), b->p_stride, a.offsets, a.n_lists, nullptr, a.ids, a.n_pairs,
+                            a.out, s, b->qbits);
     });
 }
 
@@ -3148,9 +2987,9 @@ qamd_status qamd_bin_score_batch(const qamd_bin *h, const qamd_bin_query_batch *
         const uint64_t left = b->n_queries - q;
         const uint8_t *qb = bin_batch_query(b, q);
         float *o = out_dev + q * h->count;
-        if (left >= 8 && multi_step<8>(h, qb, b->q_stride, o, s)) q += 8;
-        else if (left >= 4 && multi_step<4>(h, qb, b->q_stride, o, s)) q += 4;
-        else if (left >= 2 && multi_step<2>(h, qb, b->q_stride, o, s)) q += 2;
+        if (left >= 8 && multi_step<8>(h, qb, b->p_stride, o, s)) q += 8;
+        else if (left >= 4 && multi_step<4>(h, qb, b->p_stride, o, s)) q += 4;
+        else if (left >= 2 && multi_step<2>(h, qb, b->p_stride, o, s)) q += 2;
         else {
             QAMD_TRY(scan_bits(h, qb, o, s));
             q += 1;
@@ -3167,7 +3006,7 @@ qamd_status qamd_bin_topk_batch(const qamd_bin *h, const qamd_bin_query_batch *b
     qamd_status args = QAMD_OK;
     if (!topk_wanted(k, b->n_queries, out_ids, out_scores, args)) return args;
     QAMD_ON_DEVICE(h->device);
-    const uint64_t qs = b->q_stride;
+    const uint64_t qs = b->p_stride;  // (a binary batch: the stride of its bit rows)
     const uint32_t planes = b->qbits;  // 1: query q is its bit row; 4 / 8: its planes (bin_batch_query)
     BatchScan scan;
     scan.filter_capable = fused_capable(h);

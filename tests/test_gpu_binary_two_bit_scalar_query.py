@@ -503,3 +503,63 @@ def test_the_other_queries_are_what_they_were():
     sign = np.where(np.unpackbits(orows, axis=1, bitorder="little")[:, :dim] != 0, 1.0, -1.0)
     qsign = np.where(queries[0] > 0, 1.0, -1.0)
     assert_bits_equal(one.score_all(one.encode_query(queries[0])), (sign @ qsign).astype(f32), "binary query, one-bit rows")
+
+
+# ---------------------------------------------------------------------------------------------------- handle reuse
+def _reuse_stores():
+    """A: one-bit, dim 100, U128.  B: two-bit, dim 100, U128 (200 bits to a row, no multiple of 64), also at 4100 rows,
+    where a batch of 6 takes the matrix cores.  C: two-bit, dim 20, U8 (the tiny rows).  D: one-bit, dim 1160, U128."""
+    rng = np.random.default_rng(2024)
+
+    def make(dim, n, store, encoding):
+        x = rng.normal(size=(n, dim)).astype(f32)
+        return E.encode(x, qa.VectorParameters(dim, n, D.Dot, False), store=store, encoding=encoding)
+
+    one = qa.BinaryEncoding.OneBit
+    return {"A": make(100, 300, S.U128, one), "B": make(100, 300, S.U128, TWO), "C": make(20, 300, S.U8, TWO),
+            "D": make(1160, 300, S.U128, one), "B4100": make(100, 4100, S.U128, TWO)}
+
+
+REUSE_STEPS = [("D", 1, False), ("B", 8, True), ("A", 4, False), ("C", 4, True), ("B", 1, False), ("D", 8, False), ("A", 1, False)]
+
+
+def test_one_handle_through_every_kind_of_query():
+    """A query handle and a batch handle reused across stores, encodings, row lengths, bit counts and query counts give
+    what fresh ones give: the bytes they hold, and every score and top-k as raw bits."""
+    stores = _reuse_stores()
+    rng = np.random.default_rng(7)
+    q = None
+    for name, bits, weighted in REUSE_STEPS:
+        enc, what = stores[name], f"single, store {name}, {bits} bits"
+        query = rng.normal(size=enc.vector_parameters.dim).astype(f32)
+        q = enc.encode_query(query, q, query_bits=bits, weighted=weighted)
+        fresh = enc.encode_query(query, query_bits=bits, weighted=weighted)
+        assert q.bits == fresh.bits == bits
+        _same(q.encoded_vector, fresh.encoded_vector, what + ": encoded_vector")
+        _same(np.float32(q.max_abs), np.float32(fresh.max_abs), what + ": max_abs")
+        _same(enc.score_all(q), enc.score_all(fresh), what + ": score_all")
+        for got, want in zip(enc.topk(q, 10), enc.topk(fresh, 10)):
+            _same(got, want, what + ": topk")
+
+    def check_batch(enc, b, queries, bits, weighted, what):
+        fresh = enc.encode_query_batch(queries, query_bits=bits, weighted=weighted)
+        assert b.bits == fresh.bits == bits
+        for qi in range(len(queries)):
+            _same(b.encoded_vector(qi), fresh.encoded_vector(qi), f"{what}: encoded_vector({qi})")
+        _same(enc.score_batch(b), enc.score_batch(fresh), what + ": score_batch")
+        for got, want in zip(enc.topk_batch(b, 10), enc.topk_batch(fresh, 10)):
+            _same(got, want, what + ": topk_batch")
+
+    b = None
+    for name, bits, weighted in REUSE_STEPS:
+        enc = stores[name]
+        queries = rng.normal(size=(6, enc.vector_parameters.dim)).astype(f32)
+        b = enc.encode_query_batch(queries, b, query_bits=bits, weighted=weighted)
+        check_batch(enc, b, queries, bits, weighted, f"batch of 6, store {name}, {bits} bits")
+    enc = stores["B4100"]  # shrink and regrow on the matrix route: a stale code image or C tail would show
+    for bits in (8, 4):
+        for nq in (6, 2, 6):
+            queries = rng.normal(size=(nq, 100)).astype(f32)
+            b = enc.encode_query_batch(queries, b, query_bits=bits, weighted=True)
+            assert enc.batch_kernel(b, 0) == ("bin_gemm_rs_kernel" if nq == 6 else "bin_scan_kernel")
+            check_batch(enc, b, queries, bits, True, f"batch of {nq}, 4100 rows, {bits} bits")
