@@ -22,7 +22,7 @@ import sys
 import numpy as np
 import pytest
 
-from util import assert_bits_equal, topk_want
+from util import assert_bits_equal, oracle_meta, qa_meta, store_rows, topk_want, u8_actual_dim as actual_dim
 
 qa = pytest.importorskip("quantization_amd")
 D = qa.DistanceType
@@ -43,27 +43,6 @@ TOPK_KS = (100, 1024)
 TOPK_CASES = [(768, 20011), (144, 4099)]  # k > 64: the fused top-k, whose filtering pass is the FILTER form
 BIG = (144, 2_100_003)  # past the single-launch top-k's 2^21 rows; 32 813 blocks: one wave per block on any GPU
 LAYOUT = [(128, 1), (144, 65), (768, 1025), (2048, 130)]
-ALPHA = np.float32(1.0 / 127.0)
-
-
-def actual_dim(dim):
-    return -(-dim // 16) * 16
-
-
-def multiplier(dist):
-    return np.float32(ALPHA * ALPHA) if dist == D.Dot else np.float32(np.float32(-2.0) * ALPHA * ALPHA)
-
-
-def store_rows(dim, n, seed=0, codes=None):
-    """Reference-format rows [vector_offset f32][codes] with uniform random codes 0..127 (or the given ones) and the
-    query that goes with them."""
-    ad = actual_dim(dim)
-    rng = np.random.default_rng(dim * 131 + n * 7 + seed)
-    rows = np.zeros((n, ad + 4), dtype=np.uint8)
-    rows[:, :4] = rng.standard_normal(n).astype(np.float32).view(np.uint8).reshape(n, 4)
-    rows[:, 4:] = rng.integers(0, 128, size=(n, ad), dtype=np.uint8) if codes is None else codes
-    query = rng.random(dim, dtype=np.float32)
-    return rows, query
 
 
 def plane_codes(rc, e, b, n):
@@ -72,15 +51,6 @@ def plane_codes(rc, e, b, n):
     codes = np.zeros((n, 16 * rc), dtype=np.uint8)
     codes[:, 16 * (p + e):16 * (p + e + 1)] = 1 << b
     return codes
-
-
-def qa_meta(dim, n, dist):
-    return {"actual_dim": actual_dim(dim), "alpha": ALPHA, "offset": np.float32(0.0), "multiplier": multiplier(dist),
-            "vector_parameters": qa.VectorParameters(dim, n, dist, False)}
-
-
-def oracle_meta(qo, dim, n, dist):
-    return qo.Meta(actual_dim(dim), float(ALPHA), 0.0, float(multiplier(dist)), dim, n, int(dist), 0)
 
 
 def numpy_pack_blocked(codes):

@@ -79,6 +79,57 @@ SPECIAL_U8_GEMM_SHAPE = (33_000, 64, 5)
 SPECIAL_U8_SHORT_ROW_BATCHES = [(2 ** 20 + 7, 32, 2), (2 ** 20 + 7, 32, 4)]  # rs: rows too short for the vector-ALU pass
 
 
+# ------------------------------------------------------------------ u8 stores adopted from reference-format rows
+# Shared by tests/test_gpu_u8_blocked.py and tests/test_gpu_u8_byte_kernels.py: the test owns every byte of the store.
+U8_ALPHA = np.float32(1.0 / 127.0)
+
+
+def u8_actual_dim(dim):
+    return -(-dim // 16) * 16
+
+
+def u8_multiplier(dist):
+    return np.float32(U8_ALPHA * U8_ALPHA) if int(dist) == 0 else np.float32(np.float32(-2.0) * U8_ALPHA * U8_ALPHA)
+
+
+def store_rows(dim, n, seed=0, codes=None):
+    """Reference-format rows [vector_offset f32][codes] with uniform random codes 0..127 (or the given ones) and the
+    query that goes with them."""
+    ad = u8_actual_dim(dim)
+    rng = np.random.default_rng(dim * 131 + n * 7 + seed)
+    rows = np.zeros((n, ad + 4), dtype=np.uint8)
+    rows[:, :4] = rng.standard_normal(n).astype(np.float32).view(np.uint8).reshape(n, 4)
+    rows[:, 4:] = rng.integers(0, 128, size=(n, ad), dtype=np.uint8) if codes is None else codes
+    query = rng.random(dim, dtype=np.float32)
+    return rows, query
+
+
+def qa_meta(dim, n, dist):
+    """from_storage metadata of a Dot or L2 store (not inverted) at alpha 1 / 127, offset 0."""
+    import quantization_amd as qa
+
+    return {"actual_dim": u8_actual_dim(dim), "alpha": U8_ALPHA, "offset": np.float32(0.0), "multiplier": u8_multiplier(dist),
+            "vector_parameters": qa.VectorParameters(dim, n, dist, False)}
+
+
+def oracle_meta(qo, dim, n, dist):
+    return qo.Meta(u8_actual_dim(dim), float(U8_ALPHA), 0.0, float(u8_multiplier(dist)), dim, n, int(dist), 0)
+
+
+def oracle_metas(qo, dim, n, dist, invert):
+    """(from_storage metadata, oracle Meta) of a store of any metric and `invert` at alpha 1 / 127, offset 0, as the
+    reference's encoder writes them: taken from the oracle's encoder run on one zero vector, so that no formula is
+    restated here."""
+    import quantization_amd as qa
+
+    _, meta = qo.u8_encode_with(np.zeros((1, dim), dtype=np.float32), int(dist), bool(invert), float(U8_ALPHA), 0.0)
+    meta.count = n
+    md = {"actual_dim": int(meta.actual_dim), "alpha": np.float32(meta.alpha), "offset": np.float32(meta.offset),
+          "multiplier": np.float32(meta.multiplier),
+          "vector_parameters": qa.VectorParameters(dim, n, qa.DistanceType(int(dist)), bool(invert))}
+    return md, meta
+
+
 def have_gpu() -> bool:
     try:
         from quantization_amd import _lib
