@@ -701,7 +701,8 @@ QAMD_API qamd_status qamd_u8_sharded_from_rows(const uint8_t *rows, qamd_mem row
 QAMD_API uint32_t qamd_u8_sharded_shard_count(const qamd_u8_sharded *h);
 /* *state = a qamd_peer_state for shard g; *reason (may be NULL) = a static or handle-owned string saying why. */
 QAMD_API qamd_status qamd_u8_sharded_peer_access(const qamd_u8_sharded *h, uint32_t g, int *state, const char **reason);
-/* Borrow shard g (owned by the sharded handle): its single-device handle, first global row, device. */
+/* Borrow shard g (owned by the sharded handle): its single-device handle, first global row, device.  The pointer is
+ * `const` (here and for the binary and PQ handles): a shard cannot be upserted or reserved, the row bases are fixed. */
 QAMD_API qamd_status qamd_u8_sharded_shard(const qamd_u8_sharded *h, uint32_t g, const qamd_u8 **shard,
                                            uint64_t *row_begin, int *device);
 QAMD_API qamd_status qamd_u8_sharded_get_metadata(const qamd_u8_sharded *h, qamd_u8_metadata *out);
@@ -940,6 +941,65 @@ QAMD_API qamd_status qamd_bin_topk_batch_rescored(const qamd_bin *h, const qamd_
                                                   uint32_t k, uint32_t candidates, int largest,
                                                   uint32_t *out_ids, float *out_scores, qamd_mem out_mem,
                                                   void *stream);
+
+/* ===================================================================================
+ * Upsert: overwrite and append rows of a built store, in place.
+ *
+ * The reference snapshot this library was written against has NO counterpart: its
+ * EncodedVectors are immutable once `encode` returns.  Upstream has since gained
+ * `upsert_vector(id, vector)` (encode with the store's existing parameters, write at `id`,
+ * grow the storage when `id` is past the end); this header and DESIGN.md 3.9 are the
+ * specification of the form kept here: one call for a contiguous row range.
+ *
+ * Range.  `data` holds n_rows x vp.dim values; row first_row + r becomes the encoding of
+ *   data[r].  first_row <= count is required (a hole is QAMD_ERR_ARGUMENTS); rows below
+ *   count are overwritten, rows at and past count extend the store: count and
+ *   vector_parameters.count become max(count, first_row + n_rows) for *_get_metadata, save
+ *   and the count check of *_topk_rescored.  n_rows == 0 is QAMD_OK and touches nothing.
+ *   A new count above 0xFFFFFFFF is QAMD_ERR_ARGUMENTS.
+ * Parameters are the store's own; nothing is learnt again.  u8: metadata alpha / offset
+ *   (values outside the interval saturate as in the encoder; codes stay <= 127).  PQ: the
+ *   handle's centroids.  Binary: one bit, or the handle's lo / hi thresholds.  f32: the
+ *   handle's element type (f32 data is narrowed for f16 / bf16 stores; the source / store type
+ *   pairs are those of qamd_f32_from_data_typed).
+ * Refused with QAMD_ERR_ARGUMENTS: a u8 handle whose alpha is 0 (the metadata of an empty
+ *   store: there is no interval to encode with), a PQ handle without centroids, a borrowed
+ *   qamd_f32 (borrow = 1: the buffer is the caller's), a PQ store with a planar scan image
+ *   (several LUT slices, m % 32 == 0) that would reach 2^28 rows (its row stride would change).
+ *   Sharded handles and their shards cannot be upserted: qamd_*_sharded_shard hands out
+ *   `const` pointers, and the sharded handle's row bases are fixed.
+ * Derived images follow: the u8 offsets and 7-bit blocked scan image (kept when the store has
+ *   one; if growing it fails the store drops it and serves from its byte codes: the call still
+ *   succeeds), the PQ planar image, and the lazily gathered top-k pivot samples (discarded; the
+ *   next query batch gathers them again).  Lane mode, encoding and thresholds are untouched.
+ * Capacity.  A handle has room for *_capacity rows; every builder leaves capacity = count, so
+ *   a handle that is never upserted allocates what it always did.  reserve(c) with
+ *   c > capacity reallocates to c rows (internally round_up(c, 1024) + 1024, zero-filled past
+ *   count) and copies the rows device to device; c <= capacity is a no-op.  An upsert that
+ *   needs more than capacity first reserves max(needed, capacity + capacity / 2).  A failed
+ *   allocation is QAMD_ERR_DEVICE and leaves the handle as it was.
+ * Concurrency.  upsert and reserve are WRITERS: no other call on the same handle may be
+ *   running, or enqueued and unfinished, when they start.  They return after the rows are in
+ *   place (`stream` is synchronised).  Encoded queries and query batches made before an upsert
+ *   stay valid.
+ * =================================================================================== */
+QAMD_API qamd_status qamd_u8_upsert(qamd_u8 *h, uint64_t first_row, const float *data, qamd_mem data_mem,
+                                    uint64_t n_rows, void *stream);
+QAMD_API qamd_status qamd_pq_upsert(qamd_pq *h, uint64_t first_row, const float *data, qamd_mem data_mem,
+                                    uint64_t n_rows, void *stream);
+QAMD_API qamd_status qamd_bin_upsert(qamd_bin *h, uint64_t first_row, const float *data, qamd_mem data_mem,
+                                     uint64_t n_rows, void *stream);
+QAMD_API qamd_status qamd_f32_upsert(qamd_f32 *h, uint64_t first_row, const void *data, qamd_dtype data_dtype,
+                                     qamd_mem data_mem, uint64_t n_rows, void *stream);
+QAMD_API qamd_status qamd_u8_reserve(qamd_u8 *h, uint64_t capacity_rows, void *stream);
+QAMD_API qamd_status qamd_pq_reserve(qamd_pq *h, uint64_t capacity_rows, void *stream);
+QAMD_API qamd_status qamd_bin_reserve(qamd_bin *h, uint64_t capacity_rows, void *stream);
+QAMD_API qamd_status qamd_f32_reserve(qamd_f32 *h, uint64_t capacity_rows, void *stream);
+/* Rows the handle has room for without reallocating (0 for a null handle; count for a borrowed qamd_f32). */
+QAMD_API uint64_t qamd_u8_capacity(const qamd_u8 *h);
+QAMD_API uint64_t qamd_pq_capacity(const qamd_pq *h);
+QAMD_API uint64_t qamd_bin_capacity(const qamd_bin *h);
+QAMD_API uint64_t qamd_f32_capacity(const qamd_f32 *h);
 
 /* ===================================================================================
  * Selection over an existing score array (device memory), e.g. after a multi-GPU gather.

@@ -8,7 +8,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .encoded_vectors import check, check_same_device, in_buf, out_buf, stream_ptr
+from .encoded_vectors import (EncodingError, VectorParameters, check, check_same_device, flatten_rows, in_buf, out_buf,
+                              stream_ptr)
 
 
 class EncodedQueryBase:
@@ -66,7 +67,7 @@ class EncodedVectorsBase:
 
     @property
     def count(self) -> int:
-        if self._count is None:  # immutable after construction: one ABI round trip, not one per query
+        if self._count is None:  # changes only in upsert, which resets it: one ABI round trip, not one per query
             self._count = int(self.vector_parameters.count)
         return self._count
 
@@ -233,6 +234,44 @@ class EncodedVectorsBase:
         if isinstance(ids, np.ndarray):
             return ids.reshape(nq, k), sc.reshape(nq, k)
         return ids, sc
+
+    # ------------------------------------------------------------------ upsert: overwrite / append rows in place
+    def _writable(self):
+        if not self._owned:
+            raise ValueError("a shard borrowed from a sharded handle cannot be written: the sharded handle's row bases are fixed")
+
+    def upsert(self, first_row: int, data, stream=None) -> None:
+        """Rows first_row .. first_row + len(data) become the encodings of `data` [n, dim] under the store's own
+        parameters (nothing is learnt again); rows past the end extend the store, `first_row > count` is refused.  A
+        writer: no other call on this store may be running.  Upstream's later `upsert_vector(id, vector)`, for a row
+        range; the reference snapshot has no counterpart."""
+        self._writable()
+        vp = self.vector_parameters
+        data = flatten_rows(data, vp.dim)
+        shape = tuple(data.shape)
+        if len(shape) != 2 or (shape[0] and shape[1] != vp.dim):
+            raise EncodingError(_lib.ERR_ARGUMENTS, f"upsert takes [n, {vp.dim}] rows, got {shape}")
+        check_same_device(self._device, data)
+        buf = in_buf(data, np.float32)
+        check(self._fn("upsert")(self._h, int(first_row), buf.ptr, buf.mem, int(shape[0]), stream_ptr(stream)))
+        self._count = None  # the cached count: one ABI round trip again
+        if hasattr(self, "_vp"):
+            self._vp = VectorParameters(vp.dim, max(vp.count, int(first_row) + int(shape[0])), vp.distance_type, vp.invert)
+
+    def append(self, data, stream=None) -> None:
+        """upsert(count, data)."""
+        self._writable()
+        self.upsert(self.count, data, stream)
+
+    def reserve(self, n: int, stream=None) -> None:
+        """Room for `n` rows, so that upserts up to there do not reallocate; no-op when there already is."""
+        self._writable()
+        check(self._fn("reserve")(self._h, int(n), stream_ptr(stream)))
+
+    @property
+    def capacity(self) -> int:
+        """Rows the store has room for without reallocating."""
+        return int(self._fn("capacity")(self._h))
 
     def __del__(self):
         if getattr(self, "_h", None) and getattr(self, "_owned", True):

@@ -257,6 +257,19 @@ def lib() -> C.CDLL:
         "qamd_pq_topk_batch_rescored": (i32, [vp, vp, vp, vp, u64, u64, i32, u32, u32, i32, vp, vp, i32, vp]),
         "qamd_bin_topk_rescored": (i32, [vp, vp, vp, vp, u64, i32, u32, u32, i32, vp, vp, i32, vp]),
         "qamd_bin_topk_batch_rescored": (i32, [vp, vp, vp, vp, u64, u64, i32, u32, u32, i32, vp, vp, i32, vp]),
+        # upsert: overwrite / append rows of a built store
+        "qamd_u8_upsert": (i32, [vp, u64, vp, i32, u64, vp]),
+        "qamd_pq_upsert": (i32, [vp, u64, vp, i32, u64, vp]),
+        "qamd_bin_upsert": (i32, [vp, u64, vp, i32, u64, vp]),
+        "qamd_f32_upsert": (i32, [vp, u64, vp, i32, i32, u64, vp]),
+        "qamd_u8_reserve": (i32, [vp, u64, vp]),
+        "qamd_pq_reserve": (i32, [vp, u64, vp]),
+        "qamd_bin_reserve": (i32, [vp, u64, vp]),
+        "qamd_f32_reserve": (i32, [vp, u64, vp]),
+        "qamd_u8_capacity": (u64, [vp]),
+        "qamd_pq_capacity": (u64, [vp]),
+        "qamd_bin_capacity": (u64, [vp]),
+        "qamd_f32_capacity": (u64, [vp]),
         "qamd_topk_scores": (i32, [vp, u64, u32, i32, vp, vp, i32, vp]),
         "qamd_topk_merge": (i32, [vp, vp, u64, vp, u32, u32, u32, i32, vp, vp, i32, vp]),
     }

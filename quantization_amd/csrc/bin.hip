@@ -40,7 +40,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kScanBlock = 512;
-constexpr uint64_t kRowPad = 1024;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld_nt(const uint4 *p) {
@@ -806,9 +805,10 @@ struct qamd_bin {
     qamd_vector_parameters vp{};
     int store = 0;
     uint64_t count = 0;
+    uint64_t capacity = 0;  // rows there is room for: count after every builder, more after reserve / upsert
     uint64_t nb = 0;  // reference row bytes
     uint64_t ds = 0;  // device row stride (bytes)
-    DevBuf rows;      // [padded_rows][ds]
+    DevBuf rows;      // [round_up(capacity, 1024) + 1024][ds], zero from row count on
     // Two-bit rows: a row holds code_bits = 2 dim bits and is scored as a one-bit row of that length;
     // vp.dim stays the vectors' dimension (thresholds, queries, the originals of a rescored top-k).
     int encoding = QAMD_BIN_ONE_BIT;
@@ -816,7 +816,7 @@ struct qamd_bin {
     std::vector<float> thr_host;  // two-bit: lo[dim] | hi[dim]
     DevBuf thr;                   // the same, for the encoders of rows and queries
     // the batched top-k's pivot sample (rows hash(j) of the store, j < sample_count, then 512 zero rows);
-    // gathered once on first use (count / 64 rows at most), immutable after
+    // gathered on first use (count / 64 rows at most), discarded by an upsert
     mutable std::mutex sample_mu;
     mutable DevBuf sample_rows;
     mutable uint32_t sample_count = 0;
@@ -836,8 +836,8 @@ qamd_status alloc_store(qamd_bin *h) {
     h->code_bits = h->encoding == QAMD_BIN_TWO_BITS ? 2 * h->vp.dim : h->vp.dim;
     h->nb = row_bytes_of(h->code_bits, h->store);
     h->ds = device_stride_of(h->nb);
-    const uint64_t padded = round_up(h->count, kRowPad) + kRowPad;
-    return h->rows.alloc(padded * h->ds, true);
+    h->capacity = h->count;
+    return h->rows.alloc(padded_rows_of(h->capacity) * h->ds, true);
 }
 
 // calculate_metric's `dim` for a query of `planes` bit planes: the row's bits * (2^planes - 1), exact in f32
@@ -3177,6 +3177,58 @@ qamd_status qamd_bin_encoder_finish(qamd_bin_encoder *e, qamd_bin **out) {
 }
 
 void qamd_bin_encoder_abort(qamd_bin_encoder *e) { abort_encoder(e); }
+
+// ---- upsert: rows overwritten or appended with the store's own encoding and thresholds - launch_bin_encode
+// at a row offset, as the streaming encoder's push.  The reference snapshot has no counterpart.
+static qamd_status bin_grow(qamd_bin *h, uint64_t cap) {
+    if (cap <= h->capacity) return QAMD_OK;
+    DevBuf rows;
+    QAMD_TRY(grow_copy(h->rows, padded_rows_of(cap) * h->ds, h->count * h->ds, rows));
+    h->rows = std::move(rows);  // (the old buffer goes through hipFree, which waits for the device)
+    h->capacity = cap;
+    return QAMD_OK;
+}
+
+uint64_t qamd_bin_capacity(const qamd_bin *h) { return h ? h->capacity : 0; }
+
+qamd_status qamd_bin_reserve(qamd_bin *h, uint64_t capacity_rows, void *stream) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    if (capacity_rows > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "capacity exceeds u32 row ids");
+    if (capacity_rows <= h->capacity) return QAMD_OK;
+    QAMD_ON_DEVICE(h->device);
+    QAMD_HIP(hipStreamSynchronize(as_stream(stream)));
+    return bin_grow(h, capacity_rows);
+}
+
+qamd_status qamd_bin_upsert(qamd_bin *h, uint64_t first_row, const float *data, qamd_mem data_mem, uint64_t n_rows,
+                            void *stream) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    const uint64_t dim = h->vp.dim;
+    QAMD_TRY(check_upsert(first_row, n_rows, h->count, data, dim));
+    if (n_rows == 0) return QAMD_OK;
+    QAMD_ON_DEVICE(h->device);
+    hipStream_t s = as_stream(stream);
+    const uint64_t end = first_row + n_rows;
+    if (end > h->capacity) {
+        QAMD_HIP(hipStreamSynchronize(s));
+        QAMD_TRY(bin_grow(h, std::min<uint64_t>(upsert_capacity(end, h->capacity), 0xFFFFFFFFull)));
+    }
+    if (dim) {
+        DevBuf stage;
+        const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / (dim * 4));
+        QAMD_TRY(for_each_staged_piece(data, data_mem, n_rows, dim, piece_rows, stage, s,
+                                       [&](const float *src, uint64_t r, uint64_t nr) {
+            return launch_bin_encode(h, src, nr, first_row + r, s);
+        }));
+    }
+    QAMD_HIP(hipStreamSynchronize(s));
+    h->count = std::max(h->count, end);
+    h->vp.count = h->count;
+    std::lock_guard<std::mutex> lk(h->sample_mu);  // the next query batch gathers its pivot sample again
+    h->sample_rows.release();
+    h->sample_count = 0;
+    return QAMD_OK;
+}
 
 }  // extern "C"
 

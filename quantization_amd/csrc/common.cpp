@@ -95,6 +95,16 @@ void DevBuf::release() {
     bytes = 0;
 }
 
+qamd_status grow_copy(const DevBuf &old, size_t n, size_t keep, DevBuf &out) {
+    if (keep > n || keep > old.bytes) return fail(QAMD_ERR_ARGUMENTS, "grow_copy: keeps %zu of %zu bytes in %zu", keep, old.bytes, n);
+    QAMD_TRY(out.alloc_zero_tail(n, keep));
+    if (keep) {
+        QAMD_HIP(hipMemcpyAsync(out.ptr, old.ptr, keep, hipMemcpyDeviceToDevice, nullptr));
+        QAMD_HIP(hipStreamSynchronize(nullptr));
+    }
+    return QAMD_OK;
+}
+
 namespace {
 struct QueryBufCache {
     struct Entry { void *ptr; size_t bytes; int dev; };
@@ -525,6 +535,17 @@ qamd_status check_row_range(uint64_t first_row, uint64_t n_rows, uint64_t count)
     if (first_row > count || n_rows > count - first_row)
         return fail(QAMD_ERR_OUT_OF_RANGE, "rows [%llu, +%llu) out of range (count %llu)", (unsigned long long)first_row,
                     (unsigned long long)n_rows, (unsigned long long)count);
+    return QAMD_OK;
+}
+
+qamd_status check_upsert(uint64_t first_row, uint64_t n_rows, uint64_t count, const void *data, uint64_t dim) {
+    if (first_row > count)
+        return fail(QAMD_ERR_ARGUMENTS, "upsert at row %llu would leave a hole: the store has %llu rows", (unsigned long long)first_row,
+                    (unsigned long long)count);
+    if (n_rows > 0xFFFFFFFFull - first_row)
+        return fail(QAMD_ERR_ARGUMENTS, "upsert of %llu rows at row %llu: count exceeds u32 row ids", (unsigned long long)n_rows,
+                    (unsigned long long)first_row);
+    if (n_rows && dim && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
     return QAMD_OK;
 }
 

@@ -172,6 +172,11 @@ struct DevBuf {
     template <typename T> T *as() const { return static_cast<T *>(ptr); }
 };
 
+// Growth of a store's buffer (reserve / upsert): `out` becomes a fresh allocation of `n` bytes whose first `keep` bytes are
+// a device-to-device copy of `old`'s and whose tail [keep, n) is zero.  `old` stays as it is: a caller swaps the buffers in
+// only after every allocation of its call has succeeded.  Complete on return.
+qamd_status grow_copy(const DevBuf &old, size_t n, size_t keep, DevBuf &out);
+
 // Recycles the small device buffers behind encoded-query objects.  The reference's encode_query
 // returns a fresh EncodedQuery value per call (encoded_vectors.rs:27); a binding that mirrors that
 // creates and drops one query object per search, and a hipMalloc + hipFree pair costs more than a
@@ -298,6 +303,14 @@ template <class Encoder> void abort_encoder(Encoder *e) {
 }
 // The range check of *_export_rows_range.
 qamd_status check_row_range(uint64_t first_row, uint64_t n_rows, uint64_t count);
+// The argument checks of *_upsert (no device call): a hole, null data for rows of `dim` > 0 values, a count past u32 ids.
+qamd_status check_upsert(uint64_t first_row, uint64_t n_rows, uint64_t count, const void *data, uint64_t dim);
+// Rows a store is allocated for, given the rows it has room for: rows are padded so that every wave tile is in bounds
+// (whole tiles of 64 and 1024 rows exist past every row).
+constexpr uint64_t kRowPad = 1024;
+inline uint64_t padded_rows_of(uint64_t capacity) { return (capacity + kRowPad - 1) / kRowPad * kRowPad + kRowPad; }
+// What an upsert that needs room for `needed` rows reserves: growth by half, so that appends cost amortised O(1) copies.
+inline uint64_t upsert_capacity(uint64_t needed, uint64_t capacity) { return std::max(needed, capacity + capacity / 2); }
 
 struct DeviceInfo {
     int cu_count = 256;

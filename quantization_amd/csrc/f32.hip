@@ -466,7 +466,27 @@ qamd_status from_data_any(const void *data, qamd_dtype data_dtype, qamd_mem data
         if (data_mem == QAMD_MEM_DEVICE || data_dtype != store_dtype) QAMD_HIP(hipStreamSynchronize(s));
         h->data = h->owned.ptr;
     }
+    h->capacity = vp->count;
     *out = h.release();
+    return QAMD_OK;
+}
+
+// upsert: room for `cap` rows of an owned store.  No kernel reads past row count, so the tail is only kept
+// zero for the sake of one rule for all four stores.
+qamd_status f32_grow(qamd_f32 *h, uint64_t cap) {
+    if (cap <= h->capacity) return QAMD_OK;
+    const uint64_t row_bytes = h->vp.dim * dtype_size(h->dtype);
+    DevBuf rows;
+    QAMD_TRY(grow_copy(h->owned, std::max<uint64_t>(padded_rows_of(cap) * row_bytes, 1), h->vp.count * row_bytes, rows));
+    h->owned = std::move(rows);  // (the old buffer goes through hipFree, which waits for the device)
+    h->data = h->owned.ptr;
+    h->capacity = cap;
+    return QAMD_OK;
+}
+
+qamd_status check_owned(const qamd_f32 *h) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    if (!h->owned.ptr) return fail(QAMD_ERR_ARGUMENTS, "a borrowed store cannot be written: its buffer is the caller's");
     return QAMD_OK;
 }
 
@@ -546,6 +566,54 @@ qamd_status qamd_f32_rerank_batch(const qamd_f32 *h, const float *queries, uint6
                                   int largest, uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream) {
     return rerank_any(h, queries, n_queries, qdim, queries_mem, ids, n_ids, ids_mem, k, largest, out_ids, out_scores, out_mem,
                       as_stream(stream));
+}
+
+uint64_t qamd_f32_capacity(const qamd_f32 *h) { return h ? (h->owned.ptr ? h->capacity : h->vp.count) : 0; }
+
+qamd_status qamd_f32_reserve(qamd_f32 *h, uint64_t capacity_rows, void *stream) {
+    QAMD_TRY(check_owned(h));
+    if (capacity_rows > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "at most 2^32 - 1 vectors");
+    if (capacity_rows <= h->capacity) return QAMD_OK;
+    QAMD_ON_DEVICE(h->device);
+    QAMD_HIP(hipStreamSynchronize(as_stream(stream)));
+    return f32_grow(h, capacity_rows);
+}
+
+// Rows [first_row, first_row + n_rows) of an owned store become `data` (the store's element type, or f32 narrowed to it
+// as in qamd_f32_from_data_typed); rows past the end extend it.
+qamd_status qamd_f32_upsert(qamd_f32 *h, uint64_t first_row, const void *data, qamd_dtype data_dtype, qamd_mem data_mem,
+                            uint64_t n_rows, void *stream) {
+    QAMD_TRY(check_owned(h));
+    const uint64_t dim = h->vp.dim;
+    QAMD_TRY(check_upsert(first_row, n_rows, h->vp.count, data, dim));
+    if (!dtype_known(data_dtype)) return fail(QAMD_ERR_ARGUMENTS, "unknown element type (data %d)", (int)data_dtype);
+    if (data_dtype != h->dtype && data_dtype != QAMD_DTYPE_F32)
+        return fail(QAMD_ERR_ARGUMENTS, "%s data cannot be kept as %s: only f32 data is converted", dtype_name(data_dtype),
+                    dtype_name(h->dtype));
+    if (n_rows == 0) return QAMD_OK;
+    QAMD_ON_DEVICE(h->device);
+    hipStream_t s = as_stream(stream);
+    const uint64_t end = first_row + n_rows;
+    if (end > h->capacity) {
+        QAMD_HIP(hipStreamSynchronize(s));
+        QAMD_TRY(f32_grow(h, std::min<uint64_t>(upsert_capacity(end, h->capacity), 0xFFFFFFFFull)));
+    }
+    const size_t esize = dtype_size(h->dtype);
+    char *dst = h->owned.as<char>() + first_row * dim * esize;
+    if (data_dtype == h->dtype) {
+        QAMD_TRY(copy_in(dst, data, data_mem, n_rows * dim * esize, s));
+    } else if (dim) {  // narrowed on the device, piece by piece (from_data_any)
+        uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / (dim * 4));
+        if (piece_rows > 4) piece_rows -= piece_rows % 4;
+        DevBuf stage;
+        QAMD_TRY(for_each_staged_piece(static_cast<const float *>(data), data_mem, n_rows, dim, piece_rows, stage, s,
+                                       [&](const float *src, uint64_t r, uint64_t nr) {
+                                           return narrow_launch(src, reinterpret_cast<uint16_t *>(dst) + r * dim, nr * dim, h->dtype, s);
+                                       }));
+    }
+    QAMD_HIP(hipStreamSynchronize(s));
+    h->vp.count = std::max(h->vp.count, end);
+    return QAMD_OK;
 }
 
 }  // extern "C"

@@ -35,7 +35,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kScanBlock = 1024;
-constexpr uint64_t kRowPad = 1024;
 constexpr int kCentroids = QAMD_PQ_CENTROIDS;
 constexpr uint64_t kKmeansSample = 10000;  // KMEANS_SAMPLE_SIZE (:22)
 constexpr int kKmeansMaxIter = 100;        // KMEANS_MAX_ITERATIONS (:23)
@@ -1294,13 +1293,14 @@ struct qamd_pq {
     uint32_t kmeans_workers = 1;        // max_kmeans_threads: fixes the f64 summation order (kmeans.rs:77-107)
     uint32_t kmeans_iterations = 0;     // iterations the slowest chunk took (0: centroids were given)
     uint32_t kmeans_empty_clusters = 0; // clusters re-seeded over all iterations (kmeans.rs:111-118)
-    DevBuf rows;                        // [padded][ds]
+    uint64_t capacity = 0;              // rows there is room for: count after every builder, more after reserve / upsert
+    DevBuf rows;                        // [padded][ds], zero from row count on
     // Rows of several LUT slices (m > 144) with m % 32 == 0: the scan image - slice after slice, each a contiguous
     // [padded][chunks of the slice] array (slice i starts at byte slice_chunk0[i] * padded) - that pq_scan_skew_kernel<SLICED>
     // reads; `rows` stays the random-access image (score_ids, bursts, score_internal, export).
     DevBuf planar;
     std::vector<uint32_t> slice_chunk0, slice_chunks;
-    uint64_t padded = 0;
+    uint64_t padded = 0;  // round_up(capacity, 1024) + 1024
 };
 
 struct qamd_pq_query {
@@ -1336,7 +1336,8 @@ qamd_status alloc_store(qamd_pq *h) {
     // slices (m > 144, not a multiple of 32) sit on a 128-byte pitch so that a slice launch reads whole lines
     h->ds = h->m < 16 ? round_up(std::max<uint64_t>(h->m, 1), 4)
           : (valid_pieces(h->m) > kMaxSlicePieces && !planar) ? round_up(h->m, 16 * kSlicePiecesAligned) : round_up(h->m, 16);
-    h->padded = round_up(h->count, kRowPad) + kRowPad;
+    h->capacity = h->count;
+    h->padded = padded_rows_of(h->capacity);
     if (planar) QAMD_TRY(h->planar.alloc(h->padded * h->m, true));
     return h->rows.alloc(h->padded * h->ds, true);
 }
@@ -2419,6 +2420,89 @@ qamd_status qamd_pq_encoder_finish(qamd_pq_encoder *e, qamd_pq **out) {
 }
 
 void qamd_pq_encoder_abort(qamd_pq_encoder *e) { abort_encoder(e); }
+
+}  // extern "C"
+
+// ============================================================================= upsert
+// Rows of a built store are overwritten or appended with the handle's centroids: launch_assign at a row offset, as the
+// streaming encoder's push.  The reference snapshot has no counterpart (upstream's later upsert_vector is the model).
+namespace {
+
+// Room for `cap` rows.  The planar image's slice bases are multiples of `padded`, so a grown image is laid out again from
+// the row-major rows (build_planar over all of them) instead of being copied.
+qamd_status pq_grow(qamd_pq *h, uint64_t cap, hipStream_t s) {
+    if (cap <= h->capacity) return QAMD_OK;
+    const uint64_t padded = padded_rows_of(cap);
+    DevBuf rows, planar;
+    QAMD_TRY(grow_copy(h->rows, padded * h->ds, h->count * h->ds, rows));
+    if (h->planar.ptr) QAMD_TRY(planar.alloc(padded * h->m, true));
+    h->rows = std::move(rows);  // (the old buffers go through hipFree, which waits for the device)
+    if (planar.ptr) h->planar = std::move(planar);
+    h->capacity = cap;
+    h->padded = padded;
+    QAMD_TRY(build_planar(h, 0, h->count, s));
+    QAMD_HIP(hipStreamSynchronize(s));
+    return QAMD_OK;
+}
+
+// A store with a planar image stays below the row count at which alloc_store gives none: the row stride differs there.
+qamd_status pq_check_planar_rows(const qamd_pq *h, uint64_t rows) {
+    if (h->planar.ptr && rows >= pq_planar_max_rows())
+        return fail(QAMD_ERR_ARGUMENTS, "a store with a planar scan image cannot reach %llu rows (asked for %llu): build it anew",
+                    (unsigned long long)pq_planar_max_rows(), (unsigned long long)rows);
+    return QAMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t qamd_pq_capacity(const qamd_pq *h) { return h ? h->capacity : 0; }
+
+qamd_status qamd_pq_reserve(qamd_pq *h, uint64_t capacity_rows, void *stream) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    if (capacity_rows > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "capacity exceeds u32 row ids");
+    if (capacity_rows <= h->capacity) return QAMD_OK;
+    QAMD_TRY(pq_check_planar_rows(h, capacity_rows));
+    QAMD_ON_DEVICE(h->device);
+    QAMD_HIP(hipStreamSynchronize(as_stream(stream)));
+    return pq_grow(h, capacity_rows, as_stream(stream));
+}
+
+qamd_status qamd_pq_upsert(qamd_pq *h, uint64_t first_row, const float *data, qamd_mem data_mem, uint64_t n_rows,
+                           void *stream) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    const uint64_t dim = h->vp.dim;
+    QAMD_TRY(check_upsert(first_row, n_rows, h->count, data, dim));
+    if (n_rows == 0) return QAMD_OK;
+    if (h->centroids_host.empty()) return fail(QAMD_ERR_ARGUMENTS, "the store has no centroids to encode with");
+    const uint64_t end = first_row + n_rows;
+    QAMD_TRY(pq_check_planar_rows(h, end));
+    QAMD_ON_DEVICE(h->device);
+    hipStream_t s = as_stream(stream);
+    if (end > h->capacity) {
+        uint64_t cap = std::min<uint64_t>(upsert_capacity(end, h->capacity), 0xFFFFFFFFull);
+        if (h->planar.ptr) cap = std::min(cap, pq_planar_max_rows() - 1);  // (end is below it)
+        QAMD_HIP(hipStreamSynchronize(s));
+        QAMD_TRY(pq_grow(h, cap, s));
+    }
+    if (dim) {
+        DevBuf stage, pair_table;
+        if (cs_fast_shape(dim, h->chunk_size))
+            QAMD_TRY(build_pair_table(h->centroids.as<float>(), dim, h->chunk_size, h->m, pair_table, s));
+        const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / (dim * 4));
+        QAMD_TRY(for_each_staged_piece(data, data_mem, n_rows, dim, piece_rows, stage, s,
+                                       [&](const float *src, uint64_t r, uint64_t nr) -> qamd_status {
+            QAMD_TRY(launch_assign(src, nr, dim, h->chunk_size, h->m, h->centroids.as<float>(), &pair_table,
+                                   h->rows.as<uint8_t>(), h->ds, first_row + r, s));
+            return build_planar(h, first_row + r, nr, s);  // only the touched rows
+        }));
+    }
+    QAMD_HIP(hipStreamSynchronize(s));
+    h->count = std::max(h->count, end);
+    h->vp.count = h->count;
+    return QAMD_OK;
+}
 
 }  // extern "C"
 

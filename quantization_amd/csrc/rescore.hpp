@@ -17,6 +17,7 @@ struct qamd_f32 {
     qamd_dtype dtype = QAMD_DTYPE_F32;
     const void *data = nullptr;
     qamd::DevBuf owned;
+    uint64_t capacity = 0;  // rows `owned` has room for: count after from_data, more after reserve / upsert
 };
 
 namespace qamd {

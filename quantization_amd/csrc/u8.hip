@@ -48,7 +48,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kScanBlock = 512;  // scan workgroup (tuning sweep: 512 and 1024 tie, 256 is ~1% behind)
-constexpr uint64_t kRowPad = 1024;  // rows are padded so that every wave tile is in bounds
 constexpr uint64_t kQuantileSample = 100000;  // QUANTILE_SAMPLE_SIZE, quantile.rs:3
 
 enum Epilogue : int { EPI_POINT = 0, EPI_INTERNAL = 1 };
@@ -1157,6 +1156,31 @@ __global__ __launch_bounds__(kBlock) void u8_pack7_kernel(const uint4 *__restric
     if (high & 0x80808080u) atomicOr(bad, 1u);
 }
 
+// u8_pack7_kernel for rows [r0, r0 + n_rows) of a store that has an image (upsert): every (row, chunk) slot is 16 bytes of
+// its own, so the slots of the block's other rows stay as they are.  The rows come from the store's own encoder: no code
+// is above 127, and nothing is reported.
+__global__ __launch_bounds__(kBlock) void u8_pack7_range_kernel(const uint4 *__restrict__ codes, uint64_t r0, uint64_t n_rows,
+                                                                uint32_t row_chunks, uint32_t pchunks, uint32_t n_extra,
+                                                                uint4 *__restrict__ packed) {
+    const uint64_t total = n_rows * pchunks, stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
+        const uint64_t r = r0 + t / pchunks;
+        const uint32_t j = (uint32_t)(t % pchunks);
+        const uint4 *row = codes + r * row_chunks;
+        const uint4 a = row[j];
+        uint32_t w[4] = {a.x & 0x7F7F7F7Fu, a.y & 0x7F7F7F7Fu, a.z & 0x7F7F7F7Fu, a.w & 0x7F7F7F7Fu};
+        if (j < 7 * n_extra) {
+            const uint4 x = row[pchunks + j / 7];
+            const uint32_t b = j % 7;
+            w[0] |= ((x.x >> b) & 0x01010101u) << 7;
+            w[1] |= ((x.y >> b) & 0x01010101u) << 7;
+            w[2] |= ((x.z >> b) & 0x01010101u) << 7;
+            w[3] |= ((x.w >> b) & 0x01010101u) << 7;
+        }
+        packed[((r / kPackBlockRows) * pchunks + j) * kPackBlockRows + r % kPackBlockRows] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
 int grid_for(uint64_t work_items, uint64_t per_block, int blocks_per_cu) {
     uint64_t want = (work_items + per_block - 1) / per_block;
     uint64_t cap = (uint64_t)device_info().cu_count * blocks_per_cu;
@@ -1180,7 +1204,8 @@ uint64_t actual_dim_of(uint64_t dim) { return dim + (16 - dim % 16) % 16; }  // 
 namespace {
 
 qamd_status alloc_store(qamd_u8 *h) {
-    h->padded_rows = round_up(h->count, kRowPad) + kRowPad;
+    h->capacity = h->count;
+    h->padded_rows = padded_rows_of(h->capacity);
     h->row_chunks = (uint32_t)(h->meta.actual_dim / 16);
     // every builder (encode, from_rows, load) writes all `count` rows; only the padding is zeroed
     QAMD_TRY(h->codes.alloc_zero_tail(h->padded_rows * h->meta.actual_dim, h->count * h->meta.actual_dim));
@@ -2397,6 +2422,96 @@ qamd_status qamd_u8_encoder_finish(qamd_u8_encoder *e, qamd_u8 **out) {
 }
 
 void qamd_u8_encoder_abort(qamd_u8_encoder *e) { abort_encoder(e); }
+
+}  // extern "C"
+
+// ============================================================================= upsert
+// Rows of a built store are overwritten or appended with the store's own alpha / offset: launch_quantize at a row offset,
+// as the streaming encoder's push.  The reference snapshot has no counterpart (upstream's later upsert_vector is the model).
+namespace {
+
+// Room for `cap` rows: new buffers with the rows copied and a zero tail, swapped in once all of them exist.  The packed
+// image's block index does not depend on the row count, so its whole blocks are copied as they are; when the larger image
+// cannot be had the store goes on without one (its scans read the byte codes), which is not a failure of the call.
+qamd_status u8_grow(qamd_u8 *h, uint64_t cap) {
+    if (cap <= h->capacity) return QAMD_OK;
+    const uint64_t padded = padded_rows_of(cap), ad = h->meta.actual_dim;
+    DevBuf codes, offsets, packed;
+    QAMD_TRY(grow_copy(h->codes, padded * ad, h->count * ad, codes));
+    QAMD_TRY(grow_copy(h->offsets, padded * sizeof(float), h->count * sizeof(float), offsets));
+    bool image = h->packed_chunks != 0;
+    if (image) {
+        const uint64_t chunk_bytes = (uint64_t)h->packed_chunks * 16;
+        const std::string err = last_error();
+        if (grow_copy(h->packed, padded * chunk_bytes, round_up(h->count, kPackBlockRows) * chunk_bytes, packed) != QAMD_OK) {
+            (void)hipGetLastError();  // an out-of-memory here only costs the image
+            last_error() = err;
+            packed.release();
+            image = false;
+        }
+    }
+    h->codes = std::move(codes);  // (the old buffers go through hipFree, which waits for the device)
+    h->offsets = std::move(offsets);
+    h->packed = std::move(packed);
+    if (!image) h->packed_chunks = 0;
+    h->packed_rows.release();
+    h->capacity = cap;
+    h->padded_rows = padded;
+    return QAMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t qamd_u8_capacity(const qamd_u8 *h) { return h ? h->capacity : 0; }
+
+qamd_status qamd_u8_reserve(qamd_u8 *h, uint64_t capacity_rows, void *stream) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    if (capacity_rows > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "capacity exceeds u32 row ids");
+    if (capacity_rows <= h->capacity) return QAMD_OK;
+    QAMD_ON_DEVICE(h->device);
+    QAMD_HIP(hipStreamSynchronize(as_stream(stream)));
+    return u8_grow(h, capacity_rows);
+}
+
+qamd_status qamd_u8_upsert(qamd_u8 *h, uint64_t first_row, const float *data, qamd_mem data_mem, uint64_t n_rows,
+                           void *stream) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    const uint64_t dim = h->meta.vector_parameters.dim;
+    QAMD_TRY(check_upsert(first_row, n_rows, h->count, data, dim));
+    if (n_rows == 0) return QAMD_OK;
+    if (h->meta.alpha == 0.0f)
+        return fail(QAMD_ERR_ARGUMENTS, "the store has no quantization interval (alpha is 0: it was built empty)");
+    QAMD_ON_DEVICE(h->device);
+    hipStream_t s = as_stream(stream);
+    const uint64_t end = first_row + n_rows;
+    if (end > h->capacity) {
+        QAMD_HIP(hipStreamSynchronize(s));
+        QAMD_TRY(u8_grow(h, std::min<uint64_t>(upsert_capacity(end, h->capacity), 0xFFFFFFFFull)));
+    }
+    DevBuf stage;
+    const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(kStagePieceBytes) / (dim * 4 + 1));
+    QAMD_TRY(for_each_staged_piece(data, data_mem, n_rows, dim, piece_rows, stage, s,
+                                   [&](const float *src, uint64_t r, uint64_t nr) {
+        return launch_quantize(h, src, nr, first_row + r, h->meta.alpha, h->meta.offset, s);
+    }));
+    if (h->packed_chunks) {
+        const uint32_t rc = h->row_chunks, pchunks = h->packed_chunks;
+        hipLaunchKernelGGL(u8_pack7_range_kernel, dim3(grid_for(n_rows * pchunks, kBlock, 8)), dim3(kBlock), 0, s,
+                           h->codes.as<uint4>(), first_row, n_rows, rc, pchunks, rc / 8, h->packed.as<uint4>());
+        QAMD_HIP(hipGetLastError());
+    }
+    QAMD_HIP(hipStreamSynchronize(s));
+    h->count = std::max(h->count, end);
+    h->meta.vector_parameters.count = h->count;
+    h->packed_rows.release();
+    std::lock_guard<std::mutex> lk(h->sample_mu);  // the next query batch gathers its pivot sample again
+    h->sample_codes.release();
+    h->sample_offsets.release();
+    h->sample_rows = 0;
+    return QAMD_OK;
+}
 
 }  // extern "C"
 

@@ -11,7 +11,8 @@ struct qamd_u8 {
     int device = 0;
     qamd_u8_metadata meta{};
     uint64_t count = 0;
-    uint64_t padded_rows = 0;  // round_up(count, 1024) + 1024 zero rows: tiles never need a load guard
+    uint64_t capacity = 0;     // rows there is room for: count after every builder, more after reserve / upsert
+    uint64_t padded_rows = 0;  // round_up(capacity, 1024) + 1024; rows from count on are zero: tiles never need a load guard
     uint32_t row_chunks = 0;   // actual_dim / 16
     int lane_mode = 0;         // 0: integer sum rounded once; 1: avx2.c lane order
     qamd::DevBuf codes;        // [padded_rows][actual_dim]
@@ -29,7 +30,7 @@ struct qamd_u8 {
     mutable std::atomic<int> last_scan_split{0};   // waves per block of the last blocked scan launch (developer report)
     mutable qamd::DevBuf packed_rows;              // developer report: the image un-blocked, [count][packed_chunks]
     // The batched top-k's pivot sample (u8_batch.hip): rows hash(j) of the store, j < sample_rows, then 512
-    // zero rows; gathered once on first use (count / 64 rows at most: 1.6 % of the store), immutable after.
+    // zero rows; gathered on first use (count / 64 rows at most: 1.6 % of the store), discarded by an upsert.
     mutable std::mutex sample_mu;
     mutable qamd::DevBuf sample_codes, sample_offsets;
     mutable uint32_t sample_rows = 0;

@@ -107,6 +107,46 @@ class OriginalVectors:
         check(_lib.lib().qamd_f32_get_parameters(self._h, C.byref(c)))
         return VectorParameters.from_c(c)
 
+    # ------------------------------------------------------------------ upsert: overwrite / append rows in place
+    def upsert(self, first_row: int, data, stream=None) -> None:
+        """Rows first_row .. first_row + len(data) become `data` [n, dim]: data of the store's own element type (f16,
+        bf16, or uint16 bit patterns for a bf16 store) is taken as it is, anything else is read as f32 and narrowed.
+        Rows past the end extend the store; `first_row > count` and a borrowed store are refused.  A writer: no other
+        call on this store may be running."""
+        dim, kept = self.vector_parameters.dim, self.dtype
+        data = flatten_rows(data, dim)
+        shape = tuple(data.shape)
+        if len(shape) != 2 or (shape[0] and shape[1] != dim):
+            raise ValueError(f"upsert takes [n, {dim}] rows, got {shape}")
+        given = _element_type(data)
+        if given == "u16":
+            if kept != "bf16":
+                raise ValueError("uint16 data is taken as bf16 bit patterns: the store keeps " + kept)
+            given = "bf16"
+        if given in ("f16", "bf16") and given != kept:
+            raise ValueError(f"{given} data cannot be kept as {kept}: only f32 data is converted")
+        check_same_device(self._device, data)
+        if given == kept and given != "f32":
+            buf = _raw_buf(data)
+        else:
+            buf, given = in_buf(data, np.float32), "f32"
+        check(_lib.lib().qamd_f32_upsert(self._h, int(first_row), buf.ptr, DTYPES[given], buf.mem, int(shape[0]),
+                                         stream_ptr(stream)))
+        self.vector_parameters = self.get_parameters()  # the cached parameters: count may have grown
+
+    def append(self, data, stream=None) -> None:
+        """upsert(count, data)."""
+        self.upsert(self.count, data, stream)
+
+    def reserve(self, n: int, stream=None) -> None:
+        """Room for `n` rows, so that upserts up to there do not reallocate; no-op when there already is."""
+        check(_lib.lib().qamd_f32_reserve(self._h, int(n), stream_ptr(stream)))
+
+    @property
+    def capacity(self) -> int:
+        """Rows the store has room for without reallocating (a borrowed store: its count)."""
+        return int(_lib.lib().qamd_f32_capacity(self._h))
+
     def _query(self, q):
         check_same_device(self._device, q)
         return in_buf(q, np.float32)
