@@ -23,7 +23,8 @@ import numpy as np
 import pytest
 
 import quantization_amd as qa
-from util import assert_bits_equal, scalar_codes, scalar_metric, scalar_planes, scalar_xor, topk_want
+from util import BinOracle as Oracle, assert_bits_equal, bin_open_rows as open_rows, bin_query_of as query_of
+from util import bin_random_rows as random_rows, gaussian, scalar_codes, scalar_planes, topk_want
 
 pytestmark = pytest.mark.gpu
 
@@ -49,53 +50,9 @@ TIE_DIM = 128
 
 
 # ------------------------------------------------------------------ data and the oracle
-def gaussian(rng, shape):
-    x = rng.standard_normal(shape).astype(np.float32)
-    flat = x.reshape(-1)
-    if flat.size >= 8:
-        at = rng.choice(flat.size, size=max(2, flat.size // 50), replace=False)
-        flat[at[::2]] = 0.0
-        flat[at[1::2]] = -0.0
-    return x
-
-
-def query_of(dim, seed=0):
-    return gaussian(np.random.default_rng(77_000 + 13 * dim + seed), (dim,))
-
-
-def row_bytes(dim, kind=U8):
-    return qa.EncodedVectorsBin.get_quantized_vector_size_from_params(qa.VectorParameters(dim, 1, D.Dot, False), kind)
-
-
-def random_rows(n, dim, seed, kind=U8):
-    """Random bits in the store's own row size, pad bits zero as the encoder leaves them."""
-    bits = np.random.default_rng(seed).integers(0, 2, size=(n, dim), dtype=np.uint8)
-    rows = np.zeros((n, row_bytes(dim, kind)), dtype=np.uint8)
-    packed = np.packbits(bits, axis=1, bitorder="little")
-    rows[:, :packed.shape[1]] = packed
-    return rows
-
-
 def tie_rows(n):
     rng = np.random.default_rng(8 + n)
     return np.ascontiguousarray(rng.integers(0, 256, size=(8, TIE_DIM // 8), dtype=np.uint8)[rng.integers(0, 8, size=n)])
-
-
-def open_rows(rows, dim, dist=D.Dot, invert=False, kind=U8):
-    return qa.EncodedVectorsBin.from_storage(rows, qa.VectorParameters(dim, rows.shape[0], dist, invert), store=kind)
-
-
-class Oracle:
-    """X of every row for one (rows, query), computed once per bit width; the six metrics are taken from it."""
-
-    def __init__(self, rows, query, dim):
-        self.rows, self.query, self.dim, self._x = rows, query, dim, {}
-
-    def scores(self, bits, dist=D.Dot, invert=False):
-        if bits not in self._x:
-            codes = (np.asarray(self.query) > 0).astype(np.uint32) if bits == 1 else scalar_codes(self.query, bits)[0]
-            self._x[bits] = scalar_xor(self.rows, codes, self.dim, bits)
-        return scalar_metric(self._x[bits], self.dim, bits, dist, invert)
 
 
 _ORACLES = {}

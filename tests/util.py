@@ -267,20 +267,27 @@ def scalar_planes(codes, bits: int, nb: int) -> np.ndarray:
 
 def scalar_xor(rows_u8, codes, dim: int, bits: int) -> np.ndarray:
     """int64[n]: X of every stored bit row.  Bit i of a row is byte i / 8, bit i % 8 (s_i in {0, 1});
-    S = sum_i (2 s_i - 1)(2 c_i - L) and X = (dim * L - S) / 2, exact.  Only the first `dim` bits of a row are read."""
+    S = sum_i (2 s_i - 1)(2 c_i - L) and X = (dim * L - S) / 2, exact.  Only the first `dim` bits of a row are read.
+    `codes` of shape [queries, dim] give int64[queries, n]: the same sum per query, the rows' bits taken apart once."""
     rows_u8 = np.asarray(rows_u8, dtype=np.uint8)
     n = rows_u8.shape[0]
     L = (1 << bits) - 1
-    centred = 2 * np.asarray(codes, dtype=np.int64)[:dim] - L
-    assert centred.size == dim
+    codes = np.asarray(codes, dtype=np.int64)
+    centred = 2 * codes[..., :dim] - L
+    assert centred.shape[-1] == dim
     at = np.arange(dim)
-    x = np.empty(n, dtype=np.int64)
+    x = np.empty(codes.shape[:-1] + (n,), dtype=np.int64)
     for r0 in range(0, n, 2048):
         block = rows_u8[r0:r0 + 2048]
         s = ((block[:, at // 8] >> (at % 8).astype(np.uint8)) & 1).astype(np.int64)
-        twice = dim * L - (2 * s - 1) @ centred
+        if centred.ndim == 1:
+            dot = (2 * s - 1) @ centred
+        else:  # a block of queries: the f64 product (BLAS) of integers whose sums stay far below 2^53 is exact
+            assert dim * L < 1 << 50
+            dot = ((2 * s - 1).astype(np.float64) @ centred.T.astype(np.float64)).T.astype(np.int64)
+        twice = dim * L - dot
         assert not np.any(twice & 1) and np.all(twice >= 0) and np.all(twice <= 2 * dim * L)
-        x[r0:r0 + 2048] = twice // 2
+        x[..., r0:r0 + 2048] = twice // 2
     return x
 
 
@@ -307,6 +314,66 @@ def scalar_scores(rows_u8, codes, dim: int, bits: int, dist, invert) -> np.ndarr
     """float32[n]: the score of every stored bit row against the codes of a scalar query (scalar_xor, then
     scalar_metric).  bits = 1 with codes (q_i > 0) is the binary score."""
     return scalar_metric(scalar_xor(rows_u8, codes, dim, bits), dim, bits, dist, invert)
+
+
+# ------------------------------------------------------------------ binary stores the test owns every bit of
+# Shared by tests/test_gpu_binary_scalar_query_matrix.py and tests/test_gpu_binary_row_shapes.py.
+def gaussian(rng, shape):
+    """Standard normal f32 values with a few +0.0 and -0.0 among them (neither is > 0: both encode as a zero bit)."""
+    x = rng.standard_normal(shape).astype(np.float32)
+    flat = x.reshape(-1)
+    if flat.size >= 8:
+        at = rng.choice(flat.size, size=max(2, flat.size // 50), replace=False)
+        flat[at[::2]] = 0.0
+        flat[at[1::2]] = -0.0
+    return x
+
+
+def bin_query_of(dim, seed=0):
+    return gaussian(np.random.default_rng(77_000 + 13 * dim + seed), (dim,))
+
+
+def bin_row_bytes(dim, kind=0):
+    """Bytes of a stored bit row; `kind`: a BitsStoreType (0: U8)."""
+    import quantization_amd as qa
+
+    return qa.EncodedVectorsBin.get_quantized_vector_size_from_params(
+        qa.VectorParameters(dim, 1, qa.DistanceType.Dot, False), qa.BitsStoreType(int(kind)))
+
+
+def bin_random_rows(n, dim, seed, kind=0):
+    """Uniform random bits in the store's own row size, pad bits zero as the encoder leaves them."""
+    rows = np.random.default_rng(seed).integers(0, 256, size=(n, bin_row_bytes(dim, kind)), dtype=np.uint8)
+    whole, rest = divmod(dim, 8)
+    if rest:
+        rows[:, whole] &= (1 << rest) - 1
+    rows[:, whole + (rest != 0):] = 0
+    return rows
+
+
+def bin_open_rows(rows, dim, dist=None, invert=False, kind=0):
+    import quantization_amd as qa
+
+    dist = qa.DistanceType.Dot if dist is None else dist
+    return qa.EncodedVectorsBin.from_storage(rows, qa.VectorParameters(dim, rows.shape[0], dist, invert),
+                                             store=qa.BitsStoreType(int(kind)))
+
+
+def bin_query_codes(query, bits: int) -> np.ndarray:
+    """The per-dimension codes of a query: (q_i > 0) for a binary query, scalar_codes for 4 and 8 bits."""
+    return (np.asarray(query) > 0).astype(np.uint32) if bits == 1 else scalar_codes(query, bits)[0]
+
+
+class BinOracle:
+    """X of every row for one (rows, query), computed once per bit width; the six metrics are taken from it."""
+
+    def __init__(self, rows, query, dim):
+        self.rows, self.query, self.dim, self._x = rows, query, dim, {}
+
+    def scores(self, bits, dist="Dot", invert=False):
+        if bits not in self._x:
+            self._x[bits] = scalar_xor(self.rows, bin_query_codes(self.query, bits), self.dim, bits)
+        return scalar_metric(self._x[bits], self.dim, bits, dist, invert)
 
 
 # ------------------------------------------------------------------ product quantizer: inputs at the encoder's edges
