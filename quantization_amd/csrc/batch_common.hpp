@@ -1,9 +1,14 @@
 // Pieces shared by the many-queries-at-once paths (csrc/u8_batch.hip; the binary matrix-core path): the
 // candidate-filter descriptor, the integer pre-filter bound, and the per-query kernels around a filtering
-// pass (pivot sample gather, pivot selection, scatter of the wave-private candidate lists, emit).
+// pass (pivot sample gather, pivot selection, scatter of the wave-private candidate lists, emit), and the host side of
+// such a pass: BatchTopkPass (scratch arena, pivots, scatter, emit, status read-back) and BatchTopkOutputs (staging of
+// host outputs, exact redo of the queries the pass could not serve).
 // Internal linkage: every translation unit that includes this gets its own copies.
 #pragma once
 #include <cmath>
+#include <cstdio>
+#include <type_traits>
+#include <vector>
 
 #include "common.hpp"
 #include "topk.hpp"
@@ -316,6 +321,201 @@ __global__ __launch_bounds__(1024) void batch_emit_wave_kernel(const unsigned lo
 
 // waves (= candidate lists) of one launch of a persistent 8-wave-per-CU matrix-core kernel
 inline uint32_t pp_waves_per_launch() { return (uint32_t)std::max(1, device_info().cu_count / 8) * 8 * 8; }
+
+// fn(std::bool_constant<LOW>): LOW is the direction of the integer pre-filter of MODE 1 / 2 - "may pass" is s <= bound
+// when the score falls with s (multiplier < 0) xor smallest-first.  The other modes have no pre-filter (LOW = false).
+template <int MODE, typename Fn>
+qamd_status with_low(float multiplier, Fn &&fn) {
+    if constexpr (MODE == 1 || MODE == 2) {
+        if ((multiplier < 0.0f) != (MODE == 2)) return fn(std::true_type{});
+    }
+    return fn(std::false_type{});
+}
+
+// QAMD_DEBUG_TOPK (tools/lib build): one line per matrix-core topk_batch call on stderr.
+inline bool batch_debug_topk() {
+    static const bool on = dev_env("QAMD_DEBUG_TOPK") != nullptr;
+    return on;
+}
+
+// The host side of one matrix-core topk_batch pass, used in a straight line:
+//     BatchTopkPass pass(n, Q, q_pad, k, largest, n_lists, wave_cap, stream);
+//     off = pass.reserve(bytes) ...             the quantizer's own scratch (sample scores, ...)
+//     pass.alloc()                              one allocation, one memset
+//     <sample GEMM>  pass.pivots(...)  <filter GEMM with pass.filter()>  pass.scatter()
+//     pass.emit(ids, scores)  pass.read_status(status)  pass.debug_line(...)
+// n_lists = 0: the filter kernel appends to the per-query lists itself (no wave-private lists, no scatter).
+struct BatchTopkPass {
+    const uint64_t n, Q, q_pad;
+    const uint32_t k;
+    const int largest;
+    const uint32_t n_lists, wave_cap;
+    const hipStream_t s;
+    // ONE stream-ordered allocation for all scratch of the call, carved up here: hipFreeAsync
+    // costs ~65 us per buffer on this runtime, and ten buffers were a third of a small batch's time.
+    StreamBuf arena;
+    size_t arena_bytes = 0, zero_bytes = 0;
+    size_t o_pivots, o_counters, o_wcounts, o_cand = 0, o_status = 0, o_bounds = 0, o_wcand = 0;
+    char *base = nullptr;
+    HostScratch hs;
+    uint32_t *status_dev = nullptr;  // [Q] per-query status, then the wave-list overflow flag
+
+    BatchTopkPass(uint64_t n_, uint64_t Q_, uint64_t q_pad_, uint32_t k_, int largest_, uint32_t n_lists_, uint32_t wave_cap_,
+                  hipStream_t s_)
+        : n(n_), Q(Q_), q_pad(q_pad_), k(k_), largest(largest_), n_lists(n_lists_), wave_cap(wave_cap_), s(s_) {
+        // zero-initialised part first (one memset): pivots, counters, wave counts
+        o_pivots = reserve(q_pad * 4);
+        o_counters = reserve(q_pad * kCounterStride * 4);
+        o_wcounts = reserve((uint64_t)n_lists * 4);
+        zero_bytes = arena_bytes;
+    }
+    size_t reserve(size_t bytes) {
+        const size_t off = arena_bytes;
+        arena_bytes += round_up(std::max<size_t>(bytes, 16), 256);
+        return off;
+    }
+    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
+    // query_bounds: the filter kernel wants [q_pad] words of scratch for its integer bounds (BatchFilter::query_bounds)
+    qamd_status alloc(bool query_bounds = false) {
+        o_cand = reserve(Q * (uint64_t)kBatchCap * 8);
+        o_status = reserve((Q + 1) * 4);
+        if (query_bounds) o_bounds = reserve(q_pad * 4);
+        o_wcand = reserve((uint64_t)n_lists * wave_cap * sizeof(uint4));
+        QAMD_TRY(arena.alloc(arena_bytes, s));
+        base = arena.as<char>();
+        QAMD_HIP(hipMemsetAsync(base, 0, zero_bytes, s));
+        // The per-query status words and the overflow flag come back through the calling thread's mapped
+        // host scratch when they fit (the kernels write host memory directly: one stream sync, no copy
+        // calls), else through one copy from the arena.
+        hs = Q + 1 <= 2048 ? host_scratch() : HostScratch{};
+        status_dev = hs.dev ? hs.dev : at<uint32_t>(o_status);
+        if (hs.host) hs.host[Q] = 0;
+        else QAMD_HIP(hipMemsetAsync(status_dev + Q, 0, 4, s));
+        return QAMD_OK;
+    }
+    float *pivot_scores() const { return at<float>(o_pivots); }
+    uint32_t *counters() const { return at<uint32_t>(o_counters); }
+    unsigned long long *candidates() const { return at<unsigned long long>(o_cand); }
+    BatchFilter filter() const {
+        BatchFilter f{};
+        f.pivot_scores = pivot_scores();
+        f.counters = counters();
+        f.candidates = candidates();
+        f.largest = largest;
+        f.n_queries = (uint32_t)Q;
+        if (o_bounds) f.query_bounds = at<int>(o_bounds);
+        if (n_lists) {
+            f.wave_cap = wave_cap;
+            f.wave_cand = at<uint4>(o_wcand);
+            f.wave_counts = at<uint32_t>(o_wcounts);
+        }
+        return f;
+    }
+    // every query's pivot: the r-th best of its `cols` sample scores (or block bests) in scores[q * pitch ...]
+    void pivots(const float *scores, uint32_t cols, uint64_t pitch, uint32_t r) {
+        hipLaunchKernelGGL(batch_pivot_kernel, dim3((unsigned)q_pad), dim3(1024), 0, s, scores, cols, pitch, r, largest, (uint32_t)Q,
+                           pivot_scores(), counters());
+    }
+    // wave-private lists -> per-query lists.  Nothing to do for a pass without wave lists.
+    void scatter() {
+        if (!n_lists) return;
+        if (Q <= 4096)
+            hipLaunchKernelGGL(wave_scatter_grouped_kernel, dim3(std::min<uint32_t>(n_lists, 128)), dim3(1024), (size_t)Q * 8, s,
+                               at<uint4>(o_wcand), at<uint32_t>(o_wcounts), wave_cap, n_lists, (uint32_t)Q, counters(), candidates(),
+                               status_dev + Q);
+        else
+            hipLaunchKernelGGL(wave_scatter_kernel, dim3(n_lists), dim3(256), 0, s, at<uint4>(o_wcand), at<uint32_t>(o_wcounts), wave_cap,
+                               counters(), candidates(), status_dev + Q);
+    }
+    qamd_status emit(uint32_t *ids_dev, float *sc_dev) {
+        if (k <= kSmallTopkMaxK)
+            hipLaunchKernelGGL(batch_emit_wave_kernel, dim3((unsigned)Q), dim3(1024), 0, s, candidates(), counters(), n, k, largest,
+                               ids_dev, sc_dev, status_dev);
+        else
+            hipLaunchKernelGGL(batch_emit_kernel, dim3((unsigned)Q), dim3(1024), 0, s, candidates(), counters(), n, k, largest, ids_dev,
+                               sc_dev, status_dev);
+        QAMD_HIP(hipGetLastError());
+        return QAMD_OK;
+    }
+    // status[q] != 0: query q must be redone exactly (its list over- or underflowed).  Synchronises the stream.
+    qamd_status read_status(std::vector<uint32_t> &status) {
+        uint32_t overflow = 0;
+        if (hs.host) {
+            QAMD_HIP(hipStreamSynchronize(s));
+            std::copy(hs.host, hs.host + Q, status.begin());
+            overflow = hs.host[Q];
+        } else {
+            std::vector<uint32_t> back(Q + 1);
+            QAMD_TRY(copy_out(back.data(), QAMD_MEM_HOST, status_dev, (Q + 1) * 4, s));  // synchronises
+            std::copy(back.begin(), back.begin() + Q, status.begin());
+            overflow = back[Q];
+        }
+        // A wave list overflowed: redo all exactly.  Only the two scatter kernels write the flag (alloc() clears it), so a
+        // pass without wave lists, which runs neither, reads 0 here: no test of n_lists is needed.
+        if (overflow) std::fill(status.begin(), status.end(), 1u);
+        return QAMD_OK;
+    }
+    void debug_line(const char *tag, uint32_t r, const char *kernel_name, const char *tail, const std::vector<uint32_t> &status) {
+        if (!batch_debug_topk()) return;
+        std::vector<uint32_t> cnt(q_pad * kCounterStride);
+        (void)hipMemcpy(cnt.data(), counters(), cnt.size() * 4, hipMemcpyDeviceToHost);
+        uint32_t mx = 0, mn = ~0u, redo = 0;
+        uint64_t sum = 0;
+        for (uint64_t q = 0; q < Q; q++) {
+            const uint32_t c = cnt[q * kCounterStride];
+            mx = std::max(mx, c);
+            mn = std::min(mn, c);
+            sum += c;
+            redo += status[q] != 0;
+        }
+        fprintf(stderr, "%s Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, filter %s, %u queries redone%s\n", tag,
+                (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx, kernel_name, redo, tail);
+    }
+};
+
+// The outputs of a topk_batch whose matrix-core pass may leave queries to an exact single-query path: host outputs are
+// staged in device memory, status[q] != 0 marks the queries to redo (all of them until a pass says otherwise).
+struct BatchTopkOutputs {
+    StreamBuf ids_tmp, sc_tmp;
+    uint32_t *ids_dev = nullptr;  // [Q][k], device memory: the caller's own, or the staging copy
+    float *sc_dev = nullptr;
+    std::vector<uint32_t> status;
+    uint64_t Q = 0;
+    uint32_t k = 0;
+    uint32_t *out_ids = nullptr;
+    float *out_scores = nullptr;
+    qamd_mem out_mem = QAMD_MEM_DEVICE;
+    hipStream_t s = nullptr;
+
+    qamd_status begin(uint64_t Q_, uint32_t k_, uint32_t *out_ids_, float *out_scores_, qamd_mem out_mem_, hipStream_t s_) {
+        Q = Q_, k = k_, out_ids = out_ids_, out_scores = out_scores_, out_mem = out_mem_, s = s_;
+        ids_dev = out_ids;
+        sc_dev = out_scores;
+        if (out_mem == QAMD_MEM_HOST) {
+            QAMD_TRY(ids_tmp.alloc(Q * k * 4, s));
+            QAMD_TRY(sc_tmp.alloc(Q * k * 4, s));
+            ids_dev = ids_tmp.as<uint32_t>();
+            sc_dev = sc_tmp.as<float>();
+        }
+        status.assign(Q, 1);
+        return QAMD_OK;
+    }
+    // redo(q, ids_dev, scores_dev): the quantizer's exact top-k of query q into device memory
+    template <class Redo>
+    qamd_status finish(Redo &&redo) {
+        for (uint64_t q = 0; q < Q; q++) {
+            if (!status[q]) continue;
+            QAMD_TRY(redo(q, ids_dev + q * k, sc_dev + q * k));
+        }
+        if (out_mem == QAMD_MEM_HOST) {
+            QAMD_TRY(copy_out(out_ids, QAMD_MEM_HOST, ids_dev, Q * k * 4, s));
+            QAMD_TRY(copy_out(out_scores, QAMD_MEM_HOST, sc_dev, Q * k * 4, s));
+        } else {
+            QAMD_HIP(hipStreamSynchronize(s));  // scratch buffers are released on return
+        }
+        return QAMD_OK;
+    }
+};
 
 }  // namespace
 }  // namespace qamd

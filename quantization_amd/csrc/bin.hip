@@ -25,6 +25,7 @@
 #include <mutex>
 
 #include "batch_common.hpp"
+#include "bin_batch_route.hpp"
 #include "common.hpp"
 #include "lists.hpp"
 #include "multi_reduce.hpp"
@@ -918,7 +919,7 @@ qamd_status score_ids_any(const qamd_bin *h, const uint32_t *qbits, const uint32
     });
 }
 
-bool fused_capable(const qamd_bin *h) { return h->ds % 16 == 0 && h->ds / 16 <= 64; }
+bool fused_capable(const qamd_bin *h) { return bin_fused_rows(h->ds); }
 
 // The scan of a query's planes (1: its bit row), bin_scan_kernel's mapping per row length; the 8-lane rows of a scalar
 // query scan half the rows per wave, to leave the registers their 16-row tile takes to the planes of a piece.
@@ -1933,7 +1934,6 @@ __global__ __launch_bounds__(512) void bin_gemm_rs_kernel(const uint8_t *__restr
 // (bin_frag4_kernel: per 16 queries and 128-bit k-step one 1 KiB piece, lane (i, g) = bits [128 s + 32 g, +32) of query
 // i).  Same epilogue arithmetic as bin_gemm_rs_kernel: the scores are the reference's bit for bit.  Rows of 512 / 768 / 1024 /
 // 1536 bits.
-constexpr uint64_t kQs4Slice = 2048, kQs4MinQueries = 129;  // queries per launch of bin_gemm_qs4_kernel; from where it is used
 typedef int v8i_t __attribute__((ext_vector_type(8)));
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 
@@ -2283,14 +2283,7 @@ __global__ __launch_bounds__(512) void bin_gemm_qs4_kernel(const uint8_t *__rest
 // loads, every line fetched once); k-step s multiplies dword NS g + s of the row with the same dword of the query, which is
 // where the staging copy puts it (any pairing of K positions is the same dot product).  Arithmetic, bounds and candidate
 // lists are bin_gemm_qs4_kernel's.
-constexpr uint32_t kRs4MinQueries = 12;  // (the int8 matrix-core form; the fp4 form takes 3 and 5+ queries)
-constexpr uint32_t kRs4MaxPasses = 4;  // (measured: profiles/r04_bin_batch.txt; four passes tie with the query-streaming form)
-inline uint32_t rs4_max_queries(uint64_t ds) {  // whole 32-query tile pairs whose nibble image + bounds fit the CU's LDS
-    return (uint32_t)((160 * 1024 - 1024) / (ds * 4 + 4) / 32 * 32);
-}
-// Waves per workgroup: 12 (three per SIMD: 166 registers at NS = 8) where the registers allow, else 8 - a third wave covers
-// more of the other two's vector-ALU phases with MFMAs.
-constexpr int rs4_waves(int ns) { return ns <= 8 ? 12 : 8; }
+// (its batch sizes, passes and waves per workgroup: bin_batch_route.hpp)
 template <int MODE, bool LOW, int NS>  // MODE 1 / 2: filter for the largest / smallest scores; NS = k-steps = ds / 16
 __global__ __launch_bounds__(64 * rs4_waves(NS)) void bin_gemm_rs4_kernel(const uint8_t *__restrict__ rows, const uint4 *__restrict__ qfrag,
                                                           const float *__restrict__ q_offsets, const int *__restrict__ bq_all,
@@ -2450,173 +2443,213 @@ __global__ __launch_bounds__(256) void bin_gather_rows_kernel(const uint4 *__res
 
 namespace {
 
-// Query fragments per workgroup tile that fit in LDS for this row length (0: none).
-inline int bin_mfma_frags(uint64_t ds, uint64_t n_queries = ~0ull) {
-    const uint64_t nkb = ds / 16;
-    if (n_queries > 32 && (size_t)64 * (nkb * 128 + 16) + 2048 <= 160 * 1024) return 2;
-    if ((size_t)32 * (nkb * 128 + 16) + 2048 <= 160 * 1024) return 1;
-    return 0;
+// The developer switches of the batch route, read once per process (tools/lib build; all-default in the product library).
+const BinBatchSwitches &bin_batch_switches() {
+    static const BinBatchSwitches switches = [] {
+        auto number = [](const char *name) {
+            const char *e = dev_env(name);
+            return BinBatchSwitches::Number{e != nullptr, e ? (uint64_t)atoll(e) : 0};
+        };
+        auto is_off = [](const char *name) {
+            const char *e = dev_env(name);
+            return e && e[0] == '0';
+        };
+        BinBatchSwitches d;
+        d.fp4 = !is_off("QAMD_BIN4");
+        d.fp4_min = number("QAMD_BIN4_MIN");
+        d.rs4 = !is_off("QAMD_BIN_RS4");
+        if (const char *e = dev_env("QAMD_BIN_RS4_PASSES")) d.rs4_passes = {true, (uint32_t)atoi(e)};
+        d.mfma_min = number("QAMD_BIN_MFMA_MIN");
+        d.scalar_mfma_min = dev_env_u64("QAMD_BIN_SCALAR_MFMA_MIN", 0);
+        return d;
+    }();
+    return switches;
 }
 
-template <int MODE>
-qamd_status launch_bin_gemm(const qamd_bin *h, const qamd_bin_query_batch *b, const uint8_t *rows, uint64_t n_rows, uint32_t q0,
-                            int mi, float *out, uint64_t out_pitch, const BatchFilter &filt, hipStream_t s) {
-    const bool zx = (h->vp.distance_type == QAMD_DOT) != (h->vp.invert != 0);
-    const bool low = MODE != 0 && (!zx) != (MODE == 2);  // multiplier = zx ? +4 : -4
-    const size_t lds = (size_t)32 * mi * ((h->ds / 16) * 128 + 16) + 3 * 64 * 4 + 64;
-    const uint32_t grid = (uint32_t)std::max(1, device_info().cu_count / 8) * 8;
+// The route (bin_batch_route.hpp) of score_batch (k = 0) or topk_batch(k) for this store and batch.
+BinBatchRoute bin_route(const qamd_bin *h, const qamd_bin_query_batch *b, uint32_t k) {
+    BinBatchInputs in;
+    in.ds = h->ds;
+    in.code_bits = h->code_bits;
+    in.count = h->count;
+    in.n_queries = b->n_queries;
+    in.qbits = b->qbits;
+    in.k = k;
+    in.waves_per_launch = pp_waves_per_launch();
+    return bin_batch_route(in, bin_batch_switches());
+}
+
+inline bool bin_zx(const qamd_bin *h) { return (h->vp.distance_type == QAMD_DOT) != (h->vp.invert != 0); }  // multiplier = zx ? +4 : -4
+inline uint32_t bin_persistent_grid() { return (uint32_t)std::max(1, device_info().cu_count / 8) * 8; }
+
+// One launch of bin_gemm_rs_kernel: rows [0, n_rows) against the tile of 32 * mi queries that starts at query q0.
+// MODE 0: scores out; 1 / 2: filter for the largest / smallest.
+struct BinRsCall {
+    const qamd_bin *h;
+    const qamd_bin_query_batch *b;
+    const uint8_t *rows;
+    uint64_t n_rows;
+    uint32_t q0;
+    int mi;
+    float *out;
+    uint64_t out_pitch;
+    BatchFilter filt;
+    hipStream_t s;
+};
+template <int MODE, bool LOW, int MI, bool CODES>
+qamd_status launch_bin_rs_as(const BinRsCall &c) {
+    const qamd_bin *h = c.h;
+    const qamd_bin_query_batch *b = c.b;
+    const size_t lds = (size_t)32 * c.mi * ((h->ds / 16) * 128 + 16) + 3 * 64 * 4 + 64;
+    QAMD_LDS_OPT_IN((&bin_gemm_rs_kernel<MODE, LOW, MI, CODES>), 160 * 1024);
     // a binary batch: its bit rows (the one plane); a scalar batch: its code image at the kernel's own LDS pitch, and
     // dim * L for dim (never its planes, never as bits)
-#define QAMD_BIN_GEMM(M_, LOW_, MI_, CODES_)                                                                                \
-    do {                                                                                                                   \
-        QAMD_LDS_OPT_IN((&bin_gemm_rs_kernel<M_, LOW_, MI_, CODES_>), 160 * 1024);                                          \
-        hipLaunchKernelGGL((bin_gemm_rs_kernel<M_, LOW_, MI_, CODES_>), dim3(grid), dim3(512), lds, s, rows, (uint32_t)h->ds, \
-                           CODES_ ? b->codes.as<uint8_t>() : b->planes.as<uint8_t>(),                                      \
-                           (uint32_t)(CODES_ ? b->code_pitch : b->p_stride), metric_dim(h, b->qbits), zx ? 1 : 0,          \
-                           (uint32_t)n_rows, (uint32_t)b->n_queries, q0, out, out_pitch, filt);                            \
-    } while (0)
-    constexpr int M = MODE == 0 ? 1 : MODE;
-    if (b->qbits != 1) {
-        if (b->code_pitch != (h->ds / 16) * 128 + 16) return fail(QAMD_ERR_ARGUMENTS, "the batch's code image has another pitch");
-        // The filter runs on 32-query tiles only (bin_topk_batch_mfma): the 64-query filter forms need 20 bytes of scratch
-        // per lane at 256 registers - the binary ones have since they were written - and are not instantiated for codes.
-        if (MODE != 0 && mi != 1) return fail(QAMD_ERR_ARGUMENTS, "scalar batches filter on 32-query tiles");
-        if (MODE == 0) {
-            if (mi == 2) QAMD_BIN_GEMM(0, false, 2, true);
-            else QAMD_BIN_GEMM(0, false, 1, true);
-        } else if (low) {
-            QAMD_BIN_GEMM(M, true, 1, true);
-        } else {
-            QAMD_BIN_GEMM(M, false, 1, true);
-        }
-    } else if (MODE == 0) {
-        if (mi == 2) QAMD_BIN_GEMM(0, false, 2, false);
-        else QAMD_BIN_GEMM(0, false, 1, false);
-    } else if (low) {
-        if (mi == 2) QAMD_BIN_GEMM(M, true, 2, false);
-        else QAMD_BIN_GEMM(M, true, 1, false);
-    } else {
-        if (mi == 2) QAMD_BIN_GEMM(M, false, 2, false);
-        else QAMD_BIN_GEMM(M, false, 1, false);
-    }
-#undef QAMD_BIN_GEMM
+    hipLaunchKernelGGL((bin_gemm_rs_kernel<MODE, LOW, MI, CODES>), dim3(bin_persistent_grid()), dim3(512), lds, c.s, c.rows,
+                       (uint32_t)h->ds, CODES ? b->codes.as<uint8_t>() : b->planes.as<uint8_t>(),
+                       (uint32_t)(CODES ? b->code_pitch : b->p_stride), metric_dim(h, b->qbits), bin_zx(h) ? 1 : 0, (uint32_t)c.n_rows,
+                       (uint32_t)b->n_queries, c.q0, c.out, c.out_pitch, c.filt);
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
 }
-
-// Which filter the matrix-core top-k runs for this store and batch: the one place that decides it (bin_topk_batch_mfma
-// launches what this says, qamd_bin_batch_kernel names it).  Scalar batches take the int8 kernel only: centred codes are
-// not exact in E2M1.
-struct BinFilterPlan {
-    bool rs4 = false, qs4 = false;  // neither: bin_gemm_rs_kernel
-    uint32_t rs4_passes = 0, rs4_per_pass = 0;
-};
-BinFilterPlan bin_filter_plan(const qamd_bin *h, const qamd_bin_query_batch *b) {
-    BinFilterPlan p;
-    if (b->qbits != 1) return p;
-    const uint64_t Q = b->n_queries;
-    // rows of 512 / 1024 / 2048 bits, enough queries: the FP4 query-streaming form (QAMD_BIN4=0 / QAMD_BIN4_MIN: developer A/B)
-    static const char *e4 = dev_env("QAMD_BIN4"), *e4min = dev_env("QAMD_BIN4_MIN");
-    static const char *ers4 = dev_env("QAMD_BIN_RS4");  // developer A/B: 0 = without the row-streaming fp4 form
-    const bool fp4_shape = (h->ds == 64 || h->ds == 96 || h->ds == 128 || h->ds == 192) && !(e4 && e4[0] == '0');
-    // the whole batch's nibble image in LDS: the row-streaming fp4 form (one pass, no barriers); larger batches: query-streaming
-    // A batch of up to kRs4MaxPasses LDS images goes through that form in as many passes over the rows, the queries spread evenly
-    // (50M x 1024 bits: 289 queries = two passes of 160: 6.4 ms against the query-streaming form's 10.1; 576 = 2 x 288: 10.4 / 15.7)
-    static const char *ers4p = dev_env("QAMD_BIN_RS4_PASSES");  // developer A/B: the most passes the row-streaming form may take
-    const uint32_t rs4_cap = rs4_max_queries(h->ds), rs4_most = ers4p ? (uint32_t)atoi(ers4p) : kRs4MaxPasses;
-    p.rs4_passes = rs4_cap ? (uint32_t)((round_up(Q, 32) + rs4_cap - 1) / rs4_cap) : 0u;
-    p.rs4 = fp4_shape && !(ers4 && ers4[0] == '0') && p.rs4_passes >= 1 && p.rs4_passes <= rs4_most;
-    p.rs4_per_pass = p.rs4 ? (uint32_t)round_up((Q + p.rs4_passes - 1) / p.rs4_passes, 32) : 0u;  // queries per pass (whole tile pairs)
-    p.qs4 = p.rs4 || (fp4_shape && Q >= (e4min ? (uint64_t)atoll(e4min) : kQs4MinQueries));
-    return p;
+template <int MODE>
+qamd_status launch_bin_rs(const BinRsCall &c) {
+    const bool codes = c.b->qbits != 1;
+    if (codes) {
+        if (c.b->code_pitch != (c.h->ds / 16) * 128 + 16) return fail(QAMD_ERR_ARGUMENTS, "the batch's code image has another pitch");
+        // The filter runs on 32-query tiles only (bin_batch_route): the 64-query filter forms need 20 bytes of scratch
+        // per lane at 256 registers - the binary ones have since they were written - and are not instantiated for codes.
+        if (MODE != 0 && c.mi != 1) return fail(QAMD_ERR_ARGUMENTS, "scalar batches filter on 32-query tiles");
+    }
+    return with_low<MODE>(bin_zx(c.h) ? 4.0f : -4.0f, [&](auto low) -> qamd_status {
+        constexpr bool LOW = decltype(low)::value;
+        if (codes) {
+            if constexpr (MODE == 0) {
+                if (c.mi == 2) return launch_bin_rs_as<MODE, LOW, 2, true>(c);
+            }
+            return launch_bin_rs_as<MODE, LOW, 1, true>(c);
+        }
+        if (c.mi == 2) return launch_bin_rs_as<MODE, LOW, 2, false>(c);
+        return launch_bin_rs_as<MODE, LOW, 1, false>(c);
+    });
 }
 
-// The batch on the matrix cores: per-query pivot from a cached row sample, one filtering pass per query tile
-// (32 or 64 queries), candidates scattered to per-query lists, one emit.  status[q] != 0: query q must be redone
+// One launch of an FP4 filter kernel: the rows of the store against queries [q_base, q_base + nq) of the batch's nibble
+// image (bin_frag4_kernel: fragments, offsets and integer bounds of every query).  MODE 1 / 2: largest / smallest.
+struct BinFp4Call {
+    const qamd_bin *h;
+    const uint4 *frag;
+    const float *q_off;
+    const int *bq;
+    uint64_t q_base;
+    uint32_t nq;
+    BatchFilter filt;
+    hipStream_t s;
+};
+template <int MODE, bool LOW, int NS>
+qamd_status launch_bin_rs4_as(const BinFp4Call &c) {
+    const qamd_bin *h = c.h;
+    const uint32_t n_tiles = (uint32_t)(round_up(c.nq, 32) / 16);
+    const size_t lds = (size_t)n_tiles * h->ds * 64 + (size_t)n_tiles * 64 + 64;
+    QAMD_LDS_OPT_IN((&bin_gemm_rs4_kernel<MODE, LOW, NS>), 160 * 1024);
+    hipLaunchKernelGGL((bin_gemm_rs4_kernel<MODE, LOW, NS>), dim3(bin_persistent_grid()), dim3(64 * rs4_waves(NS)), lds, c.s,
+                       h->rows.as<uint8_t>(), c.frag + (c.q_base / 16) * NS * 64, c.q_off + c.q_base, c.bq + c.q_base, bin_zx(h) ? 1 : 0,
+                       (uint32_t)h->count, n_tiles, c.filt);
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
+template <int MODE>
+qamd_status launch_bin_rs4(const BinBatchRoute &rt, const BinFp4Call &c) {
+    return with_low<MODE>(bin_zx(c.h) ? 4.0f : -4.0f, [&](auto low) -> qamd_status {
+        constexpr bool LOW = decltype(low)::value;
+        switch (rt.rs4_ns) {
+            case 4: return launch_bin_rs4_as<MODE, LOW, 4>(c);
+            case 6: return launch_bin_rs4_as<MODE, LOW, 6>(c);
+            case 8: return launch_bin_rs4_as<MODE, LOW, 8>(c);
+            case 12: return launch_bin_rs4_as<MODE, LOW, 12>(c);
+        }
+        return fail(QAMD_ERR_ARGUMENTS, "no %s for rows of %d k-steps", rt.name, rt.rs4_ns);
+    });
+}
+template <int MODE, bool LOW, int IT, int JT>
+qamd_status launch_bin_qs4_as(const BinFp4Call &c) {
+    const qamd_bin *h = c.h;
+    const size_t qs_rows = 16 * JT;
+    const size_t lds = 2 * qs_rows * round_up(h->ds * 4, 256) + 4 * qs_rows * 4 + 64 + kQs4Slice * 4;
+    QAMD_LDS_OPT_IN((&bin_gemm_qs4_kernel<MODE, LOW, IT, JT>), 160 * 1024);
+    hipLaunchKernelGGL((bin_gemm_qs4_kernel<MODE, LOW, IT, JT>), dim3(bin_persistent_grid()), dim3(512), lds, c.s, h->rows.as<uint8_t>(),
+                       (uint32_t)h->ds, c.frag + (c.q_base / 16) * (h->ds / 16) * 64, c.q_off + c.q_base, c.bq + c.q_base,
+                       bin_zx(h) ? 1 : 0, (uint32_t)h->count, c.nq, c.filt);
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
+template <int MODE>
+qamd_status launch_bin_qs4(const BinBatchRoute &rt, const BinFp4Call &c) {
+    return with_low<MODE>(bin_zx(c.h) ? 4.0f : -4.0f, [&](auto low) -> qamd_status {
+        constexpr bool LOW = decltype(low)::value;
+        switch (rt.qs4_it * 10 + rt.qs4_jt) {
+            case 16: return launch_bin_qs4_as<MODE, LOW, 1, 6>(c);
+            case 18: return launch_bin_qs4_as<MODE, LOW, 1, 8>(c);
+            case 26: return launch_bin_qs4_as<MODE, LOW, 2, 6>(c);
+            case 28: return launch_bin_qs4_as<MODE, LOW, 2, 8>(c);
+            case 46: return launch_bin_qs4_as<MODE, LOW, 4, 6>(c);
+            case 48: return launch_bin_qs4_as<MODE, LOW, 4, 8>(c);
+        }
+        return fail(QAMD_ERR_ARGUMENTS, "no %s of shape %d x %d", rt.name, rt.qs4_it, rt.qs4_jt);
+    });
+}
+
+// The pivot sample of a store, gathered once per handle: every call uses a prefix (see sample_store in u8_batch.hip).
+qamd_status bin_sample_rows(const qamd_bin *h, uint32_t rows_all, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(h->sample_mu);
+    if (h->sample_count < rows_all) {
+        DevBuf c;
+        QAMD_TRY(c.alloc((uint64_t)(rows_all + 512) * h->ds));
+        hipLaunchKernelGGL(bin_gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->rows.as<uint4>(),
+                           (uint32_t)(h->ds / 16), h->count, rows_all, 512u, c.as<uint4>());
+        QAMD_HIP(hipGetLastError());
+        QAMD_HIP(hipStreamSynchronize(s));
+        h->sample_rows = std::move(c);
+        h->sample_count = rows_all;
+    }
+    return QAMD_OK;
+}
+
+// The batch on the matrix cores: per-query pivot from a cached row sample, the filtering pass of the route (`rt`, of
+// this store, batch and k), candidates scattered to per-query lists, one emit.  status[q] != 0: query q must be redone
 // by the exact path (its list over- or underflowed: heavy ties, an unlucky sample).
-qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b, uint32_t k, int largest, uint32_t *ids_dev,
-                                float *sc_dev, std::vector<uint32_t> &status, hipStream_t s) {
+qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b, const BinBatchRoute &rt, uint32_t k, int largest,
+                                uint32_t *ids_dev, float *sc_dev, std::vector<uint32_t> &status, hipStream_t s) {
     const uint64_t Q = b->n_queries, n = h->count;
-    const int mi = b->qbits != 1 ? 1 : bin_mfma_frags(h->ds, Q);  // (scalar batches: 32-query tiles, launch_bin_gemm)
-    const uint32_t TQ = 32u * (uint32_t)mi;
+    const uint32_t TQ = 32u * (uint32_t)rt.mi;
     const uint64_t q_pad = round_up(Q, 64);
-    const double want = std::max<double>(Q <= 128 ? 1024.0 : 512.0, 3.0 * k);
-    const double s_min = n < (1u << 20) ? 2048.0 : (double)kTopkSample;
-    const double s_mem_cap = std::max<double>(s_min, std::floor((double)(6ull << 30) / (4.0 * (double)Q) / 256.0) * 256.0);
-    const uint32_t S = (uint32_t)std::min<double>(std::min<double>(524288.0, s_mem_cap),
-                                                  std::max<double>(s_min, round_up((uint64_t)(8.0 * (double)n / want), 256)));
-    const double target = std::max<double>(want, 8.0 * (double)n / (double)S);
-    const uint32_t r = (uint32_t)std::ceil((double)S * target / (double)n);
+    const BatchSamplePlan plan = batch_sample_plan(n, Q, k);
+    const uint32_t S = plan.S, r = plan.r;
     if (r > 64) {  // (tiny stores are not routed here)
         std::fill(status.begin(), status.end(), 1u);
         return QAMD_OK;
     }
-    // the pivot sample of the store: gathered once per handle, every call uses a prefix (see u8_batch.hip)
-    const uint32_t rows_all = (uint32_t)std::min<double>(524288.0, std::max<double>(s_min, (double)round_up((uint64_t)(8.0 * (double)n / 512.0), 256)));
-    const uint32_t rc = (uint32_t)(h->ds / 16);
-    {
-        std::lock_guard<std::mutex> lk(h->sample_mu);
-        if (h->sample_count < rows_all) {
-            DevBuf c;
-            QAMD_TRY(c.alloc((uint64_t)(rows_all + 512) * h->ds));
-            hipLaunchKernelGGL(bin_gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->rows.as<uint4>(), rc, n,
-                               rows_all, 512u, c.as<uint4>());
-            QAMD_HIP(hipGetLastError());
-            QAMD_HIP(hipStreamSynchronize(s));
-            h->sample_rows = std::move(c);
-            h->sample_count = rows_all;
-        }
-    }
-    const BinFilterPlan plan = bin_filter_plan(h, b);
-    const bool rs4 = plan.rs4, qs4 = plan.qs4;
-    const uint32_t rs4_passes = plan.rs4_passes, rs4_per_pass = plan.rs4_per_pass;
-    const uint32_t rs4_lists = pp_waves_per_launch() / 8 * (uint32_t)rs4_waves((int)(h->ds / 16));  // one list per wave of a launch
-    const uint32_t n_lists = rs4 ? rs4_passes * rs4_lists
-                                 : pp_waves_per_launch() * (qs4 ? (uint32_t)((Q + kQs4Slice - 1) / kQs4Slice) : 1u);
-    const double per_wave = 2.0 * target * (double)std::min<uint64_t>(Q, qs4 ? kQs4Slice : TQ) / (double)pp_waves_per_launch();
+    QAMD_TRY(bin_sample_rows(h, plan.rows_all, s));
+    const double per_wave = 2.0 * plan.target * (double)rt.per_wave_queries / (double)pp_waves_per_launch();
     // (at least 1024 slots: queries of one batch can be near-duplicates, and then a passing row appends to every
     // query's list at once - 64 entries in one wave's list per such row)
     const uint32_t wave_cap = (uint32_t)std::min<double>(1u << 20, std::max<double>(1024.0, 16.0 * per_wave));
-    size_t arena_bytes = 0;
-    auto reserve = [&](size_t bytes) {
-        const size_t off = arena_bytes;
-        arena_bytes += round_up(std::max<size_t>(bytes, 16), 256);
-        return off;
-    };
-    const size_t o_pivots = reserve(q_pad * 4), o_counters = reserve(q_pad * kCounterStride * 4), o_wcounts = reserve((size_t)n_lists * 4);
-    const size_t zero_bytes = arena_bytes;
-    const size_t o_scores = reserve(Q * (uint64_t)S * 4), o_cand = reserve(Q * (uint64_t)kBatchCap * 8), o_status = reserve((Q + 1) * 4),
-                 o_wcand = reserve((uint64_t)n_lists * wave_cap * sizeof(uint4));
-    StreamBuf arena;
-    QAMD_TRY(arena.alloc(arena_bytes, s));
-    char *base = arena.as<char>();
-    QAMD_HIP(hipMemsetAsync(base, 0, zero_bytes, s));
-    float *pivots = reinterpret_cast<float *>(base + o_pivots);
-    uint32_t *counters = reinterpret_cast<uint32_t *>(base + o_counters);
-    uint32_t *wave_counts = reinterpret_cast<uint32_t *>(base + o_wcounts);
-    float *s_scores = reinterpret_cast<float *>(base + o_scores);
-    unsigned long long *cand = reinterpret_cast<unsigned long long *>(base + o_cand);
-    uint4 *wave_cand = reinterpret_cast<uint4 *>(base + o_wcand);
-    const HostScratch hs = Q + 1 <= 2048 ? host_scratch() : HostScratch{};
-    uint32_t *status_dev = hs.dev ? hs.dev : reinterpret_cast<uint32_t *>(base + o_status);
-    uint32_t *overflow_dev = status_dev + Q;
-    if (hs.host) hs.host[Q] = 0;
-    else QAMD_HIP(hipMemsetAsync(overflow_dev, 0, 4, s));
+    BatchTopkPass pass(n, Q, q_pad, k, largest, rt.n_lists, wave_cap, s);
+    const size_t o_scores = pass.reserve(Q * (uint64_t)S * 4);
+    QAMD_TRY(pass.alloc());
     // sample scores of every query, then every query's pivot
+    float *s_scores = pass.at<float>(o_scores);
     for (uint32_t q0 = 0; q0 < Q; q0 += TQ)
-        QAMD_TRY(launch_bin_gemm<0>(h, b, h->sample_rows.as<uint8_t>(), S, q0, mi, s_scores, S, BatchFilter{}, s));
-    hipLaunchKernelGGL(batch_pivot_kernel, dim3((unsigned)q_pad), dim3(1024), 0, s, s_scores, S, (uint64_t)S, r, largest, (uint32_t)Q,
-                       pivots, counters);
-    BatchFilter f{};
-    f.pivot_scores = pivots;
-    f.counters = counters;
-    f.candidates = cand;
-    f.largest = largest;
-    f.wave_cap = wave_cap;
-    f.wave_cand = wave_cand;
-    f.wave_counts = wave_counts;
-    if (qs4) {  // ONE pass over the rows for up to 2048 queries (bin_gemm_qs4_kernel), then one scatter
-        const bool zx = (h->vp.distance_type == QAMD_DOT) != (h->vp.invert != 0);
+        QAMD_TRY(launch_bin_rs<0>({h, b, h->sample_rows.as<uint8_t>(), S, q0, rt.mi, s_scores, S, BatchFilter{}, s}));
+    pass.pivots(s_scores, S, S, r);
+    const BatchFilter f = pass.filter();
+    if (rt.kernel == BinBatchKernel::Rs) {
+        for (uint32_t q0 = 0; q0 < Q; q0 += TQ) {  // one pass over the rows per query tile; its lists are scattered right away
+            const BinRsCall c{h, b, h->rows.as<uint8_t>(), n, q0, rt.mi, nullptr, 0, f, s};
+            QAMD_TRY(largest ? launch_bin_rs<1>(c) : launch_bin_rs<2>(c));
+            pass.scatter();
+        }
+    } else {  // the FP4 forms: the batch's nibble image once, a launch per pass or slice, then one scatter
+        const bool zx = bin_zx(h);
         const bool low = (!zx) != (largest == 0);  // multiplier = zx ? +4 : -4; MODE 2 (smallest) flips
         const uint32_t nsteps = (uint32_t)(h->ds / 16);
         StreamBuf prep;
@@ -2628,141 +2661,28 @@ qamd_status bin_topk_batch_mfma(const qamd_bin *h, const qamd_bin_query_batch *b
         const unsigned pgrid = (unsigned)std::max<uint64_t>((q_pad + 255) / 256, std::min<uint64_t>(2048, (frag_bytes / 16 + 255) / 256));
         if (low)
             hipLaunchKernelGGL(bin_frag4_kernel<true>, dim3(pgrid), dim3(256), 0, s, b->planes.as<uint8_t>(), (uint32_t)b->p_stride, (uint32_t)Q,
-                               (uint32_t)q_pad, nsteps, metric_dim(h, 1), zx ? 1 : 0, largest, pivots, frag, q_off, bq);
+                               (uint32_t)q_pad, nsteps, metric_dim(h, 1), zx ? 1 : 0, largest, pass.pivot_scores(), frag, q_off, bq);
         else
             hipLaunchKernelGGL(bin_frag4_kernel<false>, dim3(pgrid), dim3(256), 0, s, b->planes.as<uint8_t>(), (uint32_t)b->p_stride, (uint32_t)Q,
-                               (uint32_t)q_pad, nsteps, metric_dim(h, 1), zx ? 1 : 0, largest, pivots, frag, q_off, bq);
-        const size_t qs_rows = h->ds > 128 ? 96 : 128;
-        const size_t lds = 2 * qs_rows * round_up(h->ds * 4, 256) + 4 * qs_rows * 4 + 64 + kQs4Slice * 4;
-        const uint32_t grid = (uint32_t)std::max(1, device_info().cu_count / 8) * 8;
-        if (rs4)
-        for (uint32_t pass = 0; pass < rs4_passes; pass++) {
-            const uint64_t q_base = (uint64_t)pass * rs4_per_pass;
-            if (q_base >= Q) break;
-            const uint32_t nq = (uint32_t)std::min<uint64_t>(rs4_per_pass, Q - q_base);
-            const uint32_t n_tiles = (uint32_t)(round_up(nq, 32) / 16);
-            const size_t lds4 = (size_t)n_tiles * h->ds * 64 + (size_t)n_tiles * 64 + 64;
-            BatchFilter fs = f;
-            fs.pivot_scores = pivots + q_base;
-            fs.query_base = (uint32_t)q_base;
-            fs.wave_base = pass * rs4_lists;
-#define QAMD_RS4_NS(M_, LOW_, NS_)                                                                                          \
-    do {                                                                                                                   \
-        QAMD_LDS_OPT_IN((&bin_gemm_rs4_kernel<M_, LOW_, NS_>), 160 * 1024);                                                 \
-        hipLaunchKernelGGL((bin_gemm_rs4_kernel<M_, LOW_, NS_>), dim3(grid), dim3(64 * rs4_waves(NS_)), lds4, s, h->rows.as<uint8_t>(), \
-                           frag + (q_base / 16) * nsteps * 64, q_off + q_base, bq + q_base, zx ? 1 : 0, (uint32_t)n, n_tiles, fs); \
-    } while (0)
-#define QAMD_RS4(M_, LOW_)                                                                                                  \
-    do {                                                                                                                   \
-        switch (h->ds) {                                                                                                   \
-            case 64: QAMD_RS4_NS(M_, LOW_, 4); break;                                                                      \
-            case 96: QAMD_RS4_NS(M_, LOW_, 6); break;                                                                      \
-            case 128: QAMD_RS4_NS(M_, LOW_, 8); break;                                                                     \
-            default: QAMD_RS4_NS(M_, LOW_, 12); break;                                                                     \
-        }                                                                                                                  \
-    } while (0)
-            if (largest) {
-                if (low) QAMD_RS4(1, true);
-                else QAMD_RS4(1, false);
-            } else {
-                if (low) QAMD_RS4(2, true);
-                else QAMD_RS4(2, false);
-            }
-#undef QAMD_RS4
-#undef QAMD_RS4_NS
-            QAMD_HIP(hipGetLastError());
-        } else
-        for (uint64_t q_base = 0; q_base < Q; q_base += kQs4Slice) {
-            const uint32_t nq = (uint32_t)std::min<uint64_t>(kQs4Slice, Q - q_base);
-            BatchFilter fs = f;
-            fs.pivot_scores = pivots + q_base;
-            fs.query_base = (uint32_t)q_base;
-            fs.wave_base = (uint32_t)(q_base / kQs4Slice) * pp_waves_per_launch();
-#define QAMD_QS4_JT(M_, LOW_, IT_, JT_)                                                                                     \
-    do {                                                                                                                   \
-        QAMD_LDS_OPT_IN((&bin_gemm_qs4_kernel<M_, LOW_, IT_, JT_>), 160 * 1024); \
-        hipLaunchKernelGGL((bin_gemm_qs4_kernel<M_, LOW_, IT_, JT_>), dim3(grid), dim3(512), lds, s, h->rows.as<uint8_t>(), \
-                           (uint32_t)h->ds, frag + (q_base / 16) * nsteps * 64, q_off + q_base, bq + q_base, zx ? 1 : 0,   \
-                           (uint32_t)n, nq, fs);                                                                           \
-    } while (0)
-#define QAMD_QS4_IT(M_, LOW_, IT_)                                                                                          \
-    do {                                                                                                                   \
-        if (h->ds > 128) QAMD_QS4_JT(M_, LOW_, IT_, 6);                                                                    \
-        else QAMD_QS4_JT(M_, LOW_, IT_, 8);                                                                                \
-    } while (0)
-#define QAMD_QS4(M_, LOW_)                                                                                                  \
-    do {                                                                                                                   \
-        if (Q <= 128) QAMD_QS4_IT(M_, LOW_, 1);                                                                            \
-        else if (Q <= 256) QAMD_QS4_IT(M_, LOW_, 2);                                                                       \
-        else QAMD_QS4_IT(M_, LOW_, 4);                                                                                     \
-    } while (0)
-            if (largest) {
-                if (low) QAMD_QS4(1, true);
-                else QAMD_QS4(1, false);
-            } else {
-                if (low) QAMD_QS4(2, true);
-                else QAMD_QS4(2, false);
-            }
-#undef QAMD_QS4
-#undef QAMD_QS4_IT
-#undef QAMD_QS4_JT
-            QAMD_HIP(hipGetLastError());
+                               (uint32_t)q_pad, nsteps, metric_dim(h, 1), zx ? 1 : 0, largest, pass.pivot_scores(), frag, q_off, bq);
+        const bool rs4 = rt.kernel == BinBatchKernel::Rs4;
+        const uint64_t per_launch = rs4 ? rt.rs4_per_pass : kQs4Slice;
+        const uint32_t lists_per_launch = rs4 ? rt.n_lists / rt.rs4_passes : pp_waves_per_launch();
+        for (uint64_t q_base = 0; q_base < Q; q_base += per_launch) {
+            BinFp4Call c{h, frag, q_off, bq, q_base, (uint32_t)std::min<uint64_t>(per_launch, Q - q_base), f, s};
+            c.filt.pivot_scores += q_base;
+            c.filt.query_base = (uint32_t)q_base;
+            c.filt.wave_base = (uint32_t)(q_base / per_launch) * lists_per_launch;
+            if (rs4) QAMD_TRY(largest ? launch_bin_rs4<1>(rt, c) : launch_bin_rs4<2>(rt, c));
+            else QAMD_TRY(largest ? launch_bin_qs4<1>(rt, c) : launch_bin_qs4<2>(rt, c));
         }
-        if (Q <= 4096)
-            hipLaunchKernelGGL(wave_scatter_grouped_kernel, dim3(std::min<uint32_t>(n_lists, 128)), dim3(1024), (size_t)Q * 8, s, wave_cand,
-                               wave_counts, wave_cap, n_lists, (uint32_t)Q, counters, cand, overflow_dev);
-        else
-            hipLaunchKernelGGL(wave_scatter_kernel, dim3(n_lists), dim3(256), 0, s, wave_cand, wave_counts, wave_cap, counters, cand,
-                               overflow_dev);
-    } else
-    for (uint32_t q0 = 0; q0 < Q; q0 += TQ) {  // one pass over the rows per query tile; its lists are scattered right away
-        if (largest) QAMD_TRY(launch_bin_gemm<1>(h, b, h->rows.as<uint8_t>(), n, q0, mi, nullptr, 0, f, s));
-        else QAMD_TRY(launch_bin_gemm<2>(h, b, h->rows.as<uint8_t>(), n, q0, mi, nullptr, 0, f, s));
-        if (Q <= 4096)
-            hipLaunchKernelGGL(wave_scatter_grouped_kernel, dim3(std::min<uint32_t>(n_lists, 128)), dim3(1024), (size_t)Q * 8, s, wave_cand,
-                               wave_counts, wave_cap, n_lists, (uint32_t)Q, counters, cand, overflow_dev);
-        else
-            hipLaunchKernelGGL(wave_scatter_kernel, dim3(n_lists), dim3(256), 0, s, wave_cand, wave_counts, wave_cap, counters, cand,
-                               overflow_dev);
+        pass.scatter();
     }
-    if (k <= kSmallTopkMaxK)
-        hipLaunchKernelGGL(batch_emit_wave_kernel, dim3((unsigned)Q), dim3(1024), 0, s, cand, counters, n, k, largest, ids_dev, sc_dev,
-                           status_dev);
-    else
-        hipLaunchKernelGGL(batch_emit_kernel, dim3((unsigned)Q), dim3(1024), 0, s, cand, counters, n, k, largest, ids_dev, sc_dev,
-                           status_dev);
-    QAMD_HIP(hipGetLastError());
-    uint32_t overflow = 0;
-    if (hs.host) {
-        QAMD_HIP(hipStreamSynchronize(s));
-        std::copy(hs.host, hs.host + Q, status.begin());
-        overflow = hs.host[Q];
-    } else {
-        std::vector<uint32_t> back(Q + 1);
-        QAMD_TRY(copy_out(back.data(), QAMD_MEM_HOST, status_dev, (Q + 1) * 4, s));
-        std::copy(back.begin(), back.begin() + Q, status.begin());
-        overflow = back[Q];
-    }
-    if (overflow) std::fill(status.begin(), status.end(), 1u);
-    static const bool debug_topk = dev_env("QAMD_DEBUG_TOPK") != nullptr;
-    if (debug_topk) {
-        std::vector<uint32_t> cnt(q_pad * kCounterStride);
-        (void)hipMemcpy(cnt.data(), counters, cnt.size() * 4, hipMemcpyDeviceToHost);
-        uint32_t mx = 0, mn = ~0u, redo = 0;
-        uint64_t sum = 0;
-        for (uint64_t q = 0; q < Q; q++) {
-            const uint32_t c = cnt[q * kCounterStride];
-            mx = std::max(mx, c);
-            mn = std::min(mn, c);
-            sum += c;
-            redo += status[q] != 0;
-        }
-        char tail[32] = "";  // a scalar batch adds its bit count behind the fields the binary line has
-        if (b->qbits != 1) snprintf(tail, sizeof tail, ", query bits %u", b->qbits);
-        fprintf(stderr, "[qamd bin topk_batch] Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, filter %s, %u queries redone%s\n",
-                (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx,
-                rs4 ? "bin_gemm_rs4_kernel" : qs4 ? "bin_gemm_qs4_kernel" : "bin_gemm_rs_kernel", redo, tail);
-    }
+    QAMD_TRY(pass.emit(ids_dev, sc_dev));
+    QAMD_TRY(pass.read_status(status));
+    char tail[32] = "";  // a scalar batch adds its bit count behind the fields the binary line has
+    if (b->qbits != 1) snprintf(tail, sizeof tail, ", query bits %u", b->qbits);
+    pass.debug_line("[qamd bin topk_batch]", r, rt.name, tail, status);
     return QAMD_OK;
 }
 
@@ -2889,52 +2809,12 @@ static qamd_status bin_check_batch(const qamd_bin *h, const qamd_bin_query_batch
     return QAMD_OK;
 }
 
-// ---- routing: ONE predicate per entry point, called by the entry point and by qamd_bin_batch_kernel
-// The matrix gate both share: the query tile must fit LDS (bin_mfma_frags != 0: rows of at most 39 K-blocks = 4992 bits),
-// and at that length every operand and partial sum of the f32 epilogue is an integer below 2^23 - binary: 4 * 4992 + 2 *
-// 4992; scalar: 512 dim + 255 dim + 2 dim = 769 * 4992 < 2^22 - so the scores are those of the scan kernels bit for bit.
-static bool bin_mfma_capable(const qamd_bin *h) { return fused_capable(h) && bin_mfma_frags(h->ds) != 0 && h->code_bits >= 64; }
-
-// The smallest scalar batch the matrix cores take: the values of the binary int8 route, 5 for score_batch and
-// kRs4MinQueries = 12 for topk_batch.  Measured (profiles/bin_scalar_batch.txt, 50M x 1024, 4 / 8 bits, batch against a loop
-// of single-query calls on the same handle; min-max within 5 % of every median): score_batch of 8 queries 2.15 / 2.24 ms
-// against 8.46 / 9.76 (3.9 x / 4.4 x), 32 queries 12.5 x / 14.1 x, 64 queries 16.5 x / 18.4 x; topk_batch(30) of 32 queries
-// 2.28 / 2.41 ms against 31.0 / 37.6 (13.6 x / 15.6 x), 64 queries 13.7 x / 16.2 x; 8 queries are under the topk gate and
-// tie with the loop (1.01 x).  A tile costs about 2.2 ms at 50M rows whatever its fill and one scalar scan 1.0 - 1.2 ms, so
-// the crossover is probably near 3 queries for both calls; batches of 2 .. 7 were not timed, so the gates stay at the
-// smallest sizes the table supports.  QAMD_BIN_SCALAR_MFMA_MIN: developer A/B, next to QAMD_BIN_MFMA_MIN.
-static uint64_t bin_scalar_mfma_min(uint64_t dflt) {
-    static const uint64_t v = dev_env_u64("QAMD_BIN_SCALAR_MFMA_MIN", 0);
-    return v ? v : dflt;
-}
-
-static bool bin_score_batch_on_mfma(const qamd_bin *h, const qamd_bin_query_batch *b) {
-    const uint64_t least = b->qbits == 1 ? 5 : bin_scalar_mfma_min(5);
-    return b->n_queries >= least && h->count >= 4096 && bin_mfma_capable(h);
-}
-
-static bool bin_topk_batch_on_mfma(const qamd_bin *h, const qamd_bin_query_batch *b, uint32_t k) {
-    const uint64_t Q = b->n_queries;
-    bool enough;
-    if (b->qbits != 1) {
-        enough = Q >= bin_scalar_mfma_min(kRs4MinQueries);
-    } else {
-        static const char *emin = dev_env("QAMD_BIN_MFMA_MIN");  // developer A/B: the smallest batch the matrix cores take
-        // rows of 512 / 768 / 1024 / 1536 bits: a pass of the row-streaming fp4 kernel costs 1.4-1.5 ms per 50M x 1024 whatever the batch,
-        // the vector-ALU scan 1.04 / 1.98 / 1.26 / 2.2 / 1.8 / 3.7 ms at 2 / 3 / 4 / 5 / 8 / 11 queries (profiles/r04_bin_batch.txt)
-        const bool fp4_rows = h->ds == 64 || h->ds == 96 || h->ds == 128 || h->ds == 192;
-        enough = emin ? Q >= (uint64_t)atoll(emin) : (fp4_rows ? (Q == 3 || Q >= 5) : Q >= kRs4MinQueries);
-    }
-    return enough && h->count >= 32768 && k <= 1024 && bin_mfma_capable(h);
-}
-
+// ---- routing: ONE route (bin_route -> bin_batch_route.hpp, with the gates and the measurements behind them), read by the
+// entry points and by qamd_bin_batch_kernel
 const char *qamd_bin_batch_kernel(const qamd_bin *h, const qamd_bin_query_batch *b, uint32_t k) {
     if (bin_check_batch(h, b) != QAMD_OK) return nullptr;
-    if (k == 0 ? bin_score_batch_on_mfma(h, b) : bin_topk_batch_on_mfma(h, b, k)) {
-        if (k == 0) return "bin_gemm_rs_kernel";
-        const BinFilterPlan plan = bin_filter_plan(h, b);
-        return plan.rs4 ? "bin_gemm_rs4_kernel" : plan.qs4 ? "bin_gemm_qs4_kernel" : "bin_gemm_rs_kernel";
-    }
+    const BinBatchRoute route = bin_route(h, b, k);
+    if (route.mfma) return route.name;
     // the per-query routes: small stores take the single-launch top-k; binary queries share a pass over the rows
     SmallTopkPlan small;
     if (k != 0 && h->count <= (2u << 20) && bin_small_plan(h, k, b->qbits, small)) return "bin_topk_small_kernel";
@@ -2976,10 +2856,10 @@ qamd_status qamd_bin_score_batch(const qamd_bin *h, const qamd_bin_query_batch *
     // of the epilogue is an exact integer); the row bits are read once per tile instead of once per 8 queries
     // (measured at 50M x 1024: one 32-query tile 2.28 ms whatever the batch; the vector-ALU passes 1.81 ms for 4
     // queries, 2.6 for 8, and from there 2.6 ms per 8)
-    if (bin_score_batch_on_mfma(h, b)) {
-        const int mi = bin_mfma_frags(h->ds, b->n_queries);
-        for (; q < b->n_queries; q += 32 * mi)  // (a partly filled last tile computes zero queries and stores nothing for them)
-            QAMD_TRY(launch_bin_gemm<0>(h, b, h->rows.as<uint8_t>(), h->count, (uint32_t)q, mi, out_dev, h->count, BatchFilter{}, s));
+    const BinBatchRoute route = bin_route(h, b, 0);
+    if (route.mfma) {
+        for (; q < b->n_queries; q += 32 * route.mi)  // (a partly filled last tile computes zero queries and stores nothing for them)
+            QAMD_TRY(launch_bin_rs<0>({h, b, h->rows.as<uint8_t>(), h->count, (uint32_t)q, route.mi, out_dev, h->count, BatchFilter{}, s}));
     }
     for (; b->qbits != 1 && q < b->n_queries; q++)  // scalar queries off the matrix cores: one scan of the planes each
         QAMD_TRY(scan_bits(h, bin_batch_query(b, q), out_dev + q * h->count, s, nullptr, b->qbits));
@@ -3021,55 +2901,40 @@ qamd_status qamd_bin_topk_batch(const qamd_bin *h, const qamd_bin_query_batch *b
         return bin_topk_small(h, bin_batch_query(b, q), k, largest, ids, sc, QAMD_MEM_DEVICE, st, status, planes);
     };
     // up to 8 binary queries share one pass over the rows (the filtering form of bin_scan_multi_kernel)
-    if (planes == 1)
-    scan.scan_filter_multi = [&](uint32_t q, uint32_t left, const TopkFilterSlices &sl, hipStream_t st, qamd_status &status) -> uint32_t {
-        const uint8_t *qb = bin_batch_query(b, q);
-        uint32_t took = 0;
-        if (left >= 8 && multi_step<8>(h, qb, qs, nullptr, st, &sl)) took = 8;
-        else if (left >= 4 && multi_step<4>(h, qb, qs, nullptr, st, &sl)) took = 4;
-        else if (left >= 2 && multi_step<2>(h, qb, qs, nullptr, st, &sl)) took = 2;
-        if (took && hipGetLastError() != hipSuccess) status = fail(QAMD_ERR_DEVICE, "binary multi-query filter launch failed");
-        return took;
-    };
+    if (planes == 1) {
+        scan.scan_filter_multi = [&](uint32_t q, uint32_t left, const TopkFilterSlices &sl, hipStream_t st, qamd_status &status) -> uint32_t {
+            const uint8_t *qb = bin_batch_query(b, q);
+            uint32_t took = 0;
+            if (left >= 8 && multi_step<8>(h, qb, qs, nullptr, st, &sl)) took = 8;
+            else if (left >= 4 && multi_step<4>(h, qb, qs, nullptr, st, &sl)) took = 4;
+            else if (left >= 2 && multi_step<2>(h, qb, qs, nullptr, st, &sl)) took = 2;
+            if (took && hipGetLastError() != hipSuccess) status = fail(QAMD_ERR_DEVICE, "binary multi-query filter launch failed");
+            return took;
+        };
+    }
     // 12 queries and more on stores of 32k rows and more (below that the filtering vector-ALU passes, 0.22 ms per
     // query at 50M rows, are cheaper than one matrix-core pass): bin_gemm_rs_kernel; queries whose
     // candidate list over- or underflowed there (heavy ties at small dims) go through the path below one by one
     const uint64_t Q = b->n_queries;
     hipStream_t s = as_stream(stream);
-    // (bin_topk_batch_on_mfma: the gate, with the measurements behind the binary thresholds)
-    if (bin_topk_batch_on_mfma(h, b, k)) {
-        StreamBuf ids_tmp, sc_tmp;
-        uint32_t *ids_dev = out_ids;
-        float *sc_dev = out_scores;
-        if (out_mem == QAMD_MEM_HOST) {
-            QAMD_TRY(ids_tmp.alloc(Q * k * 4, s));
-            QAMD_TRY(sc_tmp.alloc(Q * k * 4, s));
-            ids_dev = ids_tmp.as<uint32_t>();
-            sc_dev = sc_tmp.as<float>();
-        }
-        std::vector<uint32_t> status(Q, 1);
-        QAMD_TRY(bin_topk_batch_mfma(h, b, k, largest, ids_dev, sc_dev, status, s));
-        for (uint64_t q = 0; q < Q; q++) {
-            if (!status[q]) continue;
+    const BinBatchRoute route = bin_route(h, b, k);
+    if (route.mfma) {
+        BatchTopkOutputs out;
+        QAMD_TRY(out.begin(Q, k, out_ids, out_scores, out_mem, s));
+        QAMD_TRY(bin_topk_batch_mfma(h, b, route, k, largest, out.ids_dev, out.sc_dev, out.status, s));
+        return out.finish([&](uint64_t q, uint32_t *ids_dev, float *sc_dev) {
             BatchScan one;
             one.filter_capable = scan.filter_capable;
             one.scan_scores = [&, q](uint32_t, float *scores, hipStream_t st) { return scan.scan_scores((uint32_t)q, scores, st); };
             one.scan_filter = [&, q](uint32_t, const TopkFilter &f, hipStream_t st) { return scan.scan_filter((uint32_t)q, f, st); };
-            one.score_ids = [&, q](uint32_t, const uint32_t *ids, uint64_t n_ids, float *out, hipStream_t st) {
-                return scan.score_ids((uint32_t)q, ids, n_ids, out, st);
+            one.score_ids = [&, q](uint32_t, const uint32_t *ids, uint64_t n_ids, float *out1, hipStream_t st) {
+                return scan.score_ids((uint32_t)q, ids, n_ids, out1, st);
             };
             one.topk_small = [&, q](uint32_t, uint32_t *ids, float *sc, hipStream_t st, qamd_status &status1) {
                 return scan.topk_small((uint32_t)q, ids, sc, st, status1);
             };
-            QAMD_TRY(fused_topk_batch(h->count, 1, k, largest, ids_dev + q * k, sc_dev + q * k, QAMD_MEM_DEVICE, s, one));
-        }
-        if (out_mem == QAMD_MEM_HOST) {
-            QAMD_TRY(copy_out(out_ids, QAMD_MEM_HOST, ids_dev, Q * k * 4, s));
-            QAMD_TRY(copy_out(out_scores, QAMD_MEM_HOST, sc_dev, Q * k * 4, s));
-        } else {
-            QAMD_HIP(hipStreamSynchronize(s));
-        }
-        return QAMD_OK;
+            return fused_topk_batch(h->count, 1, k, largest, ids_dev, sc_dev, QAMD_MEM_DEVICE, s, one);
+        });
     }
     return fused_topk_batch(h->count, (uint32_t)b->n_queries, k, largest, out_ids, out_scores, out_mem, s, scan);
 }

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <functional>
 
+#include "batch_plan.hpp"  // kTopkSample
 #include "common.hpp"
 
 namespace qamd {
@@ -69,7 +70,6 @@ qamd_status score_all_to_host(uint64_t count, float *out, hipStream_t stream, Sc
 // Exact whenever k <= #candidates <= 8192; otherwise (heavy ties, e.g. binary scores, or an
 // unlucky pivot) the classic path runs: full score array + exact radix select.  The status
 // read-back makes this call synchronise `stream`.
-constexpr uint32_t kTopkSample = 16384;
 struct TopkFilter;
 struct TopkFilterSlices;
 struct FusedScan {

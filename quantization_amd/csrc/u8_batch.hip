@@ -1949,7 +1949,6 @@ qamd_status check_batch(const qamd_u8 *h, const qamd_u8_query_batch *b) {
 // The developer switches of this file, read once per process (tools/lib build; all-default in the product library).
 struct DevSwitches {
     U8GemmSwitches route;
-    bool debug_topk = false;  // QAMD_DEBUG_TOPK: one line per topk_batch call on stderr
 };
 const DevSwitches &dev_switches() {
     static const DevSwitches switches = [] {
@@ -1974,7 +1973,6 @@ const DevSwitches &dev_switches() {
         d.route.qr_max = number("QAMD_QR_MAX");
         d.route.rq_min = number("QAMD_RQ_MIN");
         d.route.rq_max = number("QAMD_RQ_MAX");
-        d.debug_topk = text("QAMD_DEBUG_TOPK") != nullptr;
         return d;
     }();
     return switches;
@@ -2007,16 +2005,6 @@ struct GemmCall {
     BatchFilter filt;
     hipStream_t s;
 };
-
-// fn(std::bool_constant<LOW>): LOW is the direction of the integer pre-filter of MODE 1 / 2 - "may pass" is s <= bound
-// when the score falls with s (multiplier < 0) xor smallest-first.  The other modes have no pre-filter (LOW = false).
-template <int MODE, typename Fn>
-qamd_status with_low(float multiplier, Fn &&fn) {
-    if constexpr (MODE == 1 || MODE == 2) {
-        if ((multiplier < 0.0f) != (MODE == 2)) return fn(std::true_type{});
-    }
-    return fn(std::false_type{});
-}
 
 // Per-query integer bounds of the pre-filter for the kernels that stream or hold queries in fragment order (behind the
 // pivots in stream order).
@@ -2399,97 +2387,37 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
         // status read-back per 32 queries.
         return u8_topk_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)Q, k, largest,
                                    out_ids, out_scores, out_mem, s);
-    // Pivot rank r of S sampled rows: the number of rows at least as good as the pivot is about
-    // n*Beta(r, S-r+1): mean n*r/S, relative spread 1/sqrt(r).  With many queries per call both tails
-    // matter (a list that overflows kBatchCap or holds fewer than k rows sends its query to the exact
-    // single-query path, milliseconds each), and so does the mean: every passing (query, row) pair
-    // costs an exact epilogue + a list append inside the GEMM (2048 expected per query instead of 512
-    // measured +7..10 % on the whole call).  So: about max(512, 3k) rows expected to pass at pivot
-    // rank >= 8 (P(fewer than k) < 1e-7, P(more than 8192) ~ 0); S = 8 n / that, capped at 524288
-    // sampled rows (beyond 33M rows the expected count grows instead of r shrinking).
-    // Few queries: a smaller sample (cheaper pivot pass) and more candidates per query instead (measured at
-    // 10M x 768, 5-128 queries: 1024 expected beats 512 by 0.01-0.02 ms and 2048 by 0.03-0.08 ms - the
-    // per-query scatter and sort of the candidates grow faster than the sample pass shrinks).
-    const double want = std::max<double>(Q <= 128 ? 1024.0 : 512.0, 3.0 * k);
-    // small stores (Qdrant segments: 1e5..1e6 rows) take the same route with a smaller sample: the
-    // per-query fallback costs a launch chain per query, the matrix-core pass one for the whole batch
-    const double s_min = n < (1u << 20) ? 2048.0 : (double)kTopkSample;
-    const double s_mem_cap = std::max<double>(s_min, std::floor((double)(6ull << 30) / (4.0 * (double)Q) / 256.0) * 256.0);  // <= 6 GB of sample scores
-    const uint32_t S = (uint32_t)std::min<double>(std::min<double>(524288.0, s_mem_cap),
-                                                  std::max<double>(s_min, round_up((uint64_t)(8.0 * (double)n / want), 256)));
-    const double target = std::max<double>(want, 8.0 * (double)n / (double)S);
-    const uint32_t r = n ? (uint32_t)std::ceil((double)S * target / (double)n) : 0;
-    // (the sample scores are Q x S f32: 0.6 GB at 1024 queries and 10M rows, 5 GB at 8192 queries)
+    // The pivot sample (batch_plan.hpp: the pivot rank r of S sampled rows, `target` rows expected to pass per query).
+    const BatchSamplePlan plan = batch_sample_plan(n, Q, k);
+    const uint32_t S = plan.S, r = plan.r;
     const bool fused = n >= 32768 && r <= 64 && h->meta.vector_parameters.distance_type != QAMD_L1;
 
-    StreamBuf ids_tmp, sc_tmp;
-    uint32_t *ids_dev = out_ids;
-    float *sc_dev = out_scores;
-    if (out_mem == QAMD_MEM_HOST) {
-        QAMD_TRY(ids_tmp.alloc(Q * k * 4, s));
-        QAMD_TRY(sc_tmp.alloc(Q * k * 4, s));
-        ids_dev = ids_tmp.as<uint32_t>();
-        sc_dev = sc_tmp.as<float>();
-    }
-    std::vector<uint32_t> status(Q, 1);
+    BatchTopkOutputs out;
+    QAMD_TRY(out.begin(Q, k, out_ids, out_scores, out_mem, s));
     if (fused) {
         const uint64_t ad = h->meta.actual_dim;
-        // ONE stream-ordered allocation for all scratch of the call, carved up below: hipFreeAsync
-        // costs ~65 us per buffer on this runtime, and ten buffers were a third of a small batch's time.
-        const bool pp = filter_route.wave_lists;  // every kernel but u8_gemm_kernel appends to wave-private lists
         uint32_t n_lists = 0, wave_cap = 0;
-        if (pp) {
+        if (filter_route.wave_lists) {  // every kernel but u8_gemm_kernel appends to wave-private lists
             // wave-private lists: 4x the expected appends per wave (about `target`..2*target per query)
             n_lists = filter_route.list_launches * pp_waves_per_launch();
-            const double per_wave = 2.0 * target * (double)Q / (double)n_lists;
+            const double per_wave = 2.0 * plan.target * (double)Q / (double)n_lists;
             wave_cap = (uint32_t)std::min<double>(1u << 20, std::max<double>(1024.0, 4.0 * per_wave));
         }
-        size_t arena_bytes = 0;
-        auto reserve = [&](size_t bytes) {
-            const size_t off = arena_bytes;
-            arena_bytes += round_up(std::max<size_t>(bytes, 16), 256);
-            return off;
-        };
-        // zero-initialised part first (one memset): pivots, counters, wave counts, overflow flag
-        const size_t o_pivots = reserve(b->q_pad * 4);
-        const size_t o_counters = reserve(b->q_pad * kCounterStride * 4);
-        const size_t o_wcounts = reserve((uint64_t)n_lists * 4);
-        const size_t zero_bytes = arena_bytes;
+        BatchTopkPass pass(n, Q, b->q_pad, k, largest, n_lists, wave_cap, s);
         // the sample sub-store: the handle's cached one (a prefix of it), else gathered into the arena
-        const uint32_t rows_all = (uint32_t)std::min<double>(524288.0, std::max<double>(s_min, (double)round_up((uint64_t)(8.0 * (double)n / 512.0), 256)));
         const uint8_t *s_codes = nullptr;
         const float *s_offs = nullptr;
-        const bool cached = S <= rows_all && sample_store(h, rows_all, s, &s_codes, &s_offs) == QAMD_OK;
-        const size_t o_codes = reserve(cached ? 16 : (uint64_t)(S + 512) * ad);  // + one (largest) tile of zero rows
-        const size_t o_offs = reserve(cached ? 16 : (uint64_t)(S + 512) * 4);
+        const bool cached = S <= plan.rows_all && sample_store(h, plan.rows_all, s, &s_codes, &s_offs) == QAMD_OK;
+        const size_t o_codes = pass.reserve(cached ? 16 : (uint64_t)(S + 512) * ad);  // + one (largest) tile of zero rows
+        const size_t o_offs = pass.reserve(cached ? 16 : (uint64_t)(S + 512) * 4);
         const U8GemmRoute sample_route = gemm_route(h, b, U8GemmPass::Sample, S);
         const uint32_t rows_per_block = sample_route.sample_block_rows;
-        const size_t o_scores = reserve(rows_per_block ? Q * ((uint64_t)S / 64 + 2) * 4 : Q * (uint64_t)S * 4);  // sample scores, or block bests
-        const size_t o_cand = reserve(Q * (uint64_t)kBatchCap * 8);
-        const size_t o_status = reserve((Q + 1) * 4);  // per-query status, then the wave-list overflow flag
-        const size_t o_bounds = reserve(b->q_pad * 4);
-        const size_t o_wcand = reserve((uint64_t)n_lists * wave_cap * sizeof(uint4));
-        StreamBuf arena;
-        QAMD_TRY(arena.alloc(arena_bytes, s));
-        char *base = arena.as<char>();
-        QAMD_HIP(hipMemsetAsync(base, 0, zero_bytes, s));
-        float *pivots = reinterpret_cast<float *>(base + o_pivots);
-        uint32_t *counters = reinterpret_cast<uint32_t *>(base + o_counters);
-        uint32_t *wave_counts = reinterpret_cast<uint32_t *>(base + o_wcounts);
-        float *s_scores = reinterpret_cast<float *>(base + o_scores);
-        unsigned long long *cand = reinterpret_cast<unsigned long long *>(base + o_cand);
-        // The per-query status words and the overflow flag come back through the calling thread's mapped
-        // host scratch when they fit (the kernels write host memory directly: one stream sync, no copy
-        // calls), else through one copy from the arena.
-        const HostScratch hs = Q + 1 <= 2048 ? host_scratch() : HostScratch{};
-        uint32_t *status_dev = hs.dev ? hs.dev : reinterpret_cast<uint32_t *>(base + o_status);
-        uint32_t *overflow_dev = status_dev + Q;
-        if (hs.host) hs.host[Q] = 0;
-        else QAMD_HIP(hipMemsetAsync(overflow_dev, 0, 4, s));
-        uint4 *wave_cand = reinterpret_cast<uint4 *>(base + o_wcand);
+        const size_t o_scores = pass.reserve(rows_per_block ? Q * ((uint64_t)S / 64 + 2) * 4 : Q * (uint64_t)S * 4);  // sample scores, or block bests
+        QAMD_TRY(pass.alloc(true));
+        float *s_scores = pass.at<float>(o_scores);
         if (!cached) {
-            uint8_t *g_codes = reinterpret_cast<uint8_t *>(base + o_codes);
-            float *g_offs = reinterpret_cast<float *>(base + o_offs);
+            uint8_t *g_codes = pass.at<uint8_t>(o_codes);
+            float *g_offs = pass.at<float>(o_offs);
             hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->codes.as<uint4>(),
                                h->offsets.as<float>(), h->row_chunks, n, S, 512u, reinterpret_cast<uint4 *>(g_codes), g_offs);
             s_codes = g_codes;
@@ -2505,83 +2433,26 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
             BatchFilter fs{};
             fs.largest = largest;
             QAMD_TRY(launch_gemm<3>(sample_route, {h, b, s_codes, s_offs, S, s_scores, s_blocks, fs, s}));
-            hipLaunchKernelGGL(batch_pivot_kernel, dim3((unsigned)b->q_pad), dim3(1024), 0, s, s_scores, s_blocks,
-                               (uint64_t)s_blocks, r, largest, (uint32_t)Q, pivots, counters);
+            pass.pivots(s_scores, s_blocks, s_blocks, r);
         } else {
             QAMD_TRY(launch_gemm<0>(sample_route, {h, b, s_codes, s_offs, S, s_scores, S, BatchFilter{}, s}));
-            hipLaunchKernelGGL(batch_pivot_kernel, dim3((unsigned)b->q_pad), dim3(1024), 0, s, s_scores, S, (uint64_t)S, r,
-                               largest, (uint32_t)Q, pivots, counters);
+            pass.pivots(s_scores, S, S, r);
         }
-        BatchFilter f{};
-        f.pivot_scores = pivots;
-        f.counters = counters;
-        f.candidates = cand;
-        f.largest = largest;
-        f.n_queries = (uint32_t)Q;
-        f.query_bounds = reinterpret_cast<int *>(base + o_bounds);
-        if (pp) {
-            f.wave_cap = wave_cap;
-            f.wave_cand = wave_cand;
-            f.wave_counts = wave_counts;
-        }
+        const BatchFilter f = pass.filter();
         if (largest)
             QAMD_TRY(launch_gemm<1>(filter_route, {h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
         else
             QAMD_TRY(launch_gemm<2>(filter_route, {h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
-        if (pp && Q <= 4096)
-            hipLaunchKernelGGL(wave_scatter_grouped_kernel, dim3(std::min<uint32_t>(n_lists, 128)), dim3(1024), (size_t)Q * 8, s,
-                               wave_cand, wave_counts, f.wave_cap, n_lists, (uint32_t)Q, counters, cand, overflow_dev);
-        else if (pp)
-            hipLaunchKernelGGL(wave_scatter_kernel, dim3(n_lists), dim3(256), 0, s, wave_cand, wave_counts, f.wave_cap,
-                               counters, cand, overflow_dev);
-        if (k <= kSmallTopkMaxK)
-            hipLaunchKernelGGL(batch_emit_wave_kernel, dim3((unsigned)Q), dim3(1024), 0, s, cand, counters, n, k, largest,
-                               ids_dev, sc_dev, status_dev);
-        else
-            hipLaunchKernelGGL(batch_emit_kernel, dim3((unsigned)Q), dim3(1024), 0, s, cand, counters, n, k, largest, ids_dev,
-                               sc_dev, status_dev);
-        QAMD_HIP(hipGetLastError());
-        uint32_t overflow = 0;
-        if (hs.host) {
-            QAMD_HIP(hipStreamSynchronize(s));
-            std::copy(hs.host, hs.host + Q, status.begin());
-            overflow = hs.host[Q];
-        } else {
-            std::vector<uint32_t> back(Q + 1);
-            QAMD_TRY(copy_out(back.data(), QAMD_MEM_HOST, status_dev, (Q + 1) * 4, s));  // synchronises
-            std::copy(back.begin(), back.begin() + Q, status.begin());
-            overflow = back[Q];
-        }
-        if (pp && overflow) std::fill(status.begin(), status.end(), 1u);  // a wave list overflowed: redo all exactly
-        if (dev_switches().debug_topk) {
-            std::vector<uint32_t> cnt(b->q_pad * kCounterStride);
-            (void)hipMemcpy(cnt.data(), counters, cnt.size() * 4, hipMemcpyDeviceToHost);
-            uint32_t mx = 0, mn = ~0u, redo = 0;
-            uint64_t sum = 0;
-            for (uint64_t q = 0; q < Q; q++) {
-                const uint32_t c = cnt[q * kCounterStride];
-                mx = std::max(mx, c);
-                mn = std::min(mn, c);
-                sum += c;
-                redo += status[q];
-            }
-            fprintf(stderr, "[qamd topk_batch] Q=%llu r=%u candidates min/mean/max = %u/%llu/%u, filter %s, %u queries redone\n",
-                    (unsigned long long)Q, r, mn, (unsigned long long)(sum / Q), mx, filter_route.name, redo);
-        }
+        pass.scatter();
+        QAMD_TRY(pass.emit(out.ids_dev, out.sc_dev));
+        QAMD_TRY(pass.read_status(out.status));
+        pass.debug_line("[qamd topk_batch]", r, filter_route.name, "", out.status);
     }
     // Queries not served by the fused pass (small stores, overflowed lists): exact single-query path.
-    for (uint64_t q = 0; q < Q; q++) {
-        if (!status[q]) continue;
-        QAMD_TRY(u8_topk_single(h, b->codes.as<uint8_t>() + q * b->pitch, b->offsets.as<float>() + q, k, largest,
-                                ids_dev + q * k, sc_dev + q * k, QAMD_MEM_DEVICE, s));
-    }
-    if (out_mem == QAMD_MEM_HOST) {
-        QAMD_TRY(copy_out(out_ids, QAMD_MEM_HOST, ids_dev, Q * k * 4, s));
-        QAMD_TRY(copy_out(out_scores, QAMD_MEM_HOST, sc_dev, Q * k * 4, s));
-    } else {
-        QAMD_HIP(hipStreamSynchronize(s));  // scratch buffers are released on return
-    }
-    return QAMD_OK;
+    return out.finish([&](uint64_t q, uint32_t *ids_dev, float *sc_dev) {
+        return u8_topk_single(h, b->codes.as<uint8_t>() + q * b->pitch, b->offsets.as<float>() + q, k, largest, ids_dev, sc_dev,
+                              QAMD_MEM_DEVICE, s);
+    });
 }
 
 }  // extern "C"

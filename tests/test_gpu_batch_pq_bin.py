@@ -192,3 +192,24 @@ def test_binary_batch_of_identical_queries():
     wi, ws = enc.topk(enc.encode_query(q), 30)
     for qi in (0, 31, 63):
         assert np.array_equal(ids[qi], wi) and np.array_equal(sc[qi], ws), qi
+
+
+def test_binary_batch_more_than_4096_queries():
+    """Above four row-streaming passes (4 x 608 queries of 512 bits) the batch takes bin_gemm_qs4_kernel, here in three
+    slices of 2048 queries; above 4096 queries the per-candidate scatter kernel serves (the grouped one keeps two words
+    per query in LDS) and the status words come back through the arena, not the mapped host scratch; k = 100 takes the
+    sorting emit.  Every checked list must equal the single-query top-k, ids and score bits."""
+    rng = np.random.default_rng(29)
+    n, dim, nq = 33_000, 512, 4200
+    data = rng.standard_normal((n, dim)).astype(np.float32)
+    queries = rng.standard_normal((nq, dim)).astype(np.float32)
+    for dist, largest in ((D.Dot, True), (D.L2, False)):
+        enc = qa.EncodedVectorsBin.encode(data, qa.VectorParameters(dim, n, dist, False))
+        batch = enc.encode_query_batch(queries)
+        for k in (30, 100):
+            assert enc.batch_kernel(batch, k) == "bin_gemm_qs4_kernel"
+            ids, sc = enc.topk_batch(batch, k, largest=largest)
+            for qi in (0, 2047, 2048, 4095, 4096, nq - 1):
+                wi, ws = enc.topk(enc.encode_query(queries[qi]), k, largest=largest)
+                assert np.array_equal(ids[qi], wi), (dist, k, qi)
+                assert np.array_equal(sc[qi].view(np.uint32), ws.view(np.uint32)), (dist, k, qi)
