@@ -220,6 +220,29 @@ QAMD_API qamd_status qamd_u8_score_internal_ids_batch(const qamd_u8 *h, const ui
                                                       const uint32_t *ids, uint64_t n_ids, qamd_mem lists_mem,
                                                       float *out, qamd_mem out_mem, void *stream);
 
+/* score_internal against the WHOLE store (all three quantizers; with these six the header declares 192 entry points):
+ *   *_score_internal_all: out[j] has the bits of *_score_internal(h, i, j) for every j < count.  Row i itself is included;
+ *     callers drop it.
+ *   *_topk_internal: the k best of exactly those scores under the one ordering stated at qamd_u8_topk (the total order on
+ *     the score bits, ties to the lower id, best first, NaN rule included).  k <= 1024; k == 0 is QAMD_OK.
+ * What "the rows most like stored row i" needs (recommend-by-id, near-duplicate detection, the exact neighbour lists a
+ * graph builder checks its links against) in one bandwidth-bound scan, not count pairs through *_score_internal_ids.  A
+ * stored row cannot be passed off as a query: score_point and score_internal differ in arithmetic (u8: the epilogue, PQ:
+ * the table and the summation order), and no query can be built from stored codes.
+ * The arithmetic is the reference's score_internal - encoded_vectors_u8.rs:386-453, encoded_vectors_pq.rs:566-593,
+ * encoded_vectors_binary.rs:302-314 - pair by pair; the whole-store form has no counterpart there.
+ *   - i >= count is QAMD_ERR_ARGUMENTS, refused before any launch; a null handle is refused before any device call;
+ *     an empty store is QAMD_OK (nothing is written; topk_internal writes the padding of a short list).
+ *   - Host and device outputs synchronise exactly as *_score_all / *_topk do: score_internal_all with a device output
+ *     only enqueues, topk_internal always synchronises `stream`.
+ *   - u8: lane mode (qamd_u8_set_lane_mode) holds as for every other call.  PQ: a handle without centroids is
+ *     QAMD_ERR_ARGUMENTS.
+ * Out of scope: Sharded handles have no whole-store score_internal.  There is no batched topk_internal_batch for many
+ * stored rows at once.  There is no rescored variant (topk_internal followed by a re-rank with the original vectors). */
+QAMD_API qamd_status qamd_u8_score_internal_all(const qamd_u8 *h, uint32_t i, float *out, qamd_mem out_mem, void *stream);
+QAMD_API qamd_status qamd_u8_topk_internal(const qamd_u8 *h, uint32_t i, uint32_t k, int largest,
+                                           uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream);
+
 /* NEW (batched caller loop, demos/src/ann_benchmark.rs:247-252):
  * out[i] = score_point(q, i) for i in [0, count). */
 QAMD_API qamd_status qamd_u8_score_all(const qamd_u8 *h, const qamd_u8_query *q, float *out,
@@ -446,6 +469,11 @@ QAMD_API qamd_status qamd_bin_score_internal_ids_batch(const qamd_bin *h, const 
                                                        const uint32_t *list_offsets, uint32_t n_lists,
                                                        const uint32_t *ids, uint64_t n_ids, qamd_mem lists_mem,
                                                        float *out, qamd_mem out_mem, void *stream);
+/* score_internal (:302-314) against the whole store, contract as qamd_u8_score_internal_all / _topk_internal: the metric of
+ * score_point with stored row i as the one-plane query, one-bit and two-bit rows alike. */
+QAMD_API qamd_status qamd_bin_score_internal_all(const qamd_bin *h, uint32_t i, float *out, qamd_mem out_mem, void *stream);
+QAMD_API qamd_status qamd_bin_topk_internal(const qamd_bin *h, uint32_t i, uint32_t k, int largest,
+                                            uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream);
 QAMD_API qamd_status qamd_bin_score_all(const qamd_bin *h, const qamd_bin_query *q, float *out,
                                         qamd_mem out_mem, void *stream);
 QAMD_API qamd_status qamd_bin_score_ids(const qamd_bin *h, const qamd_bin_query *q,
@@ -612,6 +640,12 @@ QAMD_API qamd_status qamd_pq_score_internal_ids_batch(const qamd_pq *h, const ui
                                                       const uint32_t *list_offsets, uint32_t n_lists,
                                                       const uint32_t *ids, uint64_t n_ids, qamd_mem lists_mem,
                                                       float *out, qamd_mem out_mem, void *stream);
+/* score_internal (:566-593) against the whole store, contract as qamd_u8_score_internal_all / _topk_internal: row i's table
+ * of centroid-to-centroid chunk metrics, summed per row strictly in chunk order and negated (invert) once after the sum -
+ * not the four-lane order of score_point. */
+QAMD_API qamd_status qamd_pq_score_internal_all(const qamd_pq *h, uint32_t i, float *out, qamd_mem out_mem, void *stream);
+QAMD_API qamd_status qamd_pq_topk_internal(const qamd_pq *h, uint32_t i, uint32_t k, int largest,
+                                           uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream);
 QAMD_API qamd_status qamd_pq_score_all(const qamd_pq *h, const qamd_pq_query *q, float *out,
                                        qamd_mem out_mem, void *stream);
 QAMD_API qamd_status qamd_pq_score_ids(const qamd_pq *h, const qamd_pq_query *q,

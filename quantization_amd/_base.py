@@ -165,6 +165,27 @@ class EncodedVectorsBase:
                                stream_ptr(stream)))
         return ids, sc
 
+    # ------------------------------------------------------------------ score_internal against the whole store
+    def score_internal_all(self, i: int, out=None, stream=None):
+        """scores[j] = score_internal(i, j) for every row j, bit for bit (row i itself included): one scan of the
+        store, where score_internal_ids(i, arange(count)) is count random-access pairs."""
+        check_same_device(self._device, out)
+        buf, ret = out_buf(out, self.count, np.float32)
+        check(self._fn("score_internal_all")(self._h, int(i), buf.ptr, buf.mem, stream_ptr(stream)))
+        return ret
+
+    def topk_internal(self, i: int, k: int, largest: bool = True, out_ids=None, out_scores=None, stream=None):
+        """The k best rows of score_internal_all(i), ordered as topk orders (ties to the lower row id, best first); row
+        i is among them unless the caller drops it.  Returns (ids, scores)."""
+        check_same_device(self._device, out_ids, out_scores)
+        ib, ids = out_buf(out_ids, k, np.uint32)
+        sb, sc = out_buf(out_scores, k, np.float32)
+        if ib.mem != sb.mem:
+            raise ValueError("out_ids and out_scores must both be host or both be device buffers")
+        check(self._fn("topk_internal")(self._h, int(i), int(k), int(bool(largest)), ib.ptr, sb.ptr, sb.mem,
+                                        stream_ptr(stream)))
+        return ids, sc
+
     # ------------------------------------------------------------------ many queries at once
     def encode_query_batch(self, queries, reuse=None, stream=None):
         """encode_query for a [n_queries, dim] block of queries (the caller's outer loop,

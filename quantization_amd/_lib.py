@@ -270,6 +270,13 @@ def lib() -> C.CDLL:
         "qamd_pq_capacity": (u64, [vp]),
         "qamd_bin_capacity": (u64, [vp]),
         "qamd_f32_capacity": (u64, [vp]),
+        # score_internal against the whole store
+        "qamd_u8_score_internal_all": (i32, [vp, u32, vp, i32, vp]),
+        "qamd_pq_score_internal_all": (i32, [vp, u32, vp, i32, vp]),
+        "qamd_bin_score_internal_all": (i32, [vp, u32, vp, i32, vp]),
+        "qamd_u8_topk_internal": (i32, [vp, u32, u32, i32, vp, vp, i32, vp]),
+        "qamd_pq_topk_internal": (i32, [vp, u32, u32, i32, vp, vp, i32, vp]),
+        "qamd_bin_topk_internal": (i32, [vp, u32, u32, i32, vp, vp, i32, vp]),
         "qamd_topk_scores": (i32, [vp, u64, u32, i32, vp, vp, i32, vp]),
         "qamd_topk_merge": (i32, [vp, vp, u64, vp, u32, u32, u32, i32, vp, vp, i32, vp]),
     }

@@ -949,11 +949,6 @@ qamd_status scan_bits(const qamd_bin *h, const void *qbits_dev, float *out_dev, 
     return QAMD_OK;
 }
 
-qamd_status scan_into(const qamd_bin *h, const qamd_bin_query *q, float *out_dev, hipStream_t s,
-                      const TopkFilter *filt = nullptr) {
-    return scan_bits(h, q->buf.ptr, out_dev, s, filt, q->bits);
-}
-
 template <int G, int ITERS, int PLANES>
 qamd_status launch_bin_small(const qamd_bin *h, const uint4 *qb, const SmallTopkPlan &pl, const SmallTopk &p, hipStream_t s) {
     const uint32_t rc = (uint32_t)(h->ds / 16);
@@ -1571,6 +1566,14 @@ qamd_status qamd_bin_query_read(const qamd_bin_query *q, uint8_t *bits, uint64_t
 
 void qamd_bin_query_free(qamd_bin_query *q) { delete q; }
 
+// score_all for a device pointer to query bits (`planes` planes): an encoded query's buffer or, for score_internal_all,
+// a stored row of the image the scan reads.
+static qamd_status score_all_bits(const qamd_bin *h, const void *qbits, uint32_t planes, float *out, qamd_mem out_mem,
+                                  hipStream_t s) {
+    if (out_mem == QAMD_MEM_DEVICE) return scan_bits(h, qbits, out, s, nullptr, planes);
+    return score_all_to_host(h->count, out, s, [&](float *scores) { return scan_bits(h, qbits, scores, s, nullptr, planes); });
+}
+
 qamd_status qamd_bin_score_all(const qamd_bin *h, const qamd_bin_query *q, float *out, qamd_mem out_mem,
                                void *stream) {
     QAMD_TRY(check_query(h, q));
@@ -1579,8 +1582,7 @@ qamd_status qamd_bin_score_all(const qamd_bin *h, const qamd_bin_query *q, float
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     QAMD_TRY(q->ready.wait(s));
-    if (out_mem == QAMD_MEM_DEVICE) return scan_into(h, q, out, s);
-    return score_all_to_host(h->count, out, s, [&](float *scores) { return scan_into(h, q, scores, s); });
+    return score_all_bits(h, q->buf.ptr, q->bits, out, out_mem, s);
 }
 
 qamd_status qamd_bin_score_ids(const qamd_bin *h, const qamd_bin_query *q, const uint32_t *ids, uint64_t n_ids,
@@ -1629,6 +1631,26 @@ qamd_status qamd_bin_score_internal_ids_batch(const qamd_bin *h, const uint32_t 
     });
 }
 
+// The routes of topk for a device pointer to query bits, as score_all_bits.
+static qamd_status topk_bits(const qamd_bin *h, const void *qbits, uint32_t planes, uint32_t k, int largest, uint32_t *out_ids,
+                             float *out_scores, qamd_mem out_mem, hipStream_t s) {
+    {   // small stores: one launch, exact under any number of ties, no status read-back
+        qamd_status st = QAMD_OK;
+        if (bin_topk_small(h, qbits, k, largest, out_ids, out_scores, out_mem, s, st, planes)) return st;
+    }
+    if (!fused_capable(h)) {
+        return topk_classic(h->count, k, largest, out_ids, out_scores, out_mem, s,
+                            [&](float *scores) { return scan_bits(h, qbits, scores, s, nullptr, planes); });
+    }
+    FusedScan scan;
+    scan.scan_scores = [&](float *scores, hipStream_t st) { return scan_bits(h, qbits, scores, st, nullptr, planes); };
+    scan.scan_filter = [&](const TopkFilter &f, hipStream_t st) { return scan_bits(h, qbits, nullptr, st, &f, planes); };
+    scan.score_ids = [&](const uint32_t *ids, uint64_t n_ids, float *out, hipStream_t st) {
+        return words_launch(h, static_cast<const uint32_t *>(qbits), ids, n_ids, out, st, planes);
+    };
+    return fused_topk(h->count, k, largest, out_ids, out_scores, out_mem, s, scan);
+}
+
 qamd_status qamd_bin_topk(const qamd_bin *h, const qamd_bin_query *q, uint32_t k, int largest, uint32_t *out_ids,
                           float *out_scores, qamd_mem out_mem, void *stream) {
     QAMD_TRY(check_query(h, q));
@@ -1637,21 +1659,30 @@ qamd_status qamd_bin_topk(const qamd_bin *h, const qamd_bin_query *q, uint32_t k
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     QAMD_TRY(q->ready.wait(s));
-    {   // small stores: one launch, exact under any number of ties, no status read-back
-        qamd_status st = QAMD_OK;
-        if (bin_topk_small(h, q->buf.ptr, k, largest, out_ids, out_scores, out_mem, s, st, q->bits)) return st;
-    }
-    if (!fused_capable(h)) {
-        return topk_classic(h->count, k, largest, out_ids, out_scores, out_mem, s,
-                            [&](float *scores) { return scan_into(h, q, scores, s); });
-    }
-    FusedScan scan;
-    scan.scan_scores = [&](float *scores, hipStream_t st) { return scan_into(h, q, scores, st); };
-    scan.scan_filter = [&](const TopkFilter &f, hipStream_t st) { return scan_into(h, q, nullptr, st, &f); };
-    scan.score_ids = [&](const uint32_t *ids, uint64_t n_ids, float *out, hipStream_t st) {
-        return words_launch(h, q->buf.as<uint32_t>(), ids, n_ids, out, st, q->bits);
-    };
-    return fused_topk(h->count, k, largest, out_ids, out_scores, out_mem, s, scan);
+    return topk_bits(h, q->buf.ptr, q->bits, k, largest, out_ids, out_scores, out_mem, s);
+}
+
+// score_internal (:302-314) against the whole store: the metric of score_point with stored row i as the one-plane query,
+// for one-bit and two-bit rows alike.  The query pointer is row i of the image every route scans (16-byte aligned wherever
+// the 16-byte kernels run: ds % 16 == 0 there); every kernel only reads both, and reads the query within its ds bytes.
+qamd_status qamd_bin_score_internal_all(const qamd_bin *h, uint32_t i, float *out, qamd_mem out_mem, void *stream) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    if (h->count == 0) return QAMD_OK;
+    if (!out) return fail(QAMD_ERR_ARGUMENTS, "out is null");
+    if (i >= h->count) return fail(QAMD_ERR_ARGUMENTS, "row id %u out of range (count %llu)", i, (unsigned long long)h->count);
+    QAMD_ON_DEVICE(h->device);
+    return score_all_bits(h, h->rows.as<uint8_t>() + (uint64_t)i * h->ds, 1, out, out_mem, as_stream(stream));
+}
+
+qamd_status qamd_bin_topk_internal(const qamd_bin *h, uint32_t i, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
+                                   qamd_mem out_mem, void *stream) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    qamd_status args = QAMD_OK;
+    if (!topk_wanted(k, 1, out_ids, out_scores, args)) return args;
+    if (h->count && i >= h->count) return fail(QAMD_ERR_ARGUMENTS, "row id %u out of range (count %llu)", i, (unsigned long long)h->count);
+    QAMD_ON_DEVICE(h->device);
+    return topk_bits(h, h->rows.as<uint8_t>() + (uint64_t)i * h->ds, 1, k, largest, out_ids, out_scores, out_mem,
+                     as_stream(stream));
 }
 
 void qamd_bin_free(qamd_bin *h) { delete h; }

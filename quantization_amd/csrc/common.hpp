@@ -258,7 +258,7 @@ void host_query_release(hipStream_t s);
 // runtime, which is most of a top-k on a small store.  A thread that alternates between stores
 // on several GPUs keeps one workspace per (slot, device).  Freed by qamd_thread_release() or when
 // the thread exits.
-enum ThreadWsSlot { WS_SCORES = 0, WS_SELECT = 1, WS_PARTIAL = 2, WS_FUSED = 3, WS_SMALL = 4, WS_RESCORE = 5, WS_SLOTS = 6 };
+enum ThreadWsSlot { WS_SCORES = 0, WS_SELECT = 1, WS_PARTIAL = 2, WS_FUSED = 3, WS_SMALL = 4, WS_RESCORE = 5, WS_ROW_LUT = 6, WS_SLOTS = 7 };
 // `tags` (optional) points at three caller-owned words that live with the buffer and are zeroed
 // whenever it is (re)allocated: what the caller has cached inside it.
 qamd_status thread_ws_acquire(ThreadWsSlot slot, size_t bytes, hipStream_t s, void **out,

@@ -1042,6 +1042,174 @@ __global__ __launch_bounds__(kBlock) void pq_internal_pairs_kernel(const uint8_t
     }
 }
 
+// ------------------------------------------------------------------------------ score_internal against the whole store
+//   score_internal (:566-593) sums the per-chunk centroid-to-centroid metrics strictly in chunk order, one
+// running f32 - not the four SSE lane sums of the query scans above - and negates once, after the sum.
+//
+// The row LUT of stored row `row`: lut[c][code] = metric(centroids[rows[row][c]][range c], centroids[code][range c]) with
+// the sequential f32 loop of pq_internal_kernel (the last chunk may be ragged).  NOT inverted: a store whose metrics are all
+// +0 must score -0.0 under `invert`, which a pre-negated table (+0 + -0 = +0) would lose.
+__global__ __launch_bounds__(kBlock) void pq_row_lut_kernel(const uint8_t *__restrict__ rows, uint32_t row_stride, uint32_t row,
+                                                           uint32_t dim, uint32_t chunk_size, uint32_t m,
+                                                           const float *__restrict__ centroids, int distance,
+                                                           float *__restrict__ lut) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m * kCentroids) return;
+    const uint32_t c = i / kCentroids, kc = i % kCentroids;
+    const uint32_t lo = c * chunk_size, len = min(chunk_size, dim - lo);
+    const float *a = centroids + (size_t)rows[(size_t)row * row_stride + c] * dim + lo, *b = centroids + (size_t)kc * dim + lo;
+    float s = 0.0f;
+    if (distance == QAMD_DOT)
+        for (uint32_t t = 0; t < len; t++) s += a[t] * b[t];
+    else if (distance == QAMD_L1)
+        for (uint32_t t = 0; t < len; t++) s += fabsf(a[t] - b[t]);
+    else
+        for (uint32_t t = 0; t < len; t++) s += (a[t] - b[t]) * (a[t] - b[t]);
+    lut[i] = s;
+}
+
+__device__ __forceinline__ float quad_bcast_f(float v, int j) {  // j is a constant after unrolling
+    switch (j) {
+        case 0: return __uint_as_float(quad_bcast<0>(__float_as_uint(v)));
+        case 1: return __uint_as_float(quad_bcast<1>(__float_as_uint(v)));
+        case 2: return __uint_as_float(quad_bcast<2>(__float_as_uint(v)));
+        default: return __uint_as_float(quad_bcast<3>(__float_as_uint(v)));
+    }
+}
+
+// The sequential-order scan of one LUT slice: NVS 16-byte pieces of every row (pieces [piece0, piece0 + NVS) of rows on a
+// pitch of pitch_pieces; a slice of the planar image has piece0 = 0), the slice's `chunks_here` <= 16 NVS LUT rows staged in
+// LDS.  Loads and the quad are pq_scan_fast_kernel's: four adjacent lanes own a row, lane k loads pieces k, k + 4, ... and
+// the dwords go round the quad by DPP.  The gathers are split four ways as there - for chunks 4g .. 4g + 3 lane k fetches
+// chunk 4g + k's entry, one ds_read per lane - but the sum is not: the four values are broadcast through the quad
+// (quad_perm DPP operands of the adds) and EVERY lane adds them to its own copy of the row's one running sum in chunk
+// order.  So a row costs the gathers of the query scan and four times its adds, all on one dependent chain; UNROLL rows
+// per lane interleave their chains.  Chunks past chunks_here (row padding) are skipped, not added: only the slice's last
+// piece can hold some (16 (NVS - 1) < chunks_here <= 16 NVS), so only its adds are guarded (wave-uniform branches).
+// first / last: a row of several slices parks its one partial sum (4 bytes) in `partial` between launches.
+template <int NVS, int UNROLL, bool FILTER>
+__global__ __launch_bounds__(kScanBlock) void pq_scan_seq_kernel(const uint4 *__restrict__ rows4, uint32_t pitch_pieces,
+                                                                uint32_t piece0, const float *__restrict__ lut_g,
+                                                                uint32_t chunks_here, int first, int last, int invert,
+                                                                float *__restrict__ partial, uint32_t n_rows,
+                                                                float *__restrict__ out, TopkFilter filt) {
+    extern __shared__ __attribute__((aligned(16))) float lut_s[];
+    {
+        const uint32_t total4 = chunks_here * (kCentroids / 4);
+        const float4 *src = reinterpret_cast<const float4 *>(lut_g);
+        float4 *dst = reinterpret_cast<float4 *>(lut_s);
+        for (uint32_t i = threadIdx.x; i < total4; i += kScanBlock) dst[i] = src[i];
+        __syncthreads();
+    }
+    constexpr int JN = (NVS + 3) / 4;
+    constexpr int TILE = 16 * UNROLL;
+    const int lane = threadIdx.x & 63;
+    const int k = lane & 3, rslot = lane >> 2;
+    const uint64_t wave = (uint64_t)blockIdx.x * (kScanBlock / 64) + (threadIdx.x >> 6);
+    const uint64_t n_waves = (uint64_t)gridDim.x * (kScanBlock / 64);
+    const uint32_t shift = 8 * k;
+    uint32_t pivot = 0;
+    if (FILTER) pivot = *filt.pivot_key;
+    for (uint64_t base = wave * TILE; base < n_rows; base += n_waves * TILE) {
+        uint4 mine[UNROLL][JN];
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+            const uint4 *p = rows4 + (base + u * 16 + rslot) * pitch_pieces + piece0;  // rows are zero-padded past the store
+#pragma unroll
+            for (int j = 0; j < JN; j++) {
+                const int piece = k + 4 * j;
+                mine[u][j] = ld_nt(p + (piece < NVS ? piece : NVS - 1));
+            }
+        }
+        float acc[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+            const uint64_t row = base + u * 16 + rslot;
+            acc[u] = (first || row >= n_rows) ? 0.0f : partial[row];
+        }
+        // Step st = 4 pc + d takes chunks 16 pc + 4 d .. + 3 of the held rows: lane k gathers chunk 16 pc + 4 d + k's entry
+        // (gather), then the quad adds the four values in chunk order (adds).  A step of the last piece, which may hold
+        // padding, skips the chunks past chunks_here; their lanes read the slice's last table, unused.
+        // The gathers of step st + 1 are issued before the adds of step st, and the scheduler is held to that: left
+        // alone it hoists every gather of the row above the first add and spills (2 KiB of scratch per lane at NVS = 9).
+        // (`st` is a constant once the loop below is unrolled.)
+        auto gather = [&](int st, float (&g)[UNROLL]) {
+            const int pc = st / 4, d = st % 4;
+            const bool whole = pc < NVS - 1;
+            const uint32_t cmine = (uint32_t)(4 * st) + k;
+            const float *l = lut_s + (size_t)((whole || cmine < chunks_here) ? cmine : chunks_here - 1) * kCentroids;
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) {
+                const uint4 &held = mine[u][pc / 4];
+                const uint32_t dw = d == 0 ? held.x : d == 1 ? held.y : d == 2 ? held.z : held.w;
+                const uint32_t w = (pc & 3) == 0 ? quad_bcast<0>(dw) : (pc & 3) == 1 ? quad_bcast<1>(dw)
+                                 : (pc & 3) == 2 ? quad_bcast<2>(dw) : quad_bcast<3>(dw);
+                g[u] = l[(w >> shift) & 255u];
+            }
+        };
+        auto adds = [&](int st, const float (&g)[UNROLL]) {
+            const bool whole = st / 4 < NVS - 1;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (whole || (uint32_t)(4 * st + j) < chunks_here) {  // wave-uniform
+#pragma unroll
+                    for (int u = 0; u < UNROLL; u++) acc[u] += quad_bcast_f(g[u], j);
+                }
+            }
+        };
+        float g[UNROLL], gn[UNROLL];
+        gather(0, g);
+#pragma unroll
+        for (int st = 0; st < 4 * NVS; st++) {
+            if (st + 1 < 4 * NVS) gather(st + 1, gn);
+            __builtin_amdgcn_sched_barrier(0);
+            adds(st, g);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < UNROLL; u++) g[u] = gn[u];
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) {
+            const uint64_t row = base + u * 16 + rslot;
+            if (k != 0 || row >= n_rows) continue;
+            if (!last) {
+                partial[row] = acc[u];
+                continue;
+            }
+            const float sc = invert ? -acc[u] : acc[u];
+            if (FILTER) topk_offer(filt, pivot, sc, (uint32_t)row);
+            else out[row] = sc;
+        }
+    }
+}
+
+// The same sum with a row per lane and the LUT read through L1 / L2, any m in one launch: the form for stores of fewer
+// than 4096 rows (staging up to 144 KiB per CU is not worth it there, as in scan_launch) and for rows of fewer than 16
+// chunks, which are not 16-byte pieces (there the LUT, at most 15 KiB, is staged when STAGE).
+template <bool STAGE>
+__global__ __launch_bounds__(kBlock) void pq_scan_seq_rows_kernel(const uint32_t *__restrict__ rows32, uint32_t row_words,
+                                                                 const float *__restrict__ lut_g, uint32_t m, int invert,
+                                                                 uint32_t n_rows, float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float lut_s[];
+    const float *lut = lut_g;
+    if (STAGE) {
+        for (uint32_t i = threadIdx.x; i < m * kCentroids; i += kBlock) lut_s[i] = lut_g[i];
+        __syncthreads();
+        lut = lut_s;
+    }
+    for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < n_rows; row += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t *p = rows32 + row * row_words;
+        float total = 0.0f;
+        for (uint32_t c = 0; c < m; c += 4) {
+            const uint32_t w = p[c >> 2];
+#pragma unroll
+            for (uint32_t b = 0; b < 4; b++)
+                if (c + b < m) total += lut[(size_t)(c + b) * kCentroids + ((w >> (8 * b)) & 255u)];
+        }
+        out[row] = invert ? -total : total;
+    }
+}
+
 // Reference rows (stride m) <-> device rows (stride round_up(m,4)).
 __global__ __launch_bounds__(kBlock) void pq_restride_kernel(const uint8_t *__restrict__ src, uint32_t src_stride,
                                                             uint8_t *__restrict__ dst, uint32_t dst_stride,
@@ -2160,6 +2328,8 @@ qamd_status qamd_pq_score_point(const qamd_pq *h, const qamd_pq_query *q, uint32
     return qamd_pq_score_ids(h, q, &i, 1, QAMD_MEM_HOST, out, QAMD_MEM_HOST, nullptr);
 }
 
+}  // extern "C"
+
 namespace {
 qamd_status internal_pairs_launch(const qamd_pq *h, uint32_t single_row, const uint32_t *lists, uint32_t n_lists,
                                   const uint32_t *list_rows, const uint32_t *ids_dev, uint64_t n, float *out_dev,
@@ -2173,7 +2343,102 @@ qamd_status internal_pairs_launch(const qamd_pq *h, uint32_t single_row, const u
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
 }
+
+// ---- score_internal against the whole store: the row LUT and the sequential-order scans ----
+bool seq_quad_capable(const qamd_pq *h) { return h->count >= 4096 && h->m >= 16; }  // else: pq_scan_seq_rows_kernel
+
+// The row LUT of stored row i (m x 256 f32, chunk-major, not inverted) into the calling thread's WS_ROW_LUT workspace;
+// the caller releases it.
+qamd_status row_lut_build(const qamd_pq *h, uint32_t i, hipStream_t s, float **lut) {
+    const size_t n = (size_t)h->m * kCentroids;
+    QAMD_TRY(thread_ws_acquire(WS_ROW_LUT, n * sizeof(float), s, reinterpret_cast<void **>(lut)));
+    hipLaunchKernelGGL(pq_row_lut_kernel, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, h->rows.as<uint8_t>(),
+                       (uint32_t)h->ds, i, (uint32_t)h->vp.dim, (uint32_t)h->chunk_size, (uint32_t)h->m,
+                       h->centroids.as<float>(), h->vp.distance_type, *lut);
+    if (hipGetLastError() != hipSuccess) {
+        thread_ws_release(WS_ROW_LUT, s);
+        return fail(QAMD_ERR_DEVICE, "pq_row_lut_kernel did not launch");
+    }
+    return QAMD_OK;
+}
+
+template <bool FILTER>
+qamd_status seq_launch_quad(const qamd_pq *h, const float *lut, float *out_dev, const TopkFilter *filt, hipStream_t s) {
+    const uint32_t m = (uint32_t)h->m, n = (uint32_t)h->count;
+    // the slices: the planar image's where the store has one (each a contiguous array of whole pieces), else pieces of
+    // the row-major image as launch_fast cuts them (one slice up to 144 chunks, line-sized ones beyond)
+    struct Slice {
+        const uint4 *rows4;
+        uint32_t pitch, piece0, chunk0, chunks;
+    };
+    std::vector<Slice> slices;
+    if (h->planar.ptr) {
+        for (size_t sl = 0; sl < h->slice_chunks.size(); sl++)
+            slices.push_back({reinterpret_cast<const uint4 *>(h->planar.as<uint8_t>() + (uint64_t)h->slice_chunk0[sl] * h->padded),
+                              h->slice_chunks[sl] / 16, 0u, h->slice_chunk0[sl], h->slice_chunks[sl]});
+    } else {
+        const uint32_t pieces = (uint32_t)valid_pieces(m), per = pieces <= kMaxSlicePieces ? pieces : kSlicePiecesAligned;
+        for (uint32_t p0 = 0; p0 < pieces; p0 += per)
+            slices.push_back({h->rows.as<uint4>(), (uint32_t)(h->ds / 16), p0, p0 * 16, std::min(per * 16, m - p0 * 16)});
+    }
+    float *partial = nullptr;
+    if (slices.size() > 1) QAMD_TRY(thread_ws_acquire(WS_PARTIAL, (size_t)n * 4, s, reinterpret_cast<void **>(&partial)));
+    const int grid = (int)std::min<uint64_t>(device_info().cu_count, ((uint64_t)n + 1023) / 1024);
+    qamd_status st = QAMD_OK;
+    for (size_t sl = 0; sl < slices.size() && st == QAMD_OK; sl++) {
+        const Slice &c = slices[sl];
+        const int first = sl == 0, last = sl + 1 == slices.size();
+        st = [&]() -> qamd_status {
+#define QAMD_PQ_SEQ(NVV, UN)                                                                                          \
+    case NVV: {                                                                                                       \
+        QAMD_LDS_OPT_IN((&pq_scan_seq_kernel<NVV, UN, FILTER>), kLdsBudget);                                          \
+        hipLaunchKernelGGL((pq_scan_seq_kernel<NVV, UN, FILTER>), dim3(grid), dim3(kScanBlock),                       \
+                           (size_t)c.chunks * kCentroids * sizeof(float), s, c.rows4, c.pitch, c.piece0,              \
+                           lut + (size_t)c.chunk0 * kCentroids, c.chunks, first, last, h->vp.invert, partial, n, out_dev, \
+                           filt ? *filt : TopkFilter{});                                                              \
+        break;                                                                                                        \
+    }
+            switch ((c.chunks + 15) / 16) {
+                QAMD_PQ_SEQ(1, 4) QAMD_PQ_SEQ(2, 4) QAMD_PQ_SEQ(3, 4) QAMD_PQ_SEQ(4, 4) QAMD_PQ_SEQ(5, 4)
+                QAMD_PQ_SEQ(6, 4) QAMD_PQ_SEQ(7, 4) QAMD_PQ_SEQ(8, 4)
+                QAMD_PQ_SEQ(9, 2)  // (the third held piece of four rows per lane does not fit 128 registers)
+                default: return fail(QAMD_ERR_ARGUMENTS, "no sequential scan for a slice of %u chunks", c.chunks);
+            }
+#undef QAMD_PQ_SEQ
+            QAMD_HIP(hipGetLastError());
+            return QAMD_OK;
+        }();
+    }
+    if (partial) thread_ws_release(WS_PARTIAL, s);
+    return st;
+}
+
+// out_dev[j] = score_internal(i, j) for every row j, given row i's LUT.
+qamd_status seq_scan(const qamd_pq *h, const float *lut, float *out_dev, hipStream_t s, const TopkFilter *filt = nullptr) {
+    if (h->count == 0) return QAMD_OK;
+    if (seq_quad_capable(h)) return filt ? seq_launch_quad<true>(h, lut, nullptr, filt, s) : seq_launch_quad<false>(h, lut, out_dev, nullptr, s);
+    if (filt) return fail(QAMD_ERR_ARGUMENTS, "no filtering scan for this store");
+    const uint32_t m = (uint32_t)h->m, n = (uint32_t)h->count;
+    const bool stage = m < 16 && n >= 4096;
+    const int grid = (int)std::min<uint64_t>((uint64_t)device_info().cu_count * 8, ((uint64_t)n + kBlock - 1) / kBlock);
+    if (stage)
+        hipLaunchKernelGGL(pq_scan_seq_rows_kernel<true>, dim3(grid), dim3(kBlock), (size_t)m * kCentroids * sizeof(float), s,
+                           h->rows.as<uint32_t>(), (uint32_t)(h->ds / 4), lut, m, h->vp.invert, n, out_dev);
+    else
+        hipLaunchKernelGGL(pq_scan_seq_rows_kernel<false>, dim3(grid), dim3(kBlock), 0, s, h->rows.as<uint32_t>(),
+                           (uint32_t)(h->ds / 4), lut, m, h->vp.invert, n, out_dev);
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
+
+qamd_status check_internal(const qamd_pq *h) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    if (h->centroids_host.empty() || h->m == 0) return fail(QAMD_ERR_ARGUMENTS, "the store has no centroids to score with");
+    return QAMD_OK;
+}
 }  // namespace
+
+extern "C" {
 
 // score_internal (:566-593) for one stored row against many: out[k] = score_internal(i, ids[k]).
 qamd_status qamd_pq_score_internal_ids(const qamd_pq *h, uint32_t i, const uint32_t *ids, uint64_t n_ids,
@@ -2247,6 +2512,54 @@ qamd_status qamd_pq_topk(const qamd_pq *h, const qamd_pq_query *q, uint32_t k, i
         return scan_launch(h, lut, ids, n_ids, out, st);
     };
     return fused_topk(h->count, k, largest, out_ids, out_scores, out_mem, s, scan);
+}
+
+// score_internal (:566-593) against the whole store: row i's LUT, then the sequential-order scan.
+qamd_status qamd_pq_score_internal_all(const qamd_pq *h, uint32_t i, float *out, qamd_mem out_mem, void *stream) {
+    QAMD_TRY(check_internal(h));
+    if (h->count == 0) return QAMD_OK;
+    if (!out) return fail(QAMD_ERR_ARGUMENTS, "out is null");
+    if (i >= h->count) return fail(QAMD_ERR_ARGUMENTS, "row id %u out of range (count %llu)", i, (unsigned long long)h->count);
+    QAMD_ON_DEVICE(h->device);
+    hipStream_t s = as_stream(stream);
+    float *lut = nullptr;
+    QAMD_TRY(row_lut_build(h, i, s, &lut));
+    qamd_status st;
+    if (out_mem == QAMD_MEM_DEVICE) st = seq_scan(h, lut, out, s);
+    else st = score_all_to_host(h->count, out, s, [&](float *scores) { return seq_scan(h, lut, scores, s); });
+    thread_ws_release(WS_ROW_LUT, s);
+    return st;
+}
+
+// Stores the quad kernel serves take the fused selection: sample pass = the pair kernel (score_internal's bits already),
+// FILTER scan, sort.  Every other store (fewer than 4096 rows, rows of fewer than 16 chunks) takes the classic one: LUT,
+// one scan, exact select - three launches where a query has one, for a call that is not made per search hop.
+qamd_status qamd_pq_topk_internal(const qamd_pq *h, uint32_t i, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
+                                  qamd_mem out_mem, void *stream) {
+    QAMD_TRY(check_internal(h));
+    qamd_status args = QAMD_OK;
+    if (!topk_wanted(k, 1, out_ids, out_scores, args)) return args;
+    if (h->count && i >= h->count)
+        return fail(QAMD_ERR_ARGUMENTS, "row id %u out of range (count %llu)", i, (unsigned long long)h->count);
+    QAMD_ON_DEVICE(h->device);
+    hipStream_t s = as_stream(stream);
+    float *lut = nullptr;
+    QAMD_TRY(row_lut_build(h, h->count ? i : 0, s, &lut));
+    qamd_status st;
+    if (!seq_quad_capable(h)) {
+        st = topk_classic(h->count, k, largest, out_ids, out_scores, out_mem, s,
+                          [&](float *scores) { return seq_scan(h, lut, scores, s); });
+    } else {
+        FusedScan scan;
+        scan.scan_scores = [&](float *scores, hipStream_t t) { return seq_scan(h, lut, scores, t); };
+        scan.scan_filter = [&](const TopkFilter &f, hipStream_t t) { return seq_scan(h, lut, nullptr, t, &f); };
+        scan.score_ids = [&](const uint32_t *ids, uint64_t n_ids, float *out, hipStream_t t) {
+            return internal_pairs_launch(h, i, nullptr, 0, nullptr, ids, n_ids, out, t);
+        };
+        st = fused_topk(h->count, k, largest, out_ids, out_scores, out_mem, s, scan);
+    }
+    thread_ws_release(WS_ROW_LUT, s);
+    return st;
 }
 
 void qamd_pq_free(qamd_pq *h) { delete h; }

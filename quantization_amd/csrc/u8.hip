@@ -176,11 +176,14 @@ __device__ __forceinline__ uint32_t f32x4_to_u8x4_fast(const float4 &f, float al
 // unconditional (clamped address + select) so that they still issue back to back.
 // FILTER: fused top-k mode — no score is written; rows at least as good as the pivot are
 // appended to the candidate buffer (topk_device.hpp).
-template <int G, int ITERS, int UNROLL, bool IS_L1, bool EXACT, bool FILTER>
+// EPI (every whole-store kernel below has it): EPI_POINT scores an encoded query; EPI_INTERNAL is score_internal against
+// the whole store - the "query" is a stored row (qcodes / q_off_p point into codes / offsets, which are only
+// read) and the epilogue takes `diff`.  A compile-time switch: the EPI_POINT code never sees `diff`.
+template <int G, int ITERS, int UNROLL, bool IS_L1, bool EXACT, bool FILTER, int EPI = EPI_POINT>
 __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
     const uint4 *__restrict__ codes, const float *__restrict__ offsets,
     const uint4 *__restrict__ qcodes, const float *__restrict__ q_off_p, float multiplier,
-    uint32_t n_rows, uint32_t row_chunks, float *__restrict__ out, TopkFilter filt) {
+    uint32_t n_rows, uint32_t row_chunks, float *__restrict__ out, TopkFilter filt, float diff) {
     constexpr int RW = 64 / G;
     constexpr int TILE = RW * UNROLL;
     const int lane = threadIdx.x & 63;
@@ -239,7 +242,7 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
 #pragma unroll
         for (int it = 0; it < ITERS; it++) acc = IS_L1 ? sad16(v[u][it], q[it], acc) : dot16(v[u][it], q[it], acc);
         acc = group_sum<G>(acc);
-        if (sub == (u % G)) mine = epilogue(multiplier, acc, q_off, v_off[u / G], 0.0f, EPI_POINT);
+        if (sub == (u % G)) mine = epilogue(multiplier, acc, q_off, v_off[u / G], EPI == EPI_POINT ? 0.0f : diff, EPI);
         if ((u % G) == G - 1 || u == UNROLL - 1) {
             constexpr int dummy = 0;
             (void)dummy;
@@ -276,11 +279,11 @@ constexpr uint32_t kPackBlockChunk = kPackBlockRows;  // uint4 between two chunk
 
 __device__ __forceinline__ uint4 and16(const uint4 &v, uint32_t m) { return make_uint4(v.x & m, v.y & m, v.z & m, v.w & m); }
 
-template <bool FILTER>
+template <bool FILTER, int EPI = EPI_POINT>
 __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void u8_scan_blocked_kernel(
     const uint4 *__restrict__ image, const float *__restrict__ offsets, const uint4 *__restrict__ qcodes,
     const float *__restrict__ q_off_p, float multiplier, uint32_t n_rows, uint32_t pchunks, uint32_t n_extra,
-    uint32_t split, float *__restrict__ out, TopkFilter filt) {
+    uint32_t split, float *__restrict__ out, TopkFilter filt, float diff) {
     __shared__ uint32_t partial[kScanBlock];
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -346,7 +349,7 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8
             for (uint32_t p = 1; p < split; p++) acc += partial[threadIdx.x + 64 * p];
     }
     if (part == 0 && row < n_rows) {
-        const float score = epilogue(multiplier, acc, q_off, v_off, 0.0f, EPI_POINT);
+        const float score = epilogue(multiplier, acc, q_off, v_off, EPI == EPI_POINT ? 0.0f : diff, EPI);
         if (FILTER) topk_offer(filt, pivot, score, (uint32_t)row);
         else __builtin_nontemporal_store(score, out + row);
     }
@@ -440,11 +443,11 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_multi_kernel(
 // workgroup / last-arriver merges of topk_device.hpp keep the best k.  100k x 768: one launch
 // replaces the sample / pivot / filtering-scan / sort chain (66 us).
 // The body, given the query's pieces in registers (q) and its offset:
-template <int G, int ITERS, bool IS_L1, bool EXACT>
+template <int G, int ITERS, bool IS_L1, bool EXACT, int EPI = EPI_POINT>
 __device__ __forceinline__ void u8_topk_small_body(const uint4 *__restrict__ codes, const float *__restrict__ offsets,
                                                    const uint4 (&q)[ITERS], float q_off, float multiplier, uint32_t n_rows,
                                                    uint32_t row_chunks, uint32_t rows_per_wg, const SmallTopk &p,
-                                                   unsigned long long (*lds)[64]) {
+                                                   unsigned long long (*lds)[64], float diff = 0.0f) {
     unsigned long long(*lists)[64] = lds;
     constexpr int RW = 64 / G;
     constexpr int UNROLL = 2;
@@ -480,7 +483,7 @@ __device__ __forceinline__ void u8_topk_small_body(const uint4 *__restrict__ cod
             if (sub == 0) {
                 unsigned long long key = ~0ull;
                 if (local < rows_per_wg && row < n_rows) {
-                    const float sc = epilogue(multiplier, acc, q_off, offsets[row], 0.0f, EPI_POINT);
+                    const float sc = epilogue(multiplier, acc, q_off, offsets[row], EPI == EPI_POINT ? 0.0f : diff, EPI);
                     key = ((unsigned long long)topk_ordered_bits(sc, p.largest != 0) << 32) | (uint32_t)row;
                 }
                 stage[acc_list.fill + rslot] = key;
@@ -493,11 +496,11 @@ __device__ __forceinline__ void u8_topk_small_body(const uint4 *__restrict__ cod
     small_topk_finish(acc_list.best, lists, p);
 }
 
-template <int G, int ITERS, bool IS_L1, bool EXACT>
+template <int G, int ITERS, bool IS_L1, bool EXACT, int EPI = EPI_POINT>
 __global__ __launch_bounds__(1024) void u8_topk_small_kernel(
     const uint4 *__restrict__ codes, const float *__restrict__ offsets, const uint4 *__restrict__ qcodes,
     const float *__restrict__ q_off_p, float multiplier, uint32_t n_rows, uint32_t row_chunks, uint32_t rows_per_wg,
-    SmallTopk p) {
+    SmallTopk p, float diff) {
     __shared__ unsigned long long lds[2 * kSmallTopkWaves][64];  // [0, 16): tournament lists, [16, 32): staging rows
     const int lane = threadIdx.x & 63, sub = lane % G;
     uint4 q[ITERS];
@@ -508,7 +511,8 @@ __global__ __launch_bounds__(1024) void u8_topk_small_kernel(
         const bool in = EXACT || c < row_chunks;
         q[it] = make_uint4(in ? t.x : 0, in ? t.y : 0, in ? t.z : 0, in ? t.w : 0);
     }
-    u8_topk_small_body<G, ITERS, IS_L1, EXACT>(codes, offsets, q, *q_off_p, multiplier, n_rows, row_chunks, rows_per_wg, p, lds);
+    u8_topk_small_body<G, ITERS, IS_L1, EXACT, EPI>(codes, offsets, q, *q_off_p, multiplier, n_rows, row_chunks, rows_per_wg, p,
+                                                    lds, diff);
 }
 
 // encode_query FOLDED INTO the single-launch top-k: one launch per search on a small store.  The f32
@@ -585,11 +589,11 @@ __global__ __launch_bounds__(1024) void u8_topk_small_fused_kernel(
 }
 
 // Generic dims (row_chunks > 16*8): runtime chunk loop, query re-read through L1/L2.
-template <bool IS_L1>
+template <bool IS_L1, int EPI = EPI_POINT>
 __global__ __launch_bounds__(kBlock) void u8_scan_generic_kernel(
     const uint4 *__restrict__ codes, const float *__restrict__ offsets,
     const uint4 *__restrict__ qcodes, const float *__restrict__ q_off_p, float multiplier,
-    uint32_t n_rows, uint32_t row_chunks, float *__restrict__ out) {
+    uint32_t n_rows, uint32_t row_chunks, float *__restrict__ out, float diff) {
     constexpr int G = 16, RW = 4;
     const int lane = threadIdx.x & 63;
     const int sub = lane % G, rslot = lane / G;
@@ -607,16 +611,16 @@ __global__ __launch_bounds__(kBlock) void u8_scan_generic_kernel(
         }
         acc = group_sum<G>(acc);
         if (sub == 0 && row < n_rows)
-            out[row] = epilogue(multiplier, acc, q_off, offsets[row], 0.0f, EPI_POINT);
+            out[row] = epilogue(multiplier, acc, q_off, offsets[row], EPI == EPI_POINT ? 0.0f : diff, EPI);
     }
 }
 
-// Lane mode 1 scan (any dim): dot16_lanes / avx2_lane_sum, the scan's EPI_POINT epilogue.
-template <bool DUMMY>
+// Lane mode 1 scan (any dim): dot16_lanes / avx2_lane_sum, the scan's epilogue on that f32 sum.
+template <bool DUMMY, int EPI = EPI_POINT>
 __global__ __launch_bounds__(kBlock) void u8_scan_avx2_lanes_kernel(
     const uint4 *__restrict__ codes, const float *__restrict__ offsets,
     const uint4 *__restrict__ qcodes, const float *__restrict__ q_off_p, float multiplier,
-    uint32_t n_rows, uint32_t row_chunks, float *__restrict__ out) {
+    uint32_t n_rows, uint32_t row_chunks, float *__restrict__ out, float diff) {
     constexpr int G = 16, RW = 4;
     const int lane = threadIdx.x & 63;
     const int sub = lane % G, rslot = lane / G;
@@ -629,7 +633,8 @@ __global__ __launch_bounds__(kBlock) void u8_scan_avx2_lanes_kernel(
         uint32_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (uint32_t c = sub; c < row_chunks; c += G) dot16_lanes(ld_nt(p + c), qcodes[c], acc);
         const float s = avx2_lane_sum<G>(acc);
-        if (sub == 0 && row < n_rows) out[row] = epilogue_f(multiplier, s, q_off, offsets[row], 0.0f, EPI_POINT);
+        if (sub == 0 && row < n_rows)
+            out[row] = epilogue_f(multiplier, s, q_off, offsets[row], EPI == EPI_POINT ? 0.0f : diff, EPI);
     }
 }
 
@@ -1252,17 +1257,30 @@ qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
     return QAMD_OK;
 }
 
+// The epilogue of a whole-store launch: an encoded query (EPI_POINT, the default) or, for score_internal against the whole
+// store, a stored row with score_internal's `diff` (internal_epi).
+struct ScanEpi {
+    float diff = 0.0f;
+    int mode = EPI_POINT;
+};
+
 template <bool IS_L1> struct ScanLaunch {
     template <int G, int ITERS, int UNROLL>
-    static void go(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt, hipStream_t s) {
+    static void go(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt, hipStream_t s,
+                   const ScanEpi &e) {
         constexpr int TILE = (64 / G) * UNROLL;
         const uint64_t waves = (h->count + TILE - 1) / TILE;  // one wave per tile
         const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
         const bool exact = h->row_chunks == (uint32_t)(G * ITERS);
-#define QAMD_U8_GO(EX, FI)                                                                                     \
-    hipLaunchKernelGGL((u8_scan_kernel<G, ITERS, UNROLL, IS_L1, EX, FI>), dim3(grid), dim3(kScanBlock), 0, s,    \
+#define QAMD_U8_GO_AS(EX, FI, EPI)                                                                              \
+    hipLaunchKernelGGL((u8_scan_kernel<G, ITERS, UNROLL, IS_L1, EX, FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, \
                        h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)h->count, \
-                       h->row_chunks, out, filt ? *filt : TopkFilter{})
+                       h->row_chunks, out, filt ? *filt : TopkFilter{}, e.diff)
+#define QAMD_U8_GO(EX, FI)                               \
+    do {                                                 \
+        if (e.mode == EPI_POINT) QAMD_U8_GO_AS(EX, FI, EPI_POINT); \
+        else QAMD_U8_GO_AS(EX, FI, EPI_INTERNAL);        \
+    } while (0)
         if (filt) {
             if (exact) QAMD_U8_GO(true, true);
             else QAMD_U8_GO(false, true);
@@ -1271,6 +1289,7 @@ template <bool IS_L1> struct ScanLaunch {
             else QAMD_U8_GO(false, false);
         }
 #undef QAMD_U8_GO
+#undef QAMD_U8_GO_AS
     }
 };
 
@@ -1286,61 +1305,71 @@ uint32_t blocked_split(uint64_t count) {
 
 // The Dot / L2 scan of a store that has a packed image: u8_scan_blocked_kernel over its blocks.
 void launch_scan_blocked(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
-                         hipStream_t s) {
+                         hipStream_t s, const ScanEpi &e) {
     const uint32_t split = blocked_split(h->count), blocks_per_wg = (kScanBlock / 64) / split;
     const uint64_t blocks = (h->count + kPackBlockRows - 1) / kPackBlockRows;
     const unsigned grid = (unsigned)((blocks + blocks_per_wg - 1) / blocks_per_wg);
     h->last_scan_split.store((int)split, std::memory_order_relaxed);
-#define QAMD_U8_BLOCKED(FI)                                                                                          \
-    hipLaunchKernelGGL((u8_scan_blocked_kernel<FI>), dim3(grid), dim3(kScanBlock), 0, s, h->packed.as<uint4>(),       \
+#define QAMD_U8_BLOCKED_AS(FI, EPI)                                                                                  \
+    hipLaunchKernelGGL((u8_scan_blocked_kernel<FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, h->packed.as<uint4>(),  \
                        h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)h->count, h->packed_chunks,      \
-                       h->row_chunks - h->packed_chunks, split, out, filt ? *filt : TopkFilter{})
+                       h->row_chunks - h->packed_chunks, split, out, filt ? *filt : TopkFilter{}, e.diff)
+#define QAMD_U8_BLOCKED(FI)                                      \
+    do {                                                         \
+        if (e.mode == EPI_POINT) QAMD_U8_BLOCKED_AS(FI, EPI_POINT); \
+        else QAMD_U8_BLOCKED_AS(FI, EPI_INTERNAL);               \
+    } while (0)
     if (filt) QAMD_U8_BLOCKED(true);
     else QAMD_U8_BLOCKED(false);
 #undef QAMD_U8_BLOCKED
+#undef QAMD_U8_BLOCKED_AS
 }
 
 // Returns false when the store's row size has no templated kernel (caller uses the generic one).
 // The Dot / L2 scans read the packed image when the store has one (its rows are 7/8 as long).
 template <bool IS_L1>
 bool launch_scan(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
-                 hipStream_t s) {
+                 hipStream_t s, const ScanEpi &e) {
     using L = ScanLaunch<IS_L1>;
     const bool packed = !IS_L1 && h->packed_chunks != 0;
     h->last_scan_packed.store(packed ? 1 : 0, std::memory_order_relaxed);
-    if (packed) return launch_scan_blocked(h, qc, qo, out, filt, s), true;
+    if (packed) return launch_scan_blocked(h, qc, qo, out, filt, s, e), true;
     const uint32_t rc = h->row_chunks;
-    if (rc == 1) return L::template go<1, 1, 4>(h, qc, qo, out, filt, s), true;
-    if (rc == 2) return L::template go<2, 1, 4>(h, qc, qo, out, filt, s), true;
-    if (rc <= 4) return L::template go<4, 1, 8>(h, qc, qo, out, filt, s), true;
-    if (rc <= 8) return L::template go<8, 1, 8>(h, qc, qo, out, filt, s), true;
+    if (rc == 1) return L::template go<1, 1, 4>(h, qc, qo, out, filt, s, e), true;
+    if (rc == 2) return L::template go<2, 1, 4>(h, qc, qo, out, filt, s, e), true;
+    if (rc <= 4) return L::template go<4, 1, 8>(h, qc, qo, out, filt, s, e), true;
+    if (rc <= 8) return L::template go<8, 1, 8>(h, qc, qo, out, filt, s, e), true;
     switch ((rc + 15) / 16) {
-        case 1: return L::template go<16, 1, 8>(h, qc, qo, out, filt, s), true;
-        case 2: return L::template go<16, 2, 4>(h, qc, qo, out, filt, s), true;
-        case 3: return L::template go<16, 3, 4>(h, qc, qo, out, filt, s), true;
-        case 4: return L::template go<16, 4, 2>(h, qc, qo, out, filt, s), true;
-        case 5: return L::template go<16, 5, 2>(h, qc, qo, out, filt, s), true;
-        case 6: return L::template go<16, 6, 2>(h, qc, qo, out, filt, s), true;
-        case 7: return L::template go<16, 7, 2>(h, qc, qo, out, filt, s), true;
-        case 8: return L::template go<16, 8, 2>(h, qc, qo, out, filt, s), true;
+        case 1: return L::template go<16, 1, 8>(h, qc, qo, out, filt, s, e), true;
+        case 2: return L::template go<16, 2, 4>(h, qc, qo, out, filt, s, e), true;
+        case 3: return L::template go<16, 3, 4>(h, qc, qo, out, filt, s, e), true;
+        case 4: return L::template go<16, 4, 2>(h, qc, qo, out, filt, s, e), true;
+        case 5: return L::template go<16, 5, 2>(h, qc, qo, out, filt, s, e), true;
+        case 6: return L::template go<16, 6, 2>(h, qc, qo, out, filt, s, e), true;
+        case 7: return L::template go<16, 7, 2>(h, qc, qo, out, filt, s, e), true;
+        case 8: return L::template go<16, 8, 2>(h, qc, qo, out, filt, s, e), true;
         default: break;
     }
     return false;
 }
 
 template <bool IS_L1>
-void launch_scan_generic(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, hipStream_t s) {
+void launch_scan_generic(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, hipStream_t s, const ScanEpi &e) {
     uint64_t waves = (h->count + 3) / 4;  // one wave per 4-row tile (non-persistent, see u8_scan_kernel)
     unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
-    hipLaunchKernelGGL((u8_scan_generic_kernel<IS_L1>), dim3(grid), dim3(kBlock), 0, s,
-                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,
-                       (uint32_t)h->count, h->row_chunks, out);
+#define QAMD_U8_GENERIC(EPI)                                                                             \
+    hipLaunchKernelGGL((u8_scan_generic_kernel<IS_L1, EPI>), dim3(grid), dim3(kBlock), 0, s,             \
+                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,         \
+                       (uint32_t)h->count, h->row_chunks, out, e.diff)
+    if (e.mode == EPI_POINT) QAMD_U8_GENERIC(EPI_POINT);
+    else QAMD_U8_GENERIC(EPI_INTERNAL);
+#undef QAMD_U8_GENERIC
 }
 
 template <bool IS_L1> struct SmallLaunch {
     template <int G, int ITERS>
     static qamd_status go(const qamd_u8 *h, const uint4 *qc, const float *qo, const FusedQuery *fq, const SmallTopkPlan &pl,
-                          const SmallTopk &p, hipStream_t s) {
+                          const SmallTopk &p, hipStream_t s, const ScanEpi &e) {
         const bool exact = h->row_chunks == (uint32_t)(G * ITERS);
         if constexpr (G * ITERS * 16 > (int)kFusedQueryDims + 15 * 16) {
             if (fq) return fail(QAMD_ERR_ARGUMENTS, "fused query does not fit the kernel arguments");
@@ -1359,13 +1388,19 @@ template <bool IS_L1> struct SmallLaunch {
             QAMD_HIP(hipGetLastError());
             return QAMD_OK;
         }
-#define QAMD_U8_SMALL(EX)                                                                                       \
-    hipLaunchKernelGGL((u8_topk_small_kernel<G, ITERS, IS_L1, EX>), dim3(pl.workgroups), dim3(1024), 0, s,       \
+#define QAMD_U8_SMALL_AS(EX, EPI)                                                                               \
+    hipLaunchKernelGGL((u8_topk_small_kernel<G, ITERS, IS_L1, EX, EPI>), dim3(pl.workgroups), dim3(1024), 0, s,  \
                        h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)h->count, \
-                       h->row_chunks, pl.rows_per_wg, p)
+                       h->row_chunks, pl.rows_per_wg, p, e.diff)
+#define QAMD_U8_SMALL(EX)                                        \
+    do {                                                         \
+        if (e.mode == EPI_POINT) QAMD_U8_SMALL_AS(EX, EPI_POINT); \
+        else QAMD_U8_SMALL_AS(EX, EPI_INTERNAL);                 \
+    } while (0)
         if (exact) QAMD_U8_SMALL(true);
         else QAMD_U8_SMALL(false);
 #undef QAMD_U8_SMALL
+#undef QAMD_U8_SMALL_AS
         QAMD_HIP(hipGetLastError());
         return QAMD_OK;
     }
@@ -1376,23 +1411,23 @@ int small_group(uint32_t rc) { return rc == 1 ? 1 : rc == 2 ? 2 : rc <= 4 ? 4 : 
 
 template <bool IS_L1>
 qamd_status launch_small(const qamd_u8 *h, const uint4 *qc, const float *qo, const FusedQuery *fq, const SmallTopkPlan &pl,
-                         const SmallTopk &p, hipStream_t s) {
+                         const SmallTopk &p, hipStream_t s, const ScanEpi &e = ScanEpi{}) {
     using L = SmallLaunch<IS_L1>;
     const uint32_t rc = h->row_chunks;
     h->last_scan_packed.store(0, std::memory_order_relaxed);
-    if (rc == 1) return L::template go<1, 1>(h, qc, qo, fq, pl, p, s);
-    if (rc == 2) return L::template go<2, 1>(h, qc, qo, fq, pl, p, s);
-    if (rc <= 4) return L::template go<4, 1>(h, qc, qo, fq, pl, p, s);
-    if (rc <= 8) return L::template go<8, 1>(h, qc, qo, fq, pl, p, s);
+    if (rc == 1) return L::template go<1, 1>(h, qc, qo, fq, pl, p, s, e);
+    if (rc == 2) return L::template go<2, 1>(h, qc, qo, fq, pl, p, s, e);
+    if (rc <= 4) return L::template go<4, 1>(h, qc, qo, fq, pl, p, s, e);
+    if (rc <= 8) return L::template go<8, 1>(h, qc, qo, fq, pl, p, s, e);
     switch ((rc + 15) / 16) {
-        case 1: return L::template go<16, 1>(h, qc, qo, fq, pl, p, s);
-        case 2: return L::template go<16, 2>(h, qc, qo, fq, pl, p, s);
-        case 3: return L::template go<16, 3>(h, qc, qo, fq, pl, p, s);
-        case 4: return L::template go<16, 4>(h, qc, qo, fq, pl, p, s);
-        case 5: return L::template go<16, 5>(h, qc, qo, fq, pl, p, s);
-        case 6: return L::template go<16, 6>(h, qc, qo, fq, pl, p, s);
-        case 7: return L::template go<16, 7>(h, qc, qo, fq, pl, p, s);
-        case 8: return L::template go<16, 8>(h, qc, qo, fq, pl, p, s);
+        case 1: return L::template go<16, 1>(h, qc, qo, fq, pl, p, s, e);
+        case 2: return L::template go<16, 2>(h, qc, qo, fq, pl, p, s, e);
+        case 3: return L::template go<16, 3>(h, qc, qo, fq, pl, p, s, e);
+        case 4: return L::template go<16, 4>(h, qc, qo, fq, pl, p, s, e);
+        case 5: return L::template go<16, 5>(h, qc, qo, fq, pl, p, s, e);
+        case 6: return L::template go<16, 6>(h, qc, qo, fq, pl, p, s, e);
+        case 7: return L::template go<16, 7>(h, qc, qo, fq, pl, p, s, e);
+        case 8: return L::template go<16, 8>(h, qc, qo, fq, pl, p, s, e);
         default: break;
     }
     return fail(QAMD_ERR_ARGUMENTS, "no small top-k kernel for %u chunks", rc);
@@ -1483,20 +1518,24 @@ bool u8_small_plan(const qamd_u8 *h, uint32_t k, SmallTopkPlan &plan) {
 // qc: the query's actual_dim codes (16-byte aligned), qo: its f32 offset -- inside a qamd_u8_query
 // or straight out of a query batch ([q][pitch] codes, [q] offsets).
 qamd_status scan_ptrs(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out_dev, hipStream_t s,
-                      const TopkFilter *filt = nullptr) {
+                      const TopkFilter *filt = nullptr, const ScanEpi &e = ScanEpi{}) {
     if (h->count == 0) return QAMD_OK;
     const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
     h->last_scan_packed.store(0, std::memory_order_relaxed);  // launch_scan reports the packed image
     if (lane_order(h)) {
         uint64_t waves = (h->count + 3) / 4;
         unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
-        hipLaunchKernelGGL((u8_scan_avx2_lanes_kernel<true>), dim3(grid), dim3(kBlock), 0, s,
-                           h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,
-                           (uint32_t)h->count, h->row_chunks, out_dev);
+#define QAMD_U8_LANES(EPI)                                                                          \
+    hipLaunchKernelGGL((u8_scan_avx2_lanes_kernel<true, EPI>), dim3(grid), dim3(kBlock), 0, s,          \
+                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,        \
+                       (uint32_t)h->count, h->row_chunks, out_dev, e.diff)
+        if (e.mode == EPI_POINT) QAMD_U8_LANES(EPI_POINT);
+        else QAMD_U8_LANES(EPI_INTERNAL);
+#undef QAMD_U8_LANES
     } else if (is_l1) {
-        if (!launch_scan<true>(h, qc, qo, out_dev, filt, s)) launch_scan_generic<true>(h, qc, qo, out_dev, s);
+        if (!launch_scan<true>(h, qc, qo, out_dev, filt, s, e)) launch_scan_generic<true>(h, qc, qo, out_dev, s, e);
     } else {
-        if (!launch_scan<false>(h, qc, qo, out_dev, filt, s)) launch_scan_generic<false>(h, qc, qo, out_dev, s);
+        if (!launch_scan<false>(h, qc, qo, out_dev, filt, s, e)) launch_scan_generic<false>(h, qc, qo, out_dev, s, e);
     }
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
@@ -2578,14 +2617,17 @@ qamd_status u8_encode_queries_device(const qamd_u8 *h, const float *queries_dev,
 // The top-k of one query given as raw device pointers (its codes and its offset): the body of
 // qamd_u8_topk, also the per-query route of the batch API, which hands in rows of a query batch
 // without copying them into a query object.  Runs on the current device.
-qamd_status u8_topk_ptrs(const qamd_u8 *h, const uint8_t *codes_dev, const float *qo, uint32_t k, int largest,
-                         uint32_t *out_ids, float *out_scores, qamd_mem out_mem, hipStream_t s, const FusedQuery *fq) {
+// `e`: the epilogue of every route - an encoded query's, or score_internal's with (codes_dev, qo) a stored row
+// (qamd_u8_topk_internal); the routing predicates are the same for both.
+static qamd_status topk_ptrs_epi(const qamd_u8 *h, const uint8_t *codes_dev, const float *qo, uint32_t k, int largest,
+                                 uint32_t *out_ids, float *out_scores, qamd_mem out_mem, hipStream_t s, const FusedQuery *fq,
+                                 const ScanEpi &e) {
     const uint4 *qc = reinterpret_cast<const uint4 *>(codes_dev);
     FusedScan scan;
-    scan.scan_scores = [&](float *scores, hipStream_t st) { return scan_ptrs(h, qc, qo, scores, st); };
-    scan.scan_filter = [&](const TopkFilter &f, hipStream_t st) { return scan_ptrs(h, qc, qo, nullptr, st, &f); };
+    scan.scan_scores = [&](float *scores, hipStream_t st) { return scan_ptrs(h, qc, qo, scores, st, nullptr, e); };
+    scan.scan_filter = [&](const TopkFilter &f, hipStream_t st) { return scan_ptrs(h, qc, qo, nullptr, st, &f, e); };
     scan.score_ids = [&](const uint32_t *ids, uint64_t n_ids, float *out, hipStream_t st) {
-        return score_ids_dev(h, qc, qo, 0.0f, EPI_POINT, ids, n_ids, out, st);
+        return score_ids_dev(h, qc, qo, e.diff, e.mode, ids, n_ids, out, st);
     };
     {   // small stores: one launch, no status read-back (device outputs only enqueue)
         SmallTopkPlan plan;
@@ -2593,17 +2635,41 @@ qamd_status u8_topk_ptrs(const qamd_u8 *h, const uint8_t *codes_dev, const float
             const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
             return small_topk(plan, k, largest, out_ids, out_scores, out_mem, s,
                               [&](const SmallTopk &p, hipStream_t st) {
-                                  return is_l1 ? launch_small<true>(h, qc, qo, fq, plan, p, st)
-                                               : launch_small<false>(h, qc, qo, fq, plan, p, st);
+                                  return is_l1 ? launch_small<true>(h, qc, qo, fq, plan, p, st, e)
+                                               : launch_small<false>(h, qc, qo, fq, plan, p, st, e);
                               });
         }
     }
     if (fq) return fail(QAMD_ERR_ARGUMENTS, "a deferred query needs the single-launch path");
     if (!fused_capable(h)) {  // rare layouts: classic path only
         return topk_classic(h->count, k, largest, out_ids, out_scores, out_mem, s,
-                            [&](float *scores) { return scan_ptrs(h, qc, qo, scores, s); });
+                            [&](float *scores) { return scan_ptrs(h, qc, qo, scores, s, nullptr, e); });
     }
     return fused_topk(h->count, k, largest, out_ids, out_scores, out_mem, s, scan);
+}
+
+qamd_status u8_topk_ptrs(const qamd_u8 *h, const uint8_t *codes_dev, const float *qo, uint32_t k, int largest,
+                         uint32_t *out_ids, float *out_scores, qamd_mem out_mem, hipStream_t s, const FusedQuery *fq) {
+    return topk_ptrs_epi(h, codes_dev, qo, k, largest, out_ids, out_scores, out_mem, s, fq, ScanEpi{});
+}
+
+// score_internal (encoded_vectors_u8.rs:386-453) against the whole store: the "query" is row i of the byte
+// codes with its stored offset - the packed image's scan reads its query as byte codes too - and every route ends in
+// score_internal's epilogue.
+static ScanEpi internal_epi(const qamd_u8 *h) { return ScanEpi{internal_diff(h), EPI_INTERNAL}; }
+
+static qamd_status u8_score_internal_all(const qamd_u8 *h, uint32_t i, float *out, qamd_mem out_mem, hipStream_t s) {
+    const uint4 *qc = h->codes.as<uint4>() + (uint64_t)i * h->row_chunks;
+    const float *qo = h->offsets.as<float>() + i;
+    const ScanEpi e = internal_epi(h);
+    if (out_mem == QAMD_MEM_DEVICE) return scan_ptrs(h, qc, qo, out, s, nullptr, e);
+    return score_all_to_host(h->count, out, s, [&](float *scores) { return scan_ptrs(h, qc, qo, scores, s, nullptr, e); });
+}
+
+static qamd_status u8_topk_internal(const qamd_u8 *h, uint32_t i, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
+                             qamd_mem out_mem, hipStream_t s) {
+    return topk_ptrs_epi(h, h->codes.as<uint8_t>() + (uint64_t)i * h->meta.actual_dim, h->offsets.as<float>() + i, k, largest,
+                         out_ids, out_scores, out_mem, s, nullptr, internal_epi(h));
 }
 
 // The batch API for the metrics with no matrix form (L1: sum |q - v| is not a contraction): the
@@ -2691,6 +2757,30 @@ qamd_status u8_score_single(const qamd_u8 *h, const uint8_t *codes_dev, const fl
 }
 
 }  // namespace qamd
+
+extern "C" {
+
+qamd_status qamd_u8_score_internal_all(const qamd_u8 *h, uint32_t i, float *out, qamd_mem out_mem, void *stream) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    if (h->count == 0) return QAMD_OK;
+    if (!out) return fail(QAMD_ERR_ARGUMENTS, "out is null");
+    if (i >= h->count) return fail(QAMD_ERR_ARGUMENTS, "row id %u out of range (count %llu)", i, (unsigned long long)h->count);
+    QAMD_ON_DEVICE(h->device);
+    return u8_score_internal_all(h, i, out, out_mem, as_stream(stream));
+}
+
+qamd_status qamd_u8_topk_internal(const qamd_u8 *h, uint32_t i, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
+                                  qamd_mem out_mem, void *stream) {
+    if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
+    qamd_status args = QAMD_OK;
+    if (!topk_wanted(k, 1, out_ids, out_scores, args)) return args;
+    if (h->count && i >= h->count)
+        return fail(QAMD_ERR_ARGUMENTS, "row id %u out of range (count %llu)", i, (unsigned long long)h->count);
+    QAMD_ON_DEVICE(h->device);
+    return u8_topk_internal(h, i, k, largest, out_ids, out_scores, out_mem, as_stream(stream));
+}
+
+}  // extern "C"
 
 #ifdef QAMD_DEV
 // Developer-only accessors for the tuning harness (tune.hip): libquantization_amd_dev.so only.
