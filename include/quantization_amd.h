@@ -369,15 +369,43 @@ QAMD_API qamd_status qamd_bin_load(const char *data_path, const char *meta_path,
  * Out of scope: the qamd_bin_sharded_* handles stay one-bit; a 1.5-bit encoding; bench.py (it measures one-bit stores).
  * Scalar (4- / 8-bit) queries against two-bit rows come from qamd_bin_encode_query_scalar_w / _batch_scalar_w below
  * (DESIGN.md 3.2f); the unweighted qamd_bin_encode_query_scalar / _batch_scalar refuse a two-bit handle
- * (QAMD_ERR_ARGUMENTS). */
-typedef enum { QAMD_BIN_ONE_BIT = 0, QAMD_BIN_TWO_BITS = 1 } qamd_bin_encoding;
+ * (QAMD_ERR_ARGUMENTS).
+ *
+ * Rotated rows: a randomized Hadamard rotation before the sign and threshold bits.  The reference has NO counterpart;
+ * DESIGN.md 3.2g is the specification.  QAMD_BIN_ROTATED is a flag or-ed onto one of the two encodings above; it rides
+ * the `encoding` argument of the four *_enc calls and the handle carries it from there (no entry point of its own).
+ * Values 2, 3, 6, 7 and above are QAMD_ERR_ARGUMENTS before any device call.
+ *   - P = the smallest power of two >= dim (1 for dim <= 1); a rotated handle has dim <= 16384 (QAMD_ERR_ARGUMENTS beyond,
+ *     before any device call).  y_i = x_i for i < dim and +0.0f up to P; y_i's sign bit is flipped iff h & 1 after, in
+ *     u32 arithmetic, h = i * 0x9E3779B1; h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *     (a fixed seed: nothing is stored per handle); then for s = 1, 2, 4, .., P / 2 in this order and every j with
+ *     (j & s) == 0: (y_j, y_{j+s}) = (y_j + y_{j+s}, y_j - y_{j+s}), one f32 operation each, round to nearest even,
+ *     subnormals kept, no normalisation; NaN and +-inf spread as IEEE 754 says.
+ *   - Everything downstream sees a vector of P dimensions.  One bit: bit i = y_i > 0, code_bits = P.  Two bits: the
+ *     two-bit rows above on y with lo, hi of P entries, code_bits = 2 P, the statistics over the P rotated columns.  Row
+ *     bytes are the one-bit size of code_bits dimensions; qamd_bin_get_encoding returns the flagged value;
+ *     qamd_bin_get_thresholds and the lo / hi arguments of the *_enc calls have P entries (they can come from another
+ *     rotated handle).  qamd_bin_find_stats stays a raw-data call: it does not rotate.
+ *   - Queries have qdim == dim and are rotated the same way first: qamd_bin_encode_query / _batch then encode as a row,
+ *     qamd_bin_encode_query_scalar / _batch_scalar serve rotated one-bit handles with codes from y (their dimension limit
+ *     applies to P), the _w calls rotated two-bit handles with w_i = y_i * (hi_i - lo_i).
+ *   - Scores, every route, score_internal, topk_internal, rescoring, upsert, save / load: a rotated store of dim is
+ *     served exactly as a plain store of code_bits bits; vp.dim stays the vectors' dimension for originals.  Metadata
+ *     says "encoding":"OneBitRotated" or "TwoBitsRotated", the latter with thresholds of P entries.
+ * Out of scope: sharded binary handles; seeds other than the fixed one; more than one round; block-diagonal rotations
+ * that would avoid padding 768 -> 1024 or 1536 -> 2048; bench.py. */
+typedef enum { QAMD_BIN_ONE_BIT = 0, QAMD_BIN_TWO_BITS = 1,
+               QAMD_BIN_ROTATED = 4,            /* flag: or-ed onto one of the two above */
+               QAMD_BIN_ONE_BIT_ROTATED = 4, QAMD_BIN_TWO_BITS_ROTATED = 5 } qamd_bin_encoding;
 QAMD_API uint64_t qamd_bin_quantized_vector_size_enc(const qamd_vector_parameters *vp, qamd_bits_store store,
                                                      qamd_bin_encoding encoding);
 /* The statistics above over ONE contiguous block of n_rows x dim values (blocks of 4096 counted from the call's first
  * row); n, sum, sumsq: dim host entries each.  On its own for the reason qamd_u8_find_min_max is: a host that holds the
  * rows in several places adds the three arrays of its holders and derives ONE set of thresholds with
  * qamd_bin_thresholds_from_stats.  Unlike min / max, a sum of per-holder sums is NOT bit-equal to the single-handle
- * result (f64 addition is not associative): every holder must then be given the same derived thresholds. */
+ * result (f64 addition is not associative): every holder must then be given the same derived thresholds.
+ * A raw-data call: it never rotates.  Thresholds for rotated two-bit rows (P entries) come from qamd_bin_encode_enc /
+ * _encoder_begin_enc with NULL thresholds, or from a rotated handle's qamd_bin_get_thresholds. */
 QAMD_API qamd_status qamd_bin_find_stats(const float *data, qamd_mem data_mem, uint64_t n_rows, uint64_t dim,
                                          void *stream, uint64_t *n, double *sum, double *sumsq);
 /* Host only: never touches a device and works on a machine without one. */
@@ -406,9 +434,10 @@ QAMD_API qamd_status qamd_bin_from_rows_enc(const uint8_t *rows, qamd_mem rows_m
                                             const qamd_vector_parameters *vp, qamd_bits_store store,
                                             qamd_bin_encoding encoding, const float *lo, const float *hi,
                                             void *stream, qamd_bin **out);
-/* Either pointer may be NULL.  *code_bits = the bits of a row: dim, or 2 * dim. */
+/* Either pointer may be NULL.  *code_bits = the bits of a row: dim, or 2 * dim.  Rotated rows: the flagged encoding
+ * (4 or 5) and P, or 2 * P. */
 QAMD_API qamd_status qamd_bin_get_encoding(const qamd_bin *h, qamd_bin_encoding *encoding, uint64_t *code_bits);
-/* dim host floats each; QAMD_ERR_ARGUMENTS on a one-bit handle. */
+/* dim host floats each (P each for rotated two-bit rows); QAMD_ERR_ARGUMENTS on a one-bit handle. */
 QAMD_API qamd_status qamd_bin_get_thresholds(const qamd_bin *h, float *lo, float *hi);
 /* qamd_bin_save of a two-bit handle writes {"vector_parameters":{..},"encoding":"TwoBits","thresholds":{"lo":[..],
  * "hi":[..]}} (infinite thresholds have no JSON form: QAMD_ERR_IO); a one-bit file is the reference's, unchanged.

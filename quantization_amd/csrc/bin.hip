@@ -782,6 +782,235 @@ __global__ __launch_bounds__(kBlock) void bin_encode_scalar_kernel(const float *
     }
 }
 
+// ---- rotated rows (the reference has no counterpart) ----
+// y = H_P (signs * pad(x)): P the power of two at or above dim, the sign of y_i from a fixed hash of i, then the
+// butterflies of stages s = 1, 2, 4, ..., P / 2 in that order - (a, b) = (y_j, y_{j+s}) -> (a + b, a - b), one f32
+// operation each (this file compiles with contraction off).  A stage reads only the stage before it, so any split of
+// the work gives the same bits; the ORDER of the stages is part of the definition (f32 addition is not associative).
+__device__ __forceinline__ float rot_signed(float v, uint32_t i) {
+    uint32_t h = i * 0x9E3779B1u;
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, v) ^ (h << 31));
+}
+
+// The value lane (l ^ M) holds.  Inside a DPP row of 16 lanes a DPP move: quad_perm for 1 and 2, row_ror:8 for 8, and for
+// 4 the two rotations by 12 and 4 (lane i reads lane (i + 4) % 16 and (i - 4) % 16), of which a lane keeps the one its
+// bit 2 asks for.  Across rows __shfl_xor (ds_bpermute).
+template <int M> __device__ __forceinline__ float lane_xor(float v, int lane) {
+    const int x = __builtin_bit_cast(int, v);
+    int r;
+    if constexpr (M == 1) {
+        r = __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false);
+    } else if constexpr (M == 2) {
+        r = __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false);
+    } else if constexpr (M == 4) {
+        const int up = __builtin_amdgcn_update_dpp(0, x, 0x12C, 0xF, 0xF, false);
+        const int dn = __builtin_amdgcn_update_dpp(0, x, 0x124, 0xF, 0xF, false);
+        r = (lane & 4) ? dn : up;
+    } else if constexpr (M == 8) {
+        r = __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, false);
+    } else {
+        r = __shfl_xor(x, M);
+    }
+    return __builtin_bit_cast(float, r);
+}
+// One stage whose pairs sit M lanes apart: the lower lane keeps a + b, the upper a - b = a + (-b).
+template <int M> __device__ __forceinline__ float lane_butterfly(float v, int lane) {
+    const float p = lane_xor<M>(v, lane);
+    return p + ((lane & M) ? -v : v);
+}
+__device__ __forceinline__ void butterfly(float &a, float &b) {
+    const float s = a + b, d = a - b;
+    a = s, b = d;
+}
+
+// What the rotation kernels do with a finished row.  MODE 0: the P rotated floats to `out` (statistics, scalar-code
+// encoders).  MODE 1: bit i = y_i > 0.  MODE 2: bit i = y_i > lo_i, bit P + i = y_i > hi_i (thr = lo | hi, 2 P floats).
+// emit_chunks: 64 lanes hold the 64 consecutive 4-value chunks c0 .. c0 + 63 of a row of P >= 256 values, lane l chunk
+// c0 + l.  A lane's four compares are a nibble at bit 4 (l % 8) of dword (c0 + l) / 8; the 8-lane DPP sum of
+// bin_encode_flat_kernel (disjoint fields, add == or) finishes the dword and the group's first lane stores it.
+template <int MODE>
+__device__ __forceinline__ void emit_chunks(const float (&y)[4], uint32_t c0, int lane, uint32_t P, const float *__restrict__ thr,
+                                            float *__restrict__ out_row, uint32_t *__restrict__ dst) {
+    const uint32_t c = c0 + lane;
+    if constexpr (MODE == 0) {
+        reinterpret_cast<float4 *>(out_row)[c] = make_float4(y[0], y[1], y[2], y[3]);
+    } else {
+        float lo[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (MODE == 2) {
+            const float4 t = reinterpret_cast<const float4 *>(thr)[c];
+            lo[0] = t.x, lo[1] = t.y, lo[2] = t.z, lo[3] = t.w;
+        }
+        const int t8 = lane & 7;
+        uint32_t nib = (y[0] > lo[0] ? 1u : 0u) | (y[1] > lo[1] ? 2u : 0u) | (y[2] > lo[2] ? 4u : 0u) | (y[3] > lo[3] ? 8u : 0u);
+        const uint32_t d0 = group_sum<8>(nib << (4 * t8));
+        if (t8 == 0) dst[c >> 3] = d0;
+        if constexpr (MODE == 2) {
+            const float4 t = reinterpret_cast<const float4 *>(thr + P)[c];
+            nib = (y[0] > t.x ? 1u : 0u) | (y[1] > t.y ? 2u : 0u) | (y[2] > t.z ? 4u : 0u) | (y[3] > t.w ? 8u : 0u);
+            const uint32_t d1 = group_sum<8>(nib << (4 * t8));
+            if (t8 == 0) dst[P / 32 + (c >> 3)] = d1;
+        }
+    }
+}
+
+// Four adjacent values of a row from index i0 on: one 16-byte load where the host found dim % 4 == 0 and an aligned
+// source (`vec`), else four guarded dword loads; +0.0 from dim on; then the signs and, the four being adjacent, stages 1
+// and 2.
+__device__ __forceinline__ void load_chunk(const float *__restrict__ src, uint32_t i0, uint32_t dim, int vec, float (&y)[4]) {
+    if (vec) {
+        const float4 t = i0 < dim ? __builtin_bit_cast(float4, ld_nt(reinterpret_cast<const uint4 *>(src + i0)))
+                                  : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        y[0] = t.x, y[1] = t.y, y[2] = t.z, y[3] = t.w;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; e++) y[e] = i0 + e < dim ? src[i0 + e] : 0.0f;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) y[e] = rot_signed(y[e], i0 + e);
+    butterfly(y[0], y[1]);
+    butterfly(y[2], y[3]);
+    butterfly(y[0], y[2]);
+    butterfly(y[1], y[3]);
+}
+
+// A wave per row, the row in registers: P = 64 E K, lane l holds value e of chunk k at index (64 k + l) E + e, so a
+// wave-load reads 64 consecutive chunks (E = 4: 1 KiB, every float once).  The index bits are e | lane | k from the low
+// end, which is the order of the stages: E = 4 does stages 1 and 2 on a chunk's own values, the six lane bits follow
+// (lane_butterfly), then the stages across a lane's K chunks, plain register adds.  E = 1 serves P <= 128; P < 64
+// (K = 1) leaves the lanes from P on idle and stops at stage P / 2.  One row per wave and pass of a grid-stride loop,
+// all 64 lanes active throughout (the DPP moves read their neighbours).
+// MODE 1 / 2 with E = 1: one ballot per plane and 64 values; the row is at most four 64-bit words, every lane puts them
+// together and lane j stores dword j of the row's row_words, pad dwords as zeros.
+template <int E, int K, int MODE>
+__global__ __launch_bounds__(kBlock) void bin_rotate_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                           uint32_t P, int vec, const float *__restrict__ thr,
+                                                           float *__restrict__ out, uint32_t *__restrict__ rows,
+                                                           uint32_t row_words, uint64_t row0) {
+    static_assert(E == 4 || (E == 1 && K <= 2), "E = 1 is for rows of at most 128 values");
+    constexpr bool kFull = E * K > 1;  // P == 64 E K: all six lane stages; <1, 1> serves every P <= 64 and asks P
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    for (uint64_t r = wave; r < n_rows; r += n_waves) {
+        const float *src = data + r * dim;
+        float y[K][E];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            if constexpr (E == 4) {
+                load_chunk(src, (uint32_t)(k * 64 + lane) * 4, dim, vec, y[k]);
+            } else {
+                const uint32_t i = k * 64 + lane;
+                y[k][0] = rot_signed(i < dim ? src[i] : 0.0f, i);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+#pragma unroll
+            for (int e = 0; e < E; e++) {
+                float v = y[k][e];
+                if (kFull || 1u < P) v = lane_butterfly<1>(v, lane);
+                if (kFull || 2u < P) v = lane_butterfly<2>(v, lane);
+                if (kFull || 4u < P) v = lane_butterfly<4>(v, lane);
+                if (kFull || 8u < P) v = lane_butterfly<8>(v, lane);
+                if (kFull || 16u < P) v = lane_butterfly<16>(v, lane);
+                if (kFull || 32u < P) v = lane_butterfly<32>(v, lane);
+                y[k][e] = v;
+            }
+        }
+#pragma unroll
+        for (int s = 1; s < K; s <<= 1) {
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                if (k & s) continue;
+#pragma unroll
+                for (int e = 0; e < E; e++) butterfly(y[k][e], y[k + s][e]);
+            }
+        }
+        float *out_row = MODE == 0 ? out + r * P : nullptr;
+        uint32_t *dst = MODE == 0 ? nullptr : rows + (row0 + r) * row_words;
+        if constexpr (E == 4) {
+#pragma unroll
+            for (int k = 0; k < K; k++) emit_chunks<MODE>(y[k], k * 64, lane, P, thr, out_row, dst);
+            if constexpr (MODE != 0)
+                for (uint32_t w = (MODE == 2 ? P / 16 : P / 32) + lane; w < row_words; w += 64) dst[w] = 0;
+        } else if constexpr (MODE == 0) {
+#pragma unroll
+            for (int k = 0; k < K; k++)
+                if ((uint32_t)(k * 64 + lane) < P) out_row[k * 64 + lane] = y[k][0];
+        } else {
+            unsigned long long b0[K], b1[K];
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const uint32_t i = k * 64 + lane;
+                const bool in = i < P;
+                const float lo = MODE == 2 && in ? thr[i] : 0.0f, hi = MODE == 2 && in ? thr[P + i] : 0.0f;
+                b0[k] = __ballot(in && y[k][0] > lo);
+                b1[k] = MODE == 2 ? __ballot(in && y[k][0] > hi) : 0ull;
+            }
+            unsigned long long w0 = b0[0], w1 = K == 2 ? b0[K - 1] : 0ull, w2 = 0, w3 = 0;
+            if constexpr (MODE == 2) {
+                if (K == 2) w2 = b1[0], w3 = b1[K - 1];
+                else if (P == 64) w1 = b1[0];
+                else w0 |= b1[0] << P;
+            }
+            if ((uint32_t)lane < row_words) {
+                const unsigned long long w = lane < 2 ? w0 : lane < 4 ? w1 : lane < 6 ? w2 : lane < 8 ? w3 : 0ull;
+                dst[lane] = (lane & 1) ? (uint32_t)(w >> 32) : (uint32_t)w;
+            }
+            for (uint32_t w = 64 + lane; w < row_words; w += 64) dst[w] = 0;
+        }
+    }
+}
+
+// A workgroup per row for the rows a wave's registers do not hold (P = 4096 .. 16384, 16 .. 64 KiB of LDS): every
+// thread loads 4-value chunks (stages 1 and 2 in registers, as above) into the LDS row, the stages from 4 on run there -
+// P / 2 pairs per stage over the 256 threads, a barrier between stages - and the chunks are read back for emit_chunks,
+// a wave 64 consecutive chunks at a time.
+constexpr uint32_t kRotWaveMax = 2048;  // the widest row bin_rotate_kernel takes: 32 values per lane
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void bin_rotate_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                               uint32_t P, int vec, const float *__restrict__ thr,
+                                                               float *__restrict__ out, uint32_t *__restrict__ rows,
+                                                               uint32_t row_words, uint64_t row0) {
+    extern __shared__ float rot_row[];
+    const int lane = threadIdx.x & 63;
+    const uint32_t chunks = P / 4;  // a multiple of kBlock
+    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const float *src = data + r * dim;
+        for (uint32_t c = threadIdx.x; c < chunks; c += kBlock) {
+            float y[4];
+            load_chunk(src, c * 4, dim, vec, y);
+            reinterpret_cast<float4 *>(rot_row)[c] = make_float4(y[0], y[1], y[2], y[3]);
+        }
+        for (uint32_t s = 4; s < P; s <<= 1) {
+            __syncthreads();
+            for (uint32_t b = threadIdx.x; b < P / 2; b += kBlock) {
+                const uint32_t j = ((b & ~(s - 1)) << 1) | (b & (s - 1));
+                float a = rot_row[j], d = rot_row[j + s];
+                butterfly(a, d);
+                rot_row[j] = a, rot_row[j + s] = d;
+            }
+        }
+        __syncthreads();
+        float *out_row = MODE == 0 ? out + r * P : nullptr;
+        uint32_t *dst = MODE == 0 ? nullptr : rows + (row0 + r) * row_words;
+        for (uint32_t c0 = (threadIdx.x >> 6) * 64; c0 < chunks; c0 += kBlock) {
+            const float4 t = reinterpret_cast<const float4 *>(rot_row)[c0 + lane];
+            const float y[4] = {t.x, t.y, t.z, t.w};
+            emit_chunks<MODE>(y, c0, lane, P, thr, out_row, dst);
+        }
+        if constexpr (MODE != 0)
+            for (uint32_t w = (MODE == 2 ? P / 16 : P / 32) + threadIdx.x; w < row_words; w += kBlock) dst[w] = 0;
+        __syncthreads();  // the next row's chunks overwrite the LDS row
+    }
+}
+
 int grid_for(uint64_t work_items, uint64_t per_block, int blocks_per_cu) {
     uint64_t want = (work_items + per_block - 1) / per_block;
     uint64_t cap = (uint64_t)device_info().cu_count * blocks_per_cu;
@@ -812,9 +1041,14 @@ struct qamd_bin {
     DevBuf rows;      // [round_up(capacity, 1024) + 1024][ds], zero from row count on
     // Two-bit rows: a row holds code_bits = 2 dim bits and is scored as a one-bit row of that length;
     // vp.dim stays the vectors' dimension (thresholds, queries, the originals of a rescored top-k).
+    // Rotated rows: the encoders see y = H_P (signs * pad(x)) of edim = P values in place of x; everything
+    // after them - thresholds, code_bits, the scans - is that of a plain store of P dimensions.
     int encoding = QAMD_BIN_ONE_BIT;
-    uint64_t code_bits = 0;       // bits of a row: dim, or 2 dim
-    std::vector<float> thr_host;  // two-bit: lo[dim] | hi[dim]
+    uint64_t edim = 0;            // what the bit encoders see: dim, or P of a rotated store
+    uint64_t code_bits = 0;       // bits of a row: edim, or 2 edim
+    std::vector<float> thr_host;  // two-bit: lo[edim] | hi[edim]
+    bool two() const { return (encoding & QAMD_BIN_TWO_BITS) != 0; }
+    bool rotated() const { return (encoding & QAMD_BIN_ROTATED) != 0; }
     DevBuf thr;                   // the same, for the encoders of rows and queries
     // the batched top-k's pivot sample (rows hash(j) of the store, j < sample_count, then 512 zero rows);
     // gathered on first use (count / 64 rows at most), discarded by an upsert
@@ -833,8 +1067,21 @@ struct qamd_bin_query {
 
 namespace {
 
+// P of DESIGN 3.2g: the smallest power of two >= dim, 1 for dim = 1 (and no dimension stays none)
+uint64_t rot_dim(uint64_t dim) {
+    if (dim == 0) return 0;
+    uint64_t p = 1;
+    while (p < dim) p <<= 1;
+    return p;
+}
+constexpr uint64_t kRotMaxDim = 16384;  // a rotated row is at most 64 KiB of f32: the LDS bin_rotate_lds_kernel asks for
+
+// The dimension the bit encoders of `encoding` see for vectors of `dim`.
+uint64_t encoder_dim(uint64_t dim, int encoding) { return (encoding & QAMD_BIN_ROTATED) ? rot_dim(dim) : dim; }
+
 qamd_status alloc_store(qamd_bin *h) {
-    h->code_bits = h->encoding == QAMD_BIN_TWO_BITS ? 2 * h->vp.dim : h->vp.dim;
+    h->edim = encoder_dim(h->vp.dim, h->encoding);
+    h->code_bits = h->two() ? 2 * h->edim : h->edim;
     h->nb = row_bytes_of(h->code_bits, h->store);
     h->ds = device_stride_of(h->nb);
     h->capacity = h->count;
@@ -1029,11 +1276,39 @@ qamd_status upload_rows(qamd_bin *h, const uint8_t *rows, qamd_mem mem, hipStrea
 // The bit encoder for a one-bit or two-bit store: `n` vectors of `dim` floats into bit rows of `row_words` dwords, the
 // first at row r0 of dst - the store's rows, a query's bit row, a batch's (one "row" per query, :288-291 is encode_vector
 // itself).
+// The rotation of `n` vectors of `dim` floats, P = rot_dim(dim).  MODE 0: P floats per vector to `out`;
+// MODE 1 / 2: the fused row encoder - bit rows of `row_words` dwords from row r0 of `rows` on, thr = lo | hi for MODE 2.
+template <int MODE>
+void launch_rotate(const float *src, uint64_t n, uint64_t dim, const float *thr, float *out, uint32_t *rows, uint64_t row_words,
+                   uint64_t r0, hipStream_t s) {
+    if (n == 0 || dim == 0) return;
+    const uint32_t P = (uint32_t)rot_dim(dim);
+    const int vec = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+#define QAMD_BIN_ROT(E, K)                                                                                               \
+    hipLaunchKernelGGL((bin_rotate_kernel<E, K, MODE>), dim3(grid_for(n, kBlock / 64, 8)), dim3(kBlock), 0, s, src, n,    \
+                       (uint32_t)dim, P, vec, thr, out, rows, (uint32_t)row_words, r0)
+    if (P > kRotWaveMax)
+        hipLaunchKernelGGL(bin_rotate_lds_kernel<MODE>, dim3(grid_for(n, 1, 160 * 1024 / (P * 4))), dim3(kBlock), P * 4, s, src, n,
+                           (uint32_t)dim, P, vec, thr, out, rows, (uint32_t)row_words, r0);
+    else if (P <= 64) QAMD_BIN_ROT(1, 1);
+    else if (P == 128) QAMD_BIN_ROT(1, 2);
+    else if (P == 256) QAMD_BIN_ROT(4, 1);
+    else if (P == 512) QAMD_BIN_ROT(4, 2);
+    else if (P == 1024) QAMD_BIN_ROT(4, 4);
+    else QAMD_BIN_ROT(4, 8);
+#undef QAMD_BIN_ROT
+}
+
 void launch_bit_encoder(const qamd_bin *h, const float *src, uint64_t n, uint64_t dim, uint64_t row_words, uint32_t *dst,
                         uint64_t r0, hipStream_t s) {
     if (n == 0 || dim == 0) return;
+    if (h->rotated()) {  // (dim is the handle's: every caller has checked it)
+        if (h->two()) launch_rotate<2>(src, n, dim, h->thr.as<float>(), nullptr, dst, row_words, r0, s);
+        else launch_rotate<1>(src, n, dim, nullptr, nullptr, dst, row_words, r0, s);
+        return;
+    }
     const int grid = grid_for(n, kBlock / 64, 8);
-    if (h->encoding == QAMD_BIN_TWO_BITS)
+    if (h->two())
         hipLaunchKernelGGL(bin_encode_thr_kernel, dim3(grid), dim3(kBlock), 0, s, src, n, (uint32_t)dim, (uint32_t)row_words,
                            h->thr.as<float>(), dst, r0);
     else
@@ -1042,10 +1317,18 @@ void launch_bit_encoder(const qamd_bin *h, const float *src, uint64_t n, uint64_
 
 // The scalar encoder for a one-bit or two-bit (weighted) store: `n` queries of `dim` floats, one workgroup
 // each.  The single query has no code image: codes = nullptr.
-void launch_scalar_encoder(const qamd_bin *h, const float *src, uint64_t n, uint64_t dim, uint64_t ds, uint32_t bits,
+qamd_status launch_scalar_encoder(const qamd_bin *h, const float *src, uint64_t n, uint64_t dim, uint64_t ds, uint32_t bits,
                            uint32_t *planes, uint64_t p_stride, float *max_abs, int8_t *codes, uint64_t code_pitch,
                            hipStream_t s) {
-    if (h->encoding == QAMD_BIN_TWO_BITS)
+    StreamBuf rot;  // a rotated store: the codes come from y, P floats per query, held until `s` has used them
+    if (h->rotated() && n && dim) {
+        const uint64_t P = rot_dim(dim);
+        QAMD_TRY(rot.alloc(n * P * 4, s));
+        launch_rotate<0>(src, n, dim, nullptr, rot.as<float>(), nullptr, 0, 0, s);
+        src = rot.as<float>();
+        dim = P;
+    }
+    if (h->two())
         hipLaunchKernelGGL(bin_encode_scalar_kernel<true>, dim3((unsigned)n), dim3(kBlock), 0, s, src, (uint32_t)dim,
                            h->thr.as<float>(), (uint32_t)(ds / 4), bits, planes, (uint32_t)(p_stride / 4), max_abs, codes,
                            (uint32_t)code_pitch);
@@ -1053,13 +1336,14 @@ void launch_scalar_encoder(const qamd_bin *h, const float *src, uint64_t n, uint
         hipLaunchKernelGGL(bin_encode_scalar_kernel<false>, dim3((unsigned)n), dim3(kBlock), 0, s, src, (uint32_t)dim,
                            static_cast<const float *>(nullptr), (uint32_t)(ds / 4), bits, planes, (uint32_t)(p_stride / 4),
                            max_abs, codes, (uint32_t)code_pitch);
+    return QAMD_OK;
 }
 
 // encode_vector (:193-208) for `nr` device-resident rows: rows r0 .. r0+nr of the store.
 qamd_status launch_bin_encode(qamd_bin *h, const float *src, uint64_t nr, uint64_t r0, hipStream_t s) {
     const uint64_t dim = h->vp.dim;
     if (nr == 0 || dim == 0) return QAMD_OK;
-    if (h->encoding != QAMD_BIN_TWO_BITS && dim % 128 == 0 && h->ds * 8 == dim && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+    if (h->encoding == QAMD_BIN_ONE_BIT && dim % 128 == 0 && h->ds * 8 == dim && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
         const uint64_t n4 = nr * dim / 4;
         const unsigned grid = (unsigned)((n4 + 1024 * (kBlock / 64) - 1) / (1024 * (kBlock / 64)));
         hipLaunchKernelGGL(bin_encode_flat_kernel, dim3(grid), dim3(kBlock), 0, s, reinterpret_cast<const float4 *>(src),
@@ -1163,15 +1447,21 @@ struct BinStats {
 
 // A batch of rows, in host or device memory, into the statistics: in pieces as the encoders stage them.
 // `stop` is polled before every piece, as the row pass polls it.
+// raw_dim != 0 (rotated rows): the rows have raw_dim floats and the statistics are those of their rotation,
+// st.dim = P columns - a piece of at most 256 MiB is rotated into a stream-ordered buffer and added from there.
 qamd_status stats_feed(BinStats &st, const float *data, qamd_mem mem, uint64_t n_rows, DevBuf &stage, hipStream_t s,
-                       qamd_stop_fn stop = nullptr, void *stop_user = nullptr) {
+                       qamd_stop_fn stop = nullptr, void *stop_user = nullptr, uint64_t raw_dim = 0) {
     if (st.dim == 0 || n_rows == 0) return QAMD_OK;
-    const uint64_t piece_bytes = stage_bytes(mem == QAMD_MEM_HOST ? (256ull << 20) : (8ull << 30));
+    const uint64_t piece_bytes = stage_bytes(mem == QAMD_MEM_HOST || raw_dim ? (256ull << 20) : (8ull << 30));
     const uint64_t piece_rows = std::max<uint64_t>(1, piece_bytes / (st.dim * 4));
-    return for_each_staged_piece(data, mem, n_rows, st.dim, piece_rows, stage, s,
+    return for_each_staged_piece(data, mem, n_rows, raw_dim ? raw_dim : st.dim, piece_rows, stage, s,
                                  [&](const float *src, uint64_t, uint64_t nr) -> qamd_status {
         if (stop && stop(stop_user)) return fail(QAMD_ERR_STOPPED, "Stopped");
-        return st.add(src, nr, s);
+        if (!raw_dim) return st.add(src, nr, s);
+        StreamBuf rot;
+        QAMD_TRY(rot.alloc(nr * st.dim * 4, s));
+        launch_rotate<0>(src, nr, raw_dim, nullptr, rot.as<float>(), nullptr, 0, 0, s);
+        return st.add(rot.as<float>(), nr, s);
     });
 }
 
@@ -1195,9 +1485,13 @@ void thresholds_of(uint64_t dim, const uint64_t *n, const double *sum, const dou
 
 // What every *_enc entry point checks before it needs a device.  `required`: two-bit rows cannot do without thresholds.
 qamd_status check_enc_args(const qamd_vector_parameters *vp, int encoding, const float *lo, const float *hi, bool required) {
-    if (encoding != QAMD_BIN_ONE_BIT && encoding != QAMD_BIN_TWO_BITS) return fail(QAMD_ERR_ARGUMENTS, "unknown binary encoding %d", encoding);
+    if ((encoding & ~(QAMD_BIN_TWO_BITS | QAMD_BIN_ROTATED)) != 0 || encoding < 0)
+        return fail(QAMD_ERR_ARGUMENTS, "unknown binary encoding %d", encoding);
     if ((lo == nullptr) != (hi == nullptr)) return fail(QAMD_ERR_ARGUMENTS, "thresholds: lo and hi come together");
-    if (encoding == QAMD_BIN_ONE_BIT) {
+    if ((encoding & QAMD_BIN_ROTATED) && vp->dim > kRotMaxDim)
+        return fail(QAMD_ERR_ARGUMENTS, "rotated rows have at most %llu dimensions, not %llu", (unsigned long long)kRotMaxDim,
+                    (unsigned long long)vp->dim);
+    if (!(encoding & QAMD_BIN_TWO_BITS)) {
         if (lo) return fail(QAMD_ERR_ARGUMENTS, "one-bit rows take no thresholds");
         return QAMD_OK;
     }
@@ -1205,7 +1499,8 @@ qamd_status check_enc_args(const qamd_vector_parameters *vp, int encoding, const
         return fail(QAMD_ERR_ARGUMENTS, "two-bit rows have at most %llu dimensions, not %llu", (unsigned long long)kTwoBitMaxDim,
                     (unsigned long long)vp->dim);
     if (!lo && required) return fail(QAMD_ERR_ARGUMENTS, "two-bit rows need their thresholds");
-    for (uint64_t i = 0; lo && i < vp->dim; i++) {
+    const uint64_t edim = encoder_dim(vp->dim, encoding);  // given thresholds have P entries for rotated rows
+    for (uint64_t i = 0; lo && i < edim; i++) {
         if (lo[i] != lo[i] || hi[i] != hi[i]) return fail(QAMD_ERR_ARGUMENTS, "threshold %llu is NaN", (unsigned long long)i);
         if (lo[i] > hi[i]) return fail(QAMD_ERR_ARGUMENTS, "threshold %llu: lo %g > hi %g", (unsigned long long)i, lo[i], hi[i]);
     }
@@ -1213,7 +1508,7 @@ qamd_status check_enc_args(const qamd_vector_parameters *vp, int encoding, const
 }
 
 qamd_status set_thresholds(qamd_bin *h, const float *lo, const float *hi, hipStream_t s) {
-    const uint64_t dim = h->vp.dim;
+    const uint64_t dim = h->edim;
     h->thr_host.resize(2 * dim);
     if (dim == 0) return QAMD_OK;
     memcpy(h->thr_host.data(), lo, dim * 4);
@@ -1225,7 +1520,7 @@ qamd_status set_thresholds(qamd_bin *h, const float *lo, const float *hi, hipStr
 }
 
 qamd_status set_thresholds_from_stats(qamd_bin *h, BinStats &st, hipStream_t s) {
-    const uint64_t dim = h->vp.dim;
+    const uint64_t dim = h->edim;
     std::vector<uint64_t> n(dim);
     std::vector<double> sum(dim), sumsq(dim);
     std::vector<float> lo(dim), hi(dim);
@@ -1253,7 +1548,8 @@ uint64_t qamd_bin_quantized_vector_size(const qamd_vector_parameters *vp, qamd_b
 }
 
 uint64_t qamd_bin_quantized_vector_size_enc(const qamd_vector_parameters *vp, qamd_bits_store store, qamd_bin_encoding encoding) {
-    return row_bytes_of(encoding == QAMD_BIN_TWO_BITS ? 2 * vp->dim : vp->dim, store);
+    const uint64_t edim = encoder_dim(vp->dim, encoding);
+    return row_bytes_of((encoding & QAMD_BIN_TWO_BITS) ? 2 * edim : edim, store);
 }
 
 qamd_status qamd_bin_find_stats(const float *data, qamd_mem data_mem, uint64_t n_rows, uint64_t dim, void *stream, uint64_t *n,
@@ -1295,11 +1591,11 @@ qamd_status qamd_bin_encode_enc(const float *data, qamd_mem data_mem, const qamd
     QAMD_TRY(new_store(vp, store, encoding, h));
     if (lo) {
         QAMD_TRY(set_thresholds(h.get(), lo, hi, s));
-    } else if (encoding == QAMD_BIN_TWO_BITS) {  // one pass over the data for the statistics, then the rows
+    } else if (h->two()) {  // one pass over the data (rotated rows: over y) for the statistics, then the rows
         BinStats st;
         DevBuf stage;
-        QAMD_TRY(st.begin(vp->dim));
-        QAMD_TRY(stats_feed(st, data, data_mem, vp->count, stage, s, stop, stop_user));
+        QAMD_TRY(st.begin(h->edim));
+        QAMD_TRY(stats_feed(st, data, data_mem, vp->count, stage, s, stop, stop_user, h->rotated() ? vp->dim : 0));
         QAMD_TRY(set_thresholds_from_stats(h.get(), st, s));
     }
     QAMD_TRY(encode_all(h.get(), data, data_mem, stop, stop_user, s));
@@ -1333,8 +1629,8 @@ qamd_status qamd_bin_get_encoding(const qamd_bin *h, qamd_bin_encoding *encoding
 
 qamd_status qamd_bin_get_thresholds(const qamd_bin *h, float *lo, float *hi) {
     if (!h || !lo || !hi) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    if (h->encoding != QAMD_BIN_TWO_BITS) return fail(QAMD_ERR_ARGUMENTS, "one-bit rows have no thresholds");
-    const uint64_t dim = h->vp.dim;
+    if (!h->two()) return fail(QAMD_ERR_ARGUMENTS, "one-bit rows have no thresholds");
+    const uint64_t dim = h->edim;
     if (dim) {
         memcpy(lo, h->thr_host.data(), dim * 4);
         memcpy(hi, h->thr_host.data() + dim, dim * 4);
@@ -1385,13 +1681,14 @@ qamd_status qamd_bin_save(const qamd_bin *h, const char *data_path, const char *
     for (float t : h->thr_host)
         if (!(fabsf(t) < __builtin_huge_valf())) return fail(QAMD_ERR_IO, "an infinite threshold has no form in the metadata file");
     std::string js = "{\"vector_parameters\":" + vector_parameters_json(h->vp);
-    if (h->encoding == QAMD_BIN_TWO_BITS) {  // (a one-bit file stays the reference's, byte for byte)
-        js += ",\"encoding\":\"TwoBits\",\"thresholds\":{";
+    if (h->encoding == QAMD_BIN_ONE_BIT_ROTATED) js += ",\"encoding\":\"OneBitRotated\"";
+    if (h->two()) {  // (a one-bit file stays the reference's, byte for byte)
+        js += h->rotated() ? ",\"encoding\":\"TwoBitsRotated\",\"thresholds\":{" : ",\"encoding\":\"TwoBits\",\"thresholds\":{";
         for (int side = 0; side < 2; side++) {
             js += side ? ",\"hi\":[" : "\"lo\":[";
-            for (uint64_t i = 0; i < h->vp.dim; i++) {
+            for (uint64_t i = 0; i < h->edim; i++) {
                 if (i) js += ",";
-                js += json_f32(h->thr_host[side * h->vp.dim + i]);
+                js += json_f32(h->thr_host[side * h->edim + i]);
             }
             js += "]";
         }
@@ -1422,36 +1719,42 @@ qamd_status qamd_bin_load(const char *data_path, const char *meta_path, const qa
     for (const auto &m : root.members) {
         if (m.first != "encoding") continue;
         if (m.second.kind == JsonValue::String && m.second.text == "TwoBits") encoding = QAMD_BIN_TWO_BITS;
+        else if (m.second.kind == JsonValue::String && m.second.text == "OneBitRotated") encoding = QAMD_BIN_ONE_BIT_ROTATED;
+        else if (m.second.kind == JsonValue::String && m.second.text == "TwoBitsRotated") encoding = QAMD_BIN_TWO_BITS_ROTATED;
         else if (m.second.kind != JsonValue::String || m.second.text != "OneBit")
             return fail(QAMD_ERR_IO, "%s: unknown encoding", meta_path);
     }
-    if (encoding == QAMD_BIN_TWO_BITS) {
+    if ((encoding & QAMD_BIN_ROTATED) && vp->dim > kRotMaxDim)
+        return fail(QAMD_ERR_IO, "%s: rotated rows of %llu dimensions", meta_path, (unsigned long long)vp->dim);
+    const uint64_t edim = encoder_dim(vp->dim, encoding);  // thresholds of a rotated file have P entries
+    if (encoding & QAMD_BIN_TWO_BITS) {
         std::string err;
         const JsonValue *tj = json_field(root, "thresholds", err);
         if (!tj) return fail(QAMD_ERR_IO, "%s: TwoBits: %s", meta_path, err.c_str());
         if (vp->dim > kTwoBitMaxDim) return fail(QAMD_ERR_IO, "%s: two-bit rows of %llu dimensions", meta_path, (unsigned long long)vp->dim);
-        thr.resize(2 * vp->dim);
+        thr.resize(2 * edim);
         for (int side = 0; side < 2; side++) {
             const JsonValue *a = json_field(*tj, side ? "hi" : "lo", err);
             if (!a) return fail(QAMD_ERR_IO, "%s: thresholds: %s", meta_path, err.c_str());
-            if (a->kind != JsonValue::Array || a->items.size() != vp->dim)
-                return fail(QAMD_ERR_IO, "%s: thresholds: expected %llu values per side", meta_path, (unsigned long long)vp->dim);
-            for (uint64_t i = 0; i < vp->dim; i++)
-                if (!json_number_as_f32(a->items[i], thr[side * vp->dim + i], err))
+            if (a->kind != JsonValue::Array || a->items.size() != edim)
+                return fail(QAMD_ERR_IO, "%s: thresholds: expected %llu values per side", meta_path, (unsigned long long)edim);
+            for (uint64_t i = 0; i < edim; i++)
+                if (!json_number_as_f32(a->items[i], thr[side * edim + i], err))
                     return fail(QAMD_ERR_IO, "%s: thresholds: %s", meta_path, err.c_str());
         }
-        for (uint64_t i = 0; i < vp->dim; i++)
-            if (!(thr[i] <= thr[vp->dim + i])) return fail(QAMD_ERR_IO, "%s: thresholds: lo > hi at %llu", meta_path, (unsigned long long)i);
+        for (uint64_t i = 0; i < edim; i++)
+            if (!(thr[i] <= thr[edim + i])) return fail(QAMD_ERR_IO, "%s: thresholds: lo > hi at %llu", meta_path, (unsigned long long)i);
     }
     std::string bytes;
-    const uint64_t code_bits = encoding == QAMD_BIN_TWO_BITS ? 2 * vp->dim : vp->dim;
+    const uint64_t code_bits = (encoding & QAMD_BIN_TWO_BITS) ? 2 * edim : edim;
     QAMD_TRY(load_rows_file(data_path, row_bytes_of(code_bits, store) * vp->count, bytes));  // :277-279
     qamd_vector_parameters eff = file_vp;  // metadata rules the metric, the caller's params the sizes
     eff.dim = vp->dim;
     eff.count = vp->count;
-    if (encoding == QAMD_BIN_TWO_BITS)
-        return qamd_bin_from_rows_enc(reinterpret_cast<const uint8_t *>(bytes.data()), QAMD_MEM_HOST, &eff, store, QAMD_BIN_TWO_BITS,
-                                      thr.data(), thr.data() + vp->dim, nullptr, out);
+    if (encoding != QAMD_BIN_ONE_BIT)
+        return qamd_bin_from_rows_enc(reinterpret_cast<const uint8_t *>(bytes.data()), QAMD_MEM_HOST, &eff, store,
+                                      (qamd_bin_encoding)encoding, thr.empty() ? nullptr : thr.data(),
+                                      thr.empty() ? nullptr : thr.data() + edim, nullptr, out);
     return qamd_bin_from_rows(reinterpret_cast<const uint8_t *>(bytes.data()), QAMD_MEM_HOST, &eff, store, nullptr,
                               out);
 }
@@ -1470,19 +1773,23 @@ static qamd_status encode_query(const qamd_bin *h, const float *query, uint64_t 
                                 bool weighted, void *stream, qamd_bin_query **query_io) {
     if (bits != 1 && bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
     if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    const bool two = h->encoding == QAMD_BIN_TWO_BITS;  // the row's thresholds and layout
+    const bool two = h->two();  // the row's thresholds and layout
     if (bits != 1 && two && !weighted)
         return fail(QAMD_ERR_ARGUMENTS, "two-bit rows take scalar queries through qamd_bin_encode_query_scalar_w");
     if (two && qdim != h->vp.dim)
         return fail(QAMD_ERR_ARGUMENTS, "a query of %llu dimensions against thresholds of %llu", (unsigned long long)qdim,
                     (unsigned long long)h->vp.dim);
+    if (h->rotated() && qdim != h->vp.dim)
+        return fail(QAMD_ERR_ARGUMENTS, "a query of %llu dimensions against rotated rows of %llu", (unsigned long long)qdim,
+                    (unsigned long long)h->vp.dim);
+    const uint64_t edim = encoder_dim(qdim, h->encoding);  // a rotated query is encoded as P values
     const uint64_t max_dim = scalar_max_dim(bits, two);
-    if (bits != 1 && qdim > max_dim)
+    if (bits != 1 && edim > max_dim)
         return fail(QAMD_ERR_ARGUMENTS, "a %u-bit query has at most %llu dimensions, not %llu", bits,
-                    (unsigned long long)max_dim, (unsigned long long)qdim);
+                    (unsigned long long)max_dim, (unsigned long long)edim);
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
-    const uint64_t nb = row_bytes_of(two ? 2 * qdim : qdim, h->store), ds = device_stride_of(nb);
+    const uint64_t nb = row_bytes_of(two ? 2 * edim : edim, h->store), ds = device_stride_of(nb);
     const uint64_t max_abs_at = scalar_max_abs_at(ds, bits), need = max_abs_at + 16 + qdim * 4 + 16;
     qamd_bin_query *q = *query_io;
     std::unique_ptr<qamd_bin_query> fresh;
@@ -1508,8 +1815,8 @@ static qamd_status encode_query(const qamd_bin *h, const float *query, uint64_t 
     if (bits == 1)
         launch_bit_encoder(h, q_dev, 1, qdim, ds / 4, q->buf.as<uint32_t>(), 0, s);
     else
-        launch_scalar_encoder(h, q_dev, 1, qdim, ds, bits, q->buf.as<uint32_t>(), 0,
-                              reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at), nullptr, 0, s);
+        QAMD_TRY(launch_scalar_encoder(h, q_dev, 1, qdim, ds, bits, q->buf.as<uint32_t>(), 0,
+                                       reinterpret_cast<float *>(q->buf.as<uint8_t>() + max_abs_at), nullptr, 0, s));
     QAMD_HIP(hipGetLastError());
     QAMD_TRY(q->ready.record(s));
     if (fresh) *query_io = fresh.release();
@@ -2728,20 +3035,24 @@ static qamd_status encode_query_batch(const qamd_bin *h, const float *queries, u
                                       qamd_bin_query_batch **batch_io) {
     if (bits != 1 && bits != 4 && bits != 8) return fail(QAMD_ERR_ARGUMENTS, "query bits must be 1, 4 or 8, not %u", bits);
     if (!h || !batch_io || (!queries && n_queries && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    const bool two = h->encoding == QAMD_BIN_TWO_BITS;
+    const bool two = h->two();
     if (bits != 1 && two && !weighted)
         return fail(QAMD_ERR_ARGUMENTS, "two-bit rows take scalar queries through qamd_bin_encode_query_batch_scalar_w");
     if (two && n_queries && qdim != h->vp.dim)
         return fail(QAMD_ERR_ARGUMENTS, "queries of %llu dimensions against thresholds of %llu", (unsigned long long)qdim,
                     (unsigned long long)h->vp.dim);
+    if (h->rotated() && n_queries && qdim != h->vp.dim)
+        return fail(QAMD_ERR_ARGUMENTS, "queries of %llu dimensions against rotated rows of %llu", (unsigned long long)qdim,
+                    (unsigned long long)h->vp.dim);
+    const uint64_t edim = encoder_dim(qdim, h->encoding);  // rotated queries are encoded as P values
     const uint64_t max_dim = scalar_max_dim(bits, two);  // as the single query: code_bits * L stays exact in f32
-    if (bits != 1 && qdim > max_dim)
+    if (bits != 1 && edim > max_dim)
         return fail(QAMD_ERR_ARGUMENTS, "a %u-bit query has at most %llu dimensions, not %llu", bits,
-                    (unsigned long long)max_dim, (unsigned long long)qdim);
+                    (unsigned long long)max_dim, (unsigned long long)edim);
     if (bits != 1 && n_queries > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "too many queries");  // one workgroup each
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
-    const uint64_t nb = row_bytes_of(two ? 2 * qdim : qdim, h->store), ds = device_stride_of(nb);
+    const uint64_t nb = row_bytes_of(two ? 2 * edim : edim, h->store), ds = device_stride_of(nb);
     if (n_queries && nb != h->nb)
         return fail(QAMD_ERR_ARGUMENTS, "queries have %llu bytes, rows have %llu", (unsigned long long)nb,
                     (unsigned long long)h->nb);
@@ -2775,8 +3086,8 @@ static qamd_status encode_query_batch(const qamd_bin *h, const float *queries, u
         if (bits == 1)
             launch_bit_encoder(h, static_cast<const float *>(qd), n_queries, qdim, p_stride / 4, b->planes.as<uint32_t>(), 0, s);
         else
-            launch_scalar_encoder(h, static_cast<const float *>(qd), n_queries, qdim, ds, bits, b->planes.as<uint32_t>(), p_stride,
-                                  b->max_abs.as<float>(), b->codes.as<int8_t>(), code_pitch, s);
+            QAMD_TRY(launch_scalar_encoder(h, static_cast<const float *>(qd), n_queries, qdim, ds, bits, b->planes.as<uint32_t>(),
+                                           p_stride, b->max_abs.as<float>(), b->codes.as<int8_t>(), code_pitch, s));
         QAMD_HIP(hipGetLastError());
         if (staged) QAMD_HIP(hipStreamSynchronize(s));
     }
@@ -3024,9 +3335,9 @@ qamd_status qamd_bin_encoder_begin_enc(const qamd_vector_parameters *vp, qamd_bi
     QAMD_TRY(new_store(vp, store, encoding, e->h));
     if (lo) {
         QAMD_TRY(set_thresholds(e->h.get(), lo, hi, e->stream));
-    } else if (encoding == QAMD_BIN_TWO_BITS) {
+    } else if (e->h->two()) {
         e->learns = e->learning = true;
-        QAMD_TRY(e->stats.begin(vp->dim));
+        QAMD_TRY(e->stats.begin(e->h->edim));
     }
     *out = e.release();
     return QAMD_OK;
@@ -3039,7 +3350,8 @@ qamd_status qamd_bin_encoder_observe(qamd_bin_encoder *e, const float *batch, ui
     if (!e->learning) return fail(QAMD_ERR_ARGUMENTS, "observe after push");
     if (e->observed + n_rows > e->h->count) return count_mismatch(e->observed + n_rows, e->h->count);
     QAMD_ON_DEVICE(e->device);
-    QAMD_TRY(stats_feed(e->stats, batch, batch_mem, n_rows, e->stage, e->stream, e->stop, e->stop_user));
+    QAMD_TRY(stats_feed(e->stats, batch, batch_mem, n_rows, e->stage, e->stream, e->stop, e->stop_user,
+                        e->h->rotated() ? e->h->vp.dim : 0));
     e->observed += n_rows;
     return QAMD_OK;
 }

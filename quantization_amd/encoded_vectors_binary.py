@@ -23,10 +23,33 @@ class BitsStoreType(enum.IntEnum):
 
 class BinaryEncoding(enum.IntEnum):
     """Bits kept per stored dimension.  TwoBits has no counterpart in the reference: two compares per dimension against
-    thresholds mean -+ t * deviation of that dimension's data."""
+    thresholds mean -+ t * deviation of that dimension's data.  The Rotated kinds (no counterpart
+    either) put a randomized Hadamard rotation before the bits: a vector of dim becomes one of P values, P
+    the power of two at or above dim (dim <= 16384), and the store is served as a plain store of P dimensions."""
 
     OneBit = 0
     TwoBits = 1
+    OneBitRotated = 4
+    TwoBitsRotated = 5
+
+    @property
+    def two_bits(self) -> bool:
+        return bool(self.value & 1)
+
+    @property
+    def rotated(self) -> bool:
+        return bool(self.value & 4)
+
+    def encoder_dim(self, dim: int) -> int:
+        """The dimensions the bits are taken from: dim, or P of a rotated encoding."""
+        return _encoder_dim(self, dim)
+
+
+def _encoder_dim(encoding, dim: int) -> int:
+    """encoder_dim for an encoding given as any integer (an unknown one is the library's to refuse)."""
+    if not int(encoding) & 4 or dim <= 1:
+        return dim
+    return 1 << (dim - 1).bit_length()
 
 
 def _thresholds_arg(thresholds, dim: int):
@@ -109,6 +132,7 @@ class EncodedVectorsBin(EncodedVectorsBase):
         enc = C.c_int()
         check(_lib.lib().qamd_bin_get_encoding(self._h, C.byref(enc), None))
         self._encoding = BinaryEncoding(enc.value)
+        self._edim = self._encoding.encoder_dim(vector_parameters.dim)
 
     @property
     def encoding(self) -> BinaryEncoding:
@@ -116,12 +140,19 @@ class EncodedVectorsBin(EncodedVectorsBase):
 
     @property
     def thresholds(self):
-        """(lo, hi), dim f32 entries each, of a two-bit store; None for one bit."""
-        if self._encoding != BinaryEncoding.TwoBits:
+        """(lo, hi), dim f32 entries each (P each for rotated rows), of a two-bit store; None for one bit."""
+        if not self._encoding.two_bits:
             return None
-        lo, hi = np.zeros(self._vp.dim, dtype=np.float32), np.zeros(self._vp.dim, dtype=np.float32)
+        lo, hi = np.zeros(self._edim, dtype=np.float32), np.zeros(self._edim, dtype=np.float32)
         check(_lib.lib().qamd_bin_get_thresholds(self._h, C.c_void_p(lo.ctypes.data), C.c_void_p(hi.ctypes.data)))
         return lo, hi
+
+    @property
+    def code_bits(self) -> int:
+        """Bits of a stored row: dim, 2 dim, or P and 2 P of the rotated encodings."""
+        bits = C.c_uint64()
+        check(_lib.lib().qamd_bin_get_encoding(self._h, None, C.byref(bits)))
+        return int(bits.value)
 
     @property
     def vector_parameters(self) -> VectorParameters:
@@ -129,8 +160,10 @@ class EncodedVectorsBin(EncodedVectorsBase):
 
     @property
     def metadata(self) -> dict:
-        if self._encoding == BinaryEncoding.TwoBits:
+        if self._encoding.two_bits:
             return {"vector_parameters": self._vp, "encoding": self._encoding, "thresholds": self.thresholds}
+        if self._encoding.rotated:
+            return {"vector_parameters": self._vp, "encoding": self._encoding}
         return {"vector_parameters": self._vp}  # :21-24
 
     @classmethod
@@ -138,14 +171,15 @@ class EncodedVectorsBin(EncodedVectorsBase):
                store: BitsStoreType = BitsStoreType.U8, stream=None,
                encoding: BinaryEncoding = BinaryEncoding.OneBit, thresholds=None) -> "EncodedVectorsBin":
         """EncodedVectorsBin::<TBitsStoreType, _>::encode (:165-191).  encoding = TwoBits: `thresholds` = (lo, hi), or
-        None to take them from the data (find_stats, then thresholds_from_stats with t = 0.43)."""
+        None to take them from the data (find_stats, then thresholds_from_stats with t = 0.43).  OneBitRotated /
+        TwoBitsRotated: the same on the rotated vectors, thresholds of P entries."""
         data = flatten_rows(orig_data, vector_parameters.dim)
         validate(data, vector_parameters)
         vp = vector_parameters.to_c()
         buf = in_buf(data, np.float32)
         stop = make_stop(stop_condition)
         out = C.c_void_p()
-        keep, lo, hi = _thresholds_arg(thresholds, vector_parameters.dim)
+        keep, lo, hi = _thresholds_arg(thresholds, _encoder_dim(encoding, vector_parameters.dim))
         with creating_on(data) as dev:
             check(_lib.lib().qamd_bin_encode_enc(buf.ptr, buf.mem, C.byref(vp), int(store), int(encoding), lo, hi, stop,
                                                  None, stream_ptr(stream), C.byref(out)))
@@ -232,12 +266,12 @@ class EncodedVectorsBin(EncodedVectorsBase):
         stop = make_stop(stop_condition)
         first = next(iter(make_batches()), None)
         enc = C.c_void_p()
-        keep, lo, hi = _thresholds_arg(thresholds, vector_parameters.dim)
+        keep, lo, hi = _thresholds_arg(thresholds, _encoder_dim(encoding, vector_parameters.dim))
         with creating_on(first) as dev:
             check(L.qamd_bin_encoder_begin_enc(C.byref(vp), int(store), int(encoding), lo, hi, stop, None,
                                                stream_ptr(stream), C.byref(enc)))
         passes = [L.qamd_bin_encoder_push]
-        if encoding == BinaryEncoding.TwoBits and thresholds is None:
+        if int(encoding) in (BinaryEncoding.TwoBits, BinaryEncoding.TwoBitsRotated) and thresholds is None:
             passes.insert(0, L.qamd_bin_encoder_observe)
         try:
             for feed in passes:
@@ -264,7 +298,7 @@ class EncodedVectorsBin(EncodedVectorsBase):
         vp = vector_parameters.to_c()
         buf = in_buf(rows, np.uint8)
         out = C.c_void_p()
-        keep, lo, hi = _thresholds_arg(thresholds, vector_parameters.dim)
+        keep, lo, hi = _thresholds_arg(thresholds, _encoder_dim(encoding, vector_parameters.dim))
         with creating_on(rows) as dev:
             check(_lib.lib().qamd_bin_from_rows_enc(buf.ptr, buf.mem, C.byref(vp), int(store), int(encoding), lo, hi,
                                                     stream_ptr(stream), C.byref(out)))

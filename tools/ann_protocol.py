@@ -176,10 +176,12 @@ def main():
                     help="binary: also search with 4- / 8-bit scalar queries against the same rows, e.g. 1,4,8; each bit "
                          "count past 1 adds a gpu_query_bits_N entry to a one-bit record (DESIGN 3.2d) and a "
                          "gpu_weighted_query_bits_N entry - weighted queries, DESIGN 3.2f - to a two-bit record")
-    ap.add_argument("--bin-encodings", default="one", metavar="one[,two[,two:T]]",
+    ap.add_argument("--bin-encodings", default="one", metavar="one[,two[,two:T[,one:rot[,two:rot]]]]",
                     help="binary: a record per row encoding: one = the reference's sign bit; two = two-bit rows with "
                          "thresholds mean -+ 0.43 deviations per dimension (DESIGN 3.2e); two:T = the same with t = T.  "
-                         "Two-bit records have no CPU loop (the oracle restates the reference); with --bin-query-bits "
+                         "one:rot / two:rot = the same two behind the randomized Hadamard rotation of DESIGN 3.2g (two:rot "
+                         "with t = 0.43, thresholds from the rotated data).  "
+                         "Two-bit and rotated records have no CPU loop (the oracle restates the reference); with --bin-query-bits "
                          "4,8 they carry weighted scalar-query entries")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -232,6 +234,12 @@ def main():
                         if how == "one":
                             variants.append(("binary", qa.EncodedVectorsBin.encode(data, vp), {}))
                             continue
+                        if how in ("one:rot", "two:rot"):
+                            two = how == "two:rot"
+                            code = qa.BinaryEncoding.TwoBitsRotated if two else qa.BinaryEncoding.OneBitRotated
+                            variants.append((f"binary {'two-bit' if two else 'one-bit'} rotated rows",
+                                             qa.EncodedVectorsBin.encode(data, vp, encoding=code), {"two_bit": two, "rotated": True}))
+                            continue
                         t = float(how.split(":")[1]) if ":" in how else 0.43
                         thr = qa.EncodedVectorsBin.thresholds_from_stats(*qa.EncodedVectorsBin.find_stats(data), t)
                         enc = qa.EncodedVectorsBin.encode(data, vp, encoding=qa.BinaryEncoding.TwoBits, thresholds=thr)
@@ -257,7 +265,7 @@ def main():
                             enc.topk_rescored(enc.encode_query(q_host[0]), orig, q_host[0], 30, args.rescore, largest=largest)
                         rec["gpu_rescored"] = run_gpu_rescored(enc, orig, q_host, truth, largest, args.rescore)
                         rec["gpu_rescored"]["orig_dtype"] = orig.dtype
-                    if args.cpu_queries > 0 and not extra.get("two_bit"):
+                    if args.cpu_queries > 0 and not extra.get("two_bit") and not extra.get("rotated"):
                         rec["cpu_oracle_loop"] = run_cpu(kind, enc, q_host[: args.cpu_queries], truth, largest, gpu_ids, extra)
                     emit(rec)
                 del variants
