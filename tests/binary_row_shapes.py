@@ -132,14 +132,22 @@ def small_tile_least(ds):
     return tile, round_up(max(16 * tile, (128 * 1024) // ds, tile), tile)
 
 
-def small_plan(n, k, ds, planes=1, cus=256):
-    """(workgroups, rows per workgroup) of the single launch, None where it does not apply."""
-    if small_shape(ds, planes) is None or n == 0 or n > 2 << 20 or k == 0 or k > 64:
+def small_topk_plan(n, k, tile, min_rows_per_wg, cus=256):
+    """topk.hip small_topk_plan: (workgroups, rows per workgroup), None where the single launch does not apply."""
+    if n == 0 or n > 2 << 20 or k == 0 or k > 64:
         return None
-    tile, least = small_tile_least(ds)
+    least = round_up(max(min_rows_per_wg, tile), tile)
     wgs = min(cus, 256, -(-n // least))
     per = round_up(-(-n // wgs), tile)
     return -(-n // per), per
+
+
+def small_plan(n, k, ds, planes=1, cus=256):
+    """(workgroups, rows per workgroup) of the single launch, None where it does not apply."""
+    if small_shape(ds, planes) is None:
+        return None
+    tile, least = small_tile_least(ds)
+    return small_topk_plan(n, k, tile, least, cus)
 
 
 def small_rows(ds):

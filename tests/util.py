@@ -597,3 +597,67 @@ def pq_special_case(dim: int, chunk: int):
         data[i, :] = f32(value)
         want[i, :] = code
     return data, np.ascontiguousarray(cen), want
+
+
+# ------------------------------------------------------------------ product quantizer: stores the row-shape tests own
+# Shared by tests/test_pq_row_shapes_model.py (which proves on the oracle alone that a chunk read too many or too few
+# changes the bits of these stores) and tests/test_gpu_pq_row_shapes.py.
+PQ_ZERO_CODES = (77, 200)  # all-zero centroids: +0.0 and -0.0 (invert) entries in every chunk table.  Never code 0: the
+                           # zero padding of a device row reads table entry 0, which has to count when it is added.
+DIST_IDS = {"Dot": 0, "L1": 1, "L2": 2}
+
+
+def pq_shape_store(m, n, chunk=4, seed=0):
+    """(rows u8 [n, m], centroids f32 [256, dim], dim, chunk size): random codes, centroids in (-0.5, 0.5) with the
+    PQ_ZERO_CODES centroids zero, a last chunk one dimension short (chunk > 1).  Row 0 is all code 0, row 1 all 255 and
+    row 2 all PQ_ZERO_CODES[0], so every chunk table is read at its first, last and a zero entry.  In every other row
+    the last chunk walks a random order of the other 252 codes: leaving the last chunk out then changes the score of
+    every such row under Dot too (no zero centroid), and against a stored row (whose table is zero at its own code
+    under L1 and L2) of all but one row in 252.  A store of fewer rows is a prefix."""
+    dim = m * chunk - 1 if chunk > 1 else m
+    rng = np.random.default_rng(100_003 * m + 17 * chunk + seed)
+    cen = (rng.random((256, dim), dtype=np.float32) - np.float32(0.5)).astype(np.float32)
+    cen[list(PQ_ZERO_CODES)] = 0.0
+    others = rng.permutation([c for c in range(256) if c not in (0, 255) + PQ_ZERO_CODES]).astype(np.uint8)
+    rows = rng.integers(0, 256, size=(n, m), dtype=np.uint8)
+    rows[0], rows[1], rows[2] = 0, 255, PQ_ZERO_CODES[0]
+    rows[3:, m - 1] = others[np.arange(n - 3) % others.size]
+    return rows, cen, dim, chunk
+
+
+def pq_shape_queries(dim, count, seed=0):
+    """f32 [count, dim] in (-0.5, 0.5) with a last dimension of at least 0.25: the short last chunk is never a zero."""
+    q = (np.random.default_rng(7_000_003 + 31 * dim + seed).random((count, dim), dtype=np.float32) - np.float32(0.5)).astype(np.float32)
+    q[:, dim - 1] = np.abs(q[:, dim - 1]) + np.float32(0.25)
+    return q
+
+
+def pq_row_table(rows, cen, dim, chunk, dist, i):
+    """f32 [m, 256]: entry (c, code) = the metric of centroid rows[i][c] and centroid `code` over chunk c, summed in
+    dimension order in f32 from 0.0 (score_internal's inner loop, encoded_vectors_pq.rs:566-593); not inverted."""
+    m = rows.shape[1]
+    cen = np.ascontiguousarray(cen, dtype=np.float32)
+    table = np.zeros((m, 256), dtype=np.float32)
+    name = getattr(dist, "name", str(dist))
+    for c in range(m):
+        lo, hi = c * chunk, min(c * chunk + chunk, dim)
+        a, b = cen[int(rows[i, c]), lo:hi], cen[:, lo:hi]
+        s = np.zeros(256, dtype=np.float32)
+        for t in range(hi - lo):
+            if name == "Dot":
+                s = s + a[t] * b[:, t]
+            elif name == "L1":
+                s = s + np.abs(a[t] - b[:, t])
+            else:
+                d = a[t] - b[:, t]
+                s = s + d * d
+        table[c] = s
+    return table
+
+
+def pq_seq_scores(rows, table, invert, chunks=None):
+    """f32 [n]: score_internal of every row given row i's table - one running f32 sum in chunk order, negated once."""
+    total = np.zeros(rows.shape[0], dtype=np.float32)
+    for c in range(rows.shape[1] if chunks is None else chunks):
+        total = total + table[c][rows[:, c]]
+    return -total if invert else total
