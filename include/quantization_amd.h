@@ -925,14 +925,26 @@ QAMD_API void qamd_f32_free(qamd_f32 *h);
 /* out[p] = distance(query, row ids[p]) (encoded_vectors.rs:37-45), sign flipped for invert.
  * Buffer rules of the quantizers' *_score_ids: host ids are validated (an id >= count returns
  * QAMD_ERR_OUT_OF_RANGE), a device id >= count scores NaN; ids and out both in device memory and
- * a device query only enqueue.  A host query is copied first (synchronises `stream`). */
+ * a device query only enqueue.  A host query is copied first (synchronises `stream`).
+ *
+ * The whole store (score_all): a NULL id list stands for the rows 0, 1, ..., n_ids - 1, with n_ids <= count --
+ * `ids = NULL` makes out[j] the exact score of row j for j < n_ids, and n_ids = count scores every row.  The rows are
+ * then read in order by one scan (16-byte loads where the rows allow them) instead of gathered by id; every score is
+ * the list form's, bit for bit.  `ids_mem` is ignored.  n_ids > count returns QAMD_ERR_OUT_OF_RANGE before any launch;
+ * n_ids == 0 stays QAMD_OK.  A device query with a device `out` only enqueues; a host `out` goes through the calling
+ * thread's score workspace and synchronises `stream`.  qamd_f32_rerank and qamd_f32_rerank_batch take the same
+ * convention (below); qamd_f32_score_ids_batch does not.  Out of scope for the null-list forms: sharded handles (scan
+ * each shard's originals and merge with qamd_topk_merge); qamd_f32_score_ids_batch, which keeps requiring its lists;
+ * a scores-of-all-queries output (a batch returns its k best only: call this once per query for the scores);
+ * *_topk_rescored and *_topk_batch_rescored, which are unchanged. */
 QAMD_API qamd_status qamd_f32_score_ids(const qamd_f32 *h, const float *query, uint64_t qdim,
                                         qamd_mem query_mem, const uint32_t *ids, uint64_t n_ids,
                                         qamd_mem ids_mem, float *out, qamd_mem out_mem, void *stream);
 /* Many (query, id list) pairs in one launch, as *_score_ids_batch: list l =
  * ids[list_offsets[l] .. list_offsets[l + 1]) is scored against query l of `queries`
  * ([n_queries][qdim] f32, n_lists <= n_queries); out[p] = distance(query l, row ids[p])
- * (encoded_vectors.rs:37-45).  Device lists need a device output. */
+ * (encoded_vectors.rs:37-45).  Device lists need a device output.  The lists are required here: the null-list
+ * convention of qamd_f32_score_ids does not extend to this call (null lists with n_ids > 0 return QAMD_ERR_ARGUMENTS). */
 QAMD_API qamd_status qamd_f32_score_ids_batch(const qamd_f32 *h, const float *queries,
                                               uint64_t n_queries, uint64_t qdim, qamd_mem queries_mem,
                                               const uint32_t *list_offsets, uint32_t n_lists,
@@ -948,13 +960,27 @@ QAMD_API qamd_status qamd_f32_score_ids_batch(const qamd_f32 *h, const float *qu
  * pattern (ascending -NaN < -inf < negative finite < -0 < +0 < positive finite < +inf < +NaN, equal bit patterns to
  * the lower id); exact scores of rows that hold inf or NaN, and the NaN of an id past the end, are ranked by it like
  * any other, and a returned score is the row's own score bits.  With every buffer in device memory the call only enqueues;
- * host outputs cost one download and synchronise `stream`. */
+ * host outputs cost one download and synchronise `stream`.
+ *
+ * The whole store (an exact top-k): a NULL id list stands for the rows 0, 1, ..., n_ids - 1, with n_ids <= count --
+ * `ids = NULL` returns the k best of the rows [0, n_ids) under the same ordering contract (the total order on score
+ * bits, ties to the lower id, best first, padding 0xFFFFFFFF with -inf / +inf when k > n_ids), from one scan of the
+ * rows and the exact select of *_topk over the calling thread's score workspace.  `ids_mem` is ignored; n_ids > count
+ * returns QAMD_ERR_OUT_OF_RANGE before any launch.  The limit of 8192 ids holds only for a list that is given;
+ * k <= 1024 holds for both.  This form may synchronise `stream` as *_topk does (host outputs always do).  Out of scope:
+ * sharded handles; qamd_f32_score_ids_batch; a scores-of-all-queries output; *_topk_rescored, which is unchanged
+ * (see qamd_f32_score_ids). */
 QAMD_API qamd_status qamd_f32_rerank(const qamd_f32 *h, const float *query, uint64_t qdim,
                                      qamd_mem query_mem, const uint32_t *ids, uint32_t n_ids,
                                      qamd_mem ids_mem, uint32_t k, int largest, uint32_t *out_ids,
                                      float *out_scores, qamd_mem out_mem, void *stream);
 /* The same for n_queries queries at once (encoded_vectors.rs:37-45): ids [n_queries][n_ids],
- * outputs [n_queries][k]. */
+ * outputs [n_queries][k].  With `ids = NULL` every one of the n_queries queries is ranked against the rows [0, n_ids),
+ * n_ids <= count (the convention of qamd_f32_rerank); the limit n_queries * n_ids < 2^32 of the list form does not
+ * apply.  The queries go in groups of up to 8 that share one pass over the rows; a group's scores take
+ * group * n_ids * 4 bytes of the calling thread's score workspace, and the group shrinks, down to 1 query, so that
+ * this stays within 512 MiB (more only when one query's n_ids * 4 bytes alone exceed it) -- never
+ * n_queries * n_ids. */
 QAMD_API qamd_status qamd_f32_rerank_batch(const qamd_f32 *h, const float *queries, uint64_t n_queries,
                                            uint64_t qdim, qamd_mem queries_mem, const uint32_t *ids,
                                            uint32_t n_ids, qamd_mem ids_mem, uint32_t k, int largest,

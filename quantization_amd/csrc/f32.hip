@@ -34,10 +34,13 @@
 //    widens the low half, adds its term, widens the high half, adds its term: the row's order.
 //  * The loads of the next segment are issued before the adds of the current one; the wave-uniform (scalar) query
 //    path and the per-lane path are those of the f32 kernel.
+// A NULL id list in qamd_f32_score_ids / qamd_f32_rerank / qamd_f32_rerank_batch stands for the rows 0 .. n_ids - 1 and
+// takes the whole-store scan of f32_scan.hip instead (rerank_scan below): rows in order, 1 to 8 queries per pass.
 // narrow_kernel: the F32 -> F16 / BF16 copy of qamd_f32_from_data_typed, a streaming kernel (16-byte loads, 8-byte
 // stores where the piece is aligned for them).
 #include "rescore.hpp"
 
+#include "f32_terms.hpp"
 #include "lists.hpp"
 #include "topk.hpp"
 
@@ -49,12 +52,6 @@ namespace {
 constexpr int kBlock = 256;      // 4 waves, each with its own tile
 constexpr int kSeg = 32;         // values of a row per pass
 constexpr int kTileStride = 33;  // dwords between two rows of a tile
-
-template <int METRIC> __device__ __forceinline__ float term(float q, float v) {
-    if (METRIC == QAMD_DOT) return q * v;
-    const float d = q - v;
-    return METRIC == QAMD_L1 ? __builtin_fabsf(d) : d * d;
-}
 
 // out[p] = distance(query of pair p, row ids[p]), negated for `invert`; NaN for an id >= count.
 // Pair p belongs to list l: offsets[l] <= p < offsets[l + 1], or l = p / per_list when offsets is null.
@@ -125,16 +122,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 }
 
 constexpr int kHalfSeg = 64;  // values of an f16 / bf16 row per pass: 128 bytes, 32 packed dwords
-
-// The two 16-bit values of a packed dword, widened exactly to f32.
-template <int DTYPE> __device__ __forceinline__ float widen_lo(uint32_t w) {
-    if (DTYPE == QAMD_DTYPE_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu));
-    return __uint_as_float(w << 16);
-}
-template <int DTYPE> __device__ __forceinline__ float widen_hi(uint32_t w) {
-    if (DTYPE == QAMD_DTYPE_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
-    return __uint_as_float(w & 0xFFFF0000u);
-}
 
 // f32_pairs_kernel for rows of 16-bit values (DTYPE: QAMD_DTYPE_F16 or QAMD_DTYPE_BF16).  ALIGNED: dim is even and
 // `data` is dword aligned, so every row starts on a dword.
@@ -323,6 +310,75 @@ qamd_status check_queries(const qamd_f32 *h, const float *queries, uint64_t qdim
     return QAMD_OK;
 }
 
+// n_rows <= count: what every null-list form checks before its first launch.
+qamd_status check_prefix(const qamd_f32 *h, uint64_t n_rows) {
+    if (n_rows > h->vp.count)
+        return fail(QAMD_ERR_OUT_OF_RANGE, "rows 0 .. %llu asked for, the store has %llu", (unsigned long long)n_rows,
+                    (unsigned long long)h->vp.count);
+    return QAMD_OK;
+}
+
+// Queries of a batch that share one pass over the rows and one score workspace of group * n_rows * 4 bytes: 8, or as
+// many as keep that workspace within kScanScoreCap, and at least 1.
+uint32_t scan_group(uint64_t n_queries, uint64_t n_rows) {
+    const uint64_t fit = kScanScoreCap / (std::max<uint64_t>(n_rows, 1) * 4);
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({8, n_queries, fit}));
+}
+
+// The re-rank entry points with a null id list: the k best of the rows 0 .. n_rows - 1 for every query, by one scan of
+// the rows per group of queries (f32_scan.hip) and the exact radix select over the group's scores.
+qamd_status rerank_scan(const qamd_f32 *h, const float *queries, uint64_t n_queries, uint64_t qdim, qamd_mem queries_mem,
+                        uint32_t n_rows, uint32_t k, int largest, uint32_t *out_ids, float *out_scores, qamd_mem out_mem,
+                        hipStream_t s) {
+    QAMD_TRY(check_queries(h, queries, qdim));
+    QAMD_TRY(check_prefix(h, n_rows));
+    if (n_queries > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "at most 2^32 - 1 queries per call");
+    QAMD_ON_DEVICE(h->device);
+    StreamBuf qstage;
+    const float *q_dev = nullptr;
+    QAMD_TRY(rescore_queries_view(queries, n_queries * qdim, queries_mem, qstage, s, &q_dev));
+    if (n_queries == 1)
+        return topk_classic(n_rows, k, largest, out_ids, out_scores, out_mem, s,
+                            [&](float *scores) { return f32_scan_launch(h, q_dev, 1, n_rows, scores, n_rows, s); });
+    const uint32_t group = scan_group(n_queries, n_rows);
+    const size_t n_out = (size_t)n_queries * k;
+    StreamBuf res;  // host outputs: results are assembled on the device, one download at the end
+    uint32_t *ids_dev = out_ids;
+    float *sc_dev = out_scores;
+    if (out_mem == QAMD_MEM_HOST) {
+        QAMD_TRY(res.alloc(n_out * 8, s));
+        ids_dev = res.as<uint32_t>();
+        sc_dev = reinterpret_cast<float *>(ids_dev + n_out);
+    }
+    float *scores = nullptr;
+    QAMD_TRY(thread_ws_acquire(WS_SCORES, (size_t)group * n_rows * 4, s, reinterpret_cast<void **>(&scores)));
+    void *sel = nullptr;
+    qamd_status st = thread_ws_acquire(WS_SELECT, round_up(topk_workspace_bytes(k), 256), s, &sel);
+    if (st != QAMD_OK) {
+        thread_ws_release(WS_SCORES, s);
+        return st;
+    }
+    for (uint64_t q0 = 0; q0 < n_queries && st == QAMD_OK; q0 += group) {  // the score workspace is reused in stream order
+        const uint32_t g = (uint32_t)std::min<uint64_t>(group, n_queries - q0);
+        st = f32_scan_launch(h, q_dev + q0 * qdim, g, n_rows, scores, n_rows, s);
+        for (uint32_t j = 0; j < g && st == QAMD_OK; j++)
+            st = topk_f32(scores + (size_t)j * n_rows, n_rows, k, largest != 0, ids_dev + (q0 + j) * k, sc_dev + (q0 + j) * k, sel, s);
+    }
+    bool synced = false;
+    if (st == QAMD_OK && out_mem == QAMD_MEM_HOST) {
+        std::vector<uint32_t> host(2 * n_out);
+        st = copy_out(host.data(), QAMD_MEM_HOST, ids_dev, n_out * 8, s);  // synchronises `s`
+        if (st == QAMD_OK) {
+            memcpy(out_ids, host.data(), n_out * 4);
+            memcpy(out_scores, host.data() + n_out, n_out * 4);
+            synced = true;
+        }
+    }
+    thread_ws_release(WS_SELECT, s, synced);
+    thread_ws_release(WS_SCORES, s, synced);
+    return st;
+}
+
 // The re-rank entry points: ids [n_queries][n_ids] from the caller, host or device.
 qamd_status rerank_any(const qamd_f32 *h, const float *queries, uint64_t n_queries, uint64_t qdim, qamd_mem queries_mem,
                        const uint32_t *ids, uint32_t n_ids, qamd_mem ids_mem, uint32_t k, int largest, uint32_t *out_ids,
@@ -330,8 +386,11 @@ qamd_status rerank_any(const qamd_f32 *h, const float *queries, uint64_t n_queri
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
     if (k == 0 || n_queries == 0) return QAMD_OK;
     if (k > 1024) return fail(QAMD_ERR_ARGUMENTS, "rerank: k=%u exceeds 1024", k);
-    if (n_ids > kRerankMaxIds) return fail(QAMD_ERR_ARGUMENTS, "rerank: %u ids per query exceed %u", n_ids, kRerankMaxIds);
-    if (!out_ids || !out_scores || (n_ids && !ids)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (ids && n_ids > kRerankMaxIds)  // what one candidate sort takes; the scan of a null list has no such limit
+        return fail(QAMD_ERR_ARGUMENTS, "rerank: %u ids per query exceed %u", n_ids, kRerankMaxIds);
+    if (!out_ids || !out_scores) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (!ids && n_ids)  // a null list stands for the rows 0 .. n_ids - 1
+        return rerank_scan(h, queries, n_queries, qdim, queries_mem, n_ids, k, largest, out_ids, out_scores, out_mem, s);
     QAMD_TRY(check_queries(h, queries, qdim));
     const uint64_t n_pairs = n_queries * n_ids;
     if (n_pairs > 0xFFFFFFFFull || n_queries > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "at most 2^32 - 1 ids per call");
@@ -523,13 +582,18 @@ qamd_status qamd_f32_score_ids(const qamd_f32 *h, const float *query, uint64_t q
                                uint64_t n_ids, qamd_mem ids_mem, float *out, qamd_mem out_mem, void *stream) {
     QAMD_TRY(check_queries(h, query, qdim));
     if (n_ids == 0) return QAMD_OK;
-    if (!ids || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (!out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (!ids) QAMD_TRY(check_prefix(h, n_ids));  // a null list stands for the rows 0 .. n_ids - 1
     if (n_ids > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "at most 2^32 - 1 ids per call");
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     StreamBuf qstage;
     const float *q_dev = nullptr;
     QAMD_TRY(rescore_queries_view(query, qdim, query_mem, qstage, s, &q_dev));
+    if (!ids) {  // the whole-store scan: no id array, the rows in order (f32_scan.hip)
+        auto scan = [&](float *out_dev) { return f32_scan_launch(h, q_dev, 1, n_ids, out_dev, n_ids, s); };
+        return out_mem == QAMD_MEM_DEVICE ? scan(out) : score_all_to_host(n_ids, out, s, scan);
+    }
     return run_ids(ids, n_ids, ids_mem, out, out_mem, h->vp.count, s, [&](const uint32_t *ids_dev, uint64_t n, float *out_dev) {
         return pairs_launch(h, q_dev, nullptr, 1, (uint32_t)n, ids_dev, n, out_dev, s);
     });

@@ -24,6 +24,9 @@ namespace qamd {
 
 constexpr uint32_t kRerankMaxIds = kTopkCandCap;  // ids per query: what one LDS sort takes (topk.hip)
 constexpr uint32_t kRerankPad = 0xFFFFFFFFu;      // the padding id of every top-k output: skipped
+// The score workspace of a null-list qamd_f32_rerank_batch: the queries of one pass over the rows (up to 8) keep
+// group * n_ids * 4 bytes of scores; the group shrinks, down to 1 query, so that this stays within the cap.
+constexpr uint64_t kScanScoreCap = 512ull << 20;
 
 // Exact best k of ids_dev[q][0..n_ids) for each of the n_queries queries (device memory, queries_dev
 // [n_queries][dim]), by the exact score; outputs [n_queries][k] in host or device memory, ordering contract of
@@ -35,6 +38,12 @@ inline size_t rerank_ws_bytes(uint32_t n_queries, uint32_t n_ids, uint32_t k, qa
 qamd_status rerank_device(const qamd_f32 *orig, const float *queries_dev, uint32_t n_queries, const uint32_t *ids_dev,
                           uint32_t n_ids, void *ws, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
                           qamd_mem out_mem, hipStream_t s);
+
+// The whole-store scan (f32_scan.hip): out_dev[q * pitch + row] = the exact score of query q and row `row`, for the
+// n_queries queries at queries_dev [n_queries][dim] and the rows 0 .. n_rows - 1 (n_rows <= count, the caller's check).
+// The rows are read once per 8 queries (a remainder in passes of 4, 2, 1).  Device memory; only enqueues on `s`.
+qamd_status f32_scan_launch(const qamd_f32 *orig, const float *queries_dev, uint32_t n_queries, uint64_t n_rows, float *out_dev,
+                            uint64_t pitch, hipStream_t s);
 
 // `queries` ([n_queries][dim] f32, host or device) as device memory: used in place, or staged into `stage`.
 qamd_status rescore_queries_view(const float *queries, uint64_t n_floats, qamd_mem mem, StreamBuf &stage, hipStream_t s,

@@ -206,6 +206,47 @@ class OriginalVectors:
             return ret_ids.reshape(nq, k), ret_sc.reshape(nq, k)
         return ret_ids, ret_sc
 
+    # ------------------------------------------------------------------ the whole store: a null id list = rows 0 .. count - 1
+    def score_all(self, query, out=None, stream=None):
+        """scores[i] = distance(query, row i) for every row, exact: one scan of the rows in order, where
+        score_ids(query, arange(count)) gathers them by id."""
+        check_same_device(self._device, out)
+        qb = self._query(query)
+        n = self.count
+        buf, ret = out_buf(out, n, np.float32)
+        check(_lib.lib().qamd_f32_score_ids(self._h, qb.ptr, _count(query), qb.mem, None, n, _lib.MEM_DEVICE, buf.ptr, buf.mem,
+                                            stream_ptr(stream)))
+        return ret
+
+    def topk(self, query, k: int, largest: bool = True, out_ids=None, out_scores=None, stream=None):
+        """The best k rows of the whole store by exact score (an exact, brute-force search): best first, ties to the
+        lower row id, padded with 0xFFFFFFFF and -inf / +inf when k > count.  Returns (ids, scores)."""
+        check_same_device(self._device, out_ids, out_scores)
+        qb = self._query(query)
+        ob, ret_ids = out_buf(out_ids, k, np.uint32)
+        sb, ret_sc = out_buf(out_scores, k, np.float32)
+        if ob.mem != sb.mem:
+            raise ValueError("out_ids and out_scores must both be host or both be device buffers")
+        check(_lib.lib().qamd_f32_rerank(self._h, qb.ptr, _count(query), qb.mem, None, self.count, _lib.MEM_DEVICE, int(k),
+                                         int(bool(largest)), ob.ptr, sb.ptr, sb.mem, stream_ptr(stream)))
+        return ret_ids, ret_sc
+
+    def topk_batch(self, queries, k: int, largest: bool = True, out_ids=None, out_scores=None, stream=None):
+        """topk for queries [n_queries, dim]: up to 8 queries share each pass over the rows.  Returns [n_queries, k]
+        ids and scores."""
+        check_same_device(self._device, out_ids, out_scores)
+        nq, qdim = int(queries.shape[0]), int(queries.shape[1])
+        qb = self._query(queries)
+        ob, ret_ids = out_buf(out_ids, nq * k, np.uint32)
+        sb, ret_sc = out_buf(out_scores, nq * k, np.float32)
+        if ob.mem != sb.mem:
+            raise ValueError("out_ids and out_scores must both be host or both be device buffers")
+        check(_lib.lib().qamd_f32_rerank_batch(self._h, qb.ptr, nq, qdim, qb.mem, None, self.count, _lib.MEM_DEVICE, int(k),
+                                               int(bool(largest)), ob.ptr, sb.ptr, sb.mem, stream_ptr(stream)))
+        if isinstance(ret_ids, np.ndarray):
+            return ret_ids.reshape(nq, k), ret_sc.reshape(nq, k)
+        return ret_ids, ret_sc
+
     def __del__(self):
         if getattr(self, "_h", None):
             try:
