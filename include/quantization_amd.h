@@ -205,7 +205,10 @@ QAMD_API qamd_status qamd_u8_score_internal(const qamd_u8 *h, uint32_t i, uint32
 
 /* score_internal (:386-453) for ONE stored row against many: out[k] = score_internal(i, ids[k]) -- what
  * graph construction asks (a new node against its candidate list), one launch instead of one per pair.
- * Host or device ids / outputs; with device ids and outputs the call only enqueues. */
+ * Host or device ids / outputs; with device ids and outputs the call only enqueues.
+ * The null id list: ids == NULL stands for the rows 0 .. n_ids - 1, served by *_score_internal_all's scan over that
+ * prefix of the store (out[j] has the bits of *_score_internal(h, i, j)); ids_mem is ignored, n_ids > count is
+ * QAMD_ERR_OUT_OF_RANGE, and the output synchronises as *_score_internal_all's does. */
 QAMD_API qamd_status qamd_u8_score_internal_ids(const qamd_u8 *h, uint32_t i, const uint32_t *ids, uint64_t n_ids,
                                                 qamd_mem ids_mem, float *out, qamd_mem out_mem, void *stream);
 /* ... and for MANY stored rows, each against its own id list, in one launch: list l is
@@ -214,7 +217,24 @@ QAMD_API qamd_status qamd_u8_score_internal_ids(const qamd_u8 *h, uint32_t i, co
  * `lists_mem` says where rows, list_offsets and ids live (one kind for the three).  Host lists are
  * validated (QAMD_ERR_OUT_OF_RANGE as score_internal) and bursts of up to ~1000 ids travel through the
  * calling thread's mapped scratch (one launch + one synchronisation, no allocation, no copy call);
- * device lists need a device output and only enqueue: an id or row out of range scores NaN. */
+ * device lists need a device output and only enqueue: an id or row out of range scores NaN.
+ * The null-list form (many stored rows against the whole store; no entry point of its own): ids == NULL stands, for
+ * EVERY list, for the rows 0 .. n_ids - 1, and n_ids is then the length of each list, not the total:
+ * out[l * n_ids + j] has the bits of *_score_internal(h, rows[l], j).  Row rows[l] itself is included; duplicates in rows
+ * are allowed.  The store is read once per group of rows (u8: 4 rows a pass, 2 for rows of 97 to 128 16-byte pieces, 8
+ * for L1 rows of up to 48; binary: 8, 4 or 2; PQ: one launch builds the group's tables, then a scan per row).
+ *   - list_offsets must be NULL too: list_offsets without ids is QAMD_ERR_ARGUMENTS (the caller forgot the ids).
+ *   - n_ids > count is QAMD_ERR_OUT_OF_RANGE before any launch; n_lists == 0 or n_ids == 0 is QAMD_OK and nothing is
+ *     written; a null handle is refused before any device call; NULL rows with n_lists > 0 is QAMD_ERR_ARGUMENTS.
+ *   - rows lives in lists_mem.  Host rows are validated: a row >= count is QAMD_ERR_OUT_OF_RANGE before any launch.
+ *     Device rows cannot be: a row >= count gives NaN in all n_ids outputs of its list, the other lists are untouched.
+ *   - Device rows need a device output, and the call then only enqueues.  Host rows with a device output synchronise
+ *     `stream` once the rows have been read, as the list form does; a host output synchronises `stream`.
+ *   - A host output is produced in groups of rows through the calling thread's score workspace: a group's scores stay
+ *     within 512 MiB (one row if need be), and the call never allocates n_lists * n_ids * 4 bytes.
+ *   - u8: lane mode holds as everywhere (mode 1 on a Dot / L2 store takes the lane-order kernel row by row).  PQ: a
+ *     handle without centroids is QAMD_ERR_ARGUMENTS.
+ * Every call with a given id list behaves as before. */
 QAMD_API qamd_status qamd_u8_score_internal_ids_batch(const qamd_u8 *h, const uint32_t *rows,
                                                       const uint32_t *list_offsets, uint32_t n_lists,
                                                       const uint32_t *ids, uint64_t n_ids, qamd_mem lists_mem,
@@ -237,8 +257,9 @@ QAMD_API qamd_status qamd_u8_score_internal_ids_batch(const qamd_u8 *h, const ui
  *     only enqueues, topk_internal always synchronises `stream`.
  *   - u8: lane mode (qamd_u8_set_lane_mode) holds as for every other call.  PQ: a handle without centroids is
  *     QAMD_ERR_ARGUMENTS.
- * Out of scope: Sharded handles have no whole-store score_internal.  There is no batched topk_internal_batch for many
- * stored rows at once.  There is no rescored variant (topk_internal followed by a re-rank with the original vectors). */
+ * Out of scope: Sharded handles have no whole-store score_internal.  There is no batched topk_internal_batch entry
+ * point: the scores of many rows come from the null-list form of *_score_internal_ids_batch, and ranking them is
+ * qamd_topk_scores per row.  There is no rescored variant (topk_internal followed by a re-rank with the original vectors). */
 QAMD_API qamd_status qamd_u8_score_internal_all(const qamd_u8 *h, uint32_t i, float *out, qamd_mem out_mem, void *stream);
 QAMD_API qamd_status qamd_u8_topk_internal(const qamd_u8 *h, uint32_t i, uint32_t k, int largest,
                                            uint32_t *out_ids, float *out_scores, qamd_mem out_mem, void *stream);
@@ -491,7 +512,8 @@ QAMD_API qamd_status qamd_bin_score_point(const qamd_bin *h, const qamd_bin_quer
                                           float *out);
 QAMD_API qamd_status qamd_bin_score_internal(const qamd_bin *h, uint32_t i, uint32_t j, float *out);
 /* Bursts of pairs in one launch (score_internal :302-314 is the metric of score_point on two stored
- * rows); arguments as qamd_u8_score_internal_ids / _ids_batch. */
+ * rows); arguments as qamd_u8_score_internal_ids / _ids_batch, the null id list (ids == NULL: the rows 0 .. n_ids - 1)
+ * as stated at qamd_u8_score_internal_ids and qamd_u8_score_internal_ids_batch. */
 QAMD_API qamd_status qamd_bin_score_internal_ids(const qamd_bin *h, uint32_t i, const uint32_t *ids, uint64_t n_ids,
                                                  qamd_mem ids_mem, float *out, qamd_mem out_mem, void *stream);
 QAMD_API qamd_status qamd_bin_score_internal_ids_batch(const qamd_bin *h, const uint32_t *rows,
@@ -662,7 +684,9 @@ QAMD_API qamd_status qamd_pq_score_point(const qamd_pq *h, const qamd_pq_query *
                                          float *out);
 QAMD_API qamd_status qamd_pq_score_internal(const qamd_pq *h, uint32_t i, uint32_t j, float *out);
 /* Bursts of pairs in one launch (score_internal :566-593: both rows decoded to centroid sub-vectors, the
- * chunk metrics summed in chunk order); arguments as qamd_u8_score_internal_ids / _ids_batch. */
+ * chunk metrics summed in chunk order); arguments as qamd_u8_score_internal_ids / _ids_batch, the null id list
+ * (ids == NULL: the rows 0 .. n_ids - 1) as stated at qamd_u8_score_internal_ids and qamd_u8_score_internal_ids_batch;
+ * with a null list a handle without centroids is QAMD_ERR_ARGUMENTS. */
 QAMD_API qamd_status qamd_pq_score_internal_ids(const qamd_pq *h, uint32_t i, const uint32_t *ids, uint64_t n_ids,
                                                 qamd_mem ids_mem, float *out, qamd_mem out_mem, void *stream);
 QAMD_API qamd_status qamd_pq_score_internal_ids_batch(const qamd_pq *h, const uint32_t *rows,

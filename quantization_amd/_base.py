@@ -113,11 +113,15 @@ class EncodedVectorsBase:
         return ret
 
     # ------------------------------------------------------------------ bursts of pairs (the HNSW caller)
-    def score_internal_ids(self, i: int, ids, out=None, stream=None):
-        """scores[k] = score_internal(i, ids[k]): one stored row against many, one launch."""
+    def score_internal_ids(self, i: int, ids, out=None, stream=None, n_rows=None):
+        """scores[k] = score_internal(i, ids[k]): one stored row against many, one launch.  `ids=None` stands for the
+        rows 0 .. n_rows - 1 (default: every row): score_internal_all's scan over a prefix of the store."""
         check_same_device(self._device, ids, out)
         ib = in_buf(ids, np.uint32)
-        n = int(ids.numel()) if hasattr(ids, "numel") else len(ids)
+        if ids is None:
+            n = self.count if n_rows is None else int(n_rows)
+        else:
+            n = int(ids.numel()) if hasattr(ids, "numel") else len(ids)
         buf, ret = out_buf(out, n, np.float32)
         check(self._fn("score_internal_ids")(self._h, int(i), ib.ptr, n, ib.mem, buf.ptr, buf.mem, stream_ptr(stream)))
         return ret
@@ -184,6 +188,62 @@ class EncodedVectorsBase:
             raise ValueError("out_ids and out_scores must both be host or both be device buffers")
         check(self._fn("topk_internal")(self._h, int(i), int(k), int(bool(largest)), ib.ptr, sb.ptr, sb.mem,
                                         stream_ptr(stream)))
+        return ids, sc
+
+    # ------------------------------------------------------------------ many stored rows against the whole store
+    _BATCH_BLOCK_BYTES = 512 << 20  # device score block of topk_internal_batch
+
+    def score_internal_all_batch(self, rows, n_rows=None, out=None, stream=None):
+        """scores[l, j] = score_internal(rows[l], j) for j < n_rows (default: every row), bit for bit: the null-list form
+        of score_internal_ids_batch - the store is read once for a group of rows instead of once per row.  `rows` and
+        `out` follow the score_internal_ids_batch rules: host rows with a host or device output, device rows (a torch
+        CUDA tensor) with a device output, where a row >= count gives a NaN list.  Returns [len(rows), n_rows]."""
+        check_same_device(self._device, rows, out)
+        rb = in_buf(rows, np.uint32)
+        n_lists = int(rows.numel()) if hasattr(rows, "numel") else len(rows)
+        n = self.count if n_rows is None else int(n_rows)
+        buf, ret = out_buf(out, n_lists * n, np.float32)
+        check(self._fn("score_internal_ids_batch")(self._h, rb.ptr, None, n_lists, None, n, rb.mem, buf.ptr, buf.mem,
+                                                   stream_ptr(stream)))
+        if isinstance(ret, np.ndarray):
+            return ret[:n_lists * n].reshape(n_lists, n)
+        return ret
+
+    def topk_internal_batch(self, rows, k: int, largest: bool = True, out_ids=None, out_scores=None, stream=None):
+        """topk_internal(rows[l], k, largest) for every l, [len(rows), k] ids and scores: groups of rows are scored into
+        a device block of at most 512 MiB (score_internal_all_batch), then each row of the block is ranked by
+        topk_scores - the same contract: total order on the score bits, ties to the lower id, best first, padding
+        when k > count.  Needs torch for the device block."""
+        import torch
+
+        from . import topk_scores
+
+        check_same_device(self._device, rows, out_ids, out_scores)
+        n_lists = int(rows.numel()) if hasattr(rows, "numel") else len(rows)
+        k, n = int(k), self.count
+        ib, ids = out_buf(out_ids, n_lists * k, np.uint32)
+        sb, sc = out_buf(out_scores, n_lists * k, np.float32)
+        if ib.mem != sb.mem:
+            raise ValueError("out_ids and out_scores must both be host or both be device buffers")
+        flat = lambda x: x.reshape(-1) if hasattr(x, "reshape") else x
+        ids_f, sc_f = flat(ids), flat(sc)
+        if n_lists and k and n == 0:  # an empty store: topk_internal's padding
+            for l in range(n_lists):
+                self.topk_internal(int(rows[l]), k, largest, ids_f[l * k:(l + 1) * k], sc_f[l * k:(l + 1) * k], stream)
+        elif n_lists and k:
+            device = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
+            group = max(1, min(n_lists, self._BATCH_BLOCK_BYTES // (4 * n)))
+            block = torch.empty(group * n, dtype=torch.float32, device=device)
+            if stream is not None:  # the block is used on the caller's stream: torch must not hand it out before that
+                block.record_stream(torch.cuda.ExternalStream(stream, device=device) if isinstance(stream, int) else stream)
+            for g in range(0, n_lists, group):
+                m = min(group, n_lists - g)
+                self.score_internal_all_batch(rows[g:g + m], out=block, stream=stream)
+                for l in range(m):
+                    o = (g + l) * k
+                    topk_scores(block[l * n:(l + 1) * n], n, k, largest, ids_f[o:o + k], sc_f[o:o + k], stream)
+        if isinstance(ids, np.ndarray):
+            return ids[:n_lists * k].reshape(n_lists, k), sc[:n_lists * k].reshape(n_lists, k)
         return ids, sc
 
     # ------------------------------------------------------------------ many queries at once

@@ -1093,16 +1093,16 @@ qamd_status alloc_store(qamd_bin *h) {
 float metric_dim(const qamd_bin *h, uint32_t planes) { return (float)(h->code_bits * ((1ull << planes) - 1)); }
 
 template <int G, int ITERS, int UNROLL, int PLANES = 1>
-void launch_bin(const qamd_bin *h, const uint4 *qb, float *out, const TopkFilter *filt, hipStream_t s) {
+void launch_bin(const qamd_bin *h, const uint4 *qb, float *out, const TopkFilter *filt, hipStream_t s, uint64_t n_rows) {
     constexpr int TILE = (64 / G) * UNROLL;
     const uint32_t rc = (uint32_t)(h->ds / 16);
     const int is_dot = h->vp.distance_type == QAMD_DOT;
-    const uint64_t waves = (h->count + TILE - 1) / TILE;
+    const uint64_t waves = (n_rows + TILE - 1) / TILE;
     const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
     const bool exact = rc == (uint32_t)(G * ITERS);
 #define QAMD_BIN_GO(EX, FI)                                                                                  \
     hipLaunchKernelGGL((bin_scan_kernel<G, ITERS, UNROLL, EX, FI, PLANES>), dim3(grid), dim3(kScanBlock), 0, s,      \
-                       h->rows.as<uint4>(), qb, metric_dim(h, PLANES), is_dot, h->vp.invert, (uint32_t)h->count, rc, \
+                       h->rows.as<uint4>(), qb, metric_dim(h, PLANES), is_dot, h->vp.invert, (uint32_t)n_rows, rc, \
                        out, filt ? *filt : TopkFilter{})
     if (filt) {
         if (exact) QAMD_BIN_GO(true, true);
@@ -1171,27 +1171,29 @@ bool fused_capable(const qamd_bin *h) { return bin_fused_rows(h->ds); }
 // The scan of a query's planes (1: its bit row), bin_scan_kernel's mapping per row length; the 8-lane rows of a scalar
 // query scan half the rows per wave, to leave the registers their 16-row tile takes to the planes of a piece.
 template <int PLANES>
-void scan_planes(const qamd_bin *h, const uint4 *qb, float *out_dev, hipStream_t s, const TopkFilter *filt) {
+void scan_planes(const qamd_bin *h, const uint4 *qb, float *out_dev, hipStream_t s, const TopkFilter *filt, uint64_t n) {
     const uint32_t rc = (uint32_t)(h->ds / 16);
-    if (rc == 1) launch_bin<1, 1, 4, PLANES>(h, qb, out_dev, filt, s);
-    else if (rc == 2) launch_bin<2, 1, 4, PLANES>(h, qb, out_dev, filt, s);
-    else if (rc <= 4) launch_bin<4, 1, 8, PLANES>(h, qb, out_dev, filt, s);
-    else if (rc <= 8) launch_bin<8, 1, (PLANES == 1 ? 16 : 8), PLANES>(h, qb, out_dev, filt, s);
-    else if (rc <= 16) launch_bin<16, 1, 8, PLANES>(h, qb, out_dev, filt, s);
-    else if (rc <= 32) launch_bin<16, 2, 4, PLANES>(h, qb, out_dev, filt, s);
-    else if (rc <= 48) launch_bin<16, 3, 4, PLANES>(h, qb, out_dev, filt, s);
-    else launch_bin<16, 4, 2, PLANES>(h, qb, out_dev, filt, s);
+    if (rc == 1) launch_bin<1, 1, 4, PLANES>(h, qb, out_dev, filt, s, n);
+    else if (rc == 2) launch_bin<2, 1, 4, PLANES>(h, qb, out_dev, filt, s, n);
+    else if (rc <= 4) launch_bin<4, 1, 8, PLANES>(h, qb, out_dev, filt, s, n);
+    else if (rc <= 8) launch_bin<8, 1, (PLANES == 1 ? 16 : 8), PLANES>(h, qb, out_dev, filt, s, n);
+    else if (rc <= 16) launch_bin<16, 1, 8, PLANES>(h, qb, out_dev, filt, s, n);
+    else if (rc <= 32) launch_bin<16, 2, 4, PLANES>(h, qb, out_dev, filt, s, n);
+    else if (rc <= 48) launch_bin<16, 3, 4, PLANES>(h, qb, out_dev, filt, s, n);
+    else launch_bin<16, 4, 2, PLANES>(h, qb, out_dev, filt, s, n);
 }
 
+// n_rows: the scan covers rows [0, n_rows) of the store (a null id list of n_ids rows); 0 = all of them.
 qamd_status scan_bits(const qamd_bin *h, const void *qbits_dev, float *out_dev, hipStream_t s,
-                      const TopkFilter *filt = nullptr, uint32_t planes = 1) {
+                      const TopkFilter *filt = nullptr, uint32_t planes = 1, uint64_t n_rows = 0) {
     if (h->count == 0) return QAMD_OK;
+    const uint64_t n = n_rows ? n_rows : h->count;
     if (!fused_capable(h))
-        return words_launch(h, static_cast<const uint32_t *>(qbits_dev), nullptr, h->count, out_dev, s, planes);
+        return words_launch(h, static_cast<const uint32_t *>(qbits_dev), nullptr, n, out_dev, s, planes);
     const uint4 *qb = static_cast<const uint4 *>(qbits_dev);
-    if (planes == 8) scan_planes<8>(h, qb, out_dev, s, filt);
-    else if (planes == 4) scan_planes<4>(h, qb, out_dev, s, filt);
-    else scan_planes<1>(h, qb, out_dev, s, filt);
+    if (planes == 8) scan_planes<8>(h, qb, out_dev, s, filt, n);
+    else if (planes == 4) scan_planes<4>(h, qb, out_dev, s, filt, n);
+    else scan_planes<1>(h, qb, out_dev, s, filt, n);
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
 }
@@ -1873,6 +1875,16 @@ qamd_status qamd_bin_query_read(const qamd_bin_query *q, uint8_t *bits, uint64_t
 
 void qamd_bin_query_free(qamd_bin_query *q) { delete q; }
 
+}  // extern "C"
+
+namespace {  // the null-list burst of score_internal (defined with the multi-query scans below)
+uint32_t internal_batch_group(const qamd_bin *h);
+qamd_status score_internal_rows_dev(const qamd_bin *h, const uint32_t *rows_dev, uint32_t n, uint64_t n_ids, float *out_dev,
+                                    hipStream_t s);
+}  // namespace
+
+extern "C" {
+
 // score_all for a device pointer to query bits (`planes` planes): an encoded query's buffer or, for score_internal_all,
 // a stored row of the image the scan reads.
 static qamd_status score_all_bits(const qamd_bin *h, const void *qbits, uint32_t planes, float *out, qamd_mem out_mem,
@@ -1912,9 +1924,16 @@ qamd_status qamd_bin_score_internal_ids(const qamd_bin *h, uint32_t i, const uin
                                         qamd_mem ids_mem, float *out, qamd_mem out_mem, void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
     if (n_ids == 0) return QAMD_OK;
-    if (!ids || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (!ids) QAMD_TRY(check_null_ids(n_ids, out, h->count));  // a null list stands for the rows 0 .. n_ids - 1
+    else if (!out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     if (i >= h->count) return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", i, (unsigned long long)h->count);
     QAMD_ON_DEVICE(h->device);
+    if (!ids) {  // score_internal_all's scan over a prefix of the store
+        hipStream_t s = as_stream(stream);
+        const uint8_t *qbits = h->rows.as<uint8_t>() + (uint64_t)i * h->ds;
+        if (out_mem == QAMD_MEM_DEVICE) return scan_bits(h, qbits, out, s, nullptr, 1, n_ids);
+        return score_all_to_host(n_ids, out, s, [&](float *scores) { return scan_bits(h, qbits, scores, s, nullptr, 1, n_ids); });
+    }
     return score_ids_any(h, h->rows.as<uint32_t>() + (uint64_t)i * (h->ds / 4), ids, n_ids, ids_mem, out, out_mem,
                          as_stream(stream));
 }
@@ -1931,6 +1950,15 @@ qamd_status qamd_bin_score_internal_ids_batch(const qamd_bin *h, const uint32_t 
                                               float *out, qamd_mem out_mem, void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
     if (n_lists && !rows) return fail(QAMD_ERR_ARGUMENTS, "rows is null");
+    if (!ids && n_lists && n_ids) {  // the null-list form: every list is the rows 0 .. n_ids - 1 (lists.hpp)
+        QAMD_TRY(check_null_lists(rows, list_offsets, n_lists, n_ids, lists_mem, out, out_mem, h->count));
+        QAMD_ON_DEVICE(h->device);
+        hipStream_t s = as_stream(stream);
+        return run_null_lists(rows, n_lists, n_ids, lists_mem, out, out_mem, h->count, internal_batch_group(h), s,
+                              [&](const uint32_t *rows_dev, uint32_t n, float *out_dev) {
+                                  return score_internal_rows_dev(h, rows_dev, n, n_ids, out_dev, s);
+                              });
+    }
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     return run_lists(list_offsets, n_lists, ids, n_ids, rows, lists_mem, out, out_mem, h->count, s, [&](const ListArgs &a) {
@@ -2022,17 +2050,18 @@ namespace {
 
 template <int G, int ITERS, int UNROLL, int NQ>
 void launch_bin_multi(const qamd_bin *h, const uint8_t *qbits, uint64_t q_stride, float *out, hipStream_t s,
-                      const TopkFilterSlices *slices = nullptr) {
+                      const TopkFilterSlices *slices = nullptr, uint64_t n_rows = 0) {
     constexpr int TILE = (64 / G) * UNROLL;
     const uint32_t rc = (uint32_t)(h->ds / 16);
-    const uint64_t waves = (h->count + TILE - 1) / TILE;
+    const uint64_t n = n_rows ? n_rows : h->count;  // rows scanned, also the pitch of `out`
+    const uint64_t waves = (n + TILE - 1) / TILE;
     const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
     const bool exact = rc == (uint32_t)(G * ITERS);
 #define QAMD_BIN_MULTI(EX, FI)                                                                                    \
     hipLaunchKernelGGL((bin_scan_multi_kernel<G, ITERS, UNROLL, NQ, EX, FI>), dim3(grid), dim3(kScanBlock), 0, s, \
                        h->rows.as<uint4>(), reinterpret_cast<const uint4 *>(qbits), (uint32_t)(q_stride / 16),    \
-                       metric_dim(h, 1), (int)(h->vp.distance_type == QAMD_DOT), h->vp.invert, (uint32_t)h->count, \
-                       rc, out, (uint64_t)h->count, slices ? *slices : TopkFilterSlices{})
+                       metric_dim(h, 1), (int)(h->vp.distance_type == QAMD_DOT), h->vp.invert, (uint32_t)n,       \
+                       rc, out, n, slices ? *slices : TopkFilterSlices{})
     if (slices) {
         if (exact) QAMD_BIN_MULTI(true, true);
         else QAMD_BIN_MULTI(false, true);
@@ -2048,15 +2077,60 @@ bool multi_rows(const qamd_bin *h) { return h->ds % 16 == 0 && h->ds / 16 >= 8 &
 
 // Queries [q0, q0 + nq) with nq in {8, 4, 2}: rows of 8 .. 64 pieces (dims 1024 .. 8192 at the u128 granule).
 template <int NQ> bool multi_step(const qamd_bin *h, const uint8_t *qbits, uint64_t q_stride, float *out, hipStream_t s,
-                                  const TopkFilterSlices *slices = nullptr) {
+                                  const TopkFilterSlices *slices = nullptr, uint64_t n_rows = 0) {
     const uint32_t rc = (uint32_t)(h->ds / 16);
     if (!multi_rows(h)) return false;
-    if (rc == 8) launch_bin_multi<8, 1, 8, NQ>(h, qbits, q_stride, out, s, slices);
-    else if (rc <= 16) launch_bin_multi<16, 1, 4, NQ>(h, qbits, q_stride, out, s, slices);
-    else if (rc <= 32) launch_bin_multi<16, 2, 2, NQ>(h, qbits, q_stride, out, s, slices);
-    else if (NQ <= 4) launch_bin_multi<16, 4, 2, NQ>(h, qbits, q_stride, out, s, slices);
+    if (rc == 8) launch_bin_multi<8, 1, 8, NQ>(h, qbits, q_stride, out, s, slices, n_rows);
+    else if (rc <= 16) launch_bin_multi<16, 1, 4, NQ>(h, qbits, q_stride, out, s, slices, n_rows);
+    else if (rc <= 32) launch_bin_multi<16, 2, 2, NQ>(h, qbits, q_stride, out, s, slices, n_rows);
+    else if (NQ <= 4) launch_bin_multi<16, 4, 2, NQ>(h, qbits, q_stride, out, s, slices, n_rows);
     else return false;
     return true;
+}
+
+// ---- score_internal of many stored rows against the rows 0 .. n_ids - 1 (the null-list burst) ----
+// Workgroup l copies the ds bytes of stored row rows[l] to qbits[l][..]: the contiguous [n][ds] block the scans read as
+// one-plane queries.  `rows` is device memory (no read-back); a row >= count is clamped to row 0 and its list becomes NaN
+// afterwards (null_list_nan_kernel).
+__global__ __launch_bounds__(64) void bin_gather_rows_kernel(const uint32_t *__restrict__ store, const uint32_t *__restrict__ rows,
+                                                             uint32_t count, uint32_t row_words, uint32_t *__restrict__ qbits) {
+    const uint32_t l = blockIdx.x;
+    uint32_t r = rows[l];
+    if (r >= count) r = 0;
+    const uint32_t *src = store + (uint64_t)r * row_words;
+    uint32_t *dst = qbits + (uint64_t)l * row_words;
+    for (uint32_t w = threadIdx.x; w < row_words; w += 64) dst[w] = src[w];
+}
+
+uint32_t internal_batch_group(const qamd_bin *h) {
+    return (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(8, (8ull << 20) / std::max<uint64_t>(h->ds, 1)));
+}
+
+// out_dev[l * n_ids + j] = score_internal(rows_dev[l], j) for l < n, j < n_ids <= count: score_internal is the metric of
+// a one-plane query whose bits are the stored row, so the gathered rows go through the multi-query passes (8, 4, 2 rows
+// per read of the store; rows of 8 .. 64 pieces) and the rest - remainders, other row sizes - through scan_bits per row.
+qamd_status score_internal_rows_dev(const qamd_bin *h, const uint32_t *rows_dev, uint32_t n, uint64_t n_ids, float *out_dev,
+                                    hipStream_t s) {
+    StreamBuf stage;
+    QAMD_TRY(stage.alloc((size_t)n * h->ds, s));
+    const uint8_t *qbits = stage.as<uint8_t>();
+    hipLaunchKernelGGL(bin_gather_rows_kernel, dim3(n), dim3(64), 0, s, h->rows.as<uint32_t>(), rows_dev, (uint32_t)h->count,
+                       (uint32_t)(h->ds / 4), stage.as<uint32_t>());
+    QAMD_HIP(hipGetLastError());
+    for (uint32_t l = 0; l < n;) {
+        const uint32_t left = n - l;
+        const uint8_t *qb = qbits + (uint64_t)l * h->ds;
+        float *o = out_dev + (uint64_t)l * n_ids;
+        if (left >= 8 && multi_step<8>(h, qb, h->ds, o, s, nullptr, n_ids)) l += 8;
+        else if (left >= 4 && multi_step<4>(h, qb, h->ds, o, s, nullptr, n_ids)) l += 4;
+        else if (left >= 2 && multi_step<2>(h, qb, h->ds, o, s, nullptr, n_ids)) l += 2;
+        else {
+            QAMD_TRY(scan_bits(h, qb, o, s, nullptr, 1, n_ids));
+            l += 1;
+        }
+    }
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
 }
 
 }  // namespace

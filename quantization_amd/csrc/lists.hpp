@@ -182,4 +182,95 @@ qamd_status run_lists(const uint32_t *list_offsets, uint32_t n_lists, const uint
     return launch(a);
 }
 
+// ---- the null-list form of *_score_internal_ids_batch / *_score_internal_ids -------------------------------------
+// ids == NULL stands, for every list, for the rows 0 .. n_ids - 1 (n_ids is then the length of each list):
+// out[l * n_ids + j] = score_internal(rows[l], j).  The quantizers share the argument checks, the walk over groups of
+// rows (a host output goes through the calling thread's score workspace, a group at a time) and the NaN rule of device
+// rows that cannot be validated.
+
+// A group's scores stay within this many bytes (f32.hip's bound for rerank_batch); a group is never less than one row.
+constexpr uint64_t kNullListGroupBytes = 512ull << 20;
+
+// The checks of the single-row call with a NULL id list (no device call).
+inline qamd_status check_null_ids(uint64_t n_ids, const float *out, uint64_t count) {
+    if (!out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (n_ids > count)
+        return fail(QAMD_ERR_OUT_OF_RANGE, "a null id list stands for the rows 0 .. n_ids - 1: n_ids = %llu, count %llu",
+                    (unsigned long long)n_ids, (unsigned long long)count);
+    return QAMD_OK;
+}
+
+// The checks of the burst with a NULL id list (no device call); n_lists and n_ids are not 0, rows is not NULL.
+inline qamd_status check_null_lists(const uint32_t *rows, const uint32_t *list_offsets, uint32_t n_lists, uint64_t n_ids,
+                                    qamd_mem lists_mem, const float *out, qamd_mem out_mem, uint64_t count) {
+    if (list_offsets)
+        return fail(QAMD_ERR_ARGUMENTS, "list_offsets without ids: a null id list (the rows 0 .. n_ids - 1) takes no offsets");
+    QAMD_TRY(check_null_ids(n_ids, out, count));
+    if (lists_mem == QAMD_MEM_HOST) {
+        for (uint32_t l = 0; l < n_lists; l++)
+            if (rows[l] >= count)
+                return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", rows[l], (unsigned long long)count);
+    } else if (out_mem == QAMD_MEM_HOST) {
+        return fail(QAMD_ERR_ARGUMENTS, "device lists need a device output buffer");
+    }
+    return QAMD_OK;
+}
+
+#ifdef __HIPCC__
+// Device rows cannot be validated: list l of a group becomes NaN when rows[l] >= count (the scans ran it against a
+// clamped row).  Runs behind the group's scans on their stream.  grid = (pieces of 256 * 8 scores, lists).
+template <int BLOCK = 256>
+__global__ __launch_bounds__(BLOCK) void null_list_nan_kernel(const uint32_t *__restrict__ rows, uint32_t count, uint64_t n_ids,
+                                                             float *__restrict__ out) {
+    const uint32_t l = blockIdx.y;
+    if (rows[l] < count) return;
+    float *o = out + (uint64_t)l * n_ids;
+    const uint64_t j0 = (uint64_t)blockIdx.x * (BLOCK * 8);
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+        const uint64_t j = j0 + (uint64_t)t * BLOCK + threadIdx.x;
+        if (j < n_ids) o[j] = __builtin_nanf("");
+    }
+}
+
+// The walk of the null-list burst: `launch(rows_dev, n, out_dev)` enqueues on `s` the scores of rows_dev[0 .. n) against
+// the rows 0 .. n_ids - 1 into out_dev[l * n_ids + j]; n <= max_group (what the quantizer's staging takes per launch).
+//   Host rows (validated by check_null_lists) are copied in once; the call then synchronises `s`, as run_lists does for
+//   host lists.  Device rows with a device output only enqueue.
+//   A host output is produced a group at a time in the thread's score workspace (kNullListGroupBytes): the call never
+//   allocates n_lists * n_ids * 4 bytes.
+template <class Launch>
+qamd_status run_null_lists(const uint32_t *rows, uint32_t n_lists, uint64_t n_ids, qamd_mem lists_mem, float *out,
+                           qamd_mem out_mem, uint64_t count, uint32_t max_group, hipStream_t s, Launch &&launch) {
+    StreamBuf in;
+    const uint32_t *rows_dev = rows;
+    if (lists_mem == QAMD_MEM_HOST) {
+        QAMD_TRY(in.alloc((size_t)n_lists * 4, s));
+        QAMD_HIP(hipMemcpyAsync(in.ptr, rows, (size_t)n_lists * 4, hipMemcpyHostToDevice, s));
+        rows_dev = in.as<uint32_t>();
+    }
+    const bool to_host = out_mem == QAMD_MEM_HOST;
+    uint64_t group = std::max<uint32_t>(max_group, 1);
+    if (to_host) group = std::min<uint64_t>(group, std::max<uint64_t>(1, kNullListGroupBytes / (n_ids * 4)));
+    group = std::min<uint64_t>(group, n_lists);
+    float *ws = nullptr;
+    if (to_host) QAMD_TRY(thread_ws_acquire(WS_SCORES, group * n_ids * 4, s, reinterpret_cast<void **>(&ws)));
+    qamd_status st = QAMD_OK;
+    for (uint64_t g = 0; g < n_lists && st == QAMD_OK; g += group) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(group, n_lists - g);
+        float *o = to_host ? ws : out + g * n_ids;
+        st = launch(rows_dev + g, n, o);
+        if (st == QAMD_OK && lists_mem == QAMD_MEM_DEVICE) {
+            hipLaunchKernelGGL(null_list_nan_kernel<256>, dim3((unsigned)((n_ids + 2047) / 2048), n), dim3(256), 0, s,
+                               rows_dev + g, (uint32_t)count, n_ids, o);
+            if (hipGetLastError() != hipSuccess) st = fail(QAMD_ERR_DEVICE, "null_list_nan_kernel did not launch");
+        }
+        if (st == QAMD_OK && to_host) st = copy_out(out + g * n_ids, QAMD_MEM_HOST, ws, (size_t)n * n_ids * 4, s);
+    }
+    if (to_host) thread_ws_release(WS_SCORES, s, st == QAMD_OK);  // the downloads synchronised the stream
+    else if (st == QAMD_OK && lists_mem == QAMD_MEM_HOST) QAMD_HIP(hipStreamSynchronize(s));  // pageable host rows
+    return st;
+}
+#endif
+
 }  // namespace qamd

@@ -1049,12 +1049,10 @@ __global__ __launch_bounds__(kBlock) void pq_internal_pairs_kernel(const uint8_t
 // The row LUT of stored row `row`: lut[c][code] = metric(centroids[rows[row][c]][range c], centroids[code][range c]) with
 // the sequential f32 loop of pq_internal_kernel (the last chunk may be ragged).  NOT inverted: a store whose metrics are all
 // +0 must score -0.0 under `invert`, which a pre-negated table (+0 + -0 = +0) would lose.
-__global__ __launch_bounds__(kBlock) void pq_row_lut_kernel(const uint8_t *__restrict__ rows, uint32_t row_stride, uint32_t row,
-                                                           uint32_t dim, uint32_t chunk_size, uint32_t m,
-                                                           const float *__restrict__ centroids, int distance,
-                                                           float *__restrict__ lut) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= m * kCentroids) return;
+// Entry i = (chunk c, code kc) of the row LUT of stored row `row`.
+__device__ __forceinline__ float row_lut_entry(const uint8_t *__restrict__ rows, uint32_t row_stride, uint32_t row, uint32_t dim,
+                                               uint32_t chunk_size, const float *__restrict__ centroids, int distance,
+                                               uint32_t i) {
     const uint32_t c = i / kCentroids, kc = i % kCentroids;
     const uint32_t lo = c * chunk_size, len = min(chunk_size, dim - lo);
     const float *a = centroids + (size_t)rows[(size_t)row * row_stride + c] * dim + lo, *b = centroids + (size_t)kc * dim + lo;
@@ -1065,7 +1063,28 @@ __global__ __launch_bounds__(kBlock) void pq_row_lut_kernel(const uint8_t *__res
         for (uint32_t t = 0; t < len; t++) s += fabsf(a[t] - b[t]);
     else
         for (uint32_t t = 0; t < len; t++) s += (a[t] - b[t]) * (a[t] - b[t]);
-    lut[i] = s;
+    return s;
+}
+__global__ __launch_bounds__(kBlock) void pq_row_lut_kernel(const uint8_t *__restrict__ rows, uint32_t row_stride, uint32_t row,
+                                                           uint32_t dim, uint32_t chunk_size, uint32_t m,
+                                                           const float *__restrict__ centroids, int distance,
+                                                           float *__restrict__ lut) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m * kCentroids) return;
+    lut[i] = row_lut_entry(rows, row_stride, row, dim, chunk_size, centroids, distance, i);
+}
+// The row LUTs of the stored rows row_ids[0 .. gridDim.y) in one launch (the null-list burst): LUT l at
+// luts + l * m * 256, entry for entry pq_row_lut_kernel's.  `row_ids` is device memory (no read-back); a row >= count is
+// clamped to row 0 and its list becomes NaN afterwards (null_list_nan_kernel).
+__global__ __launch_bounds__(kBlock) void pq_rows_lut_kernel(const uint8_t *__restrict__ rows, uint32_t row_stride,
+                                                            const uint32_t *__restrict__ row_ids, uint32_t count, uint32_t dim,
+                                                            uint32_t chunk_size, uint32_t m, const float *__restrict__ centroids,
+                                                            int distance, float *__restrict__ luts) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= m * kCentroids) return;
+    uint32_t row = row_ids[blockIdx.y];
+    if (row >= count) row = 0;
+    luts[(size_t)blockIdx.y * m * kCentroids + i] = row_lut_entry(rows, row_stride, row, dim, chunk_size, centroids, distance, i);
 }
 
 __device__ __forceinline__ float quad_bcast_f(float v, int j) {  // j is a constant after unrolling
@@ -2363,8 +2382,9 @@ qamd_status row_lut_build(const qamd_pq *h, uint32_t i, hipStream_t s, float **l
 }
 
 template <bool FILTER>
-qamd_status seq_launch_quad(const qamd_pq *h, const float *lut, float *out_dev, const TopkFilter *filt, hipStream_t s) {
-    const uint32_t m = (uint32_t)h->m, n = (uint32_t)h->count;
+qamd_status seq_launch_quad(const qamd_pq *h, const float *lut, float *out_dev, const TopkFilter *filt, hipStream_t s,
+                            uint64_t n_rows) {
+    const uint32_t m = (uint32_t)h->m, n = (uint32_t)n_rows;
     // the slices: the planar image's where the store has one (each a contiguous array of whole pieces), else pieces of
     // the row-major image as launch_fast cuts them (one slice up to 144 chunks, line-sized ones beyond)
     struct Slice {
@@ -2413,12 +2433,16 @@ qamd_status seq_launch_quad(const qamd_pq *h, const float *lut, float *out_dev, 
     return st;
 }
 
-// out_dev[j] = score_internal(i, j) for every row j, given row i's LUT.
-qamd_status seq_scan(const qamd_pq *h, const float *lut, float *out_dev, hipStream_t s, const TopkFilter *filt = nullptr) {
+// out_dev[j] = score_internal(i, j) for every row j, given row i's LUT.  n_rows: only the rows [0, n_rows) (a null id list
+// of n_ids rows); 0 = all of them.  The kernel is chosen by the store's size either way: both sum in chunk order.
+qamd_status seq_scan(const qamd_pq *h, const float *lut, float *out_dev, hipStream_t s, const TopkFilter *filt = nullptr,
+                     uint64_t n_rows = 0) {
     if (h->count == 0) return QAMD_OK;
-    if (seq_quad_capable(h)) return filt ? seq_launch_quad<true>(h, lut, nullptr, filt, s) : seq_launch_quad<false>(h, lut, out_dev, nullptr, s);
+    if (n_rows == 0) n_rows = h->count;
+    if (seq_quad_capable(h))
+        return filt ? seq_launch_quad<true>(h, lut, nullptr, filt, s, n_rows) : seq_launch_quad<false>(h, lut, out_dev, nullptr, s, n_rows);
     if (filt) return fail(QAMD_ERR_ARGUMENTS, "no filtering scan for this store");
-    const uint32_t m = (uint32_t)h->m, n = (uint32_t)h->count;
+    const uint32_t m = (uint32_t)h->m, n = (uint32_t)n_rows;
     const bool stage = m < 16 && n >= 4096;
     const int grid = (int)std::min<uint64_t>((uint64_t)device_info().cu_count * 8, ((uint64_t)n + kBlock - 1) / kBlock);
     if (stage)
@@ -2436,6 +2460,29 @@ qamd_status check_internal(const qamd_pq *h) {
     if (h->centroids_host.empty() || h->m == 0) return fail(QAMD_ERR_ARGUMENTS, "the store has no centroids to score with");
     return QAMD_OK;
 }
+
+// ---- score_internal of many stored rows against the rows 0 .. n_ids - 1 (the null-list burst) ----
+// Rows per launch group: their LUTs (m KiB each) stay within 4 MiB of the WS_ROW_LUT workspace.
+uint32_t internal_batch_group(const qamd_pq *h) {
+    return (uint32_t)std::max<uint64_t>(1, (4ull << 20) / (std::max<uint64_t>(h->m, 1) * kCentroids * sizeof(float)));
+}
+
+// out_dev[l * n_ids + j] = score_internal(rows_dev[l], j) for l < n <= internal_batch_group(h), j < n_ids <= count: ONE
+// launch builds the n row LUTs, then the sequential-order scans are enqueued back to back, one per row (the LDS holds
+// one LUT: rows cannot share a pass).  No host round trip in between.
+qamd_status score_internal_rows_dev(const qamd_pq *h, const uint32_t *rows_dev, uint32_t n, uint64_t n_ids, float *out_dev,
+                                    hipStream_t s) {
+    const size_t per = (size_t)h->m * kCentroids;
+    float *luts = nullptr;
+    QAMD_TRY(thread_ws_acquire(WS_ROW_LUT, (size_t)n * per * sizeof(float), s, reinterpret_cast<void **>(&luts)));
+    hipLaunchKernelGGL(pq_rows_lut_kernel, dim3((uint32_t)((per + kBlock - 1) / kBlock), n), dim3(kBlock), 0, s,
+                       h->rows.as<uint8_t>(), (uint32_t)h->ds, rows_dev, (uint32_t)h->count, (uint32_t)h->vp.dim,
+                       (uint32_t)h->chunk_size, (uint32_t)h->m, h->centroids.as<float>(), h->vp.distance_type, luts);
+    qamd_status st = hipGetLastError() == hipSuccess ? QAMD_OK : fail(QAMD_ERR_DEVICE, "pq_rows_lut_kernel did not launch");
+    for (uint32_t l = 0; l < n && st == QAMD_OK; l++) st = seq_scan(h, luts + l * per, out_dev + (uint64_t)l * n_ids, s, nullptr, n_ids);
+    thread_ws_release(WS_ROW_LUT, s);
+    return st;
+}
 }  // namespace
 
 extern "C" {
@@ -2445,10 +2492,24 @@ qamd_status qamd_pq_score_internal_ids(const qamd_pq *h, uint32_t i, const uint3
                                        qamd_mem ids_mem, float *out, qamd_mem out_mem, void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
     if (n_ids == 0) return QAMD_OK;
-    if (!ids || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (!ids) {  // a null list stands for the rows 0 .. n_ids - 1: score_internal_all's scan over a prefix of the store
+        QAMD_TRY(check_internal(h));
+        QAMD_TRY(check_null_ids(n_ids, out, h->count));
+    } else if (!out) {
+        return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    }
     if (i >= h->count) return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", i, (unsigned long long)h->count);
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
+    if (!ids) {
+        float *lut = nullptr;
+        QAMD_TRY(row_lut_build(h, i, s, &lut));
+        qamd_status st;
+        if (out_mem == QAMD_MEM_DEVICE) st = seq_scan(h, lut, out, s, nullptr, n_ids);
+        else st = score_all_to_host(n_ids, out, s, [&](float *scores) { return seq_scan(h, lut, scores, s, nullptr, n_ids); });
+        thread_ws_release(WS_ROW_LUT, s);
+        return st;
+    }
     // one list of n_ids ids: the list machinery with the row passed by value (no offsets needed)
     if (ids_mem == QAMD_MEM_DEVICE) {
         if (out_mem == QAMD_MEM_HOST) {
@@ -2478,6 +2539,16 @@ qamd_status qamd_pq_score_internal_ids_batch(const qamd_pq *h, const uint32_t *r
                                              float *out, qamd_mem out_mem, void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
     if (n_lists && !rows) return fail(QAMD_ERR_ARGUMENTS, "rows is null");
+    if (!ids && n_lists && n_ids) {  // the null-list form: every list is the rows 0 .. n_ids - 1 (lists.hpp)
+        QAMD_TRY(check_internal(h));
+        QAMD_TRY(check_null_lists(rows, list_offsets, n_lists, n_ids, lists_mem, out, out_mem, h->count));
+        QAMD_ON_DEVICE(h->device);
+        hipStream_t s = as_stream(stream);
+        return run_null_lists(rows, n_lists, n_ids, lists_mem, out, out_mem, h->count, internal_batch_group(h), s,
+                              [&](const uint32_t *rows_dev, uint32_t n, float *out_dev) {
+                                  return score_internal_rows_dev(h, rows_dev, n, n_ids, out_dev, s);
+                              });
+    }
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     return run_lists(list_offsets, n_lists, ids, n_ids, rows, lists_mem, out, out_mem, h->count, s, [&](const ListArgs &a) {

@@ -363,12 +363,14 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8
 // (row slot, sub = j) keeps query j's score of the row.  Same integer sum and the same f32
 // epilogue as u8_scan_kernel => the same score bits.  G >= NQ.
 // FILTER: no score is written; the lane offers its row to query j's candidate lists (slices).
-template <int G, int ITERS, int UNROLL, int NQ, bool IS_L1, bool EXACT, bool FILTER>
+// EPI_INTERNAL: the "queries" are stored rows gathered into a [NQ][q_pitch] block with their stored offsets
+// (u8_gather_rows_kernel), the epilogue is score_internal's; `diff` is wave-uniform and used after the row loop's sums only.
+template <int G, int ITERS, int UNROLL, int NQ, bool IS_L1, bool EXACT, bool FILTER, int EPI = EPI_POINT>
 __global__ __launch_bounds__(kScanBlock) void u8_scan_multi_kernel(
     const uint4 *__restrict__ codes, const float *__restrict__ offsets, const uint8_t *__restrict__ qcodes,
     uint32_t q_pitch, const float *__restrict__ q_offs, uint32_t nq_valid /* <= NQ: queries really there */,
     float multiplier, uint32_t n_rows, uint32_t row_chunks, float *__restrict__ out /* [NQ][out_pitch] */,
-    uint64_t out_pitch, TopkFilterSlices slices) {
+    uint64_t out_pitch, TopkFilterSlices slices, float diff) {
     static_assert(G >= NQ, "one lane of the row group per query");
     constexpr int RW = 64 / G;
     constexpr int TILE = RW * UNROLL;
@@ -423,7 +425,7 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_multi_kernel(
                 for (int it = 0; it < ITERS; it++)
                     acc[j] = IS_L1 ? sad16(v[u][it], q[j][it], acc[j]) : dot16(v[u][it], q[j][it], acc[j]);
             }
-            const float mine = epilogue(multiplier, multi_reduce<G, NQ>(acc, sub), q_off, v_off, 0.0f, EPI_POINT);
+            const float mine = epilogue(multiplier, multi_reduce<G, NQ>(acc, sub), q_off, v_off, EPI == EPI_POINT ? 0.0f : diff, EPI);
             if (owner && row < n_rows) {
                 if (FILTER) {
                     const TopkFilter f = topk_filter_of(slices, (uint32_t)my_q);
@@ -1262,19 +1264,22 @@ qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
 struct ScanEpi {
     float diff = 0.0f;
     int mode = EPI_POINT;
+    uint64_t rows = 0;  // the scan covers rows [0, rows) of the store (a null id list of n_ids rows); 0 = all of them
 };
+// Rows a whole-store launch covers.
+inline uint64_t scan_rows(const qamd_u8 *h, const ScanEpi &e) { return e.rows ? e.rows : h->count; }
 
 template <bool IS_L1> struct ScanLaunch {
     template <int G, int ITERS, int UNROLL>
     static void go(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt, hipStream_t s,
                    const ScanEpi &e) {
         constexpr int TILE = (64 / G) * UNROLL;
-        const uint64_t waves = (h->count + TILE - 1) / TILE;  // one wave per tile
+        const uint64_t waves = (scan_rows(h, e) + TILE - 1) / TILE;  // one wave per tile
         const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
         const bool exact = h->row_chunks == (uint32_t)(G * ITERS);
 #define QAMD_U8_GO_AS(EX, FI, EPI)                                                                              \
     hipLaunchKernelGGL((u8_scan_kernel<G, ITERS, UNROLL, IS_L1, EX, FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, \
-                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)h->count, \
+                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)scan_rows(h, e), \
                        h->row_chunks, out, filt ? *filt : TopkFilter{}, e.diff)
 #define QAMD_U8_GO(EX, FI)                               \
     do {                                                 \
@@ -1306,13 +1311,14 @@ uint32_t blocked_split(uint64_t count) {
 // The Dot / L2 scan of a store that has a packed image: u8_scan_blocked_kernel over its blocks.
 void launch_scan_blocked(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
                          hipStream_t s, const ScanEpi &e) {
-    const uint32_t split = blocked_split(h->count), blocks_per_wg = (kScanBlock / 64) / split;
-    const uint64_t blocks = (h->count + kPackBlockRows - 1) / kPackBlockRows;
+    const uint64_t n_rows = scan_rows(h, e);
+    const uint32_t split = blocked_split(n_rows), blocks_per_wg = (kScanBlock / 64) / split;
+    const uint64_t blocks = (n_rows + kPackBlockRows - 1) / kPackBlockRows;
     const unsigned grid = (unsigned)((blocks + blocks_per_wg - 1) / blocks_per_wg);
     h->last_scan_split.store((int)split, std::memory_order_relaxed);
 #define QAMD_U8_BLOCKED_AS(FI, EPI)                                                                                  \
     hipLaunchKernelGGL((u8_scan_blocked_kernel<FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, h->packed.as<uint4>(),  \
-                       h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)h->count, h->packed_chunks,      \
+                       h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)n_rows, h->packed_chunks,        \
                        h->row_chunks - h->packed_chunks, split, out, filt ? *filt : TopkFilter{}, e.diff)
 #define QAMD_U8_BLOCKED(FI)                                      \
     do {                                                         \
@@ -1355,12 +1361,12 @@ bool launch_scan(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out,
 
 template <bool IS_L1>
 void launch_scan_generic(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, hipStream_t s, const ScanEpi &e) {
-    uint64_t waves = (h->count + 3) / 4;  // one wave per 4-row tile (non-persistent, see u8_scan_kernel)
+    uint64_t waves = (scan_rows(h, e) + 3) / 4;  // one wave per 4-row tile (non-persistent, see u8_scan_kernel)
     unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
 #define QAMD_U8_GENERIC(EPI)                                                                             \
     hipLaunchKernelGGL((u8_scan_generic_kernel<IS_L1, EPI>), dim3(grid), dim3(kBlock), 0, s,             \
                        h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,         \
-                       (uint32_t)h->count, h->row_chunks, out, e.diff)
+                       (uint32_t)scan_rows(h, e), h->row_chunks, out, e.diff)
     if (e.mode == EPI_POINT) QAMD_U8_GENERIC(EPI_POINT);
     else QAMD_U8_GENERIC(EPI_INTERNAL);
 #undef QAMD_U8_GENERIC
@@ -1436,23 +1442,27 @@ qamd_status launch_small(const qamd_u8 *h, const uint4 *qc, const float *qo, con
 // ---- several queries per pass (u8_scan_multi_kernel) -------------------------------------------
 template <bool IS_L1, int G, int ITERS, int UNROLL, int NQ>
 void launch_multi_shape(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitch, const float *q_offs, uint32_t nq_valid,
-                        float *out, const TopkFilterSlices *slices, hipStream_t s) {
+                        float *out, const TopkFilterSlices *slices, hipStream_t s, const ScanEpi &e) {
     constexpr int TILE = (64 / G) * UNROLL * NQ;  // NQ tiles per wave (u8_scan_multi_kernel TPW)
-    const uint64_t waves = (h->count + TILE - 1) / TILE;
+    const uint64_t n_rows = scan_rows(h, e);  // also the pitch of `out`
+    const uint64_t waves = (n_rows + TILE - 1) / TILE;
     const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
     const bool exact = h->row_chunks == (uint32_t)(G * ITERS);
     h->last_scan_packed.store(0, std::memory_order_relaxed);
-#define QAMD_U8_MULTI(EX, FI)                                                                                      \
-    hipLaunchKernelGGL((u8_scan_multi_kernel<G, ITERS, UNROLL, NQ, IS_L1, EX, FI>), dim3(grid), dim3(kScanBlock), 0, s, \
+#define QAMD_U8_MULTI(EX, FI, EPI)                                                                                 \
+    hipLaunchKernelGGL((u8_scan_multi_kernel<G, ITERS, UNROLL, NQ, IS_L1, EX, FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, \
                        h->codes.as<uint4>(), h->offsets.as<float>(), qcodes, (uint32_t)q_pitch, q_offs, nq_valid,   \
-                       h->meta.multiplier, (uint32_t)h->count, h->row_chunks, out, (uint64_t)h->count,             \
-                       slices ? *slices : TopkFilterSlices{})
-    if (slices) {
-        if (exact) QAMD_U8_MULTI(true, true);
-        else QAMD_U8_MULTI(false, true);
+                       h->meta.multiplier, (uint32_t)n_rows, h->row_chunks, out, n_rows,                           \
+                       slices ? *slices : TopkFilterSlices{}, e.diff)
+    if (e.mode == EPI_INTERNAL) {  // score_internal of gathered rows: scores only (no filtering form is instantiated)
+        if (exact) QAMD_U8_MULTI(true, false, EPI_INTERNAL);
+        else QAMD_U8_MULTI(false, false, EPI_INTERNAL);
+    } else if (slices) {
+        if (exact) QAMD_U8_MULTI(true, true, EPI_POINT);
+        else QAMD_U8_MULTI(false, true, EPI_POINT);
     } else {
-        if (exact) QAMD_U8_MULTI(true, false);
-        else QAMD_U8_MULTI(false, false);
+        if (exact) QAMD_U8_MULTI(true, false, EPI_POINT);
+        else QAMD_U8_MULTI(false, false, EPI_POINT);
     }
 #undef QAMD_U8_MULTI
 }
@@ -1481,19 +1491,19 @@ uint32_t multi_width(const qamd_u8 *h) {
 // One pass for `nq_valid` (2 .. multi_width) queries; false = unsupported.
 template <bool IS_L1>
 bool launch_multi(const qamd_u8 *h, uint32_t nq_valid, const uint8_t *qcodes, uint64_t q_pitch, const float *q_offs,
-                  float *out, const TopkFilterSlices *slices, hipStream_t s) {
+                  float *out, const TopkFilterSlices *slices, hipStream_t s, const ScanEpi &e = ScanEpi{}) {
     const uint32_t iters = (h->row_chunks + 15) / 16, width = multi_width(h);
-    if (nq_valid < 2 || nq_valid > width) return false;
+    if (nq_valid < 2 || nq_valid > width || (slices && e.mode != EPI_POINT)) return false;
 #define QAMD_U8_MULTI_IT(IT, UN)                                                                              \
     case IT:                                                                                                  \
         if constexpr (IS_L1 && IT <= 3) {                                                                     \
             if (nq_valid > 4) {                                                                               \
-                launch_multi_shape<IS_L1, 16, IT, UN, 8>(h, qcodes, q_pitch, q_offs, nq_valid, out, slices, s); \
+                launch_multi_shape<IS_L1, 16, IT, UN, 8>(h, qcodes, q_pitch, q_offs, nq_valid, out, slices, s, e); \
                 return true;                                                                                  \
             }                                                                                                 \
         }                                                                                                     \
-        if (nq_valid > 2) launch_multi_shape<IS_L1, 16, IT, UN, (IT <= 6 ? 4 : 2)>(h, qcodes, q_pitch, q_offs, nq_valid, out, slices, s); \
-        else launch_multi_shape<IS_L1, 16, IT, UN, 2>(h, qcodes, q_pitch, q_offs, nq_valid, out, slices, s);  \
+        if (nq_valid > 2) launch_multi_shape<IS_L1, 16, IT, UN, (IT <= 6 ? 4 : 2)>(h, qcodes, q_pitch, q_offs, nq_valid, out, slices, s, e); \
+        else launch_multi_shape<IS_L1, 16, IT, UN, 2>(h, qcodes, q_pitch, q_offs, nq_valid, out, slices, s, e); \
         return true;
     switch (iters) {
         QAMD_U8_MULTI_IT(1, 4) QAMD_U8_MULTI_IT(2, 2) QAMD_U8_MULTI_IT(3, 2) QAMD_U8_MULTI_IT(4, 2)
@@ -1523,12 +1533,12 @@ qamd_status scan_ptrs(const qamd_u8 *h, const uint4 *qc, const float *qo, float 
     const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
     h->last_scan_packed.store(0, std::memory_order_relaxed);  // launch_scan reports the packed image
     if (lane_order(h)) {
-        uint64_t waves = (h->count + 3) / 4;
+        uint64_t waves = (scan_rows(h, e) + 3) / 4;
         unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
 #define QAMD_U8_LANES(EPI)                                                                          \
     hipLaunchKernelGGL((u8_scan_avx2_lanes_kernel<true, EPI>), dim3(grid), dim3(kBlock), 0, s,          \
                        h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,        \
-                       (uint32_t)h->count, h->row_chunks, out_dev, e.diff)
+                       (uint32_t)scan_rows(h, e), h->row_chunks, out_dev, e.diff)
         if (e.mode == EPI_POINT) QAMD_U8_LANES(EPI_POINT);
         else QAMD_U8_LANES(EPI_INTERNAL);
 #undef QAMD_U8_LANES
@@ -1618,6 +1628,63 @@ qamd_status score_ids_any(const qamd_u8 *h, const uint4 *qc, const float *qo, fl
     return run_ids(ids, n_ids, ids_mem, out, out_mem, h->count, s, [&](const uint32_t *ids_dev, uint64_t n, float *out_dev) {
         return score_ids_dev(h, qc, qo, diff, mode, ids_dev, n, out_dev, s);
     });
+}
+
+// ---- score_internal of many stored rows against the rows 0 .. n_ids - 1 (the null-list burst) ----
+// Workgroup l copies the byte codes of stored row rows[l] into qcodes[l][..] and its stored offset into q_offs[l]: the
+// block the scans read as their queries.  `rows` is device memory (no read-back); a row >= count (device rows cannot be
+// validated) is clamped to row 0, and its list is overwritten with NaN afterwards (null_list_nan_kernel).
+__global__ __launch_bounds__(64) void u8_gather_rows_kernel(const uint4 *__restrict__ codes, const float *__restrict__ offsets,
+                                                            const uint32_t *__restrict__ rows, uint32_t count,
+                                                            uint32_t row_chunks, uint4 *__restrict__ qcodes,
+                                                            float *__restrict__ q_offs) {
+    const uint32_t l = blockIdx.x;
+    uint32_t r = rows[l];
+    if (r >= count) r = 0;
+    const uint4 *src = codes + (uint64_t)r * row_chunks;
+    uint4 *dst = qcodes + (uint64_t)l * row_chunks;
+    for (uint32_t c = threadIdx.x; c < row_chunks; c += 64) dst[c] = src[c];
+    if (threadIdx.x == 0) q_offs[l] = offsets[r];
+}
+
+// Rows per launch group of the null-list burst: what the gathered block may take (8 MiB of codes), 4096 at the most.
+uint32_t internal_batch_group(const qamd_u8 *h) {
+    return (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(8, (8ull << 20) / std::max<uint64_t>(h->meta.actual_dim, 1)));
+}
+
+// out_dev[l * n_ids + j] = score_internal(rows_dev[l], j) for l < n, j < n_ids <= count.  The rows are gathered once;
+// then passes of multi_width(h) rows (u8_scan_multi_kernel with score_internal's epilogue: the integer sum and the f32
+// epilogue of the single-row scan, so the same bits), a remainder of one row and every row size without a multi form
+// (fewer than 9 or more than 128 pieces, lane order) through the single-row scan.  Enqueues only.
+qamd_status score_internal_rows_dev(const qamd_u8 *h, const uint32_t *rows_dev, uint32_t n, uint64_t n_ids, float *out_dev,
+                                    hipStream_t s) {
+    const uint64_t pitch = h->meta.actual_dim;  // 16 * row_chunks
+    const size_t code_bytes = (size_t)n * pitch;
+    StreamBuf stage;
+    QAMD_TRY(stage.alloc(code_bytes + (size_t)n * 4, s));
+    uint8_t *qcodes = stage.as<uint8_t>();
+    float *q_offs = reinterpret_cast<float *>(qcodes + code_bytes);
+    hipLaunchKernelGGL(u8_gather_rows_kernel, dim3(n), dim3(64), 0, s, h->codes.as<uint4>(), h->offsets.as<float>(), rows_dev,
+                       (uint32_t)h->count, h->row_chunks, reinterpret_cast<uint4 *>(qcodes), q_offs);
+    QAMD_HIP(hipGetLastError());
+    const ScanEpi e{internal_diff(h), EPI_INTERNAL, n_ids};
+    const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
+    const uint32_t width = multi_width(h);
+    for (uint32_t l = 0; l < n;) {
+        const uint32_t nq = std::min(width, n - l);
+        const uint8_t *qc = qcodes + (uint64_t)l * pitch;
+        float *o = out_dev + (uint64_t)l * n_ids;
+        const bool ok = nq >= 2 && (is_l1 ? launch_multi<true>(h, nq, qc, pitch, q_offs + l, o, nullptr, s, e)
+                                          : launch_multi<false>(h, nq, qc, pitch, q_offs + l, o, nullptr, s, e));
+        if (ok) {
+            l += nq;
+        } else {
+            QAMD_TRY(scan_ptrs(h, reinterpret_cast<const uint4 *>(qc), q_offs + l, o, s, nullptr, e));
+            l += 1;
+        }
+    }
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
 }
 
 // Gather `n_out` evenly strided rows of a device-resident [count][dim] array (quantile sample).
@@ -2192,11 +2259,19 @@ qamd_status qamd_u8_score_internal_ids(const qamd_u8 *h, uint32_t i, const uint3
                                        qamd_mem ids_mem, float *out, qamd_mem out_mem, void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
     if (n_ids == 0) return QAMD_OK;
-    if (!ids || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (!ids) QAMD_TRY(check_null_ids(n_ids, out, h->count));  // a null list stands for the rows 0 .. n_ids - 1
+    else if (!out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     if (i >= h->count) return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", i, (unsigned long long)h->count);
     QAMD_ON_DEVICE(h->device);
-    return score_ids_any(h, h->codes.as<uint4>() + (uint64_t)i * h->row_chunks, h->offsets.as<float>() + i, internal_diff(h),
-                         EPI_INTERNAL, ids, n_ids, ids_mem, out, out_mem, as_stream(stream));
+    const uint4 *qc = h->codes.as<uint4>() + (uint64_t)i * h->row_chunks;
+    const float *qo = h->offsets.as<float>() + i;
+    if (!ids) {  // score_internal_all's scan over a prefix of the store
+        hipStream_t s = as_stream(stream);
+        const ScanEpi e{internal_diff(h), EPI_INTERNAL, n_ids};
+        if (out_mem == QAMD_MEM_DEVICE) return scan_ptrs(h, qc, qo, out, s, nullptr, e);
+        return score_all_to_host(n_ids, out, s, [&](float *scores) { return scan_ptrs(h, qc, qo, scores, s, nullptr, e); });
+    }
+    return score_ids_any(h, qc, qo, internal_diff(h), EPI_INTERNAL, ids, n_ids, ids_mem, out, out_mem, as_stream(stream));
 }
 
 // Many stored rows, each against its own id list, in one launch (lists.hpp):
@@ -2206,6 +2281,15 @@ qamd_status qamd_u8_score_internal_ids_batch(const qamd_u8 *h, const uint32_t *r
                                              float *out, qamd_mem out_mem, void *stream) {
     if (!h) return fail(QAMD_ERR_ARGUMENTS, "null handle");
     if (n_lists && !rows) return fail(QAMD_ERR_ARGUMENTS, "rows is null");
+    if (!ids && n_lists && n_ids) {  // the null-list form: every list is the rows 0 .. n_ids - 1 (lists.hpp)
+        QAMD_TRY(check_null_lists(rows, list_offsets, n_lists, n_ids, lists_mem, out, out_mem, h->count));
+        QAMD_ON_DEVICE(h->device);
+        hipStream_t s = as_stream(stream);
+        return run_null_lists(rows, n_lists, n_ids, lists_mem, out, out_mem, h->count, internal_batch_group(h), s,
+                              [&](const uint32_t *rows_dev, uint32_t n, float *out_dev) {
+                                  return score_internal_rows_dev(h, rows_dev, n, n_ids, out_dev, s);
+                              });
+    }
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
     return run_lists(list_offsets, n_lists, ids, n_ids, rows, lists_mem, out, out_mem, h->count, s, [&](const ListArgs &a) {
