@@ -395,7 +395,8 @@ QAMD_API qamd_status qamd_bin_load(const char *data_path, const char *meta_path,
  * Rotated rows: a randomized Hadamard rotation before the sign and threshold bits.  The reference has NO counterpart;
  * DESIGN.md 3.2g is the specification.  QAMD_BIN_ROTATED is a flag or-ed onto one of the two encodings above; it rides
  * the `encoding` argument of the four *_enc calls and the handle carries it from there (no entry point of its own).
- * Values 2, 3, 6, 7 and above are QAMD_ERR_ARGUMENTS before any device call.
+ * Values 2, 3, 6, 7 and above (but for the two block values after the typedef) are QAMD_ERR_ARGUMENTS before any device
+ * call.
  *   - P = the smallest power of two >= dim (1 for dim <= 1); a rotated handle has dim <= 16384 (QAMD_ERR_ARGUMENTS beyond,
  *     before any device call).  y_i = x_i for i < dim and +0.0f up to P; y_i's sign bit is flipped iff h & 1 after, in
  *     u32 arithmetic, h = i * 0x9E3779B1; h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
@@ -414,10 +415,29 @@ QAMD_API qamd_status qamd_bin_load(const char *data_path, const char *meta_path,
  *     served exactly as a plain store of code_bits bits; vp.dim stays the vectors' dimension for originals.  Metadata
  *     says "encoding":"OneBitRotated" or "TwoBitsRotated", the latter with thresholds of P entries.
  * Out of scope: sharded binary handles; seeds other than the fixed one; more than one round; block-diagonal rotations
- * that would avoid padding 768 -> 1024 or 1536 -> 2048; bench.py. */
+ * with blocks of unequal size, and dims that are not a multiple of 64 (equal blocks: below); bench.py. */
 typedef enum { QAMD_BIN_ONE_BIT = 0, QAMD_BIN_TWO_BITS = 1,
                QAMD_BIN_ROTATED = 4,            /* flag: or-ed onto one of the two above */
                QAMD_BIN_ONE_BIT_ROTATED = 4, QAMD_BIN_TWO_BITS_ROTATED = 5 } qamd_bin_encoding;
+/* Block-rotated rows: the rotation above without the pad, so a row of 768 or 1536 dimensions keeps 768 or 1536 bits.
+ * DESIGN.md 3.2h is the specification.  QAMD_BIN_BLOCKS is a second flag, legal only together with QAMD_BIN_ROTATED: the
+ * two values below are qamd_bin_encoding values for every call that takes or returns one.  QAMD_BIN_BLOCKS alone (16) and
+ * 17 are refused like every unknown value (QAMD_ERR_ARGUMENTS, "unknown binary encoding"), as are 18, 19 and all above 21.
+ *   - dim % 64 == 0 and dim <= 16384, QAMD_ERR_ARGUMENTS otherwise before any device call.  B = the largest power of two
+ *     that divides dim (B >= 64).
+ *   - y_i = x_i for i < dim, no pad; the signs of the rotation above for i < dim; its stages s = 1, 2, 4, .., B / 2 in
+ *     this order over every j < dim with (j & s) == 0, one f32 operation each, no normalisation.  No pair leaves its
+ *     B-aligned block: these are dim / B Hadamard transforms of size B, all of one size so that every column carries the
+ *     same scale sqrt(B).
+ *   - Everything downstream sees a vector of dim dimensions: code_bits = dim or 2 dim, thresholds, lo / hi arguments and
+ *     qamd_bin_get_thresholds of dim entries, the statistics over the dim rotated columns, scalar queries' limits on dim.
+ *     Rows are those of a plain store's size; every item of the rotated rows above holds with dim in place of P.
+ *   - Metadata says "encoding":"OneBitRotatedBlocks" or "TwoBitsRotatedBlocks"; qamd_bin_load refuses a dim that is not a
+ *     multiple of 64 under these names, and arrays whose length is not dim, as QAMD_ERR_IO before any device call.
+ *   - A power-of-two dim >= 64 has B = dim: rows, thresholds and query codes are byte-identical to the ROTATED encodings';
+ *     only the reported encoding value and the file's name differ. */
+enum { QAMD_BIN_BLOCKS = 16,                    /* flag: or-ed onto one of the two ROTATED values, never alone */
+       QAMD_BIN_ONE_BIT_ROTATED_BLOCKS = 20, QAMD_BIN_TWO_BITS_ROTATED_BLOCKS = 21 };
 QAMD_API uint64_t qamd_bin_quantized_vector_size_enc(const qamd_vector_parameters *vp, qamd_bits_store store,
                                                      qamd_bin_encoding encoding);
 /* The statistics above over ONE contiguous block of n_rows x dim values (blocks of 4096 counted from the call's first
@@ -456,9 +476,10 @@ QAMD_API qamd_status qamd_bin_from_rows_enc(const uint8_t *rows, qamd_mem rows_m
                                             qamd_bin_encoding encoding, const float *lo, const float *hi,
                                             void *stream, qamd_bin **out);
 /* Either pointer may be NULL.  *code_bits = the bits of a row: dim, or 2 * dim.  Rotated rows: the flagged encoding
- * (4 or 5) and P, or 2 * P. */
+ * (4 or 5) and P, or 2 * P; block-rotated rows: 20 or 21 and dim, or 2 * dim. */
 QAMD_API qamd_status qamd_bin_get_encoding(const qamd_bin *h, qamd_bin_encoding *encoding, uint64_t *code_bits);
-/* dim host floats each (P each for rotated two-bit rows); QAMD_ERR_ARGUMENTS on a one-bit handle. */
+/* dim host floats each (P each for rotated two-bit rows, dim for block-rotated ones); QAMD_ERR_ARGUMENTS on a one-bit
+ * handle. */
 QAMD_API qamd_status qamd_bin_get_thresholds(const qamd_bin *h, float *lo, float *hi);
 /* qamd_bin_save of a two-bit handle writes {"vector_parameters":{..},"encoding":"TwoBits","thresholds":{"lo":[..],
  * "hi":[..]}} (infinite thresholds have no JSON form: QAMD_ERR_IO); a one-bit file is the reference's, unchanged.

@@ -1011,6 +1011,125 @@ __global__ __launch_bounds__(kBlock) void bin_rotate_lds_kernel(const float *__r
     }
 }
 
+// ---- block-rotated rows: no pad, and the network above cut off after stage B / 2 ----
+// B = the largest power of two that divides dim (dim % 64 == 0, so B >= 64): dim / B Hadamard transforms of size B side
+// by side, the row keeps dim values.  The launcher sends a power-of-two dim (B == dim) to the kernels above; these two
+// serve B < dim.  B is a wave-uniform argument, as P is for bin_rotate_kernel<1, 1>: every test on it is a scalar branch.
+//
+// A wave per row for dim <= 2048, bin_rotate_kernel<4, K, MODE>'s layout with K = ceil(dim / 256) of any value 1 .. 8.
+// Stages 1 and 2 are load_chunk's; the lane stage M pairs values 4 M apart and runs while 4 M < B (M <= 8 always).  A
+// dim <= 2048 that is no power of two has B <= 512 (B = 1024 first at 3072), so of the chunk stages only s = 1 is left,
+// values 256 apart, for B = 512 - that is dim = 1536 = 3 x 512, K = 6: chunk k pairs with k + 1 for every even k.
+// dim % 256 != 0: the lanes from dim / 4 - 64 (K - 1) on of the last chunk hold +-0.0 and stay active for the DPP reads.
+// B divides dim, so a pair lies in one B-aligned block, wholly below dim or wholly at or above it: an idle lane never
+// meets a live value (and B <= 128 there: no chunk stage).  dim / 4 is a multiple of 16, so the 8-lane groups of
+// emit_chunks are wholly live or wholly idle: the branch around it cuts along groups, and an idle group neither reads
+// thresholds nor stores.
+template <int K, int MODE>
+__global__ __launch_bounds__(kBlock) void bin_rotate_blocks_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                                  uint32_t B, int vec, const float *__restrict__ thr,
+                                                                  float *__restrict__ out, uint32_t *__restrict__ rows,
+                                                                  uint32_t row_words, uint64_t row0) {
+    static_assert(K >= 1 && K <= 8, "a lane holds at most 32 values");
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    const uint32_t chunks = dim / 4;
+    for (uint64_t r = wave; r < n_rows; r += n_waves) {
+        const float *src = data + r * dim;
+        float y[K][4];
+#pragma unroll
+        for (int k = 0; k < K; k++) load_chunk(src, (uint32_t)(k * 64 + lane) * 4, dim, vec, y[k]);
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                float v = y[k][e];
+                v = lane_butterfly<1>(v, lane);
+                v = lane_butterfly<2>(v, lane);
+                v = lane_butterfly<4>(v, lane);
+                v = lane_butterfly<8>(v, lane);
+                y[k][e] = v;
+            }
+        }
+        // (one branch per stage, not per value: the 4 K ds_bpermute of a stage stay in one block and overlap)
+        if (64u < B) {
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) y[k][e] = lane_butterfly<16>(y[k][e], lane);
+            }
+        }
+        if (128u < B) {
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) y[k][e] = lane_butterfly<32>(y[k][e], lane);
+            }
+        }
+        if (256u < B) {  // B == 512
+#pragma unroll
+            for (int k = 0; k + 1 < K; k += 2) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) butterfly(y[k][e], y[k + 1][e]);
+            }
+        }
+        float *out_row = MODE == 0 ? out + r * dim : nullptr;
+        uint32_t *dst = MODE == 0 ? nullptr : rows + (row0 + r) * row_words;
+        // only the last chunk can hold idle lanes; the chunks before it go without a branch, so their threshold loads
+        // issue together (behind a branch each load waits for the one before it)
+#pragma unroll
+        for (int k = 0; k < K - 1; k++) emit_chunks<MODE>(y[k], k * 64, lane, dim, thr, out_row, dst);
+        if ((uint32_t)((K - 1) * 64 + lane) < chunks) emit_chunks<MODE>(y[K - 1], (K - 1) * 64, lane, dim, thr, out_row, dst);
+        if constexpr (MODE != 0)
+            for (uint32_t w = (MODE == 2 ? dim / 16 : dim / 32) + lane; w < row_words; w += 64) dst[w] = 0;
+    }
+}
+
+// A workgroup per row for 2048 < dim <= 16384: bin_rotate_lds_kernel with the stage loop ending at s < B and a chunk
+// count dim / 4 that is a multiple of 16, not of kBlock - the emit loop's last pass is cut along 8-lane groups as above.
+// A stage's dim / 2 pairs: pair b is (j, j + s) with j = 2 s (b / s) + b % s, and 2 s <= B divides dim, so j + s < dim.
+// 4 dim bytes of LDS.
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void bin_rotate_blocks_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                                      uint32_t B, int vec, const float *__restrict__ thr,
+                                                                      float *__restrict__ out, uint32_t *__restrict__ rows,
+                                                                      uint32_t row_words, uint64_t row0) {
+    extern __shared__ float rot_row[];
+    const int lane = threadIdx.x & 63;
+    const uint32_t chunks = dim / 4;
+    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const float *src = data + r * dim;
+        for (uint32_t c = threadIdx.x; c < chunks; c += kBlock) {
+            float y[4];
+            load_chunk(src, c * 4, dim, vec, y);
+            reinterpret_cast<float4 *>(rot_row)[c] = make_float4(y[0], y[1], y[2], y[3]);
+        }
+        for (uint32_t s = 4; s < B; s <<= 1) {
+            __syncthreads();
+            for (uint32_t b = threadIdx.x; b < dim / 2; b += kBlock) {
+                const uint32_t j = ((b & ~(s - 1)) << 1) | (b & (s - 1));
+                float a = rot_row[j], d = rot_row[j + s];
+                butterfly(a, d);
+                rot_row[j] = a, rot_row[j + s] = d;
+            }
+        }
+        __syncthreads();
+        float *out_row = MODE == 0 ? out + r * dim : nullptr;
+        uint32_t *dst = MODE == 0 ? nullptr : rows + (row0 + r) * row_words;
+        for (uint32_t c0 = (threadIdx.x >> 6) * 64; c0 < chunks; c0 += kBlock) {
+            if (c0 + lane < chunks) {
+                const float4 t = reinterpret_cast<const float4 *>(rot_row)[c0 + lane];
+                const float y[4] = {t.x, t.y, t.z, t.w};
+                emit_chunks<MODE>(y, c0, lane, dim, thr, out_row, dst);
+            }
+        }
+        if constexpr (MODE != 0)
+            for (uint32_t w = (MODE == 2 ? dim / 16 : dim / 32) + threadIdx.x; w < row_words; w += kBlock) dst[w] = 0;
+        __syncthreads();  // the next row's chunks overwrite the LDS row
+    }
+}
+
 int grid_for(uint64_t work_items, uint64_t per_block, int blocks_per_cu) {
     uint64_t want = (work_items + per_block - 1) / per_block;
     uint64_t cap = (uint64_t)device_info().cu_count * blocks_per_cu;
@@ -1043,12 +1162,15 @@ struct qamd_bin {
     // vp.dim stays the vectors' dimension (thresholds, queries, the originals of a rescored top-k).
     // Rotated rows: the encoders see y = H_P (signs * pad(x)) of edim = P values in place of x; everything
     // after them - thresholds, code_bits, the scans - is that of a plain store of P dimensions.
+    // Block-rotated rows: y has edim = dim values, dim / B transforms of size B, and the store is a plain
+    // one of dim dimensions.
     int encoding = QAMD_BIN_ONE_BIT;
-    uint64_t edim = 0;            // what the bit encoders see: dim, or P of a rotated store
+    uint64_t edim = 0;            // what the bit encoders see: dim, or P of a (padded) rotated store
     uint64_t code_bits = 0;       // bits of a row: edim, or 2 edim
     std::vector<float> thr_host;  // two-bit: lo[edim] | hi[edim]
     bool two() const { return (encoding & QAMD_BIN_TWO_BITS) != 0; }
     bool rotated() const { return (encoding & QAMD_BIN_ROTATED) != 0; }
+    bool blocks() const { return (encoding & QAMD_BIN_BLOCKS) != 0; }
     DevBuf thr;                   // the same, for the encoders of rows and queries
     // the batched top-k's pivot sample (rows hash(j) of the store, j < sample_count, then 512 zero rows);
     // gathered on first use (count / 64 rows at most), discarded by an upsert
@@ -1075,9 +1197,15 @@ uint64_t rot_dim(uint64_t dim) {
     return p;
 }
 constexpr uint64_t kRotMaxDim = 16384;  // a rotated row is at most 64 KiB of f32: the LDS bin_rotate_lds_kernel asks for
+constexpr uint64_t kRotBlockMin = 64;   // block-rotated rows (3.2h): dim is a multiple of it, so no block is smaller
 
-// The dimension the bit encoders of `encoding` see for vectors of `dim`.
-uint64_t encoder_dim(uint64_t dim, int encoding) { return (encoding & QAMD_BIN_ROTATED) ? rot_dim(dim) : dim; }
+// B of DESIGN 3.2h: the largest power of two that divides dim (dim != 0)
+uint64_t rot_block(uint64_t dim) { return dim & (~dim + 1); }
+
+// The dimension the bit encoders of `encoding` see for vectors of `dim`: block rotation (3.2h) does not pad.
+uint64_t encoder_dim(uint64_t dim, int encoding) {
+    return (encoding & QAMD_BIN_ROTATED) && !(encoding & QAMD_BIN_BLOCKS) ? rot_dim(dim) : dim;
+}
 
 qamd_status alloc_store(qamd_bin *h) {
     h->edim = encoder_dim(h->vp.dim, h->encoding);
@@ -1280,12 +1408,39 @@ qamd_status upload_rows(qamd_bin *h, const uint8_t *rows, qamd_mem mem, hipStrea
 // itself).
 // The rotation of `n` vectors of `dim` floats, P = rot_dim(dim).  MODE 0: P floats per vector to `out`;
 // MODE 1 / 2: the fused row encoder - bit rows of `row_words` dwords from row r0 of `rows` on, thr = lo | hi for MODE 2.
+// `blocks` (dim % 64 == 0, checked by every caller's check_enc_args): dim values per vector, the network cut
+// off after stage B / 2.  A power-of-two dim has B == dim == P: the same transform, and the kernels of 3.2g serve it.
 template <int MODE>
-void launch_rotate(const float *src, uint64_t n, uint64_t dim, const float *thr, float *out, uint32_t *rows, uint64_t row_words,
-                   uint64_t r0, hipStream_t s) {
+void launch_rotate(const float *src, uint64_t n, uint64_t dim, bool blocks, const float *thr, float *out, uint32_t *rows,
+                   uint64_t row_words, uint64_t r0, hipStream_t s) {
     if (n == 0 || dim == 0) return;
-    const uint32_t P = (uint32_t)rot_dim(dim);
     const int vec = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    if (blocks && rot_block(dim) != dim) {
+        const uint32_t B = (uint32_t)rot_block(dim);
+#define QAMD_BIN_ROT_BLOCKS(K)                                                                                           \
+    case K:                                                                                                              \
+        hipLaunchKernelGGL((bin_rotate_blocks_kernel<K, MODE>), dim3(grid_for(n, kBlock / 64, 8)), dim3(kBlock), 0, s, src, n, \
+                           (uint32_t)dim, B, vec, thr, out, rows, (uint32_t)row_words, r0);                               \
+        break
+        if (dim > kRotWaveMax) {
+            hipLaunchKernelGGL(bin_rotate_blocks_lds_kernel<MODE>, dim3(grid_for(n, 1, 160 * 1024 / (dim * 4))), dim3(kBlock),
+                               dim * 4, s, src, n, (uint32_t)dim, B, vec, thr, out, rows, (uint32_t)row_words, r0);
+            return;
+        }
+        switch ((dim + 255) / 256) {
+            QAMD_BIN_ROT_BLOCKS(1);
+            QAMD_BIN_ROT_BLOCKS(2);
+            QAMD_BIN_ROT_BLOCKS(3);
+            QAMD_BIN_ROT_BLOCKS(4);
+            QAMD_BIN_ROT_BLOCKS(5);
+            QAMD_BIN_ROT_BLOCKS(6);
+            QAMD_BIN_ROT_BLOCKS(7);
+            QAMD_BIN_ROT_BLOCKS(8);
+        }
+#undef QAMD_BIN_ROT_BLOCKS
+        return;
+    }
+    const uint32_t P = (uint32_t)rot_dim(dim);
 #define QAMD_BIN_ROT(E, K)                                                                                               \
     hipLaunchKernelGGL((bin_rotate_kernel<E, K, MODE>), dim3(grid_for(n, kBlock / 64, 8)), dim3(kBlock), 0, s, src, n,    \
                        (uint32_t)dim, P, vec, thr, out, rows, (uint32_t)row_words, r0)
@@ -1305,8 +1460,8 @@ void launch_bit_encoder(const qamd_bin *h, const float *src, uint64_t n, uint64_
                         uint64_t r0, hipStream_t s) {
     if (n == 0 || dim == 0) return;
     if (h->rotated()) {  // (dim is the handle's: every caller has checked it)
-        if (h->two()) launch_rotate<2>(src, n, dim, h->thr.as<float>(), nullptr, dst, row_words, r0, s);
-        else launch_rotate<1>(src, n, dim, nullptr, nullptr, dst, row_words, r0, s);
+        if (h->two()) launch_rotate<2>(src, n, dim, h->blocks(), h->thr.as<float>(), nullptr, dst, row_words, r0, s);
+        else launch_rotate<1>(src, n, dim, h->blocks(), nullptr, nullptr, dst, row_words, r0, s);
         return;
     }
     const int grid = grid_for(n, kBlock / 64, 8);
@@ -1322,11 +1477,12 @@ void launch_bit_encoder(const qamd_bin *h, const float *src, uint64_t n, uint64_
 qamd_status launch_scalar_encoder(const qamd_bin *h, const float *src, uint64_t n, uint64_t dim, uint64_t ds, uint32_t bits,
                            uint32_t *planes, uint64_t p_stride, float *max_abs, int8_t *codes, uint64_t code_pitch,
                            hipStream_t s) {
-    StreamBuf rot;  // a rotated store: the codes come from y, P floats per query, held until `s` has used them
+    StreamBuf rot;  // a rotated store: the codes come from y, P (blocks: dim) floats per query, held
+                    // until `s` has used them
     if (h->rotated() && n && dim) {
-        const uint64_t P = rot_dim(dim);
+        const uint64_t P = encoder_dim(dim, h->encoding);
         QAMD_TRY(rot.alloc(n * P * 4, s));
-        launch_rotate<0>(src, n, dim, nullptr, rot.as<float>(), nullptr, 0, 0, s);
+        launch_rotate<0>(src, n, dim, h->blocks(), nullptr, rot.as<float>(), nullptr, 0, 0, s);
         src = rot.as<float>();
         dim = P;
     }
@@ -1450,9 +1606,10 @@ struct BinStats {
 // A batch of rows, in host or device memory, into the statistics: in pieces as the encoders stage them.
 // `stop` is polled before every piece, as the row pass polls it.
 // raw_dim != 0 (rotated rows): the rows have raw_dim floats and the statistics are those of their rotation,
-// st.dim = P columns - a piece of at most 256 MiB is rotated into a stream-ordered buffer and added from there.
+// st.dim = P columns (`blocks`, 3.2h: raw_dim columns) - a piece of at most 256 MiB is rotated into a stream-ordered
+// buffer and added from there.
 qamd_status stats_feed(BinStats &st, const float *data, qamd_mem mem, uint64_t n_rows, DevBuf &stage, hipStream_t s,
-                       qamd_stop_fn stop = nullptr, void *stop_user = nullptr, uint64_t raw_dim = 0) {
+                       qamd_stop_fn stop = nullptr, void *stop_user = nullptr, uint64_t raw_dim = 0, bool blocks = false) {
     if (st.dim == 0 || n_rows == 0) return QAMD_OK;
     const uint64_t piece_bytes = stage_bytes(mem == QAMD_MEM_HOST || raw_dim ? (256ull << 20) : (8ull << 30));
     const uint64_t piece_rows = std::max<uint64_t>(1, piece_bytes / (st.dim * 4));
@@ -1462,7 +1619,7 @@ qamd_status stats_feed(BinStats &st, const float *data, qamd_mem mem, uint64_t n
         if (!raw_dim) return st.add(src, nr, s);
         StreamBuf rot;
         QAMD_TRY(rot.alloc(nr * st.dim * 4, s));
-        launch_rotate<0>(src, nr, raw_dim, nullptr, rot.as<float>(), nullptr, 0, 0, s);
+        launch_rotate<0>(src, nr, raw_dim, blocks, nullptr, rot.as<float>(), nullptr, 0, 0, s);
         return st.add(rot.as<float>(), nr, s);
     });
 }
@@ -1487,12 +1644,16 @@ void thresholds_of(uint64_t dim, const uint64_t *n, const double *sum, const dou
 
 // What every *_enc entry point checks before it needs a device.  `required`: two-bit rows cannot do without thresholds.
 qamd_status check_enc_args(const qamd_vector_parameters *vp, int encoding, const float *lo, const float *hi, bool required) {
-    if ((encoding & ~(QAMD_BIN_TWO_BITS | QAMD_BIN_ROTATED)) != 0 || encoding < 0)
+    if ((encoding & ~(QAMD_BIN_TWO_BITS | QAMD_BIN_ROTATED | QAMD_BIN_BLOCKS)) != 0 || encoding < 0 ||
+        ((encoding & QAMD_BIN_BLOCKS) && !(encoding & QAMD_BIN_ROTATED)))  // blocks are blocks of a rotation
         return fail(QAMD_ERR_ARGUMENTS, "unknown binary encoding %d", encoding);
     if ((lo == nullptr) != (hi == nullptr)) return fail(QAMD_ERR_ARGUMENTS, "thresholds: lo and hi come together");
     if ((encoding & QAMD_BIN_ROTATED) && vp->dim > kRotMaxDim)
         return fail(QAMD_ERR_ARGUMENTS, "rotated rows have at most %llu dimensions, not %llu", (unsigned long long)kRotMaxDim,
                     (unsigned long long)vp->dim);
+    if ((encoding & QAMD_BIN_BLOCKS) && vp->dim % kRotBlockMin != 0)
+        return fail(QAMD_ERR_ARGUMENTS, "block-rotated rows have a multiple of %llu dimensions, not %llu",
+                    (unsigned long long)kRotBlockMin, (unsigned long long)vp->dim);
     if (!(encoding & QAMD_BIN_TWO_BITS)) {
         if (lo) return fail(QAMD_ERR_ARGUMENTS, "one-bit rows take no thresholds");
         return QAMD_OK;
@@ -1501,7 +1662,7 @@ qamd_status check_enc_args(const qamd_vector_parameters *vp, int encoding, const
         return fail(QAMD_ERR_ARGUMENTS, "two-bit rows have at most %llu dimensions, not %llu", (unsigned long long)kTwoBitMaxDim,
                     (unsigned long long)vp->dim);
     if (!lo && required) return fail(QAMD_ERR_ARGUMENTS, "two-bit rows need their thresholds");
-    const uint64_t edim = encoder_dim(vp->dim, encoding);  // given thresholds have P entries for rotated rows
+    const uint64_t edim = encoder_dim(vp->dim, encoding);  // given thresholds have P entries for (padded) rotated rows
     for (uint64_t i = 0; lo && i < edim; i++) {
         if (lo[i] != lo[i] || hi[i] != hi[i]) return fail(QAMD_ERR_ARGUMENTS, "threshold %llu is NaN", (unsigned long long)i);
         if (lo[i] > hi[i]) return fail(QAMD_ERR_ARGUMENTS, "threshold %llu: lo %g > hi %g", (unsigned long long)i, lo[i], hi[i]);
@@ -1597,7 +1758,7 @@ qamd_status qamd_bin_encode_enc(const float *data, qamd_mem data_mem, const qamd
         BinStats st;
         DevBuf stage;
         QAMD_TRY(st.begin(h->edim));
-        QAMD_TRY(stats_feed(st, data, data_mem, vp->count, stage, s, stop, stop_user, h->rotated() ? vp->dim : 0));
+        QAMD_TRY(stats_feed(st, data, data_mem, vp->count, stage, s, stop, stop_user, h->rotated() ? vp->dim : 0, h->blocks()));
         QAMD_TRY(set_thresholds_from_stats(h.get(), st, s));
     }
     QAMD_TRY(encode_all(h.get(), data, data_mem, stop, stop_user, s));
@@ -1683,9 +1844,11 @@ qamd_status qamd_bin_save(const qamd_bin *h, const char *data_path, const char *
     for (float t : h->thr_host)
         if (!(fabsf(t) < __builtin_huge_valf())) return fail(QAMD_ERR_IO, "an infinite threshold has no form in the metadata file");
     std::string js = "{\"vector_parameters\":" + vector_parameters_json(h->vp);
-    if (h->encoding == QAMD_BIN_ONE_BIT_ROTATED) js += ",\"encoding\":\"OneBitRotated\"";
-    if (h->two()) {  // (a one-bit file stays the reference's, byte for byte)
-        js += h->rotated() ? ",\"encoding\":\"TwoBitsRotated\",\"thresholds\":{" : ",\"encoding\":\"TwoBits\",\"thresholds\":{";
+    if (h->encoding != QAMD_BIN_ONE_BIT)  // (a one-bit file stays the reference's, byte for byte)
+        js += std::string(",\"encoding\":\"") + (h->two() ? "TwoBits" : "OneBit") + (h->rotated() ? "Rotated" : "") +
+              (h->blocks() ? "Blocks" : "") + "\"";
+    if (h->two()) {
+        js += ",\"thresholds\":{";
         for (int side = 0; side < 2; side++) {
             js += side ? ",\"hi\":[" : "\"lo\":[";
             for (uint64_t i = 0; i < h->edim; i++) {
@@ -1723,12 +1886,18 @@ qamd_status qamd_bin_load(const char *data_path, const char *meta_path, const qa
         if (m.second.kind == JsonValue::String && m.second.text == "TwoBits") encoding = QAMD_BIN_TWO_BITS;
         else if (m.second.kind == JsonValue::String && m.second.text == "OneBitRotated") encoding = QAMD_BIN_ONE_BIT_ROTATED;
         else if (m.second.kind == JsonValue::String && m.second.text == "TwoBitsRotated") encoding = QAMD_BIN_TWO_BITS_ROTATED;
+        else if (m.second.kind == JsonValue::String && m.second.text == "OneBitRotatedBlocks") encoding = QAMD_BIN_ONE_BIT_ROTATED_BLOCKS;
+        else if (m.second.kind == JsonValue::String && m.second.text == "TwoBitsRotatedBlocks") encoding = QAMD_BIN_TWO_BITS_ROTATED_BLOCKS;
         else if (m.second.kind != JsonValue::String || m.second.text != "OneBit")
             return fail(QAMD_ERR_IO, "%s: unknown encoding", meta_path);
     }
     if ((encoding & QAMD_BIN_ROTATED) && vp->dim > kRotMaxDim)
         return fail(QAMD_ERR_IO, "%s: rotated rows of %llu dimensions", meta_path, (unsigned long long)vp->dim);
-    const uint64_t edim = encoder_dim(vp->dim, encoding);  // thresholds of a rotated file have P entries
+    if ((encoding & QAMD_BIN_BLOCKS) && vp->dim % kRotBlockMin != 0)
+        return fail(QAMD_ERR_IO, "%s: block-rotated rows of %llu dimensions, not a multiple of %llu", meta_path,
+                    (unsigned long long)vp->dim, (unsigned long long)kRotBlockMin);
+    const uint64_t edim = encoder_dim(vp->dim, encoding);  // thresholds of a rotated file have P entries, dim of a
+                                                           // block-rotated one (3.2h)
     if (encoding & QAMD_BIN_TWO_BITS) {
         std::string err;
         const JsonValue *tj = json_field(root, "thresholds", err);
@@ -3425,7 +3594,7 @@ qamd_status qamd_bin_encoder_observe(qamd_bin_encoder *e, const float *batch, ui
     if (e->observed + n_rows > e->h->count) return count_mismatch(e->observed + n_rows, e->h->count);
     QAMD_ON_DEVICE(e->device);
     QAMD_TRY(stats_feed(e->stats, batch, batch_mem, n_rows, e->stage, e->stream, e->stop, e->stop_user,
-                        e->h->rotated() ? e->h->vp.dim : 0));
+                        e->h->rotated() ? e->h->vp.dim : 0, e->h->blocks()));
     e->observed += n_rows;
     return QAMD_OK;
 }

@@ -25,12 +25,18 @@ class BinaryEncoding(enum.IntEnum):
     """Bits kept per stored dimension.  TwoBits has no counterpart in the reference: two compares per dimension against
     thresholds mean -+ t * deviation of that dimension's data.  The Rotated kinds (no counterpart
     either) put a randomized Hadamard rotation before the bits: a vector of dim becomes one of P values, P
-    the power of two at or above dim (dim <= 16384), and the store is served as a plain store of P dimensions."""
+    the power of two at or above dim (dim <= 16384), and the store is served as a plain store of P dimensions.  The
+    RotatedBlocks kinds rotate without the pad: dim is a multiple of 64, B is the largest power of two
+    that divides dim (768 = 3 x 256, 1536 = 3 x 512), the vector is rotated as dim / B blocks of B values by the same
+    network cut off after stage B / 2, and the store is served as a plain store of dim dimensions - a row of 768
+    dimensions keeps 768 bits.  For a power-of-two dim, B = dim and the rows are those of the Rotated kinds."""
 
     OneBit = 0
     TwoBits = 1
     OneBitRotated = 4
     TwoBitsRotated = 5
+    OneBitRotatedBlocks = 20
+    TwoBitsRotatedBlocks = 21
 
     @property
     def two_bits(self) -> bool:
@@ -40,14 +46,18 @@ class BinaryEncoding(enum.IntEnum):
     def rotated(self) -> bool:
         return bool(self.value & 4)
 
+    @property
+    def blocks(self) -> bool:
+        return bool(self.value & 16)
+
     def encoder_dim(self, dim: int) -> int:
-        """The dimensions the bits are taken from: dim, or P of a rotated encoding."""
+        """The dimensions the bits are taken from: dim, or P of a rotated encoding without blocks."""
         return _encoder_dim(self, dim)
 
 
 def _encoder_dim(encoding, dim: int) -> int:
     """encoder_dim for an encoding given as any integer (an unknown one is the library's to refuse)."""
-    if not int(encoding) & 4 or dim <= 1:
+    if not int(encoding) & 4 or int(encoding) & 16 or dim <= 1:
         return dim
     return 1 << (dim - 1).bit_length()
 
@@ -140,7 +150,7 @@ class EncodedVectorsBin(EncodedVectorsBase):
 
     @property
     def thresholds(self):
-        """(lo, hi), dim f32 entries each (P each for rotated rows), of a two-bit store; None for one bit."""
+        """(lo, hi), dim f32 entries each (P each for rotated rows without blocks), of a two-bit store; None for one bit."""
         if not self._encoding.two_bits:
             return None
         lo, hi = np.zeros(self._edim, dtype=np.float32), np.zeros(self._edim, dtype=np.float32)
@@ -149,7 +159,7 @@ class EncodedVectorsBin(EncodedVectorsBase):
 
     @property
     def code_bits(self) -> int:
-        """Bits of a stored row: dim, 2 dim, or P and 2 P of the rotated encodings."""
+        """Bits of a stored row: dim, 2 dim (the block-rotated encodings too), or P and 2 P of the rotated encodings."""
         bits = C.c_uint64()
         check(_lib.lib().qamd_bin_get_encoding(self._h, None, C.byref(bits)))
         return int(bits.value)
@@ -172,7 +182,8 @@ class EncodedVectorsBin(EncodedVectorsBase):
                encoding: BinaryEncoding = BinaryEncoding.OneBit, thresholds=None) -> "EncodedVectorsBin":
         """EncodedVectorsBin::<TBitsStoreType, _>::encode (:165-191).  encoding = TwoBits: `thresholds` = (lo, hi), or
         None to take them from the data (find_stats, then thresholds_from_stats with t = 0.43).  OneBitRotated /
-        TwoBitsRotated: the same on the rotated vectors, thresholds of P entries."""
+        TwoBitsRotated: the same on the rotated vectors, thresholds of P entries.  OneBitRotatedBlocks /
+        TwoBitsRotatedBlocks (3.2h): dim % 64 == 0, thresholds of dim entries."""
         data = flatten_rows(orig_data, vector_parameters.dim)
         validate(data, vector_parameters)
         vp = vector_parameters.to_c()
@@ -271,7 +282,8 @@ class EncodedVectorsBin(EncodedVectorsBase):
             check(L.qamd_bin_encoder_begin_enc(C.byref(vp), int(store), int(encoding), lo, hi, stop, None,
                                                stream_ptr(stream), C.byref(enc)))
         passes = [L.qamd_bin_encoder_push]
-        if int(encoding) in (BinaryEncoding.TwoBits, BinaryEncoding.TwoBitsRotated) and thresholds is None:
+        if int(encoding) in (BinaryEncoding.TwoBits, BinaryEncoding.TwoBitsRotated,
+                             BinaryEncoding.TwoBitsRotatedBlocks) and thresholds is None:
             passes.insert(0, L.qamd_bin_encoder_observe)
         try:
             for feed in passes:

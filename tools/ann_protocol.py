@@ -176,11 +176,12 @@ def main():
                     help="binary: also search with 4- / 8-bit scalar queries against the same rows, e.g. 1,4,8; each bit "
                          "count past 1 adds a gpu_query_bits_N entry to a one-bit record (DESIGN 3.2d) and a "
                          "gpu_weighted_query_bits_N entry - weighted queries, DESIGN 3.2f - to a two-bit record")
-    ap.add_argument("--bin-encodings", default="one", metavar="one[,two[,two:T[,one:rot[,two:rot]]]]",
+    ap.add_argument("--bin-encodings", default="one", metavar="one[,two[,two:T[,one:rot[,two:rot[,one:blk[,two:blk]]]]]]",
                     help="binary: a record per row encoding: one = the reference's sign bit; two = two-bit rows with "
                          "thresholds mean -+ 0.43 deviations per dimension (DESIGN 3.2e); two:T = the same with t = T.  "
                          "one:rot / two:rot = the same two behind the randomized Hadamard rotation of DESIGN 3.2g (two:rot "
-                         "with t = 0.43, thresholds from the rotated data).  "
+                         "with t = 0.43, thresholds from the rotated data).  one:blk / two:blk = behind the block rotation "
+                         "of DESIGN 3.2h (dims that are a multiple of 64; a row keeps dim bits).  "
                          "Two-bit and rotated records have no CPU loop (the oracle restates the reference); with --bin-query-bits "
                          "4,8 they carry weighted scalar-query entries")
     ap.add_argument("--out", default="")
@@ -234,11 +235,14 @@ def main():
                         if how == "one":
                             variants.append(("binary", qa.EncodedVectorsBin.encode(data, vp), {}))
                             continue
-                        if how in ("one:rot", "two:rot"):
-                            two = how == "two:rot"
-                            code = qa.BinaryEncoding.TwoBitsRotated if two else qa.BinaryEncoding.OneBitRotated
-                            variants.append((f"binary {'two-bit' if two else 'one-bit'} rotated rows",
-                                             qa.EncodedVectorsBin.encode(data, vp, encoding=code), {"two_bit": two, "rotated": True}))
+                        if how in ("one:rot", "two:rot", "one:blk", "two:blk"):
+                            two, blocks = how.startswith("two"), how.endswith(":blk")
+                            code = qa.BinaryEncoding((21 if two else 20) if blocks else (5 if two else 4))
+                            extra = {"two_bit": two, "rotated": True}
+                            if blocks:
+                                extra["blocks"] = True
+                            variants.append((f"binary {'two-bit' if two else 'one-bit'} {'block-' if blocks else ''}rotated rows",
+                                             qa.EncodedVectorsBin.encode(data, vp, encoding=code), extra))
                             continue
                         t = float(how.split(":")[1]) if ":" in how else 0.43
                         thr = qa.EncodedVectorsBin.thresholds_from_stats(*qa.EncodedVectorsBin.find_stats(data), t)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""What the binary quantizer's rotated rows cost, each call next to its yardstick, from one process with
-HIP events around whole calls, the median of `--reps` after a pre-warm (the method of tools/time_bin_two_bit.py).
+"""What the binary quantizer's rotated rows and block-rotated rows (3.2h) cost, each call next to its
+yardstick, from one process with HIP events around whole calls, the median of `--reps` after a pre-warm (the method of
+tools/time_bin_two_bit.py).
 
     python tools/time_bin_rotated.py [--rows 10000000] [--dim 768] [--reps 5] [--out profiles/bin_rotated.txt]
 
@@ -9,6 +10,9 @@ HIP events around whole calls, the median of `--reps` after a pre-warm (the meth
     encode_query           at dims 128 and `--dim`, 1 and 8 bits, rotated against plain one-bit handles
     score_all, topk(30)    on the rotated store, against a plain one-bit store of P dimensions over the same bytes: the
                            kernels are the same, so a gap beyond the run-to-run spread is a routing mistake to find
+    blocks ...             when `--dim` is a multiple of 64: the same calls on the block-rotated encodings (rows of `--dim`
+                           bits), each against two yardsticks in lines of their own - the padded ROTATED call and the plain
+                           one-bit call (for the scans a plain store of `--dim` dimensions: the same kernels on as many bytes)
 
 Nothing here is a pass condition.  Fewer rows are taken when the device has less memory than the f32 data needs."""
 import argparse
@@ -70,6 +74,30 @@ def main():
         ("topk30", lambda: rot.topk(q_rot, 30, out_ids=ids, out_scores=top), lambda: wide.topk(q_wide, 30, out_ids=ids, out_scores=top),
          f"one-bit store of dim {p}, same bytes"),
     ]
+    if dim % 64 == 0:  # the block-rotated encodings beside the padded ones
+        blk, plain = E.encode(data, vp, encoding=B.OneBitRotatedBlocks), E.encode(data, vp)
+        thr_b = E.encode(data[:head.count], head, encoding=B.TwoBitsRotatedBlocks).thresholds  # dim entries
+        q_blk, q_plain = blk.encode_query(query), plain.encode_query(query)
+        for name, run, rot_base, plain_base, plain_what in (
+                ("blocks encode one-bit", lambda: E.encode(data, vp, encoding=B.OneBitRotatedBlocks),
+                 lambda: E.encode(data, vp, encoding=B.OneBitRotated), lambda: E.encode(data, vp), "plain one-bit encode"),
+                ("blocks encode two-bit", lambda: E.encode(data, vp, encoding=B.TwoBitsRotatedBlocks, thresholds=thr_b),
+                 lambda: E.encode(data, vp, encoding=B.TwoBitsRotated, thresholds=thr), lambda: E.encode(data, vp),
+                 "plain one-bit encode"),
+                ("blocks score_all", lambda: blk.score_all(q_blk, out=scores), lambda: rot.score_all(q_rot, out=scores),
+                 lambda: plain.score_all(q_plain, out=scores), f"plain one-bit store of dim {dim}"),
+                ("blocks topk30", lambda: blk.topk(q_blk, 30, out_ids=ids, out_scores=top),
+                 lambda: rot.topk(q_rot, 30, out_ids=ids, out_scores=top),
+                 lambda: plain.topk(q_plain, 30, out_ids=ids, out_scores=top), f"plain one-bit store of dim {dim}")):
+            pairs.append((name, run, rot_base, f"the ROTATED call, rows of {p} bits"))
+            pairs.append((name, run, plain_base, plain_what))
+        for bits in (1, 8):
+            qb, qr, qo = (h.encode_query(query, query_bits=bits) for h in (blk, rot, plain))
+            run = (lambda qb=qb, bits=bits: blk.encode_query(query, qb, query_bits=bits))
+            pairs.append((f"blocks encode_query dim {dim}, {bits} bit", run,
+                          (lambda qr=qr, bits=bits: rot.encode_query(query, qr, query_bits=bits)), "ROTATED one-bit handle"))
+            pairs.append((f"blocks encode_query dim {dim}, {bits} bit", run,
+                          (lambda qo=qo, bits=bits: plain.encode_query(query, qo, query_bits=bits)), "plain one-bit handle"))
     small = {}
     for qd in sorted({128, dim}):
         x = torch.randn((4096, qd), device="cuda", generator=g, dtype=torch.float32)
@@ -96,7 +124,7 @@ def main():
             tb.append(timed(base))
         med, mb = statistics.median(t), statistics.median(tb)
         line = f"{name:<28} {med:9.4f} ms ({min(t):.4f}-{max(t):.4f})   {what}: {mb:9.4f} ms ({min(tb):.4f}-{max(tb):.4f})   ratio {med / mb:.2f}"
-        if name.startswith("encode one") or name.startswith("encode two"):
+        if " encode one" in " " + name or " encode two" in " " + name:
             line += f"   {gb / (med * 1e-3):6.0f} GB/s of f32 read against {gb / (mb * 1e-3):6.0f} GB/s"
         lines.append(line + "\n")
         print(line, flush=True)
