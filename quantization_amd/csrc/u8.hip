@@ -734,9 +734,22 @@ __global__ __launch_bounds__(kBlock) void u8_score_pairs_kernel(
 // ------------------------------------------------------------------------------ encode kernels
 // Pass 1: global min / max (quantile.rs:5-19).  `value < min` / `value > max` ignore NaN,
 // as fminf/fmaxf do.  Per-block partials; the host folds them.
+//
+// The sign of a zero extreme: `value < min` keeps the FIRST of several equal values, and +0.0 == -0.0, so the reference
+// answers with the sign of the first zero in row order whenever the minimum (or the maximum) is zero.  No fold of
+// floats or of order-preserving keys keeps that, so both kernels report it on the side: a wave (here: a workgroup)
+// whose own extreme is zero finds its first zero and folds (flat index << 1) | sign bit into one 64-bit word with an
+// atomic minimum; MinMaxAcc::result takes the sign from that word.  `base` is the flat index of data[0] among all
+// values fed so far.  Data without a zero extreme never enters that path.
+constexpr unsigned long long kNoZero = ~0ull;
+__device__ __forceinline__ void note_zero(float v, uint64_t idx, unsigned long long &zk) {
+    if (v == 0.0f && zk == kNoZero) zk = (idx << 1) | (__float_as_uint(v) >> 31);  // a thread's indices only grow
+}
 __global__ __launch_bounds__(kBlock) void minmax_kernel(const float *__restrict__ data, uint64_t n,
-                                                       float *__restrict__ partial /* 2 per block */) {
+                                                       float *__restrict__ partial /* 2 per block */, uint64_t base,
+                                                       unsigned long long *__restrict__ first_zero) {
     float mn = 3.40282347e+38f, mx = -3.40282347e+38f;
+    unsigned long long zk = kNoZero;
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     const uint64_t n4 = ((reinterpret_cast<uintptr_t>(data) & 15) == 0) ? n / 4 : 0;
     const float4 *d4 = reinterpret_cast<const float4 *>(data);
@@ -746,11 +759,13 @@ __global__ __launch_bounds__(kBlock) void minmax_kernel(const float *__restrict_
         mn = v.y < mn ? v.y : mn; mx = v.y > mx ? v.y : mx;
         mn = v.z < mn ? v.z : mn; mx = v.z > mx ? v.z : mx;
         mn = v.w < mn ? v.w : mn; mx = v.w > mx ? v.w : mx;
+        note_zero(v.x, i * 4, zk); note_zero(v.y, i * 4 + 1, zk); note_zero(v.z, i * 4 + 2, zk); note_zero(v.w, i * 4 + 3, zk);
     }
     for (uint64_t i = n4 * 4 + (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         float v = data[i];
         mn = v < mn ? v : mn;
         mx = v > mx ? v : mx;
+        note_zero(v, i, zk);
     }
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) {
@@ -758,20 +773,26 @@ __global__ __launch_bounds__(kBlock) void minmax_kernel(const float *__restrict_
         mn = o < mn ? o : mn;
         o = __shfl_xor(mx, m, 64);
         mx = o > mx ? o : mx;
+        const unsigned long long z = __shfl_xor(zk, m, 64);
+        zk = z < zk ? z : zk;
     }
     __shared__ float smn[kBlock / 64], smx[kBlock / 64];
+    __shared__ unsigned long long szk[kBlock / 64];
     if ((threadIdx.x & 63) == 0) {
         smn[threadIdx.x >> 6] = mn;
         smx[threadIdx.x >> 6] = mx;
+        szk[threadIdx.x >> 6] = zk;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < kBlock / 64; w++) {
             mn = smn[w] < mn ? smn[w] : mn;
             mx = smx[w] > mx ? smx[w] : mx;
+            zk = szk[w] < zk ? szk[w] : zk;
         }
         partial[2 * blockIdx.x] = mn;
         partial[2 * blockIdx.x + 1] = mx;
+        if ((mn == 0.0f || mx == 0.0f) && zk != kNoZero) atomicMin(first_zero, (base << 1) + zk);
     }
 }
 
@@ -788,10 +809,13 @@ template <int CTRL> __device__ __forceinline__ float dpp_f32(float v) {
 }
 constexpr int kMinmaxSlots = 64, kMinmaxSlotStride = 64;  // one slot pair per 256-byte line
 __global__ __launch_bounds__(kScanBlock) void minmax_stream_kernel(const float4 *__restrict__ d4, uint64_t n4,
-                                                                  uint32_t *__restrict__ slots) {
+                                                                  uint32_t *__restrict__ slots, uint64_t base_values,
+                                                                  unsigned long long *__restrict__ first_zero) {
     const uint64_t wave = ((uint64_t)blockIdx.x * kScanBlock + threadIdx.x) >> 6;
     const uint64_t base = wave * 1024 + (threadIdx.x & 63);
     if (wave * 1024 >= n4) return;
+    // the same wave index in scalar registers, for the zero path at the end: nothing of it occupies a vector register
+    const uint64_t swave = (uint64_t)blockIdx.x * (kScanBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float mn = 3.40282347e+38f, mx = -3.40282347e+38f;
     const float qnan = __uint_as_float(0x7FC00000u);
     float4 v[16];
@@ -833,6 +857,37 @@ __global__ __launch_bounds__(kScanBlock) void minmax_stream_kernel(const float4 
         const uint32_t kmn = f32_order_key(wmn), kmx = f32_order_key(wmx);
         if (kmn < __builtin_nontemporal_load(slot)) atomicMin(slot, kmn);
         if (kmx > __builtin_nontemporal_load(slot + 1)) atomicMax(slot + 1, kmx);
+    }
+    // A zero extreme (see minmax_kernel): the tile's first zero in row order.  Lane 0 holds the whole wave's fold.
+    const float umn = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wmn)));
+    const float umx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wmx)));
+    // Data full of zeros (anything clipped at zero) brings every wave here; all but the first few leave at once: an
+    // earlier zero is already known.  (Reading the tile again costs as much as the first read: 2M x 768 took 4.8 ms
+    // instead of 3.8 ms without this test.)  The word only falls, so a stale value costs a redundant search, no more.
+    const unsigned long long tile_key = (base_values + swave * 4096) << 1;
+    if ((umn == 0.0f || umx == 0.0f) && __hip_atomic_load(first_zero, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > tile_key) {
+        const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));  // not threadIdx: see swave
+        uint32_t zk = 0xFFFFFFFFu;  // ((float4 of the tile * 4 + component) << 1) | sign bit
+#pragma unroll 1
+        for (int j = 15; j >= 0; j--) {  // downwards: the lowest index is written last.  The tile is read again (it
+            const uint64_t i = swave * 1024 + j * 64 + lane;  // is in the cache), a float4 at a time
+            if (i >= n4) continue;
+            const float4 t = d4[i];
+            const uint32_t at = ((uint32_t)j * 64 + lane) * 8;
+            if (t.w == 0.0f) zk = (at + 6) | (__float_as_uint(t.w) >> 31);
+            if (t.z == 0.0f) zk = (at + 4) | (__float_as_uint(t.z) >> 31);
+            if (t.y == 0.0f) zk = (at + 2) | (__float_as_uint(t.y) >> 31);
+            if (t.x == 0.0f) zk = at | (__float_as_uint(t.x) >> 31);
+        }
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const uint32_t z = __shfl_xor(zk, m, 64);
+            zk = z < zk ? z : zk;
+        }
+        if (lane == 0 && zk != 0xFFFFFFFFu) {
+            const unsigned long long key = tile_key + zk;
+            if (key < __builtin_nontemporal_load(first_zero)) atomicMin(first_zero, key);
+        }
     }
 }
 
@@ -944,28 +999,15 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
         const float *src = data + r * dim;
         uint32_t *dst = codes32 + (row0 + r) * dwords;
         uint32_t s1 = 0, s2 = 0;
-        const bool vec4 = (dim % 4 == 0) && ((reinterpret_cast<uintptr_t>(data) & 15) == 0);
-        for (uint32_t d = lane; d < dwords; d += 64) {
+        for (uint32_t d = lane; d < dwords; d += 64) {  // dword loads: dim % 4 != 0 or an unaligned source (launch_quantize)
             uint32_t packed = 0;
-            if (vec4 && d * 4 < dim) {  // whole dword inside the row: one aligned 16-byte load
-                const float4 f = ld_nt(reinterpret_cast<const float4 *>(src) + d);
-                const float fv[4] = {f.x, f.y, f.z, f.w};
 #pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    uint32_t c = f32_to_u8(fv[b], alpha, offset);
-                    packed |= c << (8 * b);
-                    s1 += c;
-                    s2 += c * c;
-                }
-            } else {
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    uint32_t j = d * 4 + b;
-                    uint32_t c = j < dim ? f32_to_u8(src[j], alpha, offset) : pad_code;
-                    packed |= c << (8 * b);
-                    s1 += c;
-                    s2 += c * c;
-                }
+            for (int b = 0; b < 4; b++) {
+                uint32_t j = d * 4 + b;
+                uint32_t c = j < dim ? f32_to_u8(src[j], alpha, offset) : pad_code;
+                packed |= c << (8 * b);
+                s1 += c;
+                s2 += c * c;
             }
             dst[d] = packed;
         }
@@ -1748,10 +1790,15 @@ struct MinMaxAcc {
     std::vector<float> hp;
     int mm_grid = 0;
     float mn = 3.40282347e+38f, mx = -3.40282347e+38f;  // folded from the scalar-form launches
+    uint64_t fed = 0;  // values fed so far: the flat index of the next feed's first value
+    static constexpr size_t kZeroWordAt = kMinmaxSlots * kMinmaxSlotStride;  // behind the slots: (index << 1) | sign of the first zero
+
+    unsigned long long *first_zero() { return reinterpret_cast<unsigned long long *>(slots.as<uint32_t>() + kZeroWordAt); }
 
     qamd_status init(hipStream_t s) {
-        QAMD_TRY(slots.alloc(kMinmaxSlots * kMinmaxSlotStride * sizeof(uint32_t)));
-        std::vector<uint32_t> init(kMinmaxSlots * kMinmaxSlotStride, 0u);
+        QAMD_TRY(slots.alloc((kZeroWordAt + 2) * sizeof(uint32_t)));
+        std::vector<uint32_t> init(kZeroWordAt + 2, 0u);
+        init[kZeroWordAt] = init[kZeroWordAt + 1] = 0xFFFFFFFFu;  // kNoZero
         for (int b = 0; b < kMinmaxSlots; b++) {
             init[b * kMinmaxSlotStride] = 0xFFFFFFFFu;  // min slot: largest key
             init[b * kMinmaxSlotStride + 1] = 0u;       // max slot: smallest key
@@ -1770,28 +1817,30 @@ struct MinMaxAcc {
             const uint64_t n4 = nvals / 4;
             const unsigned grid = (unsigned)((n4 + 1024 * (kScanBlock / 64) - 1) / (1024 * (kScanBlock / 64)));
             hipLaunchKernelGGL(minmax_stream_kernel, dim3(grid), dim3(kScanBlock), 0, s,
-                               reinterpret_cast<const float4 *>(src), n4, slots.as<uint32_t>());
+                               reinterpret_cast<const float4 *>(src), n4, slots.as<uint32_t>(), fed, first_zero());
             if (nvals % 4) {  // the 1..3 trailing values
                 hipLaunchKernelGGL(minmax_kernel, dim3(1), dim3(kBlock), 0, s, src + n4 * 4, nvals % 4,
-                                   partial.as<float>());
+                                   partial.as<float>(), fed + n4 * 4, first_zero());
                 QAMD_TRY(copy_out(hp.data(), QAMD_MEM_HOST, partial.ptr, 8, s));
                 if (hp[0] < mn) mn = hp[0];
                 if (hp[1] > mx) mx = hp[1];
             }
         } else {  // unaligned input: grid-stride scalar form
-            hipLaunchKernelGGL(minmax_kernel, dim3(mm_grid), dim3(kBlock), 0, s, src, nvals, partial.as<float>());
+            hipLaunchKernelGGL(minmax_kernel, dim3(mm_grid), dim3(kBlock), 0, s, src, nvals, partial.as<float>(), fed,
+                               first_zero());
             QAMD_TRY(copy_out(hp.data(), QAMD_MEM_HOST, partial.ptr, hp.size() * 4, s));
             for (int b = 0; b < mm_grid; b++) {
                 if (hp[2 * b] < mn) mn = hp[2 * b];
                 if (hp[2 * b + 1] > mx) mx = hp[2 * b + 1];
             }
         }
+        fed += nvals;
         QAMD_HIP(hipGetLastError());
         return QAMD_OK;
     }
 
     qamd_status result(hipStream_t s, float &out_mn, float &out_mx) {
-        std::vector<uint32_t> all_slots(kMinmaxSlots * kMinmaxSlotStride);
+        std::vector<uint32_t> all_slots(kZeroWordAt + 2);
         QAMD_TRY(copy_out(all_slots.data(), QAMD_MEM_HOST, slots.ptr, all_slots.size() * 4, s));
         auto key_to_f32 = [](uint32_t k) {
             uint32_t u = k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu);
@@ -1809,6 +1858,14 @@ struct MinMaxAcc {
                 const float v = key_to_f32(kmx);
                 if (v > mx) mx = v;
             }
+        }
+        // a zero extreme carries the sign of the first zero fed (quantile.rs:5-19 keeps the first of equal values)
+        unsigned long long zero_word;
+        memcpy(&zero_word, &all_slots[kZeroWordAt], 8);
+        if (zero_word != kNoZero) {
+            const float z = (zero_word & 1) ? -0.0f : 0.0f;
+            if (mn == 0.0f) mn = z;
+            if (mx == 0.0f) mx = z;
         }
         out_mn = mn;
         out_mx = mx;
