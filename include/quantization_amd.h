@@ -61,6 +61,20 @@ typedef enum {
 
 /* quantization/src/encoded_vectors.rs:6-11 */
 typedef enum { QAMD_DOT = 0, QAMD_L1 = 1, QAMD_L2 = 2 } qamd_distance;
+enum { QAMD_ROTATED = 8,   /* flag: or-ed onto QAMD_DOT or QAMD_L2 in qamd_vector_parameters.distance_type */
+       QAMD_DOT_ROTATED = 8, QAMD_L2_ROTATED = 10 };
+/* A ROTATED scalar-u8 store (no counterpart in the reference).  qamd_u8_encode, qamd_u8_encoder_begin and
+ * qamd_u8_from_rows take QAMD_DOT_ROTATED or QAMD_L2_ROTATED as distance_type: every row - and every query, inside
+ * qamd_u8_encode_query / qamd_u8_encode_query_batch - goes through a fixed randomized Hadamard block rotation (blocks of
+ * B = the largest power of two dividing dim, scaled by 2^(-log2(B)/2)) before the quantizer sees it.  The rotation is
+ * orthonormal, so scores approximate the same Dot / L2 as a plain store's, but no single dimension of large magnitude
+ * stretches the quantization interval.  dim must be a multiple of 64, at most 16384; QAMD_L1 | QAMD_ROTATED is refused
+ * (L1 is not rotation invariant), and so is the flag on every qamd_pq_*, qamd_bin_*, qamd_f32_* and qamd_*_sharded_*
+ * constructor (QAMD_ERR_ARGUMENTS, before any device call).  qamd_u8_get_metadata reports the flagged value, so
+ * get_metadata -> from_rows round-trips; qamd_u8_save writes the base metric plus "rotation":"HadamardBlocks".
+ * qamd_u8_upsert rotates what it is handed; qamd_u8_topk_rescored compares the BASE metric with the originals', which
+ * stay plain.  qamd_u8_find_min_max / qamd_u8_find_quantile_interval see no parameters and stay plain.  The feature adds
+ * no symbol: this header still declares 192 entry points. */
 
 typedef enum { QAMD_MEM_HOST = 0, QAMD_MEM_DEVICE = 1 } qamd_mem;
 

@@ -32,10 +32,12 @@
 #include "topk.hpp"
 #include "topk_device.hpp"
 #include "rescore.hpp"
+#include "rotate_blocks.hpp"
 
 #pragma clang fp contract(off)
 
 using namespace qamd;
+using namespace qamd::rot;
 
 namespace {
 
@@ -787,46 +789,7 @@ __global__ __launch_bounds__(kBlock) void bin_encode_scalar_kernel(const float *
 // butterflies of stages s = 1, 2, 4, ..., P / 2 in that order - (a, b) = (y_j, y_{j+s}) -> (a + b, a - b), one f32
 // operation each (this file compiles with contraction off).  A stage reads only the stage before it, so any split of
 // the work gives the same bits; the ORDER of the stages is part of the definition (f32 addition is not associative).
-__device__ __forceinline__ float rot_signed(float v, uint32_t i) {
-    uint32_t h = i * 0x9E3779B1u;
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, v) ^ (h << 31));
-}
-
-// The value lane (l ^ M) holds.  Inside a DPP row of 16 lanes a DPP move: quad_perm for 1 and 2, row_ror:8 for 8, and for
-// 4 the two rotations by 12 and 4 (lane i reads lane (i + 4) % 16 and (i - 4) % 16), of which a lane keeps the one its
-// bit 2 asks for.  Across rows __shfl_xor (ds_bpermute).
-template <int M> __device__ __forceinline__ float lane_xor(float v, int lane) {
-    const int x = __builtin_bit_cast(int, v);
-    int r;
-    if constexpr (M == 1) {
-        r = __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false);
-    } else if constexpr (M == 2) {
-        r = __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false);
-    } else if constexpr (M == 4) {
-        const int up = __builtin_amdgcn_update_dpp(0, x, 0x12C, 0xF, 0xF, false);
-        const int dn = __builtin_amdgcn_update_dpp(0, x, 0x124, 0xF, 0xF, false);
-        r = (lane & 4) ? dn : up;
-    } else if constexpr (M == 8) {
-        r = __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, false);
-    } else {
-        r = __shfl_xor(x, M);
-    }
-    return __builtin_bit_cast(float, r);
-}
-// One stage whose pairs sit M lanes apart: the lower lane keeps a + b, the upper a - b = a + (-b).
-template <int M> __device__ __forceinline__ float lane_butterfly(float v, int lane) {
-    const float p = lane_xor<M>(v, lane);
-    return p + ((lane & M) ? -v : v);
-}
-__device__ __forceinline__ void butterfly(float &a, float &b) {
-    const float s = a + b, d = a - b;
-    a = s, b = d;
-}
+// rot_signed, lane_butterfly, butterfly, load_chunk and the block rotation of a whole row: rotate_blocks.hpp.
 
 // What the rotation kernels do with a finished row.  MODE 0: the P rotated floats to `out` (statistics, scalar-code
 // encoders).  MODE 1: bit i = y_i > 0.  MODE 2: bit i = y_i > lo_i, bit P + i = y_i > hi_i (thr = lo | hi, 2 P floats).
@@ -856,26 +819,6 @@ __device__ __forceinline__ void emit_chunks(const float (&y)[4], uint32_t c0, in
             if (t8 == 0) dst[P / 32 + (c >> 3)] = d1;
         }
     }
-}
-
-// Four adjacent values of a row from index i0 on: one 16-byte load where the host found dim % 4 == 0 and an aligned
-// source (`vec`), else four guarded dword loads; +0.0 from dim on; then the signs and, the four being adjacent, stages 1
-// and 2.
-__device__ __forceinline__ void load_chunk(const float *__restrict__ src, uint32_t i0, uint32_t dim, int vec, float (&y)[4]) {
-    if (vec) {
-        const float4 t = i0 < dim ? __builtin_bit_cast(float4, ld_nt(reinterpret_cast<const uint4 *>(src + i0)))
-                                  : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        y[0] = t.x, y[1] = t.y, y[2] = t.z, y[3] = t.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; e++) y[e] = i0 + e < dim ? src[i0 + e] : 0.0f;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; e++) y[e] = rot_signed(y[e], i0 + e);
-    butterfly(y[0], y[1]);
-    butterfly(y[2], y[3]);
-    butterfly(y[0], y[2]);
-    butterfly(y[1], y[3]);
 }
 
 // A wave per row, the row in registers: P = 64 E K, lane l holds value e of chunk k at index (64 k + l) E + e, so a
@@ -971,8 +914,6 @@ __global__ __launch_bounds__(kBlock) void bin_rotate_kernel(const float *__restr
 // thread loads 4-value chunks (stages 1 and 2 in registers, as above) into the LDS row, the stages from 4 on run there -
 // P / 2 pairs per stage over the 256 threads, a barrier between stages - and the chunks are read back for emit_chunks,
 // a wave 64 consecutive chunks at a time.
-constexpr uint32_t kRotWaveMax = 2048;  // the widest row bin_rotate_kernel takes: 32 values per lane
-
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void bin_rotate_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
                                                                uint32_t P, int vec, const float *__restrict__ thr,
@@ -1038,42 +979,7 @@ __global__ __launch_bounds__(kBlock) void bin_rotate_blocks_kernel(const float *
     for (uint64_t r = wave; r < n_rows; r += n_waves) {
         const float *src = data + r * dim;
         float y[K][4];
-#pragma unroll
-        for (int k = 0; k < K; k++) load_chunk(src, (uint32_t)(k * 64 + lane) * 4, dim, vec, y[k]);
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                float v = y[k][e];
-                v = lane_butterfly<1>(v, lane);
-                v = lane_butterfly<2>(v, lane);
-                v = lane_butterfly<4>(v, lane);
-                v = lane_butterfly<8>(v, lane);
-                y[k][e] = v;
-            }
-        }
-        // (one branch per stage, not per value: the 4 K ds_bpermute of a stage stay in one block and overlap)
-        if (64u < B) {
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) y[k][e] = lane_butterfly<16>(y[k][e], lane);
-            }
-        }
-        if (128u < B) {
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) y[k][e] = lane_butterfly<32>(y[k][e], lane);
-            }
-        }
-        if (256u < B) {  // B == 512
-#pragma unroll
-            for (int k = 0; k + 1 < K; k += 2) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) butterfly(y[k][e], y[k + 1][e]);
-            }
-        }
+        rotate_blocks_wave<K>(src, dim, B, vec, lane, y);
         float *out_row = MODE == 0 ? out + r * dim : nullptr;
         uint32_t *dst = MODE == 0 ? nullptr : rows + (row0 + r) * row_words;
         // only the last chunk can hold idle lanes; the chunks before it go without a branch, so their threshold loads
@@ -1100,21 +1006,7 @@ __global__ __launch_bounds__(kBlock) void bin_rotate_blocks_lds_kernel(const flo
     const uint32_t chunks = dim / 4;
     for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
         const float *src = data + r * dim;
-        for (uint32_t c = threadIdx.x; c < chunks; c += kBlock) {
-            float y[4];
-            load_chunk(src, c * 4, dim, vec, y);
-            reinterpret_cast<float4 *>(rot_row)[c] = make_float4(y[0], y[1], y[2], y[3]);
-        }
-        for (uint32_t s = 4; s < B; s <<= 1) {
-            __syncthreads();
-            for (uint32_t b = threadIdx.x; b < dim / 2; b += kBlock) {
-                const uint32_t j = ((b & ~(s - 1)) << 1) | (b & (s - 1));
-                float a = rot_row[j], d = rot_row[j + s];
-                butterfly(a, d);
-                rot_row[j] = a, rot_row[j + s] = d;
-            }
-        }
-        __syncthreads();
+        rotate_blocks_lds(src, dim, B, vec, rot_row);
         float *out_row = MODE == 0 ? out + r * dim : nullptr;
         uint32_t *dst = MODE == 0 ? nullptr : rows + (row0 + r) * row_words;
         for (uint32_t c0 = (threadIdx.x >> 6) * 64; c0 < chunks; c0 += kBlock) {
@@ -1196,8 +1088,6 @@ uint64_t rot_dim(uint64_t dim) {
     while (p < dim) p <<= 1;
     return p;
 }
-constexpr uint64_t kRotMaxDim = 16384;  // a rotated row is at most 64 KiB of f32: the LDS bin_rotate_lds_kernel asks for
-constexpr uint64_t kRotBlockMin = 64;   // block-rotated rows (3.2h): dim is a multiple of it, so no block is smaller
 
 // B of DESIGN 3.2h: the largest power of two that divides dim (dim != 0)
 uint64_t rot_block(uint64_t dim) { return dim & (~dim + 1); }
@@ -1745,6 +1635,7 @@ qamd_status qamd_bin_encode_enc(const float *data, qamd_mem data_mem, const qamd
                                 qamd_bin_encoding encoding, const float *lo, const float *hi, qamd_stop_fn stop,
                                 void *stop_user, void *stream, qamd_bin **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    QAMD_TRY(refuse_rotated(vp));
     QAMD_TRY(check_enc_args(vp, encoding, lo, hi, false));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
@@ -1770,6 +1661,7 @@ qamd_status qamd_bin_from_rows_enc(const uint8_t *rows, qamd_mem rows_mem, const
                                    qamd_bits_store store, qamd_bin_encoding encoding, const float *lo, const float *hi,
                                    void *stream, qamd_bin **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    QAMD_TRY(refuse_rotated(vp));
     QAMD_TRY(check_enc_args(vp, encoding, lo, hi, true));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     QAMD_ON_DEVICE(current_device());
@@ -1869,6 +1761,7 @@ qamd_status qamd_bin_save(const qamd_bin *h, const char *data_path, const char *
 qamd_status qamd_bin_load(const char *data_path, const char *meta_path, const qamd_vector_parameters *vp,
                           qamd_bits_store store, qamd_bin **out) {
     if (!data_path || !meta_path || !vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    QAMD_TRY(refuse_rotated(vp));
     JsonValue root;
     QAMD_TRY(read_metadata(meta_path, root));
     qamd_vector_parameters file_vp{};
@@ -3567,6 +3460,7 @@ qamd_status qamd_bin_encoder_begin_enc(const qamd_vector_parameters *vp, qamd_bi
                                        const float *lo, const float *hi, qamd_stop_fn stop, void *stop_user, void *stream,
                                        qamd_bin_encoder **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    QAMD_TRY(refuse_rotated(vp));
     QAMD_TRY(check_enc_args(vp, encoding, lo, hi, false));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     QAMD_ON_DEVICE(current_device());

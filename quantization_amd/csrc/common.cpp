@@ -556,6 +556,12 @@ qamd_status read_metadata(const char *meta_path, JsonValue &root) {
     return QAMD_OK;
 }
 
+qamd_status refuse_rotated(const qamd_vector_parameters *vp) {
+    if (vp->distance_type >= 0 && (vp->distance_type & QAMD_ROTATED))
+        return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: only a single-GPU scalar-u8 store can be rotated", vp->distance_type);
+    return QAMD_OK;
+}
+
 const char *distance_name(int d) { return d == QAMD_DOT ? "Dot" : d == QAMD_L1 ? "L1" : "L2"; }
 
 bool parse_distance(const std::string &s, int &d) {

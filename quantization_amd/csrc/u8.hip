@@ -38,11 +38,13 @@
 #include "topk.hpp"
 #include "topk_device.hpp"
 #include "rescore.hpp"
+#include "rotate_blocks.hpp"
 #include "u8_internal.hpp"
 
 #pragma clang fp contract(off)
 
 using namespace qamd;
+using namespace qamd::rot;
 
 namespace {
 
@@ -1045,6 +1047,266 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
     }
 }
 
+// ---- rotated stores (the reference has no counterpart) ----
+// The store holds y^ = c * y, y the block rotation of the row (rotate_blocks.hpp) and c = 2^(-log2(B) / 2)
+// rounded to f32: one multiply per value, rounded on its own (__fmul_rn), then the quantizer above on y^.  dim is a
+// multiple of 64, so actual_dim == dim: no pad codes, and a 4-value chunk is one dword of codes.  Three consumers of a
+// rotated row, each as a wave per row (dim <= 2048, the row in registers: lane l holds chunk k * 64 + l in y[k]) and as
+// a workgroup per row (the row in LDS): min/max (pass 1; nothing is written per row), quantize (pass 2, push, upsert:
+// the codes and the row offset as quantize16_kernel writes them) and the values themselves (queries, the quantile sample).
+// The lanes of a last chunk past dim / 4 hold +-0.0 (rotate_blocks_wave): they are kept out of every fold and store.
+// K = 4 and K = 8 carry the chunk stages that dim = 1024 and dim = 2048, one block each, need (POW2).
+__device__ __forceinline__ uint32_t rot_quant4(const float (&v)[4], float alpha, float offset, float r_alpha, int fast) {
+    const float4 f = make_float4(v[0], v[1], v[2], v[3]);
+    if (fast) return f32x4_to_u8x4_fast(f, alpha, offset, r_alpha);
+    return f32_to_u8(f.x, alpha, offset) | (f32_to_u8(f.y, alpha, offset) << 8) | (f32_to_u8(f.z, alpha, offset) << 16) |
+           (f32_to_u8(f.w, alpha, offset) << 24);
+}
+// vector_offset of a row from its code sums (quantize16_kernel's epilogue; s1 <= 127 * 16384 < 2^24 always).  `sum2` is
+// the f32 sum of squares: (float)s2 below 2^24, else the caller's replay of the reference's sequential f32 loop.
+__device__ __forceinline__ float rot_row_offset(uint32_t dim, float alpha, float offset, int distance, int invert, uint32_t s1,
+                                                float sum2) {
+    const float D = (float)dim;
+    float vo;
+    if (distance == QAMD_DOT) {
+        const float sum = (float)s1;
+        vo = D * offset * offset + sum * alpha * offset;
+    } else {
+        vo = D * offset * offset + sum2 * alpha * alpha;
+    }
+    return invert ? -vo : vo;
+}
+// The wave's fold of pass 1 into the accumulator's slots (minmax_stream_kernel's protocol) and, for a zero extreme, the
+// first zero's (flat index << 1) | sign (minmax_kernel's).
+__device__ __forceinline__ void rot_minmax_commit(float mn, float mx, unsigned long long zk, uint64_t slot_id, int lane,
+                                                  uint32_t *__restrict__ slots, uint64_t base_values,
+                                                  unsigned long long *__restrict__ first_zero) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        float o = __shfl_xor(mn, m, 64);
+        mn = o < mn ? o : mn;
+        o = __shfl_xor(mx, m, 64);
+        mx = o > mx ? o : mx;
+        const unsigned long long z = __shfl_xor(zk, m, 64);
+        zk = z < zk ? z : zk;
+    }
+    if (lane == 0) {
+        uint32_t *slot = slots + (slot_id & (kMinmaxSlots - 1)) * kMinmaxSlotStride;
+        const uint32_t kmn = f32_order_key(mn), kmx = f32_order_key(mx);
+        if (kmn < __builtin_nontemporal_load(slot)) atomicMin(slot, kmn);
+        if (kmx > __builtin_nontemporal_load(slot + 1)) atomicMax(slot + 1, kmx);
+        if ((mn == 0.0f || mx == 0.0f) && zk != kNoZero) atomicMin(first_zero, (base_values << 1) + zk);
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(kBlock) void u8_rot_minmax_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                              uint32_t B, float c, int vec, uint32_t *__restrict__ slots,
+                                                              uint64_t base_values,
+                                                              unsigned long long *__restrict__ first_zero) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    if (wave >= n_rows) return;
+    const uint32_t chunks = dim / 4;
+    float mn = 3.40282347e+38f, mx = -3.40282347e+38f;
+    unsigned long long zk = kNoZero;
+    for (uint64_t r = wave; r < n_rows; r += n_waves) {
+        float y[K][4];
+        rotate_blocks_wave<K, K == 4 || K == 8>(data + r * dim, dim, B, vec, lane, y);
+        uint32_t z = 0xFFFFFFFFu;  // (index in the row << 1) | sign of the lane's first zero: downwards, the lowest last
+#pragma unroll
+        for (int k = K - 1; k >= 0; k--) {
+            const uint32_t ch = (uint32_t)(k * 64 + lane);
+            if (k < K - 1 || ch < chunks) {
+#pragma unroll
+                for (int e = 3; e >= 0; e--) {
+                    const float v = __fmul_rn(y[k][e], c);
+                    mn = v < mn ? v : mn;
+                    mx = v > mx ? v : mx;
+                    if (v == 0.0f) z = ((ch * 4 + e) << 1) | (__float_as_uint(v) >> 31);
+                }
+            }
+        }
+        if (z != 0xFFFFFFFFu && zk == kNoZero) zk = ((r * dim) << 1) + z;  // a lane's rows only grow
+    }
+    rot_minmax_commit(mn, mx, zk, wave, lane, slots, base_values, first_zero);
+}
+
+__global__ __launch_bounds__(kBlock) void u8_rot_minmax_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                                  uint32_t B, float c, int vec, uint32_t *__restrict__ slots,
+                                                                  uint64_t base_values,
+                                                                  unsigned long long *__restrict__ first_zero) {
+    extern __shared__ float rot_row[];
+    const uint32_t chunks = dim / 4;
+    float mn = 3.40282347e+38f, mx = -3.40282347e+38f;
+    unsigned long long zk = kNoZero;
+    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        rotate_blocks_lds(data + r * dim, dim, B, vec, rot_row);
+        uint32_t z = 0xFFFFFFFFu;
+        for (uint32_t ch = threadIdx.x; ch < chunks; ch += kBlock) {
+            const float4 t = reinterpret_cast<const float4 *>(rot_row)[ch];
+            const float y[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const float v = __fmul_rn(y[e], c);
+                mn = v < mn ? v : mn;
+                mx = v > mx ? v : mx;
+                if (v == 0.0f && z == 0xFFFFFFFFu) z = ((ch * 4 + e) << 1) | (__float_as_uint(v) >> 31);
+            }
+        }
+        if (z != 0xFFFFFFFFu && zk == kNoZero) zk = ((r * dim) << 1) + z;
+        __syncthreads();  // the next row's chunks overwrite the LDS row
+    }
+    rot_minmax_commit(mn, mx, zk, (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), threadIdx.x & 63, slots,
+                      base_values, first_zero);
+}
+
+template <int K>
+__global__ __launch_bounds__(kBlock) void u8_rot_quantize_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                                uint32_t B, float c, int vec, float alpha, float offset,
+                                                                int fast, int distance, int invert,
+                                                                uint32_t *__restrict__ codes32, float *__restrict__ offsets,
+                                                                uint64_t row0) {
+    const float r_alpha = 1.0f / alpha;
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    const uint32_t chunks = dim / 4;
+    for (uint64_t r = wave; r < n_rows; r += n_waves) {
+        float y[K][4];
+        rotate_blocks_wave<K, K == 4 || K == 8>(data + r * dim, dim, B, vec, lane, y);
+        uint32_t *dst = codes32 + (row0 + r) * chunks;
+        uint32_t packed[K];
+        uint32_t s1 = 0, s2 = 0;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const uint32_t ch = (uint32_t)(k * 64 + lane);
+            const bool live = k < K - 1 || ch < chunks;
+            const float v[4] = {__fmul_rn(y[k][0], c), __fmul_rn(y[k][1], c), __fmul_rn(y[k][2], c), __fmul_rn(y[k][3], c)};
+            const uint32_t p = live ? rot_quant4(v, alpha, offset, r_alpha, fast) : 0u;
+            packed[k] = p;
+            s1 = __builtin_amdgcn_udot4(p, 0x01010101u, s1, false);
+            s2 = __builtin_amdgcn_udot4(p, p, s2, false);
+            if (live) __builtin_nontemporal_store(p, dst + ch);  // 64 lanes x 4 B: 256 consecutive bytes of the row
+        }
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            s1 += __shfl_xor(s1, m, 64);
+            s2 += __shfl_xor(s2, m, 64);
+        }
+        s1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s1);  // every lane holds the sums: scalar from here on
+        s2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s2);
+        float sum2 = (float)s2;
+        if (distance == QAMD_L2 && s2 >= (1u << 24)) {  // the reference's sequential f32 sum, in index order
+            sum2 = 0.0f;
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                for (uint32_t l = 0; l < 64 && (uint32_t)(k * 64) + l < chunks; l++) {
+                    const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)packed[k], (int)l);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const float cf = (float)((p >> (8 * e)) & 0xFFu);
+                        sum2 += cf * cf;
+                    }
+                }
+            }
+        }
+        if (lane == 0) offsets[row0 + r] = rot_row_offset(dim, alpha, offset, distance, invert, s1, sum2);
+    }
+}
+
+// The spare words of the LDS row carry the workgroup's folds: a chunk's first word keeps its four codes (for the
+// sequential replay), words 1 and 2 of chunks 0 .. 3 the four waves' code sums.
+__global__ __launch_bounds__(kBlock) void u8_rot_quantize_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                                    uint32_t B, float c, int vec, float alpha, float offset,
+                                                                    int fast, int distance, int invert,
+                                                                    uint32_t *__restrict__ codes32, float *__restrict__ offsets,
+                                                                    uint64_t row0) {
+    extern __shared__ float rot_row[];
+    uint32_t *row_u = reinterpret_cast<uint32_t *>(rot_row);
+    const float r_alpha = 1.0f / alpha;
+    const uint32_t chunks = dim / 4;
+    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        rotate_blocks_lds(data + r * dim, dim, B, vec, rot_row);
+        uint32_t *dst = codes32 + (row0 + r) * chunks;
+        uint32_t s1 = 0, s2 = 0;
+        for (uint32_t ch = threadIdx.x; ch < chunks; ch += kBlock) {
+            const float4 t = reinterpret_cast<const float4 *>(rot_row)[ch];
+            const float v[4] = {__fmul_rn(t.x, c), __fmul_rn(t.y, c), __fmul_rn(t.z, c), __fmul_rn(t.w, c)};
+            const uint32_t p = rot_quant4(v, alpha, offset, r_alpha, fast);
+            s1 = __builtin_amdgcn_udot4(p, 0x01010101u, s1, false);
+            s2 = __builtin_amdgcn_udot4(p, p, s2, false);
+            __builtin_nontemporal_store(p, dst + ch);
+            row_u[ch * 4] = p;  // the thread's own chunk
+        }
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            s1 += __shfl_xor(s1, m, 64);
+            s2 += __shfl_xor(s2, m, 64);
+        }
+        __syncthreads();  // every chunk has been read: words 1 and 2 of chunks 0 .. 3 are free
+        if ((threadIdx.x & 63) == 0) {
+            row_u[(threadIdx.x >> 6) * 4 + 1] = s1;
+            row_u[(threadIdx.x >> 6) * 4 + 2] = s2;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            s1 = s2 = 0;
+            for (int w = 0; w < kBlock / 64; w++) s1 += row_u[w * 4 + 1], s2 += row_u[w * 4 + 2];
+            float sum2 = (float)s2;
+            if (distance == QAMD_L2 && s2 >= (1u << 24)) {
+                sum2 = 0.0f;
+                for (uint32_t ch = 0; ch < chunks; ch++) {
+                    const uint32_t p = row_u[ch * 4];
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const float cf = (float)((p >> (8 * e)) & 0xFFu);
+                        sum2 += cf * cf;
+                    }
+                }
+            }
+            offsets[row0 + r] = rot_row_offset(dim, alpha, offset, distance, invert, s1, sum2);
+        }
+        __syncthreads();  // the next row's chunks overwrite the LDS row
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(kBlock) void u8_rot_values_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                              uint32_t B, float c, int vec, float *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    const uint32_t chunks = dim / 4;
+    for (uint64_t r = wave; r < n_rows; r += n_waves) {
+        float y[K][4];
+        rotate_blocks_wave<K, K == 4 || K == 8>(data + r * dim, dim, B, vec, lane, y);
+        float4 *out_row = reinterpret_cast<float4 *>(out + r * dim);
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const uint32_t ch = (uint32_t)(k * 64 + lane);
+            if (k < K - 1 || ch < chunks)
+                out_row[ch] = make_float4(__fmul_rn(y[k][0], c), __fmul_rn(y[k][1], c), __fmul_rn(y[k][2], c), __fmul_rn(y[k][3], c));
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void u8_rot_values_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                                  uint32_t B, float c, int vec, float *__restrict__ out) {
+    extern __shared__ float rot_row[];
+    const uint32_t chunks = dim / 4;
+    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        rotate_blocks_lds(data + r * dim, dim, B, vec, rot_row);
+        float4 *out_row = reinterpret_cast<float4 *>(out + r * dim);
+        for (uint32_t ch = threadIdx.x; ch < chunks; ch += kBlock) {
+            const float4 t = reinterpret_cast<const float4 *>(rot_row)[ch];
+            out_row[ch] = make_float4(__fmul_rn(t.x, c), __fmul_rn(t.y, c), __fmul_rn(t.z, c), __fmul_rn(t.w, c));
+        }
+        __syncthreads();  // the next row's chunks overwrite the LDS row
+    }
+}
+
 // encode_query on device (encoded_vectors_u8.rs:290-329): one wave.
 // qbuf: [0] offset f32, [16..] codes.
 __global__ __launch_bounds__(64) void encode_query_kernel(const float *__restrict__ query,
@@ -1244,6 +1506,54 @@ float host_multiplier(float alpha, int distance, int invert) {  // :119-128
 }
 
 uint64_t actual_dim_of(uint64_t dim) { return dim + (16 - dim % 16) % 16; }  // :257-259
+
+// ---- rotated stores: the launchers of the u8_rot_* kernels ----
+uint32_t rot_block_of(uint64_t dim) { return (uint32_t)(dim & (~dim + 1)); }  // B: the largest power of two dividing dim
+// c = 2^(-log2(B) / 2) as an f32: a power of two for even log2(B), the f32 nearest to 2^-1/2 scaled by one for odd
+float rot_scale_of(uint32_t B) {
+    const int lg = __builtin_ctz(B);
+    return std::ldexp((lg & 1) ? 0.70710678118654752440f : 1.0f, -(lg / 2));
+}
+// A wave per row up to kRotWaveMax dimensions (K = ceil(dim / 256) chunks per lane), a workgroup per row above.
+// KERNEL / LDS_KERNEL: the two forms of one consumer; the arguments after `vec` follow.
+#define QAMD_ROT_LAUNCH(KERNEL, LDS_KERNEL, src, n, dim, s, ...)                                                          \
+    do {                                                                                                                  \
+        const uint32_t _B = rot_block_of(dim);                                                                            \
+        const float _c = rot_scale_of(_B);                                                                                \
+        const int _vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0;                                                    \
+        if ((dim) <= kRotWaveMax) {                                                                                       \
+            const dim3 _grid(grid_for((n), kBlock / 64, 8));                                                              \
+            switch (((dim) + 255) / 256) {                                                                                \
+            case 1: hipLaunchKernelGGL((KERNEL<1>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
+            case 2: hipLaunchKernelGGL((KERNEL<2>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
+            case 3: hipLaunchKernelGGL((KERNEL<3>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
+            case 4: hipLaunchKernelGGL((KERNEL<4>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
+            case 5: hipLaunchKernelGGL((KERNEL<5>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
+            case 6: hipLaunchKernelGGL((KERNEL<6>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
+            case 7: hipLaunchKernelGGL((KERNEL<7>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
+            default: hipLaunchKernelGGL((KERNEL<8>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
+            }                                                                                                             \
+        } else {                                                                                                          \
+            hipLaunchKernelGGL(LDS_KERNEL, dim3(grid_for((n), 1, (int)(160 * 1024 / ((dim) * 4)))), dim3(kBlock),         \
+                               (dim) * 4, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__);                         \
+        }                                                                                                                 \
+    } while (0)
+
+// Every caller has checked dim (rot_dim_ok) and holds `src` in device memory.
+qamd_status launch_rot_minmax(const float *src, uint64_t n, uint64_t dim, uint32_t *slots, uint64_t base_values,
+                              unsigned long long *first_zero, hipStream_t s) {
+    if (n == 0) return QAMD_OK;
+    QAMD_ROT_LAUNCH(u8_rot_minmax_kernel, u8_rot_minmax_lds_kernel, src, n, dim, s, slots, base_values, first_zero);
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
+qamd_status launch_rot_values(const float *src, uint64_t n, uint64_t dim, float *out, hipStream_t s) {
+    if (n == 0) return QAMD_OK;
+    QAMD_ROT_LAUNCH(u8_rot_values_kernel, u8_rot_values_lds_kernel, src, n, dim, s, out);
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
+bool rot_dim_ok(uint64_t dim) { return dim != 0 && dim % kRotBlockMin == 0 && dim <= kRotMaxDim; }
 
 }  // namespace
 
@@ -1749,8 +2059,10 @@ bool quantile_cut(uint64_t slice, uint64_t dim, float quantile, uint64_t &cut);
 // and the (cut+1)-th largest value — two exact radix selects on the GPU.
 // count <= 100 000: the sample is every vector (exactly the reference).  Larger stores: an
 // evenly strided subset (the reference draws a random one; statistic, not bits).
+// `rotated`: the interval is that of the sampled rows' rotation, written to a buffer of their size.
 qamd_status quantile_interval_device(const float *data, qamd_mem data_mem, uint64_t count, uint64_t dim,
-                                     float quantile, hipStream_t s, bool &found, float &mn, float &mx) {
+                                     float quantile, hipStream_t s, bool &found, float &mn, float &mx,
+                                     bool rotated = false) {
     found = false;
     const uint64_t slice = std::min<uint64_t>(count, kQuantileSample);
     const uint64_t len = slice * dim;
@@ -1775,6 +2087,12 @@ qamd_status quantile_interval_device(const float *data, qamd_mem data_mem, uint6
                            count, (uint32_t)dim, slice, sample.as<float>());
         QAMD_HIP(hipGetLastError());
         vals = sample.as<float>();
+    }
+    DevBuf rot;
+    if (rotated) {
+        QAMD_TRY(rot.alloc(len * 4));
+        QAMD_TRY(launch_rot_values(vals, slice, dim, rot.as<float>(), s));
+        vals = rot.as<float>();
     }
     QAMD_TRY(select_kth_f32(vals, len, cut + 2, false, &mn, s));
     QAMD_TRY(select_kth_f32(vals, len, cut + 1, true, &mx, s));
@@ -1839,6 +2157,13 @@ struct MinMaxAcc {
         return QAMD_OK;
     }
 
+    // feed() for `nr` rows of a rotated store: the extremes of the rotated values, which are never written
+    qamd_status feed_rotated(const float *src, uint64_t nr, uint64_t dim, hipStream_t s) {
+        QAMD_TRY(launch_rot_minmax(src, nr, dim, slots.as<uint32_t>(), fed, first_zero(), s));
+        fed += nr * dim;
+        return QAMD_OK;
+    }
+
     qamd_status result(hipStream_t s, float &out_mn, float &out_mx) {
         std::vector<uint32_t> all_slots(kZeroWordAt + 2);
         QAMD_TRY(copy_out(all_slots.data(), QAMD_MEM_HOST, slots.ptr, all_slots.size() * 4, s));
@@ -1879,12 +2204,18 @@ qamd_status launch_quantize(qamd_u8 *h, const float *src, uint64_t nr, uint64_t 
     if (nr == 0) return QAMD_OK;
     const qamd_vector_parameters &vp = h->meta.vector_parameters;
     const uint64_t dim = vp.dim;
+    // the division-free conversion needs a normal alpha well inside the exponent range (f32_to_u8_fast)
+    const bool fast = alpha >= 8.673617379884035e-19f && alpha <= 1.152921504606847e+18f;  // 2^-60 .. 2^60
+    if (h->rotated) {  // rotated in registers, no copy of the rotated values
+        QAMD_ROT_LAUNCH(u8_rot_quantize_kernel, u8_rot_quantize_lds_kernel, src, nr, dim, s, alpha, offset, (int)fast,
+                        vp.distance_type, vp.invert, h->codes.as<uint32_t>(), h->offsets.as<float>(), r0);
+        QAMD_HIP(hipGetLastError());
+        return QAMD_OK;
+    }
     if (dim % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
         const uint64_t waves = (nr + 3) / 4;
         const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
         const uint32_t per_lane = (uint32_t)((h->meta.actual_dim / 4 + 15) / 16);  // float4 per lane
-        // the division-free conversion needs a normal alpha well inside the exponent range (f32_to_u8_fast)
-        const bool fast = alpha >= 8.673617379884035e-19f && alpha <= 1.152921504606847e+18f;  // 2^-60 .. 2^60
 #define QAMD_Q16(IT)                                                                                          \
     do {                                                                                                      \
         if (fast)                                                                                             \
@@ -1925,6 +2256,21 @@ bool quantile_cut(uint64_t slice, uint64_t dim, float quantile, uint64_t &cut) {
     return !(hi <= lo || hi - lo < 2);  // :63-65
 }
 
+// The distance_type a u8 constructor is handed: a qamd_distance, or QAMD_DOT / QAMD_L2 with QAMD_ROTATED or-ed on (DESIGN
+// 3.1x).  The handle keeps `base` in its metadata and the flag beside it.  No device call.
+qamd_status split_distance(const qamd_vector_parameters &vp, int &base, bool &rotated) {
+    const int dt = vp.distance_type;
+    rotated = dt >= 0 && (dt & QAMD_ROTATED) != 0;
+    base = rotated ? (dt & ~QAMD_ROTATED) : dt;
+    if (base < 0 || base > 2) return fail(QAMD_ERR_ARGUMENTS, "bad distance_type %d", dt);
+    if (rotated && base == QAMD_L1)
+        return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: L1 is not invariant under the rotation of a rotated store", dt);
+    if (rotated && !rot_dim_ok(vp.dim))
+        return fail(QAMD_ERR_ARGUMENTS, "rotated rows have a multiple of %llu dimensions, at most %llu, not %llu",
+                    (unsigned long long)kRotBlockMin, (unsigned long long)kRotMaxDim, (unsigned long long)vp.dim);
+    return QAMD_OK;
+}
+
 }  // namespace
 
 // ================================================================================== C ABI
@@ -1940,8 +2286,9 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
                            const float *quantile, const float *alpha_offset, qamd_stop_fn stop,
                            void *stop_user, void *stream, qamd_u8 **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    if (vp->distance_type < 0 || vp->distance_type > 2)
-        return fail(QAMD_ERR_ARGUMENTS, "bad distance_type %d", vp->distance_type);
+    int base_distance = 0;
+    bool rotated = false;
+    QAMD_TRY(split_distance(*vp, base_distance, rotated));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
     QAMD_ON_DEVICE(current_device());
@@ -1951,13 +2298,15 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
     h->count = vp->count;
     h->meta.actual_dim = actual_dim_of(vp->dim);
     h->meta.vector_parameters = *vp;
+    h->meta.vector_parameters.distance_type = base_distance;
+    h->rotated = rotated;
     QAMD_TRY(alloc_store(h.get()));
     if (vp->count == 0) {  // encoded_vectors_u8.rs:43-54
         h->meta.alpha = h->meta.offset = h->meta.multiplier = 0.0f;
         if (alpha_offset) {  // an empty SHARD of a store whose interval was found elsewhere keeps that store's metadata
             h->meta.alpha = alpha_offset[0];
             h->meta.offset = alpha_offset[1];
-            h->meta.multiplier = host_multiplier(alpha_offset[0], vp->distance_type, vp->invert);
+            h->meta.multiplier = host_multiplier(alpha_offset[0], base_distance, vp->invert);
         }
         *out = h.release();
         return QAMD_OK;
@@ -2013,7 +2362,8 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
             const uint64_t nr = std::min(batch_rows, count - r0);
             const float *src = nullptr;
             QAMD_TRY(batch_src(r0, nr, src));
-            QAMD_TRY(acc.feed(src, nr * dim, s));
+            if (rotated) QAMD_TRY(acc.feed_rotated(src, nr, dim, s));
+            else QAMD_TRY(acc.feed(src, nr * dim, s));
             if (data_mem == QAMD_MEM_HOST) QAMD_HIP(hipStreamSynchronize(s));  // staging buffer is reused
         }
         float mn, mx;
@@ -2024,7 +2374,7 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
         if (quantile && !(count < 127 || *quantile >= 1.0f)) {  // :27-29
             bool found = false;
             float qmn = 0.0f, qmx = 0.0f;
-            QAMD_TRY(quantile_interval_device(data, data_mem, count, dim, *quantile, s, found, qmn, qmx));
+            QAMD_TRY(quantile_interval_device(data, data_mem, count, dim, *quantile, s, found, qmn, qmx, rotated));
             if (found) {
                 alpha = (qmx - qmn) / 127.0f;
                 offset = qmn;
@@ -2044,7 +2394,7 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
     QAMD_HIP(hipStreamSynchronize(s));
     h->meta.alpha = alpha;
     h->meta.offset = offset;
-    h->meta.multiplier = host_multiplier(alpha, vp->distance_type, vp->invert);
+    h->meta.multiplier = host_multiplier(alpha, base_distance, vp->invert);
     QAMD_TRY(build_packed(h.get(), s));
     *out = h.release();
     return QAMD_OK;
@@ -2054,6 +2404,9 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
                               void *stream, qamd_u8 **out) {
     if (!meta || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     const qamd_vector_parameters &vp = meta->vector_parameters;
+    int base_distance = vp.distance_type;
+    bool rotated = false;  // the flag get_metadata reported travels back in here
+    if (vp.distance_type >= 0 && (vp.distance_type & QAMD_ROTATED)) QAMD_TRY(split_distance(vp, base_distance, rotated));
     if (meta->actual_dim != actual_dim_of(vp.dim))
         return fail(QAMD_ERR_ARGUMENTS, "metadata actual_dim %llu does not match dim %llu",
                     (unsigned long long)meta->actual_dim, (unsigned long long)vp.dim);
@@ -2065,6 +2418,8 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
     h->device = current_device();
     h->count = vp.count;
     h->meta = *meta;
+    h->meta.vector_parameters.distance_type = base_distance;
+    h->rotated = rotated;
     QAMD_TRY(alloc_store(h.get()));
     const uint64_t stride = meta->actual_dim + 4;
     const uint32_t row_dwords = (uint32_t)(stride / 4);
@@ -2130,6 +2485,7 @@ qamd_status qamd_u8_export_rows(const qamd_u8 *h, uint8_t *rows, qamd_mem rows_m
 qamd_status qamd_u8_get_metadata(const qamd_u8 *h, qamd_u8_metadata *out) {
     if (!h || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     *out = h->meta;
+    if (h->rotated) out->vector_parameters.distance_type |= QAMD_ROTATED;
     return QAMD_OK;
 }
 
@@ -2139,7 +2495,8 @@ qamd_status qamd_u8_save(const qamd_u8 *h, const char *data_path, const char *me
     std::string js = "{\"actual_dim\":" + std::to_string(h->meta.actual_dim) +
                      ",\"alpha\":" + json_f32(h->meta.alpha) + ",\"offset\":" + json_f32(h->meta.offset) +
                      ",\"multiplier\":" + json_f32(h->meta.multiplier) +
-                     ",\"vector_parameters\":" + vector_parameters_json(h->meta.vector_parameters) + "}";
+                     ",\"vector_parameters\":" + vector_parameters_json(h->meta.vector_parameters) +
+                     (h->rotated ? ",\"rotation\":\"HadamardBlocks\"" : "") + "}";  // the base metric above; 3.1x
     QAMD_TRY(save_file(meta_path, js.data(), js.size()));
     const uint64_t stride = h->meta.actual_dim + 4;
     std::vector<uint8_t> rows(h->count * stride);
@@ -2163,6 +2520,17 @@ qamd_status qamd_u8_load(const char *data_path, const char *meta_path, const qam
             !(vpj = json_field(root, "vector_parameters", err)) || !parse_vector_parameters(*vpj, meta.vector_parameters, err))
             return fail(QAMD_ERR_IO, "%s: %s", meta_path, err.c_str());
     }
+    // "rotation" (DESIGN 3.1x): absent = a plain store; the one value a rotated store writes; anything else is not ours
+    bool rotated = false;
+    for (const auto &m : root.members) {
+        if (m.first != "rotation") continue;
+        if (rotated || m.second.kind != JsonValue::String || m.second.text != "HadamardBlocks")
+            return fail(QAMD_ERR_IO, "%s: unknown or repeated rotation", meta_path);
+        rotated = true;
+    }
+    if (rotated && (meta.vector_parameters.distance_type == QAMD_L1 || !rot_dim_ok(vp->dim)))
+        return fail(QAMD_ERR_IO, "%s: a rotated store of metric %s and %llu dimensions", meta_path,
+                    distance_name(meta.vector_parameters.distance_type), (unsigned long long)vp->dim);
     const uint64_t size = qamd_u8_quantized_vector_size(vp);
     std::string bytes;
     QAMD_TRY(load_rows_file(data_path, size * vp->count, bytes));
@@ -2171,8 +2539,10 @@ qamd_status qamd_u8_load(const char *data_path, const char *meta_path, const qam
     eff.vector_parameters.dim = vp->dim;
     eff.vector_parameters.count = vp->count;
     eff.actual_dim = actual_dim_of(vp->dim);
+    if (rotated) eff.vector_parameters.distance_type |= QAMD_ROTATED;  // from_rows takes it off again
     qamd_status st = qamd_u8_from_rows(reinterpret_cast<const uint8_t *>(bytes.data()), QAMD_MEM_HOST, &eff,
                                        nullptr, out);
+    eff.vector_parameters.distance_type = meta.vector_parameters.distance_type;
     if (st == QAMD_OK) (*out)->meta = meta.actual_dim == eff.actual_dim ? meta : eff;
     return st;
 }
@@ -2203,6 +2573,11 @@ qamd_status encode_now(const qamd_u8_query *q, const float *query, uint64_t qdim
             q_dev = stage;
         }
     }
+    if (q->rotated) {  // the rotated values go behind the staging area, and the encoder reads those
+        float *rot = reinterpret_cast<float *>(q->buf.as<uint8_t>() + 16 + round_up(ad, 16) + ad * 4);
+        QAMD_TRY(launch_rot_values(q_dev, 1, qdim, rot, s));
+        q_dev = rot;
+    }
     hipLaunchKernelGGL(encode_query_kernel, dim3(1), dim3(64), 0, s, q_dev, (uint32_t)qdim, (uint32_t)ad, q->alpha,
                        q->offset, q->distance, q->invert, q->buf.as<uint8_t>());
     QAMD_HIP(hipGetLastError());
@@ -2227,6 +2602,9 @@ extern "C" {
 qamd_status qamd_u8_encode_query(const qamd_u8 *h, const float *query, uint64_t qdim, qamd_mem query_mem,
                                  void *stream, qamd_u8_query **query_io) {
     if (!h || !query_io || (!query && qdim)) return fail(QAMD_ERR_ARGUMENTS, "null argument");
+    if (h->rotated && qdim != h->meta.vector_parameters.dim)
+        return fail(QAMD_ERR_ARGUMENTS, "a query of %llu dimensions against rotated rows of %llu", (unsigned long long)qdim,
+                    (unsigned long long)h->meta.vector_parameters.dim);
     const uint64_t ad = actual_dim_of(qdim);
     QAMD_ON_DEVICE(h->device);
     hipStream_t s = as_stream(stream);
@@ -2237,17 +2615,20 @@ qamd_status qamd_u8_encode_query(const qamd_u8 *h, const float *query, uint64_t 
         q = fresh.get();
         q->device = h->device;
     }
-    if (q->actual_dim != ad || !q->buf.ptr) {
+    // offset | codes | f32 staging | the rotated values of a rotated store's query
+    const size_t buf_bytes = 16 + round_up(ad, 16) + ad * 4 + 16 + (h->rotated ? ad * 4 : 0);
+    if (q->actual_dim != ad || !q->buf.ptr || q->buf.bytes < buf_bytes) {
         if (q->pooled) query_buf_put(q->buf, false);
-        QAMD_TRY(query_buf_get(16 + round_up(ad, 16) + ad * 4 + 16, q->buf));  // offset | codes | f32 staging
+        QAMD_TRY(query_buf_get(buf_bytes, q->buf));
         q->pooled = true;
         q->actual_dim = ad;
     }
+    q->rotated = h->rotated;
     q->alpha = h->meta.alpha;
     q->offset = h->meta.offset;
     q->distance = h->meta.vector_parameters.distance_type;
     q->invert = h->meta.vector_parameters.invert;
-    if (query_mem == QAMD_MEM_HOST && u8_host_encode_is_lazy(qdim)) {
+    if (query_mem == QAMD_MEM_HOST && u8_host_encode_is_lazy(qdim) && !h->rotated) {  // (the fused top-k does not rotate)
         // Deferred: the values are kept, nothing is launched.  On a small store the top-k kernel takes them
         // by value and quantises them itself (u8_topk_small_fused_kernel); any other consumer encodes first.
         std::lock_guard<std::mutex> lk(q->encode_mu);
@@ -2480,6 +2861,13 @@ qamd_status encoder_close_pass1(qamd_u8_encoder *e) {
         if (quantile_cut(e->slice, dim, e->quantile, cut)) {
             float qmn = 0.0f, qmx = 0.0f;
             const uint64_t len = e->slice * dim;
+            if (e->h->rotated) {  // the sample holds the rows as they came: the interval is that of their rotation
+                DevBuf rot;
+                QAMD_TRY(rot.alloc(len * 4));
+                QAMD_TRY(launch_rot_values(e->sample.as<float>(), e->slice, dim, rot.as<float>(), e->stream));
+                QAMD_HIP(hipStreamSynchronize(e->stream));
+                e->sample = std::move(rot);
+            }
             QAMD_TRY(select_kth_f32(e->sample.as<float>(), len, cut + 2, false, &qmn, e->stream));
             QAMD_TRY(select_kth_f32(e->sample.as<float>(), len, cut + 1, true, &qmx, e->stream));
             e->alpha = (qmx - qmn) / 127.0f;
@@ -2498,21 +2886,24 @@ extern "C" {
 qamd_status qamd_u8_encoder_begin(const qamd_vector_parameters *vp, const float *quantile, const float *alpha_offset,
                                   qamd_stop_fn stop, void *stop_user, void *stream, qamd_u8_encoder **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    if (vp->distance_type < 0 || vp->distance_type > 2)
-        return fail(QAMD_ERR_ARGUMENTS, "bad distance_type %d", vp->distance_type);
+    int base_distance = 0;
+    bool rotated = false;
+    QAMD_TRY(split_distance(*vp, base_distance, rotated));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     QAMD_ON_DEVICE(current_device());
     std::unique_ptr<qamd_u8_encoder> e(new qamd_u8_encoder);
     e->device = current_device();
     e->stream = as_stream(stream);
     e->vp = *vp;
+    e->vp.distance_type = base_distance;  // the flag lives in h->rotated
     e->stop = stop;
     e->stop_user = stop_user;
     e->h.reset(new qamd_u8);
     e->h->device = e->device;
     e->h->count = vp->count;
     e->h->meta.actual_dim = actual_dim_of(vp->dim);
-    e->h->meta.vector_parameters = *vp;
+    e->h->meta.vector_parameters = e->vp;
+    e->h->rotated = rotated;
     QAMD_TRY(alloc_store(e->h.get()));
     if (alpha_offset) {
         e->alpha = alpha_offset[0];
@@ -2550,7 +2941,8 @@ qamd_status qamd_u8_encoder_observe(qamd_u8_encoder *e, const float *batch, uint
     const uint64_t piece_rows = std::max<uint64_t>(1, stage_bytes(kStagePieceBytes) / (dim * 4));
     QAMD_TRY(for_each_staged_piece(batch, batch_mem, n_rows, dim, piece_rows, e->stage, e->stream,
                                    [&](const float *src, uint64_t r, uint64_t nr) -> qamd_status {
-        QAMD_TRY(e->acc.feed(src, nr * dim, e->stream));
+        if (e->h->rotated) QAMD_TRY(e->acc.feed_rotated(src, nr, dim, e->stream));
+        else QAMD_TRY(e->acc.feed(src, nr * dim, e->stream));
         if (e->slice) {
             const uint64_t base = e->observed + r;
             const uint64_t k0 = first_sample_at_or_after(base, count, e->slice);
@@ -2748,6 +3140,15 @@ qamd_status u8_encode_queries_device(const qamd_u8 *h, const float *queries_dev,
                                      uint8_t *codes_dev, uint64_t code_pitch, float *offsets_dev, hipStream_t stream) {
     if (n_queries == 0) return QAMD_OK;
     const qamd_vector_parameters &vp = h->meta.vector_parameters;
+    StreamBuf rot;  // a rotated store: the codes come from the rotated queries, held until the encoder has run
+    if (h->rotated) {
+        if (qdim != vp.dim)
+            return fail(QAMD_ERR_ARGUMENTS, "queries of %llu dimensions against rotated rows of %llu", (unsigned long long)qdim,
+                        (unsigned long long)vp.dim);
+        QAMD_TRY(rot.alloc(n_queries * qdim * sizeof(float), stream));
+        QAMD_TRY(launch_rot_values(queries_dev, n_queries, qdim, rot.as<float>(), stream));
+        queries_dev = rot.as<float>();
+    }
     hipLaunchKernelGGL(encode_queries_kernel, dim3((unsigned)n_queries), dim3(64), 0, stream, queries_dev,
                        (uint32_t)qdim, (uint32_t)actual_dim_of(qdim), h->meta.alpha, h->meta.offset,
                        vp.distance_type, vp.invert, codes_dev, (uint32_t)code_pitch, offsets_dev);

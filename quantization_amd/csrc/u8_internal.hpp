@@ -15,6 +15,10 @@ struct qamd_u8 {
     uint64_t padded_rows = 0;  // round_up(capacity, 1024) + 1024; rows from count on are zero: tiles never need a load guard
     uint32_t row_chunks = 0;   // actual_dim / 16
     int lane_mode = 0;         // 0: integer sum rounded once; 1: avx2.c lane order
+    // A rotated store: the rows are codes of the block rotation of what the caller handed in, and so are
+    // the queries.  meta.vector_parameters.distance_type keeps the BASE metric (QAMD_DOT or QAMD_L2), so no kernel, route
+    // or multiplier knows; QAMD_ROTATED is added back where metadata leaves the library (get_metadata).
+    bool rotated = false;
     qamd::DevBuf codes;        // [padded_rows][actual_dim]
     qamd::DevBuf offsets;      // [padded_rows] f32
     // Packed scan image (u8.hip build_packed): the codes at 7 bits each, packed_chunks 16-byte chunks per row.  Chunk
@@ -48,6 +52,7 @@ struct qamd_u8_query {
     mutable std::vector<float> host_f32;
     float alpha = 0.0f, offset = 0.0f;  // of the store the query was (or will be) encoded for
     int distance = 0, invert = 0;
+    bool rotated = false;  // of a rotated store: the values are rotated before they are encoded
     mutable std::atomic<bool> deferred{false};
     mutable std::mutex encode_mu;  // two threads may consume one deferred query
     bool pooled = false;     // buf came from / goes back to the query buffer cache

@@ -24,6 +24,10 @@ class DistanceType(enum.IntEnum):
     L2 = 2
 
 
+ROTATED = 8  # QAMD_ROTATED: the flag on qamd_vector_parameters.distance_type of a rotated scalar-u8 store
+ROTATION_NAME = "HadamardBlocks"  # what a rotated store's metadata says under "rotation"
+
+
 @dataclass
 class VectorParameters:
     """encoded_vectors.rs:13-19."""
@@ -33,13 +37,15 @@ class VectorParameters:
     distance_type: DistanceType
     invert: bool
 
-    def to_c(self) -> _lib.VectorParametersC:
-        return _lib.VectorParametersC(int(self.dim), int(self.count), int(self.distance_type),
-                                      int(bool(self.invert)))
+    def to_c(self, rotated: bool = False) -> _lib.VectorParametersC:
+        """`rotated`: QAMD_ROTATED or-ed onto the metric - a rotated scalar-u8 store.  The flag lives in
+        the C struct alone: `distance_type` here stays a DistanceType."""
+        return _lib.VectorParametersC(int(self.dim), int(self.count),
+                                      int(self.distance_type) | (ROTATED if rotated else 0), int(bool(self.invert)))
 
     @staticmethod
     def from_c(c: _lib.VectorParametersC) -> "VectorParameters":
-        return VectorParameters(int(c.dim), int(c.count), DistanceType(c.distance_type), bool(c.invert))
+        return VectorParameters(int(c.dim), int(c.count), DistanceType(c.distance_type & ~ROTATED), bool(c.invert))
 
 
 class EncodingError(Exception):

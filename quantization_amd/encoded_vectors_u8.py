@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._base import EncodedQueryBase, EncodedQueryBatch, EncodedVectorsBase
-from .encoded_vectors import (DistanceType, EncodingError, VectorParameters, check, check_same_device,
+from .encoded_vectors import (ROTATED, ROTATION_NAME, DistanceType, EncodingError, VectorParameters, check, check_same_device,
                               creating_on, flatten_rows, get_device, in_buf, make_stop, out_buf, stream_ptr,
                               validate)
 
@@ -55,13 +55,15 @@ class EncodedVectorsU8(EncodedVectorsBase):
     @classmethod
     def encode(cls, orig_data, vector_parameters: VectorParameters, quantile: float | None = None,
                stop_condition=None, *, alpha_offset: tuple[float, float] | None = None,
-               stream=None) -> "EncodedVectorsU8":
+               stream=None, rotated: bool = False) -> "EncodedVectorsU8":
         """EncodedVectorsU8::encode (:34-140).  `orig_data`: [count, dim] f32 array (host) or
         CUDA tensor (HBM), or an iterable of rows.  The storage builder of the reference is
-        implicit: the encoded rows live in library-owned HBM (see `storage_bytes`)."""
+        implicit: the encoded rows live in library-owned HBM (see `storage_bytes`).
+        `rotated` (no counterpart in the reference): rows and queries go through a fixed randomized
+        Hadamard block rotation before the quantizer - Dot or L2, dim a multiple of 64 up to 16384."""
         data = flatten_rows(orig_data, vector_parameters.dim)
         validate(data, vector_parameters)
-        vp = vector_parameters.to_c()
+        vp = vector_parameters.to_c(rotated)
         buf = in_buf(data, np.float32)
         q = C.c_float(quantile) if quantile is not None else None
         ao = (C.c_float * 2)(*alpha_offset) if alpha_offset is not None else None
@@ -99,13 +101,13 @@ class EncodedVectorsU8(EncodedVectorsBase):
     @classmethod
     def encode_stream(cls, make_batches, vector_parameters: VectorParameters, quantile: float | None = None,
                       stop_condition=None, *, alpha_offset: tuple[float, float] | None = None,
-                      stream=None) -> "EncodedVectorsU8":
+                      stream=None, rotated: bool = False) -> "EncodedVectorsU8":
         """The reference's own contract: `encode` takes a CLONABLE ITERATOR and walks it twice
         (:34-40, pass 1 :57-71, pass 2 :73-118).  `make_batches()` returns a fresh iterator over
         [n_i, dim] f32 batches (numpy or CUDA tensors) each time it is called; the f32 data is never
-        held as a whole.  Byte-identical to `encode` on the concatenated batches."""
+        held as a whole.  Byte-identical to `encode` on the concatenated batches, `rotated` included."""
         L = _lib.lib()
-        vp = vector_parameters.to_c()
+        vp = vector_parameters.to_c(rotated)
         q = C.c_float(quantile) if quantile is not None else None
         ao = (C.c_float * 2)(*alpha_offset) if alpha_offset is not None else None
         stop = make_stop(stop_condition)
@@ -135,14 +137,18 @@ class EncodedVectorsU8(EncodedVectorsBase):
     @classmethod
     def from_storage(cls, rows, metadata: dict, stream=None) -> "EncodedVectorsU8":
         """Adopt reference-format rows ([vector_offset f32][codes], stride actual_dim+4) plus
-        their Metadata (:24-31) — e.g. a store encoded by the reference crate."""
+        their Metadata (:24-31) — e.g. a store encoded by the reference crate.  A "rotation" entry (what a rotated
+        store's `metadata` carries) makes the new store a rotated one: its queries are rotated before they are encoded."""
+        rotation = metadata.get("rotation")
+        if rotation not in (None, ROTATION_NAME):
+            raise EncodingError(_lib.ERR_ARGUMENTS, f"unknown rotation {rotation!r}")
         vp = metadata["vector_parameters"]
         if isinstance(vp, dict):
             dt = vp["distance_type"]
             vp = VectorParameters(vp["dim"], vp["count"],
                                   DistanceType[dt] if isinstance(dt, str) else DistanceType(dt), vp["invert"])
         meta = _lib.U8MetadataC(int(metadata["actual_dim"]), float(metadata["alpha"]),
-                                float(metadata["offset"]), float(metadata["multiplier"]), vp.to_c())
+                                float(metadata["offset"]), float(metadata["multiplier"]), vp.to_c(rotation is not None))
         buf = in_buf(rows, np.uint8)
         out = C.c_void_p()
         with creating_on(rows) as dev:
@@ -166,9 +172,17 @@ class EncodedVectorsU8(EncodedVectorsBase):
     def metadata(self) -> dict:
         m = _lib.U8MetadataC()
         check(_lib.lib().qamd_u8_get_metadata(self._h, C.byref(m)))
-        return {"actual_dim": int(m.actual_dim), "alpha": np.float32(m.alpha), "offset": np.float32(m.offset),
-                "multiplier": np.float32(m.multiplier),
-                "vector_parameters": VectorParameters.from_c(m.vector_parameters)}
+        md = {"actual_dim": int(m.actual_dim), "alpha": np.float32(m.alpha), "offset": np.float32(m.offset),
+              "multiplier": np.float32(m.multiplier),
+              "vector_parameters": VectorParameters.from_c(m.vector_parameters)}
+        if m.vector_parameters.distance_type & ROTATED:  # a plain store's metadata has no such entry, as its file has none
+            md["rotation"] = ROTATION_NAME
+        return md
+
+    @property
+    def rotated(self) -> bool:
+        """Whether rows and queries are rotated before the quantizer."""
+        return "rotation" in self.metadata
 
     @property
     def vector_parameters(self) -> VectorParameters:

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .encoded_vectors import (VectorParameters, check, device_of, flatten_rows, in_buf, make_stop, out_buf,
+from .encoded_vectors import (EncodingError, VectorParameters, check, device_of, flatten_rows, in_buf, make_stop, out_buf,
                               stream_ptr, validate)
 from .encoded_vectors_binary import BitsStoreType, EncodedVectorsBin
 from .encoded_vectors_pq import CENTROIDS_COUNT, EncodedVectorsPQ
@@ -169,7 +169,9 @@ class ShardedVectorsU8(_ShardedBase):
 
     @classmethod
     def encode(cls, orig_data, vector_parameters: VectorParameters, devices, quantile: float | None = None,
-               stop_condition=None, *, alpha_offset=None, stream=None) -> "ShardedVectorsU8":
+               stop_condition=None, *, alpha_offset=None, stream=None, rotated: bool = False) -> "ShardedVectorsU8":
+        if rotated:  # (the C constructor refuses the flag too)
+            raise EncodingError(_lib.ERR_ARGUMENTS, "only a single-GPU EncodedVectorsU8 can be rotated")
         data = flatten_rows(orig_data, vector_parameters.dim)
         validate(data, vector_parameters)
         vp = vector_parameters.to_c()

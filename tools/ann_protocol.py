@@ -15,7 +15,7 @@ CANDIDATES rows and the f32 data, held as a borrowed `OriginalVectors`, re-ranks
 timings are reported beside the unrescored ones ("gpu_rescored").
 
     python tools/ann_protocol.py [--rows 1000000] [--dims 128,768] [--queries 200] [--cpu-queries 3] [--rescore 100 [--orig-dtype f16]]
-                                 [--out FILE.jsonl]
+                                 [--u8-rotated] [--out FILE.jsonl]
 """
 import sys as _sys
 if "--help" in _sys.argv[1:] or "-h" in _sys.argv[1:]:  # every tool answers --help without touching the GPU (tests/test_tools.py)
@@ -184,6 +184,9 @@ def main():
                          "of DESIGN 3.2h (dims that are a multiple of 64; a row keeps dim bits).  "
                          "Two-bit and rotated records have no CPU loop (the oracle restates the reference); with --bin-query-bits "
                          "4,8 they carry weighted scalar-query entries")
+    ap.add_argument("--u8-rotated", action="store_true",
+                    help="u8: a record per variant for the rotated store of DESIGN 3.1x too (dims that are a multiple of 64), "
+                         "beside the plain one; rotated records have no CPU loop (the oracle restates the reference)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     query_bits = [int(x) for x in args.bin_query_bits.split(",")]
@@ -220,6 +223,10 @@ def main():
                 if kind == "u8":
                     variants.append(("u8", qa.EncodedVectorsU8.encode(data, vp), {}))
                     variants.append(("u8 quantile 0.99", qa.EncodedVectorsU8.encode(data, vp, 0.99), {}))
+                    if args.u8_rotated:
+                        variants.append(("u8 rotated", qa.EncodedVectorsU8.encode(data, vp, rotated=True), {"rotated": True}))
+                        variants.append(("u8 rotated, quantile 0.99", qa.EncodedVectorsU8.encode(data, vp, 0.99, rotated=True),
+                                         {"rotated": True}))
                 elif kind == "pq":
                     extra = {"chunk": args.pq_chunk}
                     enc = qa.EncodedVectorsPQ.encode(data, vp, args.pq_chunk, max_kmeans_threads=8)
