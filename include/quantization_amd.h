@@ -63,6 +63,8 @@ typedef enum {
 typedef enum { QAMD_DOT = 0, QAMD_L1 = 1, QAMD_L2 = 2 } qamd_distance;
 enum { QAMD_ROTATED = 8,   /* flag: or-ed onto QAMD_DOT or QAMD_L2 in qamd_vector_parameters.distance_type */
        QAMD_DOT_ROTATED = 8, QAMD_L2_ROTATED = 10 };
+enum { QAMD_BITS4 = 32,    /* flag: or-ed onto QAMD_DOT or QAMD_L2, plain or rotated, in distance_type (16 is no flag) */
+       QAMD_DOT_BITS4 = 32, QAMD_L2_BITS4 = 34, QAMD_DOT_ROTATED_BITS4 = 40, QAMD_L2_ROTATED_BITS4 = 42 };
 /* A ROTATED scalar-u8 store (no counterpart in the reference).  qamd_u8_encode, qamd_u8_encoder_begin and
  * qamd_u8_from_rows take QAMD_DOT_ROTATED or QAMD_L2_ROTATED as distance_type: every row - and every query, inside
  * qamd_u8_encode_query / qamd_u8_encode_query_batch - goes through a fixed randomized Hadamard block rotation (blocks of
@@ -75,6 +77,21 @@ enum { QAMD_ROTATED = 8,   /* flag: or-ed onto QAMD_DOT or QAMD_L2 in qamd_vecto
  * qamd_u8_upsert rotates what it is handed; qamd_u8_topk_rescored compares the BASE metric with the originals', which
  * stay plain.  qamd_u8_find_min_max / qamd_u8_find_quantile_interval see no parameters and stay plain.  The feature adds
  * no symbol: this header still declares 192 entry points. */
+/* A 4-BIT scalar-u8 store (no counterpart in the reference).  The same three constructors take the metric
+ * with QAMD_BITS4 or-ed on, with or without QAMD_ROTATED.  Rows keep the reference's format - [offset f32][actual_dim
+ * code bytes] - but a code is one of 16 levels: alpha = (max - min) / 15 and code(v) = trunc(clamp((v - offset) / alpha
+ * + 0.5, 0, 15)), rounded to nearest where the 7-bit code truncates; queries are encoded with the same code().  Offsets,
+ * multiplier and every score formula are the reference's with this alpha.  A 15-level code over one interval only
+ * ranks well when every coordinate has about the same spread: use it with QAMD_ROTATED unless the data is isotropic
+ * already, and with the originals behind it (qamd_u8_topk_rescored).  QAMD_L1 | QAMD_BITS4 and any other bit beyond 8
+ * and 32 are refused, and so is the flag on every qamd_pq_*, qamd_bin_*, qamd_f32_* and qamd_*_sharded_* constructor
+ * (QAMD_ERR_ARGUMENTS, before any device call).  qamd_u8_get_metadata reports the flagged value; qamd_u8_save writes
+ * the base metric plus a last key "bits":4 (after "rotation"), and a file without the key is a 7-bit store.
+ * qamd_u8_upsert quantizes what it is handed with the handle's form.  A store of 32 to 2048 dims keeps, instead of the
+ * 7-bit scan image below, a nibble image: two codes per byte, 16 * ceil(actual_dim / 32) bytes per row in blocks of 64
+ * rows, which the single-query scans read (388 bytes per row at dim 768, qamd_u8_scan_bytes_per_row, against 676).
+ * Byte codes plus image are 1156 bytes per row at dim 768, against 1444 for a 7-bit store; the byte codes still serve
+ * every other route (pairs, bursts, batches, export, save).  No new symbol: still 192 entry points. */
 
 typedef enum { QAMD_MEM_HOST = 0, QAMD_MEM_DEVICE = 1 } qamd_mem;
 

@@ -1635,7 +1635,7 @@ qamd_status qamd_bin_encode_enc(const float *data, qamd_mem data_mem, const qamd
                                 qamd_bin_encoding encoding, const float *lo, const float *hi, qamd_stop_fn stop,
                                 void *stop_user, void *stream, qamd_bin **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     QAMD_TRY(check_enc_args(vp, encoding, lo, hi, false));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
@@ -1661,7 +1661,7 @@ qamd_status qamd_bin_from_rows_enc(const uint8_t *rows, qamd_mem rows_mem, const
                                    qamd_bits_store store, qamd_bin_encoding encoding, const float *lo, const float *hi,
                                    void *stream, qamd_bin **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     QAMD_TRY(check_enc_args(vp, encoding, lo, hi, true));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     QAMD_ON_DEVICE(current_device());
@@ -1761,7 +1761,7 @@ qamd_status qamd_bin_save(const qamd_bin *h, const char *data_path, const char *
 qamd_status qamd_bin_load(const char *data_path, const char *meta_path, const qamd_vector_parameters *vp,
                           qamd_bits_store store, qamd_bin **out) {
     if (!data_path || !meta_path || !vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     JsonValue root;
     QAMD_TRY(read_metadata(meta_path, root));
     qamd_vector_parameters file_vp{};
@@ -3460,7 +3460,7 @@ qamd_status qamd_bin_encoder_begin_enc(const qamd_vector_parameters *vp, qamd_bi
                                        const float *lo, const float *hi, qamd_stop_fn stop, void *stop_user, void *stream,
                                        qamd_bin_encoder **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     QAMD_TRY(check_enc_args(vp, encoding, lo, hi, false));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     QAMD_ON_DEVICE(current_device());

@@ -556,9 +556,11 @@ qamd_status read_metadata(const char *meta_path, JsonValue &root) {
     return QAMD_OK;
 }
 
-qamd_status refuse_rotated(const qamd_vector_parameters *vp) {
+qamd_status refuse_u8_flags(const qamd_vector_parameters *vp) {
     if (vp->distance_type >= 0 && (vp->distance_type & QAMD_ROTATED))
         return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: only a single-GPU scalar-u8 store can be rotated", vp->distance_type);
+    if (vp->distance_type >= 0 && (vp->distance_type & QAMD_BITS4))
+        return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: only a single-GPU scalar-u8 store can have 4-bit rows", vp->distance_type);
     return QAMD_OK;
 }
 

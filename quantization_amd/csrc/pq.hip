@@ -2082,7 +2082,7 @@ qamd_status qamd_pq_encode(const float *data, qamd_mem data_mem, const qamd_vect
                            uint64_t chunk_size, const float *centroids, uint32_t max_kmeans_threads,
                            qamd_stop_fn stop, void *stop_user, void *stream, qamd_pq **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     if (chunk_size == 0) return fail(QAMD_ERR_ARGUMENTS, "chunk_size must be > 0");
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
@@ -2119,7 +2119,7 @@ qamd_status qamd_pq_encode(const float *data, qamd_mem data_mem, const qamd_vect
 qamd_status qamd_pq_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd_vector_parameters *vp,
                               uint64_t chunk_size, const float *centroids, void *stream, qamd_pq **out) {
     if (!vp || !out || !centroids) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     if (chunk_size == 0) return fail(QAMD_ERR_ARGUMENTS, "chunk_size must be > 0");
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     QAMD_ON_DEVICE(current_device());
@@ -2211,7 +2211,7 @@ qamd_status qamd_pq_save(const qamd_pq *h, const char *data_path, const char *me
 qamd_status qamd_pq_load(const char *data_path, const char *meta_path, const qamd_vector_parameters *vp,
                          qamd_pq **out) {
     if (!data_path || !meta_path || !vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     JsonValue root;
     QAMD_TRY(read_metadata(meta_path, root));
     qamd_vector_parameters file_vp{};
@@ -2713,7 +2713,7 @@ qamd_status qamd_pq_encoder_begin(const qamd_vector_parameters *vp, uint64_t chu
                                   uint32_t max_kmeans_threads, qamd_stop_fn stop, void *stop_user, void *stream,
                                   qamd_pq_encoder **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     if (chunk_size == 0) return fail(QAMD_ERR_ARGUMENTS, "chunk_size must be > 0");
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     QAMD_ON_DEVICE(current_device());

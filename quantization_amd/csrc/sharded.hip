@@ -916,7 +916,7 @@ qamd_status qamd_u8_sharded_encode(const float *data, qamd_mem data_mem, const q
                                    const int *devices, uint32_t n_shards, void *stream,
                                    qamd_u8_sharded **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
     std::unique_ptr<qamd_u8_sharded> h(new qamd_u8_sharded);
     h->ops = &kU8Ops;
@@ -978,7 +978,7 @@ qamd_status qamd_u8_sharded_from_rows(const uint8_t *rows, qamd_mem rows_mem, co
                                       const int *devices, uint32_t n_shards, void *stream,
                                    qamd_u8_sharded **out) {
     if (!meta || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(&meta->vector_parameters));
+    QAMD_TRY(refuse_u8_flags(&meta->vector_parameters));
     std::unique_ptr<qamd_u8_sharded> h(new qamd_u8_sharded);
     h->ops = &kU8Ops;
     h->meta = *meta;
@@ -1050,7 +1050,7 @@ qamd_status qamd_bin_sharded_encode(const float *data, qamd_mem data_mem, const 
                                     uint32_t n_shards, void *stream,
                                    qamd_bin_sharded **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
     std::unique_ptr<qamd_bin_sharded> h(new qamd_bin_sharded);
     h->ops = &kBinOps;
@@ -1070,7 +1070,7 @@ qamd_status qamd_bin_sharded_from_rows(const uint8_t *rows, qamd_mem rows_mem, c
                                        qamd_bits_store store, const int *devices, uint32_t n_shards, void *stream,
                                    qamd_bin_sharded **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     std::unique_ptr<qamd_bin_sharded> h(new qamd_bin_sharded);
     h->ops = &kBinOps;
     h->vp = *vp;
@@ -1137,7 +1137,7 @@ qamd_status qamd_pq_sharded_encode(const float *data, qamd_mem data_mem, const q
                                    qamd_stop_fn stop, void *stop_user, const int *devices, uint32_t n_shards, void *stream,
                                    qamd_pq_sharded **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     if (chunk_size == 0) return fail(QAMD_ERR_ARGUMENTS, "chunk_size must be > 0");
     if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
     std::unique_ptr<qamd_pq_sharded> h(new qamd_pq_sharded);
@@ -1166,7 +1166,7 @@ qamd_status qamd_pq_sharded_from_rows(const uint8_t *rows, qamd_mem rows_mem, co
                                       uint64_t chunk_size, const float *centroids, const int *devices, uint32_t n_shards, void *stream,
                                    qamd_pq_sharded **out) {
     if (!vp || !out || !centroids) return fail(QAMD_ERR_ARGUMENTS, "null argument");
-    QAMD_TRY(refuse_rotated(vp));
+    QAMD_TRY(refuse_u8_flags(vp));
     if (chunk_size == 0) return fail(QAMD_ERR_ARGUMENTS, "chunk_size must be > 0");
     std::unique_ptr<qamd_pq_sharded> h(new qamd_pq_sharded);
     h->ops = &kPqOps;

@@ -10,7 +10,8 @@
 // aligned 16-byte `global_load_dwordx4`.  Dot / L2 stores also keep a packed scan image of the
 // codes at 7 bits each, in blocks of 64 rows (u8_internal.hpp, build_packed), which their
 // single-query scans read with a row per lane (u8_scan_blocked_kernel): 676 instead of 772 bytes
-// per row at dim 768.
+// per row at dim 768.  A 4-bit store (QAMD_BITS4, DESIGN 3.1y: codes 0..15, rounded to nearest) keeps a nibble image in its
+// place, two codes per byte, read by u8_scan_nibble_kernel: 388 bytes per row.
 //
 // Scan mapping of the byte codes (HBM-bound integer work, no MFMA): a row is read by G = min(16, pow2(chunks))
 // adjacent lanes, 16 B per lane per iteration, so one wave-load covers 64/G consecutive rows
@@ -140,6 +141,23 @@ __device__ __forceinline__ uint32_t f32_to_u8(float v, float alpha, float offset
     x = (x < 0.0f) ? 0.0f : x;
     x = (x > 127.0f) ? 127.0f : x;
     return (x != x) ? 0u : (uint32_t)x;
+}
+
+// The code of a 4-bit store (the reference has no counterpart): 16 levels, rounded to nearest.  Three f32
+// operations, each rounded on its own - subtract, IEEE divide, add (this file is compiled with contraction off) - then the
+// clamp and the truncation of f32_to_u8.  NaN gives 0.  No division-free form: every 4-bit encoder takes this one.
+__device__ __forceinline__ uint32_t f32_to_u4(float v, float alpha, float offset) {
+    float x = (v - offset) / alpha + 0.5f;
+    x = (x < 0.0f) ? 0.0f : x;
+    x = (x > 15.0f) ? 15.0f : x;
+    return (x != x) ? 0u : (uint32_t)x;
+}
+template <bool FOUR> __device__ __forceinline__ uint32_t f32_to_code(float v, float alpha, float offset) {
+    return FOUR ? f32_to_u4(v, alpha, offset) : f32_to_u8(v, alpha, offset);
+}
+// The same choice at run time (`four` is a kernel argument: wave-uniform), for the kernels where no time is at stake.
+__device__ __forceinline__ uint32_t f32_to_code(float v, float alpha, float offset, int four) {
+    return four ? f32_to_u4(v, alpha, offset) : f32_to_u8(v, alpha, offset);
 }
 
 // f32_to_u8 for four values without the division, for all but ~6 values in 100 000.
@@ -344,6 +362,101 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8
         for (int i = 0; i < 7; i++)
             if ((uint32_t)i < n_rest) acc = dot16(and16(v[i], 0x7F7F7F7Fu), q[i], acc);
     }
+    if (split > 1) {
+        partial[threadIdx.x] = acc;
+        __syncthreads();
+        if (part == 0)
+            for (uint32_t p = 1; p < split; p++) acc += partial[threadIdx.x + 64 * p];
+    }
+    if (part == 0 && row < n_rows) {
+        const float score = epilogue(multiplier, acc, q_off, v_off, EPI == EPI_POINT ? 0.0f : diff, EPI);
+        if (FILTER) topk_offer(filt, pivot, score, (uint32_t)row);
+        else __builtin_nontemporal_store(score, out + row);
+    }
+}
+
+// ------------------------------------------------------------------------------ blocked scan of the nibble image
+// The scan of a 4-bit store that has a nibble image (u8_internal.hpp, build_packed): P4 = ceil(rc / 2)
+// chunks per row, byte b of chunk j = codes[32 j + b] | codes[32 j + 16 + b] << 4, in u8_scan_blocked_kernel's blocks of
+// 64 rows - and that kernel's mapping: `split` waves per block, a row per lane, every wave-load one aligned kilobyte, the
+// query's byte-code chunks read at wave-uniform addresses.  Per image chunk
+//   lo += dot(v & 0x0F.., q[2j]),  hi += dot(v & 0xF0.., q[2j + 1])
+// and the row's sum is lo + (hi >> 4): hi is a multiple of 16 and at most 240 * 15 * 2048 < 2^23, so the shift is
+// exact and happens once per wave.  The n_full = rc / 2 chunks with two code chunks each are walked in groups of
+// kNibbleRing; a group's registers are refilled from the next group behind their last use.  What is left - fewer than
+// kNibbleRing full chunks and, for an odd rc, the last chunk, whose high nibbles are zero and whose second query chunk
+// does not exist and is not read - is the rest group.  kNibbleRing = 8: 32 VGPRs in flight (DESIGN 3.1y has the
+// compiler's resource report).
+constexpr int kNibbleRing = 8;
+
+template <bool FILTER, int EPI = EPI_POINT>
+__global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void u8_scan_nibble_kernel(
+    const uint4 *__restrict__ image, const float *__restrict__ offsets, const uint4 *__restrict__ qcodes,
+    const float *__restrict__ q_off_p, float multiplier, uint32_t n_rows, uint32_t pchunks, uint32_t row_chunks,
+    uint32_t split, float *__restrict__ out, TopkFilter filt, float diff) {
+    constexpr int R = kNibbleRing;
+    __shared__ uint32_t partial[kScanBlock];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t part = wave & (split - 1);
+    const uint64_t block = (uint64_t)blockIdx.x * ((kScanBlock / 64) / split) + wave / split;
+    const uint64_t row = block * kPackBlockRows + lane;
+    const bool live = block * kPackBlockRows < n_rows;  // wave-uniform; offsets[] and the image are padded past every block
+    // the groups of a row: n_full / R groups of R chunks with both nibbles, then one of the n_rest chunks left
+    const uint32_t n_full = row_chunks / 2, n_ring = n_full / R, n_rest = pchunks - R * n_ring;
+    const uint32_t n_groups = n_ring + (n_rest ? 1 : 0);
+    const uint32_t g_begin = live ? n_groups * part / split : 0, g_end = live ? n_groups * (part + 1) / split : 0;
+    const uint4 *blk = image + block * pchunks * kPackBlockChunk;
+    const uint32_t lane16 = lane * 16;
+    auto chunk_ptr = [&](uint32_t c) {
+        return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(blk + (uint64_t)c * kPackBlockChunk) + lane16);
+    };
+    const uint32_t gf_end = g_end < n_ring ? g_end : n_ring;
+    const bool has_rest = g_end > n_ring;
+
+    uint4 v[R];
+    uint32_t lo = 0, hi = 0;
+    auto eat = [&](uint32_t g, auto refill) {
+        const uint4 *q = qcodes + 2 * R * g;
+#pragma unroll
+        for (int i = 0; i < R; i++) {
+            const uint4 w = v[i];
+            lo = dot16(and16(w, 0x0F0F0F0Fu), q[2 * i], lo);
+            hi = dot16(and16(w, 0xF0F0F0F0u), q[2 * i + 1], hi);
+            if (decltype(refill)::value) {  // pinned here, so that the load reuses the chunk's registers
+                __builtin_amdgcn_sched_barrier(0);
+                v[i] = ld_nt(chunk_ptr(R * (g + 1) + i));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    if (g_begin < gf_end) {
+#pragma unroll
+        for (int i = 0; i < R; i++) v[i] = ld_nt(chunk_ptr(R * g_begin + i));
+    }
+    const float v_off = offsets[row];
+    const float q_off = *q_off_p;
+    uint32_t pivot = 0;
+    if (FILTER) pivot = *filt.pivot_key;
+    if (g_begin < gf_end) {
+        for (uint32_t g = g_begin; g + 1 < gf_end; g++) eat(g, std::true_type{});
+        eat(gf_end - 1, std::false_type{});
+    }
+    if (has_rest) {  // chunks R * n_ring .. pchunks - 1; the last has no high half when row_chunks is odd
+        const uint32_t c0 = R * n_ring;
+        const uint4 *q = qcodes + 2 * c0;
+#pragma unroll
+        for (int i = 0; i < R; i++)
+            if ((uint32_t)i < n_rest) v[i] = ld_nt(chunk_ptr(c0 + i));
+#pragma unroll
+        for (int i = 0; i < R; i++) {
+            if ((uint32_t)i < n_rest) {
+                lo = dot16(and16(v[i], 0x0F0F0F0Fu), q[2 * i], lo);
+                if (c0 + i < n_full) hi = dot16(and16(v[i], 0xF0F0F0F0u), q[2 * i + 1], hi);
+            }
+        }
+    }
+    uint32_t acc = lo + (hi >> 4);
     if (split > 1) {
         partial[threadIdx.x] = acc;
         __syncthreads();
@@ -901,7 +1014,8 @@ __global__ __launch_bounds__(kScanBlock) void minmax_stream_kernel(const float4 
 // exact division AND with the division-free conversion -- the kernel is bound by the mixed read/write stream, not
 // by the vector ALU; plain instead of nt stores: the same; a lane owning four consecutive float4 (one 16-byte
 // store per lane, loads at a 64-byte lane stride): 3.6 ms.
-template <int ITERS /* float4 per lane, 0 = any dim (loop of 4-deep batches) */, bool FAST /* f32x4_to_u8x4_fast */>
+template <int ITERS /* float4 per lane, 0 = any dim (loop of 4-deep batches) */, bool FAST /* f32x4_to_u8x4_fast */,
+          bool FOUR = false /* 4-bit codes (f32_to_u4); never FAST */>
 __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
     const float *__restrict__ data, uint64_t n_rows, uint32_t dim, uint32_t actual_dim, float alpha,
     float offset, int distance, int invert, uint32_t *__restrict__ codes32, float *__restrict__ offsets,
@@ -918,7 +1032,7 @@ __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
     const uint32_t dwords = actual_dim / 4, f4 = dim / 4;
     uint32_t *dst = codes32 + (row0 + rc) * dwords;
     const float placeholder = (distance == QAMD_DOT) ? 0.0f : offset;
-    const uint32_t pad_code = f32_to_u8(placeholder, alpha, offset);
+    const uint32_t pad_code = f32_to_code<FOUR>(placeholder, alpha, offset);
     const uint32_t pad_dword = pad_code * 0x01010101u;
     uint32_t s1 = 0, s2 = 0;
     constexpr int DEPTH = ITERS ? ITERS : 4;
@@ -938,8 +1052,8 @@ __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
                 if (FAST) {
                     packed = f32x4_to_u8x4_fast(f[j], alpha, offset, r_alpha);
                 } else {
-                    packed = f32_to_u8(f[j].x, alpha, offset) | (f32_to_u8(f[j].y, alpha, offset) << 8) |
-                             (f32_to_u8(f[j].z, alpha, offset) << 16) | (f32_to_u8(f[j].w, alpha, offset) << 24);
+                    packed = f32_to_code<FOUR>(f[j].x, alpha, offset) | (f32_to_code<FOUR>(f[j].y, alpha, offset) << 8) |
+                             (f32_to_code<FOUR>(f[j].z, alpha, offset) << 16) | (f32_to_code<FOUR>(f[j].w, alpha, offset) << 24);
                 }
                 s1 = __builtin_amdgcn_udot4(packed, 0x01010101u, s1, false);  // sum of the four codes
                 s2 = __builtin_amdgcn_udot4(packed, packed, s2, false);       // sum of their squares
@@ -962,7 +1076,7 @@ __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
             if (s1 >= (1u << 24)) {
                 sum = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++)
-                    sum += (float)(j < dim ? f32_to_u8(src[j], alpha, offset) : pad_code);
+                    sum += (float)(j < dim ? f32_to_code<FOUR>(src[j], alpha, offset) : pad_code);
             }
             vo = D * offset * offset + sum * alpha * offset;
         } else if (distance == QAMD_L1) {
@@ -972,7 +1086,7 @@ __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
             if (s2 >= (1u << 24)) {
                 sum = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++) {
-                    const float c = (float)(j < dim ? f32_to_u8(src[j], alpha, offset) : pad_code);
+                    const float c = (float)(j < dim ? f32_to_code<FOUR>(src[j], alpha, offset) : pad_code);
                     sum += c * c;
                 }
             }
@@ -990,12 +1104,12 @@ __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
 __global__ __launch_bounds__(kBlock) void quantize_kernel(
     const float *__restrict__ data, uint64_t n_rows, uint32_t dim, uint32_t actual_dim, float alpha,
     float offset, int distance, int invert, uint32_t *__restrict__ codes32 /* row stride actual_dim/4 */,
-    float *__restrict__ offsets, uint64_t row0) {
+    float *__restrict__ offsets, uint64_t row0, int four) {
     const int lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
     const float placeholder = (distance == QAMD_DOT) ? 0.0f : offset;
-    const uint32_t pad_code = f32_to_u8(placeholder, alpha, offset);
+    const uint32_t pad_code = f32_to_code(placeholder, alpha, offset, four);
     const uint32_t dwords = actual_dim / 4;
     for (uint64_t r = wave; r < n_rows; r += n_waves) {
         const float *src = data + r * dim;
@@ -1006,7 +1120,7 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
 #pragma unroll
             for (int b = 0; b < 4; b++) {
                 uint32_t j = d * 4 + b;
-                uint32_t c = j < dim ? f32_to_u8(src[j], alpha, offset) : pad_code;
+                uint32_t c = j < dim ? f32_to_code(src[j], alpha, offset, four) : pad_code;
                 packed |= c << (8 * b);
                 s1 += c;
                 s2 += c * c;
@@ -1026,7 +1140,7 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
                 if (s1 >= (1u << 24)) {
                     s = 0.0f;
                     for (uint32_t j = 0; j < actual_dim; j++)
-                        s += (float)(j < dim ? f32_to_u8(src[j], alpha, offset) : pad_code);
+                        s += (float)(j < dim ? f32_to_code(src[j], alpha, offset, four) : pad_code);
                 }
                 vo = D * offset * offset + s * alpha * offset;
             } else if (distance == QAMD_L1) {
@@ -1036,7 +1150,7 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
                 if (s2 >= (1u << 24)) {
                     s = 0.0f;
                     for (uint32_t j = 0; j < actual_dim; j++) {
-                        float c = (float)(j < dim ? f32_to_u8(src[j], alpha, offset) : pad_code);
+                        float c = (float)(j < dim ? f32_to_code(src[j], alpha, offset, four) : pad_code);
                         s += c * c;
                     }
                 }
@@ -1056,8 +1170,12 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
 // the codes and the row offset as quantize16_kernel writes them) and the values themselves (queries, the quantile sample).
 // The lanes of a last chunk past dim / 4 hold +-0.0 (rotate_blocks_wave): they are kept out of every fold and store.
 // K = 4 and K = 8 carry the chunk stages that dim = 1024 and dim = 2048, one block each, need (POW2).
+constexpr int kQuant4Bit = 2;  // `fast` of the u8_rot_quantize kernels: 0 the exact division, 1 the division-free form, 2 4-bit codes
 __device__ __forceinline__ uint32_t rot_quant4(const float (&v)[4], float alpha, float offset, float r_alpha, int fast) {
     const float4 f = make_float4(v[0], v[1], v[2], v[3]);
+    if (fast == kQuant4Bit)  // a 4-bit store; wave-uniform
+        return f32_to_u4(f.x, alpha, offset) | (f32_to_u4(f.y, alpha, offset) << 8) | (f32_to_u4(f.z, alpha, offset) << 16) |
+               (f32_to_u4(f.w, alpha, offset) << 24);
     if (fast) return f32x4_to_u8x4_fast(f, alpha, offset, r_alpha);
     return f32_to_u8(f.x, alpha, offset) | (f32_to_u8(f.y, alpha, offset) << 8) | (f32_to_u8(f.z, alpha, offset) << 16) |
            (f32_to_u8(f.w, alpha, offset) << 24);
@@ -1312,14 +1430,14 @@ __global__ __launch_bounds__(kBlock) void u8_rot_values_lds_kernel(const float *
 __global__ __launch_bounds__(64) void encode_query_kernel(const float *__restrict__ query,
                                                          uint32_t qdim, uint32_t actual_dim,
                                                          float alpha, float offset, int distance,
-                                                         int invert, uint8_t *__restrict__ qbuf) {
+                                                         int invert, uint8_t *__restrict__ qbuf, int four) {
     const int lane = threadIdx.x;
     const float placeholder = (distance == QAMD_DOT) ? 0.0f : offset;
-    const uint32_t pad_code = f32_to_u8(placeholder, alpha, offset);
+    const uint32_t pad_code = f32_to_code(placeholder, alpha, offset, four);
     uint8_t *codes = qbuf + 16;
     uint32_t s1 = 0, s2 = 0;
     for (uint32_t j = lane; j < actual_dim; j += 64) {
-        uint32_t c = j < qdim ? f32_to_u8(query[j], alpha, offset) : pad_code;
+        uint32_t c = j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code;
         codes[j] = (uint8_t)c;
         s1 += c;
         s2 += c * c;
@@ -1336,7 +1454,7 @@ __global__ __launch_bounds__(64) void encode_query_kernel(const float *__restric
             if (s1 >= (1u << 24)) {
                 s = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++)
-                    s += (float)(j < qdim ? f32_to_u8(query[j], alpha, offset) : pad_code);
+                    s += (float)(j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code);
             }
             off = s * alpha * offset;
         } else if (distance == QAMD_L1) {
@@ -1346,7 +1464,7 @@ __global__ __launch_bounds__(64) void encode_query_kernel(const float *__restric
             if (s2 >= (1u << 24)) {
                 s = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++) {
-                    float c = (float)(j < qdim ? f32_to_u8(query[j], alpha, offset) : pad_code);
+                    float c = (float)(j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code);
                     s += c * c;
                 }
             }
@@ -1361,15 +1479,15 @@ __global__ __launch_bounds__(64) void encode_query_kernel(const float *__restric
 __global__ __launch_bounds__(64) void encode_queries_kernel(const float *__restrict__ queries, uint32_t qdim,
                                                            uint32_t actual_dim, float alpha, float offset,
                                                            int distance, int invert, uint8_t *__restrict__ codes_out,
-                                                           uint32_t code_pitch, float *__restrict__ offsets_out) {
+                                                           uint32_t code_pitch, float *__restrict__ offsets_out, int four) {
     const int lane = threadIdx.x;
     const float *query = queries + (size_t)blockIdx.x * qdim;
     uint8_t *codes = codes_out + (size_t)blockIdx.x * code_pitch;
     const float placeholder = (distance == QAMD_DOT) ? 0.0f : offset;
-    const uint32_t pad_code = f32_to_u8(placeholder, alpha, offset);
+    const uint32_t pad_code = f32_to_code(placeholder, alpha, offset, four);
     uint32_t s1 = 0, s2 = 0;
     for (uint32_t j = lane; j < actual_dim; j += 64) {
-        uint32_t c = j < qdim ? f32_to_u8(query[j], alpha, offset) : pad_code;
+        uint32_t c = j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code;
         codes[j] = (uint8_t)c;
         s1 += c;
         s2 += c * c;
@@ -1386,7 +1504,7 @@ __global__ __launch_bounds__(64) void encode_queries_kernel(const float *__restr
             if (s1 >= (1u << 24)) {
                 s = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++)
-                    s += (float)(j < qdim ? f32_to_u8(query[j], alpha, offset) : pad_code);
+                    s += (float)(j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code);
             }
             off = s * alpha * offset;
         } else if (distance == QAMD_L1) {
@@ -1396,7 +1514,7 @@ __global__ __launch_bounds__(64) void encode_queries_kernel(const float *__restr
             if (s2 >= (1u << 24)) {
                 s = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++) {
-                    float c = (float)(j < qdim ? f32_to_u8(query[j], alpha, offset) : pad_code);
+                    float c = (float)(j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code);
                     s += c * c;
                 }
             }
@@ -1492,6 +1610,29 @@ __global__ __launch_bounds__(kBlock) void u8_pack7_range_kernel(const uint4 *__r
     }
 }
 
+// The nibble image (u8_internal.hpp) of rows [r0, r0 + n_rows) of a 4-bit store: one thread per (row, image chunk j),
+// code chunk 2j in the low nibbles and code chunk 2j + 1 - zeros when the row has none - in the high ones.  `bad`
+// (builders; null for upsert, whose rows come from the store's own encoder): a code above 15 anywhere in the rows
+// (bytes another producer wrote: from_rows, load) sets it, and the image is then dropped.
+__global__ __launch_bounds__(kBlock) void u8_pack4_kernel(const uint4 *__restrict__ codes, uint64_t r0, uint64_t n_rows,
+                                                          uint32_t row_chunks, uint32_t pchunks, uint4 *__restrict__ packed,
+                                                          uint32_t *__restrict__ bad) {
+    const uint64_t total = n_rows * pchunks, stride = (uint64_t)gridDim.x * kBlock;
+    uint32_t high = 0;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
+        const uint64_t r = r0 + t / pchunks;
+        const uint32_t j = (uint32_t)(t % pchunks);
+        const uint4 *row = codes + r * row_chunks;
+        const uint4 a = row[2 * j];
+        const uint4 b = 2 * j + 1 < row_chunks ? row[2 * j + 1] : make_uint4(0, 0, 0, 0);
+        high |= a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w;
+        packed[((r / kPackBlockRows) * pchunks + j) * kPackBlockRows + r % kPackBlockRows] =
+            make_uint4((a.x & 0x0F0F0F0Fu) | ((b.x & 0x0F0F0F0Fu) << 4), (a.y & 0x0F0F0F0Fu) | ((b.y & 0x0F0F0F0Fu) << 4),
+                       (a.z & 0x0F0F0F0Fu) | ((b.z & 0x0F0F0F0Fu) << 4), (a.w & 0x0F0F0F0Fu) | ((b.w & 0x0F0F0F0Fu) << 4));
+    }
+    if (bad && (high & 0xF0F0F0F0u)) atomicOr(bad, 1u);
+}
+
 int grid_for(uint64_t work_items, uint64_t per_block, int blocks_per_cu) {
     uint64_t want = (work_items + per_block - 1) / per_block;
     uint64_t cap = (uint64_t)device_info().cu_count * blocks_per_cu;
@@ -1576,13 +1717,17 @@ qamd_status alloc_store(qamd_u8 *h) {
 // the Dot / L2 scans of lane mode 0 read it, so L1 stores, stores of fewer than 8 chunks (no whole extra chunk) and of
 // more than 128 (the generic kernel) get none.  It costs 7/8 of the code bytes in HBM: it is skipped when it would
 // leave less free HBM than its own size, and a failed allocation only leaves the store on its byte codes.  So does
-// a code above 127 (rows another producer wrote).
+// a code above 127 (rows another producer wrote).  A 4-bit store gets a nibble image instead (half the code bytes; from
+// 2 chunks on; a code above 15 drops it).
 qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
     h->packed.release();
     h->packed_rows.release();
     h->packed_chunks = 0;
-    const uint32_t rc = h->row_chunks, n_extra = rc / 8, pchunks = rc - n_extra;
-    if (!u8_packed_allowed() || h->count == 0 || rc < 8 || rc > 128 ||
+    h->packed_nibble = false;
+    // A 4-bit store gets the nibble image in the 7-bit one's place, from 2 chunks on, under the same rules.
+    const bool nibble = h->four_bit;
+    const uint32_t rc = h->row_chunks, n_extra = nibble ? 0 : rc / 8, pchunks = nibble ? (rc + 1) / 2 : rc - n_extra;
+    if (!u8_packed_allowed() || h->count == 0 || rc < (nibble ? 2u : 8u) || rc > 128 ||
         h->meta.vector_parameters.distance_type == QAMD_L1)
         return QAMD_OK;
     const uint64_t bytes = h->padded_rows * pchunks * 16;
@@ -1599,8 +1744,12 @@ qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
         last_error() = err;
         return QAMD_OK;
     }
-    hipLaunchKernelGGL(u8_pack7_kernel, dim3(grid_for(h->count * pchunks, kBlock, 8)), dim3(kBlock), 0, s,
-                       h->codes.as<uint4>(), h->count, rc, pchunks, n_extra, img.as<uint4>(), bad.as<uint32_t>());
+    if (nibble)
+        hipLaunchKernelGGL(u8_pack4_kernel, dim3(grid_for(h->count * pchunks, kBlock, 8)), dim3(kBlock), 0, s,
+                           h->codes.as<uint4>(), (uint64_t)0, h->count, rc, pchunks, img.as<uint4>(), bad.as<uint32_t>());
+    else
+        hipLaunchKernelGGL(u8_pack7_kernel, dim3(grid_for(h->count * pchunks, kBlock, 8)), dim3(kBlock), 0, s,
+                           h->codes.as<uint4>(), h->count, rc, pchunks, n_extra, img.as<uint4>(), bad.as<uint32_t>());
     QAMD_HIP(hipGetLastError());
     uint32_t high = 0;
     QAMD_HIP(hipMemcpyAsync(&high, bad.ptr, sizeof(high), hipMemcpyDeviceToHost, s));
@@ -1608,6 +1757,7 @@ qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
     if (high) return QAMD_OK;
     h->packed = std::move(img);
     h->packed_chunks = pchunks;
+    h->packed_nibble = nibble;
     return QAMD_OK;
 }
 
@@ -1683,6 +1833,29 @@ void launch_scan_blocked(const qamd_u8 *h, const uint4 *qc, const float *qo, flo
 #undef QAMD_U8_BLOCKED_AS
 }
 
+// The Dot / L2 scan of a 4-bit store that has a nibble image: u8_scan_nibble_kernel over the same blocks, the same split.
+void launch_scan_nibble(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
+                        hipStream_t s, const ScanEpi &e) {
+    const uint64_t n_rows = scan_rows(h, e);
+    const uint32_t split = blocked_split(n_rows), blocks_per_wg = (kScanBlock / 64) / split;
+    const uint64_t blocks = (n_rows + kPackBlockRows - 1) / kPackBlockRows;
+    const unsigned grid = (unsigned)((blocks + blocks_per_wg - 1) / blocks_per_wg);
+    h->last_scan_split.store((int)split, std::memory_order_relaxed);
+#define QAMD_U8_NIBBLE_AS(FI, EPI)                                                                                   \
+    hipLaunchKernelGGL((u8_scan_nibble_kernel<FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, h->packed.as<uint4>(),   \
+                       h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)n_rows, h->packed_chunks,        \
+                       h->row_chunks, split, out, filt ? *filt : TopkFilter{}, e.diff)
+#define QAMD_U8_NIBBLE(FI)                                       \
+    do {                                                         \
+        if (e.mode == EPI_POINT) QAMD_U8_NIBBLE_AS(FI, EPI_POINT); \
+        else QAMD_U8_NIBBLE_AS(FI, EPI_INTERNAL);                \
+    } while (0)
+    if (filt) QAMD_U8_NIBBLE(true);
+    else QAMD_U8_NIBBLE(false);
+#undef QAMD_U8_NIBBLE
+#undef QAMD_U8_NIBBLE_AS
+}
+
 // Returns false when the store's row size has no templated kernel (caller uses the generic one).
 // The Dot / L2 scans read the packed image when the store has one (its rows are 7/8 as long).
 template <bool IS_L1>
@@ -1690,7 +1863,8 @@ bool launch_scan(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out,
                  hipStream_t s, const ScanEpi &e) {
     using L = ScanLaunch<IS_L1>;
     const bool packed = !IS_L1 && h->packed_chunks != 0;
-    h->last_scan_packed.store(packed ? 1 : 0, std::memory_order_relaxed);
+    h->last_scan_packed.store(packed ? (h->packed_nibble ? 2 : 1) : 0, std::memory_order_relaxed);
+    if (packed && h->packed_nibble) return launch_scan_nibble(h, qc, qo, out, filt, s, e), true;
     if (packed) return launch_scan_blocked(h, qc, qo, out, filt, s, e), true;
     const uint32_t rc = h->row_chunks;
     if (rc == 1) return L::template go<1, 1, 4>(h, qc, qo, out, filt, s, e), true;
@@ -2207,7 +2381,8 @@ qamd_status launch_quantize(qamd_u8 *h, const float *src, uint64_t nr, uint64_t 
     // the division-free conversion needs a normal alpha well inside the exponent range (f32_to_u8_fast)
     const bool fast = alpha >= 8.673617379884035e-19f && alpha <= 1.152921504606847e+18f;  // 2^-60 .. 2^60
     if (h->rotated) {  // rotated in registers, no copy of the rotated values
-        QAMD_ROT_LAUNCH(u8_rot_quantize_kernel, u8_rot_quantize_lds_kernel, src, nr, dim, s, alpha, offset, (int)fast,
+        QAMD_ROT_LAUNCH(u8_rot_quantize_kernel, u8_rot_quantize_lds_kernel, src, nr, dim, s, alpha, offset,
+                        h->four_bit ? kQuant4Bit : (int)fast,
                         vp.distance_type, vp.invert, h->codes.as<uint32_t>(), h->offsets.as<float>(), r0);
         QAMD_HIP(hipGetLastError());
         return QAMD_OK;
@@ -2218,7 +2393,11 @@ qamd_status launch_quantize(qamd_u8 *h, const float *src, uint64_t nr, uint64_t 
         const uint32_t per_lane = (uint32_t)((h->meta.actual_dim / 4 + 15) / 16);  // float4 per lane
 #define QAMD_Q16(IT)                                                                                          \
     do {                                                                                                      \
-        if (fast)                                                                                             \
+        if (h->four_bit)  /* 4-bit codes take the exact division */                              \
+            hipLaunchKernelGGL((quantize16_kernel<IT, false, true>), dim3(grid), dim3(kScanBlock), 0, s, src, nr, \
+                               (uint32_t)dim, (uint32_t)h->meta.actual_dim, alpha, offset, vp.distance_type,  \
+                               vp.invert, h->codes.as<uint32_t>(), h->offsets.as<float>(), r0);               \
+        else if (fast)                                                                                        \
             hipLaunchKernelGGL((quantize16_kernel<IT, true>), dim3(grid), dim3(kScanBlock), 0, s, src, nr,    \
                                (uint32_t)dim, (uint32_t)h->meta.actual_dim, alpha, offset, vp.distance_type,  \
                                vp.invert, h->codes.as<uint32_t>(), h->offsets.as<float>(), r0);               \
@@ -2239,7 +2418,7 @@ qamd_status launch_quantize(qamd_u8 *h, const float *src, uint64_t nr, uint64_t 
         int grid = grid_for(nr, kBlock / 64, 8);
         hipLaunchKernelGGL(quantize_kernel, dim3(grid), dim3(kBlock), 0, s, src, nr, (uint32_t)dim,
                            (uint32_t)h->meta.actual_dim, alpha, offset, vp.distance_type, vp.invert,
-                           h->codes.as<uint32_t>(), h->offsets.as<float>(), r0);
+                           h->codes.as<uint32_t>(), h->offsets.as<float>(), r0, (int)h->four_bit);
     }
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
@@ -2256,13 +2435,16 @@ bool quantile_cut(uint64_t slice, uint64_t dim, float quantile, uint64_t &cut) {
     return !(hi <= lo || hi - lo < 2);  // :63-65
 }
 
-// The distance_type a u8 constructor is handed: a qamd_distance, or QAMD_DOT / QAMD_L2 with QAMD_ROTATED or-ed on (DESIGN
-// 3.1x).  The handle keeps `base` in its metadata and the flag beside it.  No device call.
-qamd_status split_distance(const qamd_vector_parameters &vp, int &base, bool &rotated) {
+// The distance_type a u8 constructor is handed: a qamd_distance, or QAMD_DOT / QAMD_L2 with QAMD_ROTATED,
+// QAMD_BITS4 (3.1y) or both or-ed on.  The handle keeps `base` in its metadata and the flags beside it.  No device call.
+qamd_status split_distance(const qamd_vector_parameters &vp, int &base, bool &rotated, bool &four_bit) {
     const int dt = vp.distance_type;
     rotated = dt >= 0 && (dt & QAMD_ROTATED) != 0;
-    base = rotated ? (dt & ~QAMD_ROTATED) : dt;
+    four_bit = dt >= 0 && (dt & QAMD_BITS4) != 0;
+    base = dt >= 0 ? (dt & ~(QAMD_ROTATED | QAMD_BITS4)) : dt;
     if (base < 0 || base > 2) return fail(QAMD_ERR_ARGUMENTS, "bad distance_type %d", dt);
+    if (four_bit && base == QAMD_L1)
+        return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: 4-bit rows are for Dot and L2 stores", dt);
     if (rotated && base == QAMD_L1)
         return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: L1 is not invariant under the rotation of a rotated store", dt);
     if (rotated && !rot_dim_ok(vp.dim))
@@ -2287,8 +2469,8 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
                            void *stop_user, void *stream, qamd_u8 **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     int base_distance = 0;
-    bool rotated = false;
-    QAMD_TRY(split_distance(*vp, base_distance, rotated));
+    bool rotated = false, four_bit = false;
+    QAMD_TRY(split_distance(*vp, base_distance, rotated, four_bit));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
     QAMD_ON_DEVICE(current_device());
@@ -2300,6 +2482,8 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
     h->meta.vector_parameters = *vp;
     h->meta.vector_parameters.distance_type = base_distance;
     h->rotated = rotated;
+    h->four_bit = four_bit;
+    const float levels = four_bit ? 15.0f : 127.0f;  // alpha = (max - min) / levels (:228-232)
     QAMD_TRY(alloc_store(h.get()));
     if (vp->count == 0) {  // encoded_vectors_u8.rs:43-54
         h->meta.alpha = h->meta.offset = h->meta.multiplier = 0.0f;
@@ -2368,7 +2552,7 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
         }
         float mn, mx;
         QAMD_TRY(acc.result(s, mn, mx));
-        alpha = (mx - mn) / 127.0f;  // :228-232
+        alpha = (mx - mn) / levels;  // :228-232
         offset = mn;
         // PASS 1b (:58-71): quantile interval on <= 100 000 sampled vectors.
         if (quantile && !(count < 127 || *quantile >= 1.0f)) {  // :27-29
@@ -2376,7 +2560,7 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
             float qmn = 0.0f, qmx = 0.0f;
             QAMD_TRY(quantile_interval_device(data, data_mem, count, dim, *quantile, s, found, qmn, qmx, rotated));
             if (found) {
-                alpha = (qmx - qmn) / 127.0f;
+                alpha = (qmx - qmn) / levels;
                 offset = qmn;
             }
         }
@@ -2405,8 +2589,9 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
     if (!meta || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     const qamd_vector_parameters &vp = meta->vector_parameters;
     int base_distance = vp.distance_type;
-    bool rotated = false;  // the flag get_metadata reported travels back in here
-    if (vp.distance_type >= 0 && (vp.distance_type & QAMD_ROTATED)) QAMD_TRY(split_distance(vp, base_distance, rotated));
+    bool rotated = false, four_bit = false;  // the flags get_metadata reported travel back in here
+    if (vp.distance_type >= 0 && (vp.distance_type & (QAMD_ROTATED | QAMD_BITS4)))
+        QAMD_TRY(split_distance(vp, base_distance, rotated, four_bit));
     if (meta->actual_dim != actual_dim_of(vp.dim))
         return fail(QAMD_ERR_ARGUMENTS, "metadata actual_dim %llu does not match dim %llu",
                     (unsigned long long)meta->actual_dim, (unsigned long long)vp.dim);
@@ -2420,6 +2605,7 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
     h->meta = *meta;
     h->meta.vector_parameters.distance_type = base_distance;
     h->rotated = rotated;
+    h->four_bit = four_bit;
     QAMD_TRY(alloc_store(h.get()));
     const uint64_t stride = meta->actual_dim + 4;
     const uint32_t row_dwords = (uint32_t)(stride / 4);
@@ -2486,6 +2672,7 @@ qamd_status qamd_u8_get_metadata(const qamd_u8 *h, qamd_u8_metadata *out) {
     if (!h || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     *out = h->meta;
     if (h->rotated) out->vector_parameters.distance_type |= QAMD_ROTATED;
+    if (h->four_bit) out->vector_parameters.distance_type |= QAMD_BITS4;
     return QAMD_OK;
 }
 
@@ -2496,7 +2683,8 @@ qamd_status qamd_u8_save(const qamd_u8 *h, const char *data_path, const char *me
                      ",\"alpha\":" + json_f32(h->meta.alpha) + ",\"offset\":" + json_f32(h->meta.offset) +
                      ",\"multiplier\":" + json_f32(h->meta.multiplier) +
                      ",\"vector_parameters\":" + vector_parameters_json(h->meta.vector_parameters) +
-                     (h->rotated ? ",\"rotation\":\"HadamardBlocks\"" : "") + "}";  // the base metric above; 3.1x
+                     (h->rotated ? ",\"rotation\":\"HadamardBlocks\"" : "") +  // the base metric above; 3.1x
+                     (h->four_bit ? ",\"bits\":4" : "") + "}";                      // 3.1y
     QAMD_TRY(save_file(meta_path, js.data(), js.size()));
     const uint64_t stride = h->meta.actual_dim + 4;
     std::vector<uint8_t> rows(h->count * stride);
@@ -2531,6 +2719,17 @@ qamd_status qamd_u8_load(const char *data_path, const char *meta_path, const qam
     if (rotated && (meta.vector_parameters.distance_type == QAMD_L1 || !rot_dim_ok(vp->dim)))
         return fail(QAMD_ERR_IO, "%s: a rotated store of metric %s and %llu dimensions", meta_path,
                     distance_name(meta.vector_parameters.distance_type), (unsigned long long)vp->dim);
+    // "bits" (DESIGN 3.1y): absent = a 7-bit store; 4 is the one value a store writes
+    bool four_bit = false;
+    for (const auto &m : root.members) {
+        if (m.first != "bits") continue;
+        const JsonValue &b = m.second;
+        if (four_bit || b.kind != JsonValue::Number || !b.integer || b.negative || b.uint != 4)
+            return fail(QAMD_ERR_IO, "%s: unknown or repeated bits", meta_path);
+        four_bit = true;
+    }
+    if (four_bit && meta.vector_parameters.distance_type == QAMD_L1)
+        return fail(QAMD_ERR_IO, "%s: a 4-bit store of metric L1", meta_path);
     const uint64_t size = qamd_u8_quantized_vector_size(vp);
     std::string bytes;
     QAMD_TRY(load_rows_file(data_path, size * vp->count, bytes));
@@ -2540,6 +2739,7 @@ qamd_status qamd_u8_load(const char *data_path, const char *meta_path, const qam
     eff.vector_parameters.count = vp->count;
     eff.actual_dim = actual_dim_of(vp->dim);
     if (rotated) eff.vector_parameters.distance_type |= QAMD_ROTATED;  // from_rows takes it off again
+    if (four_bit) eff.vector_parameters.distance_type |= QAMD_BITS4;
     qamd_status st = qamd_u8_from_rows(reinterpret_cast<const uint8_t *>(bytes.data()), QAMD_MEM_HOST, &eff,
                                        nullptr, out);
     eff.vector_parameters.distance_type = meta.vector_parameters.distance_type;
@@ -2579,7 +2779,7 @@ qamd_status encode_now(const qamd_u8_query *q, const float *query, uint64_t qdim
         q_dev = rot;
     }
     hipLaunchKernelGGL(encode_query_kernel, dim3(1), dim3(64), 0, s, q_dev, (uint32_t)qdim, (uint32_t)ad, q->alpha,
-                       q->offset, q->distance, q->invert, q->buf.as<uint8_t>());
+                       q->offset, q->distance, q->invert, q->buf.as<uint8_t>(), (int)q->four_bit);
     QAMD_HIP(hipGetLastError());
     if (via_scratch) host_query_release(s);
     return q->ready.record(s);
@@ -2624,11 +2824,13 @@ qamd_status qamd_u8_encode_query(const qamd_u8 *h, const float *query, uint64_t 
         q->actual_dim = ad;
     }
     q->rotated = h->rotated;
+    q->four_bit = h->four_bit;
     q->alpha = h->meta.alpha;
     q->offset = h->meta.offset;
     q->distance = h->meta.vector_parameters.distance_type;
     q->invert = h->meta.vector_parameters.invert;
-    if (query_mem == QAMD_MEM_HOST && u8_host_encode_is_lazy(qdim) && !h->rotated) {  // (the fused top-k does not rotate)
+    // (the fused top-k neither rotates nor makes 4-bit codes)
+    if (query_mem == QAMD_MEM_HOST && u8_host_encode_is_lazy(qdim) && !h->rotated && !h->four_bit) {
         // Deferred: the values are kept, nothing is launched.  On a small store the top-k kernel takes them
         // by value and quantises them itself (u8_topk_small_fused_kernel); any other consumer encodes first.
         std::lock_guard<std::mutex> lk(q->encode_mu);
@@ -2779,7 +2981,10 @@ qamd_status qamd_u8_topk(const qamd_u8 *h, const qamd_u8_query *q, uint32_t k, i
 
 void qamd_u8_free(qamd_u8 *h) { delete h; }
 
-uint64_t qamd_u8_scan_bytes_per_row(const qamd_u8 *h) { return h ? h->meta.actual_dim + 4 : 0; }
+uint64_t qamd_u8_scan_bytes_per_row(const qamd_u8 *h) {
+    if (h && h->packed_chunks && h->packed_nibble) return 16ull * h->packed_chunks + 4;  // the nibble image
+    return h ? h->meta.actual_dim + 4 : 0;
+}
 
 // Selects how sums above 2^24 are rounded (0: once, 1: avx2.c lane order).  Not part of the
 // reference surface; see the header of this file.
@@ -2854,7 +3059,8 @@ qamd_status encoder_close_pass1(qamd_u8_encoder *e) {
                     (unsigned long long)e->observed, (unsigned long long)count);
     float mn, mx;
     QAMD_TRY(e->acc.result(e->stream, mn, mx));
-    e->alpha = (mx - mn) / 127.0f;  // :228-232
+    const float levels = e->h->four_bit ? 15.0f : 127.0f;
+    e->alpha = (mx - mn) / levels;  // :228-232
     e->offset = mn;
     if (e->slice) {
         uint64_t cut = 0;
@@ -2870,7 +3076,7 @@ qamd_status encoder_close_pass1(qamd_u8_encoder *e) {
             }
             QAMD_TRY(select_kth_f32(e->sample.as<float>(), len, cut + 2, false, &qmn, e->stream));
             QAMD_TRY(select_kth_f32(e->sample.as<float>(), len, cut + 1, true, &qmx, e->stream));
-            e->alpha = (qmx - qmn) / 127.0f;
+            e->alpha = (qmx - qmn) / levels;
             e->offset = qmn;
         }
         e->sample.release();
@@ -2887,15 +3093,15 @@ qamd_status qamd_u8_encoder_begin(const qamd_vector_parameters *vp, const float 
                                   qamd_stop_fn stop, void *stop_user, void *stream, qamd_u8_encoder **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     int base_distance = 0;
-    bool rotated = false;
-    QAMD_TRY(split_distance(*vp, base_distance, rotated));
+    bool rotated = false, four_bit = false;
+    QAMD_TRY(split_distance(*vp, base_distance, rotated, four_bit));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     QAMD_ON_DEVICE(current_device());
     std::unique_ptr<qamd_u8_encoder> e(new qamd_u8_encoder);
     e->device = current_device();
     e->stream = as_stream(stream);
     e->vp = *vp;
-    e->vp.distance_type = base_distance;  // the flag lives in h->rotated
+    e->vp.distance_type = base_distance;  // the flags live in h->rotated and h->four_bit
     e->stop = stop;
     e->stop_user = stop_user;
     e->h.reset(new qamd_u8);
@@ -2904,6 +3110,7 @@ qamd_status qamd_u8_encoder_begin(const qamd_vector_parameters *vp, const float 
     e->h->meta.actual_dim = actual_dim_of(vp->dim);
     e->h->meta.vector_parameters = e->vp;
     e->h->rotated = rotated;
+    e->h->four_bit = four_bit;
     QAMD_TRY(alloc_store(e->h.get()));
     if (alpha_offset) {
         e->alpha = alpha_offset[0];
@@ -3025,7 +3232,7 @@ qamd_status u8_grow(qamd_u8 *h, uint64_t cap) {
     h->codes = std::move(codes);  // (the old buffers go through hipFree, which waits for the device)
     h->offsets = std::move(offsets);
     h->packed = std::move(packed);
-    if (!image) h->packed_chunks = 0;
+    if (!image) h->packed_chunks = 0, h->packed_nibble = false;
     h->packed_rows.release();
     h->capacity = cap;
     h->padded_rows = padded;
@@ -3068,7 +3275,12 @@ qamd_status qamd_u8_upsert(qamd_u8 *h, uint64_t first_row, const float *data, qa
                                    [&](const float *src, uint64_t r, uint64_t nr) {
         return launch_quantize(h, src, nr, first_row + r, h->meta.alpha, h->meta.offset, s);
     }));
-    if (h->packed_chunks) {
+    if (h->packed_chunks && h->packed_nibble) {
+        hipLaunchKernelGGL(u8_pack4_kernel, dim3(grid_for(n_rows * h->packed_chunks, kBlock, 8)), dim3(kBlock), 0, s,
+                           h->codes.as<uint4>(), first_row, n_rows, h->row_chunks, h->packed_chunks, h->packed.as<uint4>(),
+                           (uint32_t *)nullptr);
+        QAMD_HIP(hipGetLastError());
+    } else if (h->packed_chunks) {
         const uint32_t rc = h->row_chunks, pchunks = h->packed_chunks;
         hipLaunchKernelGGL(u8_pack7_range_kernel, dim3(grid_for(n_rows * pchunks, kBlock, 8)), dim3(kBlock), 0, s,
                            h->codes.as<uint4>(), first_row, n_rows, rc, pchunks, rc / 8, h->packed.as<uint4>());
@@ -3151,7 +3363,7 @@ qamd_status u8_encode_queries_device(const qamd_u8 *h, const float *queries_dev,
     }
     hipLaunchKernelGGL(encode_queries_kernel, dim3((unsigned)n_queries), dim3(64), 0, stream, queries_dev,
                        (uint32_t)qdim, (uint32_t)actual_dim_of(qdim), h->meta.alpha, h->meta.offset,
-                       vp.distance_type, vp.invert, codes_dev, (uint32_t)code_pitch, offsets_dev);
+                       vp.distance_type, vp.invert, codes_dev, (uint32_t)code_pitch, offsets_dev, (int)h->four_bit);
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
 }

@@ -19,6 +19,10 @@ struct qamd_u8 {
     // the queries.  meta.vector_parameters.distance_type keeps the BASE metric (QAMD_DOT or QAMD_L2), so no kernel, route
     // or multiplier knows; QAMD_ROTATED is added back where metadata leaves the library (get_metadata).
     bool rotated = false;
+    // A 4-bit store: the byte codes hold 0..15, alpha is a fifteenth of the interval and the encoders round
+    // to nearest.  Like `rotated` it lives beside the base metric and goes back on in get_metadata; only the encoders,
+    // the query encoders and build_packed read it - the scans see the image that build_packed left (packed_nibble).
+    bool four_bit = false;
     qamd::DevBuf codes;        // [padded_rows][actual_dim]
     qamd::DevBuf offsets;      // [padded_rows] f32
     // Packed scan image (u8.hip build_packed): the codes at 7 bits each, packed_chunks 16-byte chunks per row.  Chunk
@@ -30,7 +34,11 @@ struct qamd_u8 {
     // when the store has none (L1, fewer than 8 or more than 128 chunks, a code above 127, too little free HBM).
     qamd::DevBuf packed;
     uint32_t packed_chunks = 0;
-    mutable std::atomic<int> last_scan_packed{0};  // the image the last scan launch read (developer report)
+    // The image of a 4-bit store is a nibble image instead (never both): packed_chunks = ceil(row_chunks / 2), byte b of
+    // chunk j = codes[32 j + b] | codes[32 j + 16 + b] << 4 (high nibbles of the last chunk zero when row_chunks is odd),
+    // in the same blocks of 64 rows.  u8_scan_nibble_kernel reads it; stores of 2 to 128 chunks have one.
+    bool packed_nibble = false;
+    mutable std::atomic<int> last_scan_packed{0};  // the image the last scan launch read: 1 packed, 2 nibble (developer report)
     mutable std::atomic<int> last_scan_split{0};   // waves per block of the last blocked scan launch (developer report)
     mutable qamd::DevBuf packed_rows;              // developer report: the image un-blocked, [count][packed_chunks]
     // The batched top-k's pivot sample (u8_batch.hip): rows hash(j) of the store, j < sample_rows, then 512
@@ -53,6 +61,7 @@ struct qamd_u8_query {
     float alpha = 0.0f, offset = 0.0f;  // of the store the query was (or will be) encoded for
     int distance = 0, invert = 0;
     bool rotated = false;  // of a rotated store: the values are rotated before they are encoded
+    bool four_bit = false; // of a 4-bit store: 16 levels, rounded to nearest
     mutable std::atomic<bool> deferred{false};
     mutable std::mutex encode_mu;  // two threads may consume one deferred query
     bool pooled = false;     // buf came from / goes back to the query buffer cache

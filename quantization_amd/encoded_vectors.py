@@ -26,6 +26,14 @@ class DistanceType(enum.IntEnum):
 
 ROTATED = 8  # QAMD_ROTATED: the flag on qamd_vector_parameters.distance_type of a rotated scalar-u8 store
 ROTATION_NAME = "HadamardBlocks"  # what a rotated store's metadata says under "rotation"
+BITS4 = 32  # QAMD_BITS4: the flag on distance_type of a 4-bit scalar-u8 store
+
+
+def check_bits(bits) -> bool:
+    """Whether `bits` (8, the default, or 4) asks for a 4-bit scalar-u8 store."""
+    if bits not in (8, 4):
+        raise EncodingError(_lib.ERR_ARGUMENTS, f"bits must be 8 or 4, not {bits!r}")
+    return bits == 4
 
 
 @dataclass
@@ -37,15 +45,17 @@ class VectorParameters:
     distance_type: DistanceType
     invert: bool
 
-    def to_c(self, rotated: bool = False) -> _lib.VectorParametersC:
-        """`rotated`: QAMD_ROTATED or-ed onto the metric - a rotated scalar-u8 store.  The flag lives in
-        the C struct alone: `distance_type` here stays a DistanceType."""
-        return _lib.VectorParametersC(int(self.dim), int(self.count),
-                                      int(self.distance_type) | (ROTATED if rotated else 0), int(bool(self.invert)))
+    def to_c(self, rotated: bool = False, bits: int = 8) -> _lib.VectorParametersC:
+        """`rotated`: QAMD_ROTATED or-ed onto the metric - a rotated scalar-u8 store; `bits` = 4:
+        QAMD_BITS4 - a 4-bit one (3.1y).  The flags live in the C struct alone: `distance_type` here stays a
+        DistanceType."""
+        flags = (ROTATED if rotated else 0) | (BITS4 if check_bits(bits) else 0)
+        return _lib.VectorParametersC(int(self.dim), int(self.count), int(self.distance_type) | flags,
+                                      int(bool(self.invert)))
 
     @staticmethod
     def from_c(c: _lib.VectorParametersC) -> "VectorParameters":
-        return VectorParameters(int(c.dim), int(c.count), DistanceType(c.distance_type & ~ROTATED), bool(c.invert))
+        return VectorParameters(int(c.dim), int(c.count), DistanceType(c.distance_type & ~(ROTATED | BITS4)), bool(c.invert))
 
 
 class EncodingError(Exception):
