@@ -9,9 +9,9 @@
 // offsets[count] f32.  Same 772 algorithmic bytes per scored row; every code load is an
 // aligned 16-byte `global_load_dwordx4`.  Dot / L2 stores also keep a packed scan image of the
 // codes at 7 bits each, in blocks of 64 rows (u8_internal.hpp, build_packed), which their
-// single-query scans read with a row per lane (u8_scan_blocked_kernel): 676 instead of 772 bytes
+// single-query scans read with a row per lane (u8_scan_image_kernel<Image7>): 676 instead of 772 bytes
 // per row at dim 768.  A 4-bit store (QAMD_BITS4, DESIGN 3.1y: codes 0..15, rounded to nearest) keeps a nibble image in its
-// place, two codes per byte, read by u8_scan_nibble_kernel: 388 bytes per row.
+// place, two codes per byte, read by the same kernel as Image4: 388 bytes per row.
 //
 // Scan mapping of the byte codes (HBM-bound integer work, no MFMA): a row is read by G = min(16, pow2(chunks))
 // adjacent lanes, 16 B per lane per iteration, so one wave-load covers 64/G consecutive rows
@@ -276,34 +276,116 @@ __global__ __launch_bounds__(kScanBlock) void u8_scan_kernel(
     }
 }
 
-// ------------------------------------------------------------------------------ blocked scan of the packed image
-// The scan of a Dot / L2 store that has a packed image (u8_internal.hpp, build_packed).  The image keeps P = rc - rc / 8
-// chunks per row: chunk j has chunk j's codes in bits 0..6 and, in bit 7, bit plane j % 7 of extra chunk P + j / 7
-// (j < 7 * (rc / 8)); the last rc % 8 chunks carry no plane.  Rows lie in blocks of kPackBlockRows = 64: chunk j of the
-// 64 rows of block b is the kilobyte at 16-byte index (b * P + j) * 64, one chunk per row.
+// ------------------------------------------------------------------------------ blocked scan of a scan image
+// The scan of a Dot / L2 store that has a scan image (u8_internal.hpp, build_packed): P chunks per row instead of the rc
+// chunks of byte codes, in a format IMG (Image7, Image4 below).  Rows lie in blocks of kPackBlockRows = 64: chunk j of
+// the 64 rows of block b is the kilobyte at 16-byte index (b * P + j) * 64, one chunk per row.
 //
 // Mapping: `split` (1, 2, 4, 8) waves per block, lane l owns row 64 * b + l.  Every wave-load is one whole, 1 KB-aligned
 // kilobyte (eight 128-byte lines, each requested once); no lane is ever past a row end, so one instantiation serves
-// every rc from 8 to 128.  The query chunks of a load are the same for all 64 lanes: they are read at wave-uniform
-// addresses (scalar loads through the constant cache) and occupy no vector register.  The row is walked in groups of 7
-// chunks that share one extra chunk, so the plane shift is a constant of the unrolled group:
-//   dot(v & 0x7F.., q_j) + (dot(v & 0x80.., q_extra) >> (7 - j % 7))
-// (the second dot is a multiple of 128 << plane).  Same exact integer as the byte codes give, added in another order;
-// no cross-lane reduction.  One group (7 loads, 28 VGPRs) is in flight per lane: a chunk's registers are refilled from
-// the next group right behind their last use.  40 VGPRs, 8 waves per SIMD; two groups in flight (56 VGPRs) do not fit
-// the 64 registers that 8 waves allow.
+// every rc up to 128.  The query chunks of a load are the same for all 64 lanes: they are read at wave-uniform
+// addresses (scalar loads through the constant cache) and occupy no vector register.  Same exact integer as the byte
+// codes give, added in another order; no cross-lane reduction.  The row is walked in whole groups of IMG::R chunks -
+// IMG::init says how many - and then one rest group of the chunks left.  One group (R loads, 4 R VGPRs) is in flight
+// per lane: a chunk's registers are refilled from the next group right behind their last use.  8 waves per SIMD; two
+// groups in flight do not fit the 64 registers that 8 waves allow.
 // split > 1 (stores too small to fill the GPU with one wave per block): the waves of a block take contiguous shares of
 // the groups, their partial integer sums meet in LDS behind one barrier and the first wave finishes the rows.
+//
+// A format carries what differs: R; init(P, aux) -> whole groups; group(qcodes, g) before the R calls full(w, i) of
+// whole group g; rest_group(qcodes, c0) before the calls rest(w, c0, i) of the chunks from c0 on; sum().  For the pack
+// kernel (u8_pack_image_kernel) it has chunk(), the 16 bytes of image chunk j of a row, which also gathers the bits of
+// the code chunks it read, and kNoCode, the bits no code of the format has.
 constexpr uint32_t kPackBlockRows = 64;
 constexpr uint32_t kPackBlockChunk = kPackBlockRows;  // uint4 between two chunks of one row
 
 __device__ __forceinline__ uint4 and16(const uint4 &v, uint32_t m) { return make_uint4(v.x & m, v.y & m, v.z & m, v.w & m); }
+__device__ __forceinline__ uint32_t or16(const uint4 &v) { return v.x | v.y | v.z | v.w; }
 
-template <bool FILTER, int EPI = EPI_POINT>
-__global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void u8_scan_blocked_kernel(
+// 7-bit image: P = rc - rc / 8 chunks, aux = n_extra = rc / 8.  Chunk j has chunk j's codes in bits 0..6 and, in bit 7,
+// bit plane j % 7 of extra chunk P + j / 7 (j < 7 * n_extra); the last rc % 8 chunks carry no plane and are the rest
+// group.  A whole group is the 7 chunks that share one extra chunk, so the plane shift is a constant of the unrolled
+// group and the extra query chunk is loaded once per group:
+//   dot(v & 0x7F.., q_j) + (dot(v & 0x80.., q_extra) >> (7 - j % 7))
+// (the second dot is a multiple of 128 << plane).  28 VGPRs in flight, 40 in all.
+struct Image7 {
+    static constexpr int R = 7;
+    static constexpr uint32_t kNoCode = 0x80808080u;
+    uint32_t pchunks, acc = 0;
+    const uint4 *q;
+    uint4 qx;
+    __device__ __forceinline__ uint32_t init(uint32_t p, uint32_t n_extra) {
+        pchunks = p;
+        return n_extra;
+    }
+    __device__ __forceinline__ void group(const uint4 *qcodes, uint32_t g) {
+        q = qcodes + 7 * g;
+        qx = qcodes[pchunks + g];
+    }
+    __device__ __forceinline__ void full(const uint4 &w, int i) {
+        acc = dot16(and16(w, 0x7F7F7F7Fu), q[i], acc) + (dot16(and16(w, 0x80808080u), qx, 0) >> (7 - i));
+    }
+    __device__ __forceinline__ void rest_group(const uint4 *qcodes, uint32_t c0) { q = qcodes + c0; }
+    __device__ __forceinline__ void rest(const uint4 &w, uint32_t, int i) { acc = dot16(and16(w, 0x7F7F7F7Fu), q[i], acc); }  // bit 7 is zero
+    __device__ __forceinline__ uint32_t sum() const { return acc; }
+    static __device__ __forceinline__ uint4 chunk(const uint4 *row, uint32_t j, uint32_t rc, uint32_t p, uint32_t &seen) {
+        uint4 w = row[j];
+        seen |= or16(w);
+        w = and16(w, 0x7F7F7F7Fu);
+        if (j < 7 * (rc - p)) {
+            const uint4 x = row[p + j / 7];
+            const uint32_t b = j % 7;
+            seen |= or16(x);
+            w = make_uint4(w.x | ((x.x >> b) & 0x01010101u) << 7, w.y | ((x.y >> b) & 0x01010101u) << 7,
+                           w.z | ((x.z >> b) & 0x01010101u) << 7, w.w | ((x.w >> b) & 0x01010101u) << 7);
+        }
+        return w;
+    }
+};
+
+// Nibble image of a 4-bit store: P = ceil(rc / 2) chunks, aux = rc.  Byte b of chunk j =
+// codes[32 j + b] | codes[32 j + 16 + b] << 4.  Per image chunk
+//   lo += dot(v & 0x0F.., q[2j]),  hi += dot(v & 0xF0.., q[2j + 1])
+// and the row's sum is lo + (hi >> 4): hi is a multiple of 16 and at most 240 * 15 * 2048 < 2^23, so the shift is
+// exact and happens once per wave.  The n_full = rc / 2 chunks with two code chunks each are walked in groups of R;
+// what is left - fewer than R full chunks and, for an odd rc, the last chunk, whose high nibbles are zero and whose
+// second query chunk does not exist and is not read - is the rest group.  R = 8: 32 VGPRs in flight, 45 in all (DESIGN
+// 3.1y has the compiler's resource report).
+struct Image4 {
+    static constexpr int R = 8;
+    static constexpr uint32_t kNoCode = 0xF0F0F0F0u;
+    uint32_t n_full, lo = 0, hi = 0;
+    const uint4 *q;
+    __device__ __forceinline__ uint32_t init(uint32_t, uint32_t row_chunks) {
+        n_full = row_chunks / 2;
+        return n_full / R;
+    }
+    __device__ __forceinline__ void group(const uint4 *qcodes, uint32_t g) { q = qcodes + 2 * R * g; }
+    __device__ __forceinline__ void full(const uint4 &w, int i) {
+        lo = dot16(and16(w, 0x0F0F0F0Fu), q[2 * i], lo);
+        hi = dot16(and16(w, 0xF0F0F0F0u), q[2 * i + 1], hi);
+    }
+    __device__ __forceinline__ void rest_group(const uint4 *qcodes, uint32_t c0) { q = qcodes + 2 * c0; }
+    __device__ __forceinline__ void rest(const uint4 &w, uint32_t c0, int i) {
+        lo = dot16(and16(w, 0x0F0F0F0Fu), q[2 * i], lo);
+        if (c0 + i < n_full) hi = dot16(and16(w, 0xF0F0F0F0u), q[2 * i + 1], hi);
+    }
+    __device__ __forceinline__ uint32_t sum() const { return lo + (hi >> 4); }
+    static __device__ __forceinline__ uint4 chunk(const uint4 *row, uint32_t j, uint32_t rc, uint32_t, uint32_t &seen) {
+        const uint4 a = row[2 * j];
+        const uint4 b = 2 * j + 1 < rc ? row[2 * j + 1] : make_uint4(0, 0, 0, 0);
+        seen |= or16(a) | or16(b);
+        return make_uint4((a.x & 0x0F0F0F0Fu) | ((b.x & 0x0F0F0F0Fu) << 4), (a.y & 0x0F0F0F0Fu) | ((b.y & 0x0F0F0F0Fu) << 4),
+                          (a.z & 0x0F0F0F0Fu) | ((b.z & 0x0F0F0F0Fu) << 4), (a.w & 0x0F0F0F0Fu) | ((b.w & 0x0F0F0F0Fu) << 4));
+    }
+};
+
+template <class IMG, bool FILTER, int EPI = EPI_POINT>
+__global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void u8_scan_image_kernel(
     const uint4 *__restrict__ image, const float *__restrict__ offsets, const uint4 *__restrict__ qcodes,
-    const float *__restrict__ q_off_p, float multiplier, uint32_t n_rows, uint32_t pchunks, uint32_t n_extra,
+    const float *__restrict__ q_off_p, float multiplier, uint32_t n_rows, uint32_t pchunks, uint32_t aux,
     uint32_t split, float *__restrict__ out, TopkFilter filt, float diff) {
+    constexpr int R = IMG::R;
     __shared__ uint32_t partial[kScanBlock];
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -311,8 +393,9 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     const uint64_t block = (uint64_t)blockIdx.x * ((kScanBlock / 64) / split) + wave / split;
     const uint64_t row = block * kPackBlockRows + lane;
     const bool live = block * kPackBlockRows < n_rows;  // wave-uniform; offsets[] and the image are padded past every block
-    // the groups of a row: n_extra groups of 7 chunks with a plane, then one of the n_rest chunks without
-    const uint32_t n_rest = pchunks - 7 * n_extra, n_groups = n_extra + (n_rest ? 1 : 0);
+    // the groups of a row: n_ring whole groups of R chunks, then one of the n_rest chunks left
+    IMG img;
+    const uint32_t n_ring = img.init(pchunks, aux), n_rest = pchunks - R * n_ring, n_groups = n_ring + (n_rest ? 1 : 0);
     const uint32_t g_begin = live ? n_groups * part / split : 0, g_end = live ? n_groups * (part + 1) / split : 0;
     // chunk c of the block: a wave-uniform base plus the lane's 16 bytes
     const uint4 *blk = image + block * pchunks * kPackBlockChunk;
@@ -320,109 +403,17 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     auto chunk_ptr = [&](uint32_t c) {
         return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(blk + (uint64_t)c * kPackBlockChunk) + lane16);
     };
-    // this wave's full groups [g_begin, gf_end) and whether the rest group is in its share
-    const uint32_t gf_end = g_end < n_extra ? g_end : n_extra;
-    const bool has_rest = g_end > n_extra;
-
-    uint4 v[7];
-    uint32_t acc = 0;
-    // adds full group g, held in v; REFILL: each chunk's registers are reloaded from group g + 1 behind their last use
-    auto eat = [&](uint32_t g, auto refill) {
-        const uint4 *q = qcodes + 7 * g;
-        const uint4 qx = qcodes[pchunks + g];
-#pragma unroll
-        for (int i = 0; i < 7; i++) {
-            const uint4 w = v[i];
-            acc = dot16(and16(w, 0x7F7F7F7Fu), q[i], acc) + (dot16(and16(w, 0x80808080u), qx, 0) >> (7 - i));
-            if (decltype(refill)::value) {  // pinned here, so that the load reuses the chunk's registers
-                __builtin_amdgcn_sched_barrier(0);
-                v[i] = ld_nt(chunk_ptr(7 * (g + 1) + i));
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
-    if (g_begin < gf_end) {
-#pragma unroll
-        for (int i = 0; i < 7; i++) v[i] = ld_nt(chunk_ptr(7 * g_begin + i));
-    }
-    const float v_off = offsets[row];
-    const float q_off = *q_off_p;
-    uint32_t pivot = 0;
-    if (FILTER) pivot = *filt.pivot_key;
-    if (g_begin < gf_end) {
-        for (uint32_t g = g_begin; g + 1 < gf_end; g++) eat(g, std::true_type{});
-        eat(gf_end - 1, std::false_type{});
-    }
-    if (has_rest) {  // the chunks that carry no plane: bit 7 is zero
-        const uint4 *q = qcodes + 7 * n_extra;
-#pragma unroll
-        for (int i = 0; i < 7; i++)
-            if ((uint32_t)i < n_rest) v[i] = ld_nt(chunk_ptr(7 * n_extra + i));
-#pragma unroll
-        for (int i = 0; i < 7; i++)
-            if ((uint32_t)i < n_rest) acc = dot16(and16(v[i], 0x7F7F7F7Fu), q[i], acc);
-    }
-    if (split > 1) {
-        partial[threadIdx.x] = acc;
-        __syncthreads();
-        if (part == 0)
-            for (uint32_t p = 1; p < split; p++) acc += partial[threadIdx.x + 64 * p];
-    }
-    if (part == 0 && row < n_rows) {
-        const float score = epilogue(multiplier, acc, q_off, v_off, EPI == EPI_POINT ? 0.0f : diff, EPI);
-        if (FILTER) topk_offer(filt, pivot, score, (uint32_t)row);
-        else __builtin_nontemporal_store(score, out + row);
-    }
-}
-
-// ------------------------------------------------------------------------------ blocked scan of the nibble image
-// The scan of a 4-bit store that has a nibble image (u8_internal.hpp, build_packed): P4 = ceil(rc / 2)
-// chunks per row, byte b of chunk j = codes[32 j + b] | codes[32 j + 16 + b] << 4, in u8_scan_blocked_kernel's blocks of
-// 64 rows - and that kernel's mapping: `split` waves per block, a row per lane, every wave-load one aligned kilobyte, the
-// query's byte-code chunks read at wave-uniform addresses.  Per image chunk
-//   lo += dot(v & 0x0F.., q[2j]),  hi += dot(v & 0xF0.., q[2j + 1])
-// and the row's sum is lo + (hi >> 4): hi is a multiple of 16 and at most 240 * 15 * 2048 < 2^23, so the shift is
-// exact and happens once per wave.  The n_full = rc / 2 chunks with two code chunks each are walked in groups of
-// kNibbleRing; a group's registers are refilled from the next group behind their last use.  What is left - fewer than
-// kNibbleRing full chunks and, for an odd rc, the last chunk, whose high nibbles are zero and whose second query chunk
-// does not exist and is not read - is the rest group.  kNibbleRing = 8: 32 VGPRs in flight (DESIGN 3.1y has the
-// compiler's resource report).
-constexpr int kNibbleRing = 8;
-
-template <bool FILTER, int EPI = EPI_POINT>
-__global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void u8_scan_nibble_kernel(
-    const uint4 *__restrict__ image, const float *__restrict__ offsets, const uint4 *__restrict__ qcodes,
-    const float *__restrict__ q_off_p, float multiplier, uint32_t n_rows, uint32_t pchunks, uint32_t row_chunks,
-    uint32_t split, float *__restrict__ out, TopkFilter filt, float diff) {
-    constexpr int R = kNibbleRing;
-    __shared__ uint32_t partial[kScanBlock];
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t part = wave & (split - 1);
-    const uint64_t block = (uint64_t)blockIdx.x * ((kScanBlock / 64) / split) + wave / split;
-    const uint64_t row = block * kPackBlockRows + lane;
-    const bool live = block * kPackBlockRows < n_rows;  // wave-uniform; offsets[] and the image are padded past every block
-    // the groups of a row: n_full / R groups of R chunks with both nibbles, then one of the n_rest chunks left
-    const uint32_t n_full = row_chunks / 2, n_ring = n_full / R, n_rest = pchunks - R * n_ring;
-    const uint32_t n_groups = n_ring + (n_rest ? 1 : 0);
-    const uint32_t g_begin = live ? n_groups * part / split : 0, g_end = live ? n_groups * (part + 1) / split : 0;
-    const uint4 *blk = image + block * pchunks * kPackBlockChunk;
-    const uint32_t lane16 = lane * 16;
-    auto chunk_ptr = [&](uint32_t c) {
-        return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(blk + (uint64_t)c * kPackBlockChunk) + lane16);
-    };
+    // this wave's whole groups [g_begin, gf_end) and whether the rest group is in its share
     const uint32_t gf_end = g_end < n_ring ? g_end : n_ring;
     const bool has_rest = g_end > n_ring;
 
     uint4 v[R];
-    uint32_t lo = 0, hi = 0;
+    // adds whole group g, held in v; REFILL: each chunk's registers are reloaded from group g + 1 behind their last use
     auto eat = [&](uint32_t g, auto refill) {
-        const uint4 *q = qcodes + 2 * R * g;
+        img.group(qcodes, g);
 #pragma unroll
         for (int i = 0; i < R; i++) {
-            const uint4 w = v[i];
-            lo = dot16(and16(w, 0x0F0F0F0Fu), q[2 * i], lo);
-            hi = dot16(and16(w, 0xF0F0F0F0u), q[2 * i + 1], hi);
+            img.full(v[i], i);
             if (decltype(refill)::value) {  // pinned here, so that the load reuses the chunk's registers
                 __builtin_amdgcn_sched_barrier(0);
                 v[i] = ld_nt(chunk_ptr(R * (g + 1) + i));
@@ -442,21 +433,17 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8
         for (uint32_t g = g_begin; g + 1 < gf_end; g++) eat(g, std::true_type{});
         eat(gf_end - 1, std::false_type{});
     }
-    if (has_rest) {  // chunks R * n_ring .. pchunks - 1; the last has no high half when row_chunks is odd
+    if (has_rest) {
         const uint32_t c0 = R * n_ring;
-        const uint4 *q = qcodes + 2 * c0;
+        img.rest_group(qcodes, c0);
 #pragma unroll
         for (int i = 0; i < R; i++)
             if ((uint32_t)i < n_rest) v[i] = ld_nt(chunk_ptr(c0 + i));
 #pragma unroll
-        for (int i = 0; i < R; i++) {
-            if ((uint32_t)i < n_rest) {
-                lo = dot16(and16(v[i], 0x0F0F0F0Fu), q[2 * i], lo);
-                if (c0 + i < n_full) hi = dot16(and16(v[i], 0xF0F0F0F0u), q[2 * i + 1], hi);
-            }
-        }
+        for (int i = 0; i < R; i++)
+            if ((uint32_t)i < n_rest) img.rest(v[i], c0, i);
     }
-    uint32_t acc = lo + (hi >> 4);
+    uint32_t acc = img.sum();
     if (split > 1) {
         partial[threadIdx.x] = acc;
         __syncthreads();
@@ -1555,82 +1542,24 @@ __global__ __launch_bounds__(kBlock) void join_rows_kernel(const uint32_t *__res
     }
 }
 
-// The packed scan image (u8_internal.hpp) of rows [0, n_rows): one thread per (row, packed chunk j).  Chunk j keeps
-// chunk j's codes in bits 0..6 and bit plane j % 7 of chunk P + j / 7 in bit 7, and goes to its place in the row's
-// block of kPackBlockRows rows.  A code above 127 anywhere in the rows (bytes another producer wrote: from_rows, load)
-// sets *bad, and the image is then dropped.
-__global__ __launch_bounds__(kBlock) void u8_pack7_kernel(const uint4 *__restrict__ codes, uint64_t n_rows,
-                                                          uint32_t row_chunks, uint32_t pchunks, uint32_t n_extra,
-                                                          uint4 *__restrict__ packed, uint32_t *__restrict__ bad) {
+// The scan image (u8_internal.hpp; format IMG: Image7, Image4) of rows [r0, r0 + n_rows): one thread per (row, image
+// chunk j), which writes IMG::chunk to its place in the row's block of kPackBlockRows rows.  Every (row, chunk) slot is 16
+// bytes of its own, so the slots of a block's other rows stay as they are (upsert).  `bad` (builders; null for upsert,
+// whose rows come from the store's own encoder): a code with a bit of IMG::kNoCode anywhere in the rows (bytes another
+// producer wrote: from_rows, load) sets it, and the image is then dropped.
+template <class IMG>
+__global__ __launch_bounds__(kBlock) void u8_pack_image_kernel(const uint4 *__restrict__ codes, uint64_t r0, uint64_t n_rows,
+                                                               uint32_t row_chunks, uint32_t pchunks,
+                                                               uint4 *__restrict__ packed, uint32_t *__restrict__ bad) {
     const uint64_t total = n_rows * pchunks, stride = (uint64_t)gridDim.x * kBlock;
-    uint32_t high = 0;
-    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
-        const uint64_t r = t / pchunks;
-        const uint32_t j = (uint32_t)(t - r * pchunks);
-        const uint4 *row = codes + r * row_chunks;
-        const uint4 a = row[j];
-        uint32_t w[4] = {a.x & 0x7F7F7F7Fu, a.y & 0x7F7F7F7Fu, a.z & 0x7F7F7F7Fu, a.w & 0x7F7F7F7Fu};
-        high |= a.x | a.y | a.z | a.w;
-        if (j < 7 * n_extra) {
-            const uint4 x = row[pchunks + j / 7];
-            const uint32_t b = j % 7;
-            high |= x.x | x.y | x.z | x.w;
-            w[0] |= ((x.x >> b) & 0x01010101u) << 7;
-            w[1] |= ((x.y >> b) & 0x01010101u) << 7;
-            w[2] |= ((x.z >> b) & 0x01010101u) << 7;
-            w[3] |= ((x.w >> b) & 0x01010101u) << 7;
-        }
-        packed[((r / kPackBlockRows) * pchunks + j) * kPackBlockRows + r % kPackBlockRows] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    if (high & 0x80808080u) atomicOr(bad, 1u);
-}
-
-// u8_pack7_kernel for rows [r0, r0 + n_rows) of a store that has an image (upsert): every (row, chunk) slot is 16 bytes of
-// its own, so the slots of the block's other rows stay as they are.  The rows come from the store's own encoder: no code
-// is above 127, and nothing is reported.
-__global__ __launch_bounds__(kBlock) void u8_pack7_range_kernel(const uint4 *__restrict__ codes, uint64_t r0, uint64_t n_rows,
-                                                                uint32_t row_chunks, uint32_t pchunks, uint32_t n_extra,
-                                                                uint4 *__restrict__ packed) {
-    const uint64_t total = n_rows * pchunks, stride = (uint64_t)gridDim.x * kBlock;
+    uint32_t seen = 0;
     for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
         const uint64_t r = r0 + t / pchunks;
         const uint32_t j = (uint32_t)(t % pchunks);
-        const uint4 *row = codes + r * row_chunks;
-        const uint4 a = row[j];
-        uint32_t w[4] = {a.x & 0x7F7F7F7Fu, a.y & 0x7F7F7F7Fu, a.z & 0x7F7F7F7Fu, a.w & 0x7F7F7F7Fu};
-        if (j < 7 * n_extra) {
-            const uint4 x = row[pchunks + j / 7];
-            const uint32_t b = j % 7;
-            w[0] |= ((x.x >> b) & 0x01010101u) << 7;
-            w[1] |= ((x.y >> b) & 0x01010101u) << 7;
-            w[2] |= ((x.z >> b) & 0x01010101u) << 7;
-            w[3] |= ((x.w >> b) & 0x01010101u) << 7;
-        }
-        packed[((r / kPackBlockRows) * pchunks + j) * kPackBlockRows + r % kPackBlockRows] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-// The nibble image (u8_internal.hpp) of rows [r0, r0 + n_rows) of a 4-bit store: one thread per (row, image chunk j),
-// code chunk 2j in the low nibbles and code chunk 2j + 1 - zeros when the row has none - in the high ones.  `bad`
-// (builders; null for upsert, whose rows come from the store's own encoder): a code above 15 anywhere in the rows
-// (bytes another producer wrote: from_rows, load) sets it, and the image is then dropped.
-__global__ __launch_bounds__(kBlock) void u8_pack4_kernel(const uint4 *__restrict__ codes, uint64_t r0, uint64_t n_rows,
-                                                          uint32_t row_chunks, uint32_t pchunks, uint4 *__restrict__ packed,
-                                                          uint32_t *__restrict__ bad) {
-    const uint64_t total = n_rows * pchunks, stride = (uint64_t)gridDim.x * kBlock;
-    uint32_t high = 0;
-    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
-        const uint64_t r = r0 + t / pchunks;
-        const uint32_t j = (uint32_t)(t % pchunks);
-        const uint4 *row = codes + r * row_chunks;
-        const uint4 a = row[2 * j];
-        const uint4 b = 2 * j + 1 < row_chunks ? row[2 * j + 1] : make_uint4(0, 0, 0, 0);
-        high |= a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w;
         packed[((r / kPackBlockRows) * pchunks + j) * kPackBlockRows + r % kPackBlockRows] =
-            make_uint4((a.x & 0x0F0F0F0Fu) | ((b.x & 0x0F0F0F0Fu) << 4), (a.y & 0x0F0F0F0Fu) | ((b.y & 0x0F0F0F0Fu) << 4),
-                       (a.z & 0x0F0F0F0Fu) | ((b.z & 0x0F0F0F0Fu) << 4), (a.w & 0x0F0F0F0Fu) | ((b.w & 0x0F0F0F0Fu) << 4));
+            IMG::chunk(codes + r * row_chunks, j, row_chunks, pchunks, seen);
     }
-    if (bad && (high & 0xF0F0F0F0u)) atomicOr(bad, 1u);
+    if (bad && (seen & IMG::kNoCode)) atomicOr(bad, 1u);
 }
 
 int grid_for(uint64_t work_items, uint64_t per_block, int blocks_per_cu) {
@@ -1713,52 +1642,64 @@ qamd_status alloc_store(qamd_u8 *h) {
     return QAMD_OK;
 }
 
-// Builds the store's packed scan image (u8_internal.hpp) from its byte codes; run at the end of every builder.  Only
-// the Dot / L2 scans of lane mode 0 read it, so L1 stores, stores of fewer than 8 chunks (no whole extra chunk) and of
-// more than 128 (the generic kernel) get none.  It costs 7/8 of the code bytes in HBM: it is skipped when it would
-// leave less free HBM than its own size, and a failed allocation only leaves the store on its byte codes.  So does
-// a code above 127 (rows another producer wrote).  A 4-bit store gets a nibble image instead (half the code bytes; from
-// 2 chunks on; a code above 15 drops it).
+// The scan image a store of this shape can have (u8_internal.hpp): which format, how many chunks per row, and the
+// format's second kernel argument (Image7: the extra chunks, Image4: the row's code chunks).  Only the Dot / L2 scans of
+// lane mode 0 read an image, so L1 stores and stores of more than 128 chunks (the generic kernel) have none; nor do
+// 7-bit stores of fewer than 8 chunks (no whole extra chunk) and 4-bit stores of fewer than 2.
+U8Image u8_image_of(uint32_t rc, bool four_bit, int distance) {
+    if (distance == QAMD_L1 || rc > 128 || rc < (four_bit ? 2u : 8u)) return U8Image{};
+    if (four_bit) return U8Image{U8_IMAGE_NIBBLE, (rc + 1) / 2, rc};
+    return U8Image{U8_IMAGE_7BIT, rc - rc / 8, rc / 8};
+}
+
+// Writes rows [r0, r0 + n_rows) of the store's image from their byte codes; `bad`: u8_pack_image_kernel.
+qamd_status launch_pack(const qamd_u8 *h, uint64_t r0, uint64_t n_rows, uint32_t *bad, hipStream_t s) {
+    const auto kernel = h->image.kind == U8_IMAGE_NIBBLE ? u8_pack_image_kernel<Image4> : u8_pack_image_kernel<Image7>;
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n_rows * h->image.chunks, kBlock, 8)), dim3(kBlock), 0, s, h->codes.as<uint4>(),
+                       r0, n_rows, h->row_chunks, h->image.chunks, h->packed.as<uint4>(), bad);
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
+
+// Builds the store's scan image from its byte codes; run at the end of every builder.  The 7-bit image costs 7/8 of the
+// code bytes in HBM, the nibble image of a 4-bit store half: it is skipped when it would leave less free
+// HBM than its own size, and a failed allocation only leaves the store on its byte codes.  So does a code the format
+// cannot hold (rows another producer wrote).
 qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
     h->packed.release();
     h->packed_rows.release();
-    h->packed_chunks = 0;
-    h->packed_nibble = false;
-    // A 4-bit store gets the nibble image in the 7-bit one's place, from 2 chunks on, under the same rules.
-    const bool nibble = h->four_bit;
-    const uint32_t rc = h->row_chunks, n_extra = nibble ? 0 : rc / 8, pchunks = nibble ? (rc + 1) / 2 : rc - n_extra;
-    if (!u8_packed_allowed() || h->count == 0 || rc < (nibble ? 2u : 8u) || rc > 128 ||
-        h->meta.vector_parameters.distance_type == QAMD_L1)
-        return QAMD_OK;
-    const uint64_t bytes = h->padded_rows * pchunks * 16;
+    h->image = U8Image{};
+    const U8Image im = u8_image_of(h->row_chunks, h->four_bit, h->meta.vector_parameters.distance_type);
+    if (!u8_packed_allowed() || h->count == 0 || !im.kind) return QAMD_OK;
+    const uint64_t bytes = h->padded_rows * im.chunks * 16;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 2 * bytes) {
         (void)hipGetLastError();
         return QAMD_OK;
     }
-    DevBuf img, bad;
+    DevBuf bad;
     const std::string err = last_error();
     // rows of a block are interleaved: the padding rows of the last block are zeroed with it, before it is written
-    if (img.alloc_zero_tail(bytes, h->count / kPackBlockRows * kPackBlockRows * pchunks * 16) != QAMD_OK || bad.alloc(sizeof(uint32_t), true) != QAMD_OK) {
+    if (h->packed.alloc_zero_tail(bytes, h->count / kPackBlockRows * kPackBlockRows * im.chunks * 16) != QAMD_OK ||
+        bad.alloc(sizeof(uint32_t), true) != QAMD_OK) {
         (void)hipGetLastError();  // an out-of-memory here is not the build's failure
         last_error() = err;
+        h->packed.release();
         return QAMD_OK;
     }
-    if (nibble)
-        hipLaunchKernelGGL(u8_pack4_kernel, dim3(grid_for(h->count * pchunks, kBlock, 8)), dim3(kBlock), 0, s,
-                           h->codes.as<uint4>(), (uint64_t)0, h->count, rc, pchunks, img.as<uint4>(), bad.as<uint32_t>());
-    else
-        hipLaunchKernelGGL(u8_pack7_kernel, dim3(grid_for(h->count * pchunks, kBlock, 8)), dim3(kBlock), 0, s,
-                           h->codes.as<uint4>(), h->count, rc, pchunks, n_extra, img.as<uint4>(), bad.as<uint32_t>());
-    QAMD_HIP(hipGetLastError());
-    uint32_t high = 0;
-    QAMD_HIP(hipMemcpyAsync(&high, bad.ptr, sizeof(high), hipMemcpyDeviceToHost, s));
-    QAMD_HIP(hipStreamSynchronize(s));
-    if (high) return QAMD_OK;
-    h->packed = std::move(img);
-    h->packed_chunks = pchunks;
-    h->packed_nibble = nibble;
-    return QAMD_OK;
+    h->image = im;
+    uint32_t high = 1;  // the store keeps an image that was written and found clean, and no other
+    const qamd_status st = [&]() -> qamd_status {
+        QAMD_TRY(launch_pack(h, 0, h->count, bad.as<uint32_t>(), s));
+        QAMD_HIP(hipMemcpyAsync(&high, bad.ptr, sizeof(high), hipMemcpyDeviceToHost, s));
+        QAMD_HIP(hipStreamSynchronize(s));
+        return QAMD_OK;
+    }();
+    if (st != QAMD_OK || high) {
+        h->packed.release();
+        h->image = U8Image{};
+    }
+    return st;
 }
 
 // The epilogue of a whole-store launch: an encoded query (EPI_POINT, the default) or, for score_internal against the whole
@@ -1771,6 +1712,17 @@ struct ScanEpi {
 // Rows a whole-store launch covers.
 inline uint64_t scan_rows(const qamd_u8 *h, const ScanEpi &e) { return e.rows ? e.rows : h->count; }
 
+// A run-time flag of a whole-store launch as a compile-time constant: f gets std::true_type / std::false_type, or the
+// EPI_* of e.mode as a std::integral_constant, and names the kernel instantiation with it.
+template <class F> void with_bool(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F> void with_epi(int mode, F &&f) {
+    if (mode == EPI_POINT) f(std::integral_constant<int, EPI_POINT>{});
+    else f(std::integral_constant<int, EPI_INTERNAL>{});
+}
+
 template <bool IS_L1> struct ScanLaunch {
     template <int G, int ITERS, int UNROLL>
     static void go(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt, hipStream_t s,
@@ -1778,25 +1730,15 @@ template <bool IS_L1> struct ScanLaunch {
         constexpr int TILE = (64 / G) * UNROLL;
         const uint64_t waves = (scan_rows(h, e) + TILE - 1) / TILE;  // one wave per tile
         const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
-        const bool exact = h->row_chunks == (uint32_t)(G * ITERS);
-#define QAMD_U8_GO_AS(EX, FI, EPI)                                                                              \
-    hipLaunchKernelGGL((u8_scan_kernel<G, ITERS, UNROLL, IS_L1, EX, FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, \
-                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)scan_rows(h, e), \
-                       h->row_chunks, out, filt ? *filt : TopkFilter{}, e.diff)
-#define QAMD_U8_GO(EX, FI)                               \
-    do {                                                 \
-        if (e.mode == EPI_POINT) QAMD_U8_GO_AS(EX, FI, EPI_POINT); \
-        else QAMD_U8_GO_AS(EX, FI, EPI_INTERNAL);        \
-    } while (0)
-        if (filt) {
-            if (exact) QAMD_U8_GO(true, true);
-            else QAMD_U8_GO(false, true);
-        } else {
-            if (exact) QAMD_U8_GO(true, false);
-            else QAMD_U8_GO(false, false);
-        }
-#undef QAMD_U8_GO
-#undef QAMD_U8_GO_AS
+        with_bool(h->row_chunks == (uint32_t)(G * ITERS), [&](auto ex) {
+            with_bool(filt != nullptr, [&](auto fi) {
+                with_epi(e.mode, [&](auto epi) {
+                    hipLaunchKernelGGL((u8_scan_kernel<G, ITERS, UNROLL, IS_L1, ex, fi, epi>), dim3(grid), dim3(kScanBlock), 0,
+                                       s, h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,
+                                       (uint32_t)scan_rows(h, e), h->row_chunks, out, filt ? *filt : TopkFilter{}, e.diff);
+                });
+            });
+        });
     }
 };
 
@@ -1810,62 +1752,34 @@ uint32_t blocked_split(uint64_t count) {
     return split;
 }
 
-// The Dot / L2 scan of a store that has a packed image: u8_scan_blocked_kernel over its blocks.
-void launch_scan_blocked(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
-                         hipStream_t s, const ScanEpi &e) {
+// The Dot / L2 scan of a store that has a scan image: u8_scan_image_kernel, in the image's format, over its blocks.
+void launch_scan_image(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
+                       hipStream_t s, const ScanEpi &e) {
     const uint64_t n_rows = scan_rows(h, e);
     const uint32_t split = blocked_split(n_rows), blocks_per_wg = (kScanBlock / 64) / split;
     const uint64_t blocks = (n_rows + kPackBlockRows - 1) / kPackBlockRows;
     const unsigned grid = (unsigned)((blocks + blocks_per_wg - 1) / blocks_per_wg);
     h->last_scan_split.store((int)split, std::memory_order_relaxed);
-#define QAMD_U8_BLOCKED_AS(FI, EPI)                                                                                  \
-    hipLaunchKernelGGL((u8_scan_blocked_kernel<FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, h->packed.as<uint4>(),  \
-                       h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)n_rows, h->packed_chunks,        \
-                       h->row_chunks - h->packed_chunks, split, out, filt ? *filt : TopkFilter{}, e.diff)
-#define QAMD_U8_BLOCKED(FI)                                      \
-    do {                                                         \
-        if (e.mode == EPI_POINT) QAMD_U8_BLOCKED_AS(FI, EPI_POINT); \
-        else QAMD_U8_BLOCKED_AS(FI, EPI_INTERNAL);               \
-    } while (0)
-    if (filt) QAMD_U8_BLOCKED(true);
-    else QAMD_U8_BLOCKED(false);
-#undef QAMD_U8_BLOCKED
-#undef QAMD_U8_BLOCKED_AS
-}
-
-// The Dot / L2 scan of a 4-bit store that has a nibble image: u8_scan_nibble_kernel over the same blocks, the same split.
-void launch_scan_nibble(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
-                        hipStream_t s, const ScanEpi &e) {
-    const uint64_t n_rows = scan_rows(h, e);
-    const uint32_t split = blocked_split(n_rows), blocks_per_wg = (kScanBlock / 64) / split;
-    const uint64_t blocks = (n_rows + kPackBlockRows - 1) / kPackBlockRows;
-    const unsigned grid = (unsigned)((blocks + blocks_per_wg - 1) / blocks_per_wg);
-    h->last_scan_split.store((int)split, std::memory_order_relaxed);
-#define QAMD_U8_NIBBLE_AS(FI, EPI)                                                                                   \
-    hipLaunchKernelGGL((u8_scan_nibble_kernel<FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, h->packed.as<uint4>(),   \
-                       h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)n_rows, h->packed_chunks,        \
-                       h->row_chunks, split, out, filt ? *filt : TopkFilter{}, e.diff)
-#define QAMD_U8_NIBBLE(FI)                                       \
-    do {                                                         \
-        if (e.mode == EPI_POINT) QAMD_U8_NIBBLE_AS(FI, EPI_POINT); \
-        else QAMD_U8_NIBBLE_AS(FI, EPI_INTERNAL);                \
-    } while (0)
-    if (filt) QAMD_U8_NIBBLE(true);
-    else QAMD_U8_NIBBLE(false);
-#undef QAMD_U8_NIBBLE
-#undef QAMD_U8_NIBBLE_AS
+    with_bool(h->image.kind == U8_IMAGE_NIBBLE, [&](auto nibble) {
+        using IMG = std::conditional_t<nibble, Image4, Image7>;
+        with_bool(filt != nullptr, [&](auto fi) {
+            with_epi(e.mode, [&](auto epi) {
+                hipLaunchKernelGGL((u8_scan_image_kernel<IMG, fi, epi>), dim3(grid), dim3(kScanBlock), 0, s,
+                                   h->packed.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)n_rows,
+                                   h->image.chunks, h->image.aux, split, out, filt ? *filt : TopkFilter{}, e.diff);
+            });
+        });
+    });
 }
 
 // Returns false when the store's row size has no templated kernel (caller uses the generic one).
-// The Dot / L2 scans read the packed image when the store has one (its rows are 7/8 as long).
+// The Dot / L2 scans read the scan image when the store has one (its rows are 7/8 or half as long; an L1 store has none).
 template <bool IS_L1>
 bool launch_scan(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, const TopkFilter *filt,
                  hipStream_t s, const ScanEpi &e) {
     using L = ScanLaunch<IS_L1>;
-    const bool packed = !IS_L1 && h->packed_chunks != 0;
-    h->last_scan_packed.store(packed ? (h->packed_nibble ? 2 : 1) : 0, std::memory_order_relaxed);
-    if (packed && h->packed_nibble) return launch_scan_nibble(h, qc, qo, out, filt, s, e), true;
-    if (packed) return launch_scan_blocked(h, qc, qo, out, filt, s, e), true;
+    h->last_scan_packed.store(h->image.kind, std::memory_order_relaxed);
+    if (h->image.kind) return launch_scan_image(h, qc, qo, out, filt, s, e), true;
     const uint32_t rc = h->row_chunks;
     if (rc == 1) return L::template go<1, 1, 4>(h, qc, qo, out, filt, s, e), true;
     if (rc == 2) return L::template go<2, 1, 4>(h, qc, qo, out, filt, s, e), true;
@@ -1889,13 +1803,11 @@ template <bool IS_L1>
 void launch_scan_generic(const qamd_u8 *h, const uint4 *qc, const float *qo, float *out, hipStream_t s, const ScanEpi &e) {
     uint64_t waves = (scan_rows(h, e) + 3) / 4;  // one wave per 4-row tile (non-persistent, see u8_scan_kernel)
     unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
-#define QAMD_U8_GENERIC(EPI)                                                                             \
-    hipLaunchKernelGGL((u8_scan_generic_kernel<IS_L1, EPI>), dim3(grid), dim3(kBlock), 0, s,             \
-                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,         \
-                       (uint32_t)scan_rows(h, e), h->row_chunks, out, e.diff)
-    if (e.mode == EPI_POINT) QAMD_U8_GENERIC(EPI_POINT);
-    else QAMD_U8_GENERIC(EPI_INTERNAL);
-#undef QAMD_U8_GENERIC
+    with_epi(e.mode, [&](auto epi) {
+        hipLaunchKernelGGL((u8_scan_generic_kernel<IS_L1, epi>), dim3(grid), dim3(kBlock), 0, s, h->codes.as<uint4>(),
+                           h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)scan_rows(h, e), h->row_chunks, out,
+                           e.diff);
+    });
 }
 
 template <bool IS_L1> struct SmallLaunch {
@@ -1909,30 +1821,22 @@ template <bool IS_L1> struct SmallLaunch {
             QueryByValue qv;
             memcpy(qv.v, fq->values, (size_t)fq->qdim * 4);
             const qamd_vector_parameters &vp = h->meta.vector_parameters;
-#define QAMD_U8_SMALL_FUSED(EX)                                                                                        \
-    hipLaunchKernelGGL((u8_topk_small_fused_kernel<G, ITERS, IS_L1, EX>), dim3(pl.workgroups), dim3(1024), 0, s,          \
-                       h->codes.as<uint4>(), h->offsets.as<float>(), qv, fq->qdim, (uint32_t)h->meta.actual_dim,         \
-                       h->meta.alpha, h->meta.offset, vp.distance_type, vp.invert, fq->qbuf, h->meta.multiplier,           \
-                       (uint32_t)h->count, h->row_chunks, pl.rows_per_wg, p)
-            if (exact) QAMD_U8_SMALL_FUSED(true);
-            else QAMD_U8_SMALL_FUSED(false);
-#undef QAMD_U8_SMALL_FUSED
+            with_bool(exact, [&](auto ex) {
+                hipLaunchKernelGGL((u8_topk_small_fused_kernel<G, ITERS, IS_L1, ex>), dim3(pl.workgroups), dim3(1024), 0, s,
+                                   h->codes.as<uint4>(), h->offsets.as<float>(), qv, fq->qdim, (uint32_t)h->meta.actual_dim,
+                                   h->meta.alpha, h->meta.offset, vp.distance_type, vp.invert, fq->qbuf, h->meta.multiplier,
+                                   (uint32_t)h->count, h->row_chunks, pl.rows_per_wg, p);
+            });
             QAMD_HIP(hipGetLastError());
             return QAMD_OK;
         }
-#define QAMD_U8_SMALL_AS(EX, EPI)                                                                               \
-    hipLaunchKernelGGL((u8_topk_small_kernel<G, ITERS, IS_L1, EX, EPI>), dim3(pl.workgroups), dim3(1024), 0, s,  \
-                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)h->count, \
-                       h->row_chunks, pl.rows_per_wg, p, e.diff)
-#define QAMD_U8_SMALL(EX)                                        \
-    do {                                                         \
-        if (e.mode == EPI_POINT) QAMD_U8_SMALL_AS(EX, EPI_POINT); \
-        else QAMD_U8_SMALL_AS(EX, EPI_INTERNAL);                 \
-    } while (0)
-        if (exact) QAMD_U8_SMALL(true);
-        else QAMD_U8_SMALL(false);
-#undef QAMD_U8_SMALL
-#undef QAMD_U8_SMALL_AS
+        with_bool(exact, [&](auto ex) {
+            with_epi(e.mode, [&](auto epi) {
+                hipLaunchKernelGGL((u8_topk_small_kernel<G, ITERS, IS_L1, ex, epi>), dim3(pl.workgroups), dim3(1024), 0, s,
+                                   h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,
+                                   (uint32_t)h->count, h->row_chunks, pl.rows_per_wg, p, e.diff);
+            });
+        });
         QAMD_HIP(hipGetLastError());
         return QAMD_OK;
     }
@@ -2061,13 +1965,11 @@ qamd_status scan_ptrs(const qamd_u8 *h, const uint4 *qc, const float *qo, float 
     if (lane_order(h)) {
         uint64_t waves = (scan_rows(h, e) + 3) / 4;
         unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
-#define QAMD_U8_LANES(EPI)                                                                          \
-    hipLaunchKernelGGL((u8_scan_avx2_lanes_kernel<true, EPI>), dim3(grid), dim3(kBlock), 0, s,          \
-                       h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,        \
-                       (uint32_t)scan_rows(h, e), h->row_chunks, out_dev, e.diff)
-        if (e.mode == EPI_POINT) QAMD_U8_LANES(EPI_POINT);
-        else QAMD_U8_LANES(EPI_INTERNAL);
-#undef QAMD_U8_LANES
+        with_epi(e.mode, [&](auto epi) {
+            hipLaunchKernelGGL((u8_scan_avx2_lanes_kernel<true, epi>), dim3(grid), dim3(kBlock), 0, s, h->codes.as<uint4>(),
+                               h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)scan_rows(h, e), h->row_chunks,
+                               out_dev, e.diff);
+        });
     } else if (is_l1) {
         if (!launch_scan<true>(h, qc, qo, out_dev, filt, s, e)) launch_scan_generic<true>(h, qc, qo, out_dev, s, e);
     } else {
@@ -2982,7 +2884,7 @@ qamd_status qamd_u8_topk(const qamd_u8 *h, const qamd_u8_query *q, uint32_t k, i
 void qamd_u8_free(qamd_u8 *h) { delete h; }
 
 uint64_t qamd_u8_scan_bytes_per_row(const qamd_u8 *h) {
-    if (h && h->packed_chunks && h->packed_nibble) return 16ull * h->packed_chunks + 4;  // the nibble image
+    if (h && h->image.kind == U8_IMAGE_NIBBLE) return 16ull * h->image.chunks + 4;  // the nibble image
     return h ? h->meta.actual_dim + 4 : 0;
 }
 
@@ -3218,9 +3120,9 @@ qamd_status u8_grow(qamd_u8 *h, uint64_t cap) {
     DevBuf codes, offsets, packed;
     QAMD_TRY(grow_copy(h->codes, padded * ad, h->count * ad, codes));
     QAMD_TRY(grow_copy(h->offsets, padded * sizeof(float), h->count * sizeof(float), offsets));
-    bool image = h->packed_chunks != 0;
+    bool image = h->image.kind != U8_IMAGE_NONE;
     if (image) {
-        const uint64_t chunk_bytes = (uint64_t)h->packed_chunks * 16;
+        const uint64_t chunk_bytes = (uint64_t)h->image.chunks * 16;
         const std::string err = last_error();
         if (grow_copy(h->packed, padded * chunk_bytes, round_up(h->count, kPackBlockRows) * chunk_bytes, packed) != QAMD_OK) {
             (void)hipGetLastError();  // an out-of-memory here only costs the image
@@ -3232,7 +3134,7 @@ qamd_status u8_grow(qamd_u8 *h, uint64_t cap) {
     h->codes = std::move(codes);  // (the old buffers go through hipFree, which waits for the device)
     h->offsets = std::move(offsets);
     h->packed = std::move(packed);
-    if (!image) h->packed_chunks = 0, h->packed_nibble = false;
+    if (!image) h->image = U8Image{};
     h->packed_rows.release();
     h->capacity = cap;
     h->padded_rows = padded;
@@ -3275,17 +3177,7 @@ qamd_status qamd_u8_upsert(qamd_u8 *h, uint64_t first_row, const float *data, qa
                                    [&](const float *src, uint64_t r, uint64_t nr) {
         return launch_quantize(h, src, nr, first_row + r, h->meta.alpha, h->meta.offset, s);
     }));
-    if (h->packed_chunks && h->packed_nibble) {
-        hipLaunchKernelGGL(u8_pack4_kernel, dim3(grid_for(n_rows * h->packed_chunks, kBlock, 8)), dim3(kBlock), 0, s,
-                           h->codes.as<uint4>(), first_row, n_rows, h->row_chunks, h->packed_chunks, h->packed.as<uint4>(),
-                           (uint32_t *)nullptr);
-        QAMD_HIP(hipGetLastError());
-    } else if (h->packed_chunks) {
-        const uint32_t rc = h->row_chunks, pchunks = h->packed_chunks;
-        hipLaunchKernelGGL(u8_pack7_range_kernel, dim3(grid_for(n_rows * pchunks, kBlock, 8)), dim3(kBlock), 0, s,
-                           h->codes.as<uint4>(), first_row, n_rows, rc, pchunks, rc / 8, h->packed.as<uint4>());
-        QAMD_HIP(hipGetLastError());
-    }
+    if (h->image.kind) QAMD_TRY(launch_pack(h, first_row, n_rows, nullptr, s));  // the store's own encoder: nothing to report
     QAMD_HIP(hipStreamSynchronize(s));
     h->count = std::max(h->count, end);
     h->meta.vector_parameters.count = h->count;
@@ -3563,29 +3455,29 @@ extern "C" __attribute__((visibility("default"))) void qamd_dev_u8_packed(const 
                                                                           uint32_t *chunks) {
     *packed = nullptr;
     *chunks = 0;
-    if (!h->packed_chunks) return;
+    if (!h->image.kind) return;
     if (!h->packed_rows.ptr) {
-        const uint64_t n = h->count * h->packed_chunks;
+        const uint64_t n = h->count * h->image.chunks;
         if (h->packed_rows.alloc(n * 16, false) != QAMD_OK) return;
         hipLaunchKernelGGL(u8_unblock_kernel, dim3(grid_for(n, kBlock, 8)), dim3(kBlock), 0, nullptr, h->packed.as<uint4>(),
-                           h->count, h->packed_chunks, h->packed_rows.as<uint4>());
+                           h->count, h->image.chunks, h->packed_rows.as<uint4>());
         if (hipStreamSynchronize(nullptr) != hipSuccess) {
             h->packed_rows.release();
             return;
         }
     }
     *packed = h->packed_rows.ptr;
-    *chunks = h->packed_chunks;
+    *chunks = h->image.chunks;
 }
 // The image the scan really reads: blocks of `block_rows` rows, chunk j of row r at 16-byte index
 // ((r / block_rows) * chunks + j) * block_rows + r % block_rows; padded_rows / block_rows blocks.
 extern "C" __attribute__((visibility("default"))) void qamd_dev_u8_packed_blocked(const qamd_u8 *h, const void **packed,
                                                                                   uint32_t *chunks, uint32_t *block_rows) {
     *packed = h->packed.ptr;
-    *chunks = h->packed_chunks;
+    *chunks = h->image.chunks;
     *block_rows = kPackBlockRows;
 }
-// Which image the store's last scan launch read (1: packed), and how many waves per block its last blocked scan took.
+// Which image the store's last scan launch read (U8Image::kind), and how many waves per block its last blocked scan took.
 extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_split(const qamd_u8 *h) {
     return h->last_scan_split.load(std::memory_order_relaxed);
 }

@@ -7,6 +7,14 @@
 #include "common.hpp"
 #include "lists.hpp"
 
+// The scan image of a store (qamd_u8::image): its format, its 16-byte chunks per row and the format's second kernel
+// argument.  The kinds are what qamd_dev_u8_last_scan_packed reports.
+enum : int { U8_IMAGE_NONE = 0, U8_IMAGE_7BIT = 1, U8_IMAGE_NIBBLE = 2 };
+struct U8Image {
+    int kind = U8_IMAGE_NONE;
+    uint32_t chunks = 0, aux = 0;
+};
+
 struct qamd_u8 {
     int device = 0;
     qamd_u8_metadata meta{};
@@ -21,26 +29,26 @@ struct qamd_u8 {
     bool rotated = false;
     // A 4-bit store: the byte codes hold 0..15, alpha is a fifteenth of the interval and the encoders round
     // to nearest.  Like `rotated` it lives beside the base metric and goes back on in get_metadata; only the encoders,
-    // the query encoders and build_packed read it - the scans see the image that build_packed left (packed_nibble).
+    // the query encoders and build_packed read it - the scans see the image that build_packed left (image.kind).
     bool four_bit = false;
     qamd::DevBuf codes;        // [padded_rows][actual_dim]
     qamd::DevBuf offsets;      // [padded_rows] f32
-    // Packed scan image (u8.hip build_packed): the codes at 7 bits each, packed_chunks 16-byte chunks per row.  Chunk
-    // j < packed_chunks keeps chunk j's codes in bits 0..6 of its bytes and, in bit 7, bit plane j % 7 of chunk
-    // packed_chunks + j / 7 (row_chunks / 8 such chunks).  Rows lie in blocks of 64 (kPackBlockRows): chunk j of row r is
-    // at 16-byte index ((r / 64) * packed_chunks + j) * 64 + r % 64, so that chunk j of a block's 64 rows is one aligned
-    // kilobyte, which one wave of u8_scan_blocked_kernel loads.  padded_rows is a multiple of 1024: blocks are whole, and
-    // padding rows are zero.  Only the Dot / L2 scans of lane mode 0 read it; every other kernel reads `codes`.  Empty
-    // when the store has none (L1, fewer than 8 or more than 128 chunks, a code above 127, too little free HBM).
+    // Scan image (u8.hip build_packed), `image.chunks` 16-byte chunks per row in the format `image.kind`; u8.hip
+    // u8_image_of is the one place that says which image a store can have and how long its rows are.
+    //   U8_IMAGE_7BIT: the codes at 7 bits each.  Chunk j < chunks keeps chunk j's codes in bits 0..6 of its bytes and, in
+    //     bit 7, bit plane j % 7 of chunk chunks + j / 7 (aux = row_chunks / 8 such chunks).
+    //   U8_IMAGE_NIBBLE (4-bit stores; never both): chunks = ceil(row_chunks / 2), byte b of chunk j = codes[32 j + b] |
+    //     codes[32 j + 16 + b] << 4 (high nibbles of the last chunk zero when row_chunks is odd); aux = row_chunks.
+    // Rows lie in blocks of 64 (kPackBlockRows): chunk j of row r is at 16-byte index ((r / 64) * chunks + j) * 64 + r % 64,
+    // so that chunk j of a block's 64 rows is one aligned kilobyte, which one wave of u8_scan_image_kernel loads.
+    // padded_rows is a multiple of 1024: blocks are whole, and padding rows are zero.  Only the Dot / L2 scans of lane
+    // mode 0 read it; every other kernel reads `codes`.  `packed` is empty and `image` is {} when the store has none (L1,
+    // fewer than 8 - nibble: 2 - or more than 128 chunks, a code above 127 - nibble: 15 -, too little free HBM).
     qamd::DevBuf packed;
-    uint32_t packed_chunks = 0;
-    // The image of a 4-bit store is a nibble image instead (never both): packed_chunks = ceil(row_chunks / 2), byte b of
-    // chunk j = codes[32 j + b] | codes[32 j + 16 + b] << 4 (high nibbles of the last chunk zero when row_chunks is odd),
-    // in the same blocks of 64 rows.  u8_scan_nibble_kernel reads it; stores of 2 to 128 chunks have one.
-    bool packed_nibble = false;
-    mutable std::atomic<int> last_scan_packed{0};  // the image the last scan launch read: 1 packed, 2 nibble (developer report)
+    U8Image image;
+    mutable std::atomic<int> last_scan_packed{0};  // image.kind of the image the last scan launch read (developer report)
     mutable std::atomic<int> last_scan_split{0};   // waves per block of the last blocked scan launch (developer report)
-    mutable qamd::DevBuf packed_rows;              // developer report: the image un-blocked, [count][packed_chunks]
+    mutable qamd::DevBuf packed_rows;              // developer report: the image un-blocked, [count][image.chunks]
     // The batched top-k's pivot sample (u8_batch.hip): rows hash(j) of the store, j < sample_rows, then 512
     // zero rows; gathered on first use (count / 64 rows at most: 1.6 % of the store), discarded by an upsert.
     mutable std::mutex sample_mu;

@@ -1,11 +1,11 @@
-"""The blocked packed scan (csrc/u8.hip u8_scan_blocked_kernel) against the byte codes and the oracle.
+"""The blocked packed scan (csrc/u8.hip u8_scan_image_kernel<Image7>) against the byte codes and the oracle.
 
 The packed image of a u8 store (u8_internal.hpp) lies in blocks of 64 rows: chunk j of row r is the 16 bytes at index
 ((r / 64) * P + j) * 64 + r % 64.  One wave scans one block, a row per lane, in groups of 7 chunks that share one extra
 chunk, then the rc % 8 chunks that carry no plane; stores too small to fill the GPU launch 2, 4 or 8 waves per block,
 whose partial sums meet in LDS.  None of that may change a result.  Each configuration runs in a fresh child process
 on the developer library (tools/lib): as built, with QAMD_DEV_U8_PACKED=0 (no image: every scan reads the bytes), and
-with QAMD_DEV_CU_COUNT=1, where the dispatch rule (launch_scan_blocked: one wave per block once the blocks number
+with QAMD_DEV_CU_COUNT=1, where the dispatch rule (launch_scan_image: one wave per block once the blocks number
 16 * CUs) takes one wave per block from 1024 rows on.  The parent compares the runs bit for bit with each other and
 with the oracle and reads which image and how many waves per block served each call.
 
@@ -69,7 +69,7 @@ def numpy_pack_blocked(codes):
 
 
 def model_sums(image, rc, qcodes):
-    """The integer pair sums as one lane of u8_scan_blocked_kernel adds them: groups of 7 chunks with the group's
+    """The integer pair sums as one lane of u8_scan_image_kernel<Image7> adds them: groups of 7 chunks with the group's
     extra chunk, plane shift 7 - j % 7, then the chunks without a plane.  image: numpy_pack_blocked's array."""
     e, p = rc // 8, rc - rc // 8
     q = qcodes.reshape(rc, 16).astype(np.int64)
@@ -202,7 +202,7 @@ def check_tag(runs, qo, tag, dim, n, dist, rows, query, names=("blocked", "bytes
 # ------------------------------------------------------------------ tests
 @pytest.mark.parametrize("rc", RCS)
 def test_numpy_model_of_a_lane_matches_the_oracle(qo, rc):
-    """No GPU: the decode order of u8_scan_blocked_kernel, restated in numpy on the numpy packer's image, gives the
+    """No GPU: the decode order of u8_scan_image_kernel<Image7>, restated in numpy on the numpy packer's image, gives the
     oracle's scores (the exact integer sum, then the f32 epilogue)."""
     dim, n = 16 * rc, 131
     rows, query = store_rows(dim, n, seed=1)

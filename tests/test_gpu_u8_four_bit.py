@@ -3,7 +3,7 @@
 1. Encode and query parity with the model (u8_four_bit_model.py), plain and rotated, through every conversion path of
    the encoder: the 16-lanes-per-row kernel (aligned rows of dim % 4 == 0), the dword kernel (any other source), both
    forms of the rotating kernel, and the query encoders; a sweep over the values at which code() changes.
-2. The nibble scan (csrc/u8.hip u8_scan_nibble_kernel) against the byte codes and the oracle, by the method of
+2. The nibble scan (csrc/u8.hip u8_scan_image_kernel<Image4>) against the byte codes and the oracle, by the method of
    test_gpu_u8_blocked.py: child processes on the developer library - as built, with QAMD_DEV_U8_PACKED=0 and with
    QAMD_DEV_CU_COUNT=1 - over stores adopted from uniform random codes 0..15, so the test owns every byte.
 3. One case for each route that reads the byte codes, and the write paths.
@@ -251,6 +251,12 @@ def child_main(out_path, mode):
     rows, md, _, query = store4(768, 1025, seed=3)
     rows[1000, 4 + 700] = 16
     score("code16", rows, md, query)
+    # the same at rc 3, row 65 of 70: in chunk 1, the high-nibble source of image chunk 0, and in chunk 2, the low-nibble
+    # source of the odd last image chunk
+    for chunk in (1, 2):
+        rows, md, _, query = store4(48, 70, seed=chunk)
+        rows[65, 4 + 16 * chunk + 5] = 16
+        score(f"code16/chunk{chunk}", rows, md, query)
     if mode != "cu1":
         for dim, n, ks in TOPK_CASES:
             rows, md, _, query = store4(dim, n)
@@ -366,6 +372,10 @@ def test_largest_sums_and_a_code_of_16(runs):
     rows[1000, 4 + 700] = 16
     check_tag(runs, "code16", 768, 1025, rows, meta, query, image=False)
     assert runs["nibble"][1]["layout/768x1026"][0] == 0
+    for chunk in (1, 2):  # either source chunk of an image chunk drops the image
+        rows, _, meta, query = store4(48, 70, seed=chunk)
+        rows[65, 4 + 16 * chunk + 5] = 16
+        check_tag(runs, f"code16/chunk{chunk}", 48, 70, rows, meta, query, image=False)
 
 
 @pytest.mark.parametrize("case", TOPK_CASES, ids=lambda c: f"{c[0]}x{c[1]}")

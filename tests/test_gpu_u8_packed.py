@@ -31,6 +31,7 @@ CASES = [(128, 5003, D.Dot), (144, 4099, D.L2), (240, 3001, D.Dot), (768, 20011,
          (1040, 3007, D.Dot), (1536, 4001, D.L2), (2048, 2003, D.Dot), (768, 5003, D.L1)]
 BIG = (144, 2_100_003, D.Dot)  # past the single-launch top-k's 2^21 rows: k = 1 and 30 take the fused top-k too
 LAYOUT_DIMS = (128, 240, 768, 1040)
+EXTRA_DIMS = (128, 256)  # 8 and 16 chunks: one extra chunk, two
 
 
 def packed_chunks(dim, dist):
@@ -61,10 +62,14 @@ def _image(enc):
     return int(qa.lib().qamd_dev_u8_last_scan_packed(enc._h))
 
 
-def _store(R, info, tag, enc, queries, ks=KS):
+def _store_chunks(enc):
     ptr, chunks = C.c_void_p(), C.c_uint32()
     qa.lib().qamd_dev_u8_packed(enc._h, C.byref(ptr), C.byref(chunks))
-    info[tag + "/chunks"] = int(chunks.value)
+    return int(chunks.value)
+
+
+def _store(R, info, tag, enc, queries, ks=KS):
+    info[tag + "/chunks"] = _store_chunks(enc)
     for qi, query in enumerate(queries):
         q = enc.encode_query(query)
         R[f"{tag}/q{qi}/all"] = enc.score_all(q)
@@ -118,6 +123,16 @@ def child_main(out_path, tmp_dir):
             r[n // 2, 4 + 700] = fill  # one code of one row, in an extra chunk
         enc = qa.EncodedVectorsU8.from_storage(r, st.metadata)
         _store(R, info, name, enc, queries)
+    # the same at the shortest rows: one code of 128 in the last extra chunk of row 65 of 70 (the second, partial block),
+    # which only the pack threads that take their bit plane from that chunk read
+    for xdim in EXTRA_DIMS:
+        xdata, xqueries = data_of(xdim, 70)
+        small = qa.EncodedVectorsU8.encode(xdata, qa.VectorParameters(xdim, 70, D.Dot, False))
+        info[f"x128/{xdim}/chunks_clean"] = _store_chunks(small)
+        r = small.storage_bytes().copy()
+        r[65, 4 + xdim - 16 + 5] = 128
+        _store(R, info, f"x128/{xdim}", qa.EncodedVectorsU8.from_storage(r, small.metadata), xqueries, ks=())
+        R[f"x128/{xdim}/rows"] = r
     # a two-shard handle builds its shards through the same builders
     sh = qa.ShardedVectorsU8.encode(data, vp, [0, 0])
     for qi, query in enumerate(queries):
@@ -227,3 +242,22 @@ def test_stream_load_lane_mode_and_foreign_rows(runs, qo):
             assert pinfo[f"{tag}/q{qi}/all"] == 1
             for k in KS:
                 _check_topk(P[f"{tag}/q{qi}/topk{k}"], w, k, f"{tag} topk {k}")
+
+
+@pytest.mark.parametrize("dim", EXTRA_DIMS)
+def test_a_foreign_code_in_an_extra_chunk_drops_the_image(runs, qo, dim):
+    (P, pinfo), (B, binfo) = runs["packed"], runs["bytes"]
+    tag = f"x128/{dim}"
+    assert pinfo[tag + "/chunks_clean"] == packed_chunks(dim, D.Dot), "without the foreign code the store has an image"
+    assert pinfo[tag + "/chunks"] == 0 and binfo[tag + "/chunks"] == 0, "a code of 128 in an extra chunk must drop the image"
+    _same_runs(runs, tag + "/q")
+    data, queries = data_of(dim, 70)
+    rows, meta = qo.u8_encode(data, int(D.Dot), False)
+    r = P[tag + "/rows"]
+    at = dim - 16 + 5  # the code that was replaced: the rest of the rows is the oracle's, and its chunk is an extra one
+    assert np.argwhere(r != rows).tolist() == [[65, 4 + at]] and at // 16 >= packed_chunks(dim, D.Dot)
+    for qi, query in enumerate(queries):
+        codes, qoff = qo.u8_encode_query(meta, query)
+        want = qo.u8_score_all(meta, r, codes, qoff, order=qo.ORDER_AVX2)
+        assert_bits_equal(P[f"{tag}/q{qi}/all"], want, f"{tag} score_all")
+        assert pinfo[f"{tag}/q{qi}/all"] == 0, "the scan read an image the store must not have"

@@ -189,7 +189,11 @@ def numpy_blocked(codes, padded_rows):
     return img.reshape(-1)
 
 
+RANGE_CASES = ((144, 8), (256, 8), (48, 4))  # (dim, bits)
+
+
 def child_main(out_path):
+    import u8_four_bit_model as fm
     from test_gpu_u8_packed import _device_bytes
 
     L = qa.lib()
@@ -211,6 +215,21 @@ def child_main(out_path):
             got = _device_bytes(ptr, padded * chunks.value * 16)
             want = numpy_blocked(up.storage_bytes()[:, 4:], padded)
             info[f"{dim}/image_equal"] = bool(np.array_equal(got, want))  # zero past count, block by block
+    # one pack kernel writes both formats at a row base: rows 60..69 of 130 - the end of one block and the start of the
+    # next, nothing else touched - at 9 chunks (a rest group), 16 (two extra chunks) and, 4-bit, 3 (the odd last chunk)
+    for dim, bits in RANGE_CASES:
+        data0 = make(dim, 130, 5)
+        up = qa.EncodedVectorsU8.encode(data0, qa.VectorParameters(dim, 130, D.Dot, False), bits=bits)
+        before = up.storage_bytes()
+        up.upsert(60, make(dim, 10, 6, scale=1.3))
+        codes = up.storage_bytes()[:, 4:]
+        L.qamd_dev_u8_packed_blocked(up._h, C.byref(ptr), C.byref(chunks), C.byref(brows))
+        padded = -(-up.capacity // 1024) * 1024 + 1024
+        got = _device_bytes(ptr, padded * chunks.value * 16) if chunks.value else None
+        want = numpy_blocked(codes, padded) if bits == 8 else fm.block_image(fm.pack_rows(codes), padded)
+        changed = np.flatnonzero((before[:, 4:] != codes).any(axis=1))
+        info[f"range/{dim}/{bits}"] = [int(chunks.value), got is not None and bool(np.array_equal(got, want)),
+                                       int(changed.min()), int(changed.max())]
     # a PQ store with a planar image may not reach the row count at which a builder would give it none
     dim, chunk = 384, 2
     cen = np.random.default_rng(1).random((256, dim), dtype=np.float32)
@@ -248,6 +267,9 @@ def test_u8_image_follows_and_the_planar_limit_is_refused(tmp_path):
         assert info[f"{dim}/chunks_before"] == info[f"{dim}/chunks_after"] == chunks, info
         assert info[f"{dim}/scan_read_image"] == 1 and info[f"{dim}/image_equal"] is True, info
     assert info["100/chunks_before"] == info["100/chunks_after"] == 0 and info["100/scan_read_image"] == 0, info
+    for (dim, bits), chunks in zip(RANGE_CASES, (8, 14, 2)):
+        # the new rows differ from the old ones at both ends of the range, and the WHOLE image is the packer's
+        assert info[f"range/{dim}/{bits}"] == [chunks, True, 60, 69], (dim, bits, info)
     assert info["planar/across"] == "ArgumentsError" and info["planar/below"] == "ok" and info["planar/count"] == 5999, info
     assert info["planar/reserve"] == "ArgumentsError", info
 
