@@ -789,9 +789,11 @@ __global__ __launch_bounds__(kBlock) void bin_encode_scalar_kernel(const float *
 // butterflies of stages s = 1, 2, 4, ..., P / 2 in that order - (a, b) = (y_j, y_{j+s}) -> (a + b, a - b), one f32
 // operation each (this file compiles with contraction off).  A stage reads only the stage before it, so any split of
 // the work gives the same bits; the ORDER of the stages is part of the definition (f32 addition is not associative).
-// rot_signed, lane_butterfly, butterfly, load_chunk and the block rotation of a whole row: rotate_blocks.hpp.
+// Block-rotated rows take no pad and cut the network off after stage B / 2, B the largest power of two
+// that divides dim: dim / B transforms of size B side by side.  The transform, the two kernel frames (a wave per row, a
+// workgroup per row) and their launcher: rotate_blocks.hpp, with width = B = P here and width = dim for blocks.
 
-// What the rotation kernels do with a finished row.  MODE 0: the P rotated floats to `out` (statistics, scalar-code
+// What becomes of a finished row, P its width.  MODE 0: the P rotated floats to `out` (statistics, scalar-code
 // encoders).  MODE 1: bit i = y_i > 0.  MODE 2: bit i = y_i > lo_i, bit P + i = y_i > hi_i (thr = lo | hi, 2 P floats).
 // emit_chunks: 64 lanes hold the 64 consecutive 4-value chunks c0 .. c0 + 63 of a row of P >= 256 values, lane l chunk
 // c0 + l.  A lane's four compares are a nibble at bit 4 (l % 8) of dword (c0 + l) / 8; the 8-lane DPP sum of
@@ -821,79 +823,75 @@ __device__ __forceinline__ void emit_chunks(const float (&y)[4], uint32_t c0, in
     }
 }
 
-// A wave per row, the row in registers: P = 64 E K, lane l holds value e of chunk k at index (64 k + l) E + e, so a
-// wave-load reads 64 consecutive chunks (E = 4: 1 KiB, every float once).  The index bits are e | lane | k from the low
-// end, which is the order of the stages: E = 4 does stages 1 and 2 on a chunk's own values, the six lane bits follow
-// (lane_butterfly), then the stages across a lane's K chunks, plain register adds.  E = 1 serves P <= 128; P < 64
-// (K = 1) leaves the lanes from P on idle and stops at stage P / 2.  One row per wave and pass of a grid-stride loop,
-// all 64 lanes active throughout (the DPP moves read their neighbours).
-// MODE 1 / 2 with E = 1: one ballot per plane and 64 values; the row is at most four 64-bit words, every lane puts them
-// together and lane j stores dword j of the row's row_words, pad dwords as zeros.
-template <int E, int K, int MODE>
-__global__ __launch_bounds__(kBlock) void bin_rotate_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
-                                                           uint32_t P, int vec, const float *__restrict__ thr,
-                                                           float *__restrict__ out, uint32_t *__restrict__ rows,
-                                                           uint32_t row_words, uint64_t row0) {
-    static_assert(E == 4 || (E == 1 && K <= 2), "E = 1 is for rows of at most 128 values");
-    constexpr bool kFull = E * K > 1;  // P == 64 E K: all six lane stages; <1, 1> serves every P <= 64 and asks P
+// A finished row of `width` values (P, or dim of a block-rotated row) from the two frames of rotate_blocks.hpp, for
+// width >= 256 and for every block-rotated row that is no power of two: emit_chunks per live chunk, then the row's dwords
+// past its bits as zeros.
+template <int MODE> struct BinRotSink : RotSink {
+    uint32_t width;
+    const float *thr;  // MODE 2: lo | hi, 2 width floats
+    float *out;        // MODE 0: width floats per row
+    uint32_t *rows;    // MODE 1 / 2: bit rows of row_words dwords, row r at row0 + r
+    uint32_t row_words;
+    uint64_t row0;
+    __device__ uint32_t *dst(uint64_t r) const { return rows + (row0 + r) * row_words; }
+    __device__ void chunk(State &, uint64_t r, uint32_t ch, int lane, const float (&y)[4], uint32_t &) const {
+        if constexpr (MODE == 2) __builtin_assume_separate_storage(thr, rows);
+        emit_chunks<MODE>(y, ch - lane, lane, width, thr, MODE == 0 ? out + r * width : nullptr, MODE == 0 ? nullptr : dst(r));
+    }
+    __device__ void pad(uint64_t r, uint32_t t, uint32_t threads) const {
+        if constexpr (MODE != 0)
+            for (uint32_t w = (MODE == 2 ? width / 16 : width / 32) + t; w < row_words; w += threads) dst(r)[w] = 0;
+    }
+    template <int K> __device__ void row_wave(State &, uint64_t r, int lane, const uint32_t (&)[K]) const { pad(r, lane, 64); }
+    __device__ void row_lds(State &, uint64_t r, uint32_t *) const { pad(r, threadIdx.x, kRotThreads); }
+};
+
+// Rows of P <= 128 values, another algorithm: a wave per row, lane l holds value 64 k + l in y[k] (K = 1 or 2), the six
+// lane stages (lane_butterfly) and, K = 2, one stage across the lane's two values.  P < 64 (K = 1) leaves the lanes from
+// P on idle and stops at stage P / 2.  One row per wave and pass of a grid-stride loop, all 64 lanes active throughout
+// (the DPP moves read their neighbours).
+// MODE 1 / 2: one ballot per plane and 64 values; the row is at most four 64-bit words, every lane puts them together
+// and lane j stores dword j of the row's row_words, pad dwords as zeros.
+template <int K, int MODE>
+__global__ __launch_bounds__(kBlock) void bin_rotate_small_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
+                                                                 uint32_t P, const float *__restrict__ thr,
+                                                                 float *__restrict__ out, uint32_t *__restrict__ rows,
+                                                                 uint32_t row_words, uint64_t row0) {
+    static_assert(K == 1 || K == 2, "rows of at most 128 values");
+    constexpr bool kFull = K > 1;  // P == 64 K: all six lane stages; K = 1 serves every P <= 64 and asks P
     const int lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
     for (uint64_t r = wave; r < n_rows; r += n_waves) {
         const float *src = data + r * dim;
-        float y[K][E];
+        float y[K];
 #pragma unroll
         for (int k = 0; k < K; k++) {
-            if constexpr (E == 4) {
-                load_chunk(src, (uint32_t)(k * 64 + lane) * 4, dim, vec, y[k]);
-            } else {
-                const uint32_t i = k * 64 + lane;
-                y[k][0] = rot_signed(i < dim ? src[i] : 0.0f, i);
-            }
+            const uint32_t i = k * 64 + lane;
+            float v = rot_signed(i < dim ? src[i] : 0.0f, i);
+            if (kFull || 1u < P) v = lane_butterfly<1>(v, lane);
+            if (kFull || 2u < P) v = lane_butterfly<2>(v, lane);
+            if (kFull || 4u < P) v = lane_butterfly<4>(v, lane);
+            if (kFull || 8u < P) v = lane_butterfly<8>(v, lane);
+            if (kFull || 16u < P) v = lane_butterfly<16>(v, lane);
+            if (kFull || 32u < P) v = lane_butterfly<32>(v, lane);
+            y[k] = v;
         }
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                float v = y[k][e];
-                if (kFull || 1u < P) v = lane_butterfly<1>(v, lane);
-                if (kFull || 2u < P) v = lane_butterfly<2>(v, lane);
-                if (kFull || 4u < P) v = lane_butterfly<4>(v, lane);
-                if (kFull || 8u < P) v = lane_butterfly<8>(v, lane);
-                if (kFull || 16u < P) v = lane_butterfly<16>(v, lane);
-                if (kFull || 32u < P) v = lane_butterfly<32>(v, lane);
-                y[k][e] = v;
-            }
-        }
-#pragma unroll
-        for (int s = 1; s < K; s <<= 1) {
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                if (k & s) continue;
-#pragma unroll
-                for (int e = 0; e < E; e++) butterfly(y[k][e], y[k + s][e]);
-            }
-        }
-        float *out_row = MODE == 0 ? out + r * P : nullptr;
-        uint32_t *dst = MODE == 0 ? nullptr : rows + (row0 + r) * row_words;
-        if constexpr (E == 4) {
-#pragma unroll
-            for (int k = 0; k < K; k++) emit_chunks<MODE>(y[k], k * 64, lane, P, thr, out_row, dst);
-            if constexpr (MODE != 0)
-                for (uint32_t w = (MODE == 2 ? P / 16 : P / 32) + lane; w < row_words; w += 64) dst[w] = 0;
-        } else if constexpr (MODE == 0) {
+        if constexpr (K == 2) butterfly(y[0], y[1]);
+        if constexpr (MODE == 0) {
 #pragma unroll
             for (int k = 0; k < K; k++)
-                if ((uint32_t)(k * 64 + lane) < P) out_row[k * 64 + lane] = y[k][0];
+                if ((uint32_t)(k * 64 + lane) < P) out[r * P + k * 64 + lane] = y[k];
         } else {
+            uint32_t *dst = rows + (row0 + r) * row_words;
             unsigned long long b0[K], b1[K];
 #pragma unroll
             for (int k = 0; k < K; k++) {
                 const uint32_t i = k * 64 + lane;
                 const bool in = i < P;
                 const float lo = MODE == 2 && in ? thr[i] : 0.0f, hi = MODE == 2 && in ? thr[P + i] : 0.0f;
-                b0[k] = __ballot(in && y[k][0] > lo);
-                b1[k] = MODE == 2 ? __ballot(in && y[k][0] > hi) : 0ull;
+                b0[k] = __ballot(in && y[k] > lo);
+                b1[k] = MODE == 2 ? __ballot(in && y[k] > hi) : 0ull;
             }
             unsigned long long w0 = b0[0], w1 = K == 2 ? b0[K - 1] : 0ull, w2 = 0, w3 = 0;
             if constexpr (MODE == 2) {
@@ -907,118 +905,6 @@ __global__ __launch_bounds__(kBlock) void bin_rotate_kernel(const float *__restr
             }
             for (uint32_t w = 64 + lane; w < row_words; w += 64) dst[w] = 0;
         }
-    }
-}
-
-// A workgroup per row for the rows a wave's registers do not hold (P = 4096 .. 16384, 16 .. 64 KiB of LDS): every
-// thread loads 4-value chunks (stages 1 and 2 in registers, as above) into the LDS row, the stages from 4 on run there -
-// P / 2 pairs per stage over the 256 threads, a barrier between stages - and the chunks are read back for emit_chunks,
-// a wave 64 consecutive chunks at a time.
-template <int MODE>
-__global__ __launch_bounds__(kBlock) void bin_rotate_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
-                                                               uint32_t P, int vec, const float *__restrict__ thr,
-                                                               float *__restrict__ out, uint32_t *__restrict__ rows,
-                                                               uint32_t row_words, uint64_t row0) {
-    extern __shared__ float rot_row[];
-    const int lane = threadIdx.x & 63;
-    const uint32_t chunks = P / 4;  // a multiple of kBlock
-    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        const float *src = data + r * dim;
-        for (uint32_t c = threadIdx.x; c < chunks; c += kBlock) {
-            float y[4];
-            load_chunk(src, c * 4, dim, vec, y);
-            reinterpret_cast<float4 *>(rot_row)[c] = make_float4(y[0], y[1], y[2], y[3]);
-        }
-        for (uint32_t s = 4; s < P; s <<= 1) {
-            __syncthreads();
-            for (uint32_t b = threadIdx.x; b < P / 2; b += kBlock) {
-                const uint32_t j = ((b & ~(s - 1)) << 1) | (b & (s - 1));
-                float a = rot_row[j], d = rot_row[j + s];
-                butterfly(a, d);
-                rot_row[j] = a, rot_row[j + s] = d;
-            }
-        }
-        __syncthreads();
-        float *out_row = MODE == 0 ? out + r * P : nullptr;
-        uint32_t *dst = MODE == 0 ? nullptr : rows + (row0 + r) * row_words;
-        for (uint32_t c0 = (threadIdx.x >> 6) * 64; c0 < chunks; c0 += kBlock) {
-            const float4 t = reinterpret_cast<const float4 *>(rot_row)[c0 + lane];
-            const float y[4] = {t.x, t.y, t.z, t.w};
-            emit_chunks<MODE>(y, c0, lane, P, thr, out_row, dst);
-        }
-        if constexpr (MODE != 0)
-            for (uint32_t w = (MODE == 2 ? P / 16 : P / 32) + threadIdx.x; w < row_words; w += kBlock) dst[w] = 0;
-        __syncthreads();  // the next row's chunks overwrite the LDS row
-    }
-}
-
-// ---- block-rotated rows: no pad, and the network above cut off after stage B / 2 ----
-// B = the largest power of two that divides dim (dim % 64 == 0, so B >= 64): dim / B Hadamard transforms of size B side
-// by side, the row keeps dim values.  The launcher sends a power-of-two dim (B == dim) to the kernels above; these two
-// serve B < dim.  B is a wave-uniform argument, as P is for bin_rotate_kernel<1, 1>: every test on it is a scalar branch.
-//
-// A wave per row for dim <= 2048, bin_rotate_kernel<4, K, MODE>'s layout with K = ceil(dim / 256) of any value 1 .. 8.
-// Stages 1 and 2 are load_chunk's; the lane stage M pairs values 4 M apart and runs while 4 M < B (M <= 8 always).  A
-// dim <= 2048 that is no power of two has B <= 512 (B = 1024 first at 3072), so of the chunk stages only s = 1 is left,
-// values 256 apart, for B = 512 - that is dim = 1536 = 3 x 512, K = 6: chunk k pairs with k + 1 for every even k.
-// dim % 256 != 0: the lanes from dim / 4 - 64 (K - 1) on of the last chunk hold +-0.0 and stay active for the DPP reads.
-// B divides dim, so a pair lies in one B-aligned block, wholly below dim or wholly at or above it: an idle lane never
-// meets a live value (and B <= 128 there: no chunk stage).  dim / 4 is a multiple of 16, so the 8-lane groups of
-// emit_chunks are wholly live or wholly idle: the branch around it cuts along groups, and an idle group neither reads
-// thresholds nor stores.
-template <int K, int MODE>
-__global__ __launch_bounds__(kBlock) void bin_rotate_blocks_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
-                                                                  uint32_t B, int vec, const float *__restrict__ thr,
-                                                                  float *__restrict__ out, uint32_t *__restrict__ rows,
-                                                                  uint32_t row_words, uint64_t row0) {
-    static_assert(K >= 1 && K <= 8, "a lane holds at most 32 values");
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
-    const uint32_t chunks = dim / 4;
-    for (uint64_t r = wave; r < n_rows; r += n_waves) {
-        const float *src = data + r * dim;
-        float y[K][4];
-        rotate_blocks_wave<K>(src, dim, B, vec, lane, y);
-        float *out_row = MODE == 0 ? out + r * dim : nullptr;
-        uint32_t *dst = MODE == 0 ? nullptr : rows + (row0 + r) * row_words;
-        // only the last chunk can hold idle lanes; the chunks before it go without a branch, so their threshold loads
-        // issue together (behind a branch each load waits for the one before it)
-#pragma unroll
-        for (int k = 0; k < K - 1; k++) emit_chunks<MODE>(y[k], k * 64, lane, dim, thr, out_row, dst);
-        if ((uint32_t)((K - 1) * 64 + lane) < chunks) emit_chunks<MODE>(y[K - 1], (K - 1) * 64, lane, dim, thr, out_row, dst);
-        if constexpr (MODE != 0)
-            for (uint32_t w = (MODE == 2 ? dim / 16 : dim / 32) + lane; w < row_words; w += 64) dst[w] = 0;
-    }
-}
-
-// A workgroup per row for 2048 < dim <= 16384: bin_rotate_lds_kernel with the stage loop ending at s < B and a chunk
-// count dim / 4 that is a multiple of 16, not of kBlock - the emit loop's last pass is cut along 8-lane groups as above.
-// A stage's dim / 2 pairs: pair b is (j, j + s) with j = 2 s (b / s) + b % s, and 2 s <= B divides dim, so j + s < dim.
-// 4 dim bytes of LDS.
-template <int MODE>
-__global__ __launch_bounds__(kBlock) void bin_rotate_blocks_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
-                                                                      uint32_t B, int vec, const float *__restrict__ thr,
-                                                                      float *__restrict__ out, uint32_t *__restrict__ rows,
-                                                                      uint32_t row_words, uint64_t row0) {
-    extern __shared__ float rot_row[];
-    const int lane = threadIdx.x & 63;
-    const uint32_t chunks = dim / 4;
-    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        const float *src = data + r * dim;
-        rotate_blocks_lds(src, dim, B, vec, rot_row);
-        float *out_row = MODE == 0 ? out + r * dim : nullptr;
-        uint32_t *dst = MODE == 0 ? nullptr : rows + (row0 + r) * row_words;
-        for (uint32_t c0 = (threadIdx.x >> 6) * 64; c0 < chunks; c0 += kBlock) {
-            if (c0 + lane < chunks) {
-                const float4 t = reinterpret_cast<const float4 *>(rot_row)[c0 + lane];
-                const float y[4] = {t.x, t.y, t.z, t.w};
-                emit_chunks<MODE>(y, c0, lane, dim, thr, out_row, dst);
-            }
-        }
-        if constexpr (MODE != 0)
-            for (uint32_t w = (MODE == 2 ? dim / 16 : dim / 32) + threadIdx.x; w < row_words; w += kBlock) dst[w] = 0;
-        __syncthreads();  // the next row's chunks overwrite the LDS row
     }
 }
 
@@ -1088,9 +974,6 @@ uint64_t rot_dim(uint64_t dim) {
     while (p < dim) p <<= 1;
     return p;
 }
-
-// B of DESIGN 3.2h: the largest power of two that divides dim (dim != 0)
-uint64_t rot_block(uint64_t dim) { return dim & (~dim + 1); }
 
 // The dimension the bit encoders of `encoding` see for vectors of `dim`: block rotation (3.2h) does not pad.
 uint64_t encoder_dim(uint64_t dim, int encoding) {
@@ -1296,54 +1179,25 @@ qamd_status upload_rows(qamd_bin *h, const uint8_t *rows, qamd_mem mem, hipStrea
 // The bit encoder for a one-bit or two-bit store: `n` vectors of `dim` floats into bit rows of `row_words` dwords, the
 // first at row r0 of dst - the store's rows, a query's bit row, a batch's (one "row" per query, :288-291 is encode_vector
 // itself).
-// The rotation of `n` vectors of `dim` floats, P = rot_dim(dim).  MODE 0: P floats per vector to `out`;
-// MODE 1 / 2: the fused row encoder - bit rows of `row_words` dwords from row r0 of `rows` on, thr = lo | hi for MODE 2.
-// `blocks` (dim % 64 == 0, checked by every caller's check_enc_args): dim values per vector, the network cut
-// off after stage B / 2.  A power-of-two dim has B == dim == P: the same transform, and the kernels of 3.2g serve it.
+// The rotation of `n` vectors of `dim` floats.  MODE 0: `width` floats per vector to `out`; MODE 1 / 2: the fused row
+// encoder - bit rows of `row_words` dwords from row r0 of `rows` on, thr = lo | hi for MODE 2.  Padded:
+// width = B = P = rot_dim(dim).  `blocks` (dim % 64 == 0, checked by every caller's check_enc_args):
+// width = dim, B = rot_block(dim); a power-of-two dim has B == dim == P, the same transform.  Rows of one block of at
+// most 128 values take the small kernel, every other row the frames of rotate_blocks.hpp.
 template <int MODE>
 void launch_rotate(const float *src, uint64_t n, uint64_t dim, bool blocks, const float *thr, float *out, uint32_t *rows,
                    uint64_t row_words, uint64_t r0, hipStream_t s) {
     if (n == 0 || dim == 0) return;
-    const int vec = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
-    if (blocks && rot_block(dim) != dim) {
-        const uint32_t B = (uint32_t)rot_block(dim);
-#define QAMD_BIN_ROT_BLOCKS(K)                                                                                           \
-    case K:                                                                                                              \
-        hipLaunchKernelGGL((bin_rotate_blocks_kernel<K, MODE>), dim3(grid_for(n, kBlock / 64, 8)), dim3(kBlock), 0, s, src, n, \
-                           (uint32_t)dim, B, vec, thr, out, rows, (uint32_t)row_words, r0);                               \
-        break
-        if (dim > kRotWaveMax) {
-            hipLaunchKernelGGL(bin_rotate_blocks_lds_kernel<MODE>, dim3(grid_for(n, 1, 160 * 1024 / (dim * 4))), dim3(kBlock),
-                               dim * 4, s, src, n, (uint32_t)dim, B, vec, thr, out, rows, (uint32_t)row_words, r0);
-            return;
-        }
-        switch ((dim + 255) / 256) {
-            QAMD_BIN_ROT_BLOCKS(1);
-            QAMD_BIN_ROT_BLOCKS(2);
-            QAMD_BIN_ROT_BLOCKS(3);
-            QAMD_BIN_ROT_BLOCKS(4);
-            QAMD_BIN_ROT_BLOCKS(5);
-            QAMD_BIN_ROT_BLOCKS(6);
-            QAMD_BIN_ROT_BLOCKS(7);
-            QAMD_BIN_ROT_BLOCKS(8);
-        }
-#undef QAMD_BIN_ROT_BLOCKS
+    const uint32_t width = (uint32_t)(blocks ? dim : rot_dim(dim)), B = (uint32_t)(blocks ? rot_block(dim) : width);
+    if (width == B && width <= 128) {
+        const auto small = width <= 64 ? bin_rotate_small_kernel<1, MODE> : bin_rotate_small_kernel<2, MODE>;
+        hipLaunchKernelGGL(small, dim3(grid_for(n, kBlock / 64, 8)), dim3(kBlock), 0, s, src, n, (uint32_t)dim, width, thr, out,
+                           rows, (uint32_t)row_words, r0);
         return;
     }
-    const uint32_t P = (uint32_t)rot_dim(dim);
-#define QAMD_BIN_ROT(E, K)                                                                                               \
-    hipLaunchKernelGGL((bin_rotate_kernel<E, K, MODE>), dim3(grid_for(n, kBlock / 64, 8)), dim3(kBlock), 0, s, src, n,    \
-                       (uint32_t)dim, P, vec, thr, out, rows, (uint32_t)row_words, r0)
-    if (P > kRotWaveMax)
-        hipLaunchKernelGGL(bin_rotate_lds_kernel<MODE>, dim3(grid_for(n, 1, 160 * 1024 / (P * 4))), dim3(kBlock), P * 4, s, src, n,
-                           (uint32_t)dim, P, vec, thr, out, rows, (uint32_t)row_words, r0);
-    else if (P <= 64) QAMD_BIN_ROT(1, 1);
-    else if (P == 128) QAMD_BIN_ROT(1, 2);
-    else if (P == 256) QAMD_BIN_ROT(4, 1);
-    else if (P == 512) QAMD_BIN_ROT(4, 2);
-    else if (P == 1024) QAMD_BIN_ROT(4, 4);
-    else QAMD_BIN_ROT(4, 8);
-#undef QAMD_BIN_ROT
+    BinRotSink<MODE> sink;
+    sink.width = width, sink.thr = thr, sink.out = out, sink.rows = rows, sink.row_words = (uint32_t)row_words, sink.row0 = r0;
+    launch_rot(sink, src, n, (uint32_t)dim, width, B, s);
 }
 
 void launch_bit_encoder(const qamd_bin *h, const float *src, uint64_t n, uint64_t dim, uint64_t row_words, uint32_t *dst,

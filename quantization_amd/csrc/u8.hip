@@ -1152,12 +1152,12 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
 // The store holds y^ = c * y, y the block rotation of the row (rotate_blocks.hpp) and c = 2^(-log2(B) / 2)
 // rounded to f32: one multiply per value, rounded on its own (__fmul_rn), then the quantizer above on y^.  dim is a
 // multiple of 64, so actual_dim == dim: no pad codes, and a 4-value chunk is one dword of codes.  Three consumers of a
-// rotated row, each as a wave per row (dim <= 2048, the row in registers: lane l holds chunk k * 64 + l in y[k]) and as
-// a workgroup per row (the row in LDS): min/max (pass 1; nothing is written per row), quantize (pass 2, push, upsert:
-// the codes and the row offset as quantize16_kernel writes them) and the values themselves (queries, the quantile sample).
-// The lanes of a last chunk past dim / 4 hold +-0.0 (rotate_blocks_wave): they are kept out of every fold and store.
-// K = 4 and K = 8 carry the chunk stages that dim = 1024 and dim = 2048, one block each, need (POW2).
-constexpr int kQuant4Bit = 2;  // `fast` of the u8_rot_quantize kernels: 0 the exact division, 1 the division-free form, 2 4-bit codes
+// rotated row, each a sink of the two kernel frames of rotate_blocks.hpp (a wave per row for dim <= 2048, the row in
+// registers, and a workgroup per row, the row in LDS): min/max (pass 1; nothing is written per row), quantize (pass 2,
+// push, upsert: the codes and the row offset as quantize16_kernel writes them) and the values themselves (queries, the
+// quantile sample).  The frames call a sink for live chunks only: the lanes of a last chunk past dim / 4, which hold
+// +-0.0, reach no fold and no store.
+constexpr int kQuant4Bit = 2;  // `fast` of RotQuantizeSink: 0 the exact division, 1 the division-free form, 2 4-bit codes
 __device__ __forceinline__ uint32_t rot_quant4(const float (&v)[4], float alpha, float offset, float r_alpha, int fast) {
     const float4 f = make_float4(v[0], v[1], v[2], v[3]);
     if (fast == kQuant4Bit)  // a 4-bit store; wave-uniform
@@ -1204,213 +1204,127 @@ __device__ __forceinline__ void rot_minmax_commit(float mn, float mx, unsigned l
     }
 }
 
-template <int K>
-__global__ __launch_bounds__(kBlock) void u8_rot_minmax_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
-                                                              uint32_t B, float c, int vec, uint32_t *__restrict__ slots,
-                                                              uint64_t base_values,
-                                                              unsigned long long *__restrict__ first_zero) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
-    if (wave >= n_rows) return;
-    const uint32_t chunks = dim / 4;
-    float mn = 3.40282347e+38f, mx = -3.40282347e+38f;
-    unsigned long long zk = kNoZero;
-    for (uint64_t r = wave; r < n_rows; r += n_waves) {
-        float y[K][4];
-        rotate_blocks_wave<K, K == 4 || K == 8>(data + r * dim, dim, B, vec, lane, y);
-        uint32_t z = 0xFFFFFFFFu;  // (index in the row << 1) | sign of the lane's first zero: downwards, the lowest last
+// Pass 1: the extremes of y^ over a thread's rows and the first zero among them.  A thread's chunks, and its rows, come
+// in rising order, so the first zero it meets is the one of the lowest index.
+struct RotMinmaxSink : RotSink {
+    uint32_t dim;
+    float c;
+    uint32_t *slots;
+    uint64_t base_values;
+    unsigned long long *first_zero;
+    struct State {
+        float mn = 3.40282347e+38f, mx = -3.40282347e+38f;
+        unsigned long long zk = kNoZero;
+        uint32_t z = 0xFFFFFFFFu;  // (index in the row << 1) | sign of the thread's first zero in the present row
+    };
+    __device__ void chunk(State &st, uint64_t, uint32_t ch, int, const float (&y)[4], uint32_t &) const {
 #pragma unroll
-        for (int k = K - 1; k >= 0; k--) {
-            const uint32_t ch = (uint32_t)(k * 64 + lane);
-            if (k < K - 1 || ch < chunks) {
-#pragma unroll
-                for (int e = 3; e >= 0; e--) {
-                    const float v = __fmul_rn(y[k][e], c);
-                    mn = v < mn ? v : mn;
-                    mx = v > mx ? v : mx;
-                    if (v == 0.0f) z = ((ch * 4 + e) << 1) | (__float_as_uint(v) >> 31);
-                }
-            }
+        for (int e = 0; e < 4; e++) {
+            const float v = __fmul_rn(y[e], c);
+            st.mn = v < st.mn ? v : st.mn;
+            st.mx = v > st.mx ? v : st.mx;
+            if (v == 0.0f && st.z == 0xFFFFFFFFu) st.z = ((ch * 4 + e) << 1) | (__float_as_uint(v) >> 31);
         }
-        if (z != 0xFFFFFFFFu && zk == kNoZero) zk = ((r * dim) << 1) + z;  // a lane's rows only grow
     }
-    rot_minmax_commit(mn, mx, zk, wave, lane, slots, base_values, first_zero);
-}
-
-__global__ __launch_bounds__(kBlock) void u8_rot_minmax_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
-                                                                  uint32_t B, float c, int vec, uint32_t *__restrict__ slots,
-                                                                  uint64_t base_values,
-                                                                  unsigned long long *__restrict__ first_zero) {
-    extern __shared__ float rot_row[];
-    const uint32_t chunks = dim / 4;
-    float mn = 3.40282347e+38f, mx = -3.40282347e+38f;
-    unsigned long long zk = kNoZero;
-    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        rotate_blocks_lds(data + r * dim, dim, B, vec, rot_row);
-        uint32_t z = 0xFFFFFFFFu;
-        for (uint32_t ch = threadIdx.x; ch < chunks; ch += kBlock) {
-            const float4 t = reinterpret_cast<const float4 *>(rot_row)[ch];
-            const float y[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const float v = __fmul_rn(y[e], c);
-                mn = v < mn ? v : mn;
-                mx = v > mx ? v : mx;
-                if (v == 0.0f && z == 0xFFFFFFFFu) z = ((ch * 4 + e) << 1) | (__float_as_uint(v) >> 31);
-            }
-        }
-        if (z != 0xFFFFFFFFu && zk == kNoZero) zk = ((r * dim) << 1) + z;
-        __syncthreads();  // the next row's chunks overwrite the LDS row
+    __device__ void row_end(State &st, uint64_t r) const {
+        if (st.z != 0xFFFFFFFFu && st.zk == kNoZero) st.zk = ((r * dim) << 1) + st.z;
+        st.z = 0xFFFFFFFFu;
     }
-    rot_minmax_commit(mn, mx, zk, (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), threadIdx.x & 63, slots,
-                      base_values, first_zero);
-}
+    template <int K> __device__ void row_wave(State &st, uint64_t r, int, const uint32_t (&)[K]) const { row_end(st, r); }
+    __device__ void row_lds(State &st, uint64_t r, uint32_t *) const { row_end(st, r); }
+    __device__ void finish(State &st, uint64_t slot_id, int lane) const {
+        rot_minmax_commit(st.mn, st.mx, st.zk, slot_id, lane, slots, base_values, first_zero);
+    }
+};
 
-template <int K>
-__global__ __launch_bounds__(kBlock) void u8_rot_quantize_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
-                                                                uint32_t B, float c, int vec, float alpha, float offset,
-                                                                int fast, int distance, int invert,
-                                                                uint32_t *__restrict__ codes32, float *__restrict__ offsets,
-                                                                uint64_t row0) {
-    const float r_alpha = 1.0f / alpha;
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
-    const uint32_t chunks = dim / 4;
-    for (uint64_t r = wave; r < n_rows; r += n_waves) {
-        float y[K][4];
-        rotate_blocks_wave<K, K == 4 || K == 8>(data + r * dim, dim, B, vec, lane, y);
-        uint32_t *dst = codes32 + (row0 + r) * chunks;
-        uint32_t packed[K];
+// Pass 2, push, upsert: the codes of a row and its offset.  A chunk's codes stay in the frame's `keep` word for the
+// sequential replay; State holds the thread's code sums of the present row.
+struct RotQuantizeSink : RotSink {
+    uint32_t dim;
+    float c, alpha, offset;
+    int fast, distance, invert;
+    uint32_t *codes32;
+    float *offsets;
+    uint64_t row0;
+    struct State {
         uint32_t s1 = 0, s2 = 0;
+    };
+    __device__ void chunk(State &st, uint64_t r, uint32_t ch, int, const float (&y)[4], uint32_t &keep) const {
+        const float v[4] = {__fmul_rn(y[0], c), __fmul_rn(y[1], c), __fmul_rn(y[2], c), __fmul_rn(y[3], c)};
+        const uint32_t p = rot_quant4(v, alpha, offset, 1.0f / alpha, fast);
+        st.s1 = __builtin_amdgcn_udot4(p, 0x01010101u, st.s1, false);
+        st.s2 = __builtin_amdgcn_udot4(p, p, st.s2, false);
+        // a wave's 64 lanes x 4 B: 256 consecutive bytes of the row
+        __builtin_nontemporal_store(p, codes32 + (row0 + r) * (dim / 4) + ch);
+        keep = p;
+    }
+    // (float)s2 is the f32 sum of squares below 2^24; from there on the row replays the reference's sequential f32 sum,
+    // a chunk's four codes at a time in index order
+    __device__ bool replays(uint32_t s2) const { return distance == QAMD_L2 && s2 >= (1u << 24); }
+    __device__ static void add_squares(float &sum2, uint32_t p) {
 #pragma unroll
-        for (int k = 0; k < K; k++) {
-            const uint32_t ch = (uint32_t)(k * 64 + lane);
-            const bool live = k < K - 1 || ch < chunks;
-            const float v[4] = {__fmul_rn(y[k][0], c), __fmul_rn(y[k][1], c), __fmul_rn(y[k][2], c), __fmul_rn(y[k][3], c)};
-            const uint32_t p = live ? rot_quant4(v, alpha, offset, r_alpha, fast) : 0u;
-            packed[k] = p;
-            s1 = __builtin_amdgcn_udot4(p, 0x01010101u, s1, false);
-            s2 = __builtin_amdgcn_udot4(p, p, s2, false);
-            if (live) __builtin_nontemporal_store(p, dst + ch);  // 64 lanes x 4 B: 256 consecutive bytes of the row
+        for (int e = 0; e < 4; e++) {
+            const float cf = (float)((p >> (8 * e)) & 0xFFu);
+            sum2 += cf * cf;
         }
+    }
+    __device__ void wave_sums(State &st) const {
 #pragma unroll
         for (int m = 1; m < 64; m <<= 1) {
-            s1 += __shfl_xor(s1, m, 64);
-            s2 += __shfl_xor(s2, m, 64);
+            st.s1 += __shfl_xor(st.s1, m, 64);
+            st.s2 += __shfl_xor(st.s2, m, 64);
         }
-        s1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s1);  // every lane holds the sums: scalar from here on
-        s2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s2);
+    }
+    // The wave form: every lane holds the sums, scalar from there on, and the replay reads the codes lane by lane.
+    template <int K> __device__ void row_wave(State &st, uint64_t r, int lane, const uint32_t (&kept)[K]) const {
+        wave_sums(st);
+        const uint32_t s1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.s1);
+        const uint32_t s2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.s2);
         float sum2 = (float)s2;
-        if (distance == QAMD_L2 && s2 >= (1u << 24)) {  // the reference's sequential f32 sum, in index order
+        if (replays(s2)) {
             sum2 = 0.0f;
 #pragma unroll
-            for (int k = 0; k < K; k++) {
-                for (uint32_t l = 0; l < 64 && (uint32_t)(k * 64) + l < chunks; l++) {
-                    const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)packed[k], (int)l);
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const float cf = (float)((p >> (8 * e)) & 0xFFu);
-                        sum2 += cf * cf;
-                    }
-                }
-            }
+            for (int k = 0; k < K; k++)
+                for (uint32_t l = 0; l < 64 && (uint32_t)(k * 64) + l < dim / 4; l++)
+                    add_squares(sum2, (uint32_t)__builtin_amdgcn_readlane((int)kept[k], (int)l));
         }
         if (lane == 0) offsets[row0 + r] = rot_row_offset(dim, alpha, offset, distance, invert, s1, sum2);
+        st = State();
     }
-}
-
-// The spare words of the LDS row carry the workgroup's folds: a chunk's first word keeps its four codes (for the
-// sequential replay), words 1 and 2 of chunks 0 .. 3 the four waves' code sums.
-__global__ __launch_bounds__(kBlock) void u8_rot_quantize_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
-                                                                    uint32_t B, float c, int vec, float alpha, float offset,
-                                                                    int fast, int distance, int invert,
-                                                                    uint32_t *__restrict__ codes32, float *__restrict__ offsets,
-                                                                    uint64_t row0) {
-    extern __shared__ float rot_row[];
-    uint32_t *row_u = reinterpret_cast<uint32_t *>(rot_row);
-    const float r_alpha = 1.0f / alpha;
-    const uint32_t chunks = dim / 4;
-    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        rotate_blocks_lds(data + r * dim, dim, B, vec, rot_row);
-        uint32_t *dst = codes32 + (row0 + r) * chunks;
-        uint32_t s1 = 0, s2 = 0;
-        for (uint32_t ch = threadIdx.x; ch < chunks; ch += kBlock) {
-            const float4 t = reinterpret_cast<const float4 *>(rot_row)[ch];
-            const float v[4] = {__fmul_rn(t.x, c), __fmul_rn(t.y, c), __fmul_rn(t.z, c), __fmul_rn(t.w, c)};
-            const uint32_t p = rot_quant4(v, alpha, offset, r_alpha, fast);
-            s1 = __builtin_amdgcn_udot4(p, 0x01010101u, s1, false);
-            s2 = __builtin_amdgcn_udot4(p, p, s2, false);
-            __builtin_nontemporal_store(p, dst + ch);
-            row_u[ch * 4] = p;  // the thread's own chunk
-        }
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            s1 += __shfl_xor(s1, m, 64);
-            s2 += __shfl_xor(s2, m, 64);
-        }
+    // The workgroup form: the spare words of the LDS row carry the folds.  A chunk's first word keeps its four codes
+    // (`keep`), words 1 and 2 of chunks 0 .. 3 the four waves' code sums.
+    __device__ void row_lds(State &st, uint64_t r, uint32_t *row_u) const {
+        wave_sums(st);
         __syncthreads();  // every chunk has been read: words 1 and 2 of chunks 0 .. 3 are free
         if ((threadIdx.x & 63) == 0) {
-            row_u[(threadIdx.x >> 6) * 4 + 1] = s1;
-            row_u[(threadIdx.x >> 6) * 4 + 2] = s2;
+            row_u[(threadIdx.x >> 6) * 4 + 1] = st.s1;
+            row_u[(threadIdx.x >> 6) * 4 + 2] = st.s2;
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            s1 = s2 = 0;
-            for (int w = 0; w < kBlock / 64; w++) s1 += row_u[w * 4 + 1], s2 += row_u[w * 4 + 2];
+            uint32_t s1 = 0, s2 = 0;
+            for (int w = 0; w < kRotThreads / 64; w++) s1 += row_u[w * 4 + 1], s2 += row_u[w * 4 + 2];
             float sum2 = (float)s2;
-            if (distance == QAMD_L2 && s2 >= (1u << 24)) {
+            if (replays(s2)) {
                 sum2 = 0.0f;
-                for (uint32_t ch = 0; ch < chunks; ch++) {
-                    const uint32_t p = row_u[ch * 4];
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const float cf = (float)((p >> (8 * e)) & 0xFFu);
-                        sum2 += cf * cf;
-                    }
-                }
+                for (uint32_t ch = 0; ch < dim / 4; ch++) add_squares(sum2, row_u[ch * 4]);
             }
             offsets[row0 + r] = rot_row_offset(dim, alpha, offset, distance, invert, s1, sum2);
         }
-        __syncthreads();  // the next row's chunks overwrite the LDS row
+        st = State();
     }
-}
+};
 
-template <int K>
-__global__ __launch_bounds__(kBlock) void u8_rot_values_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
-                                                              uint32_t B, float c, int vec, float *__restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
-    const uint32_t chunks = dim / 4;
-    for (uint64_t r = wave; r < n_rows; r += n_waves) {
-        float y[K][4];
-        rotate_blocks_wave<K, K == 4 || K == 8>(data + r * dim, dim, B, vec, lane, y);
-        float4 *out_row = reinterpret_cast<float4 *>(out + r * dim);
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const uint32_t ch = (uint32_t)(k * 64 + lane);
-            if (k < K - 1 || ch < chunks)
-                out_row[ch] = make_float4(__fmul_rn(y[k][0], c), __fmul_rn(y[k][1], c), __fmul_rn(y[k][2], c), __fmul_rn(y[k][3], c));
-        }
+// The values themselves (queries, the quantile sample): dim floats per row to `out`.
+struct RotValuesSink : RotSink {
+    uint32_t dim;
+    float c;
+    float *out;
+    __device__ void chunk(State &, uint64_t r, uint32_t ch, int, const float (&y)[4], uint32_t &) const {
+        reinterpret_cast<float4 *>(out + r * dim)[ch] =
+            make_float4(__fmul_rn(y[0], c), __fmul_rn(y[1], c), __fmul_rn(y[2], c), __fmul_rn(y[3], c));
     }
-}
-
-__global__ __launch_bounds__(kBlock) void u8_rot_values_lds_kernel(const float *__restrict__ data, uint64_t n_rows, uint32_t dim,
-                                                                  uint32_t B, float c, int vec, float *__restrict__ out) {
-    extern __shared__ float rot_row[];
-    const uint32_t chunks = dim / 4;
-    for (uint64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
-        rotate_blocks_lds(data + r * dim, dim, B, vec, rot_row);
-        float4 *out_row = reinterpret_cast<float4 *>(out + r * dim);
-        for (uint32_t ch = threadIdx.x; ch < chunks; ch += kBlock) {
-            const float4 t = reinterpret_cast<const float4 *>(rot_row)[ch];
-            out_row[ch] = make_float4(__fmul_rn(t.x, c), __fmul_rn(t.y, c), __fmul_rn(t.z, c), __fmul_rn(t.w, c));
-        }
-        __syncthreads();  // the next row's chunks overwrite the LDS row
-    }
-}
+};
 
 // encode_query on device (encoded_vectors_u8.rs:290-329): one wave.
 // qbuf: [0] offset f32, [16..] codes.
@@ -1577,51 +1491,33 @@ float host_multiplier(float alpha, int distance, int invert) {  // :119-128
 
 uint64_t actual_dim_of(uint64_t dim) { return dim + (16 - dim % 16) % 16; }  // :257-259
 
-// ---- rotated stores: the launchers of the u8_rot_* kernels ----
-uint32_t rot_block_of(uint64_t dim) { return (uint32_t)(dim & (~dim + 1)); }  // B: the largest power of two dividing dim
+// ---- rotated stores: the launchers of the Rot*Sink consumers (launch_rot, rotate_blocks.hpp) ----
 // c = 2^(-log2(B) / 2) as an f32: a power of two for even log2(B), the f32 nearest to 2^-1/2 scaled by one for odd
 float rot_scale_of(uint32_t B) {
     const int lg = __builtin_ctz(B);
     return std::ldexp((lg & 1) ? 0.70710678118654752440f : 1.0f, -(lg / 2));
 }
-// A wave per row up to kRotWaveMax dimensions (K = ceil(dim / 256) chunks per lane), a workgroup per row above.
-// KERNEL / LDS_KERNEL: the two forms of one consumer; the arguments after `vec` follow.
-#define QAMD_ROT_LAUNCH(KERNEL, LDS_KERNEL, src, n, dim, s, ...)                                                          \
-    do {                                                                                                                  \
-        const uint32_t _B = rot_block_of(dim);                                                                            \
-        const float _c = rot_scale_of(_B);                                                                                \
-        const int _vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0;                                                    \
-        if ((dim) <= kRotWaveMax) {                                                                                       \
-            const dim3 _grid(grid_for((n), kBlock / 64, 8));                                                              \
-            switch (((dim) + 255) / 256) {                                                                                \
-            case 1: hipLaunchKernelGGL((KERNEL<1>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
-            case 2: hipLaunchKernelGGL((KERNEL<2>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
-            case 3: hipLaunchKernelGGL((KERNEL<3>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
-            case 4: hipLaunchKernelGGL((KERNEL<4>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
-            case 5: hipLaunchKernelGGL((KERNEL<5>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
-            case 6: hipLaunchKernelGGL((KERNEL<6>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
-            case 7: hipLaunchKernelGGL((KERNEL<7>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL((KERNEL<8>), _grid, dim3(kBlock), 0, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__); break; \
-            }                                                                                                             \
-        } else {                                                                                                          \
-            hipLaunchKernelGGL(LDS_KERNEL, dim3(grid_for((n), 1, (int)(160 * 1024 / ((dim) * 4)))), dim3(kBlock),         \
-                               (dim) * 4, s, src, n, (uint32_t)(dim), _B, _c, _vec, __VA_ARGS__);                         \
-        }                                                                                                                 \
-    } while (0)
+// A u8 row keeps its dim values: src_dim = width = dim, B the largest power of two that divides it.
+template <class SINK> qamd_status launch_rot_u8(SINK sink, const float *src, uint64_t n, uint64_t dim, hipStream_t s) {
+    if (n == 0) return QAMD_OK;
+    const uint32_t B = (uint32_t)rot_block(dim);
+    sink.dim = (uint32_t)dim, sink.c = rot_scale_of(B);
+    launch_rot(sink, src, n, (uint32_t)dim, (uint32_t)dim, B, s);
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
 
 // Every caller has checked dim (rot_dim_ok) and holds `src` in device memory.
 qamd_status launch_rot_minmax(const float *src, uint64_t n, uint64_t dim, uint32_t *slots, uint64_t base_values,
                               unsigned long long *first_zero, hipStream_t s) {
-    if (n == 0) return QAMD_OK;
-    QAMD_ROT_LAUNCH(u8_rot_minmax_kernel, u8_rot_minmax_lds_kernel, src, n, dim, s, slots, base_values, first_zero);
-    QAMD_HIP(hipGetLastError());
-    return QAMD_OK;
+    RotMinmaxSink sink;
+    sink.slots = slots, sink.base_values = base_values, sink.first_zero = first_zero;
+    return launch_rot_u8(sink, src, n, dim, s);
 }
 qamd_status launch_rot_values(const float *src, uint64_t n, uint64_t dim, float *out, hipStream_t s) {
-    if (n == 0) return QAMD_OK;
-    QAMD_ROT_LAUNCH(u8_rot_values_kernel, u8_rot_values_lds_kernel, src, n, dim, s, out);
-    QAMD_HIP(hipGetLastError());
-    return QAMD_OK;
+    RotValuesSink sink;
+    sink.out = out;
+    return launch_rot_u8(sink, src, n, dim, s);
 }
 bool rot_dim_ok(uint64_t dim) { return dim != 0 && dim % kRotBlockMin == 0 && dim <= kRotMaxDim; }
 
@@ -2283,11 +2179,11 @@ qamd_status launch_quantize(qamd_u8 *h, const float *src, uint64_t nr, uint64_t 
     // the division-free conversion needs a normal alpha well inside the exponent range (f32_to_u8_fast)
     const bool fast = alpha >= 8.673617379884035e-19f && alpha <= 1.152921504606847e+18f;  // 2^-60 .. 2^60
     if (h->rotated) {  // rotated in registers, no copy of the rotated values
-        QAMD_ROT_LAUNCH(u8_rot_quantize_kernel, u8_rot_quantize_lds_kernel, src, nr, dim, s, alpha, offset,
-                        h->four_bit ? kQuant4Bit : (int)fast,
-                        vp.distance_type, vp.invert, h->codes.as<uint32_t>(), h->offsets.as<float>(), r0);
-        QAMD_HIP(hipGetLastError());
-        return QAMD_OK;
+        RotQuantizeSink sink;
+        sink.alpha = alpha, sink.offset = offset, sink.fast = h->four_bit ? kQuant4Bit : (int)fast;
+        sink.distance = vp.distance_type, sink.invert = vp.invert;
+        sink.codes32 = h->codes.as<uint32_t>(), sink.offsets = h->offsets.as<float>(), sink.row0 = r0;
+        return launch_rot_u8(sink, src, nr, dim, s);
     }
     if (dim % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
         const uint64_t waves = (nr + 3) / 4;

@@ -25,8 +25,10 @@ B = qa.BinaryEncoding
 ONE_R, TWO_R = B.OneBitRotated, B.TwoBitsRotated
 f32 = np.float32
 
-# 2048 is the widest row the wave-per-row kernel takes (kRotWaveMax): 2049 pads to 4096 and takes the workgroup-per-row one
-ROW_DIMS = [1, 2, 3, 63, 64, 65, 100, 128, 129, 1024, 1025, 2047, 2048, 2049, 16384]
+# 2048 is the widest row the wave-per-row kernel takes (kRotWaveMax): 2049 pads to 4096 and takes the workgroup-per-row one.
+# A source row shorter than P: 257 and 300 (P = 512, two chunks per lane, dword and 16-byte loads) and 5000 (P = 8192,
+# the workgroup-per-row kernel).
+ROW_DIMS = [1, 2, 3, 63, 64, 65, 100, 128, 129, 257, 300, 1024, 1025, 2047, 2048, 2049, 5000, 16384]
 
 
 def _u(a):

@@ -34,9 +34,11 @@ ROW_DIMS = [
     320,    # 5 x 64: K = 2, half-empty last chunk
     384,    # 3 x 128: stop after lane stage 16
     768,    # 3 x 256: K = 3, no chunk stage
+    832,    # 13 x 64: K = 4, whose chunk stages 1 and 2 are present but not taken
     1280,   # 5 x 256: K = 5
     1536,   # 3 x 512: K = 6, one chunk stage
     1792,   # 7 x 256: K = 7
+    1984,   # 31 x 64: K = 8, idle lanes, no chunk stage taken
     2048,   # B = dim: the ROTATED rows
     2112,   # 33 x 64: workgroup per row, 528 chunks
     3072,   # 3 x 1024: workgroup per row, stages in LDS

@@ -44,6 +44,14 @@ ROTATED = {64: (D.Dot, False), 128: (D.L2, True), 192: (D.Dot, False), 768: (D.L
            2112: (D.L2, True), 4096: (D.L2, False)}
 ROWS = (1, 65, 1025)
 CASES = [(False, dim, n) for dim in PLAIN for n in ROWS] + [(True, dim, n) for dim in ROTATED for n in ROWS]
+# Every K = ceil(dim / 256) of the rotation's wave-per-row frame, its chunk stages taken (256, 512, 1024, 2048) and not
+# taken (832, 1984: B = 64, idle lanes), and the ends of the workgroup-per-row frame (12288 = 3 x 4096, 16384), at 65
+# rows: one pass of several workgroups.
+ROTATED_MORE = {256: (D.Dot, False), 320: (D.L2, False), 512: (D.Dot, True), 832: (D.L2, True), 1024: (D.L2, False),
+                1280: (D.Dot, False), 1792: (D.L2, True), 1984: (D.Dot, True), 2048: (D.L2, False), 12288: (D.Dot, False),
+                16384: (D.L2, False)}
+ROTATED.update(ROTATED_MORE)
+CASES += [(True, dim, 65) for dim in ROTATED_MORE]
 
 
 def _data(n, dim, seed):

@@ -40,6 +40,23 @@ SHAPES = {
 }
 ROWS = (1, 65, 1025)
 CASES = [(dim, n) for dim in SHAPES for n in ROWS]
+# Every K = ceil(dim / 256) of the wave-per-row frame, its chunk stages taken and not taken, and the ends of the
+# workgroup-per-row frame: encode parity and same bytes at 65 rows (one pass of several workgroups).
+MORE_SHAPES = {
+    256: (256, D.Dot, False),      # K = 1, all six lane stages
+    320: (64, D.L2, False),        # K = 2, half-empty last chunk
+    512: (512, D.Dot, True),       # K = 2, the chunk stage
+    832: (64, D.L2, True),         # K = 4 with B = 64: the chunk stages 1 and 2 present but not taken
+    1024: (1024, D.L2, False),     # K = 4, chunk stages 1 and 2
+    1280: (256, D.Dot, False),     # K = 5
+    1792: (256, D.L2, True),       # K = 7
+    1984: (64, D.Dot, True),       # K = 8, idle lanes, B = 64
+    2048: (2048, D.L2, False),     # K = 8, chunk stages 1, 2, 4
+    12288: (4096, D.Dot, False),   # LDS form, B = 4096, three blocks
+    16384: (16384, D.L2, False),   # the largest row
+}
+SHAPES.update(MORE_SHAPES)
+MORE_CASES = CASES + [(dim, 65) for dim in MORE_SHAPES]
 
 
 def _data(n, dim, seed):
@@ -102,7 +119,7 @@ def _check_query(h, meta, q, what):
 
 
 # ------------------------------------------------------------------------------------------------------ 1. parity
-@pytest.mark.parametrize("dim,n", CASES)
+@pytest.mark.parametrize("dim,n", MORE_CASES)
 def test_encode_parity(dim, n):
     import torch
 
@@ -144,7 +161,7 @@ def test_encode_parity(dim, n):
     _check_store(E.encode(xs, vp, rotated=True), rows, meta, "min/max with +-inf", nan_offsets=True)
 
 
-@pytest.mark.parametrize("dim", [64, 1536, 2112])
+@pytest.mark.parametrize("dim", [64, 1024, 1536, 2048, 2112])
 def test_zero_extreme_keeps_the_first_zeros_sign(dim):
     """Rows of zeros: every rotated value is a zero, and min == max == 0 carry the sign of the first one in row order."""
     for first in (0.0, -0.0):
@@ -156,7 +173,7 @@ def test_zero_extreme_keeps_the_first_zeros_sign(dim):
         _check_store(h, rows, meta, f"zeros, first {first!r}")
 
 
-@pytest.mark.parametrize("dim", [1536, 2112])
+@pytest.mark.parametrize("dim", [1536, 2048, 2112])
 def test_l2_offsets_past_2_24(dim):
     """An L2 row whose sum of squared codes reaches 2^24 takes the reference's sequential f32 sum: an interval that puts
     every code at 110 or above (110^2 * 1536 > 2^24), in the wave form and in the workgroup form."""
@@ -171,7 +188,7 @@ def test_l2_offsets_past_2_24(dim):
 
 
 # ------------------------------------------------------------------------------- 2. same bytes, same answers
-@pytest.mark.parametrize("dim,n", CASES)
+@pytest.mark.parametrize("dim,n", MORE_CASES)
 def test_same_bytes_same_answers(dim, n):
     c = _case(dim, n)
     rot = E.encode(c["x"], c["vp"], rotated=True)

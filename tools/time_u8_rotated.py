@@ -7,7 +7,7 @@ the median of `--reps` after a pre-warm (the method of tools/time_bin_rotated.py
     encode                 the rotated encode (min/max) of device data against the plain encode of the same data - by this
                            build and, with --parent-lib, by another build of the library (the parent commit's), which a
                            child process of this tool loads and times before this process touches the GPU
-    encode, given interval the same with alpha_offset given: pass 2 alone (u8_rot_quantize_kernel against quantize16_kernel)
+    encode, given interval the same with alpha_offset given: pass 2 alone (RotQuantizeSink in the rotation frame against quantize16_kernel)
     score_all, topk(30)    on the rotated store against the plain store: the kernels are the same, so a gap beyond the
                            run-to-run spread is a routing mistake to find
     encode_query           a host query against the rotated and the plain handle
