@@ -65,6 +65,9 @@ enum { QAMD_ROTATED = 8,   /* flag: or-ed onto QAMD_DOT or QAMD_L2 in qamd_vecto
        QAMD_DOT_ROTATED = 8, QAMD_L2_ROTATED = 10 };
 enum { QAMD_BITS4 = 32,    /* flag: or-ed onto QAMD_DOT or QAMD_L2, plain or rotated, in distance_type (16 is no flag) */
        QAMD_DOT_BITS4 = 32, QAMD_L2_BITS4 = 34, QAMD_DOT_ROTATED_BITS4 = 40, QAMD_L2_ROTATED_BITS4 = 42 };
+enum { QAMD_COMPACT = 128, /* flag: or-ed onto a QAMD_BITS4 metric, plain or rotated; the legal values are the four below */
+       QAMD_DOT_BITS4_COMPACT = 160, QAMD_L2_BITS4_COMPACT = 162, QAMD_DOT_ROTATED_BITS4_COMPACT = 168,
+       QAMD_L2_ROTATED_BITS4_COMPACT = 170 };
 /* A ROTATED scalar-u8 store (no counterpart in the reference).  qamd_u8_encode, qamd_u8_encoder_begin and
  * qamd_u8_from_rows take QAMD_DOT_ROTATED or QAMD_L2_ROTATED as distance_type: every row - and every query, inside
  * qamd_u8_encode_query / qamd_u8_encode_query_batch - goes through a fixed randomized Hadamard block rotation (blocks of
@@ -83,8 +86,8 @@ enum { QAMD_BITS4 = 32,    /* flag: or-ed onto QAMD_DOT or QAMD_L2, plain or rot
  * + 0.5, 0, 15)), rounded to nearest where the 7-bit code truncates; queries are encoded with the same code().  Offsets,
  * multiplier and every score formula are the reference's with this alpha.  A 15-level code over one interval only
  * ranks well when every coordinate has about the same spread: use it with QAMD_ROTATED unless the data is isotropic
- * already, and with the originals behind it (qamd_u8_topk_rescored).  QAMD_L1 | QAMD_BITS4 and any other bit beyond 8
- * and 32 are refused, and so is the flag on every qamd_pq_*, qamd_bin_*, qamd_f32_* and qamd_*_sharded_* constructor
+ * already, and with the originals behind it (qamd_u8_topk_rescored).  QAMD_L1 | QAMD_BITS4 and any other bit beyond 8,
+ * 32 and QAMD_COMPACT's 128 (below) are refused, and so is the flag on every qamd_pq_*, qamd_bin_*, qamd_f32_* and qamd_*_sharded_* constructor
  * (QAMD_ERR_ARGUMENTS, before any device call).  qamd_u8_get_metadata reports the flagged value; qamd_u8_save writes
  * the base metric plus a last key "bits":4 (after "rotation"), and a file without the key is a 7-bit store.
  * qamd_u8_upsert quantizes what it is handed with the handle's form.  A store of 32 to 2048 dims keeps, instead of the
@@ -92,6 +95,21 @@ enum { QAMD_BITS4 = 32,    /* flag: or-ed onto QAMD_DOT or QAMD_L2, plain or rot
  * rows, which the single-query scans read (388 bytes per row at dim 768, qamd_u8_scan_bytes_per_row, against 676).
  * Byte codes plus image are 1156 bytes per row at dim 768, against 1444 for a 7-bit store; the byte codes still serve
  * every other route (pairs, bursts, batches, export, save).  No new symbol: still 192 entry points. */
+/* A COMPACT 4-bit store.  QAMD_COMPACT or-ed onto a QAMD_BITS4 metric (160, 162, 168, 170), in the same
+ * three constructors and, through the metadata file, in qamd_u8_load: the store keeps its f32 row offsets and the nibble
+ * image and nothing else - 388 instead of 1156 bytes of HBM per row at dim 768 - and every answer it gives is, bit for
+ * bit, that of the 4-bit store built from the same arguments without the flag.  Builders, qamd_u8_upsert and
+ * qamd_u8_reserve write the image tile by tile through a staging buffer of byte codes; pairs and bursts gather a row's
+ * pieces from the image, exports and qamd_u8_save unpack it (the files hold the reference's byte rows and the base
+ * metric, then "bits":4, then a last key "compact":true - the only value qamd_u8_load accepts for it, and only beside
+ * "bits":4; a file without the key is not compact), and query batches take one image scan per query: the matrix cores
+ * read byte codes.  Refused with QAMD_ERR_ARGUMENTS before any device call: the flag without QAMD_BITS4, with QAMD_L1,
+ * with any unknown bit, with an actual_dim that has no nibble image (below 32 or above 2048), and on every qamd_pq_*,
+ * qamd_bin_*, qamd_f32_* and qamd_*_sharded_* constructor.  A build whose image cannot be allocated fails with
+ * QAMD_ERR_DEVICE (there are no byte codes to fall back to), and qamd_u8_from_rows of a row with a code above 15 with
+ * QAMD_ERR_ARGUMENTS.  qamd_u8_get_metadata reports the flagged value, so get_metadata -> from_rows round-trips;
+ * qamd_u8_scan_bytes_per_row is unchanged.  qamd_u8_set_lane_mode(h, 1) is accepted and changes nothing: a 4-bit pair
+ * sum is at most 2048 * 15 * 15 < 2^24, where both modes give the same bits.  No new symbol: still 192 entry points. */
 
 typedef enum { QAMD_MEM_HOST = 0, QAMD_MEM_DEVICE = 1 } qamd_mem;
 

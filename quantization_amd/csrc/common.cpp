@@ -561,6 +561,8 @@ qamd_status refuse_u8_flags(const qamd_vector_parameters *vp) {
         return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: only a single-GPU scalar-u8 store can be rotated", vp->distance_type);
     if (vp->distance_type >= 0 && (vp->distance_type & QAMD_BITS4))
         return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: only a single-GPU scalar-u8 store can have 4-bit rows", vp->distance_type);
+    if (vp->distance_type >= 0 && (vp->distance_type & QAMD_COMPACT))
+        return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: only a single-GPU scalar-u8 store can be compact", vp->distance_type);
     return QAMD_OK;
 }
 

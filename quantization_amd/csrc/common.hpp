@@ -330,7 +330,7 @@ qamd_status load_rows_file(const char *data_path, uint64_t expected, std::string
 // encoded_vectors_u8.rs:278-279) with the reader's message when it cannot.
 qamd_status read_metadata(const char *meta_path, JsonValue &root);
 
-// QAMD_ROTATED and QAMD_BITS4 (3.1y) are flags of the single-GPU scalar-u8 constructors alone: every other
+// QAMD_ROTATED, QAMD_BITS4 (3.1y) and QAMD_COMPACT (3.1z) are flags of the single-GPU scalar-u8 constructors alone: every other
 // constructor - PQ, binary, the originals, every sharded handle - refuses a distance_type that carries one, before any
 // device call.
 qamd_status refuse_u8_flags(const qamd_vector_parameters *vp);

@@ -28,6 +28,7 @@
 // summation bit for bit.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <memory>
 #include <type_traits>
@@ -1460,10 +1461,12 @@ __global__ __launch_bounds__(kBlock) void join_rows_kernel(const uint32_t *__res
 // chunk j), which writes IMG::chunk to its place in the row's block of kPackBlockRows rows.  Every (row, chunk) slot is 16
 // bytes of its own, so the slots of a block's other rows stay as they are (upsert).  `bad` (builders; null for upsert,
 // whose rows come from the store's own encoder): a code with a bit of IMG::kNoCode anywhere in the rows (bytes another
-// producer wrote: from_rows, load) sets it, and the image is then dropped.
+// producer wrote: from_rows, load) sets it, and the image is then dropped (a compact store, which has nothing else, fails).
+// `c0`: the store row whose codes codes[0] holds - 0 for the store's own byte codes, the tile's first row for the staging
+// buffer of a compact store.
 template <class IMG>
-__global__ __launch_bounds__(kBlock) void u8_pack_image_kernel(const uint4 *__restrict__ codes, uint64_t r0, uint64_t n_rows,
-                                                               uint32_t row_chunks, uint32_t pchunks,
+__global__ __launch_bounds__(kBlock) void u8_pack_image_kernel(const uint4 *__restrict__ codes, uint64_t c0, uint64_t r0,
+                                                               uint64_t n_rows, uint32_t row_chunks, uint32_t pchunks,
                                                                uint4 *__restrict__ packed, uint32_t *__restrict__ bad) {
     const uint64_t total = n_rows * pchunks, stride = (uint64_t)gridDim.x * kBlock;
     uint32_t seen = 0;
@@ -1471,9 +1474,113 @@ __global__ __launch_bounds__(kBlock) void u8_pack_image_kernel(const uint4 *__re
         const uint64_t r = r0 + t / pchunks;
         const uint32_t j = (uint32_t)(t % pchunks);
         packed[((r / kPackBlockRows) * pchunks + j) * kPackBlockRows + r % kPackBlockRows] =
-            IMG::chunk(codes + r * row_chunks, j, row_chunks, pchunks, seen);
+            IMG::chunk(codes + (r - c0) * row_chunks, j, row_chunks, pchunks, seen);
     }
     if (bad && (seen & IMG::kNoCode)) atomicOr(bad, 1u);
+}
+
+// ---- compact 4-bit stores: the two kernels that read the nibble image where the others read byte codes ----
+// 16-byte index of image chunk j of row r (u8_internal.hpp).
+__device__ __forceinline__ uint64_t nibble_at(uint64_t r, uint32_t j, uint32_t pchunks) {
+    return ((r / kPackBlockRows) * pchunks + j) * kPackBlockRows + r % kPackBlockRows;
+}
+__device__ __forceinline__ uint4 nibbles_lo(const uint4 &w) { return and16(w, 0x0F0F0F0Fu); }
+__device__ __forceinline__ uint4 nibbles_hi(const uint4 &w) {
+    return make_uint4((w.x >> 4) & 0x0F0F0F0Fu, (w.y >> 4) & 0x0F0F0F0Fu, (w.z >> 4) & 0x0F0F0F0Fu, (w.w >> 4) & 0x0F0F0F0Fu);
+}
+
+// Image rows back into byte codes: out row l gets the codes of store row rows[l] (a row >= count is read as row 0, as
+// u8_gather_rows_kernel does) or, without a list, of row r0 + l; `pitch` bytes between out rows, a multiple of 16.  One
+// thread per (row, image chunk): 16 bytes in, the two code chunks 2j and 2j + 1 out (the second only where the row has it).
+// q_offs (optional): the rows' stored offsets, for the rows that become the queries of score_internal.
+__global__ __launch_bounds__(kBlock) void u8_nibble_unpack_kernel(const uint4 *__restrict__ image,
+                                                                  const float *__restrict__ offsets,
+                                                                  const uint32_t *__restrict__ rows, uint64_t r0, uint64_t n_rows,
+                                                                  uint32_t count, uint32_t row_chunks, uint32_t pchunks,
+                                                                  uint8_t *__restrict__ out, uint64_t pitch,
+                                                                  float *__restrict__ q_offs) {
+    const uint64_t total = n_rows * pchunks, stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += stride) {
+        const uint64_t l = t / pchunks;
+        const uint32_t j = (uint32_t)(t % pchunks);
+        uint64_t r = r0 + l;
+        if (rows) r = rows[l] < count ? rows[l] : 0u;
+        const uint4 w = image[nibble_at(r, j, pchunks)];
+        uint4 *dst = reinterpret_cast<uint4 *>(out + l * pitch);
+        dst[2 * j] = nibbles_lo(w);
+        if (2 * j + 1 < row_chunks) dst[2 * j + 1] = nibbles_hi(w);
+        if (q_offs && j == 0) q_offs[l] = offsets[r];
+    }
+}
+
+// u8_score_pairs_kernel over the nibble image: out[k] = score(query of pair k, ids[k]), the same three ways to name the
+// query (one byte-code query for every pair; query l of a byte-code batch for list l; stored row list_rows[l] for list l)
+// and the same walk through the lists.  One 16-lane group per pair; lane `sub` takes image chunks sub, sub + 16, ... of
+// the row - ITERS = ceil(pchunks / 16) <= 4, all of them in flight at once.  A row's chunks lie a kilobyte apart (the
+// image is laid out for the scan, a row per lane), so a pair costs `pchunks` 64-byte sectors where the byte codes cost
+// actual_dim / 64.  A chunk is expanded as the scan's Image4 reads it: low nibbles against code chunk 2j, high nibbles
+// against 2j + 1, which a row of odd row_chunks does not have (its high nibbles are zero; the query chunk is not read).
+// For a stored-row query the other side is expanded the same way.  The integer sum is the one the byte codes give (at
+// most 2048 * 15 * 15 < 2^24: exact in f32 in either lane mode), the epilogue is u8_score_pairs_kernel's: the same bits.
+template <int ITERS>
+__global__ __launch_bounds__(kBlock) void u8_nibble_pairs_kernel(
+    const uint4 *__restrict__ image, const float *__restrict__ offsets, const uint4 *__restrict__ q_single,
+    const float *__restrict__ q_off_single, const uint8_t *__restrict__ q_batch, uint32_t q_pitch,
+    const float *__restrict__ q_offs, const uint32_t *__restrict__ lists, uint32_t n_lists,
+    const uint32_t *__restrict__ list_rows, float multiplier, float diff, int mode, const uint32_t *__restrict__ ids,
+    uint64_t n_ids, uint32_t n_rows, uint32_t row_chunks, uint32_t pchunks, uint32_t pairs_per_block, float *__restrict__ out) {
+    constexpr int G = 16, GROUPS = kBlock / G;
+    __shared__ uint32_t first_list;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane % G, group = threadIdx.x / G;
+    const uint64_t p0 = (uint64_t)blockIdx.x * pairs_per_block;
+    const uint64_t p1 = p0 + pairs_per_block < n_ids ? p0 + pairs_per_block : n_ids;
+    uint32_t l = lists ? first_list_of_block(lists, n_lists, p0, &first_list) : 0u;
+    const float q_off_one = lists ? 0.0f : *q_off_single;
+    for (uint64_t k = p0 + group; k < p1; k += GROUPS) {
+        const uint32_t row = ids[k];
+        bool ok = row < n_rows;
+        const uint4 *qp = q_single;
+        float q_off = q_off_one;
+        uint32_t qrow = 0;
+        if (lists) {
+            l = advance_list(lists, n_lists, l, k);
+            if (list_rows) {
+                const uint32_t qr = list_rows[l];
+                ok = ok && qr < n_rows;
+                qrow = qr < n_rows ? qr : 0u;
+                q_off = offsets[qrow];
+            } else {
+                qp = reinterpret_cast<const uint4 *>(q_batch + (size_t)l * q_pitch);
+                q_off = q_offs[l];
+            }
+        }
+        const uint32_t r = ok ? row : 0u;
+        uint4 v[ITERS], qa[ITERS], qb[ITERS];
+#pragma unroll
+        for (int it = 0; it < ITERS; it++) {  // unconditional loads (clamped chunk): all of them issue back to back
+            const uint32_t j = sub + it * G, jc = j < pchunks ? j : pchunks - 1;
+            v[it] = image[nibble_at(r, jc, pchunks)];
+            if (list_rows) {
+                const uint4 wq = image[nibble_at(qrow, jc, pchunks)];
+                qa[it] = nibbles_lo(wq);
+                qb[it] = nibbles_hi(wq);
+            } else {
+                qa[it] = qp[2 * jc];
+                qb[it] = qp[2 * jc + 1 < row_chunks ? 2 * jc + 1 : 2 * jc];  // no such chunk: dotted with zero nibbles
+            }
+        }
+        uint32_t acc = 0;
+#pragma unroll
+        for (int it = 0; it < ITERS; it++) {
+            if (sub + it * G < pchunks) {
+                acc = dot16(nibbles_lo(v[it]), qa[it], acc);
+                acc = dot16(nibbles_hi(v[it]), qb[it], acc);
+            }
+        }
+        acc = group_sum<G>(acc);
+        if (sub == 0) out[k] = ok ? epilogue(multiplier, acc, q_off, offsets[row], diff, mode) : __builtin_nanf("");
+    }
 }
 
 int grid_for(uint64_t work_items, uint64_t per_block, int blocks_per_cu) {
@@ -1528,13 +1635,22 @@ bool rot_dim_ok(uint64_t dim) { return dim != 0 && dim % kRotBlockMin == 0 && di
 
 namespace {
 
+U8Image u8_image_of(uint32_t rc, bool four_bit, int distance);
+
 qamd_status alloc_store(qamd_u8 *h) {
     h->capacity = h->count;
     h->padded_rows = padded_rows_of(h->capacity);
     h->row_chunks = (uint32_t)(h->meta.actual_dim / 16);
     // every builder (encode, from_rows, load) writes all `count` rows; only the padding is zeroed
-    QAMD_TRY(h->codes.alloc_zero_tail(h->padded_rows * h->meta.actual_dim, h->count * h->meta.actual_dim));
     QAMD_TRY(h->offsets.alloc_zero_tail(h->padded_rows * sizeof(float), h->count * sizeof(float)));
+    if (h->compact) {  // offsets and image, no byte codes; the builders write the image tile by tile
+        h->image = u8_image_of(h->row_chunks, true, h->meta.vector_parameters.distance_type);  // split_distance: it has one
+        const uint64_t chunk_bytes = (uint64_t)h->image.chunks * 16;
+        // rows of a block are interleaved: the padding rows of the last block are zeroed with it, before it is written
+        // (a store that keeps its byte codes goes on without an image it cannot allocate; here that is QAMD_ERR_DEVICE)
+        return h->packed.alloc_zero_tail(h->padded_rows * chunk_bytes, h->count / kPackBlockRows * kPackBlockRows * chunk_bytes);
+    }
+    QAMD_TRY(h->codes.alloc_zero_tail(h->padded_rows * h->meta.actual_dim, h->count * h->meta.actual_dim));
     return QAMD_OK;
 }
 
@@ -1549,12 +1665,64 @@ U8Image u8_image_of(uint32_t rc, bool four_bit, int distance) {
 }
 
 // Writes rows [r0, r0 + n_rows) of the store's image from their byte codes; `bad`: u8_pack_image_kernel.
-qamd_status launch_pack(const qamd_u8 *h, uint64_t r0, uint64_t n_rows, uint32_t *bad, hipStream_t s) {
+// `tile` (a compact store): the byte codes of exactly these rows, in the staging buffer.
+qamd_status launch_pack(const qamd_u8 *h, uint64_t r0, uint64_t n_rows, uint32_t *bad, hipStream_t s,
+                        const uint4 *tile = nullptr) {
     const auto kernel = h->image.kind == U8_IMAGE_NIBBLE ? u8_pack_image_kernel<Image4> : u8_pack_image_kernel<Image7>;
-    hipLaunchKernelGGL(kernel, dim3(grid_for(n_rows * h->image.chunks, kBlock, 8)), dim3(kBlock), 0, s, h->codes.as<uint4>(),
-                       r0, n_rows, h->row_chunks, h->image.chunks, h->packed.as<uint4>(), bad);
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n_rows * h->image.chunks, kBlock, 8)), dim3(kBlock), 0, s,
+                       tile ? tile : h->byte_codes<uint4>(), tile ? r0 : 0, r0, n_rows, h->row_chunks, h->image.chunks,
+                       h->packed.as<uint4>(), bad);
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
+}
+
+// ---- compact stores: tiles of byte codes on their way into the image, and image rows on their way out ----
+// Rows per tile: a multiple of the image's block, so that the tiles of a builder that starts at row 0 cover whole blocks.
+// 64 MiB of byte codes, small enough to stay in the 256 MB Infinity Cache between the quantize kernel and the pack
+// kernel - which bought no measurable time against tiles of 16 MB to 768 MB; kept because it bounds the
+// staging buffer.
+constexpr uint64_t kCompactTileBytes = 64ull << 20;
+uint64_t compact_tile_rows(const qamd_u8 *h) {
+    const uint64_t rows = stage_bytes(kCompactTileBytes) / std::max<uint64_t>(h->meta.actual_dim, 1);
+    return std::max<uint64_t>(kPackBlockRows, rows / kPackBlockRows * kPackBlockRows);
+}
+// The staging buffer with room for a tile of `n_rows` rows (grown on demand, reused from tile to tile in stream order).
+qamd_status compact_stage(qamd_u8 *h, uint64_t n_rows, hipStream_t s) {
+    const uint64_t need = std::min(compact_tile_rows(h), round_up(n_rows, kPackBlockRows)) * h->meta.actual_dim;
+    if (h->stage.bytes >= need) return QAMD_OK;
+    QAMD_HIP(hipStreamSynchronize(s));  // a smaller one may still be read
+    return h->stage.alloc(need);
+}
+// The end of every builder and upsert of a compact store: the staging buffer goes back.
+void compact_done(qamd_u8 *h) {
+    h->stage.release();
+    h->packed_rows.release();
+}
+
+// Byte codes of image rows [r0, r0 + n) or, with a device list, of rows[0 .. n): u8_nibble_unpack_kernel.
+qamd_status launch_unpack(const qamd_u8 *h, const uint32_t *rows_dev, uint64_t r0, uint64_t n, uint8_t *out, uint64_t pitch,
+                          float *q_offs, hipStream_t s) {
+    if (n == 0) return QAMD_OK;
+    hipLaunchKernelGGL(u8_nibble_unpack_kernel, dim3(grid_for(n * h->image.chunks, kBlock, 8)), dim3(kBlock), 0, s,
+                       h->packed.as<uint4>(), h->offsets.as<float>(), rows_dev, r0, n, (uint32_t)h->count, h->row_chunks,
+                       h->image.chunks, out, pitch, q_offs);
+    QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
+
+// Stored row i as the query of a whole-store call or of score_internal_ids: its byte codes and where its offset lies.
+// A store with byte codes points into them; a compact one unpacks the row into `tmp`, which lives until the caller's
+// launches are enqueued (freed in stream order).
+qamd_status stored_row_query(const qamd_u8 *h, uint32_t i, StreamBuf &tmp, hipStream_t s, const uint4 *&qc, const float *&qo) {
+    qo = h->offsets.as<float>() + i;
+    if (!h->compact) {
+        qc = h->byte_codes<uint4>() + (uint64_t)i * h->row_chunks;
+        return QAMD_OK;
+    }
+    QAMD_TRY(tmp.alloc(h->meta.actual_dim, s, i >= h->count));
+    qc = tmp.as<uint4>();
+    if (i >= h->count) return QAMD_OK;  // (an empty store's top-k names a row that no kernel will read)
+    return launch_unpack(h, nullptr, i, 1, tmp.as<uint8_t>(), h->meta.actual_dim, nullptr, s);
 }
 
 // Builds the store's scan image from its byte codes; run at the end of every builder.  The 7-bit image costs 7/8 of the
@@ -1562,6 +1730,7 @@ qamd_status launch_pack(const qamd_u8 *h, uint64_t r0, uint64_t n_rows, uint32_t
 // HBM than its own size, and a failed allocation only leaves the store on its byte codes.  So does a code the format
 // cannot hold (rows another producer wrote).
 qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
+    if (h->compact) return compact_done(h), QAMD_OK;  // the image is what the builder wrote, tile by tile
     h->packed.release();
     h->packed_rows.release();
     h->image = U8Image{};
@@ -1630,7 +1799,7 @@ template <bool IS_L1> struct ScanLaunch {
             with_bool(filt != nullptr, [&](auto fi) {
                 with_epi(e.mode, [&](auto epi) {
                     hipLaunchKernelGGL((u8_scan_kernel<G, ITERS, UNROLL, IS_L1, ex, fi, epi>), dim3(grid), dim3(kScanBlock), 0,
-                                       s, h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,
+                                       s, h->byte_codes<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,
                                        (uint32_t)scan_rows(h, e), h->row_chunks, out, filt ? *filt : TopkFilter{}, e.diff);
                 });
             });
@@ -1700,7 +1869,7 @@ void launch_scan_generic(const qamd_u8 *h, const uint4 *qc, const float *qo, flo
     uint64_t waves = (scan_rows(h, e) + 3) / 4;  // one wave per 4-row tile (non-persistent, see u8_scan_kernel)
     unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
     with_epi(e.mode, [&](auto epi) {
-        hipLaunchKernelGGL((u8_scan_generic_kernel<IS_L1, epi>), dim3(grid), dim3(kBlock), 0, s, h->codes.as<uint4>(),
+        hipLaunchKernelGGL((u8_scan_generic_kernel<IS_L1, epi>), dim3(grid), dim3(kBlock), 0, s, h->byte_codes<uint4>(),
                            h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)scan_rows(h, e), h->row_chunks, out,
                            e.diff);
     });
@@ -1719,7 +1888,7 @@ template <bool IS_L1> struct SmallLaunch {
             const qamd_vector_parameters &vp = h->meta.vector_parameters;
             with_bool(exact, [&](auto ex) {
                 hipLaunchKernelGGL((u8_topk_small_fused_kernel<G, ITERS, IS_L1, ex>), dim3(pl.workgroups), dim3(1024), 0, s,
-                                   h->codes.as<uint4>(), h->offsets.as<float>(), qv, fq->qdim, (uint32_t)h->meta.actual_dim,
+                                   h->byte_codes<uint4>(), h->offsets.as<float>(), qv, fq->qdim, (uint32_t)h->meta.actual_dim,
                                    h->meta.alpha, h->meta.offset, vp.distance_type, vp.invert, fq->qbuf, h->meta.multiplier,
                                    (uint32_t)h->count, h->row_chunks, pl.rows_per_wg, p);
             });
@@ -1729,7 +1898,7 @@ template <bool IS_L1> struct SmallLaunch {
         with_bool(exact, [&](auto ex) {
             with_epi(e.mode, [&](auto epi) {
                 hipLaunchKernelGGL((u8_topk_small_kernel<G, ITERS, IS_L1, ex, epi>), dim3(pl.workgroups), dim3(1024), 0, s,
-                                   h->codes.as<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,
+                                   h->byte_codes<uint4>(), h->offsets.as<float>(), qc, qo, h->meta.multiplier,
                                    (uint32_t)h->count, h->row_chunks, pl.rows_per_wg, p, e.diff);
             });
         });
@@ -1777,7 +1946,7 @@ void launch_multi_shape(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitc
     h->last_scan_packed.store(0, std::memory_order_relaxed);
 #define QAMD_U8_MULTI(EX, FI, EPI)                                                                                 \
     hipLaunchKernelGGL((u8_scan_multi_kernel<G, ITERS, UNROLL, NQ, IS_L1, EX, FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, \
-                       h->codes.as<uint4>(), h->offsets.as<float>(), qcodes, (uint32_t)q_pitch, q_offs, nq_valid,   \
+                       h->byte_codes<uint4>(), h->offsets.as<float>(), qcodes, (uint32_t)q_pitch, q_offs, nq_valid,   \
                        h->meta.multiplier, (uint32_t)n_rows, h->row_chunks, out, n_rows,                           \
                        slices ? *slices : TopkFilterSlices{}, e.diff)
     if (e.mode == EPI_INTERNAL) {  // score_internal of gathered rows: scores only (no filtering form is instantiated)
@@ -1796,8 +1965,10 @@ void launch_multi_shape(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitc
 // Lane mode 1 on a Dot / L2 store: every score comes from the avx2.c lane-order kernels (u8_scan_avx2_lanes_kernel,
 // u8_score_pairs_kernel<.., LANES>); the kernels that sum the exact integer (single- and multi-query scans, the fused
 // and single-launch top-k, the matrix cores) are not used.  L1 has no lane order: both modes are the exact sum.
+// A compact store has no lane order either: its pair sums stay below 2^24, where both modes give the same
+// bits, so mode 1 is accepted and its image routes go on serving.
 bool lane_order(const qamd_u8 *h) {
-    return h->lane_mode == 1 && h->meta.vector_parameters.distance_type != QAMD_L1;
+    return h->lane_mode == 1 && h->meta.vector_parameters.distance_type != QAMD_L1 && !h->compact;
 }
 
 // Widest pass of the multi-query scan for this row size: 4 queries (2 for rows of more than 96
@@ -1810,7 +1981,7 @@ bool lane_order(const qamd_u8 *h) {
 uint32_t multi_width(const qamd_u8 *h) {
     const uint32_t rc = h->row_chunks, iters = (rc + 15) / 16;
     const bool l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
-    if (rc < 9 || iters > 8 || lane_order(h)) return 0;
+    if (rc < 9 || iters > 8 || lane_order(h) || h->compact) return 0;  // (the multi-query scan reads byte codes)
     return l1 && iters <= 3 ? 8 : iters <= 6 ? 4 : 2;
 }
 
@@ -1845,7 +2016,7 @@ bool fused_capable(const qamd_u8 *h) { return !lane_order(h) && h->row_chunks <=
 // The single-launch top-k serves this store and k (and, for a fused query, these dims): its plan.
 bool u8_small_plan(const qamd_u8 *h, uint32_t k, SmallTopkPlan &plan) {
     const int g = small_group(h->row_chunks);
-    if (!g || !fused_capable(h)) return false;
+    if (!g || !fused_capable(h) || h->compact) return false;  // (it reads byte codes: a compact store has none)
     const uint32_t tile = 2 * (64 / g);
     const uint32_t least = (uint32_t)std::max<uint64_t>(16 * tile, (128 * 1024) / std::max<uint64_t>(h->meta.actual_dim, 1));
     return small_topk_plan(h->count, k, tile, least, plan);
@@ -1862,7 +2033,7 @@ qamd_status scan_ptrs(const qamd_u8 *h, const uint4 *qc, const float *qo, float 
         uint64_t waves = (scan_rows(h, e) + 3) / 4;
         unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
         with_epi(e.mode, [&](auto epi) {
-            hipLaunchKernelGGL((u8_scan_avx2_lanes_kernel<true, epi>), dim3(grid), dim3(kBlock), 0, s, h->codes.as<uint4>(),
+            hipLaunchKernelGGL((u8_scan_avx2_lanes_kernel<true, epi>), dim3(grid), dim3(kBlock), 0, s, h->byte_codes<uint4>(),
                                h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)scan_rows(h, e), h->row_chunks,
                                out_dev, e.diff);
         });
@@ -1897,12 +2068,12 @@ qamd_status launch_pairs(const qamd_u8 *h, const uint4 *qc, const float *qo, con
     const unsigned grid = (unsigned)((n_ids + ppb - 1) / ppb);
     const uint32_t iters = (h->row_chunks + 15) / 16;
 #define QAMD_U8_PAIRS(IT)                                                                                                \
-    hipLaunchKernelGGL((u8_score_pairs_kernel<IS_L1, IT>), dim3(grid), dim3(kBlock), 0, s, h->codes.as<uint4>(),         \
+    hipLaunchKernelGGL((u8_score_pairs_kernel<IS_L1, IT>), dim3(grid), dim3(kBlock), 0, s, h->byte_codes<uint4>(),         \
                        h->offsets.as<float>(), qc, qo, q_batch, q_pitch, q_offs, lists, n_lists, list_rows,              \
                        h->meta.multiplier, diff, mode, ids_dev, n_ids, (uint32_t)h->count, h->row_chunks, (uint32_t)ppb, \
                        out_dev)
     if (!IS_L1 && lane_order(h)) {
-        hipLaunchKernelGGL((u8_score_pairs_kernel<false, 0, true>), dim3(grid), dim3(kBlock), 0, s, h->codes.as<uint4>(),
+        hipLaunchKernelGGL((u8_score_pairs_kernel<false, 0, true>), dim3(grid), dim3(kBlock), 0, s, h->byte_codes<uint4>(),
                            h->offsets.as<float>(), qc, qo, q_batch, q_pitch, q_offs, lists, n_lists, list_rows,
                            h->meta.multiplier, diff, mode, ids_dev, n_ids, (uint32_t)h->count, h->row_chunks, (uint32_t)ppb,
                            out_dev);
@@ -1929,6 +2100,24 @@ qamd_status score_pairs_dev(const qamd_u8 *h, const uint4 *qc, const float *qo, 
                             const float *q_offs, const uint32_t *lists, uint32_t n_lists, const uint32_t *list_rows,
                             float diff, int mode, const uint32_t *ids_dev, uint64_t n_ids, float *out_dev, hipStream_t s) {
     if (n_ids == 0) return QAMD_OK;
+    if (h->compact) {  // the pairs are gathered from the nibble image
+        const uint64_t ppb = pairs_per_block(n_ids, 16);
+        const unsigned grid = (unsigned)((n_ids + ppb - 1) / ppb);
+#define QAMD_U8_NIBBLE_PAIRS(IT)                                                                                          \
+    hipLaunchKernelGGL((u8_nibble_pairs_kernel<IT>), dim3(grid), dim3(kBlock), 0, s, h->packed.as<uint4>(),               \
+                       h->offsets.as<float>(), qc, qo, q_batch, q_pitch, q_offs, lists, n_lists, list_rows,               \
+                       h->meta.multiplier, diff, mode, ids_dev, n_ids, (uint32_t)h->count, h->row_chunks, h->image.chunks, \
+                       (uint32_t)ppb, out_dev)
+        switch ((h->image.chunks + 15) / 16) {  // at most 64 chunks (u8_image_of)
+            case 1: QAMD_U8_NIBBLE_PAIRS(1); break;
+            case 2: QAMD_U8_NIBBLE_PAIRS(2); break;
+            case 3: QAMD_U8_NIBBLE_PAIRS(3); break;
+            default: QAMD_U8_NIBBLE_PAIRS(4); break;
+        }
+#undef QAMD_U8_NIBBLE_PAIRS
+        QAMD_HIP(hipGetLastError());
+        return QAMD_OK;
+    }
     if (h->meta.vector_parameters.distance_type == QAMD_L1)
         return launch_pairs<true>(h, qc, qo, q_batch, q_pitch, q_offs, lists, n_lists, list_rows, diff, mode, ids_dev, n_ids, out_dev, s);
     return launch_pairs<false>(h, qc, qo, q_batch, q_pitch, q_offs, lists, n_lists, list_rows, diff, mode, ids_dev, n_ids, out_dev, s);
@@ -1988,9 +2177,13 @@ qamd_status score_internal_rows_dev(const qamd_u8 *h, const uint32_t *rows_dev, 
     QAMD_TRY(stage.alloc(code_bytes + (size_t)n * 4, s));
     uint8_t *qcodes = stage.as<uint8_t>();
     float *q_offs = reinterpret_cast<float *>(qcodes + code_bytes);
-    hipLaunchKernelGGL(u8_gather_rows_kernel, dim3(n), dim3(64), 0, s, h->codes.as<uint4>(), h->offsets.as<float>(), rows_dev,
-                       (uint32_t)h->count, h->row_chunks, reinterpret_cast<uint4 *>(qcodes), q_offs);
-    QAMD_HIP(hipGetLastError());
+    if (h->compact) {  // the rows come out of the image; every one of them then takes the image scan (width 0)
+        QAMD_TRY(launch_unpack(h, rows_dev, 0, n, qcodes, pitch, q_offs, s));
+    } else {
+        hipLaunchKernelGGL(u8_gather_rows_kernel, dim3(n), dim3(64), 0, s, h->byte_codes<uint4>(), h->offsets.as<float>(),
+                           rows_dev, (uint32_t)h->count, h->row_chunks, reinterpret_cast<uint4 *>(qcodes), q_offs);
+        QAMD_HIP(hipGetLastError());
+    }
     const ScanEpi e{internal_diff(h), EPI_INTERNAL, n_ids};
     const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
     const uint32_t width = multi_width(h);
@@ -2170,9 +2363,10 @@ struct MinMaxAcc {
     }
 };
 
-// PASS 2 for `nr` device-resident rows (encoded_vectors_u8.rs:73-118): rows r0 .. r0+nr of the store.
-qamd_status launch_quantize(qamd_u8 *h, const float *src, uint64_t nr, uint64_t r0, float alpha, float offset,
-                            hipStream_t s) {
+// PASS 2 for `nr` device-resident rows (encoded_vectors_u8.rs:73-118): their codes to rows r0 .. r0+nr of `codes32`, their
+// offsets to the same rows of `offsets`.
+qamd_status quantize_rows(const qamd_u8 *h, const float *src, uint64_t nr, uint32_t *codes32, float *offsets, uint64_t r0,
+                          float alpha, float offset, hipStream_t s) {
     if (nr == 0) return QAMD_OK;
     const qamd_vector_parameters &vp = h->meta.vector_parameters;
     const uint64_t dim = vp.dim;
@@ -2182,7 +2376,7 @@ qamd_status launch_quantize(qamd_u8 *h, const float *src, uint64_t nr, uint64_t 
         RotQuantizeSink sink;
         sink.alpha = alpha, sink.offset = offset, sink.fast = h->four_bit ? kQuant4Bit : (int)fast;
         sink.distance = vp.distance_type, sink.invert = vp.invert;
-        sink.codes32 = h->codes.as<uint32_t>(), sink.offsets = h->offsets.as<float>(), sink.row0 = r0;
+        sink.codes32 = codes32, sink.offsets = offsets, sink.row0 = r0;
         return launch_rot_u8(sink, src, nr, dim, s);
     }
     if (dim % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
@@ -2194,15 +2388,15 @@ qamd_status launch_quantize(qamd_u8 *h, const float *src, uint64_t nr, uint64_t 
         if (h->four_bit)  /* 4-bit codes take the exact division */                              \
             hipLaunchKernelGGL((quantize16_kernel<IT, false, true>), dim3(grid), dim3(kScanBlock), 0, s, src, nr, \
                                (uint32_t)dim, (uint32_t)h->meta.actual_dim, alpha, offset, vp.distance_type,  \
-                               vp.invert, h->codes.as<uint32_t>(), h->offsets.as<float>(), r0);               \
+                               vp.invert, codes32, offsets, r0);                                              \
         else if (fast)                                                                                        \
             hipLaunchKernelGGL((quantize16_kernel<IT, true>), dim3(grid), dim3(kScanBlock), 0, s, src, nr,    \
                                (uint32_t)dim, (uint32_t)h->meta.actual_dim, alpha, offset, vp.distance_type,  \
-                               vp.invert, h->codes.as<uint32_t>(), h->offsets.as<float>(), r0);               \
+                               vp.invert, codes32, offsets, r0);                                              \
         else                                                                                                  \
             hipLaunchKernelGGL((quantize16_kernel<IT, false>), dim3(grid), dim3(kScanBlock), 0, s, src, nr,   \
                                (uint32_t)dim, (uint32_t)h->meta.actual_dim, alpha, offset, vp.distance_type,  \
-                               vp.invert, h->codes.as<uint32_t>(), h->offsets.as<float>(), r0);               \
+                               vp.invert, codes32, offsets, r0);                                              \
     } while (0)
         if (per_lane <= 2) QAMD_Q16(2);
         else if (per_lane <= 4) QAMD_Q16(4);
@@ -2216,9 +2410,26 @@ qamd_status launch_quantize(qamd_u8 *h, const float *src, uint64_t nr, uint64_t 
         int grid = grid_for(nr, kBlock / 64, 8);
         hipLaunchKernelGGL(quantize_kernel, dim3(grid), dim3(kBlock), 0, s, src, nr, (uint32_t)dim,
                            (uint32_t)h->meta.actual_dim, alpha, offset, vp.distance_type, vp.invert,
-                           h->codes.as<uint32_t>(), h->offsets.as<float>(), r0, (int)h->four_bit);
+                           codes32, offsets, r0, (int)h->four_bit);
     }
     QAMD_HIP(hipGetLastError());
+    return QAMD_OK;
+}
+
+// Rows r0 .. r0+nr of the store from `nr` device-resident rows.  A compact store goes tile by tile: the same
+// quantize kernels write a tile's byte codes into the staging buffer (and its offsets into their place), the pack kernel
+// moves them into the image at the tile's rows.  Tiles are whole blocks of the image but for a first row inside a block
+// (an upsert, a push after an odd batch): every (row, chunk) slot of the image is 16 bytes of its own.
+qamd_status launch_quantize(qamd_u8 *h, const float *src, uint64_t nr, uint64_t r0, float alpha, float offset,
+                            hipStream_t s) {
+    if (!h->compact) return quantize_rows(h, src, nr, h->byte_codes<uint32_t>(), h->offsets.as<float>(), r0, alpha, offset, s);
+    const uint64_t tile = compact_tile_rows(h), dim = h->meta.vector_parameters.dim;
+    if (nr) QAMD_TRY(compact_stage(h, nr, s));
+    for (uint64_t t = 0; t < nr; t += tile) {
+        const uint64_t n = std::min(tile, nr - t);
+        QAMD_TRY(quantize_rows(h, src + t * dim, n, h->stage.as<uint32_t>(), h->offsets.as<float>() + r0 + t, 0, alpha, offset, s));
+        QAMD_TRY(launch_pack(h, r0 + t, n, nullptr, s, h->stage.as<uint4>()));
+    }
     return QAMD_OK;
 }
 
@@ -2234,13 +2445,25 @@ bool quantile_cut(uint64_t slice, uint64_t dim, float quantile, uint64_t &cut) {
 }
 
 // The distance_type a u8 constructor is handed: a qamd_distance, or QAMD_DOT / QAMD_L2 with QAMD_ROTATED,
-// QAMD_BITS4 (3.1y) or both or-ed on.  The handle keeps `base` in its metadata and the flags beside it.  No device call.
-qamd_status split_distance(const qamd_vector_parameters &vp, int &base, bool &rotated, bool &four_bit) {
+// QAMD_BITS4 (3.1y) or both or-ed on, and QAMD_COMPACT (3.1z) on top of QAMD_BITS4.  The handle keeps `base` in its
+// metadata and the flags beside it.  No device call.
+struct U8Flags {
+    bool rotated = false, four_bit = false, compact = false;
+};
+constexpr int kU8FlagBits = QAMD_ROTATED | QAMD_BITS4 | QAMD_COMPACT;
+qamd_status split_distance(const qamd_vector_parameters &vp, int &base, U8Flags &f) {
     const int dt = vp.distance_type;
+    bool &rotated = f.rotated, &four_bit = f.four_bit;
     rotated = dt >= 0 && (dt & QAMD_ROTATED) != 0;
     four_bit = dt >= 0 && (dt & QAMD_BITS4) != 0;
-    base = dt >= 0 ? (dt & ~(QAMD_ROTATED | QAMD_BITS4)) : dt;
+    f.compact = dt >= 0 && (dt & QAMD_COMPACT) != 0;
+    base = dt >= 0 ? (dt & ~kU8FlagBits) : dt;
     if (base < 0 || base > 2) return fail(QAMD_ERR_ARGUMENTS, "bad distance_type %d", dt);
+    if (f.compact && !four_bit)
+        return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: QAMD_COMPACT goes with QAMD_BITS4 only", dt);
+    if (f.compact && base != QAMD_L1 && !u8_image_of((uint32_t)std::min<uint64_t>(actual_dim_of(vp.dim) / 16, 0xFFFFFFFFull), true, base).kind)
+        return fail(QAMD_ERR_ARGUMENTS, "a compact store keeps only its nibble image, which rows of 32 to 2048 codes have, not %llu",
+                    (unsigned long long)actual_dim_of(vp.dim));
     if (four_bit && base == QAMD_L1)
         return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: 4-bit rows are for Dot and L2 stores", dt);
     if (rotated && base == QAMD_L1)
@@ -2267,8 +2490,9 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
                            void *stop_user, void *stream, qamd_u8 **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     int base_distance = 0;
-    bool rotated = false, four_bit = false;
-    QAMD_TRY(split_distance(*vp, base_distance, rotated, four_bit));
+    U8Flags flags;
+    QAMD_TRY(split_distance(*vp, base_distance, flags));
+    const bool rotated = flags.rotated, four_bit = flags.four_bit;
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     if (vp->count > 0 && vp->dim > 0 && !data) return fail(QAMD_ERR_ARGUMENTS, "data is null");
     QAMD_ON_DEVICE(current_device());
@@ -2281,6 +2505,7 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
     h->meta.vector_parameters.distance_type = base_distance;
     h->rotated = rotated;
     h->four_bit = four_bit;
+    h->compact = flags.compact;
     const float levels = four_bit ? 15.0f : 127.0f;  // alpha = (max - min) / levels (:228-232)
     QAMD_TRY(alloc_store(h.get()));
     if (vp->count == 0) {  // encoded_vectors_u8.rs:43-54
@@ -2387,9 +2612,8 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
     if (!meta || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     const qamd_vector_parameters &vp = meta->vector_parameters;
     int base_distance = vp.distance_type;
-    bool rotated = false, four_bit = false;  // the flags get_metadata reported travel back in here
-    if (vp.distance_type >= 0 && (vp.distance_type & (QAMD_ROTATED | QAMD_BITS4)))
-        QAMD_TRY(split_distance(vp, base_distance, rotated, four_bit));
+    U8Flags flags;  // the flags get_metadata reported travel back in here
+    if (vp.distance_type >= 0 && (vp.distance_type & kU8FlagBits)) QAMD_TRY(split_distance(vp, base_distance, flags));
     if (meta->actual_dim != actual_dim_of(vp.dim))
         return fail(QAMD_ERR_ARGUMENTS, "metadata actual_dim %llu does not match dim %llu",
                     (unsigned long long)meta->actual_dim, (unsigned long long)vp.dim);
@@ -2402,12 +2626,21 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
     h->count = vp.count;
     h->meta = *meta;
     h->meta.vector_parameters.distance_type = base_distance;
-    h->rotated = rotated;
-    h->four_bit = four_bit;
+    h->rotated = flags.rotated;
+    h->four_bit = flags.four_bit;
+    h->compact = flags.compact;
     QAMD_TRY(alloc_store(h.get()));
     const uint64_t stride = meta->actual_dim + 4;
     const uint32_t row_dwords = (uint32_t)(stride / 4);
-    const uint64_t batch_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / stride);
+    uint64_t batch_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / stride);
+    // A compact store: a batch is a tile - split into the staging buffer, packed into the image from there.
+    // The bytes are another producer's, and the image is all the store keeps: the pack kernel reports a code above 15.
+    DevBuf bad;
+    if (h->compact) {
+        batch_rows = std::min(batch_rows, compact_tile_rows(h.get()));
+        QAMD_TRY(bad.alloc(sizeof(uint32_t), true));
+        if (vp.count) QAMD_TRY(compact_stage(h.get(), std::min<uint64_t>(batch_rows, vp.count), s));
+    }
     DevBuf stage;
     if (rows_mem == QAMD_MEM_HOST && vp.count)
         QAMD_TRY(stage.alloc(std::min<uint64_t>(batch_rows, vp.count) * stride));
@@ -2421,9 +2654,17 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
         int grid = grid_for(nr * row_dwords, kBlock * 4, 8);
         hipLaunchKernelGGL(split_rows_kernel, dim3(grid), dim3(kBlock), 0, s,
                            reinterpret_cast<const uint32_t *>(src), nr, row_dwords,
-                           h->codes.as<uint32_t>() + r0 * (row_dwords - 1), h->offsets.as<float>() + r0);
+                           h->compact ? h->stage.as<uint32_t>() : h->byte_codes<uint32_t>() + r0 * (row_dwords - 1),
+                           h->offsets.as<float>() + r0);
         QAMD_HIP(hipGetLastError());
+        if (h->compact) QAMD_TRY(launch_pack(h.get(), r0, nr, bad.as<uint32_t>(), s, h->stage.as<uint4>()));
         if (rows_mem == QAMD_MEM_HOST) QAMD_HIP(hipStreamSynchronize(s));
+    }
+    if (h->compact) {
+        uint32_t high = 1;
+        QAMD_HIP(hipMemcpyAsync(&high, bad.ptr, sizeof(high), hipMemcpyDeviceToHost, s));
+        QAMD_HIP(hipStreamSynchronize(s));
+        if (high) return fail(QAMD_ERR_ARGUMENTS, "a compact store keeps codes 0 .. 15 only, and the rows hold a larger one");
     }
     QAMD_HIP(hipStreamSynchronize(s));
     QAMD_TRY(build_packed(h.get(), s));
@@ -2444,15 +2685,23 @@ qamd_status qamd_u8_export_rows_range(const qamd_u8 *h, uint64_t first_row, uint
     hipStream_t s = as_stream(stream);
     const uint64_t stride = h->meta.actual_dim + 4;
     const uint32_t row_dwords = (uint32_t)(stride / 4);
-    const uint64_t batch_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / stride);
+    uint64_t batch_rows = std::max<uint64_t>(1, stage_bytes(256ull << 20) / stride);
+    // A compact store: a batch is a tile, whose byte codes come out of the image into call-local scratch.
+    StreamBuf tile;
+    if (h->compact) {
+        batch_rows = std::min(batch_rows, compact_tile_rows(h));
+        QAMD_TRY(tile.alloc(std::min<uint64_t>(batch_rows, n_rows) * h->meta.actual_dim, s));
+    }
     DevBuf stage;
     if (rows_mem == QAMD_MEM_HOST) QAMD_TRY(stage.alloc(std::min<uint64_t>(batch_rows, n_rows) * stride));
     for (uint64_t r0 = 0; r0 < n_rows; r0 += batch_rows) {
         const uint64_t nr = std::min(batch_rows, n_rows - r0), src_row = first_row + r0;
         uint8_t *dst = rows_mem == QAMD_MEM_HOST ? stage.as<uint8_t>() : rows + r0 * stride;
         int grid = grid_for(nr * row_dwords, kBlock * 4, 8);
+        if (h->compact) QAMD_TRY(launch_unpack(h, nullptr, src_row, nr, tile.as<uint8_t>(), h->meta.actual_dim, nullptr, s));
         hipLaunchKernelGGL(join_rows_kernel, dim3(grid), dim3(kBlock), 0, s,
-                           h->codes.as<uint32_t>() + src_row * (row_dwords - 1), h->offsets.as<float>() + src_row, nr,
+                           h->compact ? tile.as<uint32_t>() : h->byte_codes<uint32_t>() + src_row * (row_dwords - 1),
+                           h->offsets.as<float>() + src_row, nr,
                            row_dwords, reinterpret_cast<uint32_t *>(dst));
         QAMD_HIP(hipGetLastError());
         if (rows_mem == QAMD_MEM_HOST)
@@ -2471,6 +2720,7 @@ qamd_status qamd_u8_get_metadata(const qamd_u8 *h, qamd_u8_metadata *out) {
     *out = h->meta;
     if (h->rotated) out->vector_parameters.distance_type |= QAMD_ROTATED;
     if (h->four_bit) out->vector_parameters.distance_type |= QAMD_BITS4;
+    if (h->compact) out->vector_parameters.distance_type |= QAMD_COMPACT;
     return QAMD_OK;
 }
 
@@ -2482,7 +2732,8 @@ qamd_status qamd_u8_save(const qamd_u8 *h, const char *data_path, const char *me
                      ",\"multiplier\":" + json_f32(h->meta.multiplier) +
                      ",\"vector_parameters\":" + vector_parameters_json(h->meta.vector_parameters) +
                      (h->rotated ? ",\"rotation\":\"HadamardBlocks\"" : "") +  // the base metric above; 3.1x
-                     (h->four_bit ? ",\"bits\":4" : "") + "}";                      // 3.1y
+                     (h->four_bit ? ",\"bits\":4" : "") +                           // 3.1y
+                     (h->compact ? ",\"compact\":true" : "") + "}";                 // 3.1z: the rows below are byte rows all the same
     QAMD_TRY(save_file(meta_path, js.data(), js.size()));
     const uint64_t stride = h->meta.actual_dim + 4;
     std::vector<uint8_t> rows(h->count * stride);
@@ -2528,6 +2779,17 @@ qamd_status qamd_u8_load(const char *data_path, const char *meta_path, const qam
     }
     if (four_bit && meta.vector_parameters.distance_type == QAMD_L1)
         return fail(QAMD_ERR_IO, "%s: a 4-bit store of metric L1", meta_path);
+    // "compact" (DESIGN 3.1z): absent = the store keeps its byte codes; true, beside "bits":4, is the one value a store writes
+    bool compact = false;
+    for (const auto &m : root.members) {
+        if (m.first != "compact") continue;
+        if (compact || m.second.kind != JsonValue::Bool || !m.second.boolean || !four_bit)
+            return fail(QAMD_ERR_IO, "%s: unknown, repeated or misplaced compact", meta_path);
+        compact = true;
+    }
+    if (compact && !u8_image_of((uint32_t)std::min<uint64_t>(actual_dim_of(vp->dim) / 16, 0xFFFFFFFFull), true,
+                                meta.vector_parameters.distance_type).kind)
+        return fail(QAMD_ERR_IO, "%s: a compact store of %llu dimensions", meta_path, (unsigned long long)vp->dim);
     const uint64_t size = qamd_u8_quantized_vector_size(vp);
     std::string bytes;
     QAMD_TRY(load_rows_file(data_path, size * vp->count, bytes));
@@ -2538,6 +2800,7 @@ qamd_status qamd_u8_load(const char *data_path, const char *meta_path, const qam
     eff.actual_dim = actual_dim_of(vp->dim);
     if (rotated) eff.vector_parameters.distance_type |= QAMD_ROTATED;  // from_rows takes it off again
     if (four_bit) eff.vector_parameters.distance_type |= QAMD_BITS4;
+    if (compact) eff.vector_parameters.distance_type |= QAMD_COMPACT;
     qamd_status st = qamd_u8_from_rows(reinterpret_cast<const uint8_t *>(bytes.data()), QAMD_MEM_HOST, &eff,
                                        nullptr, out);
     eff.vector_parameters.distance_type = meta.vector_parameters.distance_type;
@@ -2701,15 +2964,17 @@ qamd_status qamd_u8_score_internal_ids(const qamd_u8 *h, uint32_t i, const uint3
     else if (!out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     if (i >= h->count) return fail(QAMD_ERR_OUT_OF_RANGE, "row id %u out of range (count %llu)", i, (unsigned long long)h->count);
     QAMD_ON_DEVICE(h->device);
-    const uint4 *qc = h->codes.as<uint4>() + (uint64_t)i * h->row_chunks;
-    const float *qo = h->offsets.as<float>() + i;
+    hipStream_t s = as_stream(stream);
+    const uint4 *qc = nullptr;
+    const float *qo = nullptr;
+    StreamBuf row;
+    QAMD_TRY(stored_row_query(h, i, row, s, qc, qo));
     if (!ids) {  // score_internal_all's scan over a prefix of the store
-        hipStream_t s = as_stream(stream);
         const ScanEpi e{internal_diff(h), EPI_INTERNAL, n_ids};
         if (out_mem == QAMD_MEM_DEVICE) return scan_ptrs(h, qc, qo, out, s, nullptr, e);
         return score_all_to_host(n_ids, out, s, [&](float *scores) { return scan_ptrs(h, qc, qo, scores, s, nullptr, e); });
     }
-    return score_ids_any(h, qc, qo, internal_diff(h), EPI_INTERNAL, ids, n_ids, ids_mem, out, out_mem, as_stream(stream));
+    return score_ids_any(h, qc, qo, internal_diff(h), EPI_INTERNAL, ids, n_ids, ids_mem, out, out_mem, s);
 }
 
 // Many stored rows, each against its own id list, in one launch (lists.hpp):
@@ -2891,8 +3156,8 @@ qamd_status qamd_u8_encoder_begin(const qamd_vector_parameters *vp, const float 
                                   qamd_stop_fn stop, void *stop_user, void *stream, qamd_u8_encoder **out) {
     if (!vp || !out) return fail(QAMD_ERR_ARGUMENTS, "null argument");
     int base_distance = 0;
-    bool rotated = false, four_bit = false;
-    QAMD_TRY(split_distance(*vp, base_distance, rotated, four_bit));
+    U8Flags flags;
+    QAMD_TRY(split_distance(*vp, base_distance, flags));
     if (vp->count > 0xFFFFFFFFull) return fail(QAMD_ERR_ARGUMENTS, "count exceeds u32 row ids");
     QAMD_ON_DEVICE(current_device());
     std::unique_ptr<qamd_u8_encoder> e(new qamd_u8_encoder);
@@ -2907,8 +3172,9 @@ qamd_status qamd_u8_encoder_begin(const qamd_vector_parameters *vp, const float 
     e->h->count = vp->count;
     e->h->meta.actual_dim = actual_dim_of(vp->dim);
     e->h->meta.vector_parameters = e->vp;
-    e->h->rotated = rotated;
-    e->h->four_bit = four_bit;
+    e->h->rotated = flags.rotated;
+    e->h->four_bit = flags.four_bit;
+    e->h->compact = flags.compact;
     QAMD_TRY(alloc_store(e->h.get()));
     if (alpha_offset) {
         e->alpha = alpha_offset[0];
@@ -3014,13 +3280,14 @@ qamd_status u8_grow(qamd_u8 *h, uint64_t cap) {
     if (cap <= h->capacity) return QAMD_OK;
     const uint64_t padded = padded_rows_of(cap), ad = h->meta.actual_dim;
     DevBuf codes, offsets, packed;
-    QAMD_TRY(grow_copy(h->codes, padded * ad, h->count * ad, codes));
+    if (!h->compact) QAMD_TRY(grow_copy(h->codes, padded * ad, h->count * ad, codes));
     QAMD_TRY(grow_copy(h->offsets, padded * sizeof(float), h->count * sizeof(float), offsets));
     bool image = h->image.kind != U8_IMAGE_NONE;
     if (image) {
         const uint64_t chunk_bytes = (uint64_t)h->image.chunks * 16;
         const std::string err = last_error();
         if (grow_copy(h->packed, padded * chunk_bytes, round_up(h->count, kPackBlockRows) * chunk_bytes, packed) != QAMD_OK) {
+            if (h->compact) return QAMD_ERR_DEVICE;  // offsets and image are all there is; the store stays as it was
             (void)hipGetLastError();  // an out-of-memory here only costs the image
             last_error() = err;
             packed.release();
@@ -3073,8 +3340,10 @@ qamd_status qamd_u8_upsert(qamd_u8 *h, uint64_t first_row, const float *data, qa
                                    [&](const float *src, uint64_t r, uint64_t nr) {
         return launch_quantize(h, src, nr, first_row + r, h->meta.alpha, h->meta.offset, s);
     }));
-    if (h->image.kind) QAMD_TRY(launch_pack(h, first_row, n_rows, nullptr, s));  // the store's own encoder: nothing to report
+    // the store's own encoder: nothing to report (a compact store's rows went into the image tile by tile, launch_quantize)
+    if (h->image.kind && !h->compact) QAMD_TRY(launch_pack(h, first_row, n_rows, nullptr, s));
     QAMD_HIP(hipStreamSynchronize(s));
+    if (h->compact) compact_done(h);
     h->count = std::max(h->count, end);
     h->meta.vector_parameters.count = h->count;
     h->packed_rows.release();
@@ -3201,8 +3470,10 @@ qamd_status u8_topk_ptrs(const qamd_u8 *h, const uint8_t *codes_dev, const float
 static ScanEpi internal_epi(const qamd_u8 *h) { return ScanEpi{internal_diff(h), EPI_INTERNAL}; }
 
 static qamd_status u8_score_internal_all(const qamd_u8 *h, uint32_t i, float *out, qamd_mem out_mem, hipStream_t s) {
-    const uint4 *qc = h->codes.as<uint4>() + (uint64_t)i * h->row_chunks;
-    const float *qo = h->offsets.as<float>() + i;
+    const uint4 *qc = nullptr;
+    const float *qo = nullptr;
+    StreamBuf row;  // a compact store unpacks row i out of its image
+    QAMD_TRY(stored_row_query(h, i, row, s, qc, qo));
     const ScanEpi e = internal_epi(h);
     if (out_mem == QAMD_MEM_DEVICE) return scan_ptrs(h, qc, qo, out, s, nullptr, e);
     return score_all_to_host(h->count, out, s, [&](float *scores) { return scan_ptrs(h, qc, qo, scores, s, nullptr, e); });
@@ -3210,8 +3481,12 @@ static qamd_status u8_score_internal_all(const qamd_u8 *h, uint32_t i, float *ou
 
 static qamd_status u8_topk_internal(const qamd_u8 *h, uint32_t i, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
                              qamd_mem out_mem, hipStream_t s) {
-    return topk_ptrs_epi(h, h->codes.as<uint8_t>() + (uint64_t)i * h->meta.actual_dim, h->offsets.as<float>() + i, k, largest,
-                         out_ids, out_scores, out_mem, s, nullptr, internal_epi(h));
+    const uint4 *qc = nullptr;
+    const float *qo = nullptr;
+    StreamBuf row;
+    QAMD_TRY(stored_row_query(h, i, row, s, qc, qo));
+    return topk_ptrs_epi(h, reinterpret_cast<const uint8_t *>(qc), qo, k, largest, out_ids, out_scores, out_mem, s, nullptr,
+                         internal_epi(h));
 }
 
 // The batch API for the metrics with no matrix form (L1: sum |q - v| is not a contraction): the
@@ -3258,8 +3533,14 @@ qamd_status u8_score_lists(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t 
 // How many queries the vector-ALU multi-query scan takes per pass for this store (0: none).
 uint32_t u8_multi_width(const qamd_u8 *h) { return multi_width(h); }
 
-// Lane mode 1 on a Dot / L2 store: the batch API must take the per-query scans (the matrix cores sum exactly).
-bool u8_lane_order(const qamd_u8 *h) { return lane_order(h); }
+// Lane mode 1 on a Dot / L2 store: the batch API must take the per-query scans (the matrix cores sum exactly).  So must
+// a compact store: the matrix-core kernels and the multi-query scan read byte codes, which it has not.
+bool u8_batch_by_scans(const qamd_u8 *h) { return lane_order(h) || h->compact; }
+
+void no_byte_codes() {
+    std::fprintf(stderr, "quantization_amd: a route asked for the byte codes of a compact u8 store (DESIGN 3.1z)\n");
+    std::abort();
+}
 
 // out[j * count + row] for queries [0, n_queries) of a batch through the multi-query scan (groups of
 // `width`, then smaller groups, then single scans).
@@ -3333,6 +3614,10 @@ extern "C" __attribute__((visibility("default"))) void qamd_dev_u8_ptrs(const qa
 }
 extern "C" __attribute__((visibility("default"))) const void *qamd_dev_u8_query_ptr(const qamd_u8_query *q) {
     return q->buf.ptr;
+}
+// The device bytes the handle owns for its rows: byte codes + offsets + scan image (a compact store: the last two).
+extern "C" __attribute__((visibility("default"))) uint64_t qamd_dev_u8_store_bytes(const qamd_u8 *h) {
+    return (h->codes.ptr ? h->codes.bytes : 0) + h->offsets.bytes + (h->packed.ptr ? h->packed.bytes : 0) + h->stage.bytes;
 }
 // The packed scan image in ROW-MAJOR order, [count][chunks] 16-byte chunks (nullptr, 0 chunks: none): un-blocked on the
 // first call into a buffer the handle owns, so that a reader needs to know the bit format only.

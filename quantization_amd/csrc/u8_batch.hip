@@ -2233,7 +2233,7 @@ qamd_status sample_store(const qamd_u8 *h, uint32_t rows_all, hipStream_t s, con
         qamd::DevBuf c, o;
         QAMD_TRY(c.alloc((uint64_t)(rows_all + 512) * ad));
         QAMD_TRY(o.alloc((uint64_t)(rows_all + 512) * 4));
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->codes.as<uint4>(),
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->byte_codes<uint4>(),
                            h->offsets.as<float>(), h->row_chunks, h->count, rows_all, 512u, c.as<uint4>(), o.as<float>());
         QAMD_HIP(hipGetLastError());
         QAMD_HIP(hipStreamSynchronize(s));  // once per handle: every later call, on any stream, just reads it
@@ -2351,15 +2351,16 @@ qamd_status qamd_u8_score_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, 
     const uint32_t width = u8_multi_width(h);
     const U8GemmRoute route = gemm_route(h, b, U8GemmPass::Score, h->count);
     // (from three queries on the row-streaming MFMA kernel streams the rows as fast and does not slow down per query)
-    // Lane mode 1 (Dot, L2): the matrix cores sum exactly, so every query takes the lane-order scan (width 0).
-    if (h->meta.vector_parameters.distance_type == QAMD_L1 || u8_lane_order(h) ||
+    // Lane mode 1 (Dot, L2): the matrix cores sum exactly, so every query takes the lane-order scan (width 0).  A compact
+    // store has no byte codes for the matrix cores to read: every query takes the image scan.
+    if (h->meta.vector_parameters.distance_type == QAMD_L1 || u8_batch_by_scans(h) ||
         (width && b->n_queries >= 2 && b->n_queries <= width && (b->n_queries == 2 || !route.rs_ok))) {
         // sum |q - v| is not a contraction (no MFMA form), and for a handful of queries the vector-ALU
         // multi-query scan streams the rows faster than the matrix-core kernel's LDS-DMA path
         QAMD_TRY(u8_score_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)b->n_queries,
                                       out_dev, s));
     } else {
-        QAMD_TRY(launch_gemm<0>(route, {h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), h->count, out_dev, h->count,
+        QAMD_TRY(launch_gemm<0>(route, {h, b, h->byte_codes<uint8_t>(), h->offsets.as<float>(), h->count, out_dev, h->count,
                                         BatchFilter{}, s}));
     }
     if (out_mem == QAMD_MEM_HOST) QAMD_TRY(copy_out(out, QAMD_MEM_HOST, out_dev, total * 4, s));
@@ -2375,7 +2376,7 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
     hipStream_t s = as_stream(stream);
     const uint64_t Q = b->n_queries, n = h->count;
     const bool l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
-    if (u8_lane_order(h))  // lane mode 1 (Dot, L2): per-query lane-order scans, never the exact-sum matrix cores
+    if (u8_batch_by_scans(h))  // lane mode 1 (Dot, L2): per-query lane-order scans, never the exact-sum matrix cores; compact: image scans
         return u8_topk_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)Q, k, largest,
                                    out_ids, out_scores, out_mem, s);
     // The route of the filter pass over the store: everything below reads it (and the sample pass its own).
@@ -2418,7 +2419,7 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
         if (!cached) {
             uint8_t *g_codes = pass.at<uint8_t>(o_codes);
             float *g_offs = pass.at<float>(o_offs);
-            hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->codes.as<uint4>(),
+            hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->byte_codes<uint4>(),
                                h->offsets.as<float>(), h->row_chunks, n, S, 512u, reinterpret_cast<uint4 *>(g_codes), g_offs);
             s_codes = g_codes;
             s_offs = g_offs;
@@ -2440,9 +2441,9 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
         }
         const BatchFilter f = pass.filter();
         if (largest)
-            QAMD_TRY(launch_gemm<1>(filter_route, {h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
+            QAMD_TRY(launch_gemm<1>(filter_route, {h, b, h->byte_codes<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
         else
-            QAMD_TRY(launch_gemm<2>(filter_route, {h, b, h->codes.as<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
+            QAMD_TRY(launch_gemm<2>(filter_route, {h, b, h->byte_codes<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
         pass.scatter();
         QAMD_TRY(pass.emit(out.ids_dev, out.sc_dev));
         QAMD_TRY(pass.read_status(out.status));

@@ -15,6 +15,10 @@ struct U8Image {
     uint32_t chunks = 0, aux = 0;
 };
 
+namespace qamd {
+[[noreturn]] void no_byte_codes();  // u8.hip: says what happened and aborts (qamd_u8::byte_codes)
+}
+
 struct qamd_u8 {
     int device = 0;
     qamd_u8_metadata meta{};
@@ -31,7 +35,19 @@ struct qamd_u8 {
     // to nearest.  Like `rotated` it lives beside the base metric and goes back on in get_metadata; only the encoders,
     // the query encoders and build_packed read it - the scans see the image that build_packed left (image.kind).
     bool four_bit = false;
-    qamd::DevBuf codes;        // [padded_rows][actual_dim]
+    // A compact 4-bit store: `codes` is never allocated; the store is `offsets` and the nibble image, which
+    // every builder writes tile by tile through `stage`, and every route reads (u8.hip: the image scan, u8_nibble_pairs_kernel,
+    // u8_nibble_unpack_kernel).  Like the two flags above it goes back onto the metric in get_metadata.
+    bool compact = false;
+    // The byte codes, for every kernel argument: the one place that hands the pointer out.  A compact store has none and
+    // no route of it may ask (u8.hip routes by `compact` before it gets here), so a request is a routing bug: it stops on
+    // the host, before a kernel can be launched on a null pointer.
+    template <typename T> T *byte_codes() const {
+        if (compact) qamd::no_byte_codes();
+        return codes.as<T>();
+    }
+    qamd::DevBuf stage;        // compact builders: the byte codes of the tile in flight; released when a build or upsert ends
+    qamd::DevBuf codes;        // [padded_rows][actual_dim]; a compact store: empty
     qamd::DevBuf offsets;      // [padded_rows] f32
     // Scan image (u8.hip build_packed), `image.chunks` 16-byte chunks per row in the format `image.kind`; u8.hip
     // u8_image_of is the one place that says which image a store can have and how long its rows are.
@@ -44,6 +60,7 @@ struct qamd_u8 {
     // padded_rows is a multiple of 1024: blocks are whole, and padding rows are zero.  Only the Dot / L2 scans of lane
     // mode 0 read it; every other kernel reads `codes`.  `packed` is empty and `image` is {} when the store has none (L1,
     // fewer than 8 - nibble: 2 - or more than 128 chunks, a code above 127 - nibble: 15 -, too little free HBM).
+    // A compact store always has its nibble image (a build that cannot have one fails), and all its routes read it.
     qamd::DevBuf packed;
     U8Image image;
     mutable std::atomic<int> last_scan_packed{0};  // image.kind of the image the last scan launch read (developer report)
@@ -107,7 +124,7 @@ qamd_status u8_topk_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint
                                 uint32_t n_queries, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
                                 qamd_mem out_mem, hipStream_t stream);
 uint32_t u8_multi_width(const qamd_u8 *h);
-bool u8_lane_order(const qamd_u8 *h);
+bool u8_batch_by_scans(const qamd_u8 *h);  // lane mode 1 on Dot / L2, or a compact store: batches go query by query
 qamd_status u8_score_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t pitch, const float *offsets_dev,
                                  uint32_t n_queries, float *out_dev, hipStream_t stream);
 qamd_status u8_score_single(const qamd_u8 *h, const uint8_t *codes_dev, const float *offset_dev, float *out_dev,

@@ -27,6 +27,7 @@ class DistanceType(enum.IntEnum):
 ROTATED = 8  # QAMD_ROTATED: the flag on qamd_vector_parameters.distance_type of a rotated scalar-u8 store
 ROTATION_NAME = "HadamardBlocks"  # what a rotated store's metadata says under "rotation"
 BITS4 = 32  # QAMD_BITS4: the flag on distance_type of a 4-bit scalar-u8 store
+COMPACT = 128  # QAMD_COMPACT: on top of BITS4, a store that keeps only offsets and nibble image
 
 
 def check_bits(bits) -> bool:
@@ -45,17 +46,22 @@ class VectorParameters:
     distance_type: DistanceType
     invert: bool
 
-    def to_c(self, rotated: bool = False, bits: int = 8) -> _lib.VectorParametersC:
+    def to_c(self, rotated: bool = False, bits: int = 8, compact: bool = False) -> _lib.VectorParametersC:
         """`rotated`: QAMD_ROTATED or-ed onto the metric - a rotated scalar-u8 store; `bits` = 4:
-        QAMD_BITS4 - a 4-bit one (3.1y).  The flags live in the C struct alone: `distance_type` here stays a
-        DistanceType."""
+        QAMD_BITS4 - a 4-bit one (3.1y); `compact`: QAMD_COMPACT - a 4-bit one that keeps only its nibble image (3.1z).
+        The flags live in the C struct alone: `distance_type` here stays a DistanceType."""
         flags = (ROTATED if rotated else 0) | (BITS4 if check_bits(bits) else 0)
+        if compact:
+            if bits != 4:
+                raise EncodingError(_lib.ERR_ARGUMENTS, "compact goes with bits=4 only")
+            flags |= COMPACT
         return _lib.VectorParametersC(int(self.dim), int(self.count), int(self.distance_type) | flags,
                                       int(bool(self.invert)))
 
     @staticmethod
     def from_c(c: _lib.VectorParametersC) -> "VectorParameters":
-        return VectorParameters(int(c.dim), int(c.count), DistanceType(c.distance_type & ~(ROTATED | BITS4)), bool(c.invert))
+        return VectorParameters(int(c.dim), int(c.count), DistanceType(c.distance_type & ~(ROTATED | BITS4 | COMPACT)),
+                                bool(c.invert))
 
 
 class EncodingError(Exception):

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._base import EncodedQueryBase, EncodedQueryBatch, EncodedVectorsBase
-from .encoded_vectors import (BITS4, ROTATED, ROTATION_NAME, DistanceType, EncodingError, VectorParameters, check, check_same_device,
+from .encoded_vectors import (BITS4, COMPACT, ROTATED, ROTATION_NAME, DistanceType, EncodingError, VectorParameters, check, check_same_device,
                               creating_on, flatten_rows, get_device, in_buf, make_stop, out_buf, stream_ptr,
                               validate)
 
@@ -55,17 +55,19 @@ class EncodedVectorsU8(EncodedVectorsBase):
     @classmethod
     def encode(cls, orig_data, vector_parameters: VectorParameters, quantile: float | None = None,
                stop_condition=None, *, alpha_offset: tuple[float, float] | None = None,
-               stream=None, rotated: bool = False, bits: int = 8) -> "EncodedVectorsU8":
+               stream=None, rotated: bool = False, bits: int = 8, compact: bool = False) -> "EncodedVectorsU8":
         """EncodedVectorsU8::encode (:34-140).  `orig_data`: [count, dim] f32 array (host) or
         CUDA tensor (HBM), or an iterable of rows.  The storage builder of the reference is
         implicit: the encoded rows live in library-owned HBM (see `storage_bytes`).
         `rotated` (no counterpart in the reference): rows and queries go through a fixed randomized
         Hadamard block rotation before the quantizer - Dot or L2, dim a multiple of 64 up to 16384.
         `bits` = 4 (no counterpart either): 16 levels per code, rounded to nearest, Dot or L2; the
-        single-query scans read two codes per byte.  Meant for rotated rows, with the originals behind it for rescoring."""
+        single-query scans read two codes per byte.  Meant for rotated rows, with the originals behind it for rescoring.
+        `compact` (with `bits` = 4 only): the store keeps its row offsets and the two-codes-per-byte image
+        and no byte codes - about a third of the HBM, the same answers bit for bit; query batches take one scan per query."""
         data = flatten_rows(orig_data, vector_parameters.dim)
         validate(data, vector_parameters)
-        vp = vector_parameters.to_c(rotated, bits)
+        vp = vector_parameters.to_c(rotated, bits, compact)
         buf = in_buf(data, np.float32)
         q = C.c_float(quantile) if quantile is not None else None
         ao = (C.c_float * 2)(*alpha_offset) if alpha_offset is not None else None
@@ -103,13 +105,13 @@ class EncodedVectorsU8(EncodedVectorsBase):
     @classmethod
     def encode_stream(cls, make_batches, vector_parameters: VectorParameters, quantile: float | None = None,
                       stop_condition=None, *, alpha_offset: tuple[float, float] | None = None,
-                      stream=None, rotated: bool = False, bits: int = 8) -> "EncodedVectorsU8":
+                      stream=None, rotated: bool = False, bits: int = 8, compact: bool = False) -> "EncodedVectorsU8":
         """The reference's own contract: `encode` takes a CLONABLE ITERATOR and walks it twice
         (:34-40, pass 1 :57-71, pass 2 :73-118).  `make_batches()` returns a fresh iterator over
         [n_i, dim] f32 batches (numpy or CUDA tensors) each time it is called; the f32 data is never
-        held as a whole.  Byte-identical to `encode` on the concatenated batches, `rotated` and `bits` included."""
+        held as a whole.  Byte-identical to `encode` on the concatenated batches, `rotated`, `bits` and `compact` included."""
         L = _lib.lib()
-        vp = vector_parameters.to_c(rotated, bits)
+        vp = vector_parameters.to_c(rotated, bits, compact)
         q = C.c_float(quantile) if quantile is not None else None
         ao = (C.c_float * 2)(*alpha_offset) if alpha_offset is not None else None
         stop = make_stop(stop_condition)
@@ -137,11 +139,13 @@ class EncodedVectorsU8(EncodedVectorsBase):
         return cls(out, dev)
 
     @classmethod
-    def from_storage(cls, rows, metadata: dict, stream=None) -> "EncodedVectorsU8":
+    def from_storage(cls, rows, metadata: dict, stream=None, compact: bool = False) -> "EncodedVectorsU8":
         """Adopt reference-format rows ([vector_offset f32][codes], stride actual_dim+4) plus
         their Metadata (:24-31) — e.g. a store encoded by the reference crate.  A "rotation" entry (what a rotated
         store's `metadata` carries) makes the new store a rotated one: its queries are rotated before they are encoded.
-        A "bits" entry of 4 makes it a 4-bit store: its queries get 4-bit codes, and rows of codes 0..15 a nibble image."""
+        A "bits" entry of 4 makes it a 4-bit store: its queries get 4-bit codes, and rows of codes 0..15 a nibble image.
+        `compact`, or a true "compact" entry (what a compact store's `metadata` carries), beside "bits" 4: the store keeps
+        the nibble image alone; a code above 15 in `rows` is then an ArgumentsError."""
         rotation = metadata.get("rotation")
         if rotation not in (None, ROTATION_NAME):
             raise EncodingError(_lib.ERR_ARGUMENTS, f"unknown rotation {rotation!r}")
@@ -152,7 +156,8 @@ class EncodedVectorsU8(EncodedVectorsBase):
             vp = VectorParameters(vp["dim"], vp["count"],
                                   DistanceType[dt] if isinstance(dt, str) else DistanceType(dt), vp["invert"])
         meta = _lib.U8MetadataC(int(metadata["actual_dim"]), float(metadata["alpha"]),
-                                float(metadata["offset"]), float(metadata["multiplier"]), vp.to_c(rotation is not None, bits))
+                                float(metadata["offset"]), float(metadata["multiplier"]),
+                                vp.to_c(rotation is not None, bits, bool(compact or metadata.get("compact", False))))
         buf = in_buf(rows, np.uint8)
         out = C.c_void_p()
         with creating_on(rows) as dev:
@@ -183,6 +188,8 @@ class EncodedVectorsU8(EncodedVectorsBase):
             md["rotation"] = ROTATION_NAME
         if m.vector_parameters.distance_type & BITS4:  # a 7-bit store's metadata has no such entry, as its file has none
             md["bits"] = 4
+        if m.vector_parameters.distance_type & COMPACT:  # only a compact store's metadata has the entry, as only its file has
+            md["compact"] = True
         return md
 
     @property
@@ -194,6 +201,11 @@ class EncodedVectorsU8(EncodedVectorsBase):
     def bits(self) -> int:
         """4 for a 4-bit store, else 8: the reference's byte codes."""
         return self.metadata.get("bits", 8)
+
+    @property
+    def compact(self) -> bool:
+        """Whether the store keeps only row offsets and nibble image, no byte codes."""
+        return bool(self.metadata.get("compact", False))
 
     @property
     def vector_parameters(self) -> VectorParameters:

@@ -170,9 +170,11 @@ class ShardedVectorsU8(_ShardedBase):
     @classmethod
     def encode(cls, orig_data, vector_parameters: VectorParameters, devices, quantile: float | None = None,
                stop_condition=None, *, alpha_offset=None, stream=None, rotated: bool = False,
-               bits: int = 8) -> "ShardedVectorsU8":
+               bits: int = 8, compact: bool = False) -> "ShardedVectorsU8":
         if rotated:  # (the C constructor refuses the flag too)
             raise EncodingError(_lib.ERR_ARGUMENTS, "only a single-GPU EncodedVectorsU8 can be rotated")
+        if compact:
+            raise EncodingError(_lib.ERR_ARGUMENTS, "only a single-GPU EncodedVectorsU8 can be compact")
         if bits != 8:
             raise EncodingError(_lib.ERR_ARGUMENTS, "only a single-GPU EncodedVectorsU8 can have 4-bit rows")
         data = flatten_rows(orig_data, vector_parameters.dim)
