@@ -458,6 +458,129 @@ __global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     }
 }
 
+// NQ (2, 4, 8) queries per pass over the nibble image: the batch route of a compact 4-bit store, which has
+// no byte codes for u8_scan_multi_kernel or the matrix cores to read.  The frame is u8_scan_image_kernel<Image4>'s, line
+// for line: `split` waves per block of 64 rows, lane l owns row 64 b + l, every wave-load is one aligned kilobyte, one
+// ring of R = 8 chunks in flight and refilled behind its last use, then the rest group.  What changes is the inner step:
+// a loaded chunk is masked ONCE into its low and its (unshifted) high nibbles, and each of the NQ queries then adds
+//   lo[j] += dot(w & 0x0F.., q_j[2c]),  hi[j] += dot(w & 0xF0.., q_j[2c + 1])
+// with q_j = qcodes + j * q_pitch read at wave-uniform addresses: scalar loads through the constant cache, no vector
+// register per query.  Per 16-byte chunk a lane issues 8 `and` and 8 NQ v_dot4 instead of NQ * (8 + 8): the scan's idle
+// vector ALU pays for the extra queries while the image is read from HBM once.  Row sum j = lo[j] + (hi[j] >> 4), the
+// single kernel's exact integer (same bounds), and the same f32 epilogue, so the same score bits.  32 ring registers,
+// 2 NQ accumulators, 8 for the two masked copies.
+// An unused slot (3 queries in a 4-wide pass) re-reads the last valid query and writes nothing.  For an odd row_chunks the
+// second query chunk of the last image chunk is not read for any j: the last query of a batch ends there.
+// split > 1: the NQ partial sums of a lane meet in LDS (NQ * kScanBlock words) behind one barrier.
+// FILTER: no score is written; the lane offers its row to query j's candidate lists (slices).  EPI_INTERNAL: the queries
+// are stored rows unpacked into a [NQ][q_pitch] block with their stored offsets (u8_nibble_unpack_kernel).
+template <int NQ, bool FILTER, int EPI = EPI_POINT>
+__global__ __launch_bounds__(kScanBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void u8_scan_image_multi_kernel(
+    const uint4 *__restrict__ image, const float *__restrict__ offsets, const uint8_t *__restrict__ qcodes, uint32_t q_pitch,
+    const float *__restrict__ q_offs, uint32_t nq_valid /* 2 .. NQ: queries really there */, float multiplier,
+    uint32_t n_rows, uint32_t pchunks, uint32_t row_chunks, uint32_t split, float *__restrict__ out /* [NQ][out_pitch] */,
+    uint64_t out_pitch, TopkFilterSlices slices, float diff) {
+    constexpr int R = Image4::R;
+    __shared__ uint32_t partial[NQ][kScanBlock];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t part = wave & (split - 1);
+    const uint64_t block = (uint64_t)blockIdx.x * ((kScanBlock / 64) / split) + wave / split;
+    const uint64_t row = block * kPackBlockRows + lane;
+    const bool live = block * kPackBlockRows < n_rows;  // wave-uniform; offsets[] and the image are padded past every block
+    // the groups of a row, as in u8_scan_image_kernel: n_ring whole groups of R full chunks, then one of the n_rest left
+    const uint32_t n_full = row_chunks / 2, n_ring = n_full / R, n_rest = pchunks - R * n_ring;
+    const uint32_t n_groups = n_ring + (n_rest ? 1 : 0);
+    const uint32_t g_begin = live ? n_groups * part / split : 0, g_end = live ? n_groups * (part + 1) / split : 0;
+    const uint4 *blk = image + block * pchunks * kPackBlockChunk;
+    const uint32_t lane16 = lane * 16;
+    auto chunk_ptr = [&](uint32_t c) {
+        return reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(blk + (uint64_t)c * kPackBlockChunk) + lane16);
+    };
+    const uint32_t gf_end = g_end < n_ring ? g_end : n_ring;
+    const bool has_rest = g_end > n_ring;
+
+    const uint4 *q[NQ];  // wave-uniform
+#pragma unroll
+    for (int j = 0; j < NQ; j++)
+        q[j] = reinterpret_cast<const uint4 *>(qcodes + (size_t)((uint32_t)j < nq_valid ? (uint32_t)j : nq_valid - 1) * q_pitch);
+    uint32_t lo[NQ], hi[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; j++) lo[j] = hi[j] = 0;
+    // image chunk c against query chunks 2c and, when the row has it, 2c + 1
+    auto add = [&](const uint4 &w, uint32_t c, bool second) {
+        const uint4 l = and16(w, 0x0F0F0F0Fu), u = and16(w, 0xF0F0F0F0u);
+        uint32_t at = 32 * c;  // bytes into a query
+        // NQ = 8: the 32 query bytes of one image chunk are 64 SGPRs.  Left alone, the compiler fuses the scalar loads of two
+        // neighbouring chunks into 64-byte ones, needs 128, and spills them lane by lane into vector registers (and those to
+        // scratch).  An offset it cannot see through keeps the loads of a chunk apart from the next chunk's.
+        if constexpr (NQ == 8) asm volatile("" : "+s"(at));
+#pragma unroll
+        for (int j = 0; j < NQ; j++) {
+            const uint4 *qc = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(q[j]) + at);
+            lo[j] = dot16(l, qc[0], lo[j]);
+            if (second) hi[j] = dot16(u, qc[1], hi[j]);
+        }
+    };
+
+    uint4 v[R];
+    auto eat = [&](uint32_t g, auto refill) {
+#pragma unroll
+        for (int i = 0; i < R; i++) {
+            add(v[i], R * g + i, true);
+            if (decltype(refill)::value) {  // pinned here, so that the load reuses the chunk's registers
+                __builtin_amdgcn_sched_barrier(0);
+                v[i] = ld_nt(chunk_ptr(R * (g + 1) + i));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    if (g_begin < gf_end) {
+#pragma unroll
+        for (int i = 0; i < R; i++) v[i] = ld_nt(chunk_ptr(R * g_begin + i));
+    }
+    const float v_off = offsets[row];
+    if (g_begin < gf_end) {
+        for (uint32_t g = g_begin; g + 1 < gf_end; g++) eat(g, std::true_type{});
+        eat(gf_end - 1, std::false_type{});
+    }
+    if (has_rest) {
+        const uint32_t c0 = R * n_ring;
+#pragma unroll
+        for (int i = 0; i < R; i++)
+            if ((uint32_t)i < n_rest) v[i] = ld_nt(chunk_ptr(c0 + i));
+#pragma unroll
+        for (int i = 0; i < R; i++)
+            if ((uint32_t)i < n_rest) add(v[i], c0 + i, c0 + i < n_full);
+    }
+    uint32_t acc[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; j++) acc[j] = lo[j] + (hi[j] >> 4);
+    if (split > 1) {
+#pragma unroll
+        for (int j = 0; j < NQ; j++) partial[j][threadIdx.x] = acc[j];
+        __syncthreads();
+        if (part == 0)
+            for (uint32_t p = 1; p < split; p++) {
+#pragma unroll
+                for (int j = 0; j < NQ; j++) acc[j] += partial[j][threadIdx.x + 64 * p];
+            }
+    }
+    if (part == 0 && row < n_rows) {
+#pragma unroll
+        for (int j = 0; j < NQ; j++) {
+            if ((uint32_t)j >= nq_valid) break;
+            const float score = epilogue(multiplier, acc[j], q_offs[j], v_off, EPI == EPI_POINT ? 0.0f : diff, EPI);
+            if (FILTER) {
+                const TopkFilter f = topk_filter_of(slices, (uint32_t)j);
+                topk_offer(f, *f.pivot_key, score, (uint32_t)row);
+            } else {
+                __builtin_nontemporal_store(score, out + (uint64_t)j * out_pitch + row);
+            }
+        }
+    }
+}
+
 // NQ (2, 4, 8) queries per row read on the vector ALU -- the route of qamd_u8_topk_batch /
 // score_batch for a handful of queries over a large store, where the matrix-core kernel is bound
 // by what its LDS-DMA path moves (4.6 TB/s of row bytes: 1.67 ms per 10M x 768 whatever the batch)
@@ -1825,6 +1948,7 @@ void launch_scan_image(const qamd_u8 *h, const uint4 *qc, const float *qo, float
     const uint64_t blocks = (n_rows + kPackBlockRows - 1) / kPackBlockRows;
     const unsigned grid = (unsigned)((blocks + blocks_per_wg - 1) / blocks_per_wg);
     h->last_scan_split.store((int)split, std::memory_order_relaxed);
+    h->last_scan_queries.store(1, std::memory_order_relaxed);
     with_bool(h->image.kind == U8_IMAGE_NIBBLE, [&](auto nibble) {
         using IMG = std::conditional_t<nibble, Image4, Image7>;
         with_bool(filt != nullptr, [&](auto fi) {
@@ -1835,6 +1959,45 @@ void launch_scan_image(const qamd_u8 *h, const uint4 *qc, const float *qo, float
             });
         });
     });
+}
+
+// ---- several queries per pass over the nibble image (u8_scan_image_multi_kernel) ----------------
+// Widest pass for this store: 8 queries for a compact store (the only one whose batches have no byte codes to read),
+// 0 = none.  DESIGN 3.1z has the measurements the width rests on.  QAMD_DEV_U8_IMAGE_MULTI (developer library) caps it
+// at 2 or 4, or turns the route off (1), for the A/B of tools/time_u8_compact_batch.py.
+uint32_t image_multi_width(const qamd_u8 *h) {
+    static const uint32_t cap = (uint32_t)dev_env_u64("QAMD_DEV_U8_IMAGE_MULTI", 8);
+    if (h->image.kind != U8_IMAGE_NIBBLE || !h->compact) return 0;
+    return cap >= 8 ? 8 : cap >= 4 ? 4 : cap >= 2 ? 2 : 0;
+}
+
+// One pass for `nq_valid` (2 .. image_multi_width) queries ([q][q_pitch] codes, [q] offsets) over the rows the epilogue
+// covers, in the smallest NQ that holds them; out is [nq_valid][scan_rows].  false = not served (the caller scans singly).
+bool launch_image_multi(const qamd_u8 *h, uint32_t nq_valid, const uint8_t *qcodes, uint64_t q_pitch, const float *q_offs,
+                        float *out, const TopkFilterSlices *slices, hipStream_t s, const ScanEpi &e = ScanEpi{}) {
+    if (nq_valid < 2 || nq_valid > image_multi_width(h) || (slices && e.mode != EPI_POINT)) return false;
+    const uint64_t n_rows = scan_rows(h, e);  // also the pitch of `out`
+    const uint32_t split = blocked_split(n_rows), blocks_per_wg = (kScanBlock / 64) / split;
+    const uint64_t blocks = (n_rows + kPackBlockRows - 1) / kPackBlockRows;
+    const unsigned grid = (unsigned)((blocks + blocks_per_wg - 1) / blocks_per_wg);
+    h->last_scan_packed.store(h->image.kind, std::memory_order_relaxed);
+    h->last_scan_split.store((int)split, std::memory_order_relaxed);
+    h->last_scan_queries.store((int)nq_valid, std::memory_order_relaxed);
+    auto go = [&](auto nq) {
+        with_bool(slices != nullptr, [&](auto fi) {
+            with_epi(e.mode, [&](auto epi) {
+                if constexpr (!(fi && epi == EPI_INTERNAL))  // (no filtering form of score_internal is instantiated)
+                    hipLaunchKernelGGL((u8_scan_image_multi_kernel<nq, fi, epi>), dim3(grid), dim3(kScanBlock), 0, s,
+                                       h->packed.as<uint4>(), h->offsets.as<float>(), qcodes, (uint32_t)q_pitch, q_offs, nq_valid,
+                                       h->meta.multiplier, (uint32_t)n_rows, h->image.chunks, h->image.aux, split, out, n_rows,
+                                       slices ? *slices : TopkFilterSlices{}, e.diff);
+            });
+        });
+    };
+    if (nq_valid <= 2) go(std::integral_constant<int, 2>{});
+    else if (nq_valid <= 4) go(std::integral_constant<int, 4>{});
+    else go(std::integral_constant<int, 8>{});
+    return true;
 }
 
 // Returns false when the store's row size has no templated kernel (caller uses the generic one).
@@ -2011,6 +2174,19 @@ bool launch_multi(const qamd_u8 *h, uint32_t nq_valid, const uint8_t *qcodes, ui
     return false;
 }
 
+// What the batch callers below walk their queries with: the widest pass of the store - over the nibble image for a
+// compact store, over the byte codes otherwise - and one such pass for 2 .. pass_width queries (false = unsupported).
+uint32_t pass_width(const qamd_u8 *h) {
+    const uint32_t image_width = image_multi_width(h);
+    return image_width ? image_width : multi_width(h);
+}
+bool launch_pass(const qamd_u8 *h, uint32_t nq_valid, const uint8_t *qcodes, uint64_t q_pitch, const float *q_offs, float *out,
+                 const TopkFilterSlices *slices, hipStream_t s, const ScanEpi &e = ScanEpi{}) {
+    if (image_multi_width(h)) return launch_image_multi(h, nq_valid, qcodes, q_pitch, q_offs, out, slices, s, e);
+    return h->meta.vector_parameters.distance_type == QAMD_L1 ? launch_multi<true>(h, nq_valid, qcodes, q_pitch, q_offs, out, slices, s, e)
+                                                              : launch_multi<false>(h, nq_valid, qcodes, q_pitch, q_offs, out, slices, s, e);
+}
+
 bool fused_capable(const qamd_u8 *h) { return !lane_order(h) && h->row_chunks <= 128; }
 
 // The single-launch top-k serves this store and k (and, for a fused query, these dims): its plan.
@@ -2166,9 +2342,10 @@ uint32_t internal_batch_group(const qamd_u8 *h) {
 }
 
 // out_dev[l * n_ids + j] = score_internal(rows_dev[l], j) for l < n, j < n_ids <= count.  The rows are gathered once;
-// then passes of multi_width(h) rows (u8_scan_multi_kernel with score_internal's epilogue: the integer sum and the f32
-// epilogue of the single-row scan, so the same bits), a remainder of one row and every row size without a multi form
-// (fewer than 9 or more than 128 pieces, lane order) through the single-row scan.  Enqueues only.
+// then passes of pass_width(h) rows (u8_scan_multi_kernel or, for a compact store, u8_scan_image_multi_kernel, with
+// score_internal's epilogue: the integer sum and the f32 epilogue of the single-row scan, so the same bits), a remainder
+// of one row and every row size without a multi form (fewer than 9 or more than 128 pieces, lane order) through the
+// single-row scan.  Enqueues only.
 qamd_status score_internal_rows_dev(const qamd_u8 *h, const uint32_t *rows_dev, uint32_t n, uint64_t n_ids, float *out_dev,
                                     hipStream_t s) {
     const uint64_t pitch = h->meta.actual_dim;  // 16 * row_chunks
@@ -2177,7 +2354,7 @@ qamd_status score_internal_rows_dev(const qamd_u8 *h, const uint32_t *rows_dev, 
     QAMD_TRY(stage.alloc(code_bytes + (size_t)n * 4, s));
     uint8_t *qcodes = stage.as<uint8_t>();
     float *q_offs = reinterpret_cast<float *>(qcodes + code_bytes);
-    if (h->compact) {  // the rows come out of the image; every one of them then takes the image scan (width 0)
+    if (h->compact) {  // the rows come out of the image, and then take the image scan up to 8 at a time
         QAMD_TRY(launch_unpack(h, rows_dev, 0, n, qcodes, pitch, q_offs, s));
     } else {
         hipLaunchKernelGGL(u8_gather_rows_kernel, dim3(n), dim3(64), 0, s, h->byte_codes<uint4>(), h->offsets.as<float>(),
@@ -2185,14 +2362,12 @@ qamd_status score_internal_rows_dev(const qamd_u8 *h, const uint32_t *rows_dev, 
         QAMD_HIP(hipGetLastError());
     }
     const ScanEpi e{internal_diff(h), EPI_INTERNAL, n_ids};
-    const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
-    const uint32_t width = multi_width(h);
+    const uint32_t width = pass_width(h);
     for (uint32_t l = 0; l < n;) {
         const uint32_t nq = std::min(width, n - l);
         const uint8_t *qc = qcodes + (uint64_t)l * pitch;
         float *o = out_dev + (uint64_t)l * n_ids;
-        const bool ok = nq >= 2 && (is_l1 ? launch_multi<true>(h, nq, qc, pitch, q_offs + l, o, nullptr, s, e)
-                                          : launch_multi<false>(h, nq, qc, pitch, q_offs + l, o, nullptr, s, e));
+        const bool ok = nq >= 2 && launch_pass(h, nq, qc, pitch, q_offs + l, o, nullptr, s, e);
         if (ok) {
             l += nq;
         } else {
@@ -3505,16 +3680,14 @@ qamd_status u8_topk_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint
     scan.score_ids = [&](uint32_t q, const uint32_t *ids, uint64_t n_ids, float *out, hipStream_t st) {
         return score_ids_dev(h, qc(q), offsets_dev + q, 0.0f, EPI_POINT, ids, n_ids, out, st);
     };
-    const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
-    const uint32_t width = multi_width(h);
+    const uint32_t width = pass_width(h);
     if (width)  // one filtering pass over the rows for up to `width` queries
-        scan.scan_filter_multi = [&, width, is_l1](uint32_t q, uint32_t left, const TopkFilterSlices &sl, hipStream_t st,
-                                                   qamd_status &status) -> uint32_t {
+        scan.scan_filter_multi = [&, width](uint32_t q, uint32_t left, const TopkFilterSlices &sl, hipStream_t st,
+                                            qamd_status &status) -> uint32_t {
             const uint32_t nq = std::min(left, width);
             if (nq < 2) return 0;
             const uint8_t *qcodes = codes_dev + (uint64_t)q * pitch;
-            const bool ok = is_l1 ? launch_multi<true>(h, nq, qcodes, pitch, offsets_dev + q, nullptr, &sl, st)
-                                  : launch_multi<false>(h, nq, qcodes, pitch, offsets_dev + q, nullptr, &sl, st);
+            const bool ok = launch_pass(h, nq, qcodes, pitch, offsets_dev + q, nullptr, &sl, st);
             if (ok && hipGetLastError() != hipSuccess) status = fail(QAMD_ERR_DEVICE, "u8 multi-query filter launch failed");
             return ok ? nq : 0;
         };
@@ -3534,7 +3707,8 @@ qamd_status u8_score_lists(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t 
 uint32_t u8_multi_width(const qamd_u8 *h) { return multi_width(h); }
 
 // Lane mode 1 on a Dot / L2 store: the batch API must take the per-query scans (the matrix cores sum exactly).  So must
-// a compact store: the matrix-core kernels and the multi-query scan read byte codes, which it has not.
+// a compact store: the matrix-core kernels and u8_scan_multi_kernel read byte codes, which it has not; its
+// batches share passes over the nibble image instead (u8_scan_image_multi_kernel, pass_width).
 bool u8_batch_by_scans(const qamd_u8 *h) { return lane_order(h) || h->compact; }
 
 void no_byte_codes() {
@@ -3546,15 +3720,13 @@ void no_byte_codes() {
 // `width`, then smaller groups, then single scans).
 qamd_status u8_score_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t pitch, const float *offsets_dev,
                                  uint32_t n_queries, float *out_dev, hipStream_t stream) {
-    const bool is_l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
-    const uint32_t width = multi_width(h);
+    const uint32_t width = pass_width(h);
     uint32_t q = 0;
     while (q < n_queries) {
         const uint32_t nq = std::min(width, n_queries - q);
         const uint8_t *qcodes = codes_dev + (uint64_t)q * pitch;
         float *o = out_dev + (uint64_t)q * h->count;
-        const bool ok = nq >= 2 && (is_l1 ? launch_multi<true>(h, nq, qcodes, pitch, offsets_dev + q, o, nullptr, stream)
-                                          : launch_multi<false>(h, nq, qcodes, pitch, offsets_dev + q, o, nullptr, stream));
+        const bool ok = nq >= 2 && launch_pass(h, nq, qcodes, pitch, offsets_dev + q, o, nullptr, stream);
         if (ok) {
             q += nq;
         } else {
@@ -3658,9 +3830,13 @@ extern "C" __attribute__((visibility("default"))) void qamd_dev_u8_packed_blocke
     *chunks = h->image.chunks;
     *block_rows = kPackBlockRows;
 }
-// Which image the store's last scan launch read (U8Image::kind), and how many waves per block its last blocked scan took.
+// Which image the store's last scan launch read (U8Image::kind), and how many waves per block its last blocked scan took
+// and how many queries it served (1: u8_scan_image_kernel; 2 .. 8: one pass of u8_scan_image_multi_kernel).
 extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_split(const qamd_u8 *h) {
     return h->last_scan_split.load(std::memory_order_relaxed);
+}
+extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_queries(const qamd_u8 *h) {
+    return h->last_scan_queries.load(std::memory_order_relaxed);
 }
 extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_packed(const qamd_u8 *h) {
     return h->last_scan_packed.load(std::memory_order_relaxed);

@@ -65,6 +65,7 @@ struct qamd_u8 {
     U8Image image;
     mutable std::atomic<int> last_scan_packed{0};  // image.kind of the image the last scan launch read (developer report)
     mutable std::atomic<int> last_scan_split{0};   // waves per block of the last blocked scan launch (developer report)
+    mutable std::atomic<int> last_scan_queries{0}; // queries the last blocked scan launch served (developer report)
     mutable qamd::DevBuf packed_rows;              // developer report: the image un-blocked, [count][image.chunks]
     // The batched top-k's pivot sample (u8_batch.hip): rows hash(j) of the store, j < sample_rows, then 512
     // zero rows; gathered on first use (count / 64 rows at most: 1.6 % of the store), discarded by an upsert.
@@ -124,7 +125,9 @@ qamd_status u8_topk_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint
                                 uint32_t n_queries, uint32_t k, int largest, uint32_t *out_ids, float *out_scores,
                                 qamd_mem out_mem, hipStream_t stream);
 uint32_t u8_multi_width(const qamd_u8 *h);
-bool u8_batch_by_scans(const qamd_u8 *h);  // lane mode 1 on Dot / L2, or a compact store: batches go query by query
+// Lane mode 1 on Dot / L2: batches go query by query.  A compact store: up to 8 queries per pass over its nibble image
+// (u8_scan_image_multi_kernel), never the matrix cores.
+bool u8_batch_by_scans(const qamd_u8 *h);
 qamd_status u8_score_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t pitch, const float *offsets_dev,
                                  uint32_t n_queries, float *out_dev, hipStream_t stream);
 qamd_status u8_score_single(const qamd_u8 *h, const uint8_t *codes_dev, const float *offset_dev, float *out_dev,
