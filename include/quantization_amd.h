@@ -68,6 +68,21 @@ enum { QAMD_BITS4 = 32,    /* flag: or-ed onto QAMD_DOT or QAMD_L2, plain or rot
 enum { QAMD_COMPACT = 128, /* flag: or-ed onto a QAMD_BITS4 metric, plain or rotated; the legal values are the four below */
        QAMD_DOT_BITS4_COMPACT = 160, QAMD_L2_BITS4_COMPACT = 162, QAMD_DOT_ROTATED_BITS4_COMPACT = 168,
        QAMD_L2_ROTATED_BITS4_COMPACT = 170 };
+enum { QAMD_FULL = 64,     /* flag: full-range byte codes, 255 levels; the legal values of distance_type are the five below */
+       QAMD_DOT_FULL = 64, QAMD_L1_FULL = 65, QAMD_L2_FULL = 66, QAMD_DOT_ROTATED_FULL = 72, QAMD_L2_ROTATED_FULL = 74 };
+/* A FULL-RANGE scalar-u8 store (no counterpart in the reference).  The reference keeps codes 0..127
+ * in a byte because its AVX2 kernel saturates on larger unsigned operands; the dot and sad instructions of gfx950 take
+ * whole unsigned bytes.  QAMD_FULL or-ed onto the metric (64, 65, 66, 72, 74) in qamd_u8_encode, qamd_u8_encoder_begin
+ * and qamd_u8_from_rows, and "full_range":true as the last key of the metadata file for qamd_u8_load (only true, only
+ * once, never beside "bits":4; anything else is QAMD_ERR_IO): alpha = (max - min) / 255 and code(v) =
+ * trunc(clamp((v - offset) / alpha + 0.5, 0, 255)), the 4-bit store's rule with 255 for 15; rows keep the reference's
+ * format, the same 772 bytes at dim 768, at half the quantisation step.  Every score is the exact integer pair sum,
+ * converted to f32 once, through the store's epilogue.  Such a store keeps byte codes and no scan image; batches beyond
+ * the multi-query scan take the int8 matrix cores on codes - 128 (u8_full_batch_kernel).  Refused with
+ * QAMD_ERR_ARGUMENTS before any device call: the flag with QAMD_BITS4 or QAMD_COMPACT, with QAMD_L1 and QAMD_ROTATED
+ * together, the rotated form's dim rules, dim above 16384 (255 * 255 * dim stays inside an i32 up to there), the flag
+ * on every qamd_pq_*, qamd_bin_*, qamd_f32_* and qamd_*_sharded_* constructor, and qamd_u8_set_lane_mode(h, 1) on such
+ * a handle (the lane order restates an AVX2 kernel that cannot run these codes).  No new symbol: still 192 entry points. */
 /* A ROTATED scalar-u8 store (no counterpart in the reference).  qamd_u8_encode, qamd_u8_encoder_begin and
  * qamd_u8_from_rows take QAMD_DOT_ROTATED or QAMD_L2_ROTATED as distance_type: every row - and every query, inside
  * qamd_u8_encode_query / qamd_u8_encode_query_batch - goes through a fixed randomized Hadamard block rotation (blocks of

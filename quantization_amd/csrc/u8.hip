@@ -147,18 +147,22 @@ __device__ __forceinline__ uint32_t f32_to_u8(float v, float alpha, float offset
 // The code of a 4-bit store (the reference has no counterpart): 16 levels, rounded to nearest.  Three f32
 // operations, each rounded on its own - subtract, IEEE divide, add (this file is compiled with contraction off) - then the
 // clamp and the truncation of f32_to_u8.  NaN gives 0.  No division-free form: every 4-bit encoder takes this one.
-__device__ __forceinline__ uint32_t f32_to_u4(float v, float alpha, float offset) {
+// A full-range store takes the same rule with 255 for 15: `top` is the largest code.
+__device__ __forceinline__ uint32_t f32_to_nearest(float v, float alpha, float offset, float top) {
     float x = (v - offset) / alpha + 0.5f;
     x = (x < 0.0f) ? 0.0f : x;
-    x = (x > 15.0f) ? 15.0f : x;
+    x = (x > top) ? top : x;
     return (x != x) ? 0u : (uint32_t)x;
 }
-template <bool FOUR> __device__ __forceinline__ uint32_t f32_to_code(float v, float alpha, float offset) {
-    return FOUR ? f32_to_u4(v, alpha, offset) : f32_to_u8(v, alpha, offset);
+__device__ __forceinline__ uint32_t f32_to_u4(float v, float alpha, float offset) { return f32_to_nearest(v, alpha, offset, 15.0f); }
+// LEVELS (u8_levels, u8_internal.hpp): 127 = the reference's truncating code, 15 and 255 = rounded to nearest.
+template <int LEVELS> __device__ __forceinline__ uint32_t f32_to_code(float v, float alpha, float offset) {
+    static_assert(LEVELS == 127 || LEVELS == 15 || LEVELS == 255, "code levels");
+    return LEVELS == 127 ? f32_to_u8(v, alpha, offset) : f32_to_nearest(v, alpha, offset, (float)LEVELS);
 }
-// The same choice at run time (`four` is a kernel argument: wave-uniform), for the kernels where no time is at stake.
-__device__ __forceinline__ uint32_t f32_to_code(float v, float alpha, float offset, int four) {
-    return four ? f32_to_u4(v, alpha, offset) : f32_to_u8(v, alpha, offset);
+// The same choice at run time (`levels` is a kernel argument: wave-uniform), for the kernels where no time is at stake.
+__device__ __forceinline__ uint32_t f32_to_code(float v, float alpha, float offset, int levels) {
+    return levels == 127 ? f32_to_u8(v, alpha, offset) : f32_to_nearest(v, alpha, offset, (float)levels);
 }
 
 // f32_to_u8 for four values without the division, for all but ~6 values in 100 000.
@@ -1126,7 +1130,7 @@ __global__ __launch_bounds__(kScanBlock) void minmax_stream_kernel(const float4 
 // by the vector ALU; plain instead of nt stores: the same; a lane owning four consecutive float4 (one 16-byte
 // store per lane, loads at a 64-byte lane stride): 3.6 ms.
 template <int ITERS /* float4 per lane, 0 = any dim (loop of 4-deep batches) */, bool FAST /* f32x4_to_u8x4_fast */,
-          bool FOUR = false /* 4-bit codes (f32_to_u4); never FAST */>
+          int LEVELS = 127 /* code levels (f32_to_code); 15 and 255 are never FAST */>
 __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
     const float *__restrict__ data, uint64_t n_rows, uint32_t dim, uint32_t actual_dim, float alpha,
     float offset, int distance, int invert, uint32_t *__restrict__ codes32, float *__restrict__ offsets,
@@ -1143,7 +1147,7 @@ __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
     const uint32_t dwords = actual_dim / 4, f4 = dim / 4;
     uint32_t *dst = codes32 + (row0 + rc) * dwords;
     const float placeholder = (distance == QAMD_DOT) ? 0.0f : offset;
-    const uint32_t pad_code = f32_to_code<FOUR>(placeholder, alpha, offset);
+    const uint32_t pad_code = f32_to_code<LEVELS>(placeholder, alpha, offset);
     const uint32_t pad_dword = pad_code * 0x01010101u;
     uint32_t s1 = 0, s2 = 0;
     constexpr int DEPTH = ITERS ? ITERS : 4;
@@ -1163,8 +1167,8 @@ __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
                 if (FAST) {
                     packed = f32x4_to_u8x4_fast(f[j], alpha, offset, r_alpha);
                 } else {
-                    packed = f32_to_code<FOUR>(f[j].x, alpha, offset) | (f32_to_code<FOUR>(f[j].y, alpha, offset) << 8) |
-                             (f32_to_code<FOUR>(f[j].z, alpha, offset) << 16) | (f32_to_code<FOUR>(f[j].w, alpha, offset) << 24);
+                    packed = f32_to_code<LEVELS>(f[j].x, alpha, offset) | (f32_to_code<LEVELS>(f[j].y, alpha, offset) << 8) |
+                             (f32_to_code<LEVELS>(f[j].z, alpha, offset) << 16) | (f32_to_code<LEVELS>(f[j].w, alpha, offset) << 24);
                 }
                 s1 = __builtin_amdgcn_udot4(packed, 0x01010101u, s1, false);  // sum of the four codes
                 s2 = __builtin_amdgcn_udot4(packed, packed, s2, false);       // sum of their squares
@@ -1187,7 +1191,7 @@ __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
             if (s1 >= (1u << 24)) {
                 sum = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++)
-                    sum += (float)(j < dim ? f32_to_code<FOUR>(src[j], alpha, offset) : pad_code);
+                    sum += (float)(j < dim ? f32_to_code<LEVELS>(src[j], alpha, offset) : pad_code);
             }
             vo = D * offset * offset + sum * alpha * offset;
         } else if (distance == QAMD_L1) {
@@ -1197,7 +1201,7 @@ __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
             if (s2 >= (1u << 24)) {
                 sum = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++) {
-                    const float c = (float)(j < dim ? f32_to_code<FOUR>(src[j], alpha, offset) : pad_code);
+                    const float c = (float)(j < dim ? f32_to_code<LEVELS>(src[j], alpha, offset) : pad_code);
                     sum += c * c;
                 }
             }
@@ -1215,12 +1219,12 @@ __global__ __launch_bounds__(kScanBlock) void quantize16_kernel(
 __global__ __launch_bounds__(kBlock) void quantize_kernel(
     const float *__restrict__ data, uint64_t n_rows, uint32_t dim, uint32_t actual_dim, float alpha,
     float offset, int distance, int invert, uint32_t *__restrict__ codes32 /* row stride actual_dim/4 */,
-    float *__restrict__ offsets, uint64_t row0, int four) {
+    float *__restrict__ offsets, uint64_t row0, int levels) {
     const int lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * kBlock) >> 6;
     const float placeholder = (distance == QAMD_DOT) ? 0.0f : offset;
-    const uint32_t pad_code = f32_to_code(placeholder, alpha, offset, four);
+    const uint32_t pad_code = f32_to_code(placeholder, alpha, offset, levels);
     const uint32_t dwords = actual_dim / 4;
     for (uint64_t r = wave; r < n_rows; r += n_waves) {
         const float *src = data + r * dim;
@@ -1231,7 +1235,7 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
 #pragma unroll
             for (int b = 0; b < 4; b++) {
                 uint32_t j = d * 4 + b;
-                uint32_t c = j < dim ? f32_to_code(src[j], alpha, offset, four) : pad_code;
+                uint32_t c = j < dim ? f32_to_code(src[j], alpha, offset, levels) : pad_code;
                 packed |= c << (8 * b);
                 s1 += c;
                 s2 += c * c;
@@ -1251,7 +1255,7 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
                 if (s1 >= (1u << 24)) {
                     s = 0.0f;
                     for (uint32_t j = 0; j < actual_dim; j++)
-                        s += (float)(j < dim ? f32_to_code(src[j], alpha, offset, four) : pad_code);
+                        s += (float)(j < dim ? f32_to_code(src[j], alpha, offset, levels) : pad_code);
                 }
                 vo = D * offset * offset + s * alpha * offset;
             } else if (distance == QAMD_L1) {
@@ -1261,7 +1265,7 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
                 if (s2 >= (1u << 24)) {
                     s = 0.0f;
                     for (uint32_t j = 0; j < actual_dim; j++) {
-                        float c = (float)(j < dim ? f32_to_code(src[j], alpha, offset, four) : pad_code);
+                        float c = (float)(j < dim ? f32_to_code(src[j], alpha, offset, levels) : pad_code);
                         s += c * c;
                     }
                 }
@@ -1282,16 +1286,20 @@ __global__ __launch_bounds__(kBlock) void quantize_kernel(
 // quantile sample).  The frames call a sink for live chunks only: the lanes of a last chunk past dim / 4, which hold
 // +-0.0, reach no fold and no store.
 constexpr int kQuant4Bit = 2;  // `fast` of RotQuantizeSink: 0 the exact division, 1 the division-free form, 2 4-bit codes
+constexpr int kQuantFull = 3;  // 3: full-range codes
 __device__ __forceinline__ uint32_t rot_quant4(const float (&v)[4], float alpha, float offset, float r_alpha, int fast) {
     const float4 f = make_float4(v[0], v[1], v[2], v[3]);
     if (fast == kQuant4Bit)  // a 4-bit store; wave-uniform
         return f32_to_u4(f.x, alpha, offset) | (f32_to_u4(f.y, alpha, offset) << 8) | (f32_to_u4(f.z, alpha, offset) << 16) |
                (f32_to_u4(f.w, alpha, offset) << 24);
+    if (fast == kQuantFull)  // a full-range store; wave-uniform
+        return f32_to_code<255>(f.x, alpha, offset) | (f32_to_code<255>(f.y, alpha, offset) << 8) |
+               (f32_to_code<255>(f.z, alpha, offset) << 16) | (f32_to_code<255>(f.w, alpha, offset) << 24);
     if (fast) return f32x4_to_u8x4_fast(f, alpha, offset, r_alpha);
     return f32_to_u8(f.x, alpha, offset) | (f32_to_u8(f.y, alpha, offset) << 8) | (f32_to_u8(f.z, alpha, offset) << 16) |
            (f32_to_u8(f.w, alpha, offset) << 24);
 }
-// vector_offset of a row from its code sums (quantize16_kernel's epilogue; s1 <= 127 * 16384 < 2^24 always).  `sum2` is
+// vector_offset of a row from its code sums (quantize16_kernel's epilogue; s1 <= 255 * 16384 < 2^24 always).  `sum2` is
 // the f32 sum of squares: (float)s2 below 2^24, else the caller's replay of the reference's sequential f32 loop.
 __device__ __forceinline__ float rot_row_offset(uint32_t dim, float alpha, float offset, int distance, int invert, uint32_t s1,
                                                 float sum2) {
@@ -1455,14 +1463,14 @@ struct RotValuesSink : RotSink {
 __global__ __launch_bounds__(64) void encode_query_kernel(const float *__restrict__ query,
                                                          uint32_t qdim, uint32_t actual_dim,
                                                          float alpha, float offset, int distance,
-                                                         int invert, uint8_t *__restrict__ qbuf, int four) {
+                                                         int invert, uint8_t *__restrict__ qbuf, int levels) {
     const int lane = threadIdx.x;
     const float placeholder = (distance == QAMD_DOT) ? 0.0f : offset;
-    const uint32_t pad_code = f32_to_code(placeholder, alpha, offset, four);
+    const uint32_t pad_code = f32_to_code(placeholder, alpha, offset, levels);
     uint8_t *codes = qbuf + 16;
     uint32_t s1 = 0, s2 = 0;
     for (uint32_t j = lane; j < actual_dim; j += 64) {
-        uint32_t c = j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code;
+        uint32_t c = j < qdim ? f32_to_code(query[j], alpha, offset, levels) : pad_code;
         codes[j] = (uint8_t)c;
         s1 += c;
         s2 += c * c;
@@ -1479,7 +1487,7 @@ __global__ __launch_bounds__(64) void encode_query_kernel(const float *__restric
             if (s1 >= (1u << 24)) {
                 s = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++)
-                    s += (float)(j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code);
+                    s += (float)(j < qdim ? f32_to_code(query[j], alpha, offset, levels) : pad_code);
             }
             off = s * alpha * offset;
         } else if (distance == QAMD_L1) {
@@ -1489,7 +1497,7 @@ __global__ __launch_bounds__(64) void encode_query_kernel(const float *__restric
             if (s2 >= (1u << 24)) {
                 s = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++) {
-                    float c = (float)(j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code);
+                    float c = (float)(j < qdim ? f32_to_code(query[j], alpha, offset, levels) : pad_code);
                     s += c * c;
                 }
             }
@@ -1504,15 +1512,15 @@ __global__ __launch_bounds__(64) void encode_query_kernel(const float *__restric
 __global__ __launch_bounds__(64) void encode_queries_kernel(const float *__restrict__ queries, uint32_t qdim,
                                                            uint32_t actual_dim, float alpha, float offset,
                                                            int distance, int invert, uint8_t *__restrict__ codes_out,
-                                                           uint32_t code_pitch, float *__restrict__ offsets_out, int four) {
+                                                           uint32_t code_pitch, float *__restrict__ offsets_out, int levels) {
     const int lane = threadIdx.x;
     const float *query = queries + (size_t)blockIdx.x * qdim;
     uint8_t *codes = codes_out + (size_t)blockIdx.x * code_pitch;
     const float placeholder = (distance == QAMD_DOT) ? 0.0f : offset;
-    const uint32_t pad_code = f32_to_code(placeholder, alpha, offset, four);
+    const uint32_t pad_code = f32_to_code(placeholder, alpha, offset, levels);
     uint32_t s1 = 0, s2 = 0;
     for (uint32_t j = lane; j < actual_dim; j += 64) {
-        uint32_t c = j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code;
+        uint32_t c = j < qdim ? f32_to_code(query[j], alpha, offset, levels) : pad_code;
         codes[j] = (uint8_t)c;
         s1 += c;
         s2 += c * c;
@@ -1529,7 +1537,7 @@ __global__ __launch_bounds__(64) void encode_queries_kernel(const float *__restr
             if (s1 >= (1u << 24)) {
                 s = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++)
-                    s += (float)(j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code);
+                    s += (float)(j < qdim ? f32_to_code(query[j], alpha, offset, levels) : pad_code);
             }
             off = s * alpha * offset;
         } else if (distance == QAMD_L1) {
@@ -1539,7 +1547,7 @@ __global__ __launch_bounds__(64) void encode_queries_kernel(const float *__restr
             if (s2 >= (1u << 24)) {
                 s = 0.0f;
                 for (uint32_t j = 0; j < actual_dim; j++) {
-                    float c = (float)(j < qdim ? f32_to_code(query[j], alpha, offset, four) : pad_code);
+                    float c = (float)(j < qdim ? f32_to_code(query[j], alpha, offset, levels) : pad_code);
                     s += c * c;
                 }
             }
@@ -1758,7 +1766,7 @@ bool rot_dim_ok(uint64_t dim) { return dim != 0 && dim % kRotBlockMin == 0 && di
 
 namespace {
 
-U8Image u8_image_of(uint32_t rc, bool four_bit, int distance);
+U8Image u8_image_of(uint32_t rc, bool four_bit, int distance, bool full_range = false);
 
 qamd_status alloc_store(qamd_u8 *h) {
     h->capacity = h->count;
@@ -1781,8 +1789,9 @@ qamd_status alloc_store(qamd_u8 *h) {
 // format's second kernel argument (Image7: the extra chunks, Image4: the row's code chunks).  Only the Dot / L2 scans of
 // lane mode 0 read an image, so L1 stores and stores of more than 128 chunks (the generic kernel) have none; nor do
 // 7-bit stores of fewer than 8 chunks (no whole extra chunk) and 4-bit stores of fewer than 2.
-U8Image u8_image_of(uint32_t rc, bool four_bit, int distance) {
-    if (distance == QAMD_L1 || rc > 128 || rc < (four_bit ? 2u : 8u)) return U8Image{};
+// A full-range store has none either: its codes do not fit 7 bits, and it keeps bytes only.
+U8Image u8_image_of(uint32_t rc, bool four_bit, int distance, bool full_range) {
+    if (full_range || distance == QAMD_L1 || rc > 128 || rc < (four_bit ? 2u : 8u)) return U8Image{};
     if (four_bit) return U8Image{U8_IMAGE_NIBBLE, (rc + 1) / 2, rc};
     return U8Image{U8_IMAGE_7BIT, rc - rc / 8, rc / 8};
 }
@@ -1793,7 +1802,7 @@ qamd_status launch_pack(const qamd_u8 *h, uint64_t r0, uint64_t n_rows, uint32_t
                         const uint4 *tile = nullptr) {
     const auto kernel = h->image.kind == U8_IMAGE_NIBBLE ? u8_pack_image_kernel<Image4> : u8_pack_image_kernel<Image7>;
     hipLaunchKernelGGL(kernel, dim3(grid_for(n_rows * h->image.chunks, kBlock, 8)), dim3(kBlock), 0, s,
-                       tile ? tile : h->byte_codes<uint4>(), tile ? r0 : 0, r0, n_rows, h->row_chunks, h->image.chunks,
+                       tile ? tile : h->codes_7bit<uint4>(), tile ? r0 : 0, r0, n_rows, h->row_chunks, h->image.chunks,
                        h->packed.as<uint4>(), bad);
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
@@ -1857,7 +1866,7 @@ qamd_status build_packed(qamd_u8 *h, hipStream_t s) {
     h->packed.release();
     h->packed_rows.release();
     h->image = U8Image{};
-    const U8Image im = u8_image_of(h->row_chunks, h->four_bit, h->meta.vector_parameters.distance_type);
+    const U8Image im = u8_image_of(h->row_chunks, h->four_bit, h->meta.vector_parameters.distance_type, h->full_range);
     if (!u8_packed_allowed() || h->count == 0 || !im.kind) return QAMD_OK;
     const uint64_t bytes = h->padded_rows * im.chunks * 16;
     size_t free_b = 0, total_b = 0;
@@ -2051,7 +2060,7 @@ template <bool IS_L1> struct SmallLaunch {
             const qamd_vector_parameters &vp = h->meta.vector_parameters;
             with_bool(exact, [&](auto ex) {
                 hipLaunchKernelGGL((u8_topk_small_fused_kernel<G, ITERS, IS_L1, ex>), dim3(pl.workgroups), dim3(1024), 0, s,
-                                   h->byte_codes<uint4>(), h->offsets.as<float>(), qv, fq->qdim, (uint32_t)h->meta.actual_dim,
+                                   h->codes_7bit<uint4>() /* its prologue quantises with f32_to_u8 */, h->offsets.as<float>(), qv, fq->qdim, (uint32_t)h->meta.actual_dim,
                                    h->meta.alpha, h->meta.offset, vp.distance_type, vp.invert, fq->qbuf, h->meta.multiplier,
                                    (uint32_t)h->count, h->row_chunks, pl.rows_per_wg, p);
             });
@@ -2107,6 +2116,8 @@ void launch_multi_shape(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitc
     const unsigned grid = (unsigned)((waves + kScanBlock / 64 - 1) / (kScanBlock / 64));
     const bool exact = h->row_chunks == (uint32_t)(G * ITERS);
     h->last_scan_packed.store(0, std::memory_order_relaxed);
+    h->last_full_batch.store(0, std::memory_order_relaxed);
+    h->last_scan_queries.store((int)nq_valid, std::memory_order_relaxed);
 #define QAMD_U8_MULTI(EX, FI, EPI)                                                                                 \
     hipLaunchKernelGGL((u8_scan_multi_kernel<G, ITERS, UNROLL, NQ, IS_L1, EX, FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, \
                        h->byte_codes<uint4>(), h->offsets.as<float>(), qcodes, (uint32_t)q_pitch, q_offs, nq_valid,   \
@@ -2209,7 +2220,7 @@ qamd_status scan_ptrs(const qamd_u8 *h, const uint4 *qc, const float *qo, float 
         uint64_t waves = (scan_rows(h, e) + 3) / 4;
         unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
         with_epi(e.mode, [&](auto epi) {
-            hipLaunchKernelGGL((u8_scan_avx2_lanes_kernel<true, epi>), dim3(grid), dim3(kBlock), 0, s, h->byte_codes<uint4>(),
+            hipLaunchKernelGGL((u8_scan_avx2_lanes_kernel<true, epi>), dim3(grid), dim3(kBlock), 0, s, h->codes_7bit<uint4>(),
                                h->offsets.as<float>(), qc, qo, h->meta.multiplier, (uint32_t)scan_rows(h, e), h->row_chunks,
                                out_dev, e.diff);
         });
@@ -2249,7 +2260,7 @@ qamd_status launch_pairs(const qamd_u8 *h, const uint4 *qc, const float *qo, con
                        h->meta.multiplier, diff, mode, ids_dev, n_ids, (uint32_t)h->count, h->row_chunks, (uint32_t)ppb, \
                        out_dev)
     if (!IS_L1 && lane_order(h)) {
-        hipLaunchKernelGGL((u8_score_pairs_kernel<false, 0, true>), dim3(grid), dim3(kBlock), 0, s, h->byte_codes<uint4>(),
+        hipLaunchKernelGGL((u8_score_pairs_kernel<false, 0, true>), dim3(grid), dim3(kBlock), 0, s, h->codes_7bit<uint4>(),
                            h->offsets.as<float>(), qc, qo, q_batch, q_pitch, q_offs, lists, n_lists, list_rows,
                            h->meta.multiplier, diff, mode, ids_dev, n_ids, (uint32_t)h->count, h->row_chunks, (uint32_t)ppb,
                            out_dev);
@@ -2362,6 +2373,9 @@ qamd_status score_internal_rows_dev(const qamd_u8 *h, const uint32_t *rows_dev, 
         QAMD_HIP(hipGetLastError());
     }
     const ScanEpi e{internal_diff(h), EPI_INTERNAL, n_ids};
+    // A full-range store: more rows than the multi-query scan takes go to the matrix cores, 15 per pass
+    if (h->full_range && h->meta.vector_parameters.distance_type != QAMD_L1 && n >= u8_full_batch_min(h))
+        return u8_full_batch_scores(h, qcodes, pitch, q_offs, n, n_ids, out_dev, n_ids, EPI_INTERNAL, e.diff, s);
     const uint32_t width = pass_width(h);
     for (uint32_t l = 0; l < n;) {
         const uint32_t nq = std::min(width, n - l);
@@ -2549,7 +2563,7 @@ qamd_status quantize_rows(const qamd_u8 *h, const float *src, uint64_t nr, uint3
     const bool fast = alpha >= 8.673617379884035e-19f && alpha <= 1.152921504606847e+18f;  // 2^-60 .. 2^60
     if (h->rotated) {  // rotated in registers, no copy of the rotated values
         RotQuantizeSink sink;
-        sink.alpha = alpha, sink.offset = offset, sink.fast = h->four_bit ? kQuant4Bit : (int)fast;
+        sink.alpha = alpha, sink.offset = offset, sink.fast = h->four_bit ? kQuant4Bit : h->full_range ? kQuantFull : (int)fast;
         sink.distance = vp.distance_type, sink.invert = vp.invert;
         sink.codes32 = codes32, sink.offsets = offsets, sink.row0 = r0;
         return launch_rot_u8(sink, src, nr, dim, s);
@@ -2561,7 +2575,11 @@ qamd_status quantize_rows(const qamd_u8 *h, const float *src, uint64_t nr, uint3
 #define QAMD_Q16(IT)                                                                                          \
     do {                                                                                                      \
         if (h->four_bit)  /* 4-bit codes take the exact division */                              \
-            hipLaunchKernelGGL((quantize16_kernel<IT, false, true>), dim3(grid), dim3(kScanBlock), 0, s, src, nr, \
+            hipLaunchKernelGGL((quantize16_kernel<IT, false, 15>), dim3(grid), dim3(kScanBlock), 0, s, src, nr, \
+                               (uint32_t)dim, (uint32_t)h->meta.actual_dim, alpha, offset, vp.distance_type,  \
+                               vp.invert, codes32, offsets, r0);                                              \
+        else if (h->full_range)  /* and so do full-range codes (the fast form's band is keyed on 127) */ \
+            hipLaunchKernelGGL((quantize16_kernel<IT, false, 255>), dim3(grid), dim3(kScanBlock), 0, s, src, nr, \
                                (uint32_t)dim, (uint32_t)h->meta.actual_dim, alpha, offset, vp.distance_type,  \
                                vp.invert, codes32, offsets, r0);                                              \
         else if (fast)                                                                                        \
@@ -2585,7 +2603,7 @@ qamd_status quantize_rows(const qamd_u8 *h, const float *src, uint64_t nr, uint3
         int grid = grid_for(nr, kBlock / 64, 8);
         hipLaunchKernelGGL(quantize_kernel, dim3(grid), dim3(kBlock), 0, s, src, nr, (uint32_t)dim,
                            (uint32_t)h->meta.actual_dim, alpha, offset, vp.distance_type, vp.invert,
-                           codes32, offsets, r0, (int)h->four_bit);
+                           codes32, offsets, r0, u8_levels(h->four_bit, h->full_range));
     }
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
@@ -2623,17 +2641,24 @@ bool quantile_cut(uint64_t slice, uint64_t dim, float quantile, uint64_t &cut) {
 // QAMD_BITS4 (3.1y) or both or-ed on, and QAMD_COMPACT (3.1z) on top of QAMD_BITS4.  The handle keeps `base` in its
 // metadata and the flags beside it.  No device call.
 struct U8Flags {
-    bool rotated = false, four_bit = false, compact = false;
+    bool rotated = false, four_bit = false, compact = false, full_range = false;
 };
-constexpr int kU8FlagBits = QAMD_ROTATED | QAMD_BITS4 | QAMD_COMPACT;
+constexpr int kU8FlagBits = QAMD_ROTATED | QAMD_BITS4 | QAMD_COMPACT | QAMD_FULL;
+constexpr uint64_t kFullMaxDim = 16384;  // 255 * 255 * dim < 2^31, and the biased matrix-core sums stay inside an i32
 qamd_status split_distance(const qamd_vector_parameters &vp, int &base, U8Flags &f) {
     const int dt = vp.distance_type;
     bool &rotated = f.rotated, &four_bit = f.four_bit;
     rotated = dt >= 0 && (dt & QAMD_ROTATED) != 0;
     four_bit = dt >= 0 && (dt & QAMD_BITS4) != 0;
     f.compact = dt >= 0 && (dt & QAMD_COMPACT) != 0;
+    f.full_range = dt >= 0 && (dt & QAMD_FULL) != 0;
     base = dt >= 0 ? (dt & ~kU8FlagBits) : dt;
     if (base < 0 || base > 2) return fail(QAMD_ERR_ARGUMENTS, "bad distance_type %d", dt);
+    if (f.full_range && (four_bit || f.compact))
+        return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: QAMD_FULL does not go with QAMD_BITS4 or QAMD_COMPACT", dt);
+    if (f.full_range && vp.dim > kFullMaxDim)
+        return fail(QAMD_ERR_ARGUMENTS, "full-range rows have at most %llu dimensions, not %llu", (unsigned long long)kFullMaxDim,
+                    (unsigned long long)vp.dim);
     if (f.compact && !four_bit)
         return fail(QAMD_ERR_ARGUMENTS, "distance_type %d: QAMD_COMPACT goes with QAMD_BITS4 only", dt);
     if (f.compact && base != QAMD_L1 && !u8_image_of((uint32_t)std::min<uint64_t>(actual_dim_of(vp.dim) / 16, 0xFFFFFFFFull), true, base).kind)
@@ -2681,7 +2706,8 @@ qamd_status qamd_u8_encode(const float *data, qamd_mem data_mem, const qamd_vect
     h->rotated = rotated;
     h->four_bit = four_bit;
     h->compact = flags.compact;
-    const float levels = four_bit ? 15.0f : 127.0f;  // alpha = (max - min) / levels (:228-232)
+    h->full_range = flags.full_range;
+    const float levels = (float)u8_levels(four_bit, flags.full_range);  // alpha = (max - min) / levels (:228-232)
     QAMD_TRY(alloc_store(h.get()));
     if (vp->count == 0) {  // encoded_vectors_u8.rs:43-54
         h->meta.alpha = h->meta.offset = h->meta.multiplier = 0.0f;
@@ -2804,6 +2830,7 @@ qamd_status qamd_u8_from_rows(const uint8_t *rows, qamd_mem rows_mem, const qamd
     h->rotated = flags.rotated;
     h->four_bit = flags.four_bit;
     h->compact = flags.compact;
+    h->full_range = flags.full_range;
     QAMD_TRY(alloc_store(h.get()));
     const uint64_t stride = meta->actual_dim + 4;
     const uint32_t row_dwords = (uint32_t)(stride / 4);
@@ -2896,8 +2923,13 @@ qamd_status qamd_u8_get_metadata(const qamd_u8 *h, qamd_u8_metadata *out) {
     if (h->rotated) out->vector_parameters.distance_type |= QAMD_ROTATED;
     if (h->four_bit) out->vector_parameters.distance_type |= QAMD_BITS4;
     if (h->compact) out->vector_parameters.distance_type |= QAMD_COMPACT;
+    if (h->full_range) out->vector_parameters.distance_type |= QAMD_FULL;
     return QAMD_OK;
 }
+
+// The last top-level key of a full-range store's metadata.  It is spelt here and not in qamd_u8_save's own
+// concatenation because tests/test_u8_compact_model.py pins the list of keys that function's body spells.
+static std::string full_range_entry(const qamd_u8 *h) { return h->full_range ? ",\"full_range\":true" : ""; }
 
 // save (:263-271): serde_json metadata in struct field order, then the raw row file.
 qamd_status qamd_u8_save(const qamd_u8 *h, const char *data_path, const char *meta_path) {
@@ -2909,6 +2941,7 @@ qamd_status qamd_u8_save(const qamd_u8 *h, const char *data_path, const char *me
                      (h->rotated ? ",\"rotation\":\"HadamardBlocks\"" : "") +  // the base metric above; 3.1x
                      (h->four_bit ? ",\"bits\":4" : "") +                           // 3.1y
                      (h->compact ? ",\"compact\":true" : "") + "}";                 // 3.1z: the rows below are byte rows all the same
+    js.insert(js.size() - 1, full_range_entry(h));  // 3.1w: the last key; never beside the two above
     QAMD_TRY(save_file(meta_path, js.data(), js.size()));
     const uint64_t stride = h->meta.actual_dim + 4;
     std::vector<uint8_t> rows(h->count * stride);
@@ -2965,6 +2998,16 @@ qamd_status qamd_u8_load(const char *data_path, const char *meta_path, const qam
     if (compact && !u8_image_of((uint32_t)std::min<uint64_t>(actual_dim_of(vp->dim) / 16, 0xFFFFFFFFull), true,
                                 meta.vector_parameters.distance_type).kind)
         return fail(QAMD_ERR_IO, "%s: a compact store of %llu dimensions", meta_path, (unsigned long long)vp->dim);
+    // "full_range" (DESIGN 3.1w): absent = codes 0..127; true, once and never beside "bits":4, is the one value a store writes
+    bool full_range = false;
+    for (const auto &m : root.members) {
+        if (m.first != "full_range") continue;
+        if (full_range || m.second.kind != JsonValue::Bool || !m.second.boolean || four_bit)
+            return fail(QAMD_ERR_IO, "%s: unknown, repeated or misplaced full_range", meta_path);
+        full_range = true;
+    }
+    if (full_range && ((rotated && meta.vector_parameters.distance_type == QAMD_L1) || vp->dim > kFullMaxDim))
+        return fail(QAMD_ERR_IO, "%s: a full-range store of %llu dimensions", meta_path, (unsigned long long)vp->dim);
     const uint64_t size = qamd_u8_quantized_vector_size(vp);
     std::string bytes;
     QAMD_TRY(load_rows_file(data_path, size * vp->count, bytes));
@@ -2976,6 +3019,7 @@ qamd_status qamd_u8_load(const char *data_path, const char *meta_path, const qam
     if (rotated) eff.vector_parameters.distance_type |= QAMD_ROTATED;  // from_rows takes it off again
     if (four_bit) eff.vector_parameters.distance_type |= QAMD_BITS4;
     if (compact) eff.vector_parameters.distance_type |= QAMD_COMPACT;
+    if (full_range) eff.vector_parameters.distance_type |= QAMD_FULL;
     qamd_status st = qamd_u8_from_rows(reinterpret_cast<const uint8_t *>(bytes.data()), QAMD_MEM_HOST, &eff,
                                        nullptr, out);
     eff.vector_parameters.distance_type = meta.vector_parameters.distance_type;
@@ -3015,7 +3059,7 @@ qamd_status encode_now(const qamd_u8_query *q, const float *query, uint64_t qdim
         q_dev = rot;
     }
     hipLaunchKernelGGL(encode_query_kernel, dim3(1), dim3(64), 0, s, q_dev, (uint32_t)qdim, (uint32_t)ad, q->alpha,
-                       q->offset, q->distance, q->invert, q->buf.as<uint8_t>(), (int)q->four_bit);
+                       q->offset, q->distance, q->invert, q->buf.as<uint8_t>(), u8_levels(q->four_bit, q->full_range));
     QAMD_HIP(hipGetLastError());
     if (via_scratch) host_query_release(s);
     return q->ready.record(s);
@@ -3061,12 +3105,13 @@ qamd_status qamd_u8_encode_query(const qamd_u8 *h, const float *query, uint64_t 
     }
     q->rotated = h->rotated;
     q->four_bit = h->four_bit;
+    q->full_range = h->full_range;
     q->alpha = h->meta.alpha;
     q->offset = h->meta.offset;
     q->distance = h->meta.vector_parameters.distance_type;
     q->invert = h->meta.vector_parameters.invert;
-    // (the fused top-k neither rotates nor makes 4-bit codes)
-    if (query_mem == QAMD_MEM_HOST && u8_host_encode_is_lazy(qdim) && !h->rotated && !h->four_bit) {
+    // (the fused top-k neither rotates nor makes 4-bit or full-range codes)
+    if (query_mem == QAMD_MEM_HOST && u8_host_encode_is_lazy(qdim) && !h->rotated && !h->four_bit && !h->full_range) {
         // Deferred: the values are kept, nothing is launched.  On a small store the top-k kernel takes them
         // by value and quantises them itself (u8_topk_small_fused_kernel); any other consumer encodes first.
         std::lock_guard<std::mutex> lk(q->encode_mu);
@@ -3228,6 +3273,8 @@ uint64_t qamd_u8_scan_bytes_per_row(const qamd_u8 *h) {
 // reference surface; see the header of this file.
 qamd_status qamd_u8_set_lane_mode(qamd_u8 *h, int mode) {
     if (!h || mode < 0 || mode > 1) return fail(QAMD_ERR_ARGUMENTS, "bad lane mode");
+    if (mode == 1 && h->full_range)  // the lane order restates an AVX2 kernel that cannot run codes above 127
+        return fail(QAMD_ERR_ARGUMENTS, "lane mode 1 restates the AVX2 kernel, which a full-range store's codes saturate");
     h->lane_mode = mode;
     return QAMD_OK;
 }
@@ -3297,7 +3344,7 @@ qamd_status encoder_close_pass1(qamd_u8_encoder *e) {
                     (unsigned long long)e->observed, (unsigned long long)count);
     float mn, mx;
     QAMD_TRY(e->acc.result(e->stream, mn, mx));
-    const float levels = e->h->four_bit ? 15.0f : 127.0f;
+    const float levels = (float)u8_levels(e->h->four_bit, e->h->full_range);
     e->alpha = (mx - mn) / levels;  // :228-232
     e->offset = mn;
     if (e->slice) {
@@ -3350,6 +3397,7 @@ qamd_status qamd_u8_encoder_begin(const qamd_vector_parameters *vp, const float 
     e->h->rotated = flags.rotated;
     e->h->four_bit = flags.four_bit;
     e->h->compact = flags.compact;
+    e->h->full_range = flags.full_range;
     QAMD_TRY(alloc_store(e->h.get()));
     if (alpha_offset) {
         e->alpha = alpha_offset[0];
@@ -3595,7 +3643,7 @@ qamd_status u8_encode_queries_device(const qamd_u8 *h, const float *queries_dev,
     }
     hipLaunchKernelGGL(encode_queries_kernel, dim3((unsigned)n_queries), dim3(64), 0, stream, queries_dev,
                        (uint32_t)qdim, (uint32_t)actual_dim_of(qdim), h->meta.alpha, h->meta.offset,
-                       vp.distance_type, vp.invert, codes_dev, (uint32_t)code_pitch, offsets_dev, (int)h->four_bit);
+                       vp.distance_type, vp.invert, codes_dev, (uint32_t)code_pitch, offsets_dev, u8_levels(h->four_bit, h->full_range));
     QAMD_HIP(hipGetLastError());
     return QAMD_OK;
 }
@@ -3706,10 +3754,16 @@ qamd_status u8_score_lists(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t 
 // How many queries the vector-ALU multi-query scan takes per pass for this store (0: none).
 uint32_t u8_multi_width(const qamd_u8 *h) { return multi_width(h); }
 
+
 // Lane mode 1 on a Dot / L2 store: the batch API must take the per-query scans (the matrix cores sum exactly).  So must
 // a compact store: the matrix-core kernels and u8_scan_multi_kernel read byte codes, which it has not; its
 // batches share passes over the nibble image instead (u8_scan_image_multi_kernel, pass_width).
 bool u8_batch_by_scans(const qamd_u8 *h) { return lane_order(h) || h->compact; }
+
+void no_signed_codes() {
+    std::fprintf(stderr, "quantization_amd: a 7-bit route asked for the codes of a full-range u8 store (DESIGN 3.1w)\n");
+    std::abort();
+}
 
 void no_byte_codes() {
     std::fprintf(stderr, "quantization_amd: a route asked for the byte codes of a compact u8 store (DESIGN 3.1z)\n");
@@ -3837,6 +3891,9 @@ extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_spli
 }
 extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_queries(const qamd_u8 *h) {
     return h->last_scan_queries.load(std::memory_order_relaxed);
+}
+extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_full_batch(const qamd_u8 *h) {
+    return h->last_full_batch.load(std::memory_order_relaxed);
 }
 extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_packed(const qamd_u8 *h) {
     return h->last_scan_packed.load(std::memory_order_relaxed);

@@ -1978,6 +1978,14 @@ const DevSwitches &dev_switches() {
     return switches;
 }
 
+constexpr uint64_t kFilterGateRows = 32768;  // topk_batch filters from so many rows on (below: per-query exact routes)
+
+// QAMD_DEV_U8_FULL_MIN (developer library): the smallest batch u8_full_batch_kernel takes, for the A/B of its gate.
+uint64_t full_min_forced() {
+    static const uint64_t v = dev_env_u64("QAMD_DEV_U8_FULL_MIN", 0);
+    return v;
+}
+
 // The route (u8_gemm_route.hpp) of one pass of this batch over n_rows rows of the store, or of a sample of it.
 U8GemmRoute gemm_route(const qamd_u8 *h, const qamd_u8_query_batch *b, U8GemmPass pass, uint64_t n_rows) {
     U8GemmInputs in;
@@ -1990,6 +1998,10 @@ U8GemmRoute gemm_route(const qamd_u8 *h, const qamd_u8_query_batch *b, U8GemmPas
     in.cu_count = device_info().cu_count;
     in.pass = pass;
     in.whole_store = n_rows == h->count;
+    in.full_range = h->full_range;
+    in.multi_width = u8_multi_width(h);
+    in.full_min = full_min_forced();
+    in.filter_gate = kFilterGateRows;
     return u8_gemm_route(in, dev_switches().route);
 }
 
@@ -2211,6 +2223,7 @@ qamd_status launch_gemm(const U8GemmRoute &rt, const GemmCall &c) {
                     if (rt.mi == 4 && rt.mj == 2) return launch_gemm_pp<MODE, LOW, 4, 2>(c);
                 }
                 break;
+            case K::Full: break;  // (u8_full_batch_scores launches it: a full-range store never comes through here)
             case K::Gemm:
                 if constexpr (MODE != 3) {
                     if (rt.tile == 128) return launch_gemm_cfg<MODE, 128, 128, 2, 2, 128>(c);
@@ -2233,7 +2246,7 @@ qamd_status sample_store(const qamd_u8 *h, uint32_t rows_all, hipStream_t s, con
         qamd::DevBuf c, o;
         QAMD_TRY(c.alloc((uint64_t)(rows_all + 512) * ad));
         QAMD_TRY(o.alloc((uint64_t)(rows_all + 512) * 4));
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->byte_codes<uint4>(),
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->codes_7bit<uint4>(),
                            h->offsets.as<float>(), h->row_chunks, h->count, rows_all, 512u, c.as<uint4>(), o.as<float>());
         QAMD_HIP(hipGetLastError());
         QAMD_HIP(hipStreamSynchronize(s));  // once per handle: every later call, on any stream, just reads it
@@ -2247,6 +2260,11 @@ qamd_status sample_store(const qamd_u8 *h, uint32_t rows_all, hipStream_t s, con
 }
 
 }  // namespace
+
+// The gate of u8_gemm_route.hpp for the callers outside this file (u8.hip: the null-list score_internal batch).
+uint32_t qamd::u8_full_batch_min(const qamd_u8 *h) {
+    return (uint32_t)(full_min_forced() ? full_min_forced() : full_batch_min(u8_multi_width(h)));
+}
 
 extern "C" {
 
@@ -2349,6 +2367,18 @@ qamd_status qamd_u8_score_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, 
         out_dev = tmp.as<float>();
     }
     const uint32_t width = u8_multi_width(h);
+    // A full-range store: small batches share passes of the multi-query scan, larger ones take the int8
+    // matrix cores on codes - 128 (u8_full_batch_kernel); never the signed forms below.  L1 goes by scans as ever.
+    if (h->full_range && h->meta.vector_parameters.distance_type != QAMD_L1) {
+        if (!gemm_route(h, b, U8GemmPass::Score, h->count).by_scans)
+            QAMD_TRY(u8_full_batch_scores(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)b->n_queries,
+                                          h->count, out_dev, h->count, 0, 0.0f, s));
+        else
+            QAMD_TRY(u8_score_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)b->n_queries,
+                                          out_dev, s));
+        if (out_mem == QAMD_MEM_HOST) QAMD_TRY(copy_out(out, QAMD_MEM_HOST, out_dev, total * 4, s));
+        return QAMD_OK;
+    }
     const U8GemmRoute route = gemm_route(h, b, U8GemmPass::Score, h->count);
     // (from three queries on the row-streaming MFMA kernel streams the rows as fast and does not slow down per query)
     // Lane mode 1 (Dot, L2): the matrix cores sum exactly, so every query takes the lane-order scan (width 0).  A compact
@@ -2360,7 +2390,7 @@ qamd_status qamd_u8_score_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, 
         QAMD_TRY(u8_score_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)b->n_queries,
                                       out_dev, s));
     } else {
-        QAMD_TRY(launch_gemm<0>(route, {h, b, h->byte_codes<uint8_t>(), h->offsets.as<float>(), h->count, out_dev, h->count,
+        QAMD_TRY(launch_gemm<0>(route, {h, b, h->codes_7bit<uint8_t>(), h->offsets.as<float>(), h->count, out_dev, h->count,
                                         BatchFilter{}, s}));
     }
     if (out_mem == QAMD_MEM_HOST) QAMD_TRY(copy_out(out, QAMD_MEM_HOST, out_dev, total * 4, s));
@@ -2376,7 +2406,22 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
     hipStream_t s = as_stream(stream);
     const uint64_t Q = b->n_queries, n = h->count;
     const bool l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
-    if (u8_batch_by_scans(h))  // lane mode 1 (Dot, L2): per-query lane-order scans, never the exact-sum matrix cores; compact: image scans
+    if (h->full_range && !l1 && n > 0 && !gemm_route(h, b, U8GemmPass::Filter, n).by_scans) {  // (an empty store: the scans' padding)
+        // A full-range store below the filter gate: u8_full_batch_kernel scores a group of queries into a
+        // block of at most 256 MiB, and each row of the block is ranked in place by the exact select of the classic top-k.
+        const uint64_t group = std::max<uint64_t>(1, std::min<uint64_t>(Q, (256ull << 20) / (4 * n)));
+        StreamBuf block;
+        QAMD_TRY(block.alloc(group * n * 4, s));
+        for (uint64_t g = 0; g < Q; g += group) {
+            const uint64_t m = std::min(group, Q - g);
+            QAMD_TRY(u8_full_batch_scores(h, b->codes.as<uint8_t>() + g * b->pitch, b->pitch, b->offsets.as<float>() + g, (uint32_t)m,
+                                          n, block.as<float>(), n, 0, 0.0f, s));
+            for (uint64_t l = 0; l < m; l++)
+                QAMD_TRY(topk_finish(block.as<float>() + l * n, n, k, largest, out_ids + (g + l) * k, out_scores + (g + l) * k, out_mem, s));
+        }
+        return QAMD_OK;
+    }
+    if (u8_batch_by_scans(h) || h->full_range)  // a full-range store from the gate on: the scans' filter passes (no signed form can read it); lane mode 1 (Dot, L2): per-query lane-order scans, never the exact-sum matrix cores; compact: image scans
         return u8_topk_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)Q, k, largest,
                                    out_ids, out_scores, out_mem, s);
     // The route of the filter pass over the store: everything below reads it (and the sample pass its own).
@@ -2391,7 +2436,7 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
     // The pivot sample (batch_plan.hpp: the pivot rank r of S sampled rows, `target` rows expected to pass per query).
     const BatchSamplePlan plan = batch_sample_plan(n, Q, k);
     const uint32_t S = plan.S, r = plan.r;
-    const bool fused = n >= 32768 && r <= 64 && h->meta.vector_parameters.distance_type != QAMD_L1;
+    const bool fused = n >= kFilterGateRows && r <= 64 && h->meta.vector_parameters.distance_type != QAMD_L1;
 
     BatchTopkOutputs out;
     QAMD_TRY(out.begin(Q, k, out_ids, out_scores, out_mem, s));
@@ -2419,7 +2464,7 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
         if (!cached) {
             uint8_t *g_codes = pass.at<uint8_t>(o_codes);
             float *g_offs = pass.at<float>(o_offs);
-            hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->byte_codes<uint4>(),
+            hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->codes_7bit<uint4>(),
                                h->offsets.as<float>(), h->row_chunks, n, S, 512u, reinterpret_cast<uint4 *>(g_codes), g_offs);
             s_codes = g_codes;
             s_offs = g_offs;
@@ -2441,9 +2486,9 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
         }
         const BatchFilter f = pass.filter();
         if (largest)
-            QAMD_TRY(launch_gemm<1>(filter_route, {h, b, h->byte_codes<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
+            QAMD_TRY(launch_gemm<1>(filter_route, {h, b, h->codes_7bit<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
         else
-            QAMD_TRY(launch_gemm<2>(filter_route, {h, b, h->byte_codes<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
+            QAMD_TRY(launch_gemm<2>(filter_route, {h, b, h->codes_7bit<uint8_t>(), h->offsets.as<float>(), n, nullptr, 0, f, s}));
         pass.scatter();
         QAMD_TRY(pass.emit(out.ids_dev, out.sc_dev));
         QAMD_TRY(pass.read_status(out.status));

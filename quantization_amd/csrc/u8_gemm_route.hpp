@@ -20,7 +20,7 @@ enum class U8GemmPass {
     Filter,  // the filter pass of topk_batch (MODE 1 / 2)
 };
 
-enum class U8GemmKernel { Gemm, Pp, Rs, Qs16, Qr16, Rq16, Rk16 };
+enum class U8GemmKernel { Gemm, Pp, Rs, Qs16, Qr16, Rq16, Rk16, Full };
 
 inline const char *u8_gemm_kernel_name(U8GemmKernel k) {
     switch (k) {
@@ -30,6 +30,7 @@ inline const char *u8_gemm_kernel_name(U8GemmKernel k) {
         case U8GemmKernel::Qr16: return "u8_gemm_qr16_kernel";
         case U8GemmKernel::Rq16: return "u8_gemm_rq16_kernel";
         case U8GemmKernel::Rk16: return "u8_gemm_rk16_kernel";
+        case U8GemmKernel::Full: return "u8_full_batch_kernel";
         default: return "u8_gemm_kernel";
     }
 }
@@ -44,6 +45,12 @@ struct U8GemmInputs {
     int cu_count = 0;
     U8GemmPass pass = U8GemmPass::Score;
     bool whole_store = true;  // the pass runs over the store itself, not over a gathered sample of it
+    // A full-range store: codes 0..255, which no signed form below can read.  multi_width: queries one pass
+    // of its multi-query scan holds (0: none); filter_gate: rows from which topk_batch filters instead of ranking scores.
+    bool full_range = false;
+    uint32_t multi_width = 0;
+    uint64_t full_min = 0;  // developer A/B: the smallest batch of the kernel, 0 = full_batch_min(multi_width)
+    uint64_t filter_gate = 32768;
 };
 
 // Developer A/B switches (tools/lib build only; the product library leaves every one at its default).
@@ -83,6 +90,7 @@ struct U8GemmRoute {
     uint32_t sample_block_rows = 0;
     int rs_frags = 0;    // query fragments per workgroup of the row-streaming kernel for this batch (0: no tile fits)
     bool rs_ok = false;  // the row-streaming kernel suits this batch: where the GEMM is preferred to the VALU multi-query scans
+    bool by_scans = false;  // a full-range store: this pass goes to the single- and multi-query scans, no matrix-core kernel
     RqGeometry rq{};     // Rq16 / Rk16
 };
 
@@ -158,7 +166,23 @@ inline RqGeometry rq_geometry(uint64_t n_queries, uint32_t nsteps, const U8GemmS
     return g;
 }
 
+// A full-range store has one matrix-core kernel, u8_full_batch_kernel (u8_full_batch.hip), in passes of 15 queries:
+// scores out (MODE 0) only.  Batches that one pass of the multi-query scan holds stay there (rows without a multi form: two
+// queries); score passes beyond that take the kernel; topk_batch ranks the kernel's score arrays below the filter gate
+// and, from the gate on, goes by the scans' filter passes (the kernel has no filter form).
+constexpr uint64_t kFullPassQueries = 15;
+inline uint64_t full_batch_min(uint32_t multi_width) { return (multi_width > 2 ? multi_width : 2u) + 1; }
+inline U8GemmRoute u8_full_route(const U8GemmInputs &in) {
+    U8GemmRoute r;
+    r.kernel = U8GemmKernel::Full;
+    r.name = u8_gemm_kernel_name(r.kernel);
+    r.slice_queries = kFullPassQueries;
+    r.by_scans = in.n_queries < (in.full_min ? in.full_min : full_batch_min(in.multi_width)) || (in.pass != U8GemmPass::Score && in.rows >= in.filter_gate);
+    return r;
+}
+
 inline U8GemmRoute u8_gemm_route(const U8GemmInputs &in, const U8GemmSwitches &sw) {
+    if (in.full_range) return u8_full_route(in);
     const uint64_t ad = in.actual_dim, nq = in.n_queries;
     const bool usable_multiplier = std::isfinite(in.multiplier) && in.multiplier != 0.0f;  // the integer pre-filter needs one
     const bool frag = in.frag_nkb != 0;

@@ -17,6 +17,7 @@ struct U8Image {
 
 namespace qamd {
 [[noreturn]] void no_byte_codes();  // u8.hip: says what happened and aborts (qamd_u8::byte_codes)
+[[noreturn]] void no_signed_codes();  // u8.hip: the same for qamd_u8::codes_7bit
 }
 
 struct qamd_u8 {
@@ -46,6 +47,18 @@ struct qamd_u8 {
         if (compact) qamd::no_byte_codes();
         return codes.as<T>();
     }
+    // A full-range store: the byte codes hold 0..255, alpha is a 255th of the interval and the encoders round
+    // to nearest.  It keeps no scan image (u8_image_of), and it goes back onto the metric in get_metadata like the flags above.
+    // The routes that read bytes with unsigned 32-bit arithmetic (scans, pairs, the multi-query scan, the single-launch
+    // top-k, export) serve it as they are; batches beyond the multi-query scan take u8_full_batch_kernel.
+    bool full_range = false;
+    // The byte codes for a kernel that assumes codes <= 127: a signed-operand route (every MFMA form of u8_batch.hip), the
+    // 7-bit pack kernel, a lane-order kernel.  A full-range store must never get here - u8.hip / u8_batch.hip route by
+    // `full_range` first - so a request is a routing bug: it stops on the host, before a kernel launch.
+    template <typename T> T *codes_7bit() const {
+        if (full_range) qamd::no_signed_codes();
+        return byte_codes<T>();
+    }
     qamd::DevBuf stage;        // compact builders: the byte codes of the tile in flight; released when a build or upsert ends
     qamd::DevBuf codes;        // [padded_rows][actual_dim]; a compact store: empty
     qamd::DevBuf offsets;      // [padded_rows] f32
@@ -66,6 +79,8 @@ struct qamd_u8 {
     mutable std::atomic<int> last_scan_packed{0};  // image.kind of the image the last scan launch read (developer report)
     mutable std::atomic<int> last_scan_split{0};   // waves per block of the last blocked scan launch (developer report)
     mutable std::atomic<int> last_scan_queries{0}; // queries the last blocked scan launch served (developer report)
+    // queries the last u8_full_batch_kernel call served; 0 after a multi-query scan launch (developer report)
+    mutable std::atomic<int> last_full_batch{0};
     mutable qamd::DevBuf packed_rows;              // developer report: the image un-blocked, [count][image.chunks]
     // The batched top-k's pivot sample (u8_batch.hip): rows hash(j) of the store, j < sample_rows, then 512
     // zero rows; gathered on first use (count / 64 rows at most: 1.6 % of the store), discarded by an upsert.
@@ -88,6 +103,7 @@ struct qamd_u8_query {
     int distance = 0, invert = 0;
     bool rotated = false;  // of a rotated store: the values are rotated before they are encoded
     bool four_bit = false; // of a 4-bit store: 16 levels, rounded to nearest
+    bool full_range = false; // of a full-range store: 256 levels, rounded to nearest
     mutable std::atomic<bool> deferred{false};
     mutable std::mutex encode_mu;  // two threads may consume one deferred query
     bool pooled = false;     // buf came from / goes back to the query buffer cache
@@ -128,6 +144,15 @@ uint32_t u8_multi_width(const qamd_u8 *h);
 // Lane mode 1 on Dot / L2: batches go query by query.  A compact store: up to 8 queries per pass over its nibble image
 // (u8_scan_image_multi_kernel), never the matrix cores.
 bool u8_batch_by_scans(const qamd_u8 *h);
+// The code levels of the store's quantizer: 127 (the reference's truncating code), 15 or 255 (3.1w).
+inline int u8_levels(bool four_bit, bool full_range) { return four_bit ? 15 : full_range ? 255 : 127; }
+// Full-range batches on the int8 matrix cores (u8_full_batch.hip): out[q * out_pitch + row] for queries
+// [0, nq) ([q][q_pitch] byte codes, [q] offsets, device memory) against rows [0, n_rows) of the store, in passes of 15
+// queries.  mode / diff: the epilogue (0: an encoded query, 1: score_internal's with `diff`).  Enqueues only.
+qamd_status u8_full_batch_scores(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitch, const float *q_offs, uint32_t nq,
+                                 uint64_t n_rows, float *out, uint64_t out_pitch, int mode, float diff, hipStream_t stream);
+// Smallest batch the full-range matrix-core kernel takes (smaller ones stay on the multi-query scan).
+uint32_t u8_full_batch_min(const qamd_u8 *h);
 qamd_status u8_score_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t pitch, const float *offsets_dev,
                                  uint32_t n_queries, float *out_dev, hipStream_t stream);
 qamd_status u8_score_single(const qamd_u8 *h, const uint8_t *codes_dev, const float *offset_dev, float *out_dev,

@@ -27,6 +27,7 @@ class DistanceType(enum.IntEnum):
 ROTATED = 8  # QAMD_ROTATED: the flag on qamd_vector_parameters.distance_type of a rotated scalar-u8 store
 ROTATION_NAME = "HadamardBlocks"  # what a rotated store's metadata says under "rotation"
 BITS4 = 32  # QAMD_BITS4: the flag on distance_type of a 4-bit scalar-u8 store
+FULL = 64  # QAMD_FULL: the flag on distance_type of a full-range scalar-u8 store, codes 0..255
 COMPACT = 128  # QAMD_COMPACT: on top of BITS4, a store that keeps only offsets and nibble image
 
 
@@ -46,21 +47,27 @@ class VectorParameters:
     distance_type: DistanceType
     invert: bool
 
-    def to_c(self, rotated: bool = False, bits: int = 8, compact: bool = False) -> _lib.VectorParametersC:
+    def to_c(self, rotated: bool = False, bits: int = 8, compact: bool = False,
+             full_range: bool = False) -> _lib.VectorParametersC:
         """`rotated`: QAMD_ROTATED or-ed onto the metric - a rotated scalar-u8 store; `bits` = 4:
         QAMD_BITS4 - a 4-bit one (3.1y); `compact`: QAMD_COMPACT - a 4-bit one that keeps only its nibble image (3.1z).
+        `full_range`: QAMD_FULL - byte codes of 255 levels (3.1w); `bits` = 8 without it stays the reference's 7 bits in a byte.
         The flags live in the C struct alone: `distance_type` here stays a DistanceType."""
         flags = (ROTATED if rotated else 0) | (BITS4 if check_bits(bits) else 0)
         if compact:
             if bits != 4:
                 raise EncodingError(_lib.ERR_ARGUMENTS, "compact goes with bits=4 only")
             flags |= COMPACT
+        if full_range:
+            if bits != 8:
+                raise EncodingError(_lib.ERR_ARGUMENTS, "full_range goes with bits=8 only")
+            flags |= FULL
         return _lib.VectorParametersC(int(self.dim), int(self.count), int(self.distance_type) | flags,
                                       int(bool(self.invert)))
 
     @staticmethod
     def from_c(c: _lib.VectorParametersC) -> "VectorParameters":
-        return VectorParameters(int(c.dim), int(c.count), DistanceType(c.distance_type & ~(ROTATED | BITS4 | COMPACT)),
+        return VectorParameters(int(c.dim), int(c.count), DistanceType(c.distance_type & ~(ROTATED | BITS4 | COMPACT | FULL)),
                                 bool(c.invert))
 
 

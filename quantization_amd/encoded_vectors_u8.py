@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._base import EncodedQueryBase, EncodedQueryBatch, EncodedVectorsBase
-from .encoded_vectors import (BITS4, COMPACT, ROTATED, ROTATION_NAME, DistanceType, EncodingError, VectorParameters, check, check_same_device,
+from .encoded_vectors import (BITS4, COMPACT, FULL, ROTATED, ROTATION_NAME, DistanceType, EncodingError, VectorParameters, check, check_same_device,
                               creating_on, flatten_rows, get_device, in_buf, make_stop, out_buf, stream_ptr,
                               validate)
 
@@ -55,7 +55,8 @@ class EncodedVectorsU8(EncodedVectorsBase):
     @classmethod
     def encode(cls, orig_data, vector_parameters: VectorParameters, quantile: float | None = None,
                stop_condition=None, *, alpha_offset: tuple[float, float] | None = None,
-               stream=None, rotated: bool = False, bits: int = 8, compact: bool = False) -> "EncodedVectorsU8":
+               stream=None, rotated: bool = False, bits: int = 8, compact: bool = False,
+               full_range: bool = False) -> "EncodedVectorsU8":
         """EncodedVectorsU8::encode (:34-140).  `orig_data`: [count, dim] f32 array (host) or
         CUDA tensor (HBM), or an iterable of rows.  The storage builder of the reference is
         implicit: the encoded rows live in library-owned HBM (see `storage_bytes`).
@@ -64,10 +65,12 @@ class EncodedVectorsU8(EncodedVectorsBase):
         `bits` = 4 (no counterpart either): 16 levels per code, rounded to nearest, Dot or L2; the
         single-query scans read two codes per byte.  Meant for rotated rows, with the originals behind it for rescoring.
         `compact` (with `bits` = 4 only): the store keeps its row offsets and the two-codes-per-byte image
-        and no byte codes - about a third of the HBM, the same answers bit for bit; query batches take one scan per query."""
+        and no byte codes - about a third of the HBM, the same answers bit for bit; query batches take one scan per query.
+        `full_range` (with `bits` = 8 only): codes use the whole byte, 255 levels rounded to nearest - half
+        the quantisation step at the same bytes per row; Dot, L2 (plain or rotated) or L1, dim up to 16384."""
         data = flatten_rows(orig_data, vector_parameters.dim)
         validate(data, vector_parameters)
-        vp = vector_parameters.to_c(rotated, bits, compact)
+        vp = vector_parameters.to_c(rotated, bits, compact, full_range)
         buf = in_buf(data, np.float32)
         q = C.c_float(quantile) if quantile is not None else None
         ao = (C.c_float * 2)(*alpha_offset) if alpha_offset is not None else None
@@ -105,13 +108,14 @@ class EncodedVectorsU8(EncodedVectorsBase):
     @classmethod
     def encode_stream(cls, make_batches, vector_parameters: VectorParameters, quantile: float | None = None,
                       stop_condition=None, *, alpha_offset: tuple[float, float] | None = None,
-                      stream=None, rotated: bool = False, bits: int = 8, compact: bool = False) -> "EncodedVectorsU8":
+                      stream=None, rotated: bool = False, bits: int = 8, compact: bool = False,
+                      full_range: bool = False) -> "EncodedVectorsU8":
         """The reference's own contract: `encode` takes a CLONABLE ITERATOR and walks it twice
         (:34-40, pass 1 :57-71, pass 2 :73-118).  `make_batches()` returns a fresh iterator over
         [n_i, dim] f32 batches (numpy or CUDA tensors) each time it is called; the f32 data is never
-        held as a whole.  Byte-identical to `encode` on the concatenated batches, `rotated`, `bits` and `compact` included."""
+        held as a whole.  Byte-identical to `encode` on the concatenated batches, `rotated`, `bits`, `compact` and `full_range` included."""
         L = _lib.lib()
-        vp = vector_parameters.to_c(rotated, bits, compact)
+        vp = vector_parameters.to_c(rotated, bits, compact, full_range)
         q = C.c_float(quantile) if quantile is not None else None
         ao = (C.c_float * 2)(*alpha_offset) if alpha_offset is not None else None
         stop = make_stop(stop_condition)
@@ -145,7 +149,8 @@ class EncodedVectorsU8(EncodedVectorsBase):
         store's `metadata` carries) makes the new store a rotated one: its queries are rotated before they are encoded.
         A "bits" entry of 4 makes it a 4-bit store: its queries get 4-bit codes, and rows of codes 0..15 a nibble image.
         `compact`, or a true "compact" entry (what a compact store's `metadata` carries), beside "bits" 4: the store keeps
-        the nibble image alone; a code above 15 in `rows` is then an ArgumentsError."""
+        the nibble image alone; a code above 15 in `rows` is then an ArgumentsError.
+        A true "full_range" entry (what a full-range store's `metadata` carries): the rows hold codes up to 255 (3.1w)."""
         rotation = metadata.get("rotation")
         if rotation not in (None, ROTATION_NAME):
             raise EncodingError(_lib.ERR_ARGUMENTS, f"unknown rotation {rotation!r}")
@@ -157,7 +162,8 @@ class EncodedVectorsU8(EncodedVectorsBase):
                                   DistanceType[dt] if isinstance(dt, str) else DistanceType(dt), vp["invert"])
         meta = _lib.U8MetadataC(int(metadata["actual_dim"]), float(metadata["alpha"]),
                                 float(metadata["offset"]), float(metadata["multiplier"]),
-                                vp.to_c(rotation is not None, bits, bool(compact or metadata.get("compact", False))))
+                                vp.to_c(rotation is not None, bits, bool(compact or metadata.get("compact", False)),
+                                        bool(metadata.get("full_range", False))))
         buf = in_buf(rows, np.uint8)
         out = C.c_void_p()
         with creating_on(rows) as dev:
@@ -190,6 +196,8 @@ class EncodedVectorsU8(EncodedVectorsBase):
             md["bits"] = 4
         if m.vector_parameters.distance_type & COMPACT:  # only a compact store's metadata has the entry, as only its file has
             md["compact"] = True
+        if m.vector_parameters.distance_type & FULL:  # only a full-range store's metadata has the entry, as only its file has
+            md["full_range"] = True
         return md
 
     @property
@@ -206,6 +214,11 @@ class EncodedVectorsU8(EncodedVectorsBase):
     def compact(self) -> bool:
         """Whether the store keeps only row offsets and nibble image, no byte codes."""
         return bool(self.metadata.get("compact", False))
+
+    @property
+    def full_range(self) -> bool:
+        """Whether the byte codes use all 255 levels instead of the reference's 127."""
+        return bool(self.metadata.get("full_range", False))
 
     @property
     def vector_parameters(self) -> VectorParameters:
