@@ -2117,6 +2117,8 @@ void launch_multi_shape(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitc
     const bool exact = h->row_chunks == (uint32_t)(G * ITERS);
     h->last_scan_packed.store(0, std::memory_order_relaxed);
     h->last_full_batch.store(0, std::memory_order_relaxed);
+    h->last_full_filter.store(0, std::memory_order_relaxed);
+    h->last_full_redone.store(0, std::memory_order_relaxed);
     h->last_scan_queries.store((int)nq_valid, std::memory_order_relaxed);
 #define QAMD_U8_MULTI(EX, FI, EPI)                                                                                 \
     hipLaunchKernelGGL((u8_scan_multi_kernel<G, ITERS, UNROLL, NQ, IS_L1, EX, FI, EPI>), dim3(grid), dim3(kScanBlock), 0, s, \
@@ -3894,6 +3896,14 @@ extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_quer
 }
 extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_full_batch(const qamd_u8 *h) {
     return h->last_full_batch.load(std::memory_order_relaxed);
+}
+// Queries of the store's last topk_batch call that went through the filter form of u8_full_batch_kernel (0: the scans
+// served it), and how many of those were then redone exactly.
+extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_full_filter(const qamd_u8 *h) {
+    return h->last_full_filter.load(std::memory_order_relaxed);
+}
+extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_full_redone(const qamd_u8 *h) {
+    return h->last_full_redone.load(std::memory_order_relaxed);
 }
 extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_packed(const qamd_u8 *h) {
     return h->last_scan_packed.load(std::memory_order_relaxed);

@@ -2246,7 +2246,8 @@ qamd_status sample_store(const qamd_u8 *h, uint32_t rows_all, hipStream_t s, con
         qamd::DevBuf c, o;
         QAMD_TRY(c.alloc((uint64_t)(rows_all + 512) * ad));
         QAMD_TRY(o.alloc((uint64_t)(rows_all + 512) * 4));
-        hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->codes_7bit<uint4>(),
+        // (byte_codes: the gather copies rows and reads no code; the sample of a full-range store goes to u8_full_batch_kernel)
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->byte_codes<uint4>(),
                            h->offsets.as<float>(), h->row_chunks, h->count, rows_all, 512u, c.as<uint4>(), o.as<float>());
         QAMD_HIP(hipGetLastError());
         QAMD_HIP(hipStreamSynchronize(s));  // once per handle: every later call, on any stream, just reads it
@@ -2406,7 +2407,58 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
     hipStream_t s = as_stream(stream);
     const uint64_t Q = b->n_queries, n = h->count;
     const bool l1 = h->meta.vector_parameters.distance_type == QAMD_L1;
-    if (h->full_range && !l1 && n > 0 && !gemm_route(h, b, U8GemmPass::Filter, n).by_scans) {  // (an empty store: the scans' padding)
+    h->last_full_filter.store(0, std::memory_order_relaxed);
+    h->last_full_redone.store(0, std::memory_order_relaxed);
+    const bool full_kernel = h->full_range && !l1 && n > 0 && !gemm_route(h, b, U8GemmPass::Filter, n).by_scans;  // (an empty store: the scans' padding)
+    if (full_kernel && n >= kFilterGateRows) {
+        // A full-range store from the filter gate on: the fused pass of the 7-bit stores below with
+        // u8_full_batch_kernel in both places - its score form over the pivot sample (the Q x S matrix), its filter form
+        // over the store, appending straight to the per-query lists (no wave lists, no scatter).  Large k (r > 64): the
+        // exact per-query route, as there.
+        const BatchSamplePlan plan = batch_sample_plan(n, Q, k);
+        const uint32_t S = plan.S, r = plan.r;
+        BatchTopkOutputs out;
+        QAMD_TRY(out.begin(Q, k, out_ids, out_scores, out_mem, s));
+        int filtered = 0, redone = 0;
+        if (r <= 64) {
+            const uint64_t ad = h->meta.actual_dim;
+            BatchTopkPass pass(n, Q, b->q_pad, k, largest, 0, 0, s);
+            const uint8_t *s_codes = nullptr;
+            const float *s_offs = nullptr;
+            const bool cached = S <= plan.rows_all && sample_store(h, plan.rows_all, s, &s_codes, &s_offs) == QAMD_OK;
+            const size_t o_codes = pass.reserve(cached ? 16 : (uint64_t)S * ad);  // (the kernel clamps its loads: no zero rows)
+            const size_t o_offs = pass.reserve(cached ? 16 : (uint64_t)S * 4);
+            const size_t o_images = pass.reserve(u8_full_images_bytes(h, (uint32_t)Q));
+            const size_t o_scores = pass.reserve(Q * (uint64_t)S * 4);
+            QAMD_TRY(pass.alloc());
+            if (!cached) {
+                hipLaunchKernelGGL(gather_rows_kernel, dim3(device_info().cu_count * 8), dim3(256), 0, s, h->byte_codes<uint4>(),
+                                   h->offsets.as<float>(), h->row_chunks, n, S, 0u, pass.at<uint4>(o_codes), pass.at<float>(o_offs));
+                s_codes = pass.at<uint8_t>(o_codes);
+                s_offs = pass.at<float>(o_offs);
+            }
+            U8FullImages images;
+            QAMD_TRY(u8_full_images_build(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)Q,
+                                          pass.at<uint8_t>(o_images), s, &images));
+            float *s_scores = pass.at<float>(o_scores);
+            QAMD_TRY(u8_full_batch_scores_of(h, images, s_codes, s_offs, S, s_scores, S, 0, 0.0f, s));
+            pass.pivots(s_scores, S, S, r);
+            QAMD_TRY(u8_full_batch_filter(h, images, pass.pivot_scores(), pass.counters(), pass.candidates(), largest, s));
+            QAMD_TRY(pass.emit(out.ids_dev, out.sc_dev));
+            QAMD_TRY(pass.read_status(out.status));
+            pass.debug_line("[qamd topk_batch]", r, "u8_full_batch_kernel", "", out.status);
+            filtered = (int)Q;
+            redone = (int)std::count_if(out.status.begin(), out.status.end(), [](uint32_t v) { return v != 0; });
+        }
+        QAMD_TRY(out.finish([&](uint64_t q, uint32_t *ids_dev, float *sc_dev) {
+            return u8_topk_single(h, b->codes.as<uint8_t>() + q * b->pitch, b->offsets.as<float>() + q, k, largest, ids_dev, sc_dev,
+                                  QAMD_MEM_DEVICE, s);
+        }));
+        h->last_full_filter.store(filtered, std::memory_order_relaxed);  // (behind the redone queries' own launches)
+        h->last_full_redone.store(redone, std::memory_order_relaxed);
+        return QAMD_OK;
+    }
+    if (full_kernel) {
         // A full-range store below the filter gate: u8_full_batch_kernel scores a group of queries into a
         // block of at most 256 MiB, and each row of the block is ranked in place by the exact select of the classic top-k.
         const uint64_t group = std::max<uint64_t>(1, std::min<uint64_t>(Q, (256ull << 20) / (4 * n)));
@@ -2421,7 +2473,7 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
         }
         return QAMD_OK;
     }
-    if (u8_batch_by_scans(h) || h->full_range)  // a full-range store from the gate on: the scans' filter passes (no signed form can read it); lane mode 1 (Dot, L2): per-query lane-order scans, never the exact-sum matrix cores; compact: image scans
+    if (u8_batch_by_scans(h) || h->full_range)  // a full-range store its kernel does not take (a small batch; from the gate on, rows past 8256 bytes or an unusable multiplier): the scans' filter passes (no signed form can read it); lane mode 1 (Dot, L2): per-query lane-order scans, never the exact-sum matrix cores; compact: image scans
         return u8_topk_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)Q, k, largest,
                                    out_ids, out_scores, out_mem, s);
     // The route of the filter pass over the store: everything below reads it (and the sample pass its own).

@@ -167,17 +167,24 @@ inline RqGeometry rq_geometry(uint64_t n_queries, uint32_t nsteps, const U8GemmS
 }
 
 // A full-range store has one matrix-core kernel, u8_full_batch_kernel (u8_full_batch.hip), in passes of 15 queries:
-// scores out (MODE 0) only.  Batches that one pass of the multi-query scan holds stay there (rows without a multi form: two
-// queries); score passes beyond that take the kernel; topk_batch ranks the kernel's score arrays below the filter gate
-// and, from the gate on, goes by the scans' filter passes (the kernel has no filter form).
+// scores out, or its filter form.  Batches that one pass of the multi-query scan holds stay there (rows without a multi
+// form: two queries); score passes beyond that take the kernel; topk_batch ranks the kernel's score arrays below the
+// filter gate and, from the gate on, samples with the score form and filters with the filter form: straight into the
+// per-query lists (no wave lists), the sample as the full Q x S matrix.  The filter form's integer pre-filter is the
+// shared one (batch_common.hpp), which needs a finite non-zero multiplier and exact sums below 2^29: 255 * 255 * ad for
+// ad <= kFullFilterMaxDim (65025 * 8256 = 536 846 400 < 536 870 912).  Longer rows and unusable multipliers stay on the
+// scans' filter passes from the gate on.
 constexpr uint64_t kFullPassQueries = 15;
+constexpr uint64_t kFullFilterMaxDim = 8256;
 inline uint64_t full_batch_min(uint32_t multi_width) { return (multi_width > 2 ? multi_width : 2u) + 1; }
 inline U8GemmRoute u8_full_route(const U8GemmInputs &in) {
     U8GemmRoute r;
     r.kernel = U8GemmKernel::Full;
     r.name = u8_gemm_kernel_name(r.kernel);
     r.slice_queries = kFullPassQueries;
-    r.by_scans = in.n_queries < (in.full_min ? in.full_min : full_batch_min(in.multi_width)) || (in.pass != U8GemmPass::Score && in.rows >= in.filter_gate);
+    const bool filter_form = in.actual_dim <= kFullFilterMaxDim && std::isfinite(in.multiplier) && in.multiplier != 0.0f;
+    r.by_scans = in.n_queries < (in.full_min ? in.full_min : full_batch_min(in.multi_width)) ||
+                 (in.pass != U8GemmPass::Score && in.rows >= in.filter_gate && !filter_form);
     return r;
 }
 

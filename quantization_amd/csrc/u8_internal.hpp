@@ -81,6 +81,9 @@ struct qamd_u8 {
     mutable std::atomic<int> last_scan_queries{0}; // queries the last blocked scan launch served (developer report)
     // queries the last u8_full_batch_kernel call served; 0 after a multi-query scan launch (developer report)
     mutable std::atomic<int> last_full_batch{0};
+    // queries of the last topk_batch call that went through the kernel's filter form (0: the scans, or the score-block
+    // route, served it), and how many of those were redone exactly (developer report)
+    mutable std::atomic<int> last_full_filter{0}, last_full_redone{0};
     mutable qamd::DevBuf packed_rows;              // developer report: the image un-blocked, [count][image.chunks]
     // The batched top-k's pivot sample (u8_batch.hip): rows hash(j) of the store, j < sample_rows, then 512
     // zero rows; gathered on first use (count / 64 rows at most: 1.6 % of the store), discarded by an upsert.
@@ -151,6 +154,24 @@ inline int u8_levels(bool four_bit, bool full_range) { return four_bit ? 15 : fu
 // queries.  mode / diff: the epilogue (0: an encoded query, 1: score_internal's with `diff`).  Enqueues only.
 qamd_status u8_full_batch_scores(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitch, const float *q_offs, uint32_t nq,
                                  uint64_t n_rows, float *out, uint64_t out_pitch, int mode, float diff, hipStream_t stream);
+// The pieces of it for topk_batch from the filter gate on, which builds the batch's query images once, in scratch of its
+// own (u8_full_images_bytes of device memory), scores a gathered sample of the store with them and then filters the
+// store: u8_full_batch_filter, one launch per pass of 15 queries, appends every (query, row) whose score is at least as
+// good as the query's pivot to the per-query candidate lists of batch_common.hpp (counters: [q * 16], candidates:
+// [q][kTopkCandCap], key << 32 | row).  actual_dim <= 8256 and a finite non-zero multiplier (u8_gemm_route.hpp).
+struct U8FullImages {
+    const uint4 *image = nullptr;  // [pass][nkb][64]
+    const int *sums = nullptr;     // [pass][16]
+    const float *offs = nullptr;   // [pass][16]
+    uint32_t nq = 0, nkb = 0;
+};
+size_t u8_full_images_bytes(const qamd_u8 *h, uint32_t nq);
+qamd_status u8_full_images_build(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitch, const float *q_offs, uint32_t nq,
+                                 void *scratch, hipStream_t stream, U8FullImages *out);
+qamd_status u8_full_batch_scores_of(const qamd_u8 *h, const U8FullImages &im, const uint8_t *codes, const float *v_offsets,
+                                    uint64_t n_rows, float *out, uint64_t out_pitch, int mode, float diff, hipStream_t stream);
+qamd_status u8_full_batch_filter(const qamd_u8 *h, const U8FullImages &im, const float *pivot_scores, uint32_t *counters,
+                                 unsigned long long *candidates, int largest, hipStream_t stream);
 // Smallest batch the full-range matrix-core kernel takes (smaller ones stay on the multi-query scan).
 uint32_t u8_full_batch_min(const qamd_u8 *h);
 qamd_status u8_score_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t pitch, const float *offsets_dev,
