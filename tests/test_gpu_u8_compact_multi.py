@@ -1,8 +1,9 @@
 """Batches of a compact 4-bit u8 store: up to 8 queries per pass over the nibble image (DESIGN.md 3.1z,
 u8_scan_image_multi_kernel).  Raw bits against the oracle's scores of u8_four_bit_model's rows, and against the plain
 4-bit store.  row_chunks 2 (rest group only), 3 (odd: the unread last query chunk), 16 (one ring group), 17, 34 (refill),
-48 and 128; 2..17 queries: every NQ, an unused slot in each, a remainder of one, several groups.  The 32801-row store is
-the one whose topk_batch takes the filtering pass (32768 rows and more)."""
+48 and 128; 2..17 queries: every NQ, an unused slot in each, a remainder of one, several groups.  The 32801-row stores are
+the ones whose topk_batch takes the filtering pass (32768 rows and more): row_chunks 3 (the rest group alone), 17 (a ring
+group and the rest) and 48 (three ring groups, no rest, fewer groups than the eight waves a block is split over)."""
 import functools
 import os
 import subprocess
@@ -23,7 +24,8 @@ DEV_LIB = os.path.join(ROOT, "tools", "lib", "libquantization_amd_dev.so")
 NQS = (2, 3, 4, 5, 8, 9, 17)
 # (dim, rotated, rows, metric, invert)
 CASES = [(32, False, 1, D.Dot, False), (40, False, 65, D.L2, True), (256, False, 64, D.Dot, True), (272, False, 4099, D.L2, False),
-         (544, False, 65, D.Dot, False), (768, True, 4099, D.Dot, False), (2048, False, 64, D.L2, True), (40, False, 32801, D.Dot, False)]
+         (544, False, 65, D.Dot, False), (768, True, 4099, D.Dot, False), (2048, False, 64, D.L2, True), (40, False, 32801, D.Dot, False),
+         (272, False, 32801, D.L2, False), (768, True, 32801, D.Dot, False)]
 IDS = [f"{d}{'r' if r else ''}x{n}-{m.name}{'-inv' if i else ''}" for d, r, n, m, i in CASES]
 cases = pytest.mark.parametrize("case", CASES, ids=IDS)
 
@@ -99,7 +101,7 @@ def child_main(one_cu):
     L = qa.lib()
     seen = lambda h, f: int(getattr(L, "qamd_dev_u8_last_scan_" + f)(h._h))  # (restype int is ctypes' default)
     last = lambda nq: 1 if nq % 8 == 1 else (nq % 8 or 8)  # groups of 8, then a smaller one, a remainder of one scanned singly
-    for case in (CASES[3], CASES[7]):
+    for case in (CASES[3], CASES[7], CASES[8], CASES[9]):
         c = _case(*case)
         comp, plain, n = c["comp"], c["plain"], c["n"]
         split = 1
@@ -116,8 +118,8 @@ def child_main(one_cu):
         assert seen(comp, "queries") == 1
         plain.score_all(plain.encode_query(c["qs"][0]))
         assert seen(plain, "packed") == 2
-        plain.score_batch(plain.encode_query_batch(c["qs"][:2]))  # (rows of 17 chunks have the byte-code pass, of 3 not)
-        assert seen(plain, "packed") == (0 if n == 4099 else 2)  # a store with byte codes keeps their route
+        plain.score_batch(plain.encode_query_batch(c["qs"][:2]))  # (rows of 17 and 48 chunks have the byte-code pass, of 3 not)
+        assert seen(plain, "packed") == (0 if case[0] >= 9 * 16 else 2)  # a store with byte codes keeps their route
     print("DONE")
 
 

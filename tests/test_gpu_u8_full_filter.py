@@ -92,9 +92,13 @@ def child_main():
     L, info = qa.lib(), {}
     for name, kind, dist, sizes in (("random", "768x33000", D.Dot, (4, 5, 16)), ("ties", "ties:768x33000", D.Dot, (5, 16)),
                                     ("l1", "768x33000", D.L1, (5,))):
-        enc, qs, _ = store(kind, dist, False)
+        enc, qs, want = store(kind, dist, False)
         for nq in sizes:
-            enc.topk_batch(enc.encode_query_batch(qs[:nq]), 30)
+            ids, sc = enc.topk_batch(enc.encode_query_batch(qs[:nq]), 30)
+            for j in (j for j in (0, nq - 1) if j in want):  # (the scans' side of the gate too: four queries, L1)
+                wi, ws = ranked(want[j], 30, True)
+                assert np.array_equal(ids[j], wi), (name, nq, j)
+                same(sc[j], ws, (name, nq, j))
             info[f"{name}:{nq}"] = [int(fn(C.c_void_p(enc._h.value))) for fn in (L.qamd_dev_u8_last_full_filter, L.qamd_dev_u8_last_full_redone)]
     print("INFO " + json.dumps(info))
 
