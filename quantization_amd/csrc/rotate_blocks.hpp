@@ -1,5 +1,5 @@
 // The randomized Hadamard rotation of a row in registers or in LDS, shared by the binary quantizer's
-// rotation sinks (bin.hip) and the scalar-u8 quantizer's rotated encoders (u8.hip): the transform, the two
+// rotation sinks (bin.hip) and the scalar-u8 quantizer's rotated encoders (u8_store.hip): the transform, the two
 // kernel frames around it (a wave per row, a workgroup per row) and their launcher.  The translation unit that includes
 // it compiles with contraction off, and every add below is one f32 operation.
 //

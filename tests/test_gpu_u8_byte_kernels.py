@@ -3,8 +3,8 @@
 csrc/u8.hip compiles the byte-code kernels once per row length and picks the instantiation from rc = actual_dim / 16:
 one, two, four or eight lanes per row for rc 1, 2, 3..4, 5..8 (G1, G2, G4, G8), sixteen lanes with ITERS = ceil(rc / 16)
 = 1..8 pieces per lane for rc 9..128 (E1..E8), a run-time loop beyond.  A row that does not fill its shape takes the
-non-EXACT form, which clamps the load address and zeroes the lanes past the row end.  The same switch drives
-launch_scan, launch_small, launch_multi (E shapes, 2 / 4 / 8 queries per pass, multi_reduce.hpp) and the ITERS of
+non-EXACT form, which clamps the load address and zeroes the lanes past the row end.  The same switch (with_row_shape)
+drives launch_scan, launch_small, launch_multi (E shapes, 2 / 4 / 8 queries per pass, multi_reduce.hpp) and the ITERS of
 u8_score_pairs_kernel.  Since the Dot / L2 whole-store scan reads the packed image, these kernels serve L1 stores, short
 rows, stores with a code above 127 ("foreign" rows: no image), every top-k of k <= 64 and every random-access call --
 none of it on the benchmark's path.

@@ -2,7 +2,7 @@
 
 The scan side is pinned shape by shape in test_gpu_u8_byte_kernels.py; this file does the same for the kernels behind
 `encode`, `encode_stream`, `upsert`, `find_min_max`, `find_quantile_interval`, `encode_query` and `encode_query_batch`
-(csrc/u8.hip): the fourteen quantize16_kernel<IT, FAST> forms at the first, the last and a padded dim of each,
+(csrc/u8_store.hip): the fourteen quantize16_kernel<IT, FAST> forms at the first, the last and a padded dim of each,
 quantize_kernel (dim % 4 != 0, or a source that is not 16-byte aligned), minmax_stream_kernel and minmax_kernel with
 the extremes PLANTED at chosen lanes, pieces, components, tiles and tails, the three routes that gather the quantile
 sample of a store above 100 000 rows, and the two query encoders.  tests/u8_encode_shapes.py restates the dispatch and

@@ -1,4 +1,4 @@
-"""The packed u8 scan image (csrc/u8.hip build_packed), checked against the byte codes and the oracle.
+"""The packed u8 scan image (csrc/u8_store.hip build_packed), checked against the byte codes and the oracle.
 
 Every u8 store of 8 to 128 chunks keeps, beside its byte codes, an image of the codes at 7 bits each that the Dot and L2
 scans of lane mode 0 read (u8_internal.hpp).  It may never change a result: the pair sum is the same exact integer,

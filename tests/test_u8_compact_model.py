@@ -85,7 +85,7 @@ def test_refusals_need_no_device(tmp_path):
 def test_metadata_key_order():
     """save writes the base metric, then "rotation", then "bits":4, then the last key "compact":true - stated here from the
     writer's source, which a test without a device cannot run."""
-    src = open(os.path.join(ROOT, "quantization_amd", "csrc", "u8.hip")).read()
+    src = open(os.path.join(ROOT, "quantization_amd", "csrc", "u8_store.hip")).read()
     body = src[src.index("qamd_status qamd_u8_save("):]
     body = body[:body.index("save_file(meta_path")]
     keys = re.findall(r'\\"([a-z_]+)\\":', body)

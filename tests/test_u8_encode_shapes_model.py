@@ -1,6 +1,6 @@
 """The case lists of tests/u8_encode_shapes.py against the u8 encoder's dispatch, without a GPU.
 
-The dispatch of launch_quantize and MinMaxAcc::feed (csrc/u8.hip) is restated in u8_encode_shapes.py; here it is
+The dispatch of launch_quantize and MinMaxAcc::feed (csrc/u8_store.hip) is restated in u8_encode_shapes.py; here it is
 enumerated over dim = 1 .. 4096 x aligned x fast and the lists are held against it: every quantize16_kernel form at
 its first, its last and a padded dim, both situations of quantize_kernel, every outcome of feed().  Each list has a
 stated length and every role is asserted, so deleting any one case turns a test red.  The rest proves on the oracle

@@ -1,4 +1,4 @@
-"""The u8 ENCODER's dispatch (csrc/u8.hip) restated, and the case lists of the tests that pin it.
+"""The u8 ENCODER's dispatch (csrc/u8_store.hip) restated, and the case lists of the tests that pin it.
 
 Shared by tests/test_u8_encode_shapes_model.py (no GPU: keeps the lists honest, and proves on the oracle alone that
 the data shows what it is meant to show) and tests/test_gpu_u8_encode_shapes.py (every case against the oracle, bit
