@@ -26,6 +26,7 @@
 #include "topk.hpp"
 #include "topk_device.hpp"
 #include "rescore.hpp"
+#include "pq_pack4.hpp"
 
 #pragma clang fp contract(off)
 
@@ -367,6 +368,46 @@ struct SkewSlice {
     uint32_t run_shift;  // a wave's blocks come in runs of 1 << run_shift consecutive ones (0 or 2; COAL: 2)
 };
 
+// PACK4 (FILTER only; pq_pack4.hpp has the arithmetic and why the bound is safe): up to FOUR queries of a batch share one pass.
+// The LDS table is [code][M] DWORDS whose byte j is query j's 8-bit entry, at the f32 table's addresses - same banks, same
+// skew, same ring - so the one `ds_read_b32` per code byte now serves four queries.  A lane keeps two registers of two 16-bit
+// fields (bytes 0 | 2 and 1 | 3; a row's four lane sums are at most 128 * 255 < 65536, no field overflows), the quad's four
+// lanes are added with the two DPP steps of the f32 combine, and lane 0 compares the four sums with the queries' integer
+// thresholds, which every lane derives in the prologue from the queries' pivot keys.  Only a (query, row) that passes is
+// scored exactly (pack4_survivors below: the row's bytes and the query's chunk-major f32 table from global memory - both
+// cached, and about 2 * target of n rows survive - in exactly the lane order of the scan) and offered to that query's filter
+// slice, whose key comparison decides as in every other filter pass: the candidates are those of the single-query pass.
+// (The ring cannot serve the survivors: when a row's sum is complete, its slot has been refilled with the block after next.)
+// Padded columns (PAD, the row's own padding) hold 0 for every code; the columns of R store rows repeat, as in the f32 table.
+struct SkewPack4 {
+    const Pack4Query *params;  // of the launch's queries, for the search's direction
+    const float *luts;     // the first query's chunk-major f32 table; bt.lut_stride floats to the next query's
+    uint32_t m;            // chunks of a store row
+};
+
+// The exact scores of a row for the queries (bits of `passed`) whose integer test it passed: lane sums of chunks k, k + 4, ...,
+// then (l0 + l2) + (l1 + l3).  One call site per completed row and out of line: the scan's loop keeps its registers.
+__device__ __noinline__ void pack4_survivors(const TopkFilterSlices &fsl, uint32_t passed, const float *__restrict__ luts,
+                                             uint32_t lut_stride, const uint8_t *__restrict__ row_bytes, uint32_t m, uint32_t row,
+                                             uint32_t shard) {
+    const uint32_t *p = reinterpret_cast<const uint32_t *>(row_bytes);
+    for (uint32_t j = 0; j < 4; j++) {
+        if (!((passed >> j) & 1u)) continue;
+        const float *lut = luts + (size_t)j * lut_stride;
+        float l0 = 0.0f, l1 = 0.0f, l2 = 0.0f, l3 = 0.0f;
+        for (uint32_t t = 0; t < m / 4; t++) {
+            const uint32_t w = p[t];
+            const float *q = lut + (size_t)t * 4 * kCentroids;
+            l0 += q[w & 255u];
+            l1 += q[kCentroids + ((w >> 8) & 255u)];
+            l2 += q[2 * kCentroids + ((w >> 16) & 255u)];
+            l3 += q[3 * kCentroids + (w >> 24)];
+        }
+        const TopkFilter f = topk_filter_of(fsl, j);
+        topk_offer_shard(f, *f.pivot_key, (l0 + l2) + (l1 + l3), row, shard);
+    }
+}
+
 // R > 1: a ring row is R consecutive store rows (M = R m bytes, m % 4 == 0, m / 4 >= 8) and the LUT's columns repeat R
 // times in LDS.  That is the conflict-free scan for rows whose length is not a multiple of 32 chunks: the eight quads of a
 // lane group sit at eight consecutive chunk groups of their byte stream, and the banks those hit are distinct only if the
@@ -386,13 +427,14 @@ struct SkewSlice {
 // columns of +0.0 - whatever byte lies in the ring's padding is a valid code, and a lane sum that starts at +0.0 never is -0.0,
 // so the padded steps leave every sum bit for bit what it was.  The padded steps are executed (96 for 80, 128 for 112), but
 // the kernel's time is its stream's (above), and that carries the row's own m bytes only.
-template <int NV, int R, bool FILTER, bool SLICED, bool COAL, int PAD = 0>
-__global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_skew_kernel(const uint4 *__restrict__ rows4,
-                                                                 const float *__restrict__ lut_t_g, uint32_t n_rows,
-                                                                 float *__restrict__ out, TopkFilter filt, SkewSlice sl, SkewBatch bt) {
+// (The body of pq_scan_skew_kernel and of its sibling pq_scan_pack4_kernel, both below.)
+template <int NV, int R, bool FILTER, bool SLICED, bool COAL, int PAD, bool PACK4>
+__device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const float *__restrict__ lut_t_g, uint32_t n_rows,
+                                          float *__restrict__ out, TopkFilter filt, SkewSlice sl, SkewBatch bt, SkewPack4 pk) {
     constexpr int M = 16 * NV, S = 4 * NV;
+    static_assert(!PACK4 || (FILTER && !SLICED && !COAL), "the packed tables serve whole-row filter passes");
     uint32_t wg = blockIdx.x, n_wg = gridDim.x;  // this workgroup's place among those that share the rows
-    if (bt.n > 1) {
+    if (!PACK4 && bt.n > 1) {
         const uint32_t slot = blockIdx.x / 8u, streams = (gridDim.x / 8u) / bt.n, qi = slot % bt.n, stream_local = slot / bt.n;
         if (stream_local >= streams) return;
         wg = (blockIdx.x % 8u) * streams + stream_local;
@@ -416,7 +458,10 @@ __global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_skew_kernel(
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     {
         float4 *dst = reinterpret_cast<float4 *>(lds_raw + kLut0);
-        if (SLICED) {  // the slice's columns of the [code][m_total] table
+        if (PACK4) {  // `lut_t_g` is the group's packed [code][M] table, laid out for this ring row by pq_lut_pack4_kernel
+            const float4 *src = reinterpret_cast<const float4 *>(lut_t_g);
+            for (uint32_t i = threadIdx.x; i < (uint32_t)M * (kCentroids / 4); i += kThreads) dst[i] = src[i];
+        } else if (SLICED) {  // the slice's columns of the [code][m_total] table
             for (uint32_t i = threadIdx.x; i < (uint32_t)M * (kCentroids / 4); i += kThreads)
                 dst[i] = *reinterpret_cast<const float4 *>(lut_t_g + (size_t)(i / (M / 4)) * sl.m_total + sl.chunk0 + 4u * (i % (M / 4)));
         } else if (R == 1 && (PAD || (sl.m_total && sl.m_total != (uint32_t)M))) {
@@ -464,7 +509,16 @@ __global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_skew_kernel(
         lut_base[u] = lag ? off_new : off_cur;
     }
     uint32_t pivot = 0;
-    if (FILTER) pivot = *filt.pivot_key;
+    if (FILTER && !PACK4) pivot = *filt.pivot_key;
+    uint32_t thr[4] = {kPack4Never, kPack4Never, kPack4Never, kPack4Never};  // (a last group of 2 or 3: the unused bytes never pass)
+    if (PACK4) {
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++)
+            if (j < bt.n) {
+                const float pivot_score = topk_score_of_key(*topk_filter_of(bt.fsl, j).pivot_key, bt.fsl.largest != 0);
+                thr[j] = __builtin_amdgcn_readfirstlane(pack4_threshold(pk.params[j], pivot_score, bt.fsl.largest));
+            }
+    }
     const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(out, 0, FILTER ? 0 : n_rows * 4u, 0x00020000);
     const __amdgpu_buffer_rsrc_t partial_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(SLICED ? sl.partial : nullptr, 0, SLICED ? n_rows * 16u : 0, 0x00020000);
@@ -542,6 +596,7 @@ __global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_skew_kernel(
         vals[1][e] = 0.0f;
     }
     float acc = 0.0f, done = 0.0f, keep = 0.0f;
+    uint32_t acc02 = 0, acc13 = 0, done02 = 0, done13 = 0;  // PACK4: the 16-bit sums of queries 0 | 2 and 1 | 3
     // All of the prologue's loads have landed before the loop starts (once per wave).  The compiler places the loop's
     // `s_waitcnt vmcnt(n)` for the state of BOTH ways into the loop header, and it orders the prologue's loads its own way
     // (all 8-byte rounds first): coming from there a buffer had 3 younger loads, so the loop waited with vmcnt(3) - for
@@ -576,16 +631,37 @@ __global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_skew_kernel(
                 const uint32_t jp = G == 0 ? j0 - 1u : j0 + (uint32_t)jjp;  // its row time
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
-                    acc += vals[(G + 1) & 1][e];
+                    if (PACK4) {
+                        const uint32_t v = __float_as_uint(vals[(G + 1) & 1][e]);  // four queries' bytes
+                        acc02 += v & 0x00FF00FFu;
+                        acc13 += (v >> 8) & 0x00FF00FFu;
+                    } else {
+                        acc += vals[(G + 1) & 1][e];
+                    }
                     const int u = 8 * gp + e, w = u % SR, sub = u / SR;  // step w of store row `sub` for a quad without lag
                     if (w < 8) {  // quads r = w + 1 (mod SR): that was the last chunk group of their previous store row
                         const bool fin = kTwoGen ? (int)((r - 1u) & (uint32_t)(SR - 1)) == w : (int)r == w + 1;
-                        done = fin ? acc : done;
-                        acc = fin ? (SLICED ? init_of[jjp & 1] : 0.0f) : acc;  // their next store row starts
+                        if (PACK4) {
+                            done02 = fin ? acc02 : done02;
+                            done13 = fin ? acc13 : done13;
+                            acc02 = fin ? 0u : acc02;
+                            acc13 = fin ? 0u : acc13;
+                        } else {
+                            done = fin ? acc : done;
+                            acc = fin ? (SLICED ? init_of[jjp & 1] : 0.0f) : acc;  // their next store row starts
+                        }
                     }
                     if (w == 7 % SR) {  // every quad's previous store row is complete:  (l0 + l2) + (l1 + l3)  (:430-432)
                         const float a = done + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(done), 0x4E, 0xF, 0xF, false));
                         const float sc = a + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), 0xB1, 0xF, 0xF, false));
+                        // PACK4: the quad's four lane sums of every query, fields of 16 bits
+                        uint32_t s02 = 0, s13 = 0;
+                        if (PACK4) {
+                            const uint32_t a02 = done02 + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)done02, 0x4E, 0xF, 0xF, false);
+                            const uint32_t a13 = done13 + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)done13, 0x4E, 0xF, 0xF, false);
+                            s02 = a02 + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a02, 0xB1, 0xF, 0xF, false);
+                            s13 = a13 + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a13, 0xB1, 0xF, 0xF, false);
+                        }
                         // sub == 0: the last store row of the ring row of block jp - 1; else store row sub - 1 of block jp's
                         uint32_t jb = sub == 0 ? jp - 1u : jp, srow = (uint32_t)(sub == 0 ? R - 1 : sub - 1);
                         bool started = true;
@@ -598,6 +674,13 @@ __global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_skew_kernel(
                         const bool live = started && jb < J && row < n_rows;  // (jb = -1, -2 as unsigned: the pipeline's first trips)
                         if (SLICED && !sl.last) {  // the lane sums go back to `partial` for the next slice
                             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(done), partial_rsrc, live ? (row * 4u + k) * 4u : 0xFFFFFFFFu, 0, 0);
+                        } else if (PACK4) {
+                            const bool p0 = (s02 & 0xFFFFu) >= thr[0], p1 = (s13 & 0xFFFFu) >= thr[1], p2 = (s02 >> 16) >= thr[2], p3 = (s13 >> 16) >= thr[3];
+                            if (k == 0 && live && (p0 || p1 || p2 || p3)) {  // cold: about 2 * target of n rows per query
+                                const uint8_t *row_bytes = rows_b + (size_t)row * (uint32_t)(MROW / R);
+                                pack4_survivors(bt.fsl, (p0 ? 1u : 0u) | (p1 ? 2u : 0u) | (p2 ? 4u : 0u) | (p3 ? 8u : 0u), pk.luts, bt.lut_stride,
+                                                row_bytes, pk.m, row, wg);
+                            }
                         } else if (FILTER) {
                             // shard by wg, the workgroup's place among those of this query (blockIdx.x for one query):
                             // keyed by blockIdx.x, n queries side by side each reached only 64 / n of their lists
@@ -625,6 +708,21 @@ __global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_skew_kernel(
             if (g == 0) init_of[(jj + 1) & 1] = init_new;  // (after C: with one group per row time C still used the slot's old value)
         }
     }
+}
+
+template <int NV, int R, bool FILTER, bool SLICED, bool COAL, int PAD = 0>
+__global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_skew_kernel(const uint4 *__restrict__ rows4,
+                                                                 const float *__restrict__ lut_t_g, uint32_t n_rows,
+                                                                 float *__restrict__ out, TopkFilter filt, SkewSlice sl, SkewBatch bt) {
+    skew_scan<NV, R, FILTER, SLICED, COAL, PAD, false>(rows4, lut_t_g, n_rows, out, filt, sl, bt, SkewPack4{});
+}
+
+// The filter pass of up to four queries (bt.n, bt.fsl, bt.lut_stride) through one packed table (SkewPack4 above).
+template <int NV, int R, int PAD>
+__global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_pack4_kernel(const uint4 *__restrict__ rows4,
+                                                                  const uint32_t *__restrict__ table, uint32_t n_rows,
+                                                                  SkewSlice sl, SkewBatch bt, SkewPack4 pk) {
+    skew_scan<NV, R, true, false, false, PAD, true>(rows4, reinterpret_cast<const float *>(table), n_rows, nullptr, TopkFilter{}, sl, bt, pk);
 }
 
 // ------------------------------------------------------------------------------ encode
@@ -781,6 +879,70 @@ __global__ __launch_bounds__(kBlock) void pq_lut_batch_kernel(const float *__res
         for (uint32_t j = 0; j < len; j++) s += (a[j] - b[j]) * (a[j] - b[j]);
     luts[(size_t)blockIdx.y * m * kCentroids + i] = invert ? -s : s;
     if (luts_t) luts_t[(size_t)blockIdx.y * m * kCentroids + kc * m + c] = invert ? -s : s;
+}
+
+// The packed filter tables of a query batch (pq_pack4.hpp; scanned by pq_scan_pack4_kernel): blockIdx.x is a group of
+// four consecutive queries (the last one may hold 2 or 3: its unused bytes are 0), and for each search direction d
+// (0: smallest first, 1: largest first) the group gets one table [code][ring] of dwords at tables[(2 group + d) * 256 * ring],
+// byte j = query j's entry, laid out as the scan's LDS image: column col < cols_real is chunk col % m (two store rows per ring
+// row repeat the columns), the columns past it (padding) are 0.  params[d * n_queries + query] is the query's Pack4Query.
+// Every workgroup works out the group's statistics itself - a wave per (query, chunk) for the extremes, then one thread per
+// query over the chunks in order, so all of them get the same doubles - and writes the table rows of kPack4Codes codes
+// (blockIdx.y); the entries come from the [code][chunk] copies, coalesced.
+constexpr uint32_t kPack4Codes = 32;
+__global__ __launch_bounds__(kBlock) void pq_lut_pack4_kernel(const float *__restrict__ luts, const float *__restrict__ luts_t,
+                                                             uint32_t n_queries, uint32_t m, uint32_t ring, uint32_t cols_real,
+                                                             uint32_t *__restrict__ tables, Pack4Query *__restrict__ params) {
+    __shared__ float s_mn[4][128], s_mx[4][128];
+    __shared__ uint32_t s_finite[4][128];
+    __shared__ double s_step[2][4];  // per direction and query; 0: every entry 0 (a flagged query, an unused byte)
+    const uint32_t group = blockIdx.x, q0 = 4u * group, nq = min(4u, n_queries - q0);
+    const size_t per = (size_t)m * kCentroids;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t i = wave; i < nq * m; i += kBlock / 64) {
+        const uint32_t j = i / m, c = i % m;
+        const float4 v = reinterpret_cast<const float4 *>(luts + (q0 + j) * per + (size_t)c * kCentroids)[lane];
+        float mn = fminf(fminf(v.x, v.y), fminf(v.z, v.w)), mx = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+        const bool finite = __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z) && __builtin_isfinite(v.w);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            mn = fminf(mn, __shfl_xor(mn, d, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, d, 64));
+        }
+        const bool all_finite = __all(finite);
+        if (lane == 0) {
+            s_mn[j][c] = mn;
+            s_mx[j][c] = mx;
+            s_finite[j][c] = all_finite ? 1u : 0u;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const uint32_t j = threadIdx.x;
+        Pack4Stats st;
+        if (j < nq)
+            for (uint32_t c = 0; c < m; c++) pack4_add_chunk(st, s_mn[j][c], s_mx[j][c], s_finite[j][c] != 0);
+        for (int d = 0; d < 2; d++) {
+            const Pack4Query p = pack4_params(st, m, d);
+            s_step[d][j] = j < nq && p.bad == 0.0 ? p.step : 0.0;
+            if (j < nq && blockIdx.y == 0) params[(size_t)d * n_queries + q0 + j] = p;
+        }
+    }
+    __syncthreads();
+    const uint32_t code0 = blockIdx.y * kPack4Codes;
+    for (uint32_t i = threadIdx.x; i < kPack4Codes * ring; i += kBlock) {
+        const uint32_t code = code0 + i / ring, col = i % ring, c = col % m;
+        uint32_t word[2] = {0u, 0u};
+        if (col < cols_real)
+            for (uint32_t j = 0; j < nq; j++) {
+                const float v = luts_t[(q0 + j) * per + (size_t)code * m + c];
+#pragma unroll
+                for (int d = 0; d < 2; d++)
+                    if (s_step[d][j] > 0.0) word[d] |= pack4_entry(v, s_mn[j][c], s_mx[j][c], s_step[d][j], d) << (8u * j);
+            }
+        tables[((size_t)(2u * group + 0u) * kCentroids + code) * ring + col] = word[0];
+        tables[((size_t)(2u * group + 1u) * kCentroids + code) * ring + col] = word[1];
+    }
 }
 
 // score_internal (:566-593): decode both rows to centroid sub-vectors, sequential f32.
@@ -1632,6 +1794,56 @@ uint32_t skew_pad(const qamd_pq *h) {  // (the ring row's chunks; 0: not a padde
     return skew_padded_ring(h, &pad);
 }
 bool skew_capable(const qamd_pq *h) { return skew_rows_per_ring_row(h) != 0 || skew_pad(h) != 0; }
+
+// pq_scan_pack4_kernel: every whole-row shape of pq_scan_skew_kernel (m % 4 == 0, 16 <= m <= 128).  The ring row's chunks = the
+// columns of a packed table; 0: the store's batches get no packed tables.  The row count only has to reach the filter pass at
+// all (fast_capable); nothing in the kernel depends on XCD placement, but it has been measured on the whole device only, so a
+// device that does not report 256 CUs (a partition) keeps its filter passes query by query.
+uint32_t pack4_ring(const qamd_pq *h) {
+    static const bool on = [] { const char *e = dev_env("QAMD_PQ_PACK4"); return !(e && e[0] == '0'); }();  // developer A/B (tools/lib build): 0 = off
+    if (!on || !skew_capable(h) || device_info().cu_count != 256) return 0;
+    const uint32_t ring_rows = skew_rows_per_ring_row(h);
+    return ring_rows ? ring_rows * (uint32_t)h->m : skew_pad(h);
+}
+template <int NV, int R, int PAD> bool pack4_ready() {
+    static DeviceOnce once;
+    const qamd_status st = once.run([] {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&pq_scan_pack4_kernel<NV, R, PAD>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)skew_lds_bytes(16 * NV)) != hipSuccess) {
+            (void)hipGetLastError();
+            g_skew_unusable.store(true, std::memory_order_relaxed);
+        }
+        return QAMD_OK;
+    });
+    return st == QAMD_OK && !g_skew_unusable.load(std::memory_order_relaxed);
+}
+// One filter pass for bt.n (2 .. 4) queries of a batch: `table` is their group's packed table for the search's direction.
+// *done = false: the device refused the kernel's LDS size, nothing was launched.
+qamd_status launch_pack4(const qamd_pq *h, const uint32_t *table, const SkewBatch &bt, const SkewPack4 &pk, hipStream_t s, bool *done) {
+    *done = false;
+    uint32_t pad_bytes = 0;
+    const uint32_t ring_rows = skew_rows_per_ring_row(h), pad = skew_padded_ring(h, &pad_bytes), ring = pack4_ring(h);
+    const uint64_t n = h->count;
+    const int grid = (int)std::min<uint64_t>(device_info().cu_count, (n + 1023) / 1024);
+    SkewSlice whole{};
+    whole.run_shift = skew_run_shift(n, pad ? 1 : ring_rows, grid, ring);
+#define QAMD_PQ_PACK4(NVV, RR, PD)                                                                                              \
+    case NVV * 1000 + RR * 100 + PD:                                                                                           \
+        if (!pack4_ready<NVV, RR, PD>()) return QAMD_OK;                                                                       \
+        hipLaunchKernelGGL((pq_scan_pack4_kernel<NVV, RR, PD>), dim3(grid), dim3(64 * skew_waves(16 * NVV)), skew_lds_bytes(16 * NVV), s, \
+                           h->rows.as<uint4>(), table, (uint32_t)n, whole, bt, pk);                                            \
+        break;
+    switch (ring / 16 * 1000 + (ring_rows == 2 ? 2u : 1u) * 100 + pad_bytes) {
+        QAMD_PQ_PACK4(2, 1, 0) QAMD_PQ_PACK4(4, 1, 0) QAMD_PQ_PACK4(6, 1, 0) QAMD_PQ_PACK4(8, 1, 0)
+        QAMD_PQ_PACK4(4, 1, 16) QAMD_PQ_PACK4(6, 1, 16) QAMD_PQ_PACK4(8, 1, 16)
+        QAMD_PQ_PACK4(2, 2, 0) QAMD_PQ_PACK4(6, 2, 0)
+        default: return QAMD_OK;
+    }
+#undef QAMD_PQ_PACK4
+    QAMD_HIP(hipGetLastError());
+    *done = true;
+    return QAMD_OK;
+}
 
 // `many` (FILTER only): the launch serves many->n queries side by side (SkewBatch) - only the conflict-free kernel does that;
 // *many_done says whether it was launched that way (false: nothing was launched, the caller goes query by query).
@@ -2896,17 +3108,30 @@ qamd_status qamd_pq_upsert(qamd_pq *h, uint64_t first_row, const float *data, qa
 
 // ============================================================================= many queries at once
 // The caller's OUTER loop over queries (demos/src/ann_benchmark.rs:245-260), each with its 30-entry
-// heap (ann_benchmark_data.rs:151-167).  A PQ scan serves one query at a time -- the LDS holds one
-// chunk-major LUT (96 KiB at m = 96) and the gather rate of that LDS, not HBM, bounds it -- so the
-// batch form builds all LUTs with one launch and then ENQUEUES the per-query scans back to back:
-// no per-query allocation, no per-query synchronisation (fused_topk_batch reads the statuses back
-// once per 32 queries).  Every score and every list is bit-identical to the single-query calls.
+// heap (ann_benchmark_data.rs:151-167).  A PQ scan that must produce f32 scores serves one query at a
+// time -- the LDS holds one f32 LUT (96 KiB at m = 96) -- so the batch form builds all LUTs with one
+// launch and then ENQUEUES the per-query scans back to back: no per-query allocation, no per-query
+// synchronisation (fused_topk_batch reads the statuses back once per 32 queries).  The FILTER pass of
+// topk_batch only has to reject rows: there four queries share a pass through one packed 8-bit table
+// (pq_scan_pack4_kernel).  Every score and every list is bit-identical to the single-query calls.
 struct qamd_pq_query_batch {
     int device = 0;
     uint64_t m = 0, n_queries = 0;
     DevBuf luts;  // [n_queries][m * 256] f32, chunk-major; `transposed`: the [code][chunk] copies follow, same order
     bool transposed = false;
     const float *lut_t(uint64_t q) const { return transposed ? luts.as<float>() + (n_queries + q) * m * kCentroids : nullptr; }
+    // The packed filter tables of topk_batch (pq_lut_pack4_kernel), when the store takes pq_scan_pack4_kernel: per group of four
+    // queries and search direction 256 * pack4_ring dwords, then the [2][n_queries] Pack4Query.  pack4_ring == 0: none.
+    DevBuf pack4;
+    uint32_t pack4_ring = 0;
+    uint64_t pack4_groups() const { return n_queries / 4 + (n_queries % 4 >= 2 ? 1 : 0); }  // (a last group of one takes the single scan)
+    const uint32_t *pack4_table(uint64_t group, int largest) const {
+        return pack4.as<uint32_t>() + (2 * group + (largest ? 1 : 0)) * kCentroids * pack4_ring;
+    }
+    const Pack4Query *pack4_params(uint64_t q, int largest) const {
+        return reinterpret_cast<const Pack4Query *>(pack4.as<uint32_t>() + 2 * pack4_groups() * kCentroids * pack4_ring) +
+               (largest ? n_queries : 0) + q;
+    }
 };
 
 extern "C" {
@@ -2933,6 +3158,11 @@ qamd_status qamd_pq_encode_query_batch(const qamd_pq *h, const float *queries, u
     b->m = h->m;
     b->n_queries = n_queries;
     b->transposed = with_t;
+    b->pack4_ring = n_queries >= 2 && fast_capable(h, h->count) ? pack4_ring(h) : 0;
+    if (b->pack4_ring) {
+        const size_t bytes = 2 * b->pack4_groups() * kCentroids * b->pack4_ring * sizeof(uint32_t) + 2 * n_queries * sizeof(Pack4Query);
+        if (b->pack4.bytes < bytes) QAMD_TRY(b->pack4.alloc(bytes));
+    }
     if (per && n_queries) {
         DevBuf qtmp;
         const void *qd = nullptr;
@@ -2942,6 +3172,13 @@ qamd_status qamd_pq_encode_query_batch(const qamd_pq *h, const float *queries, u
                            dim3(kBlock), 0, s, static_cast<const float *>(qd), (uint32_t)h->vp.dim, (uint32_t)h->chunk_size,
                            (uint32_t)h->m, h->centroids.as<float>(), h->vp.distance_type, h->vp.invert, b->luts.as<float>(),
                            with_t ? b->luts.as<float>() + per * n_queries : nullptr);
+        if (b->pack4_ring && b->pack4_groups()) {
+            const uint32_t ring_rows = skew_rows_per_ring_row(h);
+            hipLaunchKernelGGL(pq_lut_pack4_kernel, dim3((uint32_t)b->pack4_groups(), kCentroids / kPack4Codes), dim3(kBlock), 0, s,
+                               b->luts.as<float>(), b->luts.as<float>() + per * n_queries, (uint32_t)n_queries, (uint32_t)h->m,
+                               b->pack4_ring, ring_rows ? ring_rows * (uint32_t)h->m : (uint32_t)h->m, b->pack4.as<uint32_t>(),
+                               const_cast<Pack4Query *>(b->pack4_params(0, 0)));
+        }
         QAMD_HIP(hipGetLastError());
         if (staged) QAMD_HIP(hipStreamSynchronize(s));  // qtmp is freed on return
     }
@@ -3053,8 +3290,25 @@ qamd_status qamd_pq_topk_batch(const qamd_pq *h, const qamd_pq_query_batch *b, u
     //   ask the same L2 lines at the same time); 12.5M x 1536 (m = 192): 0.585, two 0.563, four 0.545.  Plain instead of nt loads: worse
     //   everywhere (0.298 query by query).  Stores of a million rows and more (a quarter of the machine per query keeps its waves fed).
     static const char *eside = dev_env("QAMD_PQ_SIDE");  // developer A/B: 0 = query by query; 2 / 4 / 8: at most so many side by side
-    if (b->transposed && fast_capable(h, h->count) && device_info().cu_count == 256 && h->count >= (1u << 20) && !(eside && eside[0] == '0'))
-        scan.scan_filter_multi = [&](uint32_t q, uint32_t avail, const TopkFilterSlices &fsl, hipStream_t st, qamd_status &status) -> uint32_t {
+    const bool side = b->transposed && fast_capable(h, h->count) && device_info().cu_count == 256 && h->count >= (1u << 20) && !(eside && eside[0] == '0');
+    // Before that, groups of four queries (the batch's last: 2 or 3) in ONE pass through their packed 8-bit table
+    // (pq_scan_pack4_kernel): the batch must carry the tables of this store's ring row (encode_query_batch made them).
+    const bool pack4 = b->pack4_ring != 0 && b->pack4_ring == pack4_ring(h) && fast_capable(h, h->count);
+    scan.filter_name = qamd_pq_scan_kernel(h, nullptr);
+    if (pack4 || side)
+        scan.scan_filter_multi = [&, pack4, side](uint32_t q, uint32_t avail, const TopkFilterSlices &fsl, hipStream_t st, qamd_status &status) -> uint32_t {
+            if (pack4 && q % 4 == 0 && std::min<uint64_t>(avail, 4) == std::min<uint64_t>(b->n_queries - q, 4) && avail >= 2) {
+                SkewBatch four{};
+                four.n = std::min(avail, 4u);
+                four.lut_stride = (uint32_t)per;
+                four.fsl = fsl;
+                const SkewPack4 pk{b->pack4_params(q, largest), luts + q * per, (uint32_t)h->m};
+                bool done = false;
+                status = launch_pack4(h, b->pack4_table(q / 4, largest), four, pk, st, &done);
+                if (status == QAMD_OK && done) scan.filter_multi_name = "pq_scan_pack4_kernel";
+                if (status != QAMD_OK || done) return status == QAMD_OK ? four.n : 0u;
+            }
+            if (!side) return 0;
             const uint32_t most = eside ? (uint32_t)atoi(eside) : 4u;
             const uint32_t g = avail >= 8 && most >= 8 ? 8u : avail >= 4 && most >= 4 ? 4u : avail >= 2 && most >= 2 ? 2u : 0u;
             if (g == 0) return 0;
@@ -3064,6 +3318,7 @@ qamd_status qamd_pq_topk_batch(const qamd_pq *h, const qamd_pq_query_batch *b, u
             many.fsl = fsl;
             bool done = false;
             status = launch_fast<true>(h, nullptr, nullptr, nullptr, st, b->lut_t(q), &many, &done);
+            if (status == QAMD_OK && done) scan.filter_multi_name = skew_capable(h) ? "pq_scan_skew_kernel" : "pq_scan_skew_kernel<SLICED>";
             return status == QAMD_OK && done ? g : 0u;
         };
     return fused_topk_batch(h->count, (uint32_t)b->n_queries, k, largest, out_ids, out_scores, out_mem, as_stream(stream),

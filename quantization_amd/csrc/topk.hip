@@ -653,7 +653,8 @@ qamd_status fused_topk_batch(uint64_t n, uint32_t Q, uint32_t k, int largest, ui
         }
         if (debug_topk && st == QAMD_OK)
             fprintf(stderr, "[qamd fused_topk_batch] Q=%u r=%u candidates min/mean/max = %u/%llu/%u, side by side %u x %u, "
-                    "%u queries redone\n", Q, r, dbg_min, (unsigned long long)(dbg_sum / Q), dbg_max, dbg_side, dbg_width, dbg_redo);
+                    "filter %s, %u queries redone\n", Q, r, dbg_min, (unsigned long long)(dbg_sum / Q), dbg_max, dbg_side, dbg_width,
+                    dbg_side && scan.filter_multi_name ? scan.filter_multi_name : scan.filter_name ? scan.filter_name : "-", dbg_redo);
     }
     if (scores) {
         thread_ws_release(WS_SCORES, stream);

@@ -97,6 +97,10 @@ struct BatchScan {
     // returns how many queries it took (8, 4, 2) or 0 when it has no kernel for this store / count
     std::function<uint32_t(uint32_t q0, uint32_t nq, const TopkFilterSlices &slices, hipStream_t, qamd_status &st)>
         scan_filter_multi;
+    // for the QAMD_DEBUG_TOPK line only: the kernel behind scan_filter, and - set by scan_filter_multi when it launches - the
+    // kernel of its launches
+    const char *filter_name = nullptr;
+    const char *filter_multi_name = nullptr;
 };
 qamd_status fused_topk_batch(uint64_t n, uint32_t n_queries, uint32_t k, int largest, uint32_t *out_ids,
                              float *out_scores, qamd_mem out_mem, hipStream_t stream, const BatchScan &scan);
