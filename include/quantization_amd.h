@@ -798,8 +798,9 @@ QAMD_API void qamd_pq_free(qamd_pq *h);
  * LDS-LUT scans are enqueued back to back (one f32 LUT fills the LDS, so the queries of score_batch
  * cannot share a pass); topk_batch reads statuses back once per 32 queries and synchronises
  * the stream.  Bit-identical to the single-query calls.  For stores whose rows have 16 .. 128 chunks
- * (a multiple of 4) encode_query_batch also leaves packed 8-bit bound tables, one per four queries,
- * with which topk_batch filters four queries per pass over the rows. */
+ * (a multiple of 4), or 160 .. 256 chunks (a multiple of 32) in a planar scan image, encode_query_batch
+ * also leaves packed 8-bit bound tables, one per four queries, with which topk_batch filters four
+ * queries per pass over the rows. */
 typedef struct qamd_pq_query_batch qamd_pq_query_batch; /* n x EncodedQueryPQ */
 QAMD_API qamd_status qamd_pq_encode_query_batch(const qamd_pq *h, const float *queries, uint64_t n_queries,
                                                 uint64_t qdim, qamd_mem queries_mem, void *stream,
@@ -814,7 +815,8 @@ QAMD_API qamd_status qamd_pq_score_ids_batch(const qamd_pq *h, const qamd_pq_que
                                              void *stream);
 /* Top-k of every query of the batch, as qamd_pq_topk.  Rows of 16 .. 128 chunks (a multiple of 4): four queries share each
  * filter pass through a packed 8-bit table - a safe integer bound rejects rows, the exact f32 score of the survivors decides -
- * when `b` was encoded for this store (or one of its row shape); a query that cannot be bounded (a table entry that is not
+ * when `b` was encoded for this store (or one of its row shape); rows of 160, 192, 224 or 256 chunks take that pass slice by
+ * slice over the planar scan image, 8 bytes of workspace per row between the slices (QAMD_ERR_DEVICE if it cannot be had); a query that cannot be bounded (a table entry that is not
  * finite, a constant table) takes the exact route.  A device that does not report 256 CUs (a partitioned MI355X) runs the
  * filter passes query by query, never several queries per launch; so does a store without a planar scan image (2^28 rows and
  * more) whose rows have more than 144 chunks.  The answer is the same either way. */

@@ -379,10 +379,21 @@ struct SkewSlice {
 // slice, whose key comparison decides as in every other filter pass: the candidates are those of the single-query pass.
 // (The ring cannot serve the survivors: when a row's sum is complete, its slot has been refilled with the block after next.)
 // Padded columns (PAD, the row's own padding) hold 0 for every code; the columns of R store rows repeat, as in the f32 table.
+//
+// SLICED && PACK4 (rows of 160 .. 256 chunks, whose [256][m] dword table no longer fits the LDS): one launch per slice of the
+// planar scan image, the LDS holding that slice's packed table [code][slice chunks].  Integer sums are associative, so what is
+// parked between two slice launches is the QUAD's sum, not the lanes': one 8-byte word per row, the two registers of two
+// 16-bit fields (a whole row is at most 256 * 255 = 65280 < 65536), at sl.partial (8 bytes per row against the f32 form's 16
+// per row and query).  Lane 0 of a quad starts its sum for a row from that word (the other lanes from 0), so the two DPP
+// steps give the row's sum over all slices so far; lane 0 writes it back (unless last), and the last slice tests it against
+// the thresholds.  The survivors are scored from the store's row-major image (pk.rows), all m_total chunks in one go: the
+// slice lengths are multiples of 4, so the lane sums over k, k + 4, ... are the single-query scan's.
 struct SkewPack4 {
     const Pack4Query *params;  // of the launch's queries, for the search's direction
     const float *luts;     // the first query's chunk-major f32 table; bt.lut_stride floats to the next query's
     uint32_t m;            // chunks of a store row
+    const uint8_t *rows;   // SLICED: the store's row-major image, row_stride bytes per row (the survivors' bytes)
+    uint32_t row_stride;
 };
 
 // The exact scores of a row for the queries (bits of `passed`) whose integer test it passed: lane sums of chunks k, k + 4, ...,
@@ -432,7 +443,7 @@ template <int NV, int R, bool FILTER, bool SLICED, bool COAL, int PAD, bool PACK
 __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const float *__restrict__ lut_t_g, uint32_t n_rows,
                                           float *__restrict__ out, TopkFilter filt, SkewSlice sl, SkewBatch bt, SkewPack4 pk) {
     constexpr int M = 16 * NV, S = 4 * NV;
-    static_assert(!PACK4 || (FILTER && !SLICED && !COAL), "the packed tables serve whole-row filter passes");
+    static_assert(!PACK4 || (FILTER && !COAL), "the packed tables serve filter passes");
     uint32_t wg = blockIdx.x, n_wg = gridDim.x;  // this workgroup's place among those that share the rows
     if (!PACK4 && bt.n > 1) {
         const uint32_t slot = blockIdx.x / 8u, streams = (gridDim.x / 8u) / bt.n, qi = slot % bt.n, stream_local = slot / bt.n;
@@ -458,7 +469,7 @@ __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     {
         float4 *dst = reinterpret_cast<float4 *>(lds_raw + kLut0);
-        if (PACK4) {  // `lut_t_g` is the group's packed [code][M] table, laid out for this ring row by pq_lut_pack4_kernel
+        if (PACK4) {  // `lut_t_g` is the group's packed [code][M] table, laid out for this ring row (SLICED: this slice) by pq_lut_pack4_kernel
             const float4 *src = reinterpret_cast<const float4 *>(lut_t_g);
             for (uint32_t i = threadIdx.x; i < (uint32_t)M * (kCentroids / 4); i += kThreads) dst[i] = src[i];
         } else if (SLICED) {  // the slice's columns of the [code][m_total] table
@@ -511,7 +522,7 @@ __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const
     uint32_t pivot = 0;
     if (FILTER && !PACK4) pivot = *filt.pivot_key;
     uint32_t thr[4] = {kPack4Never, kPack4Never, kPack4Never, kPack4Never};  // (a last group of 2 or 3: the unused bytes never pass)
-    if (PACK4) {
+    if (PACK4 && (!SLICED || sl.last)) {  // (the launch that tests the sums)
 #pragma unroll
         for (uint32_t j = 0; j < 4; j++)
             if (j < bt.n) {
@@ -522,6 +533,7 @@ __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const
     const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(out, 0, FILTER ? 0 : n_rows * 4u, 0x00020000);
     const __amdgpu_buffer_rsrc_t partial_rsrc =
         __builtin_amdgcn_make_buffer_rsrc(SLICED ? sl.partial : nullptr, 0, SLICED ? n_rows * 16u : 0, 0x00020000);
+    uint2 *carry = reinterpret_cast<uint2 *>(sl.partial);  // SLICED && PACK4: a row's four u16 sums over the slices so far
 
     // A block is 16 M contiguous bytes: 1024 of them go as one 16-byte piece per lane, the other 512 (M = 32: the only
     // 512, M = 96: the second round) as 8 bytes per lane - every lane loads and writes in every round, so the refill has no
@@ -536,6 +548,7 @@ __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const
         uint4 wide[kWide > 0 ? kWide : 1];
         uint2 half;
         float init;  // SLICED: the lane's sum so far for its row of the block
+        uint32_t c02, c13;  // SLICED && PACK4: the row's sums so far in lane 0 of its quad, 0 in the others
     };
     const uint32_t wave_u = __builtin_amdgcn_readfirstlane(gw), n_waves_u = __builtin_amdgcn_readfirstlane(n_waves);
     const uint32_t J_u = __builtin_amdgcn_readfirstlane(J), rs_u = __builtin_amdgcn_readfirstlane(rs);
@@ -559,7 +572,16 @@ __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const
             h.half = make_uint2(t.x, t.y);
         }
         h.init = 0.0f;
-        if (SLICED && !sl.first) h.init = sl.partial[((size_t)blk * 16u + q) * 4u + k];
+        h.c02 = h.c13 = 0u;
+        if (SLICED && PACK4) {
+            if (!sl.first) {  // (the quad's lanes ask for the same word: no branch on k, like the loads above)
+                const uint2 w = carry[(size_t)blk * 16u + q];
+                h.c02 = k == 0 ? w.x : 0u;
+                h.c13 = k == 0 ? w.y : 0u;
+            }
+        } else if (SLICED && !sl.first) {
+            h.init = sl.partial[((size_t)blk * 16u + q) * 4u + k];
+        }
     };
     auto refill = [&](const Held &h, uint32_t slot) {
         uint8_t *d = lds_raw + stage + slot * kSlot;
@@ -574,11 +596,14 @@ __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const
     };
     Held buf[D];  // buf[j % D] = block j
     float init_of[2];  // the initial sums of the blocks in the ring's slots
+    uint32_t init02_of[2], init13_of[2];
 #pragma unroll
     for (int j = 0; j < D; j++) request(buf[j], j);
     refill(buf[0], 0);
     init_of[0] = buf[0].init;
     init_of[1] = 0.0f;
+    init02_of[0] = buf[0].c02, init13_of[0] = buf[0].c13;
+    init02_of[1] = init13_of[1] = 0u;
     request(buf[0], D);
     // A step is two dependent LDS round trips (code byte, table entry) and an add.  Steps go in groups of eight through a
     // three-stage pipeline kept in this order by scheduling barriers - A(G + 1): ask for the next group's code bytes,
@@ -607,10 +632,12 @@ __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const
         for (int G = 0; G < NG; G++) {
             const int jj = G / GR, g = G % GR;
             float init_new = 0.0f;
+            uint32_t init02_new = 0u, init13_new = 0u;
             if (g == 0) {  // the slot of block j - 1 is free (its last reads went out with A of this group): block j + 1
                            // goes there, and its registers take block j + 1 + D
                 refill(buf[(jj + 1) % D], (jj + 1) & 1);
                 init_new = buf[(jj + 1) % D].init;
+                init02_new = buf[(jj + 1) % D].c02, init13_new = buf[(jj + 1) % D].c13;
                 request(buf[(jj + 1) % D], j0 + jj + 1 + D);
             }
             {  // A(G + 1)
@@ -644,8 +671,8 @@ __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const
                         if (PACK4) {
                             done02 = fin ? acc02 : done02;
                             done13 = fin ? acc13 : done13;
-                            acc02 = fin ? 0u : acc02;
-                            acc13 = fin ? 0u : acc13;
+                            acc02 = fin ? (SLICED ? init02_of[jjp & 1] : 0u) : acc02;  // (SLICED: lane 0 carries the slices before)
+                            acc13 = fin ? (SLICED ? init13_of[jjp & 1] : 0u) : acc13;
                         } else {
                             done = fin ? acc : done;
                             acc = fin ? (SLICED ? init_of[jjp & 1] : 0.0f) : acc;  // their next store row starts
@@ -672,12 +699,14 @@ __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const
                         }
                         const uint32_t row = (block_of(jb) * 16u + q) * (uint32_t)R + srow;
                         const bool live = started && jb < J && row < n_rows;  // (jb = -1, -2 as unsigned: the pipeline's first trips)
-                        if (SLICED && !sl.last) {  // the lane sums go back to `partial` for the next slice
+                        if (SLICED && PACK4 && !sl.last) {  // the quad's sums so far: one word per row for the next slice
+                            if (k == 0 && live) carry[row] = make_uint2(s02, s13);
+                        } else if (SLICED && !sl.last) {  // the lane sums go back to `partial` for the next slice
                             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(done), partial_rsrc, live ? (row * 4u + k) * 4u : 0xFFFFFFFFu, 0, 0);
                         } else if (PACK4) {
                             const bool p0 = (s02 & 0xFFFFu) >= thr[0], p1 = (s13 & 0xFFFFu) >= thr[1], p2 = (s02 >> 16) >= thr[2], p3 = (s13 >> 16) >= thr[3];
                             if (k == 0 && live && (p0 || p1 || p2 || p3)) {  // cold: about 2 * target of n rows per query
-                                const uint8_t *row_bytes = rows_b + (size_t)row * (uint32_t)(MROW / R);
+                                const uint8_t *row_bytes = SLICED ? pk.rows + (size_t)row * pk.row_stride : rows_b + (size_t)row * (uint32_t)(MROW / R);
                                 pack4_survivors(bt.fsl, (p0 ? 1u : 0u) | (p1 ? 2u : 0u) | (p2 ? 4u : 0u) | (p3 ? 8u : 0u), pk.luts, bt.lut_stride,
                                                 row_bytes, pk.m, row, wg);
                             }
@@ -705,7 +734,10 @@ __device__ __forceinline__ void skew_scan(const uint4 *__restrict__ rows4, const
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (g == 0) init_of[(jj + 1) & 1] = init_new;  // (after C: with one group per row time C still used the slot's old value)
+            if (g == 0) {  // (after C: with one group per row time C still used the slot's old value)
+                init_of[(jj + 1) & 1] = init_new;
+                init02_of[(jj + 1) & 1] = init02_new, init13_of[(jj + 1) & 1] = init13_new;
+            }
         }
     }
 }
@@ -718,11 +750,12 @@ __global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_skew_kernel(
 }
 
 // The filter pass of up to four queries (bt.n, bt.fsl, bt.lut_stride) through one packed table (SkewPack4 above).
-template <int NV, int R, int PAD>
+// SLICED: one slice of it - `rows4` the slice of the planar scan image, `table` the slice's [code][16 NV] dwords.
+template <int NV, int R, int PAD, bool SLICED = false>
 __global__ __launch_bounds__(64 * skew_waves(16 * NV)) void pq_scan_pack4_kernel(const uint4 *__restrict__ rows4,
                                                                   const uint32_t *__restrict__ table, uint32_t n_rows,
                                                                   SkewSlice sl, SkewBatch bt, SkewPack4 pk) {
-    skew_scan<NV, R, true, false, false, PAD, true>(rows4, reinterpret_cast<const float *>(table), n_rows, nullptr, TopkFilter{}, sl, bt, pk);
+    skew_scan<NV, R, true, SLICED, false, PAD, true>(rows4, reinterpret_cast<const float *>(table), n_rows, nullptr, TopkFilter{}, sl, bt, pk);
 }
 
 // ------------------------------------------------------------------------------ encode
@@ -889,12 +922,16 @@ __global__ __launch_bounds__(kBlock) void pq_lut_batch_kernel(const float *__res
 // Every workgroup works out the group's statistics itself - a wave per (query, chunk) for the extremes, then one thread per
 // query over the chunks in order, so all of them get the same doubles - and writes the table rows of kPack4Codes codes
 // (blockIdx.y); the entries come from the [code][chunk] copies, coalesced.
+// slice_per != 0 (rows of several LUT slices, ring = cols_real = m <= 256; pq_scan_pack4_kernel<SLICED>): the statistics run
+// over all m chunks as ever, and the 256 * m dwords of a table are written slice after slice - slice i holds the chunks from
+// i * slice_per on (plan_slices) as a contiguous [code][chunks of the slice] array, the LDS image of its launch.
 constexpr uint32_t kPack4Codes = 32;
 __global__ __launch_bounds__(kBlock) void pq_lut_pack4_kernel(const float *__restrict__ luts, const float *__restrict__ luts_t,
                                                              uint32_t n_queries, uint32_t m, uint32_t ring, uint32_t cols_real,
-                                                             uint32_t *__restrict__ tables, Pack4Query *__restrict__ params) {
-    __shared__ float s_mn[4][128], s_mx[4][128];
-    __shared__ uint32_t s_finite[4][128];
+                                                             uint32_t slice_per, uint32_t *__restrict__ tables,
+                                                             Pack4Query *__restrict__ params) {
+    __shared__ float s_mn[4][256], s_mx[4][256];
+    __shared__ uint32_t s_finite[4][256];
     __shared__ double s_step[2][4];  // per direction and query; 0: every entry 0 (a flagged query, an unused byte)
     const uint32_t group = blockIdx.x, q0 = 4u * group, nq = min(4u, n_queries - q0);
     const size_t per = (size_t)m * kCentroids;
@@ -940,8 +977,13 @@ __global__ __launch_bounds__(kBlock) void pq_lut_pack4_kernel(const float *__res
                 for (int d = 0; d < 2; d++)
                     if (s_step[d][j] > 0.0) word[d] |= pack4_entry(v, s_mn[j][c], s_mx[j][c], s_step[d][j], d) << (8u * j);
             }
-        tables[((size_t)(2u * group + 0u) * kCentroids + code) * ring + col] = word[0];
-        tables[((size_t)(2u * group + 1u) * kCentroids + code) * ring + col] = word[1];
+        size_t at = (size_t)code * ring + col;
+        if (slice_per) {
+            const uint32_t c0 = col / slice_per * slice_per, width = min(slice_per, m - c0);
+            at = (size_t)kCentroids * c0 + (size_t)code * width + (col - c0);
+        }
+        tables[(size_t)(2u * group + 0u) * kCentroids * ring + at] = word[0];
+        tables[(size_t)(2u * group + 1u) * kCentroids * ring + at] = word[1];
     }
 }
 
@@ -1805,10 +1847,18 @@ uint32_t pack4_ring(const qamd_pq *h) {
     const uint32_t ring_rows = skew_rows_per_ring_row(h);
     return ring_rows ? ring_rows * (uint32_t)h->m : skew_pad(h);
 }
-template <int NV, int R, int PAD> bool pack4_ready() {
+// pq_scan_pack4_kernel<SLICED>: rows of 160, 192, 224 or 256 chunks that the store keeps as a planar scan image (two slices:
+// 128 + 32, 96 + 96, 128 + 96, 128 + 128).  256 chunks is where the 16-bit fields end (256 * 255 = 65280); longer rows keep
+// SkewBatch.  The columns of a packed table = m; 0: no packed tables.  The same switch and the same whole-device rule as above.
+uint32_t pack4_sliced(const qamd_pq *h) {
+    static const bool on = [] { const char *e = dev_env("QAMD_PQ_PACK4"); return !(e && e[0] == '0'); }();
+    if (!on || !skew_sliced_capable(h) || device_info().cu_count != 256 || h->m > 256) return 0;
+    return (uint32_t)h->m;
+}
+template <int NV, int R, int PAD, bool SLICED = false> bool pack4_ready() {
     static DeviceOnce once;
     const qamd_status st = once.run([] {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&pq_scan_pack4_kernel<NV, R, PAD>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&pq_scan_pack4_kernel<NV, R, PAD, SLICED>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)skew_lds_bytes(16 * NV)) != hipSuccess) {
             (void)hipGetLastError();
             g_skew_unusable.store(true, std::memory_order_relaxed);
@@ -1840,6 +1890,39 @@ qamd_status launch_pack4(const qamd_pq *h, const uint32_t *table, const SkewBatc
         default: return QAMD_OK;
     }
 #undef QAMD_PQ_PACK4
+    QAMD_HIP(hipGetLastError());
+    *done = true;
+    return QAMD_OK;
+}
+// The same for rows of several slices (pack4_sliced): one launch per slice of the planar image, `table` the group's slice
+// tables one after the other; between the launches a row's sums wait in 8 bytes of workspace.  An error if that cannot be had.
+qamd_status launch_pack4_sliced(const qamd_pq *h, const uint32_t *table, const SkewBatch &bt, SkewPack4 pk, hipStream_t s, bool *done) {
+    *done = false;
+    auto ready = [](uint32_t nv) {
+        return nv == 2 ? pack4_ready<2, 1, 0, true>() : nv == 6 ? pack4_ready<6, 1, 0, true>() : nv == 8 && pack4_ready<8, 1, 0, true>();
+    };
+    for (uint32_t c : h->slice_chunks)
+        if (!ready(c / 16)) return QAMD_OK;
+    const uint64_t n = h->count;
+    const int grid = (int)std::min<uint64_t>(device_info().cu_count, (n + 1023) / 1024);
+    pk.rows = h->rows.as<uint8_t>();
+    pk.row_stride = (uint32_t)h->ds;
+    float *carry = nullptr;
+    QAMD_TRY(thread_ws_acquire(WS_PARTIAL, h->padded * 8, s, reinterpret_cast<void **>(&carry)));
+    const size_t ns = h->slice_chunks.size();
+    for (size_t sl = 0; sl < ns; sl++) {
+        const uint32_t chunk0 = h->slice_chunk0[sl], chunks = h->slice_chunks[sl];
+        const SkewSlice ss{chunk0, (uint32_t)h->m, sl == 0, sl + 1 == ns, carry, skew_run_shift(n, 1, grid, chunks)};
+        const uint4 *slice = reinterpret_cast<const uint4 *>(h->planar.as<uint8_t>() + (uint64_t)chunk0 * h->padded);
+#define QAMD_PQ_PACK4_SLICE(NVV)                                                                                                \
+    case NVV:                                                                                                                  \
+        hipLaunchKernelGGL((pq_scan_pack4_kernel<NVV, 1, 0, true>), dim3(grid), dim3(64 * skew_waves(16 * NVV)), skew_lds_bytes(16 * NVV), s, \
+                           slice, table + (size_t)kCentroids * chunk0, (uint32_t)n, ss, bt, pk);                               \
+        break;
+        switch (chunks / 16) { QAMD_PQ_PACK4_SLICE(2) QAMD_PQ_PACK4_SLICE(6) QAMD_PQ_PACK4_SLICE(8) }
+#undef QAMD_PQ_PACK4_SLICE
+    }
+    thread_ws_release(WS_PARTIAL, s);
     QAMD_HIP(hipGetLastError());
     *done = true;
     return QAMD_OK;
@@ -3113,7 +3196,8 @@ qamd_status qamd_pq_upsert(qamd_pq *h, uint64_t first_row, const float *data, qa
 // launch and then ENQUEUES the per-query scans back to back: no per-query allocation, no per-query
 // synchronisation (fused_topk_batch reads the statuses back once per 32 queries).  The FILTER pass of
 // topk_batch only has to reject rows: there four queries share a pass through one packed 8-bit table
-// (pq_scan_pack4_kernel).  Every score and every list is bit-identical to the single-query calls.
+// (pq_scan_pack4_kernel; rows of 160 .. 256 chunks slice by slice).  Every score and every list is bit-identical to the
+// single-query calls.
 struct qamd_pq_query_batch {
     int device = 0;
     uint64_t m = 0, n_queries = 0;
@@ -3122,6 +3206,7 @@ struct qamd_pq_query_batch {
     const float *lut_t(uint64_t q) const { return transposed ? luts.as<float>() + (n_queries + q) * m * kCentroids : nullptr; }
     // The packed filter tables of topk_batch (pq_lut_pack4_kernel), when the store takes pq_scan_pack4_kernel: per group of four
     // queries and search direction 256 * pack4_ring dwords, then the [2][n_queries] Pack4Query.  pack4_ring == 0: none.
+    // (A store of several slices, pq_scan_pack4_kernel<SLICED>: pack4_ring = m, the 256 * m dwords slice after slice.)
     DevBuf pack4;
     uint32_t pack4_ring = 0;
     uint64_t pack4_groups() const { return n_queries / 4 + (n_queries % 4 >= 2 ? 1 : 0); }  // (a last group of one takes the single scan)
@@ -3158,7 +3243,8 @@ qamd_status qamd_pq_encode_query_batch(const qamd_pq *h, const float *queries, u
     b->m = h->m;
     b->n_queries = n_queries;
     b->transposed = with_t;
-    b->pack4_ring = n_queries >= 2 && fast_capable(h, h->count) ? pack4_ring(h) : 0;
+    const uint32_t sliced4 = pack4_sliced(h);
+    b->pack4_ring = n_queries >= 2 && fast_capable(h, h->count) ? (sliced4 ? sliced4 : pack4_ring(h)) : 0;
     if (b->pack4_ring) {
         const size_t bytes = 2 * b->pack4_groups() * kCentroids * b->pack4_ring * sizeof(uint32_t) + 2 * n_queries * sizeof(Pack4Query);
         if (b->pack4.bytes < bytes) QAMD_TRY(b->pack4.alloc(bytes));
@@ -3176,7 +3262,8 @@ qamd_status qamd_pq_encode_query_batch(const qamd_pq *h, const float *queries, u
             const uint32_t ring_rows = skew_rows_per_ring_row(h);
             hipLaunchKernelGGL(pq_lut_pack4_kernel, dim3((uint32_t)b->pack4_groups(), kCentroids / kPack4Codes), dim3(kBlock), 0, s,
                                b->luts.as<float>(), b->luts.as<float>() + per * n_queries, (uint32_t)n_queries, (uint32_t)h->m,
-                               b->pack4_ring, ring_rows ? ring_rows * (uint32_t)h->m : (uint32_t)h->m, b->pack4.as<uint32_t>(),
+                               b->pack4_ring, ring_rows ? ring_rows * (uint32_t)h->m : (uint32_t)h->m,
+                               sliced4 ? h->slice_chunks[0] : 0u, b->pack4.as<uint32_t>(),
                                const_cast<Pack4Query *>(b->pack4_params(0, 0)));
         }
         QAMD_HIP(hipGetLastError());
@@ -3293,10 +3380,12 @@ qamd_status qamd_pq_topk_batch(const qamd_pq *h, const qamd_pq_query_batch *b, u
     const bool side = b->transposed && fast_capable(h, h->count) && device_info().cu_count == 256 && h->count >= (1u << 20) && !(eside && eside[0] == '0');
     // Before that, groups of four queries (the batch's last: 2 or 3) in ONE pass through their packed 8-bit table
     // (pq_scan_pack4_kernel): the batch must carry the tables of this store's ring row (encode_query_batch made them).
-    const bool pack4 = b->pack4_ring != 0 && b->pack4_ring == pack4_ring(h) && fast_capable(h, h->count);
+    // Rows of 160 .. 256 chunks in a planar scan image: the same pass slice by slice (pq_scan_pack4_kernel<SLICED>).
+    const uint32_t sliced4 = pack4_sliced(h);
+    const bool pack4 = b->pack4_ring != 0 && b->pack4_ring == (sliced4 ? sliced4 : pack4_ring(h)) && fast_capable(h, h->count);
     scan.filter_name = qamd_pq_scan_kernel(h, nullptr);
     if (pack4 || side)
-        scan.scan_filter_multi = [&, pack4, side](uint32_t q, uint32_t avail, const TopkFilterSlices &fsl, hipStream_t st, qamd_status &status) -> uint32_t {
+        scan.scan_filter_multi = [&, pack4, side, sliced4](uint32_t q, uint32_t avail, const TopkFilterSlices &fsl, hipStream_t st, qamd_status &status) -> uint32_t {
             if (pack4 && q % 4 == 0 && std::min<uint64_t>(avail, 4) == std::min<uint64_t>(b->n_queries - q, 4) && avail >= 2) {
                 SkewBatch four{};
                 four.n = std::min(avail, 4u);
@@ -3304,8 +3393,9 @@ qamd_status qamd_pq_topk_batch(const qamd_pq *h, const qamd_pq_query_batch *b, u
                 four.fsl = fsl;
                 const SkewPack4 pk{b->pack4_params(q, largest), luts + q * per, (uint32_t)h->m};
                 bool done = false;
-                status = launch_pack4(h, b->pack4_table(q / 4, largest), four, pk, st, &done);
-                if (status == QAMD_OK && done) scan.filter_multi_name = "pq_scan_pack4_kernel";
+                status = sliced4 ? launch_pack4_sliced(h, b->pack4_table(q / 4, largest), four, pk, st, &done)
+                                 : launch_pack4(h, b->pack4_table(q / 4, largest), four, pk, st, &done);
+                if (status == QAMD_OK && done) scan.filter_multi_name = sliced4 ? "pq_scan_pack4_kernel<SLICED>" : "pq_scan_pack4_kernel";
                 if (status != QAMD_OK || done) return status == QAMD_OK ? four.n : 0u;
             }
             if (!side) return 0;

@@ -1,5 +1,5 @@
 // The arithmetic of the packed 8-bit filter tables of the PQ batch top-k (pq.hip: pq_lut_pack4_kernel builds them,
-// pq_scan_pack4_kernel scans with them).  Plain C++17 for host and device, so that the bound can be checked on a CPU
+// pq_scan_pack4_kernel scans with them - rows of up to 128 chunks whole, rows of 160 .. 256 chunks slice by slice).  Plain C++17 for host and device, so that the bound can be checked on a CPU
 // (tests/cpu/pq_pack4_bound.cpp).
 //
 // A filter pass only has to REJECT rows safely; the exact f32 score of the few survivors decides.  One byte per table entry
@@ -11,7 +11,8 @@
 //   step    = max_c (max_code L'[c] - lo[c]) / 255      ONE step per query, so that integer sums add up
 //   e[c][code] = ceil((L'[c][code] - lo[c]) / step), clamped to 0 .. 255
 // so that  sum_c L'[c][code_c]  <=  base + step * (sum_c e[c][code_c] + eps)  in real numbers: the double roundings of the
-// quotient (and a clamp of 255 + a rounding) lose less than 255 * 2^-51 of a step per chunk, eps < 1e-10 for m <= 128.
+// quotient (and a clamp of 255 + a rounding) lose less than 255 * 2^-51 of a step per chunk, eps < 1e-10 for m <= 256
+// (256 * 255 * 2^-51 = 2.9e-11; the sum of a row's per-slice integer sums IS the row's sum, so slices change nothing here).
 // The reference adds the m entries in f32, four lane sums of m / 4 terms and two combining adds: its score is within
 //   slack = (m / 4 + 3) * 2^-24 * sum_c max_code |L[c][code]|
 // of the real sum (first order (m / 4 + 1) u sum |x|; the two spare units cover the higher orders and the double roundings
@@ -33,7 +34,7 @@
 
 namespace qamd {
 
-constexpr uint32_t kPack4Never = 0xFFFFFFFFu;  // a threshold no sum of at most 128 * 255 reaches
+constexpr uint32_t kPack4Never = 0xFFFFFFFFu;  // a threshold no sum of at most 256 * 255 = 65280 (a 16-bit field) reaches
 
 struct Pack4Query {  // per (query, direction), four doubles in memory
     double base, step, slack, bad;  // bad != 0: the query cannot be bounded
