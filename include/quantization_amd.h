@@ -1096,7 +1096,18 @@ QAMD_API qamd_status qamd_f32_rerank(const qamd_f32 *h, const float *query, uint
  * apply.  The queries go in groups of up to 8 that share one pass over the rows; a group's scores take
  * group * n_ids * 4 bytes of the calling thread's score workspace, and the group shrinks, down to 1 query, so that
  * this stays within 512 MiB (more only when one query's n_ids * 4 bytes alone exceed it) -- never
- * n_queries * n_ids. */
+ * n_queries * n_ids.
+ *
+ * The matrix-core route of the null-list form (answers unchanged, bit for bit): an f16 or bf16 store with the Dot
+ * metric (either `invert`, either `largest`), n_queries >= 16, n_ids >= 32768, k <= 1024, dim % 8 == 0, dim <= 65536
+ * and a 16-byte aligned base takes one bf16 / f16 MFMA filter pass over the rows shared by all queries; the rows it
+ * cannot prove worse than the exact k-th best of a sample of S = max(8192, 4 k n_ids / 8192) rows go, 8192 ids per query
+ * at most, through the list form's exact re-rank.  The route is not taken when S exceeds max(8192, n_ids / 8) (k above
+ * 256 on a large store): scoring the sample would cost what the groups of 8 cost.  Workspace, from the calling thread's
+ * rescoring workspace, in chunks of up to 1024 queries kept within 384 MiB: per query the list of 8192 ids, its 8192
+ * exact scores, S sample ids and S sample scores, and dim * 2 bytes of the rounded query.  A query with an infinite or
+ * NaN value (or, for f16, a value that overflows f16), a query whose list overflowed, and every query when the store
+ * holds an infinite or NaN value are answered by the groups of 8 above.  This route synchronises `stream`. */
 QAMD_API qamd_status qamd_f32_rerank_batch(const qamd_f32 *h, const float *queries, uint64_t n_queries,
                                            uint64_t qdim, qamd_mem queries_mem, const uint32_t *ids,
                                            uint32_t n_ids, qamd_mem ids_mem, uint32_t k, int largest,

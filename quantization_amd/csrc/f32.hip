@@ -212,14 +212,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     if (in_range) out[p] = valid ? (invert ? -sum : sum) : __builtin_nanf("");
 }
 
-// f32 -> f16 / bf16: round to nearest even, overflow to +-inf, NaN stays NaN, subnormal results kept.
-template <int DTYPE> __device__ __forceinline__ uint32_t narrow(float x) {
-    if (DTYPE == QAMD_DTYPE_F16) return __builtin_bit_cast(uint16_t, (_Float16)x);  // v_cvt_f16_f32 in the default mode
-    const uint32_t u = __float_as_uint(x);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x0040u;  // a NaN whose payload sits in the low bits stays one
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;                    // the carry out of the mantissa is the overflow to inf
-}
-
 // dst[i] = narrow(src[i]), i < n.  VEC: src is 16-byte and dst 8-byte aligned.
 template <int DTYPE, bool VEC>
 __global__ __launch_bounds__(kBlock) void narrow_kernel(const float *__restrict__ src, uint16_t *__restrict__ dst, uint64_t n) {
@@ -350,32 +342,41 @@ qamd_status rerank_scan(const qamd_f32 *h, const float *queries, uint64_t n_quer
         ids_dev = res.as<uint32_t>();
         sc_dev = reinterpret_cast<float *>(ids_dev + n_out);
     }
-    float *scores = nullptr;
-    QAMD_TRY(thread_ws_acquire(WS_SCORES, (size_t)group * n_rows * 4, s, reinterpret_cast<void **>(&scores)));
-    void *sel = nullptr;
-    qamd_status st = thread_ws_acquire(WS_SELECT, round_up(topk_workspace_bytes(k), 256), s, &sel);
-    if (st != QAMD_OK) {
+    // the scan route for the queries first .. first + count - 1: groups share a pass over the rows and the score workspace
+    auto scan_route = [&](uint64_t first, uint64_t count) -> qamd_status {
+        float *scores = nullptr;
+        QAMD_TRY(thread_ws_acquire(WS_SCORES, (size_t)group * n_rows * 4, s, reinterpret_cast<void **>(&scores)));
+        void *sel = nullptr;
+        qamd_status st = thread_ws_acquire(WS_SELECT, round_up(topk_workspace_bytes(k), 256), s, &sel);
+        if (st != QAMD_OK) {
+            thread_ws_release(WS_SCORES, s);
+            return st;
+        }
+        for (uint64_t q0 = first; q0 < first + count && st == QAMD_OK; q0 += group) {  // the score workspace is reused in stream order
+            const uint32_t g = (uint32_t)std::min<uint64_t>(group, first + count - q0);
+            st = f32_scan_launch(h, q_dev + q0 * qdim, g, n_rows, scores, n_rows, s);
+            for (uint32_t j = 0; j < g && st == QAMD_OK; j++)
+                st = topk_f32(scores + (size_t)j * n_rows, n_rows, k, largest != 0, ids_dev + (q0 + j) * k, sc_dev + (q0 + j) * k, sel, s);
+        }
+        thread_ws_release(WS_SELECT, s);
         thread_ws_release(WS_SCORES, s);
         return st;
-    }
-    for (uint64_t q0 = 0; q0 < n_queries && st == QAMD_OK; q0 += group) {  // the score workspace is reused in stream order
-        const uint32_t g = (uint32_t)std::min<uint64_t>(group, n_queries - q0);
-        st = f32_scan_launch(h, q_dev + q0 * qdim, g, n_rows, scores, n_rows, s);
-        for (uint32_t j = 0; j < g && st == QAMD_OK; j++)
-            st = topk_f32(scores + (size_t)j * n_rows, n_rows, k, largest != 0, ids_dev + (q0 + j) * k, sc_dev + (q0 + j) * k, sel, s);
-    }
-    bool synced = false;
+    };
+    uint32_t sample = 0, chunk = 0;
+    qamd_status st;
+    if (f32_mfma_plan(h, n_queries, n_rows, k, &sample, &chunk))  // f16 / bf16 Dot batches: the matrix-core filter (f32_mfma.hip)
+        st = f32_mfma_topk_batch(h, q_dev, (uint32_t)n_queries, n_rows, k, largest, sample, chunk, ids_dev, sc_dev, s,
+                                 [&](uint32_t q0, uint32_t n) { return scan_route(q0, n); });
+    else
+        st = scan_route(0, n_queries);
     if (st == QAMD_OK && out_mem == QAMD_MEM_HOST) {
         std::vector<uint32_t> host(2 * n_out);
         st = copy_out(host.data(), QAMD_MEM_HOST, ids_dev, n_out * 8, s);  // synchronises `s`
         if (st == QAMD_OK) {
             memcpy(out_ids, host.data(), n_out * 4);
             memcpy(out_scores, host.data() + n_out, n_out * 4);
-            synced = true;
         }
     }
-    thread_ws_release(WS_SELECT, s, synced);
-    thread_ws_release(WS_SCORES, s, synced);
     return st;
 }
 
@@ -420,6 +421,11 @@ qamd_status rerank_any(const qamd_f32 *h, const float *queries, uint64_t n_queri
 }
 
 }  // namespace
+
+qamd_status rescore_pairs_launch(const qamd_f32 *orig, const float *queries_dev, uint32_t n_queries, uint32_t n_ids,
+                                 const uint32_t *ids_dev, float *out_dev, hipStream_t s) {
+    return pairs_launch(orig, queries_dev, nullptr, n_queries, n_ids, ids_dev, (uint64_t)n_queries * n_ids, out_dev, s);
+}
 
 qamd_status rescore_queries_view(const float *queries, uint64_t n_floats, qamd_mem mem, StreamBuf &stage, hipStream_t s,
                                  const float **out) {
@@ -677,6 +683,7 @@ qamd_status qamd_f32_upsert(qamd_f32 *h, uint64_t first_row, const void *data, q
     }
     QAMD_HIP(hipStreamSynchronize(s));
     h->vp.count = std::max(h->vp.count, end);
+    if (h->dtype != QAMD_DTYPE_F32) f32_mfma_fold_amax(h, first_row, n_rows, s);
     return QAMD_OK;
 }
 

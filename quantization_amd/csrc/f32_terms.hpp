@@ -22,4 +22,12 @@ template <int DTYPE> __device__ __forceinline__ float widen_hi(uint32_t w) {
     return __uint_as_float(w & 0xFFFF0000u);
 }
 
+// f32 -> f16 / bf16: round to nearest even, overflow to +-inf, NaN stays NaN, subnormal results kept.
+template <int DTYPE> __device__ __forceinline__ uint32_t narrow(float x) {
+    if (DTYPE == QAMD_DTYPE_F16) return __builtin_bit_cast(uint16_t, (_Float16)x);  // v_cvt_f16_f32 in the default mode
+    const uint32_t u = __float_as_uint(x);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x0040u;  // a NaN whose payload sits in the low bits stays one
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;                    // the carry out of the mantissa is the overflow to inf
+}
+
 }  // namespace qamd

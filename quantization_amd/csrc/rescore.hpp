@@ -6,8 +6,15 @@
 // (demos/src/ann_benchmark_data.rs:151-185 measures exactly what that step recovers).
 #pragma once
 
+#include <atomic>
+#include <functional>
+
 #include "common.hpp"
 #include "topk_device.hpp"
+
+namespace qamd {
+constexpr uint32_t kAmaxUnknown = 0xFFFFFFFFu;  // (a NaN pattern: no magnitude has it)
+}
 
 // The originals: count x dim values of `dtype` (f32, or f16 / bf16 as 16-bit patterns), row-major, in HBM of
 // `device`.  `data` is `owned.ptr` (borrow = 0) or the caller's pointer (borrow = 1: the caller keeps it alive).
@@ -18,6 +25,9 @@ struct qamd_f32 {
     const void *data = nullptr;
     qamd::DevBuf owned;
     uint64_t capacity = 0;  // rows `owned` has room for: count after from_data, more after reserve / upsert
+    // f16 / bf16: an upper bound of max |x| over the rows as f32 bits (+inf when a value is infinite or a NaN), computed by
+    // the first matrix-core topk_batch (f32_mfma.hip) and folded over the rows every upsert writes; never lowered.
+    mutable std::atomic<uint32_t> amax_bits{qamd::kAmaxUnknown};
 };
 
 namespace qamd {
@@ -44,6 +54,22 @@ qamd_status rerank_device(const qamd_f32 *orig, const float *queries_dev, uint32
 // The rows are read once per 8 queries (a remainder in passes of 4, 2, 1).  Device memory; only enqueues on `s`.
 qamd_status f32_scan_launch(const qamd_f32 *orig, const float *queries_dev, uint32_t n_queries, uint64_t n_rows, float *out_dev,
                             uint64_t pitch, hipStream_t s);
+
+// out_dev[q * n_ids + i] = the exact score of query q and row ids_dev[q * n_ids + i] (the pair kernels of f32.hip; NaN for an
+// id >= count).  Device memory; only enqueues on `s`.
+qamd_status rescore_pairs_launch(const qamd_f32 *orig, const float *queries_dev, uint32_t n_queries, uint32_t n_ids,
+                                 const uint32_t *ids_dev, float *out_dev, hipStream_t s);
+
+// The matrix-core route of a null-list qamd_f32_rerank_batch (f32_mfma.hip).  f32_mfma_plan is its gate: true when the call
+// takes the route, with the sample size and the queries per workspace chunk.  f32_mfma_topk_batch writes the k best of the
+// rows 0 .. n_rows - 1 for every query into ids_dev / sc_dev [n_queries][k] (device); `scan_route(q0, n)` must answer the
+// queries q0 .. q0 + n - 1 into the same arrays by the scan route (the queries the filter cannot serve).  Synchronises `s`.
+bool f32_mfma_plan(const qamd_f32 *orig, uint64_t n_queries, uint32_t n_rows, uint32_t k, uint32_t *sample, uint32_t *chunk);
+qamd_status f32_mfma_topk_batch(const qamd_f32 *orig, const float *queries_dev, uint32_t n_queries, uint32_t n_rows, uint32_t k,
+                                int largest, uint32_t sample, uint32_t chunk, uint32_t *ids_dev, float *sc_dev, hipStream_t s,
+                                const std::function<qamd_status(uint32_t q0, uint32_t n)> &scan_route);
+// upsert: folds max |x| of the rows just written into the handle's bound, when it has one.  Synchronises `s`.
+void f32_mfma_fold_amax(qamd_f32 *orig, uint64_t first_row, uint64_t n_rows, hipStream_t s);
 
 // `queries` ([n_queries][dim] f32, host or device) as device memory: used in place, or staged into `stage`.
 qamd_status rescore_queries_view(const float *queries, uint64_t n_floats, qamd_mem mem, StreamBuf &stage, hipStream_t s,

@@ -232,8 +232,9 @@ class OriginalVectors:
         return ret_ids, ret_sc
 
     def topk_batch(self, queries, k: int, largest: bool = True, out_ids=None, out_scores=None, stream=None):
-        """topk for queries [n_queries, dim]: up to 8 queries share each pass over the rows.  Returns [n_queries, k]
-        ids and scores."""
+        """topk for queries [n_queries, dim]: up to 8 queries share each pass over the rows.  f16 / bf16 Dot batches of
+        16 or more queries take the matrix cores (one filter pass, then the exact score of its survivors): answers are
+        unchanged.  Returns [n_queries, k] ids and scores."""
         check_same_device(self._device, out_ids, out_scores)
         nq, qdim = int(queries.shape[0]), int(queries.shape[1])
         qb = self._query(queries)
