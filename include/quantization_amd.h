@@ -117,8 +117,9 @@ enum { QAMD_FULL = 64,     /* flag: full-range byte codes, 255 levels; the legal
  * qamd_u8_reserve write the image tile by tile through a staging buffer of byte codes; pairs and bursts gather a row's
  * pieces from the image, exports and qamd_u8_save unpack it (the files hold the reference's byte rows and the base
  * metric, then "bits":4, then a last key "compact":true - the only value qamd_u8_load accepts for it, and only beside
- * "bits":4; a file without the key is not compact), and query batches take one image scan per query: the matrix cores
- * read byte codes.  Refused with QAMD_ERR_ARGUMENTS before any device call: the flag without QAMD_BITS4, with QAMD_L1,
+ * "bits":4; a file without the key is not compact), and query batches read the image too: up to 17 queries share passes of
+ * 8 on the vector ALU, and from 18 queries on (qamd_u8_score_batch, qamd_u8_topk_batch and its rescored form, the null id
+ * list of qamd_u8_score_internal_ids_batch) the int8 matrix cores take their row fragments straight from it.  Refused with QAMD_ERR_ARGUMENTS before any device call: the flag without QAMD_BITS4, with QAMD_L1,
  * with any unknown bit, with an actual_dim that has no nibble image (below 32 or above 2048), and on every qamd_pq_*,
  * qamd_bin_*, qamd_f32_* and qamd_*_sharded_* constructor.  A build whose image cannot be allocated fails with
  * QAMD_ERR_DEVICE (there are no byte codes to fall back to), and qamd_u8_from_rows of a row with a code above 15 with

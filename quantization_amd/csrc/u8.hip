@@ -1093,6 +1093,7 @@ bool launch_image_multi(const qamd_u8 *h, uint32_t nq_valid, const uint8_t *qcod
     h->last_scan_packed.store(h->image.kind, std::memory_order_relaxed);
     h->last_scan_split.store((int)split, std::memory_order_relaxed);
     h->last_scan_queries.store((int)nq_valid, std::memory_order_relaxed);
+    h->last_compact_batch.store(0, std::memory_order_relaxed);
     auto go = [&](auto nq) {
         with_bool(slices != nullptr, [&](auto fi) {
             with_epi(e.mode, [&](auto epi) {
@@ -1439,6 +1440,9 @@ qamd_status score_internal_rows_dev(const qamd_u8 *h, const uint32_t *rows_dev, 
     // A full-range store: more rows than the multi-query scan takes go to the matrix cores, 15 per pass
     if (h->full_range && h->meta.vector_parameters.distance_type != QAMD_L1 && n >= u8_full_batch_min(h))
         return u8_full_batch_scores(h, qcodes, pitch, q_offs, n, n_ids, out_dev, n_ids, EPI_INTERNAL, e.diff, s);
+    // A compact store: from its gate on, the unpacked rows are the queries of u8_compact_batch_kernel
+    if (const uint32_t cmin = u8_compact_batch_min(h); cmin && n >= cmin)
+        return u8_compact_batch_scores(h, qcodes, pitch, q_offs, n, n_ids, out_dev, n_ids, EPI_INTERNAL, e.diff, s);
     const uint32_t width = pass_width(h);
     for (uint32_t l = 0; l < n;) {
         const uint32_t nq = std::min(width, n - l);
@@ -1706,6 +1710,22 @@ uint32_t u8_multi_width(const qamd_u8 *h) { return multi_width(h); }
 // batches share passes over the nibble image instead (u8_scan_image_multi_kernel, pass_width).
 bool u8_batch_by_scans(const qamd_u8 *h) { return lane_order(h) || h->compact; }
 
+// The one gate of u8_compact_batch_kernel: a compact Dot / L2 store whose multiplier the integer pre-filter
+// can divide by sends batches of kCompactBatchMin queries and more to the matrix cores; smaller ones keep the image passes
+// (the measured crossover is in DESIGN 3.1z).  QAMD_DEV_U8_COMPACT_MIN (developer library) overrides the constant; 0
+// switches the route off.
+constexpr uint32_t kCompactBatchMin = 18;
+uint32_t u8_compact_batch_min(const qamd_u8 *h) {
+    static const uint32_t gate = [] {
+        const char *e = dev_env("QAMD_DEV_U8_COMPACT_MIN");
+        return e && *e ? (uint32_t)strtoul(e, nullptr, 10) : kCompactBatchMin;
+    }();
+    const float m = h->meta.multiplier;
+    if (!h->compact || h->image.kind != U8_IMAGE_NIBBLE || h->meta.vector_parameters.distance_type == QAMD_L1) return 0;
+    if (!(fabsf(m) < __builtin_huge_valf()) || m == 0.0f) return 0;
+    return gate;
+}
+
 // out[j * count + row] for queries [0, n_queries) of a batch through the multi-query scan (groups of
 // `width`, then smaller groups, then single scans).
 qamd_status u8_score_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t pitch, const float *offsets_dev,
@@ -1923,6 +1943,17 @@ extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_full_filt
 }
 extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_full_redone(const qamd_u8 *h) {
     return h->last_full_redone.load(std::memory_order_relaxed);
+}
+// Queries u8_compact_batch_kernel served in the store's last batch call (0: the image passes served it), the queries of its
+// last topk_batch that went through the kernel's filter form, and how many of those were then redone exactly.
+extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_compact_batch(const qamd_u8 *h) {
+    return h->last_compact_batch.load(std::memory_order_relaxed);
+}
+extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_compact_filter(const qamd_u8 *h) {
+    return h->last_compact_filter.load(std::memory_order_relaxed);
+}
+extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_compact_redone(const qamd_u8 *h) {
+    return h->last_compact_redone.load(std::memory_order_relaxed);
 }
 extern "C" __attribute__((visibility("default"))) int qamd_dev_u8_last_scan_packed(const qamd_u8 *h) {
     return h->last_scan_packed.load(std::memory_order_relaxed);

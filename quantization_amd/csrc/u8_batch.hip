@@ -2380,10 +2380,18 @@ qamd_status qamd_u8_score_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, 
         if (out_mem == QAMD_MEM_HOST) QAMD_TRY(copy_out(out, QAMD_MEM_HOST, out_dev, total * 4, s));
         return QAMD_OK;
     }
+    // A compact store from its gate on: the int8 matrix cores straight from the nibble image
+    // (u8_compact_batch_kernel); smaller batches share the image passes below.
+    if (const uint32_t cmin = u8_compact_batch_min(h); cmin && b->n_queries >= cmin) {
+        QAMD_TRY(u8_compact_batch_scores(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)b->n_queries, h->count,
+                                         out_dev, h->count, 0, 0.0f, s));
+        if (out_mem == QAMD_MEM_HOST) QAMD_TRY(copy_out(out, QAMD_MEM_HOST, out_dev, total * 4, s));
+        return QAMD_OK;
+    }
     const U8GemmRoute route = gemm_route(h, b, U8GemmPass::Score, h->count);
     // (from three queries on the row-streaming MFMA kernel streams the rows as fast and does not slow down per query)
     // Lane mode 1 (Dot, L2): the matrix cores sum exactly, so every query takes the lane-order scan (width 0).  A compact
-    // store has no byte codes for the matrix cores to read: every query takes the image scan.
+    // store below its gate: no byte codes for these kernels to read, every query takes the image scan.
     if (h->meta.vector_parameters.distance_type == QAMD_L1 || u8_batch_by_scans(h) ||
         (width && b->n_queries >= 2 && b->n_queries <= width && (b->n_queries == 2 || !route.rs_ok))) {
         // sum |q - v| is not a contraction (no MFMA form), and for a handful of queries the vector-ALU
@@ -2473,7 +2481,71 @@ qamd_status qamd_u8_topk_batch(const qamd_u8 *h, const qamd_u8_query_batch *b, u
         }
         return QAMD_OK;
     }
-    if (u8_batch_by_scans(h) || h->full_range)  // a full-range store its kernel does not take (a small batch; from the gate on, rows past 8256 bytes or an unusable multiplier): the scans' filter passes (no signed form can read it); lane mode 1 (Dot, L2): per-query lane-order scans, never the exact-sum matrix cores; compact: image scans
+    h->last_compact_batch.store(0, std::memory_order_relaxed);
+    h->last_compact_filter.store(0, std::memory_order_relaxed);
+    h->last_compact_redone.store(0, std::memory_order_relaxed);
+    const uint32_t cmin = u8_compact_batch_min(h);
+    if (cmin && Q >= cmin && n >= kFilterGateRows) {
+        // A compact store from its batch gate and the filter gate on: the full-range sequence above with
+        // u8_compact_batch_kernel in both places and a pivot sample that is itself a small blocked nibble image.
+        const BatchSamplePlan plan = batch_sample_plan(n, Q, k);
+        const uint32_t S = plan.S, r = plan.r;
+        if (r <= 64) {
+            BatchTopkOutputs out;
+            QAMD_TRY(out.begin(Q, k, out_ids, out_scores, out_mem, s));
+            BatchTopkPass pass(n, Q, b->q_pad, k, largest, 0, 0, s);
+            const void *s_image = nullptr;
+            const float *s_offs = nullptr;
+            const bool cached = S <= plan.rows_all && u8_compact_sample_store(h, plan.rows_all, s, &s_image, &s_offs) == QAMD_OK;
+            const size_t o_image = pass.reserve(cached ? 16 : u8_compact_sample_bytes(h, S));
+            const size_t o_offs = pass.reserve(cached ? 16 : ((uint64_t)S + 64) * 4);
+            const size_t o_images = pass.reserve(u8_compact_images_bytes(h, (uint32_t)Q));
+            const size_t o_scores = pass.reserve(Q * (uint64_t)S * 4);
+            QAMD_TRY(pass.alloc());
+            if (!cached) {
+                QAMD_TRY(u8_compact_sample_gather(h, S, pass.at<uint8_t>(o_image), pass.at<float>(o_offs), s));
+                s_image = pass.at<uint8_t>(o_image);
+                s_offs = pass.at<float>(o_offs);
+            }
+            U8CompactImages images;
+            QAMD_TRY(u8_compact_images_build(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)Q,
+                                             pass.at<uint8_t>(o_images), s, &images));
+            float *s_scores = pass.at<float>(o_scores);
+            QAMD_TRY(u8_compact_batch_scores_of(h, images, s_image, s_offs, S, s_scores, S, 0, 0.0f, s));
+            pass.pivots(s_scores, S, S, r);
+            QAMD_TRY(u8_compact_batch_filter(h, images, pass.pivot_scores(), pass.counters(), pass.candidates(), largest, s));
+            QAMD_TRY(pass.emit(out.ids_dev, out.sc_dev));
+            QAMD_TRY(pass.read_status(out.status));
+            pass.debug_line("[qamd topk_batch]", r, "u8_compact_batch_kernel", "", out.status);
+            const int filtered = (int)Q;
+            const int redone = (int)std::count_if(out.status.begin(), out.status.end(), [](uint32_t v) { return v != 0; });
+            QAMD_TRY(out.finish([&](uint64_t q, uint32_t *ids_dev, float *sc_dev) {
+                return u8_topk_single(h, b->codes.as<uint8_t>() + q * b->pitch, b->offsets.as<float>() + q, k, largest, ids_dev, sc_dev,
+                                      QAMD_MEM_DEVICE, s);
+            }));
+            h->last_compact_batch.store(filtered, std::memory_order_relaxed);  // (behind the redone queries' own launches)
+            h->last_compact_filter.store(filtered, std::memory_order_relaxed);
+            h->last_compact_redone.store(redone, std::memory_order_relaxed);
+            return QAMD_OK;
+        }
+        // (large k, r > 64: today's route, the image passes below)
+    } else if (cmin && Q >= cmin && n > 0) {
+        // Below the filter gate: u8_compact_batch_kernel scores a group of queries into a block of at most 256 MiB, and
+        // each row of the block is ranked in place by the exact select of the classic top-k (as for a full-range store).
+        const uint64_t group = std::max<uint64_t>(1, std::min<uint64_t>(Q, (256ull << 20) / (4 * n)));
+        StreamBuf block;
+        QAMD_TRY(block.alloc(group * n * 4, s));
+        for (uint64_t g = 0; g < Q; g += group) {
+            const uint64_t m = std::min(group, Q - g);
+            QAMD_TRY(u8_compact_batch_scores(h, b->codes.as<uint8_t>() + g * b->pitch, b->pitch, b->offsets.as<float>() + g, (uint32_t)m,
+                                             n, block.as<float>(), n, 0, 0.0f, s));
+            for (uint64_t l = 0; l < m; l++)
+                QAMD_TRY(topk_finish(block.as<float>() + l * n, n, k, largest, out_ids + (g + l) * k, out_scores + (g + l) * k, out_mem, s));
+        }
+        h->last_compact_batch.store((int)Q, std::memory_order_relaxed);
+        return QAMD_OK;
+    }
+    if (u8_batch_by_scans(h) || h->full_range)  // a full-range store its kernel does not take (a small batch; from the gate on, rows past 8256 bytes or an unusable multiplier): the scans' filter passes (no signed form can read it); lane mode 1 (Dot, L2): per-query lane-order scans, never the exact-sum matrix cores; compact below its gate, or with a large k: image scans
         return u8_topk_batch_scans(h, b->codes.as<uint8_t>(), b->pitch, b->offsets.as<float>(), (uint32_t)Q, k, largest,
                                    out_ids, out_scores, out_mem, s);
     // The route of the filter pass over the store: everything below reads it (and the sample pass its own).

@@ -103,9 +103,12 @@ struct qamd_u8 : U8Flags {
     // queries of the last topk_batch call that went through the kernel's filter form (0: the scans, or the score-block
     // route, served it), and how many of those were redone exactly (developer report)
     mutable std::atomic<int> last_full_filter{0}, last_full_redone{0};
+    // The same three for u8_compact_batch_kernel: 0 when the image passes served the call.
+    mutable std::atomic<int> last_compact_batch{0}, last_compact_filter{0}, last_compact_redone{0};
     mutable qamd::DevBuf packed_rows;              // developer report: the image un-blocked, [count][image.chunks]
     // The batched top-k's pivot sample (u8_batch.hip): rows hash(j) of the store, j < sample_rows, then 512
     // zero rows; gathered on first use (count / 64 rows at most: 1.6 % of the store), discarded by an upsert.
+    // A compact store keeps the same rows as a small blocked nibble image of whole blocks (u8_compact_batch.hip).
     mutable std::mutex sample_mu;
     mutable qamd::DevBuf sample_codes, sample_offsets;
     mutable uint32_t sample_rows = 0;
@@ -173,7 +176,7 @@ qamd_status u8_topk_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint
                                 qamd_mem out_mem, hipStream_t stream);
 uint32_t u8_multi_width(const qamd_u8 *h);
 // Lane mode 1 on Dot / L2: batches go query by query.  A compact store: up to 8 queries per pass over its nibble image
-// (u8_scan_image_multi_kernel), never the matrix cores.
+// (u8_scan_image_multi_kernel) below u8_compact_batch_min, u8_compact_batch_kernel from there on.
 bool u8_batch_by_scans(const qamd_u8 *h);
 // Full-range batches on the int8 matrix cores (u8_full_batch.hip): out[q * out_pitch + row] for queries
 // [0, nq) ([q][q_pitch] byte codes, [q] offsets, device memory) against rows [0, n_rows) of the store, in passes of 15
@@ -200,6 +203,32 @@ qamd_status u8_full_batch_filter(const qamd_u8 *h, const U8FullImages &im, const
                                  unsigned long long *candidates, int largest, hipStream_t stream);
 // Smallest batch the full-range matrix-core kernel takes (smaller ones stay on the multi-query scan).
 uint32_t u8_full_batch_min(const qamd_u8 *h);
+// Compact batches on the int8 matrix cores (u8_compact_batch.hip): the same pieces for a compact store, whose
+// rows the kernel reads from the blocked nibble image, in passes of 16, 32 or 64 queries.  `rows` of _scores_of is such
+// an image of whole blocks (the store's, or its pivot sample's) with its offsets.
+struct U8CompactImages {
+    const uint4 *image = nullptr;  // [pass] pass_stride uint4: [step][lo / hi][qt][64]
+    const float *offs = nullptr;   // [pass][64]
+    uint32_t nq = 0, nsteps = 0, passes = 0, qt_full = 0, qt_last = 0;  // tiles of 16 queries per pass, and of the last pass
+    size_t pass_stride = 0;
+};
+size_t u8_compact_images_bytes(const qamd_u8 *h, uint32_t nq);
+qamd_status u8_compact_images_build(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitch, const float *q_offs, uint32_t nq,
+                                    void *scratch, hipStream_t stream, U8CompactImages *out);
+qamd_status u8_compact_batch_scores_of(const qamd_u8 *h, const U8CompactImages &im, const void *rows, const float *v_offsets,
+                                       uint64_t n_rows, float *out, uint64_t out_pitch, int mode, float diff, hipStream_t stream);
+qamd_status u8_compact_batch_scores(const qamd_u8 *h, const uint8_t *qcodes, uint64_t q_pitch, const float *q_offs, uint32_t nq,
+                                    uint64_t n_rows, float *out, uint64_t out_pitch, int mode, float diff, hipStream_t stream);
+qamd_status u8_compact_batch_filter(const qamd_u8 *h, const U8CompactImages &im, const float *pivot_scores, uint32_t *counters,
+                                    unsigned long long *candidates, int largest, hipStream_t stream);
+// The pivot sample as a blocked nibble image (u8_nibble_gather_kernel): its bytes for `rows` sample rows, the gather into
+// scratch of the caller's, and the handle's cached one (sample_mu), which serves every call as a prefix.
+size_t u8_compact_sample_bytes(const qamd_u8 *h, uint32_t rows);
+qamd_status u8_compact_sample_gather(const qamd_u8 *h, uint32_t rows, void *image, float *offsets, hipStream_t stream);
+qamd_status u8_compact_sample_store(const qamd_u8 *h, uint32_t rows_all, hipStream_t s, const void **image, const float **offs);
+// Smallest batch u8_compact_batch_kernel takes from this store; 0: none (not compact, L1, a multiplier that is zero or not
+// finite, or the route switched off).  u8.hip, beside u8_batch_by_scans.
+uint32_t u8_compact_batch_min(const qamd_u8 *h);
 qamd_status u8_score_batch_scans(const qamd_u8 *h, const uint8_t *codes_dev, uint64_t pitch, const float *offsets_dev,
                                  uint32_t n_queries, float *out_dev, hipStream_t stream);
 qamd_status u8_score_single(const qamd_u8 *h, const uint8_t *codes_dev, const float *offset_dev, float *out_dev,
